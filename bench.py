@@ -21,6 +21,12 @@ prints ONE JSON line; `value` is whole-job blocks/s.
 `cpu_baseline` : the reference's own FPGACacheEngine::decompress (oracle/_ref,
                  kind "reference") or our C restatement (kind "port") timed on
                  this host's cores on a bounded sample of the same workload.
+
+A plain run sets up, ramps the clocks, runs the W warm-up and K timed steps and
+prints the line.  `--full` adds everything else: the as-called and sustained
+variants, the parity spot check, the extras, `cpu_baseline` and, at N > 1, the
+remote-pool (`xgmi`) phase.  `--dump-outputs DIR` writes a fixed sample of the
+last timed step's destination (see dump_outputs()).
 """
 import argparse
 import json
@@ -86,6 +92,11 @@ def parse_args():
     ap.add_argument("--ramp-ms", type=float, default=60.0, help="untimed clock ramp before the 'ramped' variant and the extras")
     ap.add_argument("--sustain-s", type=float, default=1.0, help="length of the 'sustained' variant")
     ap.add_argument("--no-variants", action="store_true", help="only the as-called figure (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the as-called and sustained variants, the parity spot check, the extras, "
+                         "the CPU baseline and, at N > 1, the remote-pool phase (a plain run does only what `value` needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed sample of the last step's fp16 destination as DIR/<name>.npy (float32)")
     ap.add_argument("--xgmi-child", action="store_true", help=argparse.SUPPRESS)   # internal: see run_xgmi_children()
     return ap.parse_args()
 
@@ -240,6 +251,26 @@ def whole_job_rate(world, units_per_rank, steps, elapsed):
     return world * units_per_rank * steps / elapsed
 
 
+DUMP_ROWS = 4096                # 4096 blocks x 2048 fp32 = 32 MiB, under the 64 MB a dump may take
+
+
+def dump_rows(n_blocks):
+    """The blocks --dump-outputs writes: a fixed, seeded sample (the same for every run of the same shape), first and last included."""
+    if n_blocks <= DUMP_ROWS:
+        return np.arange(n_blocks)
+    rows = np.random.default_rng(4242).choice(np.arange(1, n_blocks - 1), size=DUMP_ROWS - 2, replace=False)
+    return np.concatenate(([0], np.sort(rows), [n_blocks - 1]))
+
+
+def dump_outputs(out_dir, name, dst, n_blocks):
+    """What a caller of the timed path receives: the fp16 destination of the last timed step, as float32 (exact)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    rows = torch.from_numpy(dump_rows(n_blocks)).to(dst.device)
+    np.save(os.path.join(out_dir, f"{name}.npy"), dst.index_select(0, rows).float().cpu().numpy())
+
+
 def spawn_own_ranks(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves, one per GPU, as a
     CHILD `python -m torch.distributed.run` of this same script with the same arguments, pass its output through (rank 0
@@ -293,10 +324,19 @@ def main():
     import cxl_speckv_amd as pkg
 
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    assert torch.cuda.is_available(), "bench.py needs the MI355X (no CPU fallback for the data path)"
     # test hook (one-GPU boxes): SPECKV_BENCH_SINGLE_GPU_TEST=1 runs every rank on GPU 0
     # with gloo so the N>1 control flow can be exercised without a second GPU
     single_gpu_test = os.environ.get("SPECKV_BENCH_SINGLE_GPU_TEST") == "1"
+    xgmi_wanted = args.full and world > 1 and os.environ.get("SPECKV_BENCH_XGMI", "1") != "0"
+    xgmi_early = single_gpu_test and xgmi_wanted
+    if xgmi_early:
+        # every rank and every remote-pool child on the one GPU: the children run FIRST, before any rank opens the GPU, so
+        # that N ranks and N children never hold it at the same time (at N = 8 that would be 16 processes on one GPU)
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group(backend="gloo")
+        x_early = run_xgmi_children(args, torch, dist, rank, world, "cpu")
+    assert torch.cuda.is_available(), "bench.py needs the MI355X (no CPU fallback for the data path)"
     if single_gpu_test:
         local_rank = 0
     torch.cuda.set_device(local_rank)
@@ -306,7 +346,8 @@ def main():
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if single_gpu_test:
-            dist.init_process_group(backend="gloo")
+            if not dist.is_initialized():
+                dist.init_process_group(backend="gloo")
             red_dev = "cpu"
         else:
             dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
@@ -400,29 +441,36 @@ def main():
     #   ramped     the same W + K after ramp_ms of untimed launches of the same step: the contract's timed region at
     #              steady clocks -- this is `value` (as in round 1, so rounds compare)
     #   sustained  at least sustain_s seconds of back-to-back launches
+    # A plain run measures only the figure that is `value`; the other two are --full.
     state["phase"] = "main"
     torch.cuda.synchronize()
-    e1, k1, s1 = timed_region(args.steps, args.warmup)
-    alg_bytes = alg()
-    variants = {"as_called": dict(figure(e1, k1, args.steps, s1), note="--warmup steps only, straight after pool setup (cold clocks)")}
+    variants = {}
+    if args.full or args.no_variants:
+        e1, k1, s1 = timed_region(args.steps, args.warmup)
+        note = "--warmup steps only, straight after pool setup (cold clocks)"
+        variants["as_called"] = (e1, k1, args.steps, s1), dict(note=note + ("; this is `value` (--no-variants)" if args.no_variants else ""))
     if args.no_variants:
         elapsed, kern_ms = e1, k1
-        variants["as_called"]["note"] += "; this is `value` (--no-variants)"
     else:
         ramp_steps = ramp(step, torch.cuda.synchronize, args.ramp_ms)
         elapsed, kern_ms, s2 = timed_region(args.steps, args.warmup)
-        variants["ramped"] = dict(figure(elapsed, kern_ms, args.steps, s2), untimed_ramp_ms=args.ramp_ms, untimed_ramp_steps=ramp_steps,
-                                  note="same W + K steps after an untimed clock ramp; this is `value`")
-        n_sus = max(args.steps, int(1.03 * args.sustain_s / max(kern_ms * 1e-3, 1e-6)) + 1)    # a little over: steps may run faster than the ramped figure
-        e3, k3, s3 = timed_region(n_sus, 0)
-        variants["sustained"] = dict(figure(e3, k3, n_sus, s3), seconds=round(e3, 3), note=f">= {args.sustain_s} s of back-to-back launches")
+        variants["ramped"] = (elapsed, kern_ms, args.steps, s2), dict(untimed_ramp_ms=args.ramp_ms, untimed_ramp_steps=ramp_steps,
+                                                                     note="same W + K steps after an untimed clock ramp; this is `value`")
+        if args.full:
+            n_sus = max(args.steps, int(1.03 * args.sustain_s / max(kern_ms * 1e-3, 1e-6)) + 1)    # a little over: steps may run faster than the ramped figure
+            e3, k3, s3 = timed_region(n_sus, 0)
+            variants["sustained"] = (e3, k3, n_sus, s3), dict(seconds=round(e3, 3), note=f">= {args.sustain_s} s of back-to-back launches")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "fetch_decompress_fp16" + (f"_rank{rank}" if world > 1 else ""), dst, n_blocks)
+    alg_bytes = alg()
+    variants = {k: dict(figure(*fig), **extra) for k, (fig, extra) in variants.items()}
 
     # parity spot check without any checker code in the loop: the reference's own vectors (tests/golden/
     # codec_vectors.npz: inputs, RLE bytes, scale bits and fp32 outputs recorded from the reference) go through
     # the same engine entry points the timed step uses, plus the size-independent properties of the timed data
     # (every record length positive, logical ids as the reference computes them).
     parity = None
-    if rank == 0 and args.scheme == 2 and args.quant == 0:
+    if args.full and rank == 0 and args.scheme == 2 and args.quant == 0:
         gold = np.load(os.path.join(ROOT, "tests", "golden", "codec_vectors.npz"))
         names = [k[:-2] for k in gold.files if k.endswith(".x") and gold[k].size == BLOCK_ELEMS]
         x16 = np.stack([gold[f"{nm}.x"] for nm in names]).astype(np.float16)
@@ -481,24 +529,25 @@ def main():
                 "traffic_source": traffic_src,
                 "algorithmic_bytes_per_launch": int(alg_bytes),
                 "avg_launch_ms": round(kern_ms, 4),
-                "frac_as_called": variants["as_called"]["frac_hbm"],
-                "avg_launch_ms_as_called": variants["as_called"]["avg_launch_ms"],
+                **({"frac_as_called": variants["as_called"]["frac_hbm"],
+                    "avg_launch_ms_as_called": variants["as_called"]["avg_launch_ms"]} if "as_called" in variants else {}),
                 "launches": {"kernel_instance": f"k_fetch_decompress<{args.scheme}, {args.quant}, false, 0>",
                              **{k: v["launches"] for k, v in variants.items()},
                              "note": "0-based indices of this instance's dispatches in this process, in dispatch order: "
                                      "profiles/summarize_r04.py averages the same dispatches in the rocprofv3 kernel trace"},
                 "bytes_per_block": round(alg_bytes / n_blocks, 1),
                 "timed_region": "W warm-up steps then exactly K steps, preceded by an untimed clock ramp (variants.ramped); "
-                                "the cold as-called figure and a >= 1 s sustained one are in `variants`",
+                                "the cold as-called figure and a >= 1 s sustained one are in `variants` with --full",
             },
             "variants": variants,
-            "parity_spot_check": parity,
             "compress_s_untimed": round(compress_s, 4),
-            "extras": {},
         }
+        if args.full:
+            state["out"].update(parity_spot_check=parity, extras={})
     out = state["out"]
+    extras_wanted = args.full and not args.no_extras
 
-    if rank == 0 and world == 1 and not args.no_extras:      # secondary measurements: single-GPU runs only
+    if rank == 0 and world == 1 and extras_wanted:           # secondary measurements: single-GPU runs only
         state["phase"] = "extras"
         with torch.cuda.stream(stream):
             extras = run_extras(torch, pkg, lib, src, dst, n_blocks, sp)
@@ -506,16 +555,16 @@ def main():
         out["extras"] = extras
 
     kv.close()
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras_wanted:
         state["phase"] = "extras:flush_cfg4"
         out["extras"].update(flush_cfg4_extra(torch, pkg))
         state["phase"] = "extras:striped_attention"
         out["extras"].update(striped_attention_extra(torch, pkg))
-    if world > 1 and os.environ.get("SPECKV_BENCH_XGMI", "1") != "0":
+    if xgmi_wanted:
         state["phase"] = "xgmi"
         del src, dst
         torch.cuda.empty_cache()
-        x = run_xgmi_children(args, torch, dist, rank, world, red_dev)
+        x = x_early if xgmi_early else run_xgmi_children(args, torch, dist, rank, world, red_dev)   # rank 0 alone gets the object
         if rank == 0 and out is not None:
             out["xgmi"] = x
             rx = roofline_xgmi_from(x, world)
@@ -536,13 +585,13 @@ def main():
                 out["value_note"] = ("`value` = blocks/s of the local fetch+decompress path summed over ranks (replicas, no exchange: linear by "
                                      "construction); value_remote_fetch_* = 1 compute GPU fetching from its N-1 pool GPUs over xGMI "
                                      f"({rx['layout']}, {rx['engine']}); roofline.xgmi.frac is that figure over links x 153.6 GB/s")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # rank 0 at N=1 only (bench contract)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:   # rank 0 at N=1 only (bench contract)
         state["phase"] = "cpu_baseline"
         try:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         except Exception as e:                                  # the checker must never cost the result
             out["cpu_baseline"] = {"error": repr(e)}
-    elif rank == 0 and world > 1:
+    elif rank == 0 and world > 1 and args.full:
         out["cpu_baseline"] = None                              # measured by the N=1 run
     dog.cancel()
     emit()

@@ -8,8 +8,8 @@ OUT=$R/gpurun_out/${1:-prof_r02}
 rm -rf $OUT
 mkdir -p $OUT
 # 1. the bench as the driver calls it (as-called figure only: W warm-ups + K steps) and the full default bench
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_ascalled -- python3 $R/bench.py --steps 20 --warmup 5 --no-variants --no-extras --no-cpu-baseline > $OUT/bench_ascalled.json 2> $OUT/trace_ascalled.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_full -- python3 $R/bench.py --no-cpu-baseline > $OUT/bench_full.json 2> $OUT/trace_full.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_ascalled -- python3 $R/bench.py --steps 20 --warmup 5 --no-variants --no-extras --no-cpu-baseline --full > $OUT/bench_ascalled.json 2> $OUT/trace_ascalled.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_full -- python3 $R/bench.py --no-cpu-baseline --full > $OUT/bench_full.json 2> $OUT/trace_full.log
 # 2. PMC on the dominant kernel at three footprints (FETCH_SIZE and WRITE_SIZE need separate passes; hit/miss a third)
 for cfg in "4096 32" "16384 32" "8192 80"; do
   tag=$(echo $cfg | tr ' ' x)

@@ -36,7 +36,7 @@ def dispatches(trace_dir, instance):
 
 
 def main(out_dir):
-    res = {"command": "python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline"}
+    res = {"command": "python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline --full"}
     traced = last_json_line(os.path.join(out_dir, "bench_driver_cmd_traced.json"))
     plain = last_json_line(os.path.join(out_dir, "bench_driver_cmd_unprofiled.json"))
     if plain:

@@ -3,7 +3,7 @@ form: 1 compute GPU + pool GPUs; the reference's path i
 `sync_fetch_page`, one DMA descriptor per page from the pool into the compute GPU).
 
 The development pool has one GPU per box, so `SPECKV_BENCH_SINGLE_GPU_TEST=1` puts every rank and every "peer" on GPU 0
-with gloo between the ranks: `python bench.py --gpus N` starts its own ranks (torch.distributed.run as a child), every rank
+with gloo between the ranks: `python bench.py --gpus N --full` starts its own ranks (torch.distributed.run as a child), every rank
 starts the remote-fetch child process, the striping (page % (N-1)), both fetch engines, the speculative-prefetch leg and the
 accounting are the real code.  No link is crossed and the line says so itself; these tests check that the line is complete,
 that the two fetch engines delivered the same bytes, and that nothing failed, hung or was skipped.
@@ -27,7 +27,7 @@ def run_bench(n, steps=3, warmup=1, timeout=240):
         env.pop(k, None)
     t0 = time.time()
     # a FRESH child process: it starts its ranks itself, before anything in it touches the GPU
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup)],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup), "--full"],
                        env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     took = time.time() - t0
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])

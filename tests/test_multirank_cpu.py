@@ -324,3 +324,25 @@ def test_host_cpu_info_reads_model_and_physical_cores():
     import bench
     model, physical, logical = bench.host_cpu_info()
     assert isinstance(model, str) and model and logical >= 1 and (physical is None or 1 <= physical <= logical)
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded():
+    """--dump-outputs writes the same blocks on every run of a shape (two builds compare output for output), first and last
+    included, within the 64 MB a dump may take as float32; a plain run keeps the headline alone, --full is off by default."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    for n in (5, bench.DUMP_ROWS, 131072):
+        rows = bench.dump_rows(n)
+        assert np.array_equal(rows, bench.dump_rows(n)) and rows[0] == 0 and rows[-1] == n - 1
+        assert np.all(np.diff(rows) > 0) and len(rows) == min(n, bench.DUMP_ROWS)
+        assert len(rows) * bench.BLOCK_ELEMS * 4 <= 64 * 1000 * 1000
+    saved = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse_args()
+        sys.argv += ["--full", "--dump-outputs", "out"]
+        b = bench.parse_args()
+    finally:
+        sys.argv = saved
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None) and (b.full, b.dump_outputs) == (True, "out")
