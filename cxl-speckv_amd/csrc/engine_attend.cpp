@@ -622,7 +622,13 @@ int Engine::attend_batch_plan(uint32_t n_seq, const uint64_t* handles, const uin
     // (a first plan whose members differ in length and have pieces -- by whichever rule -- takes the rows-first grid, as the batch entry does)
     if (!plan_sticky && by_length && g.max_splits > 1u) plan_rows_first = true;
     if (!plan_sticky) {
-        if (plan_rooms_.size() >= 4096) plan_rooms_.clear();   // (graphs captured over plans older than this must be captured anew: not a working set anyone has)
+        // (a graph captured over a buffer replays the room of its shape without calling in: a room is dropped only once its buffer has left plans_ --
+        //  rooms of live buffers are kept however many shapes pass through them)
+        if (plan_rooms_.size() >= 4096)
+            for (auto it = plan_rooms_.begin(); it != plan_rooms_.end();) {
+                const void* buf = reinterpret_cast<const void*>(static_cast<uintptr_t>((*it).first[0]));
+                it = buf != d_plan && !plans_.count(buf) ? plan_rooms_.erase(it) : std::next(it);
+            }
         plan_rooms_[{reinterpret_cast<uintptr_t>(d_plan), n_seq | (static_cast<uint64_t>(scheme) << 32), max_pos_end | (static_cast<uint64_t>(rule_tps) << 32), rule_splits}] = {g.max_splits, plan_rows_first};
     }
     plans_[d_plan] = PlanInfo{n_seq, scheme, min_layers, max_pos_end, any_striped, any_table, stripe_n_max, any_empty, ordered, g.max_splits, plan_rows_first, rule_tps, rule_splits};
@@ -744,7 +750,7 @@ int Engine::attend_planned(int scheme, const void* d_plan, uint32_t n_seq, uint3
     // empty member (an empty sequence has no split to fold into) and the tail index by sequence; otherwise, and for the other
     // formats, one k_attend_fold_tail launch behind the attention, as the connector used to issue itself.
     const bool have_tail = tail && tail->n_tail != 0u;
-    if (have_tail && (!tail->d_k_tail || !tail->d_v_tail || !d_lse || tail->stride_elems % 8u || tail->stride_elems < static_cast<uint64_t>(layer + 1u) * heads * 128u))
+    if (have_tail && (!tail->d_k_tail || !tail->d_v_tail || !d_lse || tail->stride_elems % 8u || tail->stride_elems < static_cast<uint64_t>(layer + n_layers) * heads * 128u))
         return SPECKV_ERR_INVAL;
     const bool fold_in_kernel = have_tail && mx4 && !plan->second.any_empty && !plan->second.table && (tail->d_tail_idx || tail->n_tail == n_seq) && tuning().attend_fold_launch == 0;
     if (n_layers > 1u) {                                       // (attend_planned_layers checked the geometry: MXFP4, one split per sequence)

@@ -396,7 +396,9 @@ speckv_status_t speckv_ext_attend_mx4_planned(const void* d_plan, uint32_t n_seq
  *       for as long as every pos_end stays <= max_pos_end: grid and scratch are functions of (n_seq, max_pos_end) and of
  *       what the FIRST plan of that shape written into that buffer saw (a batch whose members differ much in length gets
  *       room for pieces per member and a merge launch; every later plan of the shape in the buffer keeps that room, so the
- *       captured launches stay valid); the lengths and piece lengths themselves are read from the plan on the device.
+ *       captured launches stay valid, however many other shapes are planned meanwhile -- the room of a shape is dropped only
+ *       once its buffer is no longer one of the engine's plan buffers: more than 64 buffers in use at once drop them all);
+ *       the lengths and piece lengths themselves are read from the plan on the device.
  *       Capture AFTER the first plan of a shape, as before.
  * Arguments as for the batch calls; max_pos_end (even) must be the value given to the plan.  `stream` must not be NULL.
  * Run each shape once outside the capture first (scratch growth during a capture is refused with SPECKV_ERR_INVAL).
@@ -432,7 +434,8 @@ speckv_status_t speckv_ext_attend_planned_tail(int scheme, const void* d_plan, u
  * layers, a benchmark, layers whose attention inputs do not depend on each other): d_q_f16 [n_layers][n_seq][heads][g][128], d_out and
  * d_lse likewise; the tail arguments as speckv_ext_attend_planned_tail (n_tail == 0: none).  MXFP4 with a launch geometry of one split
  * per sequence (a batch that fills the chip by itself): ONE launch over layers x sequences -- the next layer's workgroups start while
- * the last of this one drain; everything else: the per-layer launches, issued from this one call.  Results equal the per-layer calls. */
+ * the last of this one drain; everything else: the per-layer launches, issued from this one call.  Results equal the per-layer calls.
+ * A tail stride shorter than (layer_begin + n_layers) * heads * 128 is refused with SPECKV_ERR_INVAL before anything is launched. */
 speckv_status_t speckv_ext_attend_planned_layers(int scheme, const void* d_plan, uint32_t n_seq, uint32_t layer_begin, uint32_t n_layers,
                                                  const void* d_q_f16, uint32_t g, uint32_t max_pos_end, float sm_scale, float* d_out,
                                                  float* d_lse, uint32_t n_tail, const uint32_t* d_tail_rows, const int32_t* d_tail_idx,

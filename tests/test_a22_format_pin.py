@@ -386,3 +386,42 @@ def test_mxfp8_query_rows_and_the_mx4_attention_oracle_against_numpy(oracle):
                          _ptr(o, f32p), _ptr(l, f32p), _ptr(m, f32p))
         wo, wl, wm = attention_numpy(qd, kdec[:npos], vdec[:npos], np.float32(sm))
         assert np.allclose(o, wo, rtol=2e-6, atol=1e-7) and np.allclose(l, wl, rtol=2e-6, atol=2e-6) and np.allclose(m, wm, rtol=2e-6, atol=1e-7)
+
+
+@pytest.mark.parametrize("scheme", [3, 4, 5])
+def test_batched_head_checker_rows_equal_the_oracle_attention(oracle, scheme):
+    """tests/_gpu.py HeadChecker.want_rows (the float64 attention of many members' query rows at once, in numpy, that the batch geometry
+    tests check every row with) against HeadChecker.want, which runs the oracle's own attention (orc_attend_f16 / _fp8 / _mx4) one
+    head at a time: out, lse, sum p|v| and the score bound agree for members of different lengths -- none, two positions, a ragged
+    tile, the whole region -- and an empty member is 0 with lse -inf."""
+    from tests._gpu import D, HeadChecker
+    rng = np.random.default_rng(4100 + scheme)
+    T, G = 256, 4
+    pages = (rng.standard_normal((T, 2048)) * rng.uniform(0.2, 3.0, (T, 1))).astype(np.float16)
+    hc = HeadChecker(oracle, scheme, pages, T)
+    npos = np.array([T, 0, 2, 34, 130, T, 34, 200])
+    q = (rng.standard_normal((len(npos), G, D)) * 1.5).astype(np.float16)
+    sm = 1.0 / np.sqrt(D)
+    for head in (0, 5):
+        out, lse, mag, delta = hc.want_rows(q, head, npos, sm)
+        for i, n in enumerate(npos):
+            o, l, m, dl = hc.want(q[i], head, int(n), sm)
+            assert np.allclose(out[i], o, rtol=2e-6, atol=1e-6) and np.allclose(mag[i], m, rtol=2e-6, atol=1e-6), (scheme, head, i)
+            assert np.allclose(lse[i], l, rtol=0, atol=2e-6) if n else np.all(np.isneginf(lse[i])), (scheme, head, i)
+            assert delta[i] == pytest.approx(dl, rel=1e-4, abs=1e-12), (scheme, head, i)
+        assert np.all(out[1] == 0.0)
+        hc.check_rows(out.astype(np.float32), lse.astype(np.float32), q, head, npos, sm, ("self", scheme, head))
+        bad = out.astype(np.float32).copy(); bad[4, 2, 7] += (4e-3 + 4 * delta[4]) * mag[4, 2, 7] + 1e-5     # one value of one row off by twice the bound: caught
+        with pytest.raises(AssertionError):
+            hc.check_rows(bad, lse, q, head, npos, sm, ("perturbed", scheme, head))
+    # one more position per member outside the pool (the folded tail): the same as attention over the region with that row appended
+    kt = rng.standard_normal((len(npos), D)).astype(np.float16); vt = rng.standard_normal((len(npos), D)).astype(np.float16)
+    out, lse, mag, _ = hc.want_rows(q, 3, npos, sm, tail=(kt, vt))
+    K, V = hc.kv(3)
+    qe = hc.q_rows(q).reshape(len(npos), G, D)
+    for i, n in enumerate(npos):
+        s = np.concatenate([qe[i] @ K[:n].T, q[i].astype(np.float64) @ kt[i].astype(np.float64)[:, None]], axis=1) * sm
+        p = np.exp(s - s.max(axis=1, keepdims=True))
+        vv = np.concatenate([V[:n], vt[i].astype(np.float64)[None]])
+        assert np.allclose(out[i], p @ vv / p.sum(axis=1, keepdims=True), rtol=1e-9, atol=1e-12)
+        assert np.allclose(lse[i], s.max(axis=1) + np.log(p.sum(axis=1)), rtol=0, atol=1e-9)

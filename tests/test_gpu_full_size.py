@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import cxl_speckv_amd as pkg
-from tests._gpu import N, assert_same_float_bits, torch_mod, set_tuning
+from tests._gpu import N, HeadChecker, assert_same_float_bits, torch_mod, set_tuning
 
 pytestmark = pytest.mark.gpu
 PAGE = 4096
@@ -37,68 +37,6 @@ def synth_pages(torch, seed, n_pages):
     x = torch.randn((n_pages, N), generator=g, device="cuda", dtype=torch.float32)
     mag = torch.rand((n_pages, 1), generator=g, device="cuda", dtype=torch.float32) * 2.8 + 0.2
     return (x * mag).to(torch.float16)
-
-
-class HeadChecker:
-    """The oracle's attention of one kv head over the K / V regions of one layer, from the HOST copy of that layer's
-    pages (region = T/2 pages of K followed by T/2 pages of V), through the oracle's own compress -> records."""
-
-    def __init__(self, oracle, scheme, region_pages16, T):
-        self.oracle, self.scheme, self.T = oracle, scheme, T
-        self.scales, self.lens, self.recs = oracle.compress_blocks_f16(region_pages16, scheme, 0)
-        if scheme == 3:
-            self.dec = oracle.decompress_blocks_f16(self.recs, self.lens, self.scales, 3, 0).reshape(-1, 2, H, D)
-        elif scheme == 5:
-            self.lut = np.array([oracle.lib.orc_e4m3_to_f32(b) for b in range(256)], np.float64)
-            self.lut[np.isnan(self.lut)] = 0.0
-        else:
-            self.lut = np.array([oracle.lib.orc_e4m3_to_f32(b) for b in range(256)], np.float32)
-            self.lut[np.isnan(self.lut)] = 0.0
-
-    def want(self, q_head, head, npos, sm):
-        """q_head [G][D] fp16 -> out [G][D], lse [G], mag [G][D], delta (FP8: score error bound of the fp8 MFMA)."""
-        from oracle.bindings import _ptr, u8p, u16p, f32p
-        L = self.oracle.lib
-        hp = self.T // 2                                               # pages per K / V region
-        o = np.zeros((G, D), np.float32); l = np.zeros(G, np.float32); m = np.zeros((G, D), np.float32)
-        if npos == 0:
-            return o, np.full(G, -np.inf, np.float32), m, 0.0
-        if self.scheme == 3:
-            k16 = np.ascontiguousarray(self.dec[:hp, :, head, :].reshape(-1, D)[:npos]).view(np.uint16)
-            v16 = np.ascontiguousarray(self.dec[hp:2 * hp, :, head, :].reshape(-1, D)[:npos]).view(np.uint16)
-            L.orc_attend_f16(_ptr(np.ascontiguousarray(q_head).view(np.uint16).reshape(-1), u16p), G, _ptr(k16.reshape(-1), u16p),
-                             _ptr(v16.reshape(-1), u16p), npos, D, float(sm), _ptr(o, f32p), _ptr(l, f32p), _ptr(m, f32p))
-            return o, l, m, 0.0
-        if self.scheme == 5:                                         # MXFP4: page rows of one head + their codes (tests/test_gpu_mx4.py)
-            from tests.test_gpu_mx4 import head_rows, dequant_rows
-            kr, kc = head_rows(self.recs, 0, npos, head)
-            vr, vc = head_rows(self.recs, hp, npos, head)
-            q8 = np.zeros((G, D), np.uint8); qc = np.zeros((G, D // 16), np.uint8)
-            L.orc_quantize_rows_mxfp8(_ptr(np.ascontiguousarray(q_head).view(np.uint16).reshape(-1), u16p), G, D, 16, _ptr(q8, u8p), _ptr(qc, u8p))
-            qd = self.lut[q8] * np.repeat(np.exp2(qc.astype(np.float64) - 127.0), 16, axis=1)
-            delta = 3e-5 * float((np.abs(qd) @ np.abs(dequant_rows(kr, kc, npos)).T).max()) * sm
-            L.orc_attend_mx4(_ptr(q8, u8p), _ptr(qc, u8p), 16, G, _ptr(kr, u8p), _ptr(kc, u8p), _ptr(vr, u8p), _ptr(vc, u8p), npos, D,
-                             float(sm), _ptr(o, f32p), _ptr(l, f32p), _ptr(m, f32p))
-            return o, l, m, delta
-        r4 = self.recs[:, :N].reshape(-1, 2, H, D)
-        krows = np.ascontiguousarray(r4[:hp, :, head, :].reshape(-1, D)[:npos])
-        vrows = np.ascontiguousarray(r4[hp:2 * hp, :, head, :].reshape(-1, D)[:npos])
-        ksc = np.ascontiguousarray(np.repeat(self.scales[:hp], 2)[:npos]); vsc = np.ascontiguousarray(np.repeat(self.scales[hp:2 * hp], 2)[:npos])
-        q8 = np.zeros((G, D), np.uint8); qs = np.zeros(G, np.float32)
-        L.orc_quantize_rows_e4m3(_ptr(np.ascontiguousarray(q_head).view(np.uint16).reshape(-1), u16p), G, D, _ptr(q8, u8p), _ptr(qs, f32p))
-        smag = (np.abs(self.lut[q8]) @ np.abs(self.lut[krows]).T) * ksc[None, :] * qs[:, None] * sm
-        delta = 3e-5 * float(smag.max())
-        L.orc_attend_fp8(_ptr(q8, u8p), _ptr(qs, f32p), G, _ptr(krows, u8p), _ptr(ksc, f32p), _ptr(vrows, u8p), _ptr(vsc, f32p),
-                         npos, D, float(sm), _ptr(o, f32p), _ptr(l, f32p), _ptr(m, f32p))
-        return o, l, m, delta
-
-    def check(self, got, got_lse, q_head, head, npos, sm, what):
-        want, wlse, mag, delta = self.want(q_head, head, npos, sm)
-        err = np.abs(np.asarray(got, np.float32) - want)
-        tol = (2e-3 + 2 * delta) * mag + 1e-6
-        assert np.all(err <= tol), (what, float((err / (mag + 1e-9)).max()), delta)
-        if got_lse is not None and npos:
-            assert np.all(np.abs(np.asarray(got_lse, np.float32) - wlse) <= 2e-3 + delta), (what, float(np.abs(got_lse - wlse).max()))
 
 
 def sample_seed():

@@ -262,7 +262,7 @@ def rules():
     lib.rules_even_split.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.rules_int4_unequal.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.rules_fp8_batch_tiles_per_split.restype = C.c_uint32
-    lib.rules_fp8_batch_tiles_per_split.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.rules_fp8_batch_tiles_per_split.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.rules_balanced_tiles_per_piece.restype = C.c_uint32
     lib.rules_balanced_tiles_per_piece.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
     return lib
@@ -341,7 +341,7 @@ def test_fp8_batch_split_rule(rules):
     whole, a split launch stays within one residency (1024 workgroups) and is cheaper than whole sequences by the rule's
     own busiest-CU cost, and the rule
     for a uniform batch is the same whether the tiles come as a list or as a bound."""
-    f = rules.rules_fp8_batch_tiles_per_split
+    f = lambda tiles, n_seq, uniform_tiles, cols, n_cus=256: rules.rules_fp8_batch_tiles_per_split(tiles, n_seq, uniform_tiles, cols, n_cus)
     hq = 2                                                        # 8 kv heads: two workgroup columns per sequence
 
     def uniform(n_seq, tiles):
@@ -390,6 +390,11 @@ def test_fp8_batch_split_rule(rules):
         assert tps >= 1 and (t.max() == 0 or tps <= max(int(t.max()), 8))
         assert int(np.max(-(-t.astype(np.int64) // tps))) <= 2048
     assert f(None, 0, 100, hq) == 8 and f(None, 10, 0, hq) == 8  # nothing to do: any legal length
+    # the machine's size is an argument: a batch of more columns than CUs takes the balanced pieces, the same batch on a machine
+    # twice that size is priced by the split rule; 256 CUs is the engine's value
+    assert f(None, 200, 128, hq, 256) == uniform(200, 128)
+    assert f(None, 130, 128, hq, 256) < 128 and f(None, 130, 128, hq, 256) == rules.rules_balanced_tiles_per_piece(None, 130, 128, hq, 256, 1)
+    assert f(None, 130, 128, hq, 512) != f(None, 130, 128, hq, 256) and f(None, 100, 128, hq, 128) == rules.rules_balanced_tiles_per_piece(None, 100, 128, hq, 128, 1)
 
 
 def test_balanced_pieces_rule_for_batches_over_the_cu_count(rules):
