@@ -1,0 +1,237 @@
+// cxl-speckv_amd/csrc/attend_geometry.hpp -- the launch decision of the batched fused attention as pure host functions: which kernel form runs
+// (batch_form), the split length and the room for pieces (batch_geometry), the pieces of every member (assign_pieces) and the dispatch order
+// (batch_dispatch_order).  Engine::attend_batch, attend_batch_plan and attend_planned (engine_attend.cpp) decide with these and with nothing else,
+// so the three agree by construction; the CPU tests call the same functions (tests/csrc/host_rules_test.cpp) and replay a recorded table of
+// decisions through them (tests/golden/attend_geometry.json).  Plain C++17, no HIP: the tuning keys the rules read come in as values.
+#pragma once
+#include "ring_rule.hpp"
+
+#include <vector>
+
+namespace speckv {
+
+// the tuning keys (tuning.hpp) these rules read: attend_tiles_per_split, attend_order_as_given, attend_fp8_table_regs,
+// attend_fp8_striped_table, attend_int4_striped_wg
+struct BatchTuning { int32_t tiles_per_split, order_as_given, fp8_table_regs, fp8_striped_table, int4_striped_wg; };
+// a batch: the format (neither fp8 nor mx4: INT4_G32), members, kv heads, the CUs of the engine's device, and what the members' placement
+// allows: any_striped = a member whose records are not in one run (then the whole launch takes the striped kernels: a single run is
+// "striped over 1"), any_table = a member without a regular placement (migrated pages: the launch reads addresses from the page tables)
+struct BatchShape { bool fp8, mx4; uint32_t n_seq, heads, cus; bool any_striped, any_table; };
+enum BatchEntry : uint32_t { kEntryBatch = 0, kEntryPlan = 1 };
+
+// ---- the form ---------------------------------------------------------------------------------------------------------------
+// table / striped: AttendArgs::table_form / stripe_bases; fp8_cls: AttendArgs::fp8_cls; by_class: the members' tiles are counted by residue
+// class (kernels.hpp mx4_striped_tiles); wg8: AttendArgs::wg8 (0: not the whole-record INT4 kernel, 1: its 16-wave form, 2: one-run workgroups);
+// order_round: sequences per round of the CUs for the kernel a batch of this format runs on (0: longest first), see batch_dispatch_order
+struct BatchForm { bool table, striped, fp8_cls, int4_cls, by_class; uint32_t wg8, order_round; };
+
+// INT4 batches on the whole-record kernel (k_attend_int4_wg8<2>: workgroups = sequences x splits, one 16-wave workgroup per
+// CU resident, its two halves merged in LDS): one round of resident workgroups when the batch is smaller than that, whole
+// sequences otherwise (a whole sequence is final: no partials, no merge launch); never under 8 tiles a split.
+// More sequences than CUs: workgroups of one run (8 waves, two resident per CU) -- a finishing workgroup's successor starts
+// under its neighbour's stream, where a second round of 16-wave workgroups would wait for the whole CU (512 x 1k 0.52 -> 0.54,
+// 1024 x 1k 0.56 -> 0.595: profiles/r04_batch_short.txt); AttendArgs::wg8 = 2.
+inline uint32_t int4_wg8_form(uint32_t n_seq, uint32_t cus) { return n_seq > cus ? 2u : 1u; }
+
+inline BatchForm batch_form(const BatchShape& s, const BatchTuning& t)
+{
+    const bool int4 = !s.fp8 && !s.mx4;
+    BatchForm f{};
+    // FP8 over striped pools, every member placed regularly: the register-staged kernel by residue classes (k_attend_fp8_linear<.., CLS>);
+    // on request (tests, A/B) the DMA pipeline with its addresses from the page tables (k_attend_fp8_dma<1>), in page order
+    // (measured: batches of 256 x 8k over 7 runs 0.70-0.71 by residue classes against 0.71-0.73 through the page tables -- the table form
+    //  stays the default for batches; attend_fp8_striped_table = -1 takes the class form: tests, A/B)
+    f.fp8_cls = s.fp8 && s.any_striped && !s.any_table && t.fp8_table_regs == 0 && t.fp8_striped_table < 0;
+    f.table = s.any_table || (s.fp8 && s.any_striped && t.fp8_table_regs == 0 && !f.fp8_cls);       // (AttendSeq::lin_base carries the page table in table launches)
+    f.striped = s.any_striped && !f.table;
+    // INT4_G32, 8 kv heads, every member placed regularly (one run = "striped over 1"): the whole-record kernel by residue classes
+    f.int4_cls = int4 && f.striped && s.heads == 8u && t.int4_striped_wg == 0;
+    // the striped forms of k_attend_mx4 / k_attend_int4_wg8 / k_attend_fp8_linear count their tiles by residue class
+    f.by_class = (s.mx4 || f.int4_cls || f.fp8_cls) && f.striped;
+    if (int4 && (!s.any_striped || f.int4_cls) && !f.table && s.heads == 8u) f.wg8 = int4_wg8_form(s.n_seq, s.cus);
+    if (s.mx4) f.order_round = 0u;
+    else if (int4 && s.heads == 8u) f.order_round = s.cus;                               // whole-record kernel (one column per sequence)
+    else f.order_round = std::max(1u, s.cus / std::max(1u, s.heads / 4u));
+    return f;
+}
+
+// Sequences of different lengths (round 6, profiles/r06_ragged_batches.txt): the order their workgroups are dispatched in decides how evenly the
+// CUs are loaded -- a CU receives workgroups i, i + CUs, i + 2 CUs, ... of the launch.  Kernels that keep several workgroups resident per
+// CU (FP8: 4; INT4 on one-run workgroups: 2) get the sequences sorted by length and laid out as a serpentine over rounds of `round`
+// sequences (one round = the sequences whose workgroups cover the CUs once): a CU then holds a long one with a short one -- 256 sequences
+// of 1k .. 16k, FP8: 0.54 of the HBM roofline as given, 0.63 sorted, 0.78 as a serpentine; 512: 0.535 -> 0.79, INT4 0.48 -> 0.67.
+// round = 0 (MXFP4, one workgroup per CU): longest first, the short ones fill the tail (512 sequences 0.62 -> 0.84).
+// Returns false (order as given, nothing written) when the lengths do not differ by more than a tile in eight.  pages[i] = pages of member i.
+inline bool batch_dispatch_order(const BatchForm& f, const BatchTuning& t, const uint32_t* pages, uint32_t n_seq, uint32_t* order)
+{
+    return t.order_as_given == 0 && dispatch_order_by_length(pages, n_seq, f.order_round, order);           // ring_rule.hpp
+}
+
+// ---- the rules for members of equal length ---------------------------------------------------------------------------------------
+// INT4 batch launches between half a machine and a whole one of workgroup columns: every long sequence in a long and a short
+// piece, dispatched rows-first (ring_rule.hpp: int4_unequal_fraction / unequal_pieces).  The environment switches are for
+// measurement runs.
+using UnequalSplit = UnequalFraction;
+inline UnequalSplit int4_unequal_split(uint32_t n_seq, uint32_t hq, uint32_t tiles_max, const BatchTuning& t)
+{
+    if (t.tiles_per_split > 0) return {false, 1.0};          // (a forced split length: plain even splits)
+    return int4_unequal_fraction(n_seq * hq, tiles_max);
+}
+
+// Split length of a batch launch on the 4-head kernels (see the measurements quoted at batch_geometry).  tiles[i] = the tile count of
+// sequence i (null: n_seq sequences of uniform_tiles each, the bound a plan is sized for).
+inline uint32_t batch_tiles_per_split(bool fp8, uint32_t n_seq, uint32_t heads, const uint32_t* tiles, uint32_t uniform_tiles, const BatchTuning& t)
+{
+    if (t.tiles_per_split > 0) return static_cast<uint32_t>(t.tiles_per_split);
+    const uint32_t hq = heads / 4u;
+    // FP8: the busiest-CU cost rule of ring_rule.hpp (48 sequences x 16k: 288 workgroups 0.50 of HBM peak, 192: 0.64,
+    // 768: 0.71; 32 x 32k: 256 workgroups 0.79, 512: 0.76, 384: 0.63; 128 x 2k: unsplit 0.73, two splits 0.56)
+    if (fp8) return fp8_batch_tiles_per_split(tiles, n_seq, uniform_tiles, hq, 256u, 8u);
+    uint64_t total_tiles = tiles ? 0u : static_cast<uint64_t>(uniform_tiles) * n_seq;
+    if (tiles) for (uint32_t i = 0; i < n_seq; ++i) total_tiles += tiles[i];
+    const uint64_t wg_target = 768u;
+    uint32_t tps = static_cast<uint32_t>(std::max<uint64_t>(8, (total_tiles * hq + wg_target - 1u) / wg_target));
+    tps = (static_cast<uint64_t>(n_seq) * hq >= 384u) ? 256u : std::min(tps, 256u);   // enough columns: whole sequences
+    return tps;
+}
+
+// INT4 on the whole-record kernel (the forms: int4_wg8_form above)
+inline uint32_t int4_wg8_batch_tps(uint32_t n_seq, uint32_t tiles_max, uint32_t cus, const BatchTuning& t)
+{
+    if (t.tiles_per_split > 0) return static_cast<uint32_t>(t.tiles_per_split);      // (tests, measurement runs)
+    const uint32_t resident = cus;                                        // 16-wave workgroups (two halves each), one per CU
+    const uint32_t splits = std::max(1u, resident / std::max(1u, n_seq));
+    // more sequences than CUs: the pieces that balance the last round (ring_rule.hpp balanced_tiles_per_piece; 260 x 8k 0.45 -> 0.61
+    // of the HBM roofline, 300 0.52 -> 0.67, 340 0.58 -> 0.70, 384 0.63 -> 0.71)
+    if (n_seq > resident && tiles_max >= 64u) return balanced_tiles_per_piece(nullptr, n_seq, tiles_max, 1u, resident, kPiecesInt4Wg8);
+    // between half a machine and a whole one (the 16-wave form): 130 x 8k 0.43 -> 0.57, 160 0.53 -> 0.64, 200 and up stay whole
+    if (2u * n_seq > resident && tiles_max >= 64u) return balanced_tiles_per_piece(nullptr, n_seq, tiles_max, 1u, resident, kPiecesInt4Halves);
+    // (the floor was 32 tiles until round 6: with few sequences that left most of the machine idle -- 8 x 8k: 64 workgroups 0.16 of the HBM
+    //  roofline, 256 workgroups of 8 tiles 0.34; 16 x 8k 0.32 -> 0.49; 4 x 8k 0.08 -> 0.21)
+    return std::max(8u, (tiles_max + splits - 1u) / splits);
+}
+
+// MXFP4 batches (k_attend_mx4: one workgroup of 4 waves = the 8 kv heads per (sequence, split), three tiles deep in LDS: ONE
+// workgroup resident per CU): one round of resident workgroups -- measured at 256 sequences x 8k: whole sequences (256
+// workgroups) 0.77 of the HBM roofline, two splits each 0.73 (profiles/r05_mx4.txt) -- never under 8 tiles a split; a whole
+// sequence is final (no partials, no merge launch).
+//
+// More sequences than half the CUs (round 6): the pieces per sequence that balance the last round of workgroups (ring_rule.hpp
+// balanced_tiles_per_piece: 260 x 8k 0.57 -> 0.69 of the HBM roofline, 300 0.65 -> 0.74, 340 0.72 -> 0.78; 360 and up stay whole).
+inline uint32_t mx4_batch_tps(uint32_t n_seq, uint32_t tiles_max, uint32_t cus, const BatchTuning& t)
+{
+    if (t.tiles_per_split > 0) return static_cast<uint32_t>(t.tiles_per_split);      // (tests, measurement runs)
+    const uint32_t resident = cus;
+    const uint32_t splits = std::max(1u, resident / std::max(1u, n_seq));
+    // (up to CUs sequences whole ones run on the 8-wave halves form: pieces pay from 8k context -- 130 x 8k 0.63 -> 0.65, 160 0.71 -> 0.76; 4k: 0.63 -> 0.61, 0.73 -> 0.70)
+    if ((n_seq > resident && tiles_max >= 64u) || (2u * n_seq > resident && tiles_max >= 256u)) return balanced_tiles_per_piece(nullptr, n_seq, tiles_max, 1u, resident, kPiecesMx4);
+    return std::max(8u, (tiles_max + splits - 1u) / splits);
+}
+
+// ---- split length and room ---------------------------------------------------------------------------------------------------------
+// tps: AttendArgs::tiles_per_split; piece_tps: the length the members are cut by (assign_pieces); max_splits: AttendArgs::n_splits, the pieces a
+// member has at most -- for a plan the ROOM its launches are sized for; rows_first: AttendArgs::rows_first; rule_tps / rule_splits: what the rule
+// for equal lengths gives (a plan's room is kept per shape, and that rule is part of the shape: the tuning keys move it); fits: no member in
+// more than 2048 pieces (the entries refuse otherwise)
+struct BatchRoom { uint32_t max_splits; bool rows_first; };
+struct BatchGeometry { uint32_t tps, piece_tps, max_splits; bool rows_first; UnequalSplit unequal; uint32_t rule_tps, rule_splits; bool fits; };
+
+// the pieces of one member of n_tiles: {tiles of a piece (unequal: of the first), pieces}
+inline EvenSplit member_pieces(const BatchGeometry& g, uint32_t n_tiles)
+{
+    // the sequence's tiles divided evenly over its splits (171 + 85 tiles instead of 128 + 128 cost 15 %)
+    const EvenSplit es = g.unequal.on ? unequal_pieces(g.unequal, n_tiles) : even_split(n_tiles, (n_tiles + g.piece_tps - 1u) / g.piece_tps);
+    return EvenSplit{n_tiles ? es.tiles_per_split : g.piece_tps, es.n_splits};
+}
+
+// (MXFP4 -- and INT4_G32 on the whole-record kernel, and FP8 by residue classes -- over striped pools count tiles by residue class: at most
+//  ceil(pages / 16) + runs + 1 of them, whatever a member's run count; stripe_n_max is the largest run count of such a plan, 0 otherwise)
+inline uint32_t plan_tiles_bound(uint32_t max_pos_end, uint32_t stripe_n_max)
+{
+    return (max_pos_end / 2u + 15u) / 16u + (stripe_n_max >= 2u ? stripe_n_max + 1u : 0u);
+}
+
+// One split length for the whole batch.  A batch brings its own parallelism: the fewer, longer splits the better, down
+// to about one round of resident workgroups (256 sequences x 8k context, one layer, FP8: 8 tiles per split 0.50 of
+// HBM peak, 32: 0.59, 64: 0.67, 128: 0.72, 256 = no split: 0.74; INT4: 64..128 best, 0.59; at 2k context both
+// formats want no split at all).  INT4 target: 768 workgroups, never under 8 tiles per split; FP8: the cost rule of
+// batch_tiles_per_split.
+// INT4 (arithmetic-bound kernel): splits longer than 256 tiles stop paying (256 sequences x 32k: 256 tiles per split
+// 0.67, 512: 0.65, 1024 = no split: 0.60), shorter sequences are best left whole (8k 0.63 against 0.59 in two
+// splits, 4k 0.60 / 0.52, 2k 0.58 / 0.43: single-split rows are final, no partials and no merge).
+//
+// tiles[i] = the tiles of member i (by residue class where form.by_class); by_length = batch_dispatch_order gave an order.
+// kEntryBatch (Engine::attend_batch): everything follows from the members' tiles; bound_tiles and kept are not read.
+// kEntryPlan (Engine::attend_batch_plan, attend_planned): the launches of a plan may sit in a captured graph, so their grid (pieces per member at
+// most) and the presence of the merge launch must not change under it, and so the plan differs from the batch entry in three places:
+//  - the rule for equal lengths is taken on the plan's bound (bound_tiles = plan_tiles_bound) for every member -- it depends on the bound only, so
+//    plan and launch agree -- and, for INT4 with 8 kv heads, it is the whole-record kernel's WHATEVER the placement (a striped / table launch runs
+//    that geometry on the 4-head kernels): a page that migrates between two plans of a shape must not move the captured grid;
+//  - the FIRST plan of a shape (members, format, bound) in a buffer fixes max_splits and rows_first -- from the lengths it sees: members of
+//    different lengths get room for pieces (ragged_tiles_per_piece) and the rows-first grid -- and every later plan of that shape in that buffer
+//    keeps them (kept != null; a later batch that wants more pieces than there is room for gets longer ones).  A new shape (the caller
+//    captures anew for it anyway) decides anew;
+//  - the room of a first plan is max(8, 32768 / (members x heads)) pieces at most, whatever the lengths ask for.
+// attend_planned calls with tiles == null and the kept room of its plan: tps, max_splits and rows_first as the plan decided them.
+inline BatchGeometry batch_geometry(BatchEntry entry, const BatchShape& s, const BatchForm& f, const BatchTuning& t, const uint32_t* tiles,
+                                    uint32_t bound_tiles, bool by_length, const BatchRoom* kept)
+{
+    const bool int4 = !s.fp8 && !s.mx4, plan = entry == kEntryPlan;
+    uint32_t n_max = 0;
+    if (tiles) for (uint32_t i = 0; i < s.n_seq; ++i) n_max = std::max(n_max, tiles[i]);
+    const uint32_t tiles_max = plan ? bound_tiles : n_max;
+    const bool whole_record = int4 && (plan ? s.heads == 8u : f.wg8 != 0u);
+    BatchGeometry g{};
+    g.unequal = (s.fp8 || s.mx4 || whole_record) ? UnequalSplit{false, 1.0} : int4_unequal_split(s.n_seq, s.heads / 4u, tiles_max, t);
+    g.tps = s.mx4 ? mx4_batch_tps(s.n_seq, tiles_max, s.cus, t) : whole_record ? int4_wg8_batch_tps(s.n_seq, tiles_max, s.cus, t)
+          : plan && g.unequal.on ? tiles_max : batch_tiles_per_split(s.fp8, s.n_seq, s.heads, plan ? nullptr : tiles, tiles_max, t);
+    g.rule_tps = g.piece_tps = g.tps;
+    g.rule_splits = g.unequal.on ? 2u : std::max(1u, (tiles_max + g.tps - 1u) / g.tps);
+    // members of different lengths: pieces on account of the lengths (ring_rule.hpp ragged_tiles_per_piece), dispatched by length and rows first
+    // (INT4: on the whole-record kernel only)
+    uint32_t r = 0;
+    if (tiles && (s.fp8 || s.mx4 || f.wg8) && !g.unequal.on && t.tiles_per_split <= 0 && t.order_as_given == 0)
+        r = ragged_tiles_per_piece(tiles, s.n_seq, s.cus, s.fp8 ? s.heads / 4u : 1u, s.fp8 ? 4u : 1u);
+    if (!plan) {
+        if (r && r < g.tps) g.tps = g.piece_tps = r;
+        for (uint32_t i = 0; i < s.n_seq; ++i) g.max_splits = std::max(g.max_splits, member_pieces(g, tiles[i]).n_splits);
+        // (members of different lengths with pieces: see launch_attend_fp8_batch)
+        g.rows_first = (by_length && g.max_splits > 1u) || g.unequal.on;
+        g.fits = (n_max + g.tps - 1u) / g.tps <= 2048u;
+        return g;
+    }
+    g.fits = g.rule_splits <= 2048u;
+    g.max_splits = g.rule_splits;
+    g.rows_first = g.unequal.on;
+    if (kept) {
+        g.max_splits = kept->max_splits;
+        g.rows_first = g.rows_first || kept->rows_first;
+    } else if (r && r < g.tps) {
+        // (the launches' scratch is sized for members x heads x room: 32 768 partials = 270 MB at most, 8 pieces at least)
+        const uint32_t room = std::max(8u, 32768u / std::max(1u, s.n_seq * s.heads));
+        g.max_splits = std::max(g.max_splits, std::min(room, (n_max + r - 1u) / r));
+        g.rows_first = true;
+    }
+    if (r && r < g.tps && g.max_splits > 1u) g.piece_tps = std::max(r, (n_max + g.max_splits - 1u) / g.max_splits);      // (pieces on account of the lengths, as many as there is room for)
+    // (a first plan whose members differ in length and have pieces -- by whichever rule -- takes the rows-first grid, as the batch entry does)
+    if (!kept && by_length && g.max_splits > 1u) g.rows_first = true;
+    return g;
+}
+
+// ---- pieces per member ------------------------------------------------------------------------------------------------------------
+// seqs[i].n_splits holds the tiles of member i on entry; on return its pieces, with tiles_per_split and part_base (the member's first
+// partial: heads x pieces partials each).  Returns the partials of the launch.  (Seq = AttendSeq, kernels.hpp)
+template <class Seq> inline uint64_t assign_pieces(const BatchGeometry& g, uint32_t heads, Seq* seqs, uint32_t n_seq)
+{
+    uint64_t parts = 0;
+    for (uint32_t i = 0; i < n_seq; ++i) {
+        const EvenSplit es = member_pieces(g, seqs[i].n_splits);
+        seqs[i].tiles_per_split = es.tiles_per_split;
+        seqs[i].n_splits = es.n_splits;
+        seqs[i].part_base = static_cast<uint32_t>(parts);
+        parts += static_cast<uint64_t>(heads) * es.n_splits;
+    }
+    return parts;
+}
+
+} // namespace speckv

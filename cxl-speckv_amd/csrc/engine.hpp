@@ -27,6 +27,7 @@
 #include "../../include/speckv_ext.h"
 #include "kernels.hpp"
 #include "ring_rule.hpp"
+#include "attend_geometry.hpp"
 #include "slab_pool.hpp"
 
 #include <condition_variable>
@@ -358,12 +359,13 @@ private:
     template <int N> struct PinnedRingT { void* base = nullptr; size_t slot_bytes = 0; hipEvent_t ev[N] = {}; int next = 0; };
     PinnedRingT<kSeqRingSlots> seq_ring_;
     PinnedRingT<4> grp_ring_;
-    struct PlanInfo { uint32_t n_seq; int scheme; uint32_t n_layers, max_pos_end; bool striped, table; uint32_t mx4_stripe_n_max; bool any_empty; bool ordered;
-                      uint32_t max_splits; bool rows_first; uint32_t rule_tps, rule_splits; };      // (the launch geometry the FIRST plan of this shape in this buffer chose: attend_batch_plan)
+    // what attend_batch_plan decided for the plan a buffer holds: the shape and the form its launches take (attend_geometry.hpp), the largest run count of a plan
+    // counted by residue classes (0 otherwise), and the room -- the launch geometry the FIRST plan of this shape in this buffer chose
+    struct PlanInfo { int scheme; uint32_t n_layers, max_pos_end; BatchShape shape; BatchForm form; uint32_t stripe_n_max; bool any_empty; bool ordered; BatchRoom room; };
     std::unordered_map<const void*, PlanInfo> plans_;      // device plan buffer -> what attend_batch_plan last wrote there
     // (buffer, members | format, bound | rule's piece length, rule's pieces) -> {room for pieces, rows-first grid}: what the FIRST plan of that shape in that
     // buffer chose -- kept per shape, so that a buffer that alternates between shapes keeps every shape's captured launches valid
-    std::map<std::array<uint64_t, 4>, std::pair<uint32_t, bool>> plan_rooms_;
+    std::map<std::array<uint64_t, 4>, BatchRoom> plan_rooms_;
     CompressGroup* d_groups_ = nullptr;    // device twin of grp_ring_ (4 slots): descriptors of a grouped compress launch
     uint8_t* d_zero_page_ = nullptr;     // stands in for never-written pages in the fused attention
     std::unordered_map<uint32_t, std::vector<int32_t>> hist_;
@@ -387,6 +389,17 @@ private:
     void* scratch(Scratch& s, size_t bytes, hipStream_t user = nullptr);
     void release_allocation(Allocation* a);
     void note_use(Allocation* a, hipStream_t s);
+    // fused attention (engine_attend.cpp): the plumbing its entries share
+    struct SeqCall;                                       // one single-sequence call: allocation, stream, page addresses
+    struct BatchMembers;                                  // the members of a batch / plan: descriptors, tiles, placement
+    int attend_begin(int scheme, bool scores, uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g, uint32_t pos_begin,
+                     uint32_t pos_end, float* d_out, hipStream_t s, SeqCall& c);
+    int attend_end(const SeqCall& c, hipStream_t s);
+    int gather_members(bool batch_entry, int scheme, uint32_t n_seq, const uint64_t* handles, const uint32_t* pos_end, uint32_t layer, uint32_t max_pos_end,
+                       hipStream_t s, BatchMembers& m);
+    int take_seq_slot(size_t bytes, int* slot, void** staged);
+    int ensure_zero_page(hipStream_t s);
+    uint8_t* attend_scratch(AttendArgs& k, uint64_t parts, size_t head_bytes, hipStream_t s);
     bool quiet(const Zombie& z);
     void drain_zombies(bool wait);
     // waits that give up the ABI lock (lk_) while the GPU works

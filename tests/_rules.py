@@ -1,0 +1,70 @@
+"""The launch decision of the batched attention, asked of the engine's own functions (csrc/attend_geometry.hpp through the wrappers of
+tests/csrc/host_rules_test.cpp): decide() walks them in the order Engine::attend_batch / attend_batch_plan + attend_planned do."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FP8, INT4, MX4 = 4, 3, 5
+P, I = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+DEFAULT_TUNING = (0, 0, 0, 0, 0)           # attend_tiles_per_split, attend_order_as_given, attend_fp8_table_regs, attend_fp8_striped_table, attend_int4_striped_wg
+ORDER_AS_GIVEN = (0, 1, 0, 0, 0)           # no dispatch order and no pieces on account of the lengths: what is left is the rule for equal lengths
+
+
+def load_rules():
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "csrc")])
+    lib = C.CDLL(os.path.join(ROOT, "tests", "_build", "libhostrules_test.so"))
+    lib.rules_batch_form.restype = None
+    lib.rules_batch_form.argtypes = [P, I, P]
+    lib.rules_batch_dispatch_order.restype = C.c_int
+    lib.rules_batch_dispatch_order.argtypes = [P, I, P, P]
+    lib.rules_plan_tiles_bound.restype = C.c_uint32
+    lib.rules_plan_tiles_bound.argtypes = [C.c_uint32, C.c_uint32]
+    lib.rules_batch_geometry.restype = C.c_uint64
+    lib.rules_batch_geometry.argtypes = [C.c_uint32, P, I, P, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, P, P]
+    return lib
+
+
+def _p(a):
+    return a.ctypes.data_as(P)
+
+
+def striped_tiles(pages, stripe_n):
+    """kernels.hpp mx4_striped_tiles: the tiles of a member counted by residue class of the page index"""
+    n = np.maximum(np.asarray(stripe_n, np.int64), 1)
+    pages = np.asarray(pages, np.int64)
+    return np.where(pages > 0, n * (((pages + n - 1) // n + 15) // 16), 0)
+
+
+def decide(lib, scheme, entry, pages, n_cus, heads=8, stripe_n=1, any_table=False, tuning=DEFAULT_TUNING, kept=None, max_pos_end=None):
+    """What the entry ("batch" or "plan": attend_batch_plan followed by attend_planned) decides for members of `pages` pages each, every one in stripe_n
+    runs (1: a single run), the first without a regular placement if any_table.  kept = (max_splits, rows_first) of the shape's first plan."""
+    pages = np.ascontiguousarray(pages, np.uint32)
+    n = len(pages)
+    shape = np.array([scheme == FP8, scheme == MX4, n, heads, n_cus, stripe_n != 1 or any_table, any_table], np.uint32)
+    tun = np.array(tuning, np.int32)
+    form = np.zeros(7, np.uint32)
+    lib.rules_batch_form(_p(shape), tun.ctypes.data_as(I), _p(form))
+    d = dict(zip(("table", "striped", "fp8_cls", "int4_cls", "by_class", "wg8", "round"), (int(v) for v in form)))
+    tiles = np.ascontiguousarray(striped_tiles(pages, stripe_n) if d["by_class"] else (pages.astype(np.int64) + 15) // 16, np.uint32)
+    order = np.zeros(n, np.uint32)
+    d["by_length"] = lib.rules_batch_dispatch_order(_p(shape), tun.ctypes.data_as(I), _p(pages), _p(order))
+    d["order"] = order if d["by_length"] else None
+    plan = entry != "batch"
+    bound = 0
+    if plan:
+        max_pos_end = int(pages.max()) * 2 if max_pos_end is None else max_pos_end
+        bound = lib.rules_plan_tiles_bound(max_pos_end, stripe_n if d["by_class"] else 0)
+    out = np.zeros(8, np.uint32)
+    pieces = np.zeros(3 * n, np.uint32)
+    k = (-1, 0) if kept is None else (int(kept[0]), int(kept[1]))
+    d["parts"] = lib.rules_batch_geometry(1 if plan else 0, _p(shape), tun.ctypes.data_as(I), _p(tiles), bound, d["by_length"], k[0], k[1], _p(out), _p(pieces))
+    d.update(zip(("tps", "piece_tps", "max_splits", "rows_first", "unequal", "rule_tps", "rule_splits", "fits"), (int(v) for v in out)))
+    d["pieces"] = pieces.reshape(n, 3)
+    if plan:                                   # the launch: attend_planned asks with the plan's room and no lengths
+        launch = np.zeros(8, np.uint32)
+        lib.rules_batch_geometry(1, _p(shape), tun.ctypes.data_as(I), None, bound, 0, d["max_splits"], d["rows_first"], _p(launch), None)
+        assert (launch[0], launch[2], launch[3]) == (d["tps"], d["max_splits"], d["rows_first"]), "attend_planned disagrees with its plan"
+    return d

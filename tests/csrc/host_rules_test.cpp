@@ -1,6 +1,6 @@
 // tests/csrc/host_rules_test.cpp -- TEST-ONLY C wrappers around the header-only host/device rules of the engine
-// (ring_rule.hpp: ring run / liveness arithmetic, even splits), for the CPU property tests.
-#include "../../cxl-speckv_amd/csrc/ring_rule.hpp"
+// (ring_rule.hpp: ring run / liveness arithmetic, even splits; attend_geometry.hpp: the launch decision of the batched attention), for the CPU property tests.
+#include "../../cxl-speckv_amd/csrc/attend_geometry.hpp"
 
 extern "C" {
 void rules_ring_take(uint32_t seq, uint32_t m, uint32_t n, uint32_t* out3)
@@ -35,5 +35,43 @@ void rules_int4_unequal(uint32_t columns, uint32_t tiles_max, uint32_t n_tiles, 
     const speckv::UnequalFraction u = speckv::int4_unequal_fraction(columns, tiles_max);
     const speckv::EvenSplit e = u.on ? speckv::unequal_pieces(u, n_tiles) : speckv::EvenSplit{n_tiles ? n_tiles : 1u, n_tiles ? 1u : 0u};
     out3[0] = u.on ? 1u : 0u; out3[1] = e.tiles_per_split; out3[2] = e.n_splits;
+}
+
+// ---- attend_geometry.hpp: the functions Engine::attend_batch / attend_batch_plan / attend_planned decide with (tests/_rules.py drives them)
+// shape7 = {fp8, mx4, n_seq, heads, cus, any_striped, any_table}; tun5 = {attend_tiles_per_split, attend_order_as_given, attend_fp8_table_regs,
+// attend_fp8_striped_table, attend_int4_striped_wg}
+static speckv::BatchShape shape_of(const uint32_t* s) { return speckv::BatchShape{s[0] != 0u, s[1] != 0u, s[2], s[3], s[4], s[5] != 0u, s[6] != 0u}; }
+static speckv::BatchTuning tuning_of(const int32_t* t) { return speckv::BatchTuning{t[0], t[1], t[2], t[3], t[4]}; }
+// out7 = {table, striped, fp8_cls, int4_cls, by_class, wg8, order_round}
+void rules_batch_form(const uint32_t* shape7, const int32_t* tun5, uint32_t* out7)
+{
+    const speckv::BatchForm f = speckv::batch_form(shape_of(shape7), tuning_of(tun5));
+    out7[0] = f.table; out7[1] = f.striped; out7[2] = f.fp8_cls; out7[3] = f.int4_cls; out7[4] = f.by_class; out7[5] = f.wg8; out7[6] = f.order_round;
+}
+int rules_batch_dispatch_order(const uint32_t* shape7, const int32_t* tun5, const uint32_t* pages, uint32_t* order)
+{
+    const speckv::BatchShape s = shape_of(shape7);
+    return speckv::batch_dispatch_order(speckv::batch_form(s, tuning_of(tun5)), tuning_of(tun5), pages, s.n_seq, order) ? 1 : 0;
+}
+uint32_t rules_plan_tiles_bound(uint32_t max_pos_end, uint32_t stripe_n_max) { return speckv::plan_tiles_bound(max_pos_end, stripe_n_max); }
+// entry 0: the batch entry, 1: a plan (kept_splits >= 0: the room its shape's first plan fixed; tiles null: as attend_planned asks).
+// out8 = {tps, piece_tps, max_splits, rows_first, unequal, rule_tps, rule_splits, fits}; pieces (may be null, needs tiles) = {tiles_per_split, n_splits,
+// part_base} per member; returns the partials of the launch (0 without pieces)
+uint64_t rules_batch_geometry(uint32_t entry, const uint32_t* shape7, const int32_t* tun5, const uint32_t* tiles, uint32_t bound_tiles, uint32_t by_length,
+                              int32_t kept_splits, int32_t kept_rows_first, uint32_t* out8, uint32_t* pieces)
+{
+    const speckv::BatchShape s = shape_of(shape7);
+    const speckv::BatchTuning t = tuning_of(tun5);
+    const speckv::BatchRoom kept{static_cast<uint32_t>(kept_splits), kept_rows_first != 0};
+    const speckv::BatchGeometry g = speckv::batch_geometry(entry ? speckv::kEntryPlan : speckv::kEntryBatch, s, speckv::batch_form(s, t), t, tiles, bound_tiles,
+                                                           by_length != 0u, kept_splits >= 0 ? &kept : nullptr);
+    out8[0] = g.tps; out8[1] = g.piece_tps; out8[2] = g.max_splits; out8[3] = g.rows_first; out8[4] = g.unequal.on; out8[5] = g.rule_tps; out8[6] = g.rule_splits; out8[7] = g.fits;
+    if (!pieces || !tiles || !g.fits) return 0;
+    struct Seq { uint32_t n_splits, tiles_per_split, part_base; };
+    std::vector<Seq> seqs(s.n_seq);
+    for (uint32_t i = 0; i < s.n_seq; ++i) seqs[i].n_splits = tiles[i];
+    const uint64_t parts = speckv::assign_pieces(g, s.heads, seqs.data(), s.n_seq);
+    for (uint32_t i = 0; i < s.n_seq; ++i) { pieces[3 * i] = seqs[i].tiles_per_split; pieces[3 * i + 1] = seqs[i].n_splits; pieces[3 * i + 2] = seqs[i].part_base; }
+    return parts;
 }
 }

@@ -2,7 +2,7 @@
 (speckv_ext_attend_{fp8,int4,mx4}_batch) and the planned entry (speckv_ext_attend_batch_plan + *_planned).
 
 Each case names the geometry regime it is built to reach and proves that on the host first, through the rules the engine decides
-with (ring_rule.hpp, wrapped by tests/csrc/host_rules_test.cpp); a failing branch assertion means the case no longer tests its
+with (attend_geometry.hpp and ring_rule.hpp, wrapped by tests/csrc/host_rules_test.cpp and asked through tests/_rules.py); a failing branch assertion means the case no longer tests its
 regime.  Then EVERY (member, head, query row) of out and lse is checked against the float64 attention over the dequantised records
 (tests/_gpu.py HeadChecker.check_rows: |err| <= (2e-3 + 2 delta) sum p|v| + 1e-6, lse within 2e-3 + delta, empty members 0).
 Members share a few KV contents (each dequantised once) and have their own queries; all seeds are fixed.
@@ -19,6 +19,7 @@ import pytest
 import cxl_speckv_amd as pkg
 from cxl_speckv_amd.speckv_ctypes import SpeckvError
 from tests._gpu import D, H, HeadChecker, graph_capture, torch_mod
+from tests._rules import ORDER_AS_GIVEN, decide, load_rules
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,8 +37,7 @@ def cus():
 
 @pytest.fixture(scope="module")
 def rules():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "csrc")])
-    lib = C.CDLL(os.path.join(ROOT, "tests", "_build", "libhostrules_test.so"))
+    lib = load_rules()
     P = C.POINTER(C.c_uint32)
     for name, args in (("rules_fp8_batch_tiles_per_split", [P] + [C.c_uint32] * 4), ("rules_balanced_tiles_per_piece", [P] + [C.c_uint32] * 5),
                        ("rules_ragged_tiles_per_piece", [P] + [C.c_uint32] * 3)):
@@ -85,8 +85,9 @@ def regime(name, n_cus):
 
 
 def assert_branch(rules, name, scheme, entry, lens, n_cus):
-    """The case reaches its regime: the rules the engine decides with (engine_attend.cpp attend_batch / attend_batch_plan / plan_geometry)
-    give the geometry the regime names.  FP8 split lengths are priced for 256 CUs by the engine (batch_tiles_per_split)."""
+    """The case reaches its regime: the engine's own decision (attend_geometry.hpp batch_form / batch_geometry / batch_dispatch_order, as
+    Engine::attend_batch and attend_batch_plan + attend_planned call them; tests/_rules.py decide) gives the geometry the regime names.
+    FP8 split lengths are priced for 256 CUs by the engine (batch_tiles_per_split)."""
     n = len(lens)
     t = tiles_of(lens)
     tmax = int(t.max())
@@ -94,33 +95,40 @@ def assert_branch(rules, name, scheme, entry, lens, n_cus):
     model = {FP8: 1, MX4: 0, INT4: 3}[scheme]                     # rules_ragged_tiles_per_piece: FP8 / one column, one slot
     tarr, tp = u32(t)
     ragged = rules.rules_ragged_tiles_per_piece(tp, n, n_cus, model)
-    order = np.zeros(n, np.uint32)
-    order_round = 0 if scheme == MX4 else (n_cus // 2 if scheme == FP8 else n_cus)        # engine_attend.cpp attend_order_round (8 kv heads)
-    parr, pp = u32(np.asarray(lens) // 2)
-    by_length = rules.rules_dispatch_order(pp, n, order_round, order.ctypes.data_as(C.POINTER(C.c_uint32)))
+    pages = np.asarray(lens) // 2
+    # R5: the first member has a migrated page (no regular placement), the others lie in single runs
+    d = decide(rules, scheme, "batch" if entry == "batch" else "plan", pages, n_cus, any_table=name == "R5")
+    equal = decide(rules, scheme, "batch" if entry == "batch" else "plan", pages, n_cus, any_table=name == "R5", tuning=ORDER_AS_GIVEN)      # the rule for equal lengths
+    order_round, by_length, order, tps = d["round"], d["by_length"], d["order"], d["tps"]
+    assert d["fits"] == 1 and order_round == (0 if scheme == MX4 else (n_cus // 2 if scheme == FP8 else n_cus))
     if name == "R1":
         assert n * cols <= n_cus and ragged == 0 and by_length == 0            # one round, no pieces on account of the lengths, the order as given
+        assert d["rows_first"] == 0 and d["piece_tps"] == tps
     elif name in ("R2a", "R2b"):
-        assert ragged == 0 and by_length == 0
+        assert ragged == 0 and by_length == 0 and d["rows_first"] == 0
         if scheme == FP8:                                          # more columns than CUs, 128 tiles: the balanced pieces
             assert n * cols > 256 and tmax >= 128
-            tps = rules.rules_fp8_batch_tiles_per_split(None, n, tmax, cols, 256)
+            assert tps == rules.rules_fp8_batch_tiles_per_split(None, n, tmax, cols, 256)
             assert tps < tmax and tps == rules.rules_balanced_tiles_per_piece(None, n, tmax, cols, 256, 1)
         elif scheme == INT4:                                       # int4_wg8_batch_tps: one-run workgroups past the CU count (form 2), 16-wave ones below (form 1)
-            wg8_form = 2 if n > n_cus else 1
+            wg8_form = d["wg8"]
             assert wg8_form == (1 if name == "R2a" else 2)
-            tps = rules.rules_balanced_tiles_per_piece(None, n, tmax, 1, n_cus, 2 if wg8_form == 2 else 3)
+            assert tps == rules.rules_balanced_tiles_per_piece(None, n, tmax, 1, n_cus, 2 if wg8_form == 2 else 3)
             assert 2 * n > n_cus and tmax >= 64 and tps < tmax
         elif name == "R2b":                                        # mx4_batch_tps: past the CU count, the balanced pieces
-            assert n > n_cus and rules.rules_balanced_tiles_per_piece(None, n, tmax, 1, n_cus, 0) < tmax
+            assert n > n_cus and tps == rules.rules_balanced_tiles_per_piece(None, n, tmax, 1, n_cus, 0) and tps < tmax
         else:                                                      # MXFP4 below the CU count at 4k: whole members, the 8-wave halves form
-            assert n <= n_cus and not (2 * n > n_cus and tmax >= 256) and max(8, -(-tmax // max(1, n_cus // n))) == tmax
+            assert n <= n_cus and not (2 * n > n_cus and tmax >= 256) and tps == tmax and d["max_splits"] == 1
+        assert d["max_splits"] == -(-tmax // tps)
     elif name == "R3":                                             # pieces on account of the lengths, rows first, by length
         assert by_length == 1 and ragged != 0 and ragged < tmax
+        assert d["rows_first"] == 1 and d["max_splits"] > 1 and ragged <= d["piece_tps"] < equal["tps"]
+        if entry == "batch":
+            assert tps == ragged
         if scheme == FP8:
             assert ragged < rules.rules_fp8_batch_tiles_per_split(tp, n, 0, cols, 256)
         else:                                                      # mx4_batch_tps / int4_wg8_batch_tps below the CU count: one round of splits
-            assert n <= n_cus // 2 and ragged < max(8, -(-tmax // max(1, n_cus // n)))
+            assert n <= n_cus // 2 and ragged < equal["tps"] and equal["piece_tps"] == equal["tps"]
     elif name == "R4":                                             # the serpentine: more members than a round, one round reversed at least
         assert by_length == 1 and order_round and n > order_round
         got = np.asarray(lens)[order] // 2
@@ -129,12 +137,17 @@ def assert_branch(rules, name, scheme, entry, lens, n_cus):
         out = (C.c_uint32 * 3)()
         rules.rules_int4_unequal(2 * n, tmax, tmax, out)
         assert 384 <= 2 * n <= 672 and tmax >= 192 and out[0] == 1 and out[2] == 2 and tmax // 2 <= out[1] < tmax
-        # (the planned entry keeps the whole-record geometry for 8 kv heads whatever the placement -- plan_geometry -- and runs the
-        #  page-table form with it: what its case proves is that form, by the migration below)
+        assert d["table"] == 1 and d["wg8"] == 0
+        if entry == "batch":
+            assert d["unequal"] == 1 and d["max_splits"] == 2 and d["rows_first"] == 1 and int(d["pieces"][0, 0]) == out[1]
+        else:
+            # (the planned entry keeps the whole-record geometry for 8 kv heads whatever the placement -- batch_geometry says why -- and runs the
+            #  page-table form with it: what its case proves is that form, by the migration below)
+            assert d["unequal"] == 0
     elif name == "R6":                                             # FP8 below the machine: the split rule prices pieces
         assert n * cols <= 256
-        tps = rules.rules_fp8_batch_tiles_per_split(None, n, tmax, cols, 256)
-        assert tps < tmax and n * cols * -(-tmax // tps) > 256
+        assert tps == rules.rules_fp8_batch_tiles_per_split(None, n, tmax, cols, 256)
+        assert tps < tmax and n * cols * -(-tmax // tps) > 256 and d["max_splits"] == -(-tmax // tps)
 
 
 # ----------------------------------------------------------------------------- building a case
@@ -342,8 +355,8 @@ def test_planned_layers_tail_stride_must_cover_every_layer(oracle):
     torch = torch_mod()
     lens = np.array([256, 200, 130, 2, 64, 256, 98, 34])            # no empty member (the in-kernel fold needs every member's split 0)
     n, L = len(lens), 2
-    # one split per member: mx4_batch_tps with 8 tiles at most is 8 tiles (engine_attend.cpp), and no pieces on account of the lengths
-    assert max(8, -(-8 // max(1, cus() // n))) == 8 and int(tiles_of(lens).max()) == 8
+    # one split per member: mx4_batch_tps with 8 tiles at most is 8 tiles (attend_geometry.hpp), and no pieces on account of the lengths
+    assert decide(load_rules(), MX4, "plan", lens // 2, cus())["max_splits"] == 1 and int(tiles_of(lens).max()) == 8
     case = Case(engine(fresh=True), oracle, MX4, lens, 7400, layers=L)
     try:
         lib = case.lib

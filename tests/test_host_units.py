@@ -531,7 +531,10 @@ def test_mx4_class_enumeration_covers_every_page_once_and_stays_inside_the_plann
     """k_attend_mx4's striped form takes the pages of a range by residue class (kernels.hpp: mx4_class_tiles, mx4_striped_tiles):
     class c = pages j with j % n == c, in tiles of 16, every class with the tile count of the largest.  Restated here: every page
     of the range appears in exactly one (class, tile, row), rows past a class's end are the masked ones, and the tile count stays
-    under the bound the planner sizes its splits with (engine_attend.cpp: plan_geometry, ceil(pages / 16) + runs + 1)."""
+    under the bound the planner sizes its splits with (attend_geometry.hpp: plan_tiles_bound, ceil(pages / 16) + runs + 1)."""
+    from tests._rules import load_rules
+    bound = load_rules().rules_plan_tiles_bound                       # the engine's own bound
+
     def class_tiles(n_pages, n):
         return ((n_pages + n - 1) // n + 15) // 16
 
@@ -540,6 +543,8 @@ def test_mx4_class_enumeration_covers_every_page_once_and_stays_inside_the_plann
             m = class_tiles(pages, n)
             total = n * m
             assert total <= (pages + 15) // 16 + n + 1, (n, pages, total)
+            if n >= 2:
+                assert total <= bound(2 * pages, n) == (pages + 15) // 16 + n + 1
             if pages > 2000:
                 continue
             seen = set()
@@ -551,3 +556,36 @@ def test_mx4_class_enumeration_covers_every_page_once_and_stays_inside_the_plann
                         assert j not in seen
                         seen.add(j)
             assert len(seen) == pages, (n, pages)
+
+
+# ----------------------------------------------------------------------------- the launch decision of the batched attention, pinned
+def test_batch_attention_decision_replays_the_recorded_table(golden_dir):
+    """tests/golden/attend_geometry.json holds, for some 400 shapes (format, members, lengths, CUs, placement, tuning keys, entry), what the batched
+    attention entries decided BEFORE their decision moved into attend_geometry.hpp -- recorded from the rule functions of that time and the inline
+    decisions of attend_batch, attend_batch_plan and attend_planned around them.  The engine's functions of today must give the same: the form, the
+    split length, the room, rows-first, the dispatch order and every member's pieces."""
+    import zlib
+    from tests._rules import FP8, INT4, MX4, decide, load_rules
+    lib = load_rules()
+    g = json.load(open(os.path.join(golden_dir, "attend_geometry.json")))
+    cols, schemes = g["columns"], {"fp8": FP8, "int4": INT4, "mx4": MX4}
+    assert len(g["rows"]) >= 390
+    for r in g["rows"]:
+        row = dict(zip(cols, r))
+        spec = g["lens_pages"][row["lens"]]
+        pages = np.full(spec[1], spec[2], np.uint32) if spec[0] == "eq" else np.asarray(spec, np.uint32)
+        kept = None if row["kept_splits"] < 0 else (row["kept_splits"], row["kept_rows_first"])
+        d = decide(lib, schemes[row["format"]], row["entry"], pages, row["cus"], row["heads"], row["stripe_n"], bool(row["any_table"]),
+                   g["tunings"]["values"][row["tuning"]], kept, row["max_pos_end"])
+        assert d["fits"] == 1, r[:11]
+        got = {k: d[k] for k in ("table", "striped", "fp8_cls", "int4_cls", "by_class", "wg8", "round", "by_length", "tps", "piece_tps", "max_splits",
+                                 "rows_first", "parts")}
+        if row["entry"] == "plan":                                  # (the batch entry has no rule apart from its split length: recorded as 0)
+            got.update(rule_tps=d["rule_tps"], rule_splits=d["rule_splits"])
+        got["pieces_crc32"] = zlib.crc32(np.ascontiguousarray(d["pieces"][:, :2]).tobytes())
+        got["order_crc32"] = zlib.crc32(d["order"].tobytes()) if d["by_length"] else 0
+        assert got == {k: row[k] for k in got}, (r[:11], {k: (v, row[k]) for k, v in got.items() if v != row[k]})
+        if "pieces" in row:                                         # (small batches: the pieces in full)
+            assert d["pieces"][:, :2].ravel().tolist() == row["pieces"], r[:11]
+        base = np.concatenate(([0], np.cumsum(d["pieces"][:-1, 1].astype(np.int64) * row["heads"])))
+        assert np.array_equal(d["pieces"][:, 2], base), r[:11]     # part_base: heads x pieces partials per member, in member order
