@@ -400,6 +400,12 @@ hipError_t launch_attend_fold_tail(uint32_t n_rows, const uint32_t* d_rows, uint
                                    float* d_out, float* d_lse, hipStream_t s, uint32_t n_layers = 1, uint32_t layer_rows = 0);
 // (n_layers > 1: the same rows for n_layers consecutive layers in one launch -- layer l's q / out / lse row blocks start l * layer_rows
 //  row blocks further on, its tail rows l * heads * 128 elements further on)
+// the positions a multi-position step holds outside the pool, folded causally into rows [n_seq][heads][g][128] with g = n_q x rows_per_pos:
+// query position j of sequence i += held positions 0 .. d_base[i] + j (fp16 rows at i * seq_stride + t * pos_stride + head * 128);
+// positions >= d_n_q[i] (null: none) untouched; see k_attend_fold_held
+hipError_t launch_attend_fold_held(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
+                                   const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                                   const uint32_t* d_base, const uint32_t* d_n_q, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
 // a.lin_base set: linear form (a.scale_tab, a.q16); else page-table form (a.q8 / a.qs from launch_quantize_q_e4m3)
 hipError_t launch_attend_fp8(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s);
 // scale_tab[tile order of p] = entries[p].rec_bytes >= 2048 ? entries[p].scale : 0 for every page (set_layout time)

@@ -15,12 +15,16 @@ paged-attention layer would talk to for a BATCH of requests:
   attend                       the attention of one layer for the whole batch straight from the compressed records
                                (FP8 / INT4 pools: ``speckv_ext_attend_*_batch``), the tail position folded in with
                                the returned log-sum-exp
+  attend_spec / append_tokens  a step of SEVERAL positions per request (speculative decoding, chunked prefill, ragged
+                               batches): the S new positions ride through the same pass over the records as extra query
+                               rows, the rows held outside the pool are folded in causally by one launch
+                               (``speckv_ext_attend_fold_held``); then the accepted prefix is committed
 
 Only plain device pointers cross into the library; torch is used for device buffers and the tail fold.
 """
 from typing import Dict, List, Optional, Sequence
 
-from .speckv_ctypes import SpeckvLib
+from .speckv_ctypes import HELD_MAX, SpeckvLib
 
 PAGE = 4096
 SCHEMES = {"fp16": 0, "int8": 1, "int8_delta_rle": 2, "int4": 3, "fp8": 4, "mxfp4": 5}
@@ -93,6 +97,7 @@ class SpeckvKVConnector:
         self._step_cols = {}
         self._plan_stream = None
         self._kscale = self._kscale_inv = None               # set_k_channel_scale
+        self._spec_key = self._spec_idx = self._spec_base = None     # attend_spec: where the held rows of a step come from
 
     def set_k_channel_scale(self, scale):
         """Per-(layer, kv head, channel) pre-scale of K, folded into the query: K / scale goes into the pool, q * scale meets it, q.k is
@@ -454,3 +459,204 @@ class SpeckvKVConnector:
                 self.lib.attend_planned_layers(self.scheme, self._plan.data_ptr(), B, layer_begin, n_layers, q.data_ptr(), G, self._plan_bound, sm_scale,
                                                out.data_ptr(), lse.data_ptr(), st.cuda_stream, n_tail, rows, idx, kt, vt, self.L * self.H * self.D)
         return out
+
+    # ------------------------------------------------------------------ steps of several positions
+    @staticmethod
+    def spec_groups(S: int, rows_per_pos: int):
+        """How a step of S new positions with rows_per_pos query rows per kv head and position goes through the attention kernels,
+        which take at most 16 query rows per kv head in one pass over the records: [(first position, positions)] -- groups of
+        16 // rows_per_pos positions, the last one possibly shorter.  One group = one pass; every further group reads the records again."""
+        if not 1 <= rows_per_pos <= 16:
+            raise ValueError("rows_per_pos must be 1..16 (query rows per kv head of one position)")
+        if not 1 <= S <= HELD_MAX - 1:
+            raise ValueError(f"a step carries 1..{HELD_MAX - 1} new positions per request")
+        per = 16 // rows_per_pos
+        return [(j0, min(per, S - j0)) for j0 in range(0, S, per)]
+
+    @staticmethod
+    def commit_plan(lengths: Sequence[int], n_accept: Sequence[int]):
+        """The pool writes and tails that committing the first n_accept[b] new positions of request b (current length lengths[b])
+        comes to -- what that many single append() calls would do.  A source is the index of a new position, or -1 for the odd
+        position the request holds already.  Returns (pairs, tails): pairs[p] = [(b, page of the K region of layer 0, source of the
+        pair's first position, source of its second)] for the p-th pair of every request that has one; tails = [(b, source)] for the
+        requests that end on an odd length (requests with n_accept 0 appear in neither)."""
+        pairs, tails = [], []
+        for b, (ln, n) in enumerate(zip(lengths, n_accept)):
+            if n == 0:
+                continue
+            held = ([-1] if ln & 1 else []) + list(range(n))           # the positions outside the pool, oldest first
+            for p in range(len(held) // 2):
+                while len(pairs) <= p:
+                    pairs.append([])
+                pairs[p].append((b, (ln & ~1) // 2 + p, held[2 * p], held[2 * p + 1]))
+            if len(held) & 1:
+                tails.append((b, held[-1]))
+        return pairs, tails
+
+    def _held_rows(self, req_ids, key, reqs, k_new, v_new, layer_begin, n_layers, st):
+        """The rows a step holds outside the pool as speckv_ext_attend_fold_held takes them: fp16 [n_layers][batch][1 + S][heads][dim]
+        per kind -- the request's odd last position (if any) followed by its new positions -- and the count of positions in front of
+        the first new one, int32 [n_layers * batch].  Two torch kernels per kind; the gather indices are per (batch, lengths, S)."""
+        import torch
+        B, S = k_new.shape[0], k_new.shape[1]
+        self._prepare_tails(req_ids, key, reqs, st)                     # the odd positions of the batch as one tensor per kind
+        skey = (key, self._epoch, S, n_layers)
+        if self._spec_key != skey:
+            idx, base, rank = [], [], 0
+            for b, r in enumerate(reqs):
+                if r.length & 1:
+                    idx += [B * S + rank] + [b * S + t for t in range(S)]
+                    rank += 1
+                else:
+                    idx += [b * S + t for t in range(S)] + [b * S + S - 1]      # (the last slot is never visible)
+                base.append(r.length & 1)
+            self._spec_key, self._spec_idx, self._spec_base = skey, _device_index(idx), _device_index(base * n_layers)
+        held = []
+        for new, tails in ((k_new, self._fold_k), (v_new, self._fold_v)):
+            flat = new[:, :, layer_begin:layer_begin + n_layers].permute(2, 0, 1, 3, 4).reshape(n_layers, B * S, self.H, self.D)
+            if self._fold_n:
+                flat = torch.cat((flat, tails[:, layer_begin:layer_begin + n_layers].permute(1, 0, 2, 3)), dim=1)
+            held.append(flat.index_select(1, self._spec_idx))
+        return held[0], held[1], self._spec_base
+
+    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None):
+        """One layer of a step that carries S new positions per request -- draft tokens to verify, a chunk of a prompt: query position
+        j of a request sees everything the request holds (pool and odd last position) and the new positions 0..j.
+        q [batch][S][heads][rows_per_pos][dim] fp16; k_new / v_new [batch][S][layers][heads][dim] fp16, the positions that would follow
+        each request's current length; n_new: optional per-request counts <= S of positions that are live (a ragged step).  Returns
+        [batch][S][heads][rows_per_pos][dim] fp32; rows of positions >= n_new[b] are unspecified but finite.
+        Changes no state: lengths, tails and pool stay as they are -- append_tokens() commits what was accepted.
+        The stored positions are read ONCE for up to 16 query rows per kv head: S * rows_per_pos <= 16 is one pass over the records,
+        more goes in groups of 16 // rows_per_pos positions (spec_groups) with one pass each.  The held rows are folded in by one launch
+        per group (speckv_ext_attend_fold_held)."""
+        return self.attend_spec_layers(layer, 1, req_ids, q[None], k_new, v_new, sm_scale, n_new, stream)[0]
+
+    def attend_spec_layers(self, layer_begin: int, n_layers: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None,
+                           stream=None):
+        """attend_spec for n_layers consecutive layers whose query rows exist at once: q [n_layers][batch][S][heads][rows_per_pos][dim],
+        returns the same shape in fp32.  Per group of positions one speckv_ext_attend_planned_layers call and one fold launch over all
+        the layers."""
+        import torch
+        if self.scheme not in FUSED:
+            raise ValueError("attend_spec() needs an FP8, INT4 or MXFP4 pool")
+        NL, B, S, H, R, D = q.shape
+        if NL != n_layers or tuple(k_new.shape) != (B, S, self.L, H, D) or tuple(v_new.shape) != (B, S, self.L, H, D):
+            raise ValueError("q must be [n_layers][batch][S][heads][rows_per_pos][dim], k_new / v_new [batch][S][layers][heads][dim]")
+        groups = self.spec_groups(S, R)
+        if n_new is not None:
+            n_new = [int(n) for n in n_new]
+            if len(n_new) != B or not all(0 <= n <= S for n in n_new):
+                raise ValueError("n_new: one count 0..S per request")
+        key, reqs, _ = self._batch(req_ids)
+        if self._kscale is not None:
+            q = q * self._kscale[layer_begin:layer_begin + n_layers][:, None, None, :, None, :]
+            k_new = k_new * self._kscale_inv[None, None]
+        out = torch.empty((NL, B, S, H, R, D), dtype=torch.float32, device="cuda")
+        akey = (key, self._epoch)
+        with self._On(self, stream) as st:
+            if self._arg_key != (akey, st.cuda_stream):
+                self.plan_step(req_ids, st)
+            self._plan_stream = st
+            with torch.cuda.stream(st):
+                kh, vh, base = self._held_rows(req_ids, key, reqs, k_new, v_new, layer_begin, n_layers, st)
+                live = None if n_new is None else _device_index(n_new * NL)
+                for j0, n in groups:
+                    g = n * R
+                    qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
+                    og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
+                    lse = torch.empty((NL, B, H, g), dtype=torch.float32, device="cuda")
+                    if NL == 1:
+                        self.lib.attend_planned(self.scheme, self._plan.data_ptr(), B, layer_begin, qg.data_ptr(), g, self._plan_bound, sm_scale,
+                                                og.data_ptr(), lse.data_ptr(), st.cuda_stream)
+                    else:
+                        self.lib.attend_planned_layers(self.scheme, self._plan.data_ptr(), B, layer_begin, NL, qg.data_ptr(), g, self._plan_bound,
+                                                       sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
+                    d_base = base + j0 if j0 else base
+                    d_live = None if live is None else (live - j0).clamp_(0, n)
+                    self.lib.attend_fold_held(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
+                                              d_base.data_ptr(), 0 if d_live is None else d_live.data_ptr(), sm_scale, og.data_ptr(),
+                                              lse.data_ptr(), st.cuda_stream)
+                    out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
+        return out
+
+    def append_tokens(self, req_ids: Sequence[int], k_new, v_new, n_accept: Sequence[int], stream=None):
+        """Commit the first n_accept[b] (0..S) of the S new positions k_new[b], v_new[b] ([batch][S][layers][heads][dim] fp16) of every
+        request -- the accepted prefix of a speculative step, or a chunk of a prompt onto a request that has positions already.
+        Whole position pairs go to the pool, an odd remainder becomes the tail: the state a run of single append() calls would leave.
+        One speckv_ext_write_strided_batch call per pair index over the requests that have that pair (at most S / 2 + 1 launches).
+        n_accept[b] = 0 leaves the request untouched.  Returns the sources of the asynchronous writes, as append()."""
+        import torch
+        B, S = k_new.shape[0], k_new.shape[1]
+        n_accept = [int(n) for n in n_accept]
+        reqs = [self.requests[rid] for rid in req_ids]
+        if len(reqs) != B or len(n_accept) != B or tuple(v_new.shape) != tuple(k_new.shape) or tuple(k_new.shape[2:]) != (self.L, self.H, self.D):
+            raise ValueError("k_new / v_new must be [batch][S][layers][heads][dim], n_accept one count per request")
+        for rid, r, n in zip(req_ids, reqs, n_accept):
+            if not 0 <= n <= S:
+                raise ValueError(f"request {rid}: n_accept {n} outside 0..{S}")
+            if r.length + n > self.T:
+                raise ValueError(f"request {rid} is full")
+        pairs, tails = self.commit_plan([r.length for r in reqs], n_accept)
+        if not pairs and not tails:
+            return []
+        if self._kscale_inv is not None:
+            k_new = k_new * self._kscale_inv[None, None]        # [batch][S][layers][heads][dim]
+        used = [b for b, (r, n) in enumerate(zip(reqs, n_accept)) if n and r.length & 1]        # requests whose odd position finds its partner
+        rank = {b: i for i, b in enumerate(used)}
+        src = lambda b, t: B * S + rank[b] if t < 0 else b * S + t                              # row of the flat [new rows | odd positions] tensor
+        keep = []
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):                         # (the page images are built ON the stream the writes run on: append())
+                kf, vf = k_new.reshape(B * S, self.L, self.H, self.D), v_new.reshape(B * S, self.L, self.H, self.D)
+                if used:
+                    if tuple(req_ids[b] for b in used) == self._tail_ids:
+                        kt, vt = self._tail_k, self._tail_v
+                    else:
+                        kt = torch.stack([reqs[b].tail_k for b in used]); vt = torch.stack([reqs[b].tail_v for b in used])
+                    kf, vf = torch.cat((kf, kt)), torch.cat((vf, vt))
+                if pairs:
+                    i0 = _device_index([src(b, s0) for group in pairs for b, _, s0, _ in group])
+                    i1 = _device_index([src(b, s1) for group in pairs for b, _, _, s1 in group])
+                    # page images of all pairs, pair index by pair index: [n][layer][kind][2 positions][heads][dim]
+                    pair = torch.stack((torch.stack((kf.index_select(0, i0), kf.index_select(0, i1)), dim=2),
+                                        torch.stack((vf.index_select(0, i0), vf.index_select(0, i1)), dim=2)), dim=2).contiguous()
+                    keep.append(pair)
+                if tails:
+                    it = _device_index([src(b, t) for b, t in tails])
+                    tk, tv = kf.index_select(0, it), vf.index_select(0, it)                     # copies: the caller may reuse k_new
+            if pairs:
+                import numpy as np
+                step_bytes = pair[0].numel() * 2
+                at = pair.data_ptr()
+                for group in pairs:
+                    if len(group) == 1:
+                        self.lib.write_strided(reqs[group[0][0]].handle, group[0][1], self.region_pages, 2 * self.L, at, st.cuda_stream)
+                    else:
+                        srcs = np.arange(len(group), dtype=np.uint64) * np.uint64(step_bytes) + np.uint64(at)
+                        self.lib.write_strided_batch([reqs[b].handle for b, _, _, _ in group], np.asarray([pg for _, pg, _, _ in group], dtype=np.uint64),
+                                                     srcs, self.region_pages, 2 * self.L, st.cuda_stream)
+                    at += len(group) * step_bytes
+        for b in used:
+            reqs[b].clear_tail()
+        for i, (b, _) in enumerate(tails):
+            reqs[b].set_tail(tk, tv, i)
+        self._tail_ids, self._tail_k, self._tail_v = (tuple(req_ids[b] for b, _ in tails), tk, tv) if tails else ((), None, None)
+        for r, n in zip(reqs, n_accept):
+            r.length += n
+        self._epoch += 1
+        # the next step's attention plan while the host is ahead of the GPU, best effort, as append() makes it
+        st = self._plan_stream
+        if st is not None and self._arg_key is not None and self._arg_key[0][0] == tuple(req_ids) and self.scheme in FUSED:
+            from .speckv_ctypes import SpeckvError
+            try:
+                if not self.lib.stream_is_capturing(st.cuda_stream):
+                    self.plan_step(req_ids, st)
+                    key, robjs, _ = self._batch(req_ids)
+                    self._prepare_tails(req_ids, key, robjs, st)
+                else:
+                    self._arg_key = self._plan_stream = None
+            except SpeckvError as e:
+                self._arg_key = self._plan_stream = None
+                if e.status != -4:                             # SPECKV_ERR_INVAL: the stream cannot take the plan now; attend() plans again
+                    raise
+        return keep

@@ -86,6 +86,8 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_fp8_planned": [c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_int4_planned": [c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_fold_tail": [c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_fold_held": [c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
+                                    ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_int4": [c_uint64, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_mx4": [c_uint64, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_mx4_batch": [c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
@@ -107,6 +109,7 @@ _EXT_SIGNATURES = {
 
 
 EXT_ABI_VERSION = 6        # SPECKV_EXT_ABI_VERSION of include/speckv_ext.h
+HELD_MAX = 17              # SPECKV_HELD_MAX: positions speckv_ext_attend_fold_held takes per sequence (one left over + 16 new ones)
 
 
 def bind_ext(lib):
@@ -384,6 +387,14 @@ class SpeckvLib:
         """Fold the not-yet-stored position (fp16 K / V tails) into out / lse of rows d_rows (0 / None: all, in order)."""
         self._ext("speckv_ext_attend_fold_tail", n_rows, c_void_p(d_rows or 0), heads, g, c_void_p(d_q_f16), c_void_p(d_k_tail),
                   c_void_p(d_v_tail), tail_stride_elems, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse), c_void_p(stream or 0))
+
+    def attend_fold_held(self, n_rows, d_rows, heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems, d_base,
+                         d_n_q, sm_scale, d_out, d_lse, stream=None):
+        """Fold the positions held outside the pool causally into out / lse of rows d_rows (0 / None: all, in order): query position
+        j = row // rows_per_pos of sequence i sees held positions 0 .. d_base[i] + j; positions >= d_n_q[i] (0 / None: none) untouched."""
+        self._ext("speckv_ext_attend_fold_held", n_rows, c_void_p(d_rows or 0), heads, g, rows_per_pos, c_void_p(d_q_f16), c_void_p(d_k_held),
+                  c_void_p(d_v_held), seq_stride_elems, pos_stride_elems, c_void_p(d_base or 0), c_void_p(d_n_q or 0), ctypes.c_float(sm_scale),
+                  c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
 
     def attend_plan_bytes(self, n_seq):
         return int(self.lib.speckv_ext_attend_plan_bytes(n_seq))

@@ -455,6 +455,33 @@ speckv_status_t speckv_ext_attend_fold_tail(uint32_t n_rows, const uint32_t* d_r
                                             uint64_t tail_stride_elems, float sm_scale, float* d_out, float* d_lse,
                                             void* stream);
 
+/* speckv_ext_attend_fold_held: SEVERAL positions held outside the pool, folded causally -- the step of speculative decoding
+ * (verify n_q draft positions of a sequence at once), of chunked prefill and of batches whose members advance by different counts.
+ * The n_q query positions of a sequence ride through speckv_ext_attend_*_planned as g = n_q x rows_per_pos query rows per kv head
+ * (row r belongs to query position j = r / rows_per_pos; every query position sees every stored position, so that pass needs no
+ * mask); this entry then adds the fp16 K / V rows the caller still holds: d_base[i] positions in front of query position 0 (a
+ * connector's odd last position: 0 or 1) followed by the new positions.  Query position j of sequence i folds held positions
+ * 0 .. d_base[i] + j inclusive -- itself, not the drafts behind it -- each by the formula of speckv_ext_attend_fold_tail.
+ *   d_rows   : device array of n_rows sequence indices into d_q_f16 / d_out / d_lse, or NULL for 0..n_rows-1 (held rows, d_base and
+ *              d_n_q are indexed by i = 0..n_rows-1 either way)
+ *   d_q_f16  : [n_seq][heads][g][128] fp16     d_out : the same in fp32     d_lse : [n_seq][heads][g] fp32, required
+ *   g <= 16, a multiple of rows_per_pos;  n_q = g / rows_per_pos
+ *   d_k_held, d_v_held : fp16, position t of sequence i at i * seq_stride_elems + t * pos_stride_elems + head * 128 elements (offset
+ *              to the layer by the caller); both strides multiples of 8, pos_stride_elems >= heads * 128, seq_stride_elems >=
+ *              (n_q - 1) * pos_stride_elems + heads * 128
+ *   d_base   : device array [n_rows], d_base[i] + n_q <= SPECKV_HELD_MAX (the kernel reads no position past SPECKV_HELD_MAX - 1)
+ *   d_n_q    : device array [n_rows] of live query positions per sequence, or NULL = n_q for all; rows of the positions >= d_n_q[i]
+ *              are left exactly as they came in
+ * A row without stored positions (out = 0, lse = -inf) ends as the softmax attention over its visible held positions;
+ * d_base = 0 and n_q = 1 is speckv_ext_attend_fold_tail.  Bad arguments are SPECKV_ERR_INVAL before anything is launched.
+ * ONE launch for all sequences, heads, rows and positions, in place, nothing allocated, capturable. */
+#define SPECKV_HELD_MAX 17u              /* held positions per sequence: one left over + 16 new ones */
+speckv_status_t speckv_ext_attend_fold_held(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g,
+                                            uint32_t rows_per_pos, const void* d_q_f16, const void* d_k_held,
+                                            const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                                            const uint32_t* d_base, const uint32_t* d_n_q, float sm_scale, float* d_out,
+                                            float* d_lse, void* stream);
+
 /* ---- tier manager (CXLMemoryManager, cxl_memory_manager.h:40-90) ---------- */
 speckv_status_t speckv_ext_promote_to_l1(speckv_handle_t handle, uint64_t offset_bytes);
 speckv_status_t speckv_ext_demote_to_l3(speckv_handle_t handle, uint64_t offset_bytes);
