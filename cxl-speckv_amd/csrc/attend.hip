@@ -27,41 +27,16 @@
 #include "kernels.hpp"
 #include "tuning.hpp"
 #include "codec_device.hpp"          // the exact reciprocal divide of the codecs (div_by_scale and friends)
+#include "attend_device.hpp"
 #include <cstdlib>
 
 namespace speckv {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-__device__ __forceinline__ long pack64(uint32_t lo, uint32_t hi)
-{
-    return static_cast<long>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
-}
-// Record loads go through an explicit GLOBAL-address-space pointer.  A pointer the compiler cannot trace back to a kernel argument
-// (one that is assigned under a template condition, or read from a page-table entry) otherwise becomes a FLAT load: flat loads
-// count in lgkmcnt as well as vmcnt, the waits in front of the loop's scalar and LDS reads then drain every record load in
-// flight, and the compiler's own vmcnt(N) bookkeeping collapses to vmcnt(0) -- the linear FP8 kernel lost 15 % that way when
-// its pointers were initialised as nullptr for the striped instantiation (128 x 2k batch: 0.73 -> 0.62 of HBM peak).
-#ifdef SPECKV_ABL_FLAT_LDG      // (A/B only: the loads as they were, flat wherever the pointer's origin is not visible)
-#define SPECKV_GP(T, p) reinterpret_cast<const T*>(p)
-#else
-#define SPECKV_GP(T, p) ((const T __attribute__((address_space(1)))*)(reinterpret_cast<uintptr_t>(p)))
-#endif
-__device__ __forceinline__ uint4 ldg16(const uint8_t* p)
-{
-    typedef const u32x4 __attribute__((address_space(1)))* gp;
-    (void)sizeof(gp);
-    const u32x4 v = __builtin_nontemporal_load(SPECKV_GP(u32x4, p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
+// (global-address-space loads, SPECKV_GP: attend_device.hpp)
 __device__ __forceinline__ uint2 ldg8(const uint8_t* p)
 {
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     const u32x2 v = __builtin_nontemporal_load(SPECKV_GP(u32x2, p));
     return make_uint2(v.x, v.y);
 }
@@ -74,25 +49,6 @@ __device__ __forceinline__ f32x4 ldg_f4(const float* p)
 {
     typedef const f32x4 __attribute__((address_space(1)))* gp;
     return *(gp)(reinterpret_cast<uintptr_t>(p));
-}
-// max over the four lanes {c, c+16, c+32, c+48}
-__device__ __forceinline__ float max_over_kb(float v)
-{
-    // lane ^ 16 and lane ^ 32 through gfx950's row / half swaps (v_permlane16_swap / v_permlane32_swap: both operands the same
-    // register -> the two rows, then the two halves, side by side), not through the LDS crossbar (ds_bpermute)
-    const uint32_t u = __float_as_uint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const uint32_t m = __float_as_uint(fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1])));
-    const auto b = __builtin_amdgcn_permlane32_swap(m, m, false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float sum_over_kb(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const uint32_t m = __float_as_uint(__uint_as_float(a[0]) + __uint_as_float(a[1]));
-    const auto b = __builtin_amdgcn_permlane32_swap(m, m, false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 
 // Registers of one 32-position tile as loaded, and the per-wave running state.
@@ -779,34 +735,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
 namespace {
 constexpr uint32_t kFdBuf = 8320u, kFdV = 4096u, kFdS = 8192u;
 
-// a pointer that is the same in every lane, pinned to scalar registers (the LDS-DMA statements below take their base
-// address as an SGPR pair; a value loaded from a per-sequence descriptor is wave-uniform, but the compiler only proves
-// that while no store of the kernel could alias the descriptor)
-template <typename T> __device__ __forceinline__ T* uniform_ptr(T* p)
-{
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v)), hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-    return reinterpret_cast<T*>((static_cast<uint64_t>(hi) << 32) | lo);
-}
-__device__ __forceinline__ void fd_dma16(uint32_t lds_dst, const uint8_t* base, uint32_t voff)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_dst), "v"(voff), "s"(base) : "memory");
-}
-// the same with a full address per lane (TABLE form: every page of a tile may lie anywhere)
-__device__ __forceinline__ void fd_dma16v(uint32_t lds_dst, const uint8_t* addr)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_dst), "v"(addr) : "memory");
-}
-__device__ __forceinline__ void fd_dma4(uint32_t lds_dst, const uint8_t* base, uint32_t voff)      // active lanes only
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_dst), "v"(voff), "s"(base) : "memory");
-}
 // all but the 13 youngest DMAs have landed (V of this tile: 4, the next tile: 9): K operand of both blocks + the scales
 // (N: the TABLE form has a page-table load per tile in its queue: 14)
 template <int N = 13>
@@ -820,9 +748,8 @@ __device__ __forceinline__ void fd_take_k(uint32_t rd0, uint32_t rd1, uint32_t r
                  : "=&v"(k[0]), "=&v"(k[1]), "=&v"(k[2]), "=&v"(k[3]), "=&v"(ks), "=&v"(vs) : "v"(rd0), "v"(rd1), "v"(rs), "n"(N) : "memory");
 }
 // V of this tile has landed (younger: the next tile 9, K + scales of the one after 5)
-typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
 template <int N = 14>
-__device__ __forceinline__ void fd_take_v(const uint32_t (&rd)[4], u32x2v (&v)[8])
+__device__ __forceinline__ void fd_take_v(const uint32_t (&rd)[4], u32x2 (&v)[8])
 {
     static_assert(N == 14 || N == 16, "vmcnt immediate");
     asm volatile("s_waitcnt vmcnt(%12)\n\t"
@@ -972,16 +899,16 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
             const uint8_t* src = CLS ? ksrc_c : kreg + static_cast<uint64_t>(tc) * 32768u;
             const uint32_t dst = lbase + buf * kFdBuf;
 #pragma unroll
-            for (uint32_t i = 0; i < 4; ++i) fd_dma16(dst + 1024u * i, src, g[i]);
+            for (uint32_t i = 0; i < 4; ++i) dma16(dst + 1024u * i, src, g[i]);
             // one instruction for the 32 page scales of the tile: lanes 0..15 from the K table, 16..31 from the V table
             if (lane < 32u)
-                fd_dma4(dst + kFdS, CLS ? sc_base : reinterpret_cast<const uint8_t*>(a.scale_tab), CLS ? gsc_c : gsc + tc * 64u);
+                dma4(dst + kFdS, CLS ? sc_base : reinterpret_cast<const uint8_t*>(a.scale_tab), CLS ? gsc_c : gsc + tc * 64u);
         };
         auto issue_v = [&](uint32_t tt, uint32_t buf) {                     // (CLS: always the tile issue_k has just resolved)
             const uint8_t* src = CLS ? vsrc_c : vreg + static_cast<uint64_t>(min(tt, last)) * 32768u;
             const uint32_t dst = lbase + buf * kFdBuf + kFdV;
 #pragma unroll
-            for (uint32_t i = 0; i < 4; ++i) fd_dma16(dst + 1024u * i, src, g[i]);
+            for (uint32_t i = 0; i < 4; ++i) dma16(dst + 1024u * i, src, g[i]);
         };
         // ---- TABLE: entries two tiles ahead (lane l < 16: K page l of the tile, 16 .. 31: V page l - 16), the tile's DMAs one ahead
         const uint32_t kfirst = static_cast<uint32_t>(a.k_first + layer * a.layer_stride), vfirst = static_cast<uint32_t>(a.v_first + layer * a.layer_stride);
@@ -1022,8 +949,8 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
         auto issue_table = [&](const addr8& ad, uint32_t tt, uint32_t sbuf, uint32_t rg) __attribute__((always_inline)) {
             const uint32_t dst = lbase + sbuf * kFdBuf + (rg ? kFdV : 0u);
 #pragma unroll
-            for (uint32_t i = 0; i < 4u; ++i) fd_dma16v(__builtin_amdgcn_readfirstlane(dst + 1024u * i), ad[4u * rg + i]);
-            if (rg == 0u && lane < 32u) fd_dma4(__builtin_amdgcn_readfirstlane(lbase + sbuf * kFdBuf + kFdS), reinterpret_cast<const uint8_t*>(a.scale_tab), gsc + min(tt, last) * 64u);
+            for (uint32_t i = 0; i < 4u; ++i) dma16v(__builtin_amdgcn_readfirstlane(dst + 1024u * i), ad[4u * rg + i]);
+            if (rg == 0u && lane < 32u) dma4(__builtin_amdgcn_readfirstlane(lbase + sbuf * kFdBuf + kFdS), reinterpret_cast<const uint8_t*>(a.scale_tab), gsc + min(tt, last) * 64u);
         };
         // reader addresses inside buffer 0
         const uint32_t kslot = fd_row_slot(c), kx_ = fd_piece_xor(c);
@@ -1151,7 +1078,7 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
             const float fa = f * (vref * rinv);                            // acc: old max -> new max, old V reference -> new
             vref = vref_t;
             // ---- V pieces, then the next-but-one tile's V is requested into the buffer they came from
-            u32x2v vx[8];
+            u32x2 vx[8];
             const uint32_t rdvb[4] = {rdv[0] + bo, rdv[1] + bo, rdv[2] + bo, rdv[3] + bo};
             if (TABLE) { fd_take_v<16>(rdvb, vx); issue_table(tad, tile + 2u, buf, 1u); }
             else { fd_take_v(rdvb, vx); issue_v(tile + 2u, buf); }

@@ -26,13 +26,9 @@
 //   output O^T = V^T . P^T: rows c = d columns 8c + t, k-slots = the lane's 8 positions (as in
 //     attend.hip): the V tile goes through LDS and is read back as "8 nibbles of one position" dwords.
 #include "kernels.hpp"
+#include "attend_device.hpp"
 
 namespace speckv {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -40,40 +36,15 @@ namespace {
 // belongs to the neighbouring head = the neighbouring wave of this workgroup.  With non-temporal loads the line did not
 // stay in L2 for the partner: PMC showed 19.1 M L2 misses for 11.8 M distinct lines (1.6x the record bytes from HBM,
 // which then ran at 0.70 of its peak while the kernel delivered 0.43).  profiles/r02_int4_mem_pmc.json
-__device__ __forceinline__ uint4 ldg16(const uint8_t* p)
-{
-    // (explicit global address space: record pointers read from page-table entries would otherwise make FLAT loads, which
-    // count in lgkmcnt as well and serialise against every LDS wait -- attend.hip)
-    typedef const u32x4 __attribute__((address_space(1)))* gp;
-#ifdef SPECKV_INT4_NT_LOADS
-    const u32x4 v = __builtin_nontemporal_load((gp)(reinterpret_cast<uintptr_t>(p)));
+#ifdef SPECKV_INT4_NT_LOADS       // (A/B only)
+#define SPECKV_INT4_LDG16 ldg16
 #else
-    const u32x4 v = *(gp)(reinterpret_cast<uintptr_t>(p));
+#define SPECKV_INT4_LDG16 ldg16_temporal
 #endif
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
 template <typename T> __device__ __forceinline__ T ldg_small(const uint8_t* p)
 {
     typedef const T __attribute__((address_space(1)))* gp;
     return *(gp)(reinterpret_cast<uintptr_t>(p));
-}
-__device__ __forceinline__ float max_over_kb(float v)
-{
-    // lane ^ 16 and lane ^ 32 through gfx950's row / half swaps (v_permlane16_swap / v_permlane32_swap: both operands the same
-    // register -> the two rows, then the two halves, side by side), not through the LDS crossbar (ds_bpermute)
-    const uint32_t u = __float_as_uint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const uint32_t m = __float_as_uint(fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1])));
-    const auto b = __builtin_amdgcn_permlane32_swap(m, m, false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float sum_over_kb(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const uint32_t m = __float_as_uint(__uint_as_float(a[0]) + __uint_as_float(a[1]));
-    const auto b = __builtin_amdgcn_permlane32_swap(m, m, false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 __device__ __forceinline__ f16x2 as_h2(uint32_t u) { return __builtin_bit_cast(f16x2, u); }
 
@@ -266,23 +237,6 @@ constexpr uint32_t kWgHeads = 4;     // kv heads (= waves) per workgroup of k_at
 namespace {
 constexpr uint32_t kWgBuf = 20480u, kWgV = 8192u, kWgKs = 16384u, kWgVs = 18432u;
 
-// one LDS-DMA: lane l's 16 bytes at base + voff land at lds_dst + 16 l.  M0 (the destination) belongs to the compiler:
-// saved and restored inside the statement.
-__device__ __forceinline__ void dma16(uint32_t lds_dst, const uint8_t* base, uint32_t voff)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_dst), "v"(voff), "s"(base) : "memory");
-}
-
-// the same with a full 64-bit address per lane (striped form: a lane's rows may sit in any pool's run)
-__device__ __forceinline__ void dma16v(uint32_t lds_dst, const uint8_t* addr)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_dst), "v"(addr) : "memory");
-}
-
 // this wave's 5 DMAs of the current tile have landed (the 5 of the next tile may still be in flight); then everybody's
 // (SPECKV_ABL_* macros: timing-only ablation builds, results are garbage -- profiles/tools/int4_ablate.sh)
 #ifdef SPECKV_ABL_NO_BARRIER
@@ -461,8 +415,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SPECKV_INT4
             uint4 A[5], B[5], sink = make_uint4(0u, 0u, 0u, 0u);
             auto ld = [&](uint4 (&r)[5], uint32_t tt) {
                 const uint64_t to = static_cast<uint64_t>(tt < last ? tt : last) * tile_bytes;
-                r[0] = ldg16(kreg + to + gr0); r[1] = ldg16(kreg + to + gr1); r[2] = ldg16(vreg + to + gr0);
-                r[3] = ldg16(vreg + to + gr1); r[4] = ldg16(sreg + to + gs);
+                r[0] = SPECKV_INT4_LDG16(kreg + to + gr0); r[1] = SPECKV_INT4_LDG16(kreg + to + gr1); r[2] = SPECKV_INT4_LDG16(vreg + to + gr0);
+                r[3] = SPECKV_INT4_LDG16(vreg + to + gr1); r[4] = SPECKV_INT4_LDG16(sreg + to + gs);
             };
             auto eat = [&](const uint4 (&r)[5]) {
 #pragma unroll
@@ -671,12 +625,6 @@ __device__ __forceinline__ void w8_take_v(const uint32_t (&rd)[4], uint32_t rs, 
 #ifndef SPECKV_INT4_W8_WAVES
 #define SPECKV_INT4_W8_WAVES 4
 #endif
-__device__ __forceinline__ const uint8_t* w8_uniform_ptr(const uint8_t* p)
-{
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v)), hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-    return reinterpret_cast<const uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo);
-}
 // HALVES = 2 (fixed-grid and batch launches): 16 waves, the workgroup's run of tiles cut in two, waves 8..15 take the second
 // half with LDS stages of their own; at the end their (m, l, accumulators) cross over through LDS and waves 0..7 store the
 // merged result -- a row that fits one workgroup needs no partials and no merge launch, and a batch of 256 sequences fills
@@ -793,8 +741,8 @@ __global__ __launch_bounds__(512 * HALVES) __attribute__((amdgpu_waves_per_eu(SP
             uint32_t cnt = jq + (cls < jr ? 1u : 0u);
             if (cnt == 0u) { cls = 0u; cnt = 1u; }                        // (fewer pages than runs: an empty class fetches the range's first record, all masked)
             const uint32_t pk = kpage0 + cls, rk = pk / cls_n, pv = vpage0 + cls, rv = pv / cls_n;
-            cls_k0 = w8_uniform_ptr(reinterpret_cast<const uint8_t*>(s_bases[pk - rk * cls_n]) + static_cast<uint64_t>(rk) * kInt4RecBytes);
-            cls_v0 = w8_uniform_ptr(reinterpret_cast<const uint8_t*>(s_bases[pv - rv * cls_n]) + static_cast<uint64_t>(rv) * kInt4RecBytes);
+            cls_k0 = uniform_ptr(reinterpret_cast<const uint8_t*>(s_bases[pk - rk * cls_n]) + static_cast<uint64_t>(rk) * kInt4RecBytes);
+            cls_v0 = uniform_ptr(reinterpret_cast<const uint8_t*>(s_bases[pv - rv * cls_n]) + static_cast<uint64_t>(rv) * kInt4RecBytes);
             cls_last_tile = __builtin_amdgcn_readfirstlane((cnt - 1u) >> 4);
         };
         if (CLS) cls_enter();
@@ -813,8 +761,8 @@ __global__ __launch_bounds__(512 * HALVES) __attribute__((amdgpu_waves_per_eu(SP
             const uint32_t dst = lbase + stage_off;
             if (CLS) {                                                   // the tile's bases from its (class, tile of the class); wave-uniform
                 const uint64_t toff = static_cast<uint64_t>(min(iq_m, cls_last_tile)) * tile_bytes;      // (a tile past the class's end: its last one again, all masked)
-                kptr = w8_uniform_ptr(cls_k0 + toff);
-                vptr = w8_uniform_ptr(cls_v0 + toff);
+                kptr = uniform_ptr(cls_k0 + toff);
+                vptr = uniform_ptr(cls_v0 + toff);
                 if (++iq_m == cls_m) {
                     iq_m = 0u;
                     if (++iq_cls == cls_n && stream) {                    // (stream form: on into the next layer's regions)

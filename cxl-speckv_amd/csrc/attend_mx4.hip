@@ -35,6 +35,7 @@
 // 32-position tile of its two heads 4 for K, 4 for V, 1 + 1 for the codes -- 10 instructions for 8704 bytes -- two tiles deep per
 // wave; the operands are then read from LDS.  All vector-memory traffic of the loop is inline assembly with explicit counters.
 #include "kernels.hpp"
+#include "attend_device.hpp"
 #include <atomic>
 #include <type_traits>
 
@@ -44,16 +45,10 @@
 
 namespace speckv {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 
 namespace {
 
-#define MX_GP(T, p) ((const T __attribute__((address_space(1)))*)(reinterpret_cast<uintptr_t>(p)))
 // Records in the pool are tile-planar (kernels.hpp): 16 records of a run = 16 nibble rows (1024 B each) + 16 code rows (64 B each)
 // = 136 whole cache lines.  A 16-page tile of the kernel that starts at record R of its run reads rows R .. R+15; with R a multiple
 // of 16 (every tile-aligned range of a layout whose regions are multiples of 16 pages) that is ONE storage tile: the ten 1 KiB
@@ -70,38 +65,6 @@ constexpr uint32_t kStK = 0, kStV = 4096, kStKC = 8192, kStVC = 8448, kStage = 8
 constexpr uint32_t kStagesDefault = MX4_STAGES;              // tiles a wave keeps in LDS: the one it works on and kStages - 1 on their way
 constexpr uint32_t kTabEnt = 2u * 512u;                      // page-table form: the 32 entries (16 K pages, 16 V pages) of a tile, for the two tiles ahead
 
-template <typename T> __device__ __forceinline__ T* uniform_ptr(T* p)
-{
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v)), hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-    return reinterpret_cast<T*>((static_cast<uint64_t>(hi) << 32) | lo);
-}
-// LDS-DMA: 16 (4) bytes per lane from base + voff to LDS address lds_dst + 16 (4) * lane
-__device__ __forceinline__ void dma16(uint32_t lds_dst, const uint8_t* base, uint32_t voff)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3 nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_dst), "v"(voff), "s"(base) : "memory");
-}
-__device__ __forceinline__ void dma4(uint32_t lds_dst, const uint8_t* base, uint32_t voff)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, %3 nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_dst), "v"(voff), "s"(base) : "memory");
-}
-// the same with a full address per lane (page-table form: every row of a tile may lie anywhere)
-__device__ __forceinline__ void dma16v(uint32_t lds_dst, const uint8_t* addr)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_dst), "v"(addr) : "memory");
-}
-__device__ __forceinline__ void dma4v(uint32_t lds_dst, const uint8_t* addr)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_dst), "v"(addr) : "memory");
-}
 // a region's share of a tile in one statement: four 1 KiB pieces of rows + the codes; M0 saved and restored once
 __device__ __forceinline__ void dma_region(uint32_t lds_rows, uint32_t lds_codes, const uint8_t* base, const uint32_t (&goff)[4], uint32_t goffc)
 {
@@ -114,22 +77,6 @@ __device__ __forceinline__ void dma_region(uint32_t lds_rows, uint32_t lds_codes
                  "s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %7, %8" MX4_CODES_POLICY "\n\t"
                  "s_mov_b32 m0, %0"
                  : "=&s"(keep) : "s"(lds_rows), "s"(lds_codes), "v"(goff[0]), "v"(goff[1]), "v"(goff[2]), "v"(goff[3]), "v"(goffc), "s"(base) : "memory", "scc");
-}
-__device__ __forceinline__ float max_over_kb(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const uint32_t m = __float_as_uint(fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1])));
-    const auto b = __builtin_amdgcn_permlane32_swap(m, m, false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float sum_over_kb(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const uint32_t m = __float_as_uint(__uint_as_float(a[0]) + __uint_as_float(a[1]));
-    const auto b = __builtin_amdgcn_permlane32_swap(m, m, false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 template <uint32_t N> __device__ __forceinline__ void wait_all_but()
 {
@@ -392,8 +339,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg * HALVES) __attribute__((amdgpu_wa
             //  Rolled over the two regions: the kernel sits near the 256 registers of two waves per SIMD.)
 #pragma unroll 1
             for (uint32_t rg = 0; rg < 2u; ++rg) {
-                typedef uint32_t u32x2e __attribute__((ext_vector_type(2)));
-                u32x2e ra[4];
+                u32x2 ra[4];
                 u32x4 ec;
                 const uint32_t eaddr = ebase + (rg * 16u + srow) * 16u, caddr = ebase + (rg * 16u + (lane >> 2)) * 16u;
                 asm volatile("ds_read_b64 %0, %5\n\tds_read_b64 %1, %5 offset:64\n\tds_read_b64 %2, %5 offset:128\n\tds_read_b64 %3, %5 offset:192\n\t"
@@ -402,7 +348,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg * HALVES) __attribute__((amdgpu_wa
 #pragma unroll
                 for (uint32_t i = 0; i < 4u; ++i) {
                     const uint8_t* r = reinterpret_cast<const uint8_t*>(static_cast<uint64_t>(ra[i].x) | (static_cast<uint64_t>(ra[i].y) << 32));
-                    dma16v(dst + (rg ? kStV : kStK) + 1024u * i, r + h0 * 128u + ((sslot ^ ((4u * i + srow) & 15u)) * 16u));
+                    dma16v_nt(dst + (rg ? kStV : kStK) + 1024u * i, r + h0 * 128u + ((sslot ^ ((4u * i + srow) & 15u)) * 16u));
                 }
                 const uint8_t* rc = reinterpret_cast<const uint8_t*>(static_cast<uint64_t>(ec.x) | (static_cast<uint64_t>(ec.y) << 32));
                 dma4v(dst + (rg ? kStVC : kStKC), rc + ec.z + h0 * 8u + (lane & 3u) * 4u);
@@ -506,7 +452,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg * HALVES) __attribute__((amdgpu_wa
                 uint32_t code[4];
 #pragma unroll
                 for (int gq = 0; gq < 4; ++gq) {
-                    const u32x4 wv = *MX_GP(u32x4, qrow + 8u * kb + 32u * gq);
+                    const u32x4 wv = *SPECKV_GP(u32x4, qrow + 8u * kb + 32u * gq);
                     const uint32_t ws[4] = {wv.x, wv.y, wv.z, wv.w};
                     float amax = 0.0f;
 #pragma unroll
@@ -559,8 +505,8 @@ __global__ __launch_bounds__(64 * kWavesPerWg * HALVES) __attribute__((amdgpu_wa
                 float dot = 0.0f;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const u32x4 qw = *MX_GP(u32x4, qp + 8 * j), kw = *MX_GP(u32x4, a.tail_k + trow + 8 * j);
-                    tail_v[hh][j] = *MX_GP(u32x4, a.tail_v + trow + 8 * j);
+                    const u32x4 qw = *SPECKV_GP(u32x4, qp + 8 * j), kw = *SPECKV_GP(u32x4, a.tail_k + trow + 8 * j);
+                    tail_v[hh][j] = *SPECKV_GP(u32x4, a.tail_v + trow + 8 * j);
                     const uint32_t qq[4] = {qw.x, qw.y, qw.z, qw.w}, kk[4] = {kw.x, kw.y, kw.z, kw.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {

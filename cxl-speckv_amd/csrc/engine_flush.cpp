@@ -231,7 +231,7 @@ int Engine::prefetch_flush(uint32_t* n_issued)
 }
 
 // One run of the device-side flush pipeline for requests of allocations that share a compression scheme:
-// upload the requests, candidates -> dedupe -> ring assignment -> compaction (kernels.hip), then ONE fetch launch
+// upload the requests, candidates -> dedupe -> ring assignment -> compaction (flush_kernels.inl), then ONE fetch launch
 // that reads its block count and first slot from device memory.  Nothing comes back to the host but 16 bytes
 // (FlushResult, written to pinned memory by the assign kernel), read when somebody needs them.
 // The request columns of a flush go to the device through a copy KERNEL on the flush's stream: on an idle stream a copy

@@ -1,5 +1,10 @@
 // cxl-speckv_amd/csrc/kernels.hip -- hand-written CDNA4 (gfx950) kernels of the
-// KV hot path: block compress, fetch + decompress, prefetch lookup, verify.
+// KV hot path.  This file: the block codec (k_fetch_decompress*, k_compress), its launch shape (num_cus, codec_grid) and
+// launchers (launch_decompress, launch_compress).  The other subjects of the translation unit are included below the codec:
+//   flush_kernels.inl        prefetch lookup, device-side prefetch flush, verify
+//   page_table_kernels.inl   page-table upkeep
+//   qk_scores_kernels.inl    query quantisation and q.K^T over FP8 records (stand-alone forms)
+//   predictor_kernels.inl    the token predictor
 //
 // What they replace in the reference (paths under /root/reference):
 //   FPGACacheEngine::compress / ::decompress   src/fpga_engine/cache_engine.cpp:40-116,172-284
@@ -24,6 +29,7 @@
 #include "ring_rule.hpp"
 #include "codec_device.hpp"
 #include "encode_device.hpp"
+#include "attend_device.hpp"         // u32x4, u32x2; f32x4 and pack64 of qk_scores_kernels.inl
 
 #include <hip/hip_fp16.h>
 
@@ -51,7 +57,6 @@ constexpr int kEncLdsHalves = 2064;        // per wave: 4128 B (see kEncWaveByte
 #if !defined(SPECKV_PLAIN_STORE)
 #define SPECKV_NT_STORE 1
 #endif
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // Records and block images are reached through pointers read from page-table entries / pointer lists, which the compiler cannot
 // trace back to a kernel argument: plain C++ dereferences of them become FLAT loads and stores (an address-space check per
 // access, and every one counts in lgkmcnt as well as vmcnt, so the waits in front of LDS and scalar reads wait for them too).
@@ -97,7 +102,6 @@ __device__ __forceinline__ void st16(uint8_t* p, uint4 v)
 // The compress direction streams too: every source byte is read once, every record byte written once (the fp16 "compress"
 // is a plain copy and ran at 0.65-0.67 of HBM peak with temporal accesses against 0.77 for the same copy in the decode
 // direction; -DSPECKV_ENC_PLAIN restores them for the A/B).
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint4 enc_ld16(const uint8_t* p)
 {
 #if defined(SPECKV_ENC_PLAIN)
@@ -1321,1108 +1325,25 @@ __global__ __launch_bounds__(kThreads) void k_compress(CodecArgs a)
     }
 }
 
-// ===================================================================
-// prefetch lookup  (prefetch_core.v:150-241 ; speckv_allocator.cpp:105-113)
-// ===================================================================
-// 32 lanes per request: lane c -> kind = c>>4, position cur_pos + (c&15) + 1.
-// Pages of a position = pages covering its [head 0 .. head H-1] row in the
-// shim layout; a lane emits only pages its predecessor lane did not cover.
-struct Cand { uint32_t lo, hi; };   // half-open range of NEW pages of this lane (before residency filter)
-
-__device__ __forceinline__ Cand candidate(const Layout& lay, uint32_t req, uint32_t layer,
-                                          uint32_t pos, uint32_t depth, uint32_t c)
-{
-    Cand r{0u, 0u};
-    const uint32_t kind = c >> 4, i = (c & 15u) + 1u;
-    const uint64_t p = static_cast<uint64_t>(pos) + i;
-    if (i > depth || p >= lay.num_tokens) return r;
-    const uint64_t entry = static_cast<uint64_t>(lay.head_dim) * lay.bytes_per_element;
-    const uint64_t row = entry * lay.num_heads;
-    if (row == 0) return r;
-    // vllm_speckv_backend.py:95-100 with head = 0
-    const uint64_t off = ((((static_cast<uint64_t>(req) * lay.num_layers + layer) * 2 + kind)
-                           * lay.num_tokens + p) * lay.num_heads) * entry;
-    uint64_t pg0 = off / kPageSize;
-    const uint64_t pg1 = (off + row - 1) / kPageSize;
-    if (i > 1) {                       // predecessor position p-1 covered up to:
-        const uint64_t prev_pg1 = (off - 1) / kPageSize;   // (off - row + row - 1)
-        if (pg0 <= prev_pg1) pg0 = prev_pg1 + 1;
-    }
-    uint64_t hi = pg1 + 1;
-    if (hi > lay.alloc_pages) hi = lay.alloc_pages;
-    if (pg0 >= hi) return r;
-    r.lo = static_cast<uint32_t>(pg0);
-    r.hi = static_cast<uint32_t>(hi);
-    return r;
-}
-
-template <bool WRITE>
-__global__ __launch_bounds__(256) void k_prefetch_lookup(Layout lay, uint32_t n,
-        const uint32_t* __restrict__ req, const uint32_t* __restrict__ layer,
-        const uint32_t* __restrict__ pos, const uint32_t* __restrict__ depth,
-        const uint32_t* __restrict__ flags, uint32_t* __restrict__ wave_tot,
-        const uint32_t* __restrict__ wave_base, uint32_t* __restrict__ out, uint32_t cap)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;   // global wave = 2 requests
-    const uint32_t r = 2u * gw + (lane >> 5);
-    uint32_t cnt = 0;
-    Cand cd{0u, 0u};
-    const bool live_wave = 2u * gw < n;
-    if (r < n) {
-        uint32_t dk = depth[r];
-        if (dk > 16u) dk = 16u;
-        cd = candidate(lay, req[r], layer[r], pos[r], dk, lane & 31u);
-        for (uint32_t pg = cd.lo; pg < cd.hi; ++pg)
-            cnt += (flags && (flags[pg] & 3u)) ? 0u : 1u;
-    }
-    const uint32_t incl = wave_incl_add(cnt);
-    if (!WRITE) {
-        if (lane == 63u && live_wave) wave_tot[gw] = incl;
-    } else {
-        uint32_t w = (live_wave ? wave_base[gw] : 0u) + incl - cnt;
-        for (uint32_t pg = cd.lo; pg < cd.hi; ++pg)
-            if (!(flags && (flags[pg] & 3u))) {
-                if (w < cap) out[w] = pg;
-                ++w;
-            }
-    }
-}
-
-// single-workgroup exclusive scan of the per-wave totals (n_w is small:
-// requests/2); total is clamped to cap.
-__global__ __launch_bounds__(1024) void k_scan_totals(const uint32_t* __restrict__ tot,
-        uint32_t* __restrict__ base, uint32_t n_w, uint32_t* __restrict__ count, uint32_t cap)
-{
-    __shared__ uint32_t wsum[16];
-    __shared__ uint32_t running;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) running = 0;
-    __syncthreads();
-    for (uint32_t i0 = 0; i0 < n_w; i0 += 1024u) {
-        const uint32_t i = i0 + threadIdx.x;
-        const uint32_t v = (i < n_w) ? tot[i] : 0u;
-        const uint32_t incl = wave_incl_add(v);
-        if (lane == 63u) wsum[wave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (uint32_t w = 0; w < wave; ++w) wbase += wsum[w];
-        const uint32_t run = running;
-        if (i < n_w) base[i] = run + wbase + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023u) running = run + wbase + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = running < cap ? running : cap;
-}
+} // namespace
 
 // ===================================================================
-// device-side prefetch flush  (prefetch_core.v:150-241: the whole loop without the host)
+// the other subjects of this translation unit, each in a file of its own, in the order in which their text stood here
 // ===================================================================
-// Candidate words live at a fixed stride: request r, lane c (kind, look-ahead step), word t -> index
-// (r*32 + c)*W + t, kNoSlot when unused.  Request order = index order, so "first occurrence" of a page is the
-// smallest index naming it: every valid candidate does atomicMax(stamp[page], key(index)) with
-// key = epoch<<24 | (0xFFFFFF - index); the candidate whose key survives is the one kept.  Stamps of older
-// flushes carry an older epoch and lose against any key of this one (the host clears them when the 8-bit epoch wraps).
-__device__ __forceinline__ uint32_t flush_key(uint32_t epoch, uint32_t index) { return (epoch << 24) | (0xFFFFFFu - index); }
+// The compiler emits the kernels of a translation unit in the order of their definitions -- the instances of a kernel template in
+// the order in which the launchers first name them -- and k_fetch_decompress calls decode_rle_general pc-relatively across all of
+// them.  The headline kernel is pinned by the hash of its instructions (tests/test_build_guards.py), that call's literal
+// included, so these sections are cut out of the file, not out of the translation unit, and nothing below changes its order.
+#include "flush_kernels.inl"
+#include "page_table_kernels.inl"
+#include "qk_scores_kernels.inl"
+#include "predictor_kernels.inl"
 
-__device__ __forceinline__ void flush_candidates_of(const FlushArgs& a, uint32_t gt)      // gt: one thread per (request, lane)
-{
-    const uint32_t r = gt >> 5, c = gt & 31u;
-    if (r >= a.n) return;
-    const uint32_t row = a.row[r];
-    Cand cd{0u, 0u};
-    DevAlloc t{};
-    if (row != kNoSlot) {
-        t = a.tab[row];
-        if (t.entries) {
-            uint32_t dk = a.depth[r];
-            if (dk > 16u) dk = 16u;
-            cd = candidate(t.layout, a.req[r], a.layer[r], a.pos[r], dk, c);
-        }
-    }
-    const uint32_t base = gt * a.W;
-    for (uint32_t w = 0; w < a.W; ++w) {
-        uint32_t pg = kNoSlot;
-        if (cd.lo + w < cd.hi && !(t.d_flags[cd.lo + w] & 3u)) {
-            pg = cd.lo + w;
-            atomicMax(&t.stamp[pg], flush_key(a.epoch, base + w));
-        }
-        a.cand[base + w] = pg;
-    }
-}
-__global__ __launch_bounds__(256) void k_flush_candidates(FlushArgs a) { flush_candidates_of(a, blockIdx.x * blockDim.x + threadIdx.x); }
+namespace {
 
-// candidate word i names page `pg` of allocation row `row` and is the first occurrence of that page in the flush
-__device__ __forceinline__ bool flush_keeps(const FlushArgs& a, uint32_t i, uint32_t total, uint32_t& pg, uint32_t& row)
-{
-    pg = kNoSlot; row = kNoSlot;
-    if (i >= total) return false;
-    pg = a.cand[i];
-    if (pg == kNoSlot) return false;
-    row = a.row[i / (32u * a.W)];
-    return a.tab[row].stamp[pg] == flush_key(a.epoch, i);
-}
-// Entry `rank` of the flush lands in ring slot base + rank.  Everything about it that is pointer chasing --
-// its record descriptor, the slot's previous owner and that owner's residency words, the new owner, the
-// page's slot words on both sides -- is done here, one THREAD per page, so that the fetch launch is the plain
-// list form (descriptor + destination per block) at the bulk kernel's occupancy.  Done by the fetch kernel
-// itself, one WAVE per page with a chain of ~8 dependent loads each, the 122 880-page flush of a 256-sequence
-// decode step spent 210 us in the fetch; the chain now runs 64 pages per wave.
-// (The words are final before the data has landed: the host waits for the flight's `done` event before it
-// trusts a page whose slot lies in the flight's run, Engine::wait_landed.)
-__device__ __forceinline__ void flush_place(const FlushArgs& a, const FlushResult& res, uint32_t rank, uint32_t row, uint32_t pg)
-{
-    const uint32_t slot = res.base + rank;
-    const DevAlloc t = a.tab[row];
-    a.final_entry[rank] = t.entries[pg];
-    a.final_dst[rank] = reinterpret_cast<uint64_t>(a.ring_base + static_cast<uint64_t>(slot) * kPageSize);
-    const uint64_t prev = a.ring_owner[slot];
-    const uint64_t me = (static_cast<uint64_t>(row) << 32) | pg;
-    if (prev != kNoOwner && prev != me) {
-        const DevAlloc tp = a.tab[prev >> 32];
-        const uint32_t pp = static_cast<uint32_t>(prev);
-        // the row may have been recycled for a smaller allocation since the slot was filled
-        if (tp.entries && pp < tp.layout.alloc_pages && tp.d_slot[pp] == slot)    // still pointing here: the page leaves L2
-            atomicAnd(&tp.d_flags[pp], ~2u);
-    }
-    a.ring_owner[slot] = me;
-    t.d_slot[pg] = slot;
-    if (a.final_host) a.final_host[rank] = &t.h_slot[pg];     // stored by the fetch launch (CodecArgs::host_words)
-    else t.h_slot[pg] = res.seq + rank;                       // the page's only host-visible word (Engine::l2_live)
-    atomicOr(&t.d_flags[pg], 2u);
-}
-// the ring run of a flush that keeps `total` candidates: [base, base+m), a run never wraps (as Engine::take_l2_run on the
-// host: same rule, so host and device agree on the hand).  *a.hand is the ring's sequence number: slot = seq % n_l2; the
-// slots a run skips at the end of a lap count.
-__device__ __forceinline__ FlushResult flush_take(const FlushArgs& a, uint32_t total)
-{
-    const uint32_t m = total < a.max_take ? total : a.max_take;
-    const RingRun run = ring_take(*a.hand, m, a.n_l2);
-    if (m) *a.hand = run.next;
-    const FlushResult r{m, run.slot, total, run.seq};
-    *a.result_dev = r;
-    *a.result_host = r;
-    return r;
-}
-
-// keep[i] = candidate i is the first occurrence of its page; WRITE = false: totals per workgroup (256 candidates: the
-// single-workgroup scan of k_flush_assign is 4x shorter than over per-wave totals), true: ordered scatter (rank = the
-// workgroup's base from k_flush_assign + the kept candidates before this one in it)
-template <bool WRITE>
-__global__ __launch_bounds__(256) void k_flush_mark(FlushArgs a, const FlushResult* __restrict__ res)
-{
-    __shared__ uint32_t wcount[4];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t total = a.n * 32u * a.W;
-    uint32_t pg, row;
-    const bool keep = flush_keeps(a, i, total, pg, row);
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0u) wcount[wave] = static_cast<uint32_t>(__popcll(mask));
-    __syncthreads();
-    if (!WRITE) {
-        if (threadIdx.x == 0u) a.wave_tot[blockIdx.x] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
-    } else if (keep) {
-        uint32_t before = 0;
-        for (uint32_t w = 0; w < wave; ++w) before += wcount[w];
-        const uint32_t n_b = (total + 255u) >> 8;
-        const uint32_t rank = a.wave_tot[n_b + blockIdx.x] + before + static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1ull)));
-        if (rank < res->m) flush_place(a, *res, rank, row, pg);
-    }
-}
-
-// one workgroup: exclusive scan of the wave totals, then the ring run [base, base+m) (a run never wraps, as
-// Engine::take_l2_run on the host: same rule, so host and device agree on the hand)
-__global__ __launch_bounds__(1024) void k_flush_assign(FlushArgs a)
-{
-    __shared__ uint32_t wsum[16];
-    __shared__ uint32_t running;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t n_w = (a.n * 32u * a.W + 255u) >> 8;       // totals per workgroup of k_flush_mark
-    if (threadIdx.x == 0) running = 0;
-    __syncthreads();
-    for (uint32_t i0 = 0; i0 < n_w; i0 += 1024u) {
-        const uint32_t i = i0 + threadIdx.x;
-        const uint32_t v = (i < n_w) ? a.wave_tot[i] : 0u;
-        const uint32_t incl = wave_incl_add(v);
-        if (lane == 63u) wsum[wave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (uint32_t w = 0; w < wave; ++w) wbase += wsum[w];
-        const uint32_t run = running;
-        if (i < n_w) a.wave_tot[n_w + i] = run + wbase + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023u) running = run + wbase + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) (void)flush_take(a, running);
-}
-
-// The whole pipeline in ONE workgroup for small flushes (the reference's own call pattern: speckv_prefetch per request and
-// layer, flushed every num_layers requests -- 32 requests x 32 lanes x 2 words for an 8B-shaped model):
-// four launches and their three hand-overs become phases between barriers; the kept flags stay in a register (one bit per
-// pass of 1024 words), the counts per (pass, wave) in LDS.  Same arithmetic, same order of entries.
-constexpr uint32_t kFlushSmallPasses = 16, kFlushSmallWords = kFlushSmallPasses * 1024u;
-// measured on the MI355X (time until the pages have landed, W = 2): 4 .. 64 requests 38-42 us against 42-43 us for the four
-// launches, 80 requests 54 against 45 (one workgroup then chases the pointers of ~500 pages alone); the host's submit time is
-// 11-14 us against 19-23.  SPECKV_FLUSH_SMALL_WORDS moves the limit, SPECKV_FLUSH_NO_SMALL=1 removes the path.
-// (Letting this kernel pull the request columns from the host's pinned slot itself, instead of the upload launch in front of
-// it, saved the host another 2.5 us per flush and cost 4-5 us until landed, same box: 41.5-47 against 37.2-41.9.  Not kept.)
-constexpr uint64_t kFlushSmallDefault = 4096;
-__global__ __launch_bounds__(1024) void k_flush_small(FlushArgs a)
-{
-    __shared__ uint32_t wcnt[kFlushSmallPasses * 16u];      // kept candidates of (pass, wave) -> kept candidates before it
-    __shared__ uint32_t s_part[4];
-    __shared__ FlushResult s_res;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t total = a.n * 32u * a.W, passes = (total + 1023u) >> 10;
-    for (uint32_t gt = tid; gt < a.n * 32u; gt += 1024u) flush_candidates_of(a, gt);
-    __threadfence();                                        // the stamps' atomicMax and the candidate words are out
-    __syncthreads();
-    uint32_t keepbits = 0;
-    for (uint32_t j = 0; j < passes; ++j) {
-        uint32_t pg, row;
-        const bool keep = flush_keeps(a, j * 1024u + tid, total, pg, row);
-        const unsigned long long mask = __ballot(keep);
-        if (lane == 0u) wcnt[j * 16u + wave] = static_cast<uint32_t>(__popcll(mask));
-        keepbits |= (keep ? 1u : 0u) << j;
-    }
-    for (uint32_t e = passes * 16u + tid; e < kFlushSmallPasses * 16u; e += 1024u) wcnt[e] = 0u;
-    __syncthreads();
-    {   // exclusive scan of the 256 counts (entry order = candidate order) by the first four waves
-        uint32_t v = 0, incl = 0;
-        if (tid < 256u) { v = wcnt[tid]; incl = wave_incl_add(v); if (lane == 63u) s_part[wave] = incl; }
-        __syncthreads();
-        if (tid < 256u) {
-            uint32_t before = 0;
-            for (uint32_t w = 0; w < wave; ++w) before += s_part[w];
-            wcnt[tid] = before + incl - v;
-        }
-        if (tid == 0u) s_res = flush_take(a, s_part[0] + s_part[1] + s_part[2] + s_part[3]);
-        __syncthreads();
-    }
-    const FlushResult res = s_res;
-    for (uint32_t j = 0; j < passes; ++j) {
-        const bool keep = (keepbits >> j) & 1u;
-        const unsigned long long mask = __ballot(keep);
-        if (keep) {
-            const uint32_t i = j * 1024u + tid;
-            const uint32_t rank = wcnt[j * 16u + wave] + static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1ull)));
-            if (rank < res.m) flush_place(a, res, rank, a.row[i / (32u * a.W)], a.cand[i]);
-        }
-    }
-}
-
-// ===================================================================
-// verify  (speculative_prefetcher.cpp:84-96): hit[r] = actual[r] in predicted[r][0..k)
-// ===================================================================
-// One request per lane; the 64-bit __ballot of the per-lane result is the
-// wave's verify mask (its popcount feeds the hit counter).  A wave owns 64
-// consecutive bytes of hit[] and a workgroup 256, so no two workgroups ever
-// write into the same 128-byte line: the earlier layout (16 lanes per request,
-// 4 result bytes per wave) let eight workgroups on eight XCDs share one line and
-// showed rare wrong bytes on MI355X (tests/test_gpu_engine.py::test_verify_batch_kernel).
-__global__ __launch_bounds__(256) void k_verify(uint32_t n, uint32_t k,
-        const int32_t* __restrict__ actual, const int32_t* __restrict__ predicted,
-        uint8_t* __restrict__ hit, uint32_t* __restrict__ hit_count)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    bool h = false;
-    if (r < n) {
-        const int32_t a = actual[r];
-        const int32_t* p = predicted + static_cast<uint64_t>(r) * k;
-        for (uint32_t j = 0; j < k; ++j) h = h || (p[j] == a);
-        hit[r] = h ? 1 : 0;
-    }
-    const unsigned long long mask = __ballot(h);              // 64-bit verify mask of this wave
-    if (lane == 0u && mask) atomicAdd(hit_count, static_cast<uint32_t>(__popcll(mask)));
-}
-
-__global__ void k_apply_updates(const DevAlloc* __restrict__ tab, const MirrorUpdate* __restrict__ up, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const MirrorUpdate u = up[i];
-    const DevAlloc t = tab[u.alloc_idx];
-    if (!t.entries) return;
-    if (u.and_mask != 0xFFFFFFFFu) atomicAnd(&t.d_flags[u.page], u.and_mask);
-    if (u.or_mask) atomicOr(&t.d_flags[u.page], u.or_mask);
-    if (u.slot != kKeepSlot) t.d_slot[u.page] = u.slot;
-}
-
-__global__ void k_init_entries(PageEntry* e, uint64_t n, uint64_t base, uint64_t stride, uint64_t rec0)
-{
-    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (stride == kPlanarMx4) { e[i].pool_addr = base + mx4_nib_off(rec0 + i); e[i].rec_bytes = 0; e[i].scale = __uint_as_float(mx4_code_delta(rec0 + i)); }
-    else { e[i].pool_addr = base + i * stride; e[i].rec_bytes = 0; e[i].scale = 1.0f; }
-}
-
-// ===================================================================
-// fused dequant-matvec (BASELINE config 5): q.K^T from FP8 records on the matrix cores
-// ===================================================================
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ long pack64(uint32_t lo, uint32_t hi)
-{
-    return static_cast<long>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
-}
-
-// per query row: scale = max|q|/448 (1 if zero), e4m3 bytes of clamp(q/scale); rows >= g are zero
-__global__ __launch_bounds__(64) void k_quantize_q_e4m3(const uint16_t* __restrict__ q16, uint32_t g,
-                                                        uint32_t d, uint8_t* __restrict__ q8,
-                                                        float* __restrict__ qs)
-{
-    // blockIdx.x runs over (layer, head, row): q16 is [layers][heads][g][d], q8 [layers][heads][16][d]
-    const uint32_t lane = threadIdx.x, h = blockIdx.x / 16u, m = blockIdx.x % 16u;
-    uint8_t* out = q8 + (static_cast<uint64_t>(h) * 16u + m) * d;
-    if (m >= g) {
-        for (uint32_t i = lane; i < d; i += 64u) out[i] = 0;
-        if (lane == 0) qs[h * 16u + m] = 1.0f;
-        return;
-    }
-    const uint16_t* row = q16 + (static_cast<uint64_t>(h) * g + m) * d;
-    float mx = 0.0f;
-    for (uint32_t i = lane; i < d; i += 64u) { const float a = fabsf(half_bits_to_float(row[i])); mx = (a > mx) ? a : mx; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float t = __shfl_xor(mx, o); mx = (t > mx) ? t : mx; }
-    const float sc = (mx > 0.0f) ? (mx / 448.0f) : 1.0f;
-    for (uint32_t i = lane; i < d; i += 64u) {
-        const float v = fminf(fmaxf(half_bits_to_float(row[i]) / sc, -448.0f), 448.0f);
-        out[i] = static_cast<uint8_t>(__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.0f, 0, false) & 0xFF);
-    }
-    if (lane == 0) qs[h * 16u + m] = sc;
-}
-
-// One wave = 8 pages = 16 positions, all 8 kv heads, K tile staged in LDS.
-//   * fetch: the 16 KiB tile goes pool -> LDS with 16 global_load_lds_dwordx4 (1 KiB
-//     each, no VGPRs); instruction i brings the row block of position i (8 heads x
-//     128 B).  Whole 128-byte lines per instruction, pages read exactly once.
-//   * LDS image: row block i sits at i*1024; its 16-byte chunks are XOR-swizzled with
-//     i ON THE SOURCE SIDE (lane l fetches chunk l^i), because the MFMA reader walks
-//     16 row blocks at the same in-row offset (1 KiB stride = one bank otherwise).
-//   * MFMA 16x16x32 fp8: lane (c = l%16, kb = l/16) feeds 8 consecutive d of query
-//     row c (A) / position c (B); the d axis is permuted so lane kb owns
-//     d in [32kb, 32kb+32) -> two ds_read_b64 per 16-byte chunk.
-__global__ __launch_bounds__(128) void k_qk_scores_fp8(const PageEntry* __restrict__ entries,
-        uint64_t first_page, uint64_t layer_page_stride, uint32_t n_pages, uint32_t heads, uint32_t g,
-        const uint8_t* __restrict__ q8, const float* __restrict__ qs, float* __restrict__ out)
-{
-    __shared__ __attribute__((aligned(1024))) uint8_t tiles[2][16384];
-    // blockIdx.y = layer (several layers of one sequence in one launch)
-    first_page += blockIdx.y * layer_page_stride;
-    q8 += static_cast<uint64_t>(blockIdx.y) * heads * 16u * 128u;
-    qs += static_cast<uint64_t>(blockIdx.y) * heads * 16u;
-    out += static_cast<uint64_t>(blockIdx.y) * heads * g * 2u * n_pages;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t page0 = (blockIdx.x * 2u + wave) * 8u;            // wave-uniform
-    if (page0 >= n_pages) return;
-    uint8_t* tile = tiles[wave];
-    const uint32_t n_pos = 2u * n_pages;
-    // ---- fetch: 8 pages x 2 positions, descriptors through the scalar cache
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint32_t pg = page0 + j;
-        PageEntry e{0, 0, 0.0f};
-        if (pg < n_pages) e = entries[first_page + pg];
-        const bool ok = pg < n_pages && e.rec_bytes >= kBlockElems;       // wave-uniform
-#pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-            const int i = 2 * j + sl;
-            if (ok) {
-                const uint8_t* src = reinterpret_cast<const uint8_t*>(e.pool_addr) + sl * 1024 + ((lane ^ i) * 16u);
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void*)(src),
-                    (__attribute__((address_space(3))) void*)(tile + i * 1024), 16, 0, 0);
-            } else {
-                *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16u) = make_uint4(0u, 0u, 0u, 0u);
-            }
-        }
-    }
-    const uint32_t c = lane & 15u, kb = lane >> 4;
-    const uint32_t pgc = page0 + (c >> 1);
-    const bool live = pgc < n_pages;
-    float ks = 0.0f;
-    if (live) {
-        const PageEntry ec = entries[first_page + pgc];
-        ks = ec.rec_bytes >= kBlockElems ? ec.scale : 0.0f;
-    }
-    // query operands and row scales of all 8 heads: requested while the tile is in flight
-    uint4 a0[8], a1[8];
-    f32x4 qsc[8];
-#pragma unroll
-    for (int h = 0; h < 8; ++h) {
-        const uint8_t* qrow = q8 + (static_cast<uint64_t>(h) * 16u + c) * 128u + kb * 32u;
-        a0[h] = *reinterpret_cast<const uint4*>(qrow);
-        a1[h] = *reinterpret_cast<const uint4*>(qrow + 16);
-        qsc[h] = *reinterpret_cast<const f32x4*>(qs + h * 16u + 4u * kb);
-    }
-    const uint32_t t = page0 * 2u + c;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // DMA landed, operands loaded
-    wave_lds_fence();
-#pragma unroll
-    for (int h = 0; h < 8; ++h) {
-        // B: chunks h*8 + kb*2 (+1) of row block c, at their swizzled place
-        const uint32_t q0 = (static_cast<uint32_t>(h) * 8u + kb * 2u) ^ c, q1 = (static_cast<uint32_t>(h) * 8u + kb * 2u + 1u) ^ c;
-        const uint2 b00 = *reinterpret_cast<const uint2*>(tile + c * 1024u + q0 * 16u);
-        const uint2 b01 = *reinterpret_cast<const uint2*>(tile + c * 1024u + q0 * 16u + 8u);
-        const uint2 b10 = *reinterpret_cast<const uint2*>(tile + c * 1024u + q1 * 16u);
-        const uint2 b11 = *reinterpret_cast<const uint2*>(tile + c * 1024u + q1 * 16u + 8u);
-        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(a0[h].x, a0[h].y), pack64(b00.x, b00.y), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(a0[h].z, a0[h].w), pack64(b01.x, b01.y), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(a1[h].x, a1[h].y), pack64(b10.x, b10.y), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(a1[h].z, a1[h].w), pack64(b11.x, b11.y), acc, 0, 0, 0);
-        // accumulator: lane holds rows m = 4*kb + i (i = 0..3) of column c
-        if (live) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint32_t m = 4u * kb + i;
-                if (m < g) out[(static_cast<uint64_t>(h) * g + m) * n_pos + t] = acc[i] * ks * qsc[h][i];
-            }
-        }
-    }
-}
-
-// ===================================================================
-// token predictor  (src/prefetcher/lstm_predictor.cpp:40-188)
-// ===================================================================
-// The reference's "LSTM" is degenerate: gates fixed at 0.5, recurrent weights unused,
-// candidate g = sum_j 0.1*embedding[token][j] (lstm_predictor.cpp:117-146).  These
-// kernels compute exactly that maths for a batch of 16-token histories, then the
-// 128 x vocab output mat-vec, softmax and top-k.  fp tolerance vs the oracle: the
-// device tanhf/expf and the reduction order differ from glibc's (tests state 1e-4).
-constexpr uint32_t kPredHist = 16, kPredEmb = 64, kPredHidden = 128;
-// All-lanes reductions over the wave for the top-k rounds, written for latency (a round is a chain of six exchanges): the
-// four steps inside a row of 16 lanes are DPP moves (quad_perm xor 1, xor 2, row_half_mirror, row_mirror: a few clocks each);
-// rows 16 apart and the two halves of the wave meet through gfx950's v_permlane16_swap / v_permlane32_swap -- with both operands
-// the same register they return the two rows (halves) side by side in every lane, still in the vector ALU.  (ds_swizzle and
-// ds_bpermute, two trips through the LDS crossbar per reduction, were most of a one-request prediction: 15.7 us with them.)
-template <int CTRL> __device__ __forceinline__ uint32_t tk_dpp(uint32_t v) { return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xf, 0xf, false)); }
-template <int STEP> __device__ __forceinline__ uint32_t tk_exchange(uint32_t v)
-{
-    static_assert(STEP < 4, "rows and halves: tk_rows / tk_halves");
-    if constexpr (STEP == 0) return tk_dpp<0xB1>(v);                 // quad_perm [1,0,3,2]
-    else if constexpr (STEP == 1) return tk_dpp<0x4E>(v);            // quad_perm [2,3,0,1]
-    else if constexpr (STEP == 2) return tk_dpp<0x141>(v);           // row_half_mirror: the other quad of each 8
-    else return tk_dpp<0x140>(v);                                    // row_mirror: the other 8 of each 16
-}
-struct TkPair { uint32_t a, b; };                                    // a lane's own value and its partner's (in no particular order)
-__device__ __forceinline__ TkPair tk_rows(uint32_t v) { const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false); return TkPair{r[0], r[1]}; }      // lane ^ 16
-__device__ __forceinline__ TkPair tk_halves(uint32_t v) { const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false); return TkPair{r[0], r[1]}; }    // lane ^ 32
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t k)
-{
-#define SPECKV_TK_STEP(S) { const uint64_t other = (static_cast<uint64_t>(tk_exchange<S>(static_cast<uint32_t>(k >> 32))) << 32) | tk_exchange<S>(static_cast<uint32_t>(k)); k = other > k ? other : k; }
-    SPECKV_TK_STEP(0) SPECKV_TK_STEP(1) SPECKV_TK_STEP(2) SPECKV_TK_STEP(3)
-#undef SPECKV_TK_STEP
-    {
-        const TkPair hi = tk_rows(static_cast<uint32_t>(k >> 32)), lo = tk_rows(static_cast<uint32_t>(k));
-        const uint64_t x = (static_cast<uint64_t>(hi.a) << 32) | lo.a, y = (static_cast<uint64_t>(hi.b) << 32) | lo.b;
-        k = x > y ? x : y;
-    }
-    {
-        const TkPair hi = tk_halves(static_cast<uint32_t>(k >> 32)), lo = tk_halves(static_cast<uint32_t>(k));
-        const uint64_t x = (static_cast<uint64_t>(hi.a) << 32) | lo.a, y = (static_cast<uint64_t>(hi.b) << 32) | lo.b;
-        k = x > y ? x : y;
-    }
-    return k;
-}
-__device__ __forceinline__ float wave_max_f32(float v)
-{
-    v = fmaxf(v, __uint_as_float(tk_exchange<0>(__float_as_uint(v))));
-    v = fmaxf(v, __uint_as_float(tk_exchange<1>(__float_as_uint(v))));
-    v = fmaxf(v, __uint_as_float(tk_exchange<2>(__float_as_uint(v))));
-    v = fmaxf(v, __uint_as_float(tk_exchange<3>(__float_as_uint(v))));
-    const TkPair r = tk_rows(__float_as_uint(v));
-    v = fmaxf(__uint_as_float(r.a), __uint_as_float(r.b));
-    const TkPair h = tk_halves(__float_as_uint(v));
-    return fmaxf(__uint_as_float(h.a), __uint_as_float(h.b));
-}
-__device__ __forceinline__ float wave_sum_f32(float v)
-{
-    v += __uint_as_float(tk_exchange<0>(__float_as_uint(v)));
-    v += __uint_as_float(tk_exchange<1>(__float_as_uint(v)));
-    v += __uint_as_float(tk_exchange<2>(__float_as_uint(v)));
-    v += __uint_as_float(tk_exchange<3>(__float_as_uint(v)));
-    const TkPair r = tk_rows(__float_as_uint(v));
-    v = __uint_as_float(r.a) + __uint_as_float(r.b);
-    const TkPair h = tk_halves(__float_as_uint(v));
-    return __uint_as_float(h.a) + __uint_as_float(h.b);
-}
-// tanh(x) = 1 - 2 / (exp(2x) + 1) on the hardware exponential and reciprocal: absolute error ~1e-7, i.e. 1e-5 relative at the
-// |x| ~ 0.01 the reference's cell states have (tests: confidences within 5e-4 of the oracle).  libm's tanhf is ~100 instructions,
-// and the recurrence is a chain of 16 x layers x 2 of them.
-// exp(x) for the softmax terms (x <= 0): the hardware's exp2 on x log2(e), relative error ~1e-6 at |x| ~ 20 (libm's expf is ~20
-// instructions and every logit of every request takes one; tests state 5e-4 on the confidences against the oracle).
-__device__ __forceinline__ float pred_fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ __forceinline__ float pred_fast_tanh(float x)
-{
-    x = fminf(fmaxf(x, -15.0f), 15.0f);
-    const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);         // exp(2x)
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
-
-// one wave per request: lane 0 walks the history; every lane stores 2 of the 128 hidden values
-__global__ __launch_bounds__(64) void k_lstm_hidden(const int32_t* __restrict__ hist, uint32_t n,
-        const float* __restrict__ emb, uint32_t vocab, uint32_t layers, float* __restrict__ hid)
-{
-    const uint32_t r = blockIdx.x, lane = threadIdx.x;
-    if (r >= n) return;
-    // candidate g_t = sum_j 0.1*embedding[token_t][j]: lane j holds entry j of every token's row
-    // (16 independent loads in flight), one wave reduction per token
-    float g[kPredHist];
-#pragma unroll
-    for (uint32_t t = 0; t < kPredHist; ++t) {
-        const uint32_t tok = static_cast<uint32_t>(hist[r * kPredHist + t]);
-        g[t] = (tok < vocab) ? emb[static_cast<uint64_t>(tok) * kPredEmb + lane] * 0.1f : 0.0f;
-    }
-    float tg[kPredHist];
-#pragma unroll
-    for (uint32_t t = 0; t < kPredHist; ++t) tg[t] = 0.5f * pred_fast_tanh(wave_sum_f32(g[t]));      // (independent of the chain)
-    float h = 0.0f, c = 0.0f;
-#pragma unroll
-    for (uint32_t t = 0; t < kPredHist; ++t)
-        for (uint32_t l = 0; l < layers; ++l) {
-            c = 0.5f * c + tg[t];
-            h = 0.5f * pred_fast_tanh(c);
-        }
-    h = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(h)));
-    hid[static_cast<uint64_t>(r) * kPredHidden + lane] = h;
-    hid[static_cast<uint64_t>(r) * kPredHidden + 64u + lane] = h;
-}
-
-// A REAL LSTM cell (the reference's is degenerate, above; SURVEY 8f N1: "semantics must be defined by us"): the standard
-// cell with PyTorch's nn.LSTM conventions -- per layer  gates = W_ih x + W_hh h + b  (4 x 128 rows, order i, f, g, o),
-// c = sigmoid(f) c + sigmoid(i) tanh(g),  h = sigmoid(o) tanh(c),  h_0 = c_0 = 0, layer l > 0 fed with layer l-1's h of the
-// same time step; 16-token history, embedding width 64, hidden width 128.  Output: the top layer's last h.
-//   A prediction is a chain of 16 x layers dependent steps, so the kernel is written for the length of a step, layer by layer:
-//   * one workgroup = one request, 512 threads (256 requests = one workgroup per CU);
-//   * the layer's input projections W_ih x_t + b of ALL 16 steps have no dependency: computed first, into LDS;
-//   * a thread keeps, in 128 registers for the 16 recurrent steps, the weights of EIGHT gate rows over an eighth of the
-//     columns (lstm_arranged_index; the host arranged them so that the 512 threads read coalesced).  A step is 64
-//     packed fused multiply-adds per thread (v_pk_fma_f32 over two neighbouring columns) against its 16 values of h -- four
-//     16-byte LDS reads -- then a reduction over the eight threads that share the rows (7 exchanges: DPP inside a quad,
-//     ds_swizzle across, after which thread tid owns gate row tid);
-//   * the kernel numbers gate rows 4 * unit + gate, so the four gates of a hidden unit end in the four lanes of a quad: each
-//     lane applies its gate's non-linearity (tanh as 2 sigmoid(2x) - 1: one code path), the quad exchanges the four results
-//     with DPP, and all four lanes carry c (in a register) and h; lane 0 writes h -- to the layer's output sequence, which
-//     is also where the next step reads it, so a step has ONE barrier and no buffer is ever rewritten while it is read.
-//   The forms before this one: a thread owning ONE whole gate row read all of h, 64 16-byte LDS reads per step and wave; the
-//   LDS returns 128 bytes per clock however many lanes ask for the same word, so a step was 8 waves x 64 reads x 8 clocks =
-//   1.7 us of LDS time against 0.4 us of arithmetic (0.083 ms per prediction; with separate multiply and add,
-//   -ffp-contract=off as the reference's cell needs, 0.110-0.117 ms).  Sliced rows with the non-linearities on 256 threads
-//   between two barriers (libm tanhf, IEEE division): 0.070 ms.  First version (weights streamed from L2 in every step,
-//   8 requests per workgroup): 0.7-0.8 ms per prediction of 256 requests.
-struct LstmWeights { const float* w_ih_t[4]; const float* w_hh_t[4]; const float* bias[4]; uint32_t layers; };   // bias = b_ih + b_hh
-constexpr uint32_t kLstmPitch = kPredHidden + 4u * (kPredHidden / 16u);      // a 16-column slice starts 20 floats after the one before: the eight slices a wave reads fall in different banks
-__device__ __forceinline__ constexpr uint32_t lstm_pad(uint32_t j) { return j + 4u * (j >> 4); }
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)); }
-__device__ __forceinline__ float lane_xor7(float v) { return dpp_mov<0x141>(v); }    // row_half_mirror: lane 7 - s of each 8 (a DPP move; lane ^ 4 would be a ds_swizzle)
-__device__ __forceinline__ float lane_xor2(float v) { return dpp_mov<0x4E>(v); }     // quad_perm [2,3,0,1]
-__device__ __forceinline__ float lane_xor1(float v) { return dpp_mov<0xB1>(v); }     // quad_perm [1,0,3,2]
-// v[i] of slice-thread s holds a partial sum of gate row 8 * group + (i ^ s): after three exchanges with the threads s ^ 7,
-// s ^ 2, s ^ 1 the return value is the whole sum of row 8 * group + s, i.e. of row threadIdx.x.  (First exchange: thread s keeps
-// the rows (i ^ s), i < 4; its partner 7 - s = s ^ 7 holds its share of row i ^ s in v[(i ^ s) ^ (s ^ 7)] = v[7 - i].  All three are
-// DPP moves: the step of the recurrence has no trip through the LDS crossbar left.)
-__device__ __forceinline__ float lstm_reduce8(float (&v)[8])
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] += lane_xor7(v[7 - i]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) v[i] += lane_xor2(v[i + 2]);
-    return v[0] + lane_xor1(v[1]);
-}
-// sum over this thread's CS columns of  w[i][c] * x[c]  for its eight rows i; x: the thread's slice of the input vector
-template <uint32_t CS>
-__device__ __forceinline__ float lstm_slice_dot(const float (&w)[8u * CS], const float* x)
-{
-    f32x2 xv[CS / 2u];
-#pragma unroll
-    for (uint32_t k = 0; k < CS / 4u; ++k) {
-        const float4 a = *reinterpret_cast<const float4*>(x + 4u * k);
-        xv[2u * k] = f32x2{a.x, a.y}; xv[2u * k + 1u] = f32x2{a.z, a.w};
-    }
-    float red[8];
-#pragma unroll
-    for (uint32_t i = 0; i < 8u; ++i) {
-        f32x2 a = {0.0f, 0.0f};                                         // (even columns, odd columns)
-#pragma unroll
-        for (uint32_t k = 0; k < CS / 2u; ++k) a = pk_fma(f32x2{w[i * CS + 2u * k], w[i * CS + 2u * k + 1u]}, xv[k], a);
-        red[i] = a.x + a.y;
-    }
-    return lstm_reduce8(red);
-}
-template <uint32_t CS>
-__device__ __forceinline__ void lstm_project(const float* __restrict__ wsrc, float b, const float (&seq)[kPredHist][kLstmPitch],
-                                             float (&xp)[kPredHist][4 * kPredHidden])
-{
-    const uint32_t tid = threadIdx.x, s = tid & 7u;
-    float w[8u * CS];
-#pragma unroll
-    for (uint32_t q = 0; q < 8u * CS; ++q) w[q] = wsrc[q * 512u + tid];
-#pragma unroll 2
-    for (uint32_t t = 0; t < kPredHist; ++t) xp[t][tid] = lstm_slice_dot<CS>(w, &seq[t][lstm_pad(CS * s)]) + b;
-}
-__device__ __forceinline__ float sigmoid_rcp(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)); }     // the hardware's exp2 and reciprocal (1 ulp each; two of them on every step of the chain)
-__global__ __launch_bounds__(512) void k_lstm_cell(const int32_t* __restrict__ hist, uint32_t n, const float* __restrict__ emb, uint32_t vocab,
-                                                  LstmWeights w, float* __restrict__ hid)
-{
-    __shared__ __attribute__((aligned(16))) float seq[kPredHist][kLstmPitch];        // the layer's input sequence, then its own output (columns at lstm_pad)
-    __shared__ float xp[kPredHist][4 * kPredHidden];                                // W_ih x_t + b of the current layer; [.][tid] is written and read by thread tid only
-    const uint32_t tid = threadIdx.x, req = blockIdx.x, s = tid & 7u;
-    const uint32_t unit = tid >> 2, gate = tid & 3u;                      // the gate row this thread owns after a reduction
-    for (uint32_t i = tid; i < kPredHist * kPredEmb; i += 512u) {
-        const uint32_t t = i / kPredEmb, j = i % kPredEmb;
-        const uint32_t tok = static_cast<uint32_t>(hist[req * kPredHist + t]);
-        seq[t][lstm_pad(j)] = tok < vocab ? emb[static_cast<uint64_t>(tok) * kPredEmb + j] : 0.0f;
-    }
-    __syncthreads();
-    float h = 0.0f;
-    for (uint32_t l = 0; l < w.layers; ++l) {
-        const float b = w.bias[l][gate * kPredHidden + unit];
-        if (l == 0) lstm_project<kPredEmb / 8u>(w.w_ih_t[l], b, seq, xp);
-        else        lstm_project<kPredHidden / 8u>(w.w_ih_t[l], b, seq, xp);
-        float wh[kPredHidden];                                            // eight rows x sixteen columns of W_hh
-        {
-            const float* whp = w.w_hh_t[l] + tid;
-#pragma unroll
-            for (uint32_t q = 0; q < kPredHidden; ++q) wh[q] = whp[q * 512u];
-        }
-        float c = 0.0f;
-        __syncthreads();                                                  // everybody is done with seq as this layer's input
-#pragma unroll 1
-        for (uint32_t t = 0; t < kPredHist; ++t) {
-            float g = xp[t][tid];
-            if (t) g += lstm_slice_dot<kPredHidden / 8u>(wh, &seq[t - 1u][lstm_pad(16u * s)]);      // h_{-1} = 0
-            const bool is_g = gate == 2u;
-            const float sg = sigmoid_rcp(is_g ? g + g : g);
-            const float act = is_g ? sg + sg - 1.0f : sg;                 // tanh(x) = 2 sigmoid(2x) - 1
-            const float ai = dpp_mov<0x00>(act), af = dpp_mov<0x55>(act), ag = dpp_mov<0xAA>(act), ao = dpp_mov<0xFF>(act);   // quad_perm [k,k,k,k]
-            c = af * c + ai * ag;
-            const float sc = sigmoid_rcp(c + c);
-            h = ao * (sc + sc - 1.0f);
-            if (gate == 0u) seq[t][lstm_pad(unit)] = h;
-            __syncthreads();
-        }
-    }
-    if (gate == 0u) hid[static_cast<uint64_t>(req) * kPredHidden + unit] = h;
-}
-
-// logits[b][i] = sum_j hid[b][j] * wout[i][j] (+ bias[i]) on the fp32 matrix cores: a wave owns 32 output rows (16 KiB of
-// weights, read once and kept in 64 registers) and walks the requests in tiles of 32 with v_mfma_f32_32x32x2_f32 -- the hidden
-// vectors are the A operand (M = request), the weights the B operand (N = output row), so that an accumulator register holds
-// 32 consecutive logits of one request per half-wave and every store instruction writes two whole 128-byte lines.
-// The vector-ALU form this replaces (one quarter-row per lane, multiply and add per weight and request) needed ~80 VALU
-// instructions per request and wave, 4 cycles each on a 16-lane SIMD: 0.115 ms for 256 requests against ~0.014 ms of matrix
-// time (the instruction runs at 64 cycles back to back also on one accumulator: profiles/tools/probe/mfma_f32_rate.hip, 143-156
-// TFLOP/s).  This kernel: 0.030 ms, of which 0.004 the stores and ~0.005 the weights' first read (one request: 0.0066 ms).
-// The order of the 128 additions of one logit: k = 8j + 4*(lane/32) + e for j = 0..15, e = 0..3, the lower half-wave's k first
-// inside each instruction (fused, unlike the oracle's mul + add: covered by the confidence tolerance of the parity tests).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-// tiles of 32 output rows, rounded up to the four waves of a workgroup of k_lstm_logits (every wave loads its tile unconditionally)
-__host__ __device__ constexpr uint32_t logits_tiles_padded(uint32_t vocab) { return ((vocab + 31u) / 32u + 3u) & ~3u; }
-// The output layer's weights in the order k_lstm_logits reads them: per 32 rows, float4 [j][lane] = row (lane % 32),
-// columns 8j + 4 (lane / 32) .. + 3 -- a wave's load instruction is then one contiguous KiB (row-major, its 64 lanes touched
-// 64 different lines 16 bytes at a time).  Once per predictor_load.
-__global__ __launch_bounds__(256) void k_arrange_wout(const float* __restrict__ src, float4* __restrict__ dst, uint32_t vocab)
-{
-    const uint32_t lane = threadIdx.x & 63u, tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint32_t row = tile * 32u + (lane & 31u), kh = lane >> 5;
-    if (tile >= logits_tiles_padded(vocab)) return;         // (tiles past the vocabulary, up to a whole workgroup of k_lstm_logits: zeros)
-#pragma unroll
-    for (uint32_t j = 0; j < 16u; ++j) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row < vocab) v = *reinterpret_cast<const float4*>(src + static_cast<uint64_t>(row) * kPredHidden + 8u * j + 4u * kh);
-        dst[(static_cast<uint64_t>(tile) * 16u + j) * 64u + lane] = v;
-    }
-}
-constexpr uint32_t kLogitsTile = 32;        // requests per matrix tile
-constexpr uint32_t kLogitsChunk = 128;      // requests per workgroup column (blockIdx.y): 2 waves per SIMD at 256 requests x 32 000 rows
-constexpr uint32_t kLogitsPitch = kPredHidden + 4u;     // floats; 16 lanes x 16 B of one ds_read_b128 fall in 64 different banks
-__global__ __launch_bounds__(256) void k_lstm_logits(const float* __restrict__ hid, uint32_t n,
-        const float* __restrict__ wout, const float* __restrict__ out_bias, uint32_t vocab, float* __restrict__ logits)
-{
-    static_assert(kPredHidden == 128u, "16 float4 per lane and operand");
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t c = lane & 31u, kh = lane >> 5;
-    const uint32_t row = (blockIdx.x * 4u + wave) * 32u + c;
-    const bool live = row < vocab;
-    // the weights arrive arranged (k_arrange_wout): the wave's 32 rows are 16 KiB in a row, [j][lane] float4, rows past the vocabulary zero
-    float4 wq[16];
-    const float4* wt = reinterpret_cast<const float4*>(wout) + static_cast<uint64_t>(blockIdx.x * 4u + wave) * (16u * 64u) + lane;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) wq[j] = wt[j * 64];
-    const float bias = (out_bias && live) ? out_bias[row] : 0.0f;
-    const uint32_t b_begin = blockIdx.y * kLogitsChunk, b_end = min(n, b_begin + kLogitsChunk);
-    // A tile of hidden vectors (32 requests, 16 KiB) goes through LDS, shared by the four waves; two buffers, so one barrier
-    // per tile: a buffer is rewritten two tiles later, behind the barrier of the tile in between.
-    __shared__ __attribute__((aligned(16))) float hs[2][kLogitsTile][kLogitsPitch];
-    static_assert(kLogitsTile * kPredHidden / 4u == 4u * 256u, "four float4 per thread and tile");
-    float4 nx[4];
-    auto fetch = [&](uint32_t b0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t e = threadIdx.x + 256u * static_cast<uint32_t>(q);
-            const uint32_t r = e / (kPredHidden / 4u), c4 = e % (kPredHidden / 4u);
-            nx[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (b0 + r < b_end) nx[q] = *reinterpret_cast<const float4*>(hid + static_cast<uint64_t>(b0 + r) * kPredHidden + 4u * c4);
-        }
-    };
-    fetch(b_begin);
-    uint32_t buf = 0;
-    for (uint32_t b0 = b_begin; b0 < b_end; b0 += kLogitsTile, buf ^= 1u) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t e = threadIdx.x + 256u * static_cast<uint32_t>(q);
-            *reinterpret_cast<float4*>(&hs[buf][e / (kPredHidden / 4u)][4u * (e % (kPredHidden / 4u))]) = nx[q];
-        }
-        __syncthreads();
-        if (b0 + kLogitsTile < b_end) fetch(b0 + kLogitsTile);
-        f32x16 acc;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc[v] = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float4 h4 = *reinterpret_cast<const float4*>(&hs[buf][c][8u * j + 4u * kh]);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h4.x, wq[j].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h4.y, wq[j].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h4.z, wq[j].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h4.w, wq[j].w, acc, 0, 0, 0);
-        }
-        // acc[v]: request b0 + 8*(v/4) + 4*(lane/32) + v%4, output row `row`
-        if (live) {
-            float* o = logits + static_cast<uint64_t>(b0 + 4u * kh) * vocab + row;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const uint32_t m = 8u * (v >> 2) + (v & 3);
-                if (b0 + 4u * kh + m < b_end) o[static_cast<uint64_t>(m) * vocab] = out_bias ? acc[v] + bias : acc[v];
-            }
-        }
-    }
-}
-
-// softmax + top-k of one request per workgroup (k <= 8).  Ties: lower token id first.
-constexpr uint32_t kSmThreads = 1024;
-__global__ __launch_bounds__(1024) void k_softmax_topk(const float* __restrict__ logits, uint32_t vocab,
-        uint32_t k, int32_t* __restrict__ out_tok, float* __restrict__ out_conf)
-{
-    __shared__ float red[kSmThreads];
-    __shared__ uint32_t redi[kSmThreads];
-    const uint32_t b = blockIdx.x, tid = threadIdx.x;
-    const float* l = logits + static_cast<uint64_t>(b) * vocab;
-    float val[8];
-    uint32_t idx[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { val[i] = -INFINITY; idx[i] = 0xFFFFFFFFu; }
-    float mx = -INFINITY;
-    for (uint32_t i = tid; i < vocab; i += kSmThreads) {
-        const float v = l[i];
-        mx = fmaxf(mx, v);
-        // sorted insertion (descending value, ascending index)
-        if (v > val[7] || (v == val[7] && i < idx[7])) {
-            val[7] = v; idx[7] = i;
-#pragma unroll
-            for (int j = 7; j > 0; --j) {
-                const bool sw = val[j] > val[j - 1] || (val[j] == val[j - 1] && idx[j] < idx[j - 1]);
-                if (sw) { const float tv = val[j]; val[j] = val[j - 1]; val[j - 1] = tv;
-                          const uint32_t ti = idx[j]; idx[j] = idx[j - 1]; idx[j - 1] = ti; }
-            }
-        }
-    }
-    red[tid] = mx; __syncthreads();
-    for (uint32_t s = kSmThreads / 2; s > 0; s >>= 1) { if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]); __syncthreads(); }
-    mx = red[0]; __syncthreads();
-    float sum = 0.0f;
-    for (uint32_t i = tid; i < vocab; i += kSmThreads) sum += expf(l[i] - mx);
-    red[tid] = sum; __syncthreads();
-    for (uint32_t s = kSmThreads / 2; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
-    sum = red[0]; __syncthreads();
-    uint32_t head = 0;
-    for (uint32_t r = 0; r < k; ++r) {
-        float cv = -INFINITY; uint32_t ci = 0xFFFFFFFFu;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) if (static_cast<uint32_t>(j) == head) { cv = val[j]; ci = idx[j]; }
-        red[tid] = cv; redi[tid] = ci; __syncthreads();
-        for (uint32_t s = kSmThreads / 2; s > 0; s >>= 1) {
-            if (tid < s) {
-                const float ov = red[tid + s]; const uint32_t oi = redi[tid + s];
-                if (ov > red[tid] || (ov == red[tid] && oi < redi[tid])) { red[tid] = ov; redi[tid] = oi; }
-            }
-            __syncthreads();
-        }
-        const float bv = red[0]; const uint32_t bi = redi[0];
-        __syncthreads();
-        if (ci == bi && ci != 0xFFFFFFFFu) ++head;                 // the owner of the winner advances
-        if (tid == 0) {
-            out_tok[b * k + r] = static_cast<int32_t>(bi);
-            out_conf[b * k + r] = expf(bv - mx) / sum;
-        }
-    }
-}
-
-// The same for vocabularies of up to 262 144 tokens (kTkMaxParts parts), written for latency (one request per workgroup is a
-// chain of dependent steps: the kernel above took 48-57 us per launch whatever the batch, a 1024-thread workgroup with 32
-// logits per thread in registers 21-26 us).  A request is cut into parts of 4096 logits, one workgroup of 256 threads each, 16
-// logits per thread:
-//   * a wave finds ITS maximum, exp-sum (relative to its own maximum) and top k with shuffles only -- a candidate is one
-//     64-bit key, the logit's bits made order-preserving above ~token id, so "value descending, token id ascending" (the
-//     order of the sorted insertion above) is an unsigned maximum and a round is six exchange steps;
-//   * one barrier, then wave 0 merges the four waves (maxima, rescaled sums, 4 k keys) and writes the part's result;
-//   * a second kernel, one wave per request, merges the parts -- a lane holds one part's maximum, sum and k keys (already in
-//     order: a round offers the lane's best key not yet taken) -- and writes tokens and confidences exp(logit - max) / sum.  (One kernel whose last-arriving workgroup merges was tried: 10 us for one request, but the
-//     agent-scope release/acquire it needs writes back and invalidates the XCD's L2 once per workgroup -- 48 us for 256
-//     requests against 26 us before.)
-// A logit that is -inf or NaN is never chosen (as above: "v > best" is false for it); a rank without a candidate reports
-// token -1 and confidence 0.
-constexpr uint32_t kTkMaxParts = 64, kTkThreads = 256, kTkPer = 16, kTkSpan = kTkThreads * kTkPer;
-static_assert(kTkSpan == kPredictTopkSpan && kTkMaxParts == kPredictTopkMaxParts, "predict_ws_bytes");
-// workspace of one request: parts x (max, sum) | parts x 8 keys
-__device__ __forceinline__ uint32_t tk_ws_stride(uint32_t parts) { return parts * kPredictWsPerPart; }
-__device__ __forceinline__ uint64_t tk_key(float v, uint32_t i)
-{
-    if (!(v > -INFINITY)) return 0;
-    uint32_t bits = __float_as_uint(v);
-    bits ^= (bits >> 31) ? 0xFFFFFFFFu : 0x80000000u;
-    return (static_cast<uint64_t>(bits) << 32) | (0xFFFFFFFFu - i);
-}
-__device__ __forceinline__ float tk_value(uint64_t key)
-{
-    uint32_t bits = static_cast<uint32_t>(key >> 32);
-    bits ^= (bits >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-    return __uint_as_float(bits);
-}
-// merge of up to 64 (max, sum) pairs and 64 keys held one per lane; k rounds; lane 0 hands every round's winner to `put`
-template <typename Put>
-__device__ __forceinline__ void tk_merge(float m, float s, uint64_t key, uint32_t k, float& m_all, float& s_all, Put put)
-{
-    m_all = wave_max_f32(m);
-    s_all = wave_sum_f32(m > -INFINITY ? s * pred_fast_exp(m - m_all) : 0.0f);
-    for (uint32_t r = 0; r < k; ++r) {
-        const uint64_t w = wave_max_u64(key);
-        if (w == key) key = 0;                                          // keys are distinct (token ids are): one owner
-        put(r, w);
-    }
-}
-__global__ __launch_bounds__(256) void k_softmax_topk_small(const float* __restrict__ logits, uint32_t vocab,
-        uint32_t k, uint8_t* __restrict__ ws)
-{
-    __shared__ float wm[4], wsum[4];
-    __shared__ uint64_t wkey[4][8];
-    const uint32_t b = blockIdx.x, part = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;      // (requests on x: no 65 535 limit)
-    const float* l = logits + static_cast<uint64_t>(b) * vocab;
-    const uint32_t base = part * kTkSpan + tid;
-    float v[kTkPer];
-#pragma unroll
-    for (uint32_t j = 0; j < kTkPer; ++j) {
-        const uint32_t i = base + j * kTkThreads;
-        v[j] = i < vocab ? l[i] : -INFINITY;
-    }
-    float m = v[0];
-#pragma unroll
-    for (uint32_t j = 1; j < kTkPer; ++j) m = fmaxf(m, v[j]);
-    m = wave_max_f32(m);
-    float sum = 0.0f;
-#pragma unroll
-    for (uint32_t j = 0; j < kTkPer; ++j)
-        if (base + j * kTkThreads < vocab && m > -INFINITY) sum += pred_fast_exp(v[j] - m);
-    sum = wave_sum_f32(sum);
-    for (uint32_t r = 0; r < k; ++r) {
-        float bv = -INFINITY; int bj = -1;
-#pragma unroll
-        for (int j = 0; j < static_cast<int>(kTkPer); ++j)                // ascending token id: ">" keeps the lowest id among equals
-            if (v[j] > bv) { bv = v[j]; bj = j; }
-        const uint64_t key = bj >= 0 ? tk_key(bv, base + static_cast<uint32_t>(bj) * kTkThreads) : 0;
-        const uint64_t w = wave_max_u64(key);
-        if (w != 0 && w == key) {                                       // the owner retires the winner
-#pragma unroll
-            for (int j = 0; j < static_cast<int>(kTkPer); ++j) if (j == bj) v[j] = -INFINITY;
-        }
-        if (lane == 0u) wkey[wv][r] = w;
-    }
-    if (lane == 0u) { wm[wv] = m; wsum[wv] = sum; }
-    __syncthreads();
-    if (wv != 0u) return;
-    const uint32_t parts = gridDim.y;
-    uint8_t* mine = ws + static_cast<uint64_t>(b) * tk_ws_stride(parts);
-    float* part_ms = reinterpret_cast<float*>(mine);                     // [part] (max, sum)
-    uint64_t* part_key = reinterpret_cast<uint64_t*>(mine + parts * 8u);             // [part][8]
-    float pm, ps;
-    tk_merge(lane < 4u ? wm[lane] : -INFINITY, lane < 4u ? wsum[lane] : 0.0f, lane < 4u * k ? wkey[lane / k][lane % k] : 0, k, pm, ps,
-             [&](uint32_t r, uint64_t w) { if (lane == 0u) part_key[part * 8u + r] = w; });
-    if (lane == 0u) { part_ms[2u * part] = pm; part_ms[2u * part + 1u] = ps; }
-}
-__global__ __launch_bounds__(256) void k_softmax_topk_merge(const uint8_t* __restrict__ ws, uint32_t n, uint32_t k, uint32_t parts,
-        int32_t* __restrict__ out_tok, float* __restrict__ out_conf)
-{
-    const uint32_t b = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (b >= n) return;
-    const uint8_t* mine = ws + static_cast<uint64_t>(b) * tk_ws_stride(parts);
-    const float* part_ms = reinterpret_cast<const float*>(mine);
-    const uint64_t* part_key = reinterpret_cast<const uint64_t*>(mine + parts * 8u);
-    const bool have = lane < parts;                                      // lane = part
-    const float qm = have ? part_ms[2u * lane] : -INFINITY, qs = have ? part_ms[2u * lane + 1u] : 0.0f;
-    uint64_t key[8];
-#pragma unroll
-    for (uint32_t r = 0; r < 8u; ++r) key[r] = (have && r < k) ? part_key[lane * 8u + r] : 0;       // descending: key[0] is the part's best not yet taken
-    const float mx = wave_max_f32(qm);
-    const float total = wave_sum_f32(qm > -INFINITY ? qs * pred_fast_exp(qm - mx) : 0.0f);
-    float* conf = out_conf + static_cast<uint64_t>(b) * k;
-    int32_t* tok = out_tok + static_cast<uint64_t>(b) * k;
-    for (uint32_t r = 0; r < k; ++r) {
-        const uint64_t w = wave_max_u64(key[0]);
-        if (w != 0 && w == key[0]) {                                     // keys are distinct (token ids are): one owner, whose next key moves up
-#pragma unroll
-            for (uint32_t j = 0; j < 7u; ++j) key[j] = key[j + 1u];
-            key[7] = 0;
-        }
-        if (lane == 0u) {
-            tok[r] = w ? static_cast<int32_t>(0xFFFFFFFFu - static_cast<uint32_t>(w)) : -1;
-            conf[r] = w ? pred_fast_exp(tk_value(w) - mx) / total : 0.0f;
-        }
-    }
-}
-
-// ---- a handful of requests (n <= kPredictSmallN): written for the length of the chain, not for throughput ----------------
-// The batch path above is four launches (hidden state | logits on the matrix cores, 32 requests per tile | top-k of 4096-logit
-// parts | merge) and writes n x vocab logits to memory in between: for ONE request that is four launch gaps around 16 MB of
-// weights (23.7 us per prediction back to back, README's "< 10 us" claim of the reference's FPGA).  Here two launches:
-//   k_predict_small:  a wave takes 32 output rows (its 16 KiB of arranged weights: the same k_arrange_wout layout), forms
-//     their logits for every request with plain fused multiply-adds against the hidden vector in LDS -- which the workgroup
-//     computes itself for the reference's degenerate cell (one wave per request: the loop of k_lstm_hidden) or reads from
-//     k_lstm_cell's output for the real one -- and reduces them at once: maximum, exp-sum, top k of its 32 rows by wave
-//     exchanges, then the four waves' results to one (max, sum, k keys) of the workgroup's 128 rows.  Logits never leave
-//     the CU.
-//   k_predict_small_merge:  one workgroup per request merges the workgroups' results (a lane per part, 64 parts per wave,
-//     as k_softmax_topk_merge) and writes tokens and confidences.  (Merged by the workgroup that finishes last instead -- one
-//     launch, write-through stores, arrival counter: 17.1 us per prediction against 15.7 with the second launch; the lone
-//     workgroup's chain of counter, agent-scope loads and exchanges is longer than a launch gap.
-//     profiles/experiments/r04_predict_small_last_arriver_merge.patch)
-// Same arithmetic as the batch path up to the order of the dot product's additions (tests state 1e-4 on confidences, as for
-// the batch path against the oracle); vocabularies up to kPredictSmallMaxParts x 128 rows, larger ones take the batch path.
-__global__ __launch_bounds__(256) void k_predict_small(const int32_t* __restrict__ hist, uint32_t n, const float* __restrict__ emb,
-        const float* __restrict__ hid_in, uint32_t layers, const float* __restrict__ wout, const float* __restrict__ out_bias,
-        uint32_t vocab, uint32_t k, uint8_t* __restrict__ ws)
-{
-    __shared__ __attribute__((aligned(16))) float hs[kPredictSmallN][kPredHidden];
-    __shared__ float wm[kPredictSmallN][4], wsum[kPredictSmallN][4];
-    __shared__ uint64_t wkey[kPredictSmallN][4][8];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t c = lane & 31u, kh = lane >> 5;
-    const uint32_t tile = blockIdx.x * 4u + wave;
-    const uint32_t row = tile * 32u + c;
-    const bool live = row < vocab && kh == 0u;                          // the two halves of the wave end with the same logit: one counts
-    // the wave's weights first (they are the long pole: 16 KiB per wave from memory), then the hidden vectors under their flight
-    float4 wq[16];
-    const float4* wt = reinterpret_cast<const float4*>(wout) + static_cast<uint64_t>(tile) * (16u * 64u) + lane;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) wq[j] = wt[j * 64];
-    const float bias = (out_bias && row < vocab) ? out_bias[row] : 0.0f;
-    if (hid_in) {                                                       // the real cell's output (k_lstm_cell)
-        for (uint32_t e = threadIdx.x; e < n * kPredHidden; e += 256u) hs[e / kPredHidden][e % kPredHidden] = hid_in[e];
-    } else if (wave < n) {                                              // the reference's degenerate cell: k_lstm_hidden's loop, request = wave
-        float g[kPredHist];
-#pragma unroll
-        for (uint32_t t = 0; t < kPredHist; ++t) {
-            const uint32_t tok = static_cast<uint32_t>(hist[wave * kPredHist + t]);
-            g[t] = (tok < vocab) ? emb[static_cast<uint64_t>(tok) * kPredEmb + lane] * 0.1f : 0.0f;
-        }
-#pragma unroll
-        for (uint32_t t = 0; t < kPredHist; ++t) g[t] = wave_sum_f32(g[t]);
-        // (the recurrence: pred_fast_tanh, as k_lstm_hidden)
-        float tg[kPredHist];
-#pragma unroll
-        for (uint32_t t = 0; t < kPredHist; ++t) tg[t] = 0.5f * pred_fast_tanh(g[t]);      // (independent of the chain)
-        float h = 0.0f, cc = 0.0f;
-#pragma unroll
-        for (uint32_t t = 0; t < kPredHist; ++t)
-            for (uint32_t l = 0; l < layers; ++l) {
-                cc = 0.5f * cc + tg[t];
-                h = 0.5f * pred_fast_tanh(cc);
-            }
-        h = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(h)));
-        hs[wave][lane] = h;
-        hs[wave][64u + lane] = h;
-    }
-    __syncthreads();
-    for (uint32_t b = 0; b < n; ++b) {                                  // (n <= 4: the weights stay in registers)
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float4 h4 = *reinterpret_cast<const float4*>(&hs[b][8u * j + 4u * kh]);
-            acc = __builtin_fmaf(h4.x, wq[j].x, acc);
-            acc = __builtin_fmaf(h4.y, wq[j].y, acc);
-            acc = __builtin_fmaf(h4.z, wq[j].z, acc);
-            acc = __builtin_fmaf(h4.w, wq[j].w, acc);
-        }
-        { const TkPair h2 = tk_halves(__float_as_uint(acc)); acc = __uint_as_float(h2.a) + __uint_as_float(h2.b); }   // the other half of the columns
-        const float v = live ? (out_bias ? acc + bias : acc) : -INFINITY;
-        const float m = wave_max_f32(v);
-        const float sum = wave_sum_f32((live && m > -INFINITY) ? pred_fast_exp(v - m) : 0.0f);
-        uint64_t key = live ? tk_key(v, row) : 0;
-        for (uint32_t r = 0; r < k; ++r) {
-            const uint64_t w = wave_max_u64(key);
-            if (w == key) key = 0;                                      // one row per lane: the owner retires it
-            if (lane == 0u) wkey[b][wave][r] = w;
-        }
-        if (lane == 0u) { wm[b][wave] = m; wsum[b][wave] = sum; }
-    }
-    __syncthreads();
-    if (wave >= n) return;                                              // wave b merges request b's four results
-    const uint32_t b = wave, parts = gridDim.x, part = blockIdx.x;
-    uint8_t* mine = ws + static_cast<uint64_t>(b) * tk_ws_stride(parts);
-    float* part_ms = reinterpret_cast<float*>(mine);                     // [part] (max, sum)
-    uint64_t* part_key = reinterpret_cast<uint64_t*>(mine + parts * 8u);             // [part][8]
-    float pm, ps;
-    tk_merge(lane < 4u ? wm[b][lane] : -INFINITY, lane < 4u ? wsum[b][lane] : 0.0f, lane < 4u * k ? wkey[b][lane / k][lane % k] : 0, k, pm, ps,
-             [&](uint32_t r, uint64_t w) { if (lane == 0u) part_key[part * 8u + r] = w; });
-    if (lane == 0u) { part_ms[2u * part] = pm; part_ms[2u * part + 1u] = ps; }
-}
-__global__ __launch_bounds__(256) void k_predict_small_merge(const uint8_t* __restrict__ ws, uint32_t k, uint32_t parts,
-        int32_t* __restrict__ out_tok, float* __restrict__ out_conf)
-{
-    __shared__ float wm[4], wsum[4];
-    __shared__ uint64_t wkey[4][8];
-    const uint32_t b = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint8_t* mine = ws + static_cast<uint64_t>(b) * tk_ws_stride(parts);
-    const float* part_ms = reinterpret_cast<const float*>(mine);
-    const uint64_t* part_key = reinterpret_cast<const uint64_t*>(mine + parts * 8u);
-    const uint32_t part = wave * 64u + lane;                             // lane = part (up to 256 of them)
-    const bool have = part < parts;
-    const float qm = have ? part_ms[2u * part] : -INFINITY, qs = have ? part_ms[2u * part + 1u] : 0.0f;
-    uint64_t key[8];
-#pragma unroll
-    for (uint32_t r = 0; r < 8u; ++r) key[r] = (have && r < k) ? part_key[part * 8u + r] : 0;       // descending: key[0] is the part's best not yet taken
-    const float mx = wave_max_f32(qm);
-    const float total = wave_sum_f32(qm > -INFINITY ? qs * pred_fast_exp(qm - mx) : 0.0f);
-    for (uint32_t r = 0; r < k; ++r) {
-        const uint64_t w = wave_max_u64(key[0]);
-        if (w != 0 && w == key[0]) {                                     // keys are distinct (token ids are): one owner, whose next key moves up
-#pragma unroll
-            for (uint32_t j = 0; j < 7u; ++j) key[j] = key[j + 1u];
-            key[7] = 0;
-        }
-        if (lane == 0u) wkey[wave][r] = w;
-    }
-    if (lane == 0u) { wm[wave] = mx; wsum[wave] = total; }
-    __syncthreads();
-    if (wave != 0u) return;
-    float M, S;
-    float* conf = out_conf + static_cast<uint64_t>(b) * k;
-    int32_t* tok = out_tok + static_cast<uint64_t>(b) * k;
-    tk_merge(lane < 4u ? wm[lane] : -INFINITY, lane < 4u ? wsum[lane] : 0.0f, lane < 4u * k ? wkey[lane / k][lane % k] : 0, k, M, S,
-             [&](uint32_t r, uint64_t w) {
-                 if (lane == 0u) {
-                     tok[r] = w ? static_cast<int32_t>(0xFFFFFFFFu - static_cast<uint32_t>(w)) : -1;
-                     conf[r] = w ? pred_fast_exp(tk_value(w) - M) / S : 0.0f;
-                 }
-             });
-}
-
+// (k_repack and k_retarget_entries are page-table upkeep and belong to page_table_kernels.inl by subject, as k_copy16 further
+// down does.  They stay where they are defined: in front of the predictor's kernels they would change the order of the code
+// object.  With them stay their launchers, which need the definitions.)
 // Records move to new places (compaction into packed extents and back): one wave per page copies the record's bytes, rounded up
 // to 16 (k_compress zero-pads a record's last 16-byte piece), then re-points the page's table entry.
 __global__ __launch_bounds__(256) void k_repack(PageEntry* __restrict__ entries, const uint64_t* __restrict__ new_addr, uint64_t n)
@@ -2571,6 +1492,8 @@ hipError_t launch_compress(const CodecArgs& a, hipStream_t s)
     }
 }
 
+// The launchers of flush_kernels.inl.  They stay behind launch_compress: they are the first to name k_prefetch_lookup<> and
+// k_flush_mark<>, and in front of it those instances would be emitted ahead of the k_compress<> instances launch_compress names.
 hipError_t launch_prefetch_lookup(const Layout& lay, uint32_t n, const uint32_t* d_req,
                                   const uint32_t* d_layer, const uint32_t* d_pos,
                                   const uint32_t* d_k, const uint32_t* d_flags, uint32_t* d_out,
@@ -2624,27 +1547,6 @@ hipError_t launch_verify(uint32_t n, uint32_t k, const int32_t* d_actual,
     return hipGetLastError();
 }
 
-hipError_t launch_quantize_q_e4m3(const void* d_q_f16, uint32_t heads, uint32_t g, uint32_t d,
-                                  uint8_t* d_q8, float* d_qs, hipStream_t s)
-{
-    if (heads == 0 || g == 0 || g > 16u || d != 128u) return hipErrorInvalidValue;
-    // `heads` may be layers*heads: rows are independent
-    hipLaunchKernelGGL(k_quantize_q_e4m3, dim3(heads * 16u), dim3(64), 0, s,
-                       static_cast<const uint16_t*>(d_q_f16), g, d, d_q8, d_qs);
-    return hipGetLastError();
-}
-
-hipError_t launch_qk_scores_fp8(const PageEntry* d_entries, uint64_t first_page, uint64_t layer_page_stride,
-                                uint32_t n_layers, uint32_t n_pages, uint32_t heads, uint32_t g,
-                                const uint8_t* d_q8, const float* d_qs, float* d_out, hipStream_t s)
-{
-    if (n_pages == 0 || n_layers == 0) return hipSuccess;
-    const uint32_t waves = (n_pages + 7u) / 8u;
-    hipLaunchKernelGGL(k_qk_scores_fp8, dim3((waves + 1u) / 2u, n_layers), dim3(128), 0, s, d_entries, first_page,
-                       layer_page_stride, n_pages, heads, g, d_q8, d_qs, d_out);
-    return hipGetLastError();
-}
-
 hipError_t launch_repack(PageEntry* d_entries, const uint64_t* d_new_addr, uint64_t n, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
@@ -2660,63 +1562,6 @@ hipError_t launch_retarget_entries(PageEntry* d_entries, uint64_t n, uint64_t ba
     return hipGetLastError();
 }
 
-size_t arranged_wout_bytes(uint32_t vocab) { return static_cast<size_t>(logits_tiles_padded(vocab)) * 32u * kPredHidden * sizeof(float); }
-hipError_t launch_arrange_wout(const float* d_src, float* d_dst, uint32_t vocab, hipStream_t s)
-{
-    const uint32_t tiles = logits_tiles_padded(vocab);
-    hipLaunchKernelGGL(k_arrange_wout, dim3(tiles / 4u), dim3(256), 0, s, d_src, reinterpret_cast<float4*>(d_dst), vocab);
-    return hipGetLastError();
-}
-
-hipError_t launch_predict(uint32_t n, const int32_t* d_hist, const float* d_emb, const float* d_wout, uint32_t vocab,
-                          uint32_t layers, uint32_t k, float* d_hid, float* d_logits, void* d_ws, int32_t* d_tok, float* d_conf,
-                          hipStream_t s, const LstmParams* lstm)
-{
-    if (n == 0) return hipSuccess;
-    if (k == 0 || k > 8u || vocab < k) return hipErrorInvalidValue;
-    const uint32_t small_parts = logits_tiles_padded(vocab) / 4u;       // workgroups of 128 rows
-    if (n <= kPredictSmallN && small_parts <= kPredictSmallMaxParts && !tuning().predict_batch_path) {
-        // a handful of requests: two launches (three with the real cell), no logits in memory (k_predict_small)
-        const bool real = lstm && lstm->layers;
-        if (real) {
-            if (lstm->layers > 4u) return hipErrorInvalidValue;
-            LstmWeights w{};
-            w.layers = lstm->layers;
-            for (uint32_t l = 0; l < lstm->layers; ++l) { w.w_ih_t[l] = lstm->w_ih_t[l]; w.w_hh_t[l] = lstm->w_hh_t[l]; w.bias[l] = lstm->bias[l]; }
-            hipLaunchKernelGGL(k_lstm_cell, dim3(n), dim3(512), 0, s, d_hist, n, d_emb, vocab, w, d_hid);
-        }
-        hipLaunchKernelGGL(k_predict_small, dim3(small_parts), dim3(256), 0, s, d_hist, n, d_emb, real ? d_hid : nullptr, layers, d_wout,
-                           lstm ? lstm->out_bias : nullptr, vocab, k, static_cast<uint8_t*>(d_ws));
-        hipLaunchKernelGGL(k_predict_small_merge, dim3(n), dim3(256), 0, s, static_cast<const uint8_t*>(d_ws), k, small_parts, d_tok, d_conf);
-        return hipGetLastError();
-    }
-    if (lstm && lstm->layers) {                       // the real cell (speckv_ext_predictor_load_lstm)
-        if (lstm->layers > 4u) return hipErrorInvalidValue;
-        LstmWeights w{};
-        w.layers = lstm->layers;
-        for (uint32_t l = 0; l < lstm->layers; ++l) { w.w_ih_t[l] = lstm->w_ih_t[l]; w.w_hh_t[l] = lstm->w_hh_t[l]; w.bias[l] = lstm->bias[l]; }
-        hipLaunchKernelGGL(k_lstm_cell, dim3(n), dim3(512), 0, s, d_hist, n, d_emb, vocab, w, d_hid);
-    } else {
-        hipLaunchKernelGGL(k_lstm_hidden, dim3(n), dim3(64), 0, s, d_hist, n, d_emb, vocab, layers, d_hid);
-    }
-    const uint32_t waves = (vocab + 31u) / 32u;              // 32 output rows per wave (k_lstm_logits)
-    hipLaunchKernelGGL(k_lstm_logits, dim3((waves + 3u) / 4u, (n + kLogitsChunk - 1u) / kLogitsChunk), dim3(256), 0, s, d_hid, n, d_wout, lstm ? lstm->out_bias : nullptr, vocab, d_logits);
-    const uint32_t parts = predict_topk_parts(vocab);
-    if (parts) {
-        hipLaunchKernelGGL(k_softmax_topk_small, dim3(n, parts), dim3(kTkThreads), 0, s, d_logits, vocab, k, static_cast<uint8_t*>(d_ws));
-        hipLaunchKernelGGL(k_softmax_topk_merge, dim3((n + 3u) / 4u), dim3(256), 0, s, static_cast<const uint8_t*>(d_ws), n, k, parts, d_tok, d_conf);
-    }
-    else                           hipLaunchKernelGGL(k_softmax_topk, dim3(n), dim3(1024), 0, s, d_logits, vocab, k, d_tok, d_conf);
-    return hipGetLastError();
-}
-
-hipError_t launch_apply_updates(const DevAlloc* d_tab, const MirrorUpdate* d_updates, uint32_t n, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_apply_updates, dim3((n + 255u) / 256u), dim3(256), 0, s, d_tab, d_updates, n);
-    return hipGetLastError();
-}
-
 // 16-byte-per-lane copy (pinned host memory -> device): the request columns of a flush.  As a kernel on the flush's own
 // stream it needs no copy engine and no cross-engine dependency in front of the first flush kernel.
 __global__ __launch_bounds__(256) void k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst, uint32_t n16)
@@ -2729,15 +1574,6 @@ hipError_t launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t s
     const uint32_t n16 = static_cast<uint32_t>((bytes + 15u) / 16u);
     if (n16 == 0) return hipSuccess;
     hipLaunchKernelGGL(k_copy16, dim3((n16 + 255u) / 256u), dim3(256), 0, s, static_cast<const uint4*>(src), static_cast<uint4*>(dst), n16);
-    return hipGetLastError();
-}
-
-hipError_t launch_init_entries(PageEntry* d_entries, uint64_t n, uint64_t base, uint64_t stride,
-                               hipStream_t s, uint64_t rec0)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_init_entries, dim3(static_cast<uint32_t>((n + 255u) / 256u)), dim3(256), 0, s,
-                       d_entries, n, base, stride, rec0);
     return hipGetLastError();
 }
 

@@ -147,7 +147,7 @@ def test_no_environment_walks_behind_the_entry_points():
     csrc = os.path.join(ROOT, "cxl-speckv_amd", "csrc")
     allowed = {"tuning.cpp", "engine_internal.hpp", "engine.cpp", "tuning.hpp"}
     for fn in sorted(os.listdir(csrc)):
-        if not fn.endswith((".cpp", ".hip", ".hpp")) or fn in allowed:
+        if not fn.endswith((".cpp", ".hip", ".hpp", ".inl")) or fn in allowed:
             continue
         text = open(os.path.join(csrc, fn)).read()
         assert not re.search(r"\bgetenv\s*\(", text), f"{fn} reads the environment"

@@ -49,7 +49,7 @@ def test_the_tree_builds():
     r = subprocess.run(["make", "-s", "-j8", "-C", src], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout[-3000:]
     lib = os.path.join(ROOT, "cxl-speckv_amd", "lib", "libcxlspeckv.so")
-    newest = max(os.path.getmtime(os.path.join(src, f)) for f in os.listdir(src) if f.endswith((".hip", ".cpp", ".hpp", ".map")))
+    newest = max(os.path.getmtime(os.path.join(src, f)) for f in os.listdir(src) if f.endswith((".hip", ".cpp", ".hpp", ".inl", ".map")))
     assert os.path.getmtime(lib) >= newest
 
 
