@@ -1571,6 +1571,117 @@ hipError_t launch_attend_fold_held(uint32_t n_rows, const uint32_t* d_rows, uint
     return hipGetLastError();
 }
 
+// The same fold with visibility from a MASK instead of a causal count (speckv_ext_attend_fold_masked): a step whose drafts form a tree --
+// several continuations that share a prefix -- where a query position sees its ancestors only.  mask[i * mask_stride + j], bit t set =
+// held position t of sequence i is visible to query position j; bits >= SPECKV_HELD_MAX are dropped.  The word is the same for the whole
+// wave: it goes to a scalar register once, and the unrolled loops over the SPECKV_HELD_MAX positions are guarded by scalar bit tests, so
+// scores and rows stay in registers as in k_attend_fold_held (the build checks: no scratch).  Wave shape and arithmetic are those of
+// k_attend_fold_held -- fp32 products, their 64-lane sum and the sm_scale multiply in fp64, the maximum over the stored lse and every
+// visible score first, one weighting pass, visible positions in ascending t -- so a chain mask (1 << (base + j + 1)) - 1 gives what that
+// kernel gives.  All K loads go out before the first is used, then all V loads; the load of an invisible t is redirected to the lowest
+// visible row (an address that exists, a line already on its way), so a wave reads no held position above the highest bit of its mask.
+// A wave whose mask is 0 leaves without touching anything (a dead node of a ragged step).
+template <int R>
+__global__ __launch_bounds__(256) void k_attend_fold_masked(uint32_t n_waves, const uint32_t* __restrict__ rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos,
+                                                            const f16x2* __restrict__ q, const f16x2* __restrict__ k_held, const f16x2* __restrict__ v_held,
+                                                            uint64_t seq_stride_h2, uint64_t pos_stride_h2, const uint32_t* __restrict__ mask,
+                                                            uint32_t mask_stride, float sm_scale, float2* __restrict__ out, float* __restrict__ lse)
+{
+    uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    if (w >= n_waves) return;
+    const uint32_t chunks = rows_per_pos / R, n_q = g / rows_per_pos;
+    const uint32_t c = w % chunks; w /= chunks;
+    const uint32_t j = w % n_q; w /= n_q;
+    const uint32_t head = w % heads, i = w / heads;
+    const uint32_t vis = __builtin_amdgcn_readfirstlane(mask[static_cast<uint64_t>(i) * mask_stride + j]) & ((1u << kHeldMax) - 1u);
+    if (vis == 0) return;
+    const uint32_t t_lo = static_cast<uint32_t>(__builtin_ctz(vis));        // the row an invisible t loads instead of its own
+    const uint32_t b = rows ? rows[i] : i;
+    const uint64_t row0 = (static_cast<uint64_t>(b) * heads + head) * g + j * rows_per_pos + c * R;
+    const uint64_t held_at = i * seq_stride_h2 + head * 64u + lane;
+    f16x2 kh[kHeldMax];
+#pragma unroll
+    for (uint32_t t = 0; t < kHeldMax; ++t) kh[t] = k_held[held_at + ((vis >> t) & 1u ? t : t_lo) * pos_stride_h2];
+    float2 qv[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const f16x2 qh = q[(row0 + r) * 64u + lane];
+        qv[r] = make_float2(static_cast<float>(qh.x), static_cast<float>(qh.y));
+    }
+    float sc[R][kHeldMax];
+#pragma unroll
+    for (uint32_t t = 0; t < kHeldMax; ++t) {
+        if ((vis >> t) & 1u) {
+            const float2 kv = make_float2(static_cast<float>(kh[t].x), static_cast<float>(kh[t].y));
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                // (fp32 products, fp64 sum: see k_attend_fold_held)
+                double dot = static_cast<double>(qv[r].x * kv.x) + static_cast<double>(qv[r].y * kv.y);
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+                sc[r][t] = static_cast<float>(dot * static_cast<double>(sm_scale));
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) sc[r][t] = -__builtin_inff();
+        }
+    }
+    f16x2 vh[kHeldMax];
+#pragma unroll
+    for (uint32_t t = 0; t < kHeldMax; ++t) vh[t] = v_held[held_at + ((vis >> t) & 1u ? t : t_lo) * pos_stride_h2];
+    float2 acc[R];
+    float den[R], hi[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const float old = lse[row0 + r];
+        hi[r] = old;
+#pragma unroll
+        for (uint32_t t = 0; t < kHeldMax; ++t) hi[r] = fmaxf(hi[r], sc[r][t]);
+        const float e_old = __expf(old - hi[r]);                             // old = -inf: 0
+        const float2 o = out[(row0 + r) * 64u + lane];
+        acc[r] = make_float2(o.x * e_old, o.y * e_old);
+        den[r] = e_old;
+    }
+#pragma unroll
+    for (uint32_t t = 0; t < kHeldMax; ++t) {
+        if ((vis >> t) & 1u) {
+            const float2 vv = make_float2(static_cast<float>(vh[t].x), static_cast<float>(vh[t].y));
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float e = __expf(sc[r][t] - hi[r]);
+                acc[r].x += vv.x * e;
+                acc[r].y += vv.y * e;
+                den[r] += e;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const float inv = 1.0f / den[r];
+        out[(row0 + r) * 64u + lane] = make_float2(acc[r].x * inv, acc[r].y * inv);
+        if (lane == 0) lse[row0 + r] = hi[r] + __logf(den[r]);
+    }
+}
+
+hipError_t launch_attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
+                                     const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                                     const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+{
+    if (rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > kHeldMax - 1u || mask_stride < g / rows_per_pos) return hipErrorInvalidValue;
+    const uint32_t r = rows_per_pos % 4u == 0 ? 4u : rows_per_pos % 2u == 0 ? 2u : 1u;        // as launch_attend_fold_held
+    const uint64_t n_waves = static_cast<uint64_t>(n_rows) * heads * (g / r);
+    if (n_waves == 0) return hipSuccess;
+    if (n_waves > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<uint32_t>((n_waves + 3u) / 4u));
+#define SPECKV_FOLD_MASKED(R) hipLaunchKernelGGL(k_attend_fold_masked<R>, grid, dim3(256), 0, s, static_cast<uint32_t>(n_waves), d_rows, heads, g, rows_per_pos, \
+                                                 static_cast<const f16x2*>(d_q_f16), static_cast<const f16x2*>(d_k_held), static_cast<const f16x2*>(d_v_held),     \
+                                                 seq_stride_elems / 2u, pos_stride_elems / 2u, d_mask, mask_stride, sm_scale, reinterpret_cast<float2*>(d_out), d_lse)
+    if (r == 4u) SPECKV_FOLD_MASKED(4); else if (r == 2u) SPECKV_FOLD_MASKED(2); else SPECKV_FOLD_MASKED(1);
+#undef SPECKV_FOLD_MASKED
+    return hipGetLastError();
+}
+
 hipError_t launch_attend_fp8_batch(const AttendArgs& a, uint32_t n_seq, float* d_out, float* d_lse, hipStream_t s)
 {
     if (n_seq == 0 || a.n_splits == 0) return hipSuccess;

@@ -537,6 +537,18 @@ speckv_status_t speckv_ext_attend_fold_held(uint32_t n_rows, const uint32_t* d_r
     });
 }
 
+speckv_status_t speckv_ext_attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos,
+                                              const void* d_q_f16, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems,
+                                              uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale,
+                                              float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] {
+        return g_engine->attend_fold_masked(n_rows, d_rows, heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems,
+                                            d_mask, mask_stride, sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream));
+    });
+}
+
 speckv_status_t speckv_ext_attend_int4(speckv_handle_t handle, uint32_t layer_begin, uint32_t n_layers, const void* d_q_f16,
                                        uint32_t g, uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out,
                                        float* d_lse, void* stream)

@@ -661,6 +661,26 @@ int Engine::attend_fold_held(uint32_t n_rows, const uint32_t* d_rows, uint32_t h
     return SPECKV_OK;
 }
 
+// speckv_ext_attend_fold_masked: judged as speckv_ext_attend_fold_held, the mask table in the place of d_base / d_n_q.
+int Engine::attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
+                               const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask,
+                               uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+{
+    if (heads == 0 || g == 0 || g > 16 || rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > SPECKV_HELD_MAX - 1u) return SPECKV_ERR_INVAL;
+    const uint64_t n_q = g / rows_per_pos, row = static_cast<uint64_t>(heads) * 128u;
+    if (pos_stride_elems % 8u || seq_stride_elems % 8u || pos_stride_elems < row || seq_stride_elems < (n_q - 1u) * pos_stride_elems + row)
+        return SPECKV_ERR_INVAL;                                // (positions or sequences that overlap)
+    if (!d_q_f16 || !d_k_held || !d_v_held || !d_mask || mask_stride < n_q || !d_out || !d_lse) return SPECKV_ERR_INVAL;
+    if (null_) return no_data_path("speckv_ext_attend_fold_masked");
+    if (n_rows == 0) return SPECKV_OK;
+    DeviceScope device_scope(device_);
+    if (!s) HIP_TRY(hipDeviceSynchronize());                   // NULL: the engine's stream, synchronous (include/speckv_ext.h)
+    HIP_TRY(launch_attend_fold_masked(n_rows, d_rows, heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems,
+                                      d_mask, mask_stride, sm_scale, d_out, d_lse, s ? s : stream_));
+    if (!s) HIP_TRY(hipStreamSynchronize(stream_));
+    return SPECKV_OK;
+}
+
 // Launch geometry of the whole-record INT4 kernel (k_attend_int4_wg8; 512-thread workgroups, two resident per CU); `cus` = the
 // compute units of the ENGINE's device (Engine::cus()).
 // Stream form (many layers of one sequence): the launch's n_layers x n_tiles tiles, layer-major, in as many equal pieces as

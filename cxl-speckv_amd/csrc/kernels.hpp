@@ -406,6 +406,11 @@ hipError_t launch_attend_fold_tail(uint32_t n_rows, const uint32_t* d_rows, uint
 hipError_t launch_attend_fold_held(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
                                    const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
                                    const uint32_t* d_base, const uint32_t* d_n_q, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
+// the same with visibility from a mask: query position j of sequence i += the held positions t whose bit is set in d_mask[i * mask_stride + j]
+// (bits >= SPECKV_HELD_MAX dropped; a word of 0 leaves the position's rows untouched); see k_attend_fold_masked
+hipError_t launch_attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
+                                     const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                                     const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
 // a.lin_base set: linear form (a.scale_tab, a.q16); else page-table form (a.q8 / a.qs from launch_quantize_q_e4m3)
 hipError_t launch_attend_fp8(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s);
 // scale_tab[tile order of p] = entries[p].rec_bytes >= 2048 ? entries[p].scale : 0 for every page (set_layout time)

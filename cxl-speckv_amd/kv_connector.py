@@ -19,6 +19,9 @@ paged-attention layer would talk to for a BATCH of requests:
                                batches): the S new positions ride through the same pass over the records as extra query
                                rows, the rows held outside the pool are folded in causally by one launch
                                (``speckv_ext_attend_fold_held``); then the accepted prefix is committed
+  tree_masks / append_path     the same step with drafts that form a TREE (``attend_spec(parents=...)``): a node sees its
+                               ancestors only, the held rows are folded in by ``speckv_ext_attend_fold_masked`` with one mask
+                               word per (request, node); then the accepted root-to-node path is committed
 
 Only plain device pointers cross into the library; torch is used for device buffers and the tail fold.
 """
@@ -98,6 +101,7 @@ class SpeckvKVConnector:
         self._plan_stream = None
         self._kscale = self._kscale_inv = None               # set_k_channel_scale
         self._spec_key = self._spec_idx = self._spec_base = None     # attend_spec: where the held rows of a step come from
+        self._tree_key = self._tree_masks = None                     # attend_spec(parents=...): the mask words of a step, [n_layers * batch][S]
 
     def set_k_channel_scale(self, scale):
         """Per-(layer, kv head, channel) pre-scale of K, folded into the query: K / scale goes into the pool, q * scale meets it, q.k is
@@ -493,6 +497,56 @@ class SpeckvKVConnector:
                 tails.append((b, held[-1]))
         return pairs, tails
 
+    @staticmethod
+    def _tree_parents(parents, batch):
+        """parents as one list per request: [S] is the same tree for every request, [batch][S] one tree each.  Every entry an int in
+        -1 .. j-1 (a parent precedes its children), 1 .. SPECKV_HELD_MAX - 1 nodes, the same count for every request."""
+        import numbers
+        parents = list(parents)
+        if parents and not isinstance(parents[0], numbers.Integral):
+            trees = [list(p) for p in parents]
+            if len(trees) != batch:
+                raise ValueError("parents: one tree per request, or one tree for all")
+        else:
+            trees = [parents] * batch
+        S = len(trees[0]) if trees else 0
+        for tree in trees:
+            if len(tree) != S or not 1 <= S <= HELD_MAX - 1:
+                raise ValueError(f"parents: 1..{HELD_MAX - 1} nodes, the same count for every request")
+            for j, p in enumerate(tree):
+                if not isinstance(p, numbers.Integral) or isinstance(p, bool) or not -1 <= p < j:
+                    raise ValueError(f"parents[{j}] = {p!r}: a node's parent is -1 (the committed context) or a node in front of it")
+        return [[int(p) for p in tree] for tree in trees]
+
+    @staticmethod
+    def tree_masks(parents, base, n_new=None):
+        """The mask words of a step whose S new positions form a tree, as speckv_ext_attend_fold_masked takes them: [batch][S] ints.
+        parents: [S], or [batch][S] for one tree per request; parents[j] in -1 .. j-1, -1 = a child of the committed context, nodes in
+        an order where a parent precedes its children.  base[b]: the held positions in front of node 0 (a request's odd last position:
+        0 or 1), all visible to every node.  Node j's word = the low base[b] bits, and the bits base[b] + a of its ancestors a and of j
+        itself.  Nodes >= n_new[b] (a ragged step) are dead: word 0, and so is every node below a dead one.  A chain (parents[j] = j - 1)
+        gives (1 << (base + j + 1)) - 1, the rule of speckv_ext_attend_fold_held.  Pure python, no device."""
+        base = [int(x) for x in base]
+        trees = SpeckvKVConnector._tree_parents(parents, len(base))
+        if not trees:
+            return []
+        S = len(trees[0])
+        if n_new is None:
+            n_new = [S] * len(base)
+        n_new = [int(n) for n in n_new]
+        if len(n_new) != len(base) or not all(0 <= n <= S for n in n_new):
+            raise ValueError("n_new: one count 0..S per request")
+        if not all(0 <= x and x + S <= HELD_MAX for x in base):
+            raise ValueError(f"base: 0 .. {HELD_MAX} - S held positions in front of the new ones")
+        words = []
+        for tree, x, n in zip(trees, base, n_new):
+            row = []
+            for j, p in enumerate(tree):
+                up = ((1 << x) - 1) if p < 0 else row[p]                  # what the parent sees (0: the parent is dead)
+                row.append(up | 1 << (x + j) if j < n and (p < 0 or up) else 0)
+            words.append(row)
+        return words
+
     def _held_rows(self, req_ids, key, reqs, k_new, v_new, layer_begin, n_layers, st):
         """The rows a step holds outside the pool as speckv_ext_attend_fold_held takes them: fp16 [n_layers][batch][1 + S][heads][dim]
         per kind -- the request's odd last position (if any) followed by its new positions -- and the count of positions in front of
@@ -519,7 +573,7 @@ class SpeckvKVConnector:
             held.append(flat.index_select(1, self._spec_idx))
         return held[0], held[1], self._spec_base
 
-    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None):
+    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None):
         """One layer of a step that carries S new positions per request -- draft tokens to verify, a chunk of a prompt: query position
         j of a request sees everything the request holds (pool and odd last position) and the new positions 0..j.
         q [batch][S][heads][rows_per_pos][dim] fp16; k_new / v_new [batch][S][layers][heads][dim] fp16, the positions that would follow
@@ -528,11 +582,15 @@ class SpeckvKVConnector:
         Changes no state: lengths, tails and pool stay as they are -- append_tokens() commits what was accepted.
         The stored positions are read ONCE for up to 16 query rows per kv head: S * rows_per_pos <= 16 is one pass over the records,
         more goes in groups of 16 // rows_per_pos positions (spec_groups) with one pass each.  The held rows are folded in by one launch
-        per group (speckv_ext_attend_fold_held)."""
-        return self.attend_spec_layers(layer, 1, req_ids, q[None], k_new, v_new, sm_scale, n_new, stream)[0]
+        per group (speckv_ext_attend_fold_held).
+        parents (see tree_masks): the new positions form a tree instead of a chain -- node j sees what the request holds, its ancestors
+        and itself, not its siblings.  The pass over the records is the same; the held rows are folded in by
+        speckv_ext_attend_fold_masked, one launch per group, with the group's columns of the step's mask table (a node's ancestors in
+        earlier groups are held positions like any other).  Rows of dead nodes (>= n_new[b], or below one) are unspecified but finite."""
+        return self.attend_spec_layers(layer, 1, req_ids, q[None], k_new, v_new, sm_scale, n_new, stream, parents)[0]
 
     def attend_spec_layers(self, layer_begin: int, n_layers: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None,
-                           stream=None):
+                           stream=None, parents=None):
         """attend_spec for n_layers consecutive layers whose query rows exist at once: q [n_layers][batch][S][heads][rows_per_pos][dim],
         returns the same shape in fp32.  Per group of positions one speckv_ext_attend_planned_layers call and one fold launch over all
         the layers."""
@@ -559,7 +617,8 @@ class SpeckvKVConnector:
             self._plan_stream = st
             with torch.cuda.stream(st):
                 kh, vh, base = self._held_rows(req_ids, key, reqs, k_new, v_new, layer_begin, n_layers, st)
-                live = None if n_new is None else _device_index(n_new * NL)
+                live = None if n_new is None or parents is not None else _device_index(n_new * NL)
+                masks = None if parents is None else self._tree_table(key, reqs, parents, n_new, NL, S)
                 for j0, n in groups:
                     g = n * R
                     qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
@@ -571,6 +630,11 @@ class SpeckvKVConnector:
                     else:
                         self.lib.attend_planned_layers(self.scheme, self._plan.data_ptr(), B, layer_begin, NL, qg.data_ptr(), g, self._plan_bound,
                                                        sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
+                    if masks is not None:
+                        self.lib.attend_fold_masked(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
+                                                    masks.data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
+                        out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
+                        continue
                     d_base = base + j0 if j0 else base
                     d_live = None if live is None else (live - j0).clamp_(0, n)
                     self.lib.attend_fold_held(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
@@ -578,6 +642,60 @@ class SpeckvKVConnector:
                                               lse.data_ptr(), st.cuda_stream)
                     out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
         return out
+
+    def _tree_table(self, key, reqs, parents, n_new, n_layers, S):
+        """The mask words of a tree step on the device, int32 [n_layers * batch][S] (every layer the same words), kept per
+        (batch, epoch, layers, S, tree, live counts) as the gather indices of _held_rows are: the per-layer calls of a step find them
+        there -- the tree is judged (tree_masks) when the words are made, a call that finds them compares two tuples."""
+        import numbers
+        one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)      # one tree for every request
+        tkey = (key, self._epoch, n_layers, S, tuple(parents) if one else tuple(map(tuple, parents)), None if n_new is None else tuple(n_new))
+        if self._tree_key != tkey:
+            words = self.tree_masks(parents, [r.length & 1 for r in reqs], n_new)
+            if len(words[0]) != S:
+                raise ValueError("parents: one entry per new position")
+            self._tree_key, self._tree_masks = tkey, _device_index([w for row in words for w in row] * n_layers)
+        return self._tree_masks
+
+    def append_path(self, req_ids: Sequence[int], k_new, v_new, paths, parents=None, stream=None):
+        """Commit, per request, the nodes paths[b] of a tree step's S new positions k_new[b], v_new[b] ([batch][S][layers][heads][dim]
+        fp16): a chain from a child of the committed context down to some node, possibly empty -- the accepted path of a speculative
+        step.  With parents (see tree_masks) the chain is checked against the tree: parents[path[0]] == -1 and parents[path[i]] ==
+        path[i - 1]; without, the nodes must be in range and ascending.  A path that fails raises ValueError before any state changes.
+        The path's rows are gathered to the front of a [batch][longest path] tensor on the stream of the writes and go through
+        append_tokens with n_accept = len(path): the state that many single append() calls would leave.  Returns what append_tokens
+        returns."""
+        import torch
+        B, S = k_new.shape[0], k_new.shape[1]
+        paths = [[int(j) for j in path] for path in paths]
+        if len(paths) != B or len(req_ids) != B or tuple(v_new.shape) != tuple(k_new.shape) or tuple(k_new.shape[2:]) != (self.L, self.H, self.D):
+            raise ValueError("k_new / v_new must be [batch][S][layers][heads][dim], paths one list of nodes per request")
+        trees = None
+        if parents is not None:
+            trees = self._tree_parents(parents, B)
+            if len(trees[0]) != S:
+                raise ValueError("parents: one entry per new position")
+        for b, (rid, path) in enumerate(zip(req_ids, paths)):
+            if not all(0 <= j < S for j in path):
+                raise ValueError(f"request {rid}: path {path} leaves the step's 0..{S - 1} nodes")
+            if trees is not None:
+                if any(trees[b][j] != up for j, up in zip(path, [-1] + path)):
+                    raise ValueError(f"request {rid}: path {path} is not a chain of parents from the committed context")
+            elif any(j <= up for j, up in zip(path[1:], path)):
+                raise ValueError(f"request {rid}: path {path} does not ascend")
+            if self.requests[rid].length + len(path) > self.T:
+                raise ValueError(f"request {rid} is full")
+        n_accept = [len(path) for path in paths]
+        longest = max(n_accept, default=0)
+        if longest == 0:
+            return []
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):
+                idx = _device_index([b * S + (path[t] if t < len(path) else 0) for b, path in enumerate(paths) for t in range(longest)])
+                shape = (B, longest, self.L, self.H, self.D)
+                k_path = k_new.reshape(B * S, self.L, self.H, self.D).index_select(0, idx).view(shape)
+                v_path = v_new.reshape(B * S, self.L, self.H, self.D).index_select(0, idx).view(shape)
+        return self.append_tokens(req_ids, k_path, v_path, n_accept, stream)
 
     def append_tokens(self, req_ids: Sequence[int], k_new, v_new, n_accept: Sequence[int], stream=None):
         """Commit the first n_accept[b] (0..S) of the S new positions k_new[b], v_new[b] ([batch][S][layers][heads][dim] fp16) of every

@@ -88,6 +88,8 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_fold_tail": [c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_fold_held": [c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
                                     ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_fold_masked": [c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32,
+                                      ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_int4": [c_uint64, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_mx4": [c_uint64, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_mx4_batch": [c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
@@ -394,6 +396,14 @@ class SpeckvLib:
         j = row // rows_per_pos of sequence i sees held positions 0 .. d_base[i] + j; positions >= d_n_q[i] (0 / None: none) untouched."""
         self._ext("speckv_ext_attend_fold_held", n_rows, c_void_p(d_rows or 0), heads, g, rows_per_pos, c_void_p(d_q_f16), c_void_p(d_k_held),
                   c_void_p(d_v_held), seq_stride_elems, pos_stride_elems, c_void_p(d_base or 0), c_void_p(d_n_q or 0), ctypes.c_float(sm_scale),
+                  c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
+
+    def attend_fold_masked(self, n_rows, d_rows, heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems, d_mask,
+                           mask_stride, sm_scale, d_out, d_lse, stream=None):
+        """attend_fold_held with visibility from a mask table (a tree of drafts): query position j = row // rows_per_pos of sequence i sees
+        the held positions whose bits are set in the uint32 word d_mask[i * mask_stride + j]; a word of 0 leaves the position untouched."""
+        self._ext("speckv_ext_attend_fold_masked", n_rows, c_void_p(d_rows or 0), heads, g, rows_per_pos, c_void_p(d_q_f16), c_void_p(d_k_held),
+                  c_void_p(d_v_held), seq_stride_elems, pos_stride_elems, c_void_p(d_mask or 0), mask_stride, ctypes.c_float(sm_scale),
                   c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
 
     def attend_plan_bytes(self, n_seq):

@@ -482,6 +482,26 @@ speckv_status_t speckv_ext_attend_fold_held(uint32_t n_rows, const uint32_t* d_r
                                             const uint32_t* d_base, const uint32_t* d_n_q, float sm_scale, float* d_out,
                                             float* d_lse, void* stream);
 
+/* speckv_ext_attend_fold_masked: speckv_ext_attend_fold_held with visibility from a MASK instead of a causal chain -- the step of a
+ * speculative decoder that drafts a TREE (several continuations sharing a prefix; a node sees its ancestors, not its siblings).  The
+ * pass over the stored positions is the same (every query row sees every stored position); only this fold differs.
+ *   d_mask   : device array of 32-bit words; the word of sequence i (0..n_rows-1), query position j lies at i * mask_stride + j, with
+ *              mask_stride >= n_q = g / rows_per_pos.  Bit t set = held position t of sequence i is visible to query position j; the
+ *              visible positions are folded in ascending t, each by the formula of speckv_ext_attend_fold_tail.  Bits at or above
+ *              SPECKV_HELD_MAX are ignored.  A word of 0 leaves the rows of that query position exactly as they came in (a dead node
+ *              of a ragged step; the place of d_n_q).  The kernel reads no held position above the highest set bit of a word.
+ *   everything else -- d_rows, d_q_f16, d_out, d_lse (required), g, rows_per_pos, the held rows and their strides, stream -- as
+ *              speckv_ext_attend_fold_held.
+ * A causal chain is the mask (1 << (d_base[i] + j + 1)) - 1, with 0 for the positions >= d_n_q[i]: with those words this entry
+ * computes what speckv_ext_attend_fold_held computes.  Bad arguments (those speckv_ext_attend_fold_held refuses, a null d_mask,
+ * mask_stride < n_q) are SPECKV_ERR_INVAL before anything is launched.
+ * ONE launch for all sequences, heads, rows and positions, in place, nothing allocated, capturable. */
+speckv_status_t speckv_ext_attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g,
+                                              uint32_t rows_per_pos, const void* d_q_f16, const void* d_k_held,
+                                              const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                                              const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out,
+                                              float* d_lse, void* stream);
+
 /* ---- tier manager (CXLMemoryManager, cxl_memory_manager.h:40-90) ---------- */
 speckv_status_t speckv_ext_promote_to_l1(speckv_handle_t handle, uint64_t offset_bytes);
 speckv_status_t speckv_ext_demote_to_l3(speckv_handle_t handle, uint64_t offset_bytes);
