@@ -1458,39 +1458,63 @@ hipError_t launch_attend_fold_tail(uint32_t n_rows, const uint32_t* d_rows, uint
     return hipGetLastError();
 }
 
-// SEVERAL positions held outside the pool, folded causally (speckv_ext_attend_fold_held): a step that carries n_q query positions per
-// sequence (draft tokens to verify, a chunk of a prompt) has run them over the stored positions as g = n_q x rows_per_pos query rows
-// -- every query position sees all of those -- and now adds the fp16 K / V rows it still holds: `base` positions in front of query
-// position 0 (a connector's odd last position) and the new positions themselves.  Query position j folds held positions 0 .. base + j.
+// SEVERAL positions held outside the pool, folded into rows that already hold the attention over the stored positions
+// (speckv_ext_attend_fold_held / speckv_ext_attend_fold_masked): a step that carries n_q query positions per sequence (draft tokens to
+// verify, a chunk of a prompt) has run them over the stored positions as g = n_q x rows_per_pos query rows -- every query position sees
+// all of those -- and now adds the fp16 K / V rows it still holds: `base` positions in front of query position 0 (a connector's odd last
+// position) and the new positions themselves.  Which held positions a query position sees is all the two kernels differ in:
+//   HeldChain  causal: query position j sees held positions 0 .. base + j, itself included;
+//   HeldMask   a step whose drafts form a tree -- several continuations that share a prefix -- where a query position sees its ancestors
+//              only: bit t of mask[i * mask_stride + j] set = held position t of sequence i is visible to query position j; bits >=
+//              SPECKV_HELD_MAX are dropped.
 // One wave per (sequence, kv head, query position, R of its query rows); a lane holds two of the 128 dimensions.  The wave loads each
-// visible K row once for its R query rows, takes the maximum over the stored lse and every visible score first and weights once:
+// visible K row once for its R query rows, takes the maximum over the stored lse and every visible score first and weights once, visible
+// positions in ascending t:
 //   hi = max(lse, s_t);  den = exp(lse - hi) + sum exp(s_t - hi);  out = (out exp(lse - hi) + sum v_t exp(s_t - hi)) / den;  lse = hi + log den
-// which is the fold formula of k_attend_fold_tail applied once per visible position (fp32, but for the sum of a score).  Loops over the SPECKV_HELD_MAX positions are
-// unrolled and guarded by the wave-uniform count, so scores and rows stay in registers (the build checks: no scratch); the loads of the
-// rows go out before the first is used (index clamped to the last visible row: an address that exists, a line already on its way).
-// A wave of a position >= n_q_live[sequence] leaves without touching anything.
+// which is the fold formula of k_attend_fold_tail applied once per visible position (fp32, but for the sum of a score: see the body).
+// What a wave sees is the same for all its lanes and lives in scalar registers (the mask word through readfirstlane); the loops over the
+// SPECKV_HELD_MAX positions are unrolled and guarded by it, so scores and rows stay in registers (the build checks: no scratch).  All K
+// loads go out before the first is used, then all V loads; the load of an invisible t is redirected to a visible row -- the chain's last,
+// the mask's lowest: an address that exists, a line already on its way -- so a wave reads no held position above the highest it sees.
+// A wave with nothing to fold leaves without touching anything: a chain position >= n_q_live[sequence] (a ragged step), a mask word of 0
+// (a dead node).  Both kernels run the one body below, so a chain mask (1 << (base + j + 1)) - 1 gives bit for bit what the chain gives.
 constexpr uint32_t kHeldMax = 17;                      // SPECKV_HELD_MAX (include/speckv_ext.h)
+struct HeldChain {
+    uint32_t n;                                         // held positions 0 .. n - 1, n >= 1: a query position sees itself
+    __device__ bool sees(uint32_t t) const { return t < n; }
+    __device__ uint32_t row(uint32_t t) const { return min(t, n - 1u); }
+};
+struct HeldMask {
+    uint32_t bits, lo;                                  // the visible positions (!= 0) and the lowest of them
+    __device__ bool sees(uint32_t t) const { return (bits >> t) & 1u; }
+    __device__ uint32_t row(uint32_t t) const { return sees(t) ? t : lo; }
+};
+struct HeldWave { uint32_t c, j, head, i, lane; };     // chunk of R query rows, query position, kv head, sequence
+
 template <int R>
-__global__ __launch_bounds__(256) void k_attend_fold_held(uint32_t n_waves, const uint32_t* __restrict__ rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos,
-                                                          const f16x2* __restrict__ q, const f16x2* __restrict__ k_held, const f16x2* __restrict__ v_held,
-                                                          uint64_t seq_stride_h2, uint64_t pos_stride_h2, const uint32_t* __restrict__ base,
-                                                          const uint32_t* __restrict__ n_q_live, float sm_scale, float2* __restrict__ out, float* __restrict__ lse)
+__device__ __forceinline__ bool held_wave(uint32_t n_waves, uint32_t heads, uint32_t g, uint32_t rows_per_pos, HeldWave& at)
 {
     uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-    const uint32_t lane = threadIdx.x & 63u;
-    if (w >= n_waves) return;
+    at.lane = threadIdx.x & 63u;
+    if (w >= n_waves) return false;
     const uint32_t chunks = rows_per_pos / R, n_q = g / rows_per_pos;
-    const uint32_t c = w % chunks; w /= chunks;
-    const uint32_t j = w % n_q; w /= n_q;
-    const uint32_t head = w % heads, i = w / heads;
-    if (n_q_live && j >= n_q_live[i]) return;
-    const uint32_t n_vis = min(base[i] + j + 1u, kHeldMax);                 // >= 1: a query position sees itself
-    const uint32_t b = rows ? rows[i] : i;
-    const uint64_t row0 = (static_cast<uint64_t>(b) * heads + head) * g + j * rows_per_pos + c * R;
-    const uint64_t held_at = i * seq_stride_h2 + head * 64u + lane;
+    at.c = w % chunks; w /= chunks;
+    at.j = w % n_q; w /= n_q;
+    at.head = w % heads; at.i = w / heads;
+    return true;
+}
+
+template <int R, class Vis>
+__device__ __forceinline__ void fold_held_rows(const HeldWave& at, const Vis vis, const uint32_t* __restrict__ rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos,
+                                               const f16x2* __restrict__ q, const f16x2* __restrict__ k_held, const f16x2* __restrict__ v_held,
+                                               uint64_t seq_stride_h2, uint64_t pos_stride_h2, float sm_scale, float2* __restrict__ out, float* __restrict__ lse)
+{
+    const uint32_t lane = at.lane, b = rows ? rows[at.i] : at.i;
+    const uint64_t row0 = (static_cast<uint64_t>(b) * heads + at.head) * g + at.j * rows_per_pos + at.c * R;
+    const uint64_t held_at = at.i * seq_stride_h2 + at.head * 64u + lane;
     f16x2 kh[kHeldMax];
 #pragma unroll
-    for (uint32_t t = 0; t < kHeldMax; ++t) kh[t] = k_held[held_at + min(t, n_vis - 1u) * pos_stride_h2];
+    for (uint32_t t = 0; t < kHeldMax; ++t) kh[t] = k_held[held_at + vis.row(t) * pos_stride_h2];
     float2 qv[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -1500,7 +1524,7 @@ __global__ __launch_bounds__(256) void k_attend_fold_held(uint32_t n_waves, cons
     float sc[R][kHeldMax];
 #pragma unroll
     for (uint32_t t = 0; t < kHeldMax; ++t) {
-        if (t < n_vis) {
+        if (vis.sees(t)) {
             const float2 kv = make_float2(static_cast<float>(kh[t].x), static_cast<float>(kh[t].y));
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -1518,7 +1542,7 @@ __global__ __launch_bounds__(256) void k_attend_fold_held(uint32_t n_waves, cons
     }
     f16x2 vh[kHeldMax];
 #pragma unroll
-    for (uint32_t t = 0; t < kHeldMax; ++t) vh[t] = v_held[held_at + min(t, n_vis - 1u) * pos_stride_h2];
+    for (uint32_t t = 0; t < kHeldMax; ++t) vh[t] = v_held[held_at + vis.row(t) * pos_stride_h2];
     float2 acc[R];
     float den[R], hi[R];
 #pragma unroll
@@ -1534,7 +1558,7 @@ __global__ __launch_bounds__(256) void k_attend_fold_held(uint32_t n_waves, cons
     }
 #pragma unroll
     for (uint32_t t = 0; t < kHeldMax; ++t) {
-        if (t < n_vis) {
+        if (vis.sees(t)) {
             const float2 vv = make_float2(static_cast<float>(vh[t].x), static_cast<float>(vh[t].y));
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -1553,133 +1577,66 @@ __global__ __launch_bounds__(256) void k_attend_fold_held(uint32_t n_waves, cons
     }
 }
 
-hipError_t launch_attend_fold_held(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
-                                   const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
-                                   const uint32_t* d_base, const uint32_t* d_n_q, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+template <int R>
+__global__ __launch_bounds__(256) void k_attend_fold_held(uint32_t n_waves, const uint32_t* __restrict__ rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos,
+                                                          const f16x2* __restrict__ q, const f16x2* __restrict__ k_held, const f16x2* __restrict__ v_held,
+                                                          uint64_t seq_stride_h2, uint64_t pos_stride_h2, const uint32_t* __restrict__ base,
+                                                          const uint32_t* __restrict__ n_q_live, float sm_scale, float2* __restrict__ out, float* __restrict__ lse)
 {
-    if (rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > kHeldMax - 1u) return hipErrorInvalidValue;
-    const uint32_t r = rows_per_pos % 4u == 0 ? 4u : rows_per_pos % 2u == 0 ? 2u : 1u;        // query rows of one position a wave takes
-    const uint64_t n_waves = static_cast<uint64_t>(n_rows) * heads * (g / r);
-    if (n_waves == 0) return hipSuccess;
-    if (n_waves > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid(static_cast<uint32_t>((n_waves + 3u) / 4u));
-#define SPECKV_FOLD_HELD(R) hipLaunchKernelGGL(k_attend_fold_held<R>, grid, dim3(256), 0, s, static_cast<uint32_t>(n_waves), d_rows, heads, g, rows_per_pos, \
-                                               static_cast<const f16x2*>(d_q_f16), static_cast<const f16x2*>(d_k_held), static_cast<const f16x2*>(d_v_held),   \
-                                               seq_stride_elems / 2u, pos_stride_elems / 2u, d_base, d_n_q, sm_scale, reinterpret_cast<float2*>(d_out), d_lse)
-    if (r == 4u) SPECKV_FOLD_HELD(4); else if (r == 2u) SPECKV_FOLD_HELD(2); else SPECKV_FOLD_HELD(1);
-#undef SPECKV_FOLD_HELD
-    return hipGetLastError();
+    HeldWave at;
+    if (!held_wave<R>(n_waves, heads, g, rows_per_pos, at)) return;
+    if (n_q_live && at.j >= n_q_live[at.i]) return;
+    const HeldChain vis{min(base[at.i] + at.j + 1u, kHeldMax)};
+    fold_held_rows<R>(at, vis, rows, heads, g, rows_per_pos, q, k_held, v_held, seq_stride_h2, pos_stride_h2, sm_scale, out, lse);
 }
 
-// The same fold with visibility from a MASK instead of a causal count (speckv_ext_attend_fold_masked): a step whose drafts form a tree --
-// several continuations that share a prefix -- where a query position sees its ancestors only.  mask[i * mask_stride + j], bit t set =
-// held position t of sequence i is visible to query position j; bits >= SPECKV_HELD_MAX are dropped.  The word is the same for the whole
-// wave: it goes to a scalar register once, and the unrolled loops over the SPECKV_HELD_MAX positions are guarded by scalar bit tests, so
-// scores and rows stay in registers as in k_attend_fold_held (the build checks: no scratch).  Wave shape and arithmetic are those of
-// k_attend_fold_held -- fp32 products, their 64-lane sum and the sm_scale multiply in fp64, the maximum over the stored lse and every
-// visible score first, one weighting pass, visible positions in ascending t -- so a chain mask (1 << (base + j + 1)) - 1 gives what that
-// kernel gives.  All K loads go out before the first is used, then all V loads; the load of an invisible t is redirected to the lowest
-// visible row (an address that exists, a line already on its way), so a wave reads no held position above the highest bit of its mask.
-// A wave whose mask is 0 leaves without touching anything (a dead node of a ragged step).
 template <int R>
 __global__ __launch_bounds__(256) void k_attend_fold_masked(uint32_t n_waves, const uint32_t* __restrict__ rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos,
                                                             const f16x2* __restrict__ q, const f16x2* __restrict__ k_held, const f16x2* __restrict__ v_held,
                                                             uint64_t seq_stride_h2, uint64_t pos_stride_h2, const uint32_t* __restrict__ mask,
                                                             uint32_t mask_stride, float sm_scale, float2* __restrict__ out, float* __restrict__ lse)
 {
-    uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-    const uint32_t lane = threadIdx.x & 63u;
-    if (w >= n_waves) return;
-    const uint32_t chunks = rows_per_pos / R, n_q = g / rows_per_pos;
-    const uint32_t c = w % chunks; w /= chunks;
-    const uint32_t j = w % n_q; w /= n_q;
-    const uint32_t head = w % heads, i = w / heads;
-    const uint32_t vis = __builtin_amdgcn_readfirstlane(mask[static_cast<uint64_t>(i) * mask_stride + j]) & ((1u << kHeldMax) - 1u);
-    if (vis == 0) return;
-    const uint32_t t_lo = static_cast<uint32_t>(__builtin_ctz(vis));        // the row an invisible t loads instead of its own
-    const uint32_t b = rows ? rows[i] : i;
-    const uint64_t row0 = (static_cast<uint64_t>(b) * heads + head) * g + j * rows_per_pos + c * R;
-    const uint64_t held_at = i * seq_stride_h2 + head * 64u + lane;
-    f16x2 kh[kHeldMax];
-#pragma unroll
-    for (uint32_t t = 0; t < kHeldMax; ++t) kh[t] = k_held[held_at + ((vis >> t) & 1u ? t : t_lo) * pos_stride_h2];
-    float2 qv[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const f16x2 qh = q[(row0 + r) * 64u + lane];
-        qv[r] = make_float2(static_cast<float>(qh.x), static_cast<float>(qh.y));
-    }
-    float sc[R][kHeldMax];
-#pragma unroll
-    for (uint32_t t = 0; t < kHeldMax; ++t) {
-        if ((vis >> t) & 1u) {
-            const float2 kv = make_float2(static_cast<float>(kh[t].x), static_cast<float>(kh[t].y));
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                // (fp32 products, fp64 sum: see k_attend_fold_held)
-                double dot = static_cast<double>(qv[r].x * kv.x) + static_cast<double>(qv[r].y * kv.y);
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
-                sc[r][t] = static_cast<float>(dot * static_cast<double>(sm_scale));
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < R; ++r) sc[r][t] = -__builtin_inff();
-        }
-    }
-    f16x2 vh[kHeldMax];
-#pragma unroll
-    for (uint32_t t = 0; t < kHeldMax; ++t) vh[t] = v_held[held_at + ((vis >> t) & 1u ? t : t_lo) * pos_stride_h2];
-    float2 acc[R];
-    float den[R], hi[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const float old = lse[row0 + r];
-        hi[r] = old;
-#pragma unroll
-        for (uint32_t t = 0; t < kHeldMax; ++t) hi[r] = fmaxf(hi[r], sc[r][t]);
-        const float e_old = __expf(old - hi[r]);                             // old = -inf: 0
-        const float2 o = out[(row0 + r) * 64u + lane];
-        acc[r] = make_float2(o.x * e_old, o.y * e_old);
-        den[r] = e_old;
-    }
-#pragma unroll
-    for (uint32_t t = 0; t < kHeldMax; ++t) {
-        if ((vis >> t) & 1u) {
-            const float2 vv = make_float2(static_cast<float>(vh[t].x), static_cast<float>(vh[t].y));
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float e = __expf(sc[r][t] - hi[r]);
-                acc[r].x += vv.x * e;
-                acc[r].y += vv.y * e;
-                den[r] += e;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const float inv = 1.0f / den[r];
-        out[(row0 + r) * 64u + lane] = make_float2(acc[r].x * inv, acc[r].y * inv);
-        if (lane == 0) lse[row0 + r] = hi[r] + __logf(den[r]);
-    }
+    HeldWave at;
+    if (!held_wave<R>(n_waves, heads, g, rows_per_pos, at)) return;
+    const uint32_t bits = __builtin_amdgcn_readfirstlane(mask[static_cast<uint64_t>(at.i) * mask_stride + at.j]) & ((1u << kHeldMax) - 1u);
+    if (bits == 0) return;
+    const HeldMask vis{bits, static_cast<uint32_t>(__builtin_ctz(bits))};
+    fold_held_rows<R>(at, vis, rows, heads, g, rows_per_pos, q, k_held, v_held, seq_stride_h2, pos_stride_h2, sm_scale, out, lse);
+}
+
+// The launch of either fold: a wave takes R = 4 / 2 / 1 query rows of one position, whichever divides rows_per_pos (k4 / k2 / k1: the
+// kernel's three instances); a, b = what it takes between the strides and sm_scale (base and live counts, or the mask table and its stride).
+template <class Kernel, class A, class B>
+static hipError_t launch_fold_held_rows(Kernel k4, Kernel k2, Kernel k1, uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos,
+                                        const void* d_q_f16, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                                        A a, B b, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+{
+    if (rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > kHeldMax - 1u) return hipErrorInvalidValue;
+    const uint32_t r = rows_per_pos % 4u == 0 ? 4u : rows_per_pos % 2u == 0 ? 2u : 1u;
+    const uint64_t n_waves = static_cast<uint64_t>(n_rows) * heads * (g / r);
+    if (n_waves == 0) return hipSuccess;
+    if (n_waves > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(r == 4u ? k4 : r == 2u ? k2 : k1, dim3(static_cast<uint32_t>((n_waves + 3u) / 4u)), dim3(256), 0, s, static_cast<uint32_t>(n_waves),
+                       d_rows, heads, g, rows_per_pos, static_cast<const f16x2*>(d_q_f16), static_cast<const f16x2*>(d_k_held), static_cast<const f16x2*>(d_v_held),
+                       seq_stride_elems / 2u, pos_stride_elems / 2u, a, b, sm_scale, reinterpret_cast<float2*>(d_out), d_lse);
+    return hipGetLastError();
+}
+
+hipError_t launch_attend_fold_held(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
+                                   const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                                   const uint32_t* d_base, const uint32_t* d_n_q, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+{
+    return launch_fold_held_rows(k_attend_fold_held<4>, k_attend_fold_held<2>, k_attend_fold_held<1>, n_rows, d_rows, heads, g, rows_per_pos, d_q_f16,
+                                 d_k_held, d_v_held, seq_stride_elems, pos_stride_elems, d_base, d_n_q, sm_scale, d_out, d_lse, s);
 }
 
 hipError_t launch_attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
                                      const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
                                      const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
 {
-    if (rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > kHeldMax - 1u || mask_stride < g / rows_per_pos) return hipErrorInvalidValue;
-    const uint32_t r = rows_per_pos % 4u == 0 ? 4u : rows_per_pos % 2u == 0 ? 2u : 1u;        // as launch_attend_fold_held
-    const uint64_t n_waves = static_cast<uint64_t>(n_rows) * heads * (g / r);
-    if (n_waves == 0) return hipSuccess;
-    if (n_waves > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid(static_cast<uint32_t>((n_waves + 3u) / 4u));
-#define SPECKV_FOLD_MASKED(R) hipLaunchKernelGGL(k_attend_fold_masked<R>, grid, dim3(256), 0, s, static_cast<uint32_t>(n_waves), d_rows, heads, g, rows_per_pos, \
-                                                 static_cast<const f16x2*>(d_q_f16), static_cast<const f16x2*>(d_k_held), static_cast<const f16x2*>(d_v_held),     \
-                                                 seq_stride_elems / 2u, pos_stride_elems / 2u, d_mask, mask_stride, sm_scale, reinterpret_cast<float2*>(d_out), d_lse)
-    if (r == 4u) SPECKV_FOLD_MASKED(4); else if (r == 2u) SPECKV_FOLD_MASKED(2); else SPECKV_FOLD_MASKED(1);
-#undef SPECKV_FOLD_MASKED
-    return hipGetLastError();
+    if (rows_per_pos && mask_stride < g / rows_per_pos) return hipErrorInvalidValue;
+    return launch_fold_held_rows(k_attend_fold_masked<4>, k_attend_fold_masked<2>, k_attend_fold_masked<1>, n_rows, d_rows, heads, g, rows_per_pos, d_q_f16,
+                                 d_k_held, d_v_held, seq_stride_elems, pos_stride_elems, d_mask, mask_stride, sm_scale, d_out, d_lse, s);
 }
 
 hipError_t launch_attend_fp8_batch(const AttendArgs& a, uint32_t n_seq, float* d_out, float* d_lse, hipStream_t s)

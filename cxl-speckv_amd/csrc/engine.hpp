@@ -403,6 +403,10 @@ private:
     int attend_end(const SeqCall& c, hipStream_t s);
     int gather_members(bool batch_entry, int scheme, uint32_t n_seq, const uint64_t* handles, const uint32_t* pos_end, uint32_t layer, uint32_t max_pos_end,
                        hipStream_t s, BatchMembers& m);
+    // the folds of held rows: what attend_fold_held / _masked judge alike, and the launch bracket of those two and attend_fold_tail
+    static bool fold_held_args_ok(uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16, const void* d_k_held, const void* d_v_held,
+                                  uint64_t seq_stride_elems, uint64_t pos_stride_elems, const float* d_out, const float* d_lse);
+    template <class Launch> int launch_on(hipStream_t s, Launch launch);
     int take_seq_slot(size_t bytes, int* slot, void** staged);
     int ensure_zero_page(hipStream_t s);
     uint8_t* attend_scratch(AttendArgs& k, uint64_t parts, size_t head_bytes, hipStream_t s);

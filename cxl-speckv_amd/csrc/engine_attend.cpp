@@ -625,6 +625,17 @@ int Engine::attend_planned(int scheme, const void* d_plan, uint32_t n_seq, uint3
     return SPECKV_OK;
 }
 
+// A launch on the caller's stream; NULL: the engine's stream, synchronous (include/speckv_ext.h)
+template <class Launch>
+int Engine::launch_on(hipStream_t s, Launch launch)
+{
+    DeviceScope device_scope(device_);
+    if (!s) HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(launch(s ? s : stream_));
+    if (!s) HIP_TRY(hipStreamSynchronize(stream_));
+    return SPECKV_OK;
+}
+
 int Engine::attend_fold_tail(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, const void* d_q_f16, const void* d_k_tail,
                              const void* d_v_tail, uint64_t tail_stride_elems, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
 {
@@ -633,52 +644,45 @@ int Engine::attend_fold_tail(uint32_t n_rows, const uint32_t* d_rows, uint32_t h
     if (!d_q_f16 || !d_k_tail || !d_v_tail || !d_out || !d_lse || heads == 0 || g == 0 || g > 16 || tail_stride_elems % 2 ||
         tail_stride_elems < static_cast<uint64_t>(heads) * 128u)
         return SPECKV_ERR_INVAL;
-    DeviceScope device_scope(device_);
-    if (!s) HIP_TRY(hipDeviceSynchronize());                   // NULL: the engine's stream, synchronous (include/speckv_ext.h)
-    HIP_TRY(launch_attend_fold_tail(n_rows, d_rows, heads, g, d_q_f16, d_k_tail, d_v_tail, tail_stride_elems, sm_scale, d_out, d_lse,
-                                    s ? s : stream_));
-    if (!s) HIP_TRY(hipStreamSynchronize(stream_));
-    return SPECKV_OK;
+    return launch_on(s, [&](hipStream_t st) { return launch_attend_fold_tail(n_rows, d_rows, heads, g, d_q_f16, d_k_tail, d_v_tail, tail_stride_elems, sm_scale, d_out, d_lse, st); });
 }
 
-// speckv_ext_attend_fold_held: the arguments are judged before anything else, so a bad set is SPECKV_ERR_INVAL on every device.
+// What speckv_ext_attend_fold_held and speckv_ext_attend_fold_masked judge alike.  Both judge their arguments before anything else, so a
+// bad set is SPECKV_ERR_INVAL on every device.
+bool Engine::fold_held_args_ok(uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16, const void* d_k_held, const void* d_v_held,
+                               uint64_t seq_stride_elems, uint64_t pos_stride_elems, const float* d_out, const float* d_lse)
+{
+    if (heads == 0 || g == 0 || g > 16 || rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > SPECKV_HELD_MAX - 1u) return false;
+    const uint64_t n_q = g / rows_per_pos, row = static_cast<uint64_t>(heads) * 128u;
+    if (pos_stride_elems % 8u || seq_stride_elems % 8u || pos_stride_elems < row || seq_stride_elems < (n_q - 1u) * pos_stride_elems + row)
+        return false;                                           // (positions or sequences that overlap)
+    return d_q_f16 && d_k_held && d_v_held && d_out && d_lse;
+}
+
 int Engine::attend_fold_held(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
                              const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_base,
                              const uint32_t* d_n_q, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
 {
-    if (heads == 0 || g == 0 || g > 16 || rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > SPECKV_HELD_MAX - 1u) return SPECKV_ERR_INVAL;
-    const uint64_t n_q = g / rows_per_pos, row = static_cast<uint64_t>(heads) * 128u;
-    if (pos_stride_elems % 8u || seq_stride_elems % 8u || pos_stride_elems < row || seq_stride_elems < (n_q - 1u) * pos_stride_elems + row)
-        return SPECKV_ERR_INVAL;                                // (positions or sequences that overlap)
-    if (!d_q_f16 || !d_k_held || !d_v_held || !d_base || !d_out || !d_lse) return SPECKV_ERR_INVAL;
+    if (!fold_held_args_ok(heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems, d_out, d_lse) || !d_base)
+        return SPECKV_ERR_INVAL;
     if (null_) return no_data_path("speckv_ext_attend_fold_held");
     if (n_rows == 0) return SPECKV_OK;
-    DeviceScope device_scope(device_);
-    if (!s) HIP_TRY(hipDeviceSynchronize());                   // NULL: the engine's stream, synchronous (include/speckv_ext.h)
-    HIP_TRY(launch_attend_fold_held(n_rows, d_rows, heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems,
-                                    d_base, d_n_q, sm_scale, d_out, d_lse, s ? s : stream_));
-    if (!s) HIP_TRY(hipStreamSynchronize(stream_));
-    return SPECKV_OK;
+    return launch_on(s, [&](hipStream_t st) { return launch_attend_fold_held(n_rows, d_rows, heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems,
+                                                                             pos_stride_elems, d_base, d_n_q, sm_scale, d_out, d_lse, st); });
 }
 
-// speckv_ext_attend_fold_masked: judged as speckv_ext_attend_fold_held, the mask table in the place of d_base / d_n_q.
+// the mask table in the place of d_base / d_n_q
 int Engine::attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
                                const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask,
                                uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
 {
-    if (heads == 0 || g == 0 || g > 16 || rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > SPECKV_HELD_MAX - 1u) return SPECKV_ERR_INVAL;
-    const uint64_t n_q = g / rows_per_pos, row = static_cast<uint64_t>(heads) * 128u;
-    if (pos_stride_elems % 8u || seq_stride_elems % 8u || pos_stride_elems < row || seq_stride_elems < (n_q - 1u) * pos_stride_elems + row)
-        return SPECKV_ERR_INVAL;                                // (positions or sequences that overlap)
-    if (!d_q_f16 || !d_k_held || !d_v_held || !d_mask || mask_stride < n_q || !d_out || !d_lse) return SPECKV_ERR_INVAL;
+    if (!fold_held_args_ok(heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems, d_out, d_lse) || !d_mask ||
+        mask_stride < g / rows_per_pos)
+        return SPECKV_ERR_INVAL;
     if (null_) return no_data_path("speckv_ext_attend_fold_masked");
     if (n_rows == 0) return SPECKV_OK;
-    DeviceScope device_scope(device_);
-    if (!s) HIP_TRY(hipDeviceSynchronize());                   // NULL: the engine's stream, synchronous (include/speckv_ext.h)
-    HIP_TRY(launch_attend_fold_masked(n_rows, d_rows, heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems,
-                                      d_mask, mask_stride, sm_scale, d_out, d_lse, s ? s : stream_));
-    if (!s) HIP_TRY(hipStreamSynchronize(stream_));
-    return SPECKV_OK;
+    return launch_on(s, [&](hipStream_t st) { return launch_attend_fold_masked(n_rows, d_rows, heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems,
+                                                                               pos_stride_elems, d_mask, mask_stride, sm_scale, d_out, d_lse, st); });
 }
 
 // Launch geometry of the whole-record INT4 kernel (k_attend_int4_wg8; 512-thread workgroups, two resident per CU); `cus` = the
