@@ -165,21 +165,27 @@ int Engine::write_async(uint64_t handle, uint64_t off, const void* d_src, size_t
 // write_strided for a batch of allocations in one launch (the append of a decode step: SURVEY 8f row N2), and several
 // page runs of ONE allocation in one launch (a prompt's K / V regions: speckv_ext_write_runs).  Host side as in
 // write_strided per group (cached pages are invalidated first); the kernel takes one descriptor per group.
+// `rows` set: the pair-gather form (speckv_ext_write_pairs) -- a group is a position pair of 2 * n_layers pages read from four
+// rows (d_srcs holds four pointers per group), and an allocation may have several groups as long as they share no page.
 int Engine::write_groups(const uint64_t* handles, const uint64_t* firsts, const void* const* d_srcs, uint32_t n_groups,
-                         uint64_t step, uint64_t n_each, hipStream_t s, bool same_allocation)
+                         uint64_t step, uint64_t n_each, hipStream_t s, bool same_allocation, const PairRows* rows)
 {
     if (!handles || !firsts || !d_srcs || step == 0 || !s) return SPECKV_ERR_INVAL;
+    if (rows && rows->layer_stride % 16u) return SPECKV_ERR_INVAL;
     if (n_groups == 0 || n_each == 0) return SPECKV_OK;
     std::vector<Allocation*> as(n_groups);
     bool cached = false;
     for (uint32_t i = 0; i < n_groups; ++i) {
         Allocation* a = find(handles[same_allocation ? 0 : i]);
         if (!a) return SPECKV_ERR_GENERAL;
-        if (!d_srcs[i]) return SPECKV_ERR_INVAL;
+        if (rows) {
+            for (uint32_t k = 0; k < 4; ++k)
+                if (!d_srcs[4u * i + k] || reinterpret_cast<uintptr_t>(d_srcs[4u * i + k]) % 16u) return SPECKV_ERR_INVAL;
+        } else if (!d_srcs[i]) return SPECKV_ERR_INVAL;
         if (a->scheme != find(handles[0])->scheme) return SPECKV_ERR_INVAL;
         if (firsts[i] >= a->n_pages || (n_each - 1) > (a->n_pages - 1 - firsts[i]) / step) return SPECKV_ERR_GENERAL;
         if (a->size_bytes % kPageSize && firsts[i] + (n_each - 1) * step == a->n_pages - 1) return SPECKV_ERR_INVAL;
-        if (!same_allocation)
+        if (!same_allocation && !rows)
             for (uint32_t k = 0; k < i; ++k) if (as[k] == a) return SPECKV_ERR_INVAL;   // one descriptor per allocation
         as[i] = a;
         for (uint64_t j = 0; j < n_each && !cached; ++j) cached = (res_flags(a, firsts[i] + j * step) & 3u) != 0;
@@ -202,6 +208,17 @@ int Engine::write_groups(const uint64_t* handles, const uint64_t* firsts, const 
             for (uint32_t i = 1; i < n_groups; ++i)
                 if ((order[i] - order[0]) % step == 0 && order[i] - order[0] <= span) return SPECKV_ERR_INVAL;
     }
+    if (rows && n_groups > 1) {                                 // the pairs of one allocation must not share a page
+        std::vector<uint32_t> order(n_groups);
+        for (uint32_t i = 0; i < n_groups; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+            return handles[x] != handles[y] ? handles[x] < handles[y] : firsts[x] < firsts[y]; });
+        for (uint32_t i = 1; i < n_groups; ++i)
+            for (uint32_t k = i; k-- > 0 && handles[order[k]] == handles[order[i]];) {
+                const uint64_t d = firsts[order[i]] - firsts[order[k]];
+                if (d % step == 0 && d / step < n_each) return SPECKV_ERR_INVAL;
+            }
+    }
     DeviceScope device_scope(device_);
     if (cached || !flights_.empty() || ring_busy_ > 0) {
         RC_TRY(quiesce());
@@ -213,7 +230,7 @@ int Engine::write_groups(const uint64_t* handles, const uint64_t* firsts, const 
         RC_TRY(wait_stream());
     }
     // descriptors: pinned slot -> device slot (4 of each in rotation, guarded by an event on the caller's stream)
-    const size_t bytes = static_cast<size_t>(n_groups) * sizeof(CompressGroup);
+    const size_t bytes = static_cast<size_t>(n_groups) * (rows ? sizeof(CommitPair) : sizeof(CompressGroup));
     if (grp_ring_.slot_bytes < bytes) {
         HIP_TRY(hipDeviceSynchronize());
         if (grp_ring_.base) { (void)hipHostFree(grp_ring_.base); grp_ring_.base = nullptr; }
@@ -229,23 +246,41 @@ int Engine::write_groups(const uint64_t* handles, const uint64_t* firsts, const 
     RC_TRY(wait_event(grp_ring_.ev[slot]));                   // may release the ABI lock
     for (uint32_t i = 0; i < n_groups; ++i)
         if ((as[i] = find(handles[same_allocation ? 0 : i])) == nullptr) return SPECKV_ERR_GENERAL;
-    CompressGroup* staged = reinterpret_cast<CompressGroup*>(static_cast<uint8_t*>(grp_ring_.base) + static_cast<size_t>(slot) * grp_ring_.slot_bytes);
-    CompressGroup* d_slot = reinterpret_cast<CompressGroup*>(reinterpret_cast<uint8_t*>(d_groups_) + static_cast<size_t>(slot) * grp_ring_.slot_bytes);
+    void* staged = static_cast<uint8_t*>(grp_ring_.base) + static_cast<size_t>(slot) * grp_ring_.slot_bytes;
+    void* d_slot = reinterpret_cast<uint8_t*>(d_groups_) + static_cast<size_t>(slot) * grp_ring_.slot_bytes;
     for (uint32_t i = 0; i < n_groups; ++i) {
         const Allocation* a = as[i];
-        staged[i] = CompressGroup{a->d_entries, a->d_scale_tab, a->region_pages, a->scale_run, firsts[i],
-                                  static_cast<const uint8_t*>(d_srcs[i])};
+        if (rows) {
+            const void* const* r = d_srcs + 4u * i;
+            static_cast<CommitPair*>(staged)[i] = CommitPair{a->d_entries, a->d_scale_tab, a->region_pages, a->scale_run, firsts[i],
+                {static_cast<const uint8_t*>(r[0]), static_cast<const uint8_t*>(r[1]), static_cast<const uint8_t*>(r[2]), static_cast<const uint8_t*>(r[3])}};
+        } else {
+            static_cast<CompressGroup*>(staged)[i] = CompressGroup{a->d_entries, a->d_scale_tab, a->region_pages, a->scale_run, firsts[i],
+                                                                   static_cast<const uint8_t*>(d_srcs[i])};
+        }
     }
     HIP_TRY(hipMemcpyAsync(d_slot, staged, bytes, hipMemcpyHostToDevice, s));
     CodecArgs c{};
-    c.groups = d_slot;
-    c.group_n = n_each;
-    c.page_step = step;
-    c.data_stride = kPageSize;
-    c.scheme = as[0]->scheme;
-    c.quant_mode = quant_mode_;
     c.n = static_cast<uint64_t>(n_groups) * n_each;
-    HIP_TRY(launch_compress(c, s));
+    if (rows) {
+        PairArgs pa{};
+        pa.pairs = static_cast<const CommitPair*>(d_slot);
+        pa.n_pairs = n_groups;
+        pa.n_layers = rows->n_layers;
+        pa.page_step = step;
+        pa.layer_stride = rows->layer_stride;
+        pa.scheme = as[0]->scheme;
+        pa.quant_mode = quant_mode_;
+        HIP_TRY(launch_compress_pairs(pa, s));
+    } else {
+        c.groups = static_cast<const CompressGroup*>(d_slot);
+        c.group_n = n_each;
+        c.page_step = step;
+        c.data_stride = kPageSize;
+        c.scheme = as[0]->scheme;
+        c.quant_mode = quant_mode_;
+        HIP_TRY(launch_compress(c, s));
+    }
     for (uint32_t i = 0; i < n_groups; ++i) {           // the kernel is queued: host mirror first, then the orderings
         Allocation* a = as[i];
         note_use(a, s);
@@ -269,6 +304,16 @@ int Engine::write_strided_batch(const uint64_t* handles, const uint64_t* firsts,
 {
     if (null_) return no_data_path("speckv_ext_write_strided_batch");
     return write_groups(handles, firsts, d_srcs, n_alloc, step, n_each, s, false);
+}
+
+// speckv_ext_write_pairs: the commit of a multi-position step.  Pair i is pages first + j * step, j < 2 * n_layers, of
+// handles[i], encoded from d_rows[4 i .. 4 i + 3] (K even, K odd, V even, V odd), layer_stride bytes apart per layer.
+int Engine::write_pairs(const uint64_t* handles, const uint64_t* firsts, const void* const* d_rows, uint32_t n_pairs, uint64_t step,
+                        uint32_t n_layers, uint64_t layer_stride, hipStream_t s)
+{
+    if (null_) return no_data_path("speckv_ext_write_pairs");
+    const PairRows rows{n_layers, layer_stride};
+    return write_groups(handles, firsts, d_rows, n_pairs, step, 2ull * n_layers, s, false, &rows);
 }
 
 int Engine::write_runs(uint64_t handle, const uint64_t* firsts, const void* const* d_srcs, uint32_t n_runs, uint64_t n_each, hipStream_t s)

@@ -928,18 +928,34 @@ __device__ __forceinline__ uint32_t encode_rle_fast(const uint4 (&raw)[4], float
     return icarry;
 }
 
+// Where a block's 4096 source bytes lie.  SrcRun: one contiguous image.  SrcPair: two rows of 2048 bytes anywhere -- the even
+// and the odd position of a position pair, gathered by the encoder itself (k_compress_pairs) instead of being copied into a
+// page image first.  chunk(j, lane): this lane's j-th 16-byte load (elements [512 j + 8 lane, + 8)); elem(p): element p.  The
+// half a load falls into is a compile-time (chunk) or wave-uniform (elem: the out-of-line paths step 64 elements at a time) choice.
+struct SrcRun {
+    const uint8_t* p;
+    __device__ __forceinline__ const uint8_t* chunk(int j, uint32_t lane) const { return p + 2ull * (512u * j + 8u * lane); }
+    __device__ __forceinline__ const uint8_t* elem(uint32_t e) const { return p + 2ull * e; }
+};
+struct SrcPair {
+    const uint8_t* lo;
+    const uint8_t* hi;
+    __device__ __forceinline__ const uint8_t* chunk(int j, uint32_t lane) const { return (j < 2 ? lo : hi) + 2ull * (512u * (j & 1) + 8u * lane); }
+    __device__ __forceinline__ const uint8_t* elem(uint32_t e) const { return e < 1024u ? lo + 2ull * e : hi + 2ull * (e - 1024u); }
+};
+
 // General path (long stretches: zeros, constants; blocks with inf / NaN): one element per lane per step, rolled,
 // quantised with the exact scalar form straight from the source; stretch starts by max-scan, a run starts every 255
 // elements of a stretch.
-template <int MODE>
-__device__ __noinline__ uint32_t encode_rle_general(const uint8_t* __restrict__ src, float scale, uint8_t* wl, uint32_t lane)
+template <int MODE, class SRC>
+__device__ __forceinline__ uint32_t encode_rle_general_from(const SRC src, float scale, uint8_t* wl, uint32_t lane)
 {
     const uint32_t pair_addr = lds_addr_of(wl + kEncPairOff);
     uint32_t qtail = 0, dtail = 0, scarry = 0, mcarry = 0, icarry = 0;
 #pragma unroll 1
     for (uint32_t step = 0; step < kBlockElems / 64u; ++step) {
         const uint32_t p = 64u * step + lane;
-        const uint32_t qv = quantize<MODE>(half_bits_to_float(gload<uint16_t>(src + 2ull * p)), scale);
+        const uint32_t qv = quantize<MODE>(half_bits_to_float(gload<uint16_t>(src.elem(p))), scale);
         const uint32_t prevq = wave_shr1(qv, qtail);
         qtail = lane63(qv);
         const uint32_t d = (qv - prevq) & 0xFFu;
@@ -964,15 +980,27 @@ __device__ __noinline__ uint32_t encode_rle_general(const uint8_t* __restrict__ 
     lds_store_b8(pair_addr + 2u * icarry - 1u, kBlockElems + 1u - mcarry);
     return icarry;
 }
+// Out of line for a contiguous image.  The pair form takes the body inline: device functions are emitted in front of the
+// kernels, and one more of them would move every kernel away from decode_rle_general (the note on emission order below).
+template <int MODE>
+__device__ __noinline__ uint32_t encode_rle_general(const uint8_t* __restrict__ src, float scale, uint8_t* wl, uint32_t lane)
+{
+    return encode_rle_general_from<MODE>(SrcRun{src}, scale, wl, lane);
+}
+template <int MODE>
+__device__ __forceinline__ uint32_t encode_rle_general(const SrcRun src, float scale, uint8_t* wl, uint32_t lane) { return encode_rle_general<MODE>(src.p, scale, wl, lane); }
+template <int MODE>
+__device__ __forceinline__ uint32_t encode_rle_general(const SrcPair src, float scale, uint8_t* wl, uint32_t lane) { return encode_rle_general_from<MODE>(src, scale, wl, lane); }
 
 // the reference's own rule for blocks that hold inf / NaN: a NaN never wins the '>' compare (cache_engine.cpp:176-180).
 // Rare, out of line, and fed from memory again (a register array passed by reference would move to scratch).
-__device__ __noinline__ float absmax_with_nonfinite(const uint8_t* __restrict__ src, uint32_t lane)
+template <class SRC>
+__device__ __forceinline__ float absmax_with_nonfinite_from(const SRC src, uint32_t lane)
 {
     float mx = 0.0f;
 #pragma unroll 1
     for (uint32_t p = lane; p < kBlockElems; p += 64u)
-        mx = __builtin_fmaxf(mx, fabsf(half_bits_to_float(gload<uint16_t>(src + 2ull * p))));
+        mx = __builtin_fmaxf(mx, fabsf(half_bits_to_float(gload<uint16_t>(src.elem(p)))));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float other = __shfl_xor(mx, o);
@@ -980,15 +1008,354 @@ __device__ __noinline__ float absmax_with_nonfinite(const uint8_t* __restrict__ 
     }
     return mx;
 }
+__device__ __noinline__ float absmax_with_nonfinite(const uint8_t* __restrict__ src, uint32_t lane) { return absmax_with_nonfinite_from(SrcRun{src}, lane); }
+__device__ __forceinline__ float absmax_with_nonfinite(const SrcRun src, uint32_t lane) { return absmax_with_nonfinite(src.p, lane); }
+__device__ __forceinline__ float absmax_with_nonfinite(const SrcPair src, uint32_t lane) { return absmax_with_nonfinite_from(src, lane); }
 
 // ===================================================================
 // encode  (cache_engine.cpp:40-82,172-239)
 // ===================================================================
+// Where one block's record goes: the page table of its allocation (engine form) or the raw arrays of the codec operators.
+struct EncTarget {
+    PageEntry* entries;
+    float*     scale_tab;
+    uint32_t   region_pages, scale_run;
+    uint32_t*  len_samples;
+    uint8_t*   recs;              // raw form (entries == nullptr)
+    uint64_t   rec_stride;
+    uint32_t*  rec_bytes;
+    float*     scales;
+};
+
+// One block: 4096 source bytes (SRC says where they are) -> the record of `page`, its length, scale and table words.  The one
+// body of every encoder kernel: k_compress reads a contiguous image, k_compress_pairs two rows.
+template <int SCHEME, int MODE, class SRC>
+__device__ __forceinline__ void compress_block(const EncTarget& t, const uint64_t page, const SRC src, uint16_t* lds, const uint32_t lane, const uint32_t wave)
+{
+    PageEntry* const entries = t.entries;
+    float* const scale_tab = t.scale_tab;
+    const uint32_t region_pages = t.region_pages, scale_run = t.scale_run;
+    uint8_t* rec = entries ? reinterpret_cast<uint8_t*>(gload<uint64_t>(&entries[page].pool_addr))
+                           : t.recs + page * t.rec_stride;
+    // MXFP4 in the pool is tile-planar (kernels.hpp): the codes go mx4_code_delta behind the nibbles -- the entry's scale word
+    uint8_t* rec_codes = rec + 1024u;
+    if (SCHEME == kMxFp4 && entries) rec_codes = rec + gload<uint32_t>(reinterpret_cast<const uint32_t*>(&entries[page].scale));
+    uint32_t out_len;
+    float scale = 1.0f;
+
+    uint4 raw[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        raw[j] = enc_ld16(src.chunk(j, lane));
+
+    if (SCHEME == kFp16) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            enc_st16(rec + 2ull * (512u * j + 8u * lane), raw[j]);
+        out_len = 2u * kBlockElems;
+    } else if (SCHEME == kInt4G32) {
+        // per group of 32 elements (4 lanes x 8): s = fp16(max|x|/7), q = clamp(round(x/s), -7, 7).  The group's max|x| and
+        // its "all finite" test come from the fp16 bit patterns (v_pk_max_u16, two elements per instruction), the
+        // quantisation runs in packed fp32 (the same multiply / fma / fma / add / truncate per element as the scalar form,
+        // so the same bits).  Round 4, instruction count (the kernel ran 18 % over what the chip moves at its read : write
+        // mix, profiles/r04_store_shape.txt): max|x| / 7 and 1 / s without the IEEE divide (codec_device.hpp: two and three
+        // operations, bit-identical for fp16-valued operands); no clamp when every scale of the chunk is a normal fp16
+        // (then no quotient reaches 7.5); the nibbles summed as signed i << 4k and un-biased once per dword.
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t words[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};
+            u16x2 m2 = {0, 0};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, words[t] & 0x7FFF7FFFu));
+            uint32_t mbits = m2.x > m2.y ? m2.x : m2.y;                 // largest |bits| of the lane's 8 elements
+            mbits = umax(mbits, dpp<0xB1>(0u, mbits));                  // quad_perm [1,0,3,2]: lane ^ 1
+            mbits = umax(mbits, dpp<0x4E>(0u, mbits));                  // quad_perm [2,3,0,1]: lane ^ 2 -> the group of 32
+            const bool finite = __ballot(mbits >= 0x7C00u) == 0ull;     // wave-uniform: no inf / NaN in any group of this chunk
+            uint32_t nib = 0;
+            _Float16 s16;
+            if (finite) {
+                float sdiv = div7_of_f16_value(half_bits_to_float(mbits));
+                asm volatile("" : "+v"(sdiv));                      // keep the fp32 rounding of the divide
+                s16 = static_cast<_Float16>(sdiv);
+                const float sc = static_cast<float>(s16);
+                // |x| <= 7.5*sc in a finite group: the reciprocal divide is exact (test_fast_division_is_exact); a scale that
+                // rounds to zero (subnormal groups) gives rcp = 0 and every quotient 0, as the definition says
+                const float rcp = sc != 0.0f ? rcp_of_f16_value(sc) : 0.0f;
+                const f32x2 ss = {sc, sc}, rr = {rcp, rcp};
+                // a subnormal scale may be off by more than half a step: only then can a quotient leave [-7.5, 7.5]
+                const uint32_t sbits = __builtin_bit_cast(uint16_t, s16);
+                const bool clamp = __ballot(sbits - 1u < 0x3FFu) != 0ull;                   // (wave-uniform)
+                int iq[8];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    f32x2 x;
+                    x.x = half_bits_to_float(words[t] & 0xFFFFu);
+                    x.y = half_bits_to_float(words[t] >> 16);
+                    const f32x2 q0 = x * rr;
+                    const f32x2 e = __builtin_elementwise_fma(-q0, ss, x);
+                    const f32x2 y = __builtin_elementwise_fma(e, rr, q0);
+                    f32x2 h;
+                    h.x = __builtin_copysignf(0.5f, y.x);
+                    h.y = __builtin_copysignf(0.5f, y.y);
+                    const f32x2 r = y + h;                          // round half away from zero = truncate(y + copysign(0.5, y))
+                    iq[2 * t] = static_cast<int>(r.x);
+                    iq[2 * t + 1] = static_cast<int>(r.y);
+                }
+                if (clamp) {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) iq[k] = min(max(iq[k], -7), 7);
+                }
+                // nibble k = iq[k] & 0xF:  sum of iq[k] << 4k  =  sum of (iq[k] + 8) << 4k  -  0x88888888, and (i + 8) ^ 8 = i & 0xF
+                uint32_t acc = 0x88888888u;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc += static_cast<uint32_t>(iq[k]) << (4 * k);
+                nib = acc ^ 0x88888888u;
+            } else {
+                float xv[8];
+                float mx = 0.0f, nanacc = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    xv[k] = half_bits_to_float((words[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu);
+                    absmax_finite(xv[k], mx, nanacc);
+                }
+                float o = __shfl_xor(mx, 1); mx = (o > mx) ? o : mx;
+                o = __shfl_xor(mx, 2);       mx = (o > mx) ? o : mx;
+                float sdiv = mx / 7.0f;
+                asm volatile("" : "+v"(sdiv));
+                s16 = static_cast<_Float16>(sdiv);
+                const float sc = static_cast<float>(s16);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    float r = 0.0f;
+                    if (sc != 0.0f && sc == sc) {
+                        r = roundf(xv[k] / sc);
+                        if (!(r == r)) r = 0.0f;
+                        r = fminf(fmaxf(r, -7.0f), 7.0f);
+                    }
+                    nib |= (static_cast<uint32_t>(static_cast<int>(r)) & 0xFu) << (4 * k);
+                }
+            }
+            // The record is assembled in LDS and leaves as whole 16-byte pieces per lane: written straight from the
+            // registers it took eight store instructions of 4 / 2 bytes per lane (0.63-0.65 of HBM peak).
+            const uint32_t p0 = 512u * j + 8u * lane;
+            uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kInt4RecBytes;
+            *reinterpret_cast<uint32_t*>(wl + 128u + (p0 >> 1)) = nib;
+            if ((lane & 3u) == 0u)
+                *reinterpret_cast<uint16_t*>(wl + 2u * (p0 >> 5)) = __builtin_bit_cast(uint16_t, s16);
+        }
+        {
+            uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kInt4RecBytes;
+            wave_lds_fence();
+            enc_st16(rec + 128u + 16u * lane, *reinterpret_cast<const uint4*>(wl + 128u + 16u * lane));
+            if (lane < 8u) enc_st16(rec + 16u * lane, *reinterpret_cast<const uint4*>(wl + 16u * lane));
+            wave_lds_fence();
+        }
+        out_len = kInt4RecBytes;
+    } else if (SCHEME == kMxFp4) {
+        // OCP MX v1.0 conversion (oracle: compress_mxfp4) over the block's two halves interleaved element by element: byte i of the
+        // record = element i (low nibble) and element 1024 + i (high), one E8M0 code per 16 bytes.  This lane's raw[j] and
+        // raw[j + 2] (j = 0, 1) are exactly such partners -- elements [512 j + 8 l, + 8) and the same 1024 further on -- so the
+        // interleave never leaves the lane; a block of 32 = this lane's and lane ^ 1's 8 + 8 elements of both halves.
+        //   code = floor(log2 max|x|) - 2 + 127 = the exponent field of max|x| as a float, minus 2
+        //   q    = E2M1 of x / 2^(code-127), nearest even, saturating: one v_cvt_scalef32_pk_fp4_f16 per element pair (it divides
+        //          by the power of two its scale operand's exponent names: profiles/probes/mxprobe.hip)
+        typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t w0[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};                    // first half: elements 2t, 2t+1 per word
+            const uint32_t w1[4] = {raw[j + 2].x, raw[j + 2].y, raw[j + 2].z, raw[j + 2].w};    // their partners in the second half
+            u16x2 m2 = {0, 0};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, w0[t] & 0x7FFF7FFFu));
+                m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, w1[t] & 0x7FFF7FFFu));
+            }
+            uint32_t mbits = m2.x > m2.y ? m2.x : m2.y;                 // largest |bits| of the lane's 16 elements
+            mbits = umax(mbits, dpp<0xB1>(0u, mbits));                  // lane ^ 1 -> the block of 32
+            const bool finite = __ballot(mbits >= 0x7C00u) == 0ull;     // wave-uniform: no inf / NaN in any block of this chunk
+            uint32_t nib[2] = {0u, 0u}, code = 0;
+            if (finite) {
+                code = mbits ? (__float_as_uint(half_bits_to_float(mbits)) >> 23) - 2u : 0u;
+                const float sc = mbits ? __uint_as_float(code << 23) : 1.0f;      // (code >= 101 for any non-zero fp16: a normal float)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    // (element 2t of both halves), (element 2t+1 of both halves) -> bytes 2t, 2t+1
+                    const f16x2v ea = __builtin_bit_cast(f16x2v, __builtin_amdgcn_perm(w1[t], w0[t], 0x05040100u));
+                    const f16x2v eb = __builtin_bit_cast(f16x2v, __builtin_amdgcn_perm(w1[t], w0[t], 0x07060302u));
+                    uint32_t& o = nib[t >> 1];
+                    if (t & 1) { o = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(o, ea, sc, 2); o = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(o, eb, sc, 3); }
+                    else       { o = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(o, ea, sc, 0); o = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(o, eb, sc, 1); }
+                }
+            } else {
+                // a chunk with inf / NaN somewhere: NaN elements are skipped in the maximum and store +0, inf counts as 65504
+                float x0[8], x1[8];
+                float mx = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    float a0 = half_bits_to_float((w0[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu), a1 = half_bits_to_float((w1[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu);
+                    a0 = (a0 == a0) ? fminf(fmaxf(a0, -65504.0f), 65504.0f) : 0.0f;
+                    a1 = (a1 == a1) ? fminf(fmaxf(a1, -65504.0f), 65504.0f) : 0.0f;
+                    x0[k] = a0; x1[k] = a1;
+                    mx = fmaxf(mx, fmaxf(fabsf(a0), fabsf(a1)));
+                }
+                const float o = __shfl_xor(mx, 1);
+                mx = (o > mx) ? o : mx;
+                code = mx > 0.0f ? (__float_as_uint(mx) >> 23) - 2u : 0u;
+                const float sc = mx > 0.0f ? __uint_as_float(code << 23) : 1.0f;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    uint32_t& ob = nib[k >> 2];
+                    switch (k & 3) {
+                    case 0: ob = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(ob, x0[k], x1[k], sc, 0); break;
+                    case 1: ob = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(ob, x0[k], x1[k], sc, 1); break;
+                    case 2: ob = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(ob, x0[k], x1[k], sc, 2); break;
+                    default: ob = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(ob, x0[k], x1[k], sc, 3); break;
+                    }
+                    // a NaN element keeps no sign: +0
+                    if (((w0[k >> 1] >> ((k & 1) * 16)) & 0x7FFFu) > 0x7C00u) ob &= ~(0x0Fu << (8 * (k & 3)));
+                    if (((w1[k >> 1] >> ((k & 1) * 16)) & 0x7FFFu) > 0x7C00u) ob &= ~(0xF0u << (8 * (k & 3)));
+                }
+            }
+            // the record is assembled in LDS and leaves as whole 16-byte pieces per lane (as the INT4 record does)
+            const uint32_t p0 = 512u * j + 8u * lane;
+            uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kMx4RecBytes;
+            *reinterpret_cast<uint2*>(wl + p0) = make_uint2(nib[0], nib[1]);
+            if ((lane & 1u) == 0u) wl[1024u + (p0 >> 4)] = static_cast<uint8_t>(code);
+        }
+        {
+            uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kMx4RecBytes;
+            wave_lds_fence();
+            enc_st16(rec + 16u * lane, *reinterpret_cast<const uint4*>(wl + 16u * lane));
+            if (lane < 4u) enc_st16(rec_codes + 16u * lane, *reinterpret_cast<const uint4*>(wl + 1024u + 16u * lane));
+            wave_lds_fence();
+        }
+        out_len = kMx4RecBytes;
+    } else if (SCHEME == kFp8E4m3) {
+        float x[4][8];
+        float mx = 0.0f, nanacc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t words[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                x[j][k] = half_bits_to_float((words[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu);
+                absmax_finite(x[j][k], mx, nanacc);
+            }
+        }
+        // (mx is never a NaN and never negative: its bit pattern orders like its value -- the DPP max scan of the encoders
+        // instead of six trips through the LDS crossbar)
+        mx = __uint_as_float(lane63(wave_incl_max(__float_as_uint(mx))));
+        const bool finite = __ballot(!(nanacc == 0.0f)) == 0ull;       // wave-uniform
+        // a finite block's max|x| is an fp16 value: its scale and the reciprocal without the IEEE divide, bit-identical
+        // (codec_device.hpp; exhaustive: test_fast_division_is_exact)
+        scale = (mx > 0.0f) ? (finite ? div448_of_f16_value(mx) : mx / 448.0f) : 1.0f;
+        const float rcp = finite ? rcp_of_scale(scale) : 1.0f / scale;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float v[8];
+            if (finite) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    v[k] = fminf(fmaxf(__builtin_copysignf(div_by_scale(x[j][k], scale, rcp), x[j][k]), -448.0f), 448.0f);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = fminf(fmaxf(x[j][k] / scale, -448.0f), 448.0f);
+            }
+            int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+            lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
+            int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], 0, false);
+            hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
+            enc_st8(rec + 512u * j + 8u * lane, make_uint2(static_cast<uint32_t>(lo), static_cast<uint32_t>(hi)));
+        }
+        out_len = kBlockElems;
+    } else {
+        const uint32_t mbits = absmax_bits(raw);                       // wave-uniform
+        const bool finite = mbits < 0x7C00u;
+        const float mx = finite ? half_bits_to_float(mbits) : absmax_with_nonfinite(src, lane);
+        scale = (mx > 0.0f) ? (finite ? div127_of_f16_value(mx) : mx / 127.0f) : 1.0f;     // cache_engine.cpp:172-183 (finite: an fp16 value
+        const float rcp = finite ? rcp_of_scale(scale) : 1.0f / scale;                      //  over 127 without the IEEE divide, same bits)
+
+        if (SCHEME == kInt8) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t q[8];
+                if (finite) {
+                    quantize8<MODE>(raw[j], scale, rcp, q);
+                } else {
+                    const uint32_t words[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        q[k] = quantize<MODE>(half_bits_to_float((words[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu), scale);
+                }
+                uint2 o;
+                o.x = (q[0] & 0xFFu) | ((q[1] & 0xFFu) << 8) | ((q[2] & 0xFFu) << 16) | (q[3] << 24);
+                o.y = (q[4] & 0xFFu) | ((q[5] & 0xFFu) << 8) | ((q[6] & 0xFFu) << 16) | (q[7] << 24);
+                enc_st8(rec + 512u * j + 8u * lane, o);
+            }
+            out_len = kBlockElems;
+        } else if (mx == 0.0f) {
+            // every element is +-0 (or a NaN, which quantises to 0 as well): all deltas are 0, so the record is
+            // eight runs of 255 zeros and one of 8 (cache_engine.cpp:208-239) -- no need to encode anything
+            if (lane < 16u)
+                reinterpret_cast<uint16_t*>(rec)[lane] = lane < 8u ? 0xFF00u : (lane == 8u ? 0x0800u : 0u);
+            out_len = 18u;
+        } else {
+            uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kEncWaveBytes;
+            uint32_t nruns = finite ? encode_rle_fast<MODE>(raw, scale, rcp, wl, lane) : kEncFail;
+            wave_lds_fence();
+            if (nruns == kEncFail) {
+                if (finite) {                                        // long stretches: the fast path's SPLIT form, from the source again
+                    uint4 again[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) again[j] = enc_ld16(src.chunk(j, lane));
+                    nruns = encode_rle_fast<MODE, true>(again, scale, rcp, wl, lane);
+                } else {
+                    nruns = encode_rle_general<MODE>(src, scale, wl, lane);
+                }
+                wave_lds_fence();
+            }
+            uint8_t* pairbuf = wl + kEncPairOff;
+            // zero the tail of the last 16-byte chunk so the stored slot is deterministic
+            {
+                const uint32_t idx = nruns + lane;
+                if (lane < 8u && idx < ((nruns + 7u) & ~7u)) reinterpret_cast<uint16_t*>(pairbuf)[idx] = 0;
+            }
+            wave_lds_fence();
+            out_len = 2u * nruns;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t b = 1024u * j + 16u * lane;
+                if (b < out_len)
+                    enc_st16(rec + b, *reinterpret_cast<const uint4*>(pairbuf + b));
+            }
+            wave_lds_fence();
+        }
+    }
+    if (lane == 0u) {
+        if (entries) {
+            gstore<uint32_t>(&entries[page].rec_bytes, out_len);
+            if (SCHEME != kMxFp4) gstore<float>(&entries[page].scale, scale);       // (MXFP4: the word holds the code delta)
+            if (SCHEME == kInt8DeltaRle && t.len_samples && (page & 1023u) == 0u) gstore<uint32_t>(&t.len_samples[(page >> 10) & 15u], out_len);
+            if (scale_tab) {
+                const uint32_t j = static_cast<uint32_t>(page % region_pages) & 15u;
+                gstore<float>(&scale_tab[page - j + attend_tile_slot(j)], scale);
+                if (scale_run) gstore<float>(scale_tab + scale_run_index(page, scale_run), scale);
+            }
+        } else {
+            t.rec_bytes[page] = out_len;
+            if (t.scales) t.scales[page] = scale;
+        }
+    }
+}
+
+#define SPECKV_ENC_LDS(SCHEME) \
+    __shared__ __attribute__((aligned(16))) uint16_t lds[SCHEME == kInt8DeltaRle ? kWaves * kEncLdsHalves : SCHEME == kInt4G32 ? kWaves * (kInt4RecBytes / 2) \
+                                                         : SCHEME == kMxFp4 ? kWaves * (kMx4RecBytes / 2) : 8]
+
 template <int SCHEME, int MODE>
 __global__ __launch_bounds__(kThreads) void k_compress(CodecArgs a)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[SCHEME == kInt8DeltaRle ? kWaves * kEncLdsHalves : SCHEME == kInt4G32 ? kWaves * (kInt4RecBytes / 2)
-                                                         : SCHEME == kMxFp4 ? kWaves * (kMx4RecBytes / 2) : 8];
+    SPECKV_ENC_LDS(SCHEME);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     const uint64_t n = a.n;
@@ -1001,328 +1368,40 @@ __global__ __launch_bounds__(kThreads) void k_compress(CodecArgs a)
         uint64_t page = a.page_list ? a.page_list[i] : a.first + i * (a.page_step ? a.page_step : 1);
         const uint8_t* src = a.data_list ? reinterpret_cast<const uint8_t*>(a.data_list[i])
                                          : a.data + i * a.data_stride;
-        PageEntry* entries = a.entries;
-        float* scale_tab = a.scale_tab;
-        uint32_t region_pages = a.region_pages, scale_run = a.scale_run;
+        EncTarget t{a.entries, a.scale_tab, a.region_pages, a.scale_run, a.len_samples, a.recs, a.rec_stride, a.rec_bytes, a.scales};
         if (a.groups) {                                              // wave-uniform: this block's allocation
             const uint64_t gi = i / a.group_n, j = i - gi * a.group_n;
             const CompressGroup g = a.groups[gi];
-            entries = g.entries; scale_tab = g.scale_tab; region_pages = g.region_pages; scale_run = g.scale_run;
+            t.entries = g.entries; t.scale_tab = g.scale_tab; t.region_pages = g.region_pages; t.scale_run = g.scale_run;
             page = g.first + j * (a.page_step ? a.page_step : 1);
             src = g.data + j * a.data_stride;
         }
-        uint8_t* rec = entries ? reinterpret_cast<uint8_t*>(gload<uint64_t>(&entries[page].pool_addr))
-                               : a.recs + page * a.rec_stride;
-        // MXFP4 in the pool is tile-planar (kernels.hpp): the codes go mx4_code_delta behind the nibbles -- the entry's scale word
-        uint8_t* rec_codes = rec + 1024u;
-        if (SCHEME == kMxFp4 && entries) rec_codes = rec + gload<uint32_t>(reinterpret_cast<const uint32_t*>(&entries[page].scale));
-        uint32_t out_len;
-        float scale = 1.0f;
-
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            raw[j] = enc_ld16(src + 2ull * (512u * j + 8u * lane));
-
-        if (SCHEME == kFp16) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                enc_st16(rec + 2ull * (512u * j + 8u * lane), raw[j]);
-            out_len = 2u * kBlockElems;
-        } else if (SCHEME == kInt4G32) {
-            // per group of 32 elements (4 lanes x 8): s = fp16(max|x|/7), q = clamp(round(x/s), -7, 7).  The group's max|x| and
-            // its "all finite" test come from the fp16 bit patterns (v_pk_max_u16, two elements per instruction), the
-            // quantisation runs in packed fp32 (the same multiply / fma / fma / add / truncate per element as the scalar form,
-            // so the same bits).  Round 4, instruction count (the kernel ran 18 % over what the chip moves at its read : write
-            // mix, profiles/r04_store_shape.txt): max|x| / 7 and 1 / s without the IEEE divide (codec_device.hpp: two and three
-            // operations, bit-identical for fp16-valued operands); no clamp when every scale of the chunk is a normal fp16
-            // (then no quotient reaches 7.5); the nibbles summed as signed i << 4k and un-biased once per dword.
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t words[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};
-                u16x2 m2 = {0, 0};
-#pragma unroll
-                for (int t = 0; t < 4; ++t) m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, words[t] & 0x7FFF7FFFu));
-                uint32_t mbits = m2.x > m2.y ? m2.x : m2.y;                 // largest |bits| of the lane's 8 elements
-                mbits = umax(mbits, dpp<0xB1>(0u, mbits));                  // quad_perm [1,0,3,2]: lane ^ 1
-                mbits = umax(mbits, dpp<0x4E>(0u, mbits));                  // quad_perm [2,3,0,1]: lane ^ 2 -> the group of 32
-                const bool finite = __ballot(mbits >= 0x7C00u) == 0ull;     // wave-uniform: no inf / NaN in any group of this chunk
-                uint32_t nib = 0;
-                _Float16 s16;
-                if (finite) {
-                    float sdiv = div7_of_f16_value(half_bits_to_float(mbits));
-                    asm volatile("" : "+v"(sdiv));                      // keep the fp32 rounding of the divide
-                    s16 = static_cast<_Float16>(sdiv);
-                    const float sc = static_cast<float>(s16);
-                    // |x| <= 7.5*sc in a finite group: the reciprocal divide is exact (test_fast_division_is_exact); a scale that
-                    // rounds to zero (subnormal groups) gives rcp = 0 and every quotient 0, as the definition says
-                    const float rcp = sc != 0.0f ? rcp_of_f16_value(sc) : 0.0f;
-                    const f32x2 ss = {sc, sc}, rr = {rcp, rcp};
-                    // a subnormal scale may be off by more than half a step: only then can a quotient leave [-7.5, 7.5]
-                    const uint32_t sbits = __builtin_bit_cast(uint16_t, s16);
-                    const bool clamp = __ballot(sbits - 1u < 0x3FFu) != 0ull;                   // (wave-uniform)
-                    int iq[8];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        f32x2 x;
-                        x.x = half_bits_to_float(words[t] & 0xFFFFu);
-                        x.y = half_bits_to_float(words[t] >> 16);
-                        const f32x2 q0 = x * rr;
-                        const f32x2 e = __builtin_elementwise_fma(-q0, ss, x);
-                        const f32x2 y = __builtin_elementwise_fma(e, rr, q0);
-                        f32x2 h;
-                        h.x = __builtin_copysignf(0.5f, y.x);
-                        h.y = __builtin_copysignf(0.5f, y.y);
-                        const f32x2 r = y + h;                          // round half away from zero = truncate(y + copysign(0.5, y))
-                        iq[2 * t] = static_cast<int>(r.x);
-                        iq[2 * t + 1] = static_cast<int>(r.y);
-                    }
-                    if (clamp) {
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) iq[k] = min(max(iq[k], -7), 7);
-                    }
-                    // nibble k = iq[k] & 0xF:  sum of iq[k] << 4k  =  sum of (iq[k] + 8) << 4k  -  0x88888888, and (i + 8) ^ 8 = i & 0xF
-                    uint32_t acc = 0x88888888u;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) acc += static_cast<uint32_t>(iq[k]) << (4 * k);
-                    nib = acc ^ 0x88888888u;
-                } else {
-                    float xv[8];
-                    float mx = 0.0f, nanacc = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        xv[k] = half_bits_to_float((words[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu);
-                        absmax_finite(xv[k], mx, nanacc);
-                    }
-                    float o = __shfl_xor(mx, 1); mx = (o > mx) ? o : mx;
-                    o = __shfl_xor(mx, 2);       mx = (o > mx) ? o : mx;
-                    float sdiv = mx / 7.0f;
-                    asm volatile("" : "+v"(sdiv));
-                    s16 = static_cast<_Float16>(sdiv);
-                    const float sc = static_cast<float>(s16);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        float r = 0.0f;
-                        if (sc != 0.0f && sc == sc) {
-                            r = roundf(xv[k] / sc);
-                            if (!(r == r)) r = 0.0f;
-                            r = fminf(fmaxf(r, -7.0f), 7.0f);
-                        }
-                        nib |= (static_cast<uint32_t>(static_cast<int>(r)) & 0xFu) << (4 * k);
-                    }
-                }
-                // The record is assembled in LDS and leaves as whole 16-byte pieces per lane: written straight from the
-                // registers it took eight store instructions of 4 / 2 bytes per lane (0.63-0.65 of HBM peak).
-                const uint32_t p0 = 512u * j + 8u * lane;
-                uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kInt4RecBytes;
-                *reinterpret_cast<uint32_t*>(wl + 128u + (p0 >> 1)) = nib;
-                if ((lane & 3u) == 0u)
-                    *reinterpret_cast<uint16_t*>(wl + 2u * (p0 >> 5)) = __builtin_bit_cast(uint16_t, s16);
-            }
-            {
-                uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kInt4RecBytes;
-                wave_lds_fence();
-                enc_st16(rec + 128u + 16u * lane, *reinterpret_cast<const uint4*>(wl + 128u + 16u * lane));
-                if (lane < 8u) enc_st16(rec + 16u * lane, *reinterpret_cast<const uint4*>(wl + 16u * lane));
-                wave_lds_fence();
-            }
-            out_len = kInt4RecBytes;
-        } else if (SCHEME == kMxFp4) {
-            // OCP MX v1.0 conversion (oracle: compress_mxfp4) over the block's two halves interleaved element by element: byte i of the
-            // record = element i (low nibble) and element 1024 + i (high), one E8M0 code per 16 bytes.  This lane's raw[j] and
-            // raw[j + 2] (j = 0, 1) are exactly such partners -- elements [512 j + 8 l, + 8) and the same 1024 further on -- so the
-            // interleave never leaves the lane; a block of 32 = this lane's and lane ^ 1's 8 + 8 elements of both halves.
-            //   code = floor(log2 max|x|) - 2 + 127 = the exponent field of max|x| as a float, minus 2
-            //   q    = E2M1 of x / 2^(code-127), nearest even, saturating: one v_cvt_scalef32_pk_fp4_f16 per element pair (it divides
-            //          by the power of two its scale operand's exponent names: profiles/probes/mxprobe.hip)
-            typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const uint32_t w0[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};                    // first half: elements 2t, 2t+1 per word
-                const uint32_t w1[4] = {raw[j + 2].x, raw[j + 2].y, raw[j + 2].z, raw[j + 2].w};    // their partners in the second half
-                u16x2 m2 = {0, 0};
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, w0[t] & 0x7FFF7FFFu));
-                    m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, w1[t] & 0x7FFF7FFFu));
-                }
-                uint32_t mbits = m2.x > m2.y ? m2.x : m2.y;                 // largest |bits| of the lane's 16 elements
-                mbits = umax(mbits, dpp<0xB1>(0u, mbits));                  // lane ^ 1 -> the block of 32
-                const bool finite = __ballot(mbits >= 0x7C00u) == 0ull;     // wave-uniform: no inf / NaN in any block of this chunk
-                uint32_t nib[2] = {0u, 0u}, code = 0;
-                if (finite) {
-                    code = mbits ? (__float_as_uint(half_bits_to_float(mbits)) >> 23) - 2u : 0u;
-                    const float sc = mbits ? __uint_as_float(code << 23) : 1.0f;      // (code >= 101 for any non-zero fp16: a normal float)
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        // (element 2t of both halves), (element 2t+1 of both halves) -> bytes 2t, 2t+1
-                        const f16x2v ea = __builtin_bit_cast(f16x2v, __builtin_amdgcn_perm(w1[t], w0[t], 0x05040100u));
-                        const f16x2v eb = __builtin_bit_cast(f16x2v, __builtin_amdgcn_perm(w1[t], w0[t], 0x07060302u));
-                        uint32_t& o = nib[t >> 1];
-                        if (t & 1) { o = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(o, ea, sc, 2); o = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(o, eb, sc, 3); }
-                        else       { o = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(o, ea, sc, 0); o = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(o, eb, sc, 1); }
-                    }
-                } else {
-                    // a chunk with inf / NaN somewhere: NaN elements are skipped in the maximum and store +0, inf counts as 65504
-                    float x0[8], x1[8];
-                    float mx = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        float a0 = half_bits_to_float((w0[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu), a1 = half_bits_to_float((w1[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu);
-                        a0 = (a0 == a0) ? fminf(fmaxf(a0, -65504.0f), 65504.0f) : 0.0f;
-                        a1 = (a1 == a1) ? fminf(fmaxf(a1, -65504.0f), 65504.0f) : 0.0f;
-                        x0[k] = a0; x1[k] = a1;
-                        mx = fmaxf(mx, fmaxf(fabsf(a0), fabsf(a1)));
-                    }
-                    const float o = __shfl_xor(mx, 1);
-                    mx = (o > mx) ? o : mx;
-                    code = mx > 0.0f ? (__float_as_uint(mx) >> 23) - 2u : 0u;
-                    const float sc = mx > 0.0f ? __uint_as_float(code << 23) : 1.0f;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        uint32_t& ob = nib[k >> 2];
-                        switch (k & 3) {
-                        case 0: ob = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(ob, x0[k], x1[k], sc, 0); break;
-                        case 1: ob = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(ob, x0[k], x1[k], sc, 1); break;
-                        case 2: ob = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(ob, x0[k], x1[k], sc, 2); break;
-                        default: ob = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(ob, x0[k], x1[k], sc, 3); break;
-                        }
-                        // a NaN element keeps no sign: +0
-                        if (((w0[k >> 1] >> ((k & 1) * 16)) & 0x7FFFu) > 0x7C00u) ob &= ~(0x0Fu << (8 * (k & 3)));
-                        if (((w1[k >> 1] >> ((k & 1) * 16)) & 0x7FFFu) > 0x7C00u) ob &= ~(0xF0u << (8 * (k & 3)));
-                    }
-                }
-                // the record is assembled in LDS and leaves as whole 16-byte pieces per lane (as the INT4 record does)
-                const uint32_t p0 = 512u * j + 8u * lane;
-                uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kMx4RecBytes;
-                *reinterpret_cast<uint2*>(wl + p0) = make_uint2(nib[0], nib[1]);
-                if ((lane & 1u) == 0u) wl[1024u + (p0 >> 4)] = static_cast<uint8_t>(code);
-            }
-            {
-                uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kMx4RecBytes;
-                wave_lds_fence();
-                enc_st16(rec + 16u * lane, *reinterpret_cast<const uint4*>(wl + 16u * lane));
-                if (lane < 4u) enc_st16(rec_codes + 16u * lane, *reinterpret_cast<const uint4*>(wl + 1024u + 16u * lane));
-                wave_lds_fence();
-            }
-            out_len = kMx4RecBytes;
-        } else if (SCHEME == kFp8E4m3) {
-            float x[4][8];
-            float mx = 0.0f, nanacc = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t words[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    x[j][k] = half_bits_to_float((words[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu);
-                    absmax_finite(x[j][k], mx, nanacc);
-                }
-            }
-            // (mx is never a NaN and never negative: its bit pattern orders like its value -- the DPP max scan of the encoders
-            // instead of six trips through the LDS crossbar)
-            mx = __uint_as_float(lane63(wave_incl_max(__float_as_uint(mx))));
-            const bool finite = __ballot(!(nanacc == 0.0f)) == 0ull;       // wave-uniform
-            // a finite block's max|x| is an fp16 value: its scale and the reciprocal without the IEEE divide, bit-identical
-            // (codec_device.hpp; exhaustive: test_fast_division_is_exact)
-            scale = (mx > 0.0f) ? (finite ? div448_of_f16_value(mx) : mx / 448.0f) : 1.0f;
-            const float rcp = finite ? rcp_of_scale(scale) : 1.0f / scale;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float v[8];
-                if (finite) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k)
-                        v[k] = fminf(fmaxf(__builtin_copysignf(div_by_scale(x[j][k], scale, rcp), x[j][k]), -448.0f), 448.0f);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = fminf(fmaxf(x[j][k] / scale, -448.0f), 448.0f);
-                }
-                int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-                lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
-                int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], 0, false);
-                hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
-                enc_st8(rec + 512u * j + 8u * lane, make_uint2(static_cast<uint32_t>(lo), static_cast<uint32_t>(hi)));
-            }
-            out_len = kBlockElems;
-        } else {
-            const uint32_t mbits = absmax_bits(raw);                       // wave-uniform
-            const bool finite = mbits < 0x7C00u;
-            const float mx = finite ? half_bits_to_float(mbits) : absmax_with_nonfinite(src, lane);
-            scale = (mx > 0.0f) ? (finite ? div127_of_f16_value(mx) : mx / 127.0f) : 1.0f;     // cache_engine.cpp:172-183 (finite: an fp16 value
-            const float rcp = finite ? rcp_of_scale(scale) : 1.0f / scale;                      //  over 127 without the IEEE divide, same bits)
-
-            if (SCHEME == kInt8) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    uint32_t q[8];
-                    if (finite) {
-                        quantize8<MODE>(raw[j], scale, rcp, q);
-                    } else {
-                        const uint32_t words[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};
-#pragma unroll
-                        for (int k = 0; k < 8; ++k)
-                            q[k] = quantize<MODE>(half_bits_to_float((words[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu), scale);
-                    }
-                    uint2 o;
-                    o.x = (q[0] & 0xFFu) | ((q[1] & 0xFFu) << 8) | ((q[2] & 0xFFu) << 16) | (q[3] << 24);
-                    o.y = (q[4] & 0xFFu) | ((q[5] & 0xFFu) << 8) | ((q[6] & 0xFFu) << 16) | (q[7] << 24);
-                    enc_st8(rec + 512u * j + 8u * lane, o);
-                }
-                out_len = kBlockElems;
-            } else if (mx == 0.0f) {
-                // every element is +-0 (or a NaN, which quantises to 0 as well): all deltas are 0, so the record is
-                // eight runs of 255 zeros and one of 8 (cache_engine.cpp:208-239) -- no need to encode anything
-                if (lane < 16u)
-                    reinterpret_cast<uint16_t*>(rec)[lane] = lane < 8u ? 0xFF00u : (lane == 8u ? 0x0800u : 0u);
-                out_len = 18u;
-            } else {
-                uint8_t* wl = reinterpret_cast<uint8_t*>(lds) + wave * kEncWaveBytes;
-                uint32_t nruns = finite ? encode_rle_fast<MODE>(raw, scale, rcp, wl, lane) : kEncFail;
-                wave_lds_fence();
-                if (nruns == kEncFail) {
-                    if (finite) {                                        // long stretches: the fast path's SPLIT form, from the source again
-                        uint4 again[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) again[j] = enc_ld16(src + 2ull * (512u * j + 8u * lane));
-                        nruns = encode_rle_fast<MODE, true>(again, scale, rcp, wl, lane);
-                    } else {
-                        nruns = encode_rle_general<MODE>(src, scale, wl, lane);
-                    }
-                    wave_lds_fence();
-                }
-                uint8_t* pairbuf = wl + kEncPairOff;
-                // zero the tail of the last 16-byte chunk so the stored slot is deterministic
-                {
-                    const uint32_t idx = nruns + lane;
-                    if (lane < 8u && idx < ((nruns + 7u) & ~7u)) reinterpret_cast<uint16_t*>(pairbuf)[idx] = 0;
-                }
-                wave_lds_fence();
-                out_len = 2u * nruns;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t b = 1024u * j + 16u * lane;
-                    if (b < out_len)
-                        enc_st16(rec + b, *reinterpret_cast<const uint4*>(pairbuf + b));
-                }
-                wave_lds_fence();
-            }
-        }
-        if (lane == 0u) {
-            if (entries) {
-                gstore<uint32_t>(&entries[page].rec_bytes, out_len);
-                if (SCHEME != kMxFp4) gstore<float>(&entries[page].scale, scale);       // (MXFP4: the word holds the code delta)
-                if (SCHEME == kInt8DeltaRle && a.len_samples && (page & 1023u) == 0u) gstore<uint32_t>(&a.len_samples[(page >> 10) & 15u], out_len);
-                if (scale_tab) {
-                    const uint32_t j = static_cast<uint32_t>(page % region_pages) & 15u;
-                    gstore<float>(&scale_tab[page - j + attend_tile_slot(j)], scale);
-                    if (scale_run) gstore<float>(scale_tab + scale_run_index(page, scale_run), scale);
-                }
-            } else {
-                a.rec_bytes[page] = out_len;
-                if (a.scales) a.scales[page] = scale;
-            }
-        }
+        compress_block<SCHEME, MODE>(t, page, SrcRun{src}, lds, lane, wave);
     }
+}
+
+// The commit of a multi-position step (Engine::write_pairs): wave i encodes block j = i % (2 * n_layers) of position pair
+// i / (2 * n_layers) -- layer j >> 1, kind j & 1 (K, V), page first + j * page_step -- from the pair's two rows of that kind,
+// layer_stride bytes further on per layer.  No page image is ever assembled.  One block per wave; the records are those
+// k_compress stores for the same 4096 bytes.
+template <int SCHEME, int MODE>
+__global__ __launch_bounds__(kThreads) void k_compress_pairs(PairArgs a)
+{
+    SPECKV_ENC_LDS(SCHEME);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
+    const uint32_t per = 2u * a.n_layers;
+    if (i >= static_cast<uint64_t>(a.n_pairs) * per) return;        // (whole waves leave: the body has no workgroup barrier)
+    const uint32_t pi = static_cast<uint32_t>(i / per), j = static_cast<uint32_t>(i - static_cast<uint64_t>(pi) * per);
+    const CommitPair* g = a.pairs + pi;
+    const uint32_t kind = j & 1u;
+    const uint64_t off = static_cast<uint64_t>(j >> 1) * a.layer_stride;
+    const SrcPair src{g->row[2u * kind] + off, g->row[2u * kind + 1u] + off};     // (read by address: no register copy of row[])
+    PageEntry* entries = g->entries;
+    __builtin_assume(entries != nullptr);
+    const EncTarget t{entries, g->scale_tab, g->region_pages, g->scale_run, nullptr, nullptr, 0, nullptr, nullptr};
+    compress_block<SCHEME, MODE>(t, g->first + static_cast<uint64_t>(j) * a.page_step, src, lds, lane, wave);
 }
 
 } // namespace
@@ -1575,6 +1654,39 @@ hipError_t launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t s
     if (n16 == 0) return hipSuccess;
     hipLaunchKernelGGL(k_copy16, dim3((n16 + 255u) / 256u), dim3(256), 0, s, static_cast<const uint4*>(src), static_cast<uint4*>(dst), n16);
     return hipGetLastError();
+}
+
+// The pair-gather encoder.  Its launcher is the last of the translation unit: it is the first to name the k_compress_pairs<>
+// instances, which are therefore emitted behind everything else (see the note on emission order above).
+namespace {
+template <int SCHEME, int MODE>
+hipError_t launch_enc_pairs(const PairArgs& a, uint32_t grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_compress_pairs<SCHEME, MODE>), dim3(grid), dim3(kThreads), 0, s, a);
+    return hipGetLastError();
+}
+template <int SCHEME>
+hipError_t launch_enc_pairs_mode(const PairArgs& a, uint32_t grid, hipStream_t s)
+{
+    return a.quant_mode == kIntent ? launch_enc_pairs<SCHEME, kIntent>(a, grid, s) : launch_enc_pairs<SCHEME, kRefExact>(a, grid, s);
+}
+} // namespace
+
+hipError_t launch_compress_pairs(const PairArgs& a, hipStream_t s)
+{
+    const uint64_t waves = static_cast<uint64_t>(a.n_pairs) * 2u * a.n_layers;       // one block per wave
+    if (waves == 0) return hipSuccess;
+    if (!a.pairs || a.page_step == 0 || a.layer_stride % 16u || waves > (1ull << 31)) return hipErrorInvalidValue;
+    const uint32_t grid = static_cast<uint32_t>((waves + kWaves - 1) / kWaves);
+    switch (a.scheme) {
+    case kFp16: return launch_enc_pairs_mode<kFp16>(a, grid, s);
+    case kInt8: return launch_enc_pairs_mode<kInt8>(a, grid, s);
+    case kInt8DeltaRle: return launch_enc_pairs_mode<kInt8DeltaRle>(a, grid, s);
+    case kInt4G32: return launch_enc_pairs<kInt4G32, kRefExact>(a, grid, s);         // the quantiser mode does not apply
+    case kFp8E4m3: return launch_enc_pairs<kFp8E4m3, kRefExact>(a, grid, s);
+    case kMxFp4: return launch_enc_pairs<kMxFp4, kRefExact>(a, grid, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace speckv

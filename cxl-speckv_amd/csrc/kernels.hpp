@@ -74,6 +74,27 @@ struct CompressGroup {
     const uint8_t* data;
 };
 
+// One position pair of one request in a pair-gather compress launch (PairArgs::pairs): block j < 2 * n_layers is page
+// first + j * page_step (layer j >> 1, kind j & 1); its first 2048 bytes are row[2 * kind] + layer * layer_stride, its second
+// 2048 bytes row[2 * kind + 1] + layer * layer_stride.  Rows are 16-byte aligned.
+struct CommitPair {
+    PageEntry*     entries;
+    float*         scale_tab;
+    uint32_t       region_pages;
+    uint32_t       scale_run;
+    uint64_t       first;
+    const uint8_t* row[4];            // K even, K odd, V even, V odd
+};
+struct PairArgs {
+    const CommitPair* pairs;          // device array
+    uint32_t          n_pairs;
+    uint32_t          n_layers;
+    uint64_t          page_step;
+    uint64_t          layer_stride;   // bytes, a multiple of 16
+    int               scheme;
+    int               quant_mode;
+};
+
 // Source / destination description of one codec launch.  Exactly one of
 // {entries, recs, tab+alloc_list} is used as the record source.
 struct CodecArgs {
@@ -162,6 +183,8 @@ struct CodecArgs {
 
 hipError_t launch_compress(const CodecArgs& a, hipStream_t s);
 hipError_t launch_decompress(const CodecArgs& a, hipStream_t s);
+// the pair-gather form of the encoder: n_pairs * 2 * n_layers blocks in one launch, rows read where they lie (k_compress_pairs)
+hipError_t launch_compress_pairs(const PairArgs& a, hipStream_t s);
 
 // FPGACacheEngine::compress / ::decompress over a tensor of any length (tensor_codec.hip): one scale, one delta chain and
 // one run-length stream across the whole tensor.  d_rle: 16-byte aligned, room for 2n bytes rounded up to 16; d_ws:

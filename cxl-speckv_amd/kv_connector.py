@@ -664,8 +664,24 @@ class SpeckvKVConnector:
         path[i - 1]; without, the nodes must be in range and ascending.  A path that fails raises ValueError before any state changes.
         The path's rows are gathered to the front of a [batch][longest path] tensor on the stream of the writes and go through
         append_tokens with n_accept = len(path): the state that many single append() calls would leave.  Returns what append_tokens
-        returns."""
+        returns.  commit() leaves the same state with one launch and no gather."""
         import torch
+        B, S = k_new.shape[0], k_new.shape[1]
+        paths = self._checked_paths(req_ids, k_new, v_new, paths, parents)
+        n_accept = [len(path) for path in paths]
+        longest = max(n_accept, default=0)
+        if longest == 0:
+            return []
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):
+                idx = _device_index([b * S + (path[t] if t < len(path) else 0) for b, path in enumerate(paths) for t in range(longest)])
+                shape = (B, longest, self.L, self.H, self.D)
+                k_path = k_new.reshape(B * S, self.L, self.H, self.D).index_select(0, idx).view(shape)
+                v_path = v_new.reshape(B * S, self.L, self.H, self.D).index_select(0, idx).view(shape)
+        return self.append_tokens(req_ids, k_path, v_path, n_accept, stream)
+
+    def _checked_paths(self, req_ids, k_new, v_new, paths, parents):
+        """paths as lists of ints, judged as append_path's docstring says; raises ValueError, changes nothing."""
         B, S = k_new.shape[0], k_new.shape[1]
         paths = [[int(j) for j in path] for path in paths]
         if len(paths) != B or len(req_ids) != B or tuple(v_new.shape) != tuple(k_new.shape) or tuple(k_new.shape[2:]) != (self.L, self.H, self.D):
@@ -685,24 +701,75 @@ class SpeckvKVConnector:
                 raise ValueError(f"request {rid}: path {path} does not ascend")
             if self.requests[rid].length + len(path) > self.T:
                 raise ValueError(f"request {rid} is full")
-        n_accept = [len(path) for path in paths]
-        longest = max(n_accept, default=0)
-        if longest == 0:
+        return paths
+
+    def commit(self, req_ids: Sequence[int], k_new, v_new, nodes, parents=None, stream=None):
+        """Commit, per request, the step positions nodes[b] (in order) of the S new positions k_new[b], v_new[b] ([batch][S][layers]
+        [heads][dim] fp16) with ONE speckv_ext_write_pairs call for the whole batch: nodes[b] = range(n) is append_tokens(n_accept = n),
+        an accepted tree path is append_path -- the same pool records, lengths, tails and early plan, judged as append_path judges
+        (ValueError before any state changes).  No page image is built: the encoder reads every pair's two rows where they lie, in
+        k_new / v_new and in the tail tensors a pair consumes; the host computes their addresses.  What torch still does: the K
+        pre-scale, a contiguous copy of k_new / v_new that are not, and one index_select per kind for the new tails (copies: the
+        caller may reuse k_new).  Returns everything the asynchronous launch reads -- the (scaled) k_new, v_new and the consumed tail
+        tensors -- for the caller to hold until the stream has passed the writes, as append() returns its sources."""
+        import numpy as np
+        import torch
+        B, S = k_new.shape[0], k_new.shape[1]
+        nodes = self._checked_paths(req_ids, k_new, v_new, nodes, parents)
+        reqs = [self.requests[rid] for rid in req_ids]
+        n_accept = [len(path) for path in nodes]
+        pairs, tails = self.commit_plan([r.length for r in reqs], n_accept)
+        if not pairs and not tails:
             return []
+        used = [b for b, (r, n) in enumerate(zip(reqs, n_accept)) if n and r.length & 1]        # requests whose odd position finds its partner
+        row_bytes = self.L * self.H * self.D * 2
+        keep, tk, tv = [], None, None
         with self._On(self, stream) as st:
             with torch.cuda.stream(st):
-                idx = _device_index([b * S + (path[t] if t < len(path) else 0) for b, path in enumerate(paths) for t in range(longest)])
-                shape = (B, longest, self.L, self.H, self.D)
-                k_path = k_new.reshape(B * S, self.L, self.H, self.D).index_select(0, idx).view(shape)
-                v_path = v_new.reshape(B * S, self.L, self.H, self.D).index_select(0, idx).view(shape)
-        return self.append_tokens(req_ids, k_path, v_path, n_accept, stream)
+                if self._kscale_inv is not None:
+                    k_new = k_new * self._kscale_inv[None, None]
+                k_new, v_new = k_new.contiguous(), v_new.contiguous()
+                keep += [k_new, v_new]
+                if tails:
+                    it = _device_index([b * S + nodes[b][t] for b, t in tails])
+                    tk = k_new.view(B * S, self.L, self.H, self.D).index_select(0, it)
+                    tv = v_new.view(B * S, self.L, self.H, self.D).index_select(0, it)
+                # addresses of the odd positions that pairs consume: rows of the last append's tail tensors, or per request
+                tail_at = np.zeros((B, 2), dtype=np.uint64)
+                if used and tuple(req_ids[b] for b in used) == self._tail_ids:
+                    keep += [self._tail_k, self._tail_v]
+                    at = np.arange(len(used), dtype=np.uint64) * np.uint64(row_bytes)
+                    tail_at[used, 0], tail_at[used, 1] = at + np.uint64(self._tail_k.data_ptr()), at + np.uint64(self._tail_v.data_ptr())
+                else:
+                    for b in used:
+                        k, v, row = reqs[b]._tail
+                        if not (k.is_contiguous() and v.is_contiguous()):
+                            k, v, row = reqs[b].tail_k.contiguous(), reqs[b].tail_v.contiguous(), None
+                        keep += [k, v]
+                        tail_at[b] = k.data_ptr() + (row or 0) * row_bytes, v.data_ptr() + (row or 0) * row_bytes
+            if pairs:
+                plan = np.asarray([x for group in pairs for x in group], dtype=np.int64)       # (b, page, source, source) per pair
+                b_of, rows = plan[:, 0], np.empty((len(plan), 4), dtype=np.uint64)
+                node_of = np.zeros((B, S + 1), dtype=np.int64)                                  # [b][source]; source -1 is the last column, unused
+                for b, path in enumerate(nodes):
+                    node_of[b, :len(path)] = path
+                for half in (0, 1):
+                    t = plan[:, 2 + half]
+                    new_row = ((b_of * S + node_of[b_of, t]) * row_bytes).astype(np.uint64)
+                    rows[:, half] = np.where(t < 0, tail_at[b_of, 0], new_row + np.uint64(k_new.data_ptr()))
+                    rows[:, 2 + half] = np.where(t < 0, tail_at[b_of, 1], new_row + np.uint64(v_new.data_ptr()))
+                handles = np.asarray([reqs[b].handle for b in b_of], dtype=np.uint64)
+                self.lib.write_pairs(handles, plan[:, 1].astype(np.uint64), rows, self.region_pages, self.L, self.H * self.D * 2, st.cuda_stream)
+        self._committed(req_ids, reqs, used, tails, tk, tv, n_accept)
+        return keep
 
     def append_tokens(self, req_ids: Sequence[int], k_new, v_new, n_accept: Sequence[int], stream=None):
         """Commit the first n_accept[b] (0..S) of the S new positions k_new[b], v_new[b] ([batch][S][layers][heads][dim] fp16) of every
         request -- the accepted prefix of a speculative step, or a chunk of a prompt onto a request that has positions already.
         Whole position pairs go to the pool, an odd remainder becomes the tail: the state a run of single append() calls would leave.
         One speckv_ext_write_strided_batch call per pair index over the requests that have that pair (at most S / 2 + 1 launches).
-        n_accept[b] = 0 leaves the request untouched.  Returns the sources of the asynchronous writes, as append()."""
+        n_accept[b] = 0 leaves the request untouched.  Returns the sources of the asynchronous writes, as append().
+        commit() leaves the same state with one launch and no page images."""
         import torch
         B, S = k_new.shape[0], k_new.shape[1]
         n_accept = [int(n) for n in n_accept]
@@ -754,6 +821,12 @@ class SpeckvKVConnector:
                         self.lib.write_strided_batch([reqs[b].handle for b, _, _, _ in group], np.asarray([pg for _, pg, _, _ in group], dtype=np.uint64),
                                                      srcs, self.region_pages, 2 * self.L, st.cuda_stream)
                     at += len(group) * step_bytes
+        self._committed(req_ids, reqs, used, tails, tk if tails else None, tv if tails else None, n_accept)
+        return keep
+
+    def _committed(self, req_ids, reqs, used, tails, tk, tv, n_accept):
+        """The writes of a commit are queued: consumed tails go, the new ones (rows of tk / tv) come, lengths grow, and the next
+        step's plan is made early.  Shared by append_tokens() and commit()."""
         for b in used:
             reqs[b].clear_tail()
         for i, (b, _) in enumerate(tails):
@@ -777,4 +850,3 @@ class SpeckvKVConnector:
                 self._arg_key = self._plan_stream = None
                 if e.status != -4:                             # SPECKV_ERR_INVAL: the stream cannot take the plan now; attend() plans again
                     raise
-        return keep

@@ -110,6 +110,22 @@ speckv_status_t speckv_ext_write_async(speckv_handle_t handle, uint64_t offset_b
 speckv_status_t speckv_ext_write_strided_batch(const speckv_handle_t* handles, const uint64_t* first_pages,
                                                const void* const* d_srcs, uint32_t n_allocations, uint64_t page_step,
                                                uint64_t n_pages_each, void* stream);
+/* The commit of a multi-position decode step in ONE launch, rows gathered by the encoder: pair i is a position pair of
+ * allocation handles[i] -- pages first_pages[i] + j * page_step, j < 2 * n_layers, page j being layer j / 2, kind j % 2 (K, V)
+ * as in the shim layout.  A page's first 2048 bytes are read from d_rows[4 * i + 2 * kind] + layer * layer_stride_bytes (the
+ * even position's row), its second 2048 bytes from d_rows[4 * i + 2 * kind + 1] + layer * layer_stride_bytes (the odd one's):
+ * no page image is assembled, the rows may lie in any device tensors (a step's k_new / v_new, a held tail row).  The records
+ * are those speckv_ext_write_strided_batch stores for the same bytes laid out contiguously.  An allocation may appear in
+ * several pairs as long as no two of them share a page.  Asynchronous on `stream`; the rows must stay alive and unchanged
+ * until the stream has passed the call.
+ *   SPECKV_ERR_INVAL    NULL stream or arrays, a NULL row or one not 16-byte aligned, layer_stride_bytes not a multiple of 16,
+ *                       page_step == 0, allocations of different schemes, two pairs of one allocation that share a page
+ *   SPECKV_ERR_GENERAL  an unknown handle, pages that leave the allocation
+ * n_pairs == 0 or n_layers == 0: SPECKV_OK, nothing is done.  Cached target pages are invalidated first, as above. */
+speckv_status_t speckv_ext_write_pairs(const speckv_handle_t* handles, const uint64_t* first_pages,
+                                       const void* const* d_rows /* [n_pairs][4]: K even, K odd, V even, V odd */,
+                                       uint32_t n_pairs, uint64_t page_step, uint32_t n_layers,
+                                       uint64_t layer_stride_bytes, void* stream);
 /* Several page runs of ONE allocation in one launch: run r = pages [first_pages[r], first_pages[r] + n_pages_each) from
  * d_srcs[r] (n_pages_each * 4096 contiguous bytes).  A prompt's K and V of every layer (2 * num_layers regions of the shim
  * layout) are stored with one call.  The runs must not overlap; the stream must not be NULL. */
