@@ -3,6 +3,7 @@
 // (batch_dispatch_order).  Engine::attend_batch, attend_batch_plan and attend_planned (engine_attend.cpp) decide with these and with nothing else,
 // so the three agree by construction; the CPU tests call the same functions (tests/csrc/host_rules_test.cpp) and replay a recorded table of
 // decisions through them (tests/golden/attend_geometry.json).  Plain C++17, no HIP: the tuning keys the rules read come in as values.
+// At the end: when several layers of ONE sequence take the stream form (int4_wg8_stream, mx4_stream; Engine::attend_int4 / attend_mx4).
 #pragma once
 #include "ring_rule.hpp"
 
@@ -232,6 +233,66 @@ template <class Seq> inline uint64_t assign_pieces(const BatchGeometry& g, uint3
         parts += static_cast<uint64_t>(heads) * es.n_splits;
     }
     return parts;
+}
+
+// ---- several layers of one sequence: the stream form --------------------------------------------------------------------------------
+// Engine::attend_int4 / attend_mx4 (k_attend_int4_wg8, k_attend_mx4): the launch's n_layers x n_tiles tiles, layer-major, in one contiguous
+// piece per workgroup (ring_rule.hpp: the partition) -- one pipeline fill per workgroup, no partial last round, few partials per layer.
+// Both decisions return the AttendArgs::stream fields, n_wgs == 0: the fixed grid.  They read two tuning keys as values: attend_splits > 0
+// (a forced split count) always takes the fixed grid; attend_stream = N > 0 cuts the call into exactly N pieces whatever its size (tests reach
+// the form, and every shape of its partition, with small calls), -1 never streams, 0 decides by size.  The placement (records in one run, or
+// INT4_G32 by residue classes) is the caller's condition.
+constexpr uint32_t kStreamMinTiles = 896;            // context (tiles of 32 positions) from which several layers of one sequence take the stream form
+
+// the cut of n_layers x n_tiles tiles into n_wgs pieces; none when a piece would be empty or its length not fit 32 bits
+inline AttendStream stream_cut(uint32_t n_layers, uint32_t n_tiles, uint64_t n_wgs)
+{
+    const uint64_t total = static_cast<uint64_t>(n_layers) * n_tiles;
+    if (n_wgs == 0u || n_wgs > 0xFFFFFFFFull || total < n_wgs || total / n_wgs > 0xFFFFFFFFull) return AttendStream{};
+    AttendStream s{static_cast<uint32_t>(total / n_wgs), static_cast<uint32_t>(total % n_wgs), static_cast<uint32_t>(n_wgs), 1u, 0u};
+    for (uint32_t l = 0; l < n_layers; ++l) s.max_slots = std::max(s.max_slots, attend_stream_count(l, n_tiles, s.len, s.rem));
+    return s;
+}
+
+// INT4_G32 on the whole-record kernel (512-thread workgroups, two resident per CU): as many pieces as workgroups are resident at once.
+// Worth it when a piece is long enough to amortise its fill (>= 16 tiles) and from 28k context only (round 6: below it the fixed grid of
+// ONE round -- layers x splits <= CUs, whole-layer rows final or merged -- is faster: 80 layers x 4k 0.515 (stream) against 0.567, 8k 0.60 /
+// 0.63, 16k 0.64 / 0.66, 24k 0.667 / 0.66, 32k 0.70 / 0.67, 64k 0.71 / 0.69; 70 layers x 4k 0.46 / 0.55; profiles/r06_layers_by_context.txt).
+// n_tiles: per layer, by residue class where cls (then also AttendStream::tiles: the merge counts a layer's partials from the same count).
+// A ragged last tile (n_pages % 16 != 0) streams like any other: the kernel masks it by its index in the layer, in every layer.
+// attend_stream = N > 0: N pieces, the size thresholds bypassed -- but the class form needs pieces of two tiles at least (a one-tile piece
+// requests its tile twice, and the second request of a piece that ends a layer is addressed in the regions of the layer behind it, which the
+// allocation may not have), and the merge takes 2048 partials a row at most: the fixed grid otherwise.
+inline AttendStream int4_wg8_stream(uint32_t n_layers, uint32_t n_tiles, uint32_t cus, bool cls, int32_t attend_splits, int32_t attend_stream)
+{
+    if (n_layers < 2u || attend_splits > 0 || attend_stream < 0) return AttendStream{};
+    const uint64_t total = static_cast<uint64_t>(n_layers) * n_tiles;
+    AttendStream s{};
+    if (attend_stream > 0) {
+        s = stream_cut(n_layers, n_tiles, static_cast<uint64_t>(attend_stream));
+        if ((cls && s.len < 2u) || s.max_slots > 2048u) return AttendStream{};
+    } else {
+        const uint64_t wgs = 2ull * static_cast<uint64_t>(cus);
+        if (total < 16u * wgs || n_tiles < kStreamMinTiles) return AttendStream{};
+        s = stream_cut(n_layers, n_tiles, wgs);
+    }
+    if (s.n_wgs && cls) s.tiles = n_tiles;
+    return s;
+}
+
+// MXFP4, records in one run (k_attend_mx4 form 3; one workgroup per CU and group of eight query rows): one piece per CU, from 28k context
+// (round 6: below it the fixed grid is ahead, 80 layers x 2k 0.48 (stream) against 0.55, 4k 0.61 / 0.66, 12k 0.77 / 0.83, 24k 0.81 / 0.82,
+// 32k 0.83 / 0.80, 64k 0.84 / 0.75; 70 layers x 4k 0.56 / 0.66, 100 layers x 4k 0.65 / 0.72; profiles/r06_layers_by_context.txt), and only
+// where the fixed grid would cut the layers (fixed_splits > 1: a fixed grid of whole layers writes final rows, no partials, no merge).
+// Whole tiles only (n_pages % 16 == 0: the kernel's stream form has no ragged last tile).  zgroups = ceil(g / 8).
+inline AttendStream mx4_stream(uint32_t n_layers, uint32_t n_tiles, uint32_t n_pages, uint32_t cus, uint32_t zgroups, uint32_t fixed_splits,
+                               int32_t attend_splits, int32_t attend_stream)
+{
+    if (n_layers < 2u || (n_pages & 15u) != 0u || attend_splits > 0 || attend_stream < 0) return AttendStream{};
+    const uint64_t total = static_cast<uint64_t>(n_layers) * n_tiles;
+    const uint32_t wgs = attend_stream > 0 ? static_cast<uint32_t>(attend_stream) : cus / std::max(1u, zgroups);
+    if (attend_stream == 0 && (total < 16ull * wgs || fixed_splits <= 1u || n_tiles < kStreamMinTiles)) return AttendStream{};
+    return stream_cut(n_layers, n_tiles, wgs);
 }
 
 } // namespace speckv

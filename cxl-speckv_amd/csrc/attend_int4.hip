@@ -801,7 +801,9 @@ __global__ __launch_bounds__(512 * HALVES) __attribute__((amdgpu_waves_per_eu(SP
         // compiler neither counts them nor waits for them by itself; ONE wait statement follows, with the query registers as its
         // operands (nothing that reads them can be placed in front of it): at most the five requests of the second tile stay in
         // flight behind it.  A run of a single tile requests that tile twice (the second copy is never read) so that the same
-        // count holds; a half without tiles asks for nothing.
+        // count holds; a half without tiles asks for nothing.  (Class form, stream: the first request of a tile that ends a layer moves
+        // the class cursor on into the next layer's regions, and the second copy is fetched from there -- behind the allocation when
+        // the layer is its last.  The engine never cuts such a call into one-tile pieces: attend_geometry.hpp int4_wg8_stream.)
         if (count != 0u) {
             const uint8_t* const k0p = kptr;
             const uint8_t* const v0p = vptr;

@@ -686,26 +686,7 @@ int Engine::attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t
 }
 
 // Launch geometry of the whole-record INT4 kernel (k_attend_int4_wg8; 512-thread workgroups, two resident per CU); `cus` = the
-// compute units of the ENGINE's device (Engine::cus()).
-// Stream form (many layers of one sequence): the launch's n_layers x n_tiles tiles, layer-major, in as many equal pieces as
-// workgroups are resident at once -- one pipeline fill per workgroup, no partial last round, few partials per layer.  Worth
-// it when a piece is long enough to amortise its fill (>= 16 tiles); *max_slots = most pieces any layer is cut into.
-constexpr uint32_t kStreamMinTiles = 896;            // context (tiles of 32 positions) from which several layers of one sequence take the stream form
-static bool int4_wg8_stream(uint32_t n_layers, uint32_t n_tiles, uint32_t cus, AttendArgs::Stream* out)
-{
-    const uint64_t total = static_cast<uint64_t>(n_layers) * n_tiles;
-    uint64_t wgs = 2ull * static_cast<uint64_t>(cus);
-    // (round 6: from 28k context only.  Below it the fixed grid of ONE round -- layers x splits <= CUs, whole-layer rows final or merged --
-    //  is faster: 80 layers x 4k 0.515 (stream) against 0.567, 8k 0.60 / 0.63, 16k 0.64 / 0.66, 24k 0.667 / 0.66, 32k 0.70 / 0.67, 64k 0.71 / 0.69;
-    //  70 layers x 4k 0.46 / 0.55; profiles/r06_layers_by_context.txt)
-    if (n_layers < 2 || total < 16u * wgs || n_tiles < kStreamMinTiles) return false;
-    out->n_wgs = static_cast<uint32_t>(wgs);
-    out->len = static_cast<uint32_t>(total / wgs);
-    out->rem = static_cast<uint32_t>(total % wgs);
-    out->max_slots = 1;
-    for (uint32_t l = 0; l < n_layers; ++l) out->max_slots = std::max(out->max_slots, attend_stream_count(l, n_tiles, out->len, out->rem));
-    return true;
-}
+// compute units of the ENGINE's device (Engine::cus()).  Its stream form for many layers of one sequence: attend_geometry.hpp int4_wg8_stream.
 // Fixed grid (per-layer calls, short launches): splits x layers workgroups, in whole rounds of the resident set when the
 // launch is that long, else as many 8-tile pieces as there are.
 static uint32_t int4_wg8_splits(uint32_t n_layers, uint32_t n_tiles, uint32_t cus)
@@ -766,8 +747,9 @@ int Engine::attend_int4(uint64_t handle, uint32_t layer, uint32_t n_layers, cons
     if (!wg8 && es.n_splits > 8u && (es.n_splits & 7u) && !forced_splits)      // the rounding can fall off a multiple of 8
         es = even_split(n_tiles, es.n_splits & ~7u);
     AttendArgs k{};
-    const bool stream = wg8 && !forced_splits && int4_wg8_stream(n_layers, n_tiles, cus(), &k.stream);
-    if (stream && cls) k.stream.tiles = n_tiles;                   // (the merge counts a layer's partials from the same tile count)
+    // several layers of one long sequence: the stream form (attend_geometry.hpp; SPECKV_ATTEND_STREAM cuts small calls for the tests)
+    if (wg8) k.stream = int4_wg8_stream(n_layers, n_tiles, cus(), cls, tuning().attend_splits, tuning().attend_stream);
+    const bool stream = k.stream.n_wgs != 0u;
     const uint32_t n_splits = stream ? k.stream.max_slots : es.n_splits, tiles_per_split = es.tiles_per_split;      // (stream: slots per row)
     if (!attend_scratch(k, static_cast<uint64_t>(rows) * n_splits, 0, s)) return SPECKV_ERR_NOMEM;
     seq_args(k, a, c.k_first, c.v_first, c.layer_stride, n_pages, g, sm_scale, d_zero_page_);
@@ -819,23 +801,9 @@ int Engine::attend_mx4(uint64_t handle, uint32_t layer, uint32_t n_layers, const
     const EvenSplit es = even_split(n_tiles, std::max(1u, std::min(want, 2048u)));
     AttendArgs k{};
     // several layers of one long sequence: the stream form -- all tiles of the call in layer-major order cut into one equal piece
-    // per CU (80 layers x 3 splits of the fixed grid occupy 240 CUs of 256; profiles/r05_mx4.txt) -- from 28k context (round 6: below it
-    // the fixed grid is ahead, 80 layers x 2k 0.48 (stream) against 0.55, 4k 0.61 / 0.66, 12k 0.77 / 0.83, 24k 0.81 / 0.82, 32k 0.83 / 0.80,
-    // 64k 0.84 / 0.75; 70 layers x 4k 0.56 / 0.66, 100 layers x 4k 0.65 / 0.72; profiles/r06_layers_by_context.txt)
-    const uint32_t zgroups = (g + 7u) / 8u;
-    const uint64_t total_tiles = static_cast<uint64_t>(n_layers) * n_tiles;
-    const int32_t stream_knob = tuning().attend_stream;                  // N > 0: that many pieces (tests cut small calls oddly), -1: never
-    const uint32_t stream_wgs = stream_knob > 0 ? static_cast<uint32_t>(stream_knob) : cus() / zgroups;
-    const bool stream = linear && n_layers >= 2u && (n_pages & 15u) == 0u && tuning().attend_splits <= 0 && stream_wgs >= 1u &&
-                        total_tiles >= stream_wgs && total_tiles / stream_wgs <= 0xFFFFFFFFull &&
-                        (stream_knob > 0 || (stream_knob == 0 && total_tiles >= 16ull * stream_wgs && es.n_splits > 1u && n_tiles >= kStreamMinTiles));      // (a fixed grid of whole layers writes final rows: no partials, no merge)
-    if (stream) {
-        k.stream.n_wgs = stream_wgs;
-        k.stream.len = static_cast<uint32_t>(total_tiles / stream_wgs);
-        k.stream.rem = static_cast<uint32_t>(total_tiles % stream_wgs);
-        k.stream.max_slots = 1;
-        for (uint32_t l = 0; l < n_layers; ++l) k.stream.max_slots = std::max(k.stream.max_slots, attend_stream_count(l, n_tiles, k.stream.len, k.stream.rem));
-    }
+    // per CU (80 layers x 3 splits of the fixed grid occupy 240 CUs of 256; profiles/r05_mx4.txt); the decision: attend_geometry.hpp
+    if (linear) k.stream = mx4_stream(n_layers, n_tiles, n_pages, cus(), (g + 7u) / 8u, es.n_splits, tuning().attend_splits, tuning().attend_stream);
+    const bool stream = k.stream.n_wgs != 0u;
     const uint32_t n_splits = stream ? k.stream.max_slots : es.n_splits, tiles_per_split = es.tiles_per_split;       // (stream: slots per row)
     if (!attend_scratch(k, static_cast<uint64_t>(rows) * n_splits, 0, s)) return SPECKV_ERR_NOMEM;
     seq_args(k, a, c.k_first, c.v_first, c.layer_stride, n_pages, g, sm_scale, d_zero_page_);

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "ring_rule.hpp"
 
 namespace speckv {
 
@@ -356,7 +357,8 @@ struct AttendArgs {
     // partials then sit at (row * max_slots + slot) and the merge takes each row's count from attend_stream_count().
     uint32_t scale_run = 0;          // FP8 class forms: the allocation's run-order scale table (CodecArgs::scale_run), 0 = none (gather from the page-order table)
     uint32_t fp8_cls = 0;            // FP8 over a regularly striped pool: k_attend_fp8_dma<2>, pages by residue class (n_splits / tiles_per_split count class-major tiles)
-    struct Stream { uint32_t len, rem, n_wgs, max_slots, tiles; } stream;      // tiles: per layer, 0 = ceil(n_pages / 16) (the class form of INT4_G32 over a striped pool counts by residue class)
+    using Stream = AttendStream;     // (ring_rule.hpp: {len, rem, n_wgs, max_slots, tiles})
+    Stream stream;                   // tiles: per layer, 0 = ceil(n_pages / 16) (the class form of INT4_G32 over a striped pool counts by residue class)
     // planned batches, MXFP4: the position a sequence still keeps OUTSIDE the pool (the connector's odd last position, fp16 rows
     // [tail][layers][heads][128], tail_stride elements apart) is folded in by the attention kernel itself -- by the workgroup of
     // split 0, into its partial or final state, in the epilogue -- instead of by a launch of its own behind every layer's attention.
@@ -367,23 +369,7 @@ struct AttendArgs {
     const int32_t* tail_idx;
     uint64_t tail_stride;
 };
-// The stream partition: `total` tiles in layer-major order cut into n_wgs contiguous pieces, the first `rem` one longer
-// (len = total / n_wgs >= 1, rem = total % n_wgs).  begin(w) = first tile of piece w; wg_of(G) = the piece tile G is in.
-__host__ __device__ inline uint64_t attend_stream_begin(uint32_t w, uint32_t len, uint32_t rem)
-{
-    return static_cast<uint64_t>(w) * len + (w < rem ? w : rem);
-}
-__host__ __device__ inline uint32_t attend_stream_wg_of(uint64_t G, uint32_t len, uint32_t rem)
-{
-    const uint64_t cut = static_cast<uint64_t>(rem) * (len + 1u);
-    return G < cut ? static_cast<uint32_t>(G / (len + 1u)) : rem + static_cast<uint32_t>((G - cut) / len);
-}
-// partials of layer `layer` (n_tiles tiles per layer): pieces wg_of(first tile) .. wg_of(last tile)
-__host__ __device__ inline uint32_t attend_stream_count(uint32_t layer, uint32_t n_tiles, uint32_t len, uint32_t rem)
-{
-    const uint64_t g0 = static_cast<uint64_t>(layer) * n_tiles;
-    return attend_stream_wg_of(g0 + n_tiles - 1u, len, rem) - attend_stream_wg_of(g0, len, rem) + 1u;
-}
+// (the stream partition -- attend_stream_begin / _wg_of / _count -- is plain arithmetic the host decides with too: ring_rule.hpp)
 // MXFP4 over a striped pool (k_attend_mx4 form 1): the positions of the range are taken CLASS by class -- class c = the pages j
 // of the range with j % stripe_n == c, which are consecutive records of ONE run for K and of one run for V -- each class in
 // tiles of 16 pages; every class gets the tile count of the largest (trailing tiles of the others are masked).

@@ -44,6 +44,30 @@ __host__ __device__ inline EvenSplit even_split(uint32_t n_tiles, uint32_t want)
     return EvenSplit{tps, (n_tiles + tps - 1u) / tps};
 }
 
+// ---- the stream partition of the INT4_G32 / MXFP4 attention (AttendArgs::stream; k_attend_int4_wg8, k_attend_mx4) ----------------
+// The kernels, the merge and the engine's decision (attend_geometry.hpp) cut a launch with the same three functions; the CPU tests
+// hold them to a brute-force count (tests/test_stream_rules_cpu.py).
+// len, rem, n_wgs: the cut below, n_wgs != 0 turns the form on; max_slots: most pieces any layer is cut into (the room of a row's
+// partials); tiles: per layer, 0 = ceil(n_pages / 16) (the class form of INT4_G32 over a striped pool counts by residue class)
+struct AttendStream { uint32_t len, rem, n_wgs, max_slots, tiles; };
+// The stream partition: `total` tiles in layer-major order cut into n_wgs contiguous pieces, the first `rem` one longer
+// (len = total / n_wgs >= 1, rem = total % n_wgs).  begin(w) = first tile of piece w; wg_of(G) = the piece tile G is in.
+__host__ __device__ inline uint64_t attend_stream_begin(uint32_t w, uint32_t len, uint32_t rem)
+{
+    return static_cast<uint64_t>(w) * len + (w < rem ? w : rem);
+}
+__host__ __device__ inline uint32_t attend_stream_wg_of(uint64_t G, uint32_t len, uint32_t rem)
+{
+    const uint64_t cut = static_cast<uint64_t>(rem) * (len + 1u);
+    return G < cut ? static_cast<uint32_t>(G / (len + 1u)) : rem + static_cast<uint32_t>((G - cut) / len);
+}
+// partials of layer `layer` (n_tiles tiles per layer): pieces wg_of(first tile) .. wg_of(last tile)
+__host__ __device__ inline uint32_t attend_stream_count(uint32_t layer, uint32_t n_tiles, uint32_t len, uint32_t rem)
+{
+    const uint64_t g0 = static_cast<uint64_t>(layer) * n_tiles;
+    return attend_stream_wg_of(g0 + n_tiles - 1u, len, rem) - attend_stream_wg_of(g0, len, rem) + 1u;
+}
+
 // INT4 batch attention launches with between half a machine and a whole one of workgroup columns (sequences x head groups in
 // [384, 672]; 768 workgroups are resident, three per CU -- profiles/tools/probe/occupancy_lds.hip): unsplit they leave the
 // CUs a third or more empty for the whole launch, and the kernel is bound by instruction issue, so occupancy is speed (256 x 8k:

@@ -248,14 +248,16 @@ class HeadChecker:
         self.oracle.lib.orc_quantize_rows_e4m3(_ptr(q16.view(np.uint16).reshape(-1), u16p), R, D, _ptr(q8, u8p), _ptr(qs, f32p))
         return lut[q8] * qs.astype(np.float64)[:, None]
 
-    def want_rows(self, q16, head, npos, sm, tail=None):
+    def want_rows(self, q16, head, npos, sm, tail=None, pos_begin=0):
         """q16 [M][G][D] fp16 of M members over this content, npos [M] -> out [M][G][D], lse [M][G], mag [M][G][D] (sum p|v|), delta [M]
         (as want(): the score error bound of the 8-bit formats, per member and head).  tail = (k [M][D], v [M][D]) fp16: one more
-        position per member, outside the pool (the kernel takes its score from the fp16 query)."""
+        position per member, outside the pool (the kernel takes its score from the fp16 query).  pos_begin: the members attend positions
+        [pos_begin, pos_begin + npos) of the region instead of its first npos."""
         q16 = np.asarray(q16, np.float16)
         M, G = q16.shape[:2]
         npos = np.asarray(npos, np.int64)
         K, V = self.kv(head)
+        K, V = K[pos_begin:], V[pos_begin:]
         qe = self.q_rows(q16).reshape(M, G, D)
         out = np.zeros((M, G, D)); mag = np.zeros((M, G, D)); lse = np.full((M, G), -np.inf); delta = np.zeros(M)
         for n in np.unique(npos):
@@ -280,11 +282,11 @@ class HeadChecker:
             lse[idx] = (mx + np.log(l)).reshape(m, G)
         return out, lse, mag, delta
 
-    def check_rows(self, got, got_lse, q16, head, npos, sm, what, tail=None):
+    def check_rows(self, got, got_lse, q16, head, npos, sm, what, tail=None, pos_begin=0):
         """every row of M members' head `head` against want_rows, with check()'s bound: |err| <= (2e-3 + 2 delta) sum p|v| + 1e-6,
-        |lse err| <= 2e-3 + delta; a member with no position (and no tail) exactly 0"""
-        want, wlse, mag, delta = self.want_rows(q16, head, npos, sm, tail)
-        got = np.asarray(got, np.float64); got_lse = np.asarray(got_lse, np.float64)
+        |lse err| <= 2e-3 + delta; a member with no position (and no tail) exactly 0.  got_lse None: a call without a log-sum-exp, out only."""
+        want, wlse, mag, delta = self.want_rows(q16, head, npos, sm, tail, pos_begin)
+        got = np.asarray(got, np.float64)
         npos = np.asarray(npos)
         empty = (npos == 0) if tail is None else np.zeros(len(npos), bool)
         assert np.all(got[empty] == 0.0), (what, "empty member not 0", np.nonzero(empty)[0].tolist())
@@ -294,6 +296,9 @@ class HeadChecker:
         bad = ~(err <= tol)
         assert not bad.any(), (what, "out", [int(i) for i in np.nonzero(live)[0][np.argwhere(bad)[0][:1]]], int(bad.sum()),
                                float((err / (mag[live] + 1e-9)).max()))
+        if got_lse is None:
+            return
+        got_lse = np.asarray(got_lse, np.float64)
         lerr = np.abs(got_lse[live] - wlse[live])
         lbad = ~(lerr <= (2e-3 + delta[live])[:, None])
         assert not lbad.any(), (what, "lse", [int(i) for i in np.nonzero(live)[0][np.argwhere(lbad)[0][:1]]], float(np.nanmax(lerr)))

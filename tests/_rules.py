@@ -24,6 +24,16 @@ def load_rules():
     lib.rules_plan_tiles_bound.argtypes = [C.c_uint32, C.c_uint32]
     lib.rules_batch_geometry.restype = C.c_uint64
     lib.rules_batch_geometry.argtypes = [C.c_uint32, P, I, P, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, P, P]
+    lib.rules_stream_begin.restype = C.c_uint64
+    lib.rules_stream_begin.argtypes = [C.c_uint32] * 3
+    lib.rules_stream_wg_of.restype = C.c_uint32
+    lib.rules_stream_wg_of.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.rules_stream_count.restype = C.c_uint32
+    lib.rules_stream_count.argtypes = [C.c_uint32] * 4
+    lib.rules_int4_wg8_stream.restype = None
+    lib.rules_int4_wg8_stream.argtypes = [C.c_uint32] * 4 + [C.c_int32] * 2 + [P]
+    lib.rules_mx4_stream.restype = None
+    lib.rules_mx4_stream.argtypes = [C.c_uint32] * 6 + [C.c_int32] * 2 + [P]
     return lib
 
 
@@ -68,3 +78,23 @@ def decide(lib, scheme, entry, pages, n_cus, heads=8, stripe_n=1, any_table=Fals
         lib.rules_batch_geometry(1, _p(shape), tun.ctypes.data_as(I), None, bound, 0, d["max_splits"], d["rows_first"], _p(launch), None)
         assert (launch[0], launch[2], launch[3]) == (d["tps"], d["max_splits"], d["rows_first"]), "attend_planned disagrees with its plan"
     return d
+
+
+# ---- several layers of ONE sequence: the stream decision of Engine::attend_int4 / attend_mx4 (attend_geometry.hpp int4_wg8_stream / mx4_stream)
+def _stream(out):
+    return None if out[0] == 0 else dict(zip(("n_wgs", "len", "rem", "max_slots", "tiles"), (int(v) for v in out)))
+
+
+def int4_stream(lib, n_layers, n_tiles, n_cus, cls=False, attend_splits=0, attend_stream=0):
+    """What Engine::attend_int4 decides for n_layers x n_tiles tiles on the whole-record kernel (n_tiles by residue class where cls):
+    None = the fixed grid, else the AttendArgs::stream fields."""
+    out = np.zeros(5, np.uint32)
+    lib.rules_int4_wg8_stream(n_layers, n_tiles, n_cus, int(cls), attend_splits, attend_stream, _p(out))
+    return _stream(out)
+
+
+def mx4_stream(lib, n_layers, n_pages, n_cus, g=8, fixed_splits=2, attend_splits=0, attend_stream=0):
+    """The same of Engine::attend_mx4 for records in one run; fixed_splits = the splits its fixed grid would take."""
+    out = np.zeros(5, np.uint32)
+    lib.rules_mx4_stream(n_layers, (n_pages + 15) // 16, n_pages, n_cus, (g + 7) // 8, fixed_splits, attend_splits, attend_stream, _p(out))
+    return _stream(out)

@@ -1,5 +1,6 @@
 // tests/csrc/host_rules_test.cpp -- TEST-ONLY C wrappers around the header-only host/device rules of the engine
-// (ring_rule.hpp: ring run / liveness arithmetic, even splits; attend_geometry.hpp: the launch decision of the batched attention), for the CPU property tests.
+// (ring_rule.hpp: ring run / liveness arithmetic, even splits, the stream partition; attend_geometry.hpp: the launch decision of the batched attention and the
+// stream decision of the single-sequence INT4_G32 / MXFP4 attention), for the CPU property tests.
 #include "../../cxl-speckv_amd/csrc/attend_geometry.hpp"
 
 extern "C" {
@@ -73,5 +74,21 @@ uint64_t rules_batch_geometry(uint32_t entry, const uint32_t* shape7, const int3
     const uint64_t parts = speckv::assign_pieces(g, s.heads, seqs.data(), s.n_seq);
     for (uint32_t i = 0; i < s.n_seq; ++i) { pieces[3 * i] = seqs[i].tiles_per_split; pieces[3 * i + 1] = seqs[i].n_splits; pieces[3 * i + 2] = seqs[i].part_base; }
     return parts;
+}
+
+// ---- the stream form of several layers of one sequence: the partition (ring_rule.hpp) and the two decisions (attend_geometry.hpp)
+uint64_t rules_stream_begin(uint32_t w, uint32_t len, uint32_t rem) { return speckv::attend_stream_begin(w, len, rem); }
+uint32_t rules_stream_wg_of(uint64_t G, uint32_t len, uint32_t rem) { return speckv::attend_stream_wg_of(G, len, rem); }
+uint32_t rules_stream_count(uint32_t layer, uint32_t n_tiles, uint32_t len, uint32_t rem) { return speckv::attend_stream_count(layer, n_tiles, len, rem); }
+static void stream_out(const speckv::AttendStream& s, uint32_t* out5) { out5[0] = s.n_wgs; out5[1] = s.len; out5[2] = s.rem; out5[3] = s.max_slots; out5[4] = s.tiles; }
+// out5 = {n_wgs (0: the fixed grid), len, rem, max_slots, tiles}
+void rules_int4_wg8_stream(uint32_t n_layers, uint32_t n_tiles, uint32_t cus, uint32_t cls, int32_t attend_splits, int32_t attend_stream, uint32_t* out5)
+{
+    stream_out(speckv::int4_wg8_stream(n_layers, n_tiles, cus, cls != 0u, attend_splits, attend_stream), out5);
+}
+void rules_mx4_stream(uint32_t n_layers, uint32_t n_tiles, uint32_t n_pages, uint32_t cus, uint32_t zgroups, uint32_t fixed_splits, int32_t attend_splits,
+                      int32_t attend_stream, uint32_t* out5)
+{
+    stream_out(speckv::mx4_stream(n_layers, n_tiles, n_pages, cus, zgroups, fixed_splits, attend_splits, attend_stream), out5);
 }
 }

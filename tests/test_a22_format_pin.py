@@ -425,3 +425,11 @@ def test_batched_head_checker_rows_equal_the_oracle_attention(oracle, scheme):
         vv = np.concatenate([V[:n], vt[i].astype(np.float64)[None]])
         assert np.allclose(out[i], p @ vv / p.sum(axis=1, keepdims=True), rtol=1e-9, atol=1e-12)
         assert np.allclose(lse[i], s.max(axis=1) + np.log(p.sum(axis=1)), rtol=0, atol=1e-9)
+    # a range that starts at pos_begin: the same as a checker built over the region from that position on
+    pb = 64
+    shifted = HeadChecker(oracle, scheme, np.concatenate([pages[pb // 2:T // 2], pages[T // 2 + pb // 2:]]), T - pb)
+    part = np.minimum(npos, T - pb)
+    got = hc.want_rows(q, 5, part, sm, pos_begin=pb)
+    for a, b in zip(got, shifted.want_rows(q, 5, part, sm)):
+        assert np.array_equal(a, b)
+    assert not np.array_equal(got[0][0], hc.want_rows(q, 5, part, sm)[0][0])
