@@ -172,6 +172,14 @@ speckv_status_t speckv_ext_write_pairs(const speckv_handle_t* handles, const uin
                                                       static_cast<hipStream_t>(stream)); });
 }
 
+speckv_status_t speckv_ext_read_pairs(const speckv_handle_t* handles, const uint64_t* first_pages, void* const* d_rows, uint32_t n_pairs,
+                                      uint64_t page_step, uint32_t n_layers, uint64_t layer_stride_bytes, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] { return g_engine->read_pairs(handles, first_pages, d_rows, n_pairs, page_step, n_layers, layer_stride_bytes,
+                                                     static_cast<hipStream_t>(stream)); });
+}
+
 speckv_status_t speckv_ext_write_runs(speckv_handle_t handle, const uint64_t* first_pages, const void* const* d_srcs, uint32_t n_runs,
                                       uint64_t n_pages_each, void* stream)
 {

@@ -169,6 +169,8 @@ public:
     int write_runs(uint64_t handle, const uint64_t* firsts, const void* const* d_srcs, uint32_t n_runs, uint64_t n_each, hipStream_t s);
     int write_pairs(const uint64_t* handles, const uint64_t* firsts, const void* const* d_rows, uint32_t n_pairs, uint64_t step,
                     uint32_t n_layers, uint64_t layer_stride, hipStream_t s);
+    int read_pairs(const uint64_t* handles, const uint64_t* firsts, void* const* d_rows, uint32_t n_pairs, uint64_t step,
+                   uint32_t n_layers, uint64_t layer_stride, hipStream_t s);
     int read(uint64_t handle, uint64_t off, void* dst, size_t len, bool on_device);
     int fetch_range(uint64_t handle, uint64_t first, uint64_t n, void* d_dst, bool f32, hipStream_t s, int engine_choice);
     int fetch_list(uint64_t handle, const uint32_t* d_pages, uint32_t n, void* d_dst, bool f32, hipStream_t s);
@@ -454,6 +456,7 @@ private:
     int migrate_mx4(Allocation* a, uint64_t first, uint64_t n, uint32_t target_pool);      // tile-planar records (engine_relocate.cpp)
     int unpack(Allocation* a);                            // a compacted allocation back into fixed slots (before any write / migration)
     int settle_for_relocation(Allocation*& a, uint64_t handle);
+    int descriptor_slot(size_t bytes, int* slot, void** staged, void** d_slot);      // next slot of grp_ring_ / d_groups_
     struct PairRows { uint32_t n_layers; uint64_t layer_stride; };      // the pair-gather form of write_groups
     int write_groups(const uint64_t* handles, const uint64_t* firsts, const void* const* d_srcs, uint32_t n_groups, uint64_t step,
                      uint64_t n_each, hipStream_t s, bool same_allocation, const PairRows* rows = nullptr);

@@ -162,6 +162,31 @@ int Engine::write_async(uint64_t handle, uint64_t off, const void* d_src, size_t
     return write_strided(handle, off / kPageSize, 1, len / kPageSize, d_src, s);
 }
 
+// The descriptors of a grouped launch (write_groups, read_pairs) travel pinned slot -> device slot: 4 of each in rotation, a
+// slot guarded by an event the caller records on its stream behind the kernel (grp_ring_.ev[slot]).  Hands out the next
+// slot, `bytes` long at least, once the launch that last used it is over -- that wait may release the ABI lock: allocations
+// looked up before it have to be looked up again.
+int Engine::descriptor_slot(size_t bytes, int* slot_out, void** staged, void** d_slot)
+{
+    if (grp_ring_.slot_bytes < bytes) {
+        HIP_TRY(hipDeviceSynchronize());
+        if (grp_ring_.base) { (void)hipHostFree(grp_ring_.base); grp_ring_.base = nullptr; }
+        if (d_groups_) { (void)hipFree(d_groups_); d_groups_ = nullptr; }
+        grp_ring_.slot_bytes = std::max<size_t>(bytes * 2, 16384);
+        HIP_TRY(hipHostMalloc(&grp_ring_.base, grp_ring_.slot_bytes * 4, hipHostMallocDefault));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_groups_), grp_ring_.slot_bytes * 4));
+        for (auto& ev : grp_ring_.ev)
+            if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    const int slot = grp_ring_.next;
+    grp_ring_.next = (slot + 1) & 3;
+    RC_TRY(wait_event(grp_ring_.ev[slot]));
+    *slot_out = slot;
+    *staged = static_cast<uint8_t*>(grp_ring_.base) + static_cast<size_t>(slot) * grp_ring_.slot_bytes;
+    *d_slot = reinterpret_cast<uint8_t*>(d_groups_) + static_cast<size_t>(slot) * grp_ring_.slot_bytes;
+    return SPECKV_OK;
+}
+
 // write_strided for a batch of allocations in one launch (the append of a decode step: SURVEY 8f row N2), and several
 // page runs of ONE allocation in one launch (a prompt's K / V regions: speckv_ext_write_runs).  Host side as in
 // write_strided per group (cached pages are invalidated first); the kernel takes one descriptor per group.
@@ -229,25 +254,12 @@ int Engine::write_groups(const uint64_t* handles, const uint64_t* firsts, const 
         RC_TRY(flush_mirror());
         RC_TRY(wait_stream());
     }
-    // descriptors: pinned slot -> device slot (4 of each in rotation, guarded by an event on the caller's stream)
     const size_t bytes = static_cast<size_t>(n_groups) * (rows ? sizeof(CommitPair) : sizeof(CompressGroup));
-    if (grp_ring_.slot_bytes < bytes) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (grp_ring_.base) { (void)hipHostFree(grp_ring_.base); grp_ring_.base = nullptr; }
-        if (d_groups_) { (void)hipFree(d_groups_); d_groups_ = nullptr; }
-        grp_ring_.slot_bytes = std::max<size_t>(bytes * 2, 16384);
-        HIP_TRY(hipHostMalloc(&grp_ring_.base, grp_ring_.slot_bytes * 4, hipHostMallocDefault));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_groups_), grp_ring_.slot_bytes * 4));
-        for (auto& ev : grp_ring_.ev)
-            if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    }
-    const int slot = grp_ring_.next;
-    grp_ring_.next = (slot + 1) & 3;
-    RC_TRY(wait_event(grp_ring_.ev[slot]));                   // may release the ABI lock
+    int slot = 0;
+    void *staged = nullptr, *d_slot = nullptr;
+    RC_TRY(descriptor_slot(bytes, &slot, &staged, &d_slot));  // may release the ABI lock
     for (uint32_t i = 0; i < n_groups; ++i)
         if ((as[i] = find(handles[same_allocation ? 0 : i])) == nullptr) return SPECKV_ERR_GENERAL;
-    void* staged = static_cast<uint8_t*>(grp_ring_.base) + static_cast<size_t>(slot) * grp_ring_.slot_bytes;
-    void* d_slot = reinterpret_cast<uint8_t*>(d_groups_) + static_cast<size_t>(slot) * grp_ring_.slot_bytes;
     for (uint32_t i = 0; i < n_groups; ++i) {
         const Allocation* a = as[i];
         if (rows) {
@@ -314,6 +326,69 @@ int Engine::write_pairs(const uint64_t* handles, const uint64_t* firsts, const v
     if (null_) return no_data_path("speckv_ext_write_pairs");
     const PairRows rows{n_layers, layer_stride};
     return write_groups(handles, firsts, d_rows, n_pairs, step, 2ull * n_layers, s, false, &rows);
+}
+
+// speckv_ext_read_pairs: write_pairs read backwards (the rollback of committed positions).  Pair i is pages first + j * step,
+// j < 2 * n_layers, of handles[i], decoded into d_rows[4 i .. 4 i + 3] (K even, K odd, V even, V odd; NULL = not wanted),
+// layer_stride bytes apart per layer, by ONE launch on the caller's stream.  Ordering: the kernel follows what the caller queued
+// on `s` before it (a commit on the same stream), as any stream call does; beyond that -- fetch_range leaves this to the caller --
+// `s` is made to wait for the event of the last asynchronous pool write on every OTHER caller stream the engine knows
+// (write_evs_; not while `s` is capturing), and the engine's own writes are synchronous.  Nothing is written to the pool,
+// so a sealed allocation stays sealed and cached copies stay valid.
+int Engine::read_pairs(const uint64_t* handles, const uint64_t* firsts, void* const* d_rows, uint32_t n_pairs, uint64_t step,
+                       uint32_t n_layers, uint64_t layer_stride, hipStream_t s)
+{
+    if (null_) return no_data_path("speckv_ext_read_pairs");
+    if (!handles || !firsts || !d_rows || step == 0 || !s || layer_stride % 16u) return SPECKV_ERR_INVAL;
+    if (n_pairs == 0 || n_layers == 0) return SPECKV_OK;
+    const uint64_t n_each = 2ull * n_layers;
+    const auto check = [&](uint32_t i, Allocation** out) -> int {
+        Allocation* a = find(handles[i]);
+        if (!a) return SPECKV_ERR_GENERAL;
+        for (uint32_t k = 0; k < 4; ++k)
+            if (reinterpret_cast<uintptr_t>(d_rows[4u * i + k]) % 16u) return SPECKV_ERR_INVAL;
+        if (a->scheme != find(handles[0])->scheme) return SPECKV_ERR_INVAL;
+        if (firsts[i] >= a->n_pages || (n_each - 1) > (a->n_pages - 1 - firsts[i]) / step) return SPECKV_ERR_GENERAL;
+        *out = a;
+        return SPECKV_OK;
+    };
+    std::vector<Allocation*> as(n_pairs);
+    for (uint32_t i = 0; i < n_pairs; ++i) RC_TRY(check(i, &as[i]));
+    DeviceScope device_scope(device_);
+    const size_t bytes = static_cast<size_t>(n_pairs) * sizeof(ReadPair);
+    int slot = 0;
+    void *staged = nullptr, *d_slot = nullptr;
+    RC_TRY(descriptor_slot(bytes, &slot, &staged, &d_slot));  // may release the ABI lock: every pair is judged again
+    for (uint32_t i = 0; i < n_pairs; ++i) RC_TRY(check(i, &as[i]));
+    for (uint32_t i = 0; i < n_pairs; ++i) {
+        void* const* r = d_rows + 4u * i;
+        static_cast<ReadPair*>(staged)[i] = ReadPair{as[i]->row, 0u, firsts[i],
+            {static_cast<uint8_t*>(r[0]), static_cast<uint8_t*>(r[1]), static_cast<uint8_t*>(r[2]), static_cast<uint8_t*>(r[3])}};
+    }
+    if (!is_capturing(s))
+        for (auto& w : write_evs_)
+            if (w.s != s) HIP_TRY(hipStreamWaitEvent(s, w.ev, 0));      // (`dirty` is about the engine's stream, not this one)
+    HIP_TRY(hipMemcpyAsync(d_slot, staged, bytes, hipMemcpyHostToDevice, s));
+    ReadPairArgs ra{};
+    ra.pairs = static_cast<const ReadPair*>(d_slot);
+    ra.tab = d_tab_;
+    ra.n_pairs = n_pairs;
+    ra.n_layers = n_layers;
+    ra.page_step = step;
+    ra.layer_stride = layer_stride;
+    ra.scheme = as[0]->scheme;
+    ra.quant_mode = quant_mode_;
+    HIP_TRY(launch_read_pairs(ra, s));
+    for (uint32_t i = 0; i < n_pairs; ++i) note_use(as[i], s);           // speckv_free waits for this stream
+    const uint64_t n = static_cast<uint64_t>(n_pairs) * n_each;
+    st_.total_decompressions += n;
+    st_.dma_submitted += n;
+    st_.dma_completed += n;                                    // completion belongs to the caller's stream
+    if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel
+        (void)hipGetLastError();
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return SPECKV_OK;
 }
 
 int Engine::write_runs(uint64_t handle, const uint64_t* firsts, const void* const* d_srcs, uint32_t n_runs, uint64_t n_each, hipStream_t s)

@@ -35,6 +35,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace speckv {
 namespace {
@@ -149,14 +150,36 @@ __device__ __forceinline__ void store8_f32(uint8_t* dst, uint32_t p0, const floa
     st16(base, a);
     st16(base + 1024, b);
 }
-template <bool F32>
-__device__ __forceinline__ void store8(uint8_t* dst, uint32_t p0, const float (&y)[8])
+// Where a decoder puts a block's fp16 image.  Every decoder below takes its destination as a type: a plain pointer is the
+// contiguous 4 KiB image (fetch, ring, flush), a RowSink the two position rows of a page where a caller holds them apart
+// (k_read_pairs).  The decoders ask wants() per 512-element chunk before they load anything of it and hand whole chunks to
+// put16 / store8 -- p0 = 512 j + 8 lane, so a chunk lies in one half of the block and `p0 < 1024` is wave-uniform.
+struct RowSink {
+    uint8_t* even;      // elements [0, 1024): the even position's [heads][128] row; nullptr = not wanted
+    uint8_t* odd;       // elements [1024, 2048)
+    __device__ __forceinline__ uint8_t* row(uint32_t p) const { return p < 1024u ? even : odd; }
+};
+// (how a decoder declares its destination parameter: a plain pointer keeps the __restrict__ it always had)
+template <class DST> struct dst_arg { typedef const DST& type; };
+template <> struct dst_arg<uint8_t*> { typedef uint8_t* __restrict__ type; };
+__device__ __forceinline__ bool wants(const uint8_t*, uint32_t) { return true; }
+__device__ __forceinline__ bool wants(const RowSink& d, uint32_t p0) { return d.row(p0) != nullptr; }
+__device__ __forceinline__ void put16(const RowSink& d, uint32_t p0, uint4 v)
 {
-    if (F32) {
+    uint8_t* r = d.row(p0);
+    if (r) st16(r + 2ull * (p0 & 1023u), v);
+}
+template <bool F32, class DST>
+__device__ __forceinline__ void store8(const DST& dst, uint32_t p0, const float (&y)[8])
+{
+    if constexpr (F32) {
         store8_f32(dst, p0, y);
-    } else {
+    } else if constexpr (!std::is_same<DST, RowSink>::value) {         // (the address in front of the conversions, as it always stood)
         st16(dst + 2ull * p0, make_uint4(pack_half2(y[0], y[1]), pack_half2(y[2], y[3]),
                                          pack_half2(y[4], y[5]), pack_half2(y[6], y[7])));
+    } else {
+        put16(dst, p0, make_uint4(pack_half2(y[0], y[1]), pack_half2(y[2], y[3]),
+                                  pack_half2(y[4], y[5]), pack_half2(y[6], y[7])));
     }
 }
 
@@ -271,9 +294,9 @@ __device__ __forceinline__ bool rle_pair_chunk(const uint4 wv, uint32_t pair0, u
 // FLAT (the kernel of its own that launches hinted "structured" run, k_fetch_decompress_flat: CodecArgs::structured_hint; the
 // kernels the headline fetch runs are instantiated without it): blocks that are piecewise constant on 8-element boundaries
 // skip the scans, recurrences and conversions of the general loop -- see the whole-block path in front of it.
-template <int MODE, bool F32, bool FLAT = false>
+template <int MODE, bool F32, bool FLAT = false, class DST = uint8_t*>
 __device__ __forceinline__ bool decode_rle_fast(const uint8_t* __restrict__ rec, uint32_t len,
-                                                float scale, uint8_t* __restrict__ dst,
+                                                float scale, typename dst_arg<DST>::type dst,
                                                 uint8_t* tab, uint32_t lane, bool trusted)
 {
     const uint32_t npairs = len >> 1;                       // odd trailing byte dropped
@@ -415,9 +438,16 @@ __device__ __forceinline__ void store_elem(uint8_t* dst, uint32_t p, float y)
         gstore<uint16_t>(dst + 2ull * p, static_cast<uint16_t>(pack_half2(a, z) & 0xFFFFu));
     }
 }
-template <int MODE, bool F32>
-__device__ __noinline__ void decode_rle_general(const uint8_t* __restrict__ rec, uint32_t len,
-                                                float scale, uint8_t* __restrict__ dst, uint32_t lane)
+template <bool F32>
+__device__ __forceinline__ void store_elem(const RowSink& d, uint32_t p, float y)
+{
+    static_assert(!F32, "position rows are fp16");
+    uint8_t* r = d.row(p);
+    if (r) store_elem<false>(r, p & 1023u, y);
+}
+template <int MODE, bool F32, class DST>
+__device__ __forceinline__ void decode_rle_general_to(const uint8_t* __restrict__ rec, uint32_t len,
+                                                      float scale, typename dst_arg<DST>::type dst, uint32_t lane)
 {
     const uint32_t npairs = len >> 1;
     uint32_t carry = 0;                                     // (sum v*c mod 256)<<24 | sum c
@@ -446,15 +476,24 @@ __device__ __noinline__ void decode_rle_general(const uint8_t* __restrict__ rec,
 #pragma unroll 1
     for (uint32_t p = total + lane; p < kBlockElems; p += 64u) store_elem<F32>(dst, p, 0.0f);
 }
+// (out of line for the block images: one copy per quantiser mode and output width, called from every fetch kernel; a RowSink
+// caller takes the body above inline, so that no further function comes to lie between these and the kernels that call them)
+template <int MODE, bool F32>
+__device__ __noinline__ void decode_rle_general(const uint8_t* __restrict__ rec, uint32_t len,
+                                                float scale, uint8_t* __restrict__ dst, uint32_t lane)
+{
+    decode_rle_general_to<MODE, F32, uint8_t*>(rec, len, scale, dst, lane);
+}
 
 // decode: INT8 (quantise only)
-template <int MODE, bool F32>
+template <int MODE, bool F32, class DST = uint8_t*>
 __device__ __forceinline__ void decode_int8(const uint8_t* __restrict__ rec, uint32_t len,
-                                            float scale, uint8_t* __restrict__ dst, uint32_t lane)
+                                            float scale, typename dst_arg<DST>::type dst, uint32_t lane)
 {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const uint32_t p0 = 512u * j + 8u * lane;
+        if (!wants(dst, p0)) continue;
         uint2 w = make_uint2(0u, 0u);
         if (p0 < len) w = gload_u2(rec + p0);
         float y[8];
@@ -469,16 +508,17 @@ __device__ __forceinline__ void decode_int8(const uint8_t* __restrict__ rec, uin
 }
 
 // decode: FP16 (raw copy, optional widening)
-template <bool F32>
+template <bool F32, class DST = uint8_t*>
 __device__ __forceinline__ void decode_fp16(const uint8_t* __restrict__ rec, uint32_t len,
-                                            uint8_t* __restrict__ dst, uint32_t lane)
+                                            typename dst_arg<DST>::type dst, uint32_t lane)
 {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const uint32_t p0 = 512u * j + 8u * lane;
+        if (!wants(dst, p0)) continue;
         uint4 w = make_uint4(0u, 0u, 0u, 0u);
         if (2u * p0 < len) w = ld16(rec + 2ull * p0);
-        if (!F32) {
+        if constexpr (!F32) {
             // mask a ragged tail at element granularity
             const uint32_t words[4] = {w.x, w.y, w.z, w.w};
             uint32_t o[4];
@@ -488,7 +528,8 @@ __device__ __forceinline__ void decode_fp16(const uint8_t* __restrict__ rec, uin
                 uint32_t hi = (2u * (p0 + 2 * t + 1) + 1u < len) ? (words[t] & 0xFFFF0000u) : 0u;
                 o[t] = lo | hi;
             }
-            st16(dst + 2ull * p0, make_uint4(o[0], o[1], o[2], o[3]));
+            if constexpr (!std::is_same<DST, RowSink>::value) st16(dst + 2ull * p0, make_uint4(o[0], o[1], o[2], o[3]));
+            else put16(dst, p0, make_uint4(o[0], o[1], o[2], o[3]));
         } else {
             const uint32_t words[4] = {w.x, w.y, w.z, w.w};
             float y[8];
@@ -503,14 +544,15 @@ __device__ __forceinline__ void decode_fp16(const uint8_t* __restrict__ rec, uin
 }
 
 // decode: INT4_G32 (config 5 extension; record = 64 fp16 scales + 1024 B nibbles)
-template <bool F32>
+template <bool F32, class DST = uint8_t*>
 __device__ __forceinline__ void decode_int4(const uint8_t* __restrict__ rec, uint32_t len,
-                                            uint8_t* __restrict__ dst, uint32_t lane)
+                                            typename dst_arg<DST>::type dst, uint32_t lane)
 {
     const bool ok = len >= kInt4RecBytes;                    // short record decodes to zeros
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const uint32_t p0 = 512u * j + 8u * lane;
+        if (!wants(dst, p0)) continue;                       // (a row's 32 group scales are words 32 (p0 >> 10) .. + 31: only they are read)
         uint32_t nib = 0;
         float s = 0.0f;
         if (ok) {
@@ -534,9 +576,11 @@ __device__ __forceinline__ void decode_int4(const uint8_t* __restrict__ rec, uin
 // 255) -- the product is exact in fp32.  A lane takes bytes 8l .. 8l+7 of both 512-byte halves of the nibble area: elements
 // [512 j + 8 l, + 8) for j = 0, 1 and their partners 1024 further on (j = 2, 3 of every other decoder's lane map).
 typedef float f32x2v __attribute__((ext_vector_type(2)));
-template <bool F32>
+// (A byte carries both positions, so a RowSink that wants one of them still reads all 1024 nibble bytes and the 64 codes, and the
+// conversion widens both nibbles of a byte at once: both planes are computed, only the store of the plane nobody wants is left out.)
+template <bool F32, class DST = uint8_t*>
 __device__ __forceinline__ void decode_mx4(const uint8_t* __restrict__ rec, const uint8_t* __restrict__ codes, uint32_t len,
-                                           uint8_t* __restrict__ dst, uint32_t lane)
+                                           typename dst_arg<DST>::type dst, uint32_t lane)
 {
     const bool ok = len >= kMx4RecBytes;                     // short record decodes to zeros
 #pragma unroll
@@ -560,13 +604,14 @@ __device__ __forceinline__ void decode_mx4(const uint8_t* __restrict__ rec, cons
 }
 
 // decode: FP8_E4M3 (config 5 extension; per-block scale)
-template <bool F32>
+template <bool F32, class DST = uint8_t*>
 __device__ __forceinline__ void decode_fp8(const uint8_t* __restrict__ rec, uint32_t len,
-                                           float scale, uint8_t* __restrict__ dst, uint32_t lane)
+                                           float scale, typename dst_arg<DST>::type dst, uint32_t lane)
 {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const uint32_t p0 = 512u * j + 8u * lane;
+        if (!wants(dst, p0)) continue;
         uint2 w = make_uint2(0u, 0u);
         if (p0 < len) w = gload_u2(rec + p0);
         float y[8];
@@ -1685,6 +1730,85 @@ hipError_t launch_compress_pairs(const PairArgs& a, hipStream_t s)
     case kInt4G32: return launch_enc_pairs<kInt4G32, kRefExact>(a, grid, s);         // the quantiser mode does not apply
     case kFp8E4m3: return launch_enc_pairs<kFp8E4m3, kRefExact>(a, grid, s);
     case kMxFp4: return launch_enc_pairs<kMxFp4, kRefExact>(a, grid, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// The inverse of the pair-gather encoder (Engine::read_pairs: the rollback of committed positions).  Wave i decodes block
+// j = i % (2 * n_layers) of position pair i / (2 * n_layers) -- layer j >> 1, kind j & 1, page first + j * page_step of the
+// allocation in table row `row` -- into the pair's two rows of that kind, layer_stride bytes further on per layer.  The record is
+// found through the allocation table and the page's entry like every fetch (linear, striped, migrated, sealed: one body), and
+// decoded by the fetch kernel's own decoders through a RowSink: a row that is not wanted is neither loaded (FP16,
+// INT8, FP8, INT4_G32 and its group scales) nor stored (every scheme; the RLE stream and the MXFP4 nibble bytes carry both
+// positions and are decoded whole).  Stores are 16 B per lane, 1 KiB per instruction.  One block per wave, no workgroup barrier.  Its launcher is the
+// last of the translation unit, behind launch_compress_pairs, for the reason given there.
+namespace {
+template <int SCHEME, int MODE>
+__global__ __launch_bounds__(kThreads) void k_read_pairs(ReadPairArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds[SCHEME == kInt8DeltaRle ? kWaves * kDecLdsWords : 4];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
+    const uint32_t per = 2u * a.n_layers;
+    if (i >= static_cast<uint64_t>(a.n_pairs) * per) return;        // (whole waves leave: the body has no workgroup barrier)
+    const uint32_t pi = static_cast<uint32_t>(i / per), j = static_cast<uint32_t>(i - static_cast<uint64_t>(pi) * per);
+    const ReadPair* g = a.pairs + pi;
+    const uint32_t kind = j & 1u;
+    const uint64_t off = static_cast<uint64_t>(j >> 1) * a.layer_stride;
+    uint8_t* const even = g->row[2u * kind];
+    uint8_t* const odd = g->row[2u * kind + 1u];
+    const RowSink dst{even ? even + off : nullptr, odd ? odd + off : nullptr};
+    if (!dst.even && !dst.odd) return;
+    const PageEntry* entries = a.tab[g->table_row].entries;
+    PageEntry e{0, 0, 1.0f};
+    if (entries) e = entries[g->first + static_cast<uint64_t>(j) * a.page_step];     // a row freed meanwhile decodes as a never-written page
+    // the decoders of fetch_decompress_body, told where the two rows go (pool records: trusted streams, tile-planar MXFP4 codes)
+    const uint8_t* rec = reinterpret_cast<const uint8_t*>(e.pool_addr);
+    uint32_t len = e.rec_bytes;
+    if (SCHEME == kInt8DeltaRle) {
+        if (len > 2u * kBlockElems) len = 2u * kBlockElems;
+        uint32_t* region = lds + wave * kDecLdsWords;
+        if (!decode_rle_fast<MODE, false, false, RowSink>(rec, len, e.scale, dst, reinterpret_cast<uint8_t*>(region), lane, true))
+            decode_rle_general_to<MODE, false, RowSink>(rec, len, e.scale, dst, lane);
+    } else if (SCHEME == kInt8) {
+        decode_int8<MODE, false, RowSink>(rec, len > kBlockElems ? kBlockElems : len, e.scale, dst, lane);
+    } else if (SCHEME == kInt4G32) {
+        decode_int4<false, RowSink>(rec, len, dst, lane);
+    } else if (SCHEME == kMxFp4) {
+        decode_mx4<false, RowSink>(rec, rec + __float_as_uint(e.scale), len, dst, lane);
+    } else if (SCHEME == kFp8E4m3) {
+        decode_fp8<false, RowSink>(rec, len > kBlockElems ? kBlockElems : len, e.scale, dst, lane);
+    } else {
+        decode_fp16<false, RowSink>(rec, len > 2u * kBlockElems ? 2u * kBlockElems : len, dst, lane);
+    }
+}
+template <int SCHEME, int MODE>
+hipError_t launch_dec_pairs(const ReadPairArgs& a, uint32_t grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_read_pairs<SCHEME, MODE>), dim3(grid), dim3(kThreads), 0, s, a);
+    return hipGetLastError();
+}
+template <int SCHEME>
+hipError_t launch_dec_pairs_mode(const ReadPairArgs& a, uint32_t grid, hipStream_t s)
+{
+    return a.quant_mode == kIntent ? launch_dec_pairs<SCHEME, kIntent>(a, grid, s) : launch_dec_pairs<SCHEME, kRefExact>(a, grid, s);
+}
+} // namespace
+
+hipError_t launch_read_pairs(const ReadPairArgs& a, hipStream_t s)
+{
+    const uint64_t waves = static_cast<uint64_t>(a.n_pairs) * 2u * a.n_layers;       // one block per wave
+    if (waves == 0) return hipSuccess;
+    if (!a.pairs || !a.tab || a.page_step == 0 || a.layer_stride % 16u || waves > (1ull << 31)) return hipErrorInvalidValue;
+    const uint32_t grid = static_cast<uint32_t>((waves + kWaves - 1) / kWaves);
+    switch (a.scheme) {
+    case kFp16: return launch_dec_pairs<kFp16, kRefExact>(a, grid, s);               // (a copy: no quantiser)
+    case kInt8: return launch_dec_pairs_mode<kInt8>(a, grid, s);
+    case kInt8DeltaRle: return launch_dec_pairs_mode<kInt8DeltaRle>(a, grid, s);
+    case kInt4G32: return launch_dec_pairs<kInt4G32, kRefExact>(a, grid, s);         // the quantiser mode does not apply
+    case kFp8E4m3: return launch_dec_pairs<kFp8E4m3, kRefExact>(a, grid, s);
+    case kMxFp4: return launch_dec_pairs<kMxFp4, kRefExact>(a, grid, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -96,6 +96,27 @@ struct PairArgs {
     int               quant_mode;
 };
 
+// One position pair of one request in a pair-read launch (ReadPairArgs::pairs), the mirror image of CommitPair: block
+// j < 2 * n_layers is page first + j * page_step of the allocation in table row `table_row`; its first 2048 decoded bytes go to
+// row[2 * kind] + layer * layer_stride, its second 2048 to row[2 * kind + 1] + layer * layer_stride.  A row that is nullptr is
+// not wanted; the others are 16-byte aligned.
+struct ReadPair {
+    uint32_t table_row;               // DevAlloc row of the allocation
+    uint32_t reserved;
+    uint64_t first;
+    uint8_t* row[4];                  // K even, K odd, V even, V odd
+};
+struct ReadPairArgs {
+    const ReadPair* pairs;            // device array
+    const DevAlloc* tab;              // the device allocation table
+    uint32_t        n_pairs;
+    uint32_t        n_layers;
+    uint64_t        page_step;
+    uint64_t        layer_stride;     // bytes, a multiple of 16
+    int             scheme;
+    int             quant_mode;
+};
+
 // Source / destination description of one codec launch.  Exactly one of
 // {entries, recs, tab+alloc_list} is used as the record source.
 struct CodecArgs {
@@ -186,6 +207,7 @@ hipError_t launch_compress(const CodecArgs& a, hipStream_t s);
 hipError_t launch_decompress(const CodecArgs& a, hipStream_t s);
 // the pair-gather form of the encoder: n_pairs * 2 * n_layers blocks in one launch, rows read where they lie (k_compress_pairs)
 hipError_t launch_compress_pairs(const PairArgs& a, hipStream_t s);
+hipError_t launch_read_pairs(const ReadPairArgs& a, hipStream_t s);
 
 // FPGACacheEngine::compress / ::decompress over a tensor of any length (tensor_codec.hip): one scale, one delta chain and
 // one run-length stream across the whole tensor.  d_rle: 16-byte aligned, room for 2n bytes rounded up to 16; d_ws:

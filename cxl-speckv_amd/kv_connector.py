@@ -19,6 +19,9 @@ paged-attention layer would talk to for a BATCH of requests:
                                batches): the S new positions ride through the same pass over the records as extra query
                                rows, the rows held outside the pool are folded in causally by one launch
                                (``speckv_ext_attend_fold_held``); then the accepted prefix is committed
+  commit / truncate            the commit in one launch (``speckv_ext_write_pairs``), and its undo: roll requests back to shorter
+                               lengths, the new odd last positions read back out of their pairs by one launch
+                               (``speckv_ext_read_pairs``)
   tree_masks / append_path     the same step with drafts that form a TREE (``attend_spec(parents=...)``): a node sees its
                                ancestors only, the held rows are folded in by ``speckv_ext_attend_fold_masked`` with one mask
                                word per (request, node); then the accepted root-to-node path is committed
@@ -762,6 +765,88 @@ class SpeckvKVConnector:
                 self.lib.write_pairs(handles, plan[:, 1].astype(np.uint64), rows, self.region_pages, self.L, self.H * self.D * 2, st.cuda_stream)
         self._committed(req_ids, reqs, used, tails, tk, tv, n_accept)
         return keep
+
+    # ------------------------------------------------------------------ rollback
+    @staticmethod
+    def truncate_plan(lengths: Sequence[int], new_lengths: Sequence[int]):
+        """What cutting request b from lengths[b] back to new_lengths[b] positions comes to.  Returns (drops, reads): drops = [b] for the
+        requests that only let go of the odd position they hold (an even new length below an odd length); reads = [(b, page of the K
+        region of layer 0)] for the requests whose new last position new_len - 1 is the first half of a stored pair and has to come
+        back out of the pool, page (new_len - 1) // 2 (an odd new length below the length: the position is always a stored one, and it
+        replaces whatever the request held).  A request with new_len == length, or with two even lengths, appears in neither.
+        ValueError for new_len > length or new_len < 0.  Pure python, no device."""
+        drops, reads = [], []
+        for b, (ln, new) in enumerate(zip(lengths, new_lengths)):
+            ln, new = int(ln), int(new)
+            if not 0 <= new <= ln:
+                raise ValueError(f"request #{b}: cannot cut {ln} positions to {new}")
+            if new == ln:
+                continue
+            if new & 1:
+                reads.append((b, (new - 1) // 2))
+            elif ln & 1:
+                drops.append(b)
+        return drops, reads
+
+    def truncate(self, req_ids: Sequence[int], new_lengths: Sequence[int], stream=None):
+        """Roll the requests back to new_lengths[b] <= length positions: afterwards lengths, tails and plan bookkeeping are those of a
+        connector that had stopped there.  A request cut to an odd length inside stored pairs gets its new last position back as its
+        tail: ONE speckv_ext_read_pairs call for the whole batch decodes that row -- the even half of page (new_len - 1) // 2 -- for
+        every layer, K and V, into one [n][layers][heads][dim] tensor pair (the odd halves are not asked for and not read where the
+        format keeps them apart).  No other launch; when no request needs a row back, no launch at all.  ValueError (truncate_plan)
+        before any state changes.  The allocation keeps its size.
+
+        K pre-scale (set_k_channel_scale): a row read back is what commit() stored, K / scale -- and that is what every tail holds
+        (append() and commit() scale k_new before they keep a tail; kv_rows() scales tails and pages back alike).  So the row is
+        installed as it comes, and the commit that pairs it with a new position writes it unscaled a second time: nothing here or
+        there multiplies it again.  The row has been through the format once; its page is encoded again with its new partner.
+
+        Records beyond the new length stay in the pool as stale bytes, and nothing clears them, because their values are never used:
+        the attention kernels of all three families (FP8, INT4_G32, MXFP4) take their range from the plan's pos_end and set the scores
+        of positions at or beyond it inside the last 32-position tile to -inf before the softmax -- they have to, a never-written
+        position of score 0 would otherwise weigh exp(0 - max) -- and the weight of a masked position is exactly 0.  The held-row folds
+        (attend_fold_held / _masked) never touch the pool.  The rewrite of a pair replaces the stale record whole.  Run:
+        tests/test_gpu_rollback.py writes rows of 200x / 1000x the magnitude of the kept ones behind the cut and holds attend /
+        attend_spec to the float64 reference, in the forms those calls select for small batches of up to 128 positions; the masking
+        of the other forms (residue classes, the stream forms of large batches) was read in the source, not run against stale rows.
+        One difference to a never-written page remains: a stale V row that is not finite (the caller stored inf or NaN there) times a
+        weight of 0 is NaN where zeros gave 0.  A caller that may have committed non-finite rows rewrites or frees before it rolls back."""
+        import numpy as np
+        import torch
+        reqs = [self.requests[rid] for rid in req_ids]
+        new_lengths = [int(n) for n in new_lengths]
+        if len(new_lengths) != len(reqs):
+            raise ValueError("new_lengths: one length per request")
+        drops, reads = self.truncate_plan([r.length for r in reqs], new_lengths)
+        if all(n == r.length for n, r in zip(new_lengths, reqs)):
+            return
+        if reads:
+            n = len(reads)
+            row_bytes = self.L * self.H * self.D * 2
+            with self._On(self, stream) as st:
+                with torch.cuda.stream(st):
+                    tk = torch.empty((n, self.L, self.H, self.D), dtype=torch.float16, device="cuda")
+                    tv = torch.empty_like(tk)
+                rows = np.zeros((n, 4), dtype=np.uint64)                                         # odd rows: 0 = not wanted
+                at = np.arange(n, dtype=np.uint64) * np.uint64(row_bytes)
+                rows[:, 0], rows[:, 2] = at + np.uint64(tk.data_ptr()), at + np.uint64(tv.data_ptr())
+                handles = np.asarray([reqs[b].handle for b, _ in reads], dtype=np.uint64)
+                firsts = np.asarray([page for _, page in reads], dtype=np.uint64)              # _page(0, 0, pos) = pos // 2
+                self.lib.read_pairs(handles, firsts, rows, self.region_pages, self.L, self.H * self.D * 2, st.cuda_stream)
+        touched = set(drops) | {b for b, _ in reads}
+        for b in drops:
+            reqs[b].clear_tail()
+        for i, (b, _) in enumerate(reads):
+            reqs[b].set_tail(tk, tv, i)                                                          # as _committed installs tails
+        if reads:
+            self._tail_ids, self._tail_k, self._tail_v = tuple(req_ids[b] for b, _ in reads), tk, tv
+        elif any(req_ids[b] in self._tail_ids for b in touched):
+            self._tail_ids, self._tail_k, self._tail_v = (), None, None
+        for r, n in zip(reqs, new_lengths):
+            r.length = n
+        self._epoch += 1
+        self._arg_key = self._fold_key = None                  # the plan names ranges that no longer hold: the next attend plans again
+        self._plan_stream = None
 
     def append_tokens(self, req_ids: Sequence[int], k_new, v_new, n_accept: Sequence[int], stream=None):
         """Commit the first n_accept[b] (0..S) of the S new positions k_new[b], v_new[b] ([batch][S][layers][heads][dim] fp16) of every

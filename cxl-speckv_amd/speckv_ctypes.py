@@ -60,6 +60,7 @@ _EXT_SIGNATURES = {
     "speckv_ext_write_async": [c_uint64, c_uint64, c_void_p, c_size_t, c_void_p],
     "speckv_ext_write_runs": [c_uint64, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p],
     "speckv_ext_write_pairs": [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_uint64, c_void_p],
+    "speckv_ext_read_pairs": [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_uint64, c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
     "speckv_ext_bind_request": [c_uint32, c_uint64, c_uint32],
@@ -280,6 +281,17 @@ class SpeckvLib:
             rows = [p for r in rows for p in r]
         hs, fs, rs = as_arr(handles, c_uint64, n), as_arr(first_pages, c_uint64, n), as_arr(rows, c_uint64, 4 * n)
         self._ext("speckv_ext_write_pairs", hs, fs, rs, n, page_step, n_layers, layer_stride, c_void_p(stream))
+
+    def read_pairs(self, handles, first_pages, rows, page_step, n_layers, layer_stride, stream):
+        """write_pairs read backwards, in ONE launch (the rollback of committed positions): pair i = pages first_pages[i] + j*page_step
+        (j < 2*n_layers) of handles[i], each page decoded into two rows -- rows[i] = (K even, K odd, V even, V odd) device addresses,
+        layer_stride bytes apart per layer; an address of 0 = that row is not wanted and is not written.  Arguments as write_pairs."""
+        n = len(handles)
+        as_arr = lambda v, t, m: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * m)(*v))
+        if not hasattr(rows, "ctypes") and not isinstance(rows, ctypes.Array):
+            rows = [p for r in rows for p in r]
+        hs, fs, rs = as_arr(handles, c_uint64, n), as_arr(first_pages, c_uint64, n), as_arr(rows, c_uint64, 4 * n)
+        self._ext("speckv_ext_read_pairs", hs, fs, rs, n, page_step, n_layers, layer_stride, c_void_p(stream))
 
     def read(self, handle, offset, dst_ptr, nbytes, on_device):
         self._ext("speckv_ext_read", handle, offset, c_void_p(dst_ptr), nbytes, int(on_device))

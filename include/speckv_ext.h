@@ -126,6 +126,24 @@ speckv_status_t speckv_ext_write_pairs(const speckv_handle_t* handles, const uin
                                        const void* const* d_rows /* [n_pairs][4]: K even, K odd, V even, V odd */,
                                        uint32_t n_pairs, uint64_t page_step, uint32_t n_layers,
                                        uint64_t layer_stride_bytes, void* stream);
+/* speckv_ext_write_pairs read backwards, argument for argument: the rollback of committed positions.  Pair i names pages
+ * first_pages[i] + j * page_step, j < 2 * n_layers, of allocation handles[i] (page j: layer j / 2, kind j % 2).  The first 2048
+ * decoded bytes of a page -- the even position's row, [heads][128] fp16 -- go to d_rows[4 * i + 2 * kind] + layer *
+ * layer_stride_bytes, the second 2048 to d_rows[4 * i + 2 * kind + 1] + layer * layer_stride_bytes.  A NULL row is not wanted:
+ * that half of the page is not written (and, where the format keeps the halves apart, not read).  The bits are the
+ * corresponding half of what speckv_ext_fetch_range writes for that page as fp16, for every scheme; a page never written gives
+ * zeros.  ONE launch decodes every row where its record lies (linear, striped, migrated and sealed allocations alike; a
+ * sealed allocation stays sealed).  Asynchronous on `stream`, behind what the caller queued there before (a commit on the
+ * same stream) and behind the asynchronous pool writes (speckv_ext_write_async and its kin) handed to other streams before the
+ * call, unless `stream` is capturing; the rows must stay alive until the stream has passed the call.
+ *   SPECKV_ERR_INVAL    NULL stream or arrays, a row not 16-byte aligned, layer_stride_bytes not a multiple of 16,
+ *                       page_step == 0, allocations of different schemes
+ *   SPECKV_ERR_GENERAL  an unknown handle, pages that leave the allocation
+ * n_pairs == 0 or n_layers == 0: SPECKV_OK, nothing is done. */
+speckv_status_t speckv_ext_read_pairs(const speckv_handle_t* handles, const uint64_t* first_pages,
+                                      void* const* d_rows /* [n_pairs][4]: K even, K odd, V even, V odd; NULL = not wanted */,
+                                      uint32_t n_pairs, uint64_t page_step, uint32_t n_layers,
+                                      uint64_t layer_stride_bytes, void* stream);
 /* Several page runs of ONE allocation in one launch: run r = pages [first_pages[r], first_pages[r] + n_pages_each) from
  * d_srcs[r] (n_pages_each * 4096 contiguous bytes).  A prompt's K and V of every layer (2 * num_layers regions of the shim
  * layout) are stored with one call.  The runs must not overlap; the stream must not be NULL. */
