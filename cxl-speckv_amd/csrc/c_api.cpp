@@ -180,6 +180,13 @@ speckv_status_t speckv_ext_read_pairs(const speckv_handle_t* handles, const uint
                                                      static_cast<hipStream_t>(stream)); });
 }
 
+speckv_status_t speckv_ext_copy_runs(const speckv_handle_t* src, const speckv_handle_t* dst, const uint64_t* n_pages, uint32_t n_pairs,
+                                     const uint64_t* run_firsts, uint32_t n_runs, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] { return g_engine->copy_runs(src, dst, n_pages, n_pairs, run_firsts, n_runs, static_cast<hipStream_t>(stream)); });
+}
+
 speckv_status_t speckv_ext_write_runs(speckv_handle_t handle, const uint64_t* first_pages, const void* const* d_srcs, uint32_t n_runs,
                                       uint64_t n_pages_each, void* stream)
 {

@@ -171,6 +171,8 @@ public:
                     uint32_t n_layers, uint64_t layer_stride, hipStream_t s);
     int read_pairs(const uint64_t* handles, const uint64_t* firsts, void* const* d_rows, uint32_t n_pairs, uint64_t step,
                    uint32_t n_layers, uint64_t layer_stride, hipStream_t s);
+    int copy_runs(const uint64_t* src, const uint64_t* dst, const uint64_t* n_pages, uint32_t n_pairs, const uint64_t* run_firsts,
+                  uint32_t n_runs, hipStream_t s);
     int read(uint64_t handle, uint64_t off, void* dst, size_t len, bool on_device);
     int fetch_range(uint64_t handle, uint64_t first, uint64_t n, void* d_dst, bool f32, hipStream_t s, int engine_choice);
     int fetch_list(uint64_t handle, const uint32_t* d_pages, uint32_t n, void* d_dst, bool f32, hipStream_t s);

@@ -391,6 +391,120 @@ int Engine::read_pairs(const uint64_t* handles, const uint64_t* firsts, void* co
     return SPECKV_OK;
 }
 
+// speckv_ext_copy_runs: the stored records of pages [run_firsts[r], run_firsts[r] + n_pages[i]), every run r, copied from src[i] to
+// the same pages of dst[i] by ONE launch on the caller's stream; nothing is decoded (a request forked from positions another one
+// holds).  The source side is read_pairs': record addresses from the device allocation table (any placement, a sealed source stays
+// sealed), behind what the caller queued on `s` and behind the asynchronous pool writes on other caller streams.  The destination
+// side is write_groups': sealed destinations are unpacked, cached destination pages invalidated, the host mirror follows the launch.
+int Engine::copy_runs(const uint64_t* src, const uint64_t* dst, const uint64_t* n_pages, uint32_t n_pairs, const uint64_t* run_firsts,
+                      uint32_t n_runs, hipStream_t s)
+{
+    if (null_) return no_data_path("speckv_ext_copy_runs");
+    if (!src || !dst || !n_pages || !run_firsts || !s) return SPECKV_ERR_INVAL;
+    uint64_t most = 0;
+    for (uint32_t i = 0; i < n_pairs; ++i) most = std::max(most, n_pages[i]);
+    if (n_pairs == 0 || n_runs == 0 || most == 0) return SPECKV_OK;
+    // what depends on the arguments alone: the runs must not overlap (they do for some pair exactly if they do for the longest)
+    // and must not wrap; an allocation that is written is named once, and not read
+    std::vector<uint64_t> order(run_firsts, run_firsts + n_runs);
+    std::sort(order.begin(), order.end());
+    if (order.back() > UINT64_MAX - most) return SPECKV_ERR_GENERAL;
+    for (uint32_t r = 1; r < n_runs; ++r)
+        if (order[r] - order[r - 1] < most) return SPECKV_ERR_INVAL;
+    {
+        std::vector<uint64_t> written, read;
+        for (uint32_t i = 0; i < n_pairs; ++i) {
+            if (src[i] == dst[i]) return SPECKV_ERR_INVAL;
+            if (n_pages[i]) { written.push_back(dst[i]); read.push_back(src[i]); }
+        }
+        std::sort(written.begin(), written.end());
+        std::sort(read.begin(), read.end());
+        if (std::adjacent_find(written.begin(), written.end()) != written.end()) return SPECKV_ERR_INVAL;
+        for (uint64_t h : written)
+            if (std::binary_search(read.begin(), read.end(), h)) return SPECKV_ERR_INVAL;
+    }
+    std::vector<Allocation*> from(n_pairs), to(n_pairs);
+    const auto check = [&]() -> int {
+        int scheme = -1;
+        for (uint32_t i = 0; i < n_pairs; ++i) {
+            Allocation *a = find(src[i]), *b = find(dst[i]);
+            if (!a || !b) return SPECKV_ERR_GENERAL;
+            if (scheme < 0) scheme = a->scheme;
+            if (a->scheme != scheme || b->scheme != scheme) return SPECKV_ERR_INVAL;
+            if (n_pages[i] && (order.back() + n_pages[i] > a->n_pages || order.back() + n_pages[i] > b->n_pages)) return SPECKV_ERR_GENERAL;
+            from[i] = a;
+            to[i] = b;
+        }
+        return SPECKV_OK;
+    };
+    RC_TRY(check());
+    for (uint32_t i = 0; i < n_pairs; ++i)
+        if (n_pages[i] && to[i]->packed) {                      // sealed destinations go back into slots first
+            DeviceScope scope(device_);
+            RC_TRY(unpack(to[i]));
+            RC_TRY(check());
+        }
+    const auto each_dst_page = [&](auto&& f) {
+        for (uint32_t i = 0; i < n_pairs; ++i)
+            for (uint32_t r = 0; r < n_runs; ++r)
+                for (uint64_t p = run_firsts[r]; p < run_firsts[r] + n_pages[i]; ++p) f(to[i], p);
+    };
+    bool cached = false;
+    each_dst_page([&](Allocation* a, uint64_t p) { cached = cached || (res_flags(a, p) & 3u) != 0; });
+    DeviceScope device_scope(device_);
+    if (cached || !flights_.empty() || ring_busy_ > 0) {
+        RC_TRY(quiesce());
+        RC_TRY(check());
+        each_dst_page([&](Allocation* a, uint64_t p) { drop_page(a, static_cast<uint32_t>(p)); });
+        RC_TRY(flush_mirror());
+        RC_TRY(wait_stream());
+    }
+    const size_t pair_bytes = static_cast<size_t>(n_pairs) * sizeof(CopyPair);     // (a multiple of 8: the run firsts follow)
+    const size_t bytes = pair_bytes + static_cast<size_t>(n_runs) * sizeof(uint64_t);
+    int slot = 0;
+    void *staged = nullptr, *d_slot = nullptr;
+    RC_TRY(descriptor_slot(bytes, &slot, &staged, &d_slot));  // may release the ABI lock: every pair is judged again
+    RC_TRY(check());
+    uint64_t n_recs = 0;
+    for (uint32_t i = 0; i < n_pairs; ++i) {
+        if (n_pages[i] && to[i]->packed) return SPECKV_ERR_GENERAL;          // sealed again by another caller meanwhile
+        static_cast<CopyPair*>(staged)[i] = CopyPair{to[i]->d_entries, to[i]->d_scale_tab, to[i]->region_pages, to[i]->scale_run,
+                                                     from[i]->row, 0u, n_pages[i], n_recs};
+        n_recs += n_pages[i] * n_runs;
+    }
+    memcpy(static_cast<uint8_t*>(staged) + pair_bytes, run_firsts, static_cast<size_t>(n_runs) * sizeof(uint64_t));
+    if (!is_capturing(s))
+        for (auto& w : write_evs_)
+            if (w.s != s) HIP_TRY(hipStreamWaitEvent(s, w.ev, 0));
+    HIP_TRY(hipMemcpyAsync(d_slot, staged, bytes, hipMemcpyHostToDevice, s));
+    CopyArgs ca{};
+    ca.pairs = static_cast<const CopyPair*>(d_slot);
+    ca.run_firsts = reinterpret_cast<const uint64_t*>(static_cast<const uint8_t*>(d_slot) + pair_bytes);
+    ca.tab = d_tab_;
+    ca.n_pairs = n_pairs;
+    ca.n_runs = n_runs;
+    ca.n_recs = n_recs;
+    ca.n_cus = cus();
+    ca.scheme = from[0]->scheme;
+    HIP_TRY(launch_copy_records(ca, s));
+    for (uint32_t i = 0; i < n_pairs; ++i) {                  // the kernel is queued: host mirror first, then the orderings
+        note_use(from[i], s);                                 // speckv_free of either side waits for this stream
+        note_use(to[i], s);
+    }
+    each_dst_page([&](Allocation* a, uint64_t p) {
+        if (a->scheme != SPECKV_COMP_FP16) a->flags[p] |= 4u; else a->flags[p] &= ~4u;
+    });
+    st_.copied_pages += n_recs;
+    st_.dma_submitted += n_recs;
+    st_.dma_completed += n_recs;                              // completion belongs to the caller's stream
+    if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel
+        (void)hipGetLastError();
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    RC_TRY(note_async_write_or_wait(s));
+    return SPECKV_OK;
+}
+
 int Engine::write_runs(uint64_t handle, const uint64_t* firsts, const void* const* d_srcs, uint32_t n_runs, uint64_t n_each, hipStream_t s)
 {
     if (null_) return no_data_path("speckv_ext_write_runs");

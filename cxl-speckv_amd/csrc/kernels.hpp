@@ -117,6 +117,34 @@ struct ReadPairArgs {
     int             quant_mode;
 };
 
+// One (source, destination) pair of a record-copy launch (CopyArgs::pairs; copy_records.hip): the stored records of pages
+// [run_firsts[r], run_firsts[r] + n_pages), every run r of the launch, go from the allocation in table row `src_row` to the same
+// pages of the allocation whose page table is `entries` -- scale_tab / region_pages / scale_run as CommitPair carries them.
+// first_rec = the sum of n_runs * n_pages over the pairs in front of this one (the host's exclusive prefix: the kernel finds the pair
+// of a flat record index by binary search and needs no atomics).
+struct CopyPair {
+    PageEntry* entries;               // destination
+    float*     scale_tab;
+    uint32_t   region_pages;
+    uint32_t   scale_run;
+    uint32_t   src_row;               // DevAlloc row of the source
+    uint32_t   reserved;
+    uint64_t   n_pages;
+    uint64_t   first_rec;
+};
+struct CopyArgs {
+    const CopyPair* pairs;            // device array, and behind it in the same staged slot ...
+    const uint64_t* run_firsts;       // ... the first page of every run (device array)
+    const DevAlloc* tab;              // the device allocation table
+    uint32_t        n_pairs;
+    uint32_t        n_runs;
+    uint64_t        n_recs;           // n_runs * the sum of n_pages
+    uint32_t        n_cus;            // compute units of the device: the grid is a few workgroups per CU, grid-stride over the records
+    int             scheme;
+};
+// ONE launch; a source page never written leaves the destination page never written (rec_bytes 0, its slot zero bytes)
+hipError_t launch_copy_records(const CopyArgs& a, hipStream_t s);
+
 // Source / destination description of one codec launch.  Exactly one of
 // {entries, recs, tab+alloc_list} is used as the record source.
 struct CodecArgs {

@@ -22,6 +22,8 @@ paged-attention layer would talk to for a BATCH of requests:
   commit / truncate            the commit in one launch (``speckv_ext_write_pairs``), and its undo: roll requests back to shorter
                                lengths, the new odd last positions read back out of their pairs by one launch
                                (``speckv_ext_read_pairs``)
+  fork                         new requests started from positions other requests hold (parallel sampling, beam search, a shared
+                               prefix): the stored records copied by one launch (``speckv_ext_copy_runs``), nothing decoded
   tree_masks / append_path     the same step with drafts that form a TREE (``attend_spec(parents=...)``): a node sees its
                                ancestors only, the held rows are folded in by ``speckv_ext_attend_fold_masked`` with one mask
                                word per (request, node); then the accepted root-to-node path is committed
@@ -847,6 +849,96 @@ class SpeckvKVConnector:
         self._epoch += 1
         self._arg_key = self._fold_key = None                  # the plan names ranges that no longer hold: the next attend plans again
         self._plan_stream = None
+
+    # ------------------------------------------------------------------ fork
+    @staticmethod
+    def fork_plan(src_lengths: Sequence[int], lengths: Sequence[int]):
+        """What starting a request with the first lengths[b] positions of a request of src_lengths[b] positions comes to.  Returns
+        (n_pages, tails): n_pages[b] = lengths[b] // 2 stored pairs to copy per (layer, kind) region; tails[b] = None for an even
+        length, "held" for an odd length equal to the source's (the source holds that row outside the pool), "read" for an odd
+        shorter one (the row is the even half of stored page (length - 1) // 2 of the source).  ValueError for
+        lengths[b] > src_lengths[b] or lengths[b] < 0.  Pure python, no device."""
+        n_pages, tails = [], []
+        for b, (ln, new) in enumerate(zip(src_lengths, lengths)):
+            ln, new = int(ln), int(new)
+            if not 0 <= new <= ln:
+                raise ValueError(f"request #{b}: cannot fork {new} positions out of {ln}")
+            n_pages.append(new // 2)
+            tails.append(None if not new & 1 else "held" if new == ln else "read")
+        return n_pages, tails
+
+    def fork(self, src_ids: Sequence[int], new_ids: Sequence[int], lengths: Optional[Sequence[int]] = None, stream=None):
+        """Create the requests new_ids[b], each holding the first lengths[b] (default: all) positions of request src_ids[b]; a source
+        may appear several times (parallel sampling, beams).  Afterwards lengths, tails, _epoch and the plan keys are those of
+        requests written independently with the same values, and source and fork go their own ways: the counterpart of truncate().
+
+        ONE speckv_ext_copy_runs call for the batch copies the stored records of the lengths[b] // 2 pairs of every (layer, kind)
+        region -- records, not values: nothing is decoded, scaled or rounded again, every placement on either side (no call when no
+        pair is stored).  An odd length needs its last row as the new request's tail: equal to the source's length, the row is a CLONE
+        of the source's tail (never a view: the source stays free to change); shorter, it is the even half of stored page
+        (length - 1) // 2, and at most ONE speckv_ext_read_pairs call reads those rows from the SOURCES into one [n][layers][heads][dim]
+        tensor pair, as truncate() installs tails.  Tails are pre-scaled K like every tail (set_k_channel_scale): nothing is scaled
+        twice.
+
+        KeyError for an existing (or repeated) new id and for an unknown source, ValueError from fork_plan: before any allocation or
+        change of state.  If a launch fails the allocations made here are freed again and the sources are untouched.  Returns the
+        tensors the launches write, for the caller to hold until the stream has passed them."""
+        import contextlib
+        import numpy as np
+        import torch
+        src_ids, new_ids = list(src_ids), list(new_ids)
+        if len(src_ids) != len(new_ids):
+            raise ValueError("new_ids: one new request per source")
+        for i, rid in enumerate(new_ids):
+            if rid in self.requests or rid in new_ids[:i]:
+                raise KeyError(f"request {rid} already exists")
+        srcs = [self.requests[rid] for rid in src_ids]
+        lengths = [r.length for r in srcs] if lengths is None else [int(n) for n in lengths]
+        if len(lengths) != len(srcs):
+            raise ValueError("lengths: one length per request")
+        n_pages, tails = self.fork_plan([r.length for r in srcs], lengths)
+        if not new_ids:
+            return []
+        reads = [b for b, t in enumerate(tails) if t == "read"]
+        made, keep, tk, tv = [], [], None, None
+        try:
+            for rid in new_ids:
+                self.add_request(rid)
+                made.append(rid)
+            news = [self.requests[rid] for rid in new_ids]
+            if any(n_pages) or reads:
+                with self._On(self, stream) as st:
+                    if any(n_pages):
+                        firsts = np.arange(2 * self.L, dtype=np.uint64) * np.uint64(self.region_pages)       # _page(layer, kind, 0)
+                        self.lib.copy_runs(np.asarray([r.handle for r in srcs], dtype=np.uint64), np.asarray([r.handle for r in news], dtype=np.uint64),
+                                           np.asarray(n_pages, dtype=np.uint64), firsts, st.cuda_stream)
+                    if reads:
+                        n = len(reads)
+                        row_bytes = self.L * self.H * self.D * 2
+                        with torch.cuda.stream(st):
+                            tk = torch.empty((n, self.L, self.H, self.D), dtype=torch.float16, device="cuda")
+                            tv = torch.empty_like(tk)
+                        rows = np.zeros((n, 4), dtype=np.uint64)                                     # odd rows: 0 = not wanted
+                        at = np.arange(n, dtype=np.uint64) * np.uint64(row_bytes)
+                        rows[:, 0], rows[:, 2] = at + np.uint64(tk.data_ptr()), at + np.uint64(tv.data_ptr())
+                        handles = np.asarray([srcs[b].handle for b in reads], dtype=np.uint64)
+                        pages = np.asarray([(lengths[b] - 1) // 2 for b in reads], dtype=np.uint64)
+                        self.lib.read_pairs(handles, pages, rows, self.region_pages, self.L, self.H * self.D * 2, st.cuda_stream)
+                        keep += [tk, tv]
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():      # behind what produced the source's tail
+                for b, t in enumerate(tails):
+                    if t == "held":
+                        news[b].set_tail(srcs[b].tail_k.clone(), srcs[b].tail_v.clone())
+        except BaseException:
+            for rid in made:
+                self.free_request(rid)
+            raise
+        for i, b in enumerate(reads):
+            news[b].set_tail(tk, tv, i)
+        for r, n in zip(news, lengths):
+            r.length = n
+        self._epoch += 1
+        return keep
 
     def append_tokens(self, req_ids: Sequence[int], k_new, v_new, n_accept: Sequence[int], stream=None):
         """Commit the first n_accept[b] (0..S) of the S new positions k_new[b], v_new[b] ([batch][S][layers][heads][dim] fp16) of every

@@ -41,7 +41,8 @@ class Stats(ctypes.Structure):
         [(n, c_uint32) for n in ("prefetch_depth", "compression_scheme", "quant_mode", "n_pool_devices")] + \
         [("pool_migrated_pages", c_uint64), ("prefetch_dropped", c_uint64), ("copy_engine_runs", c_uint64),
          ("copy_engine_bytes", c_uint64), ("pool_bytes_in_use", c_uint64), ("written_pages", c_uint64),
-         ("sealed_allocations", c_uint64), ("compactions", c_uint64), ("flat_decoder_fetches", c_uint64)]
+         ("sealed_allocations", c_uint64), ("compactions", c_uint64), ("flat_decoder_fetches", c_uint64),
+         ("copied_pages", c_uint64)]
 
 
 _u32p = ctypes.POINTER(c_uint32)
@@ -61,6 +62,7 @@ _EXT_SIGNATURES = {
     "speckv_ext_write_runs": [c_uint64, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p],
     "speckv_ext_write_pairs": [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_uint64, c_void_p],
     "speckv_ext_read_pairs": [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_uint64, c_void_p],
+    "speckv_ext_copy_runs": [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
     "speckv_ext_bind_request": [c_uint32, c_uint64, c_uint32],
@@ -292,6 +294,16 @@ class SpeckvLib:
             rows = [p for r in rows for p in r]
         hs, fs, rs = as_arr(handles, c_uint64, n), as_arr(first_pages, c_uint64, n), as_arr(rows, c_uint64, 4 * n)
         self._ext("speckv_ext_read_pairs", hs, fs, rs, n, page_step, n_layers, layer_stride, c_void_p(stream))
+
+    def copy_runs(self, src, dst, n_pages, run_firsts, stream):
+        """The stored records of pages [run_firsts[r], run_firsts[r] + n_pages[i]), every run r, copied from allocation src[i] to the same
+        pages of allocation dst[i] in ONE launch, nothing decoded (a request forked from another one's positions).  src, dst, n_pages:
+        one entry per pair; numpy uint64 arrays, ctypes arrays or sequences.  One source may feed several destinations; a destination
+        appears once and is no source of the same call."""
+        n, m = len(src), len(run_firsts)
+        as_arr = lambda v, t, k: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * k)(*v))
+        ss, ds, ns, fs = as_arr(src, c_uint64, n), as_arr(dst, c_uint64, n), as_arr(n_pages, c_uint64, n), as_arr(run_firsts, c_uint64, m)
+        self._ext("speckv_ext_copy_runs", ss, ds, ns, n, fs, m, c_void_p(stream))
 
     def read(self, handle, offset, dst_ptr, nbytes, on_device):
         self._ext("speckv_ext_read", handle, offset, c_void_p(dst_ptr), nbytes, int(on_device))

@@ -144,6 +144,31 @@ speckv_status_t speckv_ext_read_pairs(const speckv_handle_t* handles, const uint
                                       void* const* d_rows /* [n_pairs][4]: K even, K odd, V even, V odd; NULL = not wanted */,
                                       uint32_t n_pairs, uint64_t page_step, uint32_t n_layers,
                                       uint64_t layer_stride_bytes, void* stream);
+/* Fork: the STORED RECORDS of page runs copied from one allocation to another, nothing decoded.  Pair i copies pages
+ * [run_firsts[r], run_firsts[r] + n_pages[i]) for every run r < n_runs from allocation src[i] to the same page numbers of
+ * allocation dst[i] (in the shim layout the runs are the 2 * num_layers (layer, kind) regions and n_pages[i] = positions / 2: a
+ * request started from positions another request holds).  ONE launch on `stream` for the whole call.  Afterwards every reader --
+ * speckv_ext_fetch_range, speckv_ext_read_pairs, every speckv_ext_attend_* form -- gives the same bits for a copied page of dst[i]
+ * as for the page of src[i], and speckv_ext_translate reports the same rec_bytes and the same scale (MXFP4 has no block scale: its
+ * aux_offset belongs to the record's slot and stays the destination's own).  A source page never written leaves the destination
+ * page never written: rec_bytes 0, decoding to zeros.  All schemes.  Source and destination may each be linear, striped over pools,
+ * migrated page by page or sealed; a sealed source stays sealed, a sealed destination is unpacked first, as by any write.
+ * Aliasing, for the pairs with n_pages[i] > 0: one source may feed several destinations; an allocation is the destination of ONE
+ * pair at most (every pair writes the same page numbers, so two pairs into one allocation would share a destination page), and an
+ * allocation that is a destination is not a source in the same call (its pages would be read while they are written);
+ * src[i] == dst[i] is refused for every pair.
+ * Asynchronous on `stream`.  The sources are read behind what the caller queued there before (a commit on the same stream) and
+ * behind the asynchronous pool writes handed to other streams before the call, unless `stream` is capturing; the destinations are
+ * written like speckv_ext_write_pairs writes (cached destination pages are invalidated first).
+ *   SPECKV_ERR_INVAL    NULL stream or arrays, allocations of different schemes, src[i] == dst[i], a destination named by two pairs
+ *                       or also named as a source, runs that overlap -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle, pages that leave either allocation
+ * n_pairs == 0, n_runs == 0 or every n_pages[i] == 0: SPECKV_OK, nothing is done.  Counted in
+ * speckv_ext_stats_t.copied_pages (and dma_submitted / dma_completed). */
+speckv_status_t speckv_ext_copy_runs(const speckv_handle_t* src, const speckv_handle_t* dst,
+                                     const uint64_t* n_pages /* [n_pairs] pages per run of pair i */, uint32_t n_pairs,
+                                     const uint64_t* run_firsts /* [n_runs] first page of each run, the same in src and dst */,
+                                     uint32_t n_runs, void* stream);
 /* Several page runs of ONE allocation in one launch: run r = pages [first_pages[r], first_pages[r] + n_pages_each) from
  * d_srcs[r] (n_pages_each * 4096 contiguous bytes).  A prompt's K and V of every layer (2 * num_layers regions of the shim
  * layout) are stored with one call.  The runs must not overlap; the stream must not be NULL. */
@@ -581,6 +606,7 @@ typedef struct {
     uint64_t sealed_allocations;    /* live allocations packed by speckv_ext_compact */
     uint64_t compactions;           /* speckv_ext_compact calls that packed an allocation */
     uint64_t flat_decoder_fetches;  /* speckv_ext_fetch_range launches that took the flat-run decoder by themselves (sealed size or length samples) */
+    uint64_t copied_pages;          /* records speckv_ext_copy_runs copied from allocation to allocation (pages never written included) */
 } speckv_ext_stats_t;
 /* The struct only ever grows at its end.  speckv_ext_stats() writes sizeof(speckv_ext_stats_t) of THIS header: a caller
  * compiled against an older header must use the sized form, which writes min(out_size, the library's size) bytes (fields
@@ -588,7 +614,9 @@ typedef struct {
  * zero-filled (a caller built against a NEWER header reads zeros there); *written (optional) = bytes of real data; out_size < 8
  * is SPECKV_ERR_INVAL.
  * SPECKV_EXT_ABI_VERSION is bumped whenever a struct of this header grows or an entry point changes meaning;
- * speckv_ext_abi_version() returns the library's value (the Python binding refuses a mismatch). */
+ * speckv_ext_abi_version() returns the library's value (the Python binding refuses a mismatch).  The one exception is this
+ * struct's growth at its end under the sized form above: copied_pages arrived with speckv_ext_copy_runs under version 6 (a
+ * library without it answers a sized call with zeros there, a caller without it never sees it). */
 #define SPECKV_EXT_ABI_VERSION 6u
 uint32_t        speckv_ext_abi_version(void);
 speckv_status_t speckv_ext_stats(speckv_ext_stats_t* out);
