@@ -1,0 +1,347 @@
+// cxl-speckv_amd/csrc/attend_chunk.hip -- k_attend_chunk: causal attention of a chunk of new positions per sequence over the
+// positions the sequence has stored in the pool and the rows it holds outside it, in ONE launch (Engine::attend_chunk,
+// speckv_ext_attend_chunk: chunked prefill, the suffix behind a fork, a prompt continued after a truncate).
+//
+// A translation unit of its own: the headline kernel of kernels.hip is pinned by the hash of its instructions and the three
+// attention units stay as they are.  The three small decoders this kernel needs are restated here for ONE head's 8 elements of both
+// positions of a page; they give the fp16 values speckv_ext_fetch_range gives (the fp32 product rounded once to fp16, pack_half2).
+//
+// Semantics.  Sequence i holds pos_end (even) stored positions, base in {0, 1} held odd last positions (the tail) and n_q <= C new
+// positions.  Query position j < n_q sees the stored positions [0, pos_end) and the held positions 0 .. base + j: the tail, the new
+// positions in front of it, itself.  out = softmax(q.K^T sm_scale).V per kv head, fp32, normalised; lse (natural log) on request.
+// THE QUERY STAYS fp16 in all three formats -- the FP8 and MXFP4 decode kernels quantise q, this kernel does not.  Both products run
+// on v_mfma_f32_16x16x32_f16; the weights are rounded to fp16; accumulation, running max and running sum are fp32.
+//
+// Execution model.  One workgroup of 4 waves owns (sequence, kv head, query block); a wave owns 16 query rows, a block is
+// 64 / rows_per_pos positions.  The workgroup walks tiles of 32 positions with an online softmax: first the pool tiles, then the
+// held tiles, up to the last held tile any live row of the block can see.  Staging: thread t takes page (t >> 4) of the tile's 16
+// pages and elements [8 (t & 15), + 8) of head h of BOTH its positions -- 16 lanes read a head's contiguous slice of a record -- and
+// the same piece of the V page; record addresses, lengths and scales come from PageEntry through the device allocation table, so
+// linear, striped, migrated and sealed allocations are one body.  A held tile is staged by the same threads from the tail row
+// (held position t < base) and from k_new / v_new where they lie (new row t - base), through strides; no gathered copy is made.
+// After staging a tile is a tile.
+//   LDS, two buffers of 17.5 KiB: K as [32 positions][128 + 8 pad] fp16 (a wave's 16-byte operand reads of 16 rows fall into 16
+//   different 4-bank groups), V TRANSPOSED as [128 dims][32 + 4 pad] fp16 (the p.V operand wants 4 consecutive positions of one
+//   dim: two 8-byte reads; rows 18 words apart spread 16 dims over the banks) -- a page's two positions go in as one 32-bit word.
+//   The next tile's global loads are issued before the products of the current one and decoded into the other buffer behind them:
+//   one workgroup barrier per tile.
+//   S^T = K.Q^T (A = K rows from LDS, B = the wave's query rows, resident in 16 VGPRs), so a lane holds 8 scores of ONE query row
+//   (row = lane & 15; positions 4 (lane >> 4) + r and 16 + 4 (lane >> 4) + r) -- exactly the 8 contraction slots of its P operand
+//   in O^T = V^T.P^T once V^T is read in the same slot order.  Row max and sum go over the 4 lanes of a row by row/half swaps.
+// No split over positions: no merge kernel, no scratch, no atomics; a row's result does not depend on which other sequences share
+// the launch.  Masks: stored positions >= pos_end and held positions beyond the sequence's count are staged as ZEROS (V) and scored
+// -inf (truncate leaves stale records there, and 0 x inf would poison the product); held position t is -inf for rows with
+// t > base + j; rows of positions >= n_q are neither loaded nor written.  Every live row sees itself, so its sum is never 0.
+// Ragged chunks: the flat workgroup index is (block, kv head) with the head fast; the block maps to its sequence by binary search
+// on the exclusive block prefixes the host computed.  Everything written goes out through vector stores.
+#include "kernels.hpp"
+#include "codec_device.hpp"          // pack_half2, half_bits_to_float
+#include "attend_device.hpp"
+
+namespace speckv {
+namespace {
+
+constexpr uint32_t kChunkThreads = 256;
+constexpr uint32_t kKRow = 128 + 8;                       // fp16 elements of a K row in LDS
+constexpr uint32_t kVRow = 32 + 4;                        // fp16 elements of a V^T row in LDS
+constexpr uint32_t kKTile = 32 * kKRow, kVTile = 128 * kVRow, kBufElems = kKTile + kVTile;
+constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
+
+typedef u32x4 __attribute__((address_space(1))) gk_u32x4;
+typedef u32x2 __attribute__((address_space(1))) gk_u32x2;
+template <typename T> __device__ __forceinline__ T ck_ld(const void* p) { return *SPECKV_GP(T, p); }
+template <typename T> __device__ __forceinline__ void ck_st(void* p, T v)
+{
+    typedef T __attribute__((address_space(1))) G;
+    *(G*)(reinterpret_cast<uintptr_t>(p)) = v;
+}
+__device__ __forceinline__ uint64_t ck_uniform(uint64_t v)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v)), hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
+    return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
+// What a thread has in flight for one kind (K or V) of the next tile: the undecoded bytes of its 8 elements of both positions.
+//   pool, FP8  : a.xy / b.xy = the 8 bytes of the even / odd position, aux = the block scale
+//   pool, INT4 : a.x / b.x = the 4 nibble bytes, a.y / b.y = the group scale (fp16 bits)
+//   pool, MXFP4: a.xy = the 8 bytes (low nibble even, high nibble odd position), a.z = the E8M0 code
+//   held       : a / b = the 8 fp16 elements of the two rows
+// len = the record length (0: zeros).
+struct Raw { u32x4 a, b; uint32_t aux, len; };
+
+template <int SCHEME>
+__device__ __forceinline__ Raw load_pool(const PageEntry* e, uint32_t p0, bool live)
+{
+    Raw r{{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, 0u, 0u};
+    if (!live) return r;
+    const u32x4 w = ck_ld<u32x4>(e);
+    const uint8_t* rec = reinterpret_cast<const uint8_t*>((static_cast<uint64_t>(w.y) << 32) | w.x);
+    r.len = w.z;
+    r.aux = w.w;
+    if (SCHEME == kFp8E4m3) {
+        if (r.len > kBlockElems) r.len = kBlockElems;
+        if (p0 < r.len) { const u32x2 v = ck_ld<u32x2>(rec + p0); r.a.x = v.x; r.a.y = v.y; }
+        if (p0 + 1024u < r.len) { const u32x2 v = ck_ld<u32x2>(rec + p0 + 1024u); r.b.x = v.x; r.b.y = v.y; }
+    } else if (SCHEME == kInt4G32) {
+        if (r.len >= kInt4RecBytes) {
+            r.a.x = ck_ld<uint32_t>(rec + 128u + (p0 >> 1));
+            r.b.x = ck_ld<uint32_t>(rec + 128u + ((p0 + 1024u) >> 1));
+            r.a.y = ck_ld<uint16_t>(rec + 2u * (p0 >> 5));
+            r.b.y = ck_ld<uint16_t>(rec + 2u * ((p0 + 1024u) >> 5));
+        } else {
+            r.len = 0u;
+        }
+    } else {
+        if (r.len >= kMx4RecBytes) {
+            const u32x2 v = ck_ld<u32x2>(rec + p0);
+            r.a.x = v.x; r.a.y = v.y;
+            r.a.z = ck_ld<uint8_t>(rec + r.aux + (p0 >> 4));         // PageEntry::scale of an MXFP4 page: the distance to its code row
+        } else {
+            r.len = 0u;
+        }
+    }
+    return r;
+}
+
+// the 8 + 8 fp16 values of a Raw: ev / od = the even / odd position, two elements per word
+template <int SCHEME>
+__device__ __forceinline__ void decode_pool(const Raw& r, uint32_t p0, uint32_t (&ev)[4], uint32_t (&od)[4])
+{
+    float y0[8], y1[8];
+    if (SCHEME == kFp8E4m3) {
+        const float s = __uint_as_float(r.aux);
+#define CK_FP8(K, W, SEL) { y0[K] = __builtin_amdgcn_cvt_f32_fp8(static_cast<int>(r.a.W), SEL); y1[K] = __builtin_amdgcn_cvt_f32_fp8(static_cast<int>(r.b.W), SEL); }
+        CK_FP8(0, x, 0) CK_FP8(1, x, 1) CK_FP8(2, x, 2) CK_FP8(3, x, 3) CK_FP8(4, y, 0) CK_FP8(5, y, 1) CK_FP8(6, y, 2) CK_FP8(7, y, 3)
+#undef CK_FP8
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            y0[k] = (p0 + k < r.len) ? y0[k] * s : 0.0f;
+            y1[k] = (p0 + 1024u + k < r.len) ? y1[k] * s : 0.0f;
+        }
+    } else if (SCHEME == kInt4G32) {
+        const float s0 = half_bits_to_float(r.a.y), s1 = half_bits_to_float(r.b.y);
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            const int q0 = static_cast<int>(r.a.x << (28u - 4u * k)) >> 28, q1 = static_cast<int>(r.b.x << (28u - 4u * k)) >> 28;
+            y0[k] = r.len ? static_cast<float>(q0) * s0 : 0.0f;
+            y1[k] = r.len ? static_cast<float>(q1) * s1 : 0.0f;
+        }
+    } else {
+        typedef float f32x2c __attribute__((ext_vector_type(2)));
+        const uint32_t code = r.len ? r.a.z : 127u;
+        const float s = __uint_as_float(code == 0u ? 0x00400000u : code == 255u ? 0x7FC00000u : code << 23);
+#define CK_MX(K, W, SEL) { const f32x2c f = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(r.a.W, 1.0f, SEL); y0[K] = f.x * s; y1[K] = f.y * s; }
+        CK_MX(0, x, 0) CK_MX(1, x, 1) CK_MX(2, x, 2) CK_MX(3, x, 3) CK_MX(4, y, 0) CK_MX(5, y, 1) CK_MX(6, y, 2) CK_MX(7, y, 3)
+#undef CK_MX
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+        ev[k] = pack_half2(y0[2 * k], y0[2 * k + 1]);
+        od[k] = pack_half2(y1[2 * k], y1[2 * k + 1]);
+    }
+}
+
+// the same piece of two held rows: addresses of 0 (beyond the sequence's held positions) give zeros
+__device__ __forceinline__ Raw load_held(const _Float16* r0, const _Float16* r1)
+{
+    Raw r{{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, 0u, 1u};
+    if (r0) r.a = ck_ld<u32x4>(r0);
+    if (r1) r.b = ck_ld<u32x4>(r1);
+    return r;
+}
+
+template <int SCHEME>
+__global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
+{
+    __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufElems];
+
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t h = blockIdx.x % a.heads, fb = blockIdx.x / a.heads;
+    // the last sequence whose block prefix is <= fb (sequences without blocks share their successor's prefix and are passed over)
+    uint32_t lo = 0, hi = a.n_seq;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(a.seqs[mid].first_block)) <= fb) lo = mid; else hi = mid;
+    }
+    const ChunkSeq* sq = a.seqs + lo;
+    const uint32_t seq = lo;
+    const uint32_t pos_end = __builtin_amdgcn_readfirstlane(sq->pos_end), n_q = __builtin_amdgcn_readfirstlane(sq->n_q);
+    const uint32_t base = __builtin_amdgcn_readfirstlane(sq->base);
+    const uint32_t blk = fb - static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(sq->first_block));
+    const uint32_t rpp = a.rows_per_pos, per_blk = 64u / rpp;
+    const uint32_t j_first = blk * per_blk;
+    if (j_first >= n_q) return;                               // (never: the host counts the blocks of live positions only)
+    const uint32_t j_last = (j_first + per_blk < n_q ? j_first + per_blk : n_q) - 1u;     // the block's last live position
+    const uint32_t n_pool = (pos_end + 31u) >> 5, n_held = ((base + j_last) >> 5) + 1u, n_tiles = n_pool + n_held;
+    const uint32_t n_pages = pos_end >> 1, held_n = base + n_q;
+
+    const PageEntry* entries = reinterpret_cast<const PageEntry*>(ck_uniform(reinterpret_cast<uint64_t>(a.tab[sq->table_row].entries)));
+    const uint64_t k_first = ck_uniform(sq->k_first), v_first = ck_uniform(sq->v_first);
+    const int32_t tail_idx = __builtin_amdgcn_readfirstlane(sq->tail_idx);
+    const uint64_t head_off = static_cast<uint64_t>(h) * 128u;
+    const _Float16* k_new = a.k_new + static_cast<uint64_t>(seq) * a.seq_stride + head_off;
+    const _Float16* v_new = a.v_new + static_cast<uint64_t>(seq) * a.seq_stride + head_off;
+    const _Float16* k_tail = base ? a.k_tail + static_cast<uint64_t>(tail_idx) * a.tail_stride + head_off : nullptr;
+    const _Float16* v_tail = base ? a.v_tail + static_cast<uint64_t>(tail_idx) * a.tail_stride + head_off : nullptr;
+
+    // staging role: page pp of the tile, elements [8 c, 8 c + 8) of head h of both its positions
+    const uint32_t pp = tid >> 4, c = tid & 15u;
+    const uint32_t p0 = h * 128u + 8u * c;                    // element of the even position inside the page
+
+    // compute role: query row qr of the block, contraction group g
+    const uint32_t col = lane & 15u, g = lane >> 4;
+    const uint32_t qr = 16u * wave + col, j = j_first + qr / rpp, sub = qr % rpp;
+    const bool row_live = j < n_q;
+    const uint64_t row_idx = ((static_cast<uint64_t>(seq) * a.C + j) * a.heads + h) * rpp + sub;
+    f16x8 qv[4];
+#pragma unroll
+    for (uint32_t s = 0; s < 4u; ++s) {
+        u32x4 w = {0u, 0u, 0u, 0u};
+        if (row_live) w = ck_ld<u32x4>(a.q + row_idx * 128u + 32u * s + 8u * g);
+        qv[s] = __builtin_bit_cast(f16x8, w);
+    }
+    // the last held position the wave's rows see: tiles behind it are skipped by the wave (it still stages and meets the barriers)
+    const uint32_t wave_j_last = j_first + (16u * wave + 15u) / rpp;
+    const uint32_t wave_t_last = base + (wave_j_last < j_last ? wave_j_last : j_last);
+    const bool wave_live = j_first + (16u * wave) / rpp < n_q;
+
+    Raw rk, rv;
+    const auto load_tile = [&](uint32_t tile) {
+        if (tile < n_pool) {
+            const uint32_t page = 16u * tile + pp;
+            const bool live = page < n_pages;
+            rk = load_pool<SCHEME>(entries + k_first + page, p0, live);
+            rv = load_pool<SCHEME>(entries + v_first + page, p0, live);
+        } else {
+            const uint32_t t0 = 32u * (tile - n_pool) + 2u * pp;
+            const _Float16 *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr;
+            if (t0 < held_n) {
+                if (t0 < base) { k0 = k_tail; v0 = v_tail; }
+                else { const uint64_t o = static_cast<uint64_t>(t0 - base) * a.pos_stride; k0 = k_new + o; v0 = v_new + o; }
+            }
+            if (t0 + 1u < held_n) { const uint64_t o = static_cast<uint64_t>(t0 + 1u - base) * a.pos_stride; k1 = k_new + o; v1 = v_new + o; }
+            rk = load_held(k0 ? k0 + 8u * c : nullptr, k1 ? k1 + 8u * c : nullptr);
+            rv = load_held(v0 ? v0 + 8u * c : nullptr, v1 ? v1 + 8u * c : nullptr);
+        }
+    };
+    const auto store_tile = [&](uint32_t tile, _Float16* buf) {
+        uint32_t ke[4], ko[4], ve[4], vo[4];
+        if (tile < n_pool) {
+            decode_pool<SCHEME>(rk, p0, ke, ko);
+            decode_pool<SCHEME>(rv, p0, ve, vo);
+        } else {
+            ke[0] = rk.a.x; ke[1] = rk.a.y; ke[2] = rk.a.z; ke[3] = rk.a.w;
+            ko[0] = rk.b.x; ko[1] = rk.b.y; ko[2] = rk.b.z; ko[3] = rk.b.w;
+            ve[0] = rv.a.x; ve[1] = rv.a.y; ve[2] = rv.a.z; ve[3] = rv.a.w;
+            vo[0] = rv.b.x; vo[1] = rv.b.y; vo[2] = rv.b.z; vo[3] = rv.b.w;
+        }
+        *reinterpret_cast<u32x4*>(buf + (2u * pp) * kKRow + 8u * c) = u32x4{ke[0], ke[1], ke[2], ke[3]};
+        *reinterpret_cast<u32x4*>(buf + (2u * pp + 1u) * kKRow + 8u * c) = u32x4{ko[0], ko[1], ko[2], ko[3]};
+        uint32_t* vt = reinterpret_cast<uint32_t*>(buf + kKTile);            // word (dim, page) = the dim's values at the page's two positions
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            const uint32_t e = (ve[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu, o = (vo[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+            vt[(8u * c + k) * (kVRow / 2u) + pp] = e | (o << 16);
+        }
+    };
+
+    f32x4 acc[8];
+#pragma unroll
+    for (uint32_t t = 0; t < 8u; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    float m_run = -__builtin_inff(), l_run = 0.0f;            // log2 domain
+    const float scale2 = a.sm_scale * kLog2e;
+
+    load_tile(0);
+    store_tile(0, lds);
+    __syncthreads();
+    for (uint32_t tile = 0; tile < n_tiles; ++tile) {
+        _Float16* buf = lds + (tile & 1u) * kBufElems;
+        const bool more = tile + 1u < n_tiles;
+        if (more) load_tile(tile + 1u);
+        const bool held = tile >= n_pool;
+        const uint32_t t_base = held ? 32u * (tile - n_pool) : 32u * tile;
+        if (wave_live && (!held || t_base <= wave_t_last)) {
+            // scores: rows = positions 16 hf + 4 g + r of the tile, column = the lane's query row
+            f32x4 sc[2];
+#pragma unroll
+            for (uint32_t hf = 0; hf < 2u; ++hf) {
+                f32x4 s4 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (uint32_t s = 0; s < 4u; ++s) {
+                    const u32x4 kw = *reinterpret_cast<const u32x4*>(buf + (16u * hf + col) * kKRow + 32u * s + 8u * g);
+                    s4 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kw), qv[s], s4, 0, 0, 0);
+                }
+                sc[hf] = s4;
+            }
+            const uint32_t limit = held ? base + j + 1u : pos_end;           // positions of this part the row sees: [0, limit)
+            float sv[8], mx = -__builtin_inff();
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; ++i) {
+                const uint32_t t = t_base + 16u * (i >> 2) + 4u * g + (i & 3u);
+                sv[i] = t < limit ? sc[i >> 2][i & 3u] * scale2 : -__builtin_inff();
+                mx = fmaxf(mx, sv[i]);
+            }
+            mx = max_over_kb(mx);
+            const float m_new = fmaxf(m_run, mx);
+            const float m_use = m_new == -__builtin_inff() ? 0.0f : m_new;  // (a dead row that sees nothing yet)
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
+            float p[8], sum = 0.0f;
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; ++i) p[i] = __builtin_amdgcn_exp2f(sv[i] - m_use);
+            uint32_t pw[4];
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; ++i) {
+                pw[i] = pack_half2(p[2 * i], p[2 * i + 1]);
+                sum += half_bits_to_float(pw[i] & 0xFFFFu) + half_bits_to_float(pw[i] >> 16);
+            }
+            sum = sum_over_kb(sum);
+            l_run = l_run * alpha + sum;
+            m_run = m_new;
+            const f16x8 P = __builtin_bit_cast(f16x8, u32x4{pw[0], pw[1], pw[2], pw[3]});
+            const _Float16* vt = buf + kKTile;
+#pragma unroll
+            for (uint32_t t = 0; t < 8u; ++t) {
+                const _Float16* vr = vt + (16u * t + col) * kVRow + 4u * g;
+                const u32x2 v0 = *reinterpret_cast<const u32x2*>(vr), v1 = *reinterpret_cast<const u32x2*>(vr + 16);
+                const f16x8 V = __builtin_bit_cast(f16x8, u32x4{v0.x, v0.y, v1.x, v1.y});
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(V, P, acc[t] * alpha, 0, 0, 0);
+            }
+        }
+        if (more) store_tile(tile + 1u, lds + ((tile + 1u) & 1u) * kBufElems);
+        __syncthreads();
+    }
+
+    if (row_live) {
+        const float inv = 1.0f / l_run;
+        float* o = a.out + row_idx * 128u + 4u * g;
+#pragma unroll
+        for (uint32_t t = 0; t < 8u; ++t) ck_st<f32x4>(o + 16u * t, acc[t] * inv);
+        if (a.lse && g == 0u) ck_st<float>(a.lse + row_idx, (m_run + __builtin_amdgcn_logf(l_run)) * kLn2);
+    }
+}
+
+template <int SCHEME>
+hipError_t launch_chunk(const ChunkArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_attend_chunk<SCHEME>, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s)
+{
+    if (a.n_blocks == 0) return hipSuccess;
+    if (!a.seqs || !a.tab || !a.q || !a.k_new || !a.v_new || !a.out || a.n_seq == 0 || a.heads == 0 || a.rows_per_pos == 0 ||
+        a.rows_per_pos > 16u || (a.rows_per_pos & (a.rows_per_pos - 1u)) || static_cast<uint64_t>(a.n_blocks) * a.heads > 0x7FFFFFFFull)
+        return hipErrorInvalidValue;
+    switch (a.scheme) {
+    case kFp8E4m3: return launch_chunk<kFp8E4m3>(a, s);
+    case kInt4G32: return launch_chunk<kInt4G32>(a, s);
+    case kMxFp4: return launch_chunk<kMxFp4>(a, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+} // namespace speckv

@@ -1,0 +1,107 @@
+// cxl-speckv_amd/csrc/engine_chunk.cpp -- speckv_ext_attend_chunk: causal attention of a chunk of new positions per sequence over
+// stored and held positions, one launch (Engine member; the kernel is attend_chunk.hip)
+#include "engine_internal.hpp"
+
+namespace speckv {
+
+// Sequence i = allocation handles[i] with pos_end[i] stored positions, its tail (tail_idx[i] >= 0: row tail_idx[i] of d_k_tail /
+// d_v_tail) and n_q[i] <= C new positions in d_k_new / d_v_new; ONE launch on the caller's stream.  Ordering as read_pairs: behind
+// what the caller queued on `s`, and behind the asynchronous pool writes on every other caller stream the engine knows.  Nothing is
+// written to the pool and no residency changes.  The per-sequence descriptors travel through a slot of the pinned descriptor ring
+// to its device twin, so the call cannot be captured into a HIP graph; nothing is allocated once the slots are large enough.
+int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                         const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new, const void* d_v_new, uint64_t seq_stride,
+                         uint64_t pos_stride, const int32_t* tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride,
+                         float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+{
+    if (null_) return no_data_path("speckv_ext_attend_chunk");
+    if (!s || !handles || !pos_end || !n_q || !d_q_f16 || !d_k_new || !d_v_new || !d_out) return SPECKV_ERR_INVAL;
+    if (rows_per_pos == 0 || rows_per_pos > 16u || (rows_per_pos & (rows_per_pos - 1u)) || C == 0) return SPECKV_ERR_INVAL;
+    const auto aligned16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16u == 0; };
+    if (!aligned16(d_q_f16) || !aligned16(d_k_new) || !aligned16(d_v_new) || !aligned16(d_k_tail) || !aligned16(d_v_tail) || !aligned16(d_out))
+        return SPECKV_ERR_INVAL;
+    // a row is one position of one layer: 8 heads x 128 elements, 16-byte aligned pieces
+    if (seq_stride % 8u || pos_stride % 8u || pos_stride < 1024u || (n_seq > 1 && seq_stride < 1024u)) return SPECKV_ERR_INVAL;
+    bool any_tail = false, any_q = false;
+    for (uint32_t i = 0; i < n_seq; ++i) {
+        if (n_q[i] > C || pos_end[i] % 2u) return SPECKV_ERR_INVAL;
+        any_q = any_q || n_q[i];
+        any_tail = any_tail || (tail_idx && tail_idx[i] >= 0);
+    }
+    if (any_tail && (!d_k_tail || !d_v_tail || tail_stride % 8u || tail_stride < 1024u)) return SPECKV_ERR_INVAL;
+    if (is_capturing(s)) {
+        SPECKV_ERR("speckv_ext_attend_chunk cannot be captured into a HIP graph (its descriptors are staged per call)");
+        return SPECKV_ERR_INVAL;
+    }
+    const uint32_t per_block = 64u / rows_per_pos;
+    std::vector<Allocation*> as(n_seq);
+    int scheme = -1;
+    const auto check = [&]() -> int {
+        for (uint32_t i = 0; i < n_seq; ++i) {
+            Allocation* a = find(handles[i]);
+            if (!a) return SPECKV_ERR_GENERAL;
+            if (scheme < 0) scheme = a->scheme;
+            if (!a->has_layout || a->scheme != scheme ||
+                (scheme != SPECKV_COMP_FP8_E4M3 && scheme != SPECKV_COMP_INT4_G32 && scheme != SPECKV_COMP_MXFP4))
+                return SPECKV_ERR_INVAL;
+            const Layout& L = a->layout;
+            if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads != 8 || L.num_tokens % 2) return SPECKV_ERR_INVAL;
+            if (layer >= L.num_layers || pos_end[i] > L.num_tokens) return SPECKV_ERR_INVAL;
+            if ((static_cast<uint64_t>(layer) + 1u) * L.num_tokens > a->n_pages) return SPECKV_ERR_INVAL;     // K + V pages of the layer
+            as[i] = a;
+        }
+        return SPECKV_OK;
+    };
+    RC_TRY(check());
+    if (n_seq == 0 || !any_q) return SPECKV_OK;
+    uint64_t n_blocks = 0;
+    for (uint32_t i = 0; i < n_seq; ++i) n_blocks += (n_q[i] + per_block - 1u) / per_block;
+    if (n_blocks * 8u > 0x7FFFFFFFull) return SPECKV_ERR_INVAL;
+    DeviceScope device_scope(device_);
+    const size_t bytes = static_cast<size_t>(n_seq) * sizeof(ChunkSeq);
+    int slot = 0;
+    void *staged = nullptr, *d_slot = nullptr;
+    RC_TRY(descriptor_slot(bytes, &slot, &staged, &d_slot));      // may release the ABI lock: every sequence is judged again
+    RC_TRY(check());
+    uint32_t first_block = 0;
+    for (uint32_t i = 0; i < n_seq; ++i) {
+        const Layout& L = as[i]->layout;
+        const uint64_t k_first = static_cast<uint64_t>(layer) * L.num_tokens;
+        const int32_t tail = tail_idx && tail_idx[i] >= 0 ? tail_idx[i] : -1;
+        static_cast<ChunkSeq*>(staged)[i] = ChunkSeq{as[i]->row, pos_end[i], n_q[i], first_block, k_first, k_first + L.num_tokens / 2u,
+                                                     tail, tail >= 0 ? 1u : 0u};
+        first_block += (n_q[i] + per_block - 1u) / per_block;
+    }
+    for (auto& w : write_evs_)
+        if (w.s != s) HIP_TRY(hipStreamWaitEvent(s, w.ev, 0));
+    HIP_TRY(hipMemcpyAsync(d_slot, staged, bytes, hipMemcpyHostToDevice, s));
+    ChunkArgs ca{};
+    ca.seqs = static_cast<const ChunkSeq*>(d_slot);
+    ca.tab = d_tab_;
+    ca.q = static_cast<const _Float16*>(d_q_f16);
+    ca.k_new = static_cast<const _Float16*>(d_k_new);
+    ca.v_new = static_cast<const _Float16*>(d_v_new);
+    ca.k_tail = static_cast<const _Float16*>(d_k_tail);
+    ca.v_tail = static_cast<const _Float16*>(d_v_tail);
+    ca.out = d_out;
+    ca.lse = d_lse;
+    ca.seq_stride = seq_stride;
+    ca.pos_stride = pos_stride;
+    ca.tail_stride = tail_stride;
+    ca.n_seq = n_seq;
+    ca.n_blocks = first_block;
+    ca.C = C;
+    ca.rows_per_pos = rows_per_pos;
+    ca.heads = 8;
+    ca.sm_scale = sm_scale;
+    ca.scheme = scheme;
+    HIP_TRY(launch_attend_chunk(ca, s));
+    for (uint32_t i = 0; i < n_seq; ++i) note_use(as[i], s);     // speckv_free waits for this stream
+    if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel
+        (void)hipGetLastError();
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return SPECKV_OK;
+}
+
+} // namespace speckv

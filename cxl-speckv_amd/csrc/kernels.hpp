@@ -145,6 +145,40 @@ struct CopyArgs {
 // ONE launch; a source page never written leaves the destination page never written (rec_bytes 0, its slot zero bytes)
 hipError_t launch_copy_records(const CopyArgs& a, hipStream_t s);
 
+// One sequence of a chunk-attention launch (ChunkArgs::seqs; attend_chunk.hip): pos_end (even) stored positions whose K pages are
+// k_first + p / 2 and whose V pages are v_first + p / 2 of the allocation in table row `table_row`, base in {0, 1} held odd last
+// positions (row tail_idx of the tail arrays) and n_q new positions.  first_block = the query blocks (ceil(n_q / (64 / rows_per_pos)))
+// of the sequences in front of this one (the host's exclusive prefix: the kernel finds the sequence of a flat block index by binary
+// search and needs no atomics).
+struct ChunkSeq {
+    uint32_t table_row;
+    uint32_t pos_end;
+    uint32_t n_q;
+    uint32_t first_block;
+    uint64_t k_first;
+    uint64_t v_first;
+    int32_t  tail_idx;
+    uint32_t base;
+};
+struct ChunkArgs {
+    const ChunkSeq* seqs;             // device array
+    const DevAlloc* tab;              // the device allocation table
+    const _Float16* q;                // [n_seq][C][heads][rows_per_pos][128]
+    const _Float16* k_new;            // new position j of sequence i, head h: k_new + i * seq_stride + j * pos_stride + 128 h
+    const _Float16* v_new;
+    const _Float16* k_tail;           // tail row r, head h: k_tail + r * tail_stride + 128 h (may be null when no sequence has a tail)
+    const _Float16* v_tail;
+    float*          out;              // as q, fp32
+    float*          lse;              // [n_seq][C][heads][rows_per_pos], natural log; may be null
+    uint64_t        seq_stride, pos_stride, tail_stride;      // elements
+    uint32_t        n_seq, n_blocks;  // n_blocks = the sum of the sequences' query blocks
+    uint32_t        C, rows_per_pos, heads;
+    float           sm_scale;
+    int             scheme;           // kFp8E4m3, kInt4G32 or kMxFp4
+};
+// ONE launch of n_blocks * heads workgroups; nothing is launched for n_blocks == 0
+hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s);
+
 // Source / destination description of one codec launch.  Exactly one of
 // {entries, recs, tab+alloc_list} is used as the record source.
 struct CodecArgs {

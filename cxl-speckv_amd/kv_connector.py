@@ -22,6 +22,8 @@ paged-attention layer would talk to for a BATCH of requests:
   commit / truncate            the commit in one launch (``speckv_ext_write_pairs``), and its undo: roll requests back to shorter
                                lengths, the new odd last positions read back out of their pairs by one launch
                                (``speckv_ext_read_pairs``)
+  attend_chunk                 the same attention for a CHUNK of any length (chunked prefill, the suffix behind a fork, a prompt continued
+                               after a truncate): one launch, a workgroup per 64 query rows of a kv head (``speckv_ext_attend_chunk``)
   fork                         new requests started from positions other requests hold (parallel sampling, beam search, a shared
                                prefix): the stored records copied by one launch (``speckv_ext_copy_runs``), nothing decoded
   tree_masks / append_path     the same step with drafts that form a TREE (``attend_spec(parents=...)``): a node sees its
@@ -646,6 +648,93 @@ class SpeckvKVConnector:
                                               d_base.data_ptr(), 0 if d_live is None else d_live.data_ptr(), sm_scale, og.data_ptr(),
                                               lse.data_ptr(), st.cuda_stream)
                     out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
+        return out
+
+    # ------------------------------------------------------------------ chunks of any length
+    @staticmethod
+    def chunk_blocks(n_new: Sequence[int], rows_per_pos: int):
+        """How a chunk step is cut into the workgroups of speckv_ext_attend_chunk: a query block is 64 // rows_per_pos positions of one
+        request (64 query rows per kv head: 16 per wave), request b with n_new[b] live positions has ceil(n_new[b] / that) blocks, none
+        for 0.  Returns (counts, firsts): the per-request block counts and their exclusive prefix -- the rule by which the kernel finds
+        the request of a flat block index (the last request whose prefix is <= the index; requests without blocks share their
+        successor's prefix and are passed over).  Pure python, no device."""
+        import numbers
+        if isinstance(rows_per_pos, bool) or not isinstance(rows_per_pos, numbers.Integral) or rows_per_pos not in (1, 2, 4, 8, 16):
+            raise ValueError("rows_per_pos must be 1, 2, 4, 8 or 16 (query rows per kv head of one position)")
+        per = 64 // int(rows_per_pos)
+        counts, firsts, total = [], [], 0
+        for n in n_new:
+            if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+                raise ValueError(f"n_new: counts of positions >= 0, not {n!r}")
+            counts.append((int(n) + per - 1) // per)
+            firsts.append(total)
+            total += counts[-1]
+        return counts, firsts
+
+    def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None):
+        """One layer of a step that carries a CHUNK of S new positions per request, S >= 1 with no bound but max_tokens -- chunked prefill
+        of a long prompt, the differing suffix behind fork(), a prompt continued after truncate().  Shapes and meaning are those of
+        attend_spec without `parents`: q [batch][S][heads][rows_per_pos][dim] fp16 (rows_per_pos 1, 2, 4, 8 or 16), k_new / v_new
+        [batch][S][layers][heads][dim] fp16, n_new optional per-request counts <= S of live positions; query position j of a request
+        sees everything the request holds (pool and odd last position) and the new positions 0..j.  Returns [batch][S][heads]
+        [rows_per_pos][dim] fp32; rows of positions >= n_new[b] are zeros.  Changes no state -- commit(nodes=range(n)) or
+        append_tokens() stores the chunk afterwards.
+        ONE launch (speckv_ext_attend_chunk): a workgroup takes 64 // rows_per_pos positions of one kv head and walks the request's
+        records once for them (chunk_blocks), k_new / v_new are read in place through their strides.  The query stays fp16 in every
+        pool format (attend() and attend_spec() over FP8 and MXFP4 pools quantise it).
+        When to use which: attend_spec splits the stored positions across the chip and is the route for short speculative steps
+        (S <= 16); attend_chunk does not split positions, so few positions over a long context leave most of the chip idle, while a
+        chunk fills it with query blocks.  The crossover between the two is not measured yet: profiles/tools/chunk_prefill_bench.py
+        times both at S = 16 and writes profiles/chunk_prefill.txt."""
+        import numpy as np
+        import torch
+        if self.scheme not in FUSED:
+            raise ValueError("attend_chunk() needs an FP8, INT4 or MXFP4 pool")
+        if len(q.shape) != 5:
+            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim]")
+        B, S, H, R, D = (int(x) for x in q.shape)
+        want = (B, S, self.L, self.H, self.D)
+        if (H, D) != (self.H, self.D) or tuple(k_new.shape) != want or tuple(v_new.shape) != want or B != len(req_ids) or S < 1:
+            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim], k_new / v_new [batch][S][layers][heads][dim], S >= 1")
+        if not 0 <= layer < self.L:
+            raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
+        if n_new is None:
+            live = [S] * B
+        else:
+            live = [int(n) for n in n_new]
+            if len(live) != B or not all(0 <= n <= S for n in live):
+                raise ValueError("n_new: one count 0..S per request")
+        counts, _ = self.chunk_blocks(live, R)
+        key, reqs, handles = self._batch(req_ids)
+        for r, n in zip(reqs, live):
+            if r.length + n > self.T:
+                raise ValueError(f"a request of {r.length} positions cannot take {n} more: max_tokens is {self.T}")
+        out = (torch.empty if n_new is None else torch.zeros)((B, S, H, R, D), dtype=torch.float32, device="cuda")
+        if not any(counts):
+            return out
+        row = self.H * self.D
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):
+                if self._kscale is not None:
+                    q = q * self._kscale[layer][None, None, :, None, :]
+                    k_new = k_new * self._kscale_inv[None, None]
+                q = q.contiguous()
+                in_place = lambda t: (t.stride(4) == 1 and t.stride(3) == self.D and t.stride(2) % 8 == 0 and t.stride(1) % 8 == 0 and
+                                      t.stride(1) >= row and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0)
+                if not (in_place(k_new) and in_place(v_new) and k_new.stride() == v_new.stride()):
+                    k_new, v_new = k_new.contiguous(), v_new.contiguous()
+                self._prepare_tails(req_ids, key, reqs, st)
+                tail_idx, rank = np.full(B, -1, dtype=np.int32), 0
+                for b, r in enumerate(reqs):
+                    if r.length & 1:
+                        tail_idx[b] = rank
+                        rank += 1
+                kt = self._fold_k.data_ptr() + 2 * layer * row if rank else 0
+                vt = self._fold_v.data_ptr() + 2 * layer * row if rank else 0
+                self.lib.attend_chunk(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                      np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
+                                      v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
+                                      self.L * row, sm_scale, out.data_ptr(), 0, st.cuda_stream)
         return out
 
     def _tree_table(self, key, reqs, parents, n_new, n_layers, S):

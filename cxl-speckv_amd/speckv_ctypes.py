@@ -63,6 +63,8 @@ _EXT_SIGNATURES = {
     "speckv_ext_write_pairs": [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_uint64, c_void_p],
     "speckv_ext_read_pairs": [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_uint64, c_void_p],
     "speckv_ext_copy_runs": [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
+    "speckv_ext_attend_chunk": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
+                                c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
     "speckv_ext_bind_request": [c_uint32, c_uint64, c_uint32],
@@ -304,6 +306,20 @@ class SpeckvLib:
         as_arr = lambda v, t, k: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * k)(*v))
         ss, ds, ns, fs = as_arr(src, c_uint64, n), as_arr(dst, c_uint64, n), as_arr(n_pages, c_uint64, n), as_arr(run_firsts, c_uint64, m)
         self._ext("speckv_ext_copy_runs", ss, ds, ns, n, fs, m, c_void_p(stream))
+
+    def attend_chunk(self, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx, d_k_tail,
+                     d_v_tail, tail_stride, sm_scale, d_out, d_lse, stream):
+        """Causal attention of a chunk of n_q[i] <= C new positions per sequence over its pos_end[i] stored positions, its held odd last
+        position (tail_idx[i] >= 0: that row of d_k_tail / d_v_tail) and the new positions themselves, ONE launch for any chunk length
+        (speckv_ext_attend_chunk; the query stays fp16).  handles, pos_end, n_q, tail_idx: one entry per sequence -- numpy arrays
+        (uint64 / uint32 / int32), ctypes arrays or sequences; tail_idx may be None.  Strides in fp16 elements; d_lse may be 0."""
+        n = len(handles)
+        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
+        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
+        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
+        self._ext("speckv_ext_attend_chunk", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
+                  seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, sm_scale, c_void_p(d_out),
+                  c_void_p(d_lse or None), c_void_p(stream))
 
     def read(self, handle, offset, dst_ptr, nbytes, on_device):
         self._ext("speckv_ext_read", handle, offset, c_void_p(dst_ptr), nbytes, int(on_device))

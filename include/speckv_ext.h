@@ -695,6 +695,42 @@ speckv_status_t speckv_ext_stream_is_capturing(void* stream, int* out_capturing)
 /* library identity: "hip" when built with the HIP data path */
 const char* speckv_ext_backend(void);
 
+/* speckv_ext_attend_chunk: causal attention of a CHUNK of new positions per sequence over everything the sequence holds, for any
+ * chunk length, in ONE launch -- chunked prefill of a long prompt, the differing suffix behind a fork, a prompt continued after a
+ * truncate.  The semantics are those of a speckv_ext_attend_*_planned pass followed by speckv_ext_attend_fold_held, without their
+ * limits of 16 query rows per pass and SPECKV_HELD_MAX held positions.  Sequence i (allocation handles[i], shim layout with 8 kv
+ * heads x 128) has pos_end[i] stored positions (even), one held odd last position if tail_idx[i] >= 0 (row tail_idx[i] of d_k_tail /
+ * d_v_tail, tail_stride_elems apart) and n_q[i] <= C new positions: new position j, head h at d_k_new / d_v_new + i * seq_stride_elems
+ * + j * pos_stride_elems + h * 128 elements (offset to the layer by the caller; read where they lie, no gathered copy).  Query
+ * position j < n_q[i] sees the stored positions [0, pos_end[i]), the tail, the new positions in front of it and itself.
+ *   d_q_f16 : [n_seq][C][heads][rows_per_pos][128] fp16, rows_per_pos in {1, 2, 4, 8, 16} query rows per kv head and position
+ *   d_out   : the same in fp32: softmax(q.K^T sm_scale).V, normalised     d_lse : [n_seq][C][heads][rows_per_pos] fp32 natural-log
+ *             sum of the exponentials, or NULL.  Rows of positions >= n_q[i] are not computed and not written.
+ * Stored K and V enter as the fp16 values speckv_ext_fetch_range decodes for the page (a page never written: zeros; records at or
+ * beyond pos_end[i], which a truncate leaves behind, are never seen).  THE QUERY STAYS fp16 for all three formats: unlike the FP8 and
+ * MXFP4 decode kernels (speckv_ext_attend_fp8_* / _mx4_*), which quantise q, this entry does not.  Both products run on fp16 MFMA with
+ * fp32 accumulation; the softmax weights are rounded to fp16.  There is no split over positions: a row's result does not depend on
+ * which other sequences share the call.  One workgroup takes 64 / rows_per_pos positions of one kv head, so the call suits chunks;
+ * a step of a few positions over a long context is spread wider by speckv_ext_attend_*_planned + speckv_ext_attend_fold_held.
+ * One layer per call.  Asynchronous on `stream`; the host arrays are copied before return.  The records are read behind what the
+ * caller queued on `stream` and behind the asynchronous pool writes handed to other streams before the call.  NOT capturable into a
+ * HIP graph: the per-sequence descriptors are staged per call through a pinned slot (a capturing stream is SPECKV_ERR_INVAL).
+ * Nothing is allocated once the descriptor slots exist; nothing in the pool or its caches changes.
+ *   SPECKV_ERR_INVAL    NULL stream or arrays, an odd pos_end[i] or one beyond the layout, n_q[i] > C, C == 0, a bad rows_per_pos,
+ *                       strides that are not multiples of 8 or shorter than heads * 128, pointers that are not 16-byte aligned, a
+ *                       tail without tail rows, allocations of different schemes or of a scheme other than FP8_E4M3, INT4_G32,
+ *                       MXFP4, a layout other than 8 x 128 fp16, a layer beyond the layout -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle
+ * n_seq == 0 or every n_q[i] == 0: SPECKV_OK, nothing is launched. */
+speckv_status_t speckv_ext_attend_chunk(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer,
+                                        const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                        const uint32_t* pos_end, const uint32_t* n_q /* host arrays [n_seq] */,
+                                        const void* d_k_new, const void* d_v_new, uint64_t seq_stride_elems,
+                                        uint64_t pos_stride_elems,
+                                        const int32_t* tail_idx /* host [n_seq], < 0 = none; may be NULL */,
+                                        const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,
+                                        float sm_scale, float* d_out, float* d_lse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
