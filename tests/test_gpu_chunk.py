@@ -7,8 +7,11 @@ fp16-query path, HeadChecker.check with delta = 0: |err| <= 2e-3 sum p|v| + 1e-6
 
 L = 2, T = 256, 8 x 128 heads; the batch holds prompts of 0, 1, 2, 37, 64 and 98 positions (no pool and no tail, a tail only, one page,
 a partial last tile with a tail, whole tiles, three tiles and a partial one) and takes S = 70 new positions with 70, 33, 17, 16, 1 and 0
-of them live: 1 to 3 held tiles, 1 to 9 query blocks, the last block partial."""
+of them live: 1 to 3 held tiles, 1 to 18 query blocks, the last block partial; every rows_per_pos the entry takes (1, 2, 4, 8, 16) and
+both layers.  Batch order, peaked scores, long chunks, the layout's end, striped pools, the K pre-scale and never-written pages: the
+second half of this file."""
 import contextlib
+import types
 
 import numpy as np
 import pytest
@@ -43,21 +46,24 @@ def _inputs(rpp):
     return _data["prompts"], _data["new"], _data[("q", rpp)]
 
 
-def _stored64(oracle, scheme, b, k, v, head):
-    """float64 K and V rows of the even part of a prompt, kv head `head`, as the oracle's records hold them (computed once per prompt)"""
-    key = (scheme, b, k.shape[1], float(np.abs(k.astype(np.float32)).sum()))
+def _stored64(oracle, scheme, b, k, v, head, layer=LAYER):
+    """float64 K and V rows of the even part of a prompt's layer, kv head `head`, as the oracle's records hold them (computed once per
+    prompt and layer)"""
+    key = (scheme, b, layer, k.shape[1], float(np.abs(k[layer].astype(np.float32)).sum()), float(np.abs(v[layer].astype(np.float32)).sum()))
     if key not in _kv64:
         even = k.shape[1] & ~1
-        _kv64[key] = HeadChecker(oracle, SCHEMES[scheme], _region(k[LAYER, :even], v[LAYER, :even], T), T)
+        _kv64[key] = HeadChecker(oracle, SCHEMES[scheme], _region(k[layer, :even], v[layer, :even], T), T)
     return _kv64[key].kv(head)
 
 
 @contextlib.contextmanager
-def _batch(torch, scheme, prompts, rids=None, **env):
-    """a connector whose requests hold the prompts"""
+def _batch(torch, scheme, prompts, rids=None, kscale=None, **env):
+    """a connector whose requests hold the prompts; kscale: a K pre-scale [L][H][D] set before the first write"""
     lib = open_lib(**env) if env else pkg.SpeckvLib(pkg.library_path(), "hip:0")
     try:
         conn = SpeckvKVConnector(lib, L, H, D, T, scheme)
+        if kscale is not None:
+            conn.set_k_channel_scale(torch.from_numpy(kscale).cuda())
         keep = []
         for rid, (k, v) in zip(rids if rids is not None else range(len(prompts)), prompts):
             conn.add_request(rid)
@@ -122,31 +128,35 @@ def _reference(K, V, tail, q, kn, vn):
     return ((p @ Va) / l[:, None]).reshape(n, R, D), (mx + np.log(l)).reshape(n, R), ((p @ np.abs(Va)) / l[:, None]).reshape(n, R, D)
 
 
-def _check64(oracle, scheme, conn, b, rid, prompt, q, new, n, out, lse, what):
-    """rows of request b's first n new positions against float64; returns the worst err / tol"""
+def _check64(oracle, scheme, conn, b, rid, prompt, q, new, n, out, lse, what, layer=LAYER):
+    """rows of request b's first n new positions against float64 at `layer`; lse None: the output only (the connector returns no lse).
+    Returns the worst err / tol"""
     k, v = prompt
     even, worst = k.shape[1] & ~1, 0.0
     r = conn.requests[rid]
     for head in range(H):
-        K, V = _stored64(oracle, scheme, b, k, v, head)
-        tail = None if not r.length & 1 else (r.tail_k[LAYER, head].cpu().numpy(), r.tail_v[LAYER, head].cpu().numpy())
-        want, wlse, mag = _reference(K[:even], V[:even], tail, q[b, :n, head], new[0][b, :n, LAYER, head], new[1][b, :n, LAYER, head])
+        K, V = _stored64(oracle, scheme, b, k, v, head, layer)
+        tail = None if not r.length & 1 else (r.tail_k[layer, head].cpu().numpy(), r.tail_v[layer, head].cpu().numpy())
+        want, wlse, mag = _reference(K[:even], V[:even], tail, q[b, :n, head], new[0][b, :n, layer, head], new[1][b, :n, layer, head])
         err, tol = np.abs(_f32(out)[b, :n, head] - want), 2e-3 * mag + 1e-6
-        lerr = np.abs(_f32(lse)[b, :n, head] - wlse)
+        lerr = np.zeros(1) if lse is None else np.abs(_f32(lse)[b, :n, head] - wlse)
         worst = max(worst, float((err / tol).max()), float(lerr.max() / 2e-3))
         assert np.all(err <= tol), (what, scheme, b, head, "out", float((err / tol).max()))
         assert np.all(lerr <= 2e-3), (what, scheme, b, head, "lse", float(lerr.max()))
     return worst
 
 
-@pytest.mark.parametrize("rpp", [1, 4, 8])
+@pytest.mark.parametrize("rpp", [1, 2, 4, 8, 16])
 @pytest.mark.parametrize("scheme", ["fp8", "int4", "mxfp4"])
 def test_attend_chunk_against_float64(oracle, scheme, rpp):
-    """the entry over the ragged batch against float64, and SpeckvKVConnector.attend_chunk gives the entry's bits (zeros for the rows
-    of positions that are not live)"""
+    """the entry over the ragged batch against float64 at layer 0 (k_first = 0) and at layer 1, and SpeckvKVConnector.attend_chunk
+    gives the entry's bits (zeros for the rows of positions that are not live)"""
     torch = torch_mod()
     prompts, new, q = _inputs(rpp)
     with _batch(torch, scheme, prompts) as (lib, conn):
+        out0, lse0 = _entry(torch, lib, conn, RIDS, q, new[0], new[1], N_NEW, layer=0)
+        worst = max(_check64(oracle, scheme, conn, b, b, prompts[b], q, new, N_NEW[b], out0, lse0, "batch, layer 0", layer=0) for b in RIDS if N_NEW[b])
+        print(f"attend_chunk {scheme} rows_per_pos {rpp} layer 0: worst err / tol {worst:.3f}")
         out, lse = _entry(torch, lib, conn, RIDS, q, new[0], new[1], N_NEW)
         worst = max(_check64(oracle, scheme, conn, b, b, prompts[b], q, new, N_NEW[b], out, lse, "batch") for b in RIDS if N_NEW[b])
         print(f"attend_chunk {scheme} rows_per_pos {rpp}: worst err / tol {worst:.3f}")
@@ -171,24 +181,40 @@ def test_rows_of_positions_that_are_not_live_are_not_written(scheme):
             assert np.all(np.isfinite(_f32(out)[b, :n])) and not np.any(out[b, :n] == PATTERN) and not np.any(lse[b, :n] == PATTERN)
 
 
+def _causal_probe(torch, lib, conn, rids, q, new, n_new, js, what):
+    """new rows behind position j replaced, for every j of js: rows <= j keep their bits, every later row changes"""
+    other = np.random.default_rng(5).standard_normal((2,) + new[0].shape).astype(np.float16)
+    out, lse = _entry(torch, lib, conn, rids, q, new[0], new[1], n_new)
+    for j in js:
+        k2, v2 = new[0].copy(), new[1].copy()
+        k2[:, j + 1:], v2[:, j + 1:] = other[0][:, j + 1:], other[1][:, j + 1:]
+        out2, lse2 = _entry(torch, lib, conn, rids, q, k2, v2, n_new)
+        for b, n in enumerate(n_new):
+            keep = min(n, j + 1)
+            assert np.array_equal(out2[b, :keep], out[b, :keep]) and np.array_equal(lse2[b, :keep], lse[b, :keep]), (what, j, b)
+            changed = (out2[b, keep:n] != out[b, keep:n]).any(axis=-1)
+            assert changed.all(), (what, j, b, "a row that sees a replaced position kept its bits")
+
+
 @pytest.mark.parametrize("scheme", ["fp8", "int4", "mxfp4"])
 def test_a_row_does_not_see_the_positions_behind_it(scheme):
     """new rows behind position j replaced, j on and beside the edges of query blocks (16 positions at rows_per_pos 4) and of held tiles
     (32 positions; requests with a tail are shifted by one): rows <= j keep their bits, every later row changes"""
     torch = torch_mod()
     prompts, new, q = _inputs(4)
-    other = np.random.default_rng(5).standard_normal((2,) + new[0].shape).astype(np.float16)
     with _batch(torch, scheme, prompts) as (lib, conn):
-        out, lse = _entry(torch, lib, conn, RIDS, q, new[0], new[1], N_NEW)
-        for j in (15, 16, 30, 31, 32, 63):
-            k2, v2 = new[0].copy(), new[1].copy()
-            k2[:, j + 1:], v2[:, j + 1:] = other[0][:, j + 1:], other[1][:, j + 1:]
-            out2, lse2 = _entry(torch, lib, conn, RIDS, q, k2, v2, N_NEW)
-            for b, n in enumerate(N_NEW):
-                keep = min(n, j + 1)
-                assert np.array_equal(out2[b, :keep], out[b, :keep]) and np.array_equal(lse2[b, :keep], lse[b, :keep]), (scheme, j, b)
-                changed = (out2[b, keep:n] != out[b, keep:n]).any(axis=-1)
-                assert changed.all(), (scheme, j, b, "a row that sees a replaced position kept its bits")
+        _causal_probe(torch, lib, conn, RIDS, q, new, N_NEW, (15, 16, 30, 31, 32, 63), scheme)
+
+
+@pytest.mark.parametrize("rpp,js", [(16, (3, 4, 7, 31, 32)), (2, (31, 32, 63))])
+@pytest.mark.parametrize("scheme", ["fp8", "int4", "mxfp4"])
+def test_a_row_does_not_see_the_positions_behind_it_at_other_rows_per_pos(scheme, rpp, js):
+    """the same probe where a wave owns ONE position and a query block is 4 (rows_per_pos 16: j on and beside the block edges, and at
+    the held tile's edge), and where a query block is exactly one held tile (rows_per_pos 2: 32 positions)"""
+    torch = torch_mod()
+    prompts, new, q = _inputs(rpp)
+    with _batch(torch, scheme, prompts) as (lib, conn):
+        _causal_probe(torch, lib, conn, RIDS, q, new, N_NEW, js, (scheme, rpp))
 
 
 @pytest.mark.parametrize("scheme", ["fp8", "int4", "mxfp4"])
@@ -339,3 +365,252 @@ def test_attend_chunk_refuses_bad_arguments_and_launches_nothing():
         none = lambda t: np.zeros(1, t)[:0]
         lib.attend_chunk(none(np.uint64), 0, 16, 1, 1, none(np.uint32), none(np.uint32), 16, 16, 1024, 1024, None, 0, 0, 0, 1.0, 16, 0, 1)
         assert bytes(lib.stats()) == before
+
+
+# =============================================================================
+# Where the flat, ordered batch above does not look: branches and index expressions of k_attend_chunk that it cannot tell from wrong
+# ones.  Same helpers, reference and bound.
+#   batch order    sequences without live positions first, two in a row in the middle, n_q ascending: the kernel's own search
+#   peaked scores  a key c x the query row (c = 0.75: the other weights small; c = 2: they underflow in fp16) in every kind of tile, so
+#                  that the running maximum jumps, alpha is tiny and a rescale that is missing or misplaced costs the whole output
+#   long chunk     200 new positions: 7 held tiles, 13 / 50 query blocks, waves of one block 2 tiles apart
+#   layout         255 positions (the last K and V pages of a layer's regions) at both layers; a pool striped over 3
+#   K pre-scale    SpeckvKVConnector.attend_chunk with set_k_channel_scale, before and after a commit
+#   never written  pages inside [0, pos_end) without a record: zeros, score 0 (not -inf)
+# What no input reaches: an FP8 record shorter than 2048 bytes (the `p0 < r.len` branches of load_pool / decode_pool with 0 < len).  The
+# FP8 encoders of the library and of the oracle write one byte per element of a whole block; a record is 2048 bytes or was never
+# written (len 0, covered here).
+# =============================================================================
+ALL = ["fp8", "int4", "mxfp4"]
+
+
+def _rows(rng, *shape):
+    return rng.standard_normal(shape).astype(np.float16)
+
+
+# ----------------------------------------------------------------------------- batch order
+@pytest.mark.parametrize("n_q", [[0, 70, 0, 0, 17, 1], [1, 0, 16, 17, 0, 70]], ids=["empty-first-and-twice", "ascending"])
+@pytest.mark.parametrize("scheme", ALL)
+def test_sequences_without_live_positions_anywhere_in_the_batch(oracle, scheme, n_q):
+    """the prompts of the ragged batch with n_q = 0 first, twice in a row in the middle and before the last, and n_q ascending: every
+    live row within the float64 bound and, bit for bit, what its request gives alone in a launch; dead rows keep the fill pattern"""
+    torch = torch_mod()
+    prompts, new, q = _inputs(4)
+    with _batch(torch, scheme, prompts) as (lib, conn):
+        out, lse = _entry(torch, lib, conn, RIDS, q, new[0], new[1], n_q, fill=PATTERN)
+        worst = max(_check64(oracle, scheme, conn, b, b, prompts[b], q, new, n_q[b], out, lse, "order") for b in RIDS if n_q[b])
+        print(f"attend_chunk {scheme} n_q {n_q}: worst err / tol {worst:.3f}")
+        for b, n in enumerate(n_q):
+            assert np.all(out[b, n:] == PATTERN) and np.all(lse[b, n:] == PATTERN), (scheme, b, "a dead row was written")
+            if n:
+                one, one_lse = _entry(torch, lib, conn, [b], q[b:b + 1], new[0][b:b + 1], new[1][b:b + 1], [n])
+                assert np.array_equal(one[0, :n], out[b, :n]) and np.array_equal(one_lse[0, :n], lse[b, :n]), (scheme, b)
+
+
+# ----------------------------------------------------------------------------- peaked scores
+J, HEAD, SUB, VCONST = 40, 5, 2, 6.0                 # the query row the needles are aligned to: position J (69 / 45 where a case says so)
+# name -> (prompt length, [(where, position, c)], query position)
+NEEDLES = {
+    "stored-0": (98, [("stored", 0)], J), "stored-31": (98, [("stored", 31)], J), "stored-32": (98, [("stored", 32)], J),
+    "stored-97": (98, [("stored", 97)], J), "tail": (99, [("stored", 98)], J), "new-0": (98, [("new", 0)], J),
+    "new-33": (98, [("new", 33)], J), "itself-69": (98, [("new", 69)], 69),
+}
+
+
+def _peaked(name, c):
+    """prompt (k, v) [L][n][H][D], new (k, v) [1][S][L][H][D], q [1][S][H][4][D], the new rows without needles, the first new position a
+    needle is at (or None), the query position the needles are aligned to"""
+    if name == "late-jump":                         # c = 0.75 in the first pool tile, c = 2 at new position 40: the maximum jumps late
+        n, places, j = 98, [("stored", 0, 0.75), ("new", 40, 2.0)], 45
+    else:
+        n, places, j = NEEDLES[name][0], [p + (c,) for p in NEEDLES[name][1]], NEEDLES[name][2]
+    rng = np.random.default_rng(4242)
+    k, v = _rows(rng, L, n, H, D), _rows(rng, L, n, H, D)
+    kn, vn, q = _rows(rng, 1, S, L, H, D), _rows(rng, 1, S, L, H, D), _rows(rng, 1, S, H, 4, D)
+    plain, first_new = (kn.copy(), vn.copy()), None
+    for where, pos, cc in places:
+        needle = (np.float32(cc) * q[0, j, HEAD, SUB].astype(np.float32)).astype(np.float16)
+        if where == "stored":
+            k[LAYER, pos, HEAD], v[LAYER, pos, HEAD] = needle, np.float16(VCONST)
+        else:
+            kn[0, pos, LAYER, HEAD], vn[0, pos, LAYER, HEAD] = needle, np.float16(VCONST)
+            first_new = pos if first_new is None else min(first_new, pos)
+    return (k, v), (kn, vn), q, plain, first_new, j
+
+
+@pytest.mark.parametrize("case", [(n, c) for n in NEEDLES for c in (0.75, 2.0)] + [("late-jump", None)], ids=lambda x: f"{x[0]}-{x[1]}")
+@pytest.mark.parametrize("scheme", ALL)
+def test_a_key_that_takes_nearly_all_the_weight(oracle, scheme, case):
+    """one request of 98 (99) positions and 70 new ones; a key c x the query row (J, HEAD, SUB) with a V row of 6.0 at one position: the
+    needle scores about 8 (c = 0.75) and 22 (c = 2) natural units above the N(0, 1) rest.  Every row against float64 under the
+    project's bound: weights rounded to fp16 and the same rounded weights summed cost <= 2 x 2^-11 of sum p|v|; fp32 accumulation of
+    exact fp16 products over 128 terms costs a score < 1e-4 while sum |q_d k_d| sm < 64, asserted here for the inputs used.  Rows of
+    positions in front of a needle among the new positions keep the bits they have without it."""
+    torch = torch_mod()
+    name, c = case
+    prompt, new, q, plain, first_new, j = _peaked(name, c)
+    with _batch(torch, scheme, [prompt]) as (lib, conn):
+        r = conn.requests[0]
+        reach = 0.0
+        for head in range(H):
+            K, _ = _stored64(oracle, scheme, 0, prompt[0], prompt[1], head)
+            keys = [np.abs(K[:r.length & ~1]), np.abs(new[0][0, :, LAYER, head].astype(np.float64))]
+            if r.length & 1:
+                keys.append(np.abs(r.tail_k[LAYER, head].cpu().numpy().astype(np.float64))[None])
+            reach = max(reach, float((np.abs(q[0, :, head].astype(np.float64)).reshape(-1, D) @ np.concatenate(keys).T).max()) * SM)
+        assert reach < 64.0, ("the inputs left the reach of the bound's argument", reach)
+        out, lse = _entry(torch, lib, conn, [0], q, new[0], new[1], [S])
+        worst = _check64(oracle, scheme, conn, 0, 0, prompt, q, new, S, out, lse, ("peaked", name, c))
+        print(f"attend_chunk {scheme} needle {name} c {c}: worst err / tol {worst:.3f} (sum |q k| sm <= {reach:.1f})")
+        # the aligned row is the needle's: its output is the needle's V row to within the weight of the rest
+        if c == 2.0 or name == "late-jump":
+            assert np.all(np.abs(_f32(out)[0, j, HEAD, SUB] - VCONST) < 1e-2), (scheme, name, _f32(out)[0, j, HEAD, SUB, :4])
+        if first_new:
+            out2, lse2 = _entry(torch, lib, conn, [0], q, plain[0], plain[1], [S])                   # the same rows without the needle
+            assert np.array_equal(out2[0, :first_new], out[0, :first_new]) and np.array_equal(lse2[0, :first_new], lse[0, :first_new])
+            assert (out2[0, first_new:, HEAD] != out[0, first_new:, HEAD]).any(axis=-1).all()
+
+
+# ----------------------------------------------------------------------------- long chunk
+S_LONG = 200
+
+
+def _long_inputs(rpp):
+    if "long" not in _data:
+        rng = np.random.default_rng(808)
+        _data["long"] = ([(_rows(rng, L, n, H, D), _rows(rng, L, n, H, D)) for n in (0, 1)], (_rows(rng, 2, S_LONG, L, H, D), _rows(rng, 2, S_LONG, L, H, D)))
+    if ("long q", rpp) not in _data:
+        _data[("long q", rpp)] = _rows(np.random.default_rng(809 + rpp), 2, S_LONG, H, rpp, D)
+    return _data["long"] + (_data[("long q", rpp)],)
+
+
+@pytest.mark.parametrize("scheme,rpp", [("fp8", 4), ("int4", 4), ("mxfp4", 4), ("int4", 16)])
+def test_a_chunk_of_200_positions(oracle, scheme, rpp):
+    """an empty request and one that holds a single position (a tail only), 200 new positions each: 7 held tiles, 13 (rows_per_pos 4)
+    and 50 (16) query blocks per request, blocks whose rows see 4 to 7 held tiles and whose first wave is 2 tiles behind its last.
+    Every row against float64, and the causal probe on and beside the edges of the later held tiles"""
+    torch = torch_mod()
+    prompts, new, q = _long_inputs(rpp)
+    n_new = [S_LONG, S_LONG]
+    with _batch(torch, scheme, prompts) as (lib, conn):
+        out, lse = _entry(torch, lib, conn, [0, 1], q, new[0], new[1], n_new)
+        worst = max(_check64(oracle, scheme, conn, b, b, prompts[b], q, new, S_LONG, out, lse, "long") for b in (0, 1))
+        print(f"attend_chunk {scheme} rows_per_pos {rpp} 200 positions: worst err / tol {worst:.3f}")
+        _causal_probe(torch, lib, conn, [0, 1], q, new, n_new, (63, 64, 127, 128, 191, 199), (scheme, rpp, "long"))
+
+
+# ----------------------------------------------------------------------------- layer, layout end, striped pool
+@pytest.mark.parametrize("scheme", ALL)
+def test_the_last_pages_of_a_layer(oracle, scheme):
+    """a request of 255 positions -- pos_end 254, a tail, the last K and V pages of each layer's regions -- takes one new position
+    through the entry (the connector's limit, 255 + 1 = T), at both layers"""
+    torch = torch_mod()
+    rng = np.random.default_rng(255)
+    prompt = (_rows(rng, L, T - 1, H, D), _rows(rng, L, T - 1, H, D))
+    new, q = (_rows(rng, 1, 1, L, H, D), _rows(rng, 1, 1, L, H, D)), _rows(rng, 1, 1, H, 4, D)
+    with _batch(torch, scheme, [prompt]) as (lib, conn):
+        for layer in range(L):
+            out, lse = _entry(torch, lib, conn, [0], q, new[0], new[1], [1], layer=layer)
+            worst = _check64(oracle, scheme, conn, 0, 0, prompt, q, new, 1, out, lse, ("255 positions", layer), layer=layer)
+            print(f"attend_chunk {scheme} 255 positions layer {layer}: worst err / tol {worst:.3f}")
+
+
+@pytest.mark.parametrize("scheme", ALL)
+def test_a_pool_striped_over_three(oracle, scheme):
+    """the ragged batch over three pools of the one GPU (pages striped page by page), both layers against float64"""
+    torch = torch_mod()
+    prompts, new, q = _inputs(4)
+    with _batch(torch, scheme, prompts, SPECKV_POOL_DEVICES="0,0,0") as (lib, conn):
+        for layer in range(L):
+            out, lse = _entry(torch, lib, conn, RIDS, q, new[0], new[1], N_NEW, layer=layer)
+            worst = max(_check64(oracle, scheme, conn, b, b, prompts[b], q, new, N_NEW[b], out, lse, ("striped", layer), layer=layer)
+                        for b in RIDS if N_NEW[b])
+            print(f"attend_chunk {scheme} striped over 3 layer {layer}: worst err / tol {worst:.3f}")
+
+
+# ----------------------------------------------------------------------------- K pre-scale
+def _kscale():
+    kscale = np.ones((L, H, D), np.float32)
+    kscale[:, :, 0::8] = 4.0; kscale[:, :, 3::8] = 0.25
+    return kscale
+
+
+def _f16_times(x, s):
+    """x (fp16) * s (powers of two), rounded once to fp16 as the connector's fp16 multiply rounds"""
+    return (x.astype(np.float32) * s).astype(np.float16)
+
+
+@pytest.mark.parametrize("scheme", ALL)
+def test_connector_attend_chunk_with_a_k_pre_scale(oracle, scheme):
+    """SpeckvKVConnector.attend_chunk of a connector with set_k_channel_scale (4.0 on channels 0::8, 0.25 on 3::8) against float64 over
+    what the kernel is given: the oracle's records of k / scale, the tails as held, k_new / scale and q x scale.  Then the chunk is
+    committed and a second chunk attends: its rows go against float64 over the records of the longer, pre-scaled prompt"""
+    torch = torch_mod()
+    prompts, new, q = _inputs(4)
+    ks = _kscale()
+    inv = (1.0 / ks)
+    dev = lambda x: torch.from_numpy(x).cuda()
+    pre = [(_f16_times(k, inv[:, None]), v) for k, v in prompts]                                    # [L][n][H][D] / [L][1][H][D]
+    new_pre = (_f16_times(new[0], inv[None, None]), new[1])                                          # [B][S][L][H][D]
+    rng = np.random.default_rng(66)
+    S2 = 20
+    new2, q2 = (_rows(rng, len(RIDS), S2, L, H, D), _rows(rng, len(RIDS), S2, L, H, D)), _rows(rng, len(RIDS), S2, H, 4, D)
+    new2_pre = (_f16_times(new2[0], inv[None, None]), new2[1])
+    with _batch(torch, scheme, prompts, kscale=ks) as (lib, conn):
+        for layer in range(L):
+            qs = _f16_times(q, ks[layer][None, None, :, None, :])
+            got = conn.attend_chunk(layer, RIDS, dev(q), dev(new[0]), dev(new[1]), SM, N_NEW)
+            torch.cuda.synchronize()
+            got = got.cpu().numpy()
+            worst = max(_check64(oracle, scheme, conn, b, b, pre[b], qs, new_pre, N_NEW[b], got, None, ("pre-scale", layer), layer=layer)
+                        for b in RIDS if N_NEW[b])
+            print(f"attend_chunk {scheme} K pre-scale layer {layer}: worst err / tol {worst:.3f}")
+            for b, n in enumerate(N_NEW):
+                assert not got[b, n:].any()
+        keep = conn.commit(RIDS, dev(new[0]), dev(new[1]), [range(n) for n in N_NEW])
+        torch.cuda.synchronize()
+        assert [conn.length(b) for b in RIDS] == [p + n for p, n in zip(PROMPTS, N_NEW)]
+        longer = [(np.concatenate([pre[b][0], new_pre[0][b, :n].transpose(1, 0, 2, 3)], axis=1),
+                   np.concatenate([pre[b][1], new_pre[1][b, :n].transpose(1, 0, 2, 3)], axis=1)) for b, n in enumerate(N_NEW)]
+        for layer in range(L):
+            qs = _f16_times(q2, ks[layer][None, None, :, None, :])
+            got = conn.attend_chunk(layer, RIDS, dev(q2), dev(new2[0]), dev(new2[1]), SM)
+            torch.cuda.synchronize()
+            got = got.cpu().numpy()
+            worst = max(_check64(oracle, scheme, conn, b, b, longer[b], qs, new2_pre, S2, got, None, ("pre-scale, after a commit", layer),
+                                 layer=layer) for b in RIDS)
+            print(f"attend_chunk {scheme} K pre-scale after a commit layer {layer}: worst err / tol {worst:.3f}")
+        del keep
+
+
+# ----------------------------------------------------------------------------- pages never written
+@pytest.mark.parametrize("layer", [0, 1])
+@pytest.mark.parametrize("scheme", ALL)
+def test_pages_never_written_count_as_zeros(oracle, scheme, layer):
+    """an allocation written through speckv_write except K page 5, V page 9 and the whole second tile (pages 16..31, K and V) of
+    pos_end = 64: a never-written K row scores 0, not -inf (it takes the weight exp(0 - max)), a never-written V row adds nothing,
+    the output is finite and within the float64 bound of the same prompt with zeros there"""
+    torch = torch_mod()
+    _, new, q = _inputs(4)
+    rng = np.random.default_rng(70 + layer)
+    k, v = _rows(rng, L, 64, H, D), _rows(rng, L, 64, H, D)
+    k[:, 2 * 5:2 * 5 + 2] = 0; v[:, 2 * 9:2 * 9 + 2] = 0
+    k[:, 32:] = 0; v[:, 32:] = 0
+    with _batch(torch, scheme, []) as (lib, conn):
+        lib.set_compression_scheme(SCHEMES[scheme])
+        h = lib.alloc(2 * T * L * H * D * 2)
+        lib.set_layout(h, T, L, H, D, 2)
+        page = lambda x, first, n: np.ascontiguousarray(x[layer, 2 * first:2 * (first + n)]).reshape(n, 2 * H * D)
+        for x, region, skip in ((k, layer * T, 5), (v, layer * T + T // 2, 9)):
+            for first, n in ((0, skip), (skip + 1, 16 - skip - 1)):
+                img = page(x, first, n)
+                lib.write(h, (region + first) * 4096, img.ctypes.data, img.nbytes, False)
+        lib.sync()
+        held = types.SimpleNamespace(requests={0: types.SimpleNamespace(handle=h, length=64, tail_k=None, tail_v=None)})
+        n = 33
+        out, lse = _entry(torch, lib, held, [0], q[:1], new[0][:1], new[1][:1], [n], layer=layer, fill=PATTERN)
+        assert np.all(np.isfinite(_f32(out)[0, :n])) and np.all(np.isfinite(_f32(lse)[0, :n]))
+        assert np.all(out[0, n:] == PATTERN) and np.all(lse[0, n:] == PATTERN)
+        worst = _check64(oracle, scheme, held, 0, 0, (k, v), q, new, n, out, lse, ("never written", layer), layer=layer)
+        print(f"attend_chunk {scheme} never-written pages layer {layer}: worst err / tol {worst:.3f}")
+        lib.free(h)
