@@ -34,6 +34,16 @@
 // t > base + j; rows of positions >= n_q are neither loaded nor written.  Every live row sees itself, so its sum is never 0.
 // Ragged chunks: the flat workgroup index is (block, kv head) with the head fast; the block maps to its sequence by binary search
 // on the exclusive block prefixes the host computed.  Everything written goes out through vector stores.
+//
+// Tree form (MASKED, ChunkArgs::mask; speckv_ext_attend_chunk_masked: a step whose new positions form a tree of drafts of any size).
+// The same body; a query row brings mask_words words, bit t of them = HELD position t is visible to it.  Held positions are numbered
+// as above (the tail is 0, new position a is base + a), so word ht of a row is exactly the 32 positions of held tile ht: a lane loads
+// the one word of its row in front of the tile's products and ANDs bit t & 31 into the causal test -- the causal bound stays, bits at
+// or beyond base + j + 1 are ignored, and n_held, wave_t_last and the tile skipping by that bound hold unchanged.  Pool tiles take no
+// mask work.  A row is live iff j < n_q AND its own bit base + j is set; a dead row is treated as rows >= n_q are (no query load, no
+// mask load: its word reads 0; nothing written), so a live row still always sees itself.  A live row may see nothing for several
+// tiles (empty pool, no tail, no ancestor in the first held tiles): m_new stays -inf, m_use = 0 gives alpha = exp2(-inf - 0) = 0,
+// p = 0 and l_run = 0 until the tile with its first visible position, where alpha = 0 rescales an accumulator that is still 0.
 #include "kernels.hpp"
 #include "codec_device.hpp"          // pack_half2, half_bits_to_float
 #include "attend_device.hpp"
@@ -150,7 +160,7 @@ __device__ __forceinline__ Raw load_held(const _Float16* r0, const _Float16* r1)
     return r;
 }
 
-template <int SCHEME>
+template <int SCHEME, bool MASKED>
 __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
 {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufElems];
@@ -192,7 +202,14 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     // compute role: query row qr of the block, contraction group g
     const uint32_t col = lane & 15u, g = lane >> 4;
     const uint32_t qr = 16u * wave + col, j = j_first + qr / rpp, sub = qr % rpp;
-    const bool row_live = j < n_q;
+    // tree form: the row's mask words (one per held tile), and whether its own bit is set
+    const uint32_t* mrow = nullptr;
+    bool row_live = j < n_q;
+    if (MASKED && row_live) {
+        mrow = a.mask + (static_cast<uint64_t>(seq) * a.C + j) * a.mask_words;
+        row_live = (ck_ld<uint32_t>(mrow + ((base + j) >> 5)) >> ((base + j) & 31u)) & 1u;
+        if (!row_live) mrow = nullptr;
+    }
     const uint64_t row_idx = ((static_cast<uint64_t>(seq) * a.C + j) * a.heads + h) * rpp + sub;
     f16x8 qv[4];
 #pragma unroll
@@ -262,6 +279,9 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
         const bool held = tile >= n_pool;
         const uint32_t t_base = held ? 32u * (tile - n_pool) : 32u * tile;
         if (wave_live && (!held || t_base <= wave_t_last)) {
+            // tree form: the row's word of this held tile (all lanes of a row read the same word), in flight under the products
+            uint32_t mword = 0xFFFFFFFFu;
+            if (MASKED && held) mword = mrow ? ck_ld<uint32_t>(mrow + (t_base >> 5)) : 0u;
             // scores: rows = positions 16 hf + 4 g + r of the tile, column = the lane's query row
             f32x4 sc[2];
 #pragma unroll
@@ -275,11 +295,18 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
                 sc[hf] = s4;
             }
             const uint32_t limit = held ? base + j + 1u : pos_end;           // positions of this part the row sees: [0, limit)
+            uint32_t vis = 0u;
+            if (MASKED) {
+                const uint32_t n_seen = limit > t_base ? limit - t_base : 0u;
+                vis = (mword & (n_seen >= 32u ? 0xFFFFFFFFu : (1u << n_seen) - 1u)) >> (4u * g);
+            }
             float sv[8], mx = -__builtin_inff();
 #pragma unroll
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t t = t_base + 16u * (i >> 2) + 4u * g + (i & 3u);
-                sv[i] = t < limit ? sc[i >> 2][i & 3u] * scale2 : -__builtin_inff();
+                // tree form: bit t & 31 of the word (t_base is a multiple of 32), the causal bound folded into the word
+                const bool seen = MASKED ? (vis >> (16u * (i >> 2) + (i & 3u))) & 1u : t < limit;
+                sv[i] = seen ? sc[i >> 2][i & 3u] * scale2 : -__builtin_inff();
                 mx = fmaxf(mx, sv[i]);
             }
             mx = max_over_kb(mx);
@@ -324,7 +351,8 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
 template <int SCHEME>
 hipError_t launch_chunk(const ChunkArgs& a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_attend_chunk<SCHEME>, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -334,7 +362,8 @@ hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s)
 {
     if (a.n_blocks == 0) return hipSuccess;
     if (!a.seqs || !a.tab || !a.q || !a.k_new || !a.v_new || !a.out || a.n_seq == 0 || a.heads == 0 || a.rows_per_pos == 0 ||
-        a.rows_per_pos > 16u || (a.rows_per_pos & (a.rows_per_pos - 1u)) || static_cast<uint64_t>(a.n_blocks) * a.heads > 0x7FFFFFFFull)
+        a.rows_per_pos > 16u || (a.rows_per_pos & (a.rows_per_pos - 1u)) || static_cast<uint64_t>(a.n_blocks) * a.heads > 0x7FFFFFFFull ||
+        (a.mask && a.mask_words < (a.C + 32u) / 32u))
         return hipErrorInvalidValue;
     switch (a.scheme) {
     case kFp8E4m3: return launch_chunk<kFp8E4m3>(a, s);

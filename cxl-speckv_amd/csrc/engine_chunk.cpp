@@ -1,5 +1,5 @@
-// cxl-speckv_amd/csrc/engine_chunk.cpp -- speckv_ext_attend_chunk: causal attention of a chunk of new positions per sequence over
-// stored and held positions, one launch (Engine member; the kernel is attend_chunk.hip)
+// cxl-speckv_amd/csrc/engine_chunk.cpp -- speckv_ext_attend_chunk / speckv_ext_attend_chunk_masked: causal attention of a chunk of
+// new positions per sequence over stored and held positions, one launch (Engine member; the kernel is attend_chunk.hip)
 #include "engine_internal.hpp"
 
 namespace speckv {
@@ -9,14 +9,20 @@ namespace speckv {
 // what the caller queued on `s`, and behind the asynchronous pool writes on every other caller stream the engine knows.  Nothing is
 // written to the pool and no residency changes.  The per-sequence descriptors travel through a slot of the pinned descriptor ring
 // to its device twin, so the call cannot be captured into a HIP graph; nothing is allocated once the slots are large enough.
+// `mask` (the masked entry; the causal one passes none): per query position mask->words words of visible HELD positions, a device
+// array the kernel reads in place -- nothing about it is staged.
 int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
                          const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new, const void* d_v_new, uint64_t seq_stride,
                          uint64_t pos_stride, const int32_t* tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride,
-                         float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+                         float sm_scale, float* d_out, float* d_lse, hipStream_t s, const ChunkMask* mask)
 {
-    if (null_) return no_data_path("speckv_ext_attend_chunk");
+    const char* entry = mask ? "speckv_ext_attend_chunk_masked" : "speckv_ext_attend_chunk";
+    if (null_) return no_data_path(entry);
     if (!s || !handles || !pos_end || !n_q || !d_q_f16 || !d_k_new || !d_v_new || !d_out) return SPECKV_ERR_INVAL;
     if (rows_per_pos == 0 || rows_per_pos > 16u || (rows_per_pos & (rows_per_pos - 1u)) || C == 0) return SPECKV_ERR_INVAL;
+    // a row's words cover held positions 0 .. C (a tail and C new positions)
+    if (mask && (!mask->d_mask || reinterpret_cast<uintptr_t>(mask->d_mask) % 4u || mask->words < (static_cast<uint64_t>(C) + 32u) / 32u))
+        return SPECKV_ERR_INVAL;
     const auto aligned16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16u == 0; };
     if (!aligned16(d_q_f16) || !aligned16(d_k_new) || !aligned16(d_v_new) || !aligned16(d_k_tail) || !aligned16(d_v_tail) || !aligned16(d_out))
         return SPECKV_ERR_INVAL;
@@ -30,7 +36,7 @@ int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer
     }
     if (any_tail && (!d_k_tail || !d_v_tail || tail_stride % 8u || tail_stride < 1024u)) return SPECKV_ERR_INVAL;
     if (is_capturing(s)) {
-        SPECKV_ERR("speckv_ext_attend_chunk cannot be captured into a HIP graph (its descriptors are staged per call)");
+        SPECKV_ERR("%s cannot be captured into a HIP graph (its descriptors are staged per call)", entry);
         return SPECKV_ERR_INVAL;
     }
     const uint32_t per_block = 64u / rows_per_pos;
@@ -95,6 +101,8 @@ int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer
     ca.heads = 8;
     ca.sm_scale = sm_scale;
     ca.scheme = scheme;
+    ca.mask = mask ? mask->d_mask : nullptr;
+    ca.mask_words = mask ? mask->words : 0u;
     HIP_TRY(launch_attend_chunk(ca, s));
     for (uint32_t i = 0; i < n_seq; ++i) note_use(as[i], s);     // speckv_free waits for this stream
     if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel

@@ -175,6 +175,11 @@ struct ChunkArgs {
     uint32_t        C, rows_per_pos, heads;
     float           sm_scale;
     int             scheme;           // kFp8E4m3, kInt4G32 or kMxFp4
+    // tree form (null: causal): row (i * C + j) * mask_words of this device array = query position j of sequence i, bit t & 31 of its
+    // word t >> 5 = HELD position t (the tail, if any, is 0; new position a is base + a) is visible, under the causal bound
+    // t < base + j + 1 as before; a row whose own bit base + j is clear is dead: not computed to the end, not written
+    const uint32_t* mask;
+    uint32_t        mask_words;       // words per query position, >= (C + 1 + 31) / 32
 };
 // ONE launch of n_blocks * heads workgroups; nothing is launched for n_blocks == 0
 hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s);

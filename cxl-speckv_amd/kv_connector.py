@@ -29,6 +29,8 @@ paged-attention layer would talk to for a BATCH of requests:
   tree_masks / append_path     the same step with drafts that form a TREE (``attend_spec(parents=...)``): a node sees its
                                ancestors only, the held rows are folded in by ``speckv_ext_attend_fold_masked`` with one mask
                                word per (request, node); then the accepted root-to-node path is committed
+  chunk_tree_masks             trees of ANY size (``attend_chunk(parents=...)``, ``speckv_ext_attend_chunk_masked``): mask rows of several
+                               words per node, one launch; ``commit(nodes=path)`` stores the accepted path
 
 Only plain device pointers cross into the library; torch is used for device buffers and the tail fold.
 """
@@ -109,6 +111,7 @@ class SpeckvKVConnector:
         self._kscale = self._kscale_inv = None               # set_k_channel_scale
         self._spec_key = self._spec_idx = self._spec_base = None     # attend_spec: where the held rows of a step come from
         self._tree_key = self._tree_masks = None                     # attend_spec(parents=...): the mask words of a step, [n_layers * batch][S]
+        self._chunk_tree_key = self._chunk_tree_masks = None         # attend_chunk(parents=...): the mask rows of a step, [batch][S][W]
 
     def set_k_channel_scale(self, scale):
         """Per-(layer, kv head, channel) pre-scale of K, folded into the query: K / scale goes into the pool, q * scale meets it, q.k is
@@ -671,7 +674,78 @@ class SpeckvKVConnector:
             total += counts[-1]
         return counts, firsts
 
-    def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None):
+    @staticmethod
+    def _chunk_tree_parents(parents, batch):
+        """_tree_parents without its bound on the node count: parents as one list per request ([S] is the same tree for every request,
+        [batch][S] one tree each), every entry an int in -1 .. j-1, S >= 1 nodes, the same count for every request."""
+        import numbers
+        parents = list(parents)
+        if parents and not isinstance(parents[0], numbers.Integral):
+            try:
+                trees = [list(p) for p in parents]
+            except TypeError:
+                raise ValueError("parents: ints, or one list of ints per request") from None
+            if len(trees) != batch:
+                raise ValueError("parents: one tree per request, or one tree for all")
+        else:
+            trees = [parents] * batch
+        S = len(trees[0]) if trees else 0
+        for tree in trees:
+            if len(tree) != S or S < 1:
+                raise ValueError("parents: at least one node, the same count for every request")
+            for j, p in enumerate(tree):
+                if not isinstance(p, numbers.Integral) or isinstance(p, bool) or not -1 <= p < j:
+                    raise ValueError(f"parents[{j}] = {p!r}: a node's parent is -1 (the committed context) or a node in front of it")
+        return [[int(p) for p in tree] for tree in trees]
+
+    @staticmethod
+    def chunk_tree_masks(parents, base, n_new=None):
+        """The mask rows of a step whose S new positions form a tree of ANY size, as speckv_ext_attend_chunk_masked takes them:
+        [batch][S][W] ints, W = (S + 1 + 31) // 32 words of 32 bits per node.  parents, base, n_new as tree_masks: parents [S] or
+        [batch][S] with parents[j] in -1 .. j-1; base[b] in {0, 1}: the request's odd last position, visible to every node.  Bit t of a
+        row (bit t & 31 of word t >> 5) = held position t: node j's row = the low base[b] bits, and the bits base[b] + a of its
+        ancestors a and of j itself.  Nodes >= n_new[b] and every node below a dead one get all-zero rows (the kernel neither computes
+        nor writes them).  For S <= 16 the single word is tree_masks' word; a chain gives (1 << (base + j + 1)) - 1 across the words.
+        Pure python, no device."""
+        base = [int(x) for x in base]
+        trees = SpeckvKVConnector._chunk_tree_parents(parents, len(base))
+        if not trees:
+            return []
+        S = len(trees[0])
+        if n_new is None:
+            n_new = [S] * len(base)
+        n_new = [int(n) for n in n_new]
+        if len(n_new) != len(base) or not all(0 <= n <= S for n in n_new):
+            raise ValueError("n_new: one count 0..S per request")
+        if not all(x in (0, 1) for x in base):
+            raise ValueError("base: 0 or 1 held positions in front of the new ones")
+        W = (S + 1 + 31) // 32
+        rows = []
+        for tree, x, n in zip(trees, base, n_new):
+            bits = []                                                     # a node's row as one python int
+            for j, p in enumerate(tree):
+                up = ((1 << x) - 1) if p < 0 else bits[p]                 # what the parent sees (0: the parent is dead)
+                bits.append(up | 1 << (x + j) if j < n and (p < 0 or bits[p]) else 0)
+            rows.append([[(v >> (32 * w)) & 0xFFFFFFFF for w in range(W)] for v in bits])
+        return rows
+
+    def _chunk_tree_table(self, key, reqs, parents, live, S):
+        """The mask rows of a tree chunk step on the device, int32 [batch][S][W] (bit patterns of the uint32 words), kept per (batch,
+        epoch, S, tree, live counts) the way _tree_table keeps its words: every layer's call of a step finds the same table."""
+        import numbers
+        import numpy as np
+        import torch
+        one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)      # one tree for every request
+        tkey = (key, self._epoch, S, tuple(parents) if one else tuple(map(tuple, parents)), tuple(live))
+        if self._chunk_tree_key != tkey:
+            rows = self.chunk_tree_masks(parents, [r.length & 1 for r in reqs], live)
+            if len(rows[0]) != S:
+                raise ValueError("parents: one entry per new position")
+            words = np.asarray(rows, dtype=np.uint32).view(np.int32)
+            self._chunk_tree_key, self._chunk_tree_masks = tkey, torch.from_numpy(words).pin_memory().to("cuda", non_blocking=True)
+        return self._chunk_tree_masks
+
+    def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None):
         """One layer of a step that carries a CHUNK of S new positions per request, S >= 1 with no bound but max_tokens -- chunked prefill
         of a long prompt, the differing suffix behind fork(), a prompt continued after truncate().  Shapes and meaning are those of
         attend_spec without `parents`: q [batch][S][heads][rows_per_pos][dim] fp16 (rows_per_pos 1, 2, 4, 8 or 16), k_new / v_new
@@ -685,7 +759,12 @@ class SpeckvKVConnector:
         When to use which: attend_spec splits the stored positions across the chip and is the route for short speculative steps
         (S <= 16); attend_chunk does not split positions, so few positions over a long context leave most of the chip idle, while a
         chunk fills it with query blocks.  The crossover between the two is not measured yet: profiles/tools/chunk_prefill_bench.py
-        times both at S = 16 and writes profiles/chunk_prefill.txt."""
+        times both at S = 16 and writes profiles/chunk_prefill.txt.
+        parents (see chunk_tree_masks): the S new positions form a TREE of drafts of any size instead of a chain -- node j sees what the
+        request holds, its ancestors and itself, not its siblings.  Still ONE launch (speckv_ext_attend_chunk_masked) with a mask table
+        built once per (batch, lengths, tree, n_new) and shared by the layers' calls; attend_spec(parents=...) stops at 16 nodes and
+        reads the records once per 16 // rows_per_pos of them.  Rows of dead nodes (>= n_new[b], or below one) are zeros.  Afterwards
+        commit(req_ids, k_new, v_new, nodes=accepted path) stores a root-to-node path of a tree of any size."""
         import numpy as np
         import torch
         if self.scheme not in FUSED:
@@ -709,7 +788,11 @@ class SpeckvKVConnector:
         for r, n in zip(reqs, live):
             if r.length + n > self.T:
                 raise ValueError(f"a request of {r.length} positions cannot take {n} more: max_tokens is {self.T}")
-        out = (torch.empty if n_new is None else torch.zeros)((B, S, H, R, D), dtype=torch.float32, device="cuda")
+        if parents is not None:
+            trees = self._chunk_tree_parents(parents, B)                  # judged in front of any library call
+            if trees and len(trees[0]) != S:
+                raise ValueError("parents: one entry per new position")
+        out = (torch.empty if n_new is None and parents is None else torch.zeros)((B, S, H, R, D), dtype=torch.float32, device="cuda")
         if not any(counts):
             return out
         row = self.H * self.D
@@ -731,6 +814,13 @@ class SpeckvKVConnector:
                         rank += 1
                 kt = self._fold_k.data_ptr() + 2 * layer * row if rank else 0
                 vt = self._fold_v.data_ptr() + 2 * layer * row if rank else 0
+                if parents is not None:
+                    masks = self._chunk_tree_table(key, reqs, parents, live, S)
+                    self.lib.attend_chunk_masked(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                                 np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
+                                                 v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
+                                                 self.L * row, masks.data_ptr(), masks.shape[2], sm_scale, out.data_ptr(), 0, st.cuda_stream)
+                    return out
                 self.lib.attend_chunk(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
                                       np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
                                       v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
@@ -805,7 +895,10 @@ class SpeckvKVConnector:
         k_new / v_new and in the tail tensors a pair consumes; the host computes their addresses.  What torch still does: the K
         pre-scale, a contiguous copy of k_new / v_new that are not, and one index_select per kind for the new tails (copies: the
         caller may reuse k_new).  Returns everything the asynchronous launch reads -- the (scaled) k_new, v_new and the consumed tail
-        tensors -- for the caller to hold until the stream has passed the writes, as append() returns its sources."""
+        tensors -- for the caller to hold until the stream has passed the writes, as append() returns its sources.
+        Large trees: without `parents` there is no bound on S, so the accepted path of a tree verified by attend_chunk(parents=...) is
+        committed here as nodes=path (ascending node indices; the caller vouches that they are a chain of the tree).  With `parents`
+        the path is checked against the tree and the tree keeps tree_masks' bound of 16 nodes."""
         import numpy as np
         import torch
         B, S = k_new.shape[0], k_new.shape[1]

@@ -65,6 +65,9 @@ _EXT_SIGNATURES = {
     "speckv_ext_copy_runs": [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
     "speckv_ext_attend_chunk": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                 c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_chunk_masked": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
+                                       c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p,
+                                       c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
     "speckv_ext_bind_request": [c_uint32, c_uint64, c_uint32],
@@ -320,6 +323,20 @@ class SpeckvLib:
         self._ext("speckv_ext_attend_chunk", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
                   seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, sm_scale, c_void_p(d_out),
                   c_void_p(d_lse or None), c_void_p(stream))
+
+    def attend_chunk_masked(self, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx,
+                            d_k_tail, d_v_tail, tail_stride, d_mask, mask_words, sm_scale, d_out, d_lse, stream):
+        """attend_chunk for new positions that form a tree (speckv_ext_attend_chunk_masked): d_mask = device uint32 [n][C][mask_words], bit
+        t of a query position's row = HELD position t (the tail, if any, is 0; new position a is base + a) is visible to it, under the
+        causal bound t < base + j + 1; a row whose own bit is clear is not written.  mask_words >= (C + 32) // 32.  The other arguments
+        as attend_chunk."""
+        n = len(handles)
+        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
+        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
+        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
+        self._ext("speckv_ext_attend_chunk_masked", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
+                  seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, c_void_p(d_mask or None),
+                  mask_words, sm_scale, c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
 
     def read(self, handle, offset, dst_ptr, nbytes, on_device):
         self._ext("speckv_ext_read", handle, offset, c_void_p(dst_ptr), nbytes, int(on_device))

@@ -731,6 +731,35 @@ speckv_status_t speckv_ext_attend_chunk(uint32_t n_seq, const speckv_handle_t* h
                                         const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,
                                         float sm_scale, float* d_out, float* d_lse, void* stream);
 
+/* speckv_ext_attend_chunk_masked: speckv_ext_attend_chunk for new positions that form a TREE of drafts of any size (no bound of 16
+ * rows per pass or SPECKV_HELD_MAX held positions: a 64-node tree is one launch that reads the records once per 64 query rows).  The
+ * arguments of speckv_ext_attend_chunk in the same order, with d_mask and mask_words in front of sm_scale; everything said there
+ * holds -- layouts, the fp16 query, ordering, NOT capturable into a HIP graph, what is refused -- except what a row sees of the HELD
+ * positions.  Those are numbered as the kernel walks them: held position 0 is the tail if sequence i has one (base = 1, else 0), new
+ * position a is held position base + a.
+ *   d_mask : device, uint32 [n_seq][C][mask_words]; the row of query position j of sequence i starts at d_mask + (i * C + j) *
+ *            mask_words.  Bit t of the row (bit t & 31 of word t >> 5) = held position t is visible to it: the low `base` bits, then
+ *            bits base + a -- the convention of speckv_ext_attend_fold_masked, continued over several words.  mask_words >=
+ *            (C + 1 + 31) / 32; a larger row stride is fine, words beyond that are not read.
+ *   The causal bound stays: held position t is seen iff t < base + j + 1 AND its bit is set, so bits at or beyond base + j + 1 are
+ *   IGNORED.  Stored positions [0, pos_end[i]) are visible to every live row.
+ *   A row is LIVE iff j < n_q[i] AND its own bit base + j is set.  A row that is not live is not computed and NOT WRITTEN (d_out and
+ *   d_lse keep what they held), exactly like rows of positions >= n_q[i]; a live row always sees itself.
+ * A chain (row j = the low base + j + 1 bits) gives speckv_ext_attend_chunk's result bit for bit.  The mask is read by the kernel in
+ * place, behind what the caller queued on `stream`.
+ *   SPECKV_ERR_INVAL    as speckv_ext_attend_chunk, and: d_mask NULL or not 4-byte aligned, mask_words < (C + 1 + 31) / 32 -- nothing
+ *                       is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle */
+speckv_status_t speckv_ext_attend_chunk_masked(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer,
+                                               const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                               const uint32_t* pos_end, const uint32_t* n_q /* host arrays [n_seq] */,
+                                               const void* d_k_new, const void* d_v_new, uint64_t seq_stride_elems,
+                                               uint64_t pos_stride_elems,
+                                               const int32_t* tail_idx /* host [n_seq], < 0 = none; may be NULL */,
+                                               const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,
+                                               const uint32_t* d_mask, uint32_t mask_words,
+                                               float sm_scale, float* d_out, float* d_lse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
