@@ -28,8 +28,8 @@
 //   S^T = K.Q^T (A = K rows from LDS, B = the wave's query rows, resident in 16 VGPRs), so a lane holds 8 scores of ONE query row
 //   (row = lane & 15; positions 4 (lane >> 4) + r and 16 + 4 (lane >> 4) + r) -- exactly the 8 contraction slots of its P operand
 //   in O^T = V^T.P^T once V^T is read in the same slot order.  Row max and sum go over the 4 lanes of a row by row/half swaps.
-// No split over positions: no merge kernel, no scratch, no atomics; a row's result does not depend on which other sequences share
-// the launch.  Masks: stored positions >= pos_end and held positions beyond the sequence's count are staged as ZEROS (V) and scored
+// No split over positions in this form (the split form is below): no merge kernel, no scratch, no atomics; a row's result does not
+// depend on which other sequences share the launch.  Masks: stored positions >= pos_end and held positions beyond the sequence's count are staged as ZEROS (V) and scored
 // -inf (truncate leaves stale records there, and 0 x inf would poison the product); held position t is -inf for rows with
 // t > base + j; rows of positions >= n_q are neither loaded nor written.  Every live row sees itself, so its sum is never 0.
 // Ragged chunks: the flat workgroup index is (block, kv head) with the head fast; the block maps to its sequence by binary search
@@ -44,6 +44,16 @@
 // mask load: its word reads 0; nothing written), so a live row still always sees itself.  A live row may see nothing for several
 // tiles (empty pool, no tail, no ancestor in the first held tiles): m_new stays -inf, m_use = 0 gives alpha = exp2(-inf - 0) = 0,
 // p = 0 and l_run = 0 until the tile with its first visible position, where alpha = 0 rescales an accumulator that is still 0.
+//
+// Split form (SPLIT, ChunkArgs::part; speckv_ext_attend_chunk_split: a short step or a small tree over a LONG context, where the
+// query blocks alone leave most of the chip idle).  The same body; the host cuts sequence i's pool tiles into n_pieces pieces of
+// tiles_per_piece tiles (chunk_split.hpp) and a work item is (sequence, query block, piece, kv head), head fast, found by the same
+// binary search over the exclusive item prefixes.  Only the tile range changes: piece p walks pool tiles [p tpp, min((p + 1) tpp,
+// n_pool)), the LAST piece also the held tiles exactly as the whole walk does (tail, new rows in place, causal bound, mask word,
+// wave_t_last); the prologue stages tile t_begin and the buffer parity counts from it.  The epilogue writes the accumulator as it
+// stands, [64 rows][128] fp32 in the row order of `out`, and (m_run, l_run) per row beside it, through vector stores; dead rows write
+// nothing.  k_chunk_combine, launched behind it on the same stream, merges a row's partials in ascending piece order.  The piece
+// bounds are wave-uniform (scalar registers): the SPLIT instances cost no vector registers worth mentioning.
 #include "kernels.hpp"
 #include "codec_device.hpp"          // pack_half2, half_bits_to_float
 #include "attend_device.hpp"
@@ -160,31 +170,42 @@ __device__ __forceinline__ Raw load_held(const _Float16* r0, const _Float16* r1)
     return r;
 }
 
-template <int SCHEME, bool MASKED>
+template <int SCHEME, bool MASKED, bool SPLIT>
 __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
 {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufElems];
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t h = blockIdx.x % a.heads, fb = blockIdx.x / a.heads;
-    // the last sequence whose block prefix is <= fb (sequences without blocks share their successor's prefix and are passed over)
+    const uint32_t h = blockIdx.x % a.heads, fb = blockIdx.x / a.heads;          // SPLIT: fb = the flat work item (block, piece)
+    // the last sequence whose block prefix is <= fb (sequences without blocks share their successor's prefix and are passed over);
+    // SPLIT: the same search over the item prefixes
     uint32_t lo = 0, hi = a.n_seq;
     while (hi - lo > 1u) {
         const uint32_t mid = (lo + hi) >> 1;
-        if (static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(a.seqs[mid].first_block)) <= fb) lo = mid; else hi = mid;
+        if (static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(SPLIT ? a.seqs[mid].first_item : a.seqs[mid].first_block)) <= fb) lo = mid; else hi = mid;
     }
     const ChunkSeq* sq = a.seqs + lo;
     const uint32_t seq = lo;
     const uint32_t pos_end = __builtin_amdgcn_readfirstlane(sq->pos_end), n_q = __builtin_amdgcn_readfirstlane(sq->n_q);
     const uint32_t base = __builtin_amdgcn_readfirstlane(sq->base);
-    const uint32_t blk = fb - static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(sq->first_block));
+    uint32_t blk = fb - static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(SPLIT ? sq->first_item : sq->first_block));
+    uint32_t piece = 0, n_pieces = 1, tpp = 0;                // (wave-uniform: they live in scalar registers)
+    if (SPLIT) {
+        n_pieces = __builtin_amdgcn_readfirstlane(sq->n_pieces);
+        tpp = __builtin_amdgcn_readfirstlane(sq->tiles_per_piece);
+        piece = blk % n_pieces;
+        blk /= n_pieces;
+    }
     const uint32_t rpp = a.rows_per_pos, per_blk = 64u / rpp;
     const uint32_t j_first = blk * per_blk;
     if (j_first >= n_q) return;                               // (never: the host counts the blocks of live positions only)
     const uint32_t j_last = (j_first + per_blk < n_q ? j_first + per_blk : n_q) - 1u;     // the block's last live position
     const uint32_t n_pool = (pos_end + 31u) >> 5, n_held = ((base + j_last) >> 5) + 1u, n_tiles = n_pool + n_held;
     const uint32_t n_pages = pos_end >> 1, held_n = base + n_q;
+    // SPLIT: piece p walks the pool tiles [p tpp, (p + 1) tpp); the LAST piece goes on through the held tiles, as the whole walk does
+    const uint32_t t_begin = SPLIT ? piece * tpp : 0u;
+    const uint32_t t_end = !SPLIT || piece + 1u == n_pieces ? n_tiles : (t_begin + tpp < n_pool ? t_begin + tpp : n_pool);
 
     const PageEntry* entries = reinterpret_cast<const PageEntry*>(ck_uniform(reinterpret_cast<uint64_t>(a.tab[sq->table_row].entries)));
     const uint64_t k_first = ck_uniform(sq->k_first), v_first = ck_uniform(sq->v_first);
@@ -269,12 +290,12 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     float m_run = -__builtin_inff(), l_run = 0.0f;            // log2 domain
     const float scale2 = a.sm_scale * kLog2e;
 
-    load_tile(0);
-    store_tile(0, lds);
+    load_tile(t_begin);
+    store_tile(t_begin, lds);
     __syncthreads();
-    for (uint32_t tile = 0; tile < n_tiles; ++tile) {
-        _Float16* buf = lds + (tile & 1u) * kBufElems;
-        const bool more = tile + 1u < n_tiles;
+    for (uint32_t tile = t_begin; tile < t_end; ++tile) {
+        _Float16* buf = lds + ((tile - t_begin) & 1u) * kBufElems;
+        const bool more = tile + 1u < t_end;
         if (more) load_tile(tile + 1u);
         const bool held = tile >= n_pool;
         const uint32_t t_base = held ? 32u * (tile - n_pool) : 32u * tile;
@@ -335,10 +356,21 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
                 acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(V, P, acc[t] * alpha, 0, 0, 0);
             }
         }
-        if (more) store_tile(tile + 1u, lds + ((tile + 1u) & 1u) * kBufElems);
+        if (more) store_tile(tile + 1u, lds + ((tile + 1u - t_begin) & 1u) * kBufElems);
         __syncthreads();
     }
 
+    if (SPLIT) {
+        // the partial of (item, head): the accumulator as it stands, (m_run, l_run) beside it; dead rows write nothing
+        if (row_live) {
+            uint8_t* pb = a.part + static_cast<uint64_t>(blockIdx.x) * kChunkPartBytes;
+            float* o = reinterpret_cast<float*>(pb) + qr * 128u + 4u * g;
+#pragma unroll
+            for (uint32_t t = 0; t < 8u; ++t) ck_st<f32x4>(o + 16u * t, acc[t]);
+            if (g == 0u) ck_st<u32x2>(pb + kChunkPartAccBytes + 8u * qr, u32x2{__float_as_uint(m_run), __float_as_uint(l_run)});
+        }
+        return;
+    }
     if (row_live) {
         const float inv = 1.0f / l_run;
         float* o = a.out + row_idx * 128u + 4u * g;
@@ -348,11 +380,76 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     }
 }
 
+// The merge of the split form: one workgroup per (flat query block, kv head), thread t = row t >> 2 of the block and the 16-byte
+// columns (t & 3) + 4 k.  A live row's n_pieces partials are read in ASCENDING piece order (the result does not depend on how the
+// pieces were scheduled): M = max m_p, out = sum acc_p 2^(m_p - M) / sum l_p 2^(m_p - M), lse = (M + log2 sum) ln 2.  A piece that
+// saw nothing (m = -inf, l = 0, acc = 0) weighs 2^-inf = 0 exactly.  Whether a row is live is decided as the pieces decided it -- n_q
+// and, in the tree form, the row's own mask bit -- never by what the scratch holds: a dead row's partials were not written and are
+// not read, and out / lse keep what they held.  Every live row saw itself in the last piece, so its sum is never 0.
+__global__ __launch_bounds__(kChunkThreads) void k_chunk_combine(ChunkArgs a)
+{
+    const uint32_t tid = threadIdx.x;
+    const uint32_t h = blockIdx.x % a.heads, fb = blockIdx.x / a.heads;
+    uint32_t lo = 0, hi = a.n_seq;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(a.seqs[mid].first_block)) <= fb) lo = mid; else hi = mid;
+    }
+    const ChunkSeq* sq = a.seqs + lo;
+    const uint32_t seq = lo;
+    const uint32_t n_q = __builtin_amdgcn_readfirstlane(sq->n_q), base = __builtin_amdgcn_readfirstlane(sq->base);
+    const uint32_t blk = fb - static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(sq->first_block));
+    const uint32_t n_pieces = __builtin_amdgcn_readfirstlane(sq->n_pieces);
+    const uint32_t item = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(sq->first_item)) + blk * n_pieces;
+    const uint32_t rpp = a.rows_per_pos, per_blk = 64u / rpp;
+    const uint32_t qr = tid >> 2, c4 = tid & 3u;
+    const uint32_t j = blk * per_blk + qr / rpp, sub = qr % rpp;
+    bool row_live = j < n_q;
+    if (a.mask && row_live) {
+        const uint32_t* mrow = a.mask + (static_cast<uint64_t>(seq) * a.C + j) * a.mask_words;
+        row_live = (ck_ld<uint32_t>(mrow + ((base + j) >> 5)) >> ((base + j) & 31u)) & 1u;
+    }
+    if (!row_live) return;
+    const uint64_t step = static_cast<uint64_t>(a.heads) * kChunkPartBytes;          // from a piece's partial to the next piece's
+    const uint8_t* pb = a.part + (static_cast<uint64_t>(item) * a.heads + h) * kChunkPartBytes;
+    const uint8_t* ml = pb + kChunkPartAccBytes + 8u * qr;
+    float M = -__builtin_inff();
+    for (uint32_t p = 0; p < n_pieces; ++p) M = fmaxf(M, ck_ld<float>(ml + p * step));
+    const float m_use = M == -__builtin_inff() ? 0.0f : M;
+    f32x4 acc[8];
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; ++k) acc[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    float l_sum = 0.0f;
+    const float* ap = reinterpret_cast<const float*>(pb) + qr * 128u + 4u * c4;
+    for (uint32_t p = 0; p < n_pieces; ++p) {
+        const u32x2 w2 = ck_ld<u32x2>(ml + p * step);
+        const float w = __builtin_amdgcn_exp2f(__uint_as_float(w2.x) - m_use);
+        l_sum += __uint_as_float(w2.y) * w;
+        const float* src = ap + p * (step / sizeof(float));
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) acc[k] += __builtin_bit_cast(f32x4, ck_ld<u32x4>(src + 16u * k)) * w;
+    }
+    const uint64_t row_idx = ((static_cast<uint64_t>(seq) * a.C + j) * a.heads + h) * rpp + sub;
+    const float inv = 1.0f / l_sum;
+    float* o = a.out + row_idx * 128u + 4u * c4;
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; ++k) ck_st<f32x4>(o + 16u * k, acc[k] * inv);
+    if (a.lse && c4 == 0u) ck_st<float>(a.lse + row_idx, (M + __builtin_amdgcn_logf(l_sum)) * kLn2);
+}
+
 template <int SCHEME>
 hipError_t launch_chunk(const ChunkArgs& a, hipStream_t s)
 {
-    if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
-    else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    if (a.part) {
+        if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
+        else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_chunk_combine, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+        return hipGetLastError();
+    }
+    if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -363,7 +460,8 @@ hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s)
     if (a.n_blocks == 0) return hipSuccess;
     if (!a.seqs || !a.tab || !a.q || !a.k_new || !a.v_new || !a.out || a.n_seq == 0 || a.heads == 0 || a.rows_per_pos == 0 ||
         a.rows_per_pos > 16u || (a.rows_per_pos & (a.rows_per_pos - 1u)) || static_cast<uint64_t>(a.n_blocks) * a.heads > 0x7FFFFFFFull ||
-        (a.mask && a.mask_words < (a.C + 32u) / 32u))
+        (a.mask && a.mask_words < (a.C + 32u) / 32u) ||
+        (a.part && (a.n_items < a.n_blocks || static_cast<uint64_t>(a.n_items) * a.heads > 0x7FFFFFFFull || reinterpret_cast<uintptr_t>(a.part) % 16u)))
         return hipErrorInvalidValue;
     switch (a.scheme) {
     case kFp8E4m3: return launch_chunk<kFp8E4m3>(a, s);

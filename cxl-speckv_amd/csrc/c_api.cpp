@@ -13,6 +13,7 @@
 #pragma GCC visibility pop
 #include "engine.hpp"
 #include "placement.hpp"
+#include "chunk_split.hpp"
 
 #include <cstring>
 #include <cstdio>
@@ -799,6 +800,32 @@ speckv_status_t speckv_ext_attend_chunk_masked(uint32_t n_seq, const speckv_hand
     return guarded([&] { return g_engine->attend_chunk(n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new,
                                                        seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
                                                        sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), &mask); });
+}
+
+speckv_status_t speckv_ext_attend_chunk_split(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C,
+                                              uint32_t rows_per_pos, const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new,
+                                              const void* d_v_new, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const int32_t* tail_idx,
+                                              const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems, const uint32_t* d_mask,
+                                              uint32_t mask_words, uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    const speckv::Engine::ChunkMask mask{d_mask, mask_words};
+    return guarded([&] { return g_engine->attend_chunk(n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new,
+                                                       seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
+                                                       sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), d_mask ? &mask : nullptr,
+                                                       &n_splits); });
+}
+
+speckv_status_t speckv_ext_chunk_split_plan(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* n_q, uint32_t rows_per_pos,
+                                            uint32_t n_splits, uint32_t n_cus, uint32_t* out_pieces, uint32_t* out_tiles_per_piece)
+{
+    if (n_seq && (!pos_end || !n_q || !out_pieces || !out_tiles_per_piece)) return SPECKV_ERR_INVAL;
+    if (!n_cus) {                                        // the engine's device, or 256 without one
+        LOCK;
+        n_cus = g_engine && !g_closing ? g_engine->cus() : 256u;
+    }
+    return speckv::chunk_split_plan(n_seq, pos_end, n_q, rows_per_pos, n_splits, n_cus, out_pieces, out_tiles_per_piece) ? SPECKV_OK
+                                                                                                                          : SPECKV_ERR_INVAL;
 }
 
 } // extern "C"

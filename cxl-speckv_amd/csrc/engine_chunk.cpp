@@ -1,6 +1,8 @@
-// cxl-speckv_amd/csrc/engine_chunk.cpp -- speckv_ext_attend_chunk / speckv_ext_attend_chunk_masked: causal attention of a chunk of
-// new positions per sequence over stored and held positions, one launch (Engine member; the kernel is attend_chunk.hip)
+// cxl-speckv_amd/csrc/engine_chunk.cpp -- speckv_ext_attend_chunk / speckv_ext_attend_chunk_masked / speckv_ext_attend_chunk_split:
+// causal attention of a chunk of new positions per sequence over stored and held positions, one launch -- or, where the stored
+// positions are split across the chip, a piece launch and its merge (Engine member; the kernels are in attend_chunk.hip)
 #include "engine_internal.hpp"
+#include "chunk_split.hpp"
 
 namespace speckv {
 
@@ -11,15 +13,20 @@ namespace speckv {
 // to its device twin, so the call cannot be captured into a HIP graph; nothing is allocated once the slots are large enough.
 // `mask` (the masked entry; the causal one passes none): per query position mask->words words of visible HELD positions, a device
 // array the kernel reads in place -- nothing about it is staged.
+// `n_splits` (the split entry; the other two pass none = every sequence whole): 1 every sequence whole, N > 1 that many pieces per
+// sequence, 0 the library's rule (chunk_split.hpp).  A plan of one piece everywhere issues the launch of the other two entries; any
+// other plan issues the piece launch and the merge behind it on `s`, the partials in a scratch buffer of their own (s_chunk_: a
+// chunk call does not order itself behind the decode entries' s_attn_ on another stream).
 int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
                          const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new, const void* d_v_new, uint64_t seq_stride,
                          uint64_t pos_stride, const int32_t* tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride,
-                         float sm_scale, float* d_out, float* d_lse, hipStream_t s, const ChunkMask* mask)
+                         float sm_scale, float* d_out, float* d_lse, hipStream_t s, const ChunkMask* mask, const uint32_t* n_splits)
 {
-    const char* entry = mask ? "speckv_ext_attend_chunk_masked" : "speckv_ext_attend_chunk";
+    const char* entry = n_splits ? "speckv_ext_attend_chunk_split" : mask ? "speckv_ext_attend_chunk_masked" : "speckv_ext_attend_chunk";
     if (null_) return no_data_path(entry);
     if (!s || !handles || !pos_end || !n_q || !d_q_f16 || !d_k_new || !d_v_new || !d_out) return SPECKV_ERR_INVAL;
     if (rows_per_pos == 0 || rows_per_pos > 16u || (rows_per_pos & (rows_per_pos - 1u)) || C == 0) return SPECKV_ERR_INVAL;
+    if (n_splits && *n_splits > kChunkSplitsMax) return SPECKV_ERR_INVAL;
     // a row's words cover held positions 0 .. C (a tail and C new positions)
     if (mask && (!mask->d_mask || reinterpret_cast<uintptr_t>(mask->d_mask) % 4u || mask->words < (static_cast<uint64_t>(C) + 32u) / 32u))
         return SPECKV_ERR_INVAL;
@@ -63,20 +70,41 @@ int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer
     uint64_t n_blocks = 0;
     for (uint32_t i = 0; i < n_seq; ++i) n_blocks += (n_q[i] + per_block - 1u) / per_block;
     if (n_blocks * 8u > 0x7FFFFFFFull) return SPECKV_ERR_INVAL;
+    // the pieces of every sequence (all 1: today's launch) -- from the arguments alone, so the plan holds across descriptor_slot
+    std::vector<uint32_t> pieces(n_seq, 1u), tpp(n_seq, 0u);
+    uint64_t n_items = n_blocks;
+    bool split = false;
+    if (n_splits && *n_splits != 1u) {
+        if (!chunk_split_plan(n_seq, pos_end, n_q, rows_per_pos, *n_splits, cus(), pieces.data(), tpp.data())) return SPECKV_ERR_INVAL;
+        n_items = 0;
+        for (uint32_t i = 0; i < n_seq; ++i) {
+            n_items += static_cast<uint64_t>((n_q[i] + per_block - 1u) / per_block) * pieces[i];
+            split = split || (n_q[i] && pieces[i] > 1u);
+        }
+        if (n_items * 8u > 0x7FFFFFFFull) return SPECKV_ERR_INVAL;
+    }
     DeviceScope device_scope(device_);
     const size_t bytes = static_cast<size_t>(n_seq) * sizeof(ChunkSeq);
     int slot = 0;
     void *staged = nullptr, *d_slot = nullptr;
     RC_TRY(descriptor_slot(bytes, &slot, &staged, &d_slot));      // may release the ABI lock: every sequence is judged again
     RC_TRY(check());
-    uint32_t first_block = 0;
+    uint8_t* part = nullptr;
+    if (split) {                                                   // items x 8 heads x (32 KiB + 512 B); nothing is launched without it
+        part = static_cast<uint8_t*>(scratch(s_chunk_, static_cast<size_t>(n_items) * 8u * kChunkPartBytes, s));
+        if (!part) return SPECKV_ERR_NOMEM;
+    }
+    uint32_t first_block = 0, first_item = 0;
     for (uint32_t i = 0; i < n_seq; ++i) {
         const Layout& L = as[i]->layout;
         const uint64_t k_first = static_cast<uint64_t>(layer) * L.num_tokens;
         const int32_t tail = tail_idx && tail_idx[i] >= 0 ? tail_idx[i] : -1;
+        const uint32_t blocks = (n_q[i] + per_block - 1u) / per_block;
+        if (!split) { pieces[i] = 1u; tpp[i] = chunk_pool_tiles(pos_end[i]); }
         static_cast<ChunkSeq*>(staged)[i] = ChunkSeq{as[i]->row, pos_end[i], n_q[i], first_block, k_first, k_first + L.num_tokens / 2u,
-                                                     tail, tail >= 0 ? 1u : 0u};
-        first_block += (n_q[i] + per_block - 1u) / per_block;
+                                                     tail, tail >= 0 ? 1u : 0u, pieces[i], tpp[i], first_item, 0u};
+        first_block += blocks;
+        first_item += blocks * pieces[i];
     }
     for (auto& w : write_evs_)
         if (w.s != s) HIP_TRY(hipStreamWaitEvent(s, w.ev, 0));
@@ -103,6 +131,8 @@ int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer
     ca.scheme = scheme;
     ca.mask = mask ? mask->d_mask : nullptr;
     ca.mask_words = mask ? mask->words : 0u;
+    ca.part = part;
+    ca.n_items = first_item;
     HIP_TRY(launch_attend_chunk(ca, s));
     for (uint32_t i = 0; i < n_seq; ++i) note_use(as[i], s);     // speckv_free waits for this stream
     if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel

@@ -150,6 +150,9 @@ hipError_t launch_copy_records(const CopyArgs& a, hipStream_t s);
 // positions (row tail_idx of the tail arrays) and n_q new positions.  first_block = the query blocks (ceil(n_q / (64 / rows_per_pos)))
 // of the sequences in front of this one (the host's exclusive prefix: the kernel finds the sequence of a flat block index by binary
 // search and needs no atomics).
+// Split form (ChunkArgs::part): the sequence's pool tiles are cut into n_pieces >= 1 pieces of tiles_per_piece tiles (chunk_split.hpp),
+// a work item is (query block, piece) with the piece fast, first_item = the items (blocks x pieces) of the sequences in front of this
+// one, found by the same search; first_block serves the merge.
 struct ChunkSeq {
     uint32_t table_row;
     uint32_t pos_end;
@@ -159,7 +162,14 @@ struct ChunkSeq {
     uint64_t v_first;
     int32_t  tail_idx;
     uint32_t base;
+    uint32_t n_pieces;
+    uint32_t tiles_per_piece;
+    uint32_t first_item;
+    uint32_t reserved;
 };
+// A partial of the split form, one per (work item, kv head): the un-normalised accumulator [64 rows][128] fp32 in the row order of
+// `out`, then (running max, running sum) per row in the log2 domain.
+constexpr size_t kChunkPartAccBytes = 64u * 128u * sizeof(float), kChunkPartBytes = kChunkPartAccBytes + 64u * 2u * sizeof(float);
 struct ChunkArgs {
     const ChunkSeq* seqs;             // device array
     const DevAlloc* tab;              // the device allocation table
@@ -180,8 +190,14 @@ struct ChunkArgs {
     // t < base + j + 1 as before; a row whose own bit base + j is clear is dead: not computed to the end, not written
     const uint32_t* mask;
     uint32_t        mask_words;       // words per query position, >= (C + 1 + 31) / 32
+    // split form (null: one workgroup walks all of a sequence's tiles and writes out / lse itself): n_items * heads partials of
+    // kChunkPartBytes, partial (item, head) at part + (item * heads + head) * kChunkPartBytes; n_items = the sum of blocks x pieces
+    uint8_t*        part;
+    uint32_t        n_items;
 };
-// ONE launch of n_blocks * heads workgroups; nothing is launched for n_blocks == 0
+// part == null: ONE launch of n_blocks * heads workgroups.  Otherwise TWO: n_items * heads workgroups that write their partials, then
+// the merge (k_chunk_combine) over n_blocks * heads, which reads a row's partials in ascending piece order and writes out / lse.
+// Nothing is launched for n_blocks == 0.
 hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s);
 
 // Source / destination description of one codec launch.  Exactly one of

@@ -675,6 +675,42 @@ class SpeckvKVConnector:
         return counts, firsts
 
     @staticmethod
+    def chunk_pieces(n_new: Sequence[int], stored: Sequence[int], rows_per_pos: int, splits: int = 0, n_cus: int = 256):
+        """How attend_chunk(splits=...) cuts the stored positions of every request into pieces (speckv_ext_chunk_split_plan restated):
+        request b with stored[b] positions (its length; an odd last position is held, not stored) has n_pool = ceil((stored[b] & ~1)
+        / 32) pool tiles of 32 positions.  splits 1: one piece each.  splits N in 2..64 (forced): min(N, max(1, n_pool)) pieces -- from
+        the request alone.  splits 0 (the library's rule, from the whole step): with G0 = 8 x the step's query blocks (chunk_blocks)
+        and target = 3 x n_cus, one piece each while G0 > target / 2, otherwise clamp(n_pool // 32, 1, min(target // G0, 64)).
+        Then tiles_per_piece = ceil(n_pool / pieces) and pieces = ceil(n_pool / tiles_per_piece), so no piece is empty; piece p walks
+        pool tiles [p * tpp, min((p + 1) * tpp, n_pool)) and the last piece also the held positions; a request without pool tiles
+        has one piece of 0 tiles.  Returns (pieces, tiles_per_piece, firsts): firsts = the exclusive prefix of blocks x pieces, the
+        rule by which the kernel finds (request, block, piece) of a flat work item -- the last request whose prefix is <= the item,
+        block = rest // pieces, piece = rest % pieces.  Pure python, no device."""
+        import numbers
+        if isinstance(splits, bool) or not isinstance(splits, numbers.Integral) or not 0 <= splits <= 64:
+            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
+        if isinstance(n_cus, bool) or not isinstance(n_cus, numbers.Integral) or n_cus < 0:
+            raise ValueError("n_cus: the compute units of the device (0: 256)")
+        counts, _ = SpeckvKVConnector.chunk_blocks(n_new, rows_per_pos)
+        stored = list(stored)
+        if len(stored) != len(counts) or any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or s < 0 for s in stored):
+            raise ValueError("stored: one count of positions >= 0 per request")
+        most = int(splits)
+        if splits == 0:
+            g0, target = 8 * sum(counts), 3 * (int(n_cus) or 256)
+            most = 1 if g0 == 0 or g0 >= target else min(target // g0, 64)
+        pieces, tiles, firsts, total = [], [], [], 0
+        for blocks, s in zip(counts, stored):
+            n_pool = ((int(s) & ~1) + 31) // 32
+            p = min(max(n_pool // 32 if splits == 0 else n_pool, 1), most)
+            tpp = -(-n_pool // p)
+            pieces.append(-(-n_pool // tpp) if tpp else 1)
+            tiles.append(tpp)
+            firsts.append(total)
+            total += blocks * pieces[-1]
+        return pieces, tiles, firsts
+
+    @staticmethod
     def _chunk_tree_parents(parents, batch):
         """_tree_parents without its bound on the node count: parents as one list per request ([S] is the same tree for every request,
         [batch][S] one tree each), every entry an int in -1 .. j-1, S >= 1 nodes, the same count for every request."""
@@ -745,7 +781,8 @@ class SpeckvKVConnector:
             self._chunk_tree_key, self._chunk_tree_masks = tkey, torch.from_numpy(words).pin_memory().to("cuda", non_blocking=True)
         return self._chunk_tree_masks
 
-    def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None):
+    def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None,
+                     splits=1):
         """One layer of a step that carries a CHUNK of S new positions per request, S >= 1 with no bound but max_tokens -- chunked prefill
         of a long prompt, the differing suffix behind fork(), a prompt continued after truncate().  Shapes and meaning are those of
         attend_spec without `parents`: q [batch][S][heads][rows_per_pos][dim] fp16 (rows_per_pos 1, 2, 4, 8 or 16), k_new / v_new
@@ -756,17 +793,29 @@ class SpeckvKVConnector:
         ONE launch (speckv_ext_attend_chunk): a workgroup takes 64 // rows_per_pos positions of one kv head and walks the request's
         records once for them (chunk_blocks), k_new / v_new are read in place through their strides.  The query stays fp16 in every
         pool format (attend() and attend_spec() over FP8 and MXFP4 pools quantise it).
-        When to use which: attend_spec splits the stored positions across the chip and is the route for short speculative steps
-        (S <= 16); attend_chunk does not split positions, so few positions over a long context leave most of the chip idle, while a
-        chunk fills it with query blocks.  The crossover between the two is not measured yet: profiles/tools/chunk_prefill_bench.py
-        times both at S = 16 and writes profiles/chunk_prefill.txt.
+        splits: 1 (the default) = no split over the stored positions: exactly the launch and the bits described above.  0 = the
+        library's rule (chunk_pieces): the stored positions of a request are cut into pieces that run side by side, and a second
+        launch merges them, whenever the step's query blocks alone would leave most of the chip idle; a step that fills the chip is
+        issued as with splits=1, bit for bit.  N in 2..64 forces min(N, pool tiles) pieces per request.  With pieces a row's bits
+        depend on its request's piece count (within the same error bound); under 0 that count depends on the whole step, under a
+        forced N on the request alone.  Works with and without `parents` (speckv_ext_attend_chunk_split).  Anything else is a
+        ValueError before any library call.
+        When to use which: few positions, or a tree, over a LONG context -- a fork's short suffix, the last short chunk of a prompt, a
+        draft tree of more than 16 nodes -- should pass splits=0: without pieces such a step leaves most of the chip idle.  A chunk
+        that fills the chip with query blocks is not split by the rule, so splits=0 costs it nothing.  attend_spec remains the route
+        for chains of S <= 16 positions (it quantises the query for FP8 and MXFP4 pools and splits the stored positions itself);
+        profiles/tools/chunk_split_bench.py times the routes side by side.
         parents (see chunk_tree_masks): the S new positions form a TREE of drafts of any size instead of a chain -- node j sees what the
         request holds, its ancestors and itself, not its siblings.  Still ONE launch (speckv_ext_attend_chunk_masked) with a mask table
         built once per (batch, lengths, tree, n_new) and shared by the layers' calls; attend_spec(parents=...) stops at 16 nodes and
         reads the records once per 16 // rows_per_pos of them.  Rows of dead nodes (>= n_new[b], or below one) are zeros.  Afterwards
         commit(req_ids, k_new, v_new, nodes=accepted path) stores a root-to-node path of a tree of any size."""
+        import numbers
         import numpy as np
         import torch
+        if isinstance(splits, bool) or not isinstance(splits, numbers.Integral) or not 0 <= splits <= 64:
+            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
+        splits = int(splits)
         if self.scheme not in FUSED:
             raise ValueError("attend_chunk() needs an FP8, INT4 or MXFP4 pool")
         if len(q.shape) != 5:
@@ -814,6 +863,14 @@ class SpeckvKVConnector:
                         rank += 1
                 kt = self._fold_k.data_ptr() + 2 * layer * row if rank else 0
                 vt = self._fold_v.data_ptr() + 2 * layer * row if rank else 0
+                if splits != 1:
+                    masks = None if parents is None else self._chunk_tree_table(key, reqs, parents, live, S)
+                    self.lib.attend_chunk_split(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                                np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
+                                                v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
+                                                self.L * row, 0 if masks is None else masks.data_ptr(), 0 if masks is None else masks.shape[2],
+                                                splits, sm_scale, out.data_ptr(), 0, st.cuda_stream)
+                    return out
                 if parents is not None:
                     masks = self._chunk_tree_table(key, reqs, parents, live, S)
                     self.lib.attend_chunk_masked(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),

@@ -68,6 +68,10 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_chunk_masked": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                        c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p,
                                        c_void_p],
+    "speckv_ext_attend_chunk_split": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
+                                      c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p,
+                                      c_void_p, c_void_p],
+    "speckv_ext_chunk_split_plan": [c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
     "speckv_ext_bind_request": [c_uint32, c_uint64, c_uint32],
@@ -120,6 +124,7 @@ _EXT_SIGNATURES = {
 
 
 EXT_ABI_VERSION = 6        # SPECKV_EXT_ABI_VERSION of include/speckv_ext.h
+CHUNK_SPLITS_MAX = 64      # SPECKV_CHUNK_SPLITS_MAX: the most pieces speckv_ext_attend_chunk_split cuts a sequence's stored positions into
 HELD_MAX = 17              # SPECKV_HELD_MAX: positions speckv_ext_attend_fold_held takes per sequence (one left over + 16 new ones)
 
 
@@ -337,6 +342,30 @@ class SpeckvLib:
         self._ext("speckv_ext_attend_chunk_masked", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
                   seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, c_void_p(d_mask or None),
                   mask_words, sm_scale, c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+
+    def attend_chunk_split(self, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx,
+                           d_k_tail, d_v_tail, tail_stride, d_mask, mask_words, n_splits, sm_scale, d_out, d_lse, stream):
+        """attend_chunk (d_mask 0) / attend_chunk_masked with the stored positions of a sequence split across the chip
+        (speckv_ext_attend_chunk_split): n_splits 1 = whole sequences (the other two entries' launch and bits), N = that many pieces
+        per sequence (from the sequence alone), 0 = the library's rule (chunk_split_plan; from the whole call).  With pieces: a piece
+        launch and a merge on `stream`; a row's bits depend on its sequence's piece count.  The other arguments as
+        attend_chunk_masked."""
+        n = len(handles)
+        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
+        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
+        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
+        self._ext("speckv_ext_attend_chunk_split", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
+                  seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, c_void_p(d_mask or None),
+                  mask_words, n_splits, sm_scale, c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+
+    def chunk_split_plan(self, pos_end, n_q, rows_per_pos, n_splits=0, n_cus=0):
+        """The piece rule of attend_chunk_split (speckv_ext_chunk_split_plan; works without init): (pieces, tiles_per_piece), one entry
+        per sequence.  n_cus 0: the engine's device, 256 without an engine."""
+        n = len(pos_end)
+        pe, nq = (c_uint32 * n)(*[int(x) for x in pos_end]), (c_uint32 * n)(*[int(x) for x in n_q])
+        pieces, tpp = (c_uint32 * n)(), (c_uint32 * n)()
+        self._ext("speckv_ext_chunk_split_plan", n, pe, nq, rows_per_pos, n_splits, n_cus, pieces, tpp)
+        return list(pieces), list(tpp)
 
     def read(self, handle, offset, dst_ptr, nbytes, on_device):
         self._ext("speckv_ext_read", handle, offset, c_void_p(dst_ptr), nbytes, int(on_device))

@@ -760,6 +760,57 @@ speckv_status_t speckv_ext_attend_chunk_masked(uint32_t n_seq, const speckv_hand
                                                const uint32_t* d_mask, uint32_t mask_words,
                                                float sm_scale, float* d_out, float* d_lse, void* stream);
 
+/* speckv_ext_attend_chunk_split: speckv_ext_attend_chunk / speckv_ext_attend_chunk_masked with the STORED positions of a sequence
+ * split across the chip -- a step of a few positions, a small draft tree (of more than 16 nodes, which the decode entries refuse), a
+ * fork's short suffix or a prompt's last short chunk over a LONG context, where the query blocks alone (8 kv heads x ceil(n_q /
+ * (64 / rows_per_pos)) workgroups per sequence) leave most of the compute units idle.  ONE entry for the causal and the tree form: the
+ * arguments of speckv_ext_attend_chunk_masked in the same order, with n_splits in front of sm_scale; d_mask == NULL is the causal
+ * form (mask_words is then ignored).  Everything said at those two entries holds -- layouts, the fp16 query, liveness, rows that are
+ * not live are NOT WRITTEN, ordering, NOT capturable into a HIP graph, what is refused.
+ *   n_splits == 1 : every sequence whole.
+ *   n_splits == N, 2 <= N <= SPECKV_CHUNK_SPLITS_MAX (forced): sequence i is cut into min(N, max(1, n_pool_i)) pieces, n_pool_i =
+ *                   ceil(pos_end[i] / 32) pool tiles, evened out so that no piece is empty (speckv_ext_chunk_split_plan).
+ *   n_splits == 0 : the library's rule (speckv_ext_chunk_split_plan): no pieces while the query blocks of the call fill the chip,
+ *                   otherwise as many as still fit one round of three workgroups per compute unit, no piece under 32 pool tiles.
+ * When the plan gives every sequence ONE piece, the call issues exactly the launch of speckv_ext_attend_chunk / _masked: no scratch,
+ * no merge, the same output bits.  Otherwise it issues TWO launches on `stream`: the pieces (piece p of a sequence walks its share of
+ * the pool tiles, the last piece also the held positions) write un-normalised partials to a scratch buffer of the engine, and a merge
+ * combines a row's partials in ascending piece order (fp32; deterministic: the same call gives the same bits, whatever the
+ * scheduling).  The buffer grows on demand to (sum of query blocks x pieces) x 8 x 33280 bytes and is kept; a call on another stream
+ * than the previous split call's is ordered behind that call.
+ * WITH n_splits != 1 A ROW'S BITS DEPEND ON THE PIECE COUNT of its sequence (another summation order; the values stay within the
+ * entry's error bound).  Under n_splits == 0 the piece count depends on the WHOLE CALL -- the other sequences, their n_q,
+ * rows_per_pos, the device -- so a row's bits may depend on which other sequences share the call.  A forced count depends on the
+ * sequence alone (its pos_end), so under it a row's bits do not depend on its batch mates.
+ *   SPECKV_ERR_INVAL    as speckv_ext_attend_chunk (and, with a mask, as speckv_ext_attend_chunk_masked: d_mask not 4-byte aligned,
+ *                       mask_words < (C + 1 + 31) / 32), and n_splits > SPECKV_CHUNK_SPLITS_MAX -- nothing is launched
+ *   SPECKV_ERR_NOMEM    the scratch buffer could not grow -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle */
+#define SPECKV_CHUNK_SPLITS_MAX 64u
+speckv_status_t speckv_ext_attend_chunk_split(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer,
+                                              const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                              const uint32_t* pos_end, const uint32_t* n_q /* host arrays [n_seq] */,
+                                              const void* d_k_new, const void* d_v_new, uint64_t seq_stride_elems,
+                                              uint64_t pos_stride_elems,
+                                              const int32_t* tail_idx /* host [n_seq], < 0 = none; may be NULL */,
+                                              const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,
+                                              const uint32_t* d_mask /* NULL: causal */, uint32_t mask_words, uint32_t n_splits,
+                                              float sm_scale, float* d_out, float* d_lse, void* stream);
+
+/* The piece rule of speckv_ext_attend_chunk_split as a pure function (the same body the entry calls): out_pieces[i] pieces of
+ * out_tiles_per_piece[i] pool tiles (32 positions) for sequence i; piece p walks tiles [p * tpp, min((p + 1) * tpp, n_pool_i)), the
+ * last piece also the held positions; a sequence without pool tiles has one piece of 0 tiles.
+ *   n_splits == 1: one piece each.   n_splits == N > 1: pieces_i = min(N, max(1, n_pool_i)).
+ *   n_splits == 0: G0 = 8 x the sum of ceil(n_q[i] / (64 / rows_per_pos)), target = 3 x n_cus (3 = resident workgroups per compute
+ *   unit at the kernel's occupancy; n_cus == 0: the engine's device, 256 without an engine).  G0 >= target (or G0 == 0): one piece
+ *   each; otherwise pieces_i = clamp(n_pool_i / 32, 1, min(floor(target / G0), SPECKV_CHUNK_SPLITS_MAX)): the pieces of a call fit
+ *   one round of resident workgroups (so G0 > target / 2 is one piece each, too).
+ *   Then tpp_i = ceil(n_pool_i / pieces_i) and pieces_i = ceil(n_pool_i / tpp_i): no piece is empty.
+ * SPECKV_ERR_INVAL: NULL arrays with n_seq > 0, a rows_per_pos other than 1, 2, 4, 8, 16, n_splits > SPECKV_CHUNK_SPLITS_MAX.
+ * Works without speckv_init. */
+speckv_status_t speckv_ext_chunk_split_plan(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* n_q, uint32_t rows_per_pos,
+                                            uint32_t n_splits, uint32_t n_cus, uint32_t* out_pieces, uint32_t* out_tiles_per_piece);
+
 #ifdef __cplusplus
 }
 #endif
