@@ -340,7 +340,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // d = 8c + t (t = 0..7), i.e. lane (c, kb) holds out[row c][32kb + 8i + t] in acc[t][i].
 //
 // The output MFMAs accumulate in place (C = acc).  acc is kept in units of the current tile's V
-// reference scale vref_t (its largest V page scale; unchanged when that is 0), so the V page scales
+// reference scale vref_t (its largest V page scale among the pages inside the range; unchanged when that is 0), so the V page scales
 // ride on the f16 weights as vs/vref_t <= 1 and the only per-tile fix-up of acc is one multiply by
 // alpha * vref_{t-1}/vref_t.
 
@@ -613,7 +613,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const uint32_t pg = tile * 16u + ((j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2));
-                    if (pg >= a.n_pages || pg < a.skip_pages) sc[j] = -INFINITY;
+                    // (a masked page's V scale leaves the tile's reference scale below as well: the page may hold a stale record of any magnitude)
+                    if (pg >= a.n_pages || pg < a.skip_pages) { sc[j] = -INFINITY; vs4[j >> 1] = 0.0f; }
                 }
             }
             if (CLS) {                                                       // pages of this tile past the end of its class
@@ -625,6 +626,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
                         const uint32_t pg = (j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2);
                         if (pg >= have) sc[j] = -INFINITY;
                     }
+                    // (... and their V scales, which the lane holds by slot until cls_scales4 below hands them out: the surplus slots fetch the
+                    //  class's last record again, or a stale one)
+                    const uint32_t sl = lane & 15u;
+                    if ((sl & 2u) * 4u + (sl >> 2) * 2u + (sl & 1u) >= have) vs_raw = 0.0f;
                 }
                 if (++cc_m == cls_m) { cc_m = 0u; ++cc_cls; }
             }
@@ -1042,7 +1047,7 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const uint32_t pg = (j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2);
-                        if (pg >= have) sc[j] = -INFINITY;
+                        if (pg >= have) { sc[j] = -INFINITY; vs4[j >> 1] = 0.0f; }      // (the V scale too: see k_attend_fp8_linear)
                     }
                 }
                 if (++cc_m == cls_m) { cc_m = 0u; ++cc_cls; }
@@ -1051,7 +1056,7 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const uint32_t pg = tile * 16u + ((j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2));
-                    if (pg >= a.n_pages || pg < a.skip_pages) sc[j] = -INFINITY;
+                    if (pg >= a.n_pages || pg < a.skip_pages) { sc[j] = -INFINITY; vs4[j >> 1] = 0.0f; }
                 }
             }
             // ---- online softmax of query row c

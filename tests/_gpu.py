@@ -282,9 +282,10 @@ class HeadChecker:
             lse[idx] = (mx + np.log(l)).reshape(m, G)
         return out, lse, mag, delta
 
-    def check_rows(self, got, got_lse, q16, head, npos, sm, what, tail=None, pos_begin=0):
+    def check_rows(self, got, got_lse, q16, head, npos, sm, what, tail=None, pos_begin=0, worst=None):
         """every row of M members' head `head` against want_rows, with check()'s bound: |err| <= (2e-3 + 2 delta) sum p|v| + 1e-6,
-        |lse err| <= 2e-3 + delta; a member with no position (and no tail) exactly 0.  got_lse None: a call without a log-sum-exp, out only."""
+        |lse err| <= 2e-3 + delta; a member with no position (and no tail) exactly 0.  got_lse None: a call without a log-sum-exp, out only.
+        worst: a list that receives the largest err / tol of out and of lse (0.0 where nothing was compared) BEFORE anything is asserted."""
         want, wlse, mag, delta = self.want_rows(q16, head, npos, sm, tail, pos_begin)
         got = np.asarray(got, np.float64)
         npos = np.asarray(npos)
@@ -293,6 +294,10 @@ class HeadChecker:
         live = ~empty
         err = np.abs(got[live] - want[live])
         tol = (2e-3 + 2 * delta[live])[:, None, None] * mag[live] + 1e-6
+        if worst is not None:
+            lerr = np.abs(np.asarray(got_lse, np.float64)[live] - wlse[live]) / (2e-3 + delta[live])[:, None] if got_lse is not None else np.zeros(0)
+            with np.errstate(invalid="ignore"):
+                worst.append(max(float(np.nan_to_num(err / tol, nan=np.inf).max(initial=0.0)), float(np.nan_to_num(lerr, nan=np.inf).max(initial=0.0))))
         bad = ~(err <= tol)
         assert not bad.any(), (what, "out", [int(i) for i in np.nonzero(live)[0][np.argwhere(bad)[0][:1]]], int(bad.sum()),
                                float((err / (mag[live] + 1e-9)).max()))
