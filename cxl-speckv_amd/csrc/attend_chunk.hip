@@ -54,9 +54,24 @@
 // stands, [64 rows][128] fp32 in the row order of `out`, and (m_run, l_run) per row beside it, through vector stores; dead rows write
 // nothing.  k_chunk_combine, launched behind it on the same stream, merges a row's partials in ascending piece order.  The piece
 // bounds are wave-uniform (scalar registers): the SPLIT instances cost no vector registers worth mentioning.
+//
+// Window form (WINDOW, ChunkArgs::window = W >= 1; speckv_ext_attend_chunk_window: a local layer of a model that interleaves
+// sliding-window and global layers).  The same body, never together with MASKED.  Query position j at the absolute position
+// P = pos_end + base + j sees the absolute positions [lo(j), P], lo(j) = max(0, P + 1 - W) (chunk_window.hpp): a stored position t
+// iff lo(j) <= t < pos_end, a held position t iff pos_end + t >= lo(j) and t <= base + j.  The block walks [t_first, n_tiles),
+// t_first = the tile of lo(j_first): exactly the tiles that hold a position a live row of the block sees, never more than
+// ceil((W + 64 / rows_per_pos - 1) / 32) + 2 of them; the prologue stages that tile and the buffer parity counts from it.  A score's
+// test gains the row's lower bound, kept as ONE absolute position per row and re-based per part (two compares).  What NO row of the
+// block sees -- positions below lo(j_first) inside the first tile -- is staged as ZEROS like the positions beyond the upper bounds,
+// down to the one position of a page an odd bound cuts; what only some rows see is real, finite data weighed 0.  Rows of later
+// positions see nothing in the block's first tile(s): the m_use path of the tree form.  A wave skips the products of tiles wholly
+// below its first row's bound, the mirror of wave_t_last.  Split form: the pieces cut the pool tiles from ChunkSeq::first_tile (the
+// first pool tile block 0 sees) on, clipped from below by the block's t_first; a piece that is not the last can be EMPTY for later
+// blocks: it stages nothing and writes m = -inf, l = 0, zeros for its live rows, which k_chunk_combine weighs 0 exactly.
 #include "kernels.hpp"
 #include "codec_device.hpp"          // pack_half2, half_bits_to_float
 #include "attend_device.hpp"
+#include "chunk_window.hpp"
 
 namespace speckv {
 namespace {
@@ -170,7 +185,7 @@ __device__ __forceinline__ Raw load_held(const _Float16* r0, const _Float16* r1)
     return r;
 }
 
-template <int SCHEME, bool MASKED, bool SPLIT>
+template <int SCHEME, bool MASKED, bool SPLIT, bool WINDOW>
 __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
 {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufElems];
@@ -204,8 +219,16 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     const uint32_t n_pool = (pos_end + 31u) >> 5, n_held = ((base + j_last) >> 5) + 1u, n_tiles = n_pool + n_held;
     const uint32_t n_pages = pos_end >> 1, held_n = base + n_q;
     // SPLIT: piece p walks the pool tiles [p tpp, (p + 1) tpp); the LAST piece goes on through the held tiles, as the whole walk does
-    const uint32_t t_begin = SPLIT ? piece * tpp : 0u;
-    const uint32_t t_end = !SPLIT || piece + 1u == n_pieces ? n_tiles : (t_begin + tpp < n_pool ? t_begin + tpp : n_pool);
+    // WINDOW: the block walks from the tile of its first row's lower bound (chunk_window.hpp); the pieces cut the pool tiles from the
+    // sequence's first_tile on and are clipped from below by the block's first tile -- a piece that is not the last can be EMPTY
+    // (t_begin >= t_end): it stages nothing and writes the partial of a piece that saw nothing
+    const uint32_t piece_first = (SPLIT && WINDOW ? static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(sq->first_tile)) : 0u) + piece * tpp;
+    const uint32_t t_first = WINDOW ? chunk_window_first_tile(pos_end, base, j_first, a.window) : 0u;
+    const uint32_t t_begin = WINDOW ? (piece_first > t_first ? piece_first : t_first) : SPLIT ? piece * tpp : 0u;
+    const uint32_t t_end = !SPLIT || piece + 1u == n_pieces ? n_tiles : (piece_first + tpp < n_pool ? piece_first + tpp : n_pool);
+    // WINDOW: what no row of the block sees, as a stored position (lo_pool) and as a held one (lo_held): staged as zeros
+    const uint32_t lo_pool = WINDOW ? chunk_window_lo(pos_end, base, j_first, a.window) : 0u;
+    const uint32_t lo_held = lo_pool > pos_end ? lo_pool - pos_end : 0u;
 
     const PageEntry* entries = reinterpret_cast<const PageEntry*>(ck_uniform(reinterpret_cast<uint64_t>(a.tab[sq->table_row].entries)));
     const uint64_t k_first = ck_uniform(sq->k_first), v_first = ck_uniform(sq->v_first);
@@ -243,22 +266,26 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     const uint32_t wave_j_last = j_first + (16u * wave + 15u) / rpp;
     const uint32_t wave_t_last = base + (wave_j_last < j_last ? wave_j_last : j_last);
     const bool wave_live = j_first + (16u * wave) / rpp < n_q;
+    // WINDOW: the row's lower bound as an absolute position (re-based per part in front of the test), and the lowest bound of the
+    // wave's rows, its first row's: tiles wholly below it are skipped by the wave as the tiles behind wave_t_last are
+    const uint32_t row_lo = WINDOW ? chunk_window_lo(pos_end, base, j, a.window) : 0u;
+    const uint32_t wave_lo = WINDOW ? chunk_window_lo(pos_end, base, j_first + (16u * wave) / rpp, a.window) : 0u;
 
     Raw rk, rv;
     const auto load_tile = [&](uint32_t tile) {
         if (tile < n_pool) {
             const uint32_t page = 16u * tile + pp;
-            const bool live = page < n_pages;
+            const bool live = page < n_pages && (!WINDOW || 2u * page + 1u >= lo_pool);
             rk = load_pool<SCHEME>(entries + k_first + page, p0, live);
             rv = load_pool<SCHEME>(entries + v_first + page, p0, live);
         } else {
             const uint32_t t0 = 32u * (tile - n_pool) + 2u * pp;
             const _Float16 *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr;
-            if (t0 < held_n) {
+            if (t0 < held_n && (!WINDOW || t0 >= lo_held)) {
                 if (t0 < base) { k0 = k_tail; v0 = v_tail; }
                 else { const uint64_t o = static_cast<uint64_t>(t0 - base) * a.pos_stride; k0 = k_new + o; v0 = v_new + o; }
             }
-            if (t0 + 1u < held_n) { const uint64_t o = static_cast<uint64_t>(t0 + 1u - base) * a.pos_stride; k1 = k_new + o; v1 = v_new + o; }
+            if (t0 + 1u < held_n && (!WINDOW || t0 + 1u >= lo_held)) { const uint64_t o = static_cast<uint64_t>(t0 + 1u - base) * a.pos_stride; k1 = k_new + o; v1 = v_new + o; }
             rk = load_held(k0 ? k0 + 8u * c : nullptr, k1 ? k1 + 8u * c : nullptr);
             rv = load_held(v0 ? v0 + 8u * c : nullptr, v1 ? v1 + 8u * c : nullptr);
         }
@@ -268,6 +295,10 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
         if (tile < n_pool) {
             decode_pool<SCHEME>(rk, p0, ke, ko);
             decode_pool<SCHEME>(rv, p0, ve, vo);
+            if (WINDOW && 2u * (16u * tile + pp) < lo_pool) {               // the page the bound cuts: its even position is below it
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; ++k) ke[k] = ve[k] = 0u;
+            }
         } else {
             ke[0] = rk.a.x; ke[1] = rk.a.y; ke[2] = rk.a.z; ke[3] = rk.a.w;
             ko[0] = rk.b.x; ko[1] = rk.b.y; ko[2] = rk.b.z; ko[3] = rk.b.w;
@@ -290,16 +321,19 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     float m_run = -__builtin_inff(), l_run = 0.0f;            // log2 domain
     const float scale2 = a.sm_scale * kLog2e;
 
-    load_tile(t_begin);
-    store_tile(t_begin, lds);
-    __syncthreads();
+    if (!(SPLIT && WINDOW) || t_begin < t_end) {              // (workgroup-uniform)
+        load_tile(t_begin);
+        store_tile(t_begin, lds);
+        __syncthreads();
+    }
     for (uint32_t tile = t_begin; tile < t_end; ++tile) {
         _Float16* buf = lds + ((tile - t_begin) & 1u) * kBufElems;
         const bool more = tile + 1u < t_end;
         if (more) load_tile(tile + 1u);
         const bool held = tile >= n_pool;
         const uint32_t t_base = held ? 32u * (tile - n_pool) : 32u * tile;
-        if (wave_live && (!held || t_base <= wave_t_last)) {
+        const uint32_t wave_lo_part = held ? (wave_lo > pos_end ? wave_lo - pos_end : 0u) : wave_lo;
+        if (wave_live && (!held || t_base <= wave_t_last) && (!WINDOW || t_base + 31u >= wave_lo_part)) {
             // tree form: the row's word of this held tile (all lanes of a row read the same word), in flight under the products
             uint32_t mword = 0xFFFFFFFFu;
             if (MASKED && held) mword = mrow ? ck_ld<uint32_t>(mrow + (t_base >> 5)) : 0u;
@@ -316,6 +350,7 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
                 sc[hf] = s4;
             }
             const uint32_t limit = held ? base + j + 1u : pos_end;           // positions of this part the row sees: [0, limit)
+            const uint32_t lower = held ? (row_lo > pos_end ? row_lo - pos_end : 0u) : row_lo;     // WINDOW: [lower, limit) of this part
             uint32_t vis = 0u;
             if (MASKED) {
                 const uint32_t n_seen = limit > t_base ? limit - t_base : 0u;
@@ -326,7 +361,7 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t t = t_base + 16u * (i >> 2) + 4u * g + (i & 3u);
                 // tree form: bit t & 31 of the word (t_base is a multiple of 32), the causal bound folded into the word
-                const bool seen = MASKED ? (vis >> (16u * (i >> 2) + (i & 3u))) & 1u : t < limit;
+                const bool seen = MASKED ? (vis >> (16u * (i >> 2) + (i & 3u))) & 1u : WINDOW ? t >= lower && t < limit : t < limit;
                 sv[i] = seen ? sc[i >> 2][i & 3u] * scale2 : -__builtin_inff();
                 mx = fmaxf(mx, sv[i]);
             }
@@ -441,15 +476,17 @@ template <int SCHEME>
 hipError_t launch_chunk(const ChunkArgs& a, hipStream_t s)
 {
     if (a.part) {
-        if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
-        else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
+        if (a.window) hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, true, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
+        else if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, true, false>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
+        else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, true, false>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_chunk_combine, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
         return hipGetLastError();
     }
-    if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
-    else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    if (a.window) hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, false, true>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    else if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, false, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, false, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -460,7 +497,7 @@ hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s)
     if (a.n_blocks == 0) return hipSuccess;
     if (!a.seqs || !a.tab || !a.q || !a.k_new || !a.v_new || !a.out || a.n_seq == 0 || a.heads == 0 || a.rows_per_pos == 0 ||
         a.rows_per_pos > 16u || (a.rows_per_pos & (a.rows_per_pos - 1u)) || static_cast<uint64_t>(a.n_blocks) * a.heads > 0x7FFFFFFFull ||
-        (a.mask && a.mask_words < (a.C + 32u) / 32u) ||
+        (a.mask && a.mask_words < (a.C + 32u) / 32u) || (a.mask && a.window) ||
         (a.part && (a.n_items < a.n_blocks || static_cast<uint64_t>(a.n_items) * a.heads > 0x7FFFFFFFull || reinterpret_cast<uintptr_t>(a.part) % 16u)))
         return hipErrorInvalidValue;
     switch (a.scheme) {

@@ -14,6 +14,7 @@
 #include "engine.hpp"
 #include "placement.hpp"
 #include "chunk_split.hpp"
+#include "chunk_window.hpp"
 
 #include <cstring>
 #include <cstdio>
@@ -814,6 +815,25 @@ speckv_status_t speckv_ext_attend_chunk_split(uint32_t n_seq, const speckv_handl
                                                        seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
                                                        sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), d_mask ? &mask : nullptr,
                                                        &n_splits); });
+}
+
+speckv_status_t speckv_ext_attend_chunk_window(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C,
+                                               uint32_t rows_per_pos, const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new,
+                                               const void* d_v_new, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const int32_t* tail_idx,
+                                               const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems, uint32_t window,
+                                               uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] { return g_engine->attend_chunk(n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new,
+                                                       seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
+                                                       sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), nullptr, &n_splits, &window); });
+}
+
+speckv_status_t speckv_ext_chunk_window_walk(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* base, const uint32_t* n_q,
+                                             uint32_t rows_per_pos, uint32_t window, uint32_t* out_first_tile, uint32_t* out_n_tiles)
+{
+    if (n_seq && (!pos_end || !n_q || !out_first_tile || !out_n_tiles)) return SPECKV_ERR_INVAL;
+    return speckv::chunk_window_walk(n_seq, pos_end, base, n_q, rows_per_pos, window, out_first_tile, out_n_tiles) ? SPECKV_OK : SPECKV_ERR_INVAL;
 }
 
 speckv_status_t speckv_ext_chunk_split_plan(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* n_q, uint32_t rows_per_pos,

@@ -1,8 +1,9 @@
-// cxl-speckv_amd/csrc/engine_chunk.cpp -- speckv_ext_attend_chunk / speckv_ext_attend_chunk_masked / speckv_ext_attend_chunk_split:
-// causal attention of a chunk of new positions per sequence over stored and held positions, one launch -- or, where the stored
+// cxl-speckv_amd/csrc/engine_chunk.cpp -- speckv_ext_attend_chunk / speckv_ext_attend_chunk_masked / speckv_ext_attend_chunk_split /
+// speckv_ext_attend_chunk_window: causal attention of a chunk of new positions per sequence over stored and held positions, one launch -- or, where the stored
 // positions are split across the chip, a piece launch and its merge (Engine member; the kernels are in attend_chunk.hip)
 #include "engine_internal.hpp"
 #include "chunk_split.hpp"
+#include "chunk_window.hpp"
 
 namespace speckv {
 
@@ -17,16 +18,23 @@ namespace speckv {
 // sequence, 0 the library's rule (chunk_split.hpp).  A plan of one piece everywhere issues the launch of the other two entries; any
 // other plan issues the piece launch and the merge behind it on `s`, the partials in a scratch buffer of their own (s_chunk_: a
 // chunk call does not order itself behind the decode entries' s_attn_ on another stream).
+// `window` (the window entry; the other three pass none): query position j sees the absolute positions [max(0, P + 1 - *window), P],
+// P = pos_end + base + j (chunk_window.hpp); never with a mask.  0, or a window under which no row of the call loses a position, issues
+// the unwindowed launch -- the other entries' bits by construction.  Otherwise the whole call runs on the WINDOW instances: a query
+// block walks from its first row's bound, and the pieces are planned by the unchanged chunk_split_plan over the pool tiles that are
+// left from the sequence's first_tile (the first pool tile its position 0 sees) on.
 int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
                          const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new, const void* d_v_new, uint64_t seq_stride,
                          uint64_t pos_stride, const int32_t* tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride,
-                         float sm_scale, float* d_out, float* d_lse, hipStream_t s, const ChunkMask* mask, const uint32_t* n_splits)
+                         float sm_scale, float* d_out, float* d_lse, hipStream_t s, const ChunkMask* mask, const uint32_t* n_splits,
+                         const uint32_t* window)
 {
-    const char* entry = n_splits ? "speckv_ext_attend_chunk_split" : mask ? "speckv_ext_attend_chunk_masked" : "speckv_ext_attend_chunk";
+    const char* entry = window ? "speckv_ext_attend_chunk_window" : n_splits ? "speckv_ext_attend_chunk_split" : mask ? "speckv_ext_attend_chunk_masked" : "speckv_ext_attend_chunk";
     if (null_) return no_data_path(entry);
     if (!s || !handles || !pos_end || !n_q || !d_q_f16 || !d_k_new || !d_v_new || !d_out) return SPECKV_ERR_INVAL;
     if (rows_per_pos == 0 || rows_per_pos > 16u || (rows_per_pos & (rows_per_pos - 1u)) || C == 0) return SPECKV_ERR_INVAL;
     if (n_splits && *n_splits > kChunkSplitsMax) return SPECKV_ERR_INVAL;
+    if (window && mask) return SPECKV_ERR_INVAL;
     // a row's words cover held positions 0 .. C (a tail and C new positions)
     if (mask && (!mask->d_mask || reinterpret_cast<uintptr_t>(mask->d_mask) % 4u || mask->words < (static_cast<uint64_t>(C) + 32u) / 32u))
         return SPECKV_ERR_INVAL;
@@ -71,11 +79,26 @@ int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer
     for (uint32_t i = 0; i < n_seq; ++i) n_blocks += (n_q[i] + per_block - 1u) / per_block;
     if (n_blocks * 8u > 0x7FFFFFFFull) return SPECKV_ERR_INVAL;
     // the pieces of every sequence (all 1: today's launch) -- from the arguments alone, so the plan holds across descriptor_slot
-    std::vector<uint32_t> pieces(n_seq, 1u), tpp(n_seq, 0u);
+    std::vector<uint32_t> pieces(n_seq, 1u), tpp(n_seq, 0u), first_tile(n_seq, 0u);
     uint64_t n_items = n_blocks;
     bool split = false;
+    // the window the kernel gets: 0 while no row of the call loses a position (the unwindowed launch)
+    uint32_t win = 0;
+    if (window && *window)
+        for (uint32_t i = 0; i < n_seq; ++i)
+            if (n_q[i] && static_cast<uint64_t>(pos_end[i]) + (tail_idx && tail_idx[i] >= 0 ? 1u : 0u) + n_q[i] > *window) win = *window;
     if (n_splits && *n_splits != 1u) {
-        if (!chunk_split_plan(n_seq, pos_end, n_q, rows_per_pos, *n_splits, cus(), pieces.data(), tpp.data())) return SPECKV_ERR_INVAL;
+        const uint32_t* plan_end = pos_end;
+        std::vector<uint32_t> rest;                                // window: the stored positions from first_tile on, as whole tiles
+        if (win) {
+            rest.resize(n_seq);
+            for (uint32_t i = 0; i < n_seq; ++i) {
+                first_tile[i] = chunk_window_first_pool_tile(pos_end[i], tail_idx && tail_idx[i] >= 0 ? 1u : 0u, win);
+                rest[i] = 32u * (chunk_pool_tiles(pos_end[i]) - first_tile[i]);
+            }
+            plan_end = rest.data();
+        }
+        if (!chunk_split_plan(n_seq, plan_end, n_q, rows_per_pos, *n_splits, cus(), pieces.data(), tpp.data())) return SPECKV_ERR_INVAL;
         n_items = 0;
         for (uint32_t i = 0; i < n_seq; ++i) {
             n_items += static_cast<uint64_t>((n_q[i] + per_block - 1u) / per_block) * pieces[i];
@@ -100,9 +123,9 @@ int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer
         const uint64_t k_first = static_cast<uint64_t>(layer) * L.num_tokens;
         const int32_t tail = tail_idx && tail_idx[i] >= 0 ? tail_idx[i] : -1;
         const uint32_t blocks = (n_q[i] + per_block - 1u) / per_block;
-        if (!split) { pieces[i] = 1u; tpp[i] = chunk_pool_tiles(pos_end[i]); }
+        if (!split) { pieces[i] = 1u; tpp[i] = chunk_pool_tiles(pos_end[i]); first_tile[i] = 0u; }
         static_cast<ChunkSeq*>(staged)[i] = ChunkSeq{as[i]->row, pos_end[i], n_q[i], first_block, k_first, k_first + L.num_tokens / 2u,
-                                                     tail, tail >= 0 ? 1u : 0u, pieces[i], tpp[i], first_item, 0u};
+                                                     tail, tail >= 0 ? 1u : 0u, pieces[i], tpp[i], first_item, first_tile[i]};
         first_block += blocks;
         first_item += blocks * pieces[i];
     }
@@ -133,6 +156,7 @@ int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer
     ca.mask_words = mask ? mask->words : 0u;
     ca.part = part;
     ca.n_items = first_item;
+    ca.window = win;
     HIP_TRY(launch_attend_chunk(ca, s));
     for (uint32_t i = 0; i < n_seq; ++i) note_use(as[i], s);     // speckv_free waits for this stream
     if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel

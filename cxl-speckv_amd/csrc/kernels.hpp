@@ -165,7 +165,7 @@ struct ChunkSeq {
     uint32_t n_pieces;
     uint32_t tiles_per_piece;
     uint32_t first_item;
-    uint32_t reserved;
+    uint32_t first_tile;              // window form: the first pool tile any block of the sequence walks (the pieces start here); else 0
 };
 // A partial of the split form, one per (work item, kv head): the un-normalised accumulator [64 rows][128] fp32 in the row order of
 // `out`, then (running max, running sum) per row in the log2 domain.
@@ -194,6 +194,9 @@ struct ChunkArgs {
     // kChunkPartBytes, partial (item, head) at part + (item * heads + head) * kChunkPartBytes; n_items = the sum of blocks x pieces
     uint8_t*        part;
     uint32_t        n_items;
+    // window form (0: none; never with a mask): query position j sees the absolute positions [max(0, P + 1 - window), P],
+    // P = pos_end + base + j (chunk_window.hpp)
+    uint32_t        window;
 };
 // part == null: ONE launch of n_blocks * heads workgroups.  Otherwise TWO: n_items * heads workgroups that write their partials, then
 // the merge (k_chunk_combine) over n_blocks * heads, which reads a row's partials in ascending piece order and writes out / lse.

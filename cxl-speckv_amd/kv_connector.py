@@ -675,7 +675,7 @@ class SpeckvKVConnector:
         return counts, firsts
 
     @staticmethod
-    def chunk_pieces(n_new: Sequence[int], stored: Sequence[int], rows_per_pos: int, splits: int = 0, n_cus: int = 256):
+    def chunk_pieces(n_new: Sequence[int], stored: Sequence[int], rows_per_pos: int, splits: int = 0, n_cus: int = 256, window=None):
         """How attend_chunk(splits=...) cuts the stored positions of every request into pieces (speckv_ext_chunk_split_plan restated):
         request b with stored[b] positions (its length; an odd last position is held, not stored) has n_pool = ceil((stored[b] & ~1)
         / 32) pool tiles of 32 positions.  splits 1: one piece each.  splits N in 2..64 (forced): min(N, max(1, n_pool)) pieces -- from
@@ -685,7 +685,13 @@ class SpeckvKVConnector:
         pool tiles [p * tpp, min((p + 1) * tpp, n_pool)) and the last piece also the held positions; a request without pool tiles
         has one piece of 0 tiles.  Returns (pieces, tiles_per_piece, firsts): firsts = the exclusive prefix of blocks x pieces, the
         rule by which the kernel finds (request, block, piece) of a flat work item -- the last request whose prefix is <= the item,
-        block = rest // pieces, piece = rest % pieces.  Pure python, no device."""
+        block = rest // pieces, piece = rest % pieces.  Pure python, no device.
+        window (None or 0: none; W >= 1 as attend_chunk(window=W) cuts when some row of the step loses a position): a fourth list is
+        returned, first_tiles, and the rule runs over the pool tiles that are LEFT -- first_tiles[b] = the first pool tile position 0
+        of the request sees, lo(0) // 32 with lo(0) = max(0, stored[b] + 1 - W), or n_pool where it sees none; n_pool - first_tiles[b]
+        takes n_pool's place above.  Piece p then covers pool tiles [first + p * tpp, min(first + (p + 1) * tpp, n_pool)), clipped
+        from below by the block's first tile (chunk_window_walk), and the last piece goes on through the held tiles from the later
+        of its start and that tile; a piece that is not the last can be empty for later blocks."""
         import numbers
         if isinstance(splits, bool) or not isinstance(splits, numbers.Integral) or not 0 <= splits <= 64:
             raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
@@ -699,16 +705,62 @@ class SpeckvKVConnector:
         if splits == 0:
             g0, target = 8 * sum(counts), 3 * (int(n_cus) or 256)
             most = 1 if g0 == 0 or g0 >= target else min(target // g0, 64)
-        pieces, tiles, firsts, total = [], [], [], 0
+        window = SpeckvKVConnector._chunk_window(window)
+        pieces, tiles, firsts, first_tiles, total = [], [], [], [], 0
         for blocks, s in zip(counts, stored):
             n_pool = ((int(s) & ~1) + 31) // 32
+            if window:
+                lo = max(0, int(s) + 1 - window)
+                first_tiles.append(lo // 32 if lo < (int(s) & ~1) else n_pool)
+                n_pool -= first_tiles[-1]
             p = min(max(n_pool // 32 if splits == 0 else n_pool, 1), most)
             tpp = -(-n_pool // p)
             pieces.append(-(-n_pool // tpp) if tpp else 1)
             tiles.append(tpp)
             firsts.append(total)
             total += blocks * pieces[-1]
+        if window:
+            return pieces, tiles, firsts, first_tiles
         return pieces, tiles, firsts
+
+    @staticmethod
+    def _chunk_window(window):
+        """window as attend_chunk takes it: None or 0 -> 0 (none), an int >= 1 -> itself; anything else is a ValueError"""
+        import numbers
+        if window is None:
+            return 0
+        if isinstance(window, bool) or not isinstance(window, numbers.Integral) or not 0 <= window <= 0xFFFFFFFF:
+            raise ValueError("window must be None or 0 (no window) or a count of positions >= 1")
+        return int(window)
+
+    @staticmethod
+    def chunk_window_walk(n_new: Sequence[int], stored: Sequence[int], rows_per_pos: int, window):
+        """Which tiles attend_chunk(window=W) walks (speckv_ext_chunk_window_walk restated): request b with stored[b] positions (its
+        length: pos_end = stored[b] & ~1 of them in the pool, base = stored[b] & 1 held) and n_new[b] new ones has n_pool =
+        ceil(pos_end / 32) pool tiles of 32 positions, counted first, then the held tiles (held position t = base + new position).
+        Query position j sits at the absolute position P = stored[b] + j and sees [lo(j), P], lo(j) = max(0, P + 1 - W) (W None or
+        0: lo = 0).  Query block blk = positions j_first = blk * (64 // rows_per_pos) .. j_last (the last live one of the block)
+        walks the tiles [t_first, n_tiles): n_tiles = n_pool + ((base + j_last) >> 5) + 1, t_first = lo(j_first) >> 5 while
+        lo(j_first) < pos_end, otherwise n_pool + ((lo(j_first) - pos_end) >> 5) -- exactly the tiles that hold a position a live row
+        of the block sees, never more than ceil((W + 64 // rows_per_pos - 1) / 32) + 2.  Returns one list per request of
+        (t_first, tile count) per block.  Pure python, no device."""
+        import numbers
+        window = SpeckvKVConnector._chunk_window(window)
+        counts, _ = SpeckvKVConnector.chunk_blocks(n_new, rows_per_pos)
+        stored = list(stored)
+        if len(stored) != len(counts) or any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or s < 0 for s in stored):
+            raise ValueError("stored: one count of positions >= 0 per request")
+        per, walks = 64 // int(rows_per_pos), []
+        for n, blocks, s in zip(n_new, counts, stored):
+            pos_end, base = int(s) & ~1, int(s) & 1
+            n_pool, walk = (pos_end + 31) // 32, []
+            for blk in range(blocks):
+                j_first, j_last = blk * per, min(blk * per + per, int(n)) - 1
+                lo = max(0, int(s) + j_first + 1 - window) if window else 0
+                t_first = lo >> 5 if lo < pos_end else n_pool + ((lo - pos_end) >> 5)
+                walk.append((t_first, n_pool + ((base + j_last) >> 5) + 1 - t_first))
+            walks.append(walk)
+        return walks
 
     @staticmethod
     def _chunk_tree_parents(parents, batch):
@@ -782,7 +834,7 @@ class SpeckvKVConnector:
         return self._chunk_tree_masks
 
     def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None,
-                     splits=1):
+                     splits=1, window=None):
         """One layer of a step that carries a CHUNK of S new positions per request, S >= 1 with no bound but max_tokens -- chunked prefill
         of a long prompt, the differing suffix behind fork(), a prompt continued after truncate().  Shapes and meaning are those of
         attend_spec without `parents`: q [batch][S][heads][rows_per_pos][dim] fp16 (rows_per_pos 1, 2, 4, 8 or 16), k_new / v_new
@@ -809,10 +861,23 @@ class SpeckvKVConnector:
         request holds, its ancestors and itself, not its siblings.  Still ONE launch (speckv_ext_attend_chunk_masked) with a mask table
         built once per (batch, lengths, tree, n_new) and shared by the layers' calls; attend_spec(parents=...) stops at 16 nodes and
         reads the records once per 16 // rows_per_pos of them.  Rows of dead nodes (>= n_new[b], or below one) are zeros.  Afterwards
-        commit(req_ids, k_new, v_new, nodes=accepted path) stores a root-to-node path of a tree of any size."""
+        commit(req_ids, k_new, v_new, nodes=accepted path) stores a root-to-node path of a tree of any size.
+        window: None or 0 (the default) = every row sees everything its request holds: the path above, untouched.  An int W >= 1 is
+        the call of a LOCAL (sliding-window) layer of a model that interleaves local and global layers: query position j at the
+        absolute position P = length + j sees the positions (P - W, P] only -- itself and the W - 1 in front of it, stored, held or
+        new (speckv_ext_attend_chunk_window, with `splits` passed through).  It serves prefill chunks and multi-position steps alike,
+        and S = 1 is the windowed DECODE step for a request of any length, odd or even -- attend() has no window.  A query block
+        walks only the tiles its rows see (chunk_window_walk), so the cost follows W, not the context; a window no row of the step
+        loses a position under issues the unwindowed launch, bit for bit.  The query stays fp16 in all pool formats; the K
+        pre-scale, the tails and the strides are those of the path above.  Not with `parents` (a node's position in a tree is its
+        depth, not its index): ValueError, as for a bool, a negative or a non-integer, before any library call.  Records below a
+        window stay in the pool: nothing is freed."""
         import numbers
         import numpy as np
         import torch
+        window = self._chunk_window(window)
+        if window and parents is not None:
+            raise ValueError("window does not combine with parents: a windowed layer takes a chain of new positions, not a tree")
         if isinstance(splits, bool) or not isinstance(splits, numbers.Integral) or not 0 <= splits <= 64:
             raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
         splits = int(splits)
@@ -863,6 +928,12 @@ class SpeckvKVConnector:
                         rank += 1
                 kt = self._fold_k.data_ptr() + 2 * layer * row if rank else 0
                 vt = self._fold_v.data_ptr() + 2 * layer * row if rank else 0
+                if window:
+                    self.lib.attend_chunk_window(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                                 np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
+                                                 v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
+                                                 self.L * row, window, splits, sm_scale, out.data_ptr(), 0, st.cuda_stream)
+                    return out
                 if splits != 1:
                     masks = None if parents is None else self._chunk_tree_table(key, reqs, parents, live, S)
                     self.lib.attend_chunk_split(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),

@@ -72,6 +72,10 @@ _EXT_SIGNATURES = {
                                       c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p,
                                       c_void_p, c_void_p],
     "speckv_ext_chunk_split_plan": [c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p],
+    "speckv_ext_attend_chunk_window": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
+                                       c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p,
+                                       c_void_p],
+    "speckv_ext_chunk_window_walk": [c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
     "speckv_ext_bind_request": [c_uint32, c_uint64, c_uint32],
@@ -366,6 +370,33 @@ class SpeckvLib:
         pieces, tpp = (c_uint32 * n)(), (c_uint32 * n)()
         self._ext("speckv_ext_chunk_split_plan", n, pe, nq, rows_per_pos, n_splits, n_cus, pieces, tpp)
         return list(pieces), list(tpp)
+
+    def attend_chunk_window(self, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx,
+                            d_k_tail, d_v_tail, tail_stride, window, n_splits, sm_scale, d_out, d_lse, stream):
+        """attend_chunk_split without a mask for a sliding-window (local) layer (speckv_ext_attend_chunk_window): query position j at the
+        absolute position P = pos_end + base + j sees the positions [max(0, P + 1 - window), P]; window 0 = none.  A window under which
+        no row loses a position issues attend_chunk_split's launches and bits; otherwise a query block walks only the tiles its rows
+        see (chunk_window_walk) and n_splits cuts the pool tiles that are left.  The other arguments as attend_chunk_split."""
+        n = len(handles)
+        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
+        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
+        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
+        self._ext("speckv_ext_attend_chunk_window", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
+                  seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, window, n_splits, sm_scale,
+                  c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+
+    def chunk_window_walk(self, pos_end, base, n_q, rows_per_pos, window):
+        """The walk rule of attend_chunk_window (speckv_ext_chunk_window_walk; works without init, needs no device): (first_tile,
+        n_tiles), one entry per (sequence, query block) -- the sequences in order, ceil(n_q / (64 // rows_per_pos)) blocks each.
+        base: 0 / 1 held tail positions per sequence, or None."""
+        n = len(pos_end)
+        per = 64 // rows_per_pos if rows_per_pos in (1, 2, 4, 8, 16) else 64
+        total = sum((int(x) + per - 1) // per for x in n_q)
+        pe, nq = (c_uint32 * n)(*[int(x) for x in pos_end]), (c_uint32 * n)(*[int(x) for x in n_q])
+        bs = None if base is None else (c_uint32 * n)(*[int(x) for x in base])
+        first, count = (c_uint32 * max(total, 1))(), (c_uint32 * max(total, 1))()
+        self._ext("speckv_ext_chunk_window_walk", n, pe, bs, nq, rows_per_pos, window, first, count)
+        return list(first)[:total], list(count)[:total]
 
     def read(self, handle, offset, dst_ptr, nbytes, on_device):
         self._ext("speckv_ext_read", handle, offset, c_void_p(dst_ptr), nbytes, int(on_device))

@@ -811,6 +811,53 @@ speckv_status_t speckv_ext_attend_chunk_split(uint32_t n_seq, const speckv_handl
 speckv_status_t speckv_ext_chunk_split_plan(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* n_q, uint32_t rows_per_pos,
                                             uint32_t n_splits, uint32_t n_cus, uint32_t* out_pieces, uint32_t* out_tiles_per_piece);
 
+/* speckv_ext_attend_chunk_window: speckv_ext_attend_chunk_split for a SLIDING-WINDOW (local) layer -- the models that interleave
+ * local and global attention layers (the Mistral family, Gemma 2 / 3, gpt-oss) call this entry on their local layers and the other
+ * chunk entries on their global ones.  The arguments of speckv_ext_attend_chunk_split in the same order with its two mask arguments
+ * replaced by `window`; there is no tree form under a window (a node's position in a tree is its depth, not its index).  Everything
+ * said at speckv_ext_attend_chunk and speckv_ext_attend_chunk_split holds -- layouts, the fp16 query, rows of positions >= n_q[i] are
+ * NOT WRITTEN, n_splits, ordering, NOT capturable into a HIP graph, what is refused -- except what a row sees.
+ *   window == W >= 1 (one value for all sequences of the call): query position j of sequence i sits at the absolute position
+ *            P = pos_end[i] + base + j (base = 1 with a tail, else 0) and sees the absolute positions [lo, P], lo = max(0, P + 1 - W):
+ *            stored position t iff lo <= t < pos_end[i]; held position t (the tail is 0, new position a is base + a; its absolute
+ *            position is pos_end[i] + t) iff pos_end[i] + t >= lo and t <= base + j.  Every live row sees itself.  W == 1 is a row
+ *            that sees itself alone.  n_q[i] == 1 is the windowed DECODE step of a sequence of any length, odd or even.
+ *   window == 0 : no window.
+ * With window == 0, and with a window under which no row of the call loses a position (W >= pos_end[i] + base + n_q[i] for every
+ * sequence with n_q[i] > 0), the call issues exactly the launches of speckv_ext_attend_chunk_split with d_mask == NULL: the same
+ * output bits.  Otherwise the whole call runs on the window form of the kernel: a query block of 64 / rows_per_pos positions walks
+ * only the 32-position tiles that hold a position one of its rows sees (speckv_ext_chunk_window_walk) -- never more than
+ * ceil((W + 64 / rows_per_pos - 1) / 32) + 2 of them, whatever the sequence's length -- and positions no row of the block sees are
+ * not read.  n_splits then cuts the pool tiles that are LEFT: from the first pool tile position 0 of the sequence sees
+ * (floor(lo(0) / 32)) on, by the rule of speckv_ext_chunk_split_plan over that many tiles; a piece that lies wholly below a later
+ * block's bound contributes nothing to it.  Records below a window stay in the pool as they are: nothing is freed or evicted.
+ *   SPECKV_ERR_INVAL    as speckv_ext_attend_chunk, and n_splits > SPECKV_CHUNK_SPLITS_MAX -- nothing is launched
+ *   SPECKV_ERR_NOMEM    the scratch buffer could not grow -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle */
+speckv_status_t speckv_ext_attend_chunk_window(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer,
+                                               const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                               const uint32_t* pos_end, const uint32_t* n_q /* host arrays [n_seq] */,
+                                               const void* d_k_new, const void* d_v_new, uint64_t seq_stride_elems,
+                                               uint64_t pos_stride_elems,
+                                               const int32_t* tail_idx /* host [n_seq], < 0 = none; may be NULL */,
+                                               const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,
+                                               uint32_t window /* 0: none */, uint32_t n_splits,
+                                               float sm_scale, float* d_out, float* d_lse, void* stream);
+
+/* The walk rule of speckv_ext_attend_chunk_window as a pure function (the same body the kernel walks by).  Sequence i has pos_end[i]
+ * (even) stored positions, base[i] in {0, 1} held tail positions (base == NULL: none) and n_q[i] new positions in query blocks of
+ * per_blk = 64 / rows_per_pos positions; the kernel's tile index counts the n_pool = ceil(pos_end[i] / 32) pool tiles first, then the
+ * held tiles.  Block blk (first position j_first = blk * per_blk, last live position j_last) walks the tiles [t_first, n_tiles):
+ *   n_tiles = n_pool + ((base + j_last) >> 5) + 1
+ *   t_first = lo >> 5 if lo < pos_end[i], else n_pool + ((lo - pos_end[i]) >> 5),  lo = max(0, pos_end[i] + base + j_first + 1 - window)
+ * (window == 0: lo = 0).  out_first_tile / out_n_tiles: one entry per (sequence, block), the sequences in order and a sequence's
+ * ceil(n_q[i] / per_blk) blocks in order -- t_first and n_tiles - t_first.
+ * SPECKV_ERR_INVAL: NULL arrays with n_seq > 0, a rows_per_pos other than 1, 2, 4, 8, 16, an odd pos_end[i], base[i] > 1.
+ * Works without speckv_init and needs no device. */
+speckv_status_t speckv_ext_chunk_window_walk(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* base /* may be NULL */,
+                                             const uint32_t* n_q, uint32_t rows_per_pos, uint32_t window,
+                                             uint32_t* out_first_tile, uint32_t* out_n_tiles);
+
 #ifdef __cplusplus
 }
 #endif
