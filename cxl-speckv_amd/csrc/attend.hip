@@ -369,7 +369,10 @@ __global__ __launch_bounds__(256) void k_build_scale_tab(const PageEntry* __rest
 // CLS (round 6): regular striping taken by residue class (see k_attend_fp8_dma<2>): the pages j = c, c + D, ... of the range are
 // consecutive records of one run, so the lane's pointers advance through a class exactly as through a linear region and are set
 // anew only where the requests enter the next class; the four page scales of a lane group come from table entries D pages apart.
-template <bool STRIPED, bool TABLE = false, bool CLS = false>
+// WINDOW: the batch form under a sliding window (AttendArgs::seq_skip) -- a per-sequence count of masked leading POSITIONS and the rule for a
+// page cut by an odd bound.  Instances of their own: carried by the plain instances the position mask cost the unwindowed batch and planned
+// entries 3 % (256 x 2k and x 8k, measured against the launch of before), outside their run-to-run spread.
+template <bool STRIPED, bool TABLE = false, bool CLS = false, bool WINDOW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 : 4, TABLE ? 3 : 4))) void k_attend_fp8_linear(AttendArgs a)
 {
     __shared__ uint64_t s_bases[8];
@@ -385,12 +388,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
     const uint64_t row = static_cast<uint64_t>(layer) * a.heads + head;  // query / output row block
     uint64_t part = row * a.n_splits + split;
     uint32_t my_splits = a.n_splits;
+    uint32_t skip_pos = 0u;                                              // WINDOW: leading positions of the sequence's tile 0 in front of its window
     if (a.seqs) {                                                        // workgroup-uniform: per-sequence geometry
         const AttendSeq sq = a.seqs[layer];
         if (split >= sq.n_splits) {
             if (sq.n_splits == 0u && split == 0u && a.direct_out && a.direct_per_seq == 2u) attend_zero_rows(a.direct_out, a.direct_lse, a.g, row, lane);
             return;
         }
+        skip_pos = WINDOW ? a.seq_skip[layer] : 0u;
         a.lin_base = sq.lin_base;
         a.scale_tab = sq.scale_tab;
         a.k_first = sq.k_first;
@@ -609,12 +614,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
 #pragma unroll
                 for (int i = 0; i < 4; ++i) sc[4 * b + i] = s[i] * (ks4[2 * b + (i >> 1)] * qscale);
             }
-            if (!CLS && ((ragged && tile + 1u == n_tiles) || (a.skip_pages && tile == 0u))) {     // wave-uniform: positions beyond / in front of the range
+            // the lane's candidate for the tile's reference V scale (below): the largest scale among its four pages
+            float vcand = WINDOW ? fmaxf(fmaxf(vs4[0], vs4[1]), fmaxf(vs4[2], vs4[3])) : 0.0f;
+            if (!CLS && ((ragged && tile + 1u == n_tiles) || ((WINDOW ? skip_pos : a.skip_pages) && tile == 0u))) {     // wave-uniform: positions beyond / in front of the range
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const uint32_t pg = tile * 16u + ((j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2));
                     // (a masked page's V scale leaves the tile's reference scale below as well: the page may hold a stale record of any magnitude)
-                    if (pg >= a.n_pages || pg < a.skip_pages) { sc[j] = -INFINITY; vs4[j >> 1] = 0.0f; }
+                    if (!WINDOW) {                                           // page-granular: a range that starts inside a tile starts on a page
+                        if (pg >= a.n_pages || pg < a.skip_pages) { sc[j] = -INFINITY; vs4[j >> 1] = 0.0f; }
+                        continue;
+                    }
+                    // position j & 1 of the page (skip_pos counts positions of tile 0: a window's bound may cut a page)
+                    if (pg >= a.n_pages || 2u * pg + (j & 1) < skip_pos) sc[j] = -INFINITY;
+                    // (a page with BOTH positions masked leaves the tile's reference V scale below as well: it may hold a stale record of any
+                    //  magnitude; a page cut by an odd bound keeps its scale -- its kept position is stored in units of it)
+                    if (pg >= a.n_pages || 2u * pg + 2u <= skip_pos) vs4[j >> 1] = 0.0f;
+                }
+                // ... but a CUT page (skip_pos odd: the page's first position masked, its second kept) stands for election as the reference
+                // with 2^-10 of its scale only: its masked row may be a stale record of any magnitude that set the page's scale, and as the
+                // reference that scale would push the weights of the tile's other 30 positions into the fp16 subnormals (V = +-1000 in front
+                // of the bound: 1.2 % of sum p|v|).  Its own weight p x scale / reference is then 1024 p at most: no overflow in fp16.
+                if (WINDOW) {
+                    vcand = 0.0f;
+#pragma unroll
+                    for (int sl = 0; sl < 4; ++sl) {
+                        const uint32_t pg = tile * 16u + (sl < 2 ? 2u * kb + sl : 8u + 2u * kb + (sl - 2));
+                        vcand = fmaxf(vcand, (tile == 0u && 2u * pg + 1u == skip_pos) ? vs4[sl] * 0.0009765625f : vs4[sl]);
+                    }
                 }
             }
             if (CLS) {                                                       // pages of this tile past the end of its class
@@ -650,7 +677,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
             m_run = m_new;
             if (CLS) vs4 = cls_scales4(vs_raw);
             // the tile's V reference scale (its largest V page scale) and the weights in units of it
-            const float vmx = max_over_kb(fmaxf(fmaxf(vs4[0], vs4[1]), fmaxf(vs4[2], vs4[3])));
+            const float vmx = max_over_kb(WINDOW ? vcand : fmaxf(fmaxf(vs4[0], vs4[1]), fmaxf(vs4[2], vs4[3])));
             const float vref_t = vmx > 0.0f ? vmx : vref;
             const float rinv = __builtin_amdgcn_rcpf(vref_t);
             float psum = 0.0f;
@@ -1647,6 +1674,7 @@ hipError_t launch_attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, ui
 hipError_t launch_attend_fp8_batch(const AttendArgs& a, uint32_t n_seq, float* d_out, float* d_lse, hipStream_t s)
 {
     if (n_seq == 0 || a.n_splits == 0) return hipSuccess;
+    if (a.seq_skip && a.fp8_cls) return hipErrorInvalidValue;           // (the class form has no leading mask: the engine plans windowed launches through the table form)
     // (rows_first: the sequences' first pieces side by side, then their second ones ...: a batch in which few members have several pieces would otherwise
     //  put every real workgroup on the same XCDs -- linear ids x + splits * y with most x > 0 empty)
     AttendArgs ar = a;
@@ -1656,8 +1684,14 @@ hipError_t launch_attend_fp8_batch(const AttendArgs& a, uint32_t n_seq, float* d
     // single-sequence form below is the other way round (8k x 80 layers: 0.61 against 0.55; 32k x 80: 0.70 both)
     if (a.fp8_cls && a.stripe_bases && !a.table_form)                   // every member placed regularly: pages by residue class
         { const dim3 gr = grid_of(a.heads / 4u); hipLaunchKernelGGL((k_attend_fp8_linear<false, false, true>), gr, dim3(256), 0, s, ar); }
-    else if (a.table_form && tuning().attend_fp8_table_regs == 0)       // striped / moved placements: the DMA pipeline with addresses from the page tables
+    else if (a.table_form && !a.seq_skip && tuning().attend_fp8_table_regs == 0)     // striped / moved placements: the DMA pipeline with addresses from the page tables (no window: it has no leading mask)
         { const dim3 gr = grid_of(a.heads / kFdHeads); hipLaunchKernelGGL(k_attend_fp8_dma<1>, gr, dim3(64 * kFdHeads), 0, s, ar); }
+    else if (a.seq_skip) {                                               // under a window: the WINDOW instances of the table, striped and linear bodies
+        const dim3 gr = grid_of(a.heads / 4u);
+        if (a.table_form) hipLaunchKernelGGL((k_attend_fp8_linear<false, true, false, true>), gr, dim3(256), 0, s, ar);
+        else if (a.stripe_bases) hipLaunchKernelGGL((k_attend_fp8_linear<true, false, false, true>), gr, dim3(256), 0, s, ar);
+        else hipLaunchKernelGGL((k_attend_fp8_linear<false, false, false, true>), gr, dim3(256), 0, s, ar);
+    }
     else if (a.table_form) { const dim3 gr = grid_of(a.heads / 4u); hipLaunchKernelGGL((k_attend_fp8_linear<false, true>), gr, dim3(256), 0, s, ar); }
     else if (a.stripe_bases) { const dim3 gr = grid_of(a.heads / 4u); hipLaunchKernelGGL(k_attend_fp8_linear<true>, gr, dim3(256), 0, s, ar); }
     else     { const dim3 gr = grid_of(a.heads / 4u); hipLaunchKernelGGL(k_attend_fp8_linear<false>, gr, dim3(256), 0, s, ar); }

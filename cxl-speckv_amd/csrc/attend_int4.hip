@@ -305,12 +305,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SPECKV_INT4
     const uint64_t row = static_cast<uint64_t>(layer) * a.heads + head;
     uint64_t part = row * a.n_splits + split;
     uint32_t my_splits = a.n_splits;
+    uint32_t skip_pos = 0u;                                              // batch form under a window: leading positions of the sequence's tile 0 in front of it
     if (a.seqs) {                                                        // workgroup-uniform: per-sequence geometry
         const AttendSeq sq = a.seqs[layer];
         if (split >= sq.n_splits) {
             if (sq.n_splits == 0u && split == 0u && a.direct_out && a.direct_per_seq == 2u) attend_zero_rows(a.direct_out, a.direct_lse, a.g, row, lane);
             return;
         }
+        if (a.seq_skip) skip_pos = a.seq_skip[layer];
         a.lin_base = sq.lin_base;
         a.k_first = sq.k_first;
         a.v_first = sq.v_first;
@@ -473,11 +475,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SPECKV_INT4
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { sc[i] = s0[i]; sc[4 + i] = s1[i]; }
                 }
-                if ((ragged && tile + 1u == n_tiles) || tile > last) {      // workgroup-uniform: positions beyond the range / the extra step
+                if ((ragged && tile + 1u == n_tiles) || tile > last || (skip_pos && tile == 0u)) {      // workgroup-uniform: positions beyond / in front of the range, the extra step
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const uint32_t pg = tile * 16u + ((j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2));
-                        if (pg >= a.n_pages || tile > last) sc[j] = -INFINITY;
+                        if (pg >= a.n_pages || tile > last || 2u * pg + (j & 1) < skip_pos) sc[j] = -INFINITY;
                     }
                 }
                 const f16x8 P = softmax_tile(sc, qscale, m_run, l_run, acc);
@@ -546,11 +548,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SPECKV_INT4
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { sc[i] = s0[i]; sc[4 + i] = s1[i]; }
             }
-            if (ragged && tile + 1u == n_tiles) {                         // workgroup-uniform: positions beyond the range
+            if ((ragged && tile + 1u == n_tiles) || (skip_pos && tile == 0u)) {     // workgroup-uniform: positions beyond / in front of the range
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const uint32_t pg = tile * 16u + ((j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2));
-                    if (pg >= a.n_pages) sc[j] = -INFINITY;
+                    if (pg >= a.n_pages || 2u * pg + (j & 1) < skip_pos) sc[j] = -INFINITY;        // (position j & 1 of the page)
                 }
             }
             const f16x8 P = softmax_tile(sc, qscale, m_run, l_run, acc);
@@ -648,6 +650,7 @@ __global__ __launch_bounds__(512 * HALVES) __attribute__((amdgpu_waves_per_eu(SP
     const uint32_t n_tiles = CLS ? mx4_striped_tiles(a.n_pages, a.stripe_n) : (a.n_pages + 15u) / 16u;       // (batch form: set per sequence below)
     // ---- this workgroup's run of tiles: `count` tiles from tile `ct` of layer `cl` on, in layer-major order
     uint32_t cl, ct, count, slot = 0u, my_splits = a.n_splits;
+    uint32_t skip_pos = 0u;                                              // batch form under a window: leading positions of the sequence's tile 0 in front of it
     uint64_t part = 0u;
     const bool stream = a.stream.n_wgs != 0u;
     uint32_t tiles_in_layer = n_tiles;
@@ -671,6 +674,7 @@ __global__ __launch_bounds__(512 * HALVES) __attribute__((amdgpu_waves_per_eu(SP
                     attend_zero_rows(a.direct_out, a.direct_lse, a.g, static_cast<uint64_t>(cl) * 8u + head, lane);
                 return;
             }
+            if (!CLS && a.seq_skip) skip_pos = a.seq_skip[cl];
             a.lin_base = sq.lin_base;
             a.k_first = sq.k_first + static_cast<uint64_t>(a.batch_layer) * sq.layer_pages;
             a.v_first = sq.v_first + static_cast<uint64_t>(a.batch_layer) * sq.layer_pages;
@@ -860,11 +864,11 @@ __global__ __launch_bounds__(512 * HALVES) __attribute__((amdgpu_waves_per_eu(SP
                     }
                 }
                 if (++cc_m == cls_m) { cc_m = 0u; if (++cc_cls == cls_n && stream) cc_cls = 0u; }
-            } else if (ragged && ct + 1u == tiles_in_layer) {             // workgroup-uniform: positions beyond the range
+            } else if ((ragged && ct + 1u == tiles_in_layer) || (skip_pos && ct == 0u)) {     // wave-uniform (HALVES == 2: each half is at its own tile; no barrier inside): positions beyond / in front of the range
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const uint32_t pg = ct * 16u + ((j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2));
-                    if (pg >= a.n_pages) sc[j] = -INFINITY;
+                    if (pg >= a.n_pages || 2u * pg + (j & 1) < skip_pos) sc[j] = -INFINITY;        // (position j & 1 of the page)
                 }
             }
             const f16x8 P = softmax_tile(sc, qscale, m_run, l_run, acc);
@@ -930,6 +934,7 @@ hipError_t launch_attend_int4(const AttendArgs& a_in, uint32_t n_layers, hipStre
     const dim3 wg_grid = a.rows_first ? dim3((n_layers * (a.heads / 4u)) | 1u, a.n_splits) : dim3(a.n_splits, n_layers * (a.heads / 4u));
     if (a.table_form) { hipLaunchKernelGGL((k_attend_int4_wg<false, true>), wg_grid, dim3(256), 0, s, a); return hipGetLastError(); }
     if (a.wg8 && !a.lin_base && a.stripe_bases && a.heads == 8u) {       // striped regularly: the same kernel over residue classes
+        if (a.seq_skip) return hipErrorInvalidValue;                     // (no leading mask by class: the engine plans windowed launches through the table form)
         const dim3 grid8 = a.stream.n_wgs ? dim3(a.stream.n_wgs) : a.rows_first ? dim3(n_layers | 1u, a.n_splits) : dim3(a.n_splits, n_layers);
         if (a.stream.n_wgs || a.wg8 == 2u) hipLaunchKernelGGL((k_attend_int4_wg8<1, true>), grid8, dim3(512), 0, s, a);
         else hipLaunchKernelGGL((k_attend_int4_wg8<2, true>), grid8, dim3(1024), 0, s, a);

@@ -159,6 +159,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg * HALVES) __attribute__((amdgpu_wa
     uint32_t my_splits = a.n_splits;
     if (STREAM) { part0 = row0 * a.stream.max_slots + slot; part_step = a.stream.max_slots; my_splits = 0u; }      // (never the direct output)
     int32_t tail = -1;                                                   // this sequence's row in the tail arrays (split 0 folds it in)
+    uint32_t seq_skip = 0u;                                              // batch form under a window: leading positions of the sequence's tile 0 in front of it
     if (a.seqs) {                                                        // workgroup-uniform: per-sequence geometry
         uint32_t seq = layer;
         if (a.batch_n_seq) {                                             // several layers in one launch: y = layer x sequence
@@ -169,6 +170,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg * HALVES) __attribute__((amdgpu_wa
         // (not the page-table form: it sits at the register limit of two waves per SIMD; the engine sends its tails through k_attend_fold_tail)
         if (FORM != 2 && a.tail_k && split == 0u) tail = a.tail_idx ? a.tail_idx[seq] : static_cast<int32_t>(seq);
         const AttendSeq sq = a.seqs[seq];
+        if (!CLS && !STREAM && a.seq_skip) seq_skip = a.seq_skip[seq];
         if (split >= sq.n_splits) {
             if (sq.n_splits == 0u && split == 0u && blockIdx.z == 0u && a.direct_out && a.direct_per_seq == 2u) {
                 attend_zero_rows(a.direct_out, a.direct_lse, a.g, row0, lane);
@@ -535,7 +537,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg * HALVES) __attribute__((amdgpu_wa
             }
         }
         const bool ragged = (a.n_pages & 15u) != 0u;
-        const uint32_t n_pos = 2u * a.n_pages, skip_pos = 2u * a.skip_pages;
+        const uint32_t n_pos = 2u * a.n_pages, skip_pos = max(seq_skip, 2u * a.skip_pages);      // (seq_skip: batch form under a window, else 0)
         uint32_t cc_cls = cls0, cc_m = t0 - cls0 * cls_m;                    // class form: the tile the arithmetic is at
         const uint32_t wshift = 16u * w;
         // one tile out of stage BUF (a compile-time constant: the LDS reads then carry the stage as an immediate offset)
@@ -577,7 +579,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg * HALVES) __attribute__((amdgpu_wa
                         for (int r = 0; r < 4; ++r)
                             if (cc_cls + cls_n * (16u * cc_m + 4u * kb + r) >= cls_pages) sc[r] = -INFINITY;
                     }
-                } else if ((ragged && tile + 1u == n_tiles) || (a.skip_pages && tile == 0u)) {  // wave-uniform: positions beyond / in front of the range
+                } else if ((ragged && tile + 1u == n_tiles) || (skip_pos && tile == 0u)) {  // wave-uniform: positions beyond / in front of the range
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const uint32_t pos = tile * 32u + 2u * (4u * kb + r) + w;
@@ -752,7 +754,7 @@ hipError_t launch_attend_mx4(const AttendArgs& a_in, uint32_t n_rows, float* d_o
     if (n_rows == 0 || a.n_splits == 0 || a.heads != 8u) return a.heads != 8u ? hipErrorInvalidValue : hipSuccess;
     if (!a.seqs && a.n_pages == 0) return hipSuccess;
     const int form = a.lin_base ? (a.stream.n_wgs ? 3 : 0) : a.stripe_bases ? 1 : a.table_form ? 2 : -1;
-    if (form == 1 && (a.skip_pages || (!a.seqs && (a.stripe_n < 1u || a.stripe_n > 8u)))) return hipErrorInvalidValue;
+    if (form == 1 && (a.skip_pages || a.seq_skip || (!a.seqs && (a.stripe_n < 1u || a.stripe_n > 8u)))) return hipErrorInvalidValue;
     if (form < 0 || (a.stream.n_wgs && (form != 3 || a.seqs || (a.n_pages & 15u) || a.skip_pages))) return hipErrorInvalidValue;
     const dim3 grid = form == 3 ? dim3(a.stream.n_wgs, 1u, (a.g + 7u) / 8u) : a.rows_first ? dim3(n_rows | 1u, a.n_splits, (a.g + 7u) / 8u) : dim3(a.n_splits, n_rows, (a.g + 7u) / 8u);
     const dim3 block(64 * kWavesPerWg);

@@ -15,6 +15,7 @@
 #include "placement.hpp"
 #include "chunk_split.hpp"
 #include "chunk_window.hpp"
+#include "decode_window.hpp"
 
 #include <cstring>
 #include <cstdio>
@@ -518,6 +519,38 @@ speckv_status_t speckv_ext_attend_batch_plan(uint32_t n_seq, const speckv_handle
 
 // one descriptor per sequence, then the dispatch order (one index per sequence: Engine::attend_batch_plan)
 size_t speckv_ext_attend_plan_bytes(uint32_t n_seq) { return static_cast<size_t>(n_seq) * (sizeof(speckv::AttendSeq) + sizeof(uint32_t)); }
+
+// ---- the batch and planned forms under a sliding window (decode_window.hpp) ----
+// ... and behind the order the skip array of the window (one count per sequence)
+size_t speckv_ext_attend_plan_window_bytes(uint32_t n_seq) { return static_cast<size_t>(n_seq) * (sizeof(speckv::AttendSeq) + 2u * sizeof(uint32_t)); }
+
+speckv_status_t speckv_ext_attend_batch_plan_window(uint32_t n_seq, const speckv_handle_t* handles, const uint32_t* pos_end, const uint32_t* q_pos,
+                                                    uint32_t window, uint32_t max_pos_end, void* d_plan, size_t plan_bytes, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] {
+        return g_engine->attend_batch_plan(n_seq, handles, pos_end, max_pos_end, d_plan, plan_bytes, static_cast<hipStream_t>(stream), q_pos, window);
+    });
+}
+
+speckv_status_t speckv_ext_attend_batch_window(int scheme, uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g,
+                                               const uint32_t* pos_end, const uint32_t* q_pos, uint32_t window, float sm_scale, float* d_out,
+                                               float* d_lse, void* stream)
+{
+    if (scheme != SPECKV_COMP_FP8_E4M3 && scheme != SPECKV_COMP_INT4_G32 && scheme != SPECKV_COMP_MXFP4) return SPECKV_ERR_INVAL;
+    LOCK; NEED_INIT;
+    return guarded([&] {
+        return g_engine->attend_batch(scheme, n_seq, handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), q_pos, window);
+    });
+}
+
+speckv_status_t speckv_ext_decode_window_range(uint32_t length, uint32_t window, uint32_t* out_begin, uint32_t* out_skip, uint32_t* out_n_pages)
+{
+    if (!out_begin || !out_skip || !out_n_pages) return SPECKV_ERR_INVAL;
+    const speckv::DecodeWindowRange r = speckv::decode_window_range(length, window);
+    *out_begin = r.begin; *out_skip = r.skip; *out_n_pages = r.n_pages;
+    return SPECKV_OK;
+}
 
 speckv_status_t speckv_ext_attend_fp8_planned(const void* d_plan, uint32_t n_seq, uint32_t layer, const void* d_q_f16, uint32_t g,
                                               uint32_t max_pos_end, float sm_scale, float* d_out, float* d_lse, void* stream)

@@ -148,8 +148,10 @@ public:
     int write_strided(uint64_t handle, uint64_t first, uint64_t step, uint64_t n, const void* d_src, hipStream_t s);
     int write_async(uint64_t handle, uint64_t off, const void* d_src, size_t len, hipStream_t s);
     hipError_t upload_pinned(void* dst, const void* staged, size_t bytes, hipStream_t s);
+    // q_pos / window: the window entries (speckv_ext_attend_batch_plan_window, speckv_ext_attend_batch_window; decode_window.hpp): member i's query
+    // sits at q_pos[i] in {pos_end[i] - 1, pos_end[i]} and sees its last `window` positions.  q_pos null: the entries without a window.
     int attend_batch_plan(uint32_t n_seq, const uint64_t* handles, const uint32_t* pos_end, uint32_t max_pos_end, void* d_plan,
-                          size_t plan_bytes, hipStream_t s);
+                          size_t plan_bytes, hipStream_t s, const uint32_t* q_pos = nullptr, uint32_t window = 0);
     // the position a caller still keeps outside the pool (speckv_ext_attend_planned_tail): fp16 rows [n_tail][layers][heads][128]
     struct TailArgs { uint32_t n_tail; const uint32_t* d_tail_rows; const int32_t* d_tail_idx; const void* d_k_tail; const void* d_v_tail; uint64_t stride_elems; };
     int attend_planned(int scheme, const void* d_plan, uint32_t n_seq, uint32_t layer, const void* d_q_f16, uint32_t g,
@@ -199,7 +201,7 @@ public:
     int attend_fp8(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
                    uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
     int attend_batch(int scheme, uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g,
-                     const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
+                     const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos = nullptr, uint32_t window = 0);
     int attend_int4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
                     uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
     int attend_mx4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
@@ -383,11 +385,13 @@ private:
     PinnedRingT<4> grp_ring_;
     // what attend_batch_plan decided for the plan a buffer holds: the shape and the form its launches take (attend_geometry.hpp), the largest run count of a plan
     // counted by residue classes (0 otherwise), and the room -- the launch geometry the FIRST plan of this shape in this buffer chose
-    struct PlanInfo { int scheme; uint32_t n_layers, max_pos_end; BatchShape shape; BatchForm form; uint32_t stripe_n_max; bool any_empty; bool ordered; BatchRoom room; };
+    // window: what speckv_ext_attend_batch_plan_window planned under (0: no window) -- its launches take the skip array behind the dispatch order and the
+    // smaller of the context's and the window's tile bound, whatever the lengths of the step (a captured launch stays valid while they change)
+    struct PlanInfo { int scheme; uint32_t n_layers, max_pos_end; BatchShape shape; BatchForm form; uint32_t stripe_n_max; bool any_empty; bool ordered; BatchRoom room; uint32_t window; };
     std::unordered_map<const void*, PlanInfo> plans_;      // device plan buffer -> what attend_batch_plan last wrote there
-    // (buffer, members | format, bound | rule's piece length, rule's pieces) -> {room for pieces, rows-first grid}: what the FIRST plan of that shape in that
+    // (buffer, members | format, bound | rule's piece length, rule's pieces, window) -> {room for pieces, rows-first grid}: what the FIRST plan of that shape in that
     // buffer chose -- kept per shape, so that a buffer that alternates between shapes keeps every shape's captured launches valid
-    std::map<std::array<uint64_t, 4>, BatchRoom> plan_rooms_;
+    std::map<std::array<uint64_t, 5>, BatchRoom> plan_rooms_;
     CompressGroup* d_groups_ = nullptr;    // device twin of grp_ring_ (4 slots): descriptors of a grouped compress launch
     uint8_t* d_zero_page_ = nullptr;     // stands in for never-written pages in the fused attention
     std::unordered_map<uint32_t, std::vector<int32_t>> hist_;
@@ -418,7 +422,7 @@ private:
                      uint32_t pos_end, float* d_out, hipStream_t s, SeqCall& c);
     int attend_end(const SeqCall& c, hipStream_t s);
     int gather_members(bool batch_entry, int scheme, uint32_t n_seq, const uint64_t* handles, const uint32_t* pos_end, uint32_t layer, uint32_t max_pos_end,
-                       hipStream_t s, BatchMembers& m);
+                       hipStream_t s, BatchMembers& m, const uint32_t* q_pos = nullptr, uint32_t window = 0);
     // the folds of held rows: what attend_fold_held / _masked judge alike, and the launch bracket of those two and attend_fold_tail
     static bool fold_held_args_ok(uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16, const void* d_k_held, const void* d_v_held,
                                   uint64_t seq_stride_elems, uint64_t pos_stride_elems, const float* d_out, const float* d_lse);

@@ -1,5 +1,6 @@
 // cxl-speckv_amd/csrc/engine_attend.cpp -- fused decode attention: launch planning for the FP8 / INT4 kernels, single sequences and batches (Engine members)
 #include "engine_internal.hpp"
+#include "decode_window.hpp"
 #include "tuning.hpp"
 
 #include <optional>
@@ -112,6 +113,21 @@ static void striped_args(AttendArgs& k, const Allocation* a)
     k.stripe_bases = a->d_stripe;
     k.stripe_n = a->stripe_n;
     k.stripe_magic = static_cast<uint32_t>((1ull << 32) / a->stripe_n + 1u);
+}
+// A launch under a window runs the bodies that mask the leading positions of a member's first tile (AttendArgs::seq_skip): the linear, striped and
+// table forms.  The forms by residue class (k_attend_mx4<1>, k_attend_int4_wg8<.., true>, k_attend_fp8_linear<.., CLS>) count their tiles class by class and
+// have no such mask: their launches go through the page tables, which take any range (FP8: the register-staged table kernel -- k_attend_fp8_dma<1> has
+// no leading mask either; launch_attend_fp8_batch).  Everything else of the decision is batch_form's.
+static BatchForm window_form(BatchForm f)
+{
+    if (f.by_class) { f.table = true; f.striped = f.fp8_cls = f.int4_cls = f.by_class = false; f.wg8 = 0u; }
+    return f;
+}
+// the tiles a member of a plan has at most: the context's bound, under a window the smaller of that and the window's
+static uint32_t plan_bound(uint32_t max_pos_end, uint32_t stripe_n_max, uint32_t window)
+{
+    const uint32_t ctx = plan_tiles_bound(max_pos_end, stripe_n_max);
+    return window ? std::min(ctx, decode_window_tiles_bound(window)) : ctx;
 }
 static BatchTuning batch_tuning()
 {
@@ -269,6 +285,8 @@ struct Engine::BatchMembers {
     int scheme = -1;
     uint32_t min_layers = UINT32_MAX, stripe_n_max = 0;      // (stripe_n_max: the largest run count, where the tiles are counted by residue class)
     uint64_t total_tiles = 0;
+    std::vector<uint32_t> skips;      // the window entries: leading positions of member i's first tile in front of its window (AttendArgs::seq_skip)
+    bool cut = false;                 // ... and whether the window cuts any member's pool positions at all
     // what the form asks of the descriptors: the page tables in table launches, the tiles counted by residue class
     void apply(const BatchForm& f)
     {
@@ -285,9 +303,10 @@ struct Engine::BatchMembers {
 
 // Looks the members up and fills their descriptors for `layer` (a plan: layer 0, the launch adds layer * layer_pages; the format from the first member).
 int Engine::gather_members(bool batch_entry, int scheme, uint32_t n_seq, const uint64_t* handles, const uint32_t* pos_end, uint32_t layer, uint32_t max_pos_end,
-                           hipStream_t s, BatchMembers& m)
+                           hipStream_t s, BatchMembers& m, const uint32_t* q_pos, uint32_t window)
 {
     m.seqs.resize(n_seq); m.ents.resize(n_seq); m.tiles.resize(n_seq); m.pages.resize(n_seq);
+    m.skips.assign(q_pos ? n_seq : 0u, 0u);
     bool any_striped = false;                 // then the whole launch takes the striped kernels (a single run is "striped over 1")
     bool any_table = false;                   // ... or, with a member that has no regular placement, the table forms
     uint32_t heads = 0;
@@ -299,9 +318,18 @@ int Engine::gather_members(bool batch_entry, int scheme, uint32_t n_seq, const u
         const Layout& L = a->layout;
         if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads * L.head_dim != 1024 || L.num_tokens % 2) return SPECKV_ERR_INVAL;
         if (layer >= L.num_layers || pos_end[i] % 2 || pos_end[i] > L.num_tokens || pos_end[i] > max_pos_end) return SPECKV_ERR_INVAL;
-        const uint32_t n_pages = pos_end[i] / 2, n_tiles = (n_pages + 15u) / 16u;
+        // under a window the member is walked from the tile of its lower bound (decode_window.hpp): the descriptor's region starts `begin` positions in,
+        // the tiles are those that are left -- they end where the member's tiles end without a window, so the same condition keeps them inside the region
+        DecodeWindowRange w{0u, 0u, pos_end[i] / 2};
+        if (q_pos) {
+            if (q_pos[i] > pos_end[i] || q_pos[i] + 1u < pos_end[i]) return SPECKV_ERR_INVAL;       // the query: the last stored position or the tail behind it
+            w = decode_window_range(q_pos[i] + 1u, window);
+            m.skips[i] = w.skip;
+            m.cut = m.cut || w.n_pages != pos_end[i] / 2 || w.skip != 0u;
+        }
+        const uint32_t n_pages = w.n_pages, n_tiles = (n_pages + 15u) / 16u;
         const bool fp8 = scheme == SPECKV_COMP_FP8_E4M3;
-        if ((fp8 && !a->d_scale_tab) || static_cast<uint64_t>(n_tiles) * 32u > L.num_tokens) {
+        if ((fp8 && !a->d_scale_tab) || static_cast<uint64_t>(w.begin) + static_cast<uint64_t>(n_tiles) * 32u > L.num_tokens) {
             if (batch_entry)
                 SPECKV_ERR("speckv_ext_attend_*_batch: sequence %u does not qualify for the tile-aligned forms (pos_end rounded up "
                            "to 32 inside the layer%s)", i, fp8 ? ", layout with num_tokens %% 32 == 0" : "");
@@ -318,7 +346,7 @@ int Engine::gather_members(bool batch_entry, int scheme, uint32_t n_seq, const u
         q.stripe_n = a->stripe_n;
         q.lin_base = a->linear_base;
         q.scale_tab = a->d_scale_tab;
-        q.k_first = static_cast<uint64_t>(layer) * L.num_tokens;       // (layer*2*T)/2
+        q.k_first = static_cast<uint64_t>(layer) * L.num_tokens + w.begin / 2u;       // (layer*2*T)/2, from the window's first tile on
         q.v_first = q.k_first + L.num_tokens / 2;
         q.n_pages = m.pages[i] = n_pages;
         q.layer_pages = L.num_tokens;                                   // K + V pages of one layer
@@ -354,10 +382,12 @@ int Engine::take_seq_slot(size_t bytes, int* slot, void** staged)
 // replay would read other calls' descriptors -- the call refuses to run on a capturing stream (the per-sequence
 // entry points speckv_ext_attend_fp8 / _int4 are capturable).
 int Engine::attend_batch(int scheme, uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g,
-                         const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+                         const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos, uint32_t window)
 {
     const bool fp8 = scheme == SPECKV_COMP_FP8_E4M3, mx4 = scheme == SPECKV_COMP_MXFP4;
     if (null_) return no_data_path("speckv_ext_attend_*_batch");
+    if (window && !q_pos) return SPECKV_ERR_INVAL;
+    if (!window) q_pos = nullptr;                              // (no window: the launches of the entries without one)
     if (n_seq == 0) return SPECKV_OK;
     if (is_capturing(s)) {
         SPECKV_ERR("speckv_ext_attend_*_batch cannot be captured into a HIP graph (its descriptors are staged per call); "
@@ -366,7 +396,7 @@ int Engine::attend_batch(int scheme, uint32_t n_seq, const uint64_t* handles, ui
     }
     if (!handles || !pos_end || !d_q_f16 || !d_out || g == 0 || g > 16) return SPECKV_ERR_INVAL;
     BatchMembers m;
-    RC_TRY(gather_members(true, scheme, n_seq, handles, pos_end, layer, UINT32_MAX, s, m));
+    RC_TRY(gather_members(true, scheme, n_seq, handles, pos_end, layer, UINT32_MAX, s, m, q_pos, window));
     const uint32_t heads = m.shape.heads;
     DeviceScope device_scope(device_);
     // NULL = the engine's stream and a synchronous call: the query may have been produced on any stream of the caller
@@ -379,8 +409,9 @@ int Engine::attend_batch(int scheme, uint32_t n_seq, const uint64_t* handles, ui
         return SPECKV_OK;
     }
     // the launch decision (attend_geometry.hpp): the form, the dispatch order, one split length for the whole batch, the pieces of every member
+    // (a window that cuts no member's pool positions: the descriptors, the form and the launches of the entry without a window, no skip array)
     const BatchTuning tun = batch_tuning();
-    const BatchForm form = batch_form(m.shape, tun);
+    const BatchForm form = m.cut ? window_form(batch_form(m.shape, tun)) : batch_form(m.shape, tun);
     m.apply(form);
     std::vector<uint32_t> order(n_seq);
     const bool ordered = batch_dispatch_order(form, tun, m.pages.data(), n_seq, order.data());
@@ -393,12 +424,14 @@ int Engine::attend_batch(int scheme, uint32_t n_seq, const uint64_t* handles, ui
     // it starts (one round trip, all workgroups at once).  Copying the slot to the device first was a copy-engine operation in
     // front of every launch, 7-8 us that the kernels waited for: 256 x 1k MXFP4 59.5 -> 53 us per call, FP8 96 -> 88
     // (profiles/r05_mx4.txt; the planned form never had it).  A slot is reused once the launches that read it have finished.
-    const size_t desc_bytes = m.seqs.size() * sizeof(AttendSeq), seq_bytes = desc_bytes + m.seqs.size() * sizeof(uint32_t);      // descriptors, then the dispatch order
+    const size_t desc_bytes = m.seqs.size() * sizeof(AttendSeq), idx_bytes = m.seqs.size() * sizeof(uint32_t);
+    const size_t seq_bytes = desc_bytes + idx_bytes + (m.cut ? idx_bytes : 0u);      // descriptors, then the dispatch order, then the skip array of a windowed launch
     int slot = 0;
     void* staged = nullptr;
     RC_TRY(take_seq_slot(seq_bytes, &slot, &staged));
     memcpy(staged, m.seqs.data(), desc_bytes);
-    if (ordered) memcpy(static_cast<uint8_t*>(staged) + desc_bytes, order.data(), n_seq * sizeof(uint32_t));
+    if (ordered) memcpy(static_cast<uint8_t*>(staged) + desc_bytes, order.data(), idx_bytes);
+    if (m.cut) memcpy(static_cast<uint8_t*>(staged) + desc_bytes + idx_bytes, m.skips.data(), idx_bytes);
     AttendSeq* d_seqs = nullptr;
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_seqs), staged, 0));
     // sequences without positions have no splits: their rows are written as zeros by the merge (L == 0)
@@ -420,6 +453,7 @@ int Engine::attend_batch(int scheme, uint32_t n_seq, const uint64_t* handles, ui
     if (form.fp8_cls) k.fp8_cls = 1u;
     k.seqs = d_seqs;
     if (ordered) k.order = reinterpret_cast<const uint32_t*>(d_seqs + n_seq);
+    if (m.cut) k.seq_skip = reinterpret_cast<const uint32_t*>(d_seqs + n_seq) + n_seq;
     if (geo.rows_first) k.rows_first = 1u;
     bool one_split_each = true;                           // then the attention kernel writes the final rows itself
     for (uint32_t i = 0; i < n_seq; ++i) one_split_each = one_split_each && m.seqs[i].n_splits == 1u;
@@ -452,19 +486,24 @@ int Engine::attend_batch(int scheme, uint32_t n_seq, const uint64_t* handles, ui
 // of the caller; speckv_ext_attend_*_planned is kernel launches only: no handle look-ups, no staging, grid and scratch
 // sized from max_pos_end alone, so a captured launch stays valid for as long as the lengths stay within that bound.
 int Engine::attend_batch_plan(uint32_t n_seq, const uint64_t* handles, const uint32_t* pos_end, uint32_t max_pos_end,
-                              void* d_plan, size_t plan_bytes, hipStream_t s)
+                              void* d_plan, size_t plan_bytes, hipStream_t s, const uint32_t* q_pos, uint32_t window)
 {
     if (null_) return no_data_path("speckv_ext_attend_batch_plan");
     if (n_seq == 0) return SPECKV_OK;
     if (!handles || !pos_end || !d_plan || !s || max_pos_end % 2 || plan_bytes < n_seq * sizeof(AttendSeq)) return SPECKV_ERR_INVAL;
+    // a plan under a window holds descriptors, dispatch order and skip array (speckv_ext_attend_plan_window_bytes), whatever the lengths of this step
+    if (window && (!q_pos || plan_bytes < n_seq * (sizeof(AttendSeq) + 2u * sizeof(uint32_t)))) return SPECKV_ERR_INVAL;
+    if (!window) q_pos = nullptr;
     if (is_capturing(s)) return SPECKV_ERR_INVAL;            // the plan is what changes between replays: it stays outside the graph
     BatchMembers m;
-    RC_TRY(gather_members(false, -1, n_seq, handles, pos_end, 0, max_pos_end, s, m));
+    RC_TRY(gather_members(false, -1, n_seq, handles, pos_end, 0, max_pos_end, s, m, q_pos, window));
     const int scheme = m.scheme;
     const BatchTuning tun = batch_tuning();
-    const BatchForm form = batch_form(m.shape, tun);                       // (the launch decision: attend_geometry.hpp)
+    // (the launch decision: attend_geometry.hpp.  Under a window the form, the bound and the skip array follow from the window alone, not from what
+    //  it cuts in this step: a graph captured over the plan's launches stays valid while the lengths move)
+    const BatchForm form = window ? window_form(batch_form(m.shape, tun)) : batch_form(m.shape, tun);
     m.apply(form);
-    const uint32_t bound_tiles = plan_tiles_bound(max_pos_end, m.stripe_n_max);
+    const uint32_t bound_tiles = plan_bound(max_pos_end, m.stripe_n_max, window);
     const BatchGeometry rule = batch_geometry(kEntryPlan, m.shape, form, tun, nullptr, bound_tiles, false, nullptr);      // the rule for equal lengths under the bound
     if (!rule.fits) return SPECKV_ERR_INVAL;
     // the dispatch order behind the descriptors, where the caller's buffer has the room (speckv_ext_attend_plan_bytes says so since round 6)
@@ -476,14 +515,16 @@ int Engine::attend_batch_plan(uint32_t n_seq, const uint64_t* handles, const uin
         for (uint32_t i = 0; i < n_seq; ++i) order[i] = i;
     // The room of this shape in this buffer: what its first plan fixed, kept by every later one (batch_geometry says why)
     // (... the rule for equal lengths is part of the shape: the tuning keys move it)
-    const std::array<uint64_t, 4> room_key{reinterpret_cast<uintptr_t>(d_plan), n_seq | (static_cast<uint64_t>(scheme) << 32), max_pos_end | (static_cast<uint64_t>(rule.rule_tps) << 32), rule.rule_splits};
+    const std::array<uint64_t, 5> room_key{reinterpret_cast<uintptr_t>(d_plan), n_seq | (static_cast<uint64_t>(scheme) << 32), max_pos_end | (static_cast<uint64_t>(rule.rule_tps) << 32), rule.rule_splits, window};
     const auto old = plan_rooms_.find(room_key);
     const bool plan_sticky = old != plan_rooms_.end();
     const BatchGeometry geo = batch_geometry(kEntryPlan, m.shape, form, tun, m.tiles.data(), bound_tiles, by_length, plan_sticky ? &old->second : nullptr);
     if (plans_.size() >= 64 && !plans_.count(d_plan)) plans_.clear();        // (buffers of long-gone steps)
     if (form.table) RC_TRY(ensure_zero_page(s));
-    bool any_empty = false;
-    for (uint32_t i = 0; i < n_seq; ++i) any_empty = any_empty || pos_end[i] == 0u;
+    // (under a window: a member without pool positions.  W = 1 is the one window under which a member that has a split in this step has none in the
+    //  next -- an odd length -- so its plans always send the tails through the fold launch: a captured launch must not fold into a split that is gone)
+    bool any_empty = window == 1u;
+    for (uint32_t i = 0; i < n_seq; ++i) any_empty = any_empty || m.pages[i] == 0u;
     if (!plan_sticky) {
         // (a graph captured over a buffer replays the room of its shape without calling in: a room is dropped only once its buffer has left plans_ --
         //  rooms of live buffers are kept however many shapes pass through them)
@@ -494,15 +535,17 @@ int Engine::attend_batch_plan(uint32_t n_seq, const uint64_t* handles, const uin
             }
         plan_rooms_[room_key] = BatchRoom{geo.max_splits, geo.rows_first};
     }
-    plans_[d_plan] = PlanInfo{scheme, m.min_layers, max_pos_end, m.shape, form, m.stripe_n_max, any_empty, ordered, BatchRoom{geo.max_splits, geo.rows_first}};
+    plans_[d_plan] = PlanInfo{scheme, m.min_layers, max_pos_end, m.shape, form, m.stripe_n_max, any_empty, ordered, BatchRoom{geo.max_splits, geo.rows_first}, window};
     assign_pieces(geo, m.shape.heads, m.seqs.data(), n_seq);
     DeviceScope device_scope(device_);
-    const size_t desc_bytes = m.seqs.size() * sizeof(AttendSeq), seq_bytes = desc_bytes + (ordered ? m.seqs.size() * sizeof(uint32_t) : 0u);
+    const size_t desc_bytes = m.seqs.size() * sizeof(AttendSeq), idx_bytes = m.seqs.size() * sizeof(uint32_t);
+    const size_t seq_bytes = desc_bytes + (ordered ? idx_bytes : 0u) + (window ? idx_bytes : 0u);      // (a windowed plan is always ordered: its buffer has the room)
     int slot = 0;
     void* staged = nullptr;
     RC_TRY(take_seq_slot(seq_bytes, &slot, &staged));
     memcpy(staged, m.seqs.data(), desc_bytes);
-    if (ordered) memcpy(static_cast<uint8_t*>(staged) + desc_bytes, order.data(), n_seq * sizeof(uint32_t));
+    if (ordered) memcpy(static_cast<uint8_t*>(staged) + desc_bytes, order.data(), idx_bytes);
+    if (window) memcpy(static_cast<uint8_t*>(staged) + desc_bytes + idx_bytes, m.skips.data(), idx_bytes);
     HIP_TRY(hipMemcpyAsync(d_plan, staged, seq_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(seq_ring_.ev[slot], s));
     return SPECKV_OK;
@@ -558,7 +601,7 @@ int Engine::attend_planned(int scheme, const void* d_plan, uint32_t n_seq, uint3
     }
     const PlanInfo& p = plan->second;
     // (tps by the rule for equal lengths under the bound; max_splits and rows_first as the first plan of this shape in this buffer fixed them: attend_batch_plan)
-    const BatchGeometry pg = batch_geometry(kEntryPlan, p.shape, p.form, batch_tuning(), nullptr, plan_tiles_bound(max_pos_end, p.stripe_n_max), false, &p.room);
+    const BatchGeometry pg = batch_geometry(kEntryPlan, p.shape, p.form, batch_tuning(), nullptr, plan_bound(max_pos_end, p.stripe_n_max, p.window), false, &p.room);
     DeviceScope device_scope(device_);
     AttendArgs k{};
     if (!attend_scratch(k, static_cast<uint64_t>(n_seq) * heads * pg.max_splits, 0, s))      // (growth during a capture is refused: warm up once)
@@ -578,6 +621,7 @@ int Engine::attend_planned(int scheme, const void* d_plan, uint32_t n_seq, uint3
     if (p.form.fp8_cls) k.fp8_cls = 1u;                        // (... the register-staged kernel by residue classes)
     k.seqs = static_cast<const AttendSeq*>(d_plan);
     if (plan->second.ordered) k.order = reinterpret_cast<const uint32_t*>(static_cast<const AttendSeq*>(d_plan) + n_seq);
+    if (p.window) k.seq_skip = reinterpret_cast<const uint32_t*>(static_cast<const AttendSeq*>(d_plan) + n_seq) + n_seq;       // (behind the order: attend_batch_plan)
     k.batch_layer = layer;
     k.direct_out = d_out;                                      // sequences with a single split are written directly ...
     k.direct_lse = d_lse;

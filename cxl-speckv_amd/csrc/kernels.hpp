@@ -476,6 +476,13 @@ struct AttendArgs {
     const uint16_t* tail_v;
     const int32_t* tail_idx;
     uint64_t tail_stride;
+    // batch form under a sliding window (decode_window.hpp): seq_skip[sequence] = the leading POSITIONS (0..31, may be odd) of the
+    // sequence's first tile that lie in front of its window -- their scores are -inf, as AttendArgs::skip_pages does per launch and per
+    // page in the single-sequence form.  Null: no sequence of the launch is cut.  FP8: the WINDOW instances of k_attend_fp8_linear (linear,
+    // striped, table) take it -- launch_attend_fp8_batch sends every launch that brings one to them, a table launch too (k_attend_fp8_dma<1>
+    // has no leading mask and is passed over); INT4_G32 and MXFP4: the existing instances k_attend_int4_wg8<1|2>, k_attend_int4_wg and
+    // k_attend_mx4<0|2>.  The forms by residue class have no leading mask: their launchers refuse it, the engine never plans them under a window.
+    const uint32_t* seq_skip;
 };
 // (the stream partition -- attend_stream_begin / _wg_of / _count -- is plain arithmetic the host decides with too: ring_rule.hpp)
 // MXFP4 over a striped pool (k_attend_mx4 form 1): the positions of the range are taken CLASS by class -- class c = the pages j

@@ -98,6 +98,7 @@ class SpeckvKVConnector:
         self._fold_key = self._arg_key = None
         self._plan = None                                     # device buffer of the step's attention plan
         self._plan_bound = 0
+        self._wplans = {}                                     # window -> [plan buffer, bound, arg key]: one plan per window value beside the global one
         self._fold_rows = self._fold_idx = self._fold_k = self._fold_v = None
         self._fold_n = 0
         # host-side bookkeeping of a decode loop is per STEP, not per layer: `_epoch` moves whenever a length or the set of
@@ -380,17 +381,57 @@ class SpeckvKVConnector:
         return out[pos_begin - lo:pos_end - lo]
 
     PLAN_BUCKET = 512
+    WINDOW_PLANS_MAX = 8                   # plan buffers kept for window values (plan_step(window=W)) beside the global one
 
-    def plan_step(self, req_ids: Sequence[int], stream):
+    @staticmethod
+    def _decode_window(window):
+        """window=None or 0: none; else an int >= 1"""
+        if window is None or window == 0:
+            return 0
+        if int(window) != window or not 1 <= int(window) < 2 ** 32:
+            raise ValueError("window must be None or an integer >= 1")
+        return int(window)
+
+    @staticmethod
+    def decode_window_range(length: int, window):
+        """The walk rule of attend(window=W) (csrc/decode_window.hpp, speckv_ext_decode_window_range), restated: a request of `length`
+        positions -- the step's own included, i.e. its length when attend() runs -- has stored = length & ~1 of them in the pool and its
+        query at length - 1 sees [lo, length - 1], lo = max(0, length - W).  Returns (begin, skip, n_pages): the launch walks the pool from
+        the tile of lo, begin = lo & ~31, with the first skip = lo - begin positions masked, over n_pages = (stored - begin) / 2 pages;
+        n_pages = 0 where lo == stored (W = 1 with an odd length, a length below 2): no pool position, the tail at most."""
+        W = SpeckvKVConnector._decode_window(window)
+        length = int(length)
+        stored = length & ~1
+        lo = length - W if W and length > W else 0
+        begin = lo & ~31
+        return begin, lo - begin, (stored - begin) // 2 if lo < stored else 0
+
+    def plan_step(self, req_ids: Sequence[int], stream, window=None):
         """The attention plan of this decode step for the batch `req_ids` at their current lengths, on `stream` (a torch
         stream, not the default one).  attend() calls it by itself when the batch or the lengths changed; a caller that
-        replays captured per-layer calls runs it before every replay.  Returns the length bound the launches are sized for."""
+        replays captured per-layer calls runs it before every replay.  Returns the length bound the launches are sized for.
+        window=W: the plan of the step's sliding-window layers of that window (speckv_ext_attend_batch_plan_window) -- ONE PLAN PER
+        WINDOW VALUE is kept beside the global one, so a step over interleaved local and global layers plans once per kind and
+        launches as before; the bound is bucketed in the same way."""
         import ctypes
         import torch
         key, reqs, handles = self._batch(req_ids)
         B = len(reqs)
         lens = [r.length & ~1 for r in reqs]
         bound = min(self.T, max(self.PLAN_BUCKET, (max(lens) + self.PLAN_BUCKET - 1) // self.PLAN_BUCKET * self.PLAN_BUCKET))
+        W = self._decode_window(window)
+        if W:
+            need = self.lib.attend_plan_window_bytes(B)
+            if W not in self._wplans and len(self._wplans) >= self.WINDOW_PLANS_MAX:      # (a model has one or two window values: the oldest goes)
+                del self._wplans[next(iter(self._wplans))]
+            slot = self._wplans.setdefault(W, [None, 0, None])
+            if slot[0] is None or slot[0].numel() < need:
+                slot[0] = torch.zeros(need, dtype=torch.uint8, device="cuda")
+            q_pos = [max(r.length, 1) - 1 for r in reqs]
+            self.lib.attend_batch_plan_window(handles, (ctypes.c_uint32 * B)(*lens), (ctypes.c_uint32 * B)(*q_pos), W, bound, slot[0].data_ptr(), need,
+                                              stream.cuda_stream)
+            slot[1], slot[2] = bound, ((key, self._epoch), stream.cuda_stream)
+            return bound
         need = self.lib.attend_plan_bytes(B)
         if self._plan is None or self._plan.numel() < need:
             self._plan = torch.zeros(need, dtype=torch.uint8, device="cuda")
@@ -425,18 +466,21 @@ class SpeckvKVConnector:
                     self._fold_k = torch.stack([reqs[b].tail_k for b in odd]).contiguous()
                     self._fold_v = torch.stack([reqs[b].tail_v for b in odd]).contiguous()
 
-    def attend(self, layer: int, req_ids: Sequence[int], q, sm_scale: float, stream=None):
+    def attend(self, layer: int, req_ids: Sequence[int], q, sm_scale: float, stream=None, window=None):
         """softmax(q.K^T * sm_scale).V of one layer for the batch.  q: [batch][heads][g][dim] fp16 (g query rows per kv
         head, GQA); returns [batch][heads][g][dim] fp32.  Stored positions come straight from the compressed records
         (one launch pair for the batch); the position still waiting for its partner goes along in the same call
-        (speckv_ext_attend_planned_tail: folded in by the MXFP4 kernel itself, by one launch inside the call otherwise)."""
-        return self.attend_layers(layer, 1, req_ids, q[None], sm_scale, stream)[0]
+        (speckv_ext_attend_planned_tail: folded in by the MXFP4 kernel itself, by one launch inside the call otherwise).
+        window=W: a sliding-window (local) layer -- every request's query sees its last W positions, its own included
+        (decode_window_range), and the launch walks the window's tiles only."""
+        return self.attend_layers(layer, 1, req_ids, q[None], sm_scale, stream, window)[0]
 
-    def attend_layers(self, layer_begin: int, n_layers: int, req_ids: Sequence[int], q, sm_scale: float, stream=None):
+    def attend_layers(self, layer_begin: int, n_layers: int, req_ids: Sequence[int], q, sm_scale: float, stream=None, window=None):
         """The same for n_layers consecutive layers whose query rows exist at once (speckv_ext_attend_planned_layers): q
         [n_layers][batch][heads][g][dim] fp16, returns [n_layers][batch][heads][g][dim] fp32.  One library call; over an MXFP4 pool
-        with a batch that fills the chip, one launch."""
+        with a batch that fills the chip, one launch.  window=W: the layers are sliding-window layers of that window (attend)."""
         import torch
+        W = self._decode_window(window)
         if self.scheme not in FUSED:
             raise ValueError("attend() needs an FP8, INT4 or MXFP4 pool; use block_table() / kv_rows() with the other schemes")
         NL, B, H, G, D = q.shape
@@ -454,8 +498,14 @@ class SpeckvKVConnector:
         # PLAN_BUCKET decode steps (plan_step() outside the graph, then the replay).
         akey = (key, self._epoch)
         with self._On(self, stream) as st:
-            if self._arg_key != (akey, st.cuda_stream):
-                self.plan_step(req_ids, st)
+            if W:                                                 # the plan of this window value, kept beside the global one
+                if W not in self._wplans or self._wplans[W][2] != (akey, st.cuda_stream):
+                    self.plan_step(req_ids, st, W)
+                plan, bound = self._wplans[W][0], self._wplans[W][1]
+            else:
+                if self._arg_key != (akey, st.cuda_stream):
+                    self.plan_step(req_ids, st)
+                plan, bound = self._plan, self._plan_bound
             self._plan_stream = st
             self._prepare_tails(req_ids, key, reqs, st)
             n_tail = self._fold_n
@@ -464,13 +514,13 @@ class SpeckvKVConnector:
             kt = self._fold_k.data_ptr() if n_tail else 0
             vt = self._fold_v.data_ptr() if n_tail else 0
             if n_layers == 1 and not n_tail:
-                self.lib.attend_planned(self.scheme, self._plan.data_ptr(), B, layer_begin, q.data_ptr(), G, self._plan_bound, sm_scale,
+                self.lib.attend_planned(self.scheme, plan.data_ptr(), B, layer_begin, q.data_ptr(), G, bound, sm_scale,
                                         out.data_ptr(), lse.data_ptr(), st.cuda_stream)
             elif n_layers == 1:
-                self.lib.attend_planned_tail(self.scheme, self._plan.data_ptr(), B, layer_begin, q.data_ptr(), G, self._plan_bound, sm_scale,
+                self.lib.attend_planned_tail(self.scheme, plan.data_ptr(), B, layer_begin, q.data_ptr(), G, bound, sm_scale,
                                              out.data_ptr(), lse.data_ptr(), n_tail, rows, idx, kt, vt, self.L * self.H * self.D, st.cuda_stream)
             else:
-                self.lib.attend_planned_layers(self.scheme, self._plan.data_ptr(), B, layer_begin, n_layers, q.data_ptr(), G, self._plan_bound, sm_scale,
+                self.lib.attend_planned_layers(self.scheme, plan.data_ptr(), B, layer_begin, n_layers, q.data_ptr(), G, bound, sm_scale,
                                                out.data_ptr(), lse.data_ptr(), st.cuda_stream, n_tail, rows, idx, kt, vt, self.L * self.H * self.D)
         return out
 

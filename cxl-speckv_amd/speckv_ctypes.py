@@ -100,6 +100,10 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_fp8_batch": [c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_int4_batch": [c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_batch_plan": [c_uint32, ctypes.POINTER(c_uint64), _u32p, c_uint32, c_void_p, c_size_t, c_void_p],
+    "speckv_ext_attend_batch_plan_window": [c_uint32, ctypes.POINTER(c_uint64), _u32p, _u32p, c_uint32, c_uint32, c_void_p, c_size_t, c_void_p],
+    "speckv_ext_attend_batch_window": [c_int, c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, _u32p, c_uint32, ctypes.c_float,
+                                       c_void_p, c_void_p, c_void_p],
+    "speckv_ext_decode_window_range": [c_uint32, c_uint32, _u32p, _u32p, _u32p],
     "speckv_ext_attend_fp8_planned": [c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_int4_planned": [c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_fold_tail": [c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
@@ -144,6 +148,7 @@ def bind_ext(lib):
         found.append(name)
     for name, res, args in (("speckv_ext_layer_compression_ratio", ctypes.c_double, [c_uint32]), ("speckv_ext_backend", c_char_p, []),
                             ("speckv_ext_attend_plan_bytes", c_size_t, [c_uint32]),
+                            ("speckv_ext_attend_plan_window_bytes", c_size_t, [c_uint32]),
                             ("speckv_ext_codec_tensor_workspace_bytes", c_size_t, [c_uint64]),
                             ("speckv_ext_codec_tensor_decode_workspace_bytes", c_size_t, [c_uint64])):
         try:
@@ -545,6 +550,37 @@ class SpeckvLib:
         hs = handles if isinstance(handles, ctypes.Array) else (c_uint64 * n)(*handles)
         pe = pos_end if isinstance(pos_end, ctypes.Array) else (c_uint32 * n)(*pos_end)
         self._ext("speckv_ext_attend_batch_plan", n, hs, pe, max_pos_end, c_void_p(d_plan), plan_bytes, c_void_p(stream))
+
+    # ---- the batch and planned forms under a sliding window (include/speckv_ext.h)
+    def attend_plan_window_bytes(self, n_seq):
+        return int(self.lib.speckv_ext_attend_plan_window_bytes(n_seq))
+
+    def attend_batch_plan_window(self, handles, pos_end, q_pos, window, max_pos_end, d_plan, plan_bytes, stream):
+        """attend_batch_plan for a sliding-window layer: member i has q_pos[i] + 1 positions (pos_end[i] = that & ~1 stored, an odd one more in
+        the caller's tail) and its query sees the last `window` of them.  The planned entries run over the plan as over any other; d_plan
+        holds attend_plan_window_bytes(n) bytes."""
+        n = len(handles)
+        hs = handles if isinstance(handles, ctypes.Array) else (c_uint64 * n)(*handles)
+        pe = pos_end if isinstance(pos_end, ctypes.Array) else (c_uint32 * n)(*[int(x) for x in pos_end])
+        qp = q_pos if isinstance(q_pos, ctypes.Array) else (c_uint32 * n)(*[int(x) for x in q_pos])
+        self._ext("speckv_ext_attend_batch_plan_window", n, hs, pe, qp, window, max_pos_end, c_void_p(d_plan), plan_bytes, c_void_p(stream))
+
+    def attend_batch_window(self, scheme, handles, layer, d_q_f16, g, pos_end, q_pos, window, sm_scale, d_out, d_lse=None, stream=None):
+        """attend_{fp8,int4,mx4}_batch for a sliding-window layer (scheme: 4 FP8_E4M3, 3 INT4_G32, 5 MXFP4); pos_end / q_pos as
+        attend_batch_plan_window.  window 0: the entry without one."""
+        n = len(handles)
+        hs = handles if isinstance(handles, ctypes.Array) else (c_uint64 * n)(*handles)
+        pe = pos_end if isinstance(pos_end, ctypes.Array) else (c_uint32 * n)(*[int(x) for x in pos_end])
+        qp = None if q_pos is None else q_pos if isinstance(q_pos, ctypes.Array) else (c_uint32 * n)(*[int(x) for x in q_pos])
+        self._ext("speckv_ext_attend_batch_window", scheme, n, hs, layer, c_void_p(d_q_f16), g, pe, qp, window, ctypes.c_float(sm_scale),
+                  c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream))
+
+    def decode_window_range(self, length, window):
+        """The walk rule of the windowed decode attention (speckv_ext_decode_window_range; works without init, needs no device): (begin, skip,
+        n_pages) of a member of `length` positions, the step's own included, under `window` (0: none)."""
+        b, k, n = c_uint32(0), c_uint32(0), c_uint32(0)
+        self._ext("speckv_ext_decode_window_range", length, window, ctypes.byref(b), ctypes.byref(k), ctypes.byref(n))
+        return b.value, k.value, n.value
 
     def attend_planned(self, scheme, d_plan, n_seq, layer, d_q_f16, g, max_pos_end, sm_scale, d_out, d_lse, stream):
         """One layer of a planned batch: kernel launches only (capturable).  scheme: 4 (FP8_E4M3) or 3 (INT4_G32)."""

@@ -675,6 +675,45 @@ double speckv_ext_layer_compression_ratio(uint32_t layer_id);
 /* width/8 * MHz/1000 * engines (cache_engine.cpp:291-296): 51.2 for the reference's defaults */
 double speckv_ext_codec_model_throughput_gbps(uint32_t num_engines, double clock_mhz, uint32_t data_width_bits);
 
+/* ---- the batch and planned forms for a SLIDING-WINDOW (local) layer ----------------------------------------------------------------
+ * One new position per request for a whole batch, on a layer whose query sees its last `window` positions only (Mistral, Gemma 2 / 3,
+ * gpt-oss interleave such layers with global ones).  The launches walk the window, not the context: never more than
+ * ceil((window + 31) / 32) tiles of 32 positions per member, whatever its length.
+ *
+ * A member has length = q_pos + 1 positions, the step's own included: pos_end[i] = length & ~1 (even) of them are stored in the pool,
+ * an odd length keeps its last position outside (the caller's tail), so q_pos[i] is pos_end[i] - 1 (the query's own position is the last
+ * stored one) or pos_end[i] (it is the tail).  The query sees [lo, q_pos], lo = max(0, length - window), window >= 1; the tail -- which
+ * the planned entries take as before -- and a step's own stored position are always visible.  speckv_ext_decode_window_range is the rule
+ * as a pure function (the same body the engine fills its descriptors by; works without speckv_init): the member is walked from
+ * begin = lo & ~31 with the first skip = lo - begin positions (0..31, odd or even) masked, over n_pages = (pos_end - begin) / 2 pages;
+ * n_pages = 0 where lo == pos_end: window 1 with an odd length, or a length below 2 -- such a member is handled as one with pos_end = 0.
+ * window = 0 in the range function: no window (begin = skip = 0).
+ *
+ *   speckv_ext_attend_batch_window        speckv_ext_attend_{fp8,int4,mx4}_batch under a window; `scheme` = the pool's format.  window = 0
+ *       (q_pos is then not read), or a window that cuts no member's pool positions, issues exactly the launches of those entries.
+ *   speckv_ext_attend_batch_plan_window   speckv_ext_attend_batch_plan under a window >= 1 (0: the plan of speckv_ext_attend_batch_plan); the buffer
+ *       holds speckv_ext_attend_plan_window_bytes(n_seq) bytes: descriptors, dispatch order, then one skip count per sequence.
+ *       speckv_ext_attend_{fp8,int4,mx4}_planned, _planned_tail and _planned_layers run over such a plan unchanged -- they find it by its
+ *       buffer.  Grid and scratch of its launches are functions of (n_seq, max_pos_end, window): the tile bound is the smaller of the
+ *       context's and the window's, and the kernel form is decided by the window being there, not by what it cuts in one step, so a
+ *       captured launch stays valid while the lengths move inside max_pos_end.  (Whether the MXFP4 kernel folds the tails itself or a
+ *       launch behind it does is decided by the plan the capture ran over -- a member without pool pages, or window 1, means the launch
+ *       -- and a captured call keeps that choice; the results are the same either way, as with speckv_ext_attend_batch_plan.)  A caller
+ *       with local and global layers keeps one plan buffer per window value beside the global one.
+ * Placements: pools in a single run take the linear kernels; a batch with a striped or migrated member runs through the page tables
+ * (the kernels by residue class have no mask for the head of a tile).  SPECKV_ERR_INVAL: a q_pos outside {pos_end - 1, pos_end}, a NULL
+ * q_pos with window != 0, a buffer below speckv_ext_attend_plan_window_bytes, a capturing stream, and whatever the entries without a
+ * window refuse. */
+size_t speckv_ext_attend_plan_window_bytes(uint32_t n_seq);
+speckv_status_t speckv_ext_attend_batch_plan_window(uint32_t n_seq, const speckv_handle_t* handles, const uint32_t* pos_end /* even, stored */,
+                                                    const uint32_t* q_pos /* pos_end - 1 <= q_pos <= pos_end */, uint32_t window,
+                                                    uint32_t max_pos_end, void* d_plan, size_t plan_bytes, void* stream);
+speckv_status_t speckv_ext_attend_batch_window(int scheme, uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer,
+                                               const void* d_q_f16, uint32_t g, const uint32_t* pos_end, const uint32_t* q_pos,
+                                               uint32_t window, float sm_scale, float* d_out, float* d_lse, void* stream);
+speckv_status_t speckv_ext_decode_window_range(uint32_t length, uint32_t window, uint32_t* out_begin, uint32_t* out_skip,
+                                               uint32_t* out_n_pages);
+
 /* Launch-form switches (tests, measurement runs): the library reads its environment ONCE, at the first speckv_init / raw codec
  * call of the process; after that a form is changed by this call only.  Keys (= the SPECKV_<KEY> environment names, lower case):
  * attend_splits, attend_tiles_per_split, attend_general, tc_multipass, tc_scan (1 one workgroup, 2 one wave), tc_no_pre,
