@@ -56,7 +56,7 @@
 // bounds are wave-uniform (scalar registers): the SPLIT instances cost no vector registers worth mentioning.
 //
 // Window form (WINDOW, ChunkArgs::window = W >= 1; speckv_ext_attend_chunk_window: a local layer of a model that interleaves
-// sliding-window and global layers).  The same body, never together with MASKED.  Query position j at the absolute position
+// sliding-window and global layers).  The same body; with MASKED it is the form behind this one.  Query position j at the absolute position
 // P = pos_end + base + j sees the absolute positions [lo(j), P], lo(j) = max(0, P + 1 - W) (chunk_window.hpp): a stored position t
 // iff lo(j) <= t < pos_end, a held position t iff pos_end + t >= lo(j) and t <= base + j.  The block walks [t_first, n_tiles),
 // t_first = the tile of lo(j_first): exactly the tiles that hold a position a live row of the block sees, never more than
@@ -68,6 +68,16 @@
 // below its first row's bound, the mirror of wave_t_last.  Split form: the pieces cut the pool tiles from ChunkSeq::first_tile (the
 // first pool tile block 0 sees) on, clipped from below by the block's t_first; a piece that is not the last can be EMPTY for later
 // blocks: it stages nothing and writes m = -inf, l = 0, zeros for its live rows, which k_chunk_combine weighs 0 exactly.
+//
+// Tree form under a window (MASKED and WINDOW, ChunkArgs::depth; speckv_ext_attend_chunk_tree_window: a draft tree on a local layer).
+// Node j sits at the absolute position pos_end + base + depth(j), so its lower bound comes from its DEPTH, a device array [n_seq][C]
+// a live row loads once beside its own mask bit: row_lo = chunk_window_lo(pos_end, base, depth[j], W).  Pool tiles: t >= row_lo and
+// t < pos_end.  Held tiles: the mask words alone, as in the tree form -- the caller has folded the window into them, the kernel
+// applies no lower bound there and stages no held zeros for the window.  Depths are not monotone in node order (a deep node may
+// stand in front of a root inside one wave), so NOTHING is derived from a block's or a wave's first row: every block of a sequence
+// walks from chunk_window_first_pool_tile, the tile of depth 0's bound (n_pool where depth 0 sees no stored position), positions
+// below that bound are staged as zeros, and no wave skips a pool tile by a lower bound (the block-uniform bound, no per-wave skip).
+// Split form: the pieces cut the pool tiles from ChunkSeq::first_tile on and every block shares that tile, so no piece is empty.
 #include "kernels.hpp"
 #include "codec_device.hpp"          // pack_half2, half_bits_to_float
 #include "attend_device.hpp"
@@ -223,12 +233,15 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     // sequence's first_tile on and are clipped from below by the block's first tile -- a piece that is not the last can be EMPTY
     // (t_begin >= t_end): it stages nothing and writes the partial of a piece that saw nothing
     const uint32_t piece_first = (SPLIT && WINDOW ? static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(sq->first_tile)) : 0u) + piece * tpp;
-    const uint32_t t_first = WINDOW ? chunk_window_first_tile(pos_end, base, j_first, a.window) : 0u;
+    // MASKED and WINDOW: a node's bound comes from its depth, which is not monotone in j: every block walks from depth 0's tile
+    const uint32_t t_first = !WINDOW ? 0u : MASKED ? chunk_window_first_pool_tile(pos_end, base, a.window)
+                                                   : chunk_window_first_tile(pos_end, base, j_first, a.window);
     const uint32_t t_begin = WINDOW ? (piece_first > t_first ? piece_first : t_first) : SPLIT ? piece * tpp : 0u;
     const uint32_t t_end = !SPLIT || piece + 1u == n_pieces ? n_tiles : (piece_first + tpp < n_pool ? piece_first + tpp : n_pool);
     // WINDOW: what no row of the block sees, as a stored position (lo_pool) and as a held one (lo_held): staged as zeros
-    const uint32_t lo_pool = WINDOW ? chunk_window_lo(pos_end, base, j_first, a.window) : 0u;
-    const uint32_t lo_held = lo_pool > pos_end ? lo_pool - pos_end : 0u;
+    // (MASKED and WINDOW: below depth 0's bound, and no held zeros -- the held part is what the mask words say)
+    const uint32_t lo_pool = WINDOW ? chunk_window_lo(pos_end, base, MASKED ? 0u : j_first, a.window) : 0u;
+    const uint32_t lo_held = !MASKED && lo_pool > pos_end ? lo_pool - pos_end : 0u;
 
     const PageEntry* entries = reinterpret_cast<const PageEntry*>(ck_uniform(reinterpret_cast<uint64_t>(a.tab[sq->table_row].entries)));
     const uint64_t k_first = ck_uniform(sq->k_first), v_first = ck_uniform(sq->v_first);
@@ -249,9 +262,11 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     // tree form: the row's mask words (one per held tile), and whether its own bit is set
     const uint32_t* mrow = nullptr;
     bool row_live = j < n_q;
+    uint32_t depth = 0u;                                      // MASKED and WINDOW: the node's depth, the j of its lower bound
     if (MASKED && row_live) {
         mrow = a.mask + (static_cast<uint64_t>(seq) * a.C + j) * a.mask_words;
         row_live = (ck_ld<uint32_t>(mrow + ((base + j) >> 5)) >> ((base + j) & 31u)) & 1u;
+        if (WINDOW) depth = ck_ld<uint32_t>(a.depth + static_cast<uint64_t>(seq) * a.C + j);
         if (!row_live) mrow = nullptr;
     }
     const uint64_t row_idx = ((static_cast<uint64_t>(seq) * a.C + j) * a.heads + h) * rpp + sub;
@@ -268,8 +283,9 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     const bool wave_live = j_first + (16u * wave) / rpp < n_q;
     // WINDOW: the row's lower bound as an absolute position (re-based per part in front of the test), and the lowest bound of the
     // wave's rows, its first row's: tiles wholly below it are skipped by the wave as the tiles behind wave_t_last are
-    const uint32_t row_lo = WINDOW ? chunk_window_lo(pos_end, base, j, a.window) : 0u;
-    const uint32_t wave_lo = WINDOW ? chunk_window_lo(pos_end, base, j_first + (16u * wave) / rpp, a.window) : 0u;
+    // (MASKED and WINDOW: the bound of the row's depth; no wave bound -- a wave's first row need not be its shallowest)
+    const uint32_t row_lo = WINDOW ? chunk_window_lo(pos_end, base, MASKED ? depth : j, a.window) : 0u;
+    const uint32_t wave_lo = WINDOW && !MASKED ? chunk_window_lo(pos_end, base, j_first + (16u * wave) / rpp, a.window) : 0u;
 
     Raw rk, rv;
     const auto load_tile = [&](uint32_t tile) {
@@ -361,7 +377,9 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t t = t_base + 16u * (i >> 2) + 4u * g + (i & 3u);
                 // tree form: bit t & 31 of the word (t_base is a multiple of 32), the causal bound folded into the word
-                const bool seen = MASKED ? (vis >> (16u * (i >> 2) + (i & 3u))) & 1u : WINDOW ? t >= lower && t < limit : t < limit;
+                // (under a window too: a stored position also needs t >= the bound of the row's depth, a held one its bit alone)
+                const bool seen = MASKED ? ((vis >> (16u * (i >> 2) + (i & 3u))) & 1u) && (!WINDOW || held || t >= row_lo)
+                                  : WINDOW ? t >= lower && t < limit : t < limit;
                 sv[i] = seen ? sc[i >> 2][i & 3u] * scale2 : -__builtin_inff();
                 mx = fmaxf(mx, sv[i]);
             }
@@ -476,7 +494,8 @@ template <int SCHEME>
 hipError_t launch_chunk(const ChunkArgs& a, hipStream_t s)
 {
     if (a.part) {
-        if (a.window) hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, true, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
+        if (a.window && a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, true, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
+        else if (a.window) hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, true, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
         else if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, true, false>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
         else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, true, false>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
         const hipError_t e = hipGetLastError();
@@ -484,7 +503,8 @@ hipError_t launch_chunk(const ChunkArgs& a, hipStream_t s)
         hipLaunchKernelGGL(k_chunk_combine, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
         return hipGetLastError();
     }
-    if (a.window) hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, false, true>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    if (a.window && a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, false, true>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    else if (a.window) hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, false, true>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
     else if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, false, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
     else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, false, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
     return hipGetLastError();
@@ -497,7 +517,7 @@ hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s)
     if (a.n_blocks == 0) return hipSuccess;
     if (!a.seqs || !a.tab || !a.q || !a.k_new || !a.v_new || !a.out || a.n_seq == 0 || a.heads == 0 || a.rows_per_pos == 0 ||
         a.rows_per_pos > 16u || (a.rows_per_pos & (a.rows_per_pos - 1u)) || static_cast<uint64_t>(a.n_blocks) * a.heads > 0x7FFFFFFFull ||
-        (a.mask && a.mask_words < (a.C + 32u) / 32u) || (a.mask && a.window) ||
+        (a.mask && a.mask_words < (a.C + 32u) / 32u) || (a.mask && a.window && !a.depth) || (a.depth && reinterpret_cast<uintptr_t>(a.depth) % 4u) ||
         (a.part && (a.n_items < a.n_blocks || static_cast<uint64_t>(a.n_items) * a.heads > 0x7FFFFFFFull || reinterpret_cast<uintptr_t>(a.part) % 16u)))
         return hipErrorInvalidValue;
     switch (a.scheme) {

@@ -862,6 +862,21 @@ speckv_status_t speckv_ext_attend_chunk_window(uint32_t n_seq, const speckv_hand
                                                        sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), nullptr, &n_splits, &window); });
 }
 
+speckv_status_t speckv_ext_attend_chunk_tree_window(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16,
+                                                    uint32_t C, uint32_t rows_per_pos, const uint32_t* pos_end, const uint32_t* n_q,
+                                                    const void* d_k_new, const void* d_v_new, uint64_t seq_stride_elems,
+                                                    uint64_t pos_stride_elems, const int32_t* tail_idx, const void* d_k_tail,
+                                                    const void* d_v_tail, uint64_t tail_stride_elems, const uint32_t* d_mask,
+                                                    uint32_t mask_words, const uint32_t* d_depth, uint32_t window, uint32_t n_splits,
+                                                    float sm_scale, float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    const speckv::Engine::ChunkMask mask{d_mask, mask_words, d_depth, true};       // a NULL d_mask is refused: this entry has no causal form
+    return guarded([&] { return g_engine->attend_chunk(n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new,
+                                                       seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
+                                                       sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), &mask, &n_splits, &window); });
+}
+
 speckv_status_t speckv_ext_chunk_window_walk(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* base, const uint32_t* n_q,
                                              uint32_t rows_per_pos, uint32_t window, uint32_t* out_first_tile, uint32_t* out_n_tiles)
 {

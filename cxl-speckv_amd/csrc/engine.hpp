@@ -177,8 +177,10 @@ public:
                   uint32_t n_runs, hipStream_t s);
     // engine_chunk.cpp; `mask` = the tree form (speckv_ext_attend_chunk_masked): device words [n_seq][C][words]; `n_splits` = the split
     // entry (speckv_ext_attend_chunk_split): 0 the library's piece rule, 1 whole sequences, N pieces forced (null: whole sequences);
-    // `window` = the window entry (speckv_ext_attend_chunk_window, never with a mask): a row sees its last *window positions (0: all)
-    struct ChunkMask { const uint32_t* d_mask; uint32_t words; };
+    // `window` = the window entry (speckv_ext_attend_chunk_window, never with a mask): a row sees its last *window positions (0: all);
+    // a mask with `by_depth` = the tree-window entry (speckv_ext_attend_chunk_tree_window), the only one that takes a mask AND a
+    // window: d_depth = device depths [n_seq][C], the window over the stored positions goes by a node's depth
+    struct ChunkMask { const uint32_t* d_mask; uint32_t words; const uint32_t* d_depth = nullptr; bool by_depth = false; };
     int attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
                      const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new, const void* d_v_new, uint64_t seq_stride,
                      uint64_t pos_stride, const int32_t* tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride,

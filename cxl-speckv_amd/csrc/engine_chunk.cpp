@@ -1,5 +1,5 @@
 // cxl-speckv_amd/csrc/engine_chunk.cpp -- speckv_ext_attend_chunk / speckv_ext_attend_chunk_masked / speckv_ext_attend_chunk_split /
-// speckv_ext_attend_chunk_window: causal attention of a chunk of new positions per sequence over stored and held positions, one launch -- or, where the stored
+// speckv_ext_attend_chunk_window / speckv_ext_attend_chunk_tree_window: causal attention of a chunk of new positions per sequence over stored and held positions, one launch -- or, where the stored
 // positions are split across the chip, a piece launch and its merge (Engine member; the kernels are in attend_chunk.hip)
 #include "engine_internal.hpp"
 #include "chunk_split.hpp"
@@ -23,18 +23,24 @@ namespace speckv {
 // the unwindowed launch -- the other entries' bits by construction.  Otherwise the whole call runs on the WINDOW instances: a query
 // block walks from its first row's bound, and the pieces are planned by the unchanged chunk_split_plan over the pool tiles that are
 // left from the sequence's first_tile (the first pool tile its position 0 sees) on.
+// `mask->by_depth` (the tree-window entry; the only one that passes a mask AND a window): mask->d_depth = device depths [n_seq][C],
+// read by the kernel in place like the mask.  The engine cannot read either array, so whether the window cuts anything is judged by
+// the same rule as above -- a depth is below n_q -- and a window that cuts nothing issues the unwindowed masked launch.  Otherwise
+// the call runs on the MASKED + WINDOW instances: every block of a sequence walks from first_tile, the pieces are planned as above.
 int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
                          const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new, const void* d_v_new, uint64_t seq_stride,
                          uint64_t pos_stride, const int32_t* tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride,
                          float sm_scale, float* d_out, float* d_lse, hipStream_t s, const ChunkMask* mask, const uint32_t* n_splits,
                          const uint32_t* window)
 {
-    const char* entry = window ? "speckv_ext_attend_chunk_window" : n_splits ? "speckv_ext_attend_chunk_split" : mask ? "speckv_ext_attend_chunk_masked" : "speckv_ext_attend_chunk";
+    const bool by_depth = mask && mask->by_depth;
+    const char* entry = by_depth ? "speckv_ext_attend_chunk_tree_window" : window ? "speckv_ext_attend_chunk_window" : n_splits ? "speckv_ext_attend_chunk_split" : mask ? "speckv_ext_attend_chunk_masked" : "speckv_ext_attend_chunk";
     if (null_) return no_data_path(entry);
     if (!s || !handles || !pos_end || !n_q || !d_q_f16 || !d_k_new || !d_v_new || !d_out) return SPECKV_ERR_INVAL;
     if (rows_per_pos == 0 || rows_per_pos > 16u || (rows_per_pos & (rows_per_pos - 1u)) || C == 0) return SPECKV_ERR_INVAL;
     if (n_splits && *n_splits > kChunkSplitsMax) return SPECKV_ERR_INVAL;
-    if (window && mask) return SPECKV_ERR_INVAL;
+    if (window && mask && !by_depth) return SPECKV_ERR_INVAL;
+    if (by_depth && (!window || !mask->d_depth || reinterpret_cast<uintptr_t>(mask->d_depth) % 4u)) return SPECKV_ERR_INVAL;
     // a row's words cover held positions 0 .. C (a tail and C new positions)
     if (mask && (!mask->d_mask || reinterpret_cast<uintptr_t>(mask->d_mask) % 4u || mask->words < (static_cast<uint64_t>(C) + 32u) / 32u))
         return SPECKV_ERR_INVAL;
@@ -157,6 +163,7 @@ int Engine::attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer
     ca.part = part;
     ca.n_items = first_item;
     ca.window = win;
+    ca.depth = win && by_depth ? mask->d_depth : nullptr;
     HIP_TRY(launch_attend_chunk(ca, s));
     for (uint32_t i = 0; i < n_seq; ++i) note_use(as[i], s);     // speckv_free waits for this stream
     if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel

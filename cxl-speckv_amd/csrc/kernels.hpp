@@ -194,9 +194,13 @@ struct ChunkArgs {
     // kChunkPartBytes, partial (item, head) at part + (item * heads + head) * kChunkPartBytes; n_items = the sum of blocks x pieces
     uint8_t*        part;
     uint32_t        n_items;
-    // window form (0: none; never with a mask): query position j sees the absolute positions [max(0, P + 1 - window), P],
-    // P = pos_end + base + j (chunk_window.hpp)
+    // window form (0: none): query position j sees the absolute positions [max(0, P + 1 - window), P], P = pos_end + base + j
+    // (chunk_window.hpp); with a mask only together with `depth`
     uint32_t        window;
+    // tree form under a window (null: none; needs mask and window): depth[i * C + j] = the depth of node j of sequence i in its tree
+    // (0: a child of the committed context), the j of its lower bound over the STORED positions; the held part is what the mask
+    // says.  The last member: the members the other forms read keep their places.
+    const uint32_t* depth;
 };
 // part == null: ONE launch of n_blocks * heads workgroups.  Otherwise TWO: n_items * heads workgroups that write their partials, then
 // the merge (k_chunk_combine) over n_blocks * heads, which reads a row's partials in ascending piece order and writes out / lse.

@@ -31,6 +31,8 @@ paged-attention layer would talk to for a BATCH of requests:
                                word per (request, node); then the accepted root-to-node path is committed
   chunk_tree_masks             trees of ANY size (``attend_chunk(parents=...)``, ``speckv_ext_attend_chunk_masked``): mask rows of several
                                words per node, one launch; ``commit(nodes=path)`` stores the accepted path
+  attend_tree                  the tree step of a layer, global or LOCAL (sliding window): a node's window goes by its DEPTH
+                               (``chunk_tree_depths``, ``chunk_tree_masks(window=W)``, ``speckv_ext_attend_chunk_tree_window``)
 
 Only plain device pointers cross into the library; torch is used for device buffers and the tail fold.
 """
@@ -113,6 +115,7 @@ class SpeckvKVConnector:
         self._spec_key = self._spec_idx = self._spec_base = None     # attend_spec: where the held rows of a step come from
         self._tree_key = self._tree_masks = None                     # attend_spec(parents=...): the mask words of a step, [n_layers * batch][S]
         self._chunk_tree_key = self._chunk_tree_masks = None         # attend_chunk(parents=...): the mask rows of a step, [batch][S][W]
+        self._chunk_tree_wtabs = {}                                  # attend_tree(window=W): W -> (key, mask rows, depths [batch][S])
 
     def set_k_channel_scale(self, scale):
         """Per-(layer, kv head, channel) pre-scale of K, folded into the query: K / scale goes into the pool, q * scale meets it, q.k is
@@ -837,14 +840,33 @@ class SpeckvKVConnector:
         return [[int(p) for p in tree] for tree in trees]
 
     @staticmethod
-    def chunk_tree_masks(parents, base, n_new=None):
+    def chunk_tree_depths(parents, batch=1):
+        """The depth of every node of a tree step, as speckv_ext_attend_chunk_tree_window takes it: [batch][S] ints, 0 for a child of
+        the committed context (parents[j] < 0), otherwise the parent's depth + 1 -- node j of a request of `length` positions sits at
+        the absolute position length + depth.  parents [S] (one tree for all `batch` requests) or [batch][S], judged as
+        chunk_tree_masks judges them.  Dead nodes have depths like any other.  Pure python, no device."""
+        depths = []
+        for tree in SpeckvKVConnector._chunk_tree_parents(parents, int(batch)):
+            d = []
+            for p in tree:
+                d.append(0 if p < 0 else d[p] + 1)
+            depths.append(d)
+        return depths
+
+    @staticmethod
+    def chunk_tree_masks(parents, base, n_new=None, window=None):
         """The mask rows of a step whose S new positions form a tree of ANY size, as speckv_ext_attend_chunk_masked takes them:
         [batch][S][W] ints, W = (S + 1 + 31) // 32 words of 32 bits per node.  parents, base, n_new as tree_masks: parents [S] or
         [batch][S] with parents[j] in -1 .. j-1; base[b] in {0, 1}: the request's odd last position, visible to every node.  Bit t of a
         row (bit t & 31 of word t >> 5) = held position t: node j's row = the low base[b] bits, and the bits base[b] + a of its
         ancestors a and of j itself.  Nodes >= n_new[b] and every node below a dead one get all-zero rows (the kernel neither computes
         nor writes them).  For S <= 16 the single word is tree_masks' word; a chain gives (1 << (base + j + 1)) - 1 across the words.
+        window (None or 0: none, the rows above; W >= 1 as speckv_ext_attend_chunk_tree_window takes them, the window folded in): node j
+        of depth d sits at the absolute position P = length + d and sees [max(0, P + 1 - W), P] on its root path, so its row keeps the
+        tail's bit iff d + 2 <= W (the tail is the position in front of depth 0), the bit of ancestor a iff depth(a) > d - W, and its
+        own bit always; which rows are dead does not depend on the window.  None of it depends on the request's length.
         Pure python, no device."""
+        window = SpeckvKVConnector._chunk_window(window)
         base = [int(x) for x in base]
         trees = SpeckvKVConnector._chunk_tree_parents(parents, len(base))
         if not trees:
@@ -864,6 +886,18 @@ class SpeckvKVConnector:
             for j, p in enumerate(tree):
                 up = ((1 << x) - 1) if p < 0 else bits[p]                 # what the parent sees (0: the parent is dead)
                 bits.append(up | 1 << (x + j) if j < n and (p < 0 or bits[p]) else 0)
+            if window:                                                    # a live row keeps itself and W - 1 positions up its path
+                depth, cut = [], []
+                for j, p in enumerate(tree):
+                    depth.append(0 if p < 0 else depth[p] + 1)
+                    v, a = 0, j
+                    for _ in range(min(depth[j] + 1, window)):
+                        v |= 1 << (x + a)
+                        a = tree[a]
+                    if x and depth[j] + 2 <= window:
+                        v |= 1
+                    cut.append(v if bits[j] else 0)
+                bits = cut
             rows.append([[(v >> (32 * w)) & 0xFFFFFFFF for w in range(W)] for v in bits])
         return rows
 
@@ -882,6 +916,49 @@ class SpeckvKVConnector:
             words = np.asarray(rows, dtype=np.uint32).view(np.int32)
             self._chunk_tree_key, self._chunk_tree_masks = tkey, torch.from_numpy(words).pin_memory().to("cuda", non_blocking=True)
         return self._chunk_tree_masks
+
+    def _chunk_tree_window_table(self, key, reqs, parents, live, S, window):
+        """(mask rows with the window folded in, depths) of a tree step on a local layer on the device, int32 [batch][S][W] and
+        [batch][S], kept per (batch, epoch, S, tree, live counts, window) as _chunk_tree_table keeps its rows: one table per window
+        value beside the global layers' one, so a model's local and global layers each find theirs at every layer of a step."""
+        import numbers
+        import numpy as np
+        import torch
+        one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)
+        tkey = (key, self._epoch, S, tuple(parents) if one else tuple(map(tuple, parents)), tuple(live), window)
+        held = self._chunk_tree_wtabs.get(window)
+        if held is None or held[0] != tkey:
+            rows = self.chunk_tree_masks(parents, [r.length & 1 for r in reqs], live, window=window)
+            if len(rows[0]) != S:
+                raise ValueError("parents: one entry per new position")
+            on_device = lambda a: torch.from_numpy(a).pin_memory().to("cuda", non_blocking=True)
+            words = np.asarray(rows, dtype=np.uint32).view(np.int32)
+            depths = np.asarray(self.chunk_tree_depths(parents, len(reqs)), dtype=np.uint32).view(np.int32)
+            if len(self._chunk_tree_wtabs) >= 4:                          # window values of layers long gone
+                self._chunk_tree_wtabs.clear()
+            held = self._chunk_tree_wtabs[window] = (tkey, on_device(words), on_device(depths))
+        return held[1], held[2]
+
+    def attend_tree(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, parents, n_new=None, stream=None, splits=1,
+                    window=None):
+        """The TREE step of one layer, global or local: attend_chunk(parents=...) with a window that goes by a node's DEPTH.  Shapes,
+        n_new, splits, stream, the K pre-scale and the result (zeros for dead nodes) are attend_chunk's; `parents` is required.
+        window None or 0 (a global layer): exactly attend_chunk(layer, ..., parents=parents, splits=splits) -- the same call, the
+        same bits.  window W >= 1 (a local layer): node j of depth d (chunk_tree_depths) sits at the absolute position P = length + d
+        and sees the positions [max(0, P + 1 - W), P] ON ITS ROOT PATH: the stored positions from that bound on, the odd last
+        position iff d + 2 <= W, ancestor a iff depth(a) > d - W, itself always (W = 1: its own V row).  ONE call
+        (speckv_ext_attend_chunk_tree_window): the library bounds the stored positions by the depth table, the held part is the mask
+        rows with the window folded in (chunk_tree_masks(window=W)); both tables are built once per (batch, lengths, tree, n_new, W)
+        and shared by the layers of a step, next to the global layers' table.  The cost follows W, not the context: every query block
+        walks the pool tiles from depth 0's bound on.  A window no node can lose a position under (length + S <= W) runs the
+        unwindowed launch, bit for bit.  A chain given as a tree agrees with attend_chunk(window=W) within the error bound, not bit
+        for bit.  Afterwards commit(req_ids, k_new, v_new, nodes=accepted path), as for any tree step.  Anything attend_chunk
+        refuses is a ValueError here, with its message, before any library call."""
+        if not self._chunk_window(window):
+            if parents is None:
+                raise ValueError("parents: ints, or one list of ints per request")
+            return self.attend_chunk(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents=parents, splits=splits)
+        return self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, splits, window, True)
 
     def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None,
                      splits=1, window=None):
@@ -920,14 +997,20 @@ class SpeckvKVConnector:
         walks only the tiles its rows see (chunk_window_walk), so the cost follows W, not the context; a window no row of the step
         loses a position under issues the unwindowed launch, bit for bit.  The query stays fp16 in all pool formats; the K
         pre-scale, the tails and the strides are those of the path above.  Not with `parents` (a node's position in a tree is its
-        depth, not its index): ValueError, as for a bool, a negative or a non-integer, before any library call.  Records below a
-        window stay in the pool: nothing is freed."""
+        depth, not its index: attend_tree is the tree step of a local layer): ValueError, as for a bool, a negative or a
+        non-integer, before any library call.  Records below a window stay in the pool: nothing is freed."""
+        return self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, splits, window, False)
+
+    def _chunk_step(self, layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, splits, window, by_depth):
+        """attend_chunk's body; by_depth: attend_tree's call under a window -- `parents` is required and the window goes by depth"""
         import numbers
         import numpy as np
         import torch
         window = self._chunk_window(window)
-        if window and parents is not None:
+        if window and parents is not None and not by_depth:
             raise ValueError("window does not combine with parents: a windowed layer takes a chain of new positions, not a tree")
+        if by_depth and parents is None:
+            raise ValueError("parents: ints, or one list of ints per request")
         if isinstance(splits, bool) or not isinstance(splits, numbers.Integral) or not 0 <= splits <= 64:
             raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
         splits = int(splits)
@@ -978,6 +1061,14 @@ class SpeckvKVConnector:
                         rank += 1
                 kt = self._fold_k.data_ptr() + 2 * layer * row if rank else 0
                 vt = self._fold_v.data_ptr() + 2 * layer * row if rank else 0
+                if window and by_depth:
+                    masks, depths = self._chunk_tree_window_table(key, reqs, parents, live, S, window)
+                    self.lib.attend_chunk_tree_window(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                                      np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
+                                                      v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx,
+                                                      kt, vt, self.L * row, masks.data_ptr(), masks.shape[2], depths.data_ptr(), window, splits,
+                                                      sm_scale, out.data_ptr(), 0, st.cuda_stream)
+                    return out
                 if window:
                     self.lib.attend_chunk_window(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
                                                  np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),

@@ -76,6 +76,9 @@ _EXT_SIGNATURES = {
                                        c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p,
                                        c_void_p],
     "speckv_ext_chunk_window_walk": [c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p],
+    "speckv_ext_attend_chunk_tree_window": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_uint32,
+                                            c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
     "speckv_ext_bind_request": [c_uint32, c_uint64, c_uint32],
@@ -389,6 +392,22 @@ class SpeckvLib:
         self._ext("speckv_ext_attend_chunk_window", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
                   seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, window, n_splits, sm_scale,
                   c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+
+    def attend_chunk_tree_window(self, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx,
+                                 d_k_tail, d_v_tail, tail_stride, d_mask, mask_words, d_depth, window, n_splits, sm_scale, d_out, d_lse, stream):
+        """attend_chunk_split with a mask for a draft tree on a sliding-window (local) layer (speckv_ext_attend_chunk_tree_window):
+        d_depth = device uint32 [n][C], the depth of every node; node j at the absolute position P = pos_end + base + depth[j] sees the
+        STORED positions [max(0, P + 1 - window), pos_end) and of the held positions what d_mask says -- the caller folds the window
+        into the mask (SpeckvKVConnector.chunk_tree_masks(window=...)), so both come from the same tree.  window 0, or one that cuts
+        nothing, issues attend_chunk_split's launches and bits.  The other arguments as attend_chunk_split."""
+        n = len(handles)
+        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
+        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
+        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
+        self._ext("speckv_ext_attend_chunk_tree_window", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new),
+                  c_void_p(d_v_new), seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride,
+                  c_void_p(d_mask or None), mask_words, c_void_p(d_depth or None), window, n_splits, sm_scale, c_void_p(d_out),
+                  c_void_p(d_lse or None), c_void_p(stream))
 
     def chunk_window_walk(self, pos_end, base, n_q, rows_per_pos, window):
         """The walk rule of attend_chunk_window (speckv_ext_chunk_window_walk; works without init, needs no device): (first_tile,

@@ -853,7 +853,8 @@ speckv_status_t speckv_ext_chunk_split_plan(uint32_t n_seq, const uint32_t* pos_
 /* speckv_ext_attend_chunk_window: speckv_ext_attend_chunk_split for a SLIDING-WINDOW (local) layer -- the models that interleave
  * local and global attention layers (the Mistral family, Gemma 2 / 3, gpt-oss) call this entry on their local layers and the other
  * chunk entries on their global ones.  The arguments of speckv_ext_attend_chunk_split in the same order with its two mask arguments
- * replaced by `window`; there is no tree form under a window (a node's position in a tree is its depth, not its index).  Everything
+ * replaced by `window`; this entry has no tree form (a node's position in a tree is its depth, not its index: a draft tree on a
+ * local layer goes to speckv_ext_attend_chunk_tree_window, at the end of this header).  Everything
  * said at speckv_ext_attend_chunk and speckv_ext_attend_chunk_split holds -- layouts, the fp16 query, rows of positions >= n_q[i] are
  * NOT WRITTEN, n_splits, ordering, NOT capturable into a HIP graph, what is refused -- except what a row sees.
  *   window == W >= 1 (one value for all sequences of the call): query position j of sequence i sits at the absolute position
@@ -896,6 +897,49 @@ speckv_status_t speckv_ext_attend_chunk_window(uint32_t n_seq, const speckv_hand
 speckv_status_t speckv_ext_chunk_window_walk(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* base /* may be NULL */,
                                              const uint32_t* n_q, uint32_t rows_per_pos, uint32_t window,
                                              uint32_t* out_first_tile, uint32_t* out_n_tiles);
+
+/* speckv_ext_attend_chunk_tree_window: a DRAFT TREE on a SLIDING-WINDOW (local) layer -- the tree step of the local layers of the
+ * models speckv_ext_attend_chunk_window names, whose global layers take the tree step through speckv_ext_attend_chunk_masked / _split.
+ * The arguments of speckv_ext_attend_chunk_split in the same order with `d_depth, window` directly behind mask_words.  Everything
+ * said at speckv_ext_attend_chunk_masked and speckv_ext_attend_chunk_split holds -- layouts, the fp16 query, the numbering of the
+ * held positions, liveness (j < n_q[i] AND the row's own bit), rows that are not live are NOT WRITTEN, n_splits, ordering, NOT
+ * capturable into a HIP graph, what is refused -- except what a live row sees of the STORED positions.
+ *   Sequence i holds length = pos_end[i] + base positions (base = 1 with a tail, else 0) and brings a tree of new nodes; node j has
+ *   depth(j) = 0 where its parent is the committed context, else depth(parent) + 1, and sits at the absolute position
+ *   P_j = length + depth(j).  Under window == W >= 1 it sees the absolute positions [lo_j, P_j] ON ITS OWN ROOT PATH,
+ *   lo_j = max(0, P_j + 1 - W):
+ *     stored position t  iff lo_j <= t < pos_end[i];
+ *     the tail           iff base == 1 and pos_end[i] >= lo_j;
+ *     ancestor a         iff length + depth(a) >= lo_j, i.e. depth(a) > depth(j) - W;
+ *     itself             always (W == 1: the node's own V row).
+ *   d_depth : device, uint32 [n_seq][C]; d_depth[i * C + j] = depth(j).  4-byte aligned; read by the kernel in place.
+ *   d_mask  : as speckv_ext_attend_chunk_masked, with the window ALREADY FOLDED IN by the caller: of the held positions (tail,
+ *             ancestors, itself) a row's bits keep those the rules above let it see.
+ * THE LIBRARY APPLIES THE WINDOW TO THE STORED POSITIONS ONLY, by d_depth.  The held part is exactly what d_mask says -- the kernel
+ * applies no lower bound there -- so d_mask and d_depth MUST COME FROM THE SAME TREE (SpeckvKVConnector.chunk_tree_masks(window=W)
+ * and chunk_tree_depths build the pair).  There is no causal form: d_mask == NULL is refused.
+ * The library cannot read the device arrays.  With window == 0, and with a window no node can lose a position under
+ * (pos_end[i] + base + n_q[i] <= W for every sequence: a depth is below n_q[i]), the call issues exactly the launches of
+ * speckv_ext_attend_chunk_split with this mask: the same output bits, d_depth is not read.  Otherwise the whole call runs on the
+ * tree-window form of the kernel: every query block of a sequence walks the pool tiles from floor(lo(depth 0) / 32) on (depths are
+ * not ordered by node index, so nothing is derived from a block's first row), then all held tiles as the masked form does; n_splits
+ * cuts the pool tiles that are left by the rule of speckv_ext_chunk_split_plan, as speckv_ext_attend_chunk_window does.  A chain
+ * given as a tree (parent j - 1, depth j) gives what speckv_ext_attend_chunk_window gives within the entry's error bound, not bit
+ * for bit.  Records below a window stay in the pool: nothing is freed.
+ *   SPECKV_ERR_INVAL    as speckv_ext_attend_chunk_split, and: d_mask or d_depth NULL or not 4-byte aligned, mask_words <
+ *                       (C + 1 + 31) / 32 -- nothing is launched
+ *   SPECKV_ERR_NOMEM    the scratch buffer could not grow -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle */
+speckv_status_t speckv_ext_attend_chunk_tree_window(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer,
+                                                    const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                                    const uint32_t* pos_end, const uint32_t* n_q /* host arrays [n_seq] */,
+                                                    const void* d_k_new, const void* d_v_new, uint64_t seq_stride_elems,
+                                                    uint64_t pos_stride_elems,
+                                                    const int32_t* tail_idx /* host [n_seq], < 0 = none; may be NULL */,
+                                                    const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,
+                                                    const uint32_t* d_mask, uint32_t mask_words,
+                                                    const uint32_t* d_depth, uint32_t window /* 0: none */, uint32_t n_splits,
+                                                    float sm_scale, float* d_out, float* d_lse, void* stream);
 
 #ifdef __cplusplus
 }
