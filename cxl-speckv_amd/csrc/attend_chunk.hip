@@ -490,23 +490,22 @@ __global__ __launch_bounds__(kChunkThreads) void k_chunk_combine(ChunkArgs a)
     if (a.lse && c4 == 0u) ck_st<float>(a.lse + row_idx, (M + __builtin_amdgcn_logf(l_sum)) * kLn2);
 }
 
+// The instance of a call, by what its arguments carry: a mask, a partial buffer (pieces: n_items work items and the merge behind
+// them; otherwise n_blocks query blocks), a window.
 template <int SCHEME>
 hipError_t launch_chunk(const ChunkArgs& a, hipStream_t s)
 {
-    if (a.part) {
-        if (a.window && a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, true, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
-        else if (a.window) hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, true, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
-        else if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, true, false>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
-        else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, true, false>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_chunk_combine, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
-        return hipGetLastError();
-    }
-    if (a.window && a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, false, true>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
-    else if (a.window) hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, false, true>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
-    else if (a.mask) hipLaunchKernelGGL((k_attend_chunk<SCHEME, true, false, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
-    else hipLaunchKernelGGL((k_attend_chunk<SCHEME, false, false, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    using Kernel = void (*)(ChunkArgs);
+    static constexpr Kernel kInstance[2][2][2] = {                 // [MASKED][SPLIT][WINDOW]
+        {{k_attend_chunk<SCHEME, false, false, false>, k_attend_chunk<SCHEME, false, false, true>},
+         {k_attend_chunk<SCHEME, false, true, false>, k_attend_chunk<SCHEME, false, true, true>}},
+        {{k_attend_chunk<SCHEME, true, false, false>, k_attend_chunk<SCHEME, true, false, true>},
+         {k_attend_chunk<SCHEME, true, true, false>, k_attend_chunk<SCHEME, true, true, true>}}};
+    hipLaunchKernelGGL(kInstance[a.mask != nullptr][a.part != nullptr][a.window != 0u], dim3((a.part ? a.n_items : a.n_blocks) * a.heads),
+                       dim3(kChunkThreads), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !a.part) return e;
+    hipLaunchKernelGGL(k_chunk_combine, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
     return hipGetLastError();
 }
 

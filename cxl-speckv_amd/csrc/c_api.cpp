@@ -810,15 +810,19 @@ uint64_t speckv_ext_pool_shard_pages(uint64_t n_pages, uint32_t n_pool, uint32_t
     return speckv::shard_pages(n_pages, n_pool, pool_index);
 }
 
+// The arguments all five chunk-attention entries share, under the names every entry gives them and in ChunkCall's order: an entry
+// starts its call description from them and sets the fields of its own form (otherwise whole sequences, no mask, no window).
+#define CHUNK_SHARED __func__, n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride_elems, \
+                     pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems, sm_scale, d_out, d_lse
+
 speckv_status_t speckv_ext_attend_chunk(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C,
                                         uint32_t rows_per_pos, const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new, const void* d_v_new,
                                         uint64_t seq_stride_elems, uint64_t pos_stride_elems, const int32_t* tail_idx, const void* d_k_tail,
                                         const void* d_v_tail, uint64_t tail_stride_elems, float sm_scale, float* d_out, float* d_lse, void* stream)
 {
     LOCK; NEED_INIT;
-    return guarded([&] { return g_engine->attend_chunk(n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new,
-                                                       seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
-                                                       sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream)); });
+    const speckv::Engine::ChunkCall c{CHUNK_SHARED};
+    return guarded([&] { return g_engine->attend_chunk(c, static_cast<hipStream_t>(stream)); });
 }
 
 const char* speckv_ext_backend(void) { return "hip"; }
@@ -830,10 +834,9 @@ speckv_status_t speckv_ext_attend_chunk_masked(uint32_t n_seq, const speckv_hand
                                                uint32_t mask_words, float sm_scale, float* d_out, float* d_lse, void* stream)
 {
     LOCK; NEED_INIT;
-    const speckv::Engine::ChunkMask mask{d_mask, mask_words};
-    return guarded([&] { return g_engine->attend_chunk(n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new,
-                                                       seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
-                                                       sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), &mask); });
+    speckv::Engine::ChunkCall c{CHUNK_SHARED};
+    c.masked = true; c.d_mask = d_mask; c.mask_words = mask_words;                 // a NULL d_mask is refused
+    return guarded([&] { return g_engine->attend_chunk(c, static_cast<hipStream_t>(stream)); });
 }
 
 speckv_status_t speckv_ext_attend_chunk_split(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C,
@@ -843,11 +846,10 @@ speckv_status_t speckv_ext_attend_chunk_split(uint32_t n_seq, const speckv_handl
                                               uint32_t mask_words, uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream)
 {
     LOCK; NEED_INIT;
-    const speckv::Engine::ChunkMask mask{d_mask, mask_words};
-    return guarded([&] { return g_engine->attend_chunk(n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new,
-                                                       seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
-                                                       sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), d_mask ? &mask : nullptr,
-                                                       &n_splits); });
+    speckv::Engine::ChunkCall c{CHUNK_SHARED};
+    c.masked = d_mask != nullptr; c.d_mask = d_mask; c.mask_words = mask_words;    // the header's rule: d_mask == NULL is the causal form
+    c.n_splits = n_splits;
+    return guarded([&] { return g_engine->attend_chunk(c, static_cast<hipStream_t>(stream)); });
 }
 
 speckv_status_t speckv_ext_attend_chunk_window(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C,
@@ -857,9 +859,9 @@ speckv_status_t speckv_ext_attend_chunk_window(uint32_t n_seq, const speckv_hand
                                                uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream)
 {
     LOCK; NEED_INIT;
-    return guarded([&] { return g_engine->attend_chunk(n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new,
-                                                       seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
-                                                       sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), nullptr, &n_splits, &window); });
+    speckv::Engine::ChunkCall c{CHUNK_SHARED};
+    c.n_splits = n_splits; c.window = window;
+    return guarded([&] { return g_engine->attend_chunk(c, static_cast<hipStream_t>(stream)); });
 }
 
 speckv_status_t speckv_ext_attend_chunk_tree_window(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16,
@@ -871,10 +873,11 @@ speckv_status_t speckv_ext_attend_chunk_tree_window(uint32_t n_seq, const speckv
                                                     float sm_scale, float* d_out, float* d_lse, void* stream)
 {
     LOCK; NEED_INIT;
-    const speckv::Engine::ChunkMask mask{d_mask, mask_words, d_depth, true};       // a NULL d_mask is refused: this entry has no causal form
-    return guarded([&] { return g_engine->attend_chunk(n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new,
-                                                       seq_stride_elems, pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems,
-                                                       sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), &mask, &n_splits, &window); });
+    speckv::Engine::ChunkCall c{CHUNK_SHARED};
+    c.masked = true; c.d_mask = d_mask; c.mask_words = mask_words;                 // a NULL d_mask or d_depth is refused: this entry
+    c.by_depth = true; c.d_depth = d_depth;                                        // has no causal form
+    c.n_splits = n_splits; c.window = window;
+    return guarded([&] { return g_engine->attend_chunk(c, static_cast<hipStream_t>(stream)); });
 }
 
 speckv_status_t speckv_ext_chunk_window_walk(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* base, const uint32_t* n_q,

@@ -175,17 +175,18 @@ public:
                    uint32_t n_layers, uint64_t layer_stride, hipStream_t s);
     int copy_runs(const uint64_t* src, const uint64_t* dst, const uint64_t* n_pages, uint32_t n_pairs, const uint64_t* run_firsts,
                   uint32_t n_runs, hipStream_t s);
-    // engine_chunk.cpp; `mask` = the tree form (speckv_ext_attend_chunk_masked): device words [n_seq][C][words]; `n_splits` = the split
-    // entry (speckv_ext_attend_chunk_split): 0 the library's piece rule, 1 whole sequences, N pieces forced (null: whole sequences);
-    // `window` = the window entry (speckv_ext_attend_chunk_window, never with a mask): a row sees its last *window positions (0: all);
-    // a mask with `by_depth` = the tree-window entry (speckv_ext_attend_chunk_tree_window), the only one that takes a mask AND a
-    // window: d_depth = device depths [n_seq][C], the window over the stored positions goes by a node's depth
-    struct ChunkMask { const uint32_t* d_mask; uint32_t words; const uint32_t* d_depth = nullptr; bool by_depth = false; };
-    int attend_chunk(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
-                     const uint32_t* pos_end, const uint32_t* n_q, const void* d_k_new, const void* d_v_new, uint64_t seq_stride,
-                     uint64_t pos_stride, const int32_t* tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride,
-                     float sm_scale, float* d_out, float* d_lse, hipStream_t s, const ChunkMask* mask = nullptr,
-                     const uint32_t* n_splits = nullptr, const uint32_t* window = nullptr);
+    // One chunk-attention call, filled in by its C entry: `entry` = that entry's name, for messages; the arguments all five entries
+    // share; then the forms as plain values (n_splits 1 = whole sequences, window 0 = none), described above Engine::attend_chunk
+    struct ChunkCall {
+        const char* entry;
+        uint32_t n_seq; const uint64_t* handles; uint32_t layer; const void* d_q_f16; uint32_t C, rows_per_pos;
+        const uint32_t *pos_end, *n_q; const void *d_k_new, *d_v_new; uint64_t seq_stride, pos_stride;
+        const int32_t* tail_idx; const void *d_k_tail, *d_v_tail; uint64_t tail_stride; float sm_scale; float *d_out, *d_lse;
+        bool masked = false; const uint32_t* d_mask = nullptr; uint32_t mask_words = 0;
+        bool by_depth = false; const uint32_t* d_depth = nullptr;
+        uint32_t n_splits = 1, window = 0;
+    };
+    int attend_chunk(const ChunkCall& c, hipStream_t s);
     int read(uint64_t handle, uint64_t off, void* dst, size_t len, bool on_device);
     int fetch_range(uint64_t handle, uint64_t first, uint64_t n, void* d_dst, bool f32, hipStream_t s, int engine_choice);
     int fetch_list(uint64_t handle, const uint32_t* d_pages, uint32_t n, void* d_dst, bool f32, hipStream_t s);

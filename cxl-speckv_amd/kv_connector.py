@@ -36,6 +36,7 @@ paged-attention layer would talk to for a BATCH of requests:
 
 Only plain device pointers cross into the library; torch is used for device buffers and the tail fold.
 """
+import numbers
 from typing import Dict, List, Optional, Sequence
 
 from .speckv_ctypes import HELD_MAX, SpeckvLib
@@ -77,6 +78,11 @@ def _device_index(values):
     """int32 index tensor on the device without a blocking copy (torch.tensor(list, device="cuda") waits for the stream)."""
     import torch
     return torch.tensor(values, dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
+
+
+def _is_int(x):
+    """an integer of any kind (python's, numpy's), but no bool"""
+    return isinstance(x, numbers.Integral) and not isinstance(x, bool)
 
 
 class SpeckvKVConnector:
@@ -564,7 +570,6 @@ class SpeckvKVConnector:
     def _tree_parents(parents, batch):
         """parents as one list per request: [S] is the same tree for every request, [batch][S] one tree each.  Every entry an int in
         -1 .. j-1 (a parent precedes its children), 1 .. SPECKV_HELD_MAX - 1 nodes, the same count for every request."""
-        import numbers
         parents = list(parents)
         if parents and not isinstance(parents[0], numbers.Integral):
             trees = [list(p) for p in parents]
@@ -714,13 +719,12 @@ class SpeckvKVConnector:
         for 0.  Returns (counts, firsts): the per-request block counts and their exclusive prefix -- the rule by which the kernel finds
         the request of a flat block index (the last request whose prefix is <= the index; requests without blocks share their
         successor's prefix and are passed over).  Pure python, no device."""
-        import numbers
-        if isinstance(rows_per_pos, bool) or not isinstance(rows_per_pos, numbers.Integral) or rows_per_pos not in (1, 2, 4, 8, 16):
+        if not _is_int(rows_per_pos) or rows_per_pos not in (1, 2, 4, 8, 16):
             raise ValueError("rows_per_pos must be 1, 2, 4, 8 or 16 (query rows per kv head of one position)")
         per = 64 // int(rows_per_pos)
         counts, firsts, total = [], [], 0
         for n in n_new:
-            if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+            if not _is_int(n) or n < 0:
                 raise ValueError(f"n_new: counts of positions >= 0, not {n!r}")
             counts.append((int(n) + per - 1) // per)
             firsts.append(total)
@@ -745,15 +749,12 @@ class SpeckvKVConnector:
         takes n_pool's place above.  Piece p then covers pool tiles [first + p * tpp, min(first + (p + 1) * tpp, n_pool)), clipped
         from below by the block's first tile (chunk_window_walk), and the last piece goes on through the held tiles from the later
         of its start and that tile; a piece that is not the last can be empty for later blocks."""
-        import numbers
-        if isinstance(splits, bool) or not isinstance(splits, numbers.Integral) or not 0 <= splits <= 64:
+        if not _is_int(splits) or not 0 <= splits <= 64:
             raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
-        if isinstance(n_cus, bool) or not isinstance(n_cus, numbers.Integral) or n_cus < 0:
+        if not _is_int(n_cus) or n_cus < 0:
             raise ValueError("n_cus: the compute units of the device (0: 256)")
         counts, _ = SpeckvKVConnector.chunk_blocks(n_new, rows_per_pos)
-        stored = list(stored)
-        if len(stored) != len(counts) or any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or s < 0 for s in stored):
-            raise ValueError("stored: one count of positions >= 0 per request")
+        stored = SpeckvKVConnector._chunk_stored(stored, len(counts))
         most = int(splits)
         if splits == 0:
             g0, target = 8 * sum(counts), 3 * (int(n_cus) or 256)
@@ -779,12 +780,19 @@ class SpeckvKVConnector:
     @staticmethod
     def _chunk_window(window):
         """window as attend_chunk takes it: None or 0 -> 0 (none), an int >= 1 -> itself; anything else is a ValueError"""
-        import numbers
         if window is None:
             return 0
-        if isinstance(window, bool) or not isinstance(window, numbers.Integral) or not 0 <= window <= 0xFFFFFFFF:
+        if not _is_int(window) or not 0 <= window <= 0xFFFFFFFF:
             raise ValueError("window must be None or 0 (no window) or a count of positions >= 1")
         return int(window)
+
+    @staticmethod
+    def _chunk_stored(stored, n):
+        """stored as chunk_pieces and chunk_window_walk take it, as a list: n counts of positions >= 0; anything else is a ValueError"""
+        stored = list(stored)
+        if len(stored) != n or not all(_is_int(s) and s >= 0 for s in stored):
+            raise ValueError("stored: one count of positions >= 0 per request")
+        return stored
 
     @staticmethod
     def chunk_window_walk(n_new: Sequence[int], stored: Sequence[int], rows_per_pos: int, window):
@@ -797,12 +805,9 @@ class SpeckvKVConnector:
         lo(j_first) < pos_end, otherwise n_pool + ((lo(j_first) - pos_end) >> 5) -- exactly the tiles that hold a position a live row
         of the block sees, never more than ceil((W + 64 // rows_per_pos - 1) / 32) + 2.  Returns one list per request of
         (t_first, tile count) per block.  Pure python, no device."""
-        import numbers
         window = SpeckvKVConnector._chunk_window(window)
         counts, _ = SpeckvKVConnector.chunk_blocks(n_new, rows_per_pos)
-        stored = list(stored)
-        if len(stored) != len(counts) or any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or s < 0 for s in stored):
-            raise ValueError("stored: one count of positions >= 0 per request")
+        stored = SpeckvKVConnector._chunk_stored(stored, len(counts))
         per, walks = 64 // int(rows_per_pos), []
         for n, blocks, s in zip(n_new, counts, stored):
             pos_end, base = int(s) & ~1, int(s) & 1
@@ -819,7 +824,6 @@ class SpeckvKVConnector:
     def _chunk_tree_parents(parents, batch):
         """_tree_parents without its bound on the node count: parents as one list per request ([S] is the same tree for every request,
         [batch][S] one tree each), every entry an int in -1 .. j-1, S >= 1 nodes, the same count for every request."""
-        import numbers
         parents = list(parents)
         if parents and not isinstance(parents[0], numbers.Integral):
             try:
@@ -835,6 +839,7 @@ class SpeckvKVConnector:
             if len(tree) != S or S < 1:
                 raise ValueError("parents: at least one node, the same count for every request")
             for j, p in enumerate(tree):
+                # spelled out, not _is_int: this runs per node of every tree at every layer's call, where a function call per node shows
                 if not isinstance(p, numbers.Integral) or isinstance(p, bool) or not -1 <= p < j:
                     raise ValueError(f"parents[{j}] = {p!r}: a node's parent is -1 (the committed context) or a node in front of it")
         return [[int(p) for p in tree] for tree in trees]
@@ -904,7 +909,6 @@ class SpeckvKVConnector:
     def _chunk_tree_table(self, key, reqs, parents, live, S):
         """The mask rows of a tree chunk step on the device, int32 [batch][S][W] (bit patterns of the uint32 words), kept per (batch,
         epoch, S, tree, live counts) the way _tree_table keeps its words: every layer's call of a step finds the same table."""
-        import numbers
         import numpy as np
         import torch
         one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)      # one tree for every request
@@ -921,7 +925,6 @@ class SpeckvKVConnector:
         """(mask rows with the window folded in, depths) of a tree step on a local layer on the device, int32 [batch][S][W] and
         [batch][S], kept per (batch, epoch, S, tree, live counts, window) as _chunk_tree_table keeps its rows: one table per window
         value beside the global layers' one, so a model's local and global layers each find theirs at every layer of a step."""
-        import numbers
         import numpy as np
         import torch
         one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)
@@ -1003,7 +1006,6 @@ class SpeckvKVConnector:
 
     def _chunk_step(self, layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, splits, window, by_depth):
         """attend_chunk's body; by_depth: attend_tree's call under a window -- `parents` is required and the window goes by depth"""
-        import numbers
         import numpy as np
         import torch
         window = self._chunk_window(window)
@@ -1011,7 +1013,7 @@ class SpeckvKVConnector:
             raise ValueError("window does not combine with parents: a windowed layer takes a chain of new positions, not a tree")
         if by_depth and parents is None:
             raise ValueError("parents: ints, or one list of ints per request")
-        if isinstance(splits, bool) or not isinstance(splits, numbers.Integral) or not 0 <= splits <= 64:
+        if not _is_int(splits) or not 0 <= splits <= 64:
             raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
         splits = int(splits)
         if self.scheme not in FUSED:
@@ -1063,44 +1065,27 @@ class SpeckvKVConnector:
                 vt = self._fold_v.data_ptr() + 2 * layer * row if rank else 0
                 if window and by_depth:
                     masks, depths = self._chunk_tree_window_table(key, reqs, parents, live, S, window)
-                    self.lib.attend_chunk_tree_window(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
-                                                      np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
-                                                      v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx,
-                                                      kt, vt, self.L * row, masks.data_ptr(), masks.shape[2], depths.data_ptr(), window, splits,
-                                                      sm_scale, out.data_ptr(), 0, st.cuda_stream)
-                    return out
-                if window:
-                    self.lib.attend_chunk_window(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
-                                                 np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
-                                                 v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
-                                                 self.L * row, window, splits, sm_scale, out.data_ptr(), 0, st.cuda_stream)
-                    return out
-                if splits != 1:
+                    entry, form = "attend_chunk_tree_window", (masks.data_ptr(), masks.shape[2], depths.data_ptr(), window, splits)
+                elif window:
+                    entry, form = "attend_chunk_window", (window, splits)
+                else:
                     masks = None if parents is None else self._chunk_tree_table(key, reqs, parents, live, S)
-                    self.lib.attend_chunk_split(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
-                                                np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
-                                                v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
-                                                self.L * row, 0 if masks is None else masks.data_ptr(), 0 if masks is None else masks.shape[2],
-                                                splits, sm_scale, out.data_ptr(), 0, st.cuda_stream)
-                    return out
-                if parents is not None:
-                    masks = self._chunk_tree_table(key, reqs, parents, live, S)
-                    self.lib.attend_chunk_masked(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
-                                                 np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
-                                                 v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
-                                                 self.L * row, masks.data_ptr(), masks.shape[2], sm_scale, out.data_ptr(), 0, st.cuda_stream)
-                    return out
-                self.lib.attend_chunk(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
-                                      np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
-                                      v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
-                                      self.L * row, sm_scale, out.data_ptr(), 0, st.cuda_stream)
+                    mask = (0, 0) if masks is None else (masks.data_ptr(), masks.shape[2])
+                    if splits != 1:
+                        entry, form = "attend_chunk_split", mask + (splits,)
+                    else:
+                        entry, form = ("attend_chunk", ()) if masks is None else ("attend_chunk_masked", mask)
+                # what every entry takes up to the tail stride, the form's own arguments in front of sm_scale, what closes every entry
+                getattr(self.lib, entry)(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                         np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
+                                         v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
+                                         self.L * row, *form, sm_scale, out.data_ptr(), 0, st.cuda_stream)
         return out
 
     def _tree_table(self, key, reqs, parents, n_new, n_layers, S):
         """The mask words of a tree step on the device, int32 [n_layers * batch][S] (every layer the same words), kept per
         (batch, epoch, layers, S, tree, live counts) as the gather indices of _held_rows are: the per-layer calls of a step find them
         there -- the tree is judged (tree_masks) when the words are made, a call that finds them compares two tuples."""
-        import numbers
         one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)      # one tree for every request
         tkey = (key, self._epoch, n_layers, S, tuple(parents) if one else tuple(map(tuple, parents)), None if n_new is None else tuple(n_new))
         if self._tree_key != tkey:

@@ -9,6 +9,11 @@ import ctypes
 from ctypes import (c_char_p, c_float, c_int, c_int32, c_size_t, c_uint8, c_uint16, c_uint32, c_uint64, c_void_p)
 
 
+def as_arr(v, t, n):
+    """v as the C array argument `t v[n]`: a ctypes array as it is, a numpy array by its own data pointer (no copy), a sequence copied"""
+    return v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
+
+
 class SpeckvError(RuntimeError):
     """RuntimeError carrying the speckv_status_t code."""
 
@@ -281,8 +286,7 @@ class SpeckvLib:
     def write_strided_batch(self, handles, first_pages, d_srcs, page_step, n_pages_each, stream):
         """One launch for a batch of allocations: handles[i] gets pages first_pages[i] + j*page_step from d_srcs[i] + j*4096."""
         n = len(handles)
-        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
-        hs, fs, ps = as_arr(handles, c_uint64), as_arr(first_pages, c_uint64), as_arr(d_srcs, c_void_p)     # numpy uint64 arrays pass as they are
+        hs, fs, ps = as_arr(handles, c_uint64, n), as_arr(first_pages, c_uint64, n), as_arr(d_srcs, c_void_p, n)     # numpy uint64 arrays pass as they are
         self._ext("speckv_ext_write_strided_batch", hs, fs, ps, n, page_step, n_pages_each, c_void_p(stream))
 
     def write_async(self, handle, offset, d_src, nbytes, stream):
@@ -300,7 +304,6 @@ class SpeckvLib:
         handles[i], each page read from two rows -- rows[i] = (K even, K odd, V even, V odd) device addresses, layer_stride bytes
         apart per layer.  handles / first_pages: uint64 arrays of n; rows: a uint64 array [n][4] (numpy arrays pass as they are)."""
         n = len(handles)
-        as_arr = lambda v, t, m: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * m)(*v))
         if not hasattr(rows, "ctypes") and not isinstance(rows, ctypes.Array):
             rows = [p for r in rows for p in r]
         hs, fs, rs = as_arr(handles, c_uint64, n), as_arr(first_pages, c_uint64, n), as_arr(rows, c_uint64, 4 * n)
@@ -311,7 +314,6 @@ class SpeckvLib:
         (j < 2*n_layers) of handles[i], each page decoded into two rows -- rows[i] = (K even, K odd, V even, V odd) device addresses,
         layer_stride bytes apart per layer; an address of 0 = that row is not wanted and is not written.  Arguments as write_pairs."""
         n = len(handles)
-        as_arr = lambda v, t, m: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * m)(*v))
         if not hasattr(rows, "ctypes") and not isinstance(rows, ctypes.Array):
             rows = [p for r in rows for p in r]
         hs, fs, rs = as_arr(handles, c_uint64, n), as_arr(first_pages, c_uint64, n), as_arr(rows, c_uint64, 4 * n)
@@ -323,9 +325,18 @@ class SpeckvLib:
         one entry per pair; numpy uint64 arrays, ctypes arrays or sequences.  One source may feed several destinations; a destination
         appears once and is no source of the same call."""
         n, m = len(src), len(run_firsts)
-        as_arr = lambda v, t, k: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * k)(*v))
         ss, ds, ns, fs = as_arr(src, c_uint64, n), as_arr(dst, c_uint64, n), as_arr(n_pages, c_uint64, n), as_arr(run_firsts, c_uint64, m)
         self._ext("speckv_ext_copy_runs", ss, ds, ns, n, fs, m, c_void_p(stream))
+
+    def _chunk(self, entry, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx, d_k_tail,
+               d_v_tail, tail_stride, form, sm_scale, d_out, d_lse, stream):
+        """One call of a chunk-attention entry: the 16 arguments all five share (n_seq from handles, then up to tail_stride), `form` -- the
+        entry's own arguments, already as C values -- in their place in front of sm_scale, and the four that close every entry."""
+        n = len(handles)
+        self._ext(entry, n, as_arr(handles, c_uint64, n), layer, c_void_p(d_q), C, rows_per_pos, as_arr(pos_end, c_uint32, n),
+                  as_arr(n_q, c_uint32, n), c_void_p(d_k_new), c_void_p(d_v_new), seq_stride, pos_stride,
+                  None if tail_idx is None else as_arr(tail_idx, c_int32, n), c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride,
+                  *form, sm_scale, c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
 
     def attend_chunk(self, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx, d_k_tail,
                      d_v_tail, tail_stride, sm_scale, d_out, d_lse, stream):
@@ -333,13 +344,8 @@ class SpeckvLib:
         position (tail_idx[i] >= 0: that row of d_k_tail / d_v_tail) and the new positions themselves, ONE launch for any chunk length
         (speckv_ext_attend_chunk; the query stays fp16).  handles, pos_end, n_q, tail_idx: one entry per sequence -- numpy arrays
         (uint64 / uint32 / int32), ctypes arrays or sequences; tail_idx may be None.  Strides in fp16 elements; d_lse may be 0."""
-        n = len(handles)
-        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
-        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
-        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
-        self._ext("speckv_ext_attend_chunk", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
-                  seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, sm_scale, c_void_p(d_out),
-                  c_void_p(d_lse or None), c_void_p(stream))
+        self._chunk("speckv_ext_attend_chunk", handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride,
+                    tail_idx, d_k_tail, d_v_tail, tail_stride, (), sm_scale, d_out, d_lse, stream)
 
     def attend_chunk_masked(self, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx,
                             d_k_tail, d_v_tail, tail_stride, d_mask, mask_words, sm_scale, d_out, d_lse, stream):
@@ -347,13 +353,8 @@ class SpeckvLib:
         t of a query position's row = HELD position t (the tail, if any, is 0; new position a is base + a) is visible to it, under the
         causal bound t < base + j + 1; a row whose own bit is clear is not written.  mask_words >= (C + 32) // 32.  The other arguments
         as attend_chunk."""
-        n = len(handles)
-        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
-        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
-        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
-        self._ext("speckv_ext_attend_chunk_masked", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
-                  seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, c_void_p(d_mask or None),
-                  mask_words, sm_scale, c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+        self._chunk("speckv_ext_attend_chunk_masked", handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride,
+                    pos_stride, tail_idx, d_k_tail, d_v_tail, tail_stride, (c_void_p(d_mask or None), mask_words), sm_scale, d_out, d_lse, stream)
 
     def attend_chunk_split(self, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx,
                            d_k_tail, d_v_tail, tail_stride, d_mask, mask_words, n_splits, sm_scale, d_out, d_lse, stream):
@@ -362,13 +363,9 @@ class SpeckvLib:
         per sequence (from the sequence alone), 0 = the library's rule (chunk_split_plan; from the whole call).  With pieces: a piece
         launch and a merge on `stream`; a row's bits depend on its sequence's piece count.  The other arguments as
         attend_chunk_masked."""
-        n = len(handles)
-        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
-        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
-        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
-        self._ext("speckv_ext_attend_chunk_split", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
-                  seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, c_void_p(d_mask or None),
-                  mask_words, n_splits, sm_scale, c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+        self._chunk("speckv_ext_attend_chunk_split", handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride,
+                    pos_stride, tail_idx, d_k_tail, d_v_tail, tail_stride, (c_void_p(d_mask or None), mask_words, n_splits), sm_scale, d_out,
+                    d_lse, stream)
 
     def chunk_split_plan(self, pos_end, n_q, rows_per_pos, n_splits=0, n_cus=0):
         """The piece rule of attend_chunk_split (speckv_ext_chunk_split_plan; works without init): (pieces, tiles_per_piece), one entry
@@ -385,13 +382,8 @@ class SpeckvLib:
         absolute position P = pos_end + base + j sees the positions [max(0, P + 1 - window), P]; window 0 = none.  A window under which
         no row loses a position issues attend_chunk_split's launches and bits; otherwise a query block walks only the tiles its rows
         see (chunk_window_walk) and n_splits cuts the pool tiles that are left.  The other arguments as attend_chunk_split."""
-        n = len(handles)
-        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
-        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
-        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
-        self._ext("speckv_ext_attend_chunk_window", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new), c_void_p(d_v_new),
-                  seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride, window, n_splits, sm_scale,
-                  c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+        self._chunk("speckv_ext_attend_chunk_window", handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride,
+                    pos_stride, tail_idx, d_k_tail, d_v_tail, tail_stride, (window, n_splits), sm_scale, d_out, d_lse, stream)
 
     def attend_chunk_tree_window(self, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx,
                                  d_k_tail, d_v_tail, tail_stride, d_mask, mask_words, d_depth, window, n_splits, sm_scale, d_out, d_lse, stream):
@@ -400,14 +392,9 @@ class SpeckvLib:
         STORED positions [max(0, P + 1 - window), pos_end) and of the held positions what d_mask says -- the caller folds the window
         into the mask (SpeckvKVConnector.chunk_tree_masks(window=...)), so both come from the same tree.  window 0, or one that cuts
         nothing, issues attend_chunk_split's launches and bits.  The other arguments as attend_chunk_split."""
-        n = len(handles)
-        as_arr = lambda v, t: v if isinstance(v, ctypes.Array) else (c_void_p(v.ctypes.data) if hasattr(v, "ctypes") else (t * n)(*v))
-        hs, pe, nq = as_arr(handles, c_uint64), as_arr(pos_end, c_uint32), as_arr(n_q, c_uint32)
-        ti = None if tail_idx is None else as_arr(tail_idx, ctypes.c_int32)
-        self._ext("speckv_ext_attend_chunk_tree_window", n, hs, layer, c_void_p(d_q), C, rows_per_pos, pe, nq, c_void_p(d_k_new),
-                  c_void_p(d_v_new), seq_stride, pos_stride, ti, c_void_p(d_k_tail or None), c_void_p(d_v_tail or None), tail_stride,
-                  c_void_p(d_mask or None), mask_words, c_void_p(d_depth or None), window, n_splits, sm_scale, c_void_p(d_out),
-                  c_void_p(d_lse or None), c_void_p(stream))
+        self._chunk("speckv_ext_attend_chunk_tree_window", handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride,
+                    pos_stride, tail_idx, d_k_tail, d_v_tail, tail_stride,
+                    (c_void_p(d_mask or None), mask_words, c_void_p(d_depth or None), window, n_splits), sm_scale, d_out, d_lse, stream)
 
     def chunk_window_walk(self, pos_end, base, n_q, rows_per_pos, window):
         """The walk rule of attend_chunk_window (speckv_ext_chunk_window_walk; works without init, needs no device): (first_tile,
