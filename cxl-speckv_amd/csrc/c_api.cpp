@@ -880,6 +880,16 @@ speckv_status_t speckv_ext_attend_chunk_tree_window(uint32_t n_seq, const speckv
     return guarded([&] { return g_engine->attend_chunk(c, static_cast<hipStream_t>(stream)); });
 }
 
+speckv_status_t speckv_ext_attend_prefix_fold(uint32_t n_groups, const speckv_handle_t* prefix_handles, const uint32_t* first_member,
+                                              uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos, const uint32_t* prefix_len,
+                                              const uint32_t* n_q, uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    const speckv::Engine::PrefixCall c{n_groups, prefix_handles, first_member, layer, d_q_f16, C, rows_per_pos, prefix_len, n_q, n_splits,
+                                       sm_scale, d_out, d_lse};
+    return guarded([&] { return g_engine->attend_prefix(c, static_cast<hipStream_t>(stream)); });
+}
+
 speckv_status_t speckv_ext_chunk_window_walk(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* base, const uint32_t* n_q,
                                              uint32_t rows_per_pos, uint32_t window, uint32_t* out_first_tile, uint32_t* out_n_tiles)
 {

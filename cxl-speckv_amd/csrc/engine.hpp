@@ -187,6 +187,12 @@ public:
         uint32_t n_splits = 1, window = 0;
     };
     int attend_chunk(const ChunkCall& c, hipStream_t s);
+    // One shared-prefix call (speckv_ext_attend_prefix_fold), described above Engine::attend_prefix (engine_prefix.cpp)
+    struct PrefixCall {
+        uint32_t n_groups; const uint64_t* handles; const uint32_t* first_member; uint32_t layer; const void* d_q_f16; uint32_t C, rows_per_pos;
+        const uint32_t *prefix_len, *n_q; uint32_t n_splits; float sm_scale; float *d_out, *d_lse;
+    };
+    int attend_prefix(const PrefixCall& c, hipStream_t s);
     int read(uint64_t handle, uint64_t off, void* dst, size_t len, bool on_device);
     int fetch_range(uint64_t handle, uint64_t first, uint64_t n, void* d_dst, bool f32, hipStream_t s, int engine_choice);
     int fetch_list(uint64_t handle, const uint32_t* d_pages, uint32_t n, void* d_dst, bool f32, hipStream_t s);

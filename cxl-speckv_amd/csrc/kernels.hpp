@@ -207,6 +207,42 @@ struct ChunkArgs {
 // Nothing is launched for n_blocks == 0.
 hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s);
 
+// One group of a shared-prefix launch (PrefixArgs::groups; attend_prefix.hip): a prefix allocation (table row, K / V pages as in
+// ChunkSeq) and the members [first_member, first_member + n_pairs / C) of the call, whose query rows see its stored positions
+// [0, prefix_len[member]).  max_len (even) = the largest prefix_len of the group's live members: the tiles a block walks.  n_pairs =
+// members x C flat (member, position) pairs, cut into blocks of 64 / rows_per_pos; first_block / first_item = the host's exclusive
+// prefixes over blocks and over blocks x pieces, as in ChunkSeq.  A group without a live pair has no blocks.
+struct PrefixGroup {
+    uint32_t table_row;
+    uint32_t max_len;
+    uint32_t first_member;
+    uint32_t n_pairs;
+    uint64_t k_first;
+    uint64_t v_first;
+    uint32_t first_block;
+    uint32_t first_item;
+    uint32_t n_pieces;
+    uint32_t tiles_per_piece;
+};
+struct PrefixArgs {
+    const PrefixGroup* groups;        // device array
+    const uint32_t* prefix_len;       // device array [n_members]: even, the stored positions of its group's prefix the member sees
+    const uint32_t* n_q;              // device array [n_members]: live positions of the member, <= C
+    const DevAlloc* tab;              // the device allocation table
+    const _Float16* q;                // [n_members][C][heads][rows_per_pos][128]
+    float*          out;              // as q, fp32: read and written (the fold)
+    float*          lse;              // [n_members][C][heads][rows_per_pos], natural log: read and written
+    uint8_t*        part;             // split form (null: none): n_items * heads partials of kChunkPartBytes, as ChunkArgs::part
+    uint32_t        n_groups, n_blocks, n_items;
+    uint32_t        C, rows_per_pos, heads;
+    float           sm_scale;
+    int             scheme;           // kFp8E4m3, kInt4G32 or kMxFp4
+};
+// part == null: ONE launch of n_blocks * heads workgroups that fold into out / lse.  Otherwise TWO: n_items * heads workgroups that
+// write their partials, then k_prefix_combine over n_blocks * heads, which merges a row's pieces in ascending order and folds.
+// Nothing is launched for n_blocks == 0.
+hipError_t launch_attend_prefix(const PrefixArgs& a, hipStream_t s);
+
 // Source / destination description of one codec launch.  Exactly one of
 // {entries, recs, tab+alloc_list} is used as the record source.
 struct CodecArgs {

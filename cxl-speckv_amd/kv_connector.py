@@ -33,6 +33,10 @@ paged-attention layer would talk to for a BATCH of requests:
                                words per node, one launch; ``commit(nodes=path)`` stores the accepted path
   attend_tree                  the tree step of a layer, global or LOCAL (sliding window): a node's window goes by its DEPTH
                                (``chunk_tree_depths``, ``chunk_tree_masks(window=W)``, ``speckv_ext_attend_chunk_tree_window``)
+  attend_shared                requests that SHARE A PREFIX without copies of it (parallel samples, beams, a system prompt): the members
+                               hold only what is their own, the prefix is a request the call names; the own step as attend / attend_chunk
+                               issue it, then ONE ``speckv_ext_attend_prefix_fold`` launch that reads the prefix once per 64 query rows
+                               and folds it in (``attend_chunk_shared`` for a member's own chunk; ``shared_groups``)
 
 Only plain device pointers cross into the library; torch is used for device buffers and the tail fold.
 """
@@ -122,6 +126,7 @@ class SpeckvKVConnector:
         self._tree_key = self._tree_masks = None                     # attend_spec(parents=...): the mask words of a step, [n_layers * batch][S]
         self._chunk_tree_key = self._chunk_tree_masks = None         # attend_chunk(parents=...): the mask rows of a step, [batch][S][W]
         self._chunk_tree_wtabs = {}                                  # attend_tree(window=W): W -> (key, mask rows, depths [batch][S])
+        self._shared_key = self._shared_plan = None                  # attend_shared / attend_chunk_shared: the judged arguments of a step
 
     def set_k_channel_scale(self, scale):
         """Per-(layer, kv head, channel) pre-scale of K, folded into the query: K / scale goes into the pool, q * scale meets it, q.k is
@@ -488,6 +493,11 @@ class SpeckvKVConnector:
         """The same for n_layers consecutive layers whose query rows exist at once (speckv_ext_attend_planned_layers): q
         [n_layers][batch][heads][g][dim] fp16, returns [n_layers][batch][heads][g][dim] fp32.  One library call; over an MXFP4 pool
         with a batch that fills the chip, one launch.  window=W: the layers are sliding-window layers of that window (attend)."""
+        return self._attend_layers_lse(layer_begin, n_layers, req_ids, q, sm_scale, stream, window)[0]
+
+    def _attend_layers_lse(self, layer_begin, n_layers, req_ids, q, sm_scale, stream, window):
+        """attend_layers' body: (out, lse [n_layers][batch][heads][g] fp32, the query as the launches read it -- contiguous, the K
+        pre-scale applied)"""
         import torch
         W = self._decode_window(window)
         if self.scheme not in FUSED:
@@ -531,7 +541,7 @@ class SpeckvKVConnector:
             else:
                 self.lib.attend_planned_layers(self.scheme, plan.data_ptr(), B, layer_begin, n_layers, q.data_ptr(), G, bound, sm_scale,
                                                out.data_ptr(), lse.data_ptr(), st.cuda_stream, n_tail, rows, idx, kt, vt, self.L * self.H * self.D)
-        return out
+        return out, lse, q
 
     # ------------------------------------------------------------------ steps of several positions
     @staticmethod
@@ -1004,8 +1014,10 @@ class SpeckvKVConnector:
         non-integer, before any library call.  Records below a window stay in the pool: nothing is freed."""
         return self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, splits, window, False)
 
-    def _chunk_step(self, layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, splits, window, by_depth):
-        """attend_chunk's body; by_depth: attend_tree's call under a window -- `parents` is required and the window goes by depth"""
+    def _chunk_step(self, layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, splits, window, by_depth, keep_lse=False):
+        """attend_chunk's body; by_depth: attend_tree's call under a window -- `parents` is required and the window goes by depth.
+        keep_lse (attend_chunk_shared): the same calls with d_lse given; returns (out, lse [batch][S][heads][rows_per_pos] fp32 with
+        -inf where nothing was written, the query as the launch read it)"""
         import numpy as np
         import torch
         window = self._chunk_window(window)
@@ -1042,8 +1054,9 @@ class SpeckvKVConnector:
             if trees and len(trees[0]) != S:
                 raise ValueError("parents: one entry per new position")
         out = (torch.empty if n_new is None and parents is None else torch.zeros)((B, S, H, R, D), dtype=torch.float32, device="cuda")
+        lse = torch.full((B, S, H, R), float("-inf"), dtype=torch.float32, device="cuda") if keep_lse else None
         if not any(counts):
-            return out
+            return (out, lse, q.contiguous()) if keep_lse else out
         row = self.H * self.D
         with self._On(self, stream) as st:
             with torch.cuda.stream(st):
@@ -1079,7 +1092,188 @@ class SpeckvKVConnector:
                 getattr(self.lib, entry)(handles, layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
                                          np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
                                          v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx, kt, vt,
-                                         self.L * row, *form, sm_scale, out.data_ptr(), 0, st.cuda_stream)
+                                         self.L * row, *form, sm_scale, out.data_ptr(), lse.data_ptr() if keep_lse else 0, st.cuda_stream)
+        return (out, lse, q) if keep_lse else out
+
+    # ------------------------------------------------------------------ a prefix shared by several requests
+    @staticmethod
+    def shared_groups(req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]]):
+        """How a call over members with shared prefixes is laid out for speckv_ext_attend_prefix_fold: (order, prefixes, first_member).
+        order = the indices 0..batch-1 so that the members of one prefix are adjacent -- the prefixes in the order of their first
+        member, the members of a prefix in the caller's order (stable), the members without a prefix (None) last, in the caller's order;
+        prefixes = the prefix id of every group; first_member = the exclusive prefix of the groups' sizes, len(prefixes) + 1 entries
+        (the members behind first_member[-1] have no prefix).  An input that is already laid out so gives order == list(range(batch))."""
+        if len(prefix_ids) != len(req_ids):
+            raise ValueError("prefix_ids: one prefix id or None per request")
+        groups, none = {}, []
+        for b, p in enumerate(prefix_ids):
+            (none if p is None else groups.setdefault(p, [])).append(b)
+        order, first = [], [0]
+        for members in groups.values():
+            order += members
+            first.append(len(order))
+        return order + none, list(groups), first
+
+    def _shared_args(self, req_ids, prefix_ids, prefix_lens, splits, what):
+        """The shared-prefix arguments of a call, judged in front of any library call and kept for the other layers of the step: the
+        judgement depends on the lists and on what the requests hold, so it is keyed by the lists (values AND types: True == 1) and
+        `_epoch`, like the attention plan.  None when no member sees a prefix; otherwise (order or None when the batch is laid out
+        already, the members in that order, the groups' handles, first_member and the members' prefix lengths in that order as the
+        arrays the entry takes).  What is kept holds handles and lengths: it is right only while EVERY method that changes a request's
+        length or handle, or the set of requests, moves `_epoch` (add_request, free_request, write_prefill, append, commit, truncate,
+        fork do) -- a new state-changing method must move it too."""
+        import numpy as np
+        key = (what, self._epoch, tuple(req_ids), tuple(prefix_ids), tuple(map(type, prefix_ids)), type(splits), splits,
+               None if prefix_lens is None else (tuple(prefix_lens), tuple(map(type, prefix_lens))))
+        if self._shared_key == key:
+            return self._shared_plan
+        plan = self._shared_judge(req_ids, prefix_ids, prefix_lens, splits, what)
+        if plan is not None:
+            order, handles, first, lens = plan
+            if order is not None:
+                req_ids, lens = [req_ids[b] for b in order], [lens[b] for b in order]
+            plan = (order, list(req_ids), np.asarray(handles, dtype=np.uint64), np.asarray(first, dtype=np.uint32), np.asarray(lens, dtype=np.uint32))
+        self._shared_key, self._shared_plan = key, plan
+        return plan
+
+    def _shared_judge(self, req_ids, prefix_ids, prefix_lens, splits, what):
+        """_shared_args' judgement: (order or None, the groups' handles, first_member, the members' prefix lengths in the CALLER's
+        order) -- or None when no member sees a prefix"""
+        if self.scheme not in FUSED:
+            raise ValueError(f"{what}() needs an FP8, INT4 or MXFP4 pool")
+        B = len(req_ids)
+        if len(prefix_ids) != B or (prefix_lens is not None and len(prefix_lens) != B):
+            raise ValueError("prefix_ids (and prefix_lens): one entry per request")
+        if not _is_int(splits) or not 0 <= splits <= 64:
+            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
+        for r in req_ids:
+            self.requests[r]                                              # KeyError: an unknown member
+        members, lens = set(req_ids), []
+        for b, p in enumerate(prefix_ids):
+            if p is None:
+                if prefix_lens is not None and prefix_lens[b] is not None and (not _is_int(prefix_lens[b]) or prefix_lens[b] != 0):
+                    raise ValueError("prefix_lens: a member without a prefix takes 0 or None")
+                lens.append(0)
+                continue
+            if not _is_int(p):
+                raise ValueError("prefix_ids: request ids (ints) or None")
+            if p not in self.requests:
+                raise KeyError(f"prefix request {p} does not exist")
+            if p in members:
+                raise ValueError(f"request {p} is a member of the call and cannot be its prefix")
+            have = self.requests[p].length
+            if prefix_lens is None or prefix_lens[b] is None:
+                if have & 1:
+                    raise ValueError(f"prefix request {p} holds an odd number of positions ({have}): pass prefix_lens and keep the "
+                                     "last position in the member (only whole stored pairs can be shared)")
+                lens.append(have)
+            else:
+                n = prefix_lens[b]
+                if not _is_int(n) or n < 0 or n & 1 or n > (have & ~1):
+                    raise ValueError(f"prefix_lens: even ints in 0..{have & ~1} for prefix request {p}")
+                lens.append(int(n))
+        if not any(lens):
+            return None
+        order, prefixes, first = self.shared_groups(req_ids, prefix_ids)
+        return (None if order == list(range(B)) else order, [self.requests[p].handle for p in prefixes], first, lens)
+
+    def attend_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, sm_scale: float, prefix_lens=None,
+                      stream=None, splits=0):
+        """attend() for requests that SHARE A PREFIX without holding a copy of it: parallel samples of one prompt, beams, a system
+        prompt in front of many users.  Shapes and result are attend()'s.  The members `req_ids` are ordinary requests that hold only
+        what is their own (add_request, append / commit); a prefix is an ordinary request too, and nothing binds them -- the call
+        names it: prefix_ids[b] = the request whose first prefix_lens[b] stored positions member b sees in front of its own, or None.
+        prefix_lens[b] defaults to the prefix's length, which must then be even (an odd last position is held outside the pool and
+        cannot be shared: pass prefix_lens and keep that position in the member); a given one is even, >= 0 and at most the
+        prefix's length rounded down to even.  Members of one prefix may see different lengths of it and need not be adjacent
+        (shared_groups; q and the result are permuted only when they are not).
+        The step: the members' own attention exactly as attend() issues it (plan, tails, the K pre-scale), with the log-sum-exp kept,
+        then ONE speckv_ext_attend_prefix_fold call on the same stream: a workgroup walks a prefix's records ONCE for 64 query rows of
+        its members and folds the result into theirs -- the softmax over prefix + own positions.  The prefix part takes the query in
+        fp16 in every pool format.  splits: 0 = the library's rule cuts a long prefix of few members across the chip, 1 = never, N =
+        forced (attend_chunk).  No member with a prefix (all None, or all lengths 0): attend()'s launches and bits.
+        When to use which: fork() + attend() copies the prefix per request and reads it once per request and step; it stays the
+        route for a FEW members or a short prefix.  This route reads the prefix once per 64 query rows -- 1/16 of the bytes at 64
+        members of 4 query rows -- and stores it once, but the call has a floor of 0.13 ms.  Measured crossover, 64 own positions
+        per member (profiles/shared_prefix.txt): the smallest member count from which this route is faster -- prefix 2k:
+        256 over an FP8 pool, none up to 256 over INT4 and MXFP4; 8k: 64 over FP8, 256 over INT4 and MXFP4; 32k: 16 over FP8, 64 over
+        INT4 and MXFP4.  At 64 members x 8k x 4 query rows it wins over FP8 (0.159 against 0.206 ms) and is 0.02 - 0.03 ms SLOWER
+        over INT4 and MXFP4.
+        Anything malformed is a ValueError / KeyError before any library call: an unknown prefix, a prefix among the members, lists
+        of the wrong length, bools or non-integers, a pool that is not FP8 / INT4 / MXFP4.  There is no window argument."""
+        import numpy as np
+        import torch
+        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_shared")
+        if len(q.shape) != 4 or q.shape[0] != len(req_ids):
+            raise ValueError("q must be [batch][heads][g][dim]")
+        if plan is None:
+            return self.attend(layer, req_ids, q, sm_scale, stream)
+        order, req_ids, handles, first, lens = plan
+        G = int(q.shape[2])
+        if G not in (1, 2, 4, 8, 16):
+            raise ValueError("attend_shared() takes 1, 2, 4, 8 or 16 query rows per kv head")
+        B = len(req_ids)
+        if order is not None:                                     # the gather runs on the stream the launches go to, as they do
+            with self._On(self, stream) as st, torch.cuda.stream(st):
+                idx, inv = self._shared_permutation(order)
+                q = q.index_select(0, idx)
+            if stream is not None:                                # attend's body scales q on torch's current stream: behind the gather
+                torch.cuda.current_stream().wait_stream(stream)
+        out, lse, qs = self._attend_layers_lse(layer, 1, req_ids, q[None], sm_scale, stream, None)
+        with self._On(self, stream) as st:
+            self.lib.attend_prefix_fold(handles, first, layer, qs.data_ptr(), 1, G, lens, np.ones(B, dtype=np.uint32), int(splits), sm_scale,
+                                        out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+            out = out[0]
+            if order is not None:                                 # and so does the way back: behind the fold, on its stream
+                with torch.cuda.stream(st):
+                    out = out.index_select(0, inv)
+        return out
+
+    @staticmethod
+    def _shared_permutation(order):
+        """(idx, inv) on the device, made on torch's current stream: x.index_select(0, idx) is x in the grouped order,
+        y.index_select(0, inv) is y back in the caller's"""
+        import torch
+        inv = [0] * len(order)
+        for at, b in enumerate(order):
+            inv[b] = at
+        both = torch.tensor([order, inv], dtype=torch.int64).pin_memory().to("cuda", non_blocking=True)
+        return both[0], both[1]
+
+    def attend_chunk_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, k_new, v_new, sm_scale: float,
+                            n_new=None, prefix_lens=None, stream=None, splits=0):
+        """attend_chunk() for members of a shared prefix: the member's OWN chunk -- a user's differing suffix behind a shared system
+        prompt -- attends what the member holds and the chunk causally, as attend_chunk(splits=1) does, and the stored positions
+        [0, prefix_lens[b]) of the request prefix_ids[b] in front of both.  Shapes, n_new, the K pre-scale and the result (zeros for
+        positions >= n_new[b]) are attend_chunk's; prefix_ids, prefix_lens, splits and what is refused are attend_shared's.  The
+        causal chunk route with the log-sum-exp requested, then ONE speckv_ext_attend_prefix_fold call with C = S on the same stream.
+        Changes no state: commit(nodes=range(n)) stores the chunk in the MEMBER afterwards.  No member with a prefix: attend_chunk's
+        launch and bits."""
+        import numpy as np
+        import torch
+        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_chunk_shared")
+        if plan is None:
+            return self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, None, 1, None, False)
+        order, req_ids, handles, first, lens = plan
+        if order is not None:
+            if n_new is not None:
+                if len(n_new) != len(order):
+                    raise ValueError("n_new: one count 0..S per request")
+                n_new = [n_new[b] for b in order]
+            with self._On(self, stream) as st, torch.cuda.stream(st):     # the gather runs on the stream the launches go to
+                idx, inv = self._shared_permutation(order)
+                q, k_new, v_new = q.index_select(0, idx), k_new.index_select(0, idx), v_new.index_select(0, idx)
+        out, lse, qs = self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, None, 1, None, False, keep_lse=True)
+        B, S, _, R, _ = (int(x) for x in qs.shape)
+        live = [S] * B if n_new is None else [int(n) for n in n_new]
+        if any(live) or order is not None:
+            with self._On(self, stream) as st:
+                if any(live):
+                    self.lib.attend_prefix_fold(handles, first, layer, qs.data_ptr(), S, R, lens, np.asarray(live, dtype=np.uint32), int(splits),
+                                                sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+                if order is not None:                             # the way back: behind the fold, on its stream
+                    with torch.cuda.stream(st):
+                        out = out.index_select(0, inv)
         return out
 
     def _tree_table(self, key, reqs, parents, n_new, n_layers, S):

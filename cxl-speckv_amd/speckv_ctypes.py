@@ -84,6 +84,8 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_chunk_tree_window": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_uint32,
                                             c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_prefix_fold": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32,
+                                      ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
     "speckv_ext_bind_request": [c_uint32, c_uint64, c_uint32],
@@ -395,6 +397,20 @@ class SpeckvLib:
         self._chunk("speckv_ext_attend_chunk_tree_window", handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride,
                     pos_stride, tail_idx, d_k_tail, d_v_tail, tail_stride,
                     (c_void_p(d_mask or None), mask_words, c_void_p(d_depth or None), window, n_splits), sm_scale, d_out, d_lse, stream)
+
+    def attend_prefix_fold(self, prefix_handles, first_member, layer, d_q, C, rows_per_pos, prefix_len, n_q, n_splits, sm_scale, d_out, d_lse,
+                           stream):
+        """Shared-prefix attention folded into the members' own result (speckv_ext_attend_prefix_fold): group g = the allocation
+        prefix_handles[g] and the members [first_member[g], first_member[g + 1]) of the call (first_member: n_groups + 1 entries,
+        ascending from 0).  Member m brings n_q[m] <= C positions (rows [m][j] of d_q fp16 / d_out fp32 / d_lse, the chunk entries'
+        layout) that see the stored positions [0, prefix_len[m]) (even) of its group's prefix; d_out / d_lse hold what the member
+        attended on its own (out = 0, lse = -inf: nothing) and are replaced by the softmax over both.  n_splits as attend_chunk_split.
+        prefix_handles, first_member, prefix_len, n_q: numpy arrays (uint64 / uint32), ctypes arrays or sequences; d_lse is required."""
+        n = len(prefix_handles)
+        m = len(prefix_len)
+        self._ext("speckv_ext_attend_prefix_fold", n, as_arr(prefix_handles, c_uint64, n), as_arr(first_member, c_uint32, n + 1), layer,
+                  c_void_p(d_q), C, rows_per_pos, as_arr(prefix_len, c_uint32, m), as_arr(n_q, c_uint32, m), n_splits, sm_scale,
+                  c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
 
     def chunk_window_walk(self, pos_end, base, n_q, rows_per_pos, window):
         """The walk rule of attend_chunk_window (speckv_ext_chunk_window_walk; works without init, needs no device): (first_tile,

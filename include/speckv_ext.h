@@ -898,6 +898,46 @@ speckv_status_t speckv_ext_chunk_window_walk(uint32_t n_seq, const uint32_t* pos
                                              const uint32_t* n_q, uint32_t rows_per_pos, uint32_t window,
                                              uint32_t* out_first_tile, uint32_t* out_n_tiles);
 
+/* speckv_ext_attend_prefix_fold: SHARED-PREFIX (cascade) attention -- the query rows of several requests attend the stored positions
+ * of ONE other allocation, read once per 64 query rows and not once per request, and the result is FOLDED into what each request
+ * attended on its own (parallel samples of one prompt, beams, a system prompt in front of many users).
+ *   Group g (g < n_groups) = the prefix allocation prefix_handles[g] and the MEMBERS [first_member[g], first_member[g + 1]) of the
+ *   call; first_member is a host array [n_groups + 1], ascending from 0; n_members = first_member[n_groups].  A member is a row of the
+ *   caller's arrays, not an allocation: the library never learns which request it belongs to.
+ *   d_q_f16 : device, fp16 [n_members][C][8 kv heads][rows_per_pos][128], 16-byte aligned -- the chunk entries' layout with the
+ *             member in the place of the sequence; C == 1 is a decode step.  THE QUERY STAYS fp16 in all three formats.
+ *   d_out   : device, fp32, the shape of d_q_f16, 16-byte aligned; d_lse : device, fp32 [n_members][C][8][rows_per_pos], natural
+ *             log, REQUIRED.  Both are READ AND WRITTEN.
+ *   prefix_len, n_q : host arrays [n_members].  Every live row of member m sees the stored positions [0, prefix_len[m]) of its
+ *             group's prefix at `layer`; prefix_len[m] is even and at most the layout's num_tokens; two members of a group may see
+ *             different lengths of the same prefix.  Member m brings n_q[m] <= C positions.  Nothing is held: no tail, no new rows,
+ *             no causal structure among the rows.  A (member, position) pair with position >= n_q[m] or prefix_len[m] == 0 is DEAD:
+ *             its q is not read and its out / lse rows are neither read nor written.
+ * THE FOLD.  The call runs on `stream` behind the launches that wrote the members' own (out, lse) -- speckv_ext_attend_*_planned*
+ * for a decode step, speckv_ext_attend_chunk* for a chunk -- and replaces them in place: with lse_p = ln sum exp(score) over the
+ * prefix positions and out_p their normalised attention, new = logaddexp(lse, lse_p), out = out exp(lse - new) + out_p exp(lse_p -
+ * new), lse = new: the softmax over the concatenation.  A member without positions of its own arrives as out = 0, lse = -inf (the
+ * decode entries' result for an empty range) and leaves as exactly out_p, lse_p.
+ *   n_splits : as speckv_ext_attend_chunk_split, over one "sequence" per group with pos_end = the largest prefix_len of the group's
+ *             live members and n_q = members x C (speckv_ext_chunk_split_plan): 1 = one workgroup walks a group's tiles for 64 rows,
+ *             N = that many pieces, 0 = the library's rule.  With pieces: a piece launch and a merge on `stream`, the partials in the
+ *             library's scratch.  A row's bits depend on its group's piece plan and on nothing else of the call.
+ * A block walks the tiles up to its group's largest prefix_len; between a member's prefix_len and that maximum lie records the
+ * member does not see: they are weighed 0, so a NON-FINITE V row stored there gives NaN (0 x NaN).
+ * Ordering as speckv_ext_attend_chunk; speckv_free of a prefix waits for `stream`.  NOT capturable into a HIP graph.
+ *   SPECKV_OK           also for zero groups, zero members and no live pair -- nothing is launched
+ *   SPECKV_ERR_INVAL    a NULL pointer (d_lse included), d_q_f16 / d_out not 16-byte aligned, rows_per_pos not 1, 2, 4, 8 or 16,
+ *                       C == 0, an odd prefix_len or one beyond num_tokens, n_q[m] > C, first_member not ascending from 0, a prefix
+ *                       without layout, a scheme other than FP8 / INT4_G32 / MXFP4 or mixed schemes, layer out of range,
+ *                       n_splits > SPECKV_CHUNK_SPLITS_MAX, more work items than a launch indexes, a capturing stream -- nothing is launched
+ *   SPECKV_ERR_NOMEM    the scratch buffer could not grow -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle */
+speckv_status_t speckv_ext_attend_prefix_fold(uint32_t n_groups, const speckv_handle_t* prefix_handles /* host [n_groups] */,
+                                              const uint32_t* first_member /* host [n_groups + 1] */, uint32_t layer,
+                                              const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                              const uint32_t* prefix_len, const uint32_t* n_q /* host arrays [n_members] */,
+                                              uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream);
+
 /* speckv_ext_attend_chunk_tree_window: a DRAFT TREE on a SLIDING-WINDOW (local) layer -- the tree step of the local layers of the
  * models speckv_ext_attend_chunk_window names, whose global layers take the tree step through speckv_ext_attend_chunk_masked / _split.
  * The arguments of speckv_ext_attend_chunk_split in the same order with `d_depth, window` directly behind mask_words.  Everything
