@@ -30,7 +30,18 @@
 // unchanged, with pos_end = max_len and n_q = members x C); piece p walks [p tpp, min((p + 1) tpp, n_pool)) and writes the chunk
 // kernel's partial (kChunkPartBytes).  A piece beyond a row's prefix_len writes m = -inf, l = 0, zeros.  k_prefix_combine merges a
 // row's pieces in ascending order exactly as k_chunk_combine does and then folds as above.
+//
+// Window form (WINDOW, PrefixArgs::window = W >= 1; speckv_ext_attend_prefix_fold_window: a local layer, decode steps, chunks and
+// draft trees).  The member's own positions lie BEHIND the prefix, so a row sees of the prefix only [lo, prefix_len),
+// lo = prefix_window_lo(prefix_len, own_seen[m], d, W) with d = depth[m * C + j] or, without a table, j (prefix_window.hpp).  A row
+// with lo >= prefix_len sees nothing and is DEAD like a pair beyond n_q -- by the rule, in the piece kernel and in the merge alike.
+// The group's walk starts at PrefixGroup::first_tile, the tile of the lowest depth-0 bound of its live members (the host's:
+// prefix_window_group), so pages below it are never loaded; a score is -inf unless lo <= t < len; the ballot gains the lower test.
+// SPLIT: the pieces cut the tiles that are left, piece p walks from first_tile + p tpp; a piece wholly below a row's lo or beyond
+// its prefix_len writes m = -inf, l = 0, zeros, and the merge gives the unsplit weights (prefix_combine).  Every live row sees
+// position lo, so its sum is never 0 and b stays finite.  The instances without WINDOW are the code above, untouched.
 #include "chunk_device.hpp"
+#include "prefix_window.hpp"
 
 namespace speckv {
 namespace {
@@ -48,16 +59,25 @@ __device__ __forceinline__ uint32_t prefix_group_of(const PrefixArgs& a, uint32_
     return lo;
 }
 
-// Query row qr of block blk of a group: its member, its position, its own prefix_len (0: dead) and where its q / out / lse rows are
-struct PrefixRow { uint32_t len; uint64_t idx; };
+// Query row qr of block blk of a group: its member, its position, its own prefix_len (0: dead) and where its q / out / lse rows are.
+// WINDOW: and its lower bound lo by the rule (prefix_window_lo); a row with lo >= prefix_len comes back dead (len = 0), so the piece
+// kernel and the merge decide a row's life by the same rule and never by what the scratch holds.
+struct PrefixRow { uint32_t len; uint64_t idx; uint32_t lo; };
+template <bool WINDOW = false>
 __device__ __forceinline__ PrefixRow prefix_row(const PrefixArgs& a, uint32_t first_member, uint32_t n_pairs, uint32_t blk, uint32_t qr, uint32_t h)
 {
     const uint32_t rpp = a.rows_per_pos, p = blk * (64u / rpp) + qr / rpp, sub = qr % rpp;
-    PrefixRow r{0u, 0u};
+    PrefixRow r{0u, 0u, 0u};
     if (p >= n_pairs) return r;
     const uint32_t m = first_member + p / a.C, j = p % a.C;
     if (j >= ck_ld<uint32_t>(a.n_q + m)) return r;
-    r.len = ck_ld<uint32_t>(a.prefix_len + m);
+    const uint32_t len = ck_ld<uint32_t>(a.prefix_len + m);
+    if (WINDOW) {
+        const uint32_t d = a.depth ? ck_ld<uint32_t>(a.depth + static_cast<uint64_t>(m) * a.C + j) : j;
+        r.lo = prefix_window_lo(len, ck_ld<uint32_t>(a.own_seen + m), d, a.window);
+        if (r.lo >= len) return PrefixRow{0u, 0u, 0u};
+    }
+    r.len = len;
     r.idx = ((static_cast<uint64_t>(m) * a.C + j) * a.heads + h) * rpp + sub;
     return r;
 }
@@ -72,7 +92,7 @@ __device__ __forceinline__ FoldW fold_weights(float own, float b)
     return FoldW{__builtin_amdgcn_exp2f(a - n), __builtin_amdgcn_exp2f(b - n), n * kLn2};
 }
 
-template <int SCHEME, bool SPLIT>
+template <int SCHEME, bool SPLIT, bool WINDOW>
 __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
 {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufElems];
@@ -92,14 +112,15 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
         blk /= n_pieces;
     }
     const uint32_t n_pool = (max_len + 31u) >> 5, n_pages = max_len >> 1;
-    const uint32_t t_begin = SPLIT ? piece * tpp : 0u;
+    const uint32_t t_first = WINDOW ? static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(gp->first_tile)) : 0u;
+    const uint32_t t_begin = t_first + (SPLIT ? piece * tpp : 0u);
     const uint32_t t_end = SPLIT ? (t_begin + tpp < n_pool ? t_begin + tpp : n_pool) : n_pool;
 
     // compute role: query row qr of the block, contraction group g
     const uint32_t col = lane & 15u, g = lane >> 4;
     const uint32_t qr = 16u * wave + col;
-    const PrefixRow row = prefix_row(a, first_member, n_pairs, blk, qr, h);
-    const bool row_live = row.len != 0u;
+    const PrefixRow row = prefix_row<WINDOW>(a, first_member, n_pairs, blk, qr, h);
+    const bool row_live = row.len != 0u;                      // (WINDOW: and lo < len -- prefix_row)
     if (!__syncthreads_or(row_live)) return;                  // a block of dead pairs (workgroup-uniform)
     if (t_begin >= t_end) return;                             // (never: no piece of the plan is empty)
 
@@ -153,7 +174,8 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
         const bool more = tile + 1u < t_end;
         if (more) load_tile(tile + 1u);
         const uint32_t t_base = 32u * tile;
-        if (__builtin_amdgcn_ballot_w64(row.len > t_base) != 0ull) {          // some row of the wave sees a position of this tile
+        // some row of the wave sees a position of this tile (a dead row has len 0)
+        if (__builtin_amdgcn_ballot_w64(row.len > t_base && (!WINDOW || row.lo < t_base + 32u)) != 0ull) {
             // scores: rows = positions 16 hf + 4 g + r of the tile, column = the lane's query row
             f32x4 sc[2];
 #pragma unroll
@@ -170,12 +192,12 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
 #pragma unroll
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t t = t_base + 16u * (i >> 2) + 4u * g + (i & 3u);
-                sv[i] = t < row.len ? sc[i >> 2][i & 3u] * scale2 : -__builtin_inff();       // the row's own prefix_len
+                sv[i] = t < row.len && (!WINDOW || t >= row.lo) ? sc[i >> 2][i & 3u] * scale2 : -__builtin_inff();   // the row's own range
                 mx = fmaxf(mx, sv[i]);
             }
             mx = max_over_kb(mx);
             const float m_new = fmaxf(m_run, mx);
-            const float m_use = m_new == -__builtin_inff() ? 0.0f : m_new;  // (a row that sees nothing: dead, or a piece beyond its prefix_len)
+            const float m_use = m_new == -__builtin_inff() ? 0.0f : m_new;  // (a row that sees nothing: dead, or a piece outside its range)
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
             float p[8], sum = 0.0f;
 #pragma unroll
@@ -228,8 +250,12 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
 // The merge of the split form: k_chunk_combine's thread roles and order -- one workgroup per (flat block, kv head), thread t = row
 // t >> 2 of the block and the 16-byte columns (t & 3) + 4 k; a live row's n_pieces partials are read in ASCENDING piece order;
 // a piece that saw nothing (m = -inf, l = 0, acc = 0) weighs 2^-inf = 0 exactly -- and then the fold of k_attend_prefix.  Whether a
-// row is live is decided as the pieces decided it, never by what the scratch holds.  Piece 0 saw position 0 of every live row.
-__global__ __launch_bounds__(kChunkThreads) void k_prefix_combine(PrefixArgs a)
+// row is live is decided as the pieces decided it -- by prefix_row's rule -- never by what the scratch holds.  Without a window piece 0
+// saw position 0 of every live row; under one (WINDOW) any number of a live row's pieces, the first ones included, lie wholly below
+// its lo or beyond its prefix_len and saw nothing, but the piece that holds lo saw it: M is finite and is the max over the pieces
+// that saw something (-inf never wins a max), the others weigh 2^(-inf - M) = 0 on l = 0 and zeros -- exactly the unsplit weights.
+template <bool WINDOW>
+__device__ __forceinline__ void prefix_combine(const PrefixArgs& a)
 {
     const uint32_t tid = threadIdx.x;
     const uint32_t h = blockIdx.x % a.heads, fb = blockIdx.x / a.heads;
@@ -238,7 +264,7 @@ __global__ __launch_bounds__(kChunkThreads) void k_prefix_combine(PrefixArgs a)
     const uint32_t n_pieces = __builtin_amdgcn_readfirstlane(gp->n_pieces);
     const uint32_t item = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(gp->first_item)) + blk * n_pieces;
     const uint32_t qr = tid >> 2, c4 = tid & 3u;
-    const PrefixRow row = prefix_row(a, __builtin_amdgcn_readfirstlane(gp->first_member), __builtin_amdgcn_readfirstlane(gp->n_pairs), blk, qr, h);
+    const PrefixRow row = prefix_row<WINDOW>(a, __builtin_amdgcn_readfirstlane(gp->first_member), __builtin_amdgcn_readfirstlane(gp->n_pairs), blk, qr, h);
     if (row.len == 0u) return;
     const uint64_t step = static_cast<uint64_t>(a.heads) * kChunkPartBytes;          // from a piece's partial to the next piece's
     const uint8_t* pb = a.part + (static_cast<uint64_t>(item) * a.heads + h) * kChunkPartBytes;
@@ -269,18 +295,20 @@ __global__ __launch_bounds__(kChunkThreads) void k_prefix_combine(PrefixArgs a)
     }
     if (c4 == 0u) ck_st<float>(a.lse + row.idx, f.lse);
 }
+__global__ __launch_bounds__(kChunkThreads) void k_prefix_combine(PrefixArgs a) { prefix_combine<false>(a); }
+__global__ __launch_bounds__(kChunkThreads) void k_prefix_combine_window(PrefixArgs a) { prefix_combine<true>(a); }
 
-template <int SCHEME>
+template <int SCHEME, bool WINDOW>
 hipError_t launch_prefix(const PrefixArgs& a, hipStream_t s)
 {
     if (!a.part) {
-        hipLaunchKernelGGL((k_attend_prefix<SCHEME, false>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+        hipLaunchKernelGGL((k_attend_prefix<SCHEME, false, WINDOW>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((k_attend_prefix<SCHEME, true>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
+    hipLaunchKernelGGL((k_attend_prefix<SCHEME, true, WINDOW>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_prefix_combine, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+    hipLaunchKernelGGL(WINDOW ? k_prefix_combine_window : k_prefix_combine, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -294,10 +322,18 @@ hipError_t launch_attend_prefix(const PrefixArgs& a, hipStream_t s)
         static_cast<uint64_t>(a.n_blocks) * a.heads > 0x7FFFFFFFull ||
         (a.part && (a.n_items < a.n_blocks || static_cast<uint64_t>(a.n_items) * a.heads > 0x7FFFFFFFull || reinterpret_cast<uintptr_t>(a.part) % 16u)))
         return hipErrorInvalidValue;
+    if (a.window) {                                           // (own_seen and depth are judged by Engine::attend_prefix)
+        switch (a.scheme) {
+        case kFp8E4m3: return launch_prefix<kFp8E4m3, true>(a, s);
+        case kInt4G32: return launch_prefix<kInt4G32, true>(a, s);
+        case kMxFp4: return launch_prefix<kMxFp4, true>(a, s);
+        default: return hipErrorInvalidValue;
+        }
+    }
     switch (a.scheme) {
-    case kFp8E4m3: return launch_prefix<kFp8E4m3>(a, s);
-    case kInt4G32: return launch_prefix<kInt4G32>(a, s);
-    case kMxFp4: return launch_prefix<kMxFp4>(a, s);
+    case kFp8E4m3: return launch_prefix<kFp8E4m3, false>(a, s);
+    case kInt4G32: return launch_prefix<kInt4G32, false>(a, s);
+    case kMxFp4: return launch_prefix<kMxFp4, false>(a, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -15,6 +15,7 @@
 #include "placement.hpp"
 #include "chunk_split.hpp"
 #include "chunk_window.hpp"
+#include "prefix_window.hpp"
 #include "decode_window.hpp"
 
 #include <cstring>
@@ -888,6 +889,29 @@ speckv_status_t speckv_ext_attend_prefix_fold(uint32_t n_groups, const speckv_ha
     const speckv::Engine::PrefixCall c{n_groups, prefix_handles, first_member, layer, d_q_f16, C, rows_per_pos, prefix_len, n_q, n_splits,
                                        sm_scale, d_out, d_lse};
     return guarded([&] { return g_engine->attend_prefix(c, static_cast<hipStream_t>(stream)); });
+}
+
+speckv_status_t speckv_ext_attend_prefix_fold_window(uint32_t n_groups, const speckv_handle_t* prefix_handles, const uint32_t* first_member,
+                                                     uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                                     const uint32_t* prefix_len, const uint32_t* n_q, const uint32_t* own_seen,
+                                                     const uint32_t* d_depth, uint32_t window, uint32_t n_splits, float sm_scale, float* d_out,
+                                                     float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    speckv::Engine::PrefixCall c{n_groups, prefix_handles, first_member, layer, d_q_f16, C, rows_per_pos, prefix_len, n_q, n_splits,
+                                 sm_scale, d_out, d_lse};
+    c.windowed = true; c.own_seen = own_seen; c.d_depth = d_depth; c.window = window;
+    return guarded([&] { return g_engine->attend_prefix(c, static_cast<hipStream_t>(stream)); });
+}
+
+speckv_status_t speckv_ext_prefix_window_walk(uint32_t n_groups, const uint32_t* first_member, const uint32_t* prefix_len,
+                                              const uint32_t* own_seen, const uint32_t* n_q, uint32_t window, uint32_t* out_first_tile,
+                                              uint32_t* out_n_tiles)
+{
+    if (n_groups && (!first_member || !out_first_tile || !out_n_tiles)) return SPECKV_ERR_INVAL;
+    if (n_groups && first_member[0] == 0u && first_member[n_groups] && (!prefix_len || !n_q)) return SPECKV_ERR_INVAL;
+    return speckv::prefix_window_walk(n_groups, first_member, prefix_len, own_seen, n_q, window, out_first_tile, out_n_tiles) ? SPECKV_OK
+                                                                                                                              : SPECKV_ERR_INVAL;
 }
 
 speckv_status_t speckv_ext_chunk_window_walk(uint32_t n_seq, const uint32_t* pos_end, const uint32_t* base, const uint32_t* n_q,

@@ -3,6 +3,7 @@
 // into the (out, lse) each member attended on its own -- one launch, or a piece launch and its merge (kernels: attend_prefix.hip)
 #include "engine_internal.hpp"
 #include "chunk_split.hpp"
+#include "prefix_window.hpp"
 
 namespace speckv {
 
@@ -14,9 +15,16 @@ namespace speckv {
 // descriptors (groups, prefix_len, n_q) travel through a slot of the pinned descriptor ring, so the call cannot be captured into a
 // HIP graph.  n_splits as Engine::attend_chunk: the piece rule is chunk_split_plan, unchanged, over one "sequence" per group with
 // pos_end = the group's largest live prefix_len and n_q = members x C; the partials live in s_chunk_.
+// The window entry (c.windowed: speckv_ext_attend_prefix_fold_window) adds own_seen (host, per member), d_depth (device, may be null)
+// and window.  window == 0, or a window under which no live row can lose a prefix position -- prefix_len[m] + own_seen[m] + n_q[m]
+// - 1 <= W for every member with n_q[m] > 0 and a prefix (a depth is below n_q[m]; d_depth is on the device and is not read here)
+// -- issues exactly the launches above.  Otherwise the WINDOW instances: a group's walk and its live members are
+// prefix_window_group's, chunk_split_plan cuts the tiles that are LEFT from first_tile on, and own_seen travels in the same
+// descriptor slot behind n_q.
 int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
 {
-    if (null_) return no_data_path("speckv_ext_attend_prefix_fold");
+    const char* entry = c.windowed ? "speckv_ext_attend_prefix_fold_window" : "speckv_ext_attend_prefix_fold";
+    if (null_) return no_data_path(entry);
     if (!s || !c.d_q_f16 || !c.d_out || !c.d_lse) return SPECKV_ERR_INVAL;
     if (c.n_groups && (!c.handles || !c.first_member)) return SPECKV_ERR_INVAL;
     if (c.rows_per_pos == 0 || c.rows_per_pos > 16u || (c.rows_per_pos & (c.rows_per_pos - 1u)) || c.C == 0) return SPECKV_ERR_INVAL;
@@ -27,20 +35,32 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
     for (uint32_t g = 0; g < c.n_groups; ++g)
         if (c.first_member[g + 1] < c.first_member[g]) return SPECKV_ERR_INVAL;
     const uint32_t n_members = c.n_groups ? c.first_member[c.n_groups] : 0u;
-    if (n_members && (!c.prefix_len || !c.n_q)) return SPECKV_ERR_INVAL;
+    if (n_members && (!c.prefix_len || !c.n_q || (c.windowed && !c.own_seen))) return SPECKV_ERR_INVAL;
+    if (reinterpret_cast<uintptr_t>(c.d_depth) % 4u) return SPECKV_ERR_INVAL;
     for (uint32_t m = 0; m < n_members; ++m)
         if (c.n_q[m] > c.C || c.prefix_len[m] % 2u) return SPECKV_ERR_INVAL;
     if (is_capturing(s)) {
-        SPECKV_ERR("speckv_ext_attend_prefix_fold cannot be captured into a HIP graph (its descriptors are staged per call)");
+        SPECKV_ERR("%s cannot be captured into a HIP graph (its descriptors are staged per call)", entry);
         return SPECKV_ERR_INVAL;
     }
     const uint32_t per_block = 64u / c.rows_per_pos;
     // per group, as chunk_split_plan takes a sequence: the largest prefix_len of a live member (0: no live pair) and members x C
-    std::vector<uint32_t> max_len(c.n_groups, 0u), pairs(c.n_groups, 0u);
+    uint32_t win = 0;                                             // the window, where it cuts something
+    if (c.windowed && c.window)
+        for (uint32_t m = 0; m < n_members && !win; ++m)
+            if (c.n_q[m] && c.prefix_len[m] && static_cast<uint64_t>(c.prefix_len[m]) + c.own_seen[m] + c.n_q[m] - 1u > c.window) win = c.window;
+    std::vector<uint32_t> max_len(c.n_groups, 0u), pairs(c.n_groups, 0u), first_tile(c.n_groups, 0u);
     uint64_t n_blocks = 0;
     for (uint32_t g = 0; g < c.n_groups; ++g) {
-        for (uint32_t m = c.first_member[g]; m < c.first_member[g + 1]; ++m)
-            if (c.n_q[m] && c.prefix_len[m] > max_len[g]) max_len[g] = c.prefix_len[m];
+        const uint32_t m0 = c.first_member[g];
+        if (win) {                                                 // the members that are live for the fold, and where they start
+            const PrefixWalk w = prefix_window_group(c.first_member[g + 1] - m0, c.prefix_len + m0, c.own_seen + m0, c.n_q + m0, win);
+            max_len[g] = w.max_len;
+            first_tile[g] = w.first_tile;
+        } else {
+            for (uint32_t m = m0; m < c.first_member[g + 1]; ++m)
+                if (c.n_q[m] && c.prefix_len[m] > max_len[g]) max_len[g] = c.prefix_len[m];
+        }
         const uint64_t p = static_cast<uint64_t>(c.first_member[g + 1] - c.first_member[g]) * c.C;
         if (p > 0x7FFFFFFFull) return SPECKV_ERR_INVAL;
         pairs[g] = max_len[g] ? static_cast<uint32_t>(p) : 0u;
@@ -73,7 +93,14 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
     bool split = false;
     uint64_t n_items = n_blocks;
     if (c.n_splits != 1u) {
-        if (!chunk_split_plan(c.n_groups, max_len.data(), pairs.data(), c.rows_per_pos, c.n_splits, cus(), pieces.data(), tpp.data()))
+        const uint32_t* plan_end = max_len.data();
+        std::vector<uint32_t> rest;                                // window: the positions from first_tile on, as whole tiles
+        if (win) {
+            rest.resize(c.n_groups);
+            for (uint32_t g = 0; g < c.n_groups; ++g) rest[g] = 32u * (chunk_pool_tiles(max_len[g]) - first_tile[g]);
+            plan_end = rest.data();
+        }
+        if (!chunk_split_plan(c.n_groups, plan_end, pairs.data(), c.rows_per_pos, c.n_splits, cus(), pieces.data(), tpp.data()))
             return SPECKV_ERR_INVAL;
         n_items = 0;
         for (uint32_t g = 0; g < c.n_groups; ++g) {
@@ -84,11 +111,11 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
     }
     if (!split) {
         n_items = n_blocks;
-        for (uint32_t g = 0; g < c.n_groups; ++g) { pieces[g] = 1u; tpp[g] = chunk_pool_tiles(max_len[g]); }
+        for (uint32_t g = 0; g < c.n_groups; ++g) { pieces[g] = 1u; tpp[g] = chunk_pool_tiles(max_len[g]) - first_tile[g]; }
     }
     DeviceScope device_scope(device_);
     const size_t group_bytes = static_cast<size_t>(c.n_groups) * sizeof(PrefixGroup), member_bytes = static_cast<size_t>(n_members) * sizeof(uint32_t);
-    const size_t bytes = group_bytes + 2u * member_bytes;
+    const size_t bytes = group_bytes + (win ? 3u : 2u) * member_bytes;
     int slot = 0;
     void *staged = nullptr, *d_slot = nullptr;
     RC_TRY(descriptor_slot(bytes, &slot, &staged, &d_slot));      // may release the ABI lock: every prefix is judged again
@@ -104,12 +131,13 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
         const uint64_t k_first = static_cast<uint64_t>(c.layer) * L.num_tokens;
         const uint32_t blocks = (pairs[g] + per_block - 1u) / per_block;
         static_cast<PrefixGroup*>(staged)[g] = PrefixGroup{as[g]->row, max_len[g], c.first_member[g], pairs[g], k_first, k_first + L.num_tokens / 2u,
-                                                           first_block, first_item, pieces[g], tpp[g]};
+                                                           first_block, first_item, pieces[g], tpp[g], first_tile[g]};
         first_block += blocks;
         first_item += blocks * pieces[g];
     }
     memcpy(static_cast<uint8_t*>(staged) + group_bytes, c.prefix_len, member_bytes);
     memcpy(static_cast<uint8_t*>(staged) + group_bytes + member_bytes, c.n_q, member_bytes);
+    if (win) memcpy(static_cast<uint8_t*>(staged) + group_bytes + 2u * member_bytes, c.own_seen, member_bytes);
     for (auto& w : write_evs_)
         if (w.s != s) HIP_TRY(hipStreamWaitEvent(s, w.ev, 0));
     HIP_TRY(hipMemcpyAsync(d_slot, staged, bytes, hipMemcpyHostToDevice, s));
@@ -130,6 +158,11 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
     pa.heads = 8;
     pa.sm_scale = c.sm_scale;
     pa.scheme = scheme;
+    if (win) {
+        pa.own_seen = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(d_slot) + group_bytes + 2u * member_bytes);
+        pa.depth = c.d_depth;
+        pa.window = win;
+    }
     HIP_TRY(launch_attend_prefix(pa, s));
     for (uint32_t g = 0; g < c.n_groups; ++g) note_use(as[g], s);  // speckv_free of a prefix waits for this stream
     if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel

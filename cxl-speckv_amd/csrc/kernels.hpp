@@ -223,6 +223,9 @@ struct PrefixGroup {
     uint32_t first_item;
     uint32_t n_pieces;
     uint32_t tiles_per_piece;
+    uint32_t first_tile;              // window form: the first tile any live row of the group sees (prefix_window.hpp; the walk and
+                                      // the pieces start here); else 0.  (It makes the struct 56 bytes where it was 48: the stride
+                                      // of the group search changed in every instance, the plain ones included.)
 };
 struct PrefixArgs {
     const PrefixGroup* groups;        // device array
@@ -237,6 +240,12 @@ struct PrefixArgs {
     uint32_t        C, rows_per_pos, heads;
     float           sm_scale;
     int             scheme;           // kFp8E4m3, kInt4G32 or kMxFp4
+    // window form (window 0: none; the engine vouches for own_seen and for depth's alignment): the row of member m and position j sees the
+    // stored positions [lo, prefix_len[m]) only, lo = prefix_window_lo(prefix_len[m], own_seen[m], d, window) with d = depth[m * C + j]
+    // or, where depth is null, j; a row with lo >= prefix_len[m] is dead like a pair beyond n_q[m]
+    const uint32_t* own_seen;         // device array [n_members]
+    const uint32_t* depth;            // device array [n_members][C], or null
+    uint32_t        window;
 };
 // part == null: ONE launch of n_blocks * heads workgroups that fold into out / lse.  Otherwise TWO: n_items * heads workgroups that
 // write their partials, then k_prefix_combine over n_blocks * heads, which merges a row's pieces in ascending order and folds.

@@ -1114,17 +1114,69 @@ class SpeckvKVConnector:
             first.append(len(order))
         return order + none, list(groups), first
 
-    def _shared_args(self, req_ids, prefix_ids, prefix_lens, splits, what):
+    @staticmethod
+    def _shared_window(window):
+        """window as the shared-prefix calls take it: None -> 0 (no window), an int >= 1 -> itself; anything else -- 0, a negative, a
+        bool, a float, a string -- is a ValueError"""
+        if window is None:
+            return 0
+        if not _is_int(window) or not 1 <= window <= 0xFFFFFFFF:
+            raise ValueError("window must be None (no window) or a count of positions >= 1")
+        return int(window)
+
+    @staticmethod
+    def _shared_tensors(what, **tensors):
+        """The rows of a shared-prefix call are torch tensors: the fold reads them by data_ptr() behind the own step, and the grouped
+        order gathers them with index_select, so None or an object that merely has a shape is a TypeError here -- behind the
+        judgement of the lists, in front of any library call -- and not an AttributeError somewhere inside the step"""
+        import torch
+        for name, t in tensors.items():
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{what}(): {name} must be a torch tensor, not {type(t).__name__}")
+
+    @staticmethod
+    def prefix_window_walk(first_member: Sequence[int], prefix_lens: Sequence[int], own_seen: Sequence[int], n_new: Sequence[int], window):
+        """Which tiles of its prefix a group of a shared-prefix call walks under a window (speckv_ext_prefix_window_walk restated).
+        Group g = the members first_member[g] .. first_member[g + 1] - 1 (shared_groups); member m sees prefix_lens[m] (even)
+        positions of the prefix in front of its own, own_seen[m] of its OWN positions are seen by its query position of depth 0,
+        itself included (a decode step: its length; a chunk or tree step: length + 1), and it brings n_new[m] live positions.  The
+        row of depth d sees [lo, prefix_lens[m]) of the prefix, lo = max(0, prefix_lens[m] + own_seen[m] + d - W) (W None: 0), and
+        nothing where that is empty.  A member COUNTS when n_new[m] > 0, prefix_lens[m] > 0 and its depth-0 bound -- its lowest --
+        is below prefix_lens[m].  The group's blocks walk the 32-position tiles [first_tile, first_tile + n_tiles): first_tile =
+        (the lowest depth-0 bound of the members that count) >> 5, n_tiles = ceil(max_len / 32) - first_tile with max_len their
+        largest prefix_lens; (0, 0) for a group no member of which counts -- it has no blocks.  Returns one (first_tile, n_tiles)
+        per group.  Pure python, no device."""
+        W = SpeckvKVConnector._shared_window(window)
+        first = list(first_member)
+        if not first or first[0] != 0 or any(not _is_int(x) for x in first) or any(b < a for a, b in zip(first, first[1:])):
+            raise ValueError("first_member: ints ascending from 0, one more than there are groups")
+        n = first[-1]
+        lens, seen, live = list(prefix_lens), list(own_seen), list(n_new)
+        if not (len(lens) == len(seen) == len(live) == n) or not all(_is_int(x) and x >= 0 for x in lens + seen + live) or any(x & 1 for x in lens):
+            raise ValueError("prefix_lens (even), own_seen, n_new: one count >= 0 per member")
+        walks = []
+        for a, b in zip(first, first[1:]):
+            bounds = [(max(0, lens[m] + seen[m] - W) if W else 0, lens[m]) for m in range(a, b) if live[m] and lens[m]]
+            bounds = [(lo, n_pre) for lo, n_pre in bounds if lo < n_pre]
+            if not bounds:
+                walks.append((0, 0))
+                continue
+            t_first = min(lo for lo, _ in bounds) >> 5
+            walks.append((t_first, (max(n_pre for _, n_pre in bounds) + 31) // 32 - t_first))
+        return walks
+
+    def _shared_args(self, req_ids, prefix_ids, prefix_lens, splits, what, window=None):
         """The shared-prefix arguments of a call, judged in front of any library call and kept for the other layers of the step: the
-        judgement depends on the lists and on what the requests hold, so it is keyed by the lists (values AND types: True == 1) and
-        `_epoch`, like the attention plan.  None when no member sees a prefix; otherwise (order or None when the batch is laid out
+        judgement depends on the lists and on what the requests hold, so it is keyed by the lists (values AND types: True == 1), the
+        window (value and type, judged by _shared_window in front of it) and `_epoch`, like the attention plan.  None when no member
+        sees a prefix; otherwise (order or None when the batch is laid out
         already, the members in that order, the groups' handles, first_member and the members' prefix lengths in that order as the
         arrays the entry takes).  What is kept holds handles and lengths: it is right only while EVERY method that changes a request's
         length or handle, or the set of requests, moves `_epoch` (add_request, free_request, write_prefill, append, commit, truncate,
         fork do) -- a new state-changing method must move it too."""
         import numpy as np
         key = (what, self._epoch, tuple(req_ids), tuple(prefix_ids), tuple(map(type, prefix_ids)), type(splits), splits,
-               None if prefix_lens is None else (tuple(prefix_lens), tuple(map(type, prefix_lens))))
+               None if prefix_lens is None else (tuple(prefix_lens), tuple(map(type, prefix_lens))), type(window), window)
         if self._shared_key == key:
             return self._shared_plan
         plan = self._shared_judge(req_ids, prefix_ids, prefix_lens, splits, what)
@@ -1178,7 +1230,7 @@ class SpeckvKVConnector:
         return (None if order == list(range(B)) else order, [self.requests[p].handle for p in prefixes], first, lens)
 
     def attend_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, sm_scale: float, prefix_lens=None,
-                      stream=None, splits=0):
+                      stream=None, splits=0, window=None):
         """attend() for requests that SHARE A PREFIX without holding a copy of it: parallel samples of one prompt, beams, a system
         prompt in front of many users.  Shapes and result are attend()'s.  The members `req_ids` are ordinary requests that hold only
         what is their own (add_request, append / commit); a prefix is an ordinary request too, and nothing binds them -- the call
@@ -1199,15 +1251,28 @@ class SpeckvKVConnector:
         256 over an FP8 pool, none up to 256 over INT4 and MXFP4; 8k: 64 over FP8, 256 over INT4 and MXFP4; 32k: 16 over FP8, 64 over
         INT4 and MXFP4.  At 64 members x 8k x 4 query rows it wins over FP8 (0.159 against 0.206 ms) and is 0.02 - 0.03 ms SLOWER
         over INT4 and MXFP4.
+        window: None (the default) = a global layer: the step above, untouched.  An int W >= 1 is the call of a LOCAL
+        (sliding-window) layer of a model that interleaves local and global layers -- a member holds only its own positions, so
+        EVERY layer of such a model goes through this route.  The member's query sees the last W positions of prefix + own, itself
+        included: the own step is attend(window=W) exactly as issued without a prefix (the window is relative), and the fold
+        (speckv_ext_attend_prefix_fold_window with own_seen = the member's length) sees the prefix positions [max(0, prefix_lens[b]
+        + length - W), prefix_lens[b]) and walks only their tiles (prefix_window_walk), so its cost follows W, not the prefix.  A
+        member whose window lies wholly in its own part (length >= W) is not touched by the fold: it keeps the bits of
+        attend(window=W).  A window that cuts nothing of any prefix issues the unwindowed fold, bit for bit.  Against fork() +
+        attend(window=W) this route is about correctness and pool capacity -- the prefix is stored once on every layer -- not speed:
+        that route walks only W / 32 tiles per member too (profiles/shared_prefix_window.txt).
         Anything malformed is a ValueError / KeyError before any library call: an unknown prefix, a prefix among the members, lists
-        of the wrong length, bools or non-integers, a pool that is not FP8 / INT4 / MXFP4.  There is no window argument."""
+        of the wrong length, bools or non-integers, a window that is not None or an int >= 1, a pool that is not FP8 / INT4 /
+        MXFP4; a q that is no torch tensor is a TypeError."""
         import numpy as np
         import torch
-        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_shared")
+        W = self._shared_window(window)
+        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_shared", window)
+        self._shared_tensors("attend_shared", q=q)
         if len(q.shape) != 4 or q.shape[0] != len(req_ids):
             raise ValueError("q must be [batch][heads][g][dim]")
         if plan is None:
-            return self.attend(layer, req_ids, q, sm_scale, stream)
+            return self.attend(layer, req_ids, q, sm_scale, stream, window)
         order, req_ids, handles, first, lens = plan
         G = int(q.shape[2])
         if G not in (1, 2, 4, 8, 16):
@@ -1219,10 +1284,15 @@ class SpeckvKVConnector:
                 q = q.index_select(0, idx)
             if stream is not None:                                # attend's body scales q on torch's current stream: behind the gather
                 torch.cuda.current_stream().wait_stream(stream)
-        out, lse, qs = self._attend_layers_lse(layer, 1, req_ids, q[None], sm_scale, stream, None)
+        out, lse, qs = self._attend_layers_lse(layer, 1, req_ids, q[None], sm_scale, stream, window)
         with self._On(self, stream) as st:
-            self.lib.attend_prefix_fold(handles, first, layer, qs.data_ptr(), 1, G, lens, np.ones(B, dtype=np.uint32), int(splits), sm_scale,
-                                        out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+            if W:
+                own = np.asarray([self.requests[r].length for r in req_ids], dtype=np.uint32)
+                self.lib.attend_prefix_fold_window(handles, first, layer, qs.data_ptr(), 1, G, lens, np.ones(B, dtype=np.uint32), own, 0, W,
+                                                   int(splits), sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+            else:
+                self.lib.attend_prefix_fold(handles, first, layer, qs.data_ptr(), 1, G, lens, np.ones(B, dtype=np.uint32), int(splits), sm_scale,
+                                            out.data_ptr(), lse.data_ptr(), st.cuda_stream)
             out = out[0]
             if order is not None:                                 # and so does the way back: behind the fold, on its stream
                 with torch.cuda.stream(st):
@@ -1241,34 +1311,86 @@ class SpeckvKVConnector:
         return both[0], both[1]
 
     def attend_chunk_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, k_new, v_new, sm_scale: float,
-                            n_new=None, prefix_lens=None, stream=None, splits=0):
+                            n_new=None, prefix_lens=None, stream=None, splits=0, window=None, parents=None):
         """attend_chunk() for members of a shared prefix: the member's OWN chunk -- a user's differing suffix behind a shared system
         prompt -- attends what the member holds and the chunk causally, as attend_chunk(splits=1) does, and the stored positions
         [0, prefix_lens[b]) of the request prefix_ids[b] in front of both.  Shapes, n_new, the K pre-scale and the result (zeros for
         positions >= n_new[b]) are attend_chunk's; prefix_ids, prefix_lens, splits and what is refused are attend_shared's.  The
         causal chunk route with the log-sum-exp requested, then ONE speckv_ext_attend_prefix_fold call with C = S on the same stream.
         Changes no state: commit(nodes=range(n)) stores the chunk in the MEMBER afterwards.  No member with a prefix: attend_chunk's
-        launch and bits."""
+        launch and bits.
+        window: None = a global layer, the step above.  An int W >= 1 = a LOCAL layer: the own part is attend_chunk(window=W) with
+        the log-sum-exp kept, and the fold (speckv_ext_attend_prefix_fold_window, own_seen = length + 1, depth = the position's
+        index) lets query position j see the prefix positions [max(0, prefix_lens[b] + length + 1 + j - W), prefix_lens[b]); a
+        position whose window lies wholly in the member's own part (length + 1 + j >= W) is not touched by the fold.
+        parents (a global layer): the new positions form a draft TREE (attend_chunk(parents=...), chunk_tree_masks) -- the masked
+        chunk route with the log-sum-exp kept, then the fold above with n_q = the live nodes: the prefix part has no structure among
+        rows, every live node sees all of it.  Afterwards commit(req_ids, k_new, v_new, nodes=accepted path) on the members, as for
+        any tree step.  parents together with window is a ValueError, as in attend_chunk: attend_tree_shared is the tree step of a
+        local layer."""
+        W = self._shared_window(window)
+        if W and parents is not None:
+            raise ValueError("window does not combine with parents: a windowed layer takes a chain of new positions, not a tree "
+                             "(attend_tree_shared is the tree step of a local layer)")
+        return self._chunk_shared(layer, req_ids, prefix_ids, q, k_new, v_new, sm_scale, n_new, prefix_lens, stream, splits, window, parents,
+                                  False, "attend_chunk_shared")
+
+    def attend_tree_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, k_new, v_new, sm_scale: float,
+                           parents, n_new=None, prefix_lens=None, stream=None, splits=0, window=None):
+        """attend_tree() for members of a shared prefix: the TREE step of one layer, global or local.  Shapes, parents, n_new, the K
+        pre-scale and the result (zeros for dead nodes) are attend_tree's; prefix_ids, prefix_lens, splits and what is refused are
+        attend_shared's.  window None (a global layer): exactly attend_chunk_shared(parents=parents) -- the same calls, the same
+        bits.  window W >= 1 (a local layer): the own part is what attend_tree(window=W) issues, by depth
+        (speckv_ext_attend_chunk_tree_window, the log-sum-exp kept), and the fold (speckv_ext_attend_prefix_fold_window, own_seen
+        = length + 1) reads the SAME depth table the own call reads -- one table, one tree: node j of depth d sees the prefix
+        positions [max(0, prefix_lens[b] + length + 1 + d - W), prefix_lens[b]), and none where its window lies wholly in the
+        member's own part.  Afterwards commit(req_ids, k_new, v_new, nodes=accepted path) on the members.  Changes no state."""
+        if parents is None:
+            raise ValueError("parents: ints, or one list of ints per request")
+        return self._chunk_shared(layer, req_ids, prefix_ids, q, k_new, v_new, sm_scale, n_new, prefix_lens, stream, splits, window, parents,
+                                  True, "attend_tree_shared")
+
+    def _chunk_shared(self, layer, req_ids, prefix_ids, q, k_new, v_new, sm_scale, n_new, prefix_lens, stream, splits, window, parents, by_depth,
+                      what):
+        """attend_chunk_shared's and attend_tree_shared's body: by_depth = a tree whose window, if any, goes by a node's depth"""
         import numpy as np
         import torch
-        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_chunk_shared")
+        W = self._shared_window(window)
+        by_depth = by_depth and W != 0                            # a tree without a window is the masked chunk
+        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, what, window)
+        self._shared_tensors(what, q=q, k_new=k_new, v_new=v_new)
         if plan is None:
-            return self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, None, 1, None, False)
+            return self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, 1, window, by_depth)
         order, req_ids, handles, first, lens = plan
         if order is not None:
             if n_new is not None:
                 if len(n_new) != len(order):
                     raise ValueError("n_new: one count 0..S per request")
                 n_new = [n_new[b] for b in order]
+            if parents is not None:
+                parents = list(parents)
+                if parents and not isinstance(parents[0], numbers.Integral):          # one tree per request: in the members' order
+                    if len(parents) != len(order):
+                        raise ValueError("parents: one tree per request, or one tree for all")
+                    parents = [parents[b] for b in order]
             with self._On(self, stream) as st, torch.cuda.stream(st):     # the gather runs on the stream the launches go to
                 idx, inv = self._shared_permutation(order)
                 q, k_new, v_new = q.index_select(0, idx), k_new.index_select(0, idx), v_new.index_select(0, idx)
-        out, lse, qs = self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, None, 1, None, False, keep_lse=True)
+        out, lse, qs = self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, 1, window, by_depth, keep_lse=True)
         B, S, _, R, _ = (int(x) for x in qs.shape)
         live = [S] * B if n_new is None else [int(n) for n in n_new]
         if any(live) or order is not None:
             with self._On(self, stream) as st:
-                if any(live):
+                if any(live) and W:
+                    key, reqs, _ = self._batch(req_ids)
+                    depths = 0
+                    if by_depth:                                  # the table the own call has just read (kept per tree and window)
+                        with torch.cuda.stream(st):
+                            depths = self._chunk_tree_window_table(key, reqs, parents, live, S, W)[1].data_ptr()
+                    self.lib.attend_prefix_fold_window(handles, first, layer, qs.data_ptr(), S, R, lens, np.asarray(live, dtype=np.uint32),
+                                                       np.asarray([r.length + 1 for r in reqs], dtype=np.uint32), depths, W, int(splits),
+                                                       sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+                elif any(live):
                     self.lib.attend_prefix_fold(handles, first, layer, qs.data_ptr(), S, R, lens, np.asarray(live, dtype=np.uint32), int(splits),
                                                 sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
                 if order is not None:                             # the way back: behind the fold, on its stream

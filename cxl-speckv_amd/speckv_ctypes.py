@@ -86,6 +86,9 @@ _EXT_SIGNATURES = {
                                             c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_prefix_fold": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32,
                                       ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_prefix_fold_window": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_prefix_window_walk": [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
     "speckv_ext_bind_request": [c_uint32, c_uint64, c_uint32],
@@ -411,6 +414,31 @@ class SpeckvLib:
         self._ext("speckv_ext_attend_prefix_fold", n, as_arr(prefix_handles, c_uint64, n), as_arr(first_member, c_uint32, n + 1), layer,
                   c_void_p(d_q), C, rows_per_pos, as_arr(prefix_len, c_uint32, m), as_arr(n_q, c_uint32, m), n_splits, sm_scale,
                   c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+
+    def attend_prefix_fold_window(self, prefix_handles, first_member, layer, d_q, C, rows_per_pos, prefix_len, n_q, own_seen, d_depth, window,
+                                  n_splits, sm_scale, d_out, d_lse, stream):
+        """attend_prefix_fold on a sliding-window (local) layer (speckv_ext_attend_prefix_fold_window): own_seen[m] = the member's own
+        positions its query position of depth 0 sees, itself included; d_depth = device uint32 [n_members][C] (0 / None: the row of
+        position j has depth j); the row of depth d sees [max(0, prefix_len[m] + own_seen[m] + d - window), prefix_len[m]) of the
+        prefix and is dead where that is empty.  window 0, or one that cuts nothing, issues attend_prefix_fold's launches.  The other
+        arguments as attend_prefix_fold; own_seen like prefix_len."""
+        n = len(prefix_handles)
+        m = len(prefix_len)
+        self._ext("speckv_ext_attend_prefix_fold_window", n, as_arr(prefix_handles, c_uint64, n), as_arr(first_member, c_uint32, n + 1), layer,
+                  c_void_p(d_q), C, rows_per_pos, as_arr(prefix_len, c_uint32, m), as_arr(n_q, c_uint32, m),
+                  None if own_seen is None else as_arr(own_seen, c_uint32, m), c_void_p(d_depth or None), window, n_splits, sm_scale,
+                  c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+
+    def prefix_window_walk(self, first_member, prefix_len, own_seen, n_q, window):
+        """The walk rule of attend_prefix_fold_window (speckv_ext_prefix_window_walk; works without init, needs no device):
+        (first_tile, n_tiles), one entry per group -- (0, 0) for a group none of whose members still sees its prefix.
+        own_seen: one count per member, or None (zeros)."""
+        n, m = len(first_member) - 1, len(prefix_len)
+        arr = lambda xs, k: (c_uint32 * max(k, 1))(*[int(x) for x in xs])
+        first, count = (c_uint32 * max(n, 1))(), (c_uint32 * max(n, 1))()
+        self._ext("speckv_ext_prefix_window_walk", n, arr(first_member, n + 1), arr(prefix_len, m),
+                  None if own_seen is None else arr(own_seen, m), arr(n_q, m), window, first, count)
+        return list(first)[:n], list(count)[:n]
 
     def chunk_window_walk(self, pos_end, base, n_q, rows_per_pos, window):
         """The walk rule of attend_chunk_window (speckv_ext_chunk_window_walk; works without init, needs no device): (first_tile,

@@ -938,6 +938,51 @@ speckv_status_t speckv_ext_attend_prefix_fold(uint32_t n_groups, const speckv_ha
                                               const uint32_t* prefix_len, const uint32_t* n_q /* host arrays [n_members] */,
                                               uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream);
 
+/* speckv_ext_attend_prefix_fold_window: speckv_ext_attend_prefix_fold on a SLIDING-WINDOW (local) layer, for decode steps, chunks
+ * and draft trees -- the local layers of the models speckv_ext_attend_chunk_window names, whose members hold only their own positions
+ * on EVERY layer.  The arguments of speckv_ext_attend_prefix_fold in the same order with `own_seen, d_depth, window` directly behind
+ * n_q; everything said there holds except which prefix positions a row sees and which rows are live.
+ *   Member m sees the stored positions [0, prefix_len[m]) of its group's prefix IN FRONT OF its own positions.
+ *   own_seen : host array [n_members]; own_seen[m] = the number of the member's OWN positions its query position of depth 0 sees
+ *             without a window, itself included: the member's length for a decode step after its position was appended,
+ *             pos_end + base + 1 for a chunk or tree step.  0: the member holds nothing and the query is judged as sitting directly
+ *             behind the prefix.
+ *   d_depth  : device, uint32 [n_members][C], 4-byte aligned, may be NULL.  The row of position j of member m has depth
+ *             d = d_depth[m * C + j] (a draft tree: the table speckv_ext_attend_chunk_tree_window takes) or, with NULL, d = j (a
+ *             chain).  It sees own_seen[m] + d own keys; the own call (speckv_ext_attend_*_planned* under a window,
+ *             speckv_ext_attend_chunk_window, speckv_ext_attend_chunk_tree_window) applies the window to those exactly as without
+ *             a prefix -- the window is relative, the own call does not change.
+ *   window   : W.  Of the prefix the row sees [lo, prefix_len[m]), lo = max(0, prefix_len[m] + own_seen[m] + d - W).  A row with
+ *             lo >= prefix_len[m] (own_seen[m] + d >= W) sees nothing of the prefix and is DEAD like a pair beyond n_q[m]: its out /
+ *             lse rows are neither read nor written.  Every live row sees position lo, so its sum is never 0.  W == 0: no window.
+ * A group's blocks walk the 32-position tiles [first_tile, ceil(max_len / 32)) only (speckv_ext_prefix_window_walk); pages below
+ * 32 first_tile are never read.  n_splits cuts the tiles that are LEFT by the rule of speckv_ext_chunk_split_plan, as
+ * speckv_ext_attend_chunk_window does; a piece wholly below a row's lo or beyond its prefix_len weighs nothing, and the merge gives
+ * the unsplit weights.
+ * With window == 0, or a window under which no live row can lose a prefix position (prefix_len[m] + own_seen[m] + n_q[m] - 1 <= W
+ * for every member with n_q[m] > 0 and prefix_len[m] > 0; a depth is below n_q[m]), the call issues exactly the launches of
+ * speckv_ext_attend_prefix_fold -- the same bits -- and d_depth is not read.
+ * Returns what speckv_ext_attend_prefix_fold returns (a capturing stream included), and SPECKV_ERR_INVAL for a NULL own_seen with
+ * members and a d_depth that is not 4-byte aligned.  Every refusal comes before any launch and leaves out / lse untouched. */
+speckv_status_t speckv_ext_attend_prefix_fold_window(uint32_t n_groups, const speckv_handle_t* prefix_handles /* host [n_groups] */,
+                                                     const uint32_t* first_member /* host [n_groups + 1] */, uint32_t layer,
+                                                     const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                                     const uint32_t* prefix_len, const uint32_t* n_q, const uint32_t* own_seen /* host arrays [n_members] */,
+                                                     const uint32_t* d_depth /* device, may be NULL */, uint32_t window /* 0: none */,
+                                                     uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream);
+
+/* The walk rule of speckv_ext_attend_prefix_fold_window as a pure function (the same body the engine plans by).  A member of group
+ * g = [first_member[g], first_member[g + 1]) COUNTS when n_q[m] > 0, prefix_len[m] > 0 and its depth-0 bound
+ * lo0 = max(0, prefix_len[m] + own_seen[m] - window) (window == 0: 0) is below prefix_len[m]; depth 0 gives a member's lowest bound.
+ *   out_first_tile[g] = (the minimum of lo0 over the members that count) >> 5
+ *   out_n_tiles[g]    = ceil(max_len / 32) - out_first_tile[g], max_len = the largest prefix_len of the members that count
+ * and 0 / 0 for a group without such a member (it has no blocks).  own_seen == NULL: zeros.
+ * SPECKV_ERR_INVAL: NULL arrays where they are needed, first_member not ascending from 0, an odd prefix_len.
+ * Works without speckv_init and needs no device. */
+speckv_status_t speckv_ext_prefix_window_walk(uint32_t n_groups, const uint32_t* first_member /* [n_groups + 1] */,
+                                              const uint32_t* prefix_len, const uint32_t* own_seen /* may be NULL */, const uint32_t* n_q,
+                                              uint32_t window, uint32_t* out_first_tile, uint32_t* out_n_tiles /* [n_groups] */);
+
 /* speckv_ext_attend_chunk_tree_window: a DRAFT TREE on a SLIDING-WINDOW (local) layer -- the tree step of the local layers of the
  * models speckv_ext_attend_chunk_window names, whose global layers take the tree step through speckv_ext_attend_chunk_masked / _split.
  * The arguments of speckv_ext_attend_chunk_split in the same order with `d_depth, window` directly behind mask_words.  Everything
