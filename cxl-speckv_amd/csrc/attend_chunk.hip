@@ -5,7 +5,8 @@
 // A translation unit of its own: the headline kernel of kernels.hip is pinned by the hash of its instructions and the three
 // attention units stay as they are.  The three small decoders this kernel needs are restated for ONE head's 8 elements of both
 // positions of a page (chunk_device.hpp, shared with attend_prefix.hip); they give the fp16 values speckv_ext_fetch_range gives (the
-// fp32 product rounded once to fp16, pack_half2).
+// fp32 product rounded once to fp16, pack_half2) -- except the K rows of an FP8 pool: those are staged as the E4M3 values
+// themselves, exact in fp16, and the page's block scale multiplies the score in fp32 (k_scale below; chunk_device.hpp says why).
 //
 // Semantics.  Sequence i holds pos_end (even) stored positions, base in {0, 1} held odd last positions (the tail) and n_q <= C new
 // positions.  Query position j < n_q sees the stored positions [0, pos_end) and the held positions 0 .. base + j: the tail, the new
@@ -89,6 +90,7 @@ template <int SCHEME, bool MASKED, bool SPLIT, bool WINDOW>
 __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
 {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufElems];
+    __shared__ float k_scale[2][16];                          // FP8: the K block scale of the 16 pages of a staged tile (held tiles: 1)
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -198,8 +200,9 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     };
     const auto store_tile = [&](uint32_t tile, _Float16* buf) {
         uint32_t ke[4], ko[4], ve[4], vo[4];
+        if (SCHEME == kFp8E4m3 && c == 0u) k_scale[buf != lds][pp] = tile < n_pool ? pool_k_scale<SCHEME>(rk) : 1.0f;
         if (tile < n_pool) {
-            decode_pool<SCHEME>(rk, p0, ke, ko);
+            decode_pool<SCHEME, true>(rk, p0, ke, ko);
             decode_pool<SCHEME>(rv, p0, ve, vo);
             if (WINDOW && 2u * (16u * tile + pp) < lo_pool) {               // the page the bound cuts: its even position is below it
 #pragma unroll
@@ -262,15 +265,17 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
                 const uint32_t n_seen = limit > t_base ? limit - t_base : 0u;
                 vis = (mword & (n_seen >= 32u ? 0xFFFFFFFFu : (1u << n_seen) - 1u)) >> (4u * g);
             }
+            const float* ks = k_scale[(tile - t_begin) & 1u];
             float sv[8], mx = -__builtin_inff();
 #pragma unroll
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t t = t_base + 16u * (i >> 2) + 4u * g + (i & 3u);
+                const float scale_i = SCHEME == kFp8E4m3 ? scale2 * ks[8u * (i >> 2) + 2u * g + ((i & 3u) >> 1)] : scale2;       // the position's page
                 // tree form: bit t & 31 of the word (t_base is a multiple of 32), the causal bound folded into the word
                 // (under a window too: a stored position also needs t >= the bound of the row's depth, a held one its bit alone)
                 const bool seen = MASKED ? ((vis >> (16u * (i >> 2) + (i & 3u))) & 1u) && (!WINDOW || held || t >= row_lo)
                                   : WINDOW ? t >= lower && t < limit : t < limit;
-                sv[i] = seen ? sc[i >> 2][i & 3u] * scale2 : -__builtin_inff();
+                sv[i] = seen ? sc[i >> 2][i & 3u] * scale_i : -__builtin_inff();
                 mx = fmaxf(mx, sv[i]);
             }
             mx = max_over_kb(mx);

@@ -96,6 +96,7 @@ template <int SCHEME, bool SPLIT, bool WINDOW>
 __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
 {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufElems];
+    __shared__ float k_scale[2][16];                          // FP8: the K block scale of the 16 pages of a staged tile (chunk_device.hpp)
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -148,7 +149,8 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
     };
     const auto store_tile = [&](_Float16* buf) {
         uint32_t ke[4], ko[4], ve[4], vo[4];
-        decode_pool<SCHEME>(rk, p0, ke, ko);
+        if (SCHEME == kFp8E4m3 && c == 0u) k_scale[buf != lds][pp] = pool_k_scale<SCHEME>(rk);
+        decode_pool<SCHEME, true>(rk, p0, ke, ko);
         decode_pool<SCHEME>(rv, p0, ve, vo);
         *reinterpret_cast<u32x4*>(buf + (2u * pp) * kKRow + 8u * c) = u32x4{ke[0], ke[1], ke[2], ke[3]};
         *reinterpret_cast<u32x4*>(buf + (2u * pp + 1u) * kKRow + 8u * c) = u32x4{ko[0], ko[1], ko[2], ko[3]};
@@ -188,11 +190,13 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
                 }
                 sc[hf] = s4;
             }
+            const float* ks = k_scale[(tile - t_begin) & 1u];
             float sv[8], mx = -__builtin_inff();
 #pragma unroll
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t t = t_base + 16u * (i >> 2) + 4u * g + (i & 3u);
-                sv[i] = t < row.len && (!WINDOW || t >= row.lo) ? sc[i >> 2][i & 3u] * scale2 : -__builtin_inff();   // the row's own range
+                const float scale_i = SCHEME == kFp8E4m3 ? scale2 * ks[8u * (i >> 2) + 2u * g + ((i & 3u) >> 1)] : scale2;       // the position's page
+                sv[i] = t < row.len && (!WINDOW || t >= row.lo) ? sc[i >> 2][i & 3u] * scale_i : -__builtin_inff();   // the row's own range
                 mx = fmaxf(mx, sv[i]);
             }
             mx = max_over_kb(mx);

@@ -1,7 +1,8 @@
 // cxl-speckv_amd/csrc/chunk_device.hpp -- what the chunk walk's translation units share (attend_chunk.hip: k_attend_chunk;
 // attend_prefix.hip: k_attend_prefix): the LDS layout of a tile, global-address-space loads and stores, the undecoded bytes a thread
 // keeps in flight for the next tile (Raw), and the three small decoders restated for ONE head's 8 elements of both positions of a
-// page; they give the fp16 values speckv_ext_fetch_range gives (the fp32 product rounded once to fp16, pack_half2).  Device code only.
+// page; they give the fp16 values speckv_ext_fetch_range gives (the fp32 product rounded once to fp16, pack_half2) -- but for the K
+// rows of an FP8 pool, staged unscaled with the block scale applied to the score (decode_pool).  Device code only.
 #pragma once
 #include "kernels.hpp"
 #include "codec_device.hpp"          // pack_half2, half_bits_to_float
@@ -73,12 +74,16 @@ __device__ __forceinline__ Raw load_pool(const PageEntry* e, uint32_t p0, bool l
 }
 
 // the 8 + 8 fp16 values of a Raw: ev / od = the even / odd position, two elements per word
-template <int SCHEME>
+// UNSCALED (the K rows of an FP8 pool): the E4M3 values themselves, exact in fp16 -- the block scale (pool_k_scale) multiplies the
+// SCORE in fp32 instead.  value x scale rounded to fp16 costs every K element a relative 2^-12, and the score error that makes grows
+// with |k|: rows of magnitude 3 took the output past the 2e-3 sum p|v| bound of this path.  The other formats decode exactly or are
+// judged against their fp16 values, and V rows keep the rounded product (its error is relative to v: within the bound at any size).
+template <int SCHEME, bool UNSCALED = false>
 __device__ __forceinline__ void decode_pool(const Raw& r, uint32_t p0, uint32_t (&ev)[4], uint32_t (&od)[4])
 {
     float y0[8], y1[8];
     if (SCHEME == kFp8E4m3) {
-        const float s = __uint_as_float(r.aux);
+        const float s = UNSCALED ? 1.0f : __uint_as_float(r.aux);
 #define CK_FP8(K, W, SEL) { y0[K] = __builtin_amdgcn_cvt_f32_fp8(static_cast<int>(r.a.W), SEL); y1[K] = __builtin_amdgcn_cvt_f32_fp8(static_cast<int>(r.b.W), SEL); }
         CK_FP8(0, x, 0) CK_FP8(1, x, 1) CK_FP8(2, x, 2) CK_FP8(3, x, 3) CK_FP8(4, y, 0) CK_FP8(5, y, 1) CK_FP8(6, y, 2) CK_FP8(7, y, 3)
 #undef CK_FP8
@@ -108,6 +113,13 @@ __device__ __forceinline__ void decode_pool(const Raw& r, uint32_t p0, uint32_t 
         ev[k] = pack_half2(y0[2 * k], y0[2 * k + 1]);
         od[k] = pack_half2(y1[2 * k], y1[2 * k + 1]);
     }
+}
+
+// what the scores of a staged page are multiplied by: the block scale of an FP8 K page (decode_pool<FP8, true>), 1 otherwise
+template <int SCHEME>
+__device__ __forceinline__ float pool_k_scale(const Raw& r)
+{
+    return SCHEME == kFp8E4m3 && r.len ? __uint_as_float(r.aux) : 1.0f;
 }
 
 // the same piece of two held rows: addresses of 0 (beyond the sequence's held positions) give zeros
