@@ -347,8 +347,8 @@ __global__ __launch_bounds__(1024) void k_softmax_topk(const float* __restrict__
     for (uint32_t i = tid; i < vocab; i += kSmThreads) {
         const float v = l[i];
         mx = fmaxf(mx, v);
-        // sorted insertion (descending value, ascending index)
-        if (v > val[7] || (v == val[7] && i < idx[7])) {
+        // sorted insertion (descending value, ascending index); an absent logit (-inf, NaN) is no candidate
+        if (v > -INFINITY && (v > val[7] || (v == val[7] && i < idx[7]))) {
             val[7] = v; idx[7] = i;
 #pragma unroll
             for (int j = 7; j > 0; --j) {
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(1024) void k_softmax_topk(const float* __restrict__
     for (uint32_t s = kSmThreads / 2; s > 0; s >>= 1) { if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]); __syncthreads(); }
     mx = red[0]; __syncthreads();
     float sum = 0.0f;
-    for (uint32_t i = tid; i < vocab; i += kSmThreads) sum += expf(l[i] - mx);
+    for (uint32_t i = tid; i < vocab; i += kSmThreads) { const float v = l[i]; if (v > -INFINITY) sum += expf(v - mx); }     // absent logits add nothing
     red[tid] = sum; __syncthreads();
     for (uint32_t s = kSmThreads / 2; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
     sum = red[0]; __syncthreads();
@@ -383,8 +383,8 @@ __global__ __launch_bounds__(1024) void k_softmax_topk(const float* __restrict__
         __syncthreads();
         if (ci == bi && ci != 0xFFFFFFFFu) ++head;                 // the owner of the winner advances
         if (tid == 0) {
-            out_tok[b * k + r] = static_cast<int32_t>(bi);
-            out_conf[b * k + r] = expf(bv - mx) / sum;
+            out_tok[b * k + r] = static_cast<int32_t>(bi);             // no candidate left: 0xFFFFFFFF = -1
+            out_conf[b * k + r] = bi != 0xFFFFFFFFu ? expf(bv - mx) / sum : 0.0f;
         }
     }
 }
@@ -401,8 +401,9 @@ __global__ __launch_bounds__(1024) void k_softmax_topk(const float* __restrict__
 //     order: a round offers the lane's best key not yet taken) -- and writes tokens and confidences exp(logit - max) / sum.  (One kernel whose last-arriving workgroup merges was tried: 10 us for one request, but the
 //     agent-scope release/acquire it needs writes back and invalidates the XCD's L2 once per workgroup -- 48 us for 256
 //     requests against 26 us before.)
-// A logit that is -inf or NaN is never chosen (as above: "v > best" is false for it); a rank without a candidate reports
-// token -1 and confidence 0.
+// A logit that is not greater than -inf (-inf or NaN) is ABSENT, in all three top-k forms and in k_predict_small: never chosen ("v > best"
+// is false for it, its key is 0), dropped from the maximum (fmaxf) and from the exp-sum (it used to enter the sum, and one NaN logit made
+// every confidence of its request NaN); a rank without a candidate reports token -1 and confidence 0.  +inf logits are not handled.
 constexpr uint32_t kTkMaxParts = 64, kTkThreads = 256, kTkPer = 16, kTkSpan = kTkThreads * kTkPer;
 static_assert(kTkSpan == kPredictTopkSpan && kTkMaxParts == kPredictTopkMaxParts, "predict_ws_bytes");
 // workspace of one request: parts x (max, sum) | parts x 8 keys
@@ -453,7 +454,7 @@ __global__ __launch_bounds__(256) void k_softmax_topk_small(const float* __restr
     float sum = 0.0f;
 #pragma unroll
     for (uint32_t j = 0; j < kTkPer; ++j)
-        if (base + j * kTkThreads < vocab && m > -INFINITY) sum += pred_fast_exp(v[j] - m);
+        if (v[j] > -INFINITY) sum += pred_fast_exp(v[j] - m);           // an absent logit (-inf, NaN, past the vocabulary) adds nothing
     sum = wave_sum_f32(sum);
     for (uint32_t r = 0; r < k; ++r) {
         float bv = -INFINITY; int bj = -1;
@@ -586,7 +587,7 @@ __global__ __launch_bounds__(256) void k_predict_small(const int32_t* __restrict
         { const TkPair h2 = tk_halves(__float_as_uint(acc)); acc = __uint_as_float(h2.a) + __uint_as_float(h2.b); }   // the other half of the columns
         const float v = live ? (out_bias ? acc + bias : acc) : -INFINITY;
         const float m = wave_max_f32(v);
-        const float sum = wave_sum_f32((live && m > -INFINITY) ? pred_fast_exp(v - m) : 0.0f);
+        const float sum = wave_sum_f32(v > -INFINITY ? pred_fast_exp(v - m) : 0.0f);       // an absent logit (-inf, NaN, a dead lane) adds nothing
         uint64_t key = live ? tk_key(v, row) : 0;
         for (uint32_t r = 0; r < k; ++r) {
             const uint64_t w = wave_max_u64(key);
