@@ -175,6 +175,14 @@ public:
                    uint32_t n_layers, uint64_t layer_stride, hipStream_t s);
     int copy_runs(const uint64_t* src, const uint64_t* dst, const uint64_t* n_pages, uint32_t n_pairs, const uint64_t* run_firsts,
                   uint32_t n_runs, hipStream_t s);
+    // Paged-cache transfers (engine_slots.cpp): spans of positions between the pool and the slots of a caller's paged cache
+    struct SlotCall {
+        const uint64_t *handles, *first_tokens, *n_tokens, *slot_begins; uint32_t n_spans;
+        const int64_t* d_slots; uint64_t n_slots; const void* const* d_caches; uint32_t layer_begin, n_layers;
+        uint64_t kind_stride, page_step;
+    };
+    int read_slots(const SlotCall& c, hipStream_t s);
+    int write_slots(const SlotCall& c, hipStream_t s);
     // One chunk-attention call, filled in by its C entry: `entry` = that entry's name, for messages; the arguments all five entries
     // share; then the forms as plain values (n_splits 1 = whole sequences, window 0 = none), described above Engine::attend_chunk
     struct ChunkCall {
@@ -404,7 +412,7 @@ private:
     // buffer chose -- kept per shape, so that a buffer that alternates between shapes keeps every shape's captured launches valid
     std::map<std::array<uint64_t, 5>, BatchRoom> plan_rooms_;
     CompressGroup* d_groups_ = nullptr;    // device twin of grp_ring_ (4 slots): descriptors of a grouped compress launch
-    uint8_t* d_zero_page_ = nullptr;     // stands in for never-written pages in the fused attention
+    uint8_t* d_zero_page_ = nullptr;     // stands in for never-written pages in the fused attention, and for the row of a padding slot in write_slots
     std::unordered_map<uint32_t, std::vector<int32_t>> hist_;
     std::unordered_map<uint32_t, std::vector<int32_t>> pred_;
     std::vector<uint32_t> hist_dirty_;
@@ -484,6 +492,7 @@ private:
     int unpack(Allocation* a);                            // a compacted allocation back into fixed slots (before any write / migration)
     int settle_for_relocation(Allocation*& a, uint64_t handle);
     int descriptor_slot(size_t bytes, int* slot, void** staged, void** d_slot);      // next slot of grp_ring_ / d_groups_
+    int slots_call(const SlotCall& c, bool write, hipStream_t s);                    // the one body of read_slots / write_slots
     struct PairRows { uint32_t n_layers; uint64_t layer_stride; };      // the pair-gather form of write_groups
     int write_groups(const uint64_t* handles, const uint64_t* firsts, const void* const* d_srcs, uint32_t n_groups, uint64_t step,
                      uint64_t n_each, hipStream_t s, bool same_allocation, const PairRows* rows = nullptr);

@@ -1,0 +1,163 @@
+// cxl-speckv_amd/csrc/engine_slots.cpp -- Engine::read_slots / write_slots, the bodies of speckv_ext_read_slots / _write_slots: spans
+// of positions moved between the pool and the slots of a caller's paged cache (one cache tensor per layer, rows addressed by a slot
+// mapping on the device) by ONE launch each way (kernels: k_read_slots / k_compress_slots, kernels.hip)
+#include "engine_internal.hpp"
+#include "tuning.hpp"
+
+namespace speckv {
+
+// Span i = positions [first_tokens[i], first_tokens[i] + n_tokens[i]) of allocation handles[i], row t of it in slot
+// d_slots[slot_begins[i] + t]; page of (layer, kind, position) = (2 * layer + kind) * page_step + position / 2 for the layers
+// [layer_begin, layer_begin + n_layers), whose cache bases are d_caches[0 .. n_layers).  What travels to the device is one
+// SlotSpan per span and the n_layers bases, through a slot of the pinned descriptor ring (so the call cannot be captured): nothing
+// grows with the token count.
+// Reading is read_pairs' bracket: record addresses from the device allocation table (any placement, a sealed allocation stays
+// sealed), behind what the caller queued on `s` and behind the asynchronous pool writes on every other caller stream the engine
+// knows; nothing is written to the pool.  Writing is write_groups': whole pairs only, sealed destinations are unpacked, cached
+// destination pages invalidated, the host mirror and note_async_write_or_wait follow the launch; two spans of one allocation that
+// share a page are refused.  Every refusal comes before any launch.
+int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
+{
+    const char* entry = write ? "speckv_ext_write_slots" : "speckv_ext_read_slots";
+    if (null_) return no_data_path(entry);
+    if (!s || !c.handles || !c.first_tokens || !c.n_tokens || !c.slot_begins || !c.d_slots || !c.d_caches) return SPECKV_ERR_INVAL;
+    if (c.kind_stride % 16u || c.page_step == 0) return SPECKV_ERR_INVAL;
+    if (c.n_spans == 0 || c.n_layers == 0) return SPECKV_OK;
+    for (uint32_t l = 0; l < c.n_layers; ++l)
+        if (!c.d_caches[l] || reinterpret_cast<uintptr_t>(c.d_caches[l]) % 16u) return SPECKV_ERR_INVAL;
+    uint64_t n_pairs = 0;
+    for (uint32_t i = 0; i < c.n_spans; ++i) {
+        const uint64_t first = c.first_tokens[i], n = c.n_tokens[i];
+        if (write && ((first | n) & 1u)) return SPECKV_ERR_INVAL;               // whole pairs only
+        if (first > UINT32_MAX || n > UINT32_MAX || first + n > UINT32_MAX) return SPECKV_ERR_GENERAL;
+        if (n) n_pairs += (first + n + 1) / 2 - first / 2;
+    }
+    if (n_pairs == 0) return SPECKV_OK;
+    if (is_capturing(s)) {
+        SPECKV_ERR("%s cannot be captured into a HIP graph (its descriptors are staged per call)", entry);
+        return SPECKV_ERR_INVAL;
+    }
+    const uint64_t n_each = 2ull * c.n_layers, first_region = 2ull * c.layer_begin;
+    if (n_pairs * n_each > (1ull << 31)) return SPECKV_ERR_INVAL;
+    std::vector<Allocation*> as(c.n_spans);
+    const auto check = [&]() -> int {
+        for (uint32_t i = 0; i < c.n_spans; ++i) {
+            Allocation* a = find(c.handles[i]);
+            if (!a) return SPECKV_ERR_GENERAL;
+            if (a->scheme != find(c.handles[0])->scheme) return SPECKV_ERR_INVAL;
+            const uint64_t end = c.first_tokens[i] + c.n_tokens[i];
+            if (end > 2 * c.page_step) return SPECKV_ERR_GENERAL;                // the span leaves its (layer, kind) region
+            if (c.n_tokens[i]) {
+                const uint64_t last = (first_region + n_each - 1) * c.page_step + (end + 1) / 2 - 1;    // the last page named
+                if (c.page_step > a->n_pages || last >= a->n_pages) return SPECKV_ERR_GENERAL;
+                if (write && a->size_bytes % kPageSize && last == a->n_pages - 1) return SPECKV_ERR_INVAL;
+            }
+            as[i] = a;
+        }
+        return SPECKV_OK;
+    };
+    RC_TRY(check());
+    // the pages of span i: (first_region + j) * page_step + p for j < n_each, p in [first / 2, (first + n + 1) / 2)
+    const auto each_page = [&](auto&& f) {
+        for (uint32_t i = 0; i < c.n_spans; ++i) {
+            if (!c.n_tokens[i]) continue;
+            const uint64_t p0 = c.first_tokens[i] / 2, p1 = (c.first_tokens[i] + c.n_tokens[i] + 1) / 2;
+            for (uint64_t j = 0; j < n_each; ++j)
+                for (uint64_t p = p0; p < p1; ++p) f(as[i], (first_region + j) * c.page_step + p);
+        }
+    };
+    if (write) {
+        std::vector<uint32_t> order;                                             // the spans of one allocation must not share a page
+        for (uint32_t i = 0; i < c.n_spans; ++i) if (c.n_tokens[i]) order.push_back(i);
+        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+            return c.handles[x] != c.handles[y] ? c.handles[x] < c.handles[y] : c.first_tokens[x] < c.first_tokens[y]; });
+        for (size_t k = 1; k < order.size(); ++k) {
+            const uint32_t x = order[k - 1], y = order[k];
+            if (c.handles[x] == c.handles[y] && c.first_tokens[y] < c.first_tokens[x] + c.n_tokens[x]) return SPECKV_ERR_INVAL;
+        }
+        for (uint32_t i = 0; i < c.n_spans; ++i)
+            if (c.n_tokens[i] && as[i]->packed) {                                // sealed destinations go back into slots first
+                DeviceScope scope(device_);
+                RC_TRY(unpack(as[i]));
+                RC_TRY(check());
+            }
+    }
+    DeviceScope device_scope(device_);
+    if (write) {
+        bool cached = false;
+        each_page([&](Allocation* a, uint64_t p) { cached = cached || (res_flags(a, p) & 3u) != 0; });
+        if (cached || !flights_.empty() || ring_busy_ > 0) {
+            RC_TRY(quiesce());
+            RC_TRY(check());
+            each_page([&](Allocation* a, uint64_t p) { drop_page(a, static_cast<uint32_t>(p)); });
+            RC_TRY(flush_mirror());
+            RC_TRY(wait_stream());
+        }
+        if (!d_zero_page_) {                                                   // the row a padding slot reads; once, and complete
+            RC_TRY(ensure_zero_page(s));                                        // before a kernel on `s` (not ordered behind the
+            HIP_TRY(hipDeviceSynchronize());                                    // null stream's memset) can read it
+        }
+    }
+    const size_t span_bytes = static_cast<size_t>(c.n_spans) * sizeof(SlotSpan);  // (a multiple of 8: the cache bases follow)
+    const size_t bytes = span_bytes + static_cast<size_t>(c.n_layers) * sizeof(uint64_t);
+    int slot = 0;
+    void *staged = nullptr, *d_slot = nullptr;
+    RC_TRY(descriptor_slot(bytes, &slot, &staged, &d_slot));     // may release the ABI lock: every span is judged again
+    RC_TRY(check());
+    uint32_t prefix = 0;
+    for (uint32_t i = 0; i < c.n_spans; ++i) {
+        const Allocation* a = as[i];
+        if (write && c.n_tokens[i] && a->packed) return SPECKV_ERR_GENERAL;      // sealed again by another caller meanwhile
+        const uint32_t first = static_cast<uint32_t>(c.first_tokens[i]), n = static_cast<uint32_t>(c.n_tokens[i]);
+        static_cast<SlotSpan*>(staged)[i] = SlotSpan{write ? a->d_entries : nullptr, write ? a->d_scale_tab : nullptr, a->region_pages,
+                                                     a->scale_run, a->row, first, n, prefix, c.slot_begins[i]};
+        if (n) prefix += (first + n + 1u) / 2u - first / 2u;
+    }
+    uint64_t* bases = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(staged) + span_bytes);
+    for (uint32_t l = 0; l < c.n_layers; ++l) bases[l] = reinterpret_cast<uint64_t>(c.d_caches[l]);
+    if (!write)
+        for (auto& w : write_evs_)
+            if (w.s != s) HIP_TRY(hipStreamWaitEvent(s, w.ev, 0));
+    HIP_TRY(hipMemcpyAsync(d_slot, staged, bytes, hipMemcpyHostToDevice, s));
+    SlotArgs sa{};
+    sa.spans = static_cast<const SlotSpan*>(d_slot);
+    sa.caches = reinterpret_cast<const uint64_t*>(static_cast<const uint8_t*>(d_slot) + span_bytes);
+    sa.slots = c.d_slots;
+    sa.tab = d_tab_;
+    sa.zeros = d_zero_page_;
+    sa.n_slots = c.n_slots;
+    sa.kind_stride = c.kind_stride;
+    sa.page_step = c.page_step;
+    sa.n_spans = c.n_spans;
+    sa.n_pairs = static_cast<uint32_t>(n_pairs);
+    sa.n_layers = c.n_layers;
+    sa.layer_begin = c.layer_begin;
+    sa.kind_fast = tuning().slots_kind_fast != 0;
+    sa.scheme = as[0]->scheme;
+    sa.quant_mode = quant_mode_;
+    HIP_TRY(write ? launch_compress_slots(sa, s) : launch_read_slots(sa, s));
+    for (uint32_t i = 0; i < c.n_spans; ++i) note_use(as[i], s);                // the kernel is queued: speckv_free waits for this stream
+    const uint64_t n = n_pairs * n_each;
+    if (write) {                                                                // host mirror first, then the orderings
+        each_page([&](Allocation* a, uint64_t p) {
+            if (a->scheme != SPECKV_COMP_FP16) a->flags[p] |= 4u; else a->flags[p] &= ~4u;
+        });
+        st_.total_compressions += n;
+        st_.original_bytes += n * kPageSize;
+    } else {
+        st_.total_decompressions += n;
+        st_.dma_submitted += n;
+        st_.dma_completed += n;                                   // completion belongs to the caller's stream
+    }
+    if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel
+        (void)hipGetLastError();
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (write) RC_TRY(note_async_write_or_wait(s));
+    return SPECKV_OK;
+}
+
+int Engine::read_slots(const SlotCall& c, hipStream_t s) { return slots_call(c, false, s); }
+int Engine::write_slots(const SlotCall& c, hipStream_t s) { return slots_call(c, true, s); }
+
+} // namespace speckv

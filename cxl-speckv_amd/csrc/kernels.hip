@@ -1813,4 +1813,171 @@ hipError_t launch_read_pairs(const ReadPairArgs& a, hipStream_t s)
     }
 }
 
+// Paged-cache transfers (Engine::read_slots / write_slots): k_read_pairs and k_compress_pairs with a row's address taken from a
+// slot mapping on the device and a cache base per layer instead of four host pointers per pair.  Wave i is one page: block
+// j < 2 * n_layers (layer layer_begin + (j >> 1), kind j & 1) of flat position pair pp < n_pairs -- i = j * n_pairs + pp (pair
+// fastest: neighbouring waves take neighbouring pages of one (layer, kind) region) or i = pp * 2 * n_layers + j (kind_fast: as
+// k_read_pairs).  The span of pp is the last one whose exclusive prefix of pair counts is <= pp (binary search as in
+// copy_records.hip), the pair first_token / 2 + (pp - prefix), its two positions rows t = 2 * pair - first_token and t + 1 of the
+// span.  A row outside [0, n_tokens) is not wanted and its slot is not read; a wanted row whose slot is < 0 or >= n_slots is no
+// row either.  Everything up to here is the same for all lanes of a wave (it depends on blockIdx and the wave number alone) and
+// is loaded once per wave.  They stay behind launch_read_pairs for the reason given at launch_compress_pairs.
+namespace {
+struct SlotWork {
+    const SlotSpan* g;
+    uint32_t j;                       // (layer, kind) of the launch: layer_begin + (j >> 1), j & 1
+    uint32_t pair;                    // position pair of the allocation
+    const uint8_t* base;              // caches[j >> 1] + (j & 1) * kind_stride
+    int64_t  slot[2];                 // of the even and the odd position; -1 = no row
+};
+__device__ __forceinline__ bool slot_work(const SlotArgs& a, uint32_t wave, SlotWork* w)
+{
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
+    const uint32_t per = 2u * a.n_layers;
+    if (i >= static_cast<uint64_t>(a.n_pairs) * per) return false;   // (whole waves leave: the bodies have no workgroup barrier)
+    uint32_t pp, j;
+    if (a.kind_fast) { pp = static_cast<uint32_t>(i / per); j = static_cast<uint32_t>(i - static_cast<uint64_t>(pp) * per); }
+    else             { j = static_cast<uint32_t>(i / a.n_pairs); pp = static_cast<uint32_t>(i - static_cast<uint64_t>(j) * a.n_pairs); }
+    uint32_t lo = 0, hi = a.n_spans;                                 // spans without pairs share their successor's prefix and are passed over
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (a.spans[mid].first_pair <= pp) lo = mid; else hi = mid;
+    }
+    const SlotSpan* g = a.spans + lo;
+    const uint32_t first = g->first_token, n = g->n_tokens;
+    const uint32_t pair = (first >> 1) + (pp - g->first_pair);
+    const int64_t t0 = 2ll * pair - static_cast<int64_t>(first);     // -1 where the span begins on an odd position
+    const int64_t n_slots = static_cast<int64_t>(a.n_slots);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int64_t t = t0 + h;
+        int64_t s = -1;
+        if (t >= 0 && t < static_cast<int64_t>(n)) s = a.slots[g->slot_begin + static_cast<uint64_t>(t)];
+        w->slot[h] = (s >= 0 && s < n_slots) ? s : -1;
+    }
+    w->g = g;
+    w->j = j;
+    w->pair = pair;
+    w->base = reinterpret_cast<const uint8_t*>(a.caches[j >> 1]) + static_cast<uint64_t>(j & 1u) * a.kind_stride;
+    return true;
+}
+
+template <int SCHEME, int MODE>
+__global__ __launch_bounds__(kThreads) void k_read_slots(SlotArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds[SCHEME == kInt8DeltaRle ? kWaves * kDecLdsWords : 4];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    SlotWork w;
+    if (!slot_work(a, wave, &w)) return;
+    uint8_t* const base = const_cast<uint8_t*>(w.base);
+    const RowSink dst{w.slot[0] >= 0 ? base + static_cast<uint64_t>(w.slot[0]) * 2048u : nullptr,
+                      w.slot[1] >= 0 ? base + static_cast<uint64_t>(w.slot[1]) * 2048u : nullptr};
+    if (!dst.even && !dst.odd) return;
+    const PageEntry* entries = a.tab[w.g->table_row].entries;
+    PageEntry e{0, 0, 1.0f};
+    if (entries) e = entries[(2ull * a.layer_begin + w.j) * a.page_step + w.pair];  // a row freed meanwhile decodes as a never-written page
+    const uint8_t* rec = reinterpret_cast<const uint8_t*>(e.pool_addr);
+    uint32_t len = e.rec_bytes;
+    if (SCHEME == kInt8DeltaRle) {
+        if (len > 2u * kBlockElems) len = 2u * kBlockElems;
+        uint32_t* region = lds + wave * kDecLdsWords;
+        if (!decode_rle_fast<MODE, false, false, RowSink>(rec, len, e.scale, dst, reinterpret_cast<uint8_t*>(region), lane, true))
+            decode_rle_general_to<MODE, false, RowSink>(rec, len, e.scale, dst, lane);
+    } else if (SCHEME == kInt8) {
+        decode_int8<MODE, false, RowSink>(rec, len > kBlockElems ? kBlockElems : len, e.scale, dst, lane);
+    } else if (SCHEME == kInt4G32) {
+        decode_int4<false, RowSink>(rec, len, dst, lane);
+    } else if (SCHEME == kMxFp4) {
+        decode_mx4<false, RowSink>(rec, rec + __float_as_uint(e.scale), len, dst, lane);
+    } else if (SCHEME == kFp8E4m3) {
+        decode_fp8<false, RowSink>(rec, len > kBlockElems ? kBlockElems : len, e.scale, dst, lane);
+    } else {
+        decode_fp16<false, RowSink>(rec, len > 2u * kBlockElems ? 2u * kBlockElems : len, dst, lane);
+    }
+}
+
+// The encoder body with its third source form: beside the contiguous image (SrcRun) and the four row pointers of a commit, the
+// two rows of a page read from the slots of a paged cache.  No row (a padding slot) reads the launch's 2048 zero bytes: the
+// record of a zero row, and never memory outside the cache.
+template <int SCHEME, int MODE>
+__global__ __launch_bounds__(kThreads) void k_compress_slots(SlotArgs a)
+{
+    SPECKV_ENC_LDS(SCHEME);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    SlotWork w;
+    if (!slot_work(a, __builtin_amdgcn_readfirstlane(wave), &w)) return;
+    const SrcPair src{w.slot[0] >= 0 ? w.base + static_cast<uint64_t>(w.slot[0]) * 2048u : a.zeros,
+                      w.slot[1] >= 0 ? w.base + static_cast<uint64_t>(w.slot[1]) * 2048u : a.zeros};
+    PageEntry* entries = w.g->entries;
+    __builtin_assume(entries != nullptr);
+    const EncTarget t{entries, w.g->scale_tab, w.g->region_pages, w.g->scale_run, nullptr, nullptr, 0, nullptr, nullptr};
+    compress_block<SCHEME, MODE>(t, (2ull * a.layer_begin + w.j) * a.page_step + w.pair, src, lds, lane, wave);
+}
+
+template <int SCHEME, int MODE>
+hipError_t launch_dec_slots(const SlotArgs& a, uint32_t grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_read_slots<SCHEME, MODE>), dim3(grid), dim3(kThreads), 0, s, a);
+    return hipGetLastError();
+}
+template <int SCHEME>
+hipError_t launch_dec_slots_mode(const SlotArgs& a, uint32_t grid, hipStream_t s)
+{
+    return a.quant_mode == kIntent ? launch_dec_slots<SCHEME, kIntent>(a, grid, s) : launch_dec_slots<SCHEME, kRefExact>(a, grid, s);
+}
+template <int SCHEME, int MODE>
+hipError_t launch_enc_slots(const SlotArgs& a, uint32_t grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_compress_slots<SCHEME, MODE>), dim3(grid), dim3(kThreads), 0, s, a);
+    return hipGetLastError();
+}
+template <int SCHEME>
+hipError_t launch_enc_slots_mode(const SlotArgs& a, uint32_t grid, hipStream_t s)
+{
+    return a.quant_mode == kIntent ? launch_enc_slots<SCHEME, kIntent>(a, grid, s) : launch_enc_slots<SCHEME, kRefExact>(a, grid, s);
+}
+// what both launchers ask of a SlotArgs; *grid = one block per wave
+bool slot_args_ok(const SlotArgs& a, uint32_t* grid)
+{
+    const uint64_t waves = static_cast<uint64_t>(a.n_pairs) * 2u * a.n_layers;
+    if (!a.spans || !a.caches || !a.slots || a.n_spans == 0 || a.page_step == 0 || a.kind_stride % 16u || waves > (1ull << 31)) return false;
+    *grid = static_cast<uint32_t>((waves + kWaves - 1) / kWaves);
+    return true;
+}
+} // namespace
+
+hipError_t launch_compress_slots(const SlotArgs& a, hipStream_t s)
+{
+    if (a.n_pairs == 0 || a.n_layers == 0) return hipSuccess;
+    uint32_t grid = 0;
+    if (!slot_args_ok(a, &grid) || !a.zeros) return hipErrorInvalidValue;
+    switch (a.scheme) {
+    case kFp16: return launch_enc_slots_mode<kFp16>(a, grid, s);
+    case kInt8: return launch_enc_slots_mode<kInt8>(a, grid, s);
+    case kInt8DeltaRle: return launch_enc_slots_mode<kInt8DeltaRle>(a, grid, s);
+    case kInt4G32: return launch_enc_slots<kInt4G32, kRefExact>(a, grid, s);         // the quantiser mode does not apply
+    case kFp8E4m3: return launch_enc_slots<kFp8E4m3, kRefExact>(a, grid, s);
+    case kMxFp4: return launch_enc_slots<kMxFp4, kRefExact>(a, grid, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_read_slots(const SlotArgs& a, hipStream_t s)
+{
+    if (a.n_pairs == 0 || a.n_layers == 0) return hipSuccess;
+    uint32_t grid = 0;
+    if (!slot_args_ok(a, &grid) || !a.tab) return hipErrorInvalidValue;
+    switch (a.scheme) {
+    case kFp16: return launch_dec_slots<kFp16, kRefExact>(a, grid, s);               // (a copy: no quantiser)
+    case kInt8: return launch_dec_slots_mode<kInt8>(a, grid, s);
+    case kInt8DeltaRle: return launch_dec_slots_mode<kInt8DeltaRle>(a, grid, s);
+    case kInt4G32: return launch_dec_slots<kInt4G32, kRefExact>(a, grid, s);         // the quantiser mode does not apply
+    case kFp8E4m3: return launch_dec_slots<kFp8E4m3, kRefExact>(a, grid, s);
+    case kMxFp4: return launch_dec_slots<kMxFp4, kRefExact>(a, grid, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 } // namespace speckv

@@ -117,6 +117,44 @@ struct ReadPairArgs {
     int             quant_mode;
 };
 
+// One span of a paged-cache transfer (SlotArgs::spans; k_read_slots / k_compress_slots): positions [first_token, first_token +
+// n_tokens) of one allocation -- the reader finds its page table through table_row, the writer is handed entries / scale_tab /
+// region_pages / scale_run as CommitPair carries them -- row t of the span lying in slot slots[slot_begin + t] of the caller's
+// paged cache.  The span covers position pairs [first_token / 2, (first_token + n_tokens + 1) / 2); first_pair = the pairs of the
+// spans in front of this one (the host's exclusive prefix: the kernel finds the span of a flat pair index by binary search and
+// needs no atomics).  Descriptors are per span, never per pair or per token.
+struct SlotSpan {
+    PageEntry* entries;               // the destination (write); unused by the reader
+    float*     scale_tab;
+    uint32_t   region_pages;
+    uint32_t   scale_run;
+    uint32_t   table_row;             // DevAlloc row of the source (read)
+    uint32_t   first_token;
+    uint32_t   n_tokens;
+    uint32_t   first_pair;            // exclusive prefix of pair counts
+    uint64_t   slot_begin;
+};
+// Page of (layer, kind, position) = (2 * layer + kind) * page_step + position / 2, layer = layer_begin + l for l < n_layers; the
+// row of slot s of that (l, kind) is caches[l] + kind * kind_stride + s * 2048.  A slot < 0 or >= n_slots is no row: not stored
+// by the reader, read as `zeros` (2048 zero bytes) by the writer.
+struct SlotArgs {
+    const SlotSpan*  spans;           // device array, and behind it in the same staged slot ...
+    const uint64_t*  caches;          // ... the n_layers cache bases (device array of device addresses)
+    const int64_t*   slots;           // the caller's slot mapping (device)
+    const DevAlloc*  tab;             // the device allocation table (read)
+    const uint8_t*   zeros;           // 2048 zero bytes (write)
+    uint64_t         n_slots;
+    uint64_t         kind_stride;     // bytes, a multiple of 16
+    uint64_t         page_step;
+    uint32_t         n_spans;
+    uint32_t         n_pairs;         // the sum of the spans' pair counts
+    uint32_t         n_layers;
+    uint32_t         layer_begin;
+    uint32_t         kind_fast;       // the order of the waves: 0 = pair fastest inside a (layer, kind), 1 = (layer, kind) fastest
+    int              scheme;
+    int              quant_mode;
+};
+
 // One (source, destination) pair of a record-copy launch (CopyArgs::pairs; copy_records.hip): the stored records of pages
 // [run_firsts[r], run_firsts[r] + n_pages), every run r of the launch, go from the allocation in table row `src_row` to the same
 // pages of the allocation whose page table is `entries` -- scale_tab / region_pages / scale_run as CommitPair carries them.
@@ -343,6 +381,9 @@ hipError_t launch_decompress(const CodecArgs& a, hipStream_t s);
 // the pair-gather form of the encoder: n_pairs * 2 * n_layers blocks in one launch, rows read where they lie (k_compress_pairs)
 hipError_t launch_compress_pairs(const PairArgs& a, hipStream_t s);
 hipError_t launch_read_pairs(const ReadPairArgs& a, hipStream_t s);
+// the paged-cache forms of both: n_pairs * 2 * n_layers blocks in one launch, rows addressed by a device slot mapping
+hipError_t launch_compress_slots(const SlotArgs& a, hipStream_t s);
+hipError_t launch_read_slots(const SlotArgs& a, hipStream_t s);
 
 // FPGACacheEngine::compress / ::decompress over a tensor of any length (tensor_codec.hip): one scale, one delta chain and
 // one run-length stream across the whole tensor.  d_rle: 16-byte aligned, room for 2n bytes rounded up to 16; d_ws:

@@ -36,6 +36,7 @@ const Key kKeys[] = {
     {"rounds_consecutive", "SPECKV_ROUNDS", &Tuning::rounds_consecutive},
     {"remote_engine", "SPECKV_REMOTE_ENGINE", &Tuning::remote_engine},
     {"copy_min_run_kb", "SPECKV_COPY_MIN_RUN_KB", &Tuning::copy_min_run_kb},
+    {"slots_kind_fast", "SPECKV_SLOTS_KIND_FAST", &Tuning::slots_kind_fast},
 };
 // a few of the environment's values are words, as they always were
 int32_t parse(const char* env_name, const char* v)

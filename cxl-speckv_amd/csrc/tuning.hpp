@@ -40,6 +40,8 @@ struct Tuning {
     // remote fetch engine: 0 per batch, 1 fused peer-load kernel, 2 copy engines (SPECKV_REMOTE_ENGINE=kernel|copy)
     int32_t remote_engine = 0;
     int32_t copy_min_run_kb = 1024;         // SPECKV_COPY_MIN_RUN_KB          shortest per-pool run the copy engines take by themselves
+    // paged-cache transfers (read_slots / write_slots): the order of the waves
+    int32_t slots_kind_fast = 0;            // SPECKV_SLOTS_KIND_FAST          1: (layer, kind) fastest, as k_read_pairs; 0: pair fastest inside a (layer, kind) (A/B)
 };
 
 Tuning& tuning();                                        // process-wide; filled from the environment on first use

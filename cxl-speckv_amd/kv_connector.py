@@ -37,6 +37,9 @@ paged-attention layer would talk to for a BATCH of requests:
                                hold only what is their own, the prefix is a request the call names; the own step as attend / attend_chunk
                                issue it, then ONE ``speckv_ext_attend_prefix_fold`` launch that reads the prefix once per 64 query rows
                                and folds it in (``attend_chunk_shared`` for a member's own chunk; ``shared_groups``)
+  load_paged / store_paged     the route in and out of the pool for vLLM-style paged caches (one tensor per layer, rows addressed by a
+                               slot mapping on the device): spans of positions of a batch of requests decoded into their slots, or encoded
+                               from them, by one launch each way (``speckv_ext_read_slots`` / ``speckv_ext_write_slots``; ``paged_spans``)
 
 Only plain device pointers cross into the library; torch is used for device buffers and the tail fold.
 """
@@ -394,8 +397,163 @@ class SpeckvKVConnector:
             out = out * self._kscale[layer][None]                        # back to the caller's scaling (exact: powers of two)
         return out[pos_begin - lo:pos_end - lo]
 
+    # ------------------------------------------------------------------ paged caches (vLLM's blocks)
+    @staticmethod
+    def paged_spans(firsts: Sequence[int], counts: Sequence[int]):
+        """The position pairs a paged transfer touches, per span [firsts[i], firsts[i] + counts[i]): (first pair, pair count, pairs of
+        the spans in front of it).  A span covers the pairs [first // 2, (first + count + 1) // 2) -- a pair it only half covers
+        included -- and an empty span none; the exclusive prefix is what the kernels search to find the span of a flat pair index
+        (speckv_ext_read_slots / _write_slots compute the same on the host).  Pure: no connector state."""
+        if len(firsts) != len(counts):
+            raise ValueError("paged_spans: one count per first position")
+        out, prefix = [], 0
+        for f, c in zip(firsts, counts):
+            f, c = int(f), int(c)
+            if f < 0 or c < 0:
+                raise ValueError(f"paged_spans: span [{f}, {f} + {c})")
+            n = (f + c + 1) // 2 - f // 2 if c else 0
+            out.append((f // 2, n, prefix))
+            prefix += n
+        return out
+
+    def _paged_geometry(self, caches):
+        """(slots per cache, bytes between the K and the V plane) if the one-launch route can address `caches` -- per layer a
+        [2, blocks, block_size, heads, dim] fp16 tensor whose slots are 2048-byte rows one after the other -- else None."""
+        import torch
+        if self._kscale is not None or len(caches) != self.L:
+            return None
+        geo = None
+        for c in caches:
+            if c.dtype != torch.float16 or c.dim() != 5 or c.shape[0] != 2 or c.shape[3] * c.shape[4] * 2 != 2048:
+                return None
+            if tuple(c.stride()[2:]) != (c.shape[3] * c.shape[4], c.shape[4], 1) or c.stride(1) != c.shape[2] * 1024:
+                return None
+            if c.data_ptr() % 16 or (c.stride(0) * 2) % 16:
+                return None
+            g = (c.shape[1] * c.shape[2], c.stride(0) * 2)
+            if geo is not None and g != geo:
+                return None
+            geo = g
+        return geo
+
+    def _paged_args(self, req_ids, counts, slot_mapping, caches):
+        import torch
+        reqs = [self.requests[rid] for rid in req_ids]
+        counts = [int(c) for c in counts]
+        if len(counts) != len(reqs) or any(c < 0 for c in counts):
+            raise ValueError("one non-negative count per request")
+        if len(caches) != self.L:
+            raise ValueError(f"{len(caches)} caches for {self.L} layers")
+        if slot_mapping.dtype != torch.int64 or slot_mapping.dim() != 1 or not slot_mapping.is_contiguous() \
+                or slot_mapping.numel() != sum(counts):
+            raise ValueError("slot_mapping: one contiguous int64 device tensor, the spans concatenated")
+        begins, at = [], 0
+        for c in counts:
+            begins.append(at)
+            at += c
+        return reqs, counts, begins
+
+    def load_paged(self, req_ids: Sequence[int], firsts: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None):
+        """Pool -> paged caches: positions [firsts[i], firsts[i] + counts[i]) of request req_ids[i] go into the slots
+        slot_mapping[b_i : b_i + counts[i]] (b_i = the counts in front: ONE int64 device tensor for the call, the spans concatenated) of
+        `caches`, the per-layer [2, blocks, block_size, 8, 128] fp16 tensors.  ONE speckv_ext_read_slots call decodes every stored row
+        of every layer where its slot is; a span that reaches a request's odd last position gets that row from the held tail by a
+        torch copy, as kv_rows does.  A slot < 0 or beyond the cache is skipped.
+        Fall-back to the row route (kv_rows + index_copy_ per request, layer and kind) when a K pre-scale is set, a cache is not
+        fp16, not contiguous in its last three dimensions, or does not have 2048-byte rows one block after the other (bf16 caches are
+        out of scope: the pool moves raw fp16 bits)."""
+        import numpy as np
+        import torch
+        reqs, counts, begins = self._paged_args(req_ids, counts, slot_mapping, caches)
+        firsts = [int(f) for f in firsts]
+        if len(firsts) != len(reqs):
+            raise ValueError("one first position per request")
+        for r, f, c in zip(reqs, firsts, counts):
+            if not 0 <= f <= f + c <= r.length:
+                raise ValueError(f"rows [{f}, {f + c}) of a request with {r.length} positions")
+        geo = self._paged_geometry(caches)
+        if geo is None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                for rid, f, c, b in zip(req_ids, firsts, counts, begins):
+                    if not c:
+                        continue
+                    slots = slot_mapping[b:b + c]
+                    for layer, cache in enumerate(caches):
+                        flat = cache.reshape(2, cache.shape[1] * cache.shape[2], cache.shape[3], cache.shape[4])
+                        for kind in (0, 1):
+                            flat[kind].index_copy_(0, slots, self.kv_rows(rid, layer, kind, f, f + c).to(flat.dtype))
+            return
+        n_slots, kind_stride = geo
+        stored = [max(min(f + c, r.length & ~1) - f, 0) for r, f, c in zip(reqs, firsts, counts)]
+        with self._On(self, stream) as st:
+            if any(stored):
+                self.lib.read_slots(np.asarray([r.handle for r in reqs], dtype=np.uint64), np.asarray(firsts, dtype=np.uint64),
+                                    np.asarray(stored, dtype=np.uint64), np.asarray(begins, dtype=np.uint64), slot_mapping.data_ptr(), n_slots,
+                                    np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride, self.region_pages, st.cuda_stream)
+            with torch.cuda.stream(st):
+                for r, f, c, b, n in zip(reqs, firsts, counts, begins, stored):
+                    if c > n:                                                 # the odd last position lives in the tail
+                        at = slot_mapping[b + n:b + n + 1]
+                        for layer, cache in enumerate(caches):
+                            cache[0].view(n_slots, self.H, self.D).index_copy_(0, at, r.tail_k[layer][None])
+                            cache[1].view(n_slots, self.H, self.D).index_copy_(0, at, r.tail_v[layer][None])
+
+    def store_paged(self, req_ids: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None):
+        """Paged caches -> pool: request req_ids[i], whose current length is even (an odd one raises ValueError: not built), gets
+        counts[i] more positions, read from the slots slot_mapping[b_i : b_i + counts[i]] of `caches` (as load_paged).  ONE
+        speckv_ext_write_slots call encodes the whole pairs of every layer straight from the caches -- no gathered copy exists, so
+        the caller holds nothing, but the caches and the mapping stay unchanged until the stream has passed the call; an odd last
+        position becomes the tail, gathered with torch.  Lengths and the step bookkeeping move as in write_prefill.  A slot < 0 or
+        beyond the cache is stored as a row of zeros.
+        Fall-back to the row route (index_select per layer, torch.stack, write_prefill per request -- for requests that are still
+        empty) under the conditions load_paged names.  Returns the tensors the row route's launches read (hold them until the
+        stream has passed), an empty list on the one-launch route."""
+        import numpy as np
+        import torch
+        reqs, counts, begins = self._paged_args(req_ids, counts, slot_mapping, caches)
+        if len(set(req_ids)) != len(reqs):
+            raise ValueError("store_paged: a request named twice")
+        for r, c in zip(reqs, counts):
+            if r.length & 1:
+                raise ValueError("store_paged on a request of odd length")
+            if r.length + c > self.T:
+                raise ValueError(f"{r.length} + {c} positions in a request built for {self.T}")
+        geo = self._paged_geometry(caches)
+        if geo is None:
+            held = []
+            if any(r.length for r, c in zip(reqs, counts) if c):
+                raise ValueError("store_paged: the row route writes whole prompts (write_prefill) and these requests hold positions")
+            for rid, c, b in zip(req_ids, counts, begins):
+                if not c:
+                    continue
+                slots = slot_mapping[b:b + c]
+                flats = [cache.reshape(2, cache.shape[1] * cache.shape[2], cache.shape[3], cache.shape[4]) for cache in caches]
+                k = torch.stack([f[0].index_select(0, slots) for f in flats]).to(torch.float16)      # [layers][tokens][heads][dim]
+                v = torch.stack([f[1].index_select(0, slots) for f in flats]).to(torch.float16)
+                held += self.write_prefill(rid, k, v, stream)
+            return held
+        n_slots, kind_stride = geo
+        whole = [c & ~1 for c in counts]
+        with self._On(self, stream) as st:
+            if any(whole):
+                self.lib.write_slots(np.asarray([r.handle for r in reqs], dtype=np.uint64), np.asarray([r.length for r in reqs], dtype=np.uint64),
+                                     np.asarray(whole, dtype=np.uint64), np.asarray(begins, dtype=np.uint64), slot_mapping.data_ptr(), n_slots,
+                                     np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride, self.region_pages, st.cuda_stream)
+            with torch.cuda.stream(st):
+                for r, c, b in zip(reqs, counts, begins):
+                    if c & 1:
+                        at = slot_mapping[b + c - 1:b + c]
+                        r.set_tail(torch.cat([cache[0].view(n_slots, self.H, self.D).index_select(0, at) for cache in caches]),
+                                   torch.cat([cache[1].view(n_slots, self.H, self.D).index_select(0, at) for cache in caches]))
+        if any(rid in self._tail_ids for rid in req_ids):
+            self._tail_ids, self._tail_k, self._tail_v = (), None, None
+        for r, c in zip(reqs, counts):
+            r.length += c
+        self._epoch += 1
+        return []
+
     PLAN_BUCKET = 512
-    WINDOW_PLANS_MAX = 8                   # plan buffers kept for window values (plan_step(window=W)) beside the global one
+    WINDOW_PLANS_MAX = 8                 # plan buffers kept for window values (plan_step(window=W)) beside the global one
 
     @staticmethod
     def _decode_window(window):

@@ -67,6 +67,10 @@ _EXT_SIGNATURES = {
     "speckv_ext_write_runs": [c_uint64, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p],
     "speckv_ext_write_pairs": [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_uint64, c_void_p],
     "speckv_ext_read_pairs": [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_uint64, c_void_p],
+    "speckv_ext_read_slots": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint64,
+                              c_uint64, c_void_p],
+    "speckv_ext_write_slots": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint64,
+                               c_uint64, c_void_p],
     "speckv_ext_copy_runs": [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
     "speckv_ext_attend_chunk": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                 c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
@@ -323,6 +327,26 @@ class SpeckvLib:
             rows = [p for r in rows for p in r]
         hs, fs, rs = as_arr(handles, c_uint64, n), as_arr(first_pages, c_uint64, n), as_arr(rows, c_uint64, 4 * n)
         self._ext("speckv_ext_read_pairs", hs, fs, rs, n, page_step, n_layers, layer_stride, c_void_p(stream))
+
+    def _slots(self, entry, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step, stream):
+        n, nl = len(handles), len(caches)
+        hs, fs, ns, bs = (as_arr(x, c_uint64, n) for x in (handles, first_tokens, n_tokens, slot_begins))
+        self._ext(entry, hs, fs, ns, bs, n, c_void_p(d_slots), n_slots, as_arr(caches, c_uint64, nl), layer_begin, nl, kind_stride, page_step,
+                  c_void_p(stream))
+
+    def read_slots(self, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step, stream):
+        """Pool -> paged cache in ONE launch (speckv_ext_read_slots): span i = positions [first_tokens[i], + n_tokens[i]) of handles[i],
+        row t of it decoded into slot d_slots[slot_begins[i] + t] (d_slots: the address of an int64 device array) of every layer
+        layer_begin + l -- caches[l] = that layer's base address, K plane at 0, V plane at kind_stride bytes, 2048 bytes per slot; a slot
+        < 0 or >= n_slots is skipped.  handles .. slot_begins, caches: numpy uint64 arrays, ctypes arrays or sequences."""
+        self._slots("speckv_ext_read_slots", handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride,
+                    page_step, stream)
+
+    def write_slots(self, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step, stream):
+        """Paged cache -> pool in ONE launch (speckv_ext_write_slots): read_slots backwards, whole pairs only (first_tokens and n_tokens
+        even); a slot < 0 or >= n_slots is stored as a row of zeros.  Arguments as read_slots."""
+        self._slots("speckv_ext_write_slots", handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride,
+                    page_step, stream)
 
     def copy_runs(self, src, dst, n_pages, run_firsts, stream):
         """The stored records of pages [run_firsts[r], run_firsts[r] + n_pages[i]), every run r, copied from allocation src[i] to the same

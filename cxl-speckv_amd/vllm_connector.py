@@ -22,6 +22,10 @@ object may play both roles (a single-process engine, the test), or two objects m
 scheduler role: it never touches the GPU) -- tests/test_gpu_round3.py runs both arrangements.
 
 paged cache layout (vLLM v1, FlashAttention backend): one tensor per layer, ``[2, num_blocks, block_size, kv_heads, head_dim]``.
+
+``paged_io=True``: a step's loads are ONE ``SpeckvKVConnector.load_paged`` call and its stores ONE ``store_paged`` call, straight
+between the pool and the registered caches (``speckv_ext_read_slots`` / ``speckv_ext_write_slots``); the default is the row route:
+a fetch and a scatter per (request, layer, kind), a gathered copy of every prompt held until its write has run.
 """
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -82,11 +86,14 @@ def _cached_requests(scheduler_output):
 
 class SpeckvVllmConnector:
     def __init__(self, lib, num_layers: int, num_kv_heads: int = 8, head_dim: int = 128, block_size: int = 16,
-                 max_tokens: int = 4096, scheme: str = "fp16"):
+                 max_tokens: int = 4096, scheme: str = "fp16", paged_io: bool = False):
         # worker role: the pool.  lib=None builds a scheduler-role object (no GPU, no library)
         self.conn = None if lib is None else SpeckvKVConnector(lib, num_layers=num_layers, num_kv_heads=num_kv_heads, head_dim=head_dim,
                                                                 max_tokens=max_tokens, scheme=scheme)
         self.L, self.block_size, self.max_tokens = num_layers, block_size, max_tokens
+        # paged_io: a step's loads are ONE SpeckvKVConnector.load_paged call and its stores ONE store_paged call, straight between the
+        # pool and the registered caches, instead of a fetch and a scatter per (request, layer, kind) and a stashed copy of every prompt
+        self.paged_io = bool(paged_io)
         # ---- scheduler-role state (never read by the worker-role methods)
         self._ids: Dict[str, int] = {}                     # vLLM request id (a string) -> the engine's request id
         self._next_id = 1
@@ -101,6 +108,7 @@ class SpeckvVllmConnector:
         self._caches = {}
         self._live: Dict[int, str] = {}                    # engine ids that have an allocation in this worker's pool
         self._stash: Dict[int, Dict[int, tuple]] = {}      # engine id -> layer index -> (k rows, v rows) waiting for wait_for_save
+        self._handed: Dict[int, set] = {}                  # paged_io: engine id -> layer indices handed over as the registered cache
         self._held = []                                    # sources of asynchronous pool writes (until the next step)
 
     # ------------------------------------------------------------------ scheduler side
@@ -220,6 +228,7 @@ class SpeckvVllmConnector:
             if self._live.pop(eid, None) is not None:
                 self.conn.free_request(eid)
             self._stash.pop(eid, None)
+            self._handed.pop(eid, None)
 
     def bind_connector_metadata(self, connector_metadata: SpeckvConnectorMetadata):
         self._meta = connector_metadata
@@ -232,20 +241,27 @@ class SpeckvVllmConnector:
     def start_load_kv(self, forward_context=None, **kwargs):
         """Pool -> paged cache for every load request of the bound metadata (fetch + decompress of the pages that hold the
         request's tokens [first_token, first_token + num_tokens), then vLLM's own scatter:
-        ``cache.reshape(2, blocks * block_size, -1)[:, slots] = rows``)."""
+        ``cache.reshape(2, blocks * block_size, -1)[:, slots] = rows``).  paged_io: ONE load_paged call for all load requests of the
+        step, one slot tensor uploaded, the rows decoded into their slots."""
         import torch
         if self._meta is None:
             return
         self._need_pool("start_load_kv")
-        for r in self._meta.requests:
-            if r.is_store:
-                continue
+        loads = [r for r in self._meta.requests if not r.is_store]
+        for r in loads:
             if r.engine_id not in self._live:
                 raise RuntimeError(f"request {r.req_id!r} (engine id {r.engine_id}) is not in this worker's pool: the scheduler "
                                    "matched tokens that no save of this worker produced")
             have = self.conn.length(r.engine_id)
             if r.first_token + r.num_tokens > have:
                 raise RuntimeError(f"request {r.req_id!r}: tokens [{r.first_token}, {r.first_token + r.num_tokens}) asked for, {have} stored")
+        if self.paged_io:
+            if loads:
+                slots = torch.tensor([s for r in loads for s in r.slot_mapping], dtype=torch.int64, device="cuda")
+                self.conn.load_paged([r.engine_id for r in loads], [r.first_token for r in loads], [r.num_tokens for r in loads], slots,
+                                     [self._caches[name] for name in self._layers])
+            return
+        for r in loads:
             slots = torch.tensor(r.slot_mapping, dtype=torch.int64, device="cuda")
             for li, name in enumerate(self._layers):
                 cache = self._caches[name]
@@ -257,27 +273,65 @@ class SpeckvVllmConnector:
     def wait_for_layer_load(self, layer_name: str):
         return                                                  # the loads were issued on the forward pass's own stream
 
-    def save_kv_layer(self, layer_name: str, kv_layer, attn_metadata=None, **kwargs):
-        """Paged cache -> (held until wait_for_save) for the store requests: vLLM's own gather by slot mapping."""
+    @staticmethod
+    def _same_tensor(a, b):
+        return a is b or (a.data_ptr() == b.data_ptr() and a.dtype == b.dtype and tuple(a.shape) == tuple(b.shape) and a.stride() == b.stride())
+
+    def _stash_layer(self, r, li, flat):
         import torch
+        slots = torch.tensor(r.slot_mapping, dtype=torch.int64, device="cuda")
+        self._stash.setdefault(r.engine_id, {})[li] = (r.req_id, flat[0].index_select(0, slots), flat[1].index_select(0, slots))
+
+    def save_kv_layer(self, layer_name: str, kv_layer, attn_metadata=None, **kwargs):
+        """Paged cache -> (held until wait_for_save) for the store requests: vLLM's own gather by slot mapping.  paged_io: nothing is
+        gathered -- the layer is recorded as handed over, and wait_for_save reads the registered cache itself; a `kv_layer` that is
+        not the registered tensor of the layer sends that request down the stash route."""
         if self._meta is None:
             return
         li = self._layers.index(layer_name)
         flat = kv_layer.reshape(2, kv_layer.shape[1] * kv_layer.shape[2], kv_layer.shape[3], kv_layer.shape[4])
+        registered = self.paged_io and self._same_tensor(kv_layer, self._caches[layer_name])
         for r in self._meta.requests:
             if not r.is_store:
                 continue
-            slots = torch.tensor(r.slot_mapping, dtype=torch.int64, device="cuda")
-            self._stash.setdefault(r.engine_id, {})[li] = (r.req_id, flat[0].index_select(0, slots), flat[1].index_select(0, slots))
+            if registered:
+                h = self._handed.setdefault(r.engine_id, {"req_id": r.req_id, "slots": r.slot_mapping, "layers": set()})
+                h["layers"].add(li)
+            else:
+                self._stash_layer(r, li, flat)
 
     def wait_for_save(self):
-        """All layers of the step have been handed over: one asynchronous pool write per request (speckv_ext_write_runs)."""
+        """All layers of the step have been handed over: one asynchronous pool write per request (speckv_ext_write_runs).  paged_io:
+        ONE store_paged call for all store requests of the step, read from the registered caches (which therefore stay unchanged
+        until the stream has passed it, as vLLM's blocks of a running step do)."""
         import torch
         self._need_pool("wait_for_save")
         self._held = []
+        for eid, h in list(self._handed.items()):
+            if eid in self._stash:                               # some layer came as another tensor: the whole request by the stash route
+                for li in h["layers"] - set(self._stash[eid]):
+                    cache = self._caches[self._layers[li]]
+                    self._stash_layer(ReqMeta(h["req_id"], eid, h["slots"], 0, len(h["slots"]), True), li,
+                                      cache.reshape(2, cache.shape[1] * cache.shape[2], cache.shape[3], cache.shape[4]))
+                del self._handed[eid]
+        for eid, h in self._handed.items():
+            if len(h["layers"]) != self.L:
+                raise RuntimeError(f"request {h['req_id']!r}: {len(h['layers'])} of {self.L} layers were saved")
         for eid, layers in self._stash.items():
             if len(layers) != self.L:
                 raise RuntimeError(f"request {layers[next(iter(layers))][0]!r}: {len(layers)} of {self.L} layers were saved")
+        if self._handed:
+            for eid, h in self._handed.items():
+                if eid in self._live:                            # the same id stored again (a re-used request id): replace
+                    self.conn.free_request(eid)
+                self.conn.add_request(eid)
+                self._live[eid] = h["req_id"]
+            slots = torch.tensor([s for h in self._handed.values() for s in h["slots"]], dtype=torch.int64, device="cuda")
+            self._held += self.conn.store_paged(list(self._handed), [len(h["slots"]) for h in self._handed.values()], slots,
+                                                [self._caches[name] for name in self._layers])
+            self._held.append(slots)
+            self._handed.clear()
+        for eid, layers in self._stash.items():
             k = torch.stack([layers[i][1] for i in range(self.L)]).to(torch.float16)     # [layers][tokens][heads][dim]
             v = torch.stack([layers[i][2] for i in range(self.L)]).to(torch.float16)
             if eid in self._live:                                # the same id stored again (a re-used request id): replace

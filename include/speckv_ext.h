@@ -144,6 +144,43 @@ speckv_status_t speckv_ext_read_pairs(const speckv_handle_t* handles, const uint
                                       void* const* d_rows /* [n_pairs][4]: K even, K odd, V even, V odd; NULL = not wanted */,
                                       uint32_t n_pairs, uint64_t page_step, uint32_t n_layers,
                                       uint64_t layer_stride_bytes, void* stream);
+/* Paged-cache transfers: spans of positions between the pool and the blocks of a caller's paged KV cache (vLLM's layout: one cache
+ * tensor per layer, a row addressed by a slot id), ONE launch per call.  Span i is positions [first_tokens[i], first_tokens[i] +
+ * n_tokens[i]) of allocation handles[i] in the shim layout: the page of (layer, kind, position) is (2 * layer + kind) * page_step +
+ * position / 2, for the layers [layer_begin, layer_begin + n_layers).  Row t of span i lies in slot d_slots[slot_begins[i] + t] --
+ * d_slots is an int64 array ON THE DEVICE, the spans' mappings concatenated (slot_begins are host values) -- and the row of slot s is
+ * the 2048 bytes ([heads][128] fp16) at d_caches[l] + kind * kind_stride_bytes + s * 2048, d_caches being a HOST array of n_layers
+ * device addresses, d_caches[l] the base of layer layer_begin + l (K plane at 0, V plane at kind_stride_bytes).  A slot that is
+ * negative (a padding slot) or >= n_slots names no row.  What is staged per call is one descriptor per span and the n_layers
+ * addresses: nothing grows with the token count.
+ * speckv_ext_read_slots decodes.  A span may begin and end on any position of the stored (paired) part of an allocation; a position
+ * outside its span, or one whose slot names no row, is not written (and, where the format keeps the halves of a page apart, not
+ * read).  The bits are those speckv_ext_fetch_range writes for the same pages as fp16, for every scheme and both quantiser modes; a
+ * page never written gives zeros.  Ordering and placement as speckv_ext_read_pairs: asynchronous on `stream`, behind what the
+ * caller queued there before and behind the asynchronous pool writes handed to other streams before the call; linear, striped,
+ * migrated and sealed allocations alike, a sealed allocation stays sealed.
+ * speckv_ext_write_slots encodes whole pairs: first_tokens[i] and n_tokens[i] are even.  The records are those
+ * speckv_ext_write_runs stores for the same rows laid out contiguously; a slot that names no row is read as a row of zeros, and
+ * nothing outside the caches is ever read.  Host side as speckv_ext_write_pairs: a sealed destination is unpacked, cached target
+ * pages are invalidated first.  The caches and d_slots must stay alive and unchanged until the stream has passed the call.
+ *   SPECKV_ERR_INVAL    NULL stream or arrays, a NULL cache pointer or one not 16-byte aligned, kind_stride_bytes not a multiple of
+ *                       16, page_step == 0, allocations of different schemes, a capturing stream; write: an odd first_tokens[i] or
+ *                       n_tokens[i], two spans of one allocation that share a page
+ *   SPECKV_ERR_GENERAL  an unknown handle, a span that leaves its (layer, kind) region (first + n > 2 * page_step) or the allocation
+ * n_spans == 0, n_layers == 0 or every n_tokens[i] == 0: SPECKV_OK, nothing is done.  Every refusal launches nothing.  The pages
+ * are counted in total_decompressions (and dma_submitted / dma_completed) or total_compressions like those of the pair entries. */
+speckv_status_t speckv_ext_read_slots(const speckv_handle_t* handles, const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                      const uint64_t* slot_begins, uint32_t n_spans,
+                                      const int64_t* d_slots /* device */, uint64_t n_slots,
+                                      void* const* d_caches /* host array of n_layers device pointers */,
+                                      uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                      uint64_t page_step, void* stream);
+speckv_status_t speckv_ext_write_slots(const speckv_handle_t* handles, const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                       const uint64_t* slot_begins, uint32_t n_spans,
+                                       const int64_t* d_slots /* device */, uint64_t n_slots,
+                                       const void* const* d_caches /* host array of n_layers device pointers */,
+                                       uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                       uint64_t page_step, void* stream);
 /* Fork: the STORED RECORDS of page runs copied from one allocation to another, nothing decoded.  Pair i copies pages
  * [run_firsts[r], run_firsts[r] + n_pages[i]) for every run r < n_runs from allocation src[i] to the same page numbers of
  * allocation dst[i] (in the shim layout the runs are the 2 * num_layers (layer, kind) regions and n_pages[i] = positions / 2: a
@@ -718,7 +755,8 @@ speckv_status_t speckv_ext_decode_window_range(uint32_t length, uint32_t window,
  * call of the process; after that a form is changed by this call only.  Keys (= the SPECKV_<KEY> environment names, lower case):
  * attend_splits, attend_tiles_per_split, attend_general, tc_multipass, tc_scan (1 one workgroup, 2 one wave), tc_no_pre,
  * tc_no_split_tiles, td_one_pass, td_expand_per_element, flush_no_small, flush_small_words, predict_batch_path, wgs_per_cu, tc_batch_one_wg (many-tensor launches: one workgroup per tensor),
- * rounds_consecutive, remote_engine (1 kernel, 2 copy engines), copy_min_run_kb, attend_stream (INT4_G32 / MXFP4, several layers of one
+ * rounds_consecutive, remote_engine (1 kernel, 2 copy engines), copy_min_run_kb, slots_kind_fast (speckv_ext_read_slots / _write_slots:
+ * the waves run (layer, kind) fastest instead of pair fastest), attend_stream (INT4_G32 / MXFP4, several layers of one
  * sequence: N > 0 the stream form in N pieces, -1 never), attend_mx4_one_half (MXFP4 batches: 4-wave workgroups also where
  * the two-halves form applies), attend_order_as_given (batches of members of different lengths: the caller's dispatch order), attend_fold_launch (speckv_ext_attend_planned_tail: the fold always as a launch of its own), attend_layers_loop
  * (speckv_ext_attend_planned_layers: always per-layer launches), attend_fp8_table_regs / attend_fp8_striped_table / attend_int4_striped_wg
