@@ -180,6 +180,9 @@ public:
         const uint64_t *handles, *first_tokens, *n_tokens, *slot_begins; uint32_t n_spans;
         const int64_t* d_slots; uint64_t n_slots; const void* const* d_caches; uint32_t layer_begin, n_layers;
         uint64_t kind_stride, page_step;
+        // the _ex entries (speckv_ext_slot_rows_t): the caches' element type and the held rows, [n_spans][2] host arrays or nullptr
+        bool ex = false; uint32_t elem = 0, reserved = 0;
+        const void* const* held_in = nullptr; void* const* held_out = nullptr; uint64_t held_stride = 0;
     };
     int read_slots(const SlotCall& c, hipStream_t s);
     int write_slots(const SlotCall& c, hipStream_t s);

@@ -16,29 +16,50 @@ namespace speckv {
 // knows; nothing is written to the pool.  Writing is write_groups': whole pairs only, sealed destinations are unpacked, cached
 // destination pages invalidated, the host mirror and note_async_write_or_wait follow the launch; two spans of one allocation that
 // share a page are refused.  Every refusal comes before any launch.
+// The _ex entries (c.ex) add the caches' element type and held rows -- one position per span and kind that lives outside pool and
+// caches as fp16 (SlotExArgs, kernels.hpp).  A span's pages are then [first / 2, p1): p1 = (first + n) / 2 on the write side (a
+// held-in row completes the first pair, a held-out row takes the odd last position), (first + n - 1) / 2 on the read side where
+// the last position comes from a held row, (first + n + 1) / 2 otherwise; a held row adds one SlotHeld per span to the staged
+// slot and the move waves to the launch.  With fp16 caches and no held rows the call is the plain one, launch for launch.
 int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
 {
-    const char* entry = write ? "speckv_ext_write_slots" : "speckv_ext_read_slots";
+    const char* entry = write ? (c.ex ? "speckv_ext_write_slots_ex" : "speckv_ext_write_slots") : (c.ex ? "speckv_ext_read_slots_ex" : "speckv_ext_read_slots");
     if (null_) return no_data_path(entry);
     if (!s || !c.handles || !c.first_tokens || !c.n_tokens || !c.slot_begins || !c.d_slots || !c.d_caches) return SPECKV_ERR_INVAL;
     if (c.kind_stride % 16u || c.page_step == 0) return SPECKV_ERR_INVAL;
+    if (c.elem > SPECKV_SLOT_ELEM_BF16 || c.reserved != 0 || c.held_stride % 16u || (!write && c.held_out)) return SPECKV_ERR_INVAL;
     if (c.n_spans == 0 || c.n_layers == 0) return SPECKV_OK;
     for (uint32_t l = 0; l < c.n_layers; ++l)
         if (!c.d_caches[l] || reinterpret_cast<uintptr_t>(c.d_caches[l]) % 16u) return SPECKV_ERR_INVAL;
-    uint64_t n_pairs = 0;
+    uint64_t n_pairs = 0, n_held = 0, n_in = 0;              // n_held: spans with a position that only moves
+    std::vector<uint64_t> p1(c.n_spans);                                         // span i's pages: [first / 2, p1[i]) of every region
     for (uint32_t i = 0; i < c.n_spans; ++i) {
         const uint64_t first = c.first_tokens[i], n = c.n_tokens[i];
-        if (write && ((first | n) & 1u)) return SPECKV_ERR_INVAL;               // whole pairs only
+        bool in = false, out = false;                                           // held rows of this span: K and V, or neither
+        for (int dir = 0; dir < 2; ++dir) {
+            const void* k = dir ? (c.held_out ? c.held_out[2 * i] : nullptr) : (c.held_in ? c.held_in[2 * i] : nullptr);
+            const void* v = dir ? (c.held_out ? c.held_out[2 * i + 1] : nullptr) : (c.held_in ? c.held_in[2 * i + 1] : nullptr);
+            if (!k != !v || reinterpret_cast<uintptr_t>(k) % 16u || reinterpret_cast<uintptr_t>(v) % 16u) return SPECKV_ERR_INVAL;
+            (dir ? out : in) = k != nullptr;
+        }
+        if (write && ((first & 1u) != (in ? 1u : 0u) || ((first + n) & 1u) != (out ? 1u : 0u))) return SPECKV_ERR_INVAL;   // whole pairs only
+        if ((in || out) && n == 0) return SPECKV_ERR_INVAL;
+        if (!write && in && ((first + n - 1) & 1u)) return SPECKV_ERR_INVAL;      // the held position of a span is an even one
         if (first > UINT32_MAX || n > UINT32_MAX || first + n > UINT32_MAX) return SPECKV_ERR_GENERAL;
-        if (n) n_pairs += (first + n + 1) / 2 - first / 2;
+        p1[i] = n == 0 ? first / 2 : write ? (first + n) / 2 : in ? (first + n - 1) / 2 : (first + n + 1) / 2;
+        n_pairs += p1[i] - first / 2;
+        n_held += (write ? out : in) ? 1u : 0u;
+        n_in += in ? 1u : 0u;
     }
-    if (n_pairs == 0) return SPECKV_OK;
+    if (n_pairs == 0 && n_held == 0) return SPECKV_OK;
+    const bool held = n_held != 0 || n_in != 0;                                 // (a held-in row of a write rides on its pair's wave)
+    const bool ex = held || c.elem != SPECKV_SLOT_ELEM_FP16;
     if (is_capturing(s)) {
         SPECKV_ERR("%s cannot be captured into a HIP graph (its descriptors are staged per call)", entry);
         return SPECKV_ERR_INVAL;
     }
     const uint64_t n_each = 2ull * c.n_layers, first_region = 2ull * c.layer_begin;
-    if (n_pairs * n_each > (1ull << 31)) return SPECKV_ERR_INVAL;
+    if ((n_pairs + (held ? c.n_spans : 0u)) * n_each > (1ull << 31)) return SPECKV_ERR_INVAL;
     std::vector<Allocation*> as(c.n_spans);
     const auto check = [&]() -> int {
         for (uint32_t i = 0; i < c.n_spans; ++i) {
@@ -47,8 +68,8 @@ int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
             if (a->scheme != find(c.handles[0])->scheme) return SPECKV_ERR_INVAL;
             const uint64_t end = c.first_tokens[i] + c.n_tokens[i];
             if (end > 2 * c.page_step) return SPECKV_ERR_GENERAL;                // the span leaves its (layer, kind) region
-            if (c.n_tokens[i]) {
-                const uint64_t last = (first_region + n_each - 1) * c.page_step + (end + 1) / 2 - 1;    // the last page named
+            if (p1[i] > c.first_tokens[i] / 2) {
+                const uint64_t last = (first_region + n_each - 1) * c.page_step + p1[i] - 1;            // the last page named
                 if (c.page_step > a->n_pages || last >= a->n_pages) return SPECKV_ERR_GENERAL;
                 if (write && a->size_bytes % kPageSize && last == a->n_pages - 1) return SPECKV_ERR_INVAL;
             }
@@ -57,26 +78,25 @@ int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
         return SPECKV_OK;
     };
     RC_TRY(check());
-    // the pages of span i: (first_region + j) * page_step + p for j < n_each, p in [first / 2, (first + n + 1) / 2)
+    // the pages of span i: (first_region + j) * page_step + p for j < n_each, p in [first / 2, p1[i])
     const auto each_page = [&](auto&& f) {
         for (uint32_t i = 0; i < c.n_spans; ++i) {
-            if (!c.n_tokens[i]) continue;
-            const uint64_t p0 = c.first_tokens[i] / 2, p1 = (c.first_tokens[i] + c.n_tokens[i] + 1) / 2;
+            const uint64_t p0 = c.first_tokens[i] / 2;
             for (uint64_t j = 0; j < n_each; ++j)
-                for (uint64_t p = p0; p < p1; ++p) f(as[i], (first_region + j) * c.page_step + p);
+                for (uint64_t p = p0; p < p1[i]; ++p) f(as[i], (first_region + j) * c.page_step + p);
         }
     };
     if (write) {
         std::vector<uint32_t> order;                                             // the spans of one allocation must not share a page
-        for (uint32_t i = 0; i < c.n_spans; ++i) if (c.n_tokens[i]) order.push_back(i);
+        for (uint32_t i = 0; i < c.n_spans; ++i) if (p1[i] > c.first_tokens[i] / 2) order.push_back(i);    // (the pair through a held-in row is one)
         std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
             return c.handles[x] != c.handles[y] ? c.handles[x] < c.handles[y] : c.first_tokens[x] < c.first_tokens[y]; });
         for (size_t k = 1; k < order.size(); ++k) {
             const uint32_t x = order[k - 1], y = order[k];
-            if (c.handles[x] == c.handles[y] && c.first_tokens[y] < c.first_tokens[x] + c.n_tokens[x]) return SPECKV_ERR_INVAL;
+            if (c.handles[x] == c.handles[y] && c.first_tokens[y] / 2 < p1[x]) return SPECKV_ERR_INVAL;
         }
         for (uint32_t i = 0; i < c.n_spans; ++i)
-            if (c.n_tokens[i] && as[i]->packed) {                                // sealed destinations go back into slots first
+            if (p1[i] > c.first_tokens[i] / 2 && as[i]->packed) {                // sealed destinations go back into slots first
                 DeviceScope scope(device_);
                 RC_TRY(unpack(as[i]));
                 RC_TRY(check());
@@ -99,7 +119,8 @@ int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
         }
     }
     const size_t span_bytes = static_cast<size_t>(c.n_spans) * sizeof(SlotSpan);  // (a multiple of 8: the cache bases follow)
-    const size_t bytes = span_bytes + static_cast<size_t>(c.n_layers) * sizeof(uint64_t);
+    const size_t base_bytes = static_cast<size_t>(c.n_layers) * sizeof(uint64_t);
+    const size_t bytes = span_bytes + base_bytes + (held ? static_cast<size_t>(c.n_spans) * sizeof(SlotHeld) : 0);   // (the held rows last)
     int slot = 0;
     void *staged = nullptr, *d_slot = nullptr;
     RC_TRY(descriptor_slot(bytes, &slot, &staged, &d_slot));     // may release the ABI lock: every span is judged again
@@ -107,14 +128,22 @@ int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
     uint32_t prefix = 0;
     for (uint32_t i = 0; i < c.n_spans; ++i) {
         const Allocation* a = as[i];
-        if (write && c.n_tokens[i] && a->packed) return SPECKV_ERR_GENERAL;      // sealed again by another caller meanwhile
+        if (write && p1[i] > c.first_tokens[i] / 2 && a->packed) return SPECKV_ERR_GENERAL;      // sealed again by another caller meanwhile
         const uint32_t first = static_cast<uint32_t>(c.first_tokens[i]), n = static_cast<uint32_t>(c.n_tokens[i]);
         static_cast<SlotSpan*>(staged)[i] = SlotSpan{write ? a->d_entries : nullptr, write ? a->d_scale_tab : nullptr, a->region_pages,
                                                      a->scale_run, a->row, first, n, prefix, c.slot_begins[i]};
-        if (n) prefix += (first + n + 1u) / 2u - first / 2u;
+        prefix += static_cast<uint32_t>(p1[i]) - first / 2u;
     }
     uint64_t* bases = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(staged) + span_bytes);
     for (uint32_t l = 0; l < c.n_layers; ++l) bases[l] = reinterpret_cast<uint64_t>(c.d_caches[l]);
+    if (held) {
+        SlotHeld* h = reinterpret_cast<SlotHeld*>(static_cast<uint8_t*>(staged) + span_bytes + base_bytes);
+        for (uint32_t i = 0; i < c.n_spans; ++i)
+            for (int k = 0; k < 2; ++k) {
+                h[i].in[k] = c.held_in ? reinterpret_cast<uint64_t>(c.held_in[2 * i + k]) : 0;
+                h[i].out[k] = c.held_out ? reinterpret_cast<uint64_t>(c.held_out[2 * i + k]) : 0;
+            }
+    }
     if (!write)
         for (auto& w : write_evs_)
             if (w.s != s) HIP_TRY(hipStreamWaitEvent(s, w.ev, 0));
@@ -135,7 +164,17 @@ int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
     sa.kind_fast = tuning().slots_kind_fast != 0;
     sa.scheme = as[0]->scheme;
     sa.quant_mode = quant_mode_;
-    HIP_TRY(write ? launch_compress_slots(sa, s) : launch_read_slots(sa, s));
+    if (ex) {
+        SlotExArgs x{};
+        x.a = sa;
+        x.held = held ? reinterpret_cast<const SlotHeld*>(static_cast<const uint8_t*>(d_slot) + span_bytes + base_bytes) : nullptr;
+        x.held_stride = c.held_stride;
+        x.n_moves = n_held ? c.n_spans * 2u * c.n_layers : 0u;
+        x.bf16 = c.elem == SPECKV_SLOT_ELEM_BF16;
+        HIP_TRY(write ? launch_compress_slots_ex(x, s) : launch_read_slots_ex(x, s));
+    } else {
+        HIP_TRY(write ? launch_compress_slots(sa, s) : launch_read_slots(sa, s));
+    }
     for (uint32_t i = 0; i < c.n_spans; ++i) note_use(as[i], s);                // the kernel is queued: speckv_free waits for this stream
     const uint64_t n = n_pairs * n_each;
     if (write) {                                                                // host mirror first, then the orderings

@@ -169,12 +169,46 @@ __device__ __forceinline__ void put16(const RowSink& d, uint32_t p0, uint4 v)
     uint8_t* r = d.row(p0);
     if (r) st16(r + 2ull * (p0 & 1023u), v);
 }
+// The same two rows where the caller's cache holds bf16 (k_read_slots_ex): a decoder still hands over the fp16 bits that
+// speckv_ext_fetch_range writes, and the sink rounds THOSE once to bf16 (nearest even; fp16 -> fp32 is exact, so the one rounding
+// is fp32 -> bf16 of the fp16 value, never of the decoder's fp32 intermediate) -- eight elements in registers, then the same one
+// 16-byte store per lane, 1 KiB per instruction.  A NaN stays a NaN.
+struct RowSinkBf16 {
+    uint8_t* even;
+    uint8_t* odd;
+    __device__ __forceinline__ uint8_t* row(uint32_t p) const { return p < 1024u ? even : odd; }
+};
+template <class DST> struct is_row_sink { static constexpr bool value = false; };
+template <> struct is_row_sink<RowSink> { static constexpr bool value = true; };
+template <> struct is_row_sink<RowSinkBf16> { static constexpr bool value = true; };
+__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b)                        // one packed conversion for the two
+{
+    typedef float pair_f32 __attribute__((ext_vector_type(2)));
+    typedef __bf16 pair_bf16 __attribute__((ext_vector_type(2)));
+    const pair_f32 f = {a, b};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, pair_bf16));
+}
+__device__ __forceinline__ uint32_t half2_to_bf16x2(uint32_t w) { return pack_bf16x2(half_bits_to_float(w & 0xFFFFu), half_bits_to_float(w >> 16)); }
+// ... and backwards, a bf16 row read by the encoder or moved into a held fp16 row: the exact value rounded once to fp16 (nearest
+// even; overflow gives inf, a NaN stays a NaN, fp16 subnormals are kept and what is smaller rounds to +-0) -- pack_half2's rounding
+__device__ __forceinline__ uint32_t bf16x2_to_half2(uint32_t w)
+{
+    return pack_half2(__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u));
+}
+__device__ __forceinline__ uint4 half8_to_bf16(uint4 v) { return make_uint4(half2_to_bf16x2(v.x), half2_to_bf16x2(v.y), half2_to_bf16x2(v.z), half2_to_bf16x2(v.w)); }
+__device__ __forceinline__ uint4 bf16_to_half8(uint4 v) { return make_uint4(bf16x2_to_half2(v.x), bf16x2_to_half2(v.y), bf16x2_to_half2(v.z), bf16x2_to_half2(v.w)); }
+__device__ __forceinline__ bool wants(const RowSinkBf16& d, uint32_t p0) { return d.row(p0) != nullptr; }
+__device__ __forceinline__ void put16(const RowSinkBf16& d, uint32_t p0, uint4 v)
+{
+    uint8_t* r = d.row(p0);
+    if (r) st16(r + 2ull * (p0 & 1023u), half8_to_bf16(v));
+}
 template <bool F32, class DST>
 __device__ __forceinline__ void store8(const DST& dst, uint32_t p0, const float (&y)[8])
 {
     if constexpr (F32) {
         store8_f32(dst, p0, y);
-    } else if constexpr (!std::is_same<DST, RowSink>::value) {         // (the address in front of the conversions, as it always stood)
+    } else if constexpr (!is_row_sink<DST>::value) {                   // (the address in front of the conversions, as it always stood)
         st16(dst + 2ull * p0, make_uint4(pack_half2(y[0], y[1]), pack_half2(y[2], y[3]),
                                          pack_half2(y[4], y[5]), pack_half2(y[6], y[7])));
     } else {
@@ -445,6 +479,14 @@ __device__ __forceinline__ void store_elem(const RowSink& d, uint32_t p, float y
     uint8_t* r = d.row(p);
     if (r) store_elem<false>(r, p & 1023u, y);
 }
+template <bool F32>
+__device__ __forceinline__ void store_elem(const RowSinkBf16& d, uint32_t p, float y)
+{
+    static_assert(!F32, "position rows are 16-bit");
+    uint8_t* r = d.row(p);
+    float a = y, z = 0.0f;
+    if (r) gstore<uint16_t>(r + 2ull * (p & 1023u), static_cast<uint16_t>(half2_to_bf16x2(pack_half2(a, z) & 0xFFFFu) & 0xFFFFu));
+}
 template <int MODE, bool F32, class DST>
 __device__ __forceinline__ void decode_rle_general_to(const uint8_t* __restrict__ rec, uint32_t len,
                                                       float scale, typename dst_arg<DST>::type dst, uint32_t lane)
@@ -528,7 +570,7 @@ __device__ __forceinline__ void decode_fp16(const uint8_t* __restrict__ rec, uin
                 uint32_t hi = (2u * (p0 + 2 * t + 1) + 1u < len) ? (words[t] & 0xFFFF0000u) : 0u;
                 o[t] = lo | hi;
             }
-            if constexpr (!std::is_same<DST, RowSink>::value) st16(dst + 2ull * p0, make_uint4(o[0], o[1], o[2], o[3]));
+            if constexpr (!is_row_sink<DST>::value) st16(dst + 2ull * p0, make_uint4(o[0], o[1], o[2], o[3]));
             else put16(dst, p0, make_uint4(o[0], o[1], o[2], o[3]));
         } else {
             const uint32_t words[4] = {w.x, w.y, w.z, w.w};
@@ -988,6 +1030,28 @@ struct SrcPair {
     __device__ __forceinline__ const uint8_t* chunk(int j, uint32_t lane) const { return (j < 2 ? lo : hi) + 2ull * (512u * (j & 1) + 8u * lane); }
     __device__ __forceinline__ const uint8_t* elem(uint32_t e) const { return e < 1024u ? lo + 2ull * e : hi + 2ull * (e - 1024u); }
 };
+// How the encoder reads a source: the fp16 bits of a lane's chunk (the fast paths) or of one element (the out-of-line paths).
+template <class SRC> __device__ __forceinline__ uint4 src_ld16(const SRC& src, int j, uint32_t lane) { return enc_ld16(src.chunk(j, lane)); }
+template <class SRC> __device__ __forceinline__ uint32_t src_half(const SRC& src, uint32_t e) { return gload<uint16_t>(src.elem(e)); }
+// SrcPair whose rows each say what they hold (k_compress_slots_ex): fp16, or bf16 that becomes fp16 by bf16x2_to_half2's one
+// rounding as it is loaded -- on both access paths, so a bf16 row with inf / NaN in it is encoded as row.to(fp16) would be.  A pair
+// made of a held fp16 row and a row of a bf16 cache is mixed; the type of a row is the same for all lanes of the wave.
+struct SrcPairMixed {
+    const uint8_t* lo;
+    const uint8_t* hi;
+    bool lo_bf16, hi_bf16;
+};
+__device__ __forceinline__ uint4 src_ld16(const SrcPairMixed& src, int j, uint32_t lane)
+{
+    const uint4 v = enc_ld16((j < 2 ? src.lo : src.hi) + 2ull * (512u * (j & 1) + 8u * lane));
+    return (j < 2 ? src.lo_bf16 : src.hi_bf16) ? bf16_to_half8(v) : v;
+}
+__device__ __forceinline__ uint32_t src_half(const SrcPairMixed& src, uint32_t e)
+{
+    const bool low = e < 1024u;
+    const uint32_t b = gload<uint16_t>(low ? src.lo + 2ull * e : src.hi + 2ull * (e - 1024u));
+    return (low ? src.lo_bf16 : src.hi_bf16) ? (bf16x2_to_half2(b) & 0xFFFFu) : b;
+}
 
 // General path (long stretches: zeros, constants; blocks with inf / NaN): one element per lane per step, rolled,
 // quantised with the exact scalar form straight from the source; stretch starts by max-scan, a run starts every 255
@@ -1000,7 +1064,7 @@ __device__ __forceinline__ uint32_t encode_rle_general_from(const SRC src, float
 #pragma unroll 1
     for (uint32_t step = 0; step < kBlockElems / 64u; ++step) {
         const uint32_t p = 64u * step + lane;
-        const uint32_t qv = quantize<MODE>(half_bits_to_float(gload<uint16_t>(src.elem(p))), scale);
+        const uint32_t qv = quantize<MODE>(half_bits_to_float(src_half(src, p)), scale);
         const uint32_t prevq = wave_shr1(qv, qtail);
         qtail = lane63(qv);
         const uint32_t d = (qv - prevq) & 0xFFu;
@@ -1036,6 +1100,8 @@ template <int MODE>
 __device__ __forceinline__ uint32_t encode_rle_general(const SrcRun src, float scale, uint8_t* wl, uint32_t lane) { return encode_rle_general<MODE>(src.p, scale, wl, lane); }
 template <int MODE>
 __device__ __forceinline__ uint32_t encode_rle_general(const SrcPair src, float scale, uint8_t* wl, uint32_t lane) { return encode_rle_general_from<MODE>(src, scale, wl, lane); }
+template <int MODE>
+__device__ __forceinline__ uint32_t encode_rle_general(const SrcPairMixed src, float scale, uint8_t* wl, uint32_t lane) { return encode_rle_general_from<MODE>(src, scale, wl, lane); }
 
 // the reference's own rule for blocks that hold inf / NaN: a NaN never wins the '>' compare (cache_engine.cpp:176-180).
 // Rare, out of line, and fed from memory again (a register array passed by reference would move to scratch).
@@ -1045,7 +1111,7 @@ __device__ __forceinline__ float absmax_with_nonfinite_from(const SRC src, uint3
     float mx = 0.0f;
 #pragma unroll 1
     for (uint32_t p = lane; p < kBlockElems; p += 64u)
-        mx = __builtin_fmaxf(mx, fabsf(half_bits_to_float(gload<uint16_t>(src.elem(p)))));
+        mx = __builtin_fmaxf(mx, fabsf(half_bits_to_float(src_half(src, p))));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float other = __shfl_xor(mx, o);
@@ -1056,6 +1122,7 @@ __device__ __forceinline__ float absmax_with_nonfinite_from(const SRC src, uint3
 __device__ __noinline__ float absmax_with_nonfinite(const uint8_t* __restrict__ src, uint32_t lane) { return absmax_with_nonfinite_from(SrcRun{src}, lane); }
 __device__ __forceinline__ float absmax_with_nonfinite(const SrcRun src, uint32_t lane) { return absmax_with_nonfinite(src.p, lane); }
 __device__ __forceinline__ float absmax_with_nonfinite(const SrcPair src, uint32_t lane) { return absmax_with_nonfinite_from(src, lane); }
+__device__ __forceinline__ float absmax_with_nonfinite(const SrcPairMixed src, uint32_t lane) { return absmax_with_nonfinite_from(src, lane); }
 
 // ===================================================================
 // encode  (cache_engine.cpp:40-82,172-239)
@@ -1091,7 +1158,7 @@ __device__ __forceinline__ void compress_block(const EncTarget& t, const uint64_
     uint4 raw[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-        raw[j] = enc_ld16(src.chunk(j, lane));
+        raw[j] = src_ld16(src, j, lane);
 
     if (SCHEME == kFp16) {
 #pragma unroll
@@ -1352,7 +1419,7 @@ __device__ __forceinline__ void compress_block(const EncTarget& t, const uint64_
                 if (finite) {                                        // long stretches: the fast path's SPLIT form, from the source again
                     uint4 again[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) again[j] = enc_ld16(src.chunk(j, lane));
+                    for (int j = 0; j < 4; ++j) again[j] = src_ld16(src, j, lane);
                     nruns = encode_rle_fast<MODE, true>(again, scale, rcp, wl, lane);
                 } else {
                     nruns = encode_rle_general<MODE>(src, scale, wl, lane);
@@ -1976,6 +2043,187 @@ hipError_t launch_read_slots(const SlotArgs& a, hipStream_t s)
     case kInt4G32: return launch_dec_slots<kInt4G32, kRefExact>(a, grid, s);         // the quantiser mode does not apply
     case kFp8E4m3: return launch_dec_slots<kFp8E4m3, kRefExact>(a, grid, s);
     case kMxFp4: return launch_dec_slots<kMxFp4, kRefExact>(a, grid, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// The two kernels above for caches that hold bf16 and for spans with held rows (SlotExArgs, kernels.hpp).  Waves [0, n_pairs *
+// 2 * n_layers) are the pages of k_read_slots / k_compress_slots, found by the same slot_work; behind them wave m = span * 2 *
+// n_layers + j moves the one position of span `span` that travels between a held row and a slot, for (layer, kind) j: 2048 bytes,
+// two 16-byte loads and stores per lane, converted in registers where the cache holds bf16, no record touched.  Which way a wave
+// goes depends on blockIdx and the wave number alone.  They stand behind everything else of the translation unit, and add no
+// out-of-line device function, so that no kernel in front of them moves (the note at launch_compress_pairs).
+namespace {
+enum { kMoveCopy = 0, kMoveToBf16 = 1, kMoveFromBf16 = 2 };
+__device__ __forceinline__ void move_row(const uint8_t* src, uint8_t* dst, uint32_t lane, int conv)     // src == nullptr: zeros
+{
+#pragma unroll
+    for (uint32_t h = 0; h < 2u; ++h) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (src) v = ld16(src + 1024u * h + 16u * lane);
+        if (conv == kMoveToBf16) v = half8_to_bf16(v);
+        else if (conv == kMoveFromBf16) v = bf16_to_half8(v);
+        st16(dst + 1024u * h + 16u * lane, v);
+    }
+}
+// move wave m's work: false = it has none.  *held_row = the held row of its span and (layer, kind), *cache_row = the row of the
+// span's last position in the cache, nullptr where its slot names no row
+__device__ __forceinline__ bool move_work(const SlotExArgs& x, uint64_t m, bool out, uint8_t** held_row, uint8_t** cache_row)
+{
+    if (m >= x.n_moves) return false;
+    const uint32_t per = 2u * x.a.n_layers;
+    const uint32_t sp = static_cast<uint32_t>(m / per), j = static_cast<uint32_t>(m - static_cast<uint64_t>(sp) * per);
+    const uint64_t h = out ? x.held[sp].out[j & 1u] : x.held[sp].in[j & 1u];
+    if (!h) return false;
+    const SlotSpan* g = x.a.spans + sp;
+    if (g->n_tokens == 0) return false;
+    const int64_t s = x.a.slots[g->slot_begin + g->n_tokens - 1u];
+    *held_row = reinterpret_cast<uint8_t*>(h) + static_cast<uint64_t>(j >> 1) * x.held_stride;
+    *cache_row = (s >= 0 && s < static_cast<int64_t>(x.a.n_slots))
+        ? reinterpret_cast<uint8_t*>(x.a.caches[j >> 1]) + static_cast<uint64_t>(j & 1u) * x.a.kind_stride + static_cast<uint64_t>(s) * 2048u : nullptr;
+    return true;
+}
+
+template <int SCHEME, int MODE, bool BF16>
+__global__ __launch_bounds__(kThreads) void k_read_slots_ex(SlotExArgs x)
+{
+    typedef typename std::conditional<BF16, RowSinkBf16, RowSink>::type Sink;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[SCHEME == kInt8DeltaRle ? kWaves * kDecLdsWords : 4];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
+    const uint64_t n_dec = static_cast<uint64_t>(x.a.n_pairs) * 2u * x.a.n_layers;
+    if (i >= n_dec) {                                                // a held row into the slot of the span's last position
+        uint8_t *held_row = nullptr, *cache_row = nullptr;
+        if (move_work(x, i - n_dec, false, &held_row, &cache_row) && cache_row) move_row(held_row, cache_row, lane, BF16 ? kMoveToBf16 : kMoveCopy);
+        return;
+    }
+    SlotWork w;
+    if (!slot_work(x.a, wave, &w)) return;
+    uint8_t* const base = const_cast<uint8_t*>(w.base);
+    const Sink dst{w.slot[0] >= 0 ? base + static_cast<uint64_t>(w.slot[0]) * 2048u : nullptr,
+                   w.slot[1] >= 0 ? base + static_cast<uint64_t>(w.slot[1]) * 2048u : nullptr};
+    if (!dst.even && !dst.odd) return;
+    const PageEntry* entries = x.a.tab[w.g->table_row].entries;
+    PageEntry e{0, 0, 1.0f};
+    if (entries) e = entries[(2ull * x.a.layer_begin + w.j) * x.a.page_step + w.pair];
+    const uint8_t* rec = reinterpret_cast<const uint8_t*>(e.pool_addr);
+    uint32_t len = e.rec_bytes;
+    if (SCHEME == kInt8DeltaRle) {
+        if (len > 2u * kBlockElems) len = 2u * kBlockElems;
+        uint32_t* region = lds + wave * kDecLdsWords;
+        if (!decode_rle_fast<MODE, false, false, Sink>(rec, len, e.scale, dst, reinterpret_cast<uint8_t*>(region), lane, true))
+            decode_rle_general_to<MODE, false, Sink>(rec, len, e.scale, dst, lane);
+    } else if (SCHEME == kInt8) {
+        decode_int8<MODE, false, Sink>(rec, len > kBlockElems ? kBlockElems : len, e.scale, dst, lane);
+    } else if (SCHEME == kInt4G32) {
+        decode_int4<false, Sink>(rec, len, dst, lane);
+    } else if (SCHEME == kMxFp4) {
+        decode_mx4<false, Sink>(rec, rec + __float_as_uint(e.scale), len, dst, lane);
+    } else if (SCHEME == kFp8E4m3) {
+        decode_fp8<false, Sink>(rec, len > kBlockElems ? kBlockElems : len, e.scale, dst, lane);
+    } else {
+        decode_fp16<false, Sink>(rec, len > 2u * kBlockElems ? 2u * kBlockElems : len, dst, lane);
+    }
+}
+
+template <int SCHEME, int MODE>
+__global__ __launch_bounds__(kThreads) void k_compress_slots_ex(SlotExArgs x)
+{
+    SPECKV_ENC_LDS(SCHEME);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint32_t uwave = __builtin_amdgcn_readfirstlane(wave);
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + uwave;
+    const uint64_t n_enc = static_cast<uint64_t>(x.a.n_pairs) * 2u * x.a.n_layers;
+    const bool bf16 = x.bf16 != 0u;
+    if (i >= n_enc) {                                                // the span's last position into its held row (no row: zeros)
+        uint8_t *held_row = nullptr, *cache_row = nullptr;
+        if (move_work(x, i - n_enc, true, &held_row, &cache_row)) move_row(cache_row, held_row, lane, bf16 ? kMoveFromBf16 : kMoveCopy);
+        return;
+    }
+    SlotWork w;
+    if (!slot_work(x.a, uwave, &w)) return;
+    SrcPairMixed src{w.slot[0] >= 0 ? w.base + static_cast<uint64_t>(w.slot[0]) * 2048u : x.a.zeros,
+                     w.slot[1] >= 0 ? w.base + static_cast<uint64_t>(w.slot[1]) * 2048u : x.a.zeros, bf16, bf16};
+    if (x.held && 2u * w.pair < w.g->first_token) {                  // the pair begins one position in front of the span: its held row
+        const uint64_t h = x.held[w.g - x.a.spans].in[w.j & 1u];
+        if (h) {
+            src.lo = reinterpret_cast<const uint8_t*>(h) + static_cast<uint64_t>(w.j >> 1) * x.held_stride;
+            src.lo_bf16 = false;
+        }
+    }
+    PageEntry* entries = w.g->entries;
+    __builtin_assume(entries != nullptr);
+    const EncTarget t{entries, w.g->scale_tab, w.g->region_pages, w.g->scale_run, nullptr, nullptr, 0, nullptr, nullptr};
+    compress_block<SCHEME, MODE>(t, (2ull * x.a.layer_begin + w.j) * x.a.page_step + w.pair, src, lds, lane, wave);
+}
+
+template <int SCHEME, int MODE>
+hipError_t launch_dec_slots_ex(const SlotExArgs& x, uint32_t grid, hipStream_t s)
+{
+    if (x.bf16) hipLaunchKernelGGL((k_read_slots_ex<SCHEME, MODE, true>), dim3(grid), dim3(kThreads), 0, s, x);
+    else hipLaunchKernelGGL((k_read_slots_ex<SCHEME, MODE, false>), dim3(grid), dim3(kThreads), 0, s, x);
+    return hipGetLastError();
+}
+template <int SCHEME>
+hipError_t launch_dec_slots_ex_mode(const SlotExArgs& x, uint32_t grid, hipStream_t s)
+{
+    return x.a.quant_mode == kIntent ? launch_dec_slots_ex<SCHEME, kIntent>(x, grid, s) : launch_dec_slots_ex<SCHEME, kRefExact>(x, grid, s);
+}
+template <int SCHEME, int MODE>
+hipError_t launch_enc_slots_ex(const SlotExArgs& x, uint32_t grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_compress_slots_ex<SCHEME, MODE>), dim3(grid), dim3(kThreads), 0, s, x);
+    return hipGetLastError();
+}
+template <int SCHEME>
+hipError_t launch_enc_slots_ex_mode(const SlotExArgs& x, uint32_t grid, hipStream_t s)
+{
+    return x.a.quant_mode == kIntent ? launch_enc_slots_ex<SCHEME, kIntent>(x, grid, s) : launch_enc_slots_ex<SCHEME, kRefExact>(x, grid, s);
+}
+// what both launchers ask of a SlotExArgs; *grid = one page or one moved row per wave, 0 = nothing to do
+bool slot_ex_args_ok(const SlotExArgs& x, uint32_t* grid)
+{
+    const SlotArgs& a = x.a;
+    const uint64_t waves = static_cast<uint64_t>(a.n_pairs) * 2u * a.n_layers + x.n_moves;
+    if (!a.spans || !a.caches || !a.slots || a.n_spans == 0 || a.page_step == 0 || a.kind_stride % 16u || x.held_stride % 16u) return false;
+    if ((x.n_moves != 0u && (!x.held || x.n_moves != static_cast<uint64_t>(a.n_spans) * 2u * a.n_layers)) || waves > (1ull << 31)) return false;
+    *grid = static_cast<uint32_t>((waves + kWaves - 1) / kWaves);
+    return true;
+}
+} // namespace
+
+hipError_t launch_compress_slots_ex(const SlotExArgs& x, hipStream_t s)
+{
+    if (x.a.n_layers == 0) return hipSuccess;
+    uint32_t grid = 0;
+    if (!slot_ex_args_ok(x, &grid) || !x.a.zeros) return hipErrorInvalidValue;
+    if (grid == 0) return hipSuccess;
+    switch (x.a.scheme) {
+    case kFp16: return launch_enc_slots_ex_mode<kFp16>(x, grid, s);
+    case kInt8: return launch_enc_slots_ex_mode<kInt8>(x, grid, s);
+    case kInt8DeltaRle: return launch_enc_slots_ex_mode<kInt8DeltaRle>(x, grid, s);
+    case kInt4G32: return launch_enc_slots_ex<kInt4G32, kRefExact>(x, grid, s);       // the quantiser mode does not apply
+    case kFp8E4m3: return launch_enc_slots_ex<kFp8E4m3, kRefExact>(x, grid, s);
+    case kMxFp4: return launch_enc_slots_ex<kMxFp4, kRefExact>(x, grid, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_read_slots_ex(const SlotExArgs& x, hipStream_t s)
+{
+    if (x.a.n_layers == 0) return hipSuccess;
+    uint32_t grid = 0;
+    if (!slot_ex_args_ok(x, &grid) || !x.a.tab) return hipErrorInvalidValue;
+    if (grid == 0) return hipSuccess;
+    switch (x.a.scheme) {
+    case kFp16: return launch_dec_slots_ex<kFp16, kRefExact>(x, grid, s);             // (a copy or a conversion: no quantiser)
+    case kInt8: return launch_dec_slots_ex_mode<kInt8>(x, grid, s);
+    case kInt8DeltaRle: return launch_dec_slots_ex_mode<kInt8DeltaRle>(x, grid, s);
+    case kInt4G32: return launch_dec_slots_ex<kInt4G32, kRefExact>(x, grid, s);       // the quantiser mode does not apply
+    case kFp8E4m3: return launch_dec_slots_ex<kFp8E4m3, kRefExact>(x, grid, s);
+    case kMxFp4: return launch_dec_slots_ex<kMxFp4, kRefExact>(x, grid, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -154,6 +154,26 @@ struct SlotArgs {
     int              scheme;
     int              quant_mode;
 };
+// The same launch with bf16 caches and held rows (k_read_slots_ex / k_compress_slots_ex).  A held row is one position that lives
+// outside both the pool and the caches, always fp16: the row of (layer layer_begin + l, kind) at in[kind] / out[kind] +
+// l * held_stride.  SlotArgs::spans then counts DECODED / ENCODED pairs only --
+//   read:   in[kind] set: the span's last position (even) is copied from the held row into its slot, its page is not read; the
+//           span's pairs are [first / 2, (first + n - 1) / 2)
+//   write:  in[kind] set: position first_token - 1 (first_token odd) comes from the held row; out[kind] set: the last position
+//           (first_token + n_tokens odd) is not encoded but written to the held row; the pairs are [first / 2, (first + n) / 2)
+// -- and the positions that only move between a held row and a slot are 2 * n_layers further waves per span behind the pair
+// waves (n_moves of them; those of a span without such a position leave at once).
+struct SlotHeld {
+    uint64_t in[2];                   // K, V; 0 = none
+    uint64_t out[2];
+};
+struct SlotExArgs {
+    SlotArgs         a;
+    const SlotHeld*  held;            // device array [n_spans] in the same staged slot; nullptr = no held rows in this call
+    uint64_t         held_stride;     // bytes between the layers of a held row block, a multiple of 16
+    uint32_t         n_moves;         // 0 or n_spans * 2 * n_layers
+    uint32_t         bf16;            // the caches' rows hold bf16
+};
 
 // One (source, destination) pair of a record-copy launch (CopyArgs::pairs; copy_records.hip): the stored records of pages
 // [run_firsts[r], run_firsts[r] + n_pages), every run r of the launch, go from the allocation in table row `src_row` to the same
@@ -384,6 +404,8 @@ hipError_t launch_read_pairs(const ReadPairArgs& a, hipStream_t s);
 // the paged-cache forms of both: n_pairs * 2 * n_layers blocks in one launch, rows addressed by a device slot mapping
 hipError_t launch_compress_slots(const SlotArgs& a, hipStream_t s);
 hipError_t launch_read_slots(const SlotArgs& a, hipStream_t s);
+hipError_t launch_compress_slots_ex(const SlotExArgs& a, hipStream_t s);
+hipError_t launch_read_slots_ex(const SlotExArgs& a, hipStream_t s);
 
 // FPGACacheEngine::compress / ::decompress over a tensor of any length (tensor_codec.hip): one scale, one delta chain and
 // one run-length stream across the whole tensor.  d_rle: 16-byte aligned, room for 2n bytes rounded up to 16; d_ws:

@@ -39,7 +39,9 @@ paged-attention layer would talk to for a BATCH of requests:
                                and folds it in (``attend_chunk_shared`` for a member's own chunk; ``shared_groups``)
   load_paged / store_paged     the route in and out of the pool for vLLM-style paged caches (one tensor per layer, rows addressed by a
                                slot mapping on the device): spans of positions of a batch of requests decoded into their slots, or encoded
-                               from them, by one launch each way (``speckv_ext_read_slots`` / ``speckv_ext_write_slots``; ``paged_spans``)
+                               from them, by one launch each way (``speckv_ext_read_slots`` / ``speckv_ext_write_slots``; ``paged_spans``);
+                               ``fused=True``: bf16 caches and odd lengths in the same launch, the tail as a held row
+                               (``speckv_ext_read_slots_ex`` / ``speckv_ext_write_slots_ex``)
 
 Only plain device pointers cross into the library; torch is used for device buffers and the tail fold.
 """
@@ -416,15 +418,17 @@ class SpeckvKVConnector:
             prefix += n
         return out
 
-    def _paged_geometry(self, caches):
+    def _paged_geometry(self, caches, bf16=False):
         """(slots per cache, bytes between the K and the V plane) if the one-launch route can address `caches` -- per layer a
-        [2, blocks, block_size, heads, dim] fp16 tensor whose slots are 2048-byte rows one after the other -- else None."""
+        [2, blocks, block_size, heads, dim] fp16 tensor whose slots are 2048-byte rows one after the other -- else None.
+        bf16=True (the fused route): the caches may all be bfloat16 instead, and the element type (SLOT_ELEM_*) comes third."""
         import torch
         if self._kscale is not None or len(caches) != self.L:
             return None
         geo = None
+        dtype = caches[0].dtype if bf16 and len(caches) and caches[0].dtype == torch.bfloat16 else torch.float16
         for c in caches:
-            if c.dtype != torch.float16 or c.dim() != 5 or c.shape[0] != 2 or c.shape[3] * c.shape[4] * 2 != 2048:
+            if c.dtype != dtype or c.dim() != 5 or c.shape[0] != 2 or c.shape[3] * c.shape[4] * 2 != 2048:
                 return None
             if tuple(c.stride()[2:]) != (c.shape[3] * c.shape[4], c.shape[4], 1) or c.stride(1) != c.shape[2] * 1024:
                 return None
@@ -434,7 +438,24 @@ class SpeckvKVConnector:
             if geo is not None and g != geo:
                 return None
             geo = g
+        if bf16 and geo is not None:
+            return geo + (1 if dtype == torch.bfloat16 else 0,)
         return geo
+
+    def _held_tail(self, r):
+        """(K address, V address) of request r's tail for a fused paged call -- fp16, 16-byte aligned, a layer every H * D elements;
+        a tail that does not lie like that (never one this class made) is laid out again first."""
+        k, v, row = r._tail
+        ok = lambda t: t.is_contiguous() and t.data_ptr() % 16 == 0
+        if row is not None:
+            if ok(k) and ok(v):                                               # a row of the batched tails: no view is made
+                step = k.stride(0) * 2
+                return k.data_ptr() + row * step, v.data_ptr() + row * step, (k, v)
+            k, v = k[row], v[row]
+        if not (ok(k) and ok(v)):
+            k, v = k.contiguous().clone(), v.contiguous().clone()
+            r.set_tail(k, v)
+        return k.data_ptr(), v.data_ptr(), (k, v)
 
     def _paged_args(self, req_ids, counts, slot_mapping, caches):
         import torch
@@ -453,15 +474,18 @@ class SpeckvKVConnector:
             at += c
         return reqs, counts, begins
 
-    def load_paged(self, req_ids: Sequence[int], firsts: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None):
+    def load_paged(self, req_ids: Sequence[int], firsts: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None, fused=False):
         """Pool -> paged caches: positions [firsts[i], firsts[i] + counts[i]) of request req_ids[i] go into the slots
         slot_mapping[b_i : b_i + counts[i]] (b_i = the counts in front: ONE int64 device tensor for the call, the spans concatenated) of
         `caches`, the per-layer [2, blocks, block_size, 8, 128] fp16 tensors.  ONE speckv_ext_read_slots call decodes every stored row
         of every layer where its slot is; a span that reaches a request's odd last position gets that row from the held tail by a
         torch copy, as kv_rows does.  A slot < 0 or beyond the cache is skipped.
         Fall-back to the row route (kv_rows + index_copy_ per request, layer and kind) when a K pre-scale is set, a cache is not
-        fp16, not contiguous in its last three dimensions, or does not have 2048-byte rows one block after the other (bf16 caches are
-        out of scope: the pool moves raw fp16 bits)."""
+        fp16, not contiguous in its last three dimensions, or does not have 2048-byte rows one block after the other (without fused=True
+        that includes bf16 caches).
+        fused=True: bf16 caches of that geometry take the one-launch route as well (the decoded fp16 value rounded once to bf16:
+        kv_rows(...).to(bfloat16)), and the tail is handed to the launch as a held row: exactly ONE speckv_ext_read_slots_ex call,
+        no torch copy per request.  The K pre-scale, other dtypes and other strides still go the row route."""
         import numpy as np
         import torch
         reqs, counts, begins = self._paged_args(req_ids, counts, slot_mapping, caches)
@@ -471,6 +495,22 @@ class SpeckvKVConnector:
         for r, f, c in zip(reqs, firsts, counts):
             if not 0 <= f <= f + c <= r.length:
                 raise ValueError(f"rows [{f}, {f + c}) of a request with {r.length} positions")
+        geo = self._paged_geometry(caches, bf16=True) if fused else None
+        if geo is not None:
+            n_slots, kind_stride, elem = geo
+            held, any_held = np.zeros(2 * len(reqs), dtype=np.uint64), False
+            for i, (r, f, c) in enumerate(zip(reqs, firsts, counts)):
+                if c and (r.length & 1) and f + c == r.length:                # the span ends on the tail: a held row
+                    held[2 * i], held[2 * i + 1], _ = self._held_tail(r)
+                    any_held = True
+            if any(counts):
+                with self._On(self, stream) as st:
+                    self.lib.read_slots_ex(np.asarray([r.handle for r in reqs], dtype=np.uint64), np.asarray(firsts, dtype=np.uint64),
+                                           np.asarray(counts, dtype=np.uint64), np.asarray(begins, dtype=np.uint64), slot_mapping.data_ptr(),
+                                           n_slots, np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride,
+                                           self.region_pages, st.cuda_stream, elem=elem, held_in=held if any_held else None,
+                                           held_stride=self.H * self.D * 2)
+            return
         geo = self._paged_geometry(caches)
         if geo is None:
             with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
@@ -498,7 +538,7 @@ class SpeckvKVConnector:
                             cache[0].view(n_slots, self.H, self.D).index_copy_(0, at, r.tail_k[layer][None])
                             cache[1].view(n_slots, self.H, self.D).index_copy_(0, at, r.tail_v[layer][None])
 
-    def store_paged(self, req_ids: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None):
+    def store_paged(self, req_ids: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None, fused=False):
         """Paged caches -> pool: request req_ids[i], whose current length is even (an odd one raises ValueError: not built), gets
         counts[i] more positions, read from the slots slot_mapping[b_i : b_i + counts[i]] of `caches` (as load_paged).  ONE
         speckv_ext_write_slots call encodes the whole pairs of every layer straight from the caches -- no gathered copy exists, so
@@ -507,17 +547,63 @@ class SpeckvKVConnector:
         beyond the cache is stored as a row of zeros.
         Fall-back to the row route (index_select per layer, torch.stack, write_prefill per request -- for requests that are still
         empty) under the conditions load_paged names.  Returns the tensors the row route's launches read (hold them until the
-        stream has passed), an empty list on the one-launch route."""
+        stream has passed), an empty list on the one-launch route.
+        fused=True: bf16 caches of that geometry take the one-launch route too (a bf16 element rounded once to fp16, and that is
+        stored: the records of row.to(float16)), and a request of odd length is accepted: its tail goes into the launch as the held
+        row that completes its pair, a new odd last position comes back through held rows -- one [tails][layers][heads][dim] fp16
+        tensor per kind for the call, installed as the batched tails a lockstep append pairs without per-request views.  Exactly
+        ONE speckv_ext_write_slots_ex call and no torch copy per request; returns the tails the launch read.  On the row route (K
+        pre-scale, other dtypes or strides) an odd length still raises."""
         import numpy as np
         import torch
         reqs, counts, begins = self._paged_args(req_ids, counts, slot_mapping, caches)
         if len(set(req_ids)) != len(reqs):
             raise ValueError("store_paged: a request named twice")
+        geo = self._paged_geometry(caches, bf16=True) if fused else None
         for r, c in zip(reqs, counts):
-            if r.length & 1:
+            if r.length & 1 and geo is None:
                 raise ValueError("store_paged on a request of odd length")
             if r.length + c > self.T:
                 raise ValueError(f"{r.length} + {c} positions in a request built for {self.T}")
+        if geo is not None:
+            n_slots, kind_stride, elem = geo
+            n = len(reqs)
+            h_in, h_out, read, tails = np.zeros(2 * n, dtype=np.uint64), np.zeros(2 * n, dtype=np.uint64), [], []
+            first = [r.length if c else r.length & ~1 for r, c in zip(reqs, counts)]      # (an empty span names an even position)
+            for i, (r, c) in enumerate(zip(reqs, counts)):
+                if c and r.length & 1:
+                    h_in[2 * i], h_in[2 * i + 1], keep = self._held_tail(r)
+                    read += keep
+                if c and (r.length + c) & 1:
+                    tails.append(i)
+            with self._On(self, stream) as st:
+                tk = tv = None
+                if tails:
+                    with torch.cuda.stream(st):
+                        tk = torch.empty((len(tails), self.L, self.H, self.D), dtype=torch.float16, device=slot_mapping.device)
+                        tv = torch.empty_like(tk)
+                    row = tk[0].numel() * 2
+                    for j, i in enumerate(tails):
+                        h_out[2 * i], h_out[2 * i + 1] = tk.data_ptr() + j * row, tv.data_ptr() + j * row
+                if any(counts):
+                    self.lib.write_slots_ex(np.asarray([r.handle for r in reqs], dtype=np.uint64), np.asarray(first, dtype=np.uint64),
+                                            np.asarray(counts, dtype=np.uint64), np.asarray(begins, dtype=np.uint64), slot_mapping.data_ptr(),
+                                            n_slots, np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride,
+                                            self.region_pages, st.cuda_stream, elem=elem, held_in=h_in if read else None,
+                                            held_stride=self.H * self.D * 2, held_out=h_out if tails else None)
+            touched = [rid for rid, c in zip(req_ids, counts) if c]
+            for r, c in zip(reqs, counts):
+                if c:
+                    r.clear_tail()
+                    r.length += c
+            for j, i in enumerate(tails):
+                reqs[i].set_tail(tk, tv, j)
+            if tails:
+                self._tail_ids, self._tail_k, self._tail_v = tuple(req_ids[i] for i in tails), tk, tv
+            elif any(rid in self._tail_ids for rid in touched):
+                self._tail_ids, self._tail_k, self._tail_v = (), None, None
+            self._epoch += 1
+            return read
         geo = self._paged_geometry(caches)
         if geo is None:
             held = []

@@ -35,6 +35,15 @@ class DmaDesc(ctypes.Structure):
     _fields_ = [("fpga_addr", c_uint64), ("gpu_addr", c_uint64), ("bytes", c_uint32), ("flags", c_uint32)]
 
 
+SLOT_ELEM_FP16, SLOT_ELEM_BF16 = 0, 1
+
+
+class SlotRows(ctypes.Structure):
+    """speckv_ext_slot_rows_t (include/speckv_ext.h)."""
+    _fields_ = [("elem", c_uint32), ("reserved", c_uint32), ("d_held_in", c_void_p), ("d_held_out", c_void_p),
+                ("held_layer_stride_bytes", c_uint64)]
+
+
 class Stats(ctypes.Structure):
     """speckv_ext_stats_t (include/speckv_ext.h)."""
     _fields_ = [(n, c_uint64) for n in (
@@ -71,6 +80,10 @@ _EXT_SIGNATURES = {
                               c_uint64, c_void_p],
     "speckv_ext_write_slots": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint64,
                                c_uint64, c_void_p],
+    "speckv_ext_read_slots_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint64,
+                                 c_uint64, c_void_p, c_void_p],
+    "speckv_ext_write_slots_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint64,
+                                  c_uint64, c_void_p, c_void_p],
     "speckv_ext_copy_runs": [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
     "speckv_ext_attend_chunk": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                 c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
@@ -347,6 +360,35 @@ class SpeckvLib:
         even); a slot < 0 or >= n_slots is stored as a row of zeros.  Arguments as read_slots."""
         self._slots("speckv_ext_write_slots", handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride,
                     page_step, stream)
+
+    def _slots_ex(self, entry, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step,
+                  stream, elem, held_in, held_out, held_stride, reserved=0):
+        n, nl = len(handles), len(caches)
+        hs, fs, ns, bs = (as_arr(x, c_uint64, n) for x in (handles, first_tokens, n_tokens, slot_begins))
+        hin = None if held_in is None else as_arr(held_in, c_uint64, 2 * n)            # (kept alive across the call)
+        hout = None if held_out is None else as_arr(held_out, c_uint64, 2 * n)
+        at = lambda a: None if a is None else (a.value if isinstance(a, c_void_p) else ctypes.addressof(a))
+        rows = SlotRows(elem, reserved, at(hin), at(hout), held_stride)
+        self._ext(entry, hs, fs, ns, bs, n, c_void_p(d_slots), n_slots, as_arr(caches, c_uint64, nl), layer_begin, nl, kind_stride, page_step,
+                  ctypes.cast(ctypes.pointer(rows), c_void_p), c_void_p(stream))
+
+    def read_slots_ex(self, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step,
+                      stream, elem=SLOT_ELEM_FP16, held_in=None, held_stride=0, held_out=None, reserved=0):
+        """read_slots for caches whose rows hold `elem` (SLOT_ELEM_FP16 / SLOT_ELEM_BF16: the decoded fp16 value rounded once to bf16)
+        and for spans whose last, even position lives in a held fp16 row (speckv_ext_read_slots_ex): held_in = 2 * len(handles)
+        device addresses (K, V per span; 0 = none), the row of layer layer_begin + l at + l * held_stride bytes.  held_out and
+        reserved exist to be refused."""
+        self._slots_ex("speckv_ext_read_slots_ex", handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin,
+                       kind_stride, page_step, stream, elem, held_in, held_out, held_stride, reserved)
+
+    def write_slots_ex(self, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step,
+                       stream, elem=SLOT_ELEM_FP16, held_in=None, held_stride=0, held_out=None, reserved=0):
+        """write_slots for caches whose rows hold `elem` (a bf16 element is rounded once to fp16, and that is encoded) and for odd
+        edges (speckv_ext_write_slots_ex): held_in[2i + kind] = the fp16 row of position first_tokens[i] - 1 (first odd),
+        held_out[2i + kind] = where the odd last position goes as fp16 instead of being encoded (first + n odd).  Arguments as
+        read_slots_ex."""
+        self._slots_ex("speckv_ext_write_slots_ex", handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin,
+                       kind_stride, page_step, stream, elem, held_in, held_out, held_stride, reserved)
 
     def copy_runs(self, src, dst, n_pages, run_firsts, stream):
         """The stored records of pages [run_firsts[r], run_firsts[r] + n_pages[i]), every run r, copied from allocation src[i] to the same

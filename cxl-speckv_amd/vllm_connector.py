@@ -26,6 +26,8 @@ paged cache layout (vLLM v1, FlashAttention backend): one tensor per layer, ``[2
 ``paged_io=True``: a step's loads are ONE ``SpeckvKVConnector.load_paged`` call and its stores ONE ``store_paged`` call, straight
 between the pool and the registered caches (``speckv_ext_read_slots`` / ``speckv_ext_write_slots``); the default is the row route:
 a fetch and a scatter per (request, layer, kind), a gathered copy of every prompt held until its write has run.
+``paged_fused=True`` on top of it passes ``fused=True`` to both calls (``speckv_ext_read_slots_ex`` / ``speckv_ext_write_slots_ex``):
+bf16 caches take the one-launch route too, and the odd last position of a prompt moves inside the launch.
 """
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -86,7 +88,7 @@ def _cached_requests(scheduler_output):
 
 class SpeckvVllmConnector:
     def __init__(self, lib, num_layers: int, num_kv_heads: int = 8, head_dim: int = 128, block_size: int = 16,
-                 max_tokens: int = 4096, scheme: str = "fp16", paged_io: bool = False):
+                 max_tokens: int = 4096, scheme: str = "fp16", paged_io: bool = False, paged_fused: bool = False):
         # worker role: the pool.  lib=None builds a scheduler-role object (no GPU, no library)
         self.conn = None if lib is None else SpeckvKVConnector(lib, num_layers=num_layers, num_kv_heads=num_kv_heads, head_dim=head_dim,
                                                                 max_tokens=max_tokens, scheme=scheme)
@@ -94,6 +96,9 @@ class SpeckvVllmConnector:
         # paged_io: a step's loads are ONE SpeckvKVConnector.load_paged call and its stores ONE store_paged call, straight between the
         # pool and the registered caches, instead of a fetch and a scatter per (request, layer, kind) and a stashed copy of every prompt
         self.paged_io = bool(paged_io)
+        # paged_fused (with paged_io): both calls get fused=True -- bf16 caches take the one-launch route as well, and an odd last
+        # position moves inside the launch
+        self._fused = {"fused": True} if paged_fused else {}
         # ---- scheduler-role state (never read by the worker-role methods)
         self._ids: Dict[str, int] = {}                     # vLLM request id (a string) -> the engine's request id
         self._next_id = 1
@@ -259,7 +264,7 @@ class SpeckvVllmConnector:
             if loads:
                 slots = torch.tensor([s for r in loads for s in r.slot_mapping], dtype=torch.int64, device="cuda")
                 self.conn.load_paged([r.engine_id for r in loads], [r.first_token for r in loads], [r.num_tokens for r in loads], slots,
-                                     [self._caches[name] for name in self._layers])
+                                     [self._caches[name] for name in self._layers], **self._fused)
             return
         for r in loads:
             slots = torch.tensor(r.slot_mapping, dtype=torch.int64, device="cuda")
@@ -328,7 +333,7 @@ class SpeckvVllmConnector:
                 self._live[eid] = h["req_id"]
             slots = torch.tensor([s for h in self._handed.values() for s in h["slots"]], dtype=torch.int64, device="cuda")
             self._held += self.conn.store_paged(list(self._handed), [len(h["slots"]) for h in self._handed.values()], slots,
-                                                [self._caches[name] for name in self._layers])
+                                                [self._caches[name] for name in self._layers], **self._fused)
             self._held.append(slots)
             self._handed.clear()
         for eid, layers in self._stash.items():

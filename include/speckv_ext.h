@@ -181,6 +181,60 @@ speckv_status_t speckv_ext_write_slots(const speckv_handle_t* handles, const uin
                                        const void* const* d_caches /* host array of n_layers device pointers */,
                                        uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
                                        uint64_t page_step, void* stream);
+/* The same two calls for caches that hold bf16 and for positions held outside pool and caches.  With elem = SPECKV_SLOT_ELEM_FP16
+ * and both held arrays NULL each _ex entry IS the entry above: the same refusals, the same launch, the same bits.
+ * elem says what the 2048-byte rows of the caches hold.  The pool does not change with it -- a record means the same whichever
+ * cache type it passed through -- so a bf16 row is converted as it is read or written, by exactly these two rules:
+ *   bf16 row -> pool   each element becomes fp16 by ONE round-to-nearest-even of its exact value: overflow gives +-inf, a NaN stays a
+ *                      NaN, fp16 subnormals are kept and anything smaller rounds to +-0.  That fp16 value is what every scheme
+ *                      encodes: the record is the one speckv_ext_write_runs stores for row.to(float16).
+ *   pool -> bf16 row   the decoded fp16 value -- the bits speckv_ext_fetch_range writes -- is rounded to bf16 by ONE
+ *                      round-to-nearest-even of its exact value (never the decoder's fp32 intermediate rounded straight to bf16:
+ *                      two routes out of one record do not disagree).
+ * Of a NaN only the position is specified, not the payload.
+ * A held row is one position of a span, per kind, that lives in neither: [heads][128] fp16 WHATEVER elem says, the row of layer
+ * layer_begin + l at pointer + l * held_layer_stride_bytes.  d_held_in / d_held_out are HOST arrays [n_spans][2] (K, V) of device
+ * pointers, or NULL; an entry pair is both NULL (no held row for that span) or both set.
+ *   read_ex,  d_held_in[2i + kind] set: the span's last position first + n - 1 is even and n >= 1; its row is copied (converted if
+ *             elem is bf16) from the held row into its slot, and its page -- never written -- is not read.  Every other position
+ *             goes as in speckv_ext_read_slots.
+ *   write_ex, d_held_in[2i + kind] set: first_tokens[i], the first position that comes from the caches, is odd, and position
+ *             first - 1 comes from the held row: pair (first - 1) / 2 is encoded from one held fp16 row and one cache row.
+ *             n_tokens[i] counts cache rows only, row t in d_slots[slot_begins[i] + t].
+ *   write_ex, d_held_out[2i + kind] set: first + n is odd; the last position is not encoded but written to the held-out row as
+ *             fp16, zeros where its slot names no row.  A span may have both (first = 5, n = 4 encodes pairs 2 and 3 and holds
+ *             position 8; first even, n = 1 only moves a row into the held-out block).
+ * Still one launch, one descriptor per span; spans of one allocation that share a page are refused, the pair through a held-in row
+ * counting as a page of its span; sealed destinations are unpacked, cached target pages invalidated, the pages moved counted as
+ * above.  The held rows must stay alive (held-in ones unchanged) until the stream has passed the call.
+ *   SPECKV_ERR_INVAL    everything the entries above refuse with it, and: an unknown elem, reserved != 0, a held pointer not 16-byte
+ *                       aligned, held_layer_stride_bytes not a multiple of 16, only one of a span's K / V pointers given, a held row
+ *                       for an empty span; read: d_held_out not NULL, held-in on a span whose last position is odd; write: an odd
+ *                       first without held-in or held-in with an even first, an odd first + n without held-out or held-out with an
+ *                       even first + n
+ * Every refusal launches nothing and leaves the held-out rows untouched.  Not built: capture into a HIP graph, a K pre-scale,
+ * rows of any other size than 2048 bytes. */
+#define SPECKV_SLOT_ELEM_FP16 0u
+#define SPECKV_SLOT_ELEM_BF16 1u
+typedef struct {
+    uint32_t elem;                      /* SPECKV_SLOT_ELEM_*: element type of the caches' rows (2048 B either way) */
+    uint32_t reserved;                  /* 0 */
+    const void* const* d_held_in;       /* NULL, or host array [n_spans][2] of device pointers (each NULL or an fp16 row block) */
+    void* const* d_held_out;            /* write only: the same shape, where the launch puts the new odd last position as fp16 */
+    uint64_t held_layer_stride_bytes;   /* a multiple of 16 */
+} speckv_ext_slot_rows_t;
+speckv_status_t speckv_ext_read_slots_ex(const speckv_handle_t* handles, const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                         const uint64_t* slot_begins, uint32_t n_spans,
+                                         const int64_t* d_slots /* device */, uint64_t n_slots,
+                                         void* const* d_caches /* host array of n_layers device pointers */,
+                                         uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                         uint64_t page_step, const speckv_ext_slot_rows_t* rows, void* stream);
+speckv_status_t speckv_ext_write_slots_ex(const speckv_handle_t* handles, const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                          const uint64_t* slot_begins, uint32_t n_spans,
+                                          const int64_t* d_slots /* device */, uint64_t n_slots,
+                                          const void* const* d_caches /* host array of n_layers device pointers */,
+                                          uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                          uint64_t page_step, const speckv_ext_slot_rows_t* rows, void* stream);
 /* Fork: the STORED RECORDS of page runs copied from one allocation to another, nothing decoded.  Pair i copies pages
  * [run_firsts[r], run_firsts[r] + n_pages[i]) for every run r < n_runs from allocation src[i] to the same page numbers of
  * allocation dst[i] (in the shim layout the runs are the 2 * num_layers (layer, kind) regions and n_pages[i] = positions / 2: a

@@ -15,6 +15,13 @@ route to the row route and its distance to the ceiling.  A store is timed on fre
 after the last).
 
     python profiles/tools/paged_io_bench.py [--layers 8] [--schemes fp8,int4,mxfp4] [--reps 5] [--rounds 3] [--out FILE]
+
+--bf16 (profiles/paged_io_bf16.txt): the fused route (load_paged / store_paged with fused=True: speckv_ext_read_slots_ex /
+_write_slots_ex) on bf16 caches, in the same process and alternating with
+  fp16 fused   the same call on fp16 caches of the same shape (equal bytes: a gap is the conversion's instruction issue);
+  bf16 rows    the row route bf16 caches take without fused=True;
+and, for stores, a request that holds one position already and gets n - 2 more (its tail goes in as the held-in row, the new odd
+last position comes back as a held-out row) against the even store of n - 2 positions into an empty request.
 """
 import argparse
 import os
@@ -26,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 REC_BYTES = {"fp8": 2048, "int4": 1152, "mxfp4": 1088}
 SHAPES = ((4, 8192), (1, 32768))
 BS = 16
-COUNTED = ("read_slots", "write_slots", "fetch_range", "write_runs")
+COUNTED = ("read_slots", "write_slots", "read_slots_ex", "write_slots_ex", "fetch_range", "write_runs")
 
 
 class Counting:
@@ -166,6 +173,97 @@ def bench(scheme, B, n, a, say):
         lib.finalize()
 
 
+def bench_bf16(scheme, B, n, a, say):
+    import numpy as np
+    import torch
+    import cxl_speckv_amd as pkg
+    from cxl_speckv_amd.kv_connector import SpeckvKVConnector
+
+    lib = Counting(pkg.SpeckvLib(pkg.library_path(), "hip:0"))
+    try:
+        H, D, L = 8, 128, a.layers
+        conn = SpeckvKVConnector(lib, L, H, D, n, scheme)
+        blocks = B * n // BS
+        c16 = [torch.randn((2, blocks, BS, H, D), device="cuda").half() for _ in range(L)]
+        cbf = [c.to(torch.bfloat16) for c in c16]
+        table = np.random.default_rng(1).permutation(blocks)
+        slots = (table[:, None] * BS + np.arange(BS)[None]).reshape(-1).astype(np.int64)
+        d_slots = torch.from_numpy(slots).cuda()
+        short = torch.from_numpy(np.concatenate([slots[i * n:i * n + n - 2] for i in range(B)])).cuda()       # n - 2 positions per request
+        ones = torch.from_numpy(np.asarray([slots[i * n + n - 1] for i in range(B)])).cuda()
+        ids = list(range(1, B + 1))
+        for rid in ids:
+            conn.add_request(rid)
+        st = torch.cuda.Stream()
+        conn.store_paged(ids, [n] * B, d_slots, cbf, stream=st, fused=True)
+        torch.cuda.synchronize()
+        fresh = iter(range(1000, 10 ** 9))
+
+        def load(caches, fused):
+            return lambda: conn.load_paged(ids, [0] * B, [n] * B, d_slots, caches, stream=st, fused=fused)
+
+        def store(caches, fused, count, mapping, held):
+            def prepare():
+                new = [next(fresh) for _ in ids]
+                for rid in new:
+                    conn.add_request(rid)
+                if held:                                            # one position first: the request's tail
+                    conn.store_paged(new, [1] * B, ones, caches, stream=st, fused=True)
+                return new
+
+            def run(new):
+                return conn.store_paged(new, [count] * B, mapping, caches, stream=st, fused=fused)
+            return prepare, run
+
+        def timed(route):
+            prepare, run = route if isinstance(route, tuple) else (None, route)
+            arg = prepare() if prepare else None
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            before = lib.n
+            e0.record(st)
+            keep = run(arg) if prepare else run()
+            e1.record(st)
+            torch.cuda.synchronize()
+            launches = lib.n - before
+            del keep
+            if prepare:
+                for rid in arg:
+                    conn.free_request(rid)
+            return e0.elapsed_time(e1), launches
+
+        loads = {"fp16 fused": load(c16, True), "bf16 fused": load(cbf, True), "bf16 rows": load(cbf, False)}
+        stores = {"fp16 fused": store(c16, True, n, d_slots, False), "bf16 fused": store(cbf, True, n, d_slots, False),
+                  "bf16 rows": store(cbf, False, n, d_slots, False),
+                  "bf16 even n-2": store(cbf, True, n - 2, short, False), "bf16 odd n-2": store(cbf, True, n - 2, short, True)}
+        pages = B * 2 * L * (n // 2)
+        moved = pages * (REC_BYTES[scheme] + 4096)
+        say(f"{scheme}: {B} request(s) x {n} positions x {L} layers = {pages} pages, {moved / 1e9:.3f} GB of records + rows")
+        for what, routes in (("load", loads), ("store", stores)):
+            for r in routes.values():
+                timed(r)                                            # warm-up: allocator, staging ring, code objects
+            ms = {name: [] for name in routes}
+            launches = {}
+            for _ in range(a.rounds):
+                one = {name: [] for name in routes}
+                for _ in range(a.reps):
+                    for name, r in routes.items():                  # alternating
+                        t, launches[name] = timed(r)
+                        one[name].append(t)
+                for name in routes:
+                    ms[name].append(statistics.median(one[name]))
+            m = {name: statistics.median(v) for name, v in ms.items()}
+            for name in routes:
+                say(f"  {what:5s} {name:14s} {m[name]:9.3f} ms (medians {min(ms[name]):.3f} .. {max(ms[name]):.3f}), {launches[name]:4d} library launches, "
+                    f"{moved / (m[name] * 1e-3) / 8e12:.3f} of the 8 TB/s roofline")
+            line = f"  {what:5s} bf16 fused / fp16 fused: {m['bf16 fused'] / m['fp16 fused']:.3f}; bf16 rows / bf16 fused: {m['bf16 rows'] / m['bf16 fused']:.2f}x"
+            if what == "store":
+                line += f"; odd (held rows) / even at n - 2: {m['bf16 odd n-2'] / m['bf16 even n-2']:.3f}"
+            say(line)
+    finally:
+        lib.finalize()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=8)
@@ -174,6 +272,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--shapes", default=",".join(f"{b}x{n}" for b, n in SHAPES))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bf16", action="store_true", help="the fused route on bf16 caches (see the module's text)")
     a = ap.parse_args()
     lines = []
 
@@ -183,7 +282,7 @@ def main():
     for shape in a.shapes.split(","):
         B, n = (int(x) for x in shape.split("x"))
         for scheme in a.schemes.split(","):
-            bench(scheme, B, n, a, say)
+            (bench_bf16 if a.bf16 else bench)(scheme, B, n, a, say)
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
