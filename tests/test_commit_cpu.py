@@ -239,14 +239,22 @@ def test_commit_refuses_what_append_path_refuses_and_changes_nothing(host):
 
 def test_pair_gather_encoder_uses_no_flat_memory_instructions():
     """k_compress_pairs<...> keeps the property tests/test_build_guards.py asks of k_compress<...>: rows and records are reached
-    through global-address-space accesses (the RLE form keeps k_compress' one tail store of the all-zero record)"""
+    through global-address-space accesses (the RLE form keeps k_compress' one tail store of the all-zero record).  It lives in
+    row_transfer.o with the other row-transfer kernels: kernels.o, whose headline kernel is pinned by its instructions, holds none
+    of them, and row_transfer.o holds nothing else -- no out-of-line device function that a kernel would reach by a pc-relative call."""
     from tests.test_build_guards import OBJ, OBJDUMP, _disassemble
     if not os.path.exists(OBJDUMP):
         pytest.skip("llvm-objdump of the ROCm toolchain not found")
-    if not os.path.exists(os.path.join(OBJ, "kernels.o")):
+    if not os.path.exists(os.path.join(OBJ, "row_transfer.o")) or not os.path.exists(os.path.join(OBJ, "kernels.o")):
         import __graft_entry__ as entry
         entry.build()
-    funcs = _disassemble("kernels.o")
+    family = r"k_(read|compress)_(pairs|slots)"
+    stray = sorted(name for name in _disassemble("kernels.o") if re.search(family, name))
+    assert not stray, f"row-transfer kernels in kernels.o: {stray}"
+    funcs = _disassemble("row_transfer.o")
+    # a kernel's symbol is <namespaces>k_<family>[_ex]<template arguments>Ev<argument struct>: the name directly behind the namespaces
+    other = sorted(name for name in funcs if not re.match(r"_ZN6speckv\d+_GLOBAL__N_1\d+" + family + r"(_ex)?I[^I]*EEv", name))
+    assert funcs and not other, f"row_transfer.o holds functions that are no row-transfer kernel: {other}"
     for pattern, allowed, instances in ((r"k_compress_pairsILi[0134]ELi\dE", 0, 6), (r"k_compress_pairsILi2ELi\dE", 1, 2), (r"k_compress_pairsILi5ELi0E", 0, 1)):
         hits = {name: n for name, n in funcs.items() if re.search(pattern, name)}
         assert len(hits) == instances, (pattern, sorted(hits))

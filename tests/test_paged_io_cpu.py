@@ -95,7 +95,7 @@ def test_paged_spans_against_brute_force():
 
 
 def _kernel_index_rule(firsts, counts, n_layers, kind_fast):
-    """numpy restatement of slot_work (kernels.hip): for every flat wave index, (span, pair, l, kind, t_even wanted, t_odd wanted) --
+    """numpy restatement of slot_work (row_transfer.hip): for every flat wave index, (span, pair, l, kind, t_even wanted, t_odd wanted) --
     the span by searching the exclusive prefix as the kernel does"""
     spans = SpeckvKVConnector.paged_spans(firsts, counts)
     prefix = np.asarray([s[2] for s in spans], dtype=np.int64)
