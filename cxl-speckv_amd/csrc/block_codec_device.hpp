@@ -658,7 +658,7 @@ __device__ __forceinline__ void decode_fp8(const uint8_t* __restrict__ rec, uint
 // buffer.  Both paths scatter, per RUN START at position p, the value byte of its own pair and the count byte of the
 // PREVIOUS pair (p - previous start); the last pair is closed after the loop.  No read-back from LDS.
 // (kEncPairOff / kEncFail, quantize8 and the SDWA / EXEC-predicated helpers of this path: encode_device.hpp, shared with
-// tensor_codec.hip)
+// tensor_compress.hip)
 
 // Fast path: no stretch of equal deltas reaches 255 elements, so every change of the delta starts a run and no run
 // has to be split (count < 255 rule).  Returns the number of runs, or kEncFail when a long stretch may exist (>= 14

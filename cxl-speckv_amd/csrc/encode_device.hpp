@@ -1,6 +1,6 @@
 // cxl-speckv_amd/csrc/encode_device.hpp -- the instruction-level helpers of the RLE encoder's fast path (device code only):
 // packed-fp32 quantisation of 8 elements, SDWA byte arithmetic, run-start predicates kept in SGPR pairs, the EXEC-predicated
-// pair scatter.  Used by k_compress (kernels.hip) and by the tile passes of the whole-tensor codec (tensor_codec.hip).
+// pair scatter.  Used by k_compress (kernels.hip) and by the tile passes of the whole-tensor compressor (tensor_compress.hip).
 #pragma once
 #include "codec_device.hpp"
 

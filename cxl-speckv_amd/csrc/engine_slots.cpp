@@ -1,6 +1,6 @@
 // cxl-speckv_amd/csrc/engine_slots.cpp -- Engine::read_slots / write_slots, the bodies of speckv_ext_read_slots / _write_slots: spans
 // of positions moved between the pool and the slots of a caller's paged cache (one cache tensor per layer, rows addressed by a slot
-// mapping on the device) by ONE launch each way (kernels: k_read_slots / k_compress_slots, kernels.hip)
+// mapping on the device) by ONE launch each way (kernels: k_read_slots / k_compress_slots, row_transfer.hip)
 #include "engine_internal.hpp"
 #include "tuning.hpp"
 

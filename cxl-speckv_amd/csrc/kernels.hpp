@@ -407,7 +407,7 @@ hipError_t launch_read_slots(const SlotArgs& a, hipStream_t s);
 hipError_t launch_compress_slots_ex(const SlotExArgs& a, hipStream_t s);
 hipError_t launch_read_slots_ex(const SlotExArgs& a, hipStream_t s);
 
-// FPGACacheEngine::compress / ::decompress over a tensor of any length (tensor_codec.hip): one scale, one delta chain and
+// FPGACacheEngine::compress / ::decompress over a tensor of any length (tensor_compress.hip, tensor_decompress.hip): one scale, one delta chain and
 // one run-length stream across the whole tensor.  d_rle: 16-byte aligned, room for 2n bytes rounded up to 16; d_ws:
 // 256-byte aligned scratch of tensor_*_workspace_bytes; d_n_out may be null.
 size_t tensor_compress_workspace_bytes(uint64_t n);
@@ -417,7 +417,7 @@ hipError_t launch_tensor_compress(const void* d_src, uint64_t n, bool src_f32, u
 hipError_t launch_tensor_decompress(const uint8_t* d_rle, uint64_t rle_bytes, float scale, void* d_dst, uint64_t dst_cap, bool out_f32,
                                     uint64_t* d_n_out, void* d_ws, size_t ws_bytes, int quant_mode, hipStream_t s);
 
-// The same over MANY tensors in one launch each way (tensor_codec.hip: k_tcm_fused / k_tdm_fused -- several workgroups per tensor,
+// The same over MANY tensors in one launch each way (tensor_compress.hip: k_tcm_fused, tensor_decompress.hip: k_tdm_fused -- several workgroups per tensor,
 // tensor-local look-back, max|x| by rendezvous; tensors of at most 16 tiles: k_tcb_fused / k_tdb_fused, one workgroup each).
 // TensorDesc = speckv_ext_tensor_t: {data (compress: the source; decompress: the destination), n (elements; decompress: room),
 // rle (the stream, 16-byte aligned), rle_cap}.  max_elems: the host's bound on n (sizes the grid); d_ws: 256-byte aligned,

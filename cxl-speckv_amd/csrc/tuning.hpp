@@ -22,7 +22,7 @@ struct Tuning {
     int32_t attend_int4_striped_wg = 0;     // SPECKV_ATTEND_INT4_STRIPED_WG   INT4_G32 over striped pools: the 4-head kernel with an address per lane (rounds 2-5) instead of the whole-record kernel by residue classes (tests, A/B)
     int32_t attend_layers_loop = 0;         // SPECKV_ATTEND_LAYERS_LOOP       planned_layers: per-layer launches also where one launch could take them all (tests, A/B)
     int32_t attend_fold_launch = 0;         // SPECKV_ATTEND_FOLD_LAUNCH       planned_tail: the tail position by a launch of its own also where the kernel could fold it (tests, A/B)
-    // whole-tensor codec: the multi-launch forms the one-pass kernels replaced, kept as cross-checks of each other (tests)
+    // whole-tensor codec: the multi-launch forms the one-pass kernels replaced, kept as cross-checks of each other (tests; tensor_compress.hip, tensor_decompress.hip)
     int32_t tc_multipass = 0;               // SPECKV_TC_MULTIPASS
     int32_t tc_scan = 0;                    // SPECKV_TC_SCAN                  0 grids of waves, 1 ("wg") one workgroup, 2 ("serial") one wave
     int32_t tc_no_pre = 0;                  // SPECKV_TC_NO_PRE                summary and emit as two plain passes
