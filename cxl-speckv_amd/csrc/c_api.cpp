@@ -981,4 +981,16 @@ speckv_status_t speckv_ext_chunk_split_plan(uint32_t n_seq, const uint32_t* pos_
                                                                                                                           : SPECKV_ERR_INVAL;
 }
 
+speckv_status_t speckv_ext_codec_launch_shape(uint64_t n_blocks, uint32_t n_cus, uint32_t* out_grid, uint64_t* out_per_wave,
+                                              uint64_t* out_wave_step)
+{
+    if (!out_grid || !out_per_wave || !out_wave_step) return SPECKV_ERR_INVAL;
+    LOCK;                                                // (speckv_ext_set_tuning writes the tuning under it)
+    const speckv::CodecLaunchShape sh = speckv::codec_launch_shape_now(n_blocks, n_cus);
+    *out_grid = sh.grid;
+    *out_per_wave = sh.per_wave;
+    *out_wave_step = sh.wave_step;
+    return SPECKV_OK;
+}
+
 } // extern "C"

@@ -1,5 +1,5 @@
 // cxl-speckv_amd/csrc/kernels.hip -- hand-written CDNA4 (gfx950) kernels of the
-// KV hot path.  This file: the block codec (k_fetch_decompress*, k_compress), its launch shape (num_cus, codec_grid) and
+// KV hot path.  This file: the block codec (k_fetch_decompress*, k_compress), its launch shape (num_cus, shape_launch) and
 // launchers (launch_decompress, launch_compress).  The codec's device code -- decoders, encoders, compress_block -- is
 // block_codec_device.hpp, which row_transfer.hip (the pair and slot kernels, a translation unit of their own) includes too.  The
 // other subjects of this translation unit are included below the codec:
@@ -198,7 +198,7 @@ __device__ __forceinline__ void fetch_decompress_body(const CodecArgs& a)
     }
     if (EXT == 3) seq0 = *a.seq0_dev;
     // a wave's blocks: one, or (launches beyond the grid cap) `per_wave` of them, one grid apart (wave_step) or
-    // consecutive (SPECKV_ROUNDS=consecutive); see codec_grid / round_strided
+    // consecutive (SPECKV_ROUNDS=consecutive); see codec_launch_shape
     const uint64_t per_wave = a.per_wave ? a.per_wave : 1;
     const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
     const uint64_t step = a.wave_step ? a.wave_step : 1;                  // 1: consecutive blocks, else one per round
@@ -361,35 +361,22 @@ int num_cus()
     }
     return g_cus;
 }
-// Launch shape: one block per wave up to per_cu workgroups per CU (short-lived waves even out the tail); beyond that
-// every wave takes the same number of consecutive blocks (*per_wave) so that no round runs half empty.
-// (A capped grid-stride loop: 655 360 blocks over 65 536 workgroups = 2.5 rounds, last one half empty: 0.73 of HBM
-// peak; balanced 0.77-0.80.  Measured with profiles/tools/footprint.py, profiles/r02_footprint.md.)
-uint32_t codec_grid(uint64_t n, uint64_t* per_wave)
+// Launch shape: the rule is codec_launch_shape (codec_launch_shape.hpp: the grid cap, the rounds, strided or consecutive, with the
+// measurements behind them) under the tuning in force (wgs_per_cu, rounds_consecutive).  Every block-codec launch is sized HERE: the
+// grid is returned, CodecArgs::per_wave / wave_step are filled in for the kernels' loops.
+uint32_t shape_launch(CodecArgs& a)
 {
-    const int per_cu = tuning().wgs_per_cu > 0 ? tuning().wgs_per_cu : 256;
-    const uint64_t want = (n + kWaves - 1) / kWaves;
-    const uint64_t cap = static_cast<uint64_t>(num_cus()) * per_cu * (4 / kWaves);
-    *per_wave = 1;
-    if (want <= cap) return static_cast<uint32_t>(want ? want : 1);
-    const uint64_t rounds = (want + cap - 1) / cap;
-    *per_wave = rounds;
-    return static_cast<uint32_t>((want + rounds - 1) / rounds);
-}
-// Multi-round launches: a wave's blocks are one grid apart (round r covers blocks [r*G, (r+1)*G) like a launch of its
-// own).  Measured against `per_wave` consecutive blocks per wave on the same device (SPECKV_ROUNDS=consecutive):
-// 0.775 / 0.772 / 0.770 of HBM peak vs 0.753 / 0.69 / 0.657 at 4 / 5 / 20 GiB of pool + destination.
-bool round_strided()
-{
-    return tuning().rounds_consecutive == 0;
+    const CodecLaunchShape sh = codec_launch_shape_now(a.n, 0);
+    a.per_wave = sh.per_wave;
+    a.wave_step = sh.wave_step;
+    return sh.grid;
 }
 
 template <int SCHEME, int MODE>
 hipError_t launch_dec2(const CodecArgs& a_in, hipStream_t s)
 {
     CodecArgs a = a_in;
-    const uint32_t grid = codec_grid(a.n, &a.per_wave);
-    a.wave_step = (round_strided() && a.per_wave > 1) ? static_cast<uint64_t>(grid) * kWaves : 0;
+    const uint32_t grid = shape_launch(a);
     const int ext = a.host_words ? 3 : (a.alloc_list || a.ring_owner) ? 2 : a.stripe_n ? 1 : 0;
     if (ext == 2 && a.stripe_n) return hipErrorInvalidValue;
     if (a.ring_owner && a.alloc_list) return hipErrorInvalidValue;      // the ring form reads one allocation's row (load_desc_ring)
@@ -415,17 +402,20 @@ hipError_t launch_dec1(const CodecArgs& a, hipStream_t s)
     return a.quant_mode == kIntent ? launch_dec2<SCHEME, kIntent>(a, s) : launch_dec2<SCHEME, kRefExact>(a, s);
 }
 template <int SCHEME>
-hipError_t launch_enc1(const CodecArgs& a_in, hipStream_t s)
+hipError_t launch_enc1(const CodecArgs& a, uint32_t grid, hipStream_t s)
 {
-    CodecArgs a = a_in;
-    const uint32_t grid = codec_grid(a.n, &a.per_wave);
-    a.wave_step = (round_strided() && a.per_wave > 1) ? static_cast<uint64_t>(grid) * kWaves : 0;
     if (a.quant_mode == kIntent) hipLaunchKernelGGL((k_compress<SCHEME, kIntent>), dim3(grid), dim3(kThreads), 0, s, a);
     else                         hipLaunchKernelGGL((k_compress<SCHEME, kRefExact>), dim3(grid), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }
 
 } // namespace
+
+CodecLaunchShape codec_launch_shape_now(uint64_t n, uint32_t n_cus)
+{
+    return codec_launch_shape(n, n_cus ? n_cus : static_cast<uint32_t>(num_cus()), tuning().wgs_per_cu, tuning().rounds_consecutive != 0,
+                              static_cast<uint32_t>(kWaves));
+}
 
 hipError_t launch_decompress(const CodecArgs& a, hipStream_t s)
 {
@@ -444,31 +434,21 @@ hipError_t launch_decompress(const CodecArgs& a, hipStream_t s)
 hipError_t launch_compress(const CodecArgs& a, hipStream_t s)
 {
     if (a.n == 0) return hipSuccess;
-    switch (a.scheme) {
-    case kFp16: return launch_enc1<kFp16>(a, s);
-    case kInt8: return launch_enc1<kInt8>(a, s);
-    case kInt8DeltaRle: return launch_enc1<kInt8DeltaRle>(a, s);
-    case kInt4G32: {
-        CodecArgs b = a;
-        const uint32_t grid = codec_grid(b.n, &b.per_wave);
-        b.wave_step = (round_strided() && b.per_wave > 1) ? static_cast<uint64_t>(grid) * kWaves : 0;
+    CodecArgs b = a;
+    const uint32_t grid = shape_launch(b);
+    switch (b.scheme) {
+    case kFp16: return launch_enc1<kFp16>(b, grid, s);
+    case kInt8: return launch_enc1<kInt8>(b, grid, s);
+    case kInt8DeltaRle: return launch_enc1<kInt8DeltaRle>(b, grid, s);
+    case kInt4G32:                                                     // (these three: the quantiser mode does not apply)
         hipLaunchKernelGGL((k_compress<kInt4G32, kRefExact>), dim3(grid), dim3(kThreads), 0, s, b);
         return hipGetLastError();
-    }
-    case kFp8E4m3: {
-        CodecArgs b = a;
-        const uint32_t grid = codec_grid(b.n, &b.per_wave);
-        b.wave_step = (round_strided() && b.per_wave > 1) ? static_cast<uint64_t>(grid) * kWaves : 0;
+    case kFp8E4m3:
         hipLaunchKernelGGL((k_compress<kFp8E4m3, kRefExact>), dim3(grid), dim3(kThreads), 0, s, b);
         return hipGetLastError();
-    }
-    case kMxFp4: {
-        CodecArgs b = a;
-        const uint32_t grid = codec_grid(b.n, &b.per_wave);
-        b.wave_step = (round_strided() && b.per_wave > 1) ? static_cast<uint64_t>(grid) * kWaves : 0;
+    case kMxFp4:
         hipLaunchKernelGGL((k_compress<kMxFp4, kRefExact>), dim3(grid), dim3(kThreads), 0, s, b);
         return hipGetLastError();
-    }
     default: return hipErrorInvalidValue;
     }
 }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "ring_rule.hpp"
+#include "codec_launch_shape.hpp"
 
 namespace speckv {
 
@@ -398,6 +399,9 @@ struct CodecArgs {
 
 hipError_t launch_compress(const CodecArgs& a, hipStream_t s);
 hipError_t launch_decompress(const CodecArgs& a, hipStream_t s);
+// the shape both give a launch of n blocks under the tuning in force (codec_launch_shape.hpp; wgs_per_cu, rounds_consecutive);
+// n_cus 0: the current device's CUs, or 256 without a device
+CodecLaunchShape codec_launch_shape_now(uint64_t n, uint32_t n_cus);
 // the pair-gather form of the encoder: n_pairs * 2 * n_layers blocks in one launch, rows read where they lie (k_compress_pairs)
 hipError_t launch_compress_pairs(const PairArgs& a, hipStream_t s);
 hipError_t launch_read_pairs(const ReadPairArgs& a, hipStream_t s);

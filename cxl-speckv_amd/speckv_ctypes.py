@@ -94,6 +94,7 @@ _EXT_SIGNATURES = {
                                       c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p,
                                       c_void_p, c_void_p],
     "speckv_ext_chunk_split_plan": [c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p],
+    "speckv_ext_codec_launch_shape": [c_uint64, c_uint32, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_chunk_window": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                        c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p,
                                        c_void_p],
@@ -748,6 +749,13 @@ class SpeckvLib:
         self.lib.speckv_ext_set_tuning.restype = ctypes.c_int
         if self.lib.speckv_ext_set_tuning(key.encode(), int(value)) != 0:
             raise ValueError(f"speckv_ext_set_tuning: no such key {key!r}")
+
+    def codec_launch_shape(self, n_blocks, n_cus=0):
+        """The shape of a block-codec launch of n_blocks under the tuning in force (speckv_ext_codec_launch_shape; works without init):
+        (grid, per_wave, wave_step).  n_cus 0: the device's CUs, 256 without a device."""
+        grid, per_wave, step = c_uint32(), c_uint64(), c_uint64()
+        self._ext("speckv_ext_codec_launch_shape", int(n_blocks), int(n_cus), ctypes.byref(grid), ctypes.byref(per_wave), ctypes.byref(step))
+        return grid.value, per_wave.value, step.value
 
     def promote_to_l1(self, handle, offset):
         return self.lib.speckv_ext_promote_to_l1(handle, offset) == 0

@@ -818,6 +818,19 @@ speckv_status_t speckv_ext_decode_window_range(uint32_t length, uint32_t window,
  * SPECKV_ERR_INVAL for an unknown key.  Works without speckv_init.  (INTEGRATION.md lists what each one does.) */
 speckv_status_t speckv_ext_set_tuning(const char* key, long long value);
 
+/* speckv_ext_codec_launch_shape: the shape the library gives a block-codec launch of n_blocks blocks (speckv_ext_codec_compress /
+ * _decompress, the pool's writes and fetches, the flush and ring fetches) under the tuning in force -- the body the launchers
+ * themselves call, as a pure function.  Workgroups have 4 waves.  Up to cap = n_cus x wgs_per_cu workgroups (tuning key wgs_per_cu,
+ * 256 by default) a wave handles one block: *grid = ceil(n_blocks / 4), *per_wave = 1, *wave_step = 0.  Beyond that the launch has
+ * rounds = ceil(ceil(n_blocks / 4) / cap) rounds: *per_wave = rounds blocks per wave and *grid = ceil(ceil(n_blocks / 4) / rounds)
+ * <= cap.  Wave w of the launch (workgroup x 4 + wave) then handles the blocks w, w + *wave_step, ... below n_blocks, with
+ * *wave_step = *grid x 4 (a round looks like a launch of its own), or, under the tuning key rounds_consecutive, the blocks
+ * [w x *per_wave, min((w + 1) x *per_wave, n_blocks)) with *wave_step = 0.  Either way every block belongs to exactly one wave, also
+ * when the device finds fewer blocks than the launch was sized for (the flush fetch).  n_blocks = 0: *grid = 1 (the launchers
+ * launch nothing).  n_cus = 0: the compute units of the current device, or 256 without a device.  Works without speckv_init.
+ * SPECKV_ERR_INVAL for a NULL output. */
+speckv_status_t speckv_ext_codec_launch_shape(uint64_t n_blocks, uint32_t n_cus, uint32_t* grid, uint64_t* per_wave, uint64_t* wave_step);
+
 /* Is `stream` (a hipStream_t) being captured into a HIP graph right now?  The batch entry points and speckv_ext_attend_batch_plan
  * refuse such a stream; a caller that plans ahead (SpeckvKVConnector.append) asks first.  *out_capturing = 0 for the NULL stream.
  * SPECKV_ERR_DRIVER when the runtime does not know the stream (destroyed by its owner).  Works without speckv_init. */
