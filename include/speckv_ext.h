@@ -394,6 +394,9 @@ speckv_status_t speckv_ext_codec_decompress(const void* d_recs, uint64_t rec_str
  *                speckv_ext_codec_tensor_decode_workspace_bytes(rle_bytes) bytes
  * Decompress: dst gets min(sum of counts, dst_cap_elems) elements (fp32 or fp16; 16-byte aligned), *d_n_out (device,
  * optional) that number; an odd trailing byte is dropped and a zero count emits nothing, as in the reference.
+ * The decoder takes a stream at any 2-BYTE aligned address (a pair is never split; an odd d_rle is SPECKV_ERR_INVAL): the
+ * 16-byte alignment above is what compress needs for the stream it writes, and what lets the decoder load 8 pairs at a time --
+ * off it the stream is read pair by pair, slower, with the same result.
  * Pass the tensor's element count as dst_cap_elems when it is known: the library picks its decoder from rle_bytes / 2 pairs
  * against dst_cap_elems (a stream of one pair per element is decoded in one pass over the pairs, one that compresses tile by
  * tile of the output); a capacity far above the real count only costs speed, never correctness.
@@ -419,7 +422,7 @@ speckv_status_t speckv_ext_codec_decompress_tensor(const void* d_rle, uint64_t r
  *   compress:   data = the source (fp16, or fp32 with src_f32), n = its elements, rle = where the stream goes (16-byte aligned),
  *               rle_cap >= 2 n rounded up to 16 (not checked); d_rle_bytes[i] / d_scales[i] receive the stream length / the scale
  *   decompress: data = the destination (16-byte aligned; fp16, or fp32 with out_f32), n = its room in elements (<= max_elems),
- *               rle = the stream (2 max_elems bytes at most), d_rle_bytes[i] / d_scales[i] as compress left them; d_n_out[i] (may be
+ *               rle = the stream (2 max_elems bytes at most; 2-byte aligned, as above), d_rle_bytes[i] / d_scales[i] as compress left them; d_n_out[i] (may be
  *               NULL) = elements decoded, clipped to the room
  *   d_workspace  256-byte aligned, speckv_ext_codec_tensors_workspace_bytes(n_tensors, max_elems) bytes (cleared by the call)
  * Asynchronous on `stream`; no engine needed. */

@@ -683,7 +683,10 @@ def test_tensor_codec_look_back_over_many_workgroups(lib, oracle):
         assert_same_float_bits(y, want, f"6Mi mode {mode}")
         y = gpu_decompress_tensor(lib, o_rle, o_scale, 1500000 + 123457, mode, False)       # clipped inside the long flat stretch, fp16 out
         assert_same_float_bits(y, want[:1500000 + 123457].astype(np.float16), f"6Mi clipped mode {mode}")
-    # a hand-made stream: long counts everywhere (every chunk spans many windows) and a zero count in some chunks
+    # a hand-made stream: long counts everywhere and a zero count in two chunks.  At 227 elements per pair the library decodes it by
+    # OUTPUT (k_td_summary, the scan, k_td_expand_scatter: the tiles that meet a zero count take td_tile_general); under td_one_pass it
+    # is k_td_fused, where every chunk spans many 4096-element windows (td_windows_behind_the_first) and the two chunks with a zero
+    # count go pair by pair (td_chunk_general), ten look-back words deep
     pairs = 300000
     stream = rng.integers(0, 256, 2 * pairs).astype(np.uint8)
     stream[1::2] = rng.integers(200, 256, pairs).astype(np.uint8)
@@ -691,6 +694,12 @@ def test_tensor_codec_look_back_over_many_workgroups(lib, oracle):
     want = oracle.decompress_f32(stream, 0.125, 0)
     y = gpu_decompress_tensor(lib, stream, 0.125, want.size + 5, 0, True)
     assert_same_float_bits(y, want, "long counts")
+    set_tuning("td_one_pass", 1)
+    try:
+        y = gpu_decompress_tensor(lib, stream, 0.125, want.size + 5, 0, True)
+    finally:
+        set_tuning("td_one_pass", 0)
+    assert_same_float_bits(y, want, "long counts, one pass")
 
 
 def test_tensor_codec_matches_oracle_over_sizes_and_structures(lib, oracle):
