@@ -1,7 +1,7 @@
 // cxl-speckv_amd/csrc/block_codec_device.hpp -- the device code of the block codec (device code only): what turns one record
 // into a block's 4 KiB image and back, without the kernels that say which block a wave owns.  Streaming global loads and stores,
 // the destination forms of a decoder (a contiguous image, the two rows of a RowSink / RowSinkBf16), every decode_* helper, the RLE
-// encoder, the source forms of an encoder (SrcRun, SrcPair, SrcPairMixed) and compress_block, the one body of every encoder kernel.
+// encoder, the source forms of an encoder (SrcRun, SrcPair, SrcPairMixed, SrcPairScaled) and compress_block, the one body of every encoder kernel.
 // Included by kernels.hip (k_fetch_decompress*, k_compress) and by row_transfer.hip (the pair and slot kernels); the
 // instruction-level helpers underneath are codec_device.hpp and encode_device.hpp.
 //
@@ -182,6 +182,61 @@ __device__ __forceinline__ void put16(const RowSinkBf16& d, uint32_t p0, uint4 v
 {
     uint8_t* r = d.row(p0);
     if (r) st16(r + 2ull * (p0 & 1023u), half8_to_bf16(v));
+}
+// The per-channel K factor of a paged-cache transfer (k_read_slots_ex / k_compress_slots_ex on a SlotKmulArgs): an element that
+// crosses between a cache row and the pool side is multiplied by the fp16 factor of its channel.  The product is taken in fp32,
+// where it is exact (11 x 11 or 8 x 11 significand bits), and rounded ONCE, to nearest even, to the destination's element type --
+// the three forms below: fp16 x factor -> fp16 (what torch's half multiply gives), fp16 x factor -> bf16, bf16 x factor -> fp16.
+__device__ __forceinline__ uint32_t mul_half2(uint32_t w, uint32_t m)
+{
+    return pack_half2(half_bits_to_float(w & 0xFFFFu) * half_bits_to_float(m & 0xFFFFu), half_bits_to_float(w >> 16) * half_bits_to_float(m >> 16));
+}
+__device__ __forceinline__ uint32_t mul_half2_to_bf16x2(uint32_t w, uint32_t m)
+{
+    return pack_bf16x2(half_bits_to_float(w & 0xFFFFu) * half_bits_to_float(m & 0xFFFFu), half_bits_to_float(w >> 16) * half_bits_to_float(m >> 16));
+}
+__device__ __forceinline__ uint32_t mul_bf16x2_to_half2(uint32_t w, uint32_t m)
+{
+    return pack_half2(__uint_as_float(w << 16) * half_bits_to_float(m & 0xFFFFu), __uint_as_float(w & 0xFFFF0000u) * half_bits_to_float(m >> 16));
+}
+__device__ __forceinline__ uint4 mul_half8(uint4 v, uint4 m) { return make_uint4(mul_half2(v.x, m.x), mul_half2(v.y, m.y), mul_half2(v.z, m.z), mul_half2(v.w, m.w)); }
+__device__ __forceinline__ uint4 mul_half8_to_bf16(uint4 v, uint4 m)
+{
+    return make_uint4(mul_half2_to_bf16x2(v.x, m.x), mul_half2_to_bf16x2(v.y, m.y), mul_half2_to_bf16x2(v.z, m.z), mul_half2_to_bf16x2(v.w, m.w));
+}
+__device__ __forceinline__ uint4 mul_bf16_to_half8(uint4 v, uint4 m)
+{
+    return make_uint4(mul_bf16x2_to_half2(v.x, m.x), mul_bf16x2_to_half2(v.y, m.y), mul_bf16x2_to_half2(v.z, m.z), mul_bf16x2_to_half2(v.w, m.w));
+}
+// RowSink / RowSinkBf16 with that factor: `mul` is the [heads][128] fp16 factor row of the block's layer, shared by the two
+// position rows (element p of the block takes factor element p & 1023).  A decoder still hands over the fp16 bits that
+// speckv_ext_fetch_range writes; the sink multiplies THOSE -- the lane's 16 bytes of factors lie at its chunk's own offset, one more
+// 16-byte load per store.
+struct RowSinkMul {
+    uint8_t* even;
+    uint8_t* odd;
+    const uint8_t* mul;
+    __device__ __forceinline__ uint8_t* row(uint32_t p) const { return p < 1024u ? even : odd; }
+};
+struct RowSinkBf16Mul {
+    uint8_t* even;
+    uint8_t* odd;
+    const uint8_t* mul;
+    __device__ __forceinline__ uint8_t* row(uint32_t p) const { return p < 1024u ? even : odd; }
+};
+template <> struct is_row_sink<RowSinkMul> { static constexpr bool value = true; };
+template <> struct is_row_sink<RowSinkBf16Mul> { static constexpr bool value = true; };
+__device__ __forceinline__ bool wants(const RowSinkMul& d, uint32_t p0) { return d.row(p0) != nullptr; }
+__device__ __forceinline__ bool wants(const RowSinkBf16Mul& d, uint32_t p0) { return d.row(p0) != nullptr; }
+__device__ __forceinline__ void put16(const RowSinkMul& d, uint32_t p0, uint4 v)
+{
+    uint8_t* r = d.row(p0);
+    if (r) st16(r + 2ull * (p0 & 1023u), mul_half8(v, ld16(d.mul + 2ull * (p0 & 1023u))));
+}
+__device__ __forceinline__ void put16(const RowSinkBf16Mul& d, uint32_t p0, uint4 v)
+{
+    uint8_t* r = d.row(p0);
+    if (r) st16(r + 2ull * (p0 & 1023u), mul_half8_to_bf16(v, ld16(d.mul + 2ull * (p0 & 1023u))));
 }
 template <bool F32, class DST>
 __device__ __forceinline__ void store8(const DST& dst, uint32_t p0, const float (&y)[8])
@@ -466,6 +521,22 @@ __device__ __forceinline__ void store_elem(const RowSinkBf16& d, uint32_t p, flo
     uint8_t* r = d.row(p);
     float a = y, z = 0.0f;
     if (r) gstore<uint16_t>(r + 2ull * (p & 1023u), static_cast<uint16_t>(half2_to_bf16x2(pack_half2(a, z) & 0xFFFFu) & 0xFFFFu));
+}
+template <bool F32>
+__device__ __forceinline__ void store_elem(const RowSinkMul& d, uint32_t p, float y)
+{
+    static_assert(!F32, "position rows are fp16");
+    uint8_t* r = d.row(p);
+    float a = y, z = 0.0f;
+    if (r) gstore<uint16_t>(r + 2ull * (p & 1023u), static_cast<uint16_t>(mul_half2(pack_half2(a, z) & 0xFFFFu, gload<uint16_t>(d.mul + 2ull * (p & 1023u))) & 0xFFFFu));
+}
+template <bool F32>
+__device__ __forceinline__ void store_elem(const RowSinkBf16Mul& d, uint32_t p, float y)
+{
+    static_assert(!F32, "position rows are 16-bit");
+    uint8_t* r = d.row(p);
+    float a = y, z = 0.0f;
+    if (r) gstore<uint16_t>(r + 2ull * (p & 1023u), static_cast<uint16_t>(mul_half2_to_bf16x2(pack_half2(a, z) & 0xFFFFu, gload<uint16_t>(d.mul + 2ull * (p & 1023u))) & 0xFFFFu));
 }
 template <int MODE, bool F32, class DST>
 __device__ __forceinline__ void decode_rle_general_to(const uint8_t* __restrict__ rec, uint32_t len,
@@ -793,6 +864,38 @@ __device__ __forceinline__ uint32_t src_half(const SrcPairMixed& src, uint32_t e
     const uint32_t b = gload<uint16_t>(low ? src.lo + 2ull * e : src.hi + 2ull * (e - 1024u));
     return (low ? src.lo_bf16 : src.hi_bf16) ? (bf16x2_to_half2(b) & 0xFFFFu) : b;
 }
+// SrcPairMixed whose rows also say whether they are scaled (the K waves of k_compress_slots_ex on a SlotKmulArgs): lo_mul / hi_mul
+// = the [heads][128] fp16 factor row of the block's layer, or nullptr for a row that is pool-side already (a held-in row is
+// neither bf16 nor scaled).  The encoder sees fp16_rne(float(x) * float(m)) of the cache element x, fp16 or bf16 -- one rounding,
+// never bf16 -> fp16 -> scaled -- on both access paths; the lane's 16 bytes of factors lie at its chunk's own offset in the row.
+struct SrcPairScaled {
+    const uint8_t* lo;
+    const uint8_t* hi;
+    bool lo_bf16, hi_bf16;
+    const uint8_t* lo_mul;
+    const uint8_t* hi_mul;
+};
+__device__ __forceinline__ uint4 src_ld16(const SrcPairScaled& src, int j, uint32_t lane)
+{
+    const uint32_t off = 2u * (512u * (j & 1) + 8u * lane);
+    const uint4 v = enc_ld16((j < 2 ? src.lo : src.hi) + off);
+    const bool bf16 = j < 2 ? src.lo_bf16 : src.hi_bf16;
+    const uint8_t* mul = j < 2 ? src.lo_mul : src.hi_mul;
+    if (!mul) return bf16 ? bf16_to_half8(v) : v;
+    const uint4 m = ld16(mul + off);
+    return bf16 ? mul_bf16_to_half8(v, m) : mul_half8(v, m);
+}
+__device__ __forceinline__ uint32_t src_half(const SrcPairScaled& src, uint32_t e)
+{
+    const bool low = e < 1024u;
+    const uint32_t r = low ? e : e - 1024u;
+    const uint32_t b = gload<uint16_t>((low ? src.lo : src.hi) + 2ull * r);
+    const bool bf16 = low ? src.lo_bf16 : src.hi_bf16;
+    const uint8_t* mul = low ? src.lo_mul : src.hi_mul;
+    if (!mul) return bf16 ? (bf16x2_to_half2(b) & 0xFFFFu) : b;
+    const uint32_t m = gload<uint16_t>(mul + 2ull * r);
+    return (bf16 ? mul_bf16x2_to_half2(b, m) : mul_half2(b, m)) & 0xFFFFu;
+}
 
 // General path (long stretches: zeros, constants; blocks with inf / NaN): one element per lane per step, rolled,
 // quantised with the exact scalar form straight from the source; stretch starts by max-scan, a run starts every 255
@@ -843,6 +946,8 @@ template <int MODE>
 __device__ __forceinline__ uint32_t encode_rle_general(const SrcPair src, float scale, uint8_t* wl, uint32_t lane) { return encode_rle_general_from<MODE>(src, scale, wl, lane); }
 template <int MODE>
 __device__ __forceinline__ uint32_t encode_rle_general(const SrcPairMixed src, float scale, uint8_t* wl, uint32_t lane) { return encode_rle_general_from<MODE>(src, scale, wl, lane); }
+template <int MODE>
+__device__ __forceinline__ uint32_t encode_rle_general(const SrcPairScaled src, float scale, uint8_t* wl, uint32_t lane) { return encode_rle_general_from<MODE>(src, scale, wl, lane); }
 
 // the reference's own rule for blocks that hold inf / NaN: a NaN never wins the '>' compare (cache_engine.cpp:176-180).
 // Rare, out of line, and fed from memory again (a register array passed by reference would move to scratch).
@@ -864,6 +969,7 @@ __device__ __noinline__ float absmax_with_nonfinite(const uint8_t* __restrict__ 
 __device__ __forceinline__ float absmax_with_nonfinite(const SrcRun src, uint32_t lane) { return absmax_with_nonfinite(src.p, lane); }
 __device__ __forceinline__ float absmax_with_nonfinite(const SrcPair src, uint32_t lane) { return absmax_with_nonfinite_from(src, lane); }
 __device__ __forceinline__ float absmax_with_nonfinite(const SrcPairMixed src, uint32_t lane) { return absmax_with_nonfinite_from(src, lane); }
+__device__ __forceinline__ float absmax_with_nonfinite(const SrcPairScaled src, uint32_t lane) { return absmax_with_nonfinite_from(src, lane); }
 
 // ===================================================================
 // encode  (cache_engine.cpp:40-82,172-239)

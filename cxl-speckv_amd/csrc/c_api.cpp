@@ -232,6 +232,36 @@ speckv_status_t speckv_ext_write_slots_ex(const speckv_handle_t* handles, const 
     return guarded([&] { return g_engine->write_slots(c, static_cast<hipStream_t>(stream)); });
 }
 
+speckv_status_t speckv_ext_read_slots_kmul(const speckv_handle_t* handles, const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                           const uint64_t* slot_begins, uint32_t n_spans, const int64_t* d_slots, uint64_t n_slots,
+                                           void* const* d_caches, uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                           uint64_t page_step, const speckv_ext_slot_rows_t* rows, const void* d_k_mul,
+                                           uint64_t k_mul_layer_stride_bytes, void* stream)
+{
+    LOCK; NEED_INIT;
+    if (!rows) return SPECKV_ERR_INVAL;
+    speckv::Engine::SlotCall c{handles, first_tokens, n_tokens, slot_begins, n_spans, d_slots, n_slots, d_caches, layer_begin, n_layers,
+                               kind_stride_bytes, page_step, true, rows->elem, rows->reserved, rows->d_held_in, rows->d_held_out,
+                               rows->held_layer_stride_bytes};
+    if (d_k_mul) { c.k_mul = d_k_mul; c.k_mul_stride = k_mul_layer_stride_bytes; }       // (without a factor: the _ex call)
+    return guarded([&] { return g_engine->read_slots(c, static_cast<hipStream_t>(stream)); });
+}
+
+speckv_status_t speckv_ext_write_slots_kmul(const speckv_handle_t* handles, const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                            const uint64_t* slot_begins, uint32_t n_spans, const int64_t* d_slots, uint64_t n_slots,
+                                            const void* const* d_caches, uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                            uint64_t page_step, const speckv_ext_slot_rows_t* rows, const void* d_k_mul,
+                                            uint64_t k_mul_layer_stride_bytes, void* stream)
+{
+    LOCK; NEED_INIT;
+    if (!rows) return SPECKV_ERR_INVAL;
+    speckv::Engine::SlotCall c{handles, first_tokens, n_tokens, slot_begins, n_spans, d_slots, n_slots, d_caches, layer_begin, n_layers,
+                               kind_stride_bytes, page_step, true, rows->elem, rows->reserved, rows->d_held_in, rows->d_held_out,
+                               rows->held_layer_stride_bytes};
+    if (d_k_mul) { c.k_mul = d_k_mul; c.k_mul_stride = k_mul_layer_stride_bytes; }
+    return guarded([&] { return g_engine->write_slots(c, static_cast<hipStream_t>(stream)); });
+}
+
 speckv_status_t speckv_ext_copy_runs(const speckv_handle_t* src, const speckv_handle_t* dst, const uint64_t* n_pages, uint32_t n_pairs,
                                      const uint64_t* run_firsts, uint32_t n_runs, void* stream)
 {

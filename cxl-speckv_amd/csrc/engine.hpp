@@ -183,6 +183,8 @@ public:
         // the _ex entries (speckv_ext_slot_rows_t): the caches' element type and the held rows, [n_spans][2] host arrays or nullptr
         bool ex = false; uint32_t elem = 0, reserved = 0;
         const void* const* held_in = nullptr; void* const* held_out = nullptr; uint64_t held_stride = 0;
+        // the _kmul entries: the fp16 [heads][128] K factor rows on the device, one per layer from layer_begin on; nullptr = the _ex call
+        const void* k_mul = nullptr; uint64_t k_mul_stride = 0;
     };
     int read_slots(const SlotCall& c, hipStream_t s);
     int write_slots(const SlotCall& c, hipStream_t s);

@@ -21,13 +21,17 @@ namespace speckv {
 // held-in row completes the first pair, a held-out row takes the odd last position), (first + n - 1) / 2 on the read side where
 // the last position comes from a held row, (first + n + 1) / 2 otherwise; a held row adds one SlotHeld per span to the staged
 // slot and the move waves to the launch.  With fp16 caches and no held rows the call is the plain one, launch for launch.
+// The _kmul entries (c.k_mul) add the K factor rows: the same call and the same waves, through the kernel instances that multiply
+// every K element between a cache row and the pool side (SlotKmulArgs, kernels.hpp); without a factor the call is the _ex one.
 int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
 {
-    const char* entry = write ? (c.ex ? "speckv_ext_write_slots_ex" : "speckv_ext_write_slots") : (c.ex ? "speckv_ext_read_slots_ex" : "speckv_ext_read_slots");
+    const char* entry = c.k_mul ? (write ? "speckv_ext_write_slots_kmul" : "speckv_ext_read_slots_kmul")
+                        : write ? (c.ex ? "speckv_ext_write_slots_ex" : "speckv_ext_write_slots") : (c.ex ? "speckv_ext_read_slots_ex" : "speckv_ext_read_slots");
     if (null_) return no_data_path(entry);
     if (!s || !c.handles || !c.first_tokens || !c.n_tokens || !c.slot_begins || !c.d_slots || !c.d_caches) return SPECKV_ERR_INVAL;
     if (c.kind_stride % 16u || c.page_step == 0) return SPECKV_ERR_INVAL;
     if (c.elem > SPECKV_SLOT_ELEM_BF16 || c.reserved != 0 || c.held_stride % 16u || (!write && c.held_out)) return SPECKV_ERR_INVAL;
+    if (c.k_mul && (reinterpret_cast<uintptr_t>(c.k_mul) % 16u || c.k_mul_stride % 16u)) return SPECKV_ERR_INVAL;      // (16-byte loads)
     if (c.n_spans == 0 || c.n_layers == 0) return SPECKV_OK;
     for (uint32_t l = 0; l < c.n_layers; ++l)
         if (!c.d_caches[l] || reinterpret_cast<uintptr_t>(c.d_caches[l]) % 16u) return SPECKV_ERR_INVAL;
@@ -53,7 +57,7 @@ int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
     }
     if (n_pairs == 0 && n_held == 0) return SPECKV_OK;
     const bool held = n_held != 0 || n_in != 0;                                 // (a held-in row of a write rides on its pair's wave)
-    const bool ex = held || c.elem != SPECKV_SLOT_ELEM_FP16;
+    const bool ex = held || c.elem != SPECKV_SLOT_ELEM_FP16 || c.k_mul;
     if (is_capturing(s)) {
         SPECKV_ERR("%s cannot be captured into a HIP graph (its descriptors are staged per call)", entry);
         return SPECKV_ERR_INVAL;
@@ -171,7 +175,12 @@ int Engine::slots_call(const SlotCall& c, bool write, hipStream_t s)
         x.held_stride = c.held_stride;
         x.n_moves = n_held ? c.n_spans * 2u * c.n_layers : 0u;
         x.bf16 = c.elem == SPECKV_SLOT_ELEM_BF16;
-        HIP_TRY(write ? launch_compress_slots_ex(x, s) : launch_read_slots_ex(x, s));
+        if (c.k_mul) {
+            const SlotKmulArgs y{x, static_cast<const uint8_t*>(c.k_mul), c.k_mul_stride};
+            HIP_TRY(write ? launch_compress_slots_kmul(y, s) : launch_read_slots_kmul(y, s));
+        } else {
+            HIP_TRY(write ? launch_compress_slots_ex(x, s) : launch_read_slots_ex(x, s));
+        }
     } else {
         HIP_TRY(write ? launch_compress_slots(sa, s) : launch_read_slots(sa, s));
     }

@@ -175,6 +175,16 @@ struct SlotExArgs {
     uint32_t         n_moves;         // 0 or n_spans * 2 * n_layers
     uint32_t         bf16;            // the caches' rows hold bf16
 };
+// The _ex launch with a per-channel K factor (the SlotKmulArgs instances of k_read_slots_ex / k_compress_slots_ex): every K
+// element that crosses between a cache row and the pool side -- records and held rows -- is multiplied by the fp16 factor of its
+// (layer, head, channel), the exact fp32 product rounded once to the destination's element type.  The [heads][128] factor row of
+// layer layer_begin + l is k_mul + l * k_mul_stride.  Whether a wave scales is j & 1 alone (K = 0): V waves take the source and
+// sink of the _ex kernels and never load a factor.  A held-in row of a write is pool-side already and is encoded as it is.
+struct SlotKmulArgs {
+    SlotExArgs       x;
+    const uint8_t*   k_mul;           // device, 16-byte aligned, never nullptr (without a factor the call is the _ex launch)
+    uint64_t         k_mul_stride;    // bytes between the layers' factor rows, a multiple of 16
+};
 
 // One (source, destination) pair of a record-copy launch (CopyArgs::pairs; copy_records.hip): the stored records of pages
 // [run_firsts[r], run_firsts[r] + n_pages), every run r of the launch, go from the allocation in table row `src_row` to the same
@@ -410,6 +420,8 @@ hipError_t launch_compress_slots(const SlotArgs& a, hipStream_t s);
 hipError_t launch_read_slots(const SlotArgs& a, hipStream_t s);
 hipError_t launch_compress_slots_ex(const SlotExArgs& a, hipStream_t s);
 hipError_t launch_read_slots_ex(const SlotExArgs& a, hipStream_t s);
+hipError_t launch_compress_slots_kmul(const SlotKmulArgs& a, hipStream_t s);
+hipError_t launch_read_slots_kmul(const SlotKmulArgs& a, hipStream_t s);
 
 // FPGACacheEngine::compress / ::decompress over a tensor of any length (tensor_compress.hip, tensor_decompress.hip): one scale, one delta chain and
 // one run-length stream across the whole tensor.  d_rle: 16-byte aligned, room for 2n bytes rounded up to 16; d_ws:

@@ -4,7 +4,8 @@
 //                                              the commit of a multi-position step and its rollback)
 //   k_compress_slots / k_read_slots            rows named by a slot mapping on the device and a cache base per layer
 //                                              (Engine::write_slots / read_slots: paged caches)
-//   k_compress_slots_ex / k_read_slots_ex      the same for caches that hold bf16 and for spans with held rows
+//   k_compress_slots_ex / k_read_slots_ex      the same for caches that hold bf16 and for spans with held rows; their SlotKmulArgs
+//                                              instances multiply K by a per-channel factor on the way (the connector's K pre-scale)
 //
 // A translation unit of its own: the headline kernel of kernels.hip is pinned by the hash of its instructions, and these kernels
 // share the block codec's device code (block_codec_device.hpp), not its launch path.  The unit contains kernels only -- every
@@ -396,6 +397,129 @@ __global__ __launch_bounds__(kThreads) void k_compress_slots_ex(SlotExArgs x)
     compress_block<SCHEME, MODE>(t, (2ull * x.a.layer_begin + w.j) * x.a.page_step + w.pair, src, lds, lane, wave);
 }
 
+// The two _ex kernels with a per-channel K factor (SlotKmulArgs, kernels.hpp), as overloads on the argument struct: the kernels of
+// this unit are the k_(read|compress)_(pairs|slots)[_ex] families and nothing else (tests/test_commit_cpu.py reads the symbols).
+// The waves, their work and every address are the _ex kernels'; a K wave (j & 1 == 0: blockIdx and the wave number alone) takes the
+// scaled sink or source with the factor row of its layer, a V wave the sink or source of the _ex kernels and loads no factor.
+// The decoders of a page entry, told where the rows go: here one device function for the two sinks of a kernel (the text that
+// stands three times above, for the reason given in k_read_pairs).
+template <int SCHEME, int MODE, class SINK>
+__device__ __forceinline__ void decode_entry(const PageEntry& e, const SINK& dst, uint32_t* lds, uint32_t wave, uint32_t lane)
+{
+    const uint8_t* rec = reinterpret_cast<const uint8_t*>(e.pool_addr);
+    uint32_t len = e.rec_bytes;
+    if (SCHEME == kInt8DeltaRle) {
+        if (len > 2u * kBlockElems) len = 2u * kBlockElems;
+        uint32_t* region = lds + wave * kDecLdsWords;
+        if (!decode_rle_fast<MODE, false, false, SINK>(rec, len, e.scale, dst, reinterpret_cast<uint8_t*>(region), lane, true))
+            decode_rle_general_to<MODE, false, SINK>(rec, len, e.scale, dst, lane);
+    } else if (SCHEME == kInt8) {
+        decode_int8<MODE, false, SINK>(rec, len > kBlockElems ? kBlockElems : len, e.scale, dst, lane);
+    } else if (SCHEME == kInt4G32) {
+        decode_int4<false, SINK>(rec, len, dst, lane);
+    } else if (SCHEME == kMxFp4) {
+        decode_mx4<false, SINK>(rec, rec + __float_as_uint(e.scale), len, dst, lane);
+    } else if (SCHEME == kFp8E4m3) {
+        decode_fp8<false, SINK>(rec, len > kBlockElems ? kBlockElems : len, e.scale, dst, lane);
+    } else {
+        decode_fp16<false, SINK>(rec, len > 2u * kBlockElems ? 2u * kBlockElems : len, dst, lane);
+    }
+}
+// move_row for a K row: every element times the factor of its channel, rounded once to the destination's type (src == nullptr:
+// zeros, as they are)
+__device__ __forceinline__ void move_row_mul(const uint8_t* src, uint8_t* dst, const uint8_t* mul, uint32_t lane, int conv)
+{
+#pragma unroll
+    for (uint32_t h = 0; h < 2u; ++h) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (src) {
+            v = ld16(src + 1024u * h + 16u * lane);
+            const uint4 m = ld16(mul + 1024u * h + 16u * lane);
+            v = conv == kMoveToBf16 ? mul_half8_to_bf16(v, m) : conv == kMoveFromBf16 ? mul_bf16_to_half8(v, m) : mul_half8(v, m);
+        }
+        st16(dst + 1024u * h + 16u * lane, v);
+    }
+}
+
+template <int SCHEME, int MODE, bool BF16>
+__global__ __launch_bounds__(kThreads) void k_read_slots_ex(SlotKmulArgs y)
+{
+    typedef typename std::conditional<BF16, RowSinkBf16, RowSink>::type Sink;
+    typedef typename std::conditional<BF16, RowSinkBf16Mul, RowSinkMul>::type SinkMul;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[SCHEME == kInt8DeltaRle ? kWaves * kDecLdsWords : 4];
+    const SlotExArgs& x = y.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
+    const uint64_t n_dec = static_cast<uint64_t>(x.a.n_pairs) * 2u * x.a.n_layers;
+    if (i >= n_dec) {                                                // a held row into the slot of the span's last position
+        const uint64_t m = i - n_dec;
+        uint8_t *held_row = nullptr, *cache_row = nullptr;
+        if (!move_work(x, m, false, &held_row, &cache_row) || !cache_row) return;
+        const uint32_t j = static_cast<uint32_t>(m % (2u * x.a.n_layers));
+        if (j & 1u) move_row(held_row, cache_row, lane, BF16 ? kMoveToBf16 : kMoveCopy);
+        else move_row_mul(held_row, cache_row, y.k_mul + static_cast<uint64_t>(j >> 1) * y.k_mul_stride, lane, BF16 ? kMoveToBf16 : kMoveCopy);
+        return;
+    }
+    SlotWork w;
+    if (!slot_work(x.a, wave, &w)) return;
+    uint8_t* const base = const_cast<uint8_t*>(w.base);
+    uint8_t* const even = w.slot[0] >= 0 ? base + static_cast<uint64_t>(w.slot[0]) * 2048u : nullptr;
+    uint8_t* const odd = w.slot[1] >= 0 ? base + static_cast<uint64_t>(w.slot[1]) * 2048u : nullptr;
+    if (!even && !odd) return;
+    const PageEntry* entries = x.a.tab[w.g->table_row].entries;
+    PageEntry e{0, 0, 1.0f};
+    if (entries) e = entries[(2ull * x.a.layer_begin + w.j) * x.a.page_step + w.pair];
+    if (w.j & 1u) decode_entry<SCHEME, MODE, Sink>(e, Sink{even, odd}, lds, wave, lane);
+    else decode_entry<SCHEME, MODE, SinkMul>(e, SinkMul{even, odd, y.k_mul + static_cast<uint64_t>(w.j >> 1) * y.k_mul_stride}, lds, wave, lane);
+}
+
+template <int SCHEME, int MODE>
+__global__ __launch_bounds__(kThreads) void k_compress_slots_ex(SlotKmulArgs y)
+{
+    SPECKV_ENC_LDS(SCHEME);
+    const SlotExArgs& x = y.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint32_t uwave = __builtin_amdgcn_readfirstlane(wave);
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + uwave;
+    const uint64_t n_enc = static_cast<uint64_t>(x.a.n_pairs) * 2u * x.a.n_layers;
+    const bool bf16 = x.bf16 != 0u;
+    if (i >= n_enc) {                                                // the span's last position into its held row (no row: zeros)
+        const uint64_t m = i - n_enc;
+        uint8_t *held_row = nullptr, *cache_row = nullptr;
+        if (!move_work(x, m, true, &held_row, &cache_row)) return;
+        const uint32_t j = static_cast<uint32_t>(m % (2u * x.a.n_layers));
+        if (j & 1u) move_row(cache_row, held_row, lane, bf16 ? kMoveFromBf16 : kMoveCopy);
+        else move_row_mul(cache_row, held_row, y.k_mul + static_cast<uint64_t>(j >> 1) * y.k_mul_stride, lane, bf16 ? kMoveFromBf16 : kMoveCopy);
+        return;
+    }
+    SlotWork w;
+    if (!slot_work(x.a, uwave, &w)) return;
+    const uint8_t* lo = w.slot[0] >= 0 ? w.base + static_cast<uint64_t>(w.slot[0]) * 2048u : nullptr;      // nullptr: a padding slot
+    const uint8_t* const hi = w.slot[1] >= 0 ? w.base + static_cast<uint64_t>(w.slot[1]) * 2048u : nullptr;
+    bool lo_cache = lo != nullptr;                                   // the row is read from the cache: bf16 where the cache is, K scaled
+    if (x.held && 2u * w.pair < w.g->first_token) {                  // the pair begins one position in front of the span: its held row
+        const uint64_t h = x.held[w.g - x.a.spans].in[w.j & 1u];
+        if (h) {
+            lo = reinterpret_cast<const uint8_t*>(h) + static_cast<uint64_t>(w.j >> 1) * x.held_stride;
+            lo_cache = false;
+        }
+    }
+    PageEntry* entries = w.g->entries;
+    __builtin_assume(entries != nullptr);
+    const EncTarget t{entries, w.g->scale_tab, w.g->region_pages, w.g->scale_run, nullptr, nullptr, 0, nullptr, nullptr};
+    const uint64_t page = (2ull * x.a.layer_begin + w.j) * x.a.page_step + w.pair;
+    if (w.j & 1u) {
+        const SrcPairMixed src{lo ? lo : x.a.zeros, hi ? hi : x.a.zeros, bf16 && lo_cache, bf16 && hi != nullptr};
+        compress_block<SCHEME, MODE>(t, page, src, lds, lane, wave);
+    } else {
+        const uint8_t* mul = y.k_mul + static_cast<uint64_t>(w.j >> 1) * y.k_mul_stride;
+        const SrcPairScaled src{lo ? lo : x.a.zeros, hi ? hi : x.a.zeros, bf16 && lo_cache, bf16 && hi != nullptr, lo_cache ? mul : nullptr, hi ? mul : nullptr};
+        compress_block<SCHEME, MODE>(t, page, src, lds, lane, wave);
+    }
+}
+
 // what both launchers ask of a SlotExArgs; *grid = one page or one moved row per wave, 0 = nothing to do
 bool slot_ex_args_ok(const SlotExArgs& x, uint32_t* grid)
 {
@@ -430,6 +554,35 @@ hipError_t launch_read_slots_ex(const SlotExArgs& x, hipStream_t s)
         constexpr int SCHEME = decltype(scheme)::value, MODE = decltype(mode)::value;
         if (x.bf16) hipLaunchKernelGGL((k_read_slots_ex<SCHEME, MODE, true>), dim3(grid), dim3(kThreads), 0, s, x);
         else hipLaunchKernelGGL((k_read_slots_ex<SCHEME, MODE, false>), dim3(grid), dim3(kThreads), 0, s, x);
+        return hipGetLastError();
+    });
+}
+
+// The _ex launches with the K factor: what the _ex launchers ask, and a factor table that 16-byte loads can read
+hipError_t launch_compress_slots_kmul(const SlotKmulArgs& y, hipStream_t s)
+{
+    if (y.x.a.n_layers == 0) return hipSuccess;
+    uint32_t grid = 0;
+    if (!slot_ex_args_ok(y.x, &grid) || !y.x.a.zeros) return hipErrorInvalidValue;
+    if (!y.k_mul || reinterpret_cast<uintptr_t>(y.k_mul) % 16u || y.k_mul_stride % 16u) return hipErrorInvalidValue;
+    if (grid == 0) return hipSuccess;
+    return by_scheme_mode<true>(y.x.a.scheme, y.x.a.quant_mode, [&](auto scheme, auto mode) {
+        hipLaunchKernelGGL((k_compress_slots_ex<decltype(scheme)::value, decltype(mode)::value>), dim3(grid), dim3(kThreads), 0, s, y);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_read_slots_kmul(const SlotKmulArgs& y, hipStream_t s)
+{
+    if (y.x.a.n_layers == 0) return hipSuccess;
+    uint32_t grid = 0;
+    if (!slot_ex_args_ok(y.x, &grid) || !y.x.a.tab) return hipErrorInvalidValue;
+    if (!y.k_mul || reinterpret_cast<uintptr_t>(y.k_mul) % 16u || y.k_mul_stride % 16u) return hipErrorInvalidValue;
+    if (grid == 0) return hipSuccess;
+    return by_scheme_mode<false>(y.x.a.scheme, y.x.a.quant_mode, [&](auto scheme, auto mode) {
+        constexpr int SCHEME = decltype(scheme)::value, MODE = decltype(mode)::value;
+        if (y.x.bf16) hipLaunchKernelGGL((k_read_slots_ex<SCHEME, MODE, true>), dim3(grid), dim3(kThreads), 0, s, y);
+        else hipLaunchKernelGGL((k_read_slots_ex<SCHEME, MODE, false>), dim3(grid), dim3(kThreads), 0, s, y);
         return hipGetLastError();
     });
 }

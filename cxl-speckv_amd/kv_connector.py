@@ -41,7 +41,9 @@ paged-attention layer would talk to for a BATCH of requests:
                                slot mapping on the device): spans of positions of a batch of requests decoded into their slots, or encoded
                                from them, by one launch each way (``speckv_ext_read_slots`` / ``speckv_ext_write_slots``; ``paged_spans``);
                                ``fused=True``: bf16 caches and odd lengths in the same launch, the tail as a held row
-                               (``speckv_ext_read_slots_ex`` / ``speckv_ext_write_slots_ex``)
+                               (``speckv_ext_read_slots_ex`` / ``speckv_ext_write_slots_ex``); ``kscale=True`` on top: a connector with a K
+                               pre-scale takes that launch too, the factor applied inside it (``speckv_ext_read_slots_kmul`` /
+                               ``speckv_ext_write_slots_kmul``)
 
 Only plain device pointers cross into the library; torch is used for device buffers and the tail fold.
 """
@@ -418,12 +420,13 @@ class SpeckvKVConnector:
             prefix += n
         return out
 
-    def _paged_geometry(self, caches, bf16=False):
+    def _paged_geometry(self, caches, bf16=False, kscale=False):
         """(slots per cache, bytes between the K and the V plane) if the one-launch route can address `caches` -- per layer a
         [2, blocks, block_size, heads, dim] fp16 tensor whose slots are 2048-byte rows one after the other -- else None.
-        bf16=True (the fused route): the caches may all be bfloat16 instead, and the element type (SLOT_ELEM_*) comes third."""
+        bf16=True (the fused route): the caches may all be bfloat16 instead, and the element type (SLOT_ELEM_*) comes third.
+        kscale=True (the fused route with the factor inside the launch): a K pre-scale does not shut the route."""
         import torch
-        if self._kscale is not None or len(caches) != self.L:
+        if (self._kscale is not None and not kscale) or len(caches) != self.L:
             return None
         geo = None
         dtype = caches[0].dtype if bf16 and len(caches) and caches[0].dtype == torch.bfloat16 else torch.float16
@@ -474,7 +477,8 @@ class SpeckvKVConnector:
             at += c
         return reqs, counts, begins
 
-    def load_paged(self, req_ids: Sequence[int], firsts: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None, fused=False):
+    def load_paged(self, req_ids: Sequence[int], firsts: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None, fused=False,
+                   kscale=False):
         """Pool -> paged caches: positions [firsts[i], firsts[i] + counts[i]) of request req_ids[i] go into the slots
         slot_mapping[b_i : b_i + counts[i]] (b_i = the counts in front: ONE int64 device tensor for the call, the spans concatenated) of
         `caches`, the per-layer [2, blocks, block_size, 8, 128] fp16 tensors.  ONE speckv_ext_read_slots call decodes every stored row
@@ -485,7 +489,11 @@ class SpeckvKVConnector:
         that includes bf16 caches).
         fused=True: bf16 caches of that geometry take the one-launch route as well (the decoded fp16 value rounded once to bf16:
         kv_rows(...).to(bfloat16)), and the tail is handed to the launch as a held row: exactly ONE speckv_ext_read_slots_ex call,
-        no torch copy per request.  The K pre-scale, other dtypes and other strides still go the row route."""
+        no torch copy per request.  The K pre-scale, other dtypes and other strides still go the row route.
+        kscale=True on top of fused=True: a connector with a K pre-scale takes the one launch as well -- ONE
+        speckv_ext_read_slots_kmul call, every K element multiplied by its channel's scale inside the kernel (the exact product
+        rounded once to the caches' element type: with fp16 caches the row route's bits), the tail as a held row.  Without a
+        pre-scale the keyword changes nothing."""
         import numpy as np
         import torch
         reqs, counts, begins = self._paged_args(req_ids, counts, slot_mapping, caches)
@@ -495,21 +503,24 @@ class SpeckvKVConnector:
         for r, f, c in zip(reqs, firsts, counts):
             if not 0 <= f <= f + c <= r.length:
                 raise ValueError(f"rows [{f}, {f + c}) of a request with {r.length} positions")
-        geo = self._paged_geometry(caches, bf16=True) if fused else None
+        geo = self._paged_geometry(caches, bf16=True, kscale=bool(kscale)) if fused else None
         if geo is not None:
             n_slots, kind_stride, elem = geo
             held, any_held = np.zeros(2 * len(reqs), dtype=np.uint64), False
+            read, factor = self.lib.read_slots_ex, {}
+            if self._kscale is not None:                                      # back to the caller's scaling inside the launch
+                read, factor = self.lib.read_slots_kmul, dict(k_mul=self._kscale.data_ptr(), k_mul_stride=self.H * self.D * 2)
             for i, (r, f, c) in enumerate(zip(reqs, firsts, counts)):
                 if c and (r.length & 1) and f + c == r.length:                # the span ends on the tail: a held row
                     held[2 * i], held[2 * i + 1], _ = self._held_tail(r)
                     any_held = True
             if any(counts):
                 with self._On(self, stream) as st:
-                    self.lib.read_slots_ex(np.asarray([r.handle for r in reqs], dtype=np.uint64), np.asarray(firsts, dtype=np.uint64),
-                                           np.asarray(counts, dtype=np.uint64), np.asarray(begins, dtype=np.uint64), slot_mapping.data_ptr(),
-                                           n_slots, np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride,
-                                           self.region_pages, st.cuda_stream, elem=elem, held_in=held if any_held else None,
-                                           held_stride=self.H * self.D * 2)
+                    read(np.asarray([r.handle for r in reqs], dtype=np.uint64), np.asarray(firsts, dtype=np.uint64),
+                         np.asarray(counts, dtype=np.uint64), np.asarray(begins, dtype=np.uint64), slot_mapping.data_ptr(),
+                         n_slots, np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride,
+                         self.region_pages, st.cuda_stream, elem=elem, held_in=held if any_held else None,
+                         held_stride=self.H * self.D * 2, **factor)
             return
         geo = self._paged_geometry(caches)
         if geo is None:
@@ -538,7 +549,7 @@ class SpeckvKVConnector:
                             cache[0].view(n_slots, self.H, self.D).index_copy_(0, at, r.tail_k[layer][None])
                             cache[1].view(n_slots, self.H, self.D).index_copy_(0, at, r.tail_v[layer][None])
 
-    def store_paged(self, req_ids: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None, fused=False):
+    def store_paged(self, req_ids: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None, fused=False, kscale=False):
         """Paged caches -> pool: request req_ids[i], whose current length is even (an odd one raises ValueError: not built), gets
         counts[i] more positions, read from the slots slot_mapping[b_i : b_i + counts[i]] of `caches` (as load_paged).  ONE
         speckv_ext_write_slots call encodes the whole pairs of every layer straight from the caches -- no gathered copy exists, so
@@ -553,13 +564,17 @@ class SpeckvKVConnector:
         row that completes its pair, a new odd last position comes back through held rows -- one [tails][layers][heads][dim] fp16
         tensor per kind for the call, installed as the batched tails a lockstep append pairs without per-request views.  Exactly
         ONE speckv_ext_write_slots_ex call and no torch copy per request; returns the tails the launch read.  On the row route (K
-        pre-scale, other dtypes or strides) an odd length still raises."""
+        pre-scale, other dtypes or strides) an odd length still raises.
+        kscale=True on top of fused=True: a connector with a K pre-scale takes the one launch too -- ONE speckv_ext_write_slots_kmul
+        call, every K element of a cache row divided by its channel's scale inside the kernel (times the power-of-two inverse, the
+        exact product rounded once to fp16: from a bf16 cache ONE rounding where the row route rounds twice), tails as held rows,
+        which hold pre-scaled K like every tail.  Without a pre-scale the keyword changes nothing."""
         import numpy as np
         import torch
         reqs, counts, begins = self._paged_args(req_ids, counts, slot_mapping, caches)
         if len(set(req_ids)) != len(reqs):
             raise ValueError("store_paged: a request named twice")
-        geo = self._paged_geometry(caches, bf16=True) if fused else None
+        geo = self._paged_geometry(caches, bf16=True, kscale=bool(kscale)) if fused else None
         for r, c in zip(reqs, counts):
             if r.length & 1 and geo is None:
                 raise ValueError("store_paged on a request of odd length")
@@ -570,6 +585,9 @@ class SpeckvKVConnector:
             n = len(reqs)
             h_in, h_out, read, tails = np.zeros(2 * n, dtype=np.uint64), np.zeros(2 * n, dtype=np.uint64), [], []
             first = [r.length if c else r.length & ~1 for r, c in zip(reqs, counts)]      # (an empty span names an even position)
+            write, factor = self.lib.write_slots_ex, {}
+            if self._kscale_inv is not None:                                  # into the pool's scaling inside the launch
+                write, factor = self.lib.write_slots_kmul, dict(k_mul=self._kscale_inv.data_ptr(), k_mul_stride=self.H * self.D * 2)
             for i, (r, c) in enumerate(zip(reqs, counts)):
                 if c and r.length & 1:
                     h_in[2 * i], h_in[2 * i + 1], keep = self._held_tail(r)
@@ -586,11 +604,11 @@ class SpeckvKVConnector:
                     for j, i in enumerate(tails):
                         h_out[2 * i], h_out[2 * i + 1] = tk.data_ptr() + j * row, tv.data_ptr() + j * row
                 if any(counts):
-                    self.lib.write_slots_ex(np.asarray([r.handle for r in reqs], dtype=np.uint64), np.asarray(first, dtype=np.uint64),
-                                            np.asarray(counts, dtype=np.uint64), np.asarray(begins, dtype=np.uint64), slot_mapping.data_ptr(),
-                                            n_slots, np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride,
-                                            self.region_pages, st.cuda_stream, elem=elem, held_in=h_in if read else None,
-                                            held_stride=self.H * self.D * 2, held_out=h_out if tails else None)
+                    write(np.asarray([r.handle for r in reqs], dtype=np.uint64), np.asarray(first, dtype=np.uint64),
+                          np.asarray(counts, dtype=np.uint64), np.asarray(begins, dtype=np.uint64), slot_mapping.data_ptr(),
+                          n_slots, np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride,
+                          self.region_pages, st.cuda_stream, elem=elem, held_in=h_in if read else None,
+                          held_stride=self.H * self.D * 2, held_out=h_out if tails else None, **factor)
             touched = [rid for rid, c in zip(req_ids, counts) if c]
             for r, c in zip(reqs, counts):
                 if c:

@@ -84,6 +84,10 @@ _EXT_SIGNATURES = {
                                  c_uint64, c_void_p, c_void_p],
     "speckv_ext_write_slots_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint64,
                                   c_uint64, c_void_p, c_void_p],
+    "speckv_ext_read_slots_kmul": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint64,
+                                   c_uint64, c_void_p, c_void_p, c_uint64, c_void_p],
+    "speckv_ext_write_slots_kmul": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint64,
+                                    c_uint64, c_void_p, c_void_p, c_uint64, c_void_p],
     "speckv_ext_copy_runs": [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
     "speckv_ext_attend_chunk": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                 c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
@@ -363,7 +367,7 @@ class SpeckvLib:
                     page_step, stream)
 
     def _slots_ex(self, entry, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step,
-                  stream, elem, held_in, held_out, held_stride, reserved=0):
+                  stream, elem, held_in, held_out, held_stride, reserved=0, k_mul=()):
         n, nl = len(handles), len(caches)
         hs, fs, ns, bs = (as_arr(x, c_uint64, n) for x in (handles, first_tokens, n_tokens, slot_begins))
         hin = None if held_in is None else as_arr(held_in, c_uint64, 2 * n)            # (kept alive across the call)
@@ -371,7 +375,7 @@ class SpeckvLib:
         at = lambda a: None if a is None else (a.value if isinstance(a, c_void_p) else ctypes.addressof(a))
         rows = SlotRows(elem, reserved, at(hin), at(hout), held_stride)
         self._ext(entry, hs, fs, ns, bs, n, c_void_p(d_slots), n_slots, as_arr(caches, c_uint64, nl), layer_begin, nl, kind_stride, page_step,
-                  ctypes.cast(ctypes.pointer(rows), c_void_p), c_void_p(stream))
+                  ctypes.cast(ctypes.pointer(rows), c_void_p), *k_mul, c_void_p(stream))     # k_mul: the _kmul entries' two arguments
 
     def read_slots_ex(self, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step,
                       stream, elem=SLOT_ELEM_FP16, held_in=None, held_stride=0, held_out=None, reserved=0):
@@ -390,6 +394,23 @@ class SpeckvLib:
         read_slots_ex."""
         self._slots_ex("speckv_ext_write_slots_ex", handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin,
                        kind_stride, page_step, stream, elem, held_in, held_out, held_stride, reserved)
+
+    def read_slots_kmul(self, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step,
+                        stream, elem=SLOT_ELEM_FP16, held_in=None, held_stride=0, held_out=None, reserved=0, k_mul=0, k_mul_stride=0):
+        """read_slots_ex with a per-channel factor on K (speckv_ext_read_slots_kmul): k_mul = the device address of fp16 [heads][128]
+        factor rows, the row of layer layer_begin + l at + l * k_mul_stride bytes; every decoded K element (the fp16 bits fetch_range
+        writes) and every K element of a held-in row is multiplied by its channel's factor, the exact product rounded once to `elem`.
+        V is not touched.  k_mul = 0 (None): the read_slots_ex call."""
+        self._slots_ex("speckv_ext_read_slots_kmul", handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin,
+                       kind_stride, page_step, stream, elem, held_in, held_out, held_stride, reserved, (c_void_p(k_mul or None), k_mul_stride))
+
+    def write_slots_kmul(self, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step,
+                         stream, elem=SLOT_ELEM_FP16, held_in=None, held_stride=0, held_out=None, reserved=0, k_mul=0, k_mul_stride=0):
+        """write_slots_ex with a per-channel factor on K (speckv_ext_write_slots_kmul): what is encoded, and what goes into a held-out
+        row, is fp16(cache element * factor) -- the exact product of the fp16 or bf16 element rounded once; a held-in row is pool-side
+        already and is not multiplied.  Arguments as read_slots_kmul."""
+        self._slots_ex("speckv_ext_write_slots_kmul", handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin,
+                       kind_stride, page_step, stream, elem, held_in, held_out, held_stride, reserved, (c_void_p(k_mul or None), k_mul_stride))
 
     def copy_runs(self, src, dst, n_pages, run_firsts, stream):
         """The stored records of pages [run_firsts[r], run_firsts[r] + n_pages[i]), every run r, copied from allocation src[i] to the same

@@ -28,6 +28,8 @@ between the pool and the registered caches (``speckv_ext_read_slots`` / ``speckv
 a fetch and a scatter per (request, layer, kind), a gathered copy of every prompt held until its write has run.
 ``paged_fused=True`` on top of it passes ``fused=True`` to both calls (``speckv_ext_read_slots_ex`` / ``speckv_ext_write_slots_ex``):
 bf16 caches take the one-launch route too, and the odd last position of a prompt moves inside the launch.
+``paged_kscale=True`` on top of both passes ``kscale=True`` as well (``speckv_ext_read_slots_kmul`` / ``speckv_ext_write_slots_kmul``):
+a pool with a K pre-scale (``conn.set_k_channel_scale``) keeps the one-launch route, the factor applied inside the launch.
 """
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -88,7 +90,8 @@ def _cached_requests(scheduler_output):
 
 class SpeckvVllmConnector:
     def __init__(self, lib, num_layers: int, num_kv_heads: int = 8, head_dim: int = 128, block_size: int = 16,
-                 max_tokens: int = 4096, scheme: str = "fp16", paged_io: bool = False, paged_fused: bool = False):
+                 max_tokens: int = 4096, scheme: str = "fp16", paged_io: bool = False, paged_fused: bool = False,
+                 paged_kscale: bool = False):
         # worker role: the pool.  lib=None builds a scheduler-role object (no GPU, no library)
         self.conn = None if lib is None else SpeckvKVConnector(lib, num_layers=num_layers, num_kv_heads=num_kv_heads, head_dim=head_dim,
                                                                 max_tokens=max_tokens, scheme=scheme)
@@ -99,6 +102,10 @@ class SpeckvVllmConnector:
         # paged_fused (with paged_io): both calls get fused=True -- bf16 caches take the one-launch route as well, and an odd last
         # position moves inside the launch
         self._fused = {"fused": True} if paged_fused else {}
+        # paged_kscale (with paged_fused): both calls get kscale=True too -- a K pre-scale is applied inside the launch instead of
+        # shutting the one-launch route
+        if paged_fused and paged_kscale:
+            self._fused["kscale"] = True
         # ---- scheduler-role state (never read by the worker-role methods)
         self._ids: Dict[str, int] = {}                     # vLLM request id (a string) -> the engine's request id
         self._next_id = 1

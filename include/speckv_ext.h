@@ -212,8 +212,30 @@ speckv_status_t speckv_ext_write_slots(const speckv_handle_t* handles, const uin
  *                       for an empty span; read: d_held_out not NULL, held-in on a span whose last position is odd; write: an odd
  *                       first without held-in or held-in with an even first, an odd first + n without held-out or held-out with an
  *                       even first + n
- * Every refusal launches nothing and leaves the held-out rows untouched.  Not built: capture into a HIP graph, a K pre-scale,
- * rows of any other size than 2048 bytes. */
+ * Every refusal launches nothing and leaves the held-out rows untouched.  Not built: capture into a HIP graph, rows of any other
+ * size than 2048 bytes.
+ * The _kmul entries below are the _ex entries with a per-channel factor on K (a K pre-scale: K / scale in the pool, q * scale against
+ * it).  d_k_mul is a DEVICE pointer to fp16 [heads][128] factor rows (2048 bytes), the row of layer layer_begin + l at d_k_mul +
+ * l * k_mul_layer_stride_bytes -- relative to layer_begin like d_caches and the held rows.  With d_k_mul == NULL each _kmul entry IS
+ * the _ex entry: the same refusals, the same kernel instances, the same bits and statistics.  Otherwise, the one rule: every K
+ * element that crosses the boundary between a cache row and the pool side is multiplied by the factor of its (layer, head,
+ * channel).  Records and held rows are the pool side (a held row is a tail, and tails hold pre-scaled K).  The product is taken
+ * exactly in fp32 (fp16 x fp16 and bf16 x fp16 are exact there) and THAT is rounded once, to nearest even, to the destination's
+ * element type -- well defined for any finite factor, not only powers of two.  V is never touched.  Element p of a page block takes
+ * factor element p & 1023: the two position rows of a page share the factor row.
+ *   write, cache row -> record   the encoder sees fp16_rne(float(x) * float(m)) of the fp16 or bf16 cache element x (for bf16 ONE
+ *                                rounding, not bf16 -> fp16 -> scaled); the record is the one speckv_ext_write_runs stores for those
+ *                                rows.  A slot that names no row reads zeros as above.
+ *   write, held-in row           pool-side already: encoded as it is, not multiplied.
+ *   write, held-out row          K is multiplied and rounded to fp16; V is copied or converted as above.
+ *   read, record -> cache row    the decoded fp16 value -- the bits speckv_ext_fetch_range writes, never the decoder's fp32
+ *                                intermediate -- is multiplied by m and rounded once to fp16 or bf16.
+ *   read, held-in row -> slot    K is multiplied and rounded to the caches' element type; V goes as above.
+ * With fp16 caches the bits are those of a half-precision multiply of the row (IEEE: the exact product rounded once).
+ *   SPECKV_ERR_INVAL    everything the _ex entries refuse with it, and: d_k_mul not 16-byte aligned, k_mul_layer_stride_bytes not
+ *                       a multiple of 16 (with d_k_mul set)
+ * Every refusal launches nothing and leaves the held-out rows untouched.  The factor rows must stay alive and unchanged until the
+ * stream has passed the call. */
 #define SPECKV_SLOT_ELEM_FP16 0u
 #define SPECKV_SLOT_ELEM_BF16 1u
 typedef struct {
@@ -235,6 +257,22 @@ speckv_status_t speckv_ext_write_slots_ex(const speckv_handle_t* handles, const 
                                           const void* const* d_caches /* host array of n_layers device pointers */,
                                           uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
                                           uint64_t page_step, const speckv_ext_slot_rows_t* rows, void* stream);
+speckv_status_t speckv_ext_read_slots_kmul(const speckv_handle_t* handles, const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                           const uint64_t* slot_begins, uint32_t n_spans,
+                                           const int64_t* d_slots /* device */, uint64_t n_slots,
+                                           void* const* d_caches /* host array of n_layers device pointers */,
+                                           uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                           uint64_t page_step, const speckv_ext_slot_rows_t* rows,
+                                           const void* d_k_mul /* device, fp16 [heads][128] per layer, or NULL */,
+                                           uint64_t k_mul_layer_stride_bytes, void* stream);
+speckv_status_t speckv_ext_write_slots_kmul(const speckv_handle_t* handles, const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                            const uint64_t* slot_begins, uint32_t n_spans,
+                                            const int64_t* d_slots /* device */, uint64_t n_slots,
+                                            const void* const* d_caches /* host array of n_layers device pointers */,
+                                            uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                            uint64_t page_step, const speckv_ext_slot_rows_t* rows,
+                                            const void* d_k_mul /* device, fp16 [heads][128] per layer, or NULL */,
+                                            uint64_t k_mul_layer_stride_bytes, void* stream);
 /* Fork: the STORED RECORDS of page runs copied from one allocation to another, nothing decoded.  Pair i copies pages
  * [run_firsts[r], run_firsts[r] + n_pages[i]) for every run r < n_runs from allocation src[i] to the same page numbers of
  * allocation dst[i] (in the shim layout the runs are the 2 * num_layers (layer, kind) regions and n_pages[i] = positions / 2: a

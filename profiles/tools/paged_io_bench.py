@@ -22,6 +22,12 @@ _write_slots_ex) on bf16 caches, in the same process and alternating with
   bf16 rows    the row route bf16 caches take without fused=True;
 and, for stores, a request that holds one position already and gets n - 2 more (its tail goes in as the held-in row, the new odd
 last position comes back as a held-out row) against the even store of n - 2 positions into an empty request.
+
+--kscale (profiles/paged_io_kscale.txt): a connector with a K pre-scale on the one launch (load_paged / store_paged with fused=True,
+kscale=True: speckv_ext_read_slots_kmul / _write_slots_kmul), on fp16 and on bf16 caches, in the same process and alternating with
+  fused        the unscaled fused call of a connector without a pre-scale on the same caches (the _ex kernels: equal bytes, so a
+               gap is the factor's load and multiply on the K waves);
+  kscale rows  the row route the pre-scaled connector takes for the same call without kscale=True.
 """
 import argparse
 import os
@@ -33,7 +39,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 REC_BYTES = {"fp8": 2048, "int4": 1152, "mxfp4": 1088}
 SHAPES = ((4, 8192), (1, 32768))
 BS = 16
-COUNTED = ("read_slots", "write_slots", "read_slots_ex", "write_slots_ex", "fetch_range", "write_runs")
+COUNTED = ("read_slots", "write_slots", "read_slots_ex", "write_slots_ex", "read_slots_kmul", "write_slots_kmul", "fetch_range", "write_runs")
 
 
 class Counting:
@@ -264,6 +270,96 @@ def bench_bf16(scheme, B, n, a, say):
         lib.finalize()
 
 
+def bench_kscale(scheme, B, n, a, say):
+    import numpy as np
+    import torch
+    import cxl_speckv_amd as pkg
+    from cxl_speckv_amd.kv_connector import SpeckvKVConnector
+
+    lib = Counting(pkg.SpeckvLib(pkg.library_path(), "hip:0"))
+    try:
+        H, D, L = 8, 128, a.layers
+        plain, scaled = SpeckvKVConnector(lib, L, H, D, n, scheme), SpeckvKVConnector(lib, L, H, D, n, scheme)
+        l, h, c = np.meshgrid(np.arange(L), np.arange(H), np.arange(D), indexing="ij")
+        scaled.set_k_channel_scale(torch.from_numpy(np.exp2(((7 * l + 3 * h + c) % 9) - 4).astype(np.float32)).cuda())
+        blocks = B * n // BS
+        c16 = [torch.randn((2, blocks, BS, H, D), device="cuda").half() for _ in range(L)]
+        cbf = [c.to(torch.bfloat16) for c in c16]
+        table = np.random.default_rng(1).permutation(blocks)
+        slots = (table[:, None] * BS + np.arange(BS)[None]).reshape(-1).astype(np.int64)
+        d_slots = torch.from_numpy(slots).cuda()
+        ids = list(range(1, B + 1))
+        st = torch.cuda.Stream()
+        for conn, kw in ((plain, dict(fused=True)), (scaled, dict(fused=True, kscale=True))):
+            for rid in ids:
+                conn.add_request(rid)
+            conn.store_paged(ids, [n] * B, d_slots, cbf, stream=st, **kw)
+        torch.cuda.synchronize()
+        fresh = iter(range(1000, 10 ** 9))
+
+        def load(conn, caches, **kw):
+            return lambda: conn.load_paged(ids, [0] * B, [n] * B, d_slots, caches, stream=st, fused=True, **kw)
+
+        def store(conn, caches, **kw):
+            def prepare():
+                new = [next(fresh) for _ in ids]
+                for rid in new:
+                    conn.add_request(rid)
+                return new
+
+            def run(new):
+                return conn.store_paged(new, [n] * B, d_slots, caches, stream=st, fused=True, **kw)
+            return prepare, run, conn
+
+        def timed(route):
+            prepare, run, owner = route if isinstance(route, tuple) else (None, route, None)
+            arg = prepare() if prepare else None
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            before = lib.n
+            e0.record(st)
+            keep = run(arg) if prepare else run()
+            e1.record(st)
+            torch.cuda.synchronize()
+            launches = lib.n - before
+            del keep
+            if prepare:
+                for rid in arg:
+                    owner.free_request(rid)
+            return e0.elapsed_time(e1), launches
+
+        loads, stores = {}, {}
+        for name, caches in (("fp16", c16), ("bf16", cbf)):
+            loads[f"{name} fused"], stores[f"{name} fused"] = load(plain, caches), store(plain, caches)
+            loads[f"{name} kscale"], stores[f"{name} kscale"] = load(scaled, caches, kscale=True), store(scaled, caches, kscale=True)
+            loads[f"{name} kscale rows"], stores[f"{name} kscale rows"] = load(scaled, caches), store(scaled, caches)
+        pages = B * 2 * L * (n // 2)
+        moved = pages * (REC_BYTES[scheme] + 4096)
+        say(f"{scheme}: {B} request(s) x {n} positions x {L} layers = {pages} pages, {moved / 1e9:.3f} GB of records + rows")
+        for what, routes in (("load", loads), ("store", stores)):
+            for r in routes.values():
+                timed(r)                                            # warm-up: allocator, staging ring, code objects
+            ms = {name: [] for name in routes}
+            launches = {}
+            for _ in range(a.rounds):
+                one = {name: [] for name in routes}
+                for _ in range(a.reps):
+                    for name, r in routes.items():                  # alternating
+                        t, launches[name] = timed(r)
+                        one[name].append(t)
+                for name in routes:
+                    ms[name].append(statistics.median(one[name]))
+            m = {name: statistics.median(v) for name, v in ms.items()}
+            for name in routes:
+                say(f"  {what:5s} {name:16s} {m[name]:9.3f} ms (medians {min(ms[name]):.3f} .. {max(ms[name]):.3f}), {launches[name]:4d} library launches, "
+                    f"{moved / (m[name] * 1e-3) / 8e12:.3f} of the 8 TB/s roofline")
+            for name in ("fp16", "bf16"):
+                say(f"  {what:5s} {name} kscale / {name} fused: {m[name + ' kscale'] / m[name + ' fused']:.3f}; "
+                    f"{name} kscale rows / {name} kscale: {m[name + ' kscale rows'] / m[name + ' kscale']:.2f}x")
+    finally:
+        lib.finalize()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=8)
@@ -273,6 +369,7 @@ def main():
     ap.add_argument("--shapes", default=",".join(f"{b}x{n}" for b, n in SHAPES))
     ap.add_argument("--out", default=None)
     ap.add_argument("--bf16", action="store_true", help="the fused route on bf16 caches (see the module's text)")
+    ap.add_argument("--kscale", action="store_true", help="a K pre-scale inside the fused route (see the module's text)")
     a = ap.parse_args()
     lines = []
 
@@ -282,7 +379,7 @@ def main():
     for shape in a.shapes.split(","):
         B, n = (int(x) for x in shape.split("x"))
         for scheme in a.schemes.split(","):
-            (bench_bf16 if a.bf16 else bench)(scheme, B, n, a, say)
+            (bench_kscale if a.kscale else bench_bf16 if a.bf16 else bench)(scheme, B, n, a, say)
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
