@@ -80,13 +80,18 @@
 // walks from chunk_window_first_pool_tile, the tile of depth 0's bound (n_pool where depth 0 sees no stored position), positions
 // below that bound are staged as zeros, and no wave skips a pool tile by a lower bound (the block-uniform bound, no per-wave skip).
 // Split form: the pieces cut the pool tiles from ChunkSeq::first_tile on and every block shares that tile, so no piece is empty.
+//
+// Split pool (KS != VS, ChunkArgs::v_scheme; speckv_ext_attend_chunk_kv: FP8 keys, MXFP4 values).  The same body with the scheme of the K
+// side (load_pool, decode_pool<.., true>, pool_k_scale, k_scale) and of the V side (load_pool, decode_pool) as two template parameters,
+// and the V pages addressed through the table of an allocation of their own (ChunkSeq::v_table_row).  With KS == VS the V table IS the
+// K table and the instances are the ones of one scheme, instruction for instruction.  (FP8, MXFP4) is the one mixed pair instantiated.
 #include "chunk_device.hpp"          // the LDS layout, Raw, load_pool, decode_pool, load_held (shared with attend_prefix.hip)
 #include "chunk_window.hpp"
 
 namespace speckv {
 namespace {
 
-template <int SCHEME, bool MASKED, bool SPLIT, bool WINDOW>
+template <int KS, int VS, bool MASKED, bool SPLIT, bool WINDOW>
 __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
 {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufElems];
@@ -136,6 +141,8 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     const uint32_t lo_held = !MASKED && lo_pool > pos_end ? lo_pool - pos_end : 0u;
 
     const PageEntry* entries = reinterpret_cast<const PageEntry*>(ck_uniform(reinterpret_cast<uint64_t>(a.tab[sq->table_row].entries)));
+    // the V pages' table: the same allocation's unless the schemes differ (the split pool: K and V in an allocation each)
+    const PageEntry* v_entries = KS == VS ? entries : reinterpret_cast<const PageEntry*>(ck_uniform(reinterpret_cast<uint64_t>(a.tab[sq->v_table_row].entries)));
     const uint64_t k_first = ck_uniform(sq->k_first), v_first = ck_uniform(sq->v_first);
     const int32_t tail_idx = __builtin_amdgcn_readfirstlane(sq->tail_idx);
     const uint64_t head_off = static_cast<uint64_t>(h) * 128u;
@@ -184,8 +191,8 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
         if (tile < n_pool) {
             const uint32_t page = 16u * tile + pp;
             const bool live = page < n_pages && (!WINDOW || 2u * page + 1u >= lo_pool);
-            rk = load_pool<SCHEME>(entries + k_first + page, p0, live);
-            rv = load_pool<SCHEME>(entries + v_first + page, p0, live);
+            rk = load_pool<KS>(entries + k_first + page, p0, live);
+            rv = load_pool<VS>(v_entries + v_first + page, p0, live);
         } else {
             const uint32_t t0 = 32u * (tile - n_pool) + 2u * pp;
             const _Float16 *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr;
@@ -200,10 +207,10 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
     };
     const auto store_tile = [&](uint32_t tile, _Float16* buf) {
         uint32_t ke[4], ko[4], ve[4], vo[4];
-        if (SCHEME == kFp8E4m3 && c == 0u) k_scale[buf != lds][pp] = tile < n_pool ? pool_k_scale<SCHEME>(rk) : 1.0f;
+        if (KS == kFp8E4m3 && c == 0u) k_scale[buf != lds][pp] = tile < n_pool ? pool_k_scale<KS>(rk) : 1.0f;
         if (tile < n_pool) {
-            decode_pool<SCHEME, true>(rk, p0, ke, ko);
-            decode_pool<SCHEME>(rv, p0, ve, vo);
+            decode_pool<KS, true>(rk, p0, ke, ko);
+            decode_pool<VS>(rv, p0, ve, vo);
             if (WINDOW && 2u * (16u * tile + pp) < lo_pool) {               // the page the bound cuts: its even position is below it
 #pragma unroll
                 for (uint32_t k = 0; k < 4u; ++k) ke[k] = ve[k] = 0u;
@@ -270,7 +277,7 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_chunk(ChunkArgs a)
 #pragma unroll
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t t = t_base + 16u * (i >> 2) + 4u * g + (i & 3u);
-                const float scale_i = SCHEME == kFp8E4m3 ? scale2 * ks[8u * (i >> 2) + 2u * g + ((i & 3u) >> 1)] : scale2;       // the position's page
+                const float scale_i = KS == kFp8E4m3 ? scale2 * ks[8u * (i >> 2) + 2u * g + ((i & 3u) >> 1)] : scale2;       // the position's page
                 // tree form: bit t & 31 of the word (t_base is a multiple of 32), the causal bound folded into the word
                 // (under a window too: a stored position also needs t >= the bound of the row's depth, a held one its bit alone)
                 const bool seen = MASKED ? ((vis >> (16u * (i >> 2) + (i & 3u))) & 1u) && (!WINDOW || held || t >= row_lo)
@@ -387,15 +394,15 @@ __global__ __launch_bounds__(kChunkThreads) void k_chunk_combine(ChunkArgs a)
 
 // The instance of a call, by what its arguments carry: a mask, a partial buffer (pieces: n_items work items and the merge behind
 // them; otherwise n_blocks query blocks), a window.
-template <int SCHEME>
+template <int KS, int VS = KS>
 hipError_t launch_chunk(const ChunkArgs& a, hipStream_t s)
 {
     using Kernel = void (*)(ChunkArgs);
     static constexpr Kernel kInstance[2][2][2] = {                 // [MASKED][SPLIT][WINDOW]
-        {{k_attend_chunk<SCHEME, false, false, false>, k_attend_chunk<SCHEME, false, false, true>},
-         {k_attend_chunk<SCHEME, false, true, false>, k_attend_chunk<SCHEME, false, true, true>}},
-        {{k_attend_chunk<SCHEME, true, false, false>, k_attend_chunk<SCHEME, true, false, true>},
-         {k_attend_chunk<SCHEME, true, true, false>, k_attend_chunk<SCHEME, true, true, true>}}};
+        {{k_attend_chunk<KS, VS, false, false, false>, k_attend_chunk<KS, VS, false, false, true>},
+         {k_attend_chunk<KS, VS, false, true, false>, k_attend_chunk<KS, VS, false, true, true>}},
+        {{k_attend_chunk<KS, VS, true, false, false>, k_attend_chunk<KS, VS, true, false, true>},
+         {k_attend_chunk<KS, VS, true, true, false>, k_attend_chunk<KS, VS, true, true, true>}}};
     hipLaunchKernelGGL(kInstance[a.mask != nullptr][a.part != nullptr][a.window != 0u], dim3((a.part ? a.n_items : a.n_blocks) * a.heads),
                        dim3(kChunkThreads), 0, s, a);
     const hipError_t e = hipGetLastError();
@@ -414,6 +421,8 @@ hipError_t launch_attend_chunk(const ChunkArgs& a, hipStream_t s)
         (a.mask && a.mask_words < (a.C + 32u) / 32u) || (a.mask && a.window && !a.depth) || (a.depth && reinterpret_cast<uintptr_t>(a.depth) % 4u) ||
         (a.part && (a.n_items < a.n_blocks || static_cast<uint64_t>(a.n_items) * a.heads > 0x7FFFFFFFull || reinterpret_cast<uintptr_t>(a.part) % 16u)))
         return hipErrorInvalidValue;
+    // the one mixed pair: K pages of an FP8 allocation, V pages of an MXFP4 one (the K8V4 split pool; ChunkSeq::v_table_row)
+    if (a.v_scheme != a.scheme) return a.scheme == kFp8E4m3 && a.v_scheme == kMxFp4 ? launch_chunk<kFp8E4m3, kMxFp4>(a, s) : hipErrorInvalidValue;
     switch (a.scheme) {
     case kFp8E4m3: return launch_chunk<kFp8E4m3>(a, s);
     case kInt4G32: return launch_chunk<kInt4G32>(a, s);

@@ -889,7 +889,7 @@ uint64_t speckv_ext_pool_shard_pages(uint64_t n_pages, uint32_t n_pool, uint32_t
     return speckv::shard_pages(n_pages, n_pool, pool_index);
 }
 
-// The arguments all five chunk-attention entries share, under the names every entry gives them and in ChunkCall's order: an entry
+// The arguments all six chunk-attention entries share, under the names every entry gives them and in ChunkCall's order: an entry
 // starts its call description from them and sets the fields of its own form (otherwise whole sequences, no mask, no window).
 #define CHUNK_SHARED __func__, n_seq, handles, layer, d_q_f16, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride_elems, \
                      pos_stride_elems, tail_idx, d_k_tail, d_v_tail, tail_stride_elems, sm_scale, d_out, d_lse
@@ -955,6 +955,24 @@ speckv_status_t speckv_ext_attend_chunk_tree_window(uint32_t n_seq, const speckv
     speckv::Engine::ChunkCall c{CHUNK_SHARED};
     c.masked = true; c.d_mask = d_mask; c.mask_words = mask_words;                 // a NULL d_mask or d_depth is refused: this entry
     c.by_depth = true; c.d_depth = d_depth;                                        // has no causal form
+    c.n_splits = n_splits; c.window = window;
+    return guarded([&] { return g_engine->attend_chunk(c, static_cast<hipStream_t>(stream)); });
+}
+
+// the split pool: K regions in the FP8 allocations k_handles, V regions in the MXFP4 allocations v_handles; every form by its arguments
+speckv_status_t speckv_ext_attend_chunk_kv(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles, uint32_t layer,
+                                           const void* d_q_f16, uint32_t C, uint32_t rows_per_pos, const uint32_t* pos_end, const uint32_t* n_q,
+                                           const void* d_k_new, const void* d_v_new, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                                           const int32_t* tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,
+                                           const uint32_t* d_mask, uint32_t mask_words, const uint32_t* d_depth, uint32_t window,
+                                           uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    const speckv_handle_t* handles = k_handles;
+    speckv::Engine::ChunkCall c{CHUNK_SHARED};
+    c.split_kv = true; c.v_handles = v_handles;
+    c.masked = d_mask != nullptr; c.d_mask = d_mask; c.mask_words = mask_words;    // d_mask == NULL is the causal form: d_depth is ignored
+    c.by_depth = c.masked && window != 0u; c.d_depth = c.by_depth ? d_depth : nullptr;       // a tree under a window goes by depth
     c.n_splits = n_splits; c.window = window;
     return guarded([&] { return g_engine->attend_chunk(c, static_cast<hipStream_t>(stream)); });
 }

@@ -2,7 +2,8 @@
 // attend_prefix.hip: k_attend_prefix): the LDS layout of a tile, global-address-space loads and stores, the undecoded bytes a thread
 // keeps in flight for the next tile (Raw), and the three small decoders restated for ONE head's 8 elements of both positions of a
 // page; they give the fp16 values speckv_ext_fetch_range gives (the fp32 product rounded once to fp16, pack_half2) -- but for the K
-// rows of an FP8 pool, staged unscaled with the block scale applied to the score (decode_pool).  Device code only.
+// rows of an FP8 pool, staged unscaled with the block scale applied to the score (decode_pool).  The decoders take the scheme of ONE
+// side: k_attend_chunk names the K side's and the V side's apart (the split pool: FP8 keys, MXFP4 values).  Device code only.
 #pragma once
 #include "kernels.hpp"
 #include "codec_device.hpp"          // pack_half2, half_bits_to_float

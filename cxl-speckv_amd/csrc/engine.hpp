@@ -198,6 +198,8 @@ public:
         bool masked = false; const uint32_t* d_mask = nullptr; uint32_t mask_words = 0;
         bool by_depth = false; const uint32_t* d_depth = nullptr;
         uint32_t n_splits = 1, window = 0;
+        // speckv_ext_attend_chunk_kv: `handles` are the FP8 allocations of the K regions, these the MXFP4 allocations of the V regions
+        const uint64_t* v_handles = nullptr; bool split_kv = false;
     };
     int attend_chunk(const ChunkCall& c, hipStream_t s);
     // One shared-prefix call (speckv_ext_attend_prefix_fold / _fold_window), described above Engine::attend_prefix (engine_prefix.cpp);

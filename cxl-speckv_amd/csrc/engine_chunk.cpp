@@ -1,5 +1,5 @@
-// cxl-speckv_amd/csrc/engine_chunk.cpp -- Engine::attend_chunk, the one body behind speckv_ext_attend_chunk, _masked, _split, _window and
-// _tree_window: causal attention of a chunk of new positions per sequence over stored and held positions, one launch -- or, where the
+// cxl-speckv_amd/csrc/engine_chunk.cpp -- Engine::attend_chunk, the one body behind speckv_ext_attend_chunk, _masked, _split, _window,
+// _tree_window and _kv (the split pool: K and V pages in an allocation each): causal attention of a chunk of new positions per sequence over stored and held positions, one launch -- or, where the
 // stored positions are split across the chip, a piece launch and its merge (the kernels are in attend_chunk.hip)
 #include "engine_internal.hpp"
 #include "chunk_split.hpp"
@@ -75,9 +75,13 @@ bool plan_chunk(const Engine::ChunkCall& c, uint32_t n_cus, ChunkPlan& p)
 // read either array, so whether the window cuts anything is judged by the same rule as above -- a depth is below n_q -- and a window
 // that cuts nothing issues the unwindowed masked launch.  Otherwise the call runs on the MASKED + WINDOW instances: every block of a
 // sequence walks from first_tile (the first pool tile its position 0 sees).  A window with a mask that does not go by depth is refused.
+// `split_kv` (speckv_ext_attend_chunk_kv, the K8V4 split pool): handles[i] is an FP8_E4M3 allocation and v_handles[i] an MXFP4 one, both
+// laid out as regions of num_tokens / 2 pages: K of the layer = region `layer` of the first, V = region `layer` of the second.  The
+// one mixed pair of schemes the kernel has instances of; everything else -- plan, forms, ordering -- is the call of one allocation.
 int Engine::attend_chunk(const ChunkCall& c, hipStream_t s)
 {
     if (null_) return no_data_path(c.entry);
+    if (c.split_kv && !c.v_handles) return SPECKV_ERR_INVAL;
     if (!s || !c.handles || !c.pos_end || !c.n_q || !c.d_q_f16 || !c.d_k_new || !c.d_v_new || !c.d_out) return SPECKV_ERR_INVAL;
     if (c.rows_per_pos == 0 || c.rows_per_pos > 16u || (c.rows_per_pos & (c.rows_per_pos - 1u)) || c.C == 0) return SPECKV_ERR_INVAL;
     if (c.n_splits > kChunkSplitsMax) return SPECKV_ERR_INVAL;
@@ -103,9 +107,25 @@ int Engine::attend_chunk(const ChunkCall& c, hipStream_t s)
         return SPECKV_ERR_INVAL;
     }
     const uint32_t per_block = 64u / c.rows_per_pos;
-    std::vector<Allocation*> as(c.n_seq);
+    std::vector<Allocation*> as(c.n_seq), vs(c.split_kv ? c.n_seq : 0u);
     int scheme = -1;
+    // a region (num_tokens / 2 pages) of an allocation of the split pool: 8 x 128 fp16, region `layer` inside its pages
+    const auto region_ok = [&](const Allocation* a, int want, uint32_t pos_end) {
+        if (!a->has_layout || a->scheme != want) return false;
+        const Layout& L = a->layout;
+        if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads != 8 || L.num_tokens % 2 || pos_end > L.num_tokens) return false;
+        return (static_cast<uint64_t>(c.layer) + 1u) * (L.num_tokens / 2u) <= a->n_pages && c.layer < 2ull * L.num_layers;
+    };
     const auto check = [&]() -> int {
+        for (uint32_t i = 0; c.split_kv && i < c.n_seq; ++i) {
+            Allocation *k = find(c.handles[i]), *v = find(c.v_handles[i]);
+            if (!k || !v) return SPECKV_ERR_GENERAL;
+            if (!region_ok(k, SPECKV_COMP_FP8_E4M3, c.pos_end[i]) || !region_ok(v, SPECKV_COMP_MXFP4, c.pos_end[i]) ||
+                k->layout.num_tokens != v->layout.num_tokens)
+                return SPECKV_ERR_INVAL;
+            as[i] = k; vs[i] = v;
+        }
+        if (c.split_kv) { scheme = SPECKV_COMP_FP8_E4M3; return SPECKV_OK; }
         for (uint32_t i = 0; i < c.n_seq; ++i) {
             Allocation* a = find(c.handles[i]);
             if (!a) return SPECKV_ERR_GENERAL;
@@ -139,11 +159,14 @@ int Engine::attend_chunk(const ChunkCall& c, hipStream_t s)
     uint32_t first_block = 0, first_item = 0;
     for (uint32_t i = 0; i < c.n_seq; ++i) {
         const Layout& L = as[i]->layout;
-        const uint64_t k_first = static_cast<uint64_t>(c.layer) * L.num_tokens;
+        // split pool: region `layer` of either allocation; otherwise the layer's K region and the V region behind it
+        const uint64_t k_first = static_cast<uint64_t>(c.layer) * (c.split_kv ? L.num_tokens / 2u : L.num_tokens);
+        const uint64_t v_first = c.split_kv ? k_first : k_first + L.num_tokens / 2u;
         const int32_t tail = c.tail_idx && c.tail_idx[i] >= 0 ? c.tail_idx[i] : -1;
         const uint32_t blocks = (c.n_q[i] + per_block - 1u) / per_block;
-        static_cast<ChunkSeq*>(staged)[i] = ChunkSeq{as[i]->row, c.pos_end[i], c.n_q[i], first_block, k_first, k_first + L.num_tokens / 2u,
-                                                     tail, tail >= 0 ? 1u : 0u, plan.pieces[i], plan.tpp[i], first_item, plan.first_tile[i]};
+        static_cast<ChunkSeq*>(staged)[i] = ChunkSeq{as[i]->row, c.pos_end[i], c.n_q[i], first_block, k_first, v_first,
+                                                     tail, tail >= 0 ? 1u : 0u, plan.pieces[i], plan.tpp[i], first_item, plan.first_tile[i],
+                                                     c.split_kv ? vs[i]->row : as[i]->row};
         first_block += blocks;
         first_item += blocks * plan.pieces[i];
     }
@@ -170,6 +193,7 @@ int Engine::attend_chunk(const ChunkCall& c, hipStream_t s)
     ca.heads = 8;
     ca.sm_scale = c.sm_scale;
     ca.scheme = scheme;
+    ca.v_scheme = c.split_kv ? SPECKV_COMP_MXFP4 : scheme;
     ca.mask = c.masked ? c.d_mask : nullptr;
     ca.mask_words = c.masked ? c.mask_words : 0u;
     ca.part = part;
@@ -178,6 +202,7 @@ int Engine::attend_chunk(const ChunkCall& c, hipStream_t s)
     ca.depth = plan.win && c.by_depth ? c.d_depth : nullptr;
     HIP_TRY(launch_attend_chunk(ca, s));
     for (uint32_t i = 0; i < c.n_seq; ++i) note_use(as[i], s);   // speckv_free waits for this stream
+    for (Allocation* v : vs) note_use(v, s);
     if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel
         (void)hipGetLastError();
         HIP_TRY(hipStreamSynchronize(s));

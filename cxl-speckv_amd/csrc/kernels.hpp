@@ -235,6 +235,8 @@ struct ChunkSeq {
     uint32_t tiles_per_piece;
     uint32_t first_item;
     uint32_t first_tile;              // window form: the first pool tile any block of the sequence walks (the pieces start here); else 0
+    uint32_t v_table_row;             // the table row of the allocation whose pages v_first counts: table_row, but in the split pool
+                                      // (ChunkArgs::v_scheme != scheme), where the V pages lie in an allocation of their own
 };
 // A partial of the split form, one per (work item, kv head): the un-normalised accumulator [64 rows][128] fp32 in the row order of
 // `out`, then (running max, running sum) per row in the log2 domain.
@@ -253,7 +255,7 @@ struct ChunkArgs {
     uint32_t        n_seq, n_blocks;  // n_blocks = the sum of the sequences' query blocks
     uint32_t        C, rows_per_pos, heads;
     float           sm_scale;
-    int             scheme;           // kFp8E4m3, kInt4G32 or kMxFp4
+    int             scheme;           // kFp8E4m3, kInt4G32 or kMxFp4: the scheme of the K pages (and, but in the split pool, of the V pages)
     // tree form (null: causal): row (i * C + j) * mask_words of this device array = query position j of sequence i, bit t & 31 of its
     // word t >> 5 = HELD position t (the tail, if any, is 0; new position a is base + a) is visible, under the causal bound
     // t < base + j + 1 as before; a row whose own bit base + j is clear is dead: not computed to the end, not written
@@ -268,8 +270,11 @@ struct ChunkArgs {
     uint32_t        window;
     // tree form under a window (null: none; needs mask and window): depth[i * C + j] = the depth of node j of sequence i in its tree
     // (0: a child of the committed context), the j of its lower bound over the STORED positions; the held part is what the mask
-    // says.  The last member: the members the other forms read keep their places.
+    // says.  The last member the kernels read: the members the other forms read keep their places.
     const uint32_t* depth;
+    // the scheme of the V pages (the launcher's alone: it picks the instance).  Equal to `scheme` everywhere but in the K8V4 split pool,
+    // scheme == kFp8E4m3 and v_scheme == kMxFp4 -- the one mixed pair there are instances of; any other is refused.
+    int             v_scheme;
 };
 // part == null: ONE launch of n_blocks * heads workgroups.  Otherwise TWO: n_items * heads workgroups that write their partials, then
 // the merge (k_chunk_combine) over n_blocks * heads, which reads a row's partials in ascending piece order and writes out / lse.

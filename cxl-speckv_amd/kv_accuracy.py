@@ -153,3 +153,130 @@ def format_table(acc):
             m = res[r]
             rows.append(f"| {name} | {r} | {m['rel_l2']:.4f} ({m['format_rel_l2']:.4f} + {m['kernel_rel_l2']:.4f}) | {m['rel_l2_worst_row']:.4f} | {m['cosine_mean']:.5f} / {m['cosine_min']:.5f} | {m['top1_agreement']:.3f} |")
     return "\n".join(rows)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The pool formats restated in numpy, and the split pool ("K8V4": FP8 keys, MXFP4 values).  No GPU in the first half: the formats'
+# own cost on the data above, for any pair of K and V formats (DESIGN section 4's table of the routes to a denser pool).
+# ------------------------------------------------------------------------------------------------------------------------------
+def _pages(x):
+    """[T][H][D] fp16 (T even, H * D = 1024) -> the pool's blocks in page order, fp32 [T / 2][2048]: a page is two positions"""
+    x = np.asarray(x)
+    if x.ndim != 3 or x.shape[0] % 2 or x.shape[1] * x.shape[2] != N // 2:
+        raise ValueError("a tensor of [T][H][D] with T even and H * D = 1024: whole pages of two positions")
+    return np.ascontiguousarray(x.astype(np.float16)).astype(np.float32).reshape(-1, N)
+
+
+def _held(y32, shape):
+    """what fetch_range gives for fp32 decoded values: rounded once to fp16; as float64 in the tensor's shape"""
+    with np.errstate(over="ignore"):
+        return y32.astype(np.float16).astype(np.float64).reshape(shape)
+
+
+def quantize_fp8_e4m3(x):
+    """The values an FP8_E4M3 pool holds for x ([T][H][D] fp16), float64: per page scale = max|x| / 448 (1 for a page of zeros),
+    x / scale rounded to nearest-even E4M3 (saturating at 448), times the scale in fp32, rounded to fp16 as fetch_range does."""
+    b = _pages(x)
+    mx = np.abs(b).max(axis=1, keepdims=True)
+    s = np.where(mx > 0, mx / np.float32(448.0), np.float32(1.0)).astype(np.float32)
+    v = np.clip((b / s).astype(np.float32), -448.0, 448.0)
+    _, ex = np.frexp(np.abs(v))                                                  # |v| = m 2^ex, m in [0.5, 1): floor(log2) = ex - 1
+    quantum = np.exp2(np.maximum(ex - 1, -6) - 3.0)                              # three mantissa bits; subnormals below 2^-6: 2^-9
+    e4m3 = (np.rint(v.astype(np.float64) / quantum) * quantum).astype(np.float32)    # (exact: a power of two; rint is ties-to-even, -0 stays -0)
+    return _held(e4m3 * s, np.shape(x))
+
+
+def quantize_mxfp4(x):
+    """The values an MXFP4 pool holds for x, float64: an MX block is 16 channels of BOTH positions of a page, its E8M0 scale
+    2^(floor(log2 max|x|) - 2), the elements E2M1 (0, .5, 1, 1.5, 2, 3, 4, 6; ties to the even code, saturating at 6)."""
+    b = _pages(x).astype(np.float64).reshape(-1, 2, N // 32, 16)                 # [page][position][group][16 channels]
+    amax = np.abs(b).max(axis=(1, 3), keepdims=True)
+    _, ex = np.frexp(amax)
+    code = np.where(amax > 0, np.clip(ex - 1 - 2 + 127, 0, 254), 0)
+    a = np.abs(np.ldexp(b, 127 - code))
+    idx = sum((a > m).astype(np.int64) for m in (0.25, 1.25, 2.5, 5.0)) + sum((a >= m).astype(np.int64) for m in (0.75, 1.75, 3.5))
+    mag = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])[idx]
+    y = np.copysign(np.ldexp(mag, code - 127), b)
+    return _held(y.astype(np.float32), np.shape(x))
+
+
+def quantize_int4_g32(x):
+    """The values an INT4_G32 pool holds for x, float64: groups of 32 consecutive channels of one position, scale = fp16(max|x| / 7),
+    elements round(x / scale) (halves away from zero) in -7 .. 7."""
+    b = _pages(x).reshape(-1, 32)
+    s = (np.abs(b).max(axis=1, keepdims=True) / np.float32(7.0)).astype(np.float16).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = (b / s).astype(np.float32).astype(np.float64)
+    r = np.where(s != 0, np.clip(np.copysign(np.floor(np.abs(r) + 0.5), r), -7.0, 7.0), 0.0)
+    return _held((r + 0.0).astype(np.float32) * s, np.shape(x))                 # (an integer has no sign of zero: -0 + 0 = +0)
+
+
+def quantize_mxfp4_tile_mean(x):
+    """A route that was weighed and NOT built (route a): MXFP4 of x minus an fp16 offset per (32-position tile,
+    channel) -- the tile's mean -- with the offset added back.  T a multiple of 32."""
+    x32 = np.asarray(x).astype(np.float32)
+    tiles = x32.reshape(-1, 32, *x32.shape[1:])
+    mean = tiles.mean(axis=1, keepdims=True).astype(np.float16).astype(np.float32)
+    rest = (tiles - mean).astype(np.float16).reshape(x32.shape)
+    return (quantize_mxfp4(rest).reshape(tiles.shape) + mean.astype(np.float64)).reshape(x32.shape)
+
+
+def quantize_mxfp4_top4_fp8(x):
+    """A route that was weighed and NOT built (route b): per head the 4 channels of the largest max|x| kept in an FP8_E4M3 side plane
+    (here: their values out of the FP8 pool's blocks), the other channels MXFP4 with those four zeroed, so that they set no block scale."""
+    x16 = np.asarray(x).astype(np.float16)
+    top = np.argsort(np.abs(x16.astype(np.float32)).max(axis=0), axis=-1)[:, -4:]                     # [H][4]
+    side = np.zeros(x16.shape[1:], bool)
+    np.put_along_axis(side, top, True, axis=-1)
+    return np.where(side[None], quantize_fp8_e4m3(x16), quantize_mxfp4(np.where(side[None], np.float16(0), x16)))
+
+
+QUANTIZERS = {"fp8_e4m3": quantize_fp8_e4m3, "mxfp4": quantize_mxfp4, "int4_g32": quantize_int4_g32, "exact": lambda x: np.asarray(x, np.float64),
+              "mxfp4_tile_mean": quantize_mxfp4_tile_mean, "mxfp4_top4_fp8": quantize_mxfp4_top4_fp8}
+
+
+def format_accuracy_cpu(k_format, v_format, T=2048, g=8, seed=7001):
+    """{regime: rel. L2 error} of float64 attention over K as `k_format` and V as `v_format` hold them (names of QUANTIZERS) with the
+    exact fp16 query, against float64 attention over the original rows: the "format alone" column of kv_format_accuracy for any pair
+    of formats, without a GPU."""
+    K, V, qs, _ = synth_kv(T, g, seed)
+    Kq, Vq = QUANTIZERS[k_format](K), QUANTIZERS[v_format](V)
+    sm = 1.0 / np.sqrt(D)
+    return {r: _rel(attention_f64(Kq, Vq, qs[r], sm)[0], attention_f64(K, V, qs[r], sm)[0]) for r in REGIMES}
+
+
+def kv_split_accuracy(lib, T=2048, g=8, seed=7001):
+    """kv_format_accuracy's figures for the split pool on the HIP engine behind `lib` (a SpeckvLib): the data goes through
+    SpeckvSplitKVConnector -- T - 2 positions as a prompt, the last two as a chunk whose last row carries the regime's queries, so the
+    call walks pool tiles and a held tile -- and {regime: metrics} comes back, with format_rel_l2 (float64 over the numpy restatement
+    of what the two allocations hold; the two held rows are exact) and kernel_rel_l2 (the launch against that) per regime."""
+    import torch
+    from .kv_split_connector import SpeckvSplitKVConnector
+    K, V, qs, _ = synth_kv(T, g, seed)
+    sm = 1.0 / np.sqrt(D)
+    Kq, Vq = quantize_fp8_e4m3(K[:T - 2]), quantize_mxfp4(V[:T - 2])
+    Kq, Vq = np.concatenate([Kq, K[T - 2:].astype(np.float64)]), np.concatenate([Vq, V[T - 2:].astype(np.float64)])
+    conn = SpeckvSplitKVConnector(lib, 2, H, D, (T + 31) // 32 * 32)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    two = lambda a: np.stack([a, a])                                            # the same rows in both layers
+    conn.add_request(0)
+    res = {}
+    try:
+        keep = conn.write_prefill(0, dev(two(K[:T - 2])), dev(two(V[:T - 2])))
+        k_new, v_new = dev(two(K[T - 2:]).transpose(1, 0, 2, 3)[None]), dev(two(V[T - 2:]).transpose(1, 0, 2, 3)[None])    # [1][2][L][H][D]
+        for r in REGIMES:
+            q = np.zeros((1, 2, H, g, D), np.float16)
+            q[0, 1] = qs[r]
+            o = conn.attend_chunk(1, [0], dev(q), k_new, v_new, sm)
+            torch.cuda.synchronize()
+            got = o.cpu().numpy()[0, 1]
+            ref, top1_ref, _ = attention_f64(K, V, qs[r], sm)
+            of, top1_fmt, _ = attention_f64(Kq, Vq, qs[r], sm)
+            m = _metrics(got, ref, top1_fmt, top1_ref)
+            m["format_rel_l2"] = _rel(of, ref)
+            m["kernel_rel_l2"] = _rel(got, of)
+            res[r] = {k: round(v, 5) for k, v in m.items()}
+        del keep
+    finally:
+        conn.free_request(0)
+    return res

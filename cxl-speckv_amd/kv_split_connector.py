@@ -1,0 +1,267 @@
+"""The split pool ("K8V4"): a request's K rows in an FP8_E4M3 allocation, its V rows in an MXFP4 allocation, one chunk-attention launch
+over both (speckv_ext_attend_chunk_kv).
+
+Why: on KV-like data the decode-regime error of the 4-bit pools is K's (kv_accuracy.format_accuracy_cpu: MXFP4 / MXFP4 0.60-0.75, FP8 /
+MXFP4 0.19-0.22 relative L2 against 0.13-0.18 for FP8 / FP8), while V in 4 bits costs a flat 0.13-0.14 in every regime.  2048 + 1088
+bytes per position pair, layer and kind pair: 2.61 : 1 against fp16, 0.77 of an FP8 pool's bytes.
+
+The engine keeps one scheme and one record stride per allocation, so a request is TWO allocations of T * L * H * D * 2 bytes, each laid
+out as L regions of T / 2 pages (set_layout(T, L / 2, H, D, 2): 2 * (L / 2) regions): region l of the K allocation is layer l's K,
+region l of the V allocation layer l's V.  Every write, copy and placement path of the library works per allocation unchanged.
+
+  add_request / free_request / length   the two allocations of a request; nothing is bound for prefetch
+  write_prefill                         one speckv_ext_write_runs per allocation; an odd last position waits in an fp16 tail
+  attend_chunk                          one layer of a step of S >= 1 new positions per request -- a prefill chunk, a draft chain or tree,
+                                        S = 1 the decode step -- causal, under a window, a tree, a tree under a window, split over the chip
+  commit                                the accepted prefix of a step into the pool: one speckv_ext_write_pairs per allocation
+
+Not in this class: the planned and captured decode kernels (decode goes through the chunk walk), load_paged /
+store_paged, the shared-prefix fold, fork, truncate, begin_step and the K pre-scale."""
+from typing import Dict, Sequence
+
+from . import kv_connector as _kc
+from .kv_connector import SpeckvKVConnector, _is_int
+from .speckv_ctypes import SpeckvLib
+
+K_SCHEME, V_SCHEME = 4, 5                # SPECKV_COMP_FP8_E4M3, SPECKV_COMP_MXFP4
+
+
+class _SplitRequest:
+    """the two handles, the length, and the fp16 K / V rows of an odd last position ([layers][heads][dim] each, contiguous)"""
+    __slots__ = ("k_handle", "v_handle", "length", "tail_k", "tail_v")
+
+    def __init__(self, k_handle, v_handle):
+        self.k_handle, self.v_handle, self.length, self.tail_k, self.tail_v = k_handle, v_handle, 0, None, None
+
+
+class SpeckvSplitKVConnector:
+    _On = SpeckvKVConnector._On          # the stream rule of the connector: torch's NULL stream goes through a side stream
+
+    def __init__(self, lib: SpeckvLib, num_layers: int, num_kv_heads: int = 8, head_dim: int = 128, max_tokens: int = 4096):
+        if num_kv_heads * head_dim * 2 != 2048:
+            raise ValueError("the page-wise layout needs num_kv_heads * head_dim == 1024 fp16 elements per position "
+                             "(8 kv heads x 128: Llama-3 8B / 70B)")
+        if max_tokens % 32:
+            raise ValueError("max_tokens must be a multiple of 32 (tile size of the fused attention)")
+        if not _is_int(num_layers) or num_layers < 2 or num_layers % 2:
+            raise ValueError("num_layers must be even: an allocation's layout counts (K, V) region pairs, and a single-kind allocation "
+                             "holds num_layers / 2 of them")
+        self.lib = lib
+        self.L, self.H, self.D, self.T = int(num_layers), num_kv_heads, head_dim, max_tokens
+        self.requests: Dict[int, _SplitRequest] = {}
+        self.region_pages = max_tokens // 2                   # pages of one layer's region, in either allocation
+        self._side = None
+        self._epoch = 0                                       # moves with every length: what a step derives from (batch, lengths) is keyed by it
+        self._tails = (None, None, None, None)                # key, tail_idx, K rows, V rows of the step's requests with an odd length
+        self._tree = (None, None, None)                       # key, mask rows, depths of the step's tree
+
+    # ------------------------------------------------------------------ requests
+    def add_request(self, req_id: int):
+        """-> (K handle, V handle)"""
+        if req_id in self.requests:
+            raise KeyError(f"request {req_id} already exists")
+        handles = []
+        for scheme in (K_SCHEME, V_SCHEME):
+            self.lib.set_compression_scheme(scheme)
+            h = self.lib.alloc(self.T * self.L * self.H * self.D * 2)
+            self.lib.set_layout(h, self.T, self.L // 2, self.H, self.D, 2)
+            handles.append(h)
+        self.requests[req_id] = _SplitRequest(*handles)
+        self._epoch += 1
+        return tuple(handles)
+
+    def free_request(self, req_id: int):
+        r = self.requests.pop(req_id)
+        self._epoch += 1
+        self._tails = (None, None, None, None)
+        self.lib.free(r.k_handle)
+        self.lib.free(r.v_handle)
+
+    def length(self, req_id: int) -> int:
+        return self.requests[req_id].length
+
+    def _page(self, layer: int, pos: int) -> int:
+        """the page of (layer, position) in either allocation"""
+        return layer * self.region_pages + pos // 2
+
+    # ------------------------------------------------------------------ writes
+    def write_prefill(self, req_id: int, k, v, stream=None):
+        """k, v: [layers][tokens][heads][dim] fp16 CUDA tensors of the prompt.  One asynchronous speckv_ext_write_runs per allocation (the
+        layers' regions are page runs, read in place from k and from v); returns the tensors the launches read -- hold them until the
+        stream has passed them."""
+        r = self.requests[req_id]
+        n = k.shape[1]
+        if r.length:
+            raise ValueError("write_prefill on a request that already has positions")
+        if tuple(k.shape) != (self.L, n, self.H, self.D) or tuple(v.shape) != tuple(k.shape) or n > self.T:
+            raise ValueError("k, v must be [layers][tokens][heads][dim], tokens <= max_tokens")
+        even = n & ~1
+        k = k.contiguous(); v = v.contiguous()
+        if even:
+            layer_bytes = n * self.H * self.D * 2
+            firsts = [self._page(layer, 0) for layer in range(self.L)]
+            with self._On(self, stream) as st:
+                for handle, t in ((r.k_handle, k), (r.v_handle, v)):
+                    self.lib.write_runs(handle, firsts, [t.data_ptr() + layer * layer_bytes for layer in range(self.L)], even // 2, st.cuda_stream)
+        if n & 1:
+            r.tail_k, r.tail_v = k[:, n - 1].contiguous().clone(), v[:, n - 1].contiguous().clone()
+        r.length = n
+        self._epoch += 1
+        return [k, v]
+
+    # ------------------------------------------------------------------ attention
+    def _step_tails(self, req_ids, reqs):
+        """(tail_idx int32 [batch], K rows, V rows [n][layers][heads][dim] or None) of the requests with an odd length, once per step"""
+        import numpy as np
+        import torch
+        key = (tuple(req_ids), self._epoch)
+        if self._tails[0] != key:
+            tail_idx, rank = np.full(len(reqs), -1, dtype=np.int32), 0
+            for b, r in enumerate(reqs):
+                if r.length & 1:
+                    tail_idx[b] = rank
+                    rank += 1
+            odd = [r for r in reqs if r.length & 1]
+            tk = torch.stack([r.tail_k for r in odd]).contiguous() if odd else None
+            tv = torch.stack([r.tail_v for r in odd]).contiguous() if odd else None
+            self._tails = (key, tail_idx, tk, tv)
+        return self._tails[1:]
+
+    def _step_tree(self, req_ids, reqs, parents, live, S, window):
+        """(mask rows int32 [batch][S][W], depths int32 [batch][S] or None) of a tree step on the device, once per (batch, lengths, tree,
+        live counts, window): the static helpers of SpeckvKVConnector build both, the window folded into the rows"""
+        import numbers
+        import numpy as np
+        import torch
+        one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)
+        key = (tuple(req_ids), self._epoch, S, tuple(parents) if one else tuple(map(tuple, parents)), tuple(live), window)
+        if self._tree[0] != key:
+            rows = SpeckvKVConnector.chunk_tree_masks(parents, [r.length & 1 for r in reqs], live, window=window or None)
+            on_device = lambda a: torch.from_numpy(a).pin_memory().to("cuda", non_blocking=True)
+            masks = on_device(np.asarray(rows, dtype=np.uint32).view(np.int32))
+            depths = None
+            if window:
+                depths = on_device(np.asarray(SpeckvKVConnector.chunk_tree_depths(parents, len(reqs)), dtype=np.uint32).view(np.int32))
+            self._tree = (key, masks, depths)
+        return self._tree[1:]
+
+    def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, splits=1,
+                     window=None, parents=None):
+        """One layer of a step of S >= 1 new positions per request over the split pool; conventions as SpeckvKVConnector.attend_chunk:
+        q [batch][S][heads][rows_per_pos][dim] fp16 (rows_per_pos 1, 2, 4, 8 or 16), k_new / v_new [batch][S][layers][heads][dim] fp16,
+        n_new optional counts <= S of live positions; returns [batch][S][heads][rows_per_pos][dim] fp32, zeros for rows that are not
+        live.  Changes no state -- commit() stores the accepted prefix afterwards.  S = 1 is the decode step.
+        ONE library call (speckv_ext_attend_chunk_kv) in every form: splits as attend_chunk (1 none, 0 the library's rule, N forced
+        pieces); window W >= 1 a sliding-window layer; parents a tree of drafts (chunk_tree_masks); window together with parents goes by
+        a node's DEPTH, as SpeckvKVConnector.attend_tree.  The stored K enters as its E4M3 values with the block scale on the score, the
+        stored V as the fp16 values of its MXFP4 records, the query stays fp16."""
+        import numpy as np
+        import torch
+        window = SpeckvKVConnector._chunk_window(window)
+        if not _is_int(splits) or not 0 <= splits <= 64:
+            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
+        if len(q.shape) != 5:
+            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim]")
+        B, S, H, R, D = (int(x) for x in q.shape)
+        want = (B, S, self.L, self.H, self.D)
+        if (H, D) != (self.H, self.D) or tuple(k_new.shape) != want or tuple(v_new.shape) != want or B != len(req_ids) or S < 1:
+            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim], k_new / v_new [batch][S][layers][heads][dim], S >= 1")
+        if not 0 <= layer < self.L:
+            raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
+        if n_new is None:
+            live = [S] * B
+        else:
+            live = [int(n) for n in n_new]
+            if len(live) != B or not all(0 <= n <= S for n in live):
+                raise ValueError("n_new: one count 0..S per request")
+        counts, _ = SpeckvKVConnector.chunk_blocks(live, R)
+        reqs = [self.requests[r] for r in req_ids]
+        for r, n in zip(reqs, live):
+            if r.length + n > self.T:
+                raise ValueError(f"a request of {r.length} positions cannot take {n} more: max_tokens is {self.T}")
+        if parents is not None:
+            trees = SpeckvKVConnector._chunk_tree_parents(parents, B)     # judged in front of any library call
+            if trees and len(trees[0]) != S:
+                raise ValueError("parents: one entry per new position")
+        out = (torch.empty if n_new is None and parents is None else torch.zeros)((B, S, H, R, D), dtype=torch.float32, device="cuda")
+        if not any(counts):
+            return out
+        row = self.H * self.D
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):
+                q = q.contiguous()
+                in_place = lambda t: (t.stride(4) == 1 and t.stride(3) == self.D and t.stride(2) % 8 == 0 and t.stride(1) % 8 == 0 and
+                                      t.stride(1) >= row and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0)
+                if not (in_place(k_new) and in_place(v_new) and k_new.stride() == v_new.stride()):
+                    k_new, v_new = k_new.contiguous(), v_new.contiguous()
+                tail_idx, tk, tv = self._step_tails(req_ids, reqs)
+                masks, depths = (None, None) if parents is None else self._step_tree(req_ids, reqs, parents, live, S, window)
+            self.lib.attend_chunk_kv(np.asarray([r.k_handle for r in reqs], dtype=np.uint64), np.asarray([r.v_handle for r in reqs], dtype=np.uint64),
+                                     layer, q.data_ptr(), S, R, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                     np.asarray(live, dtype=np.uint32), k_new.data_ptr() + 2 * layer * k_new.stride(2),
+                                     v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx,
+                                     tk.data_ptr() + 2 * layer * row if tk is not None else 0, tv.data_ptr() + 2 * layer * row if tv is not None else 0,
+                                     self.L * row, masks.data_ptr() if masks is not None else 0, masks.shape[2] if masks is not None else 0,
+                                     depths.data_ptr() if depths is not None else 0, window, int(splits), sm_scale, out.data_ptr(), 0, st.cuda_stream)
+        return out
+
+    # ------------------------------------------------------------------ commit
+    def commit(self, req_ids: Sequence[int], k_new, v_new, n_accept: Sequence[int], stream=None):
+        """Store the first n_accept[b] (0..S) of the S new positions k_new[b], v_new[b] ([batch][S][layers][heads][dim] fp16) of every
+        request: the tail and the new rows are paired into pages, a leftover odd position becomes the tail (SpeckvKVConnector.commit_plan).
+        TWO library calls for the whole batch, one speckv_ext_write_pairs per allocation, rows read where they lie.  That entry numbers
+        the pages of a pair j = 0 .. 2 n_layers - 1 as (layer j / 2, kind j % 2) and reads row d_rows[2 kind (+ 1)] + (j / 2) *
+        layer_stride; a single-kind allocation of L regions is addressed with n_layers = L / 2, layer_stride = two real layer strides,
+        the even / odd rows of real layer 0 in the "K" slots and the same rows of real layer 1 in the "V" slots -- region j then reads
+        the row of real layer j.  Returns what the asynchronous launches read, to be held until the stream has passed them."""
+        import numpy as np
+        import torch
+        B, S = k_new.shape[0], k_new.shape[1]
+        n_accept = [int(n) for n in n_accept]
+        reqs = [self.requests[rid] for rid in req_ids]
+        if len(reqs) != B or len(n_accept) != B or tuple(v_new.shape) != tuple(k_new.shape) or tuple(k_new.shape[2:]) != (self.L, self.H, self.D):
+            raise ValueError("k_new / v_new must be [batch][S][layers][heads][dim], n_accept one count per request")
+        for rid, r, n in zip(req_ids, reqs, n_accept):
+            if not 0 <= n <= S:
+                raise ValueError(f"request {rid}: n_accept {n} outside 0..{S}")
+            if r.length + n > self.T:
+                raise ValueError(f"request {rid} is full")
+        pairs, tails = SpeckvKVConnector.commit_plan([r.length for r in reqs], n_accept)
+        if not pairs and not tails:
+            return []
+        used = [b for b, (r, n) in enumerate(zip(reqs, n_accept)) if n and r.length & 1]        # requests whose odd position finds its partner
+        layer_bytes = self.H * self.D * 2
+        row_bytes = self.L * layer_bytes
+        keep, tk, tv = [], None, None
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):
+                k_new, v_new = k_new.contiguous(), v_new.contiguous()
+                keep += [k_new, v_new]
+                if tails:                                                                       # copies: the caller may reuse k_new
+                    it = _kc._device_index([b * S + t for b, t in tails])
+                    tk = k_new.view(B * S, self.L, self.H, self.D).index_select(0, it)
+                    tv = v_new.view(B * S, self.L, self.H, self.D).index_select(0, it)
+            if pairs:
+                plan = np.asarray([x for group in pairs for x in group], dtype=np.int64)       # (b, page of layer 0, source, source) per pair
+                b_of = plan[:, 0]
+                tail_at = np.zeros((B, 2), dtype=np.uint64)
+                for b in used:
+                    keep += [reqs[b].tail_k, reqs[b].tail_v]
+                    tail_at[b] = reqs[b].tail_k.data_ptr(), reqs[b].tail_v.data_ptr()
+                for kind, (new, handle) in enumerate(((k_new, "k_handle"), (v_new, "v_handle"))):
+                    rows = np.empty((len(plan), 4), dtype=np.uint64)
+                    for half in (0, 1):
+                        t = plan[:, 2 + half]
+                        new_row = ((b_of * S + np.maximum(t, 0)) * row_bytes).astype(np.uint64) + np.uint64(new.data_ptr())
+                        rows[:, half] = np.where(t < 0, tail_at[b_of, kind], new_row)          # real layer 0: the "K" slots
+                        rows[:, 2 + half] = rows[:, half] + np.uint64(layer_bytes)             # real layer 1: the "V" slots
+                    handles = np.asarray([getattr(reqs[b], handle) for b in b_of], dtype=np.uint64)
+                    self.lib.write_pairs(handles, plan[:, 1].astype(np.uint64), rows, self.region_pages, self.L // 2, 2 * layer_bytes, st.cuda_stream)
+        for b in used:
+            reqs[b].tail_k = reqs[b].tail_v = None
+        for i, (b, _) in enumerate(tails):
+            reqs[b].tail_k, reqs[b].tail_v = tk[i], tv[i]
+        for r, n in zip(reqs, n_accept):
+            r.length += n
+        self._epoch += 1
+        return keep

@@ -106,6 +106,9 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_chunk_tree_window": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_uint32,
                                             c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_chunk_kv": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_uint32,
+                                   c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_prefix_fold": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32,
                                       ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_prefix_fold_window": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
@@ -488,6 +491,20 @@ class SpeckvLib:
         self._chunk("speckv_ext_attend_chunk_tree_window", handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride,
                     pos_stride, tail_idx, d_k_tail, d_v_tail, tail_stride,
                     (c_void_p(d_mask or None), mask_words, c_void_p(d_depth or None), window, n_splits), sm_scale, d_out, d_lse, stream)
+
+    def attend_chunk_kv(self, k_handles, v_handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride,
+                        tail_idx, d_k_tail, d_v_tail, tail_stride, d_mask, mask_words, d_depth, window, n_splits, sm_scale, d_out, d_lse, stream):
+        """The chunk attention over a split pool (speckv_ext_attend_chunk_kv): K of `layer` = region `layer` (num_tokens / 2 pages) of the
+        FP8 allocation k_handles[i], V = region `layer` of the MXFP4 allocation v_handles[i], ONE launch.  d_mask 0 = the causal form
+        (d_depth ignored, window as attend_chunk_window); a mask with a window needs d_depth (attend_chunk_tree_window); n_splits as
+        attend_chunk_split.  The other arguments as attend_chunk."""
+        n = len(v_handles if k_handles is None else k_handles)             # (None: a NULL array, for the library to refuse)
+        handles = lambda h: None if h is None else as_arr(h, c_uint64, n)
+        self._ext("speckv_ext_attend_chunk_kv", n, handles(k_handles), handles(v_handles), layer, c_void_p(d_q), C,
+                  rows_per_pos, as_arr(pos_end, c_uint32, n), as_arr(n_q, c_uint32, n), c_void_p(d_k_new), c_void_p(d_v_new), seq_stride,
+                  pos_stride, None if tail_idx is None else as_arr(tail_idx, c_int32, n), c_void_p(d_k_tail or None),
+                  c_void_p(d_v_tail or None), tail_stride, c_void_p(d_mask or None), mask_words, c_void_p(d_depth or None), window, n_splits,
+                  sm_scale, c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
 
     def attend_prefix_fold(self, prefix_handles, first_member, layer, d_q, C, rows_per_pos, prefix_len, n_q, n_splits, sm_scale, d_out, d_lse,
                            stream):

@@ -1129,6 +1129,45 @@ speckv_status_t speckv_ext_prefix_window_walk(uint32_t n_groups, const uint32_t*
                                               const uint32_t* prefix_len, const uint32_t* own_seen /* may be NULL */, const uint32_t* n_q,
                                               uint32_t window, uint32_t* out_first_tile, uint32_t* out_n_tiles /* [n_groups] */);
 
+/* speckv_ext_attend_chunk_kv: the chunk attention over a SPLIT POOL ("K8V4") -- a request's K rows in an FP8_E4M3 allocation and its
+ * V rows in an MXFP4 allocation of their own, read by ONE launch.  FP8 keys keep the score error of the FP8 pool (the decode-regime
+ * error of the 4-bit pools is K's), MXFP4 values cost what V in 4 bits costs in every regime: 2048 + 1088 bytes per position pair,
+ * 2.61 : 1 against fp16.  An additive entry: SPECKV_EXT_ABI_VERSION stays what it is.
+ * The arguments: k_handles and v_handles (host arrays [n_seq]) in the place of `handles`, `layer`, then exactly the argument list of
+ * speckv_ext_attend_chunk_tree_window (declared behind this entry, at the end of this header) from d_q_f16 on.  Everything said at
+ * speckv_ext_attend_chunk and its forms holds -- the fp16 query, held positions, liveness, rows that are not live are NOT WRITTEN, ordering behind asynchronous pool writes, NOT capturable
+ * into a HIP graph.  The forms, by argument:
+ *   d_mask == NULL : the causal form; d_depth is ignored and `window` acts as at speckv_ext_attend_chunk_window.
+ *   d_mask != NULL : the tree form (speckv_ext_attend_chunk_masked); with window != 0, d_depth is required and the call is
+ *                    speckv_ext_attend_chunk_tree_window's (the window folded into the mask by the caller, applied by depth to the
+ *                    stored positions by the library).
+ *   n_splits       : as speckv_ext_attend_chunk_split, in every form.
+ * Addressing.  Both allocations are read as arrays of REGIONS of num_tokens / 2 pages (num_tokens = the layout's): K of `layer` is
+ * region `layer` of k_handles[i], V of `layer` is region `layer` of v_handles[i]; stored position p of the layer lies in page
+ * layer * num_tokens / 2 + p / 2 of either.  (In an ordinary layout region r is layer r / 2, kind r % 2: a layout of
+ * (num_tokens, n / 2 layers, 8, 128, 2) describes n such regions.)
+ * Values.  A stored K element enters the score as the E4M3 value of its record, the page's block scale multiplies the score in fp32
+ * -- exactly what speckv_ext_attend_chunk does over an FP8 pool.  A stored V element enters as the fp16 value speckv_ext_fetch_range
+ * decodes from the MXFP4 record.  The query, the tail and the new rows stay fp16.  A page never written reads as zeros.
+ *   SPECKV_ERR_INVAL    everything the chunk entries refuse (speckv_ext_attend_chunk, _masked, _split, _tree_window), and: k_handles or
+ *                       v_handles NULL, a K allocation whose scheme is not SPECKV_COMP_FP8_E4M3, a V allocation whose scheme is not
+ *                       SPECKV_COMP_MXFP4, a layout that is not 8 heads x 128 fp16 or whose num_tokens is odd, num_tokens that differ
+ *                       between the two allocations of a sequence, pos_end[i] > num_tokens, (layer + 1) * num_tokens / 2 beyond
+ *                       either allocation's pages, a capturing stream -- nothing is launched
+ *   SPECKV_ERR_NOMEM    the scratch buffer of a split call could not grow -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle
+ * speckv_free of either allocation waits for `stream`. */
+speckv_status_t speckv_ext_attend_chunk_kv(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                           uint32_t layer, const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                           const uint32_t* pos_end, const uint32_t* n_q /* host arrays [n_seq] */,
+                                           const void* d_k_new, const void* d_v_new, uint64_t seq_stride_elems,
+                                           uint64_t pos_stride_elems,
+                                           const int32_t* tail_idx /* host [n_seq], < 0 = none; may be NULL */,
+                                           const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,
+                                           const uint32_t* d_mask /* NULL: causal */, uint32_t mask_words,
+                                           const uint32_t* d_depth, uint32_t window /* 0: none */, uint32_t n_splits,
+                                           float sm_scale, float* d_out, float* d_lse, void* stream);
+
 /* speckv_ext_attend_chunk_tree_window: a DRAFT TREE on a SLIDING-WINDOW (local) layer -- the tree step of the local layers of the
  * models speckv_ext_attend_chunk_window names, whose global layers take the tree step through speckv_ext_attend_chunk_masked / _split.
  * The arguments of speckv_ext_attend_chunk_split in the same order with `d_depth, window` directly behind mask_words.  Everything
