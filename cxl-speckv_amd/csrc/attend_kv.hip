@@ -1,0 +1,261 @@
+// cxl-speckv_amd/csrc/attend_kv.hip -- batch decode attention straight from the records of the SPLIT POOL ("K8V4"): a sequence's K rows
+// in an FP8_E4M3 allocation, its V rows in an MXFP4 allocation (kv_split_connector.py).  One new position per sequence
+// (g query rows per kv head), no fp16 K or V is materialised.
+//
+// The workgroup shape and the K side are k_attend_fp8_linear<false>'s (attend.hip): one wave = one kv head of one sequence over one
+// contiguous split of its positions, tiles of 32 positions (16 pages), four waves = four heads of the same split; grid (splits,
+// sequences x heads / 4) or rows-first.  Lane (c = lane % 16, kb = lane / 16) owns query row c:
+//   scores  S^T = K . q^T on v_mfma_f32_16x16x32_fp8_fp8: the fp16 query quantised here to E4M3 x a row scale (the arithmetic of the FP8
+//           kernel, bit for bit), the K bytes as they lie in the record, the page scale (the K allocation's scale table, tile order) on the
+//           score in fp32.  The lane ends with sc[8]: sc[j] = page slot j / 2 (pages 2kb, 2kb + 1, 8 + 2kb, 9 + 2kb of the tile), position j % 2.
+//   output  O^T = V^T . P^T on v_mfma_f32_16x16x32_f16.  An MXFP4 head row of a page is 128 bytes [channel], low nibble = position 0, high
+//           nibble = position 1, one E8M0 code per 16 bytes.  The lane holds bytes 8c .. 8c + 7 of its four pages; for MFMA t (channel
+//           8c + t) v_cvt_scalef32_pk_f16_fp4 turns byte t of each page into the f16 pair (position 0, position 1) x 2^(code - 127): two
+//           consecutive k slots, four conversions = one f16x8 in exactly the k order of the weights P[j].  The lane's 8 channels lie in
+//           block c / 2: ONE code per page.  The block scale sits inside the conversion, the weights are the plain p in f16: there is no
+//           per-tile V reference scale as in the FP8 kernel.
+//           -> lane (c, kb) holds out[query row c][32kb + 8i + t] in acc[t][i].
+// Per tile and wave: 4 sixteen-byte K loads, one load of 4 page scales, 4 eight-byte V loads, 4 code bytes (the FP8 kernel: 8 eight-byte
+// V loads and a second scale load).  Register-staged like that kernel: ONE register set, K(t + 1) requested behind the scores of tile t,
+// V(t + 1) behind p.V.
+//
+// V records are tile-planar (kernels.hpp: mx4_nib_off, mx4_code_delta, kMx4CodePlane); a region starts on a multiple of 16 records
+// (num_tokens % 32 == 0), so a kernel tile is exactly one storage tile of 17 408 bytes: nibble rows at + 1024 page, code rows at
+// kMx4CodePlane + 64 page.  Never-written records are zero bytes on both sides: K scale 0 -> score 0 (NOT -inf), V = 0.
+#include "kernels.hpp"
+#include "codec_device.hpp"          // the exact reciprocal divide of the codecs (div_by_scale and friends)
+#include "attend_device.hpp"
+
+namespace speckv {
+
+namespace {
+
+__device__ __forceinline__ uint2 kv_ldg8(const uint8_t* p)
+{
+    const u32x2 v = __builtin_nontemporal_load(SPECKV_GP(u32x2, p));
+    return make_uint2(v.x, v.y);
+}
+__device__ __forceinline__ uint32_t kv_ldg1(const uint8_t* p) { return *SPECKV_GP(uint8_t, p); }
+// four floats of the scale table (temporal: small, and every workgroup of a sequence reads it)
+__device__ __forceinline__ f32x4 kv_ldg_f4(const float* p) { return *SPECKV_GP(f32x4, p); }
+
+} // namespace
+
+// a.seqs: the K side and the split bookkeeping of every sequence (lin_base, scale_tab, k_first of the K allocation; v_first and
+// layer_pages are not read); vside[sequence]: the V allocation's run and the first record of the layer's V region (a multiple of 16).
+// a.direct_out / direct_lse are always set: a sequence with ONE split is written final, one without positions as zeros / -inf, the
+// others leave partials (part_acc / part_ml, true units) for launch_attend_combine, which skips the single-split sequences.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_attend_k8v4(AttendArgs a, const AttendKvSide* __restrict__ vside)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t c = lane & 15u, kb = lane >> 4;
+    const uint32_t split = a.rows_first ? blockIdx.y : blockIdx.x, by = a.rows_first ? blockIdx.x : blockIdx.y;
+    if (a.rows_first && by >= a.rows_real) return;                      // (padding row: see AttendArgs::rows_real)
+    const uint32_t hq = a.heads / 4u;
+    uint32_t seq = by / hq;
+    if (a.order) seq = a.order[seq];                                     // (workgroup-uniform)
+    const uint32_t head = (by % hq) * 4u + wave;
+    const uint64_t row = static_cast<uint64_t>(seq) * a.heads + head;    // query / output row block
+    const AttendSeq sq = a.seqs[seq];
+    if (split >= sq.n_splits) {
+        if (sq.n_splits == 0u && split == 0u) attend_zero_rows(a.direct_out, a.direct_lse, a.g, row, lane);
+        return;
+    }
+    const AttendKvSide vsd = vside[seq];
+    const uint64_t part = sq.part_base + static_cast<uint64_t>(head) * sq.n_splits + split;
+    const uint32_t n_pages = sq.n_pages;
+
+    // query operand: see k_attend_fp8_linear (attend.hip) -- row c of this head, lane kb takes d = 16kb .. 16kb + 15 of both 64-element
+    // halves, the split the K loads follow; scale = max|q| / 448 over the row (1 if zero), e4m3 of clamp(q / scale); rows >= g are zero
+    uint32_t qd[8];
+    float qscale = 1.0f;
+    auto quantise_query = [&]() {
+        float xq[32];
+        float mx = 0.0f;
+        const uint16_t* qsrc = a.q16 + (row * a.g + min(c, a.g - 1u)) * 128u + kb * 16u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint4 w = *reinterpret_cast<const uint4*>(qsrc + 8 * (i & 1) + 64 * (i >> 1));
+            const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                xq[8 * i + k] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(ws[k >> 1] >> (16 * (k & 1)))));
+                mx = fmaxf(mx, fabsf(xq[8 * i + k]));
+            }
+        }
+        mx = max_over_kb(mx);
+        const bool finite = mx < INFINITY;                                // (inf / NaN rows: the IEEE divide)
+        const float sc = (mx > 0.0f) ? (finite ? div448_of_f16_value(mx) : mx / 448.0f) : 1.0f;
+        const float rcp = finite ? rcp_of_scale(sc) : 0.0f;
+        const bool live = c < a.g;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float x = xq[4 * i + k];
+                const float qt = finite ? __builtin_copysignf(div_by_scale(x, sc, rcp), x) : x / sc;
+                v[k] = live ? fminf(fmaxf(qt, -448.0f), 448.0f) : 0.0f;
+            }
+            int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+            pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
+            qd[i] = static_cast<uint32_t>(pk);
+        }
+        qscale = (live ? sc : 1.0f) * a.scale_log2e;
+    };
+
+    const uint32_t n_tiles = (n_pages + 15u) / 16u;
+    const uint32_t t0 = split * sq.tiles_per_split;
+    const uint32_t t1 = min(t0 + sq.tiles_per_split, n_tiles);
+    float m_run = -INFINITY, l_run = 0.0f;
+    f32x4 acc[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    if (t0 < t1) {                                                       // wave-uniform
+        // running pointers of the tile being requested.  K: row 16b + c of the tile, bytes [16kb, 16kb + 16) of both halves; block b: + 16 KiB
+        const uint8_t* kp = sq.lin_base + sq.k_first * 2048ull + head * 128u + kb * 16u + (static_cast<uint64_t>(t0) * 32u + c) * 1024u;
+        const float* kt = sq.scale_tab + (sq.k_first + static_cast<uint64_t>(t0) * 16u) + 4u * kb;
+        // V: the storage tile of kernel tile t0; the lane's page slot r = page 2kb + (r & 1) + 8 (r >> 1): nibbles + 1024 page, codes behind the plane
+        const uint8_t* vtile = vsd.v_base + ((vsd.v_first >> 4) + t0) * static_cast<uint64_t>(kMx4TileBytes);
+        const uint8_t* vp = vtile + 2u * kb * 1024u + head * 128u + 8u * c;
+        const uint8_t* vc = vtile + kMx4CodePlane + 2u * kb * 64u + head * 8u + (c >> 1);
+
+        uint4 kx[2][2];
+        uint2 vx[4];
+        uint32_t vcode[4];
+        f32x4 ks4;
+        auto issue_k = [&]() {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) { kx[b][0] = ldg16(kp + 16384 * b); kx[b][1] = ldg16(kp + 16384 * b + 64); }
+            ks4 = kv_ldg_f4(kt);
+        };
+        auto issue_v = [&]() {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vx[r] = kv_ldg8(vp + 1024 * (r & 1) + 8192 * (r >> 1));
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vcode[r] = kv_ldg1(vc + 64 * (r & 1) + 512 * (r >> 1));
+        };
+        // same request order as in the loop (K before V), pinned, so that the wait at the loop head is "everything up to K" on both paths into it
+        __builtin_amdgcn_sched_barrier(0);
+        issue_k();
+        __builtin_amdgcn_sched_barrier(0);
+        issue_v();
+        __builtin_amdgcn_sched_barrier(0);
+        quantise_query();                                                // (its loads are the youngest: they and the tile arrive together)
+        __builtin_amdgcn_sched_barrier(0);
+        const bool ragged = (n_pages & 15u) != 0u;
+#pragma unroll 1
+        for (uint32_t tile = t0; tile < t1; ++tile) {
+            // the refills are unconditional -- the last iteration re-requests its own tile -- so the loop body is one basic block
+            const uint32_t step = (tile + 1u < t1) ? 1u : 0u;            // scalar
+            // ---- scores
+            float sc[8];
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const uint32_t kd[8] = {kx[b][0].x, kx[b][0].y, kx[b][0].z, kx[b][0].w, kx[b][1].x, kx[b][1].y, kx[b][1].z, kx[b][1].w};
+                f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int st = 0; st < 4; ++st)
+                    s = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(kd[2 * st], kd[2 * st + 1]), pack64(qd[2 * st], qd[2 * st + 1]), s, 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) sc[4 * b + i] = s[i] * (ks4[2 * b + (i >> 1)] * qscale);
+            }
+            if (ragged && tile + 1u == n_tiles) {                         // wave-uniform: pages at or beyond pos_end (even: whole pages)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const uint32_t pg = tile * 16u + 2u * kb + (r & 1) + 8u * (r >> 1);
+                    // (the masked page's code goes too: it may be a stale record of any magnitude, and its weight of exactly 0 must meet a finite value)
+                    if (pg >= n_pages) { sc[2 * r] = -INFINITY; sc[2 * r + 1] = -INFINITY; vcode[r] = 0u; }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            kp += step * 32768u; kt += step * 16u;
+            issue_k();
+            __builtin_amdgcn_sched_barrier(0);
+            // ---- online softmax of query row c
+            float mx = sc[0];
+#pragma unroll
+            for (int j = 1; j < 8; ++j) mx = fmaxf(mx, sc[j]);
+            mx = max_over_kb(mx);
+            const float m_new = fmaxf(m_run, mx);
+            const float m_use = (m_new == -INFINITY) ? 0.0f : m_new;
+            const float f = __builtin_amdgcn_exp2f(m_run - m_use);
+            m_run = m_new;
+            float psum = 0.0f;
+            f16x8 P;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float p = __builtin_amdgcn_exp2f(sc[j] - m_use);
+                psum += p;
+                P[j] = static_cast<_Float16>(p);
+            }
+            l_run = l_run * f + psum;
+            // ---- out^T += V^T . P^T: byte t of a page = channel 8c + t of both positions -> one operand register
+            float vsc[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vsc[r] = __uint_as_float(vcode[r] << 23);        // the block's E8M0 code as a float's exponent field
+#define KV_PV(T, WORD, SEL)                                                                                                       \
+    {                                                                                                                              \
+        const u32x4 vw = {__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(vx[0].WORD, vsc[0], SEL)),          \
+                          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(vx[1].WORD, vsc[1], SEL)),          \
+                          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(vx[2].WORD, vsc[2], SEL)),          \
+                          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(vx[3].WORD, vsc[3], SEL))};         \
+        acc[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, vw), P, acc[T] * f, 0, 0, 0);                     \
+    }
+            KV_PV(0, x, 0) KV_PV(1, x, 1) KV_PV(2, x, 2) KV_PV(3, x, 3) KV_PV(4, y, 0) KV_PV(5, y, 1) KV_PV(6, y, 2) KV_PV(7, y, 3)
+#undef KV_PV
+            __builtin_amdgcn_sched_barrier(0);
+            vp += step * kMx4TileBytes; vc += step * kMx4TileBytes;
+            issue_v();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // ---- a single split: the final rows; otherwise the partial of this split, in true units
+    const float l_tot = sum_over_kb(l_run);
+    if (sq.n_splits == 1u) {
+        if (c < a.g) {
+            const float w = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
+            float* dst = a.direct_out + (row * a.g + c) * 128u + 32u * kb;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                *reinterpret_cast<f32x4*>(dst + 8 * i) = f32x4{acc[0][i], acc[1][i], acc[2][i], acc[3][i]} * w;
+                *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{acc[4][i], acc[5][i], acc[6][i], acc[7][i]} * w;
+            }
+            if (a.direct_lse && kb == 0)
+                a.direct_lse[row * a.g + c] = l_tot > 0.0f ? (m_run + log2f(l_tot)) * 0.6931471805599453f : -INFINITY;
+        }
+        return;
+    }
+    if (kb == 0) {
+        a.part_ml[part * 32u + c] = m_run;
+        a.part_ml[part * 32u + 16u + c] = l_tot;
+    }
+    if (c < a.g) {
+        float* dst = a.part_acc + (part * 16u + c) * 128u + 32u * kb;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            *reinterpret_cast<f32x4*>(dst + 8 * i) = f32x4{acc[0][i], acc[1][i], acc[2][i], acc[3][i]};
+            *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{acc[4][i], acc[5][i], acc[6][i], acc[7][i]};
+        }
+    }
+}
+
+// a.seqs / d_vside (device-visible) hold n_seq descriptors, a.n_splits = the largest per-sequence split count (0: no sequence has positions),
+// a.direct_out = d_out and a.direct_per_seq = 1; merge = some sequence has several splits (launch_attend_combine behind the attention launch)
+hipError_t launch_attend_k8v4(const AttendArgs& a, const AttendKvSide* d_vside, uint32_t n_seq, bool merge, float* d_out, float* d_lse, hipStream_t s)
+{
+    if (n_seq == 0) return hipSuccess;
+    if (!a.seqs || !d_vside || !a.q16 || a.direct_out != d_out || a.heads % 4u || a.g == 0 || a.g > 16u) return hipErrorInvalidValue;
+    AttendArgs ar = a;
+    const uint32_t rows = n_seq * (a.heads / 4u), splits = a.n_splits ? a.n_splits : 1u;      // (split 0 of a sequence without positions writes its zeros)
+    ar.rows_real = rows;
+    const dim3 gr = a.rows_first ? dim3(rows | 1u, splits) : dim3(splits, rows);
+    hipLaunchKernelGGL(k_attend_k8v4, gr, dim3(256), 0, s, ar, d_vside);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !merge) return e;
+    return launch_attend_combine(a, n_seq, d_out, d_lse, s);
+}
+
+} // namespace speckv

@@ -1,0 +1,120 @@
+// cxl-speckv_amd/csrc/engine_attend_kv.cpp -- Engine::attend_batch_kv, the body behind speckv_ext_attend_kv_batch: one decode step of a
+// batch over the SPLIT POOL ("K8V4": a sequence's K rows in an FP8_E4M3 allocation, its V rows in an MXFP4 allocation), one attention
+// launch (k_attend_k8v4, attend_kv.hip) and, where members have several pieces, the merge behind it
+#include "engine_internal.hpp"
+#include "tuning.hpp"
+
+namespace speckv {
+
+// Sequence i = the allocations k_handles[i] / v_handles[i] with pos_end[i] stored positions; both are read as arrays of regions of
+// num_tokens / 2 pages, region `layer` of either (the addressing of Engine::attend_chunk's split_kv form, judged by the same rule).
+// The workgroup shape is the FP8 batch kernel's, so the launch decision is attend_geometry.hpp's for BatchShape{fp8 = true}: form,
+// dispatch order, one split length, the members' pieces -- with the tuning keys attend_tiles_per_split and attend_order_as_given.
+// ONE form: both allocations of every member in a single run (Allocation::linear_base) and a scale table on K; any other placement
+// (striped over several pools, pages migrated) is refused with SPECKV_ERR_INVAL before anything is launched.
+// The descriptors travel through a slot of the pinned descriptor ring, read in place: not capturable into a HIP graph.
+int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
+                            const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+{
+    if (null_) return no_data_path("speckv_ext_attend_kv_batch");
+    if (n_seq == 0) return SPECKV_OK;
+    if (is_capturing(s)) {
+        SPECKV_ERR("speckv_ext_attend_kv_batch cannot be captured into a HIP graph (its descriptors are staged per call)");
+        return SPECKV_ERR_INVAL;
+    }
+    if (!k_handles || !v_handles || !pos_end || !d_q_f16 || !d_out || g == 0 || g > 16) return SPECKV_ERR_INVAL;
+    if (reinterpret_cast<uintptr_t>(d_q_f16) % 16u || reinterpret_cast<uintptr_t>(d_out) % 16u) return SPECKV_ERR_INVAL;
+    // a region (num_tokens / 2 pages) of an allocation of the split pool: 8 x 128 fp16, region `layer` inside its pages (engine_chunk.cpp: region_ok)
+    const auto region_ok = [&](const Allocation* a, int want, uint32_t end) {
+        if (!a->has_layout || a->scheme != want) return false;
+        const Layout& L = a->layout;
+        if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads != 8 || L.num_tokens % 32 || end % 2 || end > L.num_tokens) return false;
+        return (static_cast<uint64_t>(layer) + 1u) * (L.num_tokens / 2u) <= a->n_pages && layer < 2ull * L.num_layers;
+    };
+    std::vector<AttendSeq> seqs(n_seq);
+    std::vector<AttendKvSide> vside(n_seq);
+    std::vector<uint32_t> tiles(n_seq), pages(n_seq);
+    std::vector<Allocation*> ks(n_seq), vs(n_seq);
+    uint64_t total_tiles = 0;
+    for (uint32_t i = 0; i < n_seq; ++i) {
+        Allocation *k = find(k_handles[i]), *v = find(v_handles[i]);
+        if (!k || !v) return SPECKV_ERR_GENERAL;
+        if (!region_ok(k, SPECKV_COMP_FP8_E4M3, pos_end[i]) || !region_ok(v, SPECKV_COMP_MXFP4, pos_end[i]) ||
+            k->layout.num_tokens != v->layout.num_tokens)
+            return SPECKV_ERR_INVAL;
+        if (!k->linear_base || !k->d_scale_tab || !v->linear_base) {
+            SPECKV_ERR("speckv_ext_attend_kv_batch: sequence %u: the %s allocation's records do not lie in one run (striped over several pools, "
+                       "or pages migrated); this entry has the single-run form only -- speckv_ext_attend_chunk_kv serves any placement",
+                       i, (!k->linear_base || !k->d_scale_tab) ? "K" : "V");
+            return SPECKV_ERR_INVAL;
+        }
+        ks[i] = k; vs[i] = v;
+        const uint32_t region = k->layout.num_tokens / 2u;
+        AttendSeq& q = seqs[i];
+        q = AttendSeq{};
+        q.lin_base = k->linear_base;
+        q.scale_tab = k->d_scale_tab;
+        q.k_first = q.v_first = static_cast<uint64_t>(layer) * region;
+        q.n_pages = pages[i] = pos_end[i] / 2u;
+        q.layer_pages = region;
+        q.stripe_n = 1u;
+        q.n_splits = tiles[i] = (q.n_pages + 15u) / 16u;                 // tiles for now, pieces below
+        total_tiles += tiles[i];
+        vside[i] = AttendKvSide{v->linear_base, static_cast<uint64_t>(layer) * region};       // (region % 16 == 0: a kernel tile is one storage tile)
+    }
+    DeviceScope device_scope(device_);
+    // NULL = the engine's stream and a synchronous call: the query may have been produced on any stream of the caller
+    if (!s) HIP_TRY(hipDeviceSynchronize());
+    hipStream_t st = s ? s : stream_;
+    // the launch decision of the FP8 batch kernel (attend_geometry.hpp), members in one run each
+    const Tuning& t = tuning();
+    const BatchTuning tun{t.attend_tiles_per_split, t.attend_order_as_given, t.attend_fp8_table_regs, t.attend_fp8_striped_table, t.attend_int4_striped_wg};
+    const BatchShape shape{true, false, n_seq, 8u, cus(), false, false};
+    const BatchForm form = batch_form(shape, tun);
+    std::vector<uint32_t> order(n_seq);
+    const bool ordered = batch_dispatch_order(form, tun, pages.data(), n_seq, order.data());
+    const BatchGeometry geo = batch_geometry(kEntryBatch, shape, form, tun, tiles.data(), 0, ordered, nullptr);
+    if (!geo.fits) return SPECKV_ERR_INVAL;
+    const uint64_t parts = assign_pieces(geo, 8u, seqs.data(), n_seq);
+    bool merge = false;
+    for (uint32_t i = 0; i < n_seq; ++i) merge = merge || seqs[i].n_splits > 1u;
+    AttendArgs k{};
+    if (!attend_scratch(k, merge ? parts : 1u, 0, s)) return SPECKV_ERR_NOMEM;
+    // descriptors, then the V sides, then the dispatch order: one slot, read in place by the kernels (Engine::attend_batch)
+    const size_t desc_bytes = n_seq * sizeof(AttendSeq), side_bytes = n_seq * sizeof(AttendKvSide), idx_bytes = n_seq * sizeof(uint32_t);
+    int slot = 0;
+    void* staged = nullptr;
+    RC_TRY(take_seq_slot(desc_bytes + side_bytes + idx_bytes, &slot, &staged));
+    memcpy(staged, seqs.data(), desc_bytes);
+    memcpy(static_cast<uint8_t*>(staged) + desc_bytes, vside.data(), side_bytes);
+    if (ordered) memcpy(static_cast<uint8_t*>(staged) + desc_bytes + side_bytes, order.data(), idx_bytes);
+    uint8_t* d_slot = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_slot), staged, 0));
+    k.heads = 8u;
+    k.g = g;
+    k.n_splits = total_tiles ? geo.max_splits : 0u;
+    k.tiles_per_split = geo.tps;
+    k.q16 = static_cast<const uint16_t*>(d_q_f16);
+    k.scale_log2e = sm_scale * 1.4426950408889634f;
+    k.lin_base = seqs[0].lin_base;                                       // (overridden per sequence)
+    k.seqs = reinterpret_cast<const AttendSeq*>(d_slot);
+    if (ordered) k.order = reinterpret_cast<const uint32_t*>(d_slot + desc_bytes + side_bytes);
+    if (geo.rows_first) k.rows_first = 1u;
+    k.direct_out = d_out;
+    k.direct_lse = d_lse;
+    k.direct_per_seq = 1u;                                               // members with one piece are final, the merge passes them over
+    // behind the asynchronous pool writes on every other caller stream the engine knows (a commit on another stream)
+    for (auto& w : write_evs_)
+        if (w.s != st) HIP_TRY(hipStreamWaitEvent(st, w.ev, 0));
+    for (uint32_t i = 0; i < n_seq; ++i) { note_use(ks[i], s); note_use(vs[i], s); }      // speckv_free waits for this stream
+    // The guard event is recorded on every way out from here on: the slot must not be written again under a kernel still reading it.
+    struct SlotGuard {
+        hipEvent_t ev; hipStream_t st;
+        ~SlotGuard() { if (hipEventRecord(ev, st) != hipSuccess) (void)hipGetLastError(); }
+    } slot_guard{seq_ring_.ev[slot], st};
+    HIP_TRY(launch_attend_k8v4(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), n_seq, merge, d_out, d_lse, st));
+    if (!s) HIP_TRY(hipStreamSynchronize(stream_));
+    return SPECKV_OK;
+}
+
+} // namespace speckv

@@ -693,6 +693,16 @@ hipError_t launch_qk_scores_fp8_linear(const AttendArgs& a, uint32_t n_layers, f
 // batch form: a.seqs (device) holds n_seq descriptors, a.q16 = [n_seq][heads][g][128], a.n_splits = the largest
 // per-sequence split count; d_out [n_seq][heads][g][128]
 hipError_t launch_attend_fp8_batch(const AttendArgs& a, uint32_t n_seq, float* d_out, float* d_lse, hipStream_t s);
+// The split pool's batch decode attention (attend_kv.hip: k_attend_k8v4): K from FP8_E4M3 records, V from MXFP4 records of a second
+// allocation.  a.seqs carries the K side (lin_base, scale_tab, k_first) and the split bookkeeping, as for launch_attend_fp8_batch; the
+// V side rides beside it, one AttendKvSide per sequence: AttendSeq stays 64 bytes and AttendArgs what every other kernel takes by value.
+struct AttendKvSide {
+    const uint8_t* v_base;            // the V allocation's tile-planar run (Allocation::linear_base)
+    uint64_t v_first;                 // first record of the wanted layer's V region: a multiple of kMx4TileRecs
+};
+// a.direct_out == d_out, a.direct_per_seq == 1: sequences with one split are written final, those without positions as zeros / lse -inf;
+// merge: some sequence has several splits -- launch_attend_combine follows on `s`
+hipError_t launch_attend_k8v4(const AttendArgs& a, const AttendKvSide* d_vside, uint32_t n_seq, bool merge, float* d_out, float* d_lse, hipStream_t s);
 
 // every page's record (rec_bytes rounded up to 16) copied to d_new_addr[page], then entries[page].pool_addr = d_new_addr[page]
 hipError_t launch_repack(PageEntry* d_entries, const uint64_t* d_new_addr, uint64_t n, hipStream_t s);

@@ -186,6 +186,20 @@ def quantize_fp8_e4m3(x):
     return _held(e4m3 * s, np.shape(x))
 
 
+def quantize_query_e4m3(q):
+    """The query rows the FP8-score kernels multiply (k_attend_fp8_linear, k_attend_k8v4), float64 in q's shape: per row ([..., D] fp16)
+    scale = max|q| / 448 in fp32 (1 for a row of zeros), q / scale in fp32 rounded to nearest-even E4M3 (saturating at 448) as
+    quantize_fp8_e4m3 rounds, times the scale -- NOT rounded to fp16: the row scale multiplies the score in fp32."""
+    x = np.asarray(q).astype(np.float16).astype(np.float32)
+    mx = np.abs(x).max(axis=-1, keepdims=True)
+    s = np.where(mx > 0, mx / np.float32(448.0), np.float32(1.0)).astype(np.float32)
+    v = np.clip((x / s).astype(np.float32), -448.0, 448.0)
+    _, ex = np.frexp(np.abs(v))
+    quantum = np.exp2(np.maximum(ex - 1, -6) - 3.0)
+    e4m3 = np.rint(v.astype(np.float64) / quantum) * quantum
+    return e4m3 * s.astype(np.float64)
+
+
 def quantize_mxfp4(x):
     """The values an MXFP4 pool holds for x, float64: an MX block is 16 channels of BOTH positions of a page, its E8M0 scale
     2^(floor(log2 max|x|) - 2), the elements E2M1 (0, .5, 1, 1.5, 2, 3, 4, 6; ties to the even code, saturating at 6)."""
@@ -235,14 +249,18 @@ QUANTIZERS = {"fp8_e4m3": quantize_fp8_e4m3, "mxfp4": quantize_mxfp4, "int4_g32"
               "mxfp4_tile_mean": quantize_mxfp4_tile_mean, "mxfp4_top4_fp8": quantize_mxfp4_top4_fp8}
 
 
-def format_accuracy_cpu(k_format, v_format, T=2048, g=8, seed=7001):
+def format_accuracy_cpu(k_format, v_format, T=2048, g=8, seed=7001, query="fp16"):
     """{regime: rel. L2 error} of float64 attention over K as `k_format` and V as `v_format` hold them (names of QUANTIZERS) with the
     exact fp16 query, against float64 attention over the original rows: the "format alone" column of kv_format_accuracy for any pair
-    of formats, without a GPU."""
+    of formats, without a GPU.  query="e4m3": the formats' side takes the query as the FP8-score decode kernels restate it
+    (quantize_query_e4m3) -- what a route through those kernels costs, the query's share included; the reference keeps the fp16 query."""
+    if query not in ("fp16", "e4m3"):
+        raise ValueError('query: "fp16" or "e4m3"')
     K, V, qs, _ = synth_kv(T, g, seed)
     Kq, Vq = QUANTIZERS[k_format](K), QUANTIZERS[v_format](V)
     sm = 1.0 / np.sqrt(D)
-    return {r: _rel(attention_f64(Kq, Vq, qs[r], sm)[0], attention_f64(K, V, qs[r], sm)[0]) for r in REGIMES}
+    seen = (lambda q: q) if query == "fp16" else quantize_query_e4m3
+    return {r: _rel(attention_f64(Kq, Vq, seen(qs[r]), sm)[0], attention_f64(K, V, qs[r], sm)[0]) for r in REGIMES}
 
 
 def kv_split_accuracy(lib, T=2048, g=8, seed=7001):
@@ -275,6 +293,44 @@ def kv_split_accuracy(lib, T=2048, g=8, seed=7001):
             m = _metrics(got, ref, top1_fmt, top1_ref)
             m["format_rel_l2"] = _rel(of, ref)
             m["kernel_rel_l2"] = _rel(got, of)
+            res[r] = {k: round(v, 5) for k, v in m.items()}
+        del keep
+    finally:
+        conn.free_request(0)
+    return res
+
+
+def kv_split_decode_accuracy(lib, T=2048, g=8, seed=7001):
+    """kv_split_accuracy's figures for the split pool's DECODE route on the HIP engine behind `lib`: all T positions (even) go in as a
+    prompt through SpeckvSplitKVConnector and are attended through conn.attend -- speckv_ext_attend_kv_batch, the batch kernel over FP8
+    keys and MXFP4 values.  {regime: metrics}: rel_l2 and its kin against float64 over the original rows with the fp16 query;
+    format_rel_l2 = float64 over the numpy restatement of what the two allocations hold, with the fp16 query; kernel_rel_l2 = the launch
+    against float64 over those values with the query as the kernel restates it (quantize_query_e4m3), so the query's share is in rel_l2
+    and not in kernel_rel_l2."""
+    import torch
+    from .kv_split_connector import SpeckvSplitKVConnector
+    if T % 2:
+        raise ValueError("T even: every position is stored")
+    K, V, qs, _ = synth_kv(T, g, seed)
+    sm = 1.0 / np.sqrt(D)
+    Kq, Vq = quantize_fp8_e4m3(K), quantize_mxfp4(V)
+    conn = SpeckvSplitKVConnector(lib, 2, H, D, (T + 31) // 32 * 32)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    two = lambda a: np.stack([a, a])                                            # the same rows in both layers
+    conn.add_request(0)
+    res = {}
+    try:
+        keep = conn.write_prefill(0, dev(two(K)), dev(two(V)))
+        for r in REGIMES:
+            o = conn.attend(1, [0], dev(qs[r][None]), sm)
+            torch.cuda.synchronize()
+            got = o.cpu().numpy()[0]
+            ref, top1_ref, _ = attention_f64(K, V, qs[r], sm)
+            of, top1_fmt, _ = attention_f64(Kq, Vq, qs[r], sm)
+            oq = attention_f64(Kq, Vq, quantize_query_e4m3(qs[r]), sm)[0]
+            m = _metrics(got, ref, top1_fmt, top1_ref)
+            m["format_rel_l2"] = _rel(of, ref)
+            m["kernel_rel_l2"] = _rel(got, oq)
             res[r] = {k: round(v, 5) for k, v in m.items()}
         del keep
     finally:

@@ -11,12 +11,17 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
 
   add_request / free_request / length   the two allocations of a request; nothing is bound for prefetch
   write_prefill                         one speckv_ext_write_runs per allocation; an odd last position waits in an fp16 tail
-  attend_chunk                          one layer of a step of S >= 1 new positions per request -- a prefill chunk, a draft chain or tree,
-                                        S = 1 the decode step -- causal, under a window, a tree, a tree under a window, split over the chip
+  attend                                one layer of the DECODE step (one new position per request, already held as the tail or stored):
+                                        ONE speckv_ext_attend_kv_batch -- the batch kernel over FP8 keys and MXFP4 values, no fp16 tile is
+                                        materialised -- and one speckv_ext_attend_fold_tail for the requests with an odd length
+  attend_chunk                          one layer of a step of S >= 1 new positions per request -- a prefill chunk, a draft chain or tree --
+                                        causal, under a window, a tree, a tree under a window, split over the chip (S = 1 works, but a
+                                        64-row query block then carries rows_per_pos live rows: attend is the decode route)
   commit                                the accepted prefix of a step into the pool: one speckv_ext_write_pairs per allocation
 
-Not in this class: the planned and captured decode kernels (decode goes through the chunk walk), load_paged /
-store_paged, the shared-prefix fold, fork, truncate, begin_step and the K pre-scale."""
+Not in this class: the planned and captured decode route (plan_step, HIP graphs: attend stages its descriptors
+per call), sliding windows on attend, multi-position steps on the decode kernel (attend_spec), load_paged / store_paged, the
+shared-prefix fold, fork, truncate, begin_step and the K pre-scale."""
 from typing import Dict, Sequence
 
 from . import kv_connector as _kc
@@ -54,6 +59,8 @@ class SpeckvSplitKVConnector:
         self._epoch = 0                                       # moves with every length: what a step derives from (batch, lengths) is keyed by it
         self._tails = (None, None, None, None)                # key, tail_idx, K rows, V rows of the step's requests with an odd length
         self._tree = (None, None, None)                       # key, mask rows, depths of the step's tree
+        self._fold = (None,)                                  # attend: key, then what a step's calls share -- the count and device indices of the
+                                                              # requests with an odd length, the handle arrays, the stored lengths
 
     # ------------------------------------------------------------------ requests
     def add_request(self, req_id: int):
@@ -144,6 +151,47 @@ class SpeckvSplitKVConnector:
                 depths = on_device(np.asarray(SpeckvKVConnector.chunk_tree_depths(parents, len(reqs)), dtype=np.uint32).view(np.int32))
             self._tree = (key, masks, depths)
         return self._tree[1:]
+
+    def attend(self, layer: int, req_ids: Sequence[int], q, sm_scale: float, stream=None):
+        """softmax(q.K^T * sm_scale).V of one layer for the batch over everything the requests hold -- the decode step.  q
+        [batch][heads][g][dim] fp16 (g = 1..16 query rows per kv head, GQA); returns [batch][heads][g][dim] fp32, shapes as
+        SpeckvKVConnector.attend.  Changes no state.
+        ONE speckv_ext_attend_kv_batch call (with a log-sum-exp buffer) over the stored positions, then -- only if some request has an
+        odd length -- ONE speckv_ext_attend_fold_tail call that folds the fp16 tails into the rows of those requests.  The query enters
+        the stored part as E4M3 x a row scale (the FP8 batch kernel's quantisation), the stored K as its E4M3 values with the block
+        scale on the score, the stored V as the fp16 values of its MXFP4 records; the tail is folded with the fp16 query.
+        The library serves allocations whose records lie in one run (an engine with one pool); for a striped or migrated placement it
+        refuses with SpeckvError (status -4, SPECKV_ERR_INVAL) and the error passes through: there is no silent fall-back -- such
+        a caller goes through attend_chunk with the step's new rows."""
+        import numpy as np
+        import torch
+        if len(q.shape) != 4:
+            raise ValueError("q must be [batch][heads][g][dim]")
+        B, H, G, D = (int(x) for x in q.shape)
+        if (H, D) != (self.H, self.D) or B != len(req_ids) or not 1 <= G <= 16:
+            raise ValueError("q must be [batch][heads][g][dim] with g = 1..16 and one row block per request")
+        if not 0 <= layer < self.L:
+            raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
+        reqs = [self.requests[r] for r in req_ids]
+        out = torch.empty((B, H, G, D), dtype=torch.float32, device="cuda")
+        lse = torch.empty((B, H, G), dtype=torch.float32, device="cuda")
+        row = self.H * self.D
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):
+                q = q.contiguous()
+                _, tk, tv = self._step_tails(req_ids, reqs)
+                key = (tuple(req_ids), self._epoch)
+                if self._fold[0] != key:          # once per step: the same for every layer (the host's share of a 256-request call counts)
+                    odd = [b for b, r in enumerate(reqs) if r.length & 1]
+                    self._fold = (key, len(odd), _kc._device_index(odd) if odd else None,
+                                  np.asarray([r.k_handle for r in reqs], dtype=np.uint64), np.asarray([r.v_handle for r in reqs], dtype=np.uint64),
+                                  np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32))
+                _, n_odd, rows, k_handles, v_handles, pos_end = self._fold
+            self.lib.attend_kv_batch(k_handles, v_handles, layer, q.data_ptr(), G, pos_end, sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+            if n_odd:
+                self.lib.attend_fold_tail(n_odd, rows.data_ptr(), self.H, G, q.data_ptr(), tk.data_ptr() + 2 * layer * row,
+                                          tv.data_ptr() + 2 * layer * row, self.L * row, sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+        return out
 
     def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, splits=1,
                      window=None, parents=None):

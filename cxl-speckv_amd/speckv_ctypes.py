@@ -136,6 +136,7 @@ _EXT_SIGNATURES = {
     "speckv_ext_qk_scores_fp8_layers": [c_uint64, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p],
     "speckv_ext_attend_fp8": [c_uint64, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_fp8_batch": [c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_kv_batch": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_int4_batch": [c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_batch_plan": [c_uint32, ctypes.POINTER(c_uint64), _u32p, c_uint32, c_void_p, c_size_t, c_void_p],
     "speckv_ext_attend_batch_plan_window": [c_uint32, ctypes.POINTER(c_uint64), _u32p, _u32p, c_uint32, c_uint32, c_void_p, c_size_t, c_void_p],
@@ -663,6 +664,17 @@ class SpeckvLib:
         pe = pos_end if isinstance(pos_end, ctypes.Array) else (c_uint32 * n)(*pos_end)
         self._ext("speckv_ext_attend_fp8_batch", n, hs, layer, c_void_p(d_q_f16), g, pe, ctypes.c_float(sm_scale),
                   c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
+
+    def attend_kv_batch(self, k_handles, v_handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse=None, stream=None):
+        """One decode step of a batch over a split pool (speckv_ext_attend_kv_batch): K of `layer` = region `layer` (num_tokens / 2 pages) of
+        the FP8 allocation k_handles[i], V = region `layer` of the MXFP4 allocation v_handles[i]; d_q_f16 [n][heads][g][128] fp16, d_out
+        [n][heads][g][128] fp32, d_lse optional [n][heads][g].  k_handles / v_handles / pos_end: numpy arrays (uint64 / uint32), ctypes
+        arrays or sequences; None stands for a NULL array (for the library to refuse)."""
+        n = len(pos_end if k_handles is None and v_handles is None else (v_handles if k_handles is None else k_handles))
+        handles = lambda h: None if h is None else as_arr(h, c_uint64, n)
+        self._ext("speckv_ext_attend_kv_batch", n, handles(k_handles), handles(v_handles), layer, c_void_p(d_q_f16), g,
+                  None if pos_end is None else as_arr(pos_end, c_uint32, n), ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0),
+                  c_void_p(stream or 0))
 
     def attend_int4_batch(self, handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse=None, stream=None):
         """handles / pos_end: sequences of ints, or ready ctypes arrays (c_uint64 / c_uint32) that a caller reuses over

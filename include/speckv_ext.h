@@ -1168,6 +1168,42 @@ speckv_status_t speckv_ext_attend_chunk_kv(uint32_t n_seq, const speckv_handle_t
                                            const uint32_t* d_depth, uint32_t window /* 0: none */, uint32_t n_splits,
                                            float sm_scale, float* d_out, float* d_lse, void* stream);
 
+/* speckv_ext_attend_kv_batch: one DECODE STEP of a batch over a SPLIT POOL ("K8V4", see speckv_ext_attend_chunk_kv) -- the fused
+ * attention of ONE layer for n_seq sequences over the stored positions [0, pos_end[i]), one new position per sequence with g query rows
+ * per kv head, in one attention launch (and a merge launch where sequences are cut into pieces).  The decode-shaped counterpart of
+ * speckv_ext_attend_chunk_kv, whose 64-row query blocks carry 1..16 live rows in a decode step and decode every tile to fp16 for them:
+ * here K feeds v_mfma_f32_16x16x32_fp8_fp8 as it lies in the FP8 record and V is widened from the MXFP4 record in registers
+ * (v_cvt_scalef32_pk_f16_fp4), no fp16 K or V is materialised.  An additive entry: SPECKV_EXT_ABI_VERSION stays what it is.
+ *   k_handles, v_handles, pos_end : host arrays of n_seq      d_q_f16 : [n_seq][8][g][128] fp16 (device, 16-byte aligned)
+ *   d_out : [n_seq][8][g][128] fp32 (16-byte aligned)         d_lse : optional [n_seq][8][g] fp32 log-sum-exp of the scaled scores
+ * Shapes and stream rules are those of speckv_ext_attend_fp8_batch: g = 1..16, asynchronous on `stream` (the host arrays are copied
+ * before the call returns; NULL = the engine's stream and a synchronous call), calls on several streams are ordered by the library
+ * (one scratch buffer for the partials).  The call is ordered behind the asynchronous pool writes on every caller stream the engine
+ * knows.  A sequence with pos_end[i] == 0 gets zeros and lse = -inf; a position the connector still holds outside the pool (an odd
+ * length) is folded in afterwards by speckv_ext_attend_fold_tail, which is why a caller with such sequences passes d_lse.
+ * Addressing.  As speckv_ext_attend_chunk_kv: both allocations are arrays of REGIONS of num_tokens / 2 pages, K of `layer` is region
+ * `layer` of k_handles[i], V of `layer` region `layer` of v_handles[i]; stored position p lies in page layer * num_tokens / 2 + p / 2.
+ * Values.  The query is quantised by the kernel to E4M3 x a row scale (max|q| / 448 over the row, 1 for a zero row) exactly as
+ * speckv_ext_attend_fp8_batch does.  A stored K element enters the score as the E4M3 value of its record, the page's block scale
+ * multiplies the score in fp32.  A stored V element enters as the fp16 value speckv_ext_fetch_range decodes from the MXFP4 record; the
+ * softmax weights meet it in fp16, accumulation is fp32.  A page never written reads as zeros: its positions score 0 (not -inf).
+ * Placement.  ONE form: the records of both allocations of every sequence lie in a single run of one pool (what an engine with one
+ * pool gives every allocation).  Striped and migrated placements are served by speckv_ext_attend_chunk_kv only.
+ * The per-call descriptors travel through a pinned slot that later calls reuse: NOT capturable into a HIP graph.
+ *   SPECKV_ERR_INVAL    k_handles, v_handles, pos_end, d_q_f16 or d_out NULL (with n_seq != 0), d_q_f16 or d_out not 16-byte aligned,
+ *                       g == 0 or g > 16, a K allocation whose scheme is not SPECKV_COMP_FP8_E4M3, a V allocation whose scheme is not
+ *                       SPECKV_COMP_MXFP4, a layout that is not 8 heads x 128 fp16 or whose num_tokens is not a multiple of 32,
+ *                       num_tokens that differ between the two allocations of a sequence, pos_end[i] odd or > num_tokens,
+ *                       (layer + 1) * num_tokens / 2 beyond either allocation's pages, an allocation whose records do not lie in one
+ *                       run (the error text names the sequence), a capturing stream -- nothing is launched, d_out is untouched
+ *   SPECKV_ERR_NOMEM    the scratch buffer of the partials could not grow -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle
+ *   SPECKV_ERR_DRIVER   an engine without a device ("/dev/null"): no data path
+ * speckv_free of either allocation waits for `stream`. */
+speckv_status_t speckv_ext_attend_kv_batch(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                           uint32_t layer, const void* d_q_f16, uint32_t g, const uint32_t* pos_end,
+                                           float sm_scale, float* d_out, float* d_lse, void* stream);
+
 /* speckv_ext_attend_chunk_tree_window: a DRAFT TREE on a SLIDING-WINDOW (local) layer -- the tree step of the local layers of the
  * models speckv_ext_attend_chunk_window names, whose global layers take the tree step through speckv_ext_attend_chunk_masked / _split.
  * The arguments of speckv_ext_attend_chunk_split in the same order with `d_depth, window` directly behind mask_words.  Everything

@@ -4,15 +4,17 @@
 One process, layer 0 of 2, rows_per_pos = 4.
   chunk   a 512-position chunk over 8k and 32k stored positions, one and four requests: SpeckvSplitKVConnector.attend_chunk (K8V4) and
           SpeckvKVConnector.attend_chunk over an FP8 and an MXFP4 pool -- the same kernel body, three instances; splits = 1 everywhere.
-  decode  a 256-request step of ONE new position at 2k and 8k stored positions: K8V4 through attend_chunk (n_new = 1; splits = 1 and the
-          library's rule, splits = 0) next to FP8 through SpeckvKVConnector.attend -- the planned decode kernels, which quantise the query.
+  decode  a 256-request step of ONE new position at 2k and 8k stored positions: K8V4 through SpeckvSplitKVConnector.attend (the batch
+          decode kernel over FP8 keys and MXFP4 values, which quantises the query) and through attend_chunk (n_new = 1; splits = 1 and the
+          library's rule, splits = 0) next to FP8 and MXFP4 through SpeckvKVConnector.attend -- the planned decode kernels.
 Device time between two HIP events around one call; clock ramp and warm-up untimed; the variants of a shape timed IN TURN within every
 round, per round the median of --reps calls, --rounds rounds, the median of the rounds' medians; the spread (max - min of the rounds'
 medians) stands beside each figure.  Bytes per call are the records the call has to read, from the shapes: requests x stored positions x
 (K bytes + V bytes per position and layer: FP8 1024, MXFP4 544); GB/s = those bytes over the time (a chunk's query blocks read them
 again from the caches: not counted).
 
-    python profiles/tools/k8v4_bench.py [--reps 5] [--rounds 3] [--out profiles/k8v4.txt]
+    python profiles/tools/k8v4_bench.py [--reps 5] [--rounds 3] [--sections chunk,decode] [--out profiles/k8v4.txt]
+(profiles/k8v4_decode.txt: --sections decode --out profiles/k8v4_decode.txt)
 """
 import argparse
 import os
@@ -56,6 +58,7 @@ def main():
     ap.add_argument("--chunk-seqs", default="1,4")
     ap.add_argument("--decode-ctxs", default="2048,8192")
     ap.add_argument("--decode-seqs", type=int, default=256)
+    ap.add_argument("--sections", default="chunk,decode")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "k8v4.txt"))
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -104,8 +107,10 @@ def main():
 
     say(f"K8V4 split pool next to FP8 and MXFP4: layer 0 of {L}, rows_per_pos {R}, {torch.cuda.get_device_properties(0).multi_processor_count} CUs "
         f"(profiles/tools/k8v4_bench.py, {a.rounds} rounds of {a.reps} calls, variants in turn; median of the rounds' medians)")
-    say(f"chunk: {S} new positions per request through attend_chunk, splits = 1")
-    for B in [int(s) for s in a.chunk_seqs.split(",")]:
+    sections = a.sections.split(",")
+    if "chunk" in sections:
+        say(f"chunk: {S} new positions per request through attend_chunk, splits = 1")
+    for B in [int(s) for s in a.chunk_seqs.split(",")] if "chunk" in sections else []:
         for ctx in [int(c) for c in a.chunk_ctxs.split(",")]:
             lib = pkg.SpeckvLib(pkg.library_path(), "hip:0")
             try:
@@ -119,8 +124,10 @@ def main():
             finally:
                 lib.finalize()
     B = a.decode_seqs
-    say(f"decode: {B} requests, ONE new position each; K8V4 through attend_chunk (n_new = 1), FP8 through attend (the planned decode kernels)")
-    for ctx in [int(c) for c in a.decode_ctxs.split(",")]:
+    if "decode" in sections:
+        say(f"decode: {B} requests, ONE new position each; K8V4 through attend (the batch decode kernel) and through attend_chunk (n_new = 1), "
+            f"FP8 and MXFP4 through attend (the planned decode kernels)")
+    for ctx in [int(c) for c in a.decode_ctxs.split(",")] if "decode" in sections else []:
         lib = pkg.SpeckvLib(pkg.library_path(), "hip:0")
         try:
             made = pools(lib, ctx + 32, B, ctx)
@@ -129,13 +136,16 @@ def main():
             split, ids = made["k8v4"]
             fp8, _ = made["fp8"]
             mx4, _ = made["mxfp4"]
-            names = ["k8v4 chunk splits=1", "k8v4 chunk splits=0", "fp8 chunk splits=1", "fp8 attend", "mxfp4 attend"]
-            fns = [lambda: split.attend_chunk(0, ids, q, kn, vn, sm), lambda: split.attend_chunk(0, ids, q, kn, vn, sm, splits=0),
+            names = ["k8v4 attend", "k8v4 chunk splits=1", "k8v4 chunk splits=0", "fp8 chunk splits=1", "fp8 attend", "mxfp4 attend"]
+            fns = [lambda: split.attend(0, ids, qd, sm), lambda: split.attend_chunk(0, ids, q, kn, vn, sm), lambda: split.attend_chunk(0, ids, q, kn, vn, sm, splits=0),
                    lambda: fp8.attend_chunk(0, ids, q, kn, vn, sm), lambda: fp8.attend(0, ids, qd, sm), lambda: mx4.attend(0, ids, qd, sm)]
             got = report(f"{B} x {ctx:5d} + 1", names, in_turn(torch, fns, a.reps, a.rounds), {n: B * ctx * REC[n] for n in REC})
             best = min(got["k8v4 chunk splits=1"], got["k8v4 chunk splits=0"])
             say(f"  {'':22s} k8v4 chunk route / fp8 attend = {best / got['fp8 attend']:.2f} x the time at {REC['k8v4'] / REC['fp8']:.3f} of the bytes; "
                 f"fp8 chunk route / fp8 attend = {got['fp8 chunk splits=1'] / got['fp8 attend']:.2f} x")
+            say(f"  {'':22s} k8v4 attend / k8v4 chunk route = {got['k8v4 attend'] / best:.3f} of the time; k8v4 attend / fp8 attend = "
+                f"{got['k8v4 attend'] / got['fp8 attend']:.3f} ({REC['k8v4'] / REC['fp8']:.3f} of the bytes); k8v4 attend / mxfp4 attend = "
+                f"{got['k8v4 attend'] / got['mxfp4 attend']:.3f} ({REC['k8v4'] / REC['mxfp4']:.3f} of the bytes)")
         finally:
             lib.finalize()
 
