@@ -200,13 +200,20 @@ def quantize_query_e4m3(q):
     return e4m3 * s.astype(np.float64)
 
 
+def mxfp4_codes(x):
+    """The E8M0 codes an MXFP4 pool holds for x ([T][H][D] fp16), int64 [T / 2][H * D / 16]: one per page and block of 16 channels (of
+    BOTH positions of the page), floor(log2 max|x|) - 2 + 127 clipped to 0 .. 254, 0 for a block of zeros."""
+    b = _pages(x).astype(np.float64).reshape(-1, 2, N // 32, 16)                 # [page][position][group][16 channels]
+    amax = np.abs(b).max(axis=(1, 3))
+    _, ex = np.frexp(amax)
+    return np.where(amax > 0, np.clip(ex - 1 - 2 + 127, 0, 254), 0).astype(np.int64)
+
+
 def quantize_mxfp4(x):
     """The values an MXFP4 pool holds for x, float64: an MX block is 16 channels of BOTH positions of a page, its E8M0 scale
-    2^(floor(log2 max|x|) - 2), the elements E2M1 (0, .5, 1, 1.5, 2, 3, 4, 6; ties to the even code, saturating at 6)."""
+    2^(floor(log2 max|x|) - 2) (mxfp4_codes), the elements E2M1 (0, .5, 1, 1.5, 2, 3, 4, 6; ties to the even code, saturating at 6)."""
     b = _pages(x).astype(np.float64).reshape(-1, 2, N // 32, 16)                 # [page][position][group][16 channels]
-    amax = np.abs(b).max(axis=(1, 3), keepdims=True)
-    _, ex = np.frexp(amax)
-    code = np.where(amax > 0, np.clip(ex - 1 - 2 + 127, 0, 254), 0)
+    code = mxfp4_codes(x)[:, None, :, None]
     a = np.abs(np.ldexp(b, 127 - code))
     idx = sum((a > m).astype(np.int64) for m in (0.25, 1.25, 2.5, 5.0)) + sum((a >= m).astype(np.int64) for m in (0.75, 1.75, 3.5))
     mag = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])[idx]

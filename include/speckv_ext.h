@@ -1181,6 +1181,7 @@ speckv_status_t speckv_ext_attend_chunk_kv(uint32_t n_seq, const speckv_handle_t
  * (one scratch buffer for the partials).  The call is ordered behind the asynchronous pool writes on every caller stream the engine
  * knows.  A sequence with pos_end[i] == 0 gets zeros and lse = -inf; a position the connector still holds outside the pool (an odd
  * length) is folded in afterwards by speckv_ext_attend_fold_tail, which is why a caller with such sequences passes d_lse.
+ * The entry only reads, so a pair may appear many times in one call (each time with its own pos_end and query rows).
  * Addressing.  As speckv_ext_attend_chunk_kv: both allocations are arrays of REGIONS of num_tokens / 2 pages, K of `layer` is region
  * `layer` of k_handles[i], V of `layer` region `layer` of v_handles[i]; stored position p lies in page layer * num_tokens / 2 + p / 2.
  * Values.  The query is quantised by the kernel to E4M3 x a row scale (max|q| / 448 over the row, 1 for a zero row) exactly as
@@ -1195,7 +1196,9 @@ speckv_status_t speckv_ext_attend_chunk_kv(uint32_t n_seq, const speckv_handle_t
  *                       SPECKV_COMP_MXFP4, a layout that is not 8 heads x 128 fp16 or whose num_tokens is not a multiple of 32,
  *                       num_tokens that differ between the two allocations of a sequence, pos_end[i] odd or > num_tokens,
  *                       (layer + 1) * num_tokens / 2 beyond either allocation's pages, an allocation whose records do not lie in one
- *                       run (the error text names the sequence), a capturing stream -- nothing is launched, d_out is untouched
+ *                       run (the error text names the sequence), a member in more than 2048 pieces (the merge takes 2048 partials a
+ *                       row at most; the library's own split rule stays far below, a forced attend_tiles_per_split may not), a
+ *                       capturing stream -- nothing is launched, d_out is untouched
  *   SPECKV_ERR_NOMEM    the scratch buffer of the partials could not grow -- nothing is launched
  *   SPECKV_ERR_GENERAL  an unknown handle
  *   SPECKV_ERR_DRIVER   an engine without a device ("/dev/null"): no data path
