@@ -2,7 +2,7 @@
 // records (BASELINE config 5 "fused dequant-matvec", SURVEY 8a row A22: both halves,
 // q.K^T and p.V; no reference counterpart, parity is against oracle/orc_attend_fp8).
 //
-// No fp16 K or V is ever materialised: K bytes feed v_mfma_f32_16x16x32_fp8_fp8 as they
+// No fp16 K or V is ever materialised: K bytes feed the FP8 MFMA (16x16x32) as they
 // lie in the record; V bytes are widened to f16 in registers (exact) and feed
 // v_mfma_f32_16x16x32_f16 against the softmax weights.
 //
@@ -26,30 +26,12 @@
 //           -> lane (c, kb) holds out[query row c][64blk + 16kb + 4i + t].
 #include "kernels.hpp"
 #include "tuning.hpp"
-#include "codec_device.hpp"          // the exact reciprocal divide of the codecs (div_by_scale and friends)
-#include "attend_device.hpp"
+#include "attend_fp8_device.hpp"     // the tile arithmetic shared with attend_kv.hip: query operand, scores, softmax step, FP8 p.V, epilogue
 #include <cstdlib>
 
 namespace speckv {
 
 namespace {
-
-// (global-address-space loads, SPECKV_GP: attend_device.hpp)
-__device__ __forceinline__ uint2 ldg8(const uint8_t* p)
-{
-    const u32x2 v = __builtin_nontemporal_load(SPECKV_GP(u32x2, p));
-    return make_uint2(v.x, v.y);
-}
-__device__ __forceinline__ uint32_t ldg4(const uint8_t* p)
-{
-    return __builtin_nontemporal_load(SPECKV_GP(uint32_t, p));
-}
-// four floats of a scale table (temporal: the table is small and every workgroup of a layer reads it), global address space as above
-__device__ __forceinline__ f32x4 ldg_f4(const float* p)
-{
-    typedef const f32x4 __attribute__((address_space(1)))* gp;
-    return *(gp)(reinterpret_cast<uintptr_t>(p));
-}
 
 // Registers of one 32-position tile as loaded, and the per-wave running state.
 struct AttTile {
@@ -69,15 +51,11 @@ __device__ __forceinline__ void att_scores(const uint4 (&kx)[2][2], const float 
 {
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-        const uint32_t kd[8] = {kx[b][0].x, kx[b][0].y, kx[b][0].z, kx[b][0].w, kx[b][1].x, kx[b][1].y, kx[b][1].z, kx[b][1].w};
-        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int st = 0; st < 4; ++st)
-            s = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(kd[2 * st], kd[2 * st + 1]), pack64(qd[2 * st], qd[2 * st + 1]), s, 0, 0, 0);
+        const f32x4 s = fp8_scores_raw(kx[b][0], kx[b][1], qd);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int j = 4 * b + i;
-            sc[j] = inr[j >> 1] ? s[i] * ks[j >> 1] * qscale : -INFINITY;
+            sc[j] = inr[j >> 1] ? s[i] * ks[j >> 1] * qscale : -INFINITY;      // (sum x page scale) x query scale: this form's own order
         }
     }
 }
@@ -85,14 +63,8 @@ __device__ __forceinline__ void att_scores(const uint4 (&kx)[2][2], const float 
 // then out^T += V^T . P^T from the V registers.
 __device__ __forceinline__ void att_softmax_pv(const float (&sc)[8], const uint32_t (&vx)[2][8], const float (&vs)[4], AttState& S)
 {
-    float mx = sc[0];
-#pragma unroll
-    for (int j = 1; j < 8; ++j) mx = fmaxf(mx, sc[j]);
-    mx = max_over_kb(mx);
-    const float m_new = fmaxf(S.m_run, mx);
-    const float m_use = (m_new == -INFINITY) ? 0.0f : m_new;              // a fully masked row stays at weight 0
-    const float alpha = __builtin_amdgcn_exp2f(S.m_run - m_use);
-    S.m_run = m_new;
+    float m_use;
+    const float alpha = att_softmax_step(sc, S.m_run, m_use);
     float vmx = fmaxf(fmaxf(vs[0], vs[1]), fmaxf(vs[2], vs[3]));
     vmx = max_over_kb(vmx);                                               // the tile's largest V page scale
     const float vinv = vmx > 0.0f ? 1.0f / vmx : 0.0f;
@@ -202,41 +174,7 @@ __device__ __forceinline__ void quantize_query_operand(const uint16_t* qsrc, boo
     }
     row_scale = live ? sc : 1.0f;
 }
-// The same from the four 16-byte pieces of the row already in registers (the fast kernels ask for them behind their first tile's
-// requests), with the 32 quotients through the row's reciprocal: div_by_scale is bit-identical to the IEEE divide for an fp16
-// dividend and a scale m / 448 (exhaustive device check: test_fast_division_is_exact); rows with inf / NaN keep the divide.
-__device__ __forceinline__ void quantize_query_rows(const u32x4 (&w4)[4], bool live, uint32_t (&qd)[8], float& row_scale)
-{
-    float xq[32];
-    float mx = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t ws[4] = {w4[i].x, w4[i].y, w4[i].z, w4[i].w};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            xq[8 * i + k] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(ws[k >> 1] >> (16 * (k & 1)))));
-            mx = fmaxf(mx, fabsf(xq[8 * i + k]));
-        }
-    }
-    mx = max_over_kb(mx);
-    const bool finite = mx < INFINITY;
-    const float sc = (mx > 0.0f) ? (finite ? div448_of_f16_value(mx) : mx / 448.0f) : 1.0f;
-    const float rcp = finite ? rcp_of_scale(sc) : 0.0f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        float v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float x = xq[4 * i + k];
-            const float qt = finite ? __builtin_copysignf(div_by_scale(x, sc, rcp), x) : x / sc;
-            v[k] = live ? fminf(fmaxf(qt, -448.0f), 448.0f) : 0.0f;
-        }
-        int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-        pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
-        qd[i] = static_cast<uint32_t>(pk);
-    }
-    row_scale = live ? sc : 1.0f;
-}
+// (the fast kernels take the same operand through the row's reciprocal: fp8_quantize_query, attend_fp8_device.hpp)
 
 } // namespace
 
@@ -286,7 +224,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const uint32_t pg = pg0 + (r < 2 ? 2u * kb + r : 8u + 2u * kb + (r - 2));
+            const uint32_t pg = pg0 + att_slot_page(kb, r);
             d.vaddr[r] = a.zero_page + 4u * c;
             d.ks[r] = 0.0f;
             d.vs[r] = 0.0f;
@@ -309,7 +247,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         bool inr[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            inr[r] = pg0 + (r < 2 ? 2u * kb + r : 8u + 2u * kb + (r - 2)) < a.n_pages;
+            inr[r] = pg0 + att_slot_page(kb, r) < a.n_pages;
             T.ks[r] = cur.ks[r];
             T.vs[r] = cur.vs[r];
         }
@@ -419,47 +357,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
         __syncthreads();
     }
 
-    // query operand: row c of this head, d = 32kb + 8*step + e, quantised here exactly as k_quantize_q_e4m3 does
-    // (scale = max|q|/448 over the row, 1 if zero; e4m3 of clamp(q/scale)); rows >= g are zero.  Called BEHIND the first tile's
-    // requests: descriptor -> {tile, query} -> scores instead of descriptor -> query -> tile -> scores, and the 32 quotients through
-    // the row's reciprocal (div_by_scale: bit-identical for these operands, exhaustive check in test_fast_division_is_exact)
-    // instead of 32 IEEE divides -- a launch of 256 x 1k lasts 100 us and this stood in front of every workgroup's first load.
+    // query operand: row c of this head (d split: see quantize_query_operand), rows >= g are zero.  Called BEHIND the first tile's
+    // requests (fp8_query_operand, attend_fp8_device.hpp).
     uint32_t qd[8];
     float qscale = 1.0f;
-    auto quantise_query = [&]() {
-        float xq[32];
-        float mx = 0.0f;
-        const uint16_t* qsrc = a.q16 + (row * a.g + min(c, a.g - 1u)) * 128u + kb * 16u;     // d split: see quantize_query_operand
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint4 w = *reinterpret_cast<const uint4*>(qsrc + 8 * (i & 1) + 64 * (i >> 1));
-            const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                xq[8 * i + k] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(ws[k >> 1] >> (16 * (k & 1)))));
-                mx = fmaxf(mx, fabsf(xq[8 * i + k]));
-            }
-        }
-        mx = max_over_kb(mx);
-        const bool finite = mx < INFINITY;                                // (inf / NaN rows: the IEEE divide, as before)
-        const float sc = (mx > 0.0f) ? (finite ? div448_of_f16_value(mx) : mx / 448.0f) : 1.0f;
-        const float rcp = finite ? rcp_of_scale(sc) : 0.0f;
-        const bool live = c < a.g;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float x = xq[4 * i + k];
-                const float qt = finite ? __builtin_copysignf(div_by_scale(x, sc, rcp), x) : x / sc;
-                v[k] = live ? fminf(fmaxf(qt, -448.0f), 448.0f) : 0.0f;
-            }
-            int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-            pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
-            qd[i] = static_cast<uint32_t>(pk);
-        }
-        qscale = (live ? sc : 1.0f) * a.scale_log2e;
-    };
+    auto quantise_query = [&]() { fp8_query_operand(a.q16 + (row * a.g + min(c, a.g - 1u)) * 128u + kb * 16u, c < a.g, a.scale_log2e, qd, qscale); };
 
     const uint32_t n_tiles = CLS ? mx4_striped_tiles(a.n_pages, a.stripe_n) : (a.n_pages + 15u) / 16u;
     const uint32_t t0 = split * a.tiles_per_split;
@@ -605,21 +507,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
             // ---- scores
             float sc[8];
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const uint32_t kd[8] = {kx[b][0].x, kx[b][0].y, kx[b][0].z, kx[b][0].w, kx[b][1].x, kx[b][1].y, kx[b][1].z, kx[b][1].w};
-                f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int st = 0; st < 4; ++st)
-                    s = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(kd[2 * st], kd[2 * st + 1]), pack64(qd[2 * st], qd[2 * st + 1]), s, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) sc[4 * b + i] = s[i] * (ks4[2 * b + (i >> 1)] * qscale);
-            }
+            for (int b = 0; b < 2; ++b) fp8_scores(kx[b][0], kx[b][1], qd, ks4, qscale, b, sc);
             // the lane's candidate for the tile's reference V scale (below): the largest scale among its four pages
-            float vcand = WINDOW ? fmaxf(fmaxf(vs4[0], vs4[1]), fmaxf(vs4[2], vs4[3])) : 0.0f;
+            float vcand = WINDOW ? max4(vs4) : 0.0f;
             if (!CLS && ((ragged && tile + 1u == n_tiles) || ((WINDOW ? skip_pos : a.skip_pages) && tile == 0u))) {     // wave-uniform: positions beyond / in front of the range
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const uint32_t pg = tile * 16u + ((j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2));
+                    const uint32_t pg = tile * 16u + att_slot_page(kb, j >> 1);
                     // (a masked page's V scale leaves the tile's reference scale below as well: the page may hold a stale record of any magnitude)
                     if (!WINDOW) {                                           // page-granular: a range that starts inside a tile starts on a page
                         if (pg >= a.n_pages || pg < a.skip_pages) { sc[j] = -INFINITY; vs4[j >> 1] = 0.0f; }
@@ -639,7 +533,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
                     vcand = 0.0f;
 #pragma unroll
                     for (int sl = 0; sl < 4; ++sl) {
-                        const uint32_t pg = tile * 16u + (sl < 2 ? 2u * kb + sl : 8u + 2u * kb + (sl - 2));
+                        const uint32_t pg = tile * 16u + att_slot_page(kb, sl);
                         vcand = fmaxf(vcand, (tile == 0u && 2u * pg + 1u == skip_pos) ? vs4[sl] * 0.0009765625f : vs4[sl]);
                     }
                 }
@@ -650,7 +544,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
                 if (have < 16u) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        const uint32_t pg = (j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2);
+                        const uint32_t pg = att_slot_page(kb, j >> 1);
                         if (pg >= have) sc[j] = -INFINITY;
                     }
                     // (... and their V scales, which the lane holds by slot until cls_scales4 below hands them out: the surplus slots fetch the
@@ -666,52 +560,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
             } else { kp += step * 32768u; kt += step * 16u; tile_k += step; }
             issue_k();
             __builtin_amdgcn_sched_barrier(0);
-            // ---- online softmax of query row c
-            float mx = sc[0];
-#pragma unroll
-            for (int j = 1; j < 8; ++j) mx = fmaxf(mx, sc[j]);
-            mx = max_over_kb(mx);
-            const float m_new = fmaxf(m_run, mx);
-            const float m_use = (m_new == -INFINITY) ? 0.0f : m_new;
-            const float f = __builtin_amdgcn_exp2f(m_run - m_use);
-            m_run = m_new;
+            // ---- online softmax of query row c; the tile's V reference scale (its largest V page scale) and the weights in units of it
+            float m_use;
+            const float f = att_softmax_step(sc, m_run, m_use);
             if (CLS) vs4 = cls_scales4(vs_raw);
-            // the tile's V reference scale (its largest V page scale) and the weights in units of it
-            const float vmx = max_over_kb(WINDOW ? vcand : fmaxf(fmaxf(vs4[0], vs4[1]), fmaxf(vs4[2], vs4[3])));
-            const float vref_t = vmx > 0.0f ? vmx : vref;
-            const float rinv = __builtin_amdgcn_rcpf(vref_t);
-            float psum = 0.0f;
             f16x8 P;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float p = __builtin_amdgcn_exp2f(sc[j] - m_use);
-                psum += p;
-                P[j] = static_cast<_Float16>(p * (vs4[j >> 1] * rinv));
-            }
-            l_run = l_run * f + psum;
-            const float fa = f * (vref * rinv);                            // acc: old max -> new max, old V reference -> new
-            vref = vref_t;
+            const float fa = fp8_v_weights(sc, m_use, f, vs4, WINDOW ? vcand : max4(vs4), vref, l_run, P);
             // ---- out^T += V^T . P^T, accumulated in place
-            uint32_t w[4][4];                                             // [row pair][byte pair of the 8 d]
-#pragma unroll
-            for (int jp = 0; jp < 4; ++jp) {
-                w[jp][0] = __builtin_amdgcn_perm(vx[2 * jp + 1].x, vx[2 * jp].x, 0x05010400u);
-                w[jp][1] = __builtin_amdgcn_perm(vx[2 * jp + 1].x, vx[2 * jp].x, 0x07030602u);
-                w[jp][2] = __builtin_amdgcn_perm(vx[2 * jp + 1].y, vx[2 * jp].y, 0x05010400u);
-                w[jp][3] = __builtin_amdgcn_perm(vx[2 * jp + 1].y, vx[2 * jp].y, 0x07030602u);
-            }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                f16x8 V;
-#pragma unroll
-                for (int jp = 0; jp < 4; ++jp) {
-                    const f16x2 h = (t & 1) ? __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[jp][t >> 1], 1.0f, true)
-                                            : __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[jp][t >> 1], 1.0f, false);
-                    V[2 * jp] = h.x;
-                    V[2 * jp + 1] = h.y;
-                }
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(V, P, acc[t] * fa, 0, 0, 0);
-            }
+            fp8_pv8(vx, P, fa, acc);
             __builtin_amdgcn_sched_barrier(0);
             if (CLS) {
                 if (step && ++qv_m == cls_m) { qv_m = 0u; ++qv_cls; cls_enter(qv_cls, vfirst32, head * 128u + 8u * c + 4u * kb * 1024u, vp_c, qv_ic, qv_cnt, qv_run); }
@@ -721,37 +577,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TABLE ? 3 :
         }
     }
     // ---- partial result of this split, back in true units (or, single split: the final result)
-    const float l_tot = sum_over_kb(l_run);
-    if (a.direct_out && (!a.direct_per_seq || my_splits == 1u)) {
-        if (c < a.g) {
-            const float w = l_tot > 0.0f ? vref / l_tot : 0.0f;
-            float* dst = a.direct_out + (row * a.g + c) * 128u + 32u * kb;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                *reinterpret_cast<f32x4*>(dst + 8 * i) = f32x4{acc[0][i], acc[1][i], acc[2][i], acc[3][i]} * w;
-                *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{acc[4][i], acc[5][i], acc[6][i], acc[7][i]} * w;
-            }
-            if (a.direct_lse && kb == 0)
-                a.direct_lse[row * a.g + c] = l_tot > 0.0f ? (m_run + log2f(l_tot)) * 0.6931471805599453f : -INFINITY;
-        }
-        return;
-    }
-    if (kb == 0) {
-        a.part_ml[part * 32u + c] = m_run;
-        a.part_ml[part * 32u + 16u + c] = l_tot;
-    }
-    if (c < a.g) {
-        float* dst = a.part_acc + (part * 16u + c) * 128u + 32u * kb;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<f32x4*>(dst + 8 * i) = f32x4{acc[0][i], acc[1][i], acc[2][i], acc[3][i]} * vref;
-            *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{acc[4][i], acc[5][i], acc[6][i], acc[7][i]} * vref;
-        }
-    }
+    att_store_rows8(a, acc, m_run, l_run, vref, a.direct_out && (!a.direct_per_seq || my_splits == 1u), row, part, c, kb);
 }
 
 // ---- linear form, LDS-DMA pipeline ------------------------------------------------------------------------------------
-// Same arithmetic as k_attend_fp8_linear; the tile travels global -> LDS without passing through registers
+// Same arithmetic as k_attend_fp8_linear (the same functions of attend_fp8_device.hpp); the tile travels global -> LDS without passing through registers
 // (global_load_lds_dwordx4, 1 KiB per wave instruction), two tiles deep per wave.  PMC on the register-staged kernel:
 // texture addresser 80 % busy at 0.70 of HBM peak with 14 load instructions per tile and wave (V as 8-byte pieces), waves
 // waiting 83 % of their cycles, VALU 23 % busy.  A head's row of one position is exactly one 128-byte line, so a wave
@@ -1032,7 +862,7 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
             issue_v(t0 + 1u, 1u);
             asm volatile("s_waitcnt vmcnt(13)" : "+v"(qw[0]), "+v"(qw[1]), "+v"(qw[2]), "+v"(qw[3]) :: "memory");
         }
-        quantize_query_rows(qw, c < a.g, qd, qscale);
+        fp8_quantize_query(qw, c < a.g, qd, qscale);
         qscale *= a.scale_log2e;
         const bool ragged = (a.n_pages & 15u) != 0u;
         uint32_t cc_cls = CLS ? t0 / cls_m : 0u, cc_m = CLS ? t0 - cc_cls * cls_m : 0u;      // CLS: (class, tile of the class) the arithmetic is at
@@ -1050,15 +880,7 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
             // ---- scores
             float sc[8];
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const uint32_t kd[8] = {kx[2 * b].x, kx[2 * b].y, kx[2 * b].z, kx[2 * b].w, kx[2 * b + 1].x, kx[2 * b + 1].y, kx[2 * b + 1].z, kx[2 * b + 1].w};
-                f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int st = 0; st < 4; ++st)
-                    s = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(kd[2 * st], kd[2 * st + 1]), pack64(qd[2 * st], qd[2 * st + 1]), s, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) sc[4 * b + i] = s[i] * (ks4[2 * b + (i >> 1)] * qscale);
-            }
+            for (int b = 0; b < 2; ++b) fp8_scores(kx[2 * b], kx[2 * b + 1], qd, ks4, qscale, b, sc);
             if (TABLE) {
                 // behind the score MFMAs (they run while the entries make their way through LDS): the entries of tile + 2 are parked,
                 // its eight request addresses formed, its K requests go out; the entries of tile + 4 are asked for
@@ -1073,7 +895,7 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
                 if (have < 16u) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        const uint32_t pg = (j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2);
+                        const uint32_t pg = att_slot_page(kb, j >> 1);
                         if (pg >= have) { sc[j] = -INFINITY; vs4[j >> 1] = 0.0f; }      // (the V scale too: see k_attend_fp8_linear)
                     }
                 }
@@ -1082,59 +904,22 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
             if ((ragged && tile + 1u == n_tiles) || (a.skip_pages && tile == 0u)) {     // wave-uniform: positions beyond / in front of the range
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const uint32_t pg = tile * 16u + ((j >> 1) < 2 ? 2u * kb + (j >> 1) : 8u + 2u * kb + ((j >> 1) - 2));
+                    const uint32_t pg = tile * 16u + att_slot_page(kb, j >> 1);
                     if (pg >= a.n_pages || pg < a.skip_pages) { sc[j] = -INFINITY; vs4[j >> 1] = 0.0f; }
                 }
             }
-            // ---- online softmax of query row c
-            float mx = sc[0];
-#pragma unroll
-            for (int j = 1; j < 8; ++j) mx = fmaxf(mx, sc[j]);
-            mx = max_over_kb(mx);
-            const float m_new = fmaxf(m_run, mx);
-            const float m_use = (m_new == -INFINITY) ? 0.0f : m_new;
-            const float f = __builtin_amdgcn_exp2f(m_run - m_use);
-            m_run = m_new;
-            const float vmx = max_over_kb(fmaxf(fmaxf(vs4[0], vs4[1]), fmaxf(vs4[2], vs4[3])));
-            const float vref_t = vmx > 0.0f ? vmx : vref;
-            const float rinv = __builtin_amdgcn_rcpf(vref_t);
-            float psum = 0.0f;
+            // ---- online softmax of query row c, the weights in units of the tile's V reference scale
+            float m_use;
+            const float f = att_softmax_step(sc, m_run, m_use);
             f16x8 P;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float p = __builtin_amdgcn_exp2f(sc[j] - m_use);
-                psum += p;
-                P[j] = static_cast<_Float16>(p * (vs4[j >> 1] * rinv));
-            }
-            l_run = l_run * f + psum;
-            const float fa = f * (vref * rinv);                            // acc: old max -> new max, old V reference -> new
-            vref = vref_t;
+            const float fa = fp8_v_weights(sc, m_use, f, vs4, max4(vs4), vref, l_run, P);
             // ---- V pieces, then the next-but-one tile's V is requested into the buffer they came from
             u32x2 vx[8];
             const uint32_t rdvb[4] = {rdv[0] + bo, rdv[1] + bo, rdv[2] + bo, rdv[3] + bo};
             if (TABLE) { fd_take_v<16>(rdvb, vx); issue_table(tad, tile + 2u, buf, 1u); }
             else { fd_take_v(rdvb, vx); issue_v(tile + 2u, buf); }
             // ---- out^T += V^T . P^T, accumulated in place
-            uint32_t w[4][4];                                             // [row pair][byte pair of the 8 d]
-#pragma unroll
-            for (int jp = 0; jp < 4; ++jp) {
-                w[jp][0] = __builtin_amdgcn_perm(vx[2 * jp + 1].x, vx[2 * jp].x, 0x05010400u);
-                w[jp][1] = __builtin_amdgcn_perm(vx[2 * jp + 1].x, vx[2 * jp].x, 0x07030602u);
-                w[jp][2] = __builtin_amdgcn_perm(vx[2 * jp + 1].y, vx[2 * jp].y, 0x05010400u);
-                w[jp][3] = __builtin_amdgcn_perm(vx[2 * jp + 1].y, vx[2 * jp].y, 0x07030602u);
-            }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                f16x8 V;
-#pragma unroll
-                for (int jp = 0; jp < 4; ++jp) {
-                    const f16x2 h = (t & 1) ? __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[jp][t >> 1], 1.0f, true)
-                                            : __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[jp][t >> 1], 1.0f, false);
-                    V[2 * jp] = h.x;
-                    V[2 * jp + 1] = h.y;
-                }
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(V, P, acc[t] * fa, 0, 0, 0);
-            }
+            fp8_pv8(vx, P, fa, acc);
         };
         if (TABLE) {
 #pragma unroll 1
@@ -1150,33 +935,7 @@ __global__ __launch_bounds__(64 * SPECKV_FP8_WG_HEADS) __attribute__((amdgpu_wav
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the re-requested tail tiles: nothing may land after the wave ends
     }
     // ---- partial result of this split, back in true units (or, single split: the final result)
-    const float l_tot = sum_over_kb(l_run);
-    if (a.direct_out && (!a.direct_per_seq || my_splits == 1u)) {
-        if (c < a.g) {
-            const float w = l_tot > 0.0f ? vref / l_tot : 0.0f;
-            float* dst = a.direct_out + (row * a.g + c) * 128u + 32u * kb;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                *reinterpret_cast<f32x4*>(dst + 8 * i) = f32x4{acc[0][i], acc[1][i], acc[2][i], acc[3][i]} * w;
-                *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{acc[4][i], acc[5][i], acc[6][i], acc[7][i]} * w;
-            }
-            if (a.direct_lse && kb == 0)
-                a.direct_lse[row * a.g + c] = l_tot > 0.0f ? (m_run + log2f(l_tot)) * 0.6931471805599453f : -INFINITY;
-        }
-        return;
-    }
-    if (kb == 0) {
-        a.part_ml[part * 32u + c] = m_run;
-        a.part_ml[part * 32u + 16u + c] = l_tot;
-    }
-    if (c < a.g) {
-        float* dst = a.part_acc + (part * 16u + c) * 128u + 32u * kb;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<f32x4*>(dst + 8 * i) = f32x4{acc[0][i], acc[1][i], acc[2][i], acc[3][i]} * vref;
-            *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{acc[4][i], acc[5][i], acc[6][i], acc[7][i]} * vref;
-        }
-    }
+    att_store_rows8(a, acc, m_run, l_run, vref, a.direct_out && (!a.direct_per_seq || my_splits == 1u), row, part, c, kb);
 }
 
 // Merge of the split partials: one workgroup of 512 threads per (layer, head, query row).  The per-layer call of a
@@ -1353,11 +1112,7 @@ __global__ __launch_bounds__(256) void k_qk_scores_fp8_linear(AttendArgs a, floa
         f32x4 sc[2];
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const uint32_t kd[8] = {T.kx[b][0].x, T.kx[b][0].y, T.kx[b][0].z, T.kx[b][0].w, T.kx[b][1].x, T.kx[b][1].y, T.kx[b][1].z, T.kx[b][1].w};
-            f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int st = 0; st < 4; ++st)
-                s = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(kd[2 * st], kd[2 * st + 1]), pack64(qd[2 * st], qd[2 * st + 1]), s, 0, 0, 0);
+            const f32x4 s = fp8_scores_raw(T.kx[b][0], T.kx[b][1], qd);
 #pragma unroll
             for (int i = 0; i < 4; ++i) sc[b][i] = s[i] * T.ks4[2 * b + (i >> 1)] * qscale;    // (acc * k scale) * q scale, as the page-table form
         }

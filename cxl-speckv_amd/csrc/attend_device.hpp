@@ -38,7 +38,18 @@ __device__ __forceinline__ uint4 ldg16(const uint8_t* p)
     const u32x4 v = __builtin_nontemporal_load(SPECKV_GP(u32x4, p));
     return make_uint4(v.x, v.y, v.z, v.w);
 }
-// the same as a plain (temporal) load, for lines that a neighbouring wave reads too; always through the global address space
+// 8 / 4 bytes of a record, non-temporal
+__device__ __forceinline__ uint2 ldg8(const uint8_t* p)
+{
+    const u32x2 v = __builtin_nontemporal_load(SPECKV_GP(u32x2, p));
+    return make_uint2(v.x, v.y);
+}
+__device__ __forceinline__ uint32_t ldg4(const uint8_t* p) { return __builtin_nontemporal_load(SPECKV_GP(uint32_t, p)); }
+// one byte of a record (temporal)
+__device__ __forceinline__ uint32_t ldg1(const uint8_t* p) { return *SPECKV_GP(uint8_t, p); }
+// four floats of a scale table (temporal: the table is small and every workgroup of a layer or sequence reads it)
+__device__ __forceinline__ f32x4 ldg_f4(const float* p) { return *SPECKV_GP(f32x4, p); }
+// 16 bytes as a plain (temporal) load, for lines that a neighbouring wave reads too; always through the global address space
 __device__ __forceinline__ uint4 ldg16_temporal(const uint8_t* p)
 {
     typedef const u32x4 __attribute__((address_space(1)))* gp;

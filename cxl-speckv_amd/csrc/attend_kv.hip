@@ -5,8 +5,8 @@
 // The workgroup shape and the K side are k_attend_fp8_linear<false>'s (attend.hip): one wave = one kv head of one sequence over one
 // contiguous split of its positions, tiles of 32 positions (16 pages), four waves = four heads of the same split; grid (splits,
 // sequences x heads / 4) or rows-first.  Lane (c = lane % 16, kb = lane / 16) owns query row c:
-//   scores  S^T = K . q^T on v_mfma_f32_16x16x32_fp8_fp8: the fp16 query quantised here to E4M3 x a row scale (the arithmetic of the FP8
-//           kernel, bit for bit), the K bytes as they lie in the record, the page scale (the K allocation's scale table, tile order) on the
+//   scores  S^T = K . q^T on the FP8 MFMA (16x16x32): the fp16 query quantised here to E4M3 x a row scale (the FP8 kernel's own
+//           functions, attend_fp8_device.hpp: the same bits), the K bytes as they lie in the record, the page scale (the K allocation's scale table, tile order) on the
 //           score in fp32.  The lane ends with sc[8]: sc[j] = page slot j / 2 (pages 2kb, 2kb + 1, 8 + 2kb, 9 + 2kb of the tile), position j % 2.
 //   output  O^T = V^T . P^T on v_mfma_f32_16x16x32_f16.  An MXFP4 head row of a page is 128 bytes [channel], low nibble = position 0, high
 //           nibble = position 1, one E8M0 code per 16 bytes.  The lane holds bytes 8c .. 8c + 7 of its four pages; for MFMA t (channel
@@ -23,23 +23,9 @@
 // (num_tokens % 32 == 0), so a kernel tile is exactly one storage tile of 17 408 bytes: nibble rows at + 1024 page, code rows at
 // kMx4CodePlane + 64 page.  Never-written records are zero bytes on both sides: K scale 0 -> score 0 (NOT -inf), V = 0.
 #include "kernels.hpp"
-#include "codec_device.hpp"          // the exact reciprocal divide of the codecs (div_by_scale and friends)
-#include "attend_device.hpp"
+#include "attend_fp8_device.hpp"     // the K side's tile arithmetic, shared with attend.hip
 
 namespace speckv {
-
-namespace {
-
-__device__ __forceinline__ uint2 kv_ldg8(const uint8_t* p)
-{
-    const u32x2 v = __builtin_nontemporal_load(SPECKV_GP(u32x2, p));
-    return make_uint2(v.x, v.y);
-}
-__device__ __forceinline__ uint32_t kv_ldg1(const uint8_t* p) { return *SPECKV_GP(uint8_t, p); }
-// four floats of the scale table (temporal: small, and every workgroup of a sequence reads it)
-__device__ __forceinline__ f32x4 kv_ldg_f4(const float* p) { return *SPECKV_GP(f32x4, p); }
-
-} // namespace
 
 // a.seqs: the K side and the split bookkeeping of every sequence (lin_base, scale_tab, k_first of the K allocation; v_first and
 // layer_pages are not read); vside[sequence]: the V allocation's run and the first record of the layer's V region (a multiple of 16).
@@ -66,44 +52,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const uint64_t part = sq.part_base + static_cast<uint64_t>(head) * sq.n_splits + split;
     const uint32_t n_pages = sq.n_pages;
 
-    // query operand: see k_attend_fp8_linear (attend.hip) -- row c of this head, lane kb takes d = 16kb .. 16kb + 15 of both 64-element
-    // halves, the split the K loads follow; scale = max|q| / 448 over the row (1 if zero), e4m3 of clamp(q / scale); rows >= g are zero
+    // query operand (fp8_query_operand): row c of this head, lane kb takes d = 16kb .. 16kb + 15 of both 64-element halves, the split the
+    // K loads follow; rows >= g are zero
     uint32_t qd[8];
     float qscale = 1.0f;
-    auto quantise_query = [&]() {
-        float xq[32];
-        float mx = 0.0f;
-        const uint16_t* qsrc = a.q16 + (row * a.g + min(c, a.g - 1u)) * 128u + kb * 16u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint4 w = *reinterpret_cast<const uint4*>(qsrc + 8 * (i & 1) + 64 * (i >> 1));
-            const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                xq[8 * i + k] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(ws[k >> 1] >> (16 * (k & 1)))));
-                mx = fmaxf(mx, fabsf(xq[8 * i + k]));
-            }
-        }
-        mx = max_over_kb(mx);
-        const bool finite = mx < INFINITY;                                // (inf / NaN rows: the IEEE divide)
-        const float sc = (mx > 0.0f) ? (finite ? div448_of_f16_value(mx) : mx / 448.0f) : 1.0f;
-        const float rcp = finite ? rcp_of_scale(sc) : 0.0f;
-        const bool live = c < a.g;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float x = xq[4 * i + k];
-                const float qt = finite ? __builtin_copysignf(div_by_scale(x, sc, rcp), x) : x / sc;
-                v[k] = live ? fminf(fmaxf(qt, -448.0f), 448.0f) : 0.0f;
-            }
-            int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-            pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
-            qd[i] = static_cast<uint32_t>(pk);
-        }
-        qscale = (live ? sc : 1.0f) * a.scale_log2e;
-    };
+    auto quantise_query = [&]() { fp8_query_operand(a.q16 + (row * a.g + min(c, a.g - 1u)) * 128u + kb * 16u, c < a.g, a.scale_log2e, qd, qscale); };
 
     const uint32_t n_tiles = (n_pages + 15u) / 16u;
     const uint32_t t0 = split * sq.tiles_per_split;
@@ -129,13 +82,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         auto issue_k = [&]() {
 #pragma unroll
             for (int b = 0; b < 2; ++b) { kx[b][0] = ldg16(kp + 16384 * b); kx[b][1] = ldg16(kp + 16384 * b + 64); }
-            ks4 = kv_ldg_f4(kt);
+            ks4 = ldg_f4(kt);
         };
         auto issue_v = [&]() {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) vx[r] = kv_ldg8(vp + 1024 * (r & 1) + 8192 * (r >> 1));
+            for (int r = 0; r < 4; ++r) vx[r] = ldg8(vp + 1024 * (r & 1) + 8192 * (r >> 1));
 #pragma unroll
-            for (int r = 0; r < 4; ++r) vcode[r] = kv_ldg1(vc + 64 * (r & 1) + 512 * (r >> 1));
+            for (int r = 0; r < 4; ++r) vcode[r] = ldg1(vc + 64 * (r & 1) + 512 * (r >> 1));
         };
         // same request order as in the loop (K before V), pinned, so that the wait at the loop head is "everything up to K" on both paths into it
         __builtin_amdgcn_sched_barrier(0);
@@ -153,19 +106,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             // ---- scores
             float sc[8];
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const uint32_t kd[8] = {kx[b][0].x, kx[b][0].y, kx[b][0].z, kx[b][0].w, kx[b][1].x, kx[b][1].y, kx[b][1].z, kx[b][1].w};
-                f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int st = 0; st < 4; ++st)
-                    s = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pack64(kd[2 * st], kd[2 * st + 1]), pack64(qd[2 * st], qd[2 * st + 1]), s, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) sc[4 * b + i] = s[i] * (ks4[2 * b + (i >> 1)] * qscale);
-            }
+            for (int b = 0; b < 2; ++b) fp8_scores(kx[b][0], kx[b][1], qd, ks4, qscale, b, sc);
             if (ragged && tile + 1u == n_tiles) {                         // wave-uniform: pages at or beyond pos_end (even: whole pages)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const uint32_t pg = tile * 16u + 2u * kb + (r & 1) + 8u * (r >> 1);
+                    const uint32_t pg = tile * 16u + att_slot_page(kb, r);
                     // (the masked page's code goes too: it may be a stale record of any magnitude, and its weight of exactly 0 must meet a finite value)
                     if (pg >= n_pages) { sc[2 * r] = -INFINITY; sc[2 * r + 1] = -INFINITY; vcode[r] = 0u; }
                 }
@@ -175,14 +120,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             issue_k();
             __builtin_amdgcn_sched_barrier(0);
             // ---- online softmax of query row c
-            float mx = sc[0];
-#pragma unroll
-            for (int j = 1; j < 8; ++j) mx = fmaxf(mx, sc[j]);
-            mx = max_over_kb(mx);
-            const float m_new = fmaxf(m_run, mx);
-            const float m_use = (m_new == -INFINITY) ? 0.0f : m_new;
-            const float f = __builtin_amdgcn_exp2f(m_run - m_use);
-            m_run = m_new;
+            float m_use;
+            const float f = att_softmax_step(sc, m_run, m_use);
             float psum = 0.0f;
             f16x8 P;
 #pragma unroll
@@ -212,34 +151,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    // ---- a single split: the final rows; otherwise the partial of this split, in true units
-    const float l_tot = sum_over_kb(l_run);
-    if (sq.n_splits == 1u) {
-        if (c < a.g) {
-            const float w = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
-            float* dst = a.direct_out + (row * a.g + c) * 128u + 32u * kb;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                *reinterpret_cast<f32x4*>(dst + 8 * i) = f32x4{acc[0][i], acc[1][i], acc[2][i], acc[3][i]} * w;
-                *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{acc[4][i], acc[5][i], acc[6][i], acc[7][i]} * w;
-            }
-            if (a.direct_lse && kb == 0)
-                a.direct_lse[row * a.g + c] = l_tot > 0.0f ? (m_run + log2f(l_tot)) * 0.6931471805599453f : -INFINITY;
-        }
-        return;
-    }
-    if (kb == 0) {
-        a.part_ml[part * 32u + c] = m_run;
-        a.part_ml[part * 32u + 16u + c] = l_tot;
-    }
-    if (c < a.g) {
-        float* dst = a.part_acc + (part * 16u + c) * 128u + 32u * kb;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<f32x4*>(dst + 8 * i) = f32x4{acc[0][i], acc[1][i], acc[2][i], acc[3][i]};
-            *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{acc[4][i], acc[5][i], acc[6][i], acc[7][i]};
-        }
-    }
+    // ---- a single split: the final rows; otherwise the partial of this split (acc is in true units here: unit 1)
+    att_store_rows8(a, acc, m_run, l_run, 1.0f, sq.n_splits == 1u, row, part, c, kb);
 }
 
 // a.seqs / d_vside (device-visible) hold n_seq descriptors, a.n_splits = the largest per-sequence split count (0: no sequence has positions),

@@ -129,11 +129,6 @@ static uint32_t plan_bound(uint32_t max_pos_end, uint32_t stripe_n_max, uint32_t
     const uint32_t ctx = plan_tiles_bound(max_pos_end, stripe_n_max);
     return window ? std::min(ctx, decode_window_tiles_bound(window)) : ctx;
 }
-static BatchTuning batch_tuning()
-{
-    const Tuning& t = tuning();
-    return BatchTuning{t.attend_tiles_per_split, t.attend_order_as_given, t.attend_fp8_table_regs, t.attend_fp8_striped_table, t.attend_int4_striped_wg};
-}
 
 int Engine::qk_scores_fp8(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
                           uint32_t pos_begin, uint32_t pos_end, float* d_out, hipStream_t s)
@@ -461,13 +456,8 @@ int Engine::attend_batch(int scheme, uint32_t n_seq, const uint64_t* handles, ui
     // MXFP4, whole sequences in single runs and a CU to each: 8-wave workgroups, the run cut in two (k_attend_mx4<0, 2>)
     if (mx4 && one_split_each && !form.striped && !form.table && static_cast<uint64_t>(n_seq) * ((g + 7u) / 8u) <= cus() && tuning().attend_mx4_one_half == 0) k.mx4_halves = 1u;
     k.wg8 = form.wg8;
-    // The kernels read the slot's descriptors in place: whatever was launched must have passed before the slot is written again.
-    // The guard event is recorded on EVERY way out from here on (a merge launch that fails behind an attention launch
-    // that went through used to leave the slot unguarded under a kernel still fetching from it).
-    struct SlotGuard {
-        hipEvent_t ev; hipStream_t st;
-        ~SlotGuard() { if (hipEventRecord(ev, st) != hipSuccess) (void)hipGetLastError(); }
-    } slot_guard{seq_ring_.ev[slot], st};
+    // The kernels read the slot's descriptors in place: the guard event is recorded on every way out from here on (SlotGuard).
+    SlotGuard slot_guard{seq_ring_.ev[slot], st};
     if (fp8) {
         HIP_TRY(launch_attend_fp8_batch(k, n_seq, d_out, d_lse, st));
     } else if (mx4) {

@@ -67,8 +67,7 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
     if (!s) HIP_TRY(hipDeviceSynchronize());
     hipStream_t st = s ? s : stream_;
     // the launch decision of the FP8 batch kernel (attend_geometry.hpp), members in one run each
-    const Tuning& t = tuning();
-    const BatchTuning tun{t.attend_tiles_per_split, t.attend_order_as_given, t.attend_fp8_table_regs, t.attend_fp8_striped_table, t.attend_int4_striped_wg};
+    const BatchTuning tun = batch_tuning();
     const BatchShape shape{true, false, n_seq, 8u, cus(), false, false};
     const BatchForm form = batch_form(shape, tun);
     std::vector<uint32_t> order(n_seq);
@@ -108,10 +107,7 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
         if (w.s != st) HIP_TRY(hipStreamWaitEvent(st, w.ev, 0));
     for (uint32_t i = 0; i < n_seq; ++i) { note_use(ks[i], s); note_use(vs[i], s); }      // speckv_free waits for this stream
     // The guard event is recorded on every way out from here on: the slot must not be written again under a kernel still reading it.
-    struct SlotGuard {
-        hipEvent_t ev; hipStream_t st;
-        ~SlotGuard() { if (hipEventRecord(ev, st) != hipSuccess) (void)hipGetLastError(); }
-    } slot_guard{seq_ring_.ev[slot], st};
+    SlotGuard slot_guard{seq_ring_.ev[slot], st};
     HIP_TRY(launch_attend_k8v4(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), n_seq, merge, d_out, d_lse, st));
     if (!s) HIP_TRY(hipStreamSynchronize(stream_));
     return SPECKV_OK;

@@ -6,6 +6,7 @@
 #pragma once
 #include "engine.hpp"
 #include "placement.hpp"
+#include "tuning.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -121,6 +122,20 @@ std::vector<int> parse_int_list(const char* env)
     return out;
 }
 
+// the tuning keys the batch attention's launch decision reads (attend_geometry.hpp takes them as values)
+BatchTuning batch_tuning()
+{
+    const Tuning& t = tuning();
+    return BatchTuning{t.attend_tiles_per_split, t.attend_order_as_given, t.attend_fp8_table_regs, t.attend_fp8_striped_table, t.attend_int4_striped_wg};
+}
+
+// A batch launch reads its descriptor slot in place: whatever was launched must have passed before the slot is written again.  The
+// slot's event is recorded on EVERY way out of the scope that holds the guard (a merge launch that fails behind an
+// attention launch that went through used to leave the slot unguarded under a kernel still fetching from it).
+struct SlotGuard {
+    hipEvent_t ev; hipStream_t st;
+    ~SlotGuard() { if (hipEventRecord(ev, st) != hipSuccess) (void)hipGetLastError(); }
+};
 
 } // namespace
 } // namespace speckv

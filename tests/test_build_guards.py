@@ -30,6 +30,7 @@ HOT = [
     ("attend.o", r"k_attend_fp8ENS", 0),
     ("attend.o", r"k_attend_fp8_dma", 0),
     ("attend.o", r"k_qk_scores_fp8_linear", 0),
+    ("attend_kv.o", r"k_attend_k8v4", 0),                                   # record pointers from per-sequence descriptors
     ("attend_int4.o", r"k_attend_int4_wgILb0E", 0),
     ("attend_int4.o", r"k_attend_int4_wgILb1E", 1),
     ("attend_int4.o", r"k_attend_int4_wg8ILi1E", 0),
