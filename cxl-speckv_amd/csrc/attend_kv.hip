@@ -31,6 +31,11 @@ namespace speckv {
 // layer_pages are not read); vside[sequence]: the V allocation's run and the first record of the layer's V region (a multiple of 16).
 // a.direct_out / direct_lse are always set: a sequence with ONE split is written final, one without positions as zeros / -inf, the
 // others leave partials (part_acc / part_ml, true units) for launch_attend_combine, which skips the single-split sequences.
+// WINDOW: the launch under a sliding window (AttendArgs::seq_skip, decode_window.hpp; speckv_ext_attend_kv_batch_window) -- the descriptors
+// start at the tile of the window's lower bound, seq_skip[sequence] = the leading POSITIONS (0..31, may be odd) of the sequence's tile 0
+// in front of it.  An instance of its own, for k_attend_fp8_linear<.., WINDOW>'s reason (attend.hip): carried by the plain instance the
+// position mask cost the unwindowed FP8 entries 3 %.  k_attend_k8v4<false> is the kernel of before, instruction for instruction.
+template <bool WINDOW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_attend_k8v4(AttendArgs a, const AttendKvSide* __restrict__ vside)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -51,6 +56,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const AttendKvSide vsd = vside[seq];
     const uint64_t part = sq.part_base + static_cast<uint64_t>(head) * sq.n_splits + split;
     const uint32_t n_pages = sq.n_pages;
+    const uint32_t skip_pos = WINDOW ? a.seq_skip[seq] : 0u;             // (workgroup-uniform)
 
     // query operand (fp8_query_operand): row c of this head, lane kb takes d = 16kb .. 16kb + 15 of both 64-element halves, the split the
     // K loads follow; rows >= g are zero
@@ -115,6 +121,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                     if (pg >= n_pages) { sc[2 * r] = -INFINITY; sc[2 * r + 1] = -INFINITY; vcode[r] = 0u; }
                 }
             }
+            // WINDOW: the positions of the sequence's tile 0 in front of the window.  `tile` is the absolute tile of the sequence, so only split 0
+            // comes here.  Where n_pages > 0 the window's lower bound lo = skip_pos is visible and lies in tile 0: no piece is masked throughout,
+            // m_run is finite from the first tile on.
+            if (WINDOW && tile == 0u && skip_pos != 0u) {                 // wave-uniform
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const uint32_t pg = att_slot_page(kb, r);
+                    if (2u * pg < skip_pos) sc[2 * r] = -INFINITY;
+                    if (2u * pg + 1u < skip_pos) sc[2 * r + 1] = -INFINITY;
+                    // a page masked in both positions loses its code as in the ragged branch (a stale or hostile record meets its weight of 0 as a
+                    // small finite number).  A CUT page (skip_pos odd: position 0 masked, position 1 kept) keeps it: the kept nibble is stored in
+                    // units of that code, the masked nibble's weight is exactly 0, and an MXFP4 value widened to fp16 by the conversion is finite
+                    // (both positions of a page are encoded together from fp16 rows: the block's code keeps 6 x 2^(code - 127) inside fp16), so 0 x it is 0
+                    if (2u * pg + 2u <= skip_pos) vcode[r] = 0u;
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);
             kp += step * 32768u; kt += step * 16u;
             issue_k();
@@ -165,7 +187,8 @@ hipError_t launch_attend_k8v4(const AttendArgs& a, const AttendKvSide* d_vside, 
     const uint32_t rows = n_seq * (a.heads / 4u), splits = a.n_splits ? a.n_splits : 1u;      // (split 0 of a sequence without positions writes its zeros)
     ar.rows_real = rows;
     const dim3 gr = a.rows_first ? dim3(rows | 1u, splits) : dim3(splits, rows);
-    hipLaunchKernelGGL(k_attend_k8v4, gr, dim3(256), 0, s, ar, d_vside);
+    if (a.seq_skip) hipLaunchKernelGGL(k_attend_k8v4<true>, gr, dim3(256), 0, s, ar, d_vside);      // under a window that cuts a sequence
+    else hipLaunchKernelGGL(k_attend_k8v4<false>, gr, dim3(256), 0, s, ar, d_vside);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || !merge) return e;
     return launch_attend_combine(a, n_seq, d_out, d_lse, s);

@@ -587,6 +587,17 @@ speckv_status_t speckv_ext_attend_kv_batch(uint32_t n_seq, const speckv_handle_t
     });
 }
 
+speckv_status_t speckv_ext_attend_kv_batch_window(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles, uint32_t layer,
+                                                  const void* d_q_f16, uint32_t g, const uint32_t* pos_end, const uint32_t* q_pos, uint32_t window,
+                                                  float sm_scale, float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] {
+        return g_engine->attend_batch_kv(n_seq, k_handles, v_handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse,
+                                         static_cast<hipStream_t>(stream), q_pos, window);
+    });
+}
+
 speckv_status_t speckv_ext_attend_int4_batch(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16,
                                              uint32_t g, const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse,
                                              void* stream)

@@ -231,9 +231,10 @@ public:
     int attend_int4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
                     uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
     // the split pool's decode step (engine_attend_kv.cpp): K of `layer` from region `layer` of the FP8 allocation k_handles[i], V from
-    // region `layer` of the MXFP4 allocation v_handles[i], one attention launch (and its merge) for the batch
+    // region `layer` of the MXFP4 allocation v_handles[i], one attention launch (and its merge) for the batch.  q_pos / window: the window
+    // entry (speckv_ext_attend_kv_batch_window; decode_window.hpp), as attend_batch's -- window = 0: the launches of the entry without one
     int attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
-                        const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
+                        const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos = nullptr, uint32_t window = 0);
     int attend_mx4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
                    uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
     int migrate(uint64_t handle, uint64_t first_page, uint64_t n_pages, uint32_t target_pool);

@@ -1,7 +1,9 @@
-// cxl-speckv_amd/csrc/engine_attend_kv.cpp -- Engine::attend_batch_kv, the body behind speckv_ext_attend_kv_batch: one decode step of a
-// batch over the SPLIT POOL ("K8V4": a sequence's K rows in an FP8_E4M3 allocation, its V rows in an MXFP4 allocation), one attention
-// launch (k_attend_k8v4, attend_kv.hip) and, where members have several pieces, the merge behind it
+// cxl-speckv_amd/csrc/engine_attend_kv.cpp -- Engine::attend_batch_kv, the body behind speckv_ext_attend_kv_batch and
+// speckv_ext_attend_kv_batch_window: one decode step of a batch over the SPLIT POOL ("K8V4": a sequence's K rows in an FP8_E4M3
+// allocation, its V rows in an MXFP4 allocation), one attention launch (k_attend_k8v4, attend_kv.hip) and, where members have several
+// pieces, the merge behind it
 #include "engine_internal.hpp"
+#include "decode_window.hpp"
 #include "tuning.hpp"
 
 namespace speckv {
@@ -13,13 +15,21 @@ namespace speckv {
 // ONE form: both allocations of every member in a single run (Allocation::linear_base) and a scale table on K; any other placement
 // (striped over several pools, pages migrated) is refused with SPECKV_ERR_INVAL before anything is launched.
 // The descriptors travel through a slot of the pinned descriptor ring, read in place: not capturable into a HIP graph.
+// Under a window (q_pos, window >= 1: a local layer; decode_window.hpp) member i's query sits at q_pos[i] -- its last stored position or the
+// tail behind it -- and sees [lo, q_pos[i]]: the descriptor starts at the tile of lo in BOTH allocations (begin / 2 pages in: a multiple
+// of 16 records, a kernel tile stays one storage tile and one group of the scale table), the tiles, the dispatch order and the pieces are
+// those of the pages actually walked, and the leading positions of tile 0 in front of lo travel as the skip array (AttendArgs::seq_skip:
+// k_attend_k8v4<true>).  window = 0, or a window that cuts no member: the descriptors, the instance and the launches of the entry without one.
 int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
-                            const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+                            const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos, uint32_t window)
 {
-    if (null_) return no_data_path("speckv_ext_attend_kv_batch");
+    const char* entry = window ? "speckv_ext_attend_kv_batch_window" : "speckv_ext_attend_kv_batch";
+    if (null_) return no_data_path(entry);
+    if (window && !q_pos) return SPECKV_ERR_INVAL;
+    if (!window) q_pos = nullptr;                                        // (no window: the launches of the entry without one)
     if (n_seq == 0) return SPECKV_OK;
     if (is_capturing(s)) {
-        SPECKV_ERR("speckv_ext_attend_kv_batch cannot be captured into a HIP graph (its descriptors are staged per call)");
+        SPECKV_ERR("%s cannot be captured into a HIP graph (its descriptors are staged per call)", entry);
         return SPECKV_ERR_INVAL;
     }
     if (!k_handles || !v_handles || !pos_end || !d_q_f16 || !d_out || g == 0 || g > 16) return SPECKV_ERR_INVAL;
@@ -33,7 +43,8 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
     };
     std::vector<AttendSeq> seqs(n_seq);
     std::vector<AttendKvSide> vside(n_seq);
-    std::vector<uint32_t> tiles(n_seq), pages(n_seq);
+    std::vector<uint32_t> tiles(n_seq), pages(n_seq), skips(q_pos ? n_seq : 0u);      // (skips: AttendArgs::seq_skip of a windowed launch)
+    bool cut = false;                                                    // the window cuts some member's pool positions
     std::vector<Allocation*> ks(n_seq), vs(n_seq);
     uint64_t total_tiles = 0;
     for (uint32_t i = 0; i < n_seq; ++i) {
@@ -43,24 +54,33 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
             k->layout.num_tokens != v->layout.num_tokens)
             return SPECKV_ERR_INVAL;
         if (!k->linear_base || !k->d_scale_tab || !v->linear_base) {
-            SPECKV_ERR("speckv_ext_attend_kv_batch: sequence %u: the %s allocation's records do not lie in one run (striped over several pools, "
+            SPECKV_ERR("%s: sequence %u: the %s allocation's records do not lie in one run (striped over several pools, "
                        "or pages migrated); this entry has the single-run form only -- speckv_ext_attend_chunk_kv serves any placement",
-                       i, (!k->linear_base || !k->d_scale_tab) ? "K" : "V");
+                       entry, i, (!k->linear_base || !k->d_scale_tab) ? "K" : "V");
             return SPECKV_ERR_INVAL;
         }
         ks[i] = k; vs[i] = v;
         const uint32_t region = k->layout.num_tokens / 2u;
+        // the member's walk: everything stored, or under a window the tiles from lo's on (they end where they ended without one: inside the region)
+        DecodeWindowRange w{0u, 0u, pos_end[i] / 2u};
+        if (q_pos) {
+            if (q_pos[i] > pos_end[i] || q_pos[i] + 1u < pos_end[i]) return SPECKV_ERR_INVAL;       // the query: the last stored position or the tail behind it
+            w = decode_window_range(q_pos[i] + 1u, window);
+            if (w.n_pages == 0u) w = DecodeWindowRange{0u, 0u, 0u};      // no pool position in the window: the member of pos_end = 0 (zeros, lse -inf)
+            skips[i] = w.skip;
+            cut = cut || w.begin != 0u || w.skip != 0u || w.n_pages != pos_end[i] / 2u;
+        }
         AttendSeq& q = seqs[i];
         q = AttendSeq{};
         q.lin_base = k->linear_base;
         q.scale_tab = k->d_scale_tab;
-        q.k_first = q.v_first = static_cast<uint64_t>(layer) * region;
-        q.n_pages = pages[i] = pos_end[i] / 2u;
+        q.k_first = q.v_first = static_cast<uint64_t>(layer) * region + w.begin / 2u;
+        q.n_pages = pages[i] = w.n_pages;
         q.layer_pages = region;
         q.stripe_n = 1u;
         q.n_splits = tiles[i] = (q.n_pages + 15u) / 16u;                 // tiles for now, pieces below
         total_tiles += tiles[i];
-        vside[i] = AttendKvSide{v->linear_base, static_cast<uint64_t>(layer) * region};       // (region % 16 == 0: a kernel tile is one storage tile)
+        vside[i] = AttendKvSide{v->linear_base, q.v_first};              // (region % 16 == 0, begin % 32 == 0: a kernel tile is one storage tile)
     }
     DeviceScope device_scope(device_);
     // NULL = the engine's stream and a synchronous call: the query may have been produced on any stream of the caller
@@ -79,14 +99,16 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
     for (uint32_t i = 0; i < n_seq; ++i) merge = merge || seqs[i].n_splits > 1u;
     AttendArgs k{};
     if (!attend_scratch(k, merge ? parts : 1u, 0, s)) return SPECKV_ERR_NOMEM;
-    // descriptors, then the V sides, then the dispatch order: one slot, read in place by the kernels (Engine::attend_batch)
+    // descriptors, then the V sides, then the dispatch order, then the skip array of a launch that a window cuts: one slot, read in place by
+    // the kernels (Engine::attend_batch)
     const size_t desc_bytes = n_seq * sizeof(AttendSeq), side_bytes = n_seq * sizeof(AttendKvSide), idx_bytes = n_seq * sizeof(uint32_t);
     int slot = 0;
     void* staged = nullptr;
-    RC_TRY(take_seq_slot(desc_bytes + side_bytes + idx_bytes, &slot, &staged));
+    RC_TRY(take_seq_slot(desc_bytes + side_bytes + idx_bytes + (cut ? idx_bytes : 0u), &slot, &staged));
     memcpy(staged, seqs.data(), desc_bytes);
     memcpy(static_cast<uint8_t*>(staged) + desc_bytes, vside.data(), side_bytes);
     if (ordered) memcpy(static_cast<uint8_t*>(staged) + desc_bytes + side_bytes, order.data(), idx_bytes);
+    if (cut) memcpy(static_cast<uint8_t*>(staged) + desc_bytes + side_bytes + idx_bytes, skips.data(), idx_bytes);
     uint8_t* d_slot = nullptr;
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_slot), staged, 0));
     k.heads = 8u;
@@ -98,6 +120,7 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
     k.lin_base = seqs[0].lin_base;                                       // (overridden per sequence)
     k.seqs = reinterpret_cast<const AttendSeq*>(d_slot);
     if (ordered) k.order = reinterpret_cast<const uint32_t*>(d_slot + desc_bytes + side_bytes);
+    if (cut) k.seq_skip = reinterpret_cast<const uint32_t*>(d_slot + desc_bytes + side_bytes + idx_bytes);
     if (geo.rows_first) k.rows_first = 1u;
     k.direct_out = d_out;
     k.direct_lse = d_lse;

@@ -615,6 +615,7 @@ struct AttendArgs {
     // striped, table) take it -- launch_attend_fp8_batch sends every launch that brings one to them, a table launch too (k_attend_fp8_dma<1>
     // has no leading mask and is passed over); INT4_G32 and MXFP4: the existing instances k_attend_int4_wg8<1|2>, k_attend_int4_wg and
     // k_attend_mx4<0|2>.  The forms by residue class have no leading mask: their launchers refuse it, the engine never plans them under a window.
+    // The split pool: k_attend_k8v4<true> (launch_attend_k8v4 picks the instance by this pointer).
     const uint32_t* seq_skip;
 };
 // (the stream partition -- attend_stream_begin / _wg_of / _count -- is plain arithmetic the host decides with too: ring_rule.hpp)
@@ -701,7 +702,8 @@ struct AttendKvSide {
     uint64_t v_first;                 // first record of the wanted layer's V region: a multiple of kMx4TileRecs
 };
 // a.direct_out == d_out, a.direct_per_seq == 1: sequences with one split are written final, those without positions as zeros / lse -inf;
-// merge: some sequence has several splits -- launch_attend_combine follows on `s`
+// merge: some sequence has several splits -- launch_attend_combine follows on `s`.  a.seq_skip set: the launch under a sliding window
+// (k_attend_k8v4<true>: the descriptors start at the window's tile, seq_skip[sequence] leading positions of its tile 0 masked), else the plain instance
 hipError_t launch_attend_k8v4(const AttendArgs& a, const AttendKvSide* d_vside, uint32_t n_seq, bool merge, float* d_out, float* d_lse, hipStream_t s);
 
 // every page's record (rec_bytes rounded up to 16) copied to d_new_addr[page], then entries[page].pool_addr = d_new_addr[page]

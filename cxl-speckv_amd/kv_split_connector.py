@@ -13,14 +13,15 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
   write_prefill                         one speckv_ext_write_runs per allocation; an odd last position waits in an fp16 tail
   attend                                one layer of the DECODE step (one new position per request, already held as the tail or stored):
                                         ONE speckv_ext_attend_kv_batch -- the batch kernel over FP8 keys and MXFP4 values, no fp16 tile is
-                                        materialised -- and one speckv_ext_attend_fold_tail for the requests with an odd length
+                                        materialised -- and one speckv_ext_attend_fold_tail for the requests with an odd length;
+                                        window=W: a sliding-window layer, ONE speckv_ext_attend_kv_batch_window that walks the window only
   attend_chunk                          one layer of a step of S >= 1 new positions per request -- a prefill chunk, a draft chain or tree --
                                         causal, under a window, a tree, a tree under a window, split over the chip (S = 1 works, but a
                                         64-row query block then carries rows_per_pos live rows: attend is the decode route)
   commit                                the accepted prefix of a step into the pool: one speckv_ext_write_pairs per allocation
 
 Not in this class: the planned and captured decode route (plan_step, HIP graphs: attend stages its descriptors
-per call), sliding windows on attend, multi-position steps on the decode kernel (attend_spec), load_paged / store_paged, the
+per call), multi-position steps on the decode kernel (attend_spec), load_paged / store_paged, the
 shared-prefix fold, fork, truncate, begin_step and the K pre-scale."""
 from typing import Dict, Sequence
 
@@ -60,7 +61,8 @@ class SpeckvSplitKVConnector:
         self._tails = (None, None, None, None)                # key, tail_idx, K rows, V rows of the step's requests with an odd length
         self._tree = (None, None, None)                       # key, mask rows, depths of the step's tree
         self._fold = (None,)                                  # attend: key, then what a step's calls share -- the count and device indices of the
-                                                              # requests with an odd length, the handle arrays, the stored lengths
+                                                              # requests with an odd length, the handle arrays, the stored lengths,
+                                                              # the query positions (attend under a window)
 
     # ------------------------------------------------------------------ requests
     def add_request(self, req_id: int):
@@ -152,10 +154,14 @@ class SpeckvSplitKVConnector:
             self._tree = (key, masks, depths)
         return self._tree[1:]
 
-    def attend(self, layer: int, req_ids: Sequence[int], q, sm_scale: float, stream=None):
+    def attend(self, layer: int, req_ids: Sequence[int], q, sm_scale: float, stream=None, window=None):
         """softmax(q.K^T * sm_scale).V of one layer for the batch over everything the requests hold -- the decode step.  q
         [batch][heads][g][dim] fp16 (g = 1..16 query rows per kv head, GQA); returns [batch][heads][g][dim] fp32, shapes as
         SpeckvKVConnector.attend.  Changes no state.
+        window=W >= 1: a sliding-window (local) layer -- a request of `length` positions (the step's own included) attends the last
+        W of them, its query at length - 1.  ONE speckv_ext_attend_kv_batch_window call in place of the batch call below: every request
+        is walked from its window's tile in both allocations (SpeckvKVConnector.decode_window_range), ceil((W + 31) / 32) tiles at most
+        whatever its context; the tail is always inside the window and is folded as without one.  window=None / 0: today's call.
         ONE speckv_ext_attend_kv_batch call (with a log-sum-exp buffer) over the stored positions, then -- only if some request has an
         odd length -- ONE speckv_ext_attend_fold_tail call that folds the fp16 tails into the rows of those requests.  The query enters
         the stored part as E4M3 x a row scale (the FP8 batch kernel's quantisation), the stored K as its E4M3 values with the block
@@ -165,6 +171,7 @@ class SpeckvSplitKVConnector:
         a caller goes through attend_chunk with the step's new rows."""
         import numpy as np
         import torch
+        W = SpeckvKVConnector._decode_window(window)
         if len(q.shape) != 4:
             raise ValueError("q must be [batch][heads][g][dim]")
         B, H, G, D = (int(x) for x in q.shape)
@@ -185,9 +192,14 @@ class SpeckvSplitKVConnector:
                     odd = [b for b, r in enumerate(reqs) if r.length & 1]
                     self._fold = (key, len(odd), _kc._device_index(odd) if odd else None,
                                   np.asarray([r.k_handle for r in reqs], dtype=np.uint64), np.asarray([r.v_handle for r in reqs], dtype=np.uint64),
-                                  np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32))
-                _, n_odd, rows, k_handles, v_handles, pos_end = self._fold
-            self.lib.attend_kv_batch(k_handles, v_handles, layer, q.data_ptr(), G, pos_end, sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+                                  np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                  np.asarray([max(r.length, 1) - 1 for r in reqs], dtype=np.uint32))
+                _, n_odd, rows, k_handles, v_handles, pos_end, q_pos = self._fold
+            if W:
+                self.lib.attend_kv_batch_window(k_handles, v_handles, layer, q.data_ptr(), G, pos_end, q_pos, W, sm_scale, out.data_ptr(),
+                                                lse.data_ptr(), st.cuda_stream)
+            else:
+                self.lib.attend_kv_batch(k_handles, v_handles, layer, q.data_ptr(), G, pos_end, sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
             if n_odd:
                 self.lib.attend_fold_tail(n_odd, rows.data_ptr(), self.H, G, q.data_ptr(), tk.data_ptr() + 2 * layer * row,
                                           tv.data_ptr() + 2 * layer * row, self.L * row, sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)

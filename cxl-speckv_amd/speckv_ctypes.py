@@ -137,6 +137,8 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_fp8": [c_uint64, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_fp8_batch": [c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_kv_batch": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_kv_batch_window": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, ctypes.c_float, c_void_p,
+                                          c_void_p, c_void_p],
     "speckv_ext_attend_int4_batch": [c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_batch_plan": [c_uint32, ctypes.POINTER(c_uint64), _u32p, c_uint32, c_void_p, c_size_t, c_void_p],
     "speckv_ext_attend_batch_plan_window": [c_uint32, ctypes.POINTER(c_uint64), _u32p, _u32p, c_uint32, c_uint32, c_void_p, c_size_t, c_void_p],
@@ -675,6 +677,17 @@ class SpeckvLib:
         self._ext("speckv_ext_attend_kv_batch", n, handles(k_handles), handles(v_handles), layer, c_void_p(d_q_f16), g,
                   None if pos_end is None else as_arr(pos_end, c_uint32, n), ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0),
                   c_void_p(stream or 0))
+
+    def attend_kv_batch_window(self, k_handles, v_handles, layer, d_q_f16, g, pos_end, q_pos, window, sm_scale, d_out, d_lse=None, stream=None):
+        """attend_kv_batch for a sliding-window layer (speckv_ext_attend_kv_batch_window): member i has q_pos[i] + 1 positions (pos_end[i] = that
+        & ~1 stored, an odd one more in the caller's tail) and its query sees the last `window` of them; every member is walked from its
+        window's tile in both allocations.  window 0 (q_pos may then be None), or a window that cuts no member: the launches of
+        attend_kv_batch.  Arrays as there; None stands for a NULL array."""
+        n = len(pos_end if k_handles is None and v_handles is None else (v_handles if k_handles is None else k_handles))
+        handles = lambda h: None if h is None else as_arr(h, c_uint64, n)
+        u32 = lambda a: None if a is None else as_arr(a, c_uint32, n)
+        self._ext("speckv_ext_attend_kv_batch_window", n, handles(k_handles), handles(v_handles), layer, c_void_p(d_q_f16), g, u32(pos_end),
+                  u32(q_pos), window, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
 
     def attend_int4_batch(self, handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse=None, stream=None):
         """handles / pos_end: sequences of ints, or ready ctypes arrays (c_uint64 / c_uint32) that a caller reuses over

@@ -1207,6 +1207,28 @@ speckv_status_t speckv_ext_attend_kv_batch(uint32_t n_seq, const speckv_handle_t
                                            uint32_t layer, const void* d_q_f16, uint32_t g, const uint32_t* pos_end,
                                            float sm_scale, float* d_out, float* d_lse, void* stream);
 
+/* speckv_ext_attend_kv_batch_window: speckv_ext_attend_kv_batch on a SLIDING-WINDOW (local) layer -- the decode step of the local layers
+ * of a model that interleaves local and global attention (Mistral, Gemma 2 / 3, gpt-oss) over a split pool.  The arguments of
+ * speckv_ext_attend_kv_batch with `q_pos, window` directly behind pos_end.  An additive entry: SPECKV_EXT_ABI_VERSION stays what it is.
+ *   pos_end, q_pos, window : the semantics of speckv_ext_attend_batch_window.  Member i has length = q_pos[i] + 1 positions, the step's
+ *       own included; pos_end[i] = length & ~1 of them are stored, so q_pos[i] is pos_end[i] - 1 (the query's own position is the last
+ *       stored one) or pos_end[i] (it is the tail the caller holds; with pos_end[i] == 0 only q_pos[i] == 0).  The query sees the stored
+ *       positions [lo, pos_end[i]), lo = max(0, length - window); speckv_ext_decode_window_range is the rule.  Each member is walked
+ *       from the tile of lo in BOTH allocations -- at most ceil((window + 31) / 32) tiles whatever its context -- with the positions of
+ *       that tile in front of lo masked (k_attend_k8v4<true>); the dispatch order and the pieces are decided on the pages walked.
+ *   window = 0 (q_pos is then not read), or a window that cuts no member's pool positions: exactly the launches of
+ *       speckv_ext_attend_kv_batch -- the same kernel instance, the same bits.
+ *   A member without a pool position in its window (window 1 with an odd length, a length below 2) is handled as one with
+ *       pos_end[i] == 0: zeros and lse = -inf.
+ * Values, addressing, placement (single runs only), stream rules and statuses are those of speckv_ext_attend_kv_batch; the tail of an odd
+ * length is always inside the window and is folded in afterwards by speckv_ext_attend_fold_tail, as there.  NOT capturable into a HIP
+ * graph.  SPECKV_ERR_INVAL besides what speckv_ext_attend_kv_batch refuses: a q_pos[i] outside {pos_end[i] - 1, pos_end[i]}, a NULL
+ * q_pos with window != 0 -- nothing is launched, d_out is untouched. */
+speckv_status_t speckv_ext_attend_kv_batch_window(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                                  uint32_t layer, const void* d_q_f16, uint32_t g, const uint32_t* pos_end,
+                                                  const uint32_t* q_pos, uint32_t window, float sm_scale, float* d_out, float* d_lse,
+                                                  void* stream);
+
 /* speckv_ext_attend_chunk_tree_window: a DRAFT TREE on a SLIDING-WINDOW (local) layer -- the tree step of the local layers of the
  * models speckv_ext_attend_chunk_window names, whose global layers take the tree step through speckv_ext_attend_chunk_masked / _split.
  * The arguments of speckv_ext_attend_chunk_split in the same order with `d_depth, window` directly behind mask_words.  Everything
