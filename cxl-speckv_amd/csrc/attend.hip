@@ -26,7 +26,8 @@
 //           -> lane (c, kb) holds out[query row c][64blk + 16kb + 4i + t].
 #include "kernels.hpp"
 #include "tuning.hpp"
-#include "attend_fp8_device.hpp"     // the tile arithmetic shared with attend_kv.hip: query operand, scores, softmax step, FP8 p.V, epilogue
+#include "attend_geometry.hpp"       // Fp8Kernel: the kernel launch_attend_fp8 is told to run
+#include "attend_fp8_device.hpp"    // the tile arithmetic shared with attend_kv.hip: query operand, scores, softmax step, FP8 p.V, epilogue
 #include <cstdlib>
 
 namespace speckv {
@@ -1463,32 +1464,22 @@ hipError_t launch_build_scale_tab(const PageEntry* d_entries, uint64_t n_pages, 
     return hipGetLastError();
 }
 
-hipError_t launch_attend_fp8(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s)
+// which kernel: the engine's decision (attend_geometry.hpp seq_decide_fp8, with the measurements behind it)
+hipError_t launch_attend_fp8(const AttendArgs& a, Fp8Kernel kernel, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s)
 {
     if (a.n_pages == 0 || n_layers == 0) return hipSuccess;
-    // one long split per row: the LDS-DMA kernel (two tiles deep per wave, 8 waves per CU); several shorter splits: the
-    // register-staged one (16 waves per CU hide more) -- 80 layers x 32k: 8 splits 0.756 (register-staged) / 0.72 (DMA),
-    // 1 split 0.58 / 0.73; 8k: 1 split DMA 0.69, 8 splits 0.63 / 0.62
-    // (launches with few workgroup columns -- the per-layer calls of one sequence -- are latency-bound either way: DMA kernel,
-    // 13.8 against 15.5 us at 8k context)
-    const bool dma_table = !a.lin_base && (a.stripe_bases || a.table_form) && a.scale_tab && a.entries && !a.skip_pages && tuning().attend_fp8_table_regs == 0;
-    if (a.fp8_cls && a.stripe_bases && a.scale_tab && !a.skip_pages) {   // striped regularly: the linear kernels over residue classes, by the linear forms' rule
-        if (a.n_splits == 1u || n_layers * (a.heads / 4u) < 128u)
-            hipLaunchKernelGGL(k_attend_fp8_dma<2>, dim3(a.n_splits, n_layers * (a.heads / kFdHeads)), dim3(64 * kFdHeads), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_attend_fp8_linear<false, false, true>), dim3(a.n_splits, n_layers * (a.heads / 4u)), dim3(256), 0, s, a);
+    const dim3 dma_grid(a.n_splits, n_layers * (a.heads / kFdHeads)), dma_block(64 * kFdHeads), grid(a.n_splits, n_layers * (a.heads / 4u)), block(256);
+    switch (kernel) {
+    case kFp8DmaCls:      hipLaunchKernelGGL(k_attend_fp8_dma<2>, dma_grid, dma_block, 0, s, a); break;
+    case kFp8RegsCls:     hipLaunchKernelGGL((k_attend_fp8_linear<false, false, true>), grid, block, 0, s, a); break;
+    case kFp8DmaTable:    hipLaunchKernelGGL(k_attend_fp8_dma<1>, dma_grid, dma_block, 0, s, a); break;
+    case kFp8DmaLinear:   hipLaunchKernelGGL(k_attend_fp8_dma<0>, dma_grid, dma_block, 0, s, a); break;
+    case kFp8RegsLinear:  hipLaunchKernelGGL(k_attend_fp8_linear<false>, grid, block, 0, s, a); break;
+    case kFp8RegsStriped: hipLaunchKernelGGL(k_attend_fp8_linear<true>, grid, block, 0, s, a); break;
+    case kFp8RegsTable:   hipLaunchKernelGGL((k_attend_fp8_linear<false, true>), grid, block, 0, s, a); break;
+    case kFp8PerWave:     hipLaunchKernelGGL(k_attend_fp8, grid, block, 0, s, a); break;
+    default: return hipErrorInvalidValue;
     }
-    else if (dma_table)                                                  // moved page by page (or striped, on request): the DMA pipeline with addresses from the page table
-        hipLaunchKernelGGL(k_attend_fp8_dma<1>, dim3(a.n_splits, n_layers * (a.heads / kFdHeads)), dim3(64 * kFdHeads), 0, s, a);
-    else if (a.lin_base && tuning().attend_fp8_dma >= 0 && (a.n_splits == 1u || n_layers * (a.heads / 4u) < 128u || tuning().attend_fp8_dma > 0))
-        hipLaunchKernelGGL(k_attend_fp8_dma<0>, dim3(a.n_splits, n_layers * (a.heads / kFdHeads)), dim3(64 * kFdHeads), 0, s, a);
-    else if (a.lin_base)
-        hipLaunchKernelGGL(k_attend_fp8_linear<false>, dim3(a.n_splits, n_layers * (a.heads / 4u)), dim3(256), 0, s, a);
-    else if (a.stripe_bases)
-        hipLaunchKernelGGL(k_attend_fp8_linear<true>, dim3(a.n_splits, n_layers * (a.heads / 4u)), dim3(256), 0, s, a);
-    else if (a.table_form)
-        hipLaunchKernelGGL((k_attend_fp8_linear<false, true>), dim3(a.n_splits, n_layers * (a.heads / 4u)), dim3(256), 0, s, a);
-    else            hipLaunchKernelGGL(k_attend_fp8, dim3(a.n_splits, n_layers * (a.heads / 4u)), dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || (a.direct_out && (a.lin_base || a.stripe_bases || a.table_form))) return e;      // (the page-table kernel always writes partials)
     return launch_attend_combine(a, n_layers, d_out, d_lse, s);

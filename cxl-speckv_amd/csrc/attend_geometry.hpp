@@ -1,12 +1,15 @@
-// cxl-speckv_amd/csrc/attend_geometry.hpp -- the launch decision of the batched fused attention as pure host functions: which kernel form runs
-// (batch_form), the split length and the room for pieces (batch_geometry), the pieces of every member (assign_pieces) and the dispatch order
-// (batch_dispatch_order).  Engine::attend_batch, attend_batch_plan and attend_planned (engine_attend.cpp) decide with these and with nothing else,
-// so the three agree by construction; the CPU tests call the same functions (tests/csrc/host_rules_test.cpp) and replay a recorded table of
-// decisions through them (tests/golden/attend_geometry.json).  Plain C++17, no HIP: the tuning keys the rules read come in as values.
-// At the end: when several layers of ONE sequence take the stream form (int4_wg8_stream, mx4_stream; Engine::attend_int4 / attend_mx4).
+// cxl-speckv_amd/csrc/attend_geometry.hpp -- the launch decision of the fused attention as pure host functions.
+// Batches: which kernel form runs (batch_form), the split length and the room for pieces (batch_geometry), the pieces of every member (assign_pieces)
+// and the dispatch order (batch_dispatch_order).  Engine::attend_batch, attend_batch_plan and attend_planned (engine_attend.cpp) decide with these and
+// with nothing else, so the three agree by construction.
+// One sequence (Engine::qk_scores_fp8, attend_fp8, attend_int4, attend_mx4): seq_decide gives the placement form, the tiles, the splits, the stream
+// form (int4_wg8_stream, mx4_stream), what runs in front of the launch and behind it, and for FP8 the kernel launch_attend_fp8 (attend.hip) runs.
+// The CPU tests call the same functions (tests/csrc/host_rules_test.cpp) and replay recorded tables of decisions through them
+// (tests/golden/attend_geometry.json, attend_seq_geometry.json).  Plain C++17, no HIP: the tuning keys the rules read come in as values.
 #pragma once
 #include "ring_rule.hpp"
 
+#include <cmath>
 #include <vector>
 
 namespace speckv {
@@ -22,7 +25,7 @@ enum BatchEntry : uint32_t { kEntryBatch = 0, kEntryPlan = 1 };
 
 // ---- the form ---------------------------------------------------------------------------------------------------------------
 // table / striped: AttendArgs::table_form / stripe_bases; fp8_cls: AttendArgs::fp8_cls; by_class: the members' tiles are counted by residue
-// class (kernels.hpp mx4_striped_tiles); wg8: AttendArgs::wg8 (0: not the whole-record INT4 kernel, 1: its 16-wave form, 2: one-run workgroups);
+// class (ring_rule.hpp mx4_striped_tiles); wg8: AttendArgs::wg8 (0: not the whole-record INT4 kernel, 1: its 16-wave form, 2: one-run workgroups);
 // order_round: sequences per round of the CUs for the kernel a batch of this format runs on (0: longest first), see batch_dispatch_order
 struct BatchForm { bool table, striped, fp8_cls, int4_cls, by_class; uint32_t wg8, order_round; };
 
@@ -293,6 +296,260 @@ inline AttendStream mx4_stream(uint32_t n_layers, uint32_t n_tiles, uint32_t n_p
     const uint32_t wgs = attend_stream > 0 ? static_cast<uint32_t>(attend_stream) : cus / std::max(1u, zgroups);
     if (attend_stream == 0 && (total < 16ull * wgs || fixed_splits <= 1u || n_tiles < kStreamMinTiles)) return AttendStream{};
     return stream_cut(n_layers, n_tiles, wgs);
+}
+
+// ---- one sequence: the launch decision of qk_scores_fp8, attend_fp8, attend_int4 and attend_mx4 -------------------------------------------
+// the tuning keys (tuning.hpp) these rules read: attend_general, attend_splits, attend_stream, attend_fp8_table_regs, attend_fp8_striped_table,
+// attend_int4_striped_wg, attend_fp8_dma
+struct SeqTuning { int32_t general, splits, stream, fp8_table_regs, fp8_striped_table, int4_striped_wg, fp8_dma; };
+// a call: the format (neither fp8 nor mx4: INT4_G32), scores = the scores-only entry (qk_scores_fp8), layers, kv heads, query rows per head, the CUs of
+// the engine's device, the layout's positions per layer, the range AS ATTENDED (Engine::attend_begin: FP8 over a scale table starts at the table's tile,
+// the pages in front of the caller's begin are the skip_pages masked ones) and what the allocation offers: a scale table, its records in one run
+// (Allocation::linear_base), the runs of its regular striping (Allocation::stripe_n; 0: no regular placement)
+struct SeqShape { bool fp8, mx4, scores; uint32_t n_layers, heads, g, cus, num_tokens, pos_begin, n_pages, skip_pages; bool has_tab, one_run; uint32_t stripe_n; };
+// where the record addresses come from -- AttendArgs::lin_base / stripe_bases / table_form; kSeqNone: the FP8 per-wave page-table kernels (k_attend_fp8,
+// k_qk_scores_fp8), which take the query from a quantise launch of its own
+enum SeqPlace : uint32_t { kSeqNone = 0, kSeqLinear = 1, kSeqStriped = 2, kSeqTable = 3 };
+// the kernel launch_attend_fp8 (attend.hip) runs, in the order its branches had them (the class branch has two)
+enum Fp8Kernel : uint32_t {
+    kFp8NotFp8 = 0,
+    kFp8DmaCls = 1,          // k_attend_fp8_dma<2>
+    kFp8RegsCls = 2,         // k_attend_fp8_linear<false, false, true>
+    kFp8DmaTable = 3,        // k_attend_fp8_dma<1>
+    kFp8DmaLinear = 4,       // k_attend_fp8_dma<0>
+    kFp8RegsLinear = 5,      // k_attend_fp8_linear<false>
+    kFp8RegsStriped = 6,     // k_attend_fp8_linear<true>
+    kFp8RegsTable = 7,       // k_attend_fp8_linear<false, true>
+    kFp8PerWave = 8,         // k_attend_fp8
+};
+// place; cls = the tiles are counted by residue class (AttendArgs::fp8_cls, k_attend_int4_wg8<.., CLS>, k_attend_mx4<1>); wg8 = AttendArgs::wg8; n_tiles (by
+// class where cls) in the fixed grid's n_splits x tiles_per_split; stream (n_wgs != 0: the stream form); slots = AttendArgs::n_splits, the partials a row
+// has (the stream's max_slots, else n_splits); parts = rows x slots, what the scratch is sized for; direct_out = the kernel is handed the output rows
+// (AttendArgs::direct_out), rows_final = ... and writes them: no merge launch; zero_page = Engine::ensure_zero_page in front of the launch; quantize_q =
+// launch_quantize_q_e4m3 in front of it; kernel: FP8 only
+struct SeqDecision {
+    SeqPlace place; bool cls; uint32_t wg8, n_tiles, n_splits, tiles_per_split; AttendStream stream; uint32_t slots; uint64_t parts;
+    bool direct_out, rows_final, zero_page, quantize_q; Fp8Kernel kernel;
+};
+
+// every 32-position tile of the range inside the layer's K / V region (the last one may be ragged)
+inline bool seq_fits(const SeqShape& s)
+{
+    return static_cast<uint64_t>(s.pos_begin) + static_cast<uint64_t>((s.n_pages + 15u) / 16u) * 32u <= s.num_tokens;
+}
+// what the three formats end with.  seq_even_split: a forced split count, never more than 2048 pieces; seq_partials (once stream and kernel are known):
+// the partials per row, and whether the rows are written directly
+inline void seq_even_split(SeqDecision& d, uint32_t want, const SeqTuning& t)
+{
+    if (t.splits > 0) want = static_cast<uint32_t>(t.splits);
+    const EvenSplit es = even_split(d.n_tiles, std::max(1u, std::min(want, 2048u)));
+    d.n_splits = es.n_splits;
+    d.tiles_per_split = es.tiles_per_split;
+}
+inline void seq_partials(SeqDecision& d, uint32_t rows)
+{
+    const bool stream = d.stream.n_wgs != 0u;
+    d.slots = stream ? d.stream.max_slots : d.n_splits;      // (stream: slots per row)
+    d.parts = static_cast<uint64_t>(rows) * d.slots;
+    d.direct_out = d.slots == 1u && !stream;                 // no merge launch
+    d.rows_final = d.direct_out && d.kernel != kFp8PerWave;  // (the page-table kernel always writes partials)
+}
+
+// qk_scores_fp8
+inline SeqDecision seq_decide_scores(const SeqShape& s, const SeqTuning& t)
+{
+    // linear form (records in one run, scale table, tile-aligned range inside the layer's region): direct loads
+    const bool fits = s.pos_begin % 32u == 0u && s.has_tab && s.one_run && !t.general && seq_fits(s);
+    SeqDecision d{};
+    d.place = fits ? kSeqLinear : kSeqNone;
+    d.quantize_q = !fits;
+    return d;
+}
+
+// attend_fp8 (attend.hip)
+inline SeqDecision seq_decide_fp8(const SeqShape& s, const SeqTuning& t)
+{
+    SeqDecision d{};
+    // splits: ~20 waves per CU over the launch (the LDS-DMA kernel keeps 8 resident; measured at 70B-shaped, 80 layers:
+    // 8 splits/row 0.72 of HBM peak at 32k and 0.63 at 8k, 16 splits 0.705 / 0.61, 4 splits 0.71 / 0.63, 2: 0.63 / 0.58)
+    // A launch that already has 128+ workgroup columns (layers x head quads) is best left unsplit: each workgroup then
+    // streams one long run, the rows are final (no partials, no merge launch) -- 80 layers: 1 split 0.73 / 0.70 / 0.64 of
+    // HBM peak at 32k / 8k / 2k context against 0.71 / 0.62 / 0.48 with 8 splits.
+    uint32_t n_tiles = (s.n_pages + 15u) / 16u;
+    const uint32_t rows = s.n_layers * s.heads;
+    // linear form: records in one run, scale table present, tiles aligned with the table's (pos_begin a multiple of 32),
+    // and the last (possibly ragged) 32-position tile must not read past the K / V region of its layer
+    // (with the range aligned as above and num_tokens a multiple of 32 the tiles never leave the region)
+    const bool fits = s.has_tab && seq_fits(s);
+    const bool general_env = t.general != 0;
+    const bool linear = !general_env && fits && s.one_run;
+    // regular striping over several pools: the same kernel with computed record addresses (no page-table chase)
+    const bool striped = !linear && fits && s.stripe_n >= 2 && !general_env;
+    // no regular placement (pages migrated one by one), or SPECKV_ATTEND_GENERAL set (measurements, tests): the fast kernel
+    // with its record addresses from the page table, looked up one request ahead
+    const bool table = fits && !linear && !striped;
+    // (the page-table form has nothing to gain from whole rows: it hides its look-ups behind other waves and always
+    // goes through the merge -- 80 layers x 8k: one split 0.13 of HBM peak, eight 0.18+)
+    // (striped / moved placements run the same DMA pipeline with their addresses from the page table, k_attend_fp8_dma<TABLE>: the
+    //  same rule; the register-staged kernels of rounds 2-5 -- a range that starts inside a tile, or on request -- want the splits)
+    const bool dma_table = (striped || table) && s.skip_pages == 0 && t.fp8_table_regs == 0;
+    // striped regularly: the linear pipeline over the range's pages by residue class (k_attend_fp8_dma<2>): the tiles are then counted per class
+    const bool cls = striped && dma_table && s.stripe_n <= 8 && t.fp8_striped_table <= 0;
+    if (cls) n_tiles = mx4_striped_tiles(s.n_pages, s.stripe_n);
+    uint32_t want = ((linear || dma_table) && rows / 4u >= 128u && n_tiles < 768u) ? 1u : (5120u + rows - 1u) / rows;     // (32k and beyond: 8 splits, below)
+    // per-layer calls are latency-bound: short contexts want short splits (measured best: 2 tiles per split at 2k
+    // context, 4 at 8k, 8 at 32k), long multi-layer launches are bounded by `want` above
+    const uint32_t min_tiles = std::min(8u, std::max(2u, n_tiles / 64u));
+    want = std::min(want, std::max(1u, n_tiles / min_tiles));
+    // ... and never more than ONE round of workgroups (round 6, profiles/r06_layers_by_context.txt: one layer x 128k took 512 splits = 1024
+    // workgroups 0.55 of the roofline, 128 splits = 256 workgroups 0.68; 4 layers x 32k 0.65 -> 0.74, 8 x 32k 0.59 -> 0.68, 12 x 16k 0.56 -> 0.65)
+    if (linear || dma_table) want = std::min(want, std::max(1u, s.cus / std::max(1u, rows / 4u)));
+    // Launches of many rows (several layers of one sequence): every workgroup resident at once and the CUs evenly loaded counts for
+    // more than the split length -- 80 layers = 160 workgroup rows: 3 splits = 480 workgroups (15 of 16 CUs hold two) 0.777 of the
+    // roofline at 32k and 0.738 at 8k, 5 splits = 800 (some CUs four, some three) 0.67, 8 = 1280 (a second round) 0.765, one split
+    // (the DMA kernel, 160 of 256 CUs busy) 0.73 / 0.70; 32 layers x 32k: 4 splits = 256 workgroups 0.734, 20 splits 0.72.
+    // So: the split count whose workgroups fill whole rounds of the CUs best, one round at most, splits of 64 tiles or more.
+    // (A stream form as the INT4 / MXFP4 kernels have it -- the launch's rows x tiles in one equal piece per resident workgroup --
+    //  was built for k_attend_fp8_linear and dropped: at the kernel's 128 registers the row-boundary path spilled, and the extra
+    //  partials cost the short contexts more than the balance gave: 32k x 80 0.7635 against 0.7745, 8k 0.66 / 0.74, 128k 0.794 / 0.783.)
+    if ((linear || cls) && rows / 4u >= 32u) {
+        const uint32_t wg_rows = rows / 4u, n_cu = s.cus;
+        uint32_t best_s = 1;
+        double best = -1.0;
+        for (uint32_t sp = 1; sp <= 16u; ++sp) {
+            // (pieces under 64 tiles -- never under 16 -- only while the launch has not filled one round: 32 layers x 2k were 64 workgroups 0.36 of the
+            //  roofline, 8 pieces 0.56; 4k: 128 workgroups 0.64, 8 pieces 0.685)
+            if (sp > 1u && (n_tiles / sp < 16u || (n_tiles / sp < 64u && static_cast<uint64_t>(wg_rows) * (sp - 1u) >= n_cu))) break;
+            const uint64_t wgs = static_cast<uint64_t>(wg_rows) * sp, cap = static_cast<uint64_t>(sp == 1u ? 2u : 4u) * n_cu;      // (resident: DMA kernel 2 per CU, register-staged 4)
+            if (wgs > cap && sp > 1u) break;
+            const double per_cu = static_cast<double>(wgs) / n_cu, score = per_cu / std::ceil(per_cu);
+            if (score > best + 1e-9) { best = score; best_s = sp; }
+        }
+        want = best_s;
+    }
+    d.place = linear ? kSeqLinear : striped ? kSeqStriped : table ? kSeqTable : kSeqNone;
+    d.cls = cls;
+    d.n_tiles = n_tiles;
+    seq_even_split(d, want, t);
+    // one long split per row: the LDS-DMA kernel (two tiles deep per wave, 8 waves per CU); several shorter splits: the
+    // register-staged one (16 waves per CU hide more) -- 80 layers x 32k: 8 splits 0.756 (register-staged) / 0.72 (DMA),
+    // 1 split 0.58 / 0.73; 8k: 1 split DMA 0.69, 8 splits 0.63 / 0.62
+    // (launches with few workgroup columns -- the per-layer calls of one sequence -- are latency-bound either way: DMA kernel,
+    // 13.8 against 15.5 us at 8k context)
+    const bool dma_shape = d.n_splits == 1u || s.n_layers * (s.heads / 4u) < 128u;
+    if (cls) d.kernel = dma_shape ? kFp8DmaCls : kFp8RegsCls;         // striped regularly: the linear kernels over residue classes, by the linear forms' rule
+    else if (dma_table) d.kernel = kFp8DmaTable;                       // moved page by page (or striped, on request): the DMA pipeline with addresses from the page table
+    else if (linear && t.fp8_dma >= 0 && (dma_shape || t.fp8_dma > 0)) d.kernel = kFp8DmaLinear;
+    else if (linear) d.kernel = kFp8RegsLinear;
+    else if (striped) d.kernel = kFp8RegsStriped;
+    else if (table) d.kernel = kFp8RegsTable;
+    else d.kernel = kFp8PerWave;
+    d.zero_page = true;                                                // (every form: the kernels are handed the page whether or not they read it)
+    d.quantize_q = d.place == kSeqNone;                                // the linear / striped / table forms quantise the query in their own prologue
+    seq_partials(d, rows);
+    return d;
+}
+
+// Launch geometry of the whole-record INT4 kernel (k_attend_int4_wg8; 512-thread workgroups, two resident per CU); `cus` = the
+// compute units of the ENGINE's device (Engine::cus()).  Its stream form for many layers of one sequence: int4_wg8_stream above.
+// Fixed grid (per-layer calls, short launches): splits x layers workgroups, in whole rounds of the resident set when the
+// launch is that long, else as many 8-tile pieces as there are.
+inline uint32_t int4_wg8_splits(uint32_t n_layers, uint32_t n_tiles, uint32_t cus)
+{
+    const uint64_t resident = static_cast<uint64_t>(cus);                 // (16-wave workgroups, two halves each: one per CU)
+    const uint64_t total = static_cast<uint64_t>(n_layers) * n_tiles;
+    uint64_t wgs = std::max<uint64_t>(1, total / 64u);
+    if (wgs >= resident && n_layers >= 2u) wgs = resident;                        // several layers: ONE round (80 layers x 16k: 3 splits 0.65, 6: 0.63, 10: 0.54)
+    else if (wgs >= resident) wgs = (wgs + resident / 2u) / resident * resident;  // whole rounds
+    else wgs = std::min<uint64_t>(resident, std::max<uint64_t>(wgs, total / 8u));
+    const uint64_t per_layer = std::max<uint64_t>(1, n_layers >= 2u ? wgs / n_layers : (wgs + n_layers / 2u) / n_layers);
+    return static_cast<uint32_t>(std::min<uint64_t>(per_layer, std::max<uint32_t>(1u, n_tiles / 4u)));
+}
+
+// attend_int4 (attend_int4.hip)
+inline SeqDecision seq_decide_int4(const SeqShape& s, const SeqTuning& t)
+{
+    SeqDecision d{};
+    uint32_t n_tiles = (s.n_pages + 15u) / 16u;
+    // linear form: records in one local run and every 32-position tile inside the layer's K / V region; otherwise the
+    // page-table form of the same kernel
+    const bool fits = seq_fits(s);
+    const bool general_env = t.general != 0;
+    const bool linear = s.one_run && fits && !general_env;
+    const bool striped = !linear && s.stripe_n >= 2 && fits && !general_env;
+    // a pool striped over 2..8 runs, 8 kv heads: the whole-record kernel over the range's pages by residue class (every tile 16
+    // consecutive records of one run: the linear form's fetch; k_attend_int4_wg8<.., CLS>)
+    const bool cls = striped && s.heads == 8 && s.stripe_n <= 8 && t.int4_striped_wg == 0;
+    if (cls) n_tiles = mx4_striped_tiles(s.n_pages, s.stripe_n);
+    // everything else -- no regular placement, a last tile that would leave the region, SPECKV_ATTEND_GENERAL (measurements,
+    // tests) -- takes the workgroup kernel with its record addresses from the page table: its look-ups are clamped to the
+    // range, so a ragged last tile never reads a record it has no business with.  (The per-wave page-table kernel of rounds
+    // 1-3, 0.37 of HBM peak, is gone.)
+    d.place = linear ? kSeqLinear : striped ? kSeqStriped : kSeqTable;
+    const uint32_t rows = s.n_layers * s.heads;
+    uint32_t want = (5120u + rows - 1u) / rows;      // VALU-bound kernel: fewer, longer splits measured best
+    const uint32_t min_tiles = std::min(8u, std::max(2u, n_tiles / 64u));      // per-layer calls: see seq_decide_fp8
+    want = std::min(want, std::max(1u, n_tiles / min_tiles));
+    // Workgroups go to the 8 XCDs round-robin by linear id = split + n_splits * (layer, head quad): with a split count that
+    // is a multiple of 8 the two workgroups that share a page's scale line (head quads 0 and 1) run on the same XCD, next
+    // to each other (measured at 32k x 80 layers: 8 splits 0.598, 10 or 12 splits 0.56, 16 splits 0.595)
+    if (want > 8u) want &= ~7u;
+    // whole-record kernel (8 waves = 8 heads, one workgroup per CU): workgroups = splits x layers, in whole rounds of the CUs
+    const bool wg8 = (linear || cls) && s.heads == 8;
+    if (wg8) want = int4_wg8_splits(s.n_layers, n_tiles, s.cus);
+    d.cls = cls;
+    d.wg8 = wg8 ? 1u : 0u;
+    d.n_tiles = n_tiles;
+    seq_even_split(d, want, t);
+    if (!wg8 && d.n_splits > 8u && (d.n_splits & 7u) && t.splits <= 0) {      // the rounding can fall off a multiple of 8
+        const EvenSplit es = even_split(n_tiles, d.n_splits & ~7u);
+        d.n_splits = es.n_splits;
+        d.tiles_per_split = es.tiles_per_split;
+    }
+    // several layers of one long sequence: the stream form (int4_wg8_stream above; SPECKV_ATTEND_STREAM cuts small calls for the tests)
+    if (wg8) d.stream = int4_wg8_stream(s.n_layers, n_tiles, s.cus, cls, t.splits, t.stream);
+    d.zero_page = !linear;
+    seq_partials(d, rows);
+    return d;
+}
+
+// attend_mx4 (attend_mx4.hip)
+inline SeqDecision seq_decide_mx4(const SeqShape& s, const SeqTuning& t)
+{
+    SeqDecision d{};
+    uint32_t n_tiles = (s.n_pages + 15u) / 16u;
+    // arithmetic addresses need every 32-position tile inside the layer's K / V region (the last one may be ragged); otherwise,
+    // or without a regular placement, the page-table form: its look-ups are clamped to the range
+    const bool fits = seq_fits(s);
+    const bool general_env = t.general != 0;
+    const bool linear = s.one_run && fits && !general_env;
+    // a pool striped over 2..8 runs: the range's pages by residue class of the page index (every tile 16 consecutive records of one
+    // run: the linear form's fetch), whatever the range -- rows past a class's end are masked, nothing needs to "fit"
+    const bool striped = !linear && s.stripe_n >= 2 && s.stripe_n <= 8 && !general_env;
+    const bool table = !linear && !striped;
+    if (striped) n_tiles = mx4_striped_tiles(s.n_pages, s.stripe_n);
+    // workgroups = splits x layers x query-row groups (each covers the 8 kv heads; one resident per CU): one round of the CUs,
+    // rounded down -- 80 layers at 32k: 3 splits (240 workgroups) 0.765 of the HBM roofline, 6 splits 0.72-0.75 (profiles/r05_mx4.txt)
+    const uint32_t rows = s.n_layers * s.heads;
+    const uint32_t columns = s.n_layers * ((s.g + 7u) / 8u);
+    uint32_t want = std::max(1u, (table ? 2u : 1u) * s.cus / columns);          // (the page-table form: two workgroups per CU)
+    const uint32_t min_tiles = std::min(8u, std::max(2u, n_tiles / 64u));      // per-layer calls: see seq_decide_fp8
+    want = std::min(want, std::max(1u, n_tiles / min_tiles));
+    d.place = linear ? kSeqLinear : striped ? kSeqStriped : kSeqTable;
+    d.cls = striped;
+    d.n_tiles = n_tiles;
+    seq_even_split(d, want, t);
+    // several layers of one long sequence: the stream form -- all tiles of the call in layer-major order cut into one equal piece
+    // per CU (80 layers x 3 splits of the fixed grid occupy 240 CUs of 256; profiles/r05_mx4.txt); the decision: mx4_stream above
+    if (linear) d.stream = mx4_stream(s.n_layers, n_tiles, s.n_pages, s.cus, (s.g + 7u) / 8u, d.n_splits, t.splits, t.stream);
+    d.zero_page = table;
+    seq_partials(d, rows);
+    return d;
+}
+
+inline SeqDecision seq_decide(const SeqShape& s, const SeqTuning& t)
+{
+    return s.scores ? seq_decide_scores(s, t) : s.fp8 ? seq_decide_fp8(s, t) : s.mx4 ? seq_decide_mx4(s, t) : seq_decide_int4(s, t);
 }
 
 } // namespace speckv

@@ -1,4 +1,5 @@
-// cxl-speckv_amd/csrc/engine_attend.cpp -- fused decode attention: launch planning for the FP8 / INT4 kernels, single sequences and batches (Engine members)
+// cxl-speckv_amd/csrc/engine_attend.cpp -- fused decode attention over FP8 / INT4_G32 / MXFP4 records, single sequences and batches (Engine members):
+// checks, scratch, arguments and launches around the launch decisions of attend_geometry.hpp
 #include "engine_internal.hpp"
 #include "decode_window.hpp"
 #include "tuning.hpp"
@@ -16,6 +17,42 @@ struct Engine::SeqCall {
     bool done = false;                        // an empty range: answered by attend_begin
     uint32_t pos_begin = 0, n_pages = 0, skip_pages = 0;
     uint64_t k_first = 0, v_first = 0, layer_stride = 0;
+    int scheme = -1;
+    bool scores = false;
+    uint32_t n_layers = 0, g = 0;
+    // the call as the launch decision sees it (attend_geometry.hpp)
+    SeqShape shape(uint32_t cus) const
+    {
+        return SeqShape{scheme == SPECKV_COMP_FP8_E4M3, scheme == SPECKV_COMP_MXFP4, scores, n_layers, a->layout.num_heads, g, cus, a->layout.num_tokens,
+                        pos_begin, n_pages, skip_pages, a->d_scale_tab != nullptr, a->linear_base != nullptr, a->stripe_n};
+    }
+    // the fields an attention launch takes from the call and its decision (zero_page: after ensure_zero_page, where the form needs it); the query
+    // pointers and the FP8 tables are the entry's
+    void args(AttendArgs& k, const SeqDecision& d, float sm_scale, const uint8_t* zero_page, float* d_out, float* d_lse) const
+    {
+        k.entries = a->d_entries;
+        k.k_first = k_first;
+        k.v_first = v_first;
+        k.layer_stride = layer_stride;
+        k.n_pages = n_pages;
+        k.skip_pages = skip_pages;
+        k.heads = a->layout.num_heads;
+        k.g = g;
+        k.scale_log2e = sm_scale * 1.4426950408889634f;
+        k.zero_page = zero_page;
+        k.n_splits = d.slots;
+        k.tiles_per_split = d.tiles_per_split;
+        k.stream = d.stream;
+        k.wg8 = d.wg8;
+        if (d.place == kSeqLinear) k.lin_base = a->linear_base;
+        if (d.place == kSeqStriped) {
+            k.stripe_bases = a->d_stripe;
+            k.stripe_n = a->stripe_n;
+            k.stripe_magic = static_cast<uint32_t>((1ull << 32) / a->stripe_n + 1u);
+        }
+        if (d.place == kSeqTable) k.table_form = 1u;
+        if (d.direct_out) { k.direct_out = d_out; k.direct_lse = d_lse; }
+    }
 };
 
 // Checks the allocation's layout and the range, applies the NULL stream rule, answers an empty range (zeros; qk_scores_fp8, scores: nothing to
@@ -34,6 +71,7 @@ int Engine::attend_begin(int scheme, bool scores, uint64_t handle, uint32_t laye
         return SPECKV_ERR_INVAL;
     if (g == 0 || g > 16 || !d_q_f16 || !d_out) return SPECKV_ERR_INVAL;
     c.a = a;
+    c.scheme = scheme; c.scores = scores; c.n_layers = n_layers; c.g = g;
     const bool empty = pos_end == pos_begin;
     if (scores && empty) { c.done = true; return SPECKV_OK; }
     if (!empty) {
@@ -94,26 +132,6 @@ uint8_t* Engine::attend_scratch(AttendArgs& k, uint64_t parts, size_t head_bytes
     return buf;
 }
 
-// the fields every single-sequence attention launch takes from its call (zero_page: after ensure_zero_page, where the form needs it)
-static void seq_args(AttendArgs& k, const Allocation* a, uint64_t k_first, uint64_t v_first, uint64_t layer_stride, uint32_t n_pages, uint32_t g,
-                     float sm_scale, const uint8_t* zero_page)
-{
-    k.entries = a->d_entries;
-    k.k_first = k_first;
-    k.v_first = v_first;
-    k.layer_stride = layer_stride;
-    k.n_pages = n_pages;
-    k.heads = a->layout.num_heads;
-    k.g = g;
-    k.scale_log2e = sm_scale * 1.4426950408889634f;
-    k.zero_page = zero_page;
-}
-static void striped_args(AttendArgs& k, const Allocation* a)
-{
-    k.stripe_bases = a->d_stripe;
-    k.stripe_n = a->stripe_n;
-    k.stripe_magic = static_cast<uint32_t>((1ull << 32) / a->stripe_n + 1u);
-}
 // A launch under a window runs the bodies that mask the leading positions of a member's first tile (AttendArgs::seq_skip): the linear, striped and
 // table forms.  The forms by residue class (k_attend_mx4<1>, k_attend_int4_wg8<.., true>, k_attend_fp8_linear<.., CLS>) count their tiles class by class and
 // have no such mask: their launches go through the page tables, which take any range (FP8: the register-staged table kernel -- k_attend_fp8_dma<1> has
@@ -130,6 +148,9 @@ static uint32_t plan_bound(uint32_t max_pos_end, uint32_t stripe_n_max, uint32_t
     return window ? std::min(ctx, decode_window_tiles_bound(window)) : ctx;
 }
 
+// ---- one sequence ------------------------------------------------------------------------------------------------------------
+// Every entry: attend_begin, the launch decision on the call's shape (attend_geometry.hpp seq_decide: the rules and the measurements behind them),
+// the zero page and the scratch it asks for, the arguments from call and decision, the launch, attend_end.
 int Engine::qk_scores_fp8(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
                           uint32_t pos_begin, uint32_t pos_end, float* d_out, hipStream_t s)
 {
@@ -139,35 +160,28 @@ int Engine::qk_scores_fp8(uint64_t handle, uint32_t layer, uint32_t n_layers, co
     if (rc != SPECKV_OK || c.done) return rc;
     Allocation* a = c.a;
     const Layout& L = a->layout;
-    const uint32_t n_pages = c.n_pages;
-    // shim layout [req 0][layer][kind 0 = K][pos][head]: page of (layer, pos)
-    const uint64_t first_page = c.k_first, layer_stride = c.layer_stride;
-    hipStream_t st = c.st;
-    {   // linear form (records in one run, scale table, tile-aligned range inside the layer's region): direct loads
-        const uint32_t n_tiles = (n_pages + 15u) / 16u;
-        const bool fits = pos_begin % 32u == 0u && a->d_scale_tab && a->linear_base && !tuning().attend_general &&
-                          static_cast<uint64_t>(pos_begin) + static_cast<uint64_t>(n_tiles) * 32u <= L.num_tokens;
-        if (fits) {
-            AttendArgs k{};
-            k.k_first = first_page;
-            k.layer_stride = layer_stride;
-            k.n_pages = n_pages;
-            k.heads = L.num_heads;
-            k.g = g;
-            k.tiles_per_split = 16;
-            k.lin_base = a->linear_base;
-            k.scale_tab = a->d_scale_tab;
-            k.q16 = static_cast<const uint16_t*>(d_q_f16);
-            HIP_TRY(launch_qk_scores_fp8_linear(k, n_layers, d_out, st));
-            return attend_end(c, s);
-        }
+    const SeqDecision d = seq_decide(c.shape(cus()), seq_tuning());
+    // shim layout [req 0][layer][kind 0 = K][pos][head]: page of (layer, pos) = c.k_first + layer * c.layer_stride
+    if (!d.quantize_q) {
+        AttendArgs k{};
+        k.k_first = c.k_first;
+        k.layer_stride = c.layer_stride;
+        k.n_pages = c.n_pages;
+        k.heads = L.num_heads;
+        k.g = g;
+        k.tiles_per_split = 16;
+        k.lin_base = a->linear_base;
+        k.scale_tab = a->d_scale_tab;
+        k.q16 = static_cast<const uint16_t*>(d_q_f16);
+        HIP_TRY(launch_qk_scores_fp8_linear(k, n_layers, d_out, c.st));
+        return attend_end(c, s);
     }
     const size_t rows = static_cast<size_t>(n_layers) * L.num_heads * 16;
     uint8_t* q8 = static_cast<uint8_t*>(scratch(s_req_, rows * 128 + rows * sizeof(float), s));
     if (!q8) return SPECKV_ERR_NOMEM;
     float* qs = reinterpret_cast<float*>(q8 + rows * 128);
-    HIP_TRY(launch_quantize_q_e4m3(d_q_f16, n_layers * L.num_heads, g, L.head_dim, q8, qs, st));
-    HIP_TRY(launch_qk_scores_fp8(a->d_entries, first_page, layer_stride, n_layers, n_pages, L.num_heads, g, q8, qs, d_out, st));
+    HIP_TRY(launch_quantize_q_e4m3(d_q_f16, n_layers * L.num_heads, g, L.head_dim, q8, qs, c.st));
+    HIP_TRY(launch_qk_scores_fp8(a->d_entries, c.k_first, c.layer_stride, n_layers, c.n_pages, L.num_heads, g, q8, qs, d_out, c.st));
     return attend_end(c, s);
 }
 
@@ -179,93 +193,60 @@ int Engine::attend_fp8(uint64_t handle, uint32_t layer, uint32_t n_layers, const
     SeqCall c;
     const int rc = attend_begin(SPECKV_COMP_FP8_E4M3, false, handle, layer, n_layers, d_q_f16, g, pos_begin, pos_end, d_out, s, c);
     if (rc != SPECKV_OK || c.done) return rc;
-    Allocation* a = c.a;
-    const Layout& L = a->layout;
-    hipStream_t st = c.st;
-    const bool has_tab = a->d_scale_tab != nullptr;
-    const uint32_t skip_pages = c.skip_pages, n_pages = c.n_pages;
-    pos_begin = c.pos_begin;                  // (aligned to the scale table's tiles: attend_begin)
-    RC_TRY(ensure_zero_page(s));
-    // splits: ~20 waves per CU over the launch (the LDS-DMA kernel keeps 8 resident; measured at 70B-shaped, 80 layers:
-    // 8 splits/row 0.72 of HBM peak at 32k and 0.63 at 8k, 16 splits 0.705 / 0.61, 4 splits 0.71 / 0.63, 2: 0.63 / 0.58)
-    // A launch that already has 128+ workgroup columns (layers x head quads) is best left unsplit: each workgroup then
-    // streams one long run, the rows are final (no partials, no merge launch) -- 80 layers: 1 split 0.73 / 0.70 / 0.64 of
-    // HBM peak at 32k / 8k / 2k context against 0.71 / 0.62 / 0.48 with 8 splits.
-    uint32_t n_tiles = (n_pages + 15u) / 16u;
-    const uint32_t rows = n_layers * L.num_heads;
-    // linear form: records in one run, scale table present, tiles aligned with the table's (pos_begin a multiple of 32),
-    // and the last (possibly ragged) 32-position tile must not read past the K / V region of its layer
-    // (with the range aligned as above and num_tokens a multiple of 32 the tiles never leave the region)
-    const bool fits = has_tab && static_cast<uint64_t>(pos_begin) + static_cast<uint64_t>(n_tiles) * 32u <= L.num_tokens;
-    const bool general_env = tuning().attend_general != 0;
-    const uint8_t* lin_base = (general_env || !fits) ? nullptr : a->linear_base;
-    // regular striping over several pools: the same kernel with computed record addresses (no page-table chase)
-    const bool striped = !lin_base && fits && a->stripe_n >= 2 && !general_env;
-    // no regular placement (pages migrated one by one), or SPECKV_ATTEND_GENERAL set (measurements, tests): the fast kernel
-    // with its record addresses from the page table, looked up one request ahead
-    const bool table = fits && !lin_base && !striped;
-    // (the page-table form has nothing to gain from whole rows: it hides its look-ups behind other waves and always
-    // goes through the merge -- 80 layers x 8k: one split 0.13 of HBM peak, eight 0.18+)
-    // (striped / moved placements run the same DMA pipeline with their addresses from the page table, k_attend_fp8_dma<TABLE>: the
-    //  same rule; the register-staged kernels of rounds 2-5 -- a range that starts inside a tile, or on request -- want the splits)
-    const bool dma_table = (striped || table) && skip_pages == 0 && tuning().attend_fp8_table_regs == 0;
-    // striped regularly: the linear pipeline over the range's pages by residue class (k_attend_fp8_dma<2>): the tiles are then counted per class
-    const bool cls = striped && dma_table && a->stripe_n <= 8 && tuning().attend_fp8_striped_table <= 0;
-    if (cls) n_tiles = mx4_striped_tiles(n_pages, a->stripe_n);
-    uint32_t want = ((lin_base || dma_table) && rows / 4u >= 128u && n_tiles < 768u) ? 1u : (5120u + rows - 1u) / rows;     // (32k and beyond: 8 splits, below)
-    // per-layer calls are latency-bound: short contexts want short splits (measured best: 2 tiles per split at 2k
-    // context, 4 at 8k, 8 at 32k), long multi-layer launches are bounded by `want` above
-    const uint32_t min_tiles = std::min(8u, std::max(2u, n_tiles / 64u));
-    want = std::min(want, std::max(1u, n_tiles / min_tiles));
-    // ... and never more than ONE round of workgroups (round 6, profiles/r06_layers_by_context.txt: one layer x 128k took 512 splits = 1024
-    // workgroups 0.55 of the roofline, 128 splits = 256 workgroups 0.68; 4 layers x 32k 0.65 -> 0.74, 8 x 32k 0.59 -> 0.68, 12 x 16k 0.56 -> 0.65)
-    if (lin_base || dma_table) want = std::min(want, std::max(1u, cus() / std::max(1u, rows / 4u)));
-    // Launches of many rows (several layers of one sequence): every workgroup resident at once and the CUs evenly loaded counts for
-    // more than the split length -- 80 layers = 160 workgroup rows: 3 splits = 480 workgroups (15 of 16 CUs hold two) 0.777 of the
-    // roofline at 32k and 0.738 at 8k, 5 splits = 800 (some CUs four, some three) 0.67, 8 = 1280 (a second round) 0.765, one split
-    // (the DMA kernel, 160 of 256 CUs busy) 0.73 / 0.70; 32 layers x 32k: 4 splits = 256 workgroups 0.734, 20 splits 0.72.
-    // So: the split count whose workgroups fill whole rounds of the CUs best, one round at most, splits of 64 tiles or more.
-    // (A stream form as the INT4 / MXFP4 kernels have it -- the launch's rows x tiles in one equal piece per resident workgroup --
-    //  was built for k_attend_fp8_linear and dropped: at the kernel's 128 registers the row-boundary path spilled, and the extra
-    //  partials cost the short contexts more than the balance gave: 32k x 80 0.7635 against 0.7745, 8k 0.66 / 0.74, 128k 0.794 / 0.783.)
-    if ((lin_base || cls) && rows / 4u >= 32u) {
-        const uint32_t wg_rows = rows / 4u, n_cu = cus();
-        uint32_t best_s = 1;
-        double best = -1.0;
-        for (uint32_t sp = 1; sp <= 16u; ++sp) {
-            // (pieces under 64 tiles -- never under 16 -- only while the launch has not filled one round: 32 layers x 2k were 64 workgroups 0.36 of the
-            //  roofline, 8 pieces 0.56; 4k: 128 workgroups 0.64, 8 pieces 0.685)
-            if (sp > 1u && (n_tiles / sp < 16u || (n_tiles / sp < 64u && static_cast<uint64_t>(wg_rows) * (sp - 1u) >= n_cu))) break;
-            const uint64_t wgs = static_cast<uint64_t>(wg_rows) * sp, cap = static_cast<uint64_t>(sp == 1u ? 2u : 4u) * n_cu;      // (resident: DMA kernel 2 per CU, register-staged 4)
-            if (wgs > cap && sp > 1u) break;
-            const double per_cu = static_cast<double>(wgs) / n_cu, score = per_cu / std::ceil(per_cu);
-            if (score > best + 1e-9) { best = score; best_s = sp; }
-        }
-        want = best_s;
-    }
-    if (tuning().attend_splits > 0) want = static_cast<uint32_t>(tuning().attend_splits);
-    const EvenSplit es = even_split(n_tiles, std::max(1u, std::min(want, 2048u)));
-    const uint32_t n_splits = es.n_splits, tiles_per_split = es.tiles_per_split;
+    const Allocation* a = c.a;
+    const SeqDecision d = seq_decide(c.shape(cus()), seq_tuning());
+    if (d.zero_page) RC_TRY(ensure_zero_page(s));
+    // in front of the partials: the quantised query [rows][16][128] e4m3 and its scales [rows][16]
+    const uint32_t rows = n_layers * a->layout.num_heads;
     const size_t q_bytes = static_cast<size_t>(rows) * 16 * 128, qs_bytes = static_cast<size_t>(rows) * 16 * sizeof(float);
     AttendArgs k{};
-    uint8_t* buf = attend_scratch(k, static_cast<uint64_t>(rows) * n_splits, q_bytes + qs_bytes, s);
+    uint8_t* buf = attend_scratch(k, d.parts, q_bytes + qs_bytes, s);
     if (!buf) return SPECKV_ERR_NOMEM;
-    seq_args(k, a, c.k_first, c.v_first, c.layer_stride, n_pages, g, sm_scale, d_zero_page_);
-    k.skip_pages = skip_pages;
-    k.n_splits = n_splits;
-    k.tiles_per_split = tiles_per_split;
+    c.args(k, d, sm_scale, d_zero_page_, d_out, d_lse);
     k.q8 = buf;
     k.qs = reinterpret_cast<float*>(buf + q_bytes);
     k.scale_tab = a->d_scale_tab;
     k.q16 = static_cast<const uint16_t*>(d_q_f16);
-    k.lin_base = lin_base;
-    if (striped) striped_args(k, a);
-    if (cls) { k.fp8_cls = 1u; k.scale_run = a->scale_run; }
-    if (table) { k.table_form = 1u; k.lin_base = nullptr; k.stripe_bases = nullptr; }
-    if (!k.lin_base && !striped && !table)         // the linear / striped / table forms quantise the query in their own prologue
-        HIP_TRY(launch_quantize_q_e4m3(d_q_f16, rows, g, L.head_dim, buf, reinterpret_cast<float*>(buf + q_bytes), st));
-    if (n_splits == 1u) { k.direct_out = d_out; k.direct_lse = d_lse; }      // no merge launch (linear / striped form)
-    HIP_TRY(launch_attend_fp8(k, n_layers, d_out, d_lse, st));
+    if (d.cls) { k.fp8_cls = 1u; k.scale_run = a->scale_run; }
+    if (d.quantize_q) HIP_TRY(launch_quantize_q_e4m3(d_q_f16, rows, g, a->layout.head_dim, buf, reinterpret_cast<float*>(buf + q_bytes), c.st));
+    HIP_TRY(launch_attend_fp8(k, d.kernel, n_layers, d_out, d_lse, c.st));
+    return attend_end(c, s);
+}
+
+// Fused decode attention over INT4_G32 K and V records (attend_int4.hip): any placement.
+int Engine::attend_int4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
+                        uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+{
+    if (null_) return no_data_path("speckv_ext_attend_int4");
+    SeqCall c;
+    const int rc = attend_begin(SPECKV_COMP_INT4_G32, false, handle, layer, n_layers, d_q_f16, g, pos_begin, pos_end, d_out, s, c);
+    if (rc != SPECKV_OK || c.done) return rc;
+    const SeqDecision d = seq_decide(c.shape(cus()), seq_tuning());
+    if (d.zero_page) RC_TRY(ensure_zero_page(s));
+    AttendArgs k{};
+    if (!attend_scratch(k, d.parts, 0, s)) return SPECKV_ERR_NOMEM;
+    c.args(k, d, sm_scale, d_zero_page_, d_out, d_lse);
+    k.q8 = static_cast<const uint8_t*>(d_q_f16);
+    HIP_TRY(launch_attend_int4(k, n_layers, c.st));
+    if (!d.rows_final) HIP_TRY(launch_attend_combine(k, n_layers, d_out, d_lse, c.st));
+    return attend_end(c, s);
+}
+
+// Fused decode attention over MXFP4 K and V records (attend_mx4.hip): any placement.
+int Engine::attend_mx4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
+                       uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+{
+    if (null_) return no_data_path("speckv_ext_attend_mx4");
+    SeqCall c;
+    const int rc = attend_begin(SPECKV_COMP_MXFP4, false, handle, layer, n_layers, d_q_f16, g, pos_begin, pos_end, d_out, s, c);
+    if (rc != SPECKV_OK || c.done) return rc;
+    const SeqDecision d = seq_decide(c.shape(cus()), seq_tuning());
+    if (d.zero_page) RC_TRY(ensure_zero_page(s));
+    AttendArgs k{};
+    if (!attend_scratch(k, d.parts, 0, s)) return SPECKV_ERR_NOMEM;
+    c.args(k, d, sm_scale, d_zero_page_, d_out, d_lse);
+    k.q16 = static_cast<const uint16_t*>(d_q_f16);
+    HIP_TRY(launch_attend_mx4(k, n_layers, d_out, d_lse, c.st));
     return attend_end(c, s);
 }
 
@@ -717,139 +698,6 @@ int Engine::attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t
     if (n_rows == 0) return SPECKV_OK;
     return launch_on(s, [&](hipStream_t st) { return launch_attend_fold_masked(n_rows, d_rows, heads, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems,
                                                                                pos_stride_elems, d_mask, mask_stride, sm_scale, d_out, d_lse, st); });
-}
-
-// Launch geometry of the whole-record INT4 kernel (k_attend_int4_wg8; 512-thread workgroups, two resident per CU); `cus` = the
-// compute units of the ENGINE's device (Engine::cus()).  Its stream form for many layers of one sequence: attend_geometry.hpp int4_wg8_stream.
-// Fixed grid (per-layer calls, short launches): splits x layers workgroups, in whole rounds of the resident set when the
-// launch is that long, else as many 8-tile pieces as there are.
-static uint32_t int4_wg8_splits(uint32_t n_layers, uint32_t n_tiles, uint32_t cus)
-{
-    const uint64_t resident = static_cast<uint64_t>(cus);                 // (16-wave workgroups, two halves each: one per CU)
-    const uint64_t total = static_cast<uint64_t>(n_layers) * n_tiles;
-    uint64_t wgs = std::max<uint64_t>(1, total / 64u);
-    if (wgs >= resident && n_layers >= 2u) wgs = resident;                        // several layers: ONE round (80 layers x 16k: 3 splits 0.65, 6: 0.63, 10: 0.54)
-    else if (wgs >= resident) wgs = (wgs + resident / 2u) / resident * resident;  // whole rounds
-    else wgs = std::min<uint64_t>(resident, std::max<uint64_t>(wgs, total / 8u));
-    const uint64_t per_layer = std::max<uint64_t>(1, n_layers >= 2u ? wgs / n_layers : (wgs + n_layers / 2u) / n_layers);
-    return static_cast<uint32_t>(std::min<uint64_t>(per_layer, std::max<uint32_t>(1u, n_tiles / 4u)));
-}
-
-// Fused decode attention over INT4_G32 K and V records (attend_int4.hip): linear placement only.
-int Engine::attend_int4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
-                        uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
-{
-    if (null_) return no_data_path("speckv_ext_attend_int4");
-    SeqCall c;
-    const int rc = attend_begin(SPECKV_COMP_INT4_G32, false, handle, layer, n_layers, d_q_f16, g, pos_begin, pos_end, d_out, s, c);
-    if (rc != SPECKV_OK || c.done) return rc;
-    Allocation* a = c.a;
-    const Layout& L = a->layout;
-    hipStream_t st = c.st;
-    const uint32_t n_pages = c.n_pages;
-    uint32_t n_tiles = (n_pages + 15u) / 16u;
-    // linear form: records in one local run and every 32-position tile inside the layer's K / V region; otherwise the
-    // page-table form of the same kernel
-    const bool fits = static_cast<uint64_t>(pos_begin) + static_cast<uint64_t>(n_tiles) * 32u <= L.num_tokens;
-    const bool general_env = tuning().attend_general != 0;
-    const bool linear = a->linear_base && fits && !general_env;
-    const bool striped = !linear && a->stripe_n >= 2 && fits && !general_env;
-    // a pool striped over 2..8 runs, 8 kv heads: the whole-record kernel over the range's pages by residue class (every tile 16
-    // consecutive records of one run: the linear form's fetch; k_attend_int4_wg8<.., CLS>)
-    const bool cls = striped && L.num_heads == 8 && a->stripe_n <= 8 && tuning().attend_int4_striped_wg == 0;
-    if (cls) n_tiles = mx4_striped_tiles(n_pages, a->stripe_n);
-    // everything else -- no regular placement, a last tile that would leave the region, SPECKV_ATTEND_GENERAL (measurements,
-    // tests) -- takes the workgroup kernel with its record addresses from the page table: its look-ups are clamped to the
-    // range, so a ragged last tile never reads a record it has no business with.  (The per-wave page-table kernel of rounds
-    // 1-3, 0.37 of HBM peak, is gone.)
-    const bool table = !linear && !striped;
-    if (!linear) RC_TRY(ensure_zero_page(s));
-    const uint32_t rows = n_layers * L.num_heads;
-    uint32_t want = (5120u + rows - 1u) / rows;      // VALU-bound kernel: fewer, longer splits measured best
-    const uint32_t min_tiles = std::min(8u, std::max(2u, n_tiles / 64u));      // per-layer calls: see attend_fp8
-    want = std::min(want, std::max(1u, n_tiles / min_tiles));
-    // Workgroups go to the 8 XCDs round-robin by linear id = split + n_splits * (layer, head quad): with a split count that
-    // is a multiple of 8 the two workgroups that share a page's scale line (head quads 0 and 1) run on the same XCD, next
-    // to each other (measured at 32k x 80 layers: 8 splits 0.598, 10 or 12 splits 0.56, 16 splits 0.595)
-    if (want > 8u) want &= ~7u;
-    // whole-record kernel (8 waves = 8 heads, one workgroup per CU): workgroups = splits x layers, in whole rounds of the CUs
-    const bool wg8 = (linear || cls) && L.num_heads == 8;
-    if (wg8) want = int4_wg8_splits(n_layers, n_tiles, cus());
-    const bool forced_splits = tuning().attend_splits > 0;
-    if (forced_splits) want = static_cast<uint32_t>(tuning().attend_splits);
-    EvenSplit es = even_split(n_tiles, std::max(1u, std::min(want, 2048u)));
-    if (!wg8 && es.n_splits > 8u && (es.n_splits & 7u) && !forced_splits)      // the rounding can fall off a multiple of 8
-        es = even_split(n_tiles, es.n_splits & ~7u);
-    AttendArgs k{};
-    // several layers of one long sequence: the stream form (attend_geometry.hpp; SPECKV_ATTEND_STREAM cuts small calls for the tests)
-    if (wg8) k.stream = int4_wg8_stream(n_layers, n_tiles, cus(), cls, tuning().attend_splits, tuning().attend_stream);
-    const bool stream = k.stream.n_wgs != 0u;
-    const uint32_t n_splits = stream ? k.stream.max_slots : es.n_splits, tiles_per_split = es.tiles_per_split;      // (stream: slots per row)
-    if (!attend_scratch(k, static_cast<uint64_t>(rows) * n_splits, 0, s)) return SPECKV_ERR_NOMEM;
-    seq_args(k, a, c.k_first, c.v_first, c.layer_stride, n_pages, g, sm_scale, d_zero_page_);
-    k.n_splits = n_splits;
-    k.tiles_per_split = tiles_per_split;
-    k.q8 = static_cast<const uint8_t*>(d_q_f16);
-    k.lin_base = linear ? a->linear_base : nullptr;
-    if (table) k.table_form = 1u;
-    if (wg8) k.wg8 = 1u;
-    if (striped) striped_args(k, a);
-    if (n_splits == 1u && !stream) { k.direct_out = d_out; k.direct_lse = d_lse; }      // no merge launch
-    HIP_TRY(launch_attend_int4(k, n_layers, st));
-    if (!k.direct_out) HIP_TRY(launch_attend_combine(k, n_layers, d_out, d_lse, st));
-    return attend_end(c, s);
-}
-
-// Fused decode attention over MXFP4 K and V records (attend_mx4.hip): any placement.
-int Engine::attend_mx4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
-                       uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
-{
-    if (null_) return no_data_path("speckv_ext_attend_mx4");
-    SeqCall c;
-    const int rc = attend_begin(SPECKV_COMP_MXFP4, false, handle, layer, n_layers, d_q_f16, g, pos_begin, pos_end, d_out, s, c);
-    if (rc != SPECKV_OK || c.done) return rc;
-    Allocation* a = c.a;
-    const Layout& L = a->layout;
-    hipStream_t st = c.st;
-    const uint32_t n_pages = c.n_pages;
-    uint32_t n_tiles = (n_pages + 15u) / 16u;
-    // arithmetic addresses need every 32-position tile inside the layer's K / V region (the last one may be ragged); otherwise,
-    // or without a regular placement, the page-table form: its look-ups are clamped to the range
-    const bool fits = static_cast<uint64_t>(pos_begin) + static_cast<uint64_t>(n_tiles) * 32u <= L.num_tokens;
-    const bool general_env = tuning().attend_general != 0;
-    const bool linear = a->linear_base && fits && !general_env;
-    // a pool striped over 2..8 runs: the range's pages by residue class of the page index (every tile 16 consecutive records of one
-    // run: the linear form's fetch), whatever the range -- rows past a class's end are masked, nothing needs to "fit"
-    const bool striped = !linear && a->stripe_n >= 2 && a->stripe_n <= 8 && !general_env;
-    const bool table = !linear && !striped;
-    if (table) RC_TRY(ensure_zero_page(s));
-    if (striped) n_tiles = mx4_striped_tiles(n_pages, a->stripe_n);
-    // workgroups = splits x layers x query-row groups (each covers the 8 kv heads; one resident per CU): one round of the CUs,
-    // rounded down -- 80 layers at 32k: 3 splits (240 workgroups) 0.765 of the HBM roofline, 6 splits 0.72-0.75 (profiles/r05_mx4.txt)
-    const uint32_t rows = n_layers * L.num_heads;
-    const uint32_t columns = n_layers * ((g + 7u) / 8u);
-    uint32_t want = std::max(1u, (table ? 2u : 1u) * cus() / columns);          // (the page-table form: two workgroups per CU)
-    const uint32_t min_tiles = std::min(8u, std::max(2u, n_tiles / 64u));      // per-layer calls: see attend_fp8
-    want = std::min(want, std::max(1u, n_tiles / min_tiles));
-    if (tuning().attend_splits > 0) want = static_cast<uint32_t>(tuning().attend_splits);
-    const EvenSplit es = even_split(n_tiles, std::max(1u, std::min(want, 2048u)));
-    AttendArgs k{};
-    // several layers of one long sequence: the stream form -- all tiles of the call in layer-major order cut into one equal piece
-    // per CU (80 layers x 3 splits of the fixed grid occupy 240 CUs of 256; profiles/r05_mx4.txt); the decision: attend_geometry.hpp
-    if (linear) k.stream = mx4_stream(n_layers, n_tiles, n_pages, cus(), (g + 7u) / 8u, es.n_splits, tuning().attend_splits, tuning().attend_stream);
-    const bool stream = k.stream.n_wgs != 0u;
-    const uint32_t n_splits = stream ? k.stream.max_slots : es.n_splits, tiles_per_split = es.tiles_per_split;       // (stream: slots per row)
-    if (!attend_scratch(k, static_cast<uint64_t>(rows) * n_splits, 0, s)) return SPECKV_ERR_NOMEM;
-    seq_args(k, a, c.k_first, c.v_first, c.layer_stride, n_pages, g, sm_scale, d_zero_page_);
-    k.n_splits = n_splits;
-    k.tiles_per_split = tiles_per_split;
-    k.q16 = static_cast<const uint16_t*>(d_q_f16);
-    k.lin_base = linear ? a->linear_base : nullptr;
-    if (table) k.table_form = 1u;
-    if (striped) striped_args(k, a);
-    if (n_splits == 1u && !stream) { k.direct_out = d_out; k.direct_lse = d_lse; }      // no merge launch
-    HIP_TRY(launch_attend_mx4(k, n_layers, d_out, d_lse, st));
-    return attend_end(c, s);
 }
 
 } // namespace speckv

@@ -129,6 +129,13 @@ BatchTuning batch_tuning()
     return BatchTuning{t.attend_tiles_per_split, t.attend_order_as_given, t.attend_fp8_table_regs, t.attend_fp8_striped_table, t.attend_int4_striped_wg};
 }
 
+// ... and the single-sequence entries' (qk_scores_fp8, attend_fp8 / _int4 / _mx4)
+SeqTuning seq_tuning()
+{
+    const Tuning& t = tuning();
+    return SeqTuning{t.attend_general, t.attend_splits, t.attend_stream, t.attend_fp8_table_regs, t.attend_fp8_striped_table, t.attend_int4_striped_wg, t.attend_fp8_dma};
+}
+
 // A batch launch reads its descriptor slot in place: whatever was launched must have passed before the slot is written again.  The
 // slot's event is recorded on EVERY way out of the scope that holds the guard (a merge launch that fails behind an
 // attention launch that went through used to leave the slot unguarded under a kernel still fetching from it).

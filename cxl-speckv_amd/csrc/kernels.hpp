@@ -619,19 +619,7 @@ struct AttendArgs {
     const uint32_t* seq_skip;
 };
 // (the stream partition -- attend_stream_begin / _wg_of / _count -- is plain arithmetic the host decides with too: ring_rule.hpp)
-// MXFP4 over a striped pool (k_attend_mx4 form 1): the positions of the range are taken CLASS by class -- class c = the pages j
-// of the range with j % stripe_n == c, which are consecutive records of ONE run for K and of one run for V -- each class in
-// tiles of 16 pages; every class gets the tile count of the largest (trailing tiles of the others are masked).
-__host__ __device__ inline uint32_t mx4_class_tiles(uint32_t n_pages, uint32_t stripe_n)
-{
-    return ((n_pages + stripe_n - 1u) / stripe_n + 15u) / 16u;
-}
-// tiles of a range in that form (stripe_n = 1, a single run: the plain count)
-__host__ __device__ inline uint32_t mx4_striped_tiles(uint32_t n_pages, uint32_t stripe_n)
-{
-    const uint32_t n = stripe_n ? stripe_n : 1u;
-    return n_pages ? n * mx4_class_tiles(n_pages, n) : 0u;
-}
+// (the tiles of a range taken by residue class -- mx4_class_tiles / mx4_striped_tiles -- likewise: ring_rule.hpp)
 #if defined(__HIPCC__)
 // record address of page p in the striped form; `bases` = the allocation's run bases copied to LDS
 __device__ __forceinline__ const uint8_t* attend_stripe_rec(const uint64_t* bases, uint32_t p, uint32_t n, uint32_t magic, uint32_t stride)
@@ -669,8 +657,10 @@ hipError_t launch_attend_fold_held(uint32_t n_rows, const uint32_t* d_rows, uint
 hipError_t launch_attend_fold_masked(uint32_t n_rows, const uint32_t* d_rows, uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16,
                                      const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
                                      const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
-// a.lin_base set: linear form (a.scale_tab, a.q16); else page-table form (a.q8 / a.qs from launch_quantize_q_e4m3)
-hipError_t launch_attend_fp8(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s);
+// a.lin_base set: linear form (a.scale_tab, a.q16); else page-table form (a.q8 / a.qs from launch_quantize_q_e4m3); kernel: the one the engine's
+// decision names (attend_geometry.hpp: seq_decide_fp8)
+enum Fp8Kernel : uint32_t;
+hipError_t launch_attend_fp8(const AttendArgs& a, Fp8Kernel kernel, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s);
 // scale_tab[tile order of p] = entries[p].rec_bytes >= 2048 ? entries[p].scale : 0 for every page (set_layout time)
 hipError_t launch_build_scale_tab(const PageEntry* d_entries, uint64_t n_pages, uint32_t region_pages, float* d_scale_tab, hipStream_t s, uint32_t scale_run = 0);
 // the run-order part of a scale table (CodecArgs::scale_run): index of page p relative to scale_tab

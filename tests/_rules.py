@@ -1,5 +1,6 @@
-"""The launch decision of the batched attention, asked of the engine's own functions (csrc/attend_geometry.hpp through the wrappers of
-tests/csrc/host_rules_test.cpp): decide() walks them in the order Engine::attend_batch / attend_batch_plan + attend_planned do."""
+"""The launch decision of the attention entries, asked of the engine's own functions (csrc/attend_geometry.hpp through the wrappers of
+tests/csrc/host_rules_test.cpp): decide() walks them in the order Engine::attend_batch / attend_batch_plan + attend_planned do, decide_seq() asks what
+the single-sequence entries (qk_scores_fp8, attend_fp8 / _int4 / _mx4) ask."""
 import ctypes as C
 import os
 import subprocess
@@ -34,6 +35,12 @@ def load_rules():
     lib.rules_int4_wg8_stream.argtypes = [C.c_uint32] * 4 + [C.c_int32] * 2 + [P]
     lib.rules_mx4_stream.restype = None
     lib.rules_mx4_stream.argtypes = [C.c_uint32] * 6 + [C.c_int32] * 2 + [P]
+    lib.rules_striped_tiles.restype = C.c_uint32
+    lib.rules_striped_tiles.argtypes = [C.c_uint32] * 2
+    lib.rules_int4_wg8_splits.restype = C.c_uint32
+    lib.rules_int4_wg8_splits.argtypes = [C.c_uint32] * 3
+    lib.rules_seq_decide.restype = C.c_uint64
+    lib.rules_seq_decide.argtypes = [P, I, P]
     return lib
 
 
@@ -42,7 +49,7 @@ def _p(a):
 
 
 def striped_tiles(pages, stripe_n):
-    """kernels.hpp mx4_striped_tiles: the tiles of a member counted by residue class of the page index"""
+    """ring_rule.hpp mx4_striped_tiles (rules_striped_tiles is the engine's own): the tiles of a member counted by residue class of the page index"""
     n = np.maximum(np.asarray(stripe_n, np.int64), 1)
     pages = np.asarray(pages, np.int64)
     return np.where(pages > 0, n * (((pages + n - 1) // n + 15) // 16), 0)
@@ -93,8 +100,44 @@ def int4_stream(lib, n_layers, n_tiles, n_cus, cls=False, attend_splits=0, atten
     return _stream(out)
 
 
-def mx4_stream(lib, n_layers, n_pages, n_cus, g=8, fixed_splits=2, attend_splits=0, attend_stream=0):
-    """The same of Engine::attend_mx4 for records in one run; fixed_splits = the splits its fixed grid would take."""
+def mx4_stream(lib, n_layers, n_pages, n_cus, g=8, fixed_splits=None, attend_splits=0, attend_stream=0):
+    """The same of Engine::attend_mx4 for records in one run.  fixed_splits = the splits its fixed grid would take: None = what the entry's own decision
+    gives (decide_seq; its stream must then be this one), a number = the rule alone under that count."""
+    d = None
+    if fixed_splits is None:
+        d = decide_seq(lib, MX4, n_layers, n_pages, n_cus, g=g, tuning=dict(attend_splits=attend_splits, attend_stream=attend_stream))
+        fixed_splits = d["n_splits"]
     out = np.zeros(5, np.uint32)
     lib.rules_mx4_stream(n_layers, (n_pages + 15) // 16, n_pages, n_cus, (g + 7) // 8, fixed_splits, attend_splits, attend_stream, _p(out))
+    assert d is None or d["stream"] == _stream(out), "Engine::attend_mx4's decision disagrees with mx4_stream"
     return _stream(out)
+
+
+# ---- ONE sequence: the launch decision of Engine::qk_scores_fp8 / attend_fp8 / attend_int4 / attend_mx4 (attend_geometry.hpp seq_decide)
+SEQ_TUNING_KEYS = ("attend_general", "attend_splits", "attend_stream", "attend_fp8_table_regs", "attend_fp8_striped_table", "attend_int4_striped_wg", "attend_fp8_dma")
+SEQ_PLACES = ("none", "linear", "striped", "table")
+FP8_KERNELS = ("-", "dma<2>", "linear<CLS>", "dma<1>", "dma<0>", "linear<false>", "linear<true>", "linear<false, true>", "k_attend_fp8")
+SEQ_FIELDS = ("place", "cls", "wg8", "n_tiles", "n_splits", "tiles_per_split", "stream_len", "stream_rem", "stream_n_wgs", "stream_max_slots", "stream_tiles",
+              "slots", "direct_out", "rows_final", "zero_page", "quantize_q", "fp8_kernel")
+
+
+def decide_seq(lib, scheme, n_layers, n_pages, n_cus, g=8, heads=8, num_tokens=None, pos_begin=0, skip_pages=0, has_tab=True, one_run=True, stripe_n=None,
+               scores=False, tuning=None):
+    """What the single-sequence entry of `scheme` (scores: qk_scores_fp8) decides for n_pages pages from pos_begin on -- the range AS ATTENDED: FP8 over a
+    scale table starts at the table's tile, skip_pages masked pages in front of the caller's begin.  num_tokens: the layout's positions per layer (None: the
+    range's tiles, whole); the allocation has a scale table / its records in one run / stripe_n runs (None: 1 with one_run, else 0 = no regular
+    placement).  tuning: a dict of tuning keys, or their 7 values in the order of SEQ_TUNING_KEYS.  Returns the SeqDecision fields (SEQ_FIELDS, place and
+    fp8_kernel as numbers: SEQ_PLACES, FP8_KERNELS), "parts", and "stream" as int4_stream / mx4_stream return it."""
+    if num_tokens is None:
+        num_tokens = pos_begin + (n_pages + 15) // 16 * 32
+    if stripe_n is None:
+        stripe_n = 1 if one_run else 0
+    tun = [int(tuning.get(k, 0)) for k in SEQ_TUNING_KEYS] if isinstance(tuning, dict) else list(tuning or [0] * 7)
+    assert len(tun) == 7 and (not isinstance(tuning, dict) or set(tuning) <= set(SEQ_TUNING_KEYS))
+    shape = np.array([scheme == FP8, scheme == MX4, scores, n_layers, heads, g, n_cus, num_tokens, pos_begin, n_pages, skip_pages, has_tab, one_run, stripe_n], np.uint32)
+    out = np.zeros(17, np.uint32)
+    parts = lib.rules_seq_decide(_p(shape), np.array(tun, np.int32).ctypes.data_as(I), _p(out))
+    d = dict(zip(SEQ_FIELDS, (int(v) for v in out)))
+    d["parts"] = int(parts)
+    d["stream"] = _stream([d["stream_n_wgs"], d["stream_len"], d["stream_rem"], d["stream_max_slots"], d["stream_tiles"]])
+    return d

@@ -1,6 +1,6 @@
 // tests/csrc/host_rules_test.cpp -- TEST-ONLY C wrappers around the header-only host/device rules of the engine
-// (ring_rule.hpp: ring run / liveness arithmetic, even splits, the stream partition; attend_geometry.hpp: the launch decision of the batched attention and the
-// stream decision of the single-sequence INT4_G32 / MXFP4 attention), for the CPU property tests.
+// (ring_rule.hpp: ring run / liveness arithmetic, even splits, the stream partition; attend_geometry.hpp: the launch decision of the batched attention and of
+// the single-sequence entries, the stream decision of the INT4_G32 / MXFP4 attention among them), for the CPU property tests.
 #include "../../cxl-speckv_amd/csrc/attend_geometry.hpp"
 
 extern "C" {
@@ -90,5 +90,22 @@ void rules_mx4_stream(uint32_t n_layers, uint32_t n_tiles, uint32_t n_pages, uin
                       int32_t attend_stream, uint32_t* out5)
 {
     stream_out(speckv::mx4_stream(n_layers, n_tiles, n_pages, cus, zgroups, fixed_splits, attend_splits, attend_stream), out5);
+}
+uint32_t rules_striped_tiles(uint32_t n_pages, uint32_t stripe_n) { return speckv::mx4_striped_tiles(n_pages, stripe_n); }
+uint32_t rules_int4_wg8_splits(uint32_t n_layers, uint32_t n_tiles, uint32_t cus) { return speckv::int4_wg8_splits(n_layers, n_tiles, cus); }
+
+// ---- attend_geometry.hpp: what Engine::qk_scores_fp8 / attend_fp8 / attend_int4 / attend_mx4 decide with (tests/_rules.py decide_seq)
+// shape14 = {fp8, mx4, scores, n_layers, heads, g, cus, num_tokens, pos_begin, n_pages, skip_pages, has_tab, one_run, stripe_n}; tun7 = {attend_general,
+// attend_splits, attend_stream, attend_fp8_table_regs, attend_fp8_striped_table, attend_int4_striped_wg, attend_fp8_dma}
+// out17 = {place, cls, wg8, n_tiles, n_splits, tiles_per_split, stream len, rem, n_wgs, max_slots, tiles, slots, direct_out, rows_final, zero_page,
+// quantize_q, kernel}; returns the partials
+uint64_t rules_seq_decide(const uint32_t* s, const int32_t* t, uint32_t* out17)
+{
+    const speckv::SeqShape shape{s[0] != 0u, s[1] != 0u, s[2] != 0u, s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11] != 0u, s[12] != 0u, s[13]};
+    const speckv::SeqDecision d = speckv::seq_decide(shape, speckv::SeqTuning{t[0], t[1], t[2], t[3], t[4], t[5], t[6]});
+    const uint32_t out[17] = {d.place, d.cls, d.wg8, d.n_tiles, d.n_splits, d.tiles_per_split, d.stream.len, d.stream.rem, d.stream.n_wgs, d.stream.max_slots,
+                              d.stream.tiles, d.slots, d.direct_out, d.rows_final, d.zero_page, d.quantize_q, d.kernel};
+    std::copy(out, out + 17, out17);
+    return d.parts;
 }
 }

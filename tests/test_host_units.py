@@ -528,7 +528,7 @@ def test_int4_batch_unequal_split_rule(rules):
 
 
 def test_mx4_class_enumeration_covers_every_page_once_and_stays_inside_the_planners_bound():
-    """k_attend_mx4's striped form takes the pages of a range by residue class (kernels.hpp: mx4_class_tiles, mx4_striped_tiles):
+    """k_attend_mx4's striped form takes the pages of a range by residue class (ring_rule.hpp: mx4_class_tiles, mx4_striped_tiles):
     class c = pages j with j % n == c, in tiles of 16, every class with the tile count of the largest.  Restated here: every page
     of the range appears in exactly one (class, tile, row), rows past a class's end are the masked ones, and the tile count stays
     under the bound the planner sizes its splits with (attend_geometry.hpp: plan_tiles_bound, ceil(pages / 16) + runs + 1)."""
@@ -589,3 +589,92 @@ def test_batch_attention_decision_replays_the_recorded_table(golden_dir):
             assert d["pieces"][:, :2].ravel().tolist() == row["pieces"], r[:11]
         base = np.concatenate(([0], np.cumsum(d["pieces"][:-1, 1].astype(np.int64) * row["heads"])))
         assert np.array_equal(d["pieces"][:, 2], base), r[:11]     # part_base: heads x pieces partials per member, in member order
+
+
+def test_single_sequence_attention_decision_replays_the_recorded_table(golden_dir):
+    """tests/golden/attend_seq_geometry.json holds, for some 900 calls (format or the scores entry, layers, query rows, CUs, range, placement, tuning
+    keys), what qk_scores_fp8, attend_fp8, attend_int4 and attend_mx4 decided inline -- and which kernel launch_attend_fp8 then picked from the
+    arguments -- BEFORE the decision moved into attend_geometry.hpp: recorded from a copy of that code with the allocation, the layout and the tuning
+    keys as values.  seq_decide must give the same in every field."""
+    from tests._rules import FP8, INT4, MX4, SEQ_TUNING_KEYS, decide_seq, load_rules
+    lib = load_rules()
+    g = json.load(open(os.path.join(golden_dir, "attend_seq_geometry.json")))
+    cols, schemes = g["columns"], {"fp8": FP8, "int4": INT4, "mx4": MX4, "scores": FP8}
+    assert len(g["rows"]) >= 900 and g["tunings"]["keys"] == list(SEQ_TUNING_KEYS)
+    seen = set()
+    for r in g["rows"]:
+        row = dict(zip(cols, r))
+        fmt = g["formats"][row["format"]]
+        rng = dict(zip(g["ranges"]["keys"], g["ranges"]["values"][row["range"]]))
+        one_run, stripe_n = g["placements"]["values"][row["placement"]]
+        d = decide_seq(lib, schemes[fmt], row["n_layers"], rng["n_pages"], row["cus"], g=row["g"], heads=g["heads"], num_tokens=rng["num_tokens"],
+                       pos_begin=rng["pos_begin"], skip_pages=rng["skip_pages"], has_tab=bool(rng["has_tab"]), one_run=bool(one_run), stripe_n=stripe_n,
+                       scores=fmt == "scores", tuning=g["tunings"]["values"][row["tuning"]])
+        got = {k: d[k] for k in cols[7:]}
+        assert got == {k: row[k] for k in got}, (r[:7], {k: (v, row[k]) for k, v in got.items() if v != row[k]})
+        seen.add((fmt, row["place"], row["cls"], row["wg8"], row["fp8_kernel"], bool(row["stream_n_wgs"]), row["rows_final"]))
+    # (the table reaches every kernel of launch_attend_fp8, every placement of every format, the stream form of both formats that have one)
+    assert {s[4] for s in seen if s[0] == "fp8"} == set(range(1, 9))
+    assert {(s[0], s[1]) for s in seen} >= {(f, p) for f in ("fp8", "int4", "mx4") for p in (1, 2, 3)} | {("fp8", 0), ("scores", 0), ("scores", 1)}
+    assert {s[0] for s in seen if s[5]} == {"int4", "mx4"}
+
+
+def test_single_sequence_attention_decision_properties():
+    """seq_decide over a wide sweep of the axes the recorded table samples: the splits cover the tiles with none empty, one placement form and one that
+    the allocation offers, the class forms over 2..8 runs only, the stream form only where int4_wg8_stream / mx4_stream give it, final rows exactly with
+    one split, no stream and not the FP8 per-wave kernel, and the partials the scratch is sized for."""
+    from tests._rules import FP8, INT4, MX4, P, decide_seq, int4_stream, load_rules, _stream
+    lib = load_rules()
+    rs = np.random.RandomState(20)
+    pages = [1, 15, 16, 17, 64, 100, 128, 1000, 1024, 4096, 8200, 14336, 16384, 65536]
+    tunings = [{}, {}, {}, dict(attend_general=1), dict(attend_splits=1), dict(attend_splits=2), dict(attend_splits=4096), dict(attend_stream=-1),
+               dict(attend_stream=3), dict(attend_stream=7), dict(attend_fp8_table_regs=1), dict(attend_fp8_striped_table=1), dict(attend_fp8_striped_table=-1),
+               dict(attend_int4_striped_wg=1), dict(attend_fp8_dma=-1), dict(attend_fp8_dma=1), dict(attend_splits=3, attend_stream=3)]
+    n = 0
+    for _ in range(30000):
+        scheme = (FP8, INT4, MX4)[rs.randint(3)]
+        n_layers, g, cus = (1, 2, 8, 32, 80)[rs.randint(5)], (1, 8, 9, 16)[rs.randint(4)], (64, 256, 304)[rs.randint(3)]
+        one_run, stripe_n = ((1, 1), (0, 2), (0, 7), (0, 8), (0, 9), (0, 0))[rs.randint(6)]
+        n_pages, tun = pages[rs.randint(len(pages))], tunings[rs.randint(len(tunings))]
+        begin = (0, 0, 32, 74)[rs.randint(4)]
+        skip, has_tab = 0, True
+        if scheme == FP8:                                            # (attend_begin: aligned to the scale table where there is one)
+            has_tab = rs.randint(8) != 0
+            if has_tab:
+                skip, begin = (begin % 32) // 2, begin - begin % 32
+        n_tiles = (n_pages + skip + 15) // 16
+        num_tokens = begin + n_tiles * 32 - (0, 0, 0, 6)[rs.randint(4)]      # (one in four: the last tile would leave the region)
+        d = decide_seq(lib, scheme, n_layers, n_pages + skip, cus, g=g, num_tokens=num_tokens, pos_begin=begin, skip_pages=skip, has_tab=has_tab,
+                       one_run=bool(one_run), stripe_n=stripe_n, tuning=tun)
+        key = (scheme, n_layers, g, cus, one_run, stripe_n, n_pages, skip, begin, num_tokens, has_tab, tun)
+        n += 1
+        # the splits cover the tiles, none empty, 2048 at most (a forced attend_splits is clamped there too)
+        assert d["n_splits"] * d["tiles_per_split"] >= d["n_tiles"] > (d["n_splits"] - 1) * d["tiles_per_split"] and 1 <= d["n_splits"] <= 2048, (key, d)
+        # one placement form, and one the allocation offers; the per-wave page-table kernel is FP8's and takes its query from the quantise launch
+        assert d["place"] in (0, 1, 2, 3) and (d["place"] != 1 or one_run) and (d["place"] != 2 or (not one_run and stripe_n >= 2)), (key, d)
+        assert (d["place"] == 0) == bool(d["quantize_q"]) == (d["fp8_kernel"] == 8) and (d["place"] != 0 or scheme == FP8), (key, d)
+        assert d["place"] != 3 or d["zero_page"], (key, d)
+        # the class forms: striped over 2..8 runs, their tiles counted by class
+        assert not d["cls"] or (d["place"] == 2 and 2 <= stripe_n <= 8), (key, d)
+        assert d["n_tiles"] == (lib.rules_striped_tiles(n_pages + skip, stripe_n) if d["cls"] else n_tiles), (key, d)
+        assert not d["wg8"] or (scheme == INT4 and (d["place"] == 1 or d["cls"])), (key, d)
+        # the kernel goes with the placement
+        k = d["fp8_kernel"]
+        assert (k != 0) == (scheme == FP8) and ((k in (1, 2)) == bool(d["cls"]) or scheme != FP8), (key, d)
+        assert k in {0: (8,), 1: (4, 5), 2: (1, 2, 3, 6), 3: (3, 7)}[d["place"]] or scheme != FP8, (key, d)
+        # the stream form: only where the two stream decisions give it
+        tv = (tun.get("attend_splits", 0), tun.get("attend_stream", 0))
+        if scheme == INT4 and d["wg8"]:
+            want = int4_stream(lib, n_layers, d["n_tiles"], cus, bool(d["cls"]), *tv)
+        elif scheme == MX4 and d["place"] == 1:
+            out = np.zeros(5, np.uint32)
+            lib.rules_mx4_stream(n_layers, d["n_tiles"], n_pages, cus, (g + 7) // 8, d["n_splits"], tv[0], tv[1], out.ctypes.data_as(P))
+            want = _stream(out)
+        else:
+            want = None
+        assert d["stream"] == want, (key, d)
+        # partials per row, final rows, the scratch
+        assert d["slots"] == (d["stream"]["max_slots"] if d["stream"] else d["n_splits"]) and d["parts"] == n_layers * 8 * d["slots"], (key, d)
+        assert bool(d["rows_final"]) == (d["n_splits"] == 1 and not d["stream"] and k != 8), (key, d)
+        assert bool(d["direct_out"]) == (d["slots"] == 1 and not d["stream"]), (key, d)
+    assert n == 30000

@@ -8,7 +8,7 @@ All through the wrappers of tests/csrc/host_rules_test.cpp (tests/_rules.py)."""
 import numpy as np
 import pytest
 
-from tests._rules import int4_stream, load_rules, mx4_stream
+from tests._rules import MX4, decide_seq, int4_stream, load_rules, mx4_stream
 
 
 @pytest.fixture(scope="module")
@@ -107,14 +107,20 @@ def test_stream_decisions_at_the_full_size_shapes_are_the_inline_rules(rules):
     assert int4_stream(rules, 8, 1024, cus)["len"] == 16
     assert int4_stream(rules, 80, 1024, 304) == dict(n_wgs=608, len=134, rem=448, max_slots=_max_slots(80, 1024, 608), tiles=0)
     # MXFP4, 80 layers x 32k, g = 8: 256 pieces of 320 (the fixed grid: 256 / 80 = 3 splits a layer)
-    assert mx4_stream(rules, 80, 16384, cus, g=8, fixed_splits=3) == dict(n_wgs=256, len=320, rem=0, max_slots=_max_slots(80, 1024, 256), tiles=0)
+    assert mx4_stream(rules, 80, 16384, cus, g=8) == dict(n_wgs=256, len=320, rem=0, max_slots=_max_slots(80, 1024, 256), tiles=0)
+    # g = 16, two row groups: 128 pieces -- the rule alone under three splits; the entry's fixed grid has 256 / 160 = 1 split at 80 layers, whole layers, and
+    # does not stream; 40 layers (80 columns, three splits) do
     assert mx4_stream(rules, 80, 16384, cus, g=16, fixed_splits=3) == dict(n_wgs=128, len=640, rem=0, max_slots=_max_slots(80, 1024, 128), tiles=0)
-    assert mx4_stream(rules, 80, 895 * 16, cus, fixed_splits=3) is None
-    assert mx4_stream(rules, 1, 16384, cus, fixed_splits=3) is None
-    assert mx4_stream(rules, 80, 16384, cus, fixed_splits=1) is None      # whole layers are final rows: no partials, no merge
-    assert mx4_stream(rules, 80, 16384 - 15, cus, fixed_splits=3) is None  # a ragged last tile
-    assert mx4_stream(rules, 2, 1024 * 16, cus, fixed_splits=3) is None    # 2048 tiles < 16 x 256
-    assert mx4_stream(rules, 4, 1024 * 16, cus, fixed_splits=3) == dict(n_wgs=256, len=16, rem=0, max_slots=_max_slots(4, 1024, 256), tiles=0)
+    assert decide_seq(rules, MX4, 80, 16384, cus, g=16)["n_splits"] == 1 and mx4_stream(rules, 80, 16384, cus, g=16) is None
+    assert mx4_stream(rules, 40, 16384, cus, g=16) == dict(n_wgs=128, len=320, rem=0, max_slots=_max_slots(40, 1024, 128), tiles=0)
+    assert mx4_stream(rules, 80, 895 * 16, cus) is None
+    assert mx4_stream(rules, 1, 16384, cus) is None
+    assert decide_seq(rules, MX4, 80, 16384, cus)["n_splits"] == 3         # (the fixed-grid split count: Engine::attend_mx4's own, asked by mx4_stream)
+    assert mx4_stream(rules, 80, 16384, cus, fixed_splits=1) is None      # whole layers are final rows: no partials, no merge (the rule alone) ...
+    assert decide_seq(rules, MX4, 80, 16384, 128)["n_splits"] == 1 and mx4_stream(rules, 80, 16384, 128) is None      # ... and where the entry gets there: 128 CUs
+    assert mx4_stream(rules, 80, 16384 - 15, cus) is None  # a ragged last tile
+    assert mx4_stream(rules, 2, 1024 * 16, cus) is None    # 2048 tiles < 16 x 256
+    assert mx4_stream(rules, 4, 1024 * 16, cus) == dict(n_wgs=256, len=16, rem=0, max_slots=_max_slots(4, 1024, 256), tiles=0)
 
 
 def test_stream_tuning_keys(rules):
@@ -135,8 +141,8 @@ def test_stream_tuning_keys(rules):
         assert mx4_stream(rules, n_layers, n_tiles * 16 - 1, 256, attend_stream=2) is None          # MXFP4: whole tiles only, also on request
     assert int4_stream(rules, 1, 16, 256, attend_stream=4) is None and mx4_stream(rules, 1, 256, 256, attend_stream=4) is None
     # never, and a forced split count, at the sizes that stream by themselves
-    assert int4_stream(rules, 80, 1024, 256, attend_stream=-1) is None and mx4_stream(rules, 80, 16384, 256, fixed_splits=3, attend_stream=-1) is None
-    assert int4_stream(rules, 80, 1024, 256, attend_splits=8) is None and mx4_stream(rules, 80, 16384, 256, fixed_splits=3, attend_splits=8) is None
+    assert int4_stream(rules, 80, 1024, 256, attend_stream=-1) is None and mx4_stream(rules, 80, 16384, 256, attend_stream=-1) is None
+    assert int4_stream(rules, 80, 1024, 256, attend_splits=8) is None and mx4_stream(rules, 80, 16384, 256, attend_splits=8) is None
     # the merge takes 2048 partials a row: 2 layers x 4096 tiles in one-tile pieces would be 4096
     assert int4_stream(rules, 2, 4096, 256, attend_stream=8192) is None
     assert int4_stream(rules, 2, 4096, 256, attend_stream=4096)["max_slots"] == 2048
