@@ -282,10 +282,27 @@ class HeadChecker:
             lse[idx] = (mx + np.log(l)).reshape(m, G)
         return out, lse, mag, delta
 
-    def check_rows(self, got, got_lse, q16, head, npos, sm, what, tail=None, pos_begin=0, worst=None):
+    def weight_rows(self, q16, head, n, sm, pos_begin=0, v_from=None):
+        """What a model of the kernels' weight rounding needs (tests/_value_ranges.py), from the dequantisation want_rows uses: q16 [R][D] fp16 over
+        the positions [pos_begin, pos_begin + n) -> (p [R][n]: the float64 weights exp(s - max s) against the row's final maximum, l [R] their sums,
+        mx [R] the maxima (natural log domain), V [n][D] float64, vs [n]: the V page scale of every position -- FP8 only, ones elsewhere).
+        v_from: the checker whose V rows (and V format) are attended instead of this one's -- the split pool, K here and V there."""
+        K = self.kv(head)[0][pos_begin:pos_begin + n]
+        vc = self if v_from is None else v_from
+        V = vc.kv(head)[1][pos_begin:pos_begin + n]
+        s = (self.q_rows(q16) @ K.T) * sm
+        mx = s.max(axis=1)
+        p = np.exp(s - mx[:, None])
+        hp = vc.T // 2
+        fp8_v = getattr(vc, "v_scheme", vc.scheme) == 4
+        vs = np.repeat(vc.scales[hp:2 * hp].astype(np.float64), 2)[pos_begin:pos_begin + n] if fp8_v else np.ones(n)
+        return p, p.sum(axis=1), mx, V, vs
+
+    def check_rows(self, got, got_lse, q16, head, npos, sm, what, tail=None, pos_begin=0, worst=None, extra_tol=None):
         """every row of M members' head `head` against want_rows, with check()'s bound: |err| <= (2e-3 + 2 delta) sum p|v| + 1e-6,
         |lse err| <= 2e-3 + delta; a member with no position (and no tail) exactly 0.  got_lse None: a call without a log-sum-exp, out only.
-        worst: a list that receives the largest err / tol of out and of lse (0.0 where nothing was compared) BEFORE anything is asserted."""
+        worst: a list that receives the largest err / tol of out and of lse (0.0 where nothing was compared) BEFORE anything is asserted.
+        extra_tol [M][G][D]: added to the bound of out (None: nothing) -- what a declared rounding of the format costs, worked out by the caller."""
         want, wlse, mag, delta = self.want_rows(q16, head, npos, sm, tail, pos_begin)
         got = np.asarray(got, np.float64)
         npos = np.asarray(npos)
@@ -294,6 +311,8 @@ class HeadChecker:
         live = ~empty
         err = np.abs(got[live] - want[live])
         tol = (2e-3 + 2 * delta[live])[:, None, None] * mag[live] + 1e-6
+        if extra_tol is not None:
+            tol = tol + np.asarray(extra_tol, np.float64)[live]
         if worst is not None:
             lerr = np.abs(np.asarray(got_lse, np.float64)[live] - wlse[live]) / (2e-3 + delta[live])[:, None] if got_lse is not None else np.zeros(0)
             with np.errstate(invalid="ignore"):

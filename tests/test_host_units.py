@@ -678,3 +678,22 @@ def test_single_sequence_attention_decision_properties():
         assert bool(d["rows_final"]) == (d["n_splits"] == 1 and not d["stream"] and k != 8), (key, d)
         assert bool(d["direct_out"]) == (d["slots"] == 1 and not d["stream"]), (key, d)
     assert n == 30000
+
+
+# ---- tests/_value_ranges.py model_rows: with the fp16 rounding of the weights switched off it IS HeadChecker.want_rows
+@pytest.mark.parametrize("name", ["v-page-ladder", "sink-tile-249", "ramp-up", "ties-v0-tile", "queries"])
+def test_value_range_model_without_rounding_equals_want_rows(oracle, name):
+    from tests import _value_ranges as vr
+    ds = vr.dataset(name)
+    for fmt in (vr.FP8, vr.INT4, vr.MX4, vr.K8V4):
+        hc = vr.checker(oracle, name, 256, fmt)
+        for head in (0, 5):
+            q = np.stack([ds["q"][1, head], ds["q"][0, head], ds["q"][1, head]])
+            npos = [256, 250, 64]
+            want, wlse, _, _ = hc.want_rows(q, head, npos, ds["sm"])
+            for fp8_ref in (None, True, False):                     # (the unit of the weights cancels without the rounding)
+                got, lse = vr.model_rows(hc, q, head, npos, ds["sm"], fp8_ref=fp8_ref, rounding=False)
+                assert np.allclose(got, want, rtol=1e-11, atol=1e-13 * np.abs(want).max()), (name, fmt, head, fp8_ref, float(np.abs(got - want).max()))
+                assert np.allclose(lse, wlse, rtol=0, atol=1e-11)
+            rounded = vr.model_rows(hc, q, head, npos, ds["sm"])[0]
+            assert np.any(rounded != want)                          # ... and with it, it is not
