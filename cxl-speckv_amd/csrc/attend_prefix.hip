@@ -40,6 +40,12 @@
 // SPLIT: the pieces cut the tiles that are left, piece p walks from first_tile + p tpp; a piece wholly below a row's lo or beyond
 // its prefix_len writes m = -inf, l = 0, zeros, and the merge gives the unsplit weights (prefix_combine).  Every live row sees
 // position lo, so its sum is never 0 and b stays finite.  The instances without WINDOW are the code above, untouched.
+//
+// Split pool (KS != VS, PrefixArgs::v_scheme; speckv_ext_attend_prefix_fold_kv: FP8 keys, MXFP4 values).  As in the chunk kernel: the
+// scheme of the K side (load_pool, decode_pool<.., true>, pool_k_scale, k_scale) and of the V side (load_pool, decode_pool) are two
+// template parameters, and the V pages are addressed through the table of an allocation of their own (PrefixGroup::v_table_row).  With
+// KS == VS the V table IS the K table and the instances are the ones of one scheme, instruction for instruction.  (FP8, MXFP4) is the
+// one mixed pair instantiated: four instances, SPLIT x WINDOW; the merge kernels read partials only and serve it as they are.
 #include "chunk_device.hpp"
 #include "prefix_window.hpp"
 
@@ -92,7 +98,7 @@ __device__ __forceinline__ FoldW fold_weights(float own, float b)
     return FoldW{__builtin_amdgcn_exp2f(a - n), __builtin_amdgcn_exp2f(b - n), n * kLn2};
 }
 
-template <int SCHEME, bool SPLIT, bool WINDOW>
+template <int KS, int VS, bool SPLIT, bool WINDOW>
 __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
 {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufElems];
@@ -126,6 +132,8 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
     if (t_begin >= t_end) return;                             // (never: no piece of the plan is empty)
 
     const PageEntry* entries = reinterpret_cast<const PageEntry*>(ck_uniform(reinterpret_cast<uint64_t>(a.tab[gp->table_row].entries)));
+    // the V pages' table: the same allocation's unless the schemes differ (the split pool: K and V in an allocation each)
+    const PageEntry* v_entries = KS == VS ? entries : reinterpret_cast<const PageEntry*>(ck_uniform(reinterpret_cast<uint64_t>(a.tab[gp->v_table_row].entries)));
     const uint64_t k_first = ck_uniform(gp->k_first), v_first = ck_uniform(gp->v_first);
 
     // staging role: page pp of the tile, elements [8 c, 8 c + 8) of head h of both its positions
@@ -144,14 +152,14 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
     const auto load_tile = [&](uint32_t tile) {
         const uint32_t page = 16u * tile + pp;
         const bool live = page < n_pages;
-        rk = load_pool<SCHEME>(entries + k_first + page, p0, live);
-        rv = load_pool<SCHEME>(entries + v_first + page, p0, live);
+        rk = load_pool<KS>(entries + k_first + page, p0, live);
+        rv = load_pool<VS>(v_entries + v_first + page, p0, live);
     };
     const auto store_tile = [&](_Float16* buf) {
         uint32_t ke[4], ko[4], ve[4], vo[4];
-        if (SCHEME == kFp8E4m3 && c == 0u) k_scale[buf != lds][pp] = pool_k_scale<SCHEME>(rk);
-        decode_pool<SCHEME, true>(rk, p0, ke, ko);
-        decode_pool<SCHEME>(rv, p0, ve, vo);
+        if (KS == kFp8E4m3 && c == 0u) k_scale[buf != lds][pp] = pool_k_scale<KS>(rk);
+        decode_pool<KS, true>(rk, p0, ke, ko);
+        decode_pool<VS>(rv, p0, ve, vo);
         *reinterpret_cast<u32x4*>(buf + (2u * pp) * kKRow + 8u * c) = u32x4{ke[0], ke[1], ke[2], ke[3]};
         *reinterpret_cast<u32x4*>(buf + (2u * pp + 1u) * kKRow + 8u * c) = u32x4{ko[0], ko[1], ko[2], ko[3]};
         uint32_t* vt = reinterpret_cast<uint32_t*>(buf + kKTile);            // word (dim, page) = the dim's values at the page's two positions
@@ -195,7 +203,7 @@ __global__ __launch_bounds__(kChunkThreads) void k_attend_prefix(PrefixArgs a)
 #pragma unroll
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t t = t_base + 16u * (i >> 2) + 4u * g + (i & 3u);
-                const float scale_i = SCHEME == kFp8E4m3 ? scale2 * ks[8u * (i >> 2) + 2u * g + ((i & 3u) >> 1)] : scale2;       // the position's page
+                const float scale_i = KS == kFp8E4m3 ? scale2 * ks[8u * (i >> 2) + 2u * g + ((i & 3u) >> 1)] : scale2;       // the position's page
                 sv[i] = t < row.len && (!WINDOW || t >= row.lo) ? sc[i >> 2][i & 3u] * scale_i : -__builtin_inff();   // the row's own range
                 mx = fmaxf(mx, sv[i]);
             }
@@ -302,14 +310,14 @@ __device__ __forceinline__ void prefix_combine(const PrefixArgs& a)
 __global__ __launch_bounds__(kChunkThreads) void k_prefix_combine(PrefixArgs a) { prefix_combine<false>(a); }
 __global__ __launch_bounds__(kChunkThreads) void k_prefix_combine_window(PrefixArgs a) { prefix_combine<true>(a); }
 
-template <int SCHEME, bool WINDOW>
+template <int KS, int VS, bool WINDOW>
 hipError_t launch_prefix(const PrefixArgs& a, hipStream_t s)
 {
     if (!a.part) {
-        hipLaunchKernelGGL((k_attend_prefix<SCHEME, false, WINDOW>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
+        hipLaunchKernelGGL((k_attend_prefix<KS, VS, false, WINDOW>), dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((k_attend_prefix<SCHEME, true, WINDOW>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
+    hipLaunchKernelGGL((k_attend_prefix<KS, VS, true, WINDOW>), dim3(a.n_items * a.heads), dim3(kChunkThreads), 0, s, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(WINDOW ? k_prefix_combine_window : k_prefix_combine, dim3(a.n_blocks * a.heads), dim3(kChunkThreads), 0, s, a);
@@ -326,18 +334,23 @@ hipError_t launch_attend_prefix(const PrefixArgs& a, hipStream_t s)
         static_cast<uint64_t>(a.n_blocks) * a.heads > 0x7FFFFFFFull ||
         (a.part && (a.n_items < a.n_blocks || static_cast<uint64_t>(a.n_items) * a.heads > 0x7FFFFFFFull || reinterpret_cast<uintptr_t>(a.part) % 16u)))
         return hipErrorInvalidValue;
+    // the one mixed pair: K pages of an FP8 allocation, V pages of an MXFP4 one (the K8V4 split pool; PrefixGroup::v_table_row)
+    if (a.v_scheme != a.scheme) {
+        if (a.scheme != kFp8E4m3 || a.v_scheme != kMxFp4) return hipErrorInvalidValue;
+        return a.window ? launch_prefix<kFp8E4m3, kMxFp4, true>(a, s) : launch_prefix<kFp8E4m3, kMxFp4, false>(a, s);
+    }
     if (a.window) {                                           // (own_seen and depth are judged by Engine::attend_prefix)
         switch (a.scheme) {
-        case kFp8E4m3: return launch_prefix<kFp8E4m3, true>(a, s);
-        case kInt4G32: return launch_prefix<kInt4G32, true>(a, s);
-        case kMxFp4: return launch_prefix<kMxFp4, true>(a, s);
+        case kFp8E4m3: return launch_prefix<kFp8E4m3, kFp8E4m3, true>(a, s);
+        case kInt4G32: return launch_prefix<kInt4G32, kInt4G32, true>(a, s);
+        case kMxFp4: return launch_prefix<kMxFp4, kMxFp4, true>(a, s);
         default: return hipErrorInvalidValue;
         }
     }
     switch (a.scheme) {
-    case kFp8E4m3: return launch_prefix<kFp8E4m3, false>(a, s);
-    case kInt4G32: return launch_prefix<kInt4G32, false>(a, s);
-    case kMxFp4: return launch_prefix<kMxFp4, false>(a, s);
+    case kFp8E4m3: return launch_prefix<kFp8E4m3, kFp8E4m3, false>(a, s);
+    case kInt4G32: return launch_prefix<kInt4G32, kInt4G32, false>(a, s);
+    case kMxFp4: return launch_prefix<kMxFp4, kMxFp4, false>(a, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -1022,6 +1022,22 @@ speckv_status_t speckv_ext_attend_prefix_fold_window(uint32_t n_groups, const sp
     return guarded([&] { return g_engine->attend_prefix(c, static_cast<hipStream_t>(stream)); });
 }
 
+// the split pool: the prefixes' K regions in the FP8 allocations k_handles, their V regions in the MXFP4 allocations v_handles; the
+// window entry's call otherwise (own_seen may be NULL iff window == 0: nothing reads it then)
+speckv_status_t speckv_ext_attend_prefix_fold_kv(uint32_t n_groups, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                                 const uint32_t* first_member, uint32_t layer, const void* d_q_f16, uint32_t C,
+                                                 uint32_t rows_per_pos, const uint32_t* prefix_len, const uint32_t* n_q, const uint32_t* own_seen,
+                                                 const uint32_t* d_depth, uint32_t window, uint32_t n_splits, float sm_scale, float* d_out,
+                                                 float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    speckv::Engine::PrefixCall c{n_groups, k_handles, first_member, layer, d_q_f16, C, rows_per_pos, prefix_len, n_q, n_splits,
+                                 sm_scale, d_out, d_lse};
+    c.split_kv = true; c.v_handles = v_handles;
+    c.windowed = window != 0u; c.own_seen = own_seen; c.d_depth = d_depth; c.window = window;
+    return guarded([&] { return g_engine->attend_prefix(c, static_cast<hipStream_t>(stream)); });
+}
+
 speckv_status_t speckv_ext_prefix_window_walk(uint32_t n_groups, const uint32_t* first_member, const uint32_t* prefix_len,
                                               const uint32_t* own_seen, const uint32_t* n_q, uint32_t window, uint32_t* out_first_tile,
                                               uint32_t* out_n_tiles)

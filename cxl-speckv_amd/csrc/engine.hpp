@@ -202,12 +202,14 @@ public:
         const uint64_t* v_handles = nullptr; bool split_kv = false;
     };
     int attend_chunk(const ChunkCall& c, hipStream_t s);
-    // One shared-prefix call (speckv_ext_attend_prefix_fold / _fold_window), described above Engine::attend_prefix (engine_prefix.cpp);
+    // One shared-prefix call (speckv_ext_attend_prefix_fold / _fold_window / _fold_kv), described above Engine::attend_prefix (engine_prefix.cpp);
     // windowed = the window entry's call: own_seen is required with members whatever the window, d_depth may be null
     struct PrefixCall {
         uint32_t n_groups; const uint64_t* handles; const uint32_t* first_member; uint32_t layer; const void* d_q_f16; uint32_t C, rows_per_pos;
         const uint32_t *prefix_len, *n_q; uint32_t n_splits; float sm_scale; float *d_out, *d_lse;
         bool windowed = false; const uint32_t* own_seen = nullptr; const uint32_t* d_depth = nullptr; uint32_t window = 0;
+        // speckv_ext_attend_prefix_fold_kv: `handles` are the prefixes' FP8 allocations (K regions), these their MXFP4 allocations (V regions)
+        const uint64_t* v_handles = nullptr; bool split_kv = false;
     };
     int attend_prefix(const PrefixCall& c, hipStream_t s);
     int read(uint64_t handle, uint64_t off, void* dst, size_t len, bool on_device);

@@ -21,10 +21,15 @@ namespace speckv {
 // -- issues exactly the launches above.  Otherwise the WINDOW instances: a group's walk and its live members are
 // prefix_window_group's, chunk_split_plan cuts the tiles that are LEFT from first_tile on, and own_seen travels in the same
 // descriptor slot behind n_q.
+// `split_kv` (speckv_ext_attend_prefix_fold_kv, the K8V4 split pool): handles[g] is the prefix's FP8_E4M3 allocation and v_handles[g] its
+// MXFP4 one, both laid out as regions of num_tokens / 2 pages and judged by the region rule of Engine::attend_chunk: K of the layer =
+// region `layer` of the first, V = region `layer` of the second.  The one mixed pair of schemes the kernel has instances of;
+// everything else -- plan, window rule, descriptor slot, ordering -- is the call of one allocation per group.
 int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
 {
-    const char* entry = c.windowed ? "speckv_ext_attend_prefix_fold_window" : "speckv_ext_attend_prefix_fold";
+    const char* entry = c.split_kv ? "speckv_ext_attend_prefix_fold_kv" : c.windowed ? "speckv_ext_attend_prefix_fold_window" : "speckv_ext_attend_prefix_fold";
     if (null_) return no_data_path(entry);
+    if (c.split_kv && (!c.handles || !c.v_handles)) return SPECKV_ERR_INVAL;
     if (!s || !c.d_q_f16 || !c.d_out || !c.d_lse) return SPECKV_ERR_INVAL;
     if (c.n_groups && (!c.handles || !c.first_member)) return SPECKV_ERR_INVAL;
     if (c.rows_per_pos == 0 || c.rows_per_pos > 16u || (c.rows_per_pos & (c.rows_per_pos - 1u)) || c.C == 0) return SPECKV_ERR_INVAL;
@@ -67,9 +72,26 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
         n_blocks += (pairs[g] + per_block - 1u) / per_block;
     }
     if (n_blocks * 8u > 0x7FFFFFFFull) return SPECKV_ERR_INVAL;
-    std::vector<Allocation*> as(c.n_groups);
+    std::vector<Allocation*> as(c.n_groups), vs(c.split_kv ? c.n_groups : 0u);
     int scheme = -1;
+    // a region (num_tokens / 2 pages) of an allocation of the split pool: 8 x 128 fp16, region `layer` inside its pages
+    const auto region_ok = [&](const Allocation* a, int want) {
+        if (!a->has_layout || a->scheme != want) return false;
+        const Layout& L = a->layout;
+        if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads != 8 || L.num_tokens % 2) return false;
+        return (static_cast<uint64_t>(c.layer) + 1u) * (L.num_tokens / 2u) <= a->n_pages && c.layer < 2ull * L.num_layers;
+    };
     const auto check = [&]() -> int {
+        for (uint32_t g = 0; c.split_kv && g < c.n_groups; ++g) {
+            Allocation *k = find(c.handles[g]), *v = find(c.v_handles[g]);
+            if (!k || !v) return SPECKV_ERR_GENERAL;
+            if (!region_ok(k, SPECKV_COMP_FP8_E4M3) || !region_ok(v, SPECKV_COMP_MXFP4) || k->layout.num_tokens != v->layout.num_tokens)
+                return SPECKV_ERR_INVAL;
+            for (uint32_t m = c.first_member[g]; m < c.first_member[g + 1]; ++m)
+                if (c.prefix_len[m] > k->layout.num_tokens) return SPECKV_ERR_INVAL;
+            as[g] = k; vs[g] = v;
+        }
+        if (c.split_kv) { scheme = SPECKV_COMP_FP8_E4M3; return SPECKV_OK; }
         for (uint32_t g = 0; g < c.n_groups; ++g) {
             Allocation* a = find(c.handles[g]);
             if (!a) return SPECKV_ERR_GENERAL;
@@ -128,10 +150,13 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
     uint32_t first_block = 0, first_item = 0;
     for (uint32_t g = 0; g < c.n_groups; ++g) {
         const Layout& L = as[g]->layout;
-        const uint64_t k_first = static_cast<uint64_t>(c.layer) * L.num_tokens;
+        // split pool: region `layer` of either allocation; otherwise the layer's K region and the V region behind it
+        const uint64_t k_first = static_cast<uint64_t>(c.layer) * (c.split_kv ? L.num_tokens / 2u : L.num_tokens);
+        const uint64_t v_first = c.split_kv ? k_first : k_first + L.num_tokens / 2u;
         const uint32_t blocks = (pairs[g] + per_block - 1u) / per_block;
-        static_cast<PrefixGroup*>(staged)[g] = PrefixGroup{as[g]->row, max_len[g], c.first_member[g], pairs[g], k_first, k_first + L.num_tokens / 2u,
-                                                           first_block, first_item, pieces[g], tpp[g], first_tile[g]};
+        static_cast<PrefixGroup*>(staged)[g] = PrefixGroup{as[g]->row, max_len[g], c.first_member[g], pairs[g], k_first, v_first,
+                                                           first_block, first_item, pieces[g], tpp[g], first_tile[g],
+                                                           c.split_kv ? vs[g]->row : as[g]->row};
         first_block += blocks;
         first_item += blocks * pieces[g];
     }
@@ -158,6 +183,7 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
     pa.heads = 8;
     pa.sm_scale = c.sm_scale;
     pa.scheme = scheme;
+    pa.v_scheme = c.split_kv ? SPECKV_COMP_MXFP4 : scheme;
     if (win) {
         pa.own_seen = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(d_slot) + group_bytes + 2u * member_bytes);
         pa.depth = c.d_depth;
@@ -165,6 +191,7 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
     }
     HIP_TRY(launch_attend_prefix(pa, s));
     for (uint32_t g = 0; g < c.n_groups; ++g) note_use(as[g], s);  // speckv_free of a prefix waits for this stream
+    for (Allocation* v : vs) note_use(v, s);                       // (of either allocation in the split pool)
     if (hipEventRecord(grp_ring_.ev[slot], s) != hipSuccess) {      // the staging slot must not be reused under the kernel
         (void)hipGetLastError();
         HIP_TRY(hipStreamSynchronize(s));

@@ -300,7 +300,10 @@ struct PrefixGroup {
     uint32_t first_tile;              // window form: the first tile any live row of the group sees (prefix_window.hpp; the walk and
                                       // the pieces start here); else 0.  (It makes the struct 56 bytes where it was 48: the stride
                                       // of the group search changed in every instance, the plain ones included.)
+    uint32_t v_table_row;             // the table row of the allocation whose pages v_first counts: table_row, but in the split pool
+                                      // (PrefixArgs::v_scheme != scheme).  It takes the word that padded 52 bytes of members to 56.
 };
+static_assert(sizeof(PrefixGroup) == 56, "the stride of the group search (prefix_group_of) is part of every instance");
 struct PrefixArgs {
     const PrefixGroup* groups;        // device array
     const uint32_t* prefix_len;       // device array [n_members]: even, the stored positions of its group's prefix the member sees
@@ -313,13 +316,16 @@ struct PrefixArgs {
     uint32_t        n_groups, n_blocks, n_items;
     uint32_t        C, rows_per_pos, heads;
     float           sm_scale;
-    int             scheme;           // kFp8E4m3, kInt4G32 or kMxFp4
+    int             scheme;           // kFp8E4m3, kInt4G32 or kMxFp4: the scheme of the K pages (and, but in the split pool, of the V pages)
     // window form (window 0: none; the engine vouches for own_seen and for depth's alignment): the row of member m and position j sees the
     // stored positions [lo, prefix_len[m]) only, lo = prefix_window_lo(prefix_len[m], own_seen[m], d, window) with d = depth[m * C + j]
     // or, where depth is null, j; a row with lo >= prefix_len[m] is dead like a pair beyond n_q[m]
     const uint32_t* own_seen;         // device array [n_members]
     const uint32_t* depth;            // device array [n_members][C], or null
     uint32_t        window;
+    // the scheme of the V pages (the launcher's alone: it picks the instance), as ChunkArgs::v_scheme: equal to `scheme` everywhere but
+    // in the K8V4 split pool, scheme == kFp8E4m3 and v_scheme == kMxFp4 -- the one mixed pair there are instances of; any other is refused.
+    int             v_scheme;
 };
 // part == null: ONE launch of n_blocks * heads workgroups that fold into out / lse.  Otherwise TWO: n_items * heads workgroups that
 // write their partials, then k_prefix_combine over n_blocks * heads, which merges a row's pieces in ascending order and folds.

@@ -18,12 +18,16 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
   attend_chunk                          one layer of a step of S >= 1 new positions per request -- a prefill chunk, a draft chain or tree --
                                         causal, under a window, a tree, a tree under a window, split over the chip (S = 1 works, but a
                                         64-row query block then carries rows_per_pos live rows: attend is the decode route)
+  attend_shared / attend_chunk_shared   attend / attend_chunk for members that SHARE A PREFIX without holding a copy of it: the own part as
+                                        those methods issue it with the log-sum-exp kept, then ONE speckv_ext_attend_prefix_fold_kv launch
+                                        that reads the prefix's FP8 keys and MXFP4 values once per 64 query rows and folds them in
   commit                                the accepted prefix of a step into the pool: one speckv_ext_write_pairs per allocation
 
 Not in this class: the planned and captured decode route (plan_step, HIP graphs: attend stages its descriptors
-per call), multi-position steps on the decode kernel (attend_spec), load_paged / store_paged, the
-shared-prefix fold, fork, truncate, begin_step and the K pre-scale."""
-from typing import Dict, Sequence
+per call), multi-position steps on the decode kernel (attend_spec), load_paged / store_paged, fork, truncate, begin_step and the
+K pre-scale; a shared prefix is one level deep and one layer per call."""
+import numbers
+from typing import Dict, Optional, Sequence
 
 from . import kv_connector as _kc
 from .kv_connector import SpeckvKVConnector, _is_int
@@ -63,6 +67,7 @@ class SpeckvSplitKVConnector:
         self._fold = (None,)                                  # attend: key, then what a step's calls share -- the count and device indices of the
                                                               # requests with an odd length, the handle arrays, the stored lengths,
                                                               # the query positions (attend under a window)
+        self._shared_key, self._shared_plan = None, None      # attend_shared / attend_chunk_shared: the judged call of a step (_shared_args)
 
     # ------------------------------------------------------------------ requests
     def add_request(self, req_id: int):
@@ -169,6 +174,11 @@ class SpeckvSplitKVConnector:
         The library serves allocations whose records lie in one run (an engine with one pool); for a striped or migrated placement it
         refuses with SpeckvError (status -4, SPECKV_ERR_INVAL) and the error passes through: there is no silent fall-back -- such
         a caller goes through attend_chunk with the step's new rows."""
+        return self._attend_own(layer, req_ids, q, sm_scale, stream, window)[0]
+
+    def _attend_own(self, layer, req_ids, q, sm_scale, stream, window):
+        """attend's body: -> (out, lse [batch][heads][g] fp32 -- -inf for a request that holds nothing --, the query as the launches
+        read it); attend_shared folds the prefix part into the first two"""
         import numpy as np
         import torch
         W = SpeckvKVConnector._decode_window(window)
@@ -203,7 +213,7 @@ class SpeckvSplitKVConnector:
             if n_odd:
                 self.lib.attend_fold_tail(n_odd, rows.data_ptr(), self.H, G, q.data_ptr(), tk.data_ptr() + 2 * layer * row,
                                           tv.data_ptr() + 2 * layer * row, self.L * row, sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
-        return out
+        return out, lse, q
 
     def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, splits=1,
                      window=None, parents=None):
@@ -215,6 +225,11 @@ class SpeckvSplitKVConnector:
         pieces); window W >= 1 a sliding-window layer; parents a tree of drafts (chunk_tree_masks); window together with parents goes by
         a node's DEPTH, as SpeckvKVConnector.attend_tree.  The stored K enters as its E4M3 values with the block scale on the score, the
         stored V as the fp16 values of its MXFP4 records, the query stays fp16."""
+        return self._chunk_own(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, splits, window, parents)
+
+    def _chunk_own(self, layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, splits, window, parents, keep_lse=False):
+        """attend_chunk's body.  keep_lse (attend_chunk_shared): the same call with d_lse given; returns (out, lse
+        [batch][S][heads][rows_per_pos] fp32 with -inf where nothing was written, the query as the launch read it)"""
         import numpy as np
         import torch
         window = SpeckvKVConnector._chunk_window(window)
@@ -244,8 +259,9 @@ class SpeckvSplitKVConnector:
             if trees and len(trees[0]) != S:
                 raise ValueError("parents: one entry per new position")
         out = (torch.empty if n_new is None and parents is None else torch.zeros)((B, S, H, R, D), dtype=torch.float32, device="cuda")
+        lse = torch.full((B, S, H, R), float("-inf"), dtype=torch.float32, device="cuda") if keep_lse else None
         if not any(counts):
-            return out
+            return (out, lse, q.contiguous()) if keep_lse else out
         row = self.H * self.D
         with self._On(self, stream) as st:
             with torch.cuda.stream(st):
@@ -262,7 +278,177 @@ class SpeckvSplitKVConnector:
                                      v_new.data_ptr() + 2 * layer * v_new.stride(2), k_new.stride(0), k_new.stride(1), tail_idx,
                                      tk.data_ptr() + 2 * layer * row if tk is not None else 0, tv.data_ptr() + 2 * layer * row if tv is not None else 0,
                                      self.L * row, masks.data_ptr() if masks is not None else 0, masks.shape[2] if masks is not None else 0,
-                                     depths.data_ptr() if depths is not None else 0, window, int(splits), sm_scale, out.data_ptr(), 0, st.cuda_stream)
+                                     depths.data_ptr() if depths is not None else 0, window, int(splits), sm_scale, out.data_ptr(),
+                                     lse.data_ptr() if keep_lse else 0, st.cuda_stream)
+        return (out, lse, q) if keep_lse else out
+
+    # ------------------------------------------------------------------ a prefix shared by several requests
+    shared_groups = staticmethod(SpeckvKVConnector.shared_groups)
+    _shared_permutation = staticmethod(SpeckvKVConnector._shared_permutation)
+
+    def _shared_args(self, req_ids, prefix_ids, prefix_lens, splits, what, window=None):
+        """The shared-prefix arguments of a call, judged in front of any library call and kept for the other layers of the step, keyed as
+        SpeckvKVConnector._shared_args keys them: by the lists (values AND types: True == 1), the window (value and type, judged in
+        front of it) and `_epoch`.  None when no member sees a prefix; otherwise (order or None when the batch is laid out already, the
+        members in that order, the groups' K handles, their V handles, first_member and the members' prefix lengths in that order as
+        the arrays the entry takes).  Every method that changes a request's length or handle, or the set of requests, moves `_epoch`
+        (add_request, free_request, write_prefill, commit do) -- a new state-changing method must move it too."""
+        import numpy as np
+        key = (what, self._epoch, tuple(req_ids), tuple(prefix_ids), tuple(map(type, prefix_ids)), type(splits), splits,
+               None if prefix_lens is None else (tuple(prefix_lens), tuple(map(type, prefix_lens))), type(window), window)
+        if self._shared_key == key:
+            return self._shared_plan
+        plan = self._shared_judge(req_ids, prefix_ids, prefix_lens, splits)
+        if plan is not None:
+            order, prefixes, first, lens = plan
+            if order is not None:
+                req_ids, lens = [req_ids[b] for b in order], [lens[b] for b in order]
+            plan = (order, list(req_ids), np.asarray([self.requests[p].k_handle for p in prefixes], dtype=np.uint64),
+                    np.asarray([self.requests[p].v_handle for p in prefixes], dtype=np.uint64), np.asarray(first, dtype=np.uint32),
+                    np.asarray(lens, dtype=np.uint32))
+        self._shared_key, self._shared_plan = key, plan
+        return plan
+
+    def _shared_judge(self, req_ids, prefix_ids, prefix_lens, splits):
+        """SpeckvKVConnector._shared_judge restated over split requests: (order or None, the groups' prefix ids, first_member, the
+        members' prefix lengths in the CALLER's order) -- or None when no member sees a prefix"""
+        B = len(req_ids)
+        if len(prefix_ids) != B or (prefix_lens is not None and len(prefix_lens) != B):
+            raise ValueError("prefix_ids (and prefix_lens): one entry per request")
+        if not _is_int(splits) or not 0 <= splits <= 64:
+            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
+        for r in req_ids:
+            self.requests[r]                                              # KeyError: an unknown member
+        members, lens = set(req_ids), []
+        for b, p in enumerate(prefix_ids):
+            if p is None:
+                if prefix_lens is not None and prefix_lens[b] is not None and (not _is_int(prefix_lens[b]) or prefix_lens[b] != 0):
+                    raise ValueError("prefix_lens: a member without a prefix takes 0 or None")
+                lens.append(0)
+                continue
+            if not _is_int(p):
+                raise ValueError("prefix_ids: request ids (ints) or None")
+            if p not in self.requests:
+                raise KeyError(f"prefix request {p} does not exist")
+            if p in members:
+                raise ValueError(f"request {p} is a member of the call and cannot be its prefix")
+            have = self.requests[p].length
+            if prefix_lens is None or prefix_lens[b] is None:
+                if have & 1:
+                    raise ValueError(f"prefix request {p} holds an odd number of positions ({have}): pass prefix_lens and keep the "
+                                     "last position in the member (only whole stored pairs can be shared)")
+                lens.append(have)
+            else:
+                n = prefix_lens[b]
+                if not _is_int(n) or n < 0 or n & 1 or n > (have & ~1):
+                    raise ValueError(f"prefix_lens: even ints in 0..{have & ~1} for prefix request {p}")
+                lens.append(int(n))
+        if not any(lens):
+            return None
+        order, prefixes, first = self.shared_groups(req_ids, prefix_ids)
+        return (None if order == list(range(B)) else order, prefixes, first, lens)
+
+    def attend_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, sm_scale: float, prefix_lens=None,
+                      stream=None, splits=0, window=None):
+        """attend() for requests that SHARE A PREFIX without holding a copy of it (parallel samples of one prompt, beams, a system prompt
+        in front of many users); the contract of SpeckvKVConnector.attend_shared over the split pool.  Shapes and result are attend()'s.
+        A prefix is an ordinary split request the call names: prefix_ids[b] = the request whose first prefix_lens[b] stored positions
+        member b sees in front of its own, or None.  prefix_lens[b] defaults to the prefix's length, which must then be even; a given
+        one is even, >= 0 and at most the prefix's length rounded down to even.  A prefix may not be a member; members of one prefix
+        may see different lengths of it and need not be adjacent (shared_groups; q and the result are permuted only when they are not).
+        g is 1, 2, 4, 8 or 16.
+        The step: the members' own attention exactly as attend(window=window) issues it (speckv_ext_attend_kv_batch[_window] and the
+        tail fold), with the log-sum-exp kept, then ONE speckv_ext_attend_prefix_fold_kv call on the same stream with C = 1, own_seen =
+        the member's length and the chain depth 0: a workgroup walks the prefix's FP8 key records and MXFP4 value records ONCE for 64
+        query rows of its members and folds the result into theirs -- the softmax over prefix + own positions.  THE OWN PART TAKES THE
+        QUERY AS E4M3 x A ROW SCALE, as attend does; THE PREFIX PART TAKES IT IN fp16.  splits: 0 = the library's rule cuts a long
+        prefix of few members across the chip, 1 = never, N = forced.  window None = a global layer; an int W >= 1 = a local layer:
+        the member's query sees the last W positions of prefix + own, the fold the prefix positions [max(0, prefix_lens[b] + length -
+        W), prefix_lens[b]); a member with length >= W keeps the bits of attend(window=W).  No member with a prefix (all None, or all
+        lengths 0): attend()'s launches and bits.  The pool holds the prefix once: (members - 1) x prefix pairs x 3136 bytes per layer
+        less than members that each hold a copy.
+        Anything malformed is a ValueError / KeyError before any library call; a q that is no torch tensor is a TypeError."""
+        import numpy as np
+        import torch
+        W = SpeckvKVConnector._shared_window(window)
+        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_shared", window)
+        SpeckvKVConnector._shared_tensors("attend_shared", q=q)
+        if len(q.shape) != 4 or q.shape[0] != len(req_ids):
+            raise ValueError("q must be [batch][heads][g][dim]")
+        if plan is None:
+            return self.attend(layer, req_ids, q, sm_scale, stream, window)
+        order, req_ids, k_handles, v_handles, first, lens = plan
+        G = int(q.shape[2])
+        if G not in (1, 2, 4, 8, 16):
+            raise ValueError("attend_shared() takes 1, 2, 4, 8 or 16 query rows per kv head")
+        B = len(req_ids)
+        if order is not None:                                     # the gather runs on the stream the launches go to, as they do
+            with self._On(self, stream) as st, torch.cuda.stream(st):
+                idx, inv = self._shared_permutation(order)
+                q = q.index_select(0, idx)
+        out, lse, qs = self._attend_own(layer, req_ids, q, sm_scale, stream, window)
+        with self._On(self, stream) as st:
+            own = np.asarray([self.requests[r].length for r in req_ids], dtype=np.uint32)
+            self.lib.attend_prefix_fold_kv(k_handles, v_handles, first, layer, qs.data_ptr(), 1, G, lens, np.ones(B, dtype=np.uint32), own, 0, W,
+                                           int(splits), sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+            if order is not None:                                 # the way back: behind the fold, on its stream
+                with torch.cuda.stream(st):
+                    out = out.index_select(0, inv)
+        return out
+
+    def attend_chunk_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, k_new, v_new, sm_scale: float,
+                            n_new=None, prefix_lens=None, stream=None, splits=0, window=None, parents=None):
+        """attend_chunk() for members of a shared prefix; the contract of SpeckvKVConnector.attend_chunk_shared over the split pool.  The
+        member's OWN step -- a user's differing suffix behind a shared system prompt, a draft chain or tree -- is what
+        attend_chunk(splits=1, window=window, parents=parents) issues (ONE speckv_ext_attend_chunk_kv call) with the log-sum-exp kept;
+        then ONE speckv_ext_attend_prefix_fold_kv call with C = S, n_q = the live counts and own_seen = length + 1 on the same stream
+        folds in the stored positions [0, prefix_lens[b]) of the request prefix_ids[b].  Shapes, n_new and the result (zeros for
+        positions >= n_new[b]) are attend_chunk's; prefix_ids, prefix_lens, splits and what is refused are attend_shared's.  Both
+        parts take the query in fp16.  window W >= 1: query position j sees the prefix positions [max(0, prefix_lens[b] + length + 1
+        + j - W), prefix_lens[b]).  parents: the prefix part has no structure among rows, every live node sees all of it; parents
+        together with window goes by a node's DEPTH as attend_chunk does -- the fold reads the same depth table the own call reads,
+        node j of depth d sees from max(0, prefix_lens[b] + length + 1 + d - W) on -- so this one method is the tree step of a local
+        layer too.  Changes no state: commit() stores the accepted positions in the MEMBER afterwards.  No member with a prefix:
+        attend_chunk(splits=1)'s launch and bits."""
+        import numpy as np
+        import torch
+        W = SpeckvKVConnector._shared_window(window)
+        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_chunk_shared", window)
+        SpeckvKVConnector._shared_tensors("attend_chunk_shared", q=q, k_new=k_new, v_new=v_new)
+        if plan is None:
+            return self.attend_chunk(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, 1, window, parents)
+        order, req_ids, k_handles, v_handles, first, lens = plan
+        if order is not None:
+            if n_new is not None:
+                if len(n_new) != len(order):
+                    raise ValueError("n_new: one count 0..S per request")
+                n_new = [n_new[b] for b in order]
+            if parents is not None:
+                parents = list(parents)
+                if parents and not isinstance(parents[0], numbers.Integral):          # one tree per request: in the members' order
+                    if len(parents) != len(order):
+                        raise ValueError("parents: one tree per request, or one tree for all")
+                    parents = [parents[b] for b in order]
+            with self._On(self, stream) as st, torch.cuda.stream(st):     # the gather runs on the stream the launches go to
+                idx, inv = self._shared_permutation(order)
+                q, k_new, v_new = q.index_select(0, idx), k_new.index_select(0, idx), v_new.index_select(0, idx)
+        out, lse, qs = self._chunk_own(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, 1, window, parents, keep_lse=True)
+        B, S, _, R, _ = (int(x) for x in qs.shape)
+        live = [S] * B if n_new is None else [int(n) for n in n_new]
+        if any(live) or order is not None:
+            with self._On(self, stream) as st:
+                if any(live):
+                    reqs = [self.requests[r] for r in req_ids]
+                    depths = 0
+                    if W and parents is not None:                 # the table the own call has just read (kept per tree and window)
+                        with torch.cuda.stream(st):
+                            depths = self._step_tree(req_ids, reqs, parents, live, S, W)[1].data_ptr()
+                    self.lib.attend_prefix_fold_kv(k_handles, v_handles, first, layer, qs.data_ptr(), S, R, lens, np.asarray(live, dtype=np.uint32),
+                                                   np.asarray([r.length + 1 for r in reqs], dtype=np.uint32), depths, W, int(splits), sm_scale,
+                                                   out.data_ptr(), lse.data_ptr(), st.cuda_stream)
+                if order is not None:                             # the way back: behind the fold, on its stream
+                    with torch.cuda.stream(st):
+                        out = out.index_select(0, inv)
         return out
 
     # ------------------------------------------------------------------ commit

@@ -113,6 +113,8 @@ _EXT_SIGNATURES = {
                                       ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_prefix_fold_window": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_prefix_fold_kv": [c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_prefix_window_walk": [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p],
     "speckv_ext_fetch_range": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p],
     "speckv_ext_fetch_range_engine": [c_uint64, c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_int],
@@ -533,6 +535,19 @@ class SpeckvLib:
         n = len(prefix_handles)
         m = len(prefix_len)
         self._ext("speckv_ext_attend_prefix_fold_window", n, as_arr(prefix_handles, c_uint64, n), as_arr(first_member, c_uint32, n + 1), layer,
+                  c_void_p(d_q), C, rows_per_pos, as_arr(prefix_len, c_uint32, m), as_arr(n_q, c_uint32, m),
+                  None if own_seen is None else as_arr(own_seen, c_uint32, m), c_void_p(d_depth or None), window, n_splits, sm_scale,
+                  c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))
+
+    def attend_prefix_fold_kv(self, k_handles, v_handles, first_member, layer, d_q, C, rows_per_pos, prefix_len, n_q, own_seen, d_depth, window,
+                              n_splits, sm_scale, d_out, d_lse, stream):
+        """attend_prefix_fold_window over a split pool (speckv_ext_attend_prefix_fold_kv): the prefix of group g = region `layer`
+        (num_tokens / 2 pages) of the FP8 allocation k_handles[g] for K and of the MXFP4 allocation v_handles[g] for V.  window 0 (own_seen
+        may then be None), or one that cuts nothing, issues the unwindowed launches.  The other arguments as attend_prefix_fold_window."""
+        n = len(v_handles if k_handles is None else k_handles)             # (None: a NULL array, for the library to refuse)
+        m = len(prefix_len)
+        handles = lambda h: None if h is None else as_arr(h, c_uint64, n)
+        self._ext("speckv_ext_attend_prefix_fold_kv", n, handles(k_handles), handles(v_handles), as_arr(first_member, c_uint32, n + 1), layer,
                   c_void_p(d_q), C, rows_per_pos, as_arr(prefix_len, c_uint32, m), as_arr(n_q, c_uint32, m),
                   None if own_seen is None else as_arr(own_seen, c_uint32, m), c_void_p(d_depth or None), window, n_splits, sm_scale,
                   c_void_p(d_out), c_void_p(d_lse or None), c_void_p(stream))

@@ -1168,6 +1168,42 @@ speckv_status_t speckv_ext_attend_chunk_kv(uint32_t n_seq, const speckv_handle_t
                                            const uint32_t* d_depth, uint32_t window /* 0: none */, uint32_t n_splits,
                                            float sm_scale, float* d_out, float* d_lse, void* stream);
 
+/* speckv_ext_attend_prefix_fold_kv: SHARED-PREFIX attention over a SPLIT POOL ("K8V4", see speckv_ext_attend_chunk_kv) -- the prefix
+ * of a group is a request of the split pool, its K rows in an FP8_E4M3 allocation and its V rows in an MXFP4 allocation of their own,
+ * read once per 64 query rows of the group's members by ONE launch (or a piece launch and its merge) and folded into what each member
+ * attended on its own.  An additive entry: SPECKV_EXT_ABI_VERSION stays what it is.
+ * The arguments: k_handles and v_handles (host arrays [n_groups]) in the place of `prefix_handles`, then exactly the argument list of
+ * speckv_ext_attend_prefix_fold_window from first_member on.  Everything said at speckv_ext_attend_prefix_fold and at
+ * speckv_ext_attend_prefix_fold_window holds word for word -- the members, the fp16 query, d_out / d_lse READ AND WRITTEN, THE FOLD (a
+ * member without positions of its own arrives as out = 0, lse = -inf), DEAD pairs, the walk to the group's largest prefix_len,
+ * n_splits, own_seen / d_depth / window and which rows a window leaves live, ordering, NOT capturable into a HIP graph.
+ *   own_seen : may be NULL iff window == 0 (nothing reads it then).
+ *   window   : 0, or a window that cuts nothing by the rule stated at speckv_ext_attend_prefix_fold_window, issues the unwindowed
+ *              launches and their bits; d_depth is not read then.
+ * Addressing.  As speckv_ext_attend_chunk_kv: both allocations are arrays of REGIONS of num_tokens / 2 pages, K of `layer` is region
+ * `layer` of k_handles[g], V of `layer` is region `layer` of v_handles[g]; stored position p of the layer lies in page
+ * layer * num_tokens / 2 + p / 2 of either.
+ * Values.  A stored K element enters the score as the E4M3 value of its record, the page's block scale multiplies the score in fp32
+ * -- exactly what speckv_ext_attend_prefix_fold does over an FP8 pool.  A stored V element enters as the fp16 value
+ * speckv_ext_fetch_range decodes from the MXFP4 record.  The query stays fp16.  A page never written reads as zeros.
+ *   SPECKV_OK           also for zero groups, zero members and no live pair -- nothing is launched
+ *   SPECKV_ERR_INVAL    everything speckv_ext_attend_prefix_fold_window refuses (a NULL own_seen with members only where window != 0),
+ *                       and: k_handles or v_handles NULL, a K allocation whose scheme is not SPECKV_COMP_FP8_E4M3, a V allocation whose
+ *                       scheme is not SPECKV_COMP_MXFP4, a layout that is not 8 heads x 128 fp16 or whose num_tokens is odd, num_tokens
+ *                       that differ between the two allocations of a group, prefix_len[m] > num_tokens, (layer + 1) * num_tokens / 2
+ *                       beyond either allocation's pages, layer >= 2 * num_layers, a capturing stream -- nothing is launched
+ *   SPECKV_ERR_NOMEM    the scratch buffer of a split call could not grow -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle
+ * Every refusal comes before any launch and leaves out / lse untouched.  speckv_free of either allocation waits for `stream`. */
+speckv_status_t speckv_ext_attend_prefix_fold_kv(uint32_t n_groups, const speckv_handle_t* k_handles,
+                                                 const speckv_handle_t* v_handles /* host [n_groups] */,
+                                                 const uint32_t* first_member /* host [n_groups + 1] */, uint32_t layer,
+                                                 const void* d_q_f16, uint32_t C, uint32_t rows_per_pos,
+                                                 const uint32_t* prefix_len, const uint32_t* n_q,
+                                                 const uint32_t* own_seen /* host [n_members]; may be NULL iff window == 0 */,
+                                                 const uint32_t* d_depth /* device, may be NULL */, uint32_t window /* 0: none */,
+                                                 uint32_t n_splits, float sm_scale, float* d_out, float* d_lse, void* stream);
+
 /* speckv_ext_attend_kv_batch: one DECODE STEP of a batch over a SPLIT POOL ("K8V4", see speckv_ext_attend_chunk_kv) -- the fused
  * attention of ONE layer for n_seq sequences over the stored positions [0, pos_end[i]), one new position per sequence with g query rows
  * per kv head, in one attention launch (and a merge launch where sequences are cut into pieces).  The decode-shaped counterpart of
