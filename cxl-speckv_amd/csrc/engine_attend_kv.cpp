@@ -34,13 +34,6 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
     }
     if (!k_handles || !v_handles || !pos_end || !d_q_f16 || !d_out || g == 0 || g > 16) return SPECKV_ERR_INVAL;
     if (reinterpret_cast<uintptr_t>(d_q_f16) % 16u || reinterpret_cast<uintptr_t>(d_out) % 16u) return SPECKV_ERR_INVAL;
-    // a region (num_tokens / 2 pages) of an allocation of the split pool: 8 x 128 fp16, region `layer` inside its pages (engine_chunk.cpp: region_ok)
-    const auto region_ok = [&](const Allocation* a, int want, uint32_t end) {
-        if (!a->has_layout || a->scheme != want) return false;
-        const Layout& L = a->layout;
-        if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads != 8 || L.num_tokens % 32 || end % 2 || end > L.num_tokens) return false;
-        return (static_cast<uint64_t>(layer) + 1u) * (L.num_tokens / 2u) <= a->n_pages && layer < 2ull * L.num_layers;
-    };
     std::vector<AttendSeq> seqs(n_seq);
     std::vector<AttendKvSide> vside(n_seq);
     std::vector<uint32_t> tiles(n_seq), pages(n_seq), skips(q_pos ? n_seq : 0u);      // (skips: AttendArgs::seq_skip of a windowed launch)
@@ -50,7 +43,7 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
     for (uint32_t i = 0; i < n_seq; ++i) {
         Allocation *k = find(k_handles[i]), *v = find(v_handles[i]);
         if (!k || !v) return SPECKV_ERR_GENERAL;
-        if (!region_ok(k, SPECKV_COMP_FP8_E4M3, pos_end[i]) || !region_ok(v, SPECKV_COMP_MXFP4, pos_end[i]) ||
+        if (pos_end[i] % 2u || !split_region_ok(k, SPECKV_COMP_FP8_E4M3, layer, pos_end[i], 32u) || !split_region_ok(v, SPECKV_COMP_MXFP4, layer, pos_end[i], 32u) ||
             k->layout.num_tokens != v->layout.num_tokens)
             return SPECKV_ERR_INVAL;
         if (!k->linear_base || !k->d_scale_tab || !v->linear_base) {

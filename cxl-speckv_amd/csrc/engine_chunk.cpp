@@ -109,18 +109,11 @@ int Engine::attend_chunk(const ChunkCall& c, hipStream_t s)
     const uint32_t per_block = 64u / c.rows_per_pos;
     std::vector<Allocation*> as(c.n_seq), vs(c.split_kv ? c.n_seq : 0u);
     int scheme = -1;
-    // a region (num_tokens / 2 pages) of an allocation of the split pool: 8 x 128 fp16, region `layer` inside its pages
-    const auto region_ok = [&](const Allocation* a, int want, uint32_t pos_end) {
-        if (!a->has_layout || a->scheme != want) return false;
-        const Layout& L = a->layout;
-        if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads != 8 || L.num_tokens % 2 || pos_end > L.num_tokens) return false;
-        return (static_cast<uint64_t>(c.layer) + 1u) * (L.num_tokens / 2u) <= a->n_pages && c.layer < 2ull * L.num_layers;
-    };
     const auto check = [&]() -> int {
         for (uint32_t i = 0; c.split_kv && i < c.n_seq; ++i) {
             Allocation *k = find(c.handles[i]), *v = find(c.v_handles[i]);
             if (!k || !v) return SPECKV_ERR_GENERAL;
-            if (!region_ok(k, SPECKV_COMP_FP8_E4M3, c.pos_end[i]) || !region_ok(v, SPECKV_COMP_MXFP4, c.pos_end[i]) ||
+            if (!split_region_ok(k, SPECKV_COMP_FP8_E4M3, c.layer, c.pos_end[i], 2u) || !split_region_ok(v, SPECKV_COMP_MXFP4, c.layer, c.pos_end[i], 2u) ||
                 k->layout.num_tokens != v->layout.num_tokens)
                 return SPECKV_ERR_INVAL;
             as[i] = k; vs[i] = v;

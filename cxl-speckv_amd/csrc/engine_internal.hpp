@@ -136,6 +136,16 @@ SeqTuning seq_tuning()
     return SeqTuning{t.attend_general, t.attend_splits, t.attend_stream, t.attend_fp8_table_regs, t.attend_fp8_striped_table, t.attend_int4_striped_wg, t.attend_fp8_dma};
 }
 
+// The region rule of an allocation of the split pool (FP8 keys in one, MXFP4 values in the other): scheme `want`, 8 x 128 fp16 per
+// position, num_tokens a multiple of `tokens_multiple`, pos_end inside it, and region `layer` (num_tokens / 2 pages) inside its pages
+bool split_region_ok(const Allocation* a, int want, uint32_t layer, uint32_t pos_end, uint32_t tokens_multiple)
+{
+    if (!a->has_layout || a->scheme != want) return false;
+    const Layout& L = a->layout;
+    if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads != 8 || L.num_tokens % tokens_multiple || pos_end > L.num_tokens) return false;
+    return (static_cast<uint64_t>(layer) + 1u) * (L.num_tokens / 2u) <= a->n_pages && layer < 2ull * L.num_layers;
+}
+
 // A batch launch reads its descriptor slot in place: whatever was launched must have passed before the slot is written again.  The
 // slot's event is recorded on EVERY way out of the scope that holds the guard (a merge launch that fails behind an
 // attention launch that went through used to leave the slot unguarded under a kernel still fetching from it).

@@ -74,18 +74,12 @@ int Engine::attend_prefix(const PrefixCall& c, hipStream_t s)
     if (n_blocks * 8u > 0x7FFFFFFFull) return SPECKV_ERR_INVAL;
     std::vector<Allocation*> as(c.n_groups), vs(c.split_kv ? c.n_groups : 0u);
     int scheme = -1;
-    // a region (num_tokens / 2 pages) of an allocation of the split pool: 8 x 128 fp16, region `layer` inside its pages
-    const auto region_ok = [&](const Allocation* a, int want) {
-        if (!a->has_layout || a->scheme != want) return false;
-        const Layout& L = a->layout;
-        if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads != 8 || L.num_tokens % 2) return false;
-        return (static_cast<uint64_t>(c.layer) + 1u) * (L.num_tokens / 2u) <= a->n_pages && c.layer < 2ull * L.num_layers;
-    };
     const auto check = [&]() -> int {
         for (uint32_t g = 0; c.split_kv && g < c.n_groups; ++g) {
             Allocation *k = find(c.handles[g]), *v = find(c.v_handles[g]);
             if (!k || !v) return SPECKV_ERR_GENERAL;
-            if (!region_ok(k, SPECKV_COMP_FP8_E4M3) || !region_ok(v, SPECKV_COMP_MXFP4) || k->layout.num_tokens != v->layout.num_tokens)
+            if (!split_region_ok(k, SPECKV_COMP_FP8_E4M3, c.layer, 0u, 2u) || !split_region_ok(v, SPECKV_COMP_MXFP4, c.layer, 0u, 2u) ||
+                k->layout.num_tokens != v->layout.num_tokens)
                 return SPECKV_ERR_INVAL;
             for (uint32_t m = c.first_member[g]; m < c.first_member[g + 1]; ++m)
                 if (c.prefix_len[m] > k->layout.num_tokens) return SPECKV_ERR_INVAL;

@@ -50,6 +50,7 @@ Only plain device pointers cross into the library; torch is used for device buff
 import numbers
 from typing import Dict, List, Optional, Sequence
 
+from .kv_shared import PARENTS_RULE, SPLITS_RULE, SharedPrefixSteps, _is_int, tail_index
 from .speckv_ctypes import HELD_MAX, SpeckvLib
 
 PAGE = 4096
@@ -91,12 +92,7 @@ def _device_index(values):
     return torch.tensor(values, dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
 
 
-def _is_int(x):
-    """an integer of any kind (python's, numpy's), but no bool"""
-    return isinstance(x, numbers.Integral) and not isinstance(x, bool)
-
-
-class SpeckvKVConnector:
+class SpeckvKVConnector(SharedPrefixSteps):
     def __init__(self, lib: SpeckvLib, num_layers: int, num_kv_heads: int = 8, head_dim: int = 128, max_tokens: int = 4096,
                  scheme: str = "fp8"):
         if num_kv_heads * head_dim * 2 != 2048:
@@ -346,7 +342,7 @@ class SpeckvKVConnector:
                     self._arg_key = self._plan_stream = None
             except SpeckvError as e:
                 self._arg_key = self._plan_stream = None
-                if e.status != -4:                             # SPECKV_ERR_INVAL: the stream cannot take the plan now (capturing / destroyed): attend() plans again
+                if e.status != -4:                             # SPECKV_ERR_INVAL: the stream refuses the plan now (capturing / destroyed): attend() plans again
                     raise
         return keep                                            # sources of the asynchronous writes: hold until the stream passed them
 
@@ -846,7 +842,7 @@ class SpeckvKVConnector:
         if parents and not isinstance(parents[0], numbers.Integral):
             trees = [list(p) for p in parents]
             if len(trees) != batch:
-                raise ValueError("parents: one tree per request, or one tree for all")
+                raise ValueError(PARENTS_RULE)
         else:
             trees = [parents] * batch
         S = len(trees[0]) if trees else 0
@@ -1022,7 +1018,7 @@ class SpeckvKVConnector:
         from below by the block's first tile (chunk_window_walk), and the last piece goes on through the held tiles from the later
         of its start and that tile; a piece that is not the last can be empty for later blocks."""
         if not _is_int(splits) or not 0 <= splits <= 64:
-            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
+            raise ValueError(SPLITS_RULE)
         if not _is_int(n_cus) or n_cus < 0:
             raise ValueError("n_cus: the compute units of the device (0: 256)")
         counts, _ = SpeckvKVConnector.chunk_blocks(n_new, rows_per_pos)
@@ -1103,7 +1099,7 @@ class SpeckvKVConnector:
             except TypeError:
                 raise ValueError("parents: ints, or one list of ints per request") from None
             if len(trees) != batch:
-                raise ValueError("parents: one tree per request, or one tree for all")
+                raise ValueError(PARENTS_RULE)
         else:
             trees = [parents] * batch
         S = len(trees[0]) if trees else 0
@@ -1287,55 +1283,20 @@ class SpeckvKVConnector:
             raise ValueError("window does not combine with parents: a windowed layer takes a chain of new positions, not a tree")
         if by_depth and parents is None:
             raise ValueError("parents: ints, or one list of ints per request")
-        if not _is_int(splits) or not 0 <= splits <= 64:
-            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
-        splits = int(splits)
-        if self.scheme not in FUSED:
-            raise ValueError("attend_chunk() needs an FP8, INT4 or MXFP4 pool")
-        if len(q.shape) != 5:
-            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim]")
-        B, S, H, R, D = (int(x) for x in q.shape)
-        want = (B, S, self.L, self.H, self.D)
-        if (H, D) != (self.H, self.D) or tuple(k_new.shape) != want or tuple(v_new.shape) != want or B != len(req_ids) or S < 1:
-            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim], k_new / v_new [batch][S][layers][heads][dim], S >= 1")
-        if not 0 <= layer < self.L:
-            raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
-        if n_new is None:
-            live = [S] * B
-        else:
-            live = [int(n) for n in n_new]
-            if len(live) != B or not all(0 <= n <= S for n in live):
-                raise ValueError("n_new: one count 0..S per request")
-        counts, _ = self.chunk_blocks(live, R)
-        key, reqs, handles = self._batch(req_ids)
-        for r, n in zip(reqs, live):
-            if r.length + n > self.T:
-                raise ValueError(f"a request of {r.length} positions cannot take {n} more: max_tokens is {self.T}")
-        if parents is not None:
-            trees = self._chunk_tree_parents(parents, B)                  # judged in front of any library call
-            if trees and len(trees[0]) != S:
-                raise ValueError("parents: one entry per new position")
-        out = (torch.empty if n_new is None and parents is None else torch.zeros)((B, S, H, R, D), dtype=torch.float32, device="cuda")
-        lse = torch.full((B, S, H, R), float("-inf"), dtype=torch.float32, device="cuda") if keep_lse else None
-        if not any(counts):
+        reqs, live, (S, R), out, lse, some = self._chunk_judge(layer, req_ids, q, k_new, v_new, n_new, splits, parents, keep_lse)
+        if not some:
             return (out, lse, q.contiguous()) if keep_lse else out
-        row = self.H * self.D
+        key, _, handles = self._batch(req_ids)
+        splits, row = int(splits), self.H * self.D
         with self._On(self, stream) as st:
             with torch.cuda.stream(st):
                 if self._kscale is not None:
                     q = q * self._kscale[layer][None, None, :, None, :]
                     k_new = k_new * self._kscale_inv[None, None]
                 q = q.contiguous()
-                in_place = lambda t: (t.stride(4) == 1 and t.stride(3) == self.D and t.stride(2) % 8 == 0 and t.stride(1) % 8 == 0 and
-                                      t.stride(1) >= row and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0)
-                if not (in_place(k_new) and in_place(v_new) and k_new.stride() == v_new.stride()):
-                    k_new, v_new = k_new.contiguous(), v_new.contiguous()
+                k_new, v_new = self._chunk_rows(k_new, v_new)
                 self._prepare_tails(req_ids, key, reqs, st)
-                tail_idx, rank = np.full(B, -1, dtype=np.int32), 0
-                for b, r in enumerate(reqs):
-                    if r.length & 1:
-                        tail_idx[b] = rank
-                        rank += 1
+                tail_idx, rank = tail_index(reqs)
                 kt = self._fold_k.data_ptr() + 2 * layer * row if rank else 0
                 vt = self._fold_v.data_ptr() + 2 * layer * row if rank else 0
                 if window and by_depth:
@@ -1358,138 +1319,42 @@ class SpeckvKVConnector:
         return (out, lse, q) if keep_lse else out
 
     # ------------------------------------------------------------------ a prefix shared by several requests
-    @staticmethod
-    def shared_groups(req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]]):
-        """How a call over members with shared prefixes is laid out for speckv_ext_attend_prefix_fold: (order, prefixes, first_member).
-        order = the indices 0..batch-1 so that the members of one prefix are adjacent -- the prefixes in the order of their first
-        member, the members of a prefix in the caller's order (stable), the members without a prefix (None) last, in the caller's order;
-        prefixes = the prefix id of every group; first_member = the exclusive prefix of the groups' sizes, len(prefixes) + 1 entries
-        (the members behind first_member[-1] have no prefix).  An input that is already laid out so gives order == list(range(batch))."""
-        if len(prefix_ids) != len(req_ids):
-            raise ValueError("prefix_ids: one prefix id or None per request")
-        groups, none = {}, []
-        for b, p in enumerate(prefix_ids):
-            (none if p is None else groups.setdefault(p, [])).append(b)
-        order, first = [], [0]
-        for members in groups.values():
-            order += members
-            first.append(len(order))
-        return order + none, list(groups), first
-
-    @staticmethod
-    def _shared_window(window):
-        """window as the shared-prefix calls take it: None -> 0 (no window), an int >= 1 -> itself; anything else -- 0, a negative, a
-        bool, a float, a string -- is a ValueError"""
-        if window is None:
-            return 0
-        if not _is_int(window) or not 1 <= window <= 0xFFFFFFFF:
-            raise ValueError("window must be None (no window) or a count of positions >= 1")
-        return int(window)
-
-    @staticmethod
-    def _shared_tensors(what, **tensors):
-        """The rows of a shared-prefix call are torch tensors: the fold reads them by data_ptr() behind the own step, and the grouped
-        order gathers them with index_select, so None or an object that merely has a shape is a TypeError here -- behind the
-        judgement of the lists, in front of any library call -- and not an AttributeError somewhere inside the step"""
-        import torch
-        for name, t in tensors.items():
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{what}(): {name} must be a torch tensor, not {type(t).__name__}")
-
-    @staticmethod
-    def prefix_window_walk(first_member: Sequence[int], prefix_lens: Sequence[int], own_seen: Sequence[int], n_new: Sequence[int], window):
-        """Which tiles of its prefix a group of a shared-prefix call walks under a window (speckv_ext_prefix_window_walk restated).
-        Group g = the members first_member[g] .. first_member[g + 1] - 1 (shared_groups); member m sees prefix_lens[m] (even)
-        positions of the prefix in front of its own, own_seen[m] of its OWN positions are seen by its query position of depth 0,
-        itself included (a decode step: its length; a chunk or tree step: length + 1), and it brings n_new[m] live positions.  The
-        row of depth d sees [lo, prefix_lens[m]) of the prefix, lo = max(0, prefix_lens[m] + own_seen[m] + d - W) (W None: 0), and
-        nothing where that is empty.  A member COUNTS when n_new[m] > 0, prefix_lens[m] > 0 and its depth-0 bound -- its lowest --
-        is below prefix_lens[m].  The group's blocks walk the 32-position tiles [first_tile, first_tile + n_tiles): first_tile =
-        (the lowest depth-0 bound of the members that count) >> 5, n_tiles = ceil(max_len / 32) - first_tile with max_len their
-        largest prefix_lens; (0, 0) for a group no member of which counts -- it has no blocks.  Returns one (first_tile, n_tiles)
-        per group.  Pure python, no device."""
-        W = SpeckvKVConnector._shared_window(window)
-        first = list(first_member)
-        if not first or first[0] != 0 or any(not _is_int(x) for x in first) or any(b < a for a, b in zip(first, first[1:])):
-            raise ValueError("first_member: ints ascending from 0, one more than there are groups")
-        n = first[-1]
-        lens, seen, live = list(prefix_lens), list(own_seen), list(n_new)
-        if not (len(lens) == len(seen) == len(live) == n) or not all(_is_int(x) and x >= 0 for x in lens + seen + live) or any(x & 1 for x in lens):
-            raise ValueError("prefix_lens (even), own_seen, n_new: one count >= 0 per member")
-        walks = []
-        for a, b in zip(first, first[1:]):
-            bounds = [(max(0, lens[m] + seen[m] - W) if W else 0, lens[m]) for m in range(a, b) if live[m] and lens[m]]
-            bounds = [(lo, n_pre) for lo, n_pre in bounds if lo < n_pre]
-            if not bounds:
-                walks.append((0, 0))
-                continue
-            t_first = min(lo for lo, _ in bounds) >> 5
-            walks.append((t_first, (max(n_pre for _, n_pre in bounds) + 31) // 32 - t_first))
-        return walks
-
-    def _shared_args(self, req_ids, prefix_ids, prefix_lens, splits, what, window=None):
-        """The shared-prefix arguments of a call, judged in front of any library call and kept for the other layers of the step: the
-        judgement depends on the lists and on what the requests hold, so it is keyed by the lists (values AND types: True == 1), the
-        window (value and type, judged by _shared_window in front of it) and `_epoch`, like the attention plan.  None when no member
-        sees a prefix; otherwise (order or None when the batch is laid out
-        already, the members in that order, the groups' handles, first_member and the members' prefix lengths in that order as the
-        arrays the entry takes).  What is kept holds handles and lengths: it is right only while EVERY method that changes a request's
-        length or handle, or the set of requests, moves `_epoch` (add_request, free_request, write_prefill, append, commit, truncate,
-        fork do) -- a new state-changing method must move it too."""
-        import numpy as np
-        key = (what, self._epoch, tuple(req_ids), tuple(prefix_ids), tuple(map(type, prefix_ids)), type(splits), splits,
-               None if prefix_lens is None else (tuple(prefix_lens), tuple(map(type, prefix_lens))), type(window), window)
-        if self._shared_key == key:
-            return self._shared_plan
-        plan = self._shared_judge(req_ids, prefix_ids, prefix_lens, splits, what)
-        if plan is not None:
-            order, handles, first, lens = plan
-            if order is not None:
-                req_ids, lens = [req_ids[b] for b in order], [lens[b] for b in order]
-            plan = (order, list(req_ids), np.asarray(handles, dtype=np.uint64), np.asarray(first, dtype=np.uint32), np.asarray(lens, dtype=np.uint32))
-        self._shared_key, self._shared_plan = key, plan
-        return plan
-
-    def _shared_judge(self, req_ids, prefix_ids, prefix_lens, splits, what):
-        """_shared_args' judgement: (order or None, the groups' handles, first_member, the members' prefix lengths in the CALLER's
-        order) -- or None when no member sees a prefix"""
+    # (the bodies are SharedPrefixSteps': what follows is this connector's side of them)
+    def _pool_check(self, what):
         if self.scheme not in FUSED:
             raise ValueError(f"{what}() needs an FP8, INT4 or MXFP4 pool")
-        B = len(req_ids)
-        if len(prefix_ids) != B or (prefix_lens is not None and len(prefix_lens) != B):
-            raise ValueError("prefix_ids (and prefix_lens): one entry per request")
-        if not _is_int(splits) or not 0 <= splits <= 64:
-            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
-        for r in req_ids:
-            self.requests[r]                                              # KeyError: an unknown member
-        members, lens = set(req_ids), []
-        for b, p in enumerate(prefix_ids):
-            if p is None:
-                if prefix_lens is not None and prefix_lens[b] is not None and (not _is_int(prefix_lens[b]) or prefix_lens[b] != 0):
-                    raise ValueError("prefix_lens: a member without a prefix takes 0 or None")
-                lens.append(0)
-                continue
-            if not _is_int(p):
-                raise ValueError("prefix_ids: request ids (ints) or None")
-            if p not in self.requests:
-                raise KeyError(f"prefix request {p} does not exist")
-            if p in members:
-                raise ValueError(f"request {p} is a member of the call and cannot be its prefix")
-            have = self.requests[p].length
-            if prefix_lens is None or prefix_lens[b] is None:
-                if have & 1:
-                    raise ValueError(f"prefix request {p} holds an odd number of positions ({have}): pass prefix_lens and keep the "
-                                     "last position in the member (only whole stored pairs can be shared)")
-                lens.append(have)
-            else:
-                n = prefix_lens[b]
-                if not _is_int(n) or n < 0 or n & 1 or n > (have & ~1):
-                    raise ValueError(f"prefix_lens: even ints in 0..{have & ~1} for prefix request {p}")
-                lens.append(int(n))
-        if not any(lens):
-            return None
-        order, prefixes, first = self.shared_groups(req_ids, prefix_ids)
-        return (None if order == list(range(B)) else order, [self.requests[p].handle for p in prefixes], first, lens)
+
+    def _reqs(self, req_ids):
+        return self._batch(req_ids)[1]
+
+    def _prefix_handles(self, prefix_ids):
+        import numpy as np
+        return (np.asarray([self.requests[p].handle for p in prefix_ids], dtype=np.uint64),)
+
+    def _own_decode(self, layer, req_ids, q, sm_scale, stream, window, gathered):
+        import torch
+        if gathered and stream is not None:                       # attend's body scales q on torch's current stream: behind the gather
+            torch.cuda.current_stream().wait_stream(stream)
+        out, lse, qs = self._attend_layers_lse(layer, 1, req_ids, q[None], sm_scale, stream, window)
+        return out[0], lse, qs
+
+    def _own_chunk(self, layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, window, parents, by_depth, **keep_lse):
+        return self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, 1, window, by_depth, **keep_lse)
+
+    def _prefix_fold(self, handles, first, layer, req_ids, ahead, d_q, C, R, lens, n_q, depths, W, splits, sm_scale, d_out, d_lse, cuda_stream):
+        """own_seen = length + ahead (0: a decode step, whose position is stored already; 1: a chunk step), under a window only"""
+        import numpy as np
+        if W:
+            own = np.asarray([r.length for r in self._reqs(req_ids)], dtype=np.uint32)
+            if ahead:
+                own += np.uint32(ahead)
+            self.lib.attend_prefix_fold_window(*handles, first, layer, d_q, C, R, lens, n_q, own, depths, W, splits, sm_scale, d_out, d_lse, cuda_stream)
+        else:
+            self.lib.attend_prefix_fold(*handles, first, layer, d_q, C, R, lens, n_q, splits, sm_scale, d_out, d_lse, cuda_stream)
+
+    def _depth_table(self, req_ids, parents, live, S, W):
+        key, reqs, _ = self._batch(req_ids)
+        return self._chunk_tree_window_table(key, reqs, parents, live, S, W)[1].data_ptr()
 
     def attend_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, sm_scale: float, prefix_lens=None,
                       stream=None, splits=0, window=None):
@@ -1498,7 +1363,7 @@ class SpeckvKVConnector:
         what is their own (add_request, append / commit); a prefix is an ordinary request too, and nothing binds them -- the call
         names it: prefix_ids[b] = the request whose first prefix_lens[b] stored positions member b sees in front of its own, or None.
         prefix_lens[b] defaults to the prefix's length, which must then be even (an odd last position is held outside the pool and
-        cannot be shared: pass prefix_lens and keep that position in the member); a given one is even, >= 0 and at most the
+        cannot be shared: pass prefix_lens, keeping that position in the member); a given one is even, >= 0 and at most the
         prefix's length rounded down to even.  Members of one prefix may see different lengths of it and need not be adjacent
         (shared_groups; q and the result are permuted only when they are not).
         The step: the members' own attention exactly as attend() issues it (plan, tails, the K pre-scale), with the log-sum-exp kept,
@@ -1526,51 +1391,7 @@ class SpeckvKVConnector:
         Anything malformed is a ValueError / KeyError before any library call: an unknown prefix, a prefix among the members, lists
         of the wrong length, bools or non-integers, a window that is not None or an int >= 1, a pool that is not FP8 / INT4 /
         MXFP4; a q that is no torch tensor is a TypeError."""
-        import numpy as np
-        import torch
-        W = self._shared_window(window)
-        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_shared", window)
-        self._shared_tensors("attend_shared", q=q)
-        if len(q.shape) != 4 or q.shape[0] != len(req_ids):
-            raise ValueError("q must be [batch][heads][g][dim]")
-        if plan is None:
-            return self.attend(layer, req_ids, q, sm_scale, stream, window)
-        order, req_ids, handles, first, lens = plan
-        G = int(q.shape[2])
-        if G not in (1, 2, 4, 8, 16):
-            raise ValueError("attend_shared() takes 1, 2, 4, 8 or 16 query rows per kv head")
-        B = len(req_ids)
-        if order is not None:                                     # the gather runs on the stream the launches go to, as they do
-            with self._On(self, stream) as st, torch.cuda.stream(st):
-                idx, inv = self._shared_permutation(order)
-                q = q.index_select(0, idx)
-            if stream is not None:                                # attend's body scales q on torch's current stream: behind the gather
-                torch.cuda.current_stream().wait_stream(stream)
-        out, lse, qs = self._attend_layers_lse(layer, 1, req_ids, q[None], sm_scale, stream, window)
-        with self._On(self, stream) as st:
-            if W:
-                own = np.asarray([self.requests[r].length for r in req_ids], dtype=np.uint32)
-                self.lib.attend_prefix_fold_window(handles, first, layer, qs.data_ptr(), 1, G, lens, np.ones(B, dtype=np.uint32), own, 0, W,
-                                                   int(splits), sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
-            else:
-                self.lib.attend_prefix_fold(handles, first, layer, qs.data_ptr(), 1, G, lens, np.ones(B, dtype=np.uint32), int(splits), sm_scale,
-                                            out.data_ptr(), lse.data_ptr(), st.cuda_stream)
-            out = out[0]
-            if order is not None:                                 # and so does the way back: behind the fold, on its stream
-                with torch.cuda.stream(st):
-                    out = out.index_select(0, inv)
-        return out
-
-    @staticmethod
-    def _shared_permutation(order):
-        """(idx, inv) on the device, made on torch's current stream: x.index_select(0, idx) is x in the grouped order,
-        y.index_select(0, inv) is y back in the caller's"""
-        import torch
-        inv = [0] * len(order)
-        for at, b in enumerate(order):
-            inv[b] = at
-        both = torch.tensor([order, inv], dtype=torch.int64).pin_memory().to("cuda", non_blocking=True)
-        return both[0], both[1]
+        return self._decode_shared(layer, req_ids, prefix_ids, q, sm_scale, prefix_lens, stream, splits, window)
 
     def attend_chunk_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, k_new, v_new, sm_scale: float,
                             n_new=None, prefix_lens=None, stream=None, splits=0, window=None, parents=None):
@@ -1611,54 +1432,6 @@ class SpeckvKVConnector:
             raise ValueError("parents: ints, or one list of ints per request")
         return self._chunk_shared(layer, req_ids, prefix_ids, q, k_new, v_new, sm_scale, n_new, prefix_lens, stream, splits, window, parents,
                                   True, "attend_tree_shared")
-
-    def _chunk_shared(self, layer, req_ids, prefix_ids, q, k_new, v_new, sm_scale, n_new, prefix_lens, stream, splits, window, parents, by_depth,
-                      what):
-        """attend_chunk_shared's and attend_tree_shared's body: by_depth = a tree whose window, if any, goes by a node's depth"""
-        import numpy as np
-        import torch
-        W = self._shared_window(window)
-        by_depth = by_depth and W != 0                            # a tree without a window is the masked chunk
-        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, what, window)
-        self._shared_tensors(what, q=q, k_new=k_new, v_new=v_new)
-        if plan is None:
-            return self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, 1, window, by_depth)
-        order, req_ids, handles, first, lens = plan
-        if order is not None:
-            if n_new is not None:
-                if len(n_new) != len(order):
-                    raise ValueError("n_new: one count 0..S per request")
-                n_new = [n_new[b] for b in order]
-            if parents is not None:
-                parents = list(parents)
-                if parents and not isinstance(parents[0], numbers.Integral):          # one tree per request: in the members' order
-                    if len(parents) != len(order):
-                        raise ValueError("parents: one tree per request, or one tree for all")
-                    parents = [parents[b] for b in order]
-            with self._On(self, stream) as st, torch.cuda.stream(st):     # the gather runs on the stream the launches go to
-                idx, inv = self._shared_permutation(order)
-                q, k_new, v_new = q.index_select(0, idx), k_new.index_select(0, idx), v_new.index_select(0, idx)
-        out, lse, qs = self._chunk_step(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, parents, 1, window, by_depth, keep_lse=True)
-        B, S, _, R, _ = (int(x) for x in qs.shape)
-        live = [S] * B if n_new is None else [int(n) for n in n_new]
-        if any(live) or order is not None:
-            with self._On(self, stream) as st:
-                if any(live) and W:
-                    key, reqs, _ = self._batch(req_ids)
-                    depths = 0
-                    if by_depth:                                  # the table the own call has just read (kept per tree and window)
-                        with torch.cuda.stream(st):
-                            depths = self._chunk_tree_window_table(key, reqs, parents, live, S, W)[1].data_ptr()
-                    self.lib.attend_prefix_fold_window(handles, first, layer, qs.data_ptr(), S, R, lens, np.asarray(live, dtype=np.uint32),
-                                                       np.asarray([r.length + 1 for r in reqs], dtype=np.uint32), depths, W, int(splits),
-                                                       sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
-                elif any(live):
-                    self.lib.attend_prefix_fold(handles, first, layer, qs.data_ptr(), S, R, lens, np.asarray(live, dtype=np.uint32), int(splits),
-                                                sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
-                if order is not None:                             # the way back: behind the fold, on its stream
-                    with torch.cuda.stream(st):
-                        out = out.index_select(0, inv)
-        return out
 
     def _tree_table(self, key, reqs, parents, n_new, n_layers, S):
         """The mask words of a tree step on the device, int32 [n_layers * batch][S] (every layer the same words), kept per
@@ -2039,5 +1812,5 @@ class SpeckvKVConnector:
                     self._arg_key = self._plan_stream = None
             except SpeckvError as e:
                 self._arg_key = self._plan_stream = None
-                if e.status != -4:                             # SPECKV_ERR_INVAL: the stream cannot take the plan now; attend() plans again
+                if e.status != -4:                             # SPECKV_ERR_INVAL: the stream refuses the plan now; attend() plans again
                     raise

@@ -23,14 +23,18 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
                                         that reads the prefix's FP8 keys and MXFP4 values once per 64 query rows and folds them in
   commit                                the accepted prefix of a step into the pool: one speckv_ext_write_pairs per allocation
 
+The bodies of attend_shared and attend_chunk_shared, the judgement of their lists (_shared_args, _shared_judge) and the judging half
+of attend_chunk (_chunk_judge, _chunk_rows) are SharedPrefixSteps' (kv_shared.py), the same code SpeckvKVConnector runs; what is this
+class's own there is the (K, V) handle arrays of a prefix, its decode and chunk step, the fold entry and the depth table.
+
 Not in this class: the planned and captured decode route (plan_step, HIP graphs: attend stages its descriptors
 per call), multi-position steps on the decode kernel (attend_spec), load_paged / store_paged, fork, truncate, begin_step and the
 K pre-scale; a shared prefix is one level deep and one layer per call."""
-import numbers
 from typing import Dict, Optional, Sequence
 
 from . import kv_connector as _kc
-from .kv_connector import SpeckvKVConnector, _is_int
+from .kv_connector import SpeckvKVConnector
+from .kv_shared import SharedPrefixSteps, _is_int, tail_index
 from .speckv_ctypes import SpeckvLib
 
 K_SCHEME, V_SCHEME = 4, 5                # SPECKV_COMP_FP8_E4M3, SPECKV_COMP_MXFP4
@@ -44,8 +48,10 @@ class _SplitRequest:
         self.k_handle, self.v_handle, self.length, self.tail_k, self.tail_v = k_handle, v_handle, 0, None, None
 
 
-class SpeckvSplitKVConnector:
+class SpeckvSplitKVConnector(SharedPrefixSteps):
     _On = SpeckvKVConnector._On          # the stream rule of the connector: torch's NULL stream goes through a side stream
+    chunk_blocks = staticmethod(SpeckvKVConnector.chunk_blocks)
+    _chunk_tree_parents = staticmethod(SpeckvKVConnector._chunk_tree_parents)
 
     def __init__(self, lib: SpeckvLib, num_layers: int, num_kv_heads: int = 8, head_dim: int = 128, max_tokens: int = 4096):
         if num_kv_heads * head_dim * 2 != 2048:
@@ -126,15 +132,10 @@ class SpeckvSplitKVConnector:
     # ------------------------------------------------------------------ attention
     def _step_tails(self, req_ids, reqs):
         """(tail_idx int32 [batch], K rows, V rows [n][layers][heads][dim] or None) of the requests with an odd length, once per step"""
-        import numpy as np
         import torch
         key = (tuple(req_ids), self._epoch)
         if self._tails[0] != key:
-            tail_idx, rank = np.full(len(reqs), -1, dtype=np.int32), 0
-            for b, r in enumerate(reqs):
-                if r.length & 1:
-                    tail_idx[b] = rank
-                    rank += 1
+            tail_idx, _ = tail_index(reqs)
             odd = [r for r in reqs if r.length & 1]
             tk = torch.stack([r.tail_k for r in odd]).contiguous() if odd else None
             tv = torch.stack([r.tail_v for r in odd]).contiguous() if odd else None
@@ -233,43 +234,14 @@ class SpeckvSplitKVConnector:
         import numpy as np
         import torch
         window = SpeckvKVConnector._chunk_window(window)
-        if not _is_int(splits) or not 0 <= splits <= 64:
-            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
-        if len(q.shape) != 5:
-            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim]")
-        B, S, H, R, D = (int(x) for x in q.shape)
-        want = (B, S, self.L, self.H, self.D)
-        if (H, D) != (self.H, self.D) or tuple(k_new.shape) != want or tuple(v_new.shape) != want or B != len(req_ids) or S < 1:
-            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim], k_new / v_new [batch][S][layers][heads][dim], S >= 1")
-        if not 0 <= layer < self.L:
-            raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
-        if n_new is None:
-            live = [S] * B
-        else:
-            live = [int(n) for n in n_new]
-            if len(live) != B or not all(0 <= n <= S for n in live):
-                raise ValueError("n_new: one count 0..S per request")
-        counts, _ = SpeckvKVConnector.chunk_blocks(live, R)
-        reqs = [self.requests[r] for r in req_ids]
-        for r, n in zip(reqs, live):
-            if r.length + n > self.T:
-                raise ValueError(f"a request of {r.length} positions cannot take {n} more: max_tokens is {self.T}")
-        if parents is not None:
-            trees = SpeckvKVConnector._chunk_tree_parents(parents, B)     # judged in front of any library call
-            if trees and len(trees[0]) != S:
-                raise ValueError("parents: one entry per new position")
-        out = (torch.empty if n_new is None and parents is None else torch.zeros)((B, S, H, R, D), dtype=torch.float32, device="cuda")
-        lse = torch.full((B, S, H, R), float("-inf"), dtype=torch.float32, device="cuda") if keep_lse else None
-        if not any(counts):
+        reqs, live, (S, R), out, lse, some = self._chunk_judge(layer, req_ids, q, k_new, v_new, n_new, splits, parents, keep_lse)
+        if not some:
             return (out, lse, q.contiguous()) if keep_lse else out
         row = self.H * self.D
         with self._On(self, stream) as st:
             with torch.cuda.stream(st):
                 q = q.contiguous()
-                in_place = lambda t: (t.stride(4) == 1 and t.stride(3) == self.D and t.stride(2) % 8 == 0 and t.stride(1) % 8 == 0 and
-                                      t.stride(1) >= row and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0)
-                if not (in_place(k_new) and in_place(v_new) and k_new.stride() == v_new.stride()):
-                    k_new, v_new = k_new.contiguous(), v_new.contiguous()
+                k_new, v_new = self._chunk_rows(k_new, v_new)
                 tail_idx, tk, tv = self._step_tails(req_ids, reqs)
                 masks, depths = (None, None) if parents is None else self._step_tree(req_ids, reqs, parents, live, S, window)
             self.lib.attend_chunk_kv(np.asarray([r.k_handle for r in reqs], dtype=np.uint64), np.asarray([r.v_handle for r in reqs], dtype=np.uint64),
@@ -283,70 +255,30 @@ class SpeckvSplitKVConnector:
         return (out, lse, q) if keep_lse else out
 
     # ------------------------------------------------------------------ a prefix shared by several requests
-    shared_groups = staticmethod(SpeckvKVConnector.shared_groups)
-    _shared_permutation = staticmethod(SpeckvKVConnector._shared_permutation)
-
-    def _shared_args(self, req_ids, prefix_ids, prefix_lens, splits, what, window=None):
-        """The shared-prefix arguments of a call, judged in front of any library call and kept for the other layers of the step, keyed as
-        SpeckvKVConnector._shared_args keys them: by the lists (values AND types: True == 1), the window (value and type, judged in
-        front of it) and `_epoch`.  None when no member sees a prefix; otherwise (order or None when the batch is laid out already, the
-        members in that order, the groups' K handles, their V handles, first_member and the members' prefix lengths in that order as
-        the arrays the entry takes).  Every method that changes a request's length or handle, or the set of requests, moves `_epoch`
-        (add_request, free_request, write_prefill, commit do) -- a new state-changing method must move it too."""
+    # (the bodies are SharedPrefixSteps': this connector's side of them, then the two methods)
+    def _prefix_handles(self, prefix_ids):
         import numpy as np
-        key = (what, self._epoch, tuple(req_ids), tuple(prefix_ids), tuple(map(type, prefix_ids)), type(splits), splits,
-               None if prefix_lens is None else (tuple(prefix_lens), tuple(map(type, prefix_lens))), type(window), window)
-        if self._shared_key == key:
-            return self._shared_plan
-        plan = self._shared_judge(req_ids, prefix_ids, prefix_lens, splits)
-        if plan is not None:
-            order, prefixes, first, lens = plan
-            if order is not None:
-                req_ids, lens = [req_ids[b] for b in order], [lens[b] for b in order]
-            plan = (order, list(req_ids), np.asarray([self.requests[p].k_handle for p in prefixes], dtype=np.uint64),
-                    np.asarray([self.requests[p].v_handle for p in prefixes], dtype=np.uint64), np.asarray(first, dtype=np.uint32),
-                    np.asarray(lens, dtype=np.uint32))
-        self._shared_key, self._shared_plan = key, plan
-        return plan
+        return (np.asarray([self.requests[p].k_handle for p in prefix_ids], dtype=np.uint64),
+                np.asarray([self.requests[p].v_handle for p in prefix_ids], dtype=np.uint64))
 
-    def _shared_judge(self, req_ids, prefix_ids, prefix_lens, splits):
-        """SpeckvKVConnector._shared_judge restated over split requests: (order or None, the groups' prefix ids, first_member, the
-        members' prefix lengths in the CALLER's order) -- or None when no member sees a prefix"""
-        B = len(req_ids)
-        if len(prefix_ids) != B or (prefix_lens is not None and len(prefix_lens) != B):
-            raise ValueError("prefix_ids (and prefix_lens): one entry per request")
-        if not _is_int(splits) or not 0 <= splits <= 64:
-            raise ValueError("splits must be 0 (the library's rule), 1 (no pieces) or a forced piece count 2..64")
-        for r in req_ids:
-            self.requests[r]                                              # KeyError: an unknown member
-        members, lens = set(req_ids), []
-        for b, p in enumerate(prefix_ids):
-            if p is None:
-                if prefix_lens is not None and prefix_lens[b] is not None and (not _is_int(prefix_lens[b]) or prefix_lens[b] != 0):
-                    raise ValueError("prefix_lens: a member without a prefix takes 0 or None")
-                lens.append(0)
-                continue
-            if not _is_int(p):
-                raise ValueError("prefix_ids: request ids (ints) or None")
-            if p not in self.requests:
-                raise KeyError(f"prefix request {p} does not exist")
-            if p in members:
-                raise ValueError(f"request {p} is a member of the call and cannot be its prefix")
-            have = self.requests[p].length
-            if prefix_lens is None or prefix_lens[b] is None:
-                if have & 1:
-                    raise ValueError(f"prefix request {p} holds an odd number of positions ({have}): pass prefix_lens and keep the "
-                                     "last position in the member (only whole stored pairs can be shared)")
-                lens.append(have)
-            else:
-                n = prefix_lens[b]
-                if not _is_int(n) or n < 0 or n & 1 or n > (have & ~1):
-                    raise ValueError(f"prefix_lens: even ints in 0..{have & ~1} for prefix request {p}")
-                lens.append(int(n))
-        if not any(lens):
-            return None
-        order, prefixes, first = self.shared_groups(req_ids, prefix_ids)
-        return (None if order == list(range(B)) else order, prefixes, first, lens)
+    def _own_decode(self, layer, req_ids, q, sm_scale, stream, window, gathered):
+        return self._attend_own(layer, req_ids, q, sm_scale, stream, window)
+
+    def _own_chunk(self, layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, window, parents, by_depth, keep_lse=False):
+        if not keep_lse:
+            return self.attend_chunk(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, 1, window, parents)
+        return self._chunk_own(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, 1, window, parents, keep_lse=True)
+
+    def _prefix_fold(self, handles, first, layer, req_ids, ahead, d_q, C, R, lens, n_q, depths, W, splits, sm_scale, d_out, d_lse, cuda_stream):
+        """own_seen = length + ahead (0: a decode step, whose position is held already; 1: a chunk step), with and without a window"""
+        import numpy as np
+        own = np.asarray([self.requests[r].length for r in req_ids], dtype=np.uint32)
+        if ahead:
+            own += np.uint32(ahead)
+        self.lib.attend_prefix_fold_kv(*handles, first, layer, d_q, C, R, lens, n_q, own, depths, W, splits, sm_scale, d_out, d_lse, cuda_stream)
+
+    def _depth_table(self, req_ids, parents, live, S, W):
+        return self._step_tree(req_ids, self._reqs(req_ids), parents, live, S, W)[1].data_ptr()
 
     def attend_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, sm_scale: float, prefix_lens=None,
                       stream=None, splits=0, window=None):
@@ -368,33 +300,7 @@ class SpeckvSplitKVConnector:
         lengths 0): attend()'s launches and bits.  The pool holds the prefix once: (members - 1) x prefix pairs x 3136 bytes per layer
         less than members that each hold a copy.
         Anything malformed is a ValueError / KeyError before any library call; a q that is no torch tensor is a TypeError."""
-        import numpy as np
-        import torch
-        W = SpeckvKVConnector._shared_window(window)
-        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_shared", window)
-        SpeckvKVConnector._shared_tensors("attend_shared", q=q)
-        if len(q.shape) != 4 or q.shape[0] != len(req_ids):
-            raise ValueError("q must be [batch][heads][g][dim]")
-        if plan is None:
-            return self.attend(layer, req_ids, q, sm_scale, stream, window)
-        order, req_ids, k_handles, v_handles, first, lens = plan
-        G = int(q.shape[2])
-        if G not in (1, 2, 4, 8, 16):
-            raise ValueError("attend_shared() takes 1, 2, 4, 8 or 16 query rows per kv head")
-        B = len(req_ids)
-        if order is not None:                                     # the gather runs on the stream the launches go to, as they do
-            with self._On(self, stream) as st, torch.cuda.stream(st):
-                idx, inv = self._shared_permutation(order)
-                q = q.index_select(0, idx)
-        out, lse, qs = self._attend_own(layer, req_ids, q, sm_scale, stream, window)
-        with self._On(self, stream) as st:
-            own = np.asarray([self.requests[r].length for r in req_ids], dtype=np.uint32)
-            self.lib.attend_prefix_fold_kv(k_handles, v_handles, first, layer, qs.data_ptr(), 1, G, lens, np.ones(B, dtype=np.uint32), own, 0, W,
-                                           int(splits), sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
-            if order is not None:                                 # the way back: behind the fold, on its stream
-                with torch.cuda.stream(st):
-                    out = out.index_select(0, inv)
-        return out
+        return self._decode_shared(layer, req_ids, prefix_ids, q, sm_scale, prefix_lens, stream, splits, window)
 
     def attend_chunk_shared(self, layer: int, req_ids: Sequence[int], prefix_ids: Sequence[Optional[int]], q, k_new, v_new, sm_scale: float,
                             n_new=None, prefix_lens=None, stream=None, splits=0, window=None, parents=None):
@@ -410,46 +316,8 @@ class SpeckvSplitKVConnector:
         node j of depth d sees from max(0, prefix_lens[b] + length + 1 + d - W) on -- so this one method is the tree step of a local
         layer too.  Changes no state: commit() stores the accepted positions in the MEMBER afterwards.  No member with a prefix:
         attend_chunk(splits=1)'s launch and bits."""
-        import numpy as np
-        import torch
-        W = SpeckvKVConnector._shared_window(window)
-        plan = self._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_chunk_shared", window)
-        SpeckvKVConnector._shared_tensors("attend_chunk_shared", q=q, k_new=k_new, v_new=v_new)
-        if plan is None:
-            return self.attend_chunk(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, 1, window, parents)
-        order, req_ids, k_handles, v_handles, first, lens = plan
-        if order is not None:
-            if n_new is not None:
-                if len(n_new) != len(order):
-                    raise ValueError("n_new: one count 0..S per request")
-                n_new = [n_new[b] for b in order]
-            if parents is not None:
-                parents = list(parents)
-                if parents and not isinstance(parents[0], numbers.Integral):          # one tree per request: in the members' order
-                    if len(parents) != len(order):
-                        raise ValueError("parents: one tree per request, or one tree for all")
-                    parents = [parents[b] for b in order]
-            with self._On(self, stream) as st, torch.cuda.stream(st):     # the gather runs on the stream the launches go to
-                idx, inv = self._shared_permutation(order)
-                q, k_new, v_new = q.index_select(0, idx), k_new.index_select(0, idx), v_new.index_select(0, idx)
-        out, lse, qs = self._chunk_own(layer, req_ids, q, k_new, v_new, sm_scale, n_new, stream, 1, window, parents, keep_lse=True)
-        B, S, _, R, _ = (int(x) for x in qs.shape)
-        live = [S] * B if n_new is None else [int(n) for n in n_new]
-        if any(live) or order is not None:
-            with self._On(self, stream) as st:
-                if any(live):
-                    reqs = [self.requests[r] for r in req_ids]
-                    depths = 0
-                    if W and parents is not None:                 # the table the own call has just read (kept per tree and window)
-                        with torch.cuda.stream(st):
-                            depths = self._step_tree(req_ids, reqs, parents, live, S, W)[1].data_ptr()
-                    self.lib.attend_prefix_fold_kv(k_handles, v_handles, first, layer, qs.data_ptr(), S, R, lens, np.asarray(live, dtype=np.uint32),
-                                                   np.asarray([r.length + 1 for r in reqs], dtype=np.uint32), depths, W, int(splits), sm_scale,
-                                                   out.data_ptr(), lse.data_ptr(), st.cuda_stream)
-                if order is not None:                             # the way back: behind the fold, on its stream
-                    with torch.cuda.stream(st):
-                        out = out.index_select(0, inv)
-        return out
+        return self._chunk_shared(layer, req_ids, prefix_ids, q, k_new, v_new, sm_scale, n_new, prefix_lens, stream, splits, window, parents,
+                                  parents is not None, "attend_chunk_shared")
 
     # ------------------------------------------------------------------ commit
     def commit(self, req_ids: Sequence[int], k_new, v_new, n_accept: Sequence[int], stream=None):

@@ -206,6 +206,80 @@ def test_without_a_prefix_the_calls_reach_attend_and_attend_chunk_only():
                     ("attend_chunk", (1, [1, 2], qc, new, new, 0.1, [3, 1], "s", 1, 40, [-1, 0, 0]))]
 
 
+def test_both_connectors_judge_a_shared_prefix_call_alike():
+    """_shared_args of SpeckvKVConnector and of SpeckvSplitKVConnector over the same ids and lengths, 400 seeded calls: members in
+    scattered order, None prefixes, given and absent prefix_lens, odd prefix lengths, unknown ids, bools / floats / strings in every
+    list, bad splits and windows.  Both raise the same exception type with the same message, or return plans that agree on the
+    order, the members, first_member and the lengths; an identical second call returns the kept plan object, and one behind a move
+    of _epoch does not."""
+    import random
+    from cxl_speckv_amd.kv_connector import SpeckvKVConnector, _Request
+    lengths = ((1, 0), (2, 5), (3, 6), (4, 33), (50, 64), (51, 37), (52, 128))
+    split = _connector(lengths)
+    fp8 = SpeckvKVConnector(_NoLib(), num_layers=2, max_tokens=256, scheme="fp8")
+    for rid, n in lengths:
+        fp8.requests[rid] = _Request(1000 + rid)
+        fp8.requests[rid].length = n
+    have = dict(lengths)
+
+    def judged(conn, args):
+        req_ids, prefix_ids, prefix_lens, splits, window = args
+        try:
+            SpeckvKVConnector._shared_window(window)                      # as the methods of both do, in front of the lists
+            return None, conn._shared_args(req_ids, prefix_ids, prefix_lens, splits, "attend_shared", window)
+        except (ValueError, KeyError, TypeError) as e:
+            return (type(e), str(e)), None
+
+    rng = random.Random(20261021)
+    junk = (True, False, 2.0, 1.5, "2", np.int64(2), np.bool_(True))
+    plans = raised = permuted = 0
+    for _ in range(400):
+        req_ids = rng.sample([1, 2, 3, 4], rng.randint(1, 4))
+        prefix_ids = [rng.choice([None, 50, 50, 51, 52]) for _ in req_ids]
+        prefix_lens = None
+        if rng.random() < 0.6:
+            prefix_lens = [None if p is None or rng.random() < 0.2 else rng.randrange(0, have[p] + 1, 2) for p in prefix_ids]
+        splits, window = rng.choice([0, 0, 1, 5, 64]), rng.choice([None, None, 1, 40, 300])
+        roll = rng.random()
+        if roll < 0.08:
+            prefix_ids[rng.randrange(len(prefix_ids))] = rng.choice(junk + (99, req_ids[0], [50]))
+        elif roll < 0.16 and prefix_lens is not None:
+            prefix_lens[rng.randrange(len(prefix_lens))] = rng.choice(junk + (-2, 3, 37, 130, 0))
+        elif roll < 0.22:
+            req_ids[rng.randrange(len(req_ids))] = rng.choice((98, 50, True, 2.0))
+        elif roll < 0.28:
+            splits = rng.choice((-1, 65, True, 1.5, "1", None))
+        elif roll < 0.34:
+            window = rng.choice((0, -3, True, 1.5, "64", 2 ** 32))
+        elif roll < 0.38:
+            prefix_ids = prefix_ids[:-1]
+        elif roll < 0.42 and prefix_lens is not None:
+            prefix_lens = prefix_lens + [0]
+        args = (req_ids, prefix_ids, prefix_lens, splits, window)
+        (err_a, plan_a), (err_b, plan_b) = judged(fp8, args), judged(split, args)
+        assert err_a == err_b, (args, err_a, err_b)
+        if err_a is not None:
+            raised += 1
+            continue
+        assert (plan_a is None) == (plan_b is None), args
+        for conn, plan in ((fp8, plan_a), (split, plan_b)):
+            assert judged(conn, args)[1] is plan                         # the kept plan of the step
+        if plan_a is None:
+            continue
+        plans += 1
+        permuted += plan_a[0] is not None
+        assert plan_a[0] == plan_b[0] and plan_a[1] == plan_b[1], args    # the order, the members in it
+        for a, b in ((plan_a[-2], plan_b[-2]), (plan_a[-1], plan_b[-1])):                 # first_member, the lengths
+            assert a.dtype == b.dtype == np.uint32 and np.array_equal(a, b), args
+        order = plan_a[0] if plan_a[0] is not None else list(range(len(req_ids)))
+        assert plan_a[1] == [req_ids[b] for b in order]
+        for conn, plan in ((fp8, plan_a), (split, plan_b)):
+            conn._epoch += 1
+            again = judged(conn, args)[1]
+            assert again is not plan and again[1] == plan[1] and np.array_equal(again[-1], plan[-1])
+    assert plans >= 100 and raised >= 60 and permuted >= 30, (plans, raised, permuted)     # the matrix reaches every kind of call
+
+
 # ----------------------------------------------------------------------------- the float64 emulation
 def _ceil(a, b):
     return -(-a // b)
