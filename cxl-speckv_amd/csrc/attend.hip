@@ -958,6 +958,7 @@ __global__ __launch_bounds__(512) void k_attend_combine(const float* __restrict_
     if (seqs) {
         const AttendSeq sq = seqs[rowq / heads];
         if (skip_single && sq.n_splits == 1u) return;        // written by the attention kernel itself (workgroup-uniform)
+        if (skip_single == 2u && sq.n_splits == 0u) return;  // ... and so is a sequence with nothing stored (the held rows of a multi-position step)
         n_splits = sq.n_splits;
         part0 = sq.part_base + static_cast<uint64_t>(rowq % heads) * n_splits;
     }
@@ -1034,6 +1035,7 @@ __global__ __launch_bounds__(256) void k_attend_combine_small(const float* __res
     if (seqs) {
         const AttendSeq sq = seqs[rowq / heads];
         if (skip_single && sq.n_splits == 1u) return;
+        if (skip_single == 2u && sq.n_splits == 0u) return;
         n_splits = sq.n_splits;
         part0 = sq.part_base + static_cast<uint64_t>(rowq % heads) * n_splits;
     }
@@ -1177,18 +1179,20 @@ hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* 
     const uint32_t splits = a.stream.n_wgs ? a.stream.max_slots : a.n_splits;      // most partials a row can have
     const uint32_t n_tiles = a.stream.tiles ? a.stream.tiles : (a.n_pages + 15u) / 16u;
     if (splits > kMaxSplits) return hipErrorInvalidValue;
+    // rows the attention kernel wrote itself: none, those of sequences with one split, or (direct_per_seq == 3) those of sequences without a split as well
+    const uint32_t skip_single = (a.direct_out && a.direct_per_seq) ? (a.direct_per_seq == 3u ? 2u : 1u) : 0u;
     if (splits <= kSmallCombineSplits) {
         const uint32_t n_rows = n_layers * a.heads;
         if (n_rows <= kSmallCombineRowsShared)
             hipLaunchKernelGGL(k_attend_combine_small<4>, dim3(n_rows), dim3(256), 0, s, a.part_acc, a.part_ml, a.g,
-                               a.n_splits, d_out, d_lse, a.seqs, a.heads, (a.direct_out && a.direct_per_seq) ? 1u : 0u, n_rows, a.stream, n_tiles);
+                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles);
         else
             hipLaunchKernelGGL(k_attend_combine_small<1>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, a.part_acc, a.part_ml, a.g,
-                               a.n_splits, d_out, d_lse, a.seqs, a.heads, (a.direct_out && a.direct_per_seq) ? 1u : 0u, n_rows, a.stream, n_tiles);
+                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_attend_combine, dim3(n_layers * a.heads * a.g), dim3(512), 0, s, a.part_acc, a.part_ml, a.g,
-                       a.n_splits, d_out, d_lse, a.seqs, a.heads, (a.direct_out && a.direct_per_seq) ? 1u : 0u, a.stream, n_tiles);
+                       a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, a.stream, n_tiles);
     return hipGetLastError();
 }
 

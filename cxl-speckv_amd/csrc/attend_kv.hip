@@ -1,6 +1,7 @@
 // cxl-speckv_amd/csrc/attend_kv.hip -- batch decode attention straight from the records of the SPLIT POOL ("K8V4"): a sequence's K rows
 // in an FP8_E4M3 allocation, its V rows in an MXFP4 allocation (kv_split_connector.py).  One new position per sequence
-// (g query rows per kv head), no fp16 K or V is materialised.
+// (g query rows per kv head), no fp16 K or V is materialised.  The HELD instance serves a step of SEVERAL new positions per sequence (draft
+// positions to verify): the same walk for g = positions x rows per position, the rows held outside the pool folded in by split 0.
 //
 // The workgroup shape and the K side are k_attend_fp8_linear<false>'s (attend.hip): one wave = one kv head of one sequence over one
 // contiguous split of its positions, tiles of 32 positions (16 pages), four waves = four heads of the same split; grid (splits,
@@ -27,6 +28,71 @@
 
 namespace speckv {
 
+constexpr uint32_t kHeldMax = 17;                      // SPECKV_HELD_MAX (include/speckv_ext.h)
+
+// The held positions of a step (k_attend_k8v4<false, true>), folded into the running state of query row c by the wave of split 0.
+// 64 bytes of a held row: channels 32kb .. 32kb + 31 of kv head `head`
+struct HeldPiece { uint4 w[4]; };
+__device__ __forceinline__ HeldPiece held_piece(const uint16_t* rows, uint64_t at)
+{
+    HeldPiece p;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) p.w[i] = ldg16_temporal(reinterpret_cast<const uint8_t*>(rows + at) + 16 * i);
+    return p;
+}
+__device__ __forceinline__ float held_f16(uint32_t w, int hi) { return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w >> (16 * hi)))); }
+
+__device__ __forceinline__ void k8v4_fold_held(const AttendArgs& a, const AttendHeldArgs& h, uint32_t seq, uint32_t head, uint64_t row, uint32_t c, uint32_t kb,
+                                               float& m_run, float& l_run, f32x4 (&acc)[8])
+{
+    // the word of the lane's query position; a lane without a query row sees nothing
+    uint32_t word = 0u;
+    if (c < a.g) word = *SPECKV_GP(uint32_t, h.mask + static_cast<uint64_t>(seq) * h.mask_stride + c / h.rows_per_pos) & ((1u << kHeldMax) - 1u);
+    uint32_t n_held = 0u;                                                // 1 + the highest bit set in any word of the sequence (wave-uniform)
+#pragma unroll
+    for (uint32_t t = 0; t < kHeldMax; ++t)
+        if (__builtin_amdgcn_ballot_w64((word >> t) & 1u) != 0ull) n_held = t + 1u;
+    if (n_held == 0u) return;
+    const uint64_t at0 = static_cast<uint64_t>(seq) * h.seq_stride + head * 128u + 32u * kb;
+    // K two positions deep, V one: the next K row is requested in front of the score, the next V row behind the accumulation
+    HeldPiece kn = held_piece(h.k_held, at0), vx = held_piece(h.v_held, at0);
+    const HeldPiece q = held_piece(a.q16, (row * a.g + min(c, a.g - 1u)) * 128u + 32u * kb);
+#pragma unroll 1
+    for (uint32_t t = 0; t < n_held; ++t) {
+        const HeldPiece kx = kn;
+        const bool more = t + 1u < n_held;                                // scalar: nothing above the highest visible position is read
+        const uint64_t at = at0 + static_cast<uint64_t>(t + 1u) * h.pos_stride;
+        if (more) kn = held_piece(h.k_held, at);
+        const bool sees = (word >> t) & 1u;
+        float dot = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t qw[4] = {q.w[i].x, q.w[i].y, q.w[i].z, q.w[i].w}, kw[4] = {kx.w[i].x, kx.w[i].y, kx.w[i].z, kx.w[i].w};
+            // v_dot2_f32_f16 on the words as they were loaded: a query widened to 32 floats would not fit beside the accumulators
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dot = __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, qw[e]), __builtin_bit_cast(f16x2, kw[e]), dot, false);
+        }
+        const float s = sees ? sum_over_kb(dot) * a.scale_log2e : -INFINITY;
+        // the loop's online-softmax step over this one position
+        const float m_new = fmaxf(m_run, s);
+        const float m_use = (m_new == -INFINITY) ? 0.0f : m_new;
+        const float f = __builtin_amdgcn_exp2f(m_run - m_use);
+        const float p = __builtin_amdgcn_exp2f(s - m_use);
+        m_run = m_new;
+        l_run = l_run * f + (kb == 0u ? p : 0.0f);                        // (att_store_rows8 sums l_run over kb: the weight enters one lane)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t vw[4] = {vx.w[i].x, vx.w[i].y, vx.w[i].z, vx.w[i].w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float pv = p * held_f16(vw[e >> 1], e & 1);
+                acc[e][i] = acc[e][i] * f + (sees ? pv : 0.0f);
+            }
+        }
+        if (more) vx = held_piece(h.v_held, at);
+    }
+}
+
 // a.seqs: the K side and the split bookkeeping of every sequence (lin_base, scale_tab, k_first of the K allocation; v_first and
 // layer_pages are not read); vside[sequence]: the V allocation's run and the first record of the layer's V region (a multiple of 16).
 // a.direct_out / direct_lse are always set: a sequence with ONE split is written final, one without positions as zeros / -inf, the
@@ -34,10 +100,20 @@ namespace speckv {
 // WINDOW: the launch under a sliding window (AttendArgs::seq_skip, decode_window.hpp; speckv_ext_attend_kv_batch_window) -- the descriptors
 // start at the tile of the window's lower bound, seq_skip[sequence] = the leading POSITIONS (0..31, may be odd) of the sequence's tile 0
 // in front of it.  An instance of its own, for k_attend_fp8_linear<.., WINDOW>'s reason (attend.hip): carried by the plain instance the
-// position mask cost the unwindowed FP8 entries 3 %.  k_attend_k8v4<false> is the kernel of before, instruction for instruction.
-template <bool WINDOW>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_attend_k8v4(AttendArgs a, const AttendKvSide* __restrict__ vside)
+// position mask cost the unwindowed FP8 entries 3 %.  k_attend_k8v4<false, false> is the kernel of before, instruction for instruction.
+// HELD: the step of several positions (speckv_ext_attend_kv_spec) -- g = n_q x rows_per_pos query rows per kv head, row r of query position
+// r / rows_per_pos; every row sees every stored position, so the walk is the plain one.  Split 0 of every sequence then folds in, in front of
+// att_store_rows8, the positions the caller holds outside the pool (AttendHeldArgs: fp16 rows, one mask word per query position) with the
+// online-softmax step of the loop -- into its final rows or its partial, the merge runs as ever; a sequence with nothing stored runs that
+// epilogue alone.  The held scores take the FP16 query (the stand-alone folds' choice): the fp32 dot of the lane group's channels 32kb ..
+// 32kb + 31, summed over kb, in log2 units; a position a row does not see is -inf and its V contribution 0, both by a select.  A lane reads
+// the 64 bytes of channels 32kb .. 32kb + 31 of a held row for K and for V (acc[t][i] = channel 32kb + 8i + t: element t of the i-th 16
+// bytes), one position computed while the next one's rows are under way; the loop ends at the highest bit set in any word of the sequence
+// and no held position above that is read.  `held` is AttendHeldArgs for HELD and empty otherwise: the plain instances keep their argument block.
+template <bool WINDOW, bool HELD, class... Held>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_attend_k8v4(AttendArgs a, const AttendKvSide* __restrict__ vside, Held... held)
 {
+    static_assert(!(WINDOW && HELD) && sizeof...(Held) == (HELD ? 1 : 0), "instances: <false, false>, <true, false>, <false, true, AttendHeldArgs>");
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t c = lane & 15u, kb = lane >> 4;
@@ -50,8 +126,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const uint64_t row = static_cast<uint64_t>(seq) * a.heads + head;    // query / output row block
     const AttendSeq sq = a.seqs[seq];
     if (split >= sq.n_splits) {
-        if (sq.n_splits == 0u && split == 0u) attend_zero_rows(a.direct_out, a.direct_lse, a.g, row, lane);
-        return;
+        if constexpr (!HELD) {
+            if (sq.n_splits == 0u && split == 0u) attend_zero_rows(a.direct_out, a.direct_lse, a.g, row, lane);
+            return;
+        } else if (sq.n_splits != 0u || split != 0u) return;             // (nothing stored: split 0 goes on to the held positions alone)
     }
     const AttendKvSide vsd = vside[seq];
     const uint64_t part = sq.part_base + static_cast<uint64_t>(head) * sq.n_splits + split;
@@ -173,8 +251,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    if constexpr (HELD) {
+        if (split == 0u) k8v4_fold_held(a, held..., seq, head, row, c, kb, m_run, l_run, acc);      // workgroup-uniform
+    }
     // ---- a single split: the final rows; otherwise the partial of this split (acc is in true units here: unit 1)
-    att_store_rows8(a, acc, m_run, l_run, 1.0f, sq.n_splits == 1u, row, part, c, kb);
+    att_store_rows8(a, acc, m_run, l_run, 1.0f, HELD ? sq.n_splits <= 1u : sq.n_splits == 1u, row, part, c, kb);
 }
 
 // a.seqs / d_vside (device-visible) hold n_seq descriptors, a.n_splits = the largest per-sequence split count (0: no sequence has positions),
@@ -187,11 +268,32 @@ hipError_t launch_attend_k8v4(const AttendArgs& a, const AttendKvSide* d_vside, 
     const uint32_t rows = n_seq * (a.heads / 4u), splits = a.n_splits ? a.n_splits : 1u;      // (split 0 of a sequence without positions writes its zeros)
     ar.rows_real = rows;
     const dim3 gr = a.rows_first ? dim3(rows | 1u, splits) : dim3(splits, rows);
-    if (a.seq_skip) hipLaunchKernelGGL(k_attend_k8v4<true>, gr, dim3(256), 0, s, ar, d_vside);      // under a window that cuts a sequence
-    else hipLaunchKernelGGL(k_attend_k8v4<false>, gr, dim3(256), 0, s, ar, d_vside);
+    if (a.seq_skip) hipLaunchKernelGGL((k_attend_k8v4<true, false>), gr, dim3(256), 0, s, ar, d_vside);      // under a window that cuts a sequence
+    else hipLaunchKernelGGL((k_attend_k8v4<false, false>), gr, dim3(256), 0, s, ar, d_vside);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || !merge) return e;
     return launch_attend_combine(a, n_seq, d_out, d_lse, s);
+}
+
+// The step of several positions: the launch above with the held positions of every sequence folded in by its split 0 (k_attend_k8v4<false,
+// true>).  No instance under a window: a.seq_skip is refused.
+hipError_t launch_attend_k8v4_held(const AttendArgs& a, const AttendKvSide* d_vside, const AttendHeldArgs& h, uint32_t n_seq, bool merge, float* d_out,
+                                   float* d_lse, hipStream_t s)
+{
+    if (n_seq == 0) return hipSuccess;
+    if (!a.seqs || !d_vside || !a.q16 || a.direct_out != d_out || a.heads % 4u || a.g == 0 || a.g > 16u || a.seq_skip) return hipErrorInvalidValue;
+    if (!h.k_held || !h.v_held || !h.mask || h.rows_per_pos == 0 || a.g % h.rows_per_pos || a.g / h.rows_per_pos > kHeldMax - 1u ||
+        h.mask_stride < a.g / h.rows_per_pos || h.seq_stride % 8u || h.pos_stride % 8u)
+        return hipErrorInvalidValue;
+    AttendArgs ar = a;
+    const uint32_t rows = n_seq * (a.heads / 4u), splits = a.n_splits ? a.n_splits : 1u;      // (split 0 of a sequence without positions folds its held ones)
+    ar.rows_real = rows;
+    const dim3 gr = a.rows_first ? dim3(rows | 1u, splits) : dim3(splits, rows);
+    hipLaunchKernelGGL((k_attend_k8v4<false, true, AttendHeldArgs>), gr, dim3(256), 0, s, ar, d_vside, h);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !merge) return e;
+    ar.direct_per_seq = 3u;                                              // the merge passes over the sequences without a split too: their rows are the softmax over the held positions
+    return launch_attend_combine(ar, n_seq, d_out, d_lse, s);
 }
 
 } // namespace speckv

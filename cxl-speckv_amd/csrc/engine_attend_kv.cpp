@@ -1,5 +1,5 @@
-// cxl-speckv_amd/csrc/engine_attend_kv.cpp -- Engine::attend_batch_kv, the body behind speckv_ext_attend_kv_batch and
-// speckv_ext_attend_kv_batch_window: one decode step of a batch over the SPLIT POOL ("K8V4": a sequence's K rows in an FP8_E4M3
+// cxl-speckv_amd/csrc/engine_attend_kv.cpp -- Engine::attend_batch_kv, the body behind speckv_ext_attend_kv_batch,
+// speckv_ext_attend_kv_batch_window and speckv_ext_attend_kv_spec: one decode step of a batch over the SPLIT POOL ("K8V4": a sequence's K rows in an FP8_E4M3
 // allocation, its V rows in an MXFP4 allocation), one attention launch (k_attend_k8v4, attend_kv.hip) and, where members have several
 // pieces, the merge behind it
 #include "engine_internal.hpp"
@@ -20,10 +20,15 @@ namespace speckv {
 // of 16 records, a kernel tile stays one storage tile and one group of the scale table), the tiles, the dispatch order and the pieces are
 // those of the pages actually walked, and the leading positions of tile 0 in front of lo travel as the skip array (AttendArgs::seq_skip:
 // k_attend_k8v4<true>).  window = 0, or a window that cuts no member: the descriptors, the instance and the launches of the entry without one.
+// held (attend_spec_kv, never with a window): the step of several positions -- g = n_q x rows_per_pos query rows that all see every stored
+// position, so descriptors, geometry, pieces and slot are those of a decode step of g rows; the launch is k_attend_k8v4<false, true>, whose
+// split 0 folds the held rows of every member into its final rows or its partial (launch_attend_k8v4_held).
 int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
-                            const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos, uint32_t window)
+                            const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos, uint32_t window,
+                            const AttendHeldArgs* held)
 {
-    const char* entry = window ? "speckv_ext_attend_kv_batch_window" : "speckv_ext_attend_kv_batch";
+    const char* entry = held ? "speckv_ext_attend_kv_spec" : window ? "speckv_ext_attend_kv_batch_window" : "speckv_ext_attend_kv_batch";
+    if (held && window) return SPECKV_ERR_INVAL;
     if (null_) return no_data_path(entry);
     if (window && !q_pos) return SPECKV_ERR_INVAL;
     if (!window) q_pos = nullptr;                                        // (no window: the launches of the entry without one)
@@ -124,9 +129,25 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
     for (uint32_t i = 0; i < n_seq; ++i) { note_use(ks[i], s); note_use(vs[i], s); }      // speckv_free waits for this stream
     // The guard event is recorded on every way out from here on: the slot must not be written again under a kernel still reading it.
     SlotGuard slot_guard{seq_ring_.ev[slot], st};
-    HIP_TRY(launch_attend_k8v4(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), n_seq, merge, d_out, d_lse, st));
+    if (held) HIP_TRY(launch_attend_k8v4_held(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), *held, n_seq, merge, d_out, d_lse, st));
+    else HIP_TRY(launch_attend_k8v4(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), n_seq, merge, d_out, d_lse, st));
     if (!s) HIP_TRY(hipStreamSynchronize(stream_));
     return SPECKV_OK;
+}
+
+// speckv_ext_attend_kv_spec.  What concerns the held rows and the mask is judged first, so a bad set is SPECKV_ERR_INVAL on every engine
+// (the folds' rule: Engine::fold_held_args_ok); the rest is attend_batch_kv's.
+int Engine::attend_spec_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
+                           uint32_t rows_per_pos, const uint32_t* pos_end, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems,
+                           uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+{
+    if (rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > SPECKV_HELD_MAX - 1u) return SPECKV_ERR_INVAL;
+    if (!d_k_held || !d_v_held || !d_mask || mask_stride < g / rows_per_pos) return SPECKV_ERR_INVAL;
+    if (seq_stride_elems % 8u || pos_stride_elems % 8u || pos_stride_elems < 8u * 128u) return SPECKV_ERR_INVAL;
+    if (reinterpret_cast<uintptr_t>(d_k_held) % 16u || reinterpret_cast<uintptr_t>(d_v_held) % 16u) return SPECKV_ERR_INVAL;
+    const AttendHeldArgs held{static_cast<const uint16_t*>(d_k_held), static_cast<const uint16_t*>(d_v_held), seq_stride_elems, pos_stride_elems,
+                              d_mask, mask_stride, rows_per_pos};
+    return attend_batch_kv(n_seq, k_handles, v_handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse, s, nullptr, 0u, &held);
 }
 
 } // namespace speckv

@@ -573,7 +573,8 @@ struct AttendArgs {
     // planned batches (descriptors resident on the device, one set for all layers of a decode step): the layer of this
     // launch, and "decide per sequence": 1 = a sequence with one split is written directly, the others through the merge
     // launch that follows; 2 = the launch geometry allows one split at most, NO merge follows: sequences without
-    // positions are zeroed by the attention kernel itself (attend_zero_rows)
+    // positions are zeroed by the attention kernel itself (attend_zero_rows); 3 (to launch_attend_combine only, from launch_attend_k8v4_held) =
+    // as 1, and the rows of a sequence WITHOUT a split are the attention kernel's as well: the merge leaves them alone
     uint32_t batch_layer;
     uint32_t direct_per_seq;
     // ... and SEVERAL layers of the planned batch in one launch (speckv_ext_attend_planned_layers: callers that have the query rows of
@@ -701,6 +702,22 @@ struct AttendKvSide {
 // merge: some sequence has several splits -- launch_attend_combine follows on `s`.  a.seq_skip set: the launch under a sliding window
 // (k_attend_k8v4<true>: the descriptors start at the window's tile, seq_skip[sequence] leading positions of its tile 0 masked), else the plain instance
 hipError_t launch_attend_k8v4(const AttendArgs& a, const AttendKvSide* d_vside, uint32_t n_seq, bool merge, float* d_out, float* d_lse, hipStream_t s);
+// The step of several positions over the split pool (k_attend_k8v4<false, true>; speckv_ext_attend_kv_spec): what the caller holds outside
+// the pool, folded in by split 0 of every sequence inside the attention launch.  A struct of its own beside AttendArgs, which keeps its
+// size and layout for every other kernel.  Held position t of sequence i, kv head h: fp16 at i * seq_stride + t * pos_stride + h * 128
+// elements (both strides multiples of 8: a lane reads 16 bytes at a time); query position j = row / rows_per_pos of sequence i sees the held
+// positions whose bit is set in mask[i * mask_stride + j] (bits >= SPECKV_HELD_MAX dropped).  No held position above the highest bit set in
+// any word of a sequence is read.
+struct AttendHeldArgs {
+    const uint16_t* k_held;
+    const uint16_t* v_held;
+    uint64_t seq_stride, pos_stride;  // elements
+    const uint32_t* mask;
+    uint32_t mask_stride, rows_per_pos;
+};
+// launch_attend_k8v4 with the held positions; a.g = n_q x h.rows_per_pos.  There is no instance under a window: a.seq_skip is refused.
+hipError_t launch_attend_k8v4_held(const AttendArgs& a, const AttendKvSide* d_vside, const AttendHeldArgs& h, uint32_t n_seq, bool merge, float* d_out,
+                                   float* d_lse, hipStream_t s);
 
 // every page's record (rec_bytes rounded up to 16) copied to d_new_addr[page], then entries[page].pool_addr = d_new_addr[page]
 hipError_t launch_repack(PageEntry* d_entries, const uint64_t* d_new_addr, uint64_t n, hipStream_t s);

@@ -18,6 +18,9 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
   attend_chunk                          one layer of a step of S >= 1 new positions per request -- a prefill chunk, a draft chain or tree --
                                         causal, under a window, a tree, a tree under a window, split over the chip (S = 1 works, but a
                                         64-row query block then carries rows_per_pos live rows: attend is the decode route)
+  attend_spec                           one layer of a DRAFT step (S new positions per request, a chain or a tree) on the decode kernel: per
+                                        group of 16 // rows_per_pos positions ONE speckv_ext_attend_kv_spec -- the stored positions walked
+                                        once for up to 16 query rows per kv head, the tail and the new rows folded in inside that launch
   attend_shared / attend_chunk_shared   attend / attend_chunk for members that SHARE A PREFIX without holding a copy of it: the own part as
                                         those methods issue it with the log-sum-exp kept, then ONE speckv_ext_attend_prefix_fold_kv launch
                                         that reads the prefix's FP8 keys and MXFP4 values once per 64 query rows and folds them in
@@ -28,8 +31,8 @@ of attend_chunk (_chunk_judge, _chunk_rows) are SharedPrefixSteps' (kv_shared.py
 class's own there is the (K, V) handle arrays of a prefix, its decode and chunk step, the fold entry and the depth table.
 
 Not in this class: the planned and captured decode route (plan_step, HIP graphs: attend stages its descriptors
-per call), multi-position steps on the decode kernel (attend_spec), load_paged / store_paged, fork, truncate, begin_step and the
-K pre-scale; a shared prefix is one level deep and one layer per call."""
+per call), attend_spec under a sliding window, over a shared prefix or for several layers at once, commit(nodes=path), load_paged /
+store_paged, fork, truncate, begin_step and the K pre-scale; a shared prefix is one level deep and one layer per call."""
 from typing import Dict, Optional, Sequence
 
 from . import kv_connector as _kc
@@ -73,6 +76,8 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         self._fold = (None,)                                  # attend: key, then what a step's calls share -- the count and device indices of the
                                                               # requests with an odd length, the handle arrays, the stored lengths,
                                                               # the query positions (attend under a window)
+        self._spec = (None,)                                  # attend_spec: key, then the step's mask words and gather index on the device, the
+                                                              # handle arrays and the stored lengths
         self._shared_key, self._shared_plan = None, None      # attend_shared / attend_chunk_shared: the judged call of a step (_shared_args)
 
     # ------------------------------------------------------------------ requests
@@ -253,6 +258,93 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                                      depths.data_ptr() if depths is not None else 0, window, int(splits), sm_scale, out.data_ptr(),
                                      lse.data_ptr() if keep_lse else 0, st.cuda_stream)
         return (out, lse, q) if keep_lse else out
+
+    # ------------------------------------------------------------------ a draft step on the decode kernel
+    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None):
+        """One layer of a step that carries S new positions per request -- draft tokens to verify -- on the DECODE kernel; signature and
+        contract of SpeckvKVConnector.attend_spec.  q [batch][S][heads][rows_per_pos][dim] fp16; k_new / v_new
+        [batch][S][layers][heads][dim] fp16, the positions that would follow each request's current length; n_new: optional per-request
+        counts <= S of live positions (a ragged step); parents (SpeckvKVConnector.tree_masks): the new positions form a tree -- node j
+        sees what the request holds, its ancestors and itself, not its siblings; None = a chain, which is the tree [-1, 0, 1, ...].
+        Returns [batch][S][heads][rows_per_pos][dim] fp32.  Changes no state -- commit() stores the accepted prefix afterwards.
+        The groups are SpeckvKVConnector.spec_groups(S, rows_per_pos): S * rows_per_pos <= 16 is one pass over the records, more goes
+        in groups of 16 // rows_per_pos positions.  Each group is ONE speckv_ext_attend_kv_spec call and nothing else: the stored
+        positions are walked once for the group's query rows (k_attend_k8v4<false, true>) and the rows held outside the pool -- the
+        request's odd last position where it has one, then the new positions -- are folded in inside that launch; there is no tail
+        fold and no fold launch.  A later group sees the earlier groups' positions as held positions through its columns of the
+        step's mask table.  The query enters the stored part as E4M3 x a row scale, as in attend; the held part takes it in fp16.
+        Rows of dead positions (>= n_new[b], or below a dead node) are the stored part alone, finite: zeros for a request that has
+        nothing stored.  Indices, masks and handle arrays are derived once per (batch, lengths, S, tree, live counts).
+        Against attend_chunk with the same step, the only other route (profiles/k8v4_spec_step.txt, 16 query rows per kv head): 0.34
+        of its time at 256 requests x 2k stored positions, 0.25-0.26 at 256 x 8k, 0.49-0.51 at 8 x 32k -- faster at every shape
+        measured; 1.07-1.31 single attend steps.  Sliding-window layers stay with attend_chunk(window=W).
+        Malformed arguments are a ValueError / KeyError before any library call; a placement the decode kernel does not serve
+        (striped, migrated) is the library's SpeckvError, passed through as in attend."""
+        import numbers
+        import numpy as np
+        import torch
+        if len(q.shape) != 5:
+            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim]")
+        B, S, H, R, D = (int(x) for x in q.shape)
+        if (H, D) != (self.H, self.D) or B != len(req_ids):
+            raise ValueError("q must be [batch][S][heads][rows_per_pos][dim] with one block per request")
+        if tuple(k_new.shape) != (B, S, self.L, H, D) or tuple(v_new.shape) != (B, S, self.L, H, D):
+            raise ValueError("k_new / v_new must be [batch][S][layers][heads][dim]")
+        if not _is_int(layer) or not 0 <= layer < self.L:
+            raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
+        groups = SpeckvKVConnector.spec_groups(S, R)
+        if n_new is not None:
+            n_new = [int(n) for n in n_new]
+            if len(n_new) != B or not all(0 <= n <= S for n in n_new):
+                raise ValueError("n_new: one count 0..S per request")
+        reqs = [self.requests[r] for r in req_ids]
+        if parents is not None:                       # (judged once per step, below: a walk over batch x S entries is the host's share of a call)
+            parents = list(parents)
+            shared = len(parents) > 0 and isinstance(parents[0], numbers.Integral)
+            tree_key = tuple(parents) if shared else tuple(tuple(p) for p in parents)
+        row = self.H * self.D
+        out = torch.empty((B, S, H, R, D), dtype=torch.float32, device="cuda")
+        if B == 0:
+            return out
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):
+                _, tk, tv = self._step_tails(req_ids, reqs)
+                key = (tuple(req_ids), self._epoch, S, None if parents is None else tree_key, None if n_new is None else tuple(n_new))
+                if self._spec[0] != key:              # once per step: the same for every layer and group
+                    trees = SpeckvKVConnector._tree_parents(list(range(-1, S - 1)) if parents is None else parents, B)
+                    if len(trees[0]) != S:
+                        raise ValueError("parents: one entry per new position")
+                    words = SpeckvKVConnector.tree_masks(trees, [r.length & 1 for r in reqs], n_new)
+                    idx, rank = [], 0
+                    for b, r in enumerate(reqs):      # the tail first where the length is odd, then the new positions (_held_rows)
+                        if r.length & 1:
+                            idx += [B * S + rank] + [b * S + t for t in range(S)]
+                            rank += 1
+                        else:
+                            idx += [b * S + t for t in range(S)] + [b * S + S - 1]       # (the last slot is never visible)
+                    self._spec = (key, _kc._device_index([w for per_request in words for w in per_request]),     # [batch][S] words (< 2^17)
+                                  _kc._device_index(idx), np.asarray([r.k_handle for r in reqs], dtype=np.uint64),
+                                  np.asarray([r.v_handle for r in reqs], dtype=np.uint64), np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32))
+                _, masks, idx, k_handles, v_handles, pos_end = self._spec
+                held = []
+                for new, tails in ((k_new, tk), (v_new, tv)):
+                    flat = new[:, :, layer].reshape(B * S, H, D)
+                    if tails is not None:
+                        flat = torch.cat((flat, tails[:, layer]), dim=0)
+                    held.append(flat.index_select(0, idx))                              # [batch * (1 + S)][heads][dim]
+                kh, vh = held
+                parts = []
+                for j0, n in groups:
+                    g = n * R
+                    parts.append((j0, n, g, q[:, j0:j0 + n].permute(0, 2, 1, 3, 4).reshape(B, H, g, D).contiguous(),
+                                  torch.empty((B, H, g, D), dtype=torch.float32, device="cuda")))
+            for j0, n, g, qg, og in parts:
+                self.lib.attend_kv_spec(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, kh.data_ptr(), vh.data_ptr(), (1 + S) * row, row,
+                                        masks.data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(), 0, st.cuda_stream)
+            with torch.cuda.stream(st):
+                for j0, n, g, qg, og in parts:
+                    out[:, j0:j0 + n] = og.view(B, H, n, R, D).permute(0, 2, 1, 3, 4)
+        return out
 
     # ------------------------------------------------------------------ a prefix shared by several requests
     # (the bodies are SharedPrefixSteps': this connector's side of them, then the two methods)

@@ -150,6 +150,8 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_fp8_planned": [c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_int4_planned": [c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_fold_tail": [c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_kv_spec": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64,
+                                  c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_fold_held": [c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
                                     ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_fold_masked": [c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32,
@@ -703,6 +705,19 @@ class SpeckvLib:
         u32 = lambda a: None if a is None else as_arr(a, c_uint32, n)
         self._ext("speckv_ext_attend_kv_batch_window", n, handles(k_handles), handles(v_handles), layer, c_void_p(d_q_f16), g, u32(pos_end),
                   u32(q_pos), window, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
+
+    def attend_kv_spec(self, k_handles, v_handles, layer, d_q_f16, g, rows_per_pos, pos_end, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems,
+                       d_mask, mask_stride, sm_scale, d_out, d_lse=None, stream=None):
+        """One multi-position step of a batch over a split pool (speckv_ext_attend_kv_spec): attend_kv_batch with g = n_q x rows_per_pos
+        query rows per kv head, and the positions held outside the pool (fp16 rows as attend_fold_held takes them, visibility from the
+        uint32 words d_mask[i * mask_stride + j] as attend_fold_masked takes them) folded in inside the same launch.  Arrays as
+        attend_kv_batch; 0 / None stands for a NULL pointer (for the library to refuse)."""
+        n = len(pos_end if k_handles is None and v_handles is None else (v_handles if k_handles is None else k_handles))
+        handles = lambda h: None if h is None else as_arr(h, c_uint64, n)
+        self._ext("speckv_ext_attend_kv_spec", n, handles(k_handles), handles(v_handles), layer, c_void_p(d_q_f16), g, rows_per_pos,
+                  None if pos_end is None else as_arr(pos_end, c_uint32, n), c_void_p(d_k_held or 0), c_void_p(d_v_held or 0), seq_stride_elems,
+                  pos_stride_elems, c_void_p(d_mask or 0), mask_stride, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0),
+                  c_void_p(stream or 0))
 
     def attend_int4_batch(self, handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse=None, stream=None):
         """handles / pos_end: sequences of ints, or ready ctypes arrays (c_uint64 / c_uint32) that a caller reuses over

@@ -1265,6 +1265,41 @@ speckv_status_t speckv_ext_attend_kv_batch_window(uint32_t n_seq, const speckv_h
                                                   const uint32_t* q_pos, uint32_t window, float sm_scale, float* d_out, float* d_lse,
                                                   void* stream);
 
+/* speckv_ext_attend_kv_spec: one MULTI-POSITION STEP of a batch over a SPLIT POOL -- verifying the draft positions of every sequence, a
+ * chain or a tree, on the decode kernel: speckv_ext_attend_kv_batch with g = n_q x rows_per_pos query rows per kv head (row r belongs to
+ * query position j = r / rows_per_pos, n_q <= SPECKV_HELD_MAX - 1), every row over all stored positions [0, pos_end[i]) in ONE pass over
+ * the records, and the positions the caller holds OUTSIDE the pool folded in INSIDE the same launch -- by the workgroups of a sequence's
+ * first piece, into its final rows or its partial; the merge then runs as in speckv_ext_attend_kv_batch.  No fold launch follows; what
+ * speckv_ext_attend_kv_batch + speckv_ext_attend_fold_masked compute in two calls.  An additive entry: SPECKV_EXT_ABI_VERSION stays what it is.
+ *   k_handles, v_handles, layer, d_q_f16 ([n_seq][8][g][128] fp16), g, pos_end, sm_scale, d_out, d_lse (optional), stream :
+ *       as speckv_ext_attend_kv_batch
+ *   d_k_held, d_v_held : the held positions, fp16, the layout of speckv_ext_attend_fold_held: position t of sequence i, kv head h, at
+ *       element i * seq_stride_elems + t * pos_stride_elems + h * 128 (the pointers already offset to the layer).  Held position 0 is the
+ *       sequence's odd last position where it has one, the step's new positions follow; at most SPECKV_HELD_MAX per sequence.  Device
+ *       pointers, 16-byte aligned; both strides multiples of 8, pos_stride_elems >= 8 * 128.
+ *   d_mask, mask_stride : device array, d_mask[i * mask_stride + j] = the held positions query position j of sequence i sees, bit t =
+ *       position t (the convention of speckv_ext_attend_fold_masked; bits >= SPECKV_HELD_MAX are dropped).  A causal chain behind `base`
+ *       earlier held positions is the word (1 << (base + j + 1)) - 1: one form for chains and trees.  mask_stride >= g / rows_per_pos; a
+ *       later group of a step that goes in several calls passes d_mask + its first position.
+ *       The kernel reads NO held position above the highest bit set in any word of the sequence: such rows may hold anything.
+ *       A word of 0 is a dead node of a ragged step: its rows leave as the attention over the stored positions alone (what
+ *       speckv_ext_attend_kv_batch writes there), zeros and lse = -inf where nothing is stored.
+ * Values.  The stored part as speckv_ext_attend_kv_batch (query as E4M3 x a row scale, K as its E4M3 values with the block scale on the
+ * score, V as the fp16 values of its MXFP4 records).  A held position is scored with the FP16 query -- the fp32 sum of the products
+ * over the 128 channels, x sm_scale -- and its fp16 V row is weighted in fp32; it enters the same running softmax as the stored tiles.
+ * A sequence with pos_end[i] == 0 gets the softmax over its visible held positions.
+ * Addressing, placement (single runs only), stream rules, ordering behind pool writes and statuses are those of
+ * speckv_ext_attend_kv_batch.  NOT capturable into a HIP graph.  There is no form under a sliding window: a draft step on a local layer
+ * goes through speckv_ext_attend_chunk_kv.  SPECKV_ERR_INVAL besides what speckv_ext_attend_kv_batch refuses, judged before anything
+ * else and on every engine: rows_per_pos == 0, g not a multiple of rows_per_pos, g / rows_per_pos > SPECKV_HELD_MAX - 1, a NULL
+ * d_k_held, d_v_held or d_mask, mask_stride < g / rows_per_pos, a stride that is not a multiple of 8, pos_stride_elems < 8 * 128, a held
+ * pointer that is not 16-byte aligned -- nothing is launched, d_out is untouched. */
+speckv_status_t speckv_ext_attend_kv_spec(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                          uint32_t layer, const void* d_q_f16, uint32_t g, uint32_t rows_per_pos, const uint32_t* pos_end,
+                                          const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                                          const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse /* optional */,
+                                          void* stream);
+
 /* speckv_ext_attend_chunk_tree_window: a DRAFT TREE on a SLIDING-WINDOW (local) layer -- the tree step of the local layers of the
  * models speckv_ext_attend_chunk_window names, whose global layers take the tree step through speckv_ext_attend_chunk_masked / _split.
  * The arguments of speckv_ext_attend_chunk_split in the same order with `d_depth, window` directly behind mask_words.  Everything
