@@ -25,6 +25,7 @@
 // kMx4CodePlane + 64 page.  Never-written records are zero bytes on both sides: K scale 0 -> score 0 (NOT -inf), V = 0.
 #include "kernels.hpp"
 #include "attend_fp8_device.hpp"     // the K side's tile arithmetic, shared with attend.hip
+#include "spec_window.hpp"           // the walk rule of the held step under a window
 
 namespace speckv {
 
@@ -93,6 +94,16 @@ __device__ __forceinline__ void k8v4_fold_held(const AttendArgs& a, const Attend
     }
 }
 
+// k_attend_k8v4<true, true>: the leading positions of the sequence's walk that the lane's query row does not see (spec_window.hpp) -- rel of
+// the sequence + the depth of the row's query position, from the depth table that lies beside the mask words.  A lane without a query
+// row reads no depth.
+__device__ __forceinline__ uint32_t k8v4_row_skip(const AttendHeldArgs& h, uint32_t g, uint32_t seq, uint32_t c, int32_t rel)
+{
+    uint32_t depth = 0u;
+    if (c < g) depth = *SPECKV_GP(uint32_t, h.depth + static_cast<uint64_t>(seq) * h.mask_stride + c / h.rows_per_pos);
+    return spec_window_skip(rel, depth);
+}
+
 // a.seqs: the K side and the split bookkeeping of every sequence (lin_base, scale_tab, k_first of the K allocation; v_first and
 // layer_pages are not read); vside[sequence]: the V allocation's run and the first record of the layer's V region (a multiple of 16).
 // a.direct_out / direct_lse are always set: a sequence with ONE split is written final, one without positions as zeros / -inf, the
@@ -110,10 +121,17 @@ __device__ __forceinline__ void k8v4_fold_held(const AttendArgs& a, const Attend
 // the 64 bytes of channels 32kb .. 32kb + 31 of a held row for K and for V (acc[t][i] = channel 32kb + 8i + t: element t of the i-th 16
 // bytes), one position computed while the next one's rows are under way; the loop ends at the highest bit set in any word of the sequence
 // and no held position above that is read.  `held` is AttendHeldArgs for HELD and empty otherwise: the plain instances keep their argument block.
+// WINDOW and HELD (speckv_ext_attend_kv_spec_window): the step of several positions on a sliding-window layer.  The rows of a wave no longer
+// share a lower bound -- a node of depth d sits at length + d and sees the stored positions from length + d + 1 - W on -- so the descriptors
+// start at the tile of DEPTH 0's bound, a.seq_skip[sequence] carries the signed rel of spec_window.hpp instead of a position count, and the
+// lane masks its eight scores by its own row's skip = max(0, rel + depth) <= 46: in tiles 0 and 1 of the walk (the gate is wave-uniform:
+// tiles whose first position lies at or behind rel + 15 carry no mask).  A row may be masked throughout a tile or a whole piece: it then
+// carries m_run = -inf, l_run = 0, which att_softmax_step, k8v4_fold_held, att_store_rows8 and both merges turn into weight 0.  The held
+// positions are folded as in <false, true>: what a node sees of them under the window lies in the mask words alone.
 template <bool WINDOW, bool HELD, class... Held>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_attend_k8v4(AttendArgs a, const AttendKvSide* __restrict__ vside, Held... held)
 {
-    static_assert(!(WINDOW && HELD) && sizeof...(Held) == (HELD ? 1 : 0), "instances: <false, false>, <true, false>, <false, true, AttendHeldArgs>");
+    static_assert(sizeof...(Held) == (HELD ? 1 : 0), "instances: <false, false>, <true, false>, <false, true, AttendHeldArgs>, <true, true, AttendHeldArgs>");
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t c = lane & 15u, kb = lane >> 4;
@@ -134,7 +152,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const AttendKvSide vsd = vside[seq];
     const uint64_t part = sq.part_base + static_cast<uint64_t>(head) * sq.n_splits + split;
     const uint32_t n_pages = sq.n_pages;
-    const uint32_t skip_pos = WINDOW ? a.seq_skip[seq] : 0u;             // (workgroup-uniform)
+    const uint32_t skip_pos = (WINDOW && !HELD) ? a.seq_skip[seq] : 0u;  // (workgroup-uniform)
+    // WINDOW and HELD: that word is the sequence's signed rel; row_skip = the lane's own row, cut_pos = depth 0's = the least of any row (uniform)
+    uint32_t row_skip = 0u, cut_pos = 0u;
+    int32_t rel = 0;
+    if constexpr (WINDOW && HELD) {
+        rel = static_cast<int32_t>(*SPECKV_GP(uint32_t, a.seq_skip + seq));
+        row_skip = k8v4_row_skip(held..., a.g, seq, c, rel);
+        cut_pos = spec_window_skip(rel, 0u);
+    }
 
     // query operand (fp8_query_operand): row c of this head, lane kb takes d = 16kb .. 16kb + 15 of both 64-element halves, the split the
     // K loads follow; rows >= g are zero
@@ -202,7 +228,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             // WINDOW: the positions of the sequence's tile 0 in front of the window.  `tile` is the absolute tile of the sequence, so only split 0
             // comes here.  Where n_pages > 0 the window's lower bound lo = skip_pos is visible and lies in tile 0: no piece is masked throughout,
             // m_run is finite from the first tile on.
-            if (WINDOW && tile == 0u && skip_pos != 0u) {                 // wave-uniform
+            if (WINDOW && !HELD && tile == 0u && skip_pos != 0u) {        // wave-uniform
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const uint32_t pg = att_slot_page(kb, r);
@@ -213,6 +239,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                     // units of that code, the masked nibble's weight is exactly 0, and an MXFP4 value widened to fp16 by the conversion is finite
                     // (both positions of a page are encoded together from fp16 rows: the block's code keeps 6 x 2^(code - 127) inside fp16), so 0 x it is 0
                     if (2u * pg + 2u <= skip_pos) vcode[r] = 0u;
+                }
+            }
+            // WINDOW and HELD: the mask is the ROW's.  Tiles whose first position lies below rel + 15, the deepest row's bound, can carry one:
+            // tiles 0 and 1 (rel <= 31).  The V bytes and code bytes of a lane are not its query row's: they belong to the lane as holder of
+            // channels 8c .. 8c + 7 and meet EVERY row's weights in the MFMA.  So a page's code may go only where the page is masked for every
+            // row, 2 page + 2 <= cut_pos (depth 0's bound, wave-uniform) -- the windowed instance's reason: a stale or hostile record in front
+            // of every window meets its weights of 0 as a small finite number.  Pages between that bound and a deeper row's own are stored,
+            // encoded records some shallower row still reads in their code's units; for the deeper row a weight of exactly 0 meets a finite
+            // fp16 value there (an MXFP4 value widened by the conversion is finite), and 0 x it is 0.
+            if constexpr (WINDOW && HELD) {
+                if (tile < 2u && static_cast<int32_t>(tile * 32u) < rel + static_cast<int32_t>(kSpecWindowMaxDepth)) {      // wave-uniform
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const uint32_t p0 = 2u * (tile * 16u + att_slot_page(kb, r));
+                        if (p0 < row_skip) sc[2 * r] = -INFINITY;
+                        if (p0 + 1u < row_skip) sc[2 * r + 1] = -INFINITY;
+                        if (p0 + 2u <= cut_pos) vcode[r] = 0u;
+                    }
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -276,12 +320,13 @@ hipError_t launch_attend_k8v4(const AttendArgs& a, const AttendKvSide* d_vside, 
 }
 
 // The step of several positions: the launch above with the held positions of every sequence folded in by its split 0 (k_attend_k8v4<false,
-// true>).  No instance under a window: a.seq_skip is refused.
+// true>).  a.seq_skip set: the step on a sliding-window layer (k_attend_k8v4<true, true>) -- the descriptors start at the tile of depth 0's
+// bound, seq_skip[sequence] is the sequence's SIGNED rel (spec_window.hpp) and h.depth the depth table beside the mask words.
 hipError_t launch_attend_k8v4_held(const AttendArgs& a, const AttendKvSide* d_vside, const AttendHeldArgs& h, uint32_t n_seq, bool merge, float* d_out,
                                    float* d_lse, hipStream_t s)
 {
     if (n_seq == 0) return hipSuccess;
-    if (!a.seqs || !d_vside || !a.q16 || a.direct_out != d_out || a.heads % 4u || a.g == 0 || a.g > 16u || a.seq_skip) return hipErrorInvalidValue;
+    if (!a.seqs || !d_vside || !a.q16 || a.direct_out != d_out || a.heads % 4u || a.g == 0 || a.g > 16u || (a.seq_skip && !h.depth)) return hipErrorInvalidValue;
     if (!h.k_held || !h.v_held || !h.mask || h.rows_per_pos == 0 || a.g % h.rows_per_pos || a.g / h.rows_per_pos > kHeldMax - 1u ||
         h.mask_stride < a.g / h.rows_per_pos || h.seq_stride % 8u || h.pos_stride % 8u)
         return hipErrorInvalidValue;
@@ -289,7 +334,8 @@ hipError_t launch_attend_k8v4_held(const AttendArgs& a, const AttendKvSide* d_vs
     const uint32_t rows = n_seq * (a.heads / 4u), splits = a.n_splits ? a.n_splits : 1u;      // (split 0 of a sequence without positions folds its held ones)
     ar.rows_real = rows;
     const dim3 gr = a.rows_first ? dim3(rows | 1u, splits) : dim3(splits, rows);
-    hipLaunchKernelGGL((k_attend_k8v4<false, true, AttendHeldArgs>), gr, dim3(256), 0, s, ar, d_vside, h);
+    if (a.seq_skip) hipLaunchKernelGGL((k_attend_k8v4<true, true, AttendHeldArgs>), gr, dim3(256), 0, s, ar, d_vside, h);
+    else hipLaunchKernelGGL((k_attend_k8v4<false, true, AttendHeldArgs>), gr, dim3(256), 0, s, ar, d_vside, h);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || !merge) return e;
     ar.direct_per_seq = 3u;                                              // the merge passes over the sequences without a split too: their rows are the softmax over the held positions

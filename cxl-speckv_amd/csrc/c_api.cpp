@@ -17,6 +17,7 @@
 #include "chunk_window.hpp"
 #include "prefix_window.hpp"
 #include "decode_window.hpp"
+#include "spec_window.hpp"
 
 #include <cstring>
 #include <cstdio>
@@ -608,6 +609,29 @@ speckv_status_t speckv_ext_attend_kv_spec(uint32_t n_seq, const speckv_handle_t*
         return g_engine->attend_spec_kv(n_seq, k_handles, v_handles, layer, d_q_f16, g, rows_per_pos, pos_end, d_k_held, d_v_held, seq_stride_elems,
                                         pos_stride_elems, d_mask, mask_stride, sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream));
     });
+}
+
+speckv_status_t speckv_ext_attend_kv_spec_window(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles, uint32_t layer,
+                                                 const void* d_q_f16, uint32_t g, uint32_t rows_per_pos, const uint32_t* pos_end, const uint32_t* length,
+                                                 const uint32_t* d_depth, uint32_t window, const void* d_k_held, const void* d_v_held,
+                                                 uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride,
+                                                 float sm_scale, float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] {
+        return g_engine->attend_spec_kv(n_seq, k_handles, v_handles, layer, d_q_f16, g, rows_per_pos, pos_end, d_k_held, d_v_held, seq_stride_elems,
+                                        pos_stride_elems, d_mask, mask_stride, sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream), length, d_depth,
+                                        window);
+    });
+}
+
+// the walk rule of that entry (spec_window.hpp); no engine needed
+speckv_status_t speckv_ext_spec_window_range(uint32_t length, uint32_t window, uint32_t* out_begin, int32_t* out_rel, uint32_t* out_n_pages)
+{
+    if (!out_begin || !out_rel || !out_n_pages || window == 0) return SPECKV_ERR_INVAL;
+    const speckv::SpecWindowRange r = speckv::spec_window_range(length, window);
+    *out_begin = r.begin; *out_rel = r.rel; *out_n_pages = r.n_pages;
+    return SPECKV_OK;
 }
 
 speckv_status_t speckv_ext_attend_int4_batch(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16,

@@ -238,10 +238,12 @@ public:
     int attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
                         const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos = nullptr, uint32_t window = 0,
                         const AttendHeldArgs* held = nullptr);
-    // the step of several positions over the split pool (speckv_ext_attend_kv_spec): its own refusals, then attend_batch_kv with the held rows
+    // the step of several positions over the split pool (speckv_ext_attend_kv_spec): its own refusals, then attend_batch_kv with the held rows;
+    // length / d_depth / window: the step on a sliding-window layer (speckv_ext_attend_kv_spec_window; spec_window.hpp), window = 0: none
     int attend_spec_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
                        uint32_t rows_per_pos, const uint32_t* pos_end, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems,
-                       uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
+                       uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s,
+                       const uint32_t* length = nullptr, const uint32_t* d_depth = nullptr, uint32_t window = 0);
     int attend_mx4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
                    uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
     int migrate(uint64_t handle, uint64_t first_page, uint64_t n_pages, uint32_t target_pool);

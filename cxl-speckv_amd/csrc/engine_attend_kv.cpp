@@ -1,9 +1,10 @@
 // cxl-speckv_amd/csrc/engine_attend_kv.cpp -- Engine::attend_batch_kv, the body behind speckv_ext_attend_kv_batch,
-// speckv_ext_attend_kv_batch_window and speckv_ext_attend_kv_spec: one decode step of a batch over the SPLIT POOL ("K8V4": a sequence's K rows in an FP8_E4M3
+// speckv_ext_attend_kv_batch_window, speckv_ext_attend_kv_spec and speckv_ext_attend_kv_spec_window: one decode step of a batch over the SPLIT POOL ("K8V4": a sequence's K rows in an FP8_E4M3
 // allocation, its V rows in an MXFP4 allocation), one attention launch (k_attend_k8v4, attend_kv.hip) and, where members have several
 // pieces, the merge behind it
 #include "engine_internal.hpp"
 #include "decode_window.hpp"
+#include "spec_window.hpp"
 #include "tuning.hpp"
 
 namespace speckv {
@@ -20,15 +21,21 @@ namespace speckv {
 // of 16 records, a kernel tile stays one storage tile and one group of the scale table), the tiles, the dispatch order and the pieces are
 // those of the pages actually walked, and the leading positions of tile 0 in front of lo travel as the skip array (AttendArgs::seq_skip:
 // k_attend_k8v4<true>).  window = 0, or a window that cuts no member: the descriptors, the instance and the launches of the entry without one.
-// held (attend_spec_kv, never with a window): the step of several positions -- g = n_q x rows_per_pos query rows that all see every stored
+// held (attend_spec_kv): the step of several positions -- g = n_q x rows_per_pos query rows that all see every stored
 // position, so descriptors, geometry, pieces and slot are those of a decode step of g rows; the launch is k_attend_k8v4<false, true>, whose
 // split 0 folds the held rows of every member into its final rows or its partial (launch_attend_k8v4_held).
+// held under a window (speckv_ext_attend_kv_spec_window; spec_window.hpp): q_pos carries the members' committed LENGTHS (judged by
+// attend_spec_kv).  The rows of a member no longer share a lower bound, so its descriptor starts at the tile of depth 0's bound in both
+// allocations whatever depths the call carries, the tiles, the dispatch order and the pieces are those of the pages walked, and the skip
+// slot of the descriptor ring carries the member's SIGNED rel (k_attend_k8v4<true, true> adds the row's depth).  A member no row of
+// which sees a pool position is one with nothing stored: its held positions alone.  A window that can cut no member (length + 16 <=
+// window for all): the descriptors, the instance and the launches of the entry without one.
 int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
                             const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos, uint32_t window,
                             const AttendHeldArgs* held)
 {
-    const char* entry = held ? "speckv_ext_attend_kv_spec" : window ? "speckv_ext_attend_kv_batch_window" : "speckv_ext_attend_kv_batch";
-    if (held && window) return SPECKV_ERR_INVAL;
+    const char* entry = held ? (window ? "speckv_ext_attend_kv_spec_window" : "speckv_ext_attend_kv_spec")
+                             : window ? "speckv_ext_attend_kv_batch_window" : "speckv_ext_attend_kv_batch";
     if (null_) return no_data_path(entry);
     if (window && !q_pos) return SPECKV_ERR_INVAL;
     if (!window) q_pos = nullptr;                                        // (no window: the launches of the entry without one)
@@ -61,7 +68,13 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
         const uint32_t region = k->layout.num_tokens / 2u;
         // the member's walk: everything stored, or under a window the tiles from lo's on (they end where they ended without one: inside the region)
         DecodeWindowRange w{0u, 0u, pos_end[i] / 2u};
-        if (q_pos) {
+        if (q_pos && held) {
+            if (q_pos[i] != pos_end[i] && q_pos[i] != pos_end[i] + 1u) return SPECKV_ERR_INVAL;     // the committed length: what is stored, or the tail behind it
+            const SpecWindowRange r = spec_window_range(q_pos[i], window);
+            w = DecodeWindowRange{r.n_pages ? r.begin : 0u, 0u, r.n_pages};                           // (no pool position in any row's window: nothing stored)
+            skips[i] = r.n_pages ? static_cast<uint32_t>(r.rel) : 0u;
+            cut = cut || static_cast<uint64_t>(q_pos[i]) + (SPECKV_HELD_MAX - 1u) > window;
+        } else if (q_pos) {
             if (q_pos[i] > pos_end[i] || q_pos[i] + 1u < pos_end[i]) return SPECKV_ERR_INVAL;       // the query: the last stored position or the tail behind it
             w = decode_window_range(q_pos[i] + 1u, window);
             if (w.n_pages == 0u) w = DecodeWindowRange{0u, 0u, 0u};      // no pool position in the window: the member of pos_end = 0 (zeros, lse -inf)
@@ -136,18 +149,25 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
 }
 
 // speckv_ext_attend_kv_spec.  What concerns the held rows and the mask is judged first, so a bad set is SPECKV_ERR_INVAL on every engine
-// (the folds' rule: Engine::fold_held_args_ok); the rest is attend_batch_kv's.
+// (the folds' rule: Engine::fold_held_args_ok); the rest is attend_batch_kv's.  window != 0 (speckv_ext_attend_kv_spec_window): length and
+// d_depth are judged here as well; window == 0: neither is looked at.
 int Engine::attend_spec_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
                            uint32_t rows_per_pos, const uint32_t* pos_end, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems,
-                           uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+                           uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s,
+                           const uint32_t* length, const uint32_t* d_depth, uint32_t window)
 {
     if (rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > SPECKV_HELD_MAX - 1u) return SPECKV_ERR_INVAL;
     if (!d_k_held || !d_v_held || !d_mask || mask_stride < g / rows_per_pos) return SPECKV_ERR_INVAL;
     if (seq_stride_elems % 8u || pos_stride_elems % 8u || pos_stride_elems < 8u * 128u) return SPECKV_ERR_INVAL;
     if (reinterpret_cast<uintptr_t>(d_k_held) % 16u || reinterpret_cast<uintptr_t>(d_v_held) % 16u) return SPECKV_ERR_INVAL;
+    if (window) {
+        if (!length || !d_depth) return SPECKV_ERR_INVAL;
+        for (uint32_t i = 0; pos_end && i < n_seq; ++i)
+            if (length[i] != pos_end[i] && length[i] != pos_end[i] + 1u) return SPECKV_ERR_INVAL;
+    }
     const AttendHeldArgs held{static_cast<const uint16_t*>(d_k_held), static_cast<const uint16_t*>(d_v_held), seq_stride_elems, pos_stride_elems,
-                              d_mask, mask_stride, rows_per_pos};
-    return attend_batch_kv(n_seq, k_handles, v_handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse, s, nullptr, 0u, &held);
+                              d_mask, mask_stride, rows_per_pos, window ? d_depth : nullptr};
+    return attend_batch_kv(n_seq, k_handles, v_handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse, s, window ? length : nullptr, window, &held);
 }
 
 } // namespace speckv

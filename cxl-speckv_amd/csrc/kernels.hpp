@@ -714,8 +714,12 @@ struct AttendHeldArgs {
     uint64_t seq_stride, pos_stride;  // elements
     const uint32_t* mask;
     uint32_t mask_stride, rows_per_pos;
+    // under a window only (k_attend_k8v4<true, true>): depth[i * mask_stride + j] = the depth of query position j of sequence i in the
+    // step's tree (0 = a root), strided like the mask words; NULL otherwise
+    const uint32_t* depth;
 };
-// launch_attend_k8v4 with the held positions; a.g = n_q x h.rows_per_pos.  There is no instance under a window: a.seq_skip is refused.
+// launch_attend_k8v4 with the held positions; a.g = n_q x h.rows_per_pos.  a.seq_skip set (with h.depth): the step under a sliding window,
+// k_attend_k8v4<true, true> -- seq_skip[sequence] is then the sequence's signed rel of spec_window.hpp, not a position count.
 hipError_t launch_attend_k8v4_held(const AttendArgs& a, const AttendKvSide* d_vside, const AttendHeldArgs& h, uint32_t n_seq, bool merge, float* d_out,
                                    float* d_lse, hipStream_t s);
 

@@ -855,13 +855,19 @@ class SpeckvKVConnector(SharedPrefixSteps):
         return [[int(p) for p in tree] for tree in trees]
 
     @staticmethod
-    def tree_masks(parents, base, n_new=None):
+    def tree_masks(parents, base, n_new=None, window=None):
         """The mask words of a step whose S new positions form a tree, as speckv_ext_attend_fold_masked takes them: [batch][S] ints.
         parents: [S], or [batch][S] for one tree per request; parents[j] in -1 .. j-1, -1 = a child of the committed context, nodes in
         an order where a parent precedes its children.  base[b]: the held positions in front of node 0 (a request's odd last position:
         0 or 1), all visible to every node.  Node j's word = the low base[b] bits, and the bits base[b] + a of its ancestors a and of j
         itself.  Nodes >= n_new[b] (a ragged step) are dead: word 0, and so is every node below a dead one.  A chain (parents[j] = j - 1)
-        gives (1 << (base + j + 1)) - 1, the rule of speckv_ext_attend_fold_held.  Pure python, no device."""
+        gives (1 << (base + j + 1)) - 1, the rule of speckv_ext_attend_fold_held.
+        window (None or 0: none, the words above; W >= 1 as speckv_ext_attend_kv_spec_window takes them): node j of depth d sits at the
+        absolute position length + d and sees [length + d + 1 - W, length + d], so its word keeps the bit of ancestor a iff depth(a) >=
+        d + 1 - W, its own bit always, and the bit of a held position in front of node 0 iff it lies inside that range -- the odd last
+        position, one in front of depth 0, iff d + 2 <= W.  Which nodes are dead does not depend on the window; W >= 17 changes no word
+        (no node is deeper than 15).  Pure python, no device."""
+        W = SpeckvKVConnector._decode_window(window)
         base = [int(x) for x in base]
         trees = SpeckvKVConnector._tree_parents(parents, len(base))
         if not trees:
@@ -880,8 +886,37 @@ class SpeckvKVConnector(SharedPrefixSteps):
             for j, p in enumerate(tree):
                 up = ((1 << x) - 1) if p < 0 else row[p]                  # what the parent sees (0: the parent is dead)
                 row.append(up | 1 << (x + j) if j < n and (p < 0 or up) else 0)
+            if W:                                                          # the window, on the finished words: liveness is decided above
+                depth = []
+                for p in tree:
+                    depth.append(0 if p < 0 else depth[p] + 1)
+                for j, d in enumerate(depth):
+                    keep = sum(1 << t for t in range(x) if d + 1 + (x - t) <= W) | sum(1 << (x + a) for a in range(j + 1) if depth[a] >= d + 1 - W)
+                    row[j] &= keep
             words.append(row)
         return words
+
+    @staticmethod
+    def spec_window_range(length: int, window):
+        """The walk rule of attend_spec(window=W) on a split pool (csrc/spec_window.hpp, speckv_ext_spec_window_range), restated: a
+        request of `length` committed positions has stored = length & ~1 of them in the pool; a draft node of depth d sits at length + d
+        and sees the absolute positions from lo(d) = max(0, length + d + 1 - W) on.  Returns (begin, rel, n_pages): the launch walks the
+        pool from the tile of depth 0's bound, begin = lo(0) & ~31, over n_pages = (stored - begin) / 2 pages (0 where lo(0) >= stored: no
+        node sees a pool position), and a row of depth d does not see the leading spec_window_skip(rel, d) positions of that walk; rel =
+        length + 1 - W - begin is signed."""
+        W = SpeckvKVConnector._decode_window(window)
+        if not W:
+            raise ValueError("window must be an integer >= 1")
+        length = int(length)
+        stored = length & ~1
+        lo = max(0, length + 1 - W)
+        begin = lo & ~31
+        return begin, length + 1 - W - begin, (stored - begin) // 2 if lo < stored else 0
+
+    @staticmethod
+    def spec_window_skip(rel: int, depth: int):
+        """max(0, rel + min(depth, 15)): the leading positions of a request's walk (spec_window_range) that a node of `depth` does not see"""
+        return max(0, int(rel) + min(int(depth), 15))
 
     def _held_rows(self, req_ids, key, reqs, k_new, v_new, layer_begin, n_layers, st):
         """The rows a step holds outside the pool as speckv_ext_attend_fold_held takes them: fp16 [n_layers][batch][1 + S][heads][dim]

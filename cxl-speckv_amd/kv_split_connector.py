@@ -20,7 +20,8 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
                                         64-row query block then carries rows_per_pos live rows: attend is the decode route)
   attend_spec                           one layer of a DRAFT step (S new positions per request, a chain or a tree) on the decode kernel: per
                                         group of 16 // rows_per_pos positions ONE speckv_ext_attend_kv_spec -- the stored positions walked
-                                        once for up to 16 query rows per kv head, the tail and the new rows folded in inside that launch
+                                        once for up to 16 query rows per kv head, the tail and the new rows folded in inside that launch;
+                                        window=W: the step on a sliding-window layer, ONE speckv_ext_attend_kv_spec_window per group
   attend_shared / attend_chunk_shared   attend / attend_chunk for members that SHARE A PREFIX without holding a copy of it: the own part as
                                         those methods issue it with the log-sum-exp kept, then ONE speckv_ext_attend_prefix_fold_kv launch
                                         that reads the prefix's FP8 keys and MXFP4 values once per 64 query rows and folds them in
@@ -31,7 +32,7 @@ of attend_chunk (_chunk_judge, _chunk_rows) are SharedPrefixSteps' (kv_shared.py
 class's own there is the (K, V) handle arrays of a prefix, its decode and chunk step, the fold entry and the depth table.
 
 Not in this class: the planned and captured decode route (plan_step, HIP graphs: attend stages its descriptors
-per call), attend_spec under a sliding window, over a shared prefix or for several layers at once, commit(nodes=path), load_paged /
+per call), attend_spec over a shared prefix or for several layers at once, commit(nodes=path), load_paged /
 store_paged, fork, truncate, begin_step and the K pre-scale; a shared prefix is one level deep and one layer per call."""
 from typing import Dict, Optional, Sequence
 
@@ -260,7 +261,8 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         return (out, lse, q) if keep_lse else out
 
     # ------------------------------------------------------------------ a draft step on the decode kernel
-    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None):
+    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None,
+                    window=None):
         """One layer of a step that carries S new positions per request -- draft tokens to verify -- on the DECODE kernel; signature and
         contract of SpeckvKVConnector.attend_spec.  q [batch][S][heads][rows_per_pos][dim] fp16; k_new / v_new
         [batch][S][layers][heads][dim] fp16, the positions that would follow each request's current length; n_new: optional per-request
@@ -277,7 +279,17 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         nothing stored.  Indices, masks and handle arrays are derived once per (batch, lengths, S, tree, live counts).
         Against attend_chunk with the same step, the only other route (profiles/k8v4_spec_step.txt, 16 query rows per kv head): 0.34
         of its time at 256 requests x 2k stored positions, 0.25-0.26 at 256 x 8k, 0.49-0.51 at 8 x 32k -- faster at every shape
-        measured; 1.07-1.31 single attend steps.  Sliding-window layers stay with attend_chunk(window=W).
+        measured; 1.07-1.31 single attend steps.
+        window (None or 0: none, exactly the calls above; W >= 1: a sliding-window layer): each group is ONE
+        speckv_ext_attend_kv_spec_window call and nothing else.  Node j of depth d (SpeckvKVConnector.chunk_tree_depths; a chain: j)
+        sits at length + d and sees the last W positions up to itself: the stored ones from length + d + 1 - W on, masked per query row
+        inside the kernel (k_attend_k8v4<true, true>; the walk starts at the tile of depth 0's bound, spec_window_range), the held ones
+        through the words of tree_masks(window=W).  A dead node's rows are the stored positions its depth's window shows, finite; zeros
+        where it shows none.  Against attend_chunk(window=W) with the same step, until now the only route on a
+        local layer (profiles/k8v4_spec_window.txt; W = 1024, 16 query rows per kv head): 0.34-0.37 of its time at 256 requests x 2k
+        and at 256 x 8k stored positions, 0.93-0.94 at 8 x 32k with (S, rows_per_pos) = (4, 4) and (2, 8); at 8 x 32k with (16, 1) the
+        two are equal within the spread (1.01, spread 0.021): with few requests and 16 positions per step attend_chunk(window=W) is as
+        good.  0.28-0.83 of an unwindowed attend_spec, 1.30-1.50 single attend(window=W) steps.
         Malformed arguments are a ValueError / KeyError before any library call; a placement the decode kernel does not serve
         (striped, migrated) is the library's SpeckvError, passed through as in attend."""
         import numbers
@@ -293,6 +305,7 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         if not _is_int(layer) or not 0 <= layer < self.L:
             raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
         groups = SpeckvKVConnector.spec_groups(S, R)
+        W = SpeckvKVConnector._decode_window(window)
         if n_new is not None:
             n_new = [int(n) for n in n_new]
             if len(n_new) != B or not all(0 <= n <= S for n in n_new):
@@ -309,12 +322,13 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         with self._On(self, stream) as st:
             with torch.cuda.stream(st):
                 _, tk, tv = self._step_tails(req_ids, reqs)
-                key = (tuple(req_ids), self._epoch, S, None if parents is None else tree_key, None if n_new is None else tuple(n_new))
+                key = (tuple(req_ids), self._epoch, S, None if parents is None else tree_key, None if n_new is None else tuple(n_new), W)
                 if self._spec[0] != key:              # once per step: the same for every layer and group
                     trees = SpeckvKVConnector._tree_parents(list(range(-1, S - 1)) if parents is None else parents, B)
                     if len(trees[0]) != S:
                         raise ValueError("parents: one entry per new position")
-                    words = SpeckvKVConnector.tree_masks(trees, [r.length & 1 for r in reqs], n_new)
+                    words = SpeckvKVConnector.tree_masks(trees, [r.length & 1 for r in reqs], n_new, window=W or None)
+                    depths = SpeckvKVConnector.chunk_tree_depths(trees, B) if W else None
                     idx, rank = [], 0
                     for b, r in enumerate(reqs):      # the tail first where the length is odd, then the new positions (_held_rows)
                         if r.length & 1:
@@ -324,8 +338,10 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                             idx += [b * S + t for t in range(S)] + [b * S + S - 1]       # (the last slot is never visible)
                     self._spec = (key, _kc._device_index([w for per_request in words for w in per_request]),     # [batch][S] words (< 2^17)
                                   _kc._device_index(idx), np.asarray([r.k_handle for r in reqs], dtype=np.uint64),
-                                  np.asarray([r.v_handle for r in reqs], dtype=np.uint64), np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32))
-                _, masks, idx, k_handles, v_handles, pos_end = self._spec
+                                  np.asarray([r.v_handle for r in reqs], dtype=np.uint64), np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                  _kc._device_index([d for per_request in depths for d in per_request]) if W else None,       # [batch][S] depths
+                                  np.asarray([r.length for r in reqs], dtype=np.uint32))
+                _, masks, idx, k_handles, v_handles, pos_end, depths, lengths = self._spec
                 held = []
                 for new, tails in ((k_new, tk), (v_new, tv)):
                     flat = new[:, :, layer].reshape(B * S, H, D)
@@ -339,6 +355,11 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                     parts.append((j0, n, g, q[:, j0:j0 + n].permute(0, 2, 1, 3, 4).reshape(B, H, g, D).contiguous(),
                                   torch.empty((B, H, g, D), dtype=torch.float32, device="cuda")))
             for j0, n, g, qg, og in parts:
+                if W:                                 # a sliding-window layer: the same launch, the stored positions masked per row by its depth
+                    self.lib.attend_kv_spec_window(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, lengths, depths.data_ptr() + 4 * j0, W,
+                                                   kh.data_ptr(), vh.data_ptr(), (1 + S) * row, row, masks.data_ptr() + 4 * j0, S, sm_scale,
+                                                   og.data_ptr(), 0, st.cuda_stream)
+                    continue
                 self.lib.attend_kv_spec(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, kh.data_ptr(), vh.data_ptr(), (1 + S) * row, row,
                                         masks.data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(), 0, st.cuda_stream)
             with torch.cuda.stream(st):

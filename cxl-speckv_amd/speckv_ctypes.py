@@ -152,6 +152,9 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_fold_tail": [c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_kv_spec": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64,
                                   c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_kv_spec_window": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32,
+                                         c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_spec_window_range": [c_uint32, c_uint32, _u32p, ctypes.POINTER(ctypes.c_int32), _u32p],
     "speckv_ext_attend_fold_held": [c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
                                     ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_fold_masked": [c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32,
@@ -719,6 +722,19 @@ class SpeckvLib:
                   pos_stride_elems, c_void_p(d_mask or 0), mask_stride, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0),
                   c_void_p(stream or 0))
 
+    def attend_kv_spec_window(self, k_handles, v_handles, layer, d_q_f16, g, rows_per_pos, pos_end, length, d_depth, window, d_k_held, d_v_held,
+                              seq_stride_elems, pos_stride_elems, d_mask, mask_stride, sm_scale, d_out, d_lse=None, stream=None):
+        """attend_kv_spec on a sliding-window layer (speckv_ext_attend_kv_spec_window): `length` = the committed positions of every
+        sequence (pos_end[i] or pos_end[i] + 1), d_depth = the device table of node depths strided like d_mask, window = W; the stored
+        positions are masked per query row by its depth, the held ones by d_mask as ever.  window = 0: attend_kv_spec.  Arrays as
+        attend_kv_batch; 0 / None stands for a NULL pointer (for the library to refuse)."""
+        n = len(pos_end if k_handles is None and v_handles is None else (v_handles if k_handles is None else k_handles))
+        handles = lambda h: None if h is None else as_arr(h, c_uint64, n)
+        u32 = lambda a: None if a is None else as_arr(a, c_uint32, n)
+        self._ext("speckv_ext_attend_kv_spec_window", n, handles(k_handles), handles(v_handles), layer, c_void_p(d_q_f16), g, rows_per_pos, u32(pos_end),
+                  u32(length), c_void_p(d_depth or 0), window, c_void_p(d_k_held or 0), c_void_p(d_v_held or 0), seq_stride_elems, pos_stride_elems,
+                  c_void_p(d_mask or 0), mask_stride, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
+
     def attend_int4_batch(self, handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse=None, stream=None):
         """handles / pos_end: sequences of ints, or ready ctypes arrays (c_uint64 / c_uint32) that a caller reuses over
         the layers of a decode step."""
@@ -791,6 +807,13 @@ class SpeckvLib:
         b, k, n = c_uint32(0), c_uint32(0), c_uint32(0)
         self._ext("speckv_ext_decode_window_range", length, window, ctypes.byref(b), ctypes.byref(k), ctypes.byref(n))
         return b.value, k.value, n.value
+
+    def spec_window_range(self, length, window):
+        """The walk rule of attend_kv_spec_window (speckv_ext_spec_window_range; works without init, needs no device): (begin, rel, n_pages)
+        of a member of `length` committed positions under `window` >= 1; rel is signed."""
+        b, r, n = c_uint32(0), ctypes.c_int32(0), c_uint32(0)
+        self._ext("speckv_ext_spec_window_range", length, window, ctypes.byref(b), ctypes.byref(r), ctypes.byref(n))
+        return b.value, r.value, n.value
 
     def attend_planned(self, scheme, d_plan, n_seq, layer, d_q_f16, g, max_pos_end, sm_scale, d_out, d_lse, stream):
         """One layer of a planned batch: kernel launches only (capturable).  scheme: 4 (FP8_E4M3) or 3 (INT4_G32)."""

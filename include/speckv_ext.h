@@ -1289,8 +1289,8 @@ speckv_status_t speckv_ext_attend_kv_batch_window(uint32_t n_seq, const speckv_h
  * over the 128 channels, x sm_scale -- and its fp16 V row is weighted in fp32; it enters the same running softmax as the stored tiles.
  * A sequence with pos_end[i] == 0 gets the softmax over its visible held positions.
  * Addressing, placement (single runs only), stream rules, ordering behind pool writes and statuses are those of
- * speckv_ext_attend_kv_batch.  NOT capturable into a HIP graph.  There is no form under a sliding window: a draft step on a local layer
- * goes through speckv_ext_attend_chunk_kv.  SPECKV_ERR_INVAL besides what speckv_ext_attend_kv_batch refuses, judged before anything
+ * speckv_ext_attend_kv_batch.  NOT capturable into a HIP graph.  The form under a sliding window (a draft step on a local
+ * layer) is speckv_ext_attend_kv_spec_window, below.  SPECKV_ERR_INVAL besides what speckv_ext_attend_kv_batch refuses, judged before anything
  * else and on every engine: rows_per_pos == 0, g not a multiple of rows_per_pos, g / rows_per_pos > SPECKV_HELD_MAX - 1, a NULL
  * d_k_held, d_v_held or d_mask, mask_stride < g / rows_per_pos, a stride that is not a multiple of 8, pos_stride_elems < 8 * 128, a held
  * pointer that is not 16-byte aligned -- nothing is launched, d_out is untouched. */
@@ -1299,6 +1299,43 @@ speckv_status_t speckv_ext_attend_kv_spec(uint32_t n_seq, const speckv_handle_t*
                                           const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
                                           const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse /* optional */,
                                           void* stream);
+
+/* speckv_ext_attend_kv_spec_window: speckv_ext_attend_kv_spec on a SLIDING-WINDOW (local) layer -- the draft step of the local layers of
+ * models that interleave local and global attention, on the decode kernel and in ONE launch as well.  The arguments of
+ * speckv_ext_attend_kv_spec in the same order with `length, d_depth, window` directly behind pos_end.  An additive entry:
+ * SPECKV_EXT_ABI_VERSION stays what it is.
+ *   length  : host array, length[i] = the committed positions of sequence i, pos_end[i] (even) or pos_end[i] + 1 (the odd last position is
+ *       held position 0).  The step's new positions follow: a node of depth d sits at the absolute position length[i] + d.
+ *   d_depth : device array strided like d_mask, d_depth[i * mask_stride + j] = the depth of query position j of sequence i in the step's
+ *       tree (0 = a root; a chain: j); depths above 15 are taken as 15.  A later group of a step passes d_depth + its first position, as it
+ *       passes d_mask + it.
+ *   window  : W >= 1.  A node of depth d sees the absolute positions [lo(d), length[i] + d], lo(d) = max(0, length[i] + d + 1 - W).  Of the
+ *       STORED positions that is [lo(d), pos_end[i]), applied by the kernel PER QUERY ROW; what the node sees of the HELD positions (the
+ *       odd last position, its ancestors, itself) is the caller's to say in d_mask, as ever: the window clears the bits of held positions
+ *       in front of lo(d).
+ * The walk (speckv_ext_spec_window_range is the rule as a pure function): each member is walked from the tile of DEPTH 0's bound,
+ * begin = lo(0) & ~31, in both allocations, whatever depths the call carries -- a later group pays one extra, partly masked tile at most
+ * -- over n_pages = (pos_end[i] - begin) / 2 pages, at most ceil((W + 31) / 32) tiles whatever the length; pieces and dispatch order are
+ * decided on the pages walked.  Row r of depth d is masked over the leading skip = max(0, rel + d) <= 46 positions of the walk, rel =
+ * length[i] + 1 - W - begin (signed): a row may see nothing of a tile or of a whole piece and still comes out right.  A member no row of
+ * which sees a stored position (lo(0) >= pos_end[i]) is handled as one with nothing stored: its held positions alone; a row that sees
+ * nothing anywhere is zeros with lse = -inf.
+ * window == 0, or a window that can cut no member (length[i] + 16 <= window for every i): exactly the launches and the bits of
+ * speckv_ext_attend_kv_spec; with window == 0 neither length nor d_depth is read.
+ * Values, addressing, placement, stream rules and statuses are those of speckv_ext_attend_kv_spec.  NOT capturable into a HIP graph.
+ * SPECKV_ERR_INVAL besides what speckv_ext_attend_kv_spec refuses, judged before anything else and on every engine: a NULL length or
+ * d_depth with window != 0, a length[i] outside {pos_end[i], pos_end[i] + 1} -- nothing is launched, d_out is untouched. */
+speckv_status_t speckv_ext_attend_kv_spec_window(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                                 uint32_t layer, const void* d_q_f16, uint32_t g, uint32_t rows_per_pos, const uint32_t* pos_end,
+                                                 const uint32_t* length, const uint32_t* d_depth, uint32_t window, const void* d_k_held,
+                                                 const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask,
+                                                 uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse /* optional */, void* stream);
+
+/* The walk rule of speckv_ext_attend_kv_spec_window as a pure function (works without speckv_init, needs no device): for a member of
+ * `length` committed positions under window W >= 1, *out_begin = the first position walked (a multiple of 32), *out_n_pages = the pages
+ * walked from there (0: no row sees a stored position), *out_rel = length + 1 - W - begin, signed -- a row of depth d does not see the
+ * leading max(0, rel + min(d, 15)) positions of the walk.  SPECKV_ERR_INVAL: a NULL out pointer, window == 0. */
+speckv_status_t speckv_ext_spec_window_range(uint32_t length, uint32_t window, uint32_t* out_begin, int32_t* out_rel, uint32_t* out_n_pages);
 
 /* speckv_ext_attend_chunk_tree_window: a DRAFT TREE on a SLIDING-WINDOW (local) layer -- the tree step of the local layers of the
  * models speckv_ext_attend_chunk_window names, whose global layers take the tree step through speckv_ext_attend_chunk_masked / _split.
