@@ -238,6 +238,37 @@ __device__ __forceinline__ void put16(const RowSinkBf16Mul& d, uint32_t p0, uint
     uint8_t* r = d.row(p0);
     if (r) st16(r + 2ull * (p0 & 1023u), mul_half8_to_bf16(v, ld16(d.mul + 2ull * (p0 & 1023u))));
 }
+// The contiguous image of a fetch whose LAUNCH chooses how its stores are marked (k_fetch_decompress, the plain forms: CodecArgs::
+// keep_stores).  Non-temporal stores are the faster ones for an image nobody touches again before it has left the Infinity Cache; a
+// range that is fetched again at once, walked the other way (fetch_sweep.hpp), overwrites the lines its previous sweep wrote last
+// while they are still on die -- if they were allocated there, which plain stores do and non-temporal ones do not (profiles/
+// sweep_direction.txt).  keep is wave-uniform (a kernel argument): a scalar branch per store instruction, both forms in one kernel.
+struct ImageSink {
+    uint8_t* p;
+    uint32_t keep;
+};
+template <> struct is_row_sink<ImageSink> { static constexpr bool value = true; };      // (stores through put16)
+__device__ __forceinline__ bool wants(const ImageSink&, uint32_t) { return true; }
+__device__ __forceinline__ void st16(const ImageSink& d, uint8_t* p, uint4 v)
+{
+    if (d.keep) *(g_u32x4*)(reinterpret_cast<uintptr_t>(p)) = u32x4{v.x, v.y, v.z, v.w};
+    else st16(p, v);
+}
+__device__ __forceinline__ void put16(const ImageSink& d, uint32_t p0, uint4 v) { st16(d, d.p + 2ull * p0, v); }
+__device__ __forceinline__ void store8_f32(const ImageSink& d, uint32_t p0, const float (&y)[8])       // store8_f32 above, the policy per store
+{
+    __shared__ __attribute__((aligned(16))) uint4 stage[kWaves][128];
+    const uint32_t lane = threadIdx.x & 63u;
+    uint4* st = stage[(threadIdx.x >> 6) % kWaves];
+    wave_lds_fence();
+    st[2u * lane] = make_uint4(__float_as_uint(y[0]), __float_as_uint(y[1]), __float_as_uint(y[2]), __float_as_uint(y[3]));
+    st[2u * lane + 1u] = make_uint4(__float_as_uint(y[4]), __float_as_uint(y[5]), __float_as_uint(y[6]), __float_as_uint(y[7]));
+    wave_lds_fence();
+    const uint4 a = st[lane], b = st[64u + lane];
+    uint8_t* base = d.p + 4ull * (p0 - 8u * lane) + 16u * lane;
+    st16(d, base, a);
+    st16(d, base + 1024, b);
+}
 template <bool F32, class DST>
 __device__ __forceinline__ void store8(const DST& dst, uint32_t p0, const float (&y)[8])
 {

@@ -1115,4 +1115,21 @@ speckv_status_t speckv_ext_codec_launch_shape(uint64_t n_blocks, uint32_t n_cus,
     return SPECKV_OK;
 }
 
+speckv_status_t speckv_ext_fetch_sweep_next(uint64_t prev_first, uint64_t prev_n, uint32_t prev_descending, uint32_t prev_valid,
+                                            uint64_t first, uint64_t n, int capturing, int mode, uint32_t* out_descending,
+                                            uint32_t* out_keep_stores, uint64_t* out_state)
+{
+    if (!out_descending || !out_keep_stores || !out_state || mode > speckv::kFetchSweepAlternateNt) return SPECKV_ERR_INVAL;
+    LOCK;                                                // (speckv_ext_set_tuning writes the tuning under it)
+    const speckv::FetchSweepState prev{prev_first, prev_n, prev_descending ? 1u : 0u, prev_valid ? 1u : 0u};
+    const speckv::FetchSweepNext nx = speckv::fetch_sweep_next(prev, first, n, capturing != 0, mode < 0 ? speckv::tuning().fetch_sweep : mode);
+    *out_descending = nx.descending;
+    *out_keep_stores = nx.keep_stores;
+    out_state[0] = nx.state.first;
+    out_state[1] = nx.state.n;
+    out_state[2] = nx.state.descending;
+    out_state[3] = nx.state.valid;
+    return SPECKV_OK;
+}
+
 } // extern "C"

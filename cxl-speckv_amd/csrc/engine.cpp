@@ -479,6 +479,7 @@ void Engine::release_allocation(Allocation* a)
         free_rows_.push_back(a->row);
         a->row = kNoSlot;
     }
+    a->sweep = FetchSweepState{};         // the row's next owner starts ascending
     for (auto& ex : a->extents)
         if (ex.base) pools_[ex.pool]->free(ex.base, ex.bytes);
     a->extents.clear();

@@ -28,6 +28,7 @@
 #include "kernels.hpp"
 #include "ring_rule.hpp"
 #include "attend_geometry.hpp"
+#include "fetch_sweep.hpp"
 #include "slab_pool.hpp"
 
 #include <condition_variable>
@@ -115,6 +116,8 @@ struct Allocation {
     uint32_t entry_bytes_seen = 0;        // length_bytes of the first speckv_access (= head_dim * bytes_per_element in the shim)
     // caller streams that have been handed asynchronous work on this allocation (speckv_free waits for those only)
     std::vector<hipStream_t> user_streams;
+    // the previous kernel-path fetch_range of this allocation: the next one over the same range walks the other way (fetch_sweep.hpp)
+    FetchSweepState sweep;
 };
 
 class Engine {

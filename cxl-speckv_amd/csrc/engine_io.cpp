@@ -683,7 +683,8 @@ int Engine::fetch_range(uint64_t handle, uint64_t first, uint64_t n, void* d_dst
     // (SPECKV_REMOTE_ENGINE=kernel|copy overrides "auto").
     int choice = engine_choice ? engine_choice : tuning().remote_engine;
     const uint32_t D = static_cast<uint32_t>(a->pool_of_residue.size());
-    const bool can_copy = (a->regular || (a->packed && a->packed_regular)) && D >= 1 && D <= 8 && a->n_pages < (1ull << 28) && !is_capturing(st);
+    const bool capturing = is_capturing(st);
+    const bool can_copy = (a->regular || (a->packed && a->packed_regular)) && D >= 1 && D <= 8 && a->n_pages < (1ull << 28) && !capturing;
     if (choice == 0) {
         bool remote = false;
         for (int p : a->pool_of_residue) remote = remote || pools_[p]->device() != device_;
@@ -715,7 +716,13 @@ int Engine::fetch_range(uint64_t handle, uint64_t first, uint64_t n, void* d_dst
             c.structured_hint = looks_structured(a) ? 1 : 0;
         }
         if (c.structured_hint) st_.flat_decoder_fetches++;
+        // the same range as this allocation's previous fetch is walked the other way, with stores that stay in the Infinity Cache
+        // (fetch_sweep.hpp: what the last sweep wrote last is what the cache still holds); the state is kept once the launch is out
+        const FetchSweepNext sweep = fetch_sweep_next(a->sweep, first, n, capturing, tuning().fetch_sweep);
+        c.descending = sweep.descending;
+        c.keep_stores = sweep.keep_stores;
         HIP_TRY(launch_decompress(c, st));
+        a->sweep = sweep.state;
     }
     note_use(a, s);
     st_.dma_submitted += n;

@@ -182,9 +182,16 @@ __device__ __forceinline__ void ring_note(const CodecArgs& a, const BlockDesc& d
     atomicOr(&r.d_flags[d.page], 2u);
 }
 
+// where a block's image goes: the plain forms choose their store policy per launch (ImageSink), the others keep the bare pointer
+template <int EXT> struct FetchDst { typedef uint8_t* type; };
+template <> struct FetchDst<0> { typedef ImageSink type; };
+template <int EXT> __device__ __forceinline__ typename FetchDst<EXT>::type fetch_dst(uint8_t* p, uint32_t) { return p; }
+template <> __device__ __forceinline__ ImageSink fetch_dst<0>(uint8_t* p, uint32_t keep) { return ImageSink{p, keep}; }
+
 template <int SCHEME, int MODE, bool F32, int EXT, bool FLAT>
 __device__ __forceinline__ void fetch_decompress_body(const CodecArgs& a)
 {
+    typedef typename FetchDst<EXT>::type Dst;
     __shared__ __attribute__((aligned(16))) uint32_t lds[SCHEME == kInt8DeltaRle ? kWaves * kDecLdsWords : 4];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -208,7 +215,10 @@ __device__ __forceinline__ void fetch_decompress_body(const CodecArgs& a)
     const bool ring = EXT == 2 && a.ring_owner;                          // (launch-uniform)
     RingLook look{};
     BlockDesc cur{};
-    if (!ring) cur = load_desc<EXT>(a, i, slot0);
+    // EXT 0 only (launch_dec2 refuses the others): a descending launch decodes block n - 1 - i where an ascending one decodes i --
+    // the same waves, rounds and strides, the range walked from its top (fetch_sweep.hpp: why)
+    const bool down = EXT == 0 && a.descending;                          // (launch-uniform)
+    if (!ring) cur = load_desc<EXT>(a, down ? n - 1 - i : i, slot0);
     for (;;) {
         // the next block's descriptor is fetched while this block is decoded (ring form: in front of its own decode,
         // these launches are short and wait on one block's chain of loads, not on throughput -- and inside the loop:
@@ -216,28 +226,29 @@ __device__ __forceinline__ void fetch_decompress_body(const CodecArgs& a)
         if (ring) cur = load_desc_ring(a, i, slot0, look);
         const uint64_t nx = i + step;
         BlockDesc nxt = cur;
-        if (nx < end && !ring) nxt = load_desc<EXT>(a, nx, slot0);
+        if (nx < end && !ring) nxt = load_desc<EXT>(a, down ? n - 1 - nx : nx, slot0);
         uint32_t len = cur.len;
+        const Dst dst = fetch_dst<EXT>(cur.dst, a.keep_stores);
         if (SCHEME == kInt8DeltaRle) {
             if (len > 2u * kBlockElems) len = 2u * kBlockElems;
             uint32_t* region = lds + wave * kDecLdsWords;
-            if (!decode_rle_fast<MODE, F32, FLAT>(cur.rec, len, cur.scale, cur.dst, reinterpret_cast<uint8_t*>(region), lane,
-                                                  a.trusted != 0))
+            if (!decode_rle_fast<MODE, F32, FLAT, Dst>(cur.rec, len, cur.scale, dst, reinterpret_cast<uint8_t*>(region), lane,
+                                                       a.trusted != 0))
                 decode_rle_general<MODE, F32>(cur.rec, len, cur.scale, cur.dst, lane);
         } else if (SCHEME == kInt8) {
             if (len > kBlockElems) len = kBlockElems;
-            decode_int8<MODE, F32>(cur.rec, len, cur.scale, cur.dst, lane);
+            decode_int8<MODE, F32, Dst>(cur.rec, len, cur.scale, dst, lane);
         } else if (SCHEME == kInt4G32) {
-            decode_int4<F32>(cur.rec, len, cur.dst, lane);
+            decode_int4<F32, Dst>(cur.rec, len, dst, lane);
         } else if (SCHEME == kMxFp4) {
             // pool records are tile-planar: the codes lie mx4_code_delta behind the nibbles (the entry's scale word); raw records: 1024
-            decode_mx4<F32>(cur.rec, cur.rec + (a.recs ? 1024u : __float_as_uint(cur.scale)), len, cur.dst, lane);
+            decode_mx4<F32, Dst>(cur.rec, cur.rec + (a.recs ? 1024u : __float_as_uint(cur.scale)), len, dst, lane);
         } else if (SCHEME == kFp8E4m3) {
             if (len > kBlockElems) len = kBlockElems;
-            decode_fp8<F32>(cur.rec, len, cur.scale, cur.dst, lane);
+            decode_fp8<F32, Dst>(cur.rec, len, cur.scale, dst, lane);
         } else {
             if (len > 2u * kBlockElems) len = 2u * kBlockElems;
-            decode_fp16<F32>(cur.rec, len, cur.dst, lane);
+            decode_fp16<F32, Dst>(cur.rec, len, dst, lane);
         }
         if (lane == 0u) {
             if (ring) ring_note(a, cur, look, slot0 + static_cast<uint32_t>(i), seq0 + static_cast<uint32_t>(i));
@@ -382,6 +393,7 @@ hipError_t launch_dec2(const CodecArgs& a_in, hipStream_t s)
     if (a.ring_owner && a.alloc_list) return hipErrorInvalidValue;      // the ring form reads one allocation's row (load_desc_ring)
     if (a.done_flag && (ext != 2 || a.per_wave > 1 || a.n_dev || !a.done_count)) return hipErrorInvalidValue;
     if (ext == 3 && (a.out_f32 || a.alloc_list || a.ring_owner || a.stripe_n || !a.seq0_dev || !a.data_list)) return hipErrorInvalidValue;
+    if ((a.descending || a.keep_stores) && ext != 0) return hipErrorInvalidValue;      // staged, ring and host-word forms: their block index carries slot and sequence meaning
 #define SPECKV_LAUNCH_DEC(F32, EXT) \
     hipLaunchKernelGGL((k_fetch_decompress<SCHEME, MODE, F32, EXT>), dim3(grid), dim3(kThreads), 0, s, a)
     if (SCHEME == kInt8DeltaRle && a.structured_hint && ext <= 1) {      // data known to compress: the FLAT instantiation (plain and copy-engine-staged forms)

@@ -416,6 +416,13 @@ struct CodecArgs {
     uint32_t*       done_flag;
     uint32_t*       done_count;
     uint32_t        done_token;
+    // decompress, plain forms only (range / list, raw records; the staged, ring and host-word forms are refused): the launch walks its
+    // blocks from the top -- wave position i decodes block n - 1 - i (n after n_dev), page and destination alike.  The bytes written
+    // are the same; the order decides what a repeated sweep finds in the Infinity Cache (fetch_sweep.hpp)
+    uint32_t        descending;
+    // ... and its stores to the destination are plain instead of non-temporal, so that the lines stay in the Infinity Cache for the
+    // sweep that follows (block_codec_device.hpp: ImageSink).  The same forms only.
+    uint32_t        keep_stores;
 };
 
 hipError_t launch_compress(const CodecArgs& a, hipStream_t s);

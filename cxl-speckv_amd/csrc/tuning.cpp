@@ -34,6 +34,7 @@ const Key kKeys[] = {
     {"predict_batch_path", "SPECKV_PREDICT_BATCH_PATH", &Tuning::predict_batch_path},
     {"wgs_per_cu", "SPECKV_WGS_PER_CU", &Tuning::wgs_per_cu},
     {"rounds_consecutive", "SPECKV_ROUNDS", &Tuning::rounds_consecutive},
+    {"fetch_sweep", "SPECKV_FETCH_SWEEP", &Tuning::fetch_sweep},
     {"remote_engine", "SPECKV_REMOTE_ENGINE", &Tuning::remote_engine},
     {"copy_min_run_kb", "SPECKV_COPY_MIN_RUN_KB", &Tuning::copy_min_run_kb},
     {"slots_kind_fast", "SPECKV_SLOTS_KIND_FAST", &Tuning::slots_kind_fast},

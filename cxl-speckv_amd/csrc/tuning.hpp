@@ -37,6 +37,7 @@ struct Tuning {
     // block codec launches
     int32_t wgs_per_cu = 0;                 // SPECKV_WGS_PER_CU               grid cap of the block codec (0: default)
     int32_t rounds_consecutive = 0;         // SPECKV_ROUNDS=consecutive       a wave's blocks consecutive instead of one grid apart
+    int32_t fetch_sweep = 1;                // SPECKV_FETCH_SWEEP              fetch_range over the same range as the allocation's previous fetch: 1 the opposite direction with plain stores (fetch_sweep.hpp), 0 always ascending, 2 always descending, 3 as 1 with non-temporal stores (tests, A/B)
     // remote fetch engine: 0 per batch, 1 fused peer-load kernel, 2 copy engines (SPECKV_REMOTE_ENGINE=kernel|copy)
     int32_t remote_engine = 0;
     int32_t copy_min_run_kb = 1024;         // SPECKV_COPY_MIN_RUN_KB          shortest per-pool run the copy engines take by themselves

@@ -99,6 +99,7 @@ _EXT_SIGNATURES = {
                                       c_void_p, c_void_p],
     "speckv_ext_chunk_split_plan": [c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p],
     "speckv_ext_codec_launch_shape": [c_uint64, c_uint32, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_fetch_sweep_next": [c_uint64, c_uint64, c_uint32, c_uint32, c_uint64, c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_chunk_window": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                        c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, ctypes.c_float, c_void_p, c_void_p,
                                        c_void_p],
@@ -872,6 +873,16 @@ class SpeckvLib:
         grid, per_wave, step = c_uint32(), c_uint64(), c_uint64()
         self._ext("speckv_ext_codec_launch_shape", int(n_blocks), int(n_cus), ctypes.byref(grid), ctypes.byref(per_wave), ctypes.byref(step))
         return grid.value, per_wave.value, step.value
+
+    def fetch_sweep_next(self, prev, first, n, capturing=False, mode=-1):
+        """The direction and store marking fetch_range gives a kernel-path launch (speckv_ext_fetch_sweep_next; works without init).
+        prev = the allocation's previous fetch (first, n, descending, valid), or None; mode < 0: the tuning key fetch_sweep in force.
+        Returns (descending, keep_stores, (first, n, descending, valid))."""
+        pf, pn, pd, pv = prev if prev is not None else (0, 0, 0, 0)
+        down, keep, state = c_uint32(), c_uint32(), (c_uint64 * 4)()
+        self._ext("speckv_ext_fetch_sweep_next", int(pf), int(pn), int(pd), int(pv), int(first), int(n), int(bool(capturing)), int(mode),
+                  ctypes.byref(down), ctypes.byref(keep), state)
+        return down.value, keep.value, tuple(int(v) for v in state)
 
     def promote_to_l1(self, handle, offset):
         return self.lib.speckv_ext_promote_to_l1(handle, offset) == 0

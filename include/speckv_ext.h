@@ -850,7 +850,8 @@ speckv_status_t speckv_ext_decode_window_range(uint32_t length, uint32_t window,
  * call of the process; after that a form is changed by this call only.  Keys (= the SPECKV_<KEY> environment names, lower case):
  * attend_splits, attend_tiles_per_split, attend_general, tc_multipass, tc_scan (1 one workgroup, 2 one wave), tc_no_pre,
  * tc_no_split_tiles, td_one_pass, td_expand_per_element, flush_no_small, flush_small_words, predict_batch_path, wgs_per_cu, tc_batch_one_wg (many-tensor launches: one workgroup per tensor),
- * rounds_consecutive, remote_engine (1 kernel, 2 copy engines), copy_min_run_kb, slots_kind_fast (speckv_ext_read_slots / _write_slots:
+ * rounds_consecutive, fetch_sweep (speckv_ext_fetch_range: 1 a fetch over the same range as the allocation's previous one walks the other
+ * way and keeps its stores in the Infinity Cache, 0 always ascending, 2 always descending, 3 as 1 with non-temporal stores; speckv_ext_fetch_sweep_next), remote_engine (1 kernel, 2 copy engines), copy_min_run_kb, slots_kind_fast (speckv_ext_read_slots / _write_slots:
  * the waves run (layer, kind) fastest instead of pair fastest), attend_stream (INT4_G32 / MXFP4, several layers of one
  * sequence: N > 0 the stream form in N pieces, -1 never), attend_mx4_one_half (MXFP4 batches: 4-wave workgroups also where
  * the two-halves form applies), attend_order_as_given (batches of members of different lengths: the caller's dispatch order), attend_fold_launch (speckv_ext_attend_planned_tail: the fold always as a launch of its own), attend_layers_loop
@@ -871,6 +872,26 @@ speckv_status_t speckv_ext_set_tuning(const char* key, long long value);
  * launch nothing).  n_cus = 0: the compute units of the current device, or 256 without a device.  Works without speckv_init.
  * SPECKV_ERR_INVAL for a NULL output. */
 speckv_status_t speckv_ext_codec_launch_shape(uint64_t n_blocks, uint32_t n_cus, uint32_t* grid, uint64_t* per_wave, uint64_t* wave_step);
+
+/* speckv_ext_fetch_sweep_next: the direction in which speckv_ext_fetch_range walks the blocks of a kernel-path launch, and how it marks
+ * its stores -- the body the engine itself calls, as a pure function.  A launch decodes every block of its range either way and writes
+ * the same bytes; a descending one starts at the top of the range, and one that keeps its stores writes the destination with plain
+ * instead of non-temporal stores, so that the lines stay in the Infinity Cache.  A range larger than that cache (256 MiB of records plus
+ * destination) that is fetched again and again in ascending order finds nothing of itself on die; walked the other way every second
+ * time, a sweep starts by overwriting what the one before it wrote last, and those lines never go to memory.  The engine keeps, per
+ * allocation, its previous kernel-path fetch: prev_first, prev_n, prev_descending, prev_valid (0: none yet, or the handle was freed).
+ * With the call's first / n, `capturing` (the stream is being captured into a graph) and mode (the tuning key fetch_sweep; < 0: the
+ * value in force) it gives *out_descending, *out_keep_stores and the state after the call in out_state[4] = {first, n, descending, valid}:
+ *   mode 1   the same (first, n) as the previous fetch and n <= 393 216 blocks (beyond that the plain stores cost more than the cache
+ *            saves): the opposite direction, stores kept; anything else: ascending, non-temporal
+ *   mode 0   ascending, non-temporal;  mode 2  descending, stores kept (tests and measurements force the other form)
+ *   mode 3   the directions of mode 1 with non-temporal stores (measurements)
+ *   capturing: ascending and non-temporal whatever the mode, and the state is returned as it came (a replayed graph cannot alternate)
+ * speckv_ext_fetch_list, the copy-engine path of speckv_ext_fetch_range (which leaves the state alone) and the staged, ring and flush
+ * fetches are always ascending and non-temporal.  Works without speckv_init.  SPECKV_ERR_INVAL for a NULL output or a mode above 3. */
+speckv_status_t speckv_ext_fetch_sweep_next(uint64_t prev_first, uint64_t prev_n, uint32_t prev_descending, uint32_t prev_valid,
+                                            uint64_t first, uint64_t n, int capturing, int mode, uint32_t* out_descending,
+                                            uint32_t* out_keep_stores, uint64_t* out_state);
 
 /* Is `stream` (a hipStream_t) being captured into a HIP graph right now?  The batch entry points and speckv_ext_attend_batch_plan
  * refuse such a stream; a caller that plans ahead (SpeckvKVConnector.append) asks first.  *out_capturing = 0 for the NULL stream.
