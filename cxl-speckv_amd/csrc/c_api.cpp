@@ -263,6 +263,34 @@ speckv_status_t speckv_ext_write_slots_kmul(const speckv_handle_t* handles, cons
     return guarded([&] { return g_engine->write_slots(c, static_cast<hipStream_t>(stream)); });
 }
 
+speckv_status_t speckv_ext_read_slots_kv(const speckv_handle_t* k_handles, const speckv_handle_t* v_handles, const uint64_t* first_tokens,
+                                         const uint64_t* n_tokens, const uint64_t* slot_begins, uint32_t n_spans, const int64_t* d_slots,
+                                         uint64_t n_slots, void* const* d_caches, uint32_t layer_begin, uint32_t n_layers,
+                                         uint64_t kind_stride_bytes, uint64_t page_step, const speckv_ext_slot_rows_t* rows, void* stream)
+{
+    LOCK; NEED_INIT;
+    speckv::Engine::SlotCall c{k_handles, first_tokens, n_tokens, slot_begins, n_spans, d_slots, n_slots, d_caches, layer_begin, n_layers,
+                               kind_stride_bytes, page_step, true};
+    if (rows) { c.elem = rows->elem; c.reserved = rows->reserved; c.held_in = rows->d_held_in; c.held_out = rows->d_held_out;
+                c.held_stride = rows->held_layer_stride_bytes; }                 // (NULL: fp16 caches, no held rows)
+    c.v_handles = v_handles; c.kv = true;
+    return guarded([&] { return g_engine->read_slots_kv(c, static_cast<hipStream_t>(stream)); });
+}
+
+speckv_status_t speckv_ext_write_slots_kv(const speckv_handle_t* k_handles, const speckv_handle_t* v_handles, const uint64_t* first_tokens,
+                                          const uint64_t* n_tokens, const uint64_t* slot_begins, uint32_t n_spans, const int64_t* d_slots,
+                                          uint64_t n_slots, const void* const* d_caches, uint32_t layer_begin, uint32_t n_layers,
+                                          uint64_t kind_stride_bytes, uint64_t page_step, const speckv_ext_slot_rows_t* rows, void* stream)
+{
+    LOCK; NEED_INIT;
+    speckv::Engine::SlotCall c{k_handles, first_tokens, n_tokens, slot_begins, n_spans, d_slots, n_slots, d_caches, layer_begin, n_layers,
+                               kind_stride_bytes, page_step, true};
+    if (rows) { c.elem = rows->elem; c.reserved = rows->reserved; c.held_in = rows->d_held_in; c.held_out = rows->d_held_out;
+                c.held_stride = rows->held_layer_stride_bytes; }
+    c.v_handles = v_handles; c.kv = true;
+    return guarded([&] { return g_engine->write_slots_kv(c, static_cast<hipStream_t>(stream)); });
+}
+
 speckv_status_t speckv_ext_copy_runs(const speckv_handle_t* src, const speckv_handle_t* dst, const uint64_t* n_pages, uint32_t n_pairs,
                                      const uint64_t* run_firsts, uint32_t n_runs, void* stream)
 {

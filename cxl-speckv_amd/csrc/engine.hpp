@@ -188,9 +188,13 @@ public:
         const void* const* held_in = nullptr; void* const* held_out = nullptr; uint64_t held_stride = 0;
         // the _kmul entries: the fp16 [heads][128] K factor rows on the device, one per layer from layer_begin on; nullptr = the _ex call
         const void* k_mul = nullptr; uint64_t k_mul_stride = 0;
+        // the _kv entries (the split pool): `handles` are the FP8_E4M3 allocations with the K rows, v_handles the MXFP4 ones with the V rows
+        const uint64_t* v_handles = nullptr; bool kv = false;
     };
     int read_slots(const SlotCall& c, hipStream_t s);
     int write_slots(const SlotCall& c, hipStream_t s);
+    int read_slots_kv(const SlotCall& c, hipStream_t s);     // c.kv: the same body over both allocations of a span
+    int write_slots_kv(const SlotCall& c, hipStream_t s);
     // One chunk-attention call, filled in by its C entry: `entry` = that entry's name, for messages; the arguments all five entries
     // share; then the forms as plain values (n_splits 1 = whole sequences, window 0 = none), described above Engine::attend_chunk
     struct ChunkCall {

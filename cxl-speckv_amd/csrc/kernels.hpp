@@ -185,6 +185,44 @@ struct SlotKmulArgs {
     const uint8_t*   k_mul;           // device, 16-byte aligned, never nullptr (without a factor the call is the _ex launch)
     uint64_t         k_mul_stride;    // bytes between the layers' factor rows, a multiple of 16
 };
+// The _ex launch for the split pool (k_read_slots_kv / k_compress_slots_kv, row_transfer_kv.hip): a span is positions of TWO
+// allocations, an FP8_E4M3 one that holds its K rows and an MXFP4 one that holds its V rows, each laid out as one region per layer.
+// The waves, their (layer, kind) j, the slots, the held rows and the move waves are those of SlotExArgs; what differs is that wave j
+// takes allocation and codec j & 1 (index 0 = K, 1 = V below) and that the page of (layer, position) in the chosen allocation is
+// layer * page_step + position / 2, layer = layer_begin + (j >> 1): no factor 2 and no kind term.
+struct SlotSpanKV {
+    PageEntry* entries[2];            // the destinations (write); unused by the reader
+    float*     scale_tab[2];
+    uint32_t   region_pages[2];
+    uint32_t   scale_run[2];
+    uint32_t   table_row[2];          // DevAlloc rows of the sources (read)
+    uint32_t   first_token;
+    uint32_t   n_tokens;
+    uint32_t   first_pair;            // exclusive prefix of pair counts
+    uint32_t   reserved;
+    uint64_t   slot_begin;
+};
+struct SlotKVArgs {
+    struct Pages {                    // SlotArgs without a scheme: the codecs are fixed by the kind
+        const SlotSpanKV* spans;
+        const uint64_t*   caches;
+        const int64_t*    slots;
+        const DevAlloc*   tab;
+        const uint8_t*    zeros;
+        uint64_t          n_slots;
+        uint64_t          kind_stride;
+        uint64_t          page_step;
+        uint32_t          n_spans;
+        uint32_t          n_pairs;
+        uint32_t          n_layers;
+        uint32_t          layer_begin;
+        uint32_t          kind_fast;
+    } a;
+    const SlotHeld*  held;            // as SlotExArgs
+    uint64_t         held_stride;
+    uint32_t         n_moves;
+    uint32_t         bf16;
+};
 
 // One (source, destination) pair of a record-copy launch (CopyArgs::pairs; copy_records.hip): the stored records of pages
 // [run_firsts[r], run_firsts[r] + n_pages), every run r of the launch, go from the allocation in table row `src_row` to the same
@@ -440,6 +478,8 @@ hipError_t launch_compress_slots_ex(const SlotExArgs& a, hipStream_t s);
 hipError_t launch_read_slots_ex(const SlotExArgs& a, hipStream_t s);
 hipError_t launch_compress_slots_kmul(const SlotKmulArgs& a, hipStream_t s);
 hipError_t launch_read_slots_kmul(const SlotKmulArgs& a, hipStream_t s);
+hipError_t launch_compress_slots_kv(const SlotKVArgs& a, hipStream_t s);     // (row_transfer_kv.hip)
+hipError_t launch_read_slots_kv(const SlotKVArgs& a, hipStream_t s);
 
 // FPGACacheEngine::compress / ::decompress over a tensor of any length (tensor_compress.hip, tensor_decompress.hip): one scale, one delta chain and
 // one run-length stream across the whole tensor.  d_rle: 16-byte aligned, room for 2n bytes rounded up to 16; d_ws:

@@ -6,6 +6,9 @@
 //                                              (Engine::write_slots / read_slots: paged caches)
 //   k_compress_slots_ex / k_read_slots_ex      the same for caches that hold bf16 and for spans with held rows; their SlotKmulArgs
 //                                              instances multiply K by a per-channel factor on the way (the connector's K pre-scale)
+// (The split pool's pair, k_compress_slots_kv / k_read_slots_kv -- a K and a V allocation per span, both codecs in one launch --
+// is row_transfer_kv.hip; what the slot kernels of both units share, slot_work and the move of a held row, is
+// slot_transfer_device.hpp.)
 //
 // A translation unit of its own: the headline kernel of kernels.hip is pinned by the hash of its instructions, and these kernels
 // share the block codec's device code (block_codec_device.hpp), not its launch path.  The unit contains kernels only -- every
@@ -19,6 +22,7 @@
 // registers (no scratch: the build checks it).
 #include "kernels.hpp"
 #include "block_codec_device.hpp"
+#include "slot_transfer_device.hpp"
 
 #include <type_traits>
 
@@ -161,44 +165,7 @@ hipError_t launch_read_pairs(const ReadPairArgs& a, hipStream_t s)
 // row either.  Everything up to here is the same for all lanes of a wave (it depends on blockIdx and the wave number alone) and
 // is loaded once per wave.
 namespace {
-struct SlotWork {
-    const SlotSpan* g;
-    uint32_t j;                       // (layer, kind) of the launch: layer_begin + (j >> 1), j & 1
-    uint32_t pair;                    // position pair of the allocation
-    const uint8_t* base;              // caches[j >> 1] + (j & 1) * kind_stride
-    int64_t  slot[2];                 // of the even and the odd position; -1 = no row
-};
-__device__ __forceinline__ bool slot_work(const SlotArgs& a, uint32_t wave, SlotWork* w)
-{
-    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
-    const uint32_t per = 2u * a.n_layers;
-    if (i >= static_cast<uint64_t>(a.n_pairs) * per) return false;   // (whole waves leave: the bodies have no workgroup barrier)
-    uint32_t pp, j;
-    if (a.kind_fast) { pp = static_cast<uint32_t>(i / per); j = static_cast<uint32_t>(i - static_cast<uint64_t>(pp) * per); }
-    else             { j = static_cast<uint32_t>(i / a.n_pairs); pp = static_cast<uint32_t>(i - static_cast<uint64_t>(j) * a.n_pairs); }
-    uint32_t lo = 0, hi = a.n_spans;                                 // spans without pairs share their successor's prefix and are passed over
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a.spans[mid].first_pair <= pp) lo = mid; else hi = mid;
-    }
-    const SlotSpan* g = a.spans + lo;
-    const uint32_t first = g->first_token, n = g->n_tokens;
-    const uint32_t pair = (first >> 1) + (pp - g->first_pair);
-    const int64_t t0 = 2ll * pair - static_cast<int64_t>(first);     // -1 where the span begins on an odd position
-    const int64_t n_slots = static_cast<int64_t>(a.n_slots);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int64_t t = t0 + h;
-        int64_t s = -1;
-        if (t >= 0 && t < static_cast<int64_t>(n)) s = a.slots[g->slot_begin + static_cast<uint64_t>(t)];
-        w->slot[h] = (s >= 0 && s < n_slots) ? s : -1;
-    }
-    w->g = g;
-    w->j = j;
-    w->pair = pair;
-    w->base = reinterpret_cast<const uint8_t*>(a.caches[j >> 1]) + static_cast<uint64_t>(j & 1u) * a.kind_stride;
-    return true;
-}
+typedef SlotWorkT<SlotSpan> SlotWork;      // (found by slot_work, slot_transfer_device.hpp)
 
 template <int SCHEME, int MODE>
 __global__ __launch_bounds__(kThreads) void k_read_slots(SlotArgs a)
@@ -292,36 +259,6 @@ hipError_t launch_read_slots(const SlotArgs& a, hipStream_t s)
 // two 16-byte loads and stores per lane, converted in registers where the cache holds bf16, no record touched.  Which way a wave
 // goes depends on blockIdx and the wave number alone.
 namespace {
-enum { kMoveCopy = 0, kMoveToBf16 = 1, kMoveFromBf16 = 2 };
-__device__ __forceinline__ void move_row(const uint8_t* src, uint8_t* dst, uint32_t lane, int conv)     // src == nullptr: zeros
-{
-#pragma unroll
-    for (uint32_t h = 0; h < 2u; ++h) {
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (src) v = ld16(src + 1024u * h + 16u * lane);
-        if (conv == kMoveToBf16) v = half8_to_bf16(v);
-        else if (conv == kMoveFromBf16) v = bf16_to_half8(v);
-        st16(dst + 1024u * h + 16u * lane, v);
-    }
-}
-// move wave m's work: false = it has none.  *held_row = the held row of its span and (layer, kind), *cache_row = the row of the
-// span's last position in the cache, nullptr where its slot names no row
-__device__ __forceinline__ bool move_work(const SlotExArgs& x, uint64_t m, bool out, uint8_t** held_row, uint8_t** cache_row)
-{
-    if (m >= x.n_moves) return false;
-    const uint32_t per = 2u * x.a.n_layers;
-    const uint32_t sp = static_cast<uint32_t>(m / per), j = static_cast<uint32_t>(m - static_cast<uint64_t>(sp) * per);
-    const uint64_t h = out ? x.held[sp].out[j & 1u] : x.held[sp].in[j & 1u];
-    if (!h) return false;
-    const SlotSpan* g = x.a.spans + sp;
-    if (g->n_tokens == 0) return false;
-    const int64_t s = x.a.slots[g->slot_begin + g->n_tokens - 1u];
-    *held_row = reinterpret_cast<uint8_t*>(h) + static_cast<uint64_t>(j >> 1) * x.held_stride;
-    *cache_row = (s >= 0 && s < static_cast<int64_t>(x.a.n_slots))
-        ? reinterpret_cast<uint8_t*>(x.a.caches[j >> 1]) + static_cast<uint64_t>(j & 1u) * x.a.kind_stride + static_cast<uint64_t>(s) * 2048u : nullptr;
-    return true;
-}
-
 template <int SCHEME, int MODE, bool BF16>
 __global__ __launch_bounds__(kThreads) void k_read_slots_ex(SlotExArgs x)
 {

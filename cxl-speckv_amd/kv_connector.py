@@ -50,7 +50,7 @@ Only plain device pointers cross into the library; torch is used for device buff
 import numbers
 from typing import Dict, List, Optional, Sequence
 
-from .kv_shared import PARENTS_RULE, SPLITS_RULE, SharedPrefixSteps, _is_int, tail_index
+from .kv_shared import PARENTS_RULE, SPLITS_RULE, SharedPrefixSteps, _is_int, paged_cache_geometry, tail_index
 from .speckv_ctypes import HELD_MAX, SpeckvLib
 
 PAGE = 4096
@@ -421,25 +421,9 @@ class SpeckvKVConnector(SharedPrefixSteps):
         [2, blocks, block_size, heads, dim] fp16 tensor whose slots are 2048-byte rows one after the other -- else None.
         bf16=True (the fused route): the caches may all be bfloat16 instead, and the element type (SLOT_ELEM_*) comes third.
         kscale=True (the fused route with the factor inside the launch): a K pre-scale does not shut the route."""
-        import torch
-        if (self._kscale is not None and not kscale) or len(caches) != self.L:
+        if self._kscale is not None and not kscale:
             return None
-        geo = None
-        dtype = caches[0].dtype if bf16 and len(caches) and caches[0].dtype == torch.bfloat16 else torch.float16
-        for c in caches:
-            if c.dtype != dtype or c.dim() != 5 or c.shape[0] != 2 or c.shape[3] * c.shape[4] * 2 != 2048:
-                return None
-            if tuple(c.stride()[2:]) != (c.shape[3] * c.shape[4], c.shape[4], 1) or c.stride(1) != c.shape[2] * 1024:
-                return None
-            if c.data_ptr() % 16 or (c.stride(0) * 2) % 16:
-                return None
-            g = (c.shape[1] * c.shape[2], c.stride(0) * 2)
-            if geo is not None and g != geo:
-                return None
-            geo = g
-        if bf16 and geo is not None:
-            return geo + (1 if dtype == torch.bfloat16 else 0,)
-        return geo
+        return paged_cache_geometry(caches, self.L, bf16)[0]          # (kv_shared.py: the split connector judges its caches by the same)
 
     def _held_tail(self, r):
         """(K address, V address) of request r's tail for a fused paged call -- fp16, 16-byte aligned, a layer every H * D elements;

@@ -30,6 +30,37 @@ def tail_index(reqs):
     return tail_idx, rank
 
 
+def paged_cache_geometry(caches, n_layers, bf16=False):
+    """Whether the one-launch paged transfers (speckv_ext_read_slots / _write_slots and their _ex, _kmul and _kv forms) can address
+    `caches`: per layer a [2, blocks, block_size, heads, dim] fp16 tensor whose slots are 2048-byte rows one block after the other,
+    16-byte aligned, the same for all n_layers caches.  bf16=True: the caches may all be bfloat16 instead.  Only shapes, strides,
+    dtype and alignment are looked at.  Returns (geometry, None) or (None, what was wrong); geometry = (slots per cache, bytes
+    between the K and the V plane), with bf16=True the element type (SLOT_ELEM_*: 0 fp16, 1 bf16) third."""
+    import torch
+    if len(caches) != n_layers:
+        return None, f"{len(caches)} caches for {n_layers} layers"
+    geo = None
+    dtype = caches[0].dtype if bf16 and len(caches) and caches[0].dtype == torch.bfloat16 else torch.float16
+    for c in caches:
+        if c.dtype != dtype:
+            return None, f"a cache of {c.dtype} among caches of {dtype}" + ("" if bf16 else " (fp16 only)")
+        if c.dim() != 5 or c.shape[0] != 2 or c.shape[3] * c.shape[4] * 2 != 2048:
+            return None, f"a cache of shape {tuple(c.shape)}: [2, blocks, block_size, heads, dim] with heads * dim * 2 == 2048 bytes is needed"
+        if tuple(c.stride()[2:]) != (c.shape[3] * c.shape[4], c.shape[4], 1) or c.stride(1) != c.shape[2] * 1024:
+            return None, f"a cache with strides {tuple(c.stride())}: its slots must be 2048-byte rows one block after the other"
+        if c.data_ptr() % 16 or (c.stride(0) * 2) % 16:
+            return None, "a cache whose K or V plane is not 16-byte aligned"
+        g = (c.shape[1] * c.shape[2], c.stride(0) * 2)
+        if geo is not None and g != geo:
+            return None, "caches that differ in their slot count or in the distance between their K and V planes"
+        geo = g
+    if geo is None:
+        return None, "no caches"
+    if bf16:
+        return geo + (1 if dtype == torch.bfloat16 else 0,), None
+    return geo, None
+
+
 class SharedPrefixSteps:
     def _pool_check(self, what):
         pass

@@ -26,19 +26,24 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
                                         those methods issue it with the log-sum-exp kept, then ONE speckv_ext_attend_prefix_fold_kv launch
                                         that reads the prefix's FP8 keys and MXFP4 values once per 64 query rows and folds them in
   commit                                the accepted prefix of a step into the pool: one speckv_ext_write_pairs per allocation
+  kv_rows                               the stored rows of one layer and kind as fp16: one speckv_ext_fetch_range on the K or the V allocation
+  load_paged / store_paged              positions between the pool and per-layer paged caches ([2, blocks, block_size, 8, 128], fp16 or
+                                        bf16: vLLM's blocks), ONE speckv_ext_read_slots_kv / _write_slots_kv launch over both allocations
+                                        and every layer; odd edges (a tail, a seam between two calls) travel as held rows
 
 The bodies of attend_shared and attend_chunk_shared, the judgement of their lists (_shared_args, _shared_judge) and the judging half
 of attend_chunk (_chunk_judge, _chunk_rows) are SharedPrefixSteps' (kv_shared.py), the same code SpeckvKVConnector runs; what is this
 class's own there is the (K, V) handle arrays of a prefix, its decode and chunk step, the fold entry and the depth table.
 
 Not in this class: the planned and captured decode route (plan_step, HIP graphs: attend stages its descriptors
-per call), attend_spec over a shared prefix or for several layers at once, commit(nodes=path), load_paged /
-store_paged, fork, truncate, begin_step and the K pre-scale; a shared prefix is one level deep and one layer per call."""
+per call), attend_spec over a shared prefix or for several layers at once, commit(nodes=path), fork, truncate, begin_step and
+the K pre-scale (load_paged / store_paged have none either); the vLLM adapter builds a SpeckvKVConnector; a shared prefix is one
+level deep and one layer per call."""
 from typing import Dict, Optional, Sequence
 
 from . import kv_connector as _kc
 from .kv_connector import SpeckvKVConnector
-from .kv_shared import SharedPrefixSteps, _is_int, tail_index
+from .kv_shared import SharedPrefixSteps, _is_int, paged_cache_geometry, tail_index
 from .speckv_ctypes import SpeckvLib
 
 K_SCHEME, V_SCHEME = 4, 5                # SPECKV_COMP_FP8_E4M3, SPECKV_COMP_MXFP4
@@ -134,6 +139,160 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         r.length = n
         self._epoch += 1
         return [k, v]
+
+    # ------------------------------------------------------------------ rows and paged caches (vLLM's blocks)
+    def kv_rows(self, req_id: int, layer: int, kind: int, pos_begin: int = 0, pos_end: Optional[int] = None):
+        """The stored rows [pos_begin, pos_end) of one layer (default: all of them) and kind (0 K, 1 V) as an fp16 tensor
+        [positions][heads][dim], tail included; the contract of SpeckvKVConnector.kv_rows.  ONE speckv_ext_fetch_range on the K or
+        the V allocation over the pages that hold the rows: the E4M3 values times their block scale, or the fp16 values of the MXFP4
+        records."""
+        import torch
+        r = self.requests[req_id]
+        pos_end = r.length if pos_end is None else pos_end
+        if not 0 <= pos_begin <= pos_end <= r.length:
+            raise ValueError(f"rows [{pos_begin}, {pos_end}) of a request with {r.length} positions")
+        if kind not in (0, 1) or not 0 <= layer < self.L:
+            raise ValueError(f"layer {layer} / kind {kind} outside 0..{self.L - 1} / 0..1")
+        even = r.length & ~1
+        lo, hi = pos_begin & ~1, min((pos_end + 1) & ~1, even)          # whole pages (2 positions each) of the stored part
+        out = torch.empty((max(hi, pos_end) - lo, self.H, self.D), dtype=torch.float16, device="cuda")
+        if hi > lo:
+            with self._On(self, None) as st:
+                self.lib.fetch_range(r.v_handle if kind else r.k_handle, self._page(layer, lo), (hi - lo) // 2, out.data_ptr(), False,
+                                     st.cuda_stream)
+        if pos_end > even:                                               # the odd last position lives in the tail
+            out[even - lo] = (r.tail_v if kind else r.tail_k)[layer]
+        return out[pos_begin - lo:pos_end - lo]
+
+    @staticmethod
+    def paged_plan(lengths: Sequence[int], firsts: Optional[Sequence[int]], counts: Sequence[int]):
+        """The pure part of load_paged (firsts given) and store_paged (firsts=None: every span starts at its request's length): per
+        span (first_token, n_tokens, slot_begin, held_in, held_out) as the one library call takes them.  slot_begin = the counts in
+        front.  Read: held_in exactly when the span is not empty and ends on the request's odd last position -- that row lives in the
+        tail, not in a page; never held_out.  Write: held_in exactly when a non-empty span starts on an odd stored boundary (the tail
+        completes its first pair), held_out exactly when it is not empty and the new length is odd (the new tail); an empty span
+        names the even position below its request's length, so that nothing of it is odd.  Raises ValueError for a span outside its
+        request (read) or malformed counts; no connector state."""
+        lengths, counts = [int(n) for n in lengths], [int(c) for c in counts]
+        write = firsts is None
+        firsts = lengths if write else [int(f) for f in firsts]
+        if len(counts) != len(lengths) or len(firsts) != len(lengths):
+            raise ValueError("paged_plan: one first position and one count per request")
+        plan, at = [], 0
+        for n, f, c in zip(lengths, firsts, counts):
+            if c < 0 or n < 0 or f < 0 or (not write and f + c > n):
+                raise ValueError(f"rows [{f}, {f} + {c}) of a request with {n} positions")
+            if write:
+                plan.append((f if c else f & ~1, c, at, bool(c and f & 1), bool(c and (f + c) & 1)))
+            else:
+                plan.append((f, c, at, bool(c and n & 1 and f + c == n), False))
+            at += c
+        return plan
+
+    def _paged_call(self, what, req_ids, counts, slot_mapping, caches):
+        """the judging both paged methods share -> (requests, counts, (slots per cache, kind stride, element type))"""
+        import torch
+        reqs = [self.requests[rid] for rid in req_ids]
+        counts = [int(c) for c in counts]
+        if len(counts) != len(reqs) or any(c < 0 for c in counts):
+            raise ValueError(f"{what}: one non-negative count per request")
+        if not isinstance(slot_mapping, torch.Tensor) or slot_mapping.dtype != torch.int64 or slot_mapping.dim() != 1 \
+                or not slot_mapping.is_contiguous() or slot_mapping.numel() != sum(counts):
+            raise ValueError(f"{what}: slot_mapping must be one contiguous int64 device tensor, the spans concatenated")
+        geo, wrong = paged_cache_geometry(caches, self.L, bf16=True)
+        if geo is None:                                               # no row route behind this class: the refusal names the cause
+            raise ValueError(f"{what}: {wrong}")
+        return reqs, counts, geo
+
+    @staticmethod
+    def _held_pair(r):
+        """(K address, V address, the tensors) of a request's tail as a held row: fp16, contiguous, 16-byte aligned"""
+        ok = lambda t: t.is_contiguous() and t.data_ptr() % 16 == 0
+        if not (ok(r.tail_k) and ok(r.tail_v)):
+            r.tail_k, r.tail_v = r.tail_k.contiguous().clone(), r.tail_v.contiguous().clone()
+        return r.tail_k.data_ptr(), r.tail_v.data_ptr(), [r.tail_k, r.tail_v]
+
+    def load_paged(self, req_ids: Sequence[int], firsts: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None):
+        """Pool -> paged caches; the contract of SpeckvKVConnector.load_paged(fused=True) over the split pool.  Positions [firsts[i],
+        firsts[i] + counts[i]) of request req_ids[i] go into the slots slot_mapping[b_i : b_i + counts[i]] (b_i = the counts in front:
+        ONE int64 device tensor for the call) of `caches`, per layer a [2, blocks, block_size, 8, 128] fp16 or bf16 tensor: the K
+        plane from the request's FP8_E4M3 allocation, the V plane from its MXFP4 allocation -- the bits of kv_rows, for bf16 caches
+        each rounded once.  Exactly ONE speckv_ext_read_slots_kv call for all requests, layers and both kinds; a span that ends on a
+        request's odd last position hands tail_k / tail_v over as the held row.  A slot < 0 or beyond the cache is skipped.  Nothing
+        is launched when every count is 0.  Changes no state.
+        There is no other route in this class: caches of another geometry (paged_cache_geometry, kv_shared.py) are a ValueError that
+        names what was wrong; what the library refuses passes through as SpeckvError."""
+        import numpy as np
+        reqs, counts, (n_slots, kind_stride, elem) = self._paged_call("load_paged", req_ids, counts, slot_mapping, caches)
+        if len(firsts) != len(reqs):
+            raise ValueError("load_paged: one first position per request")
+        plan = self.paged_plan([r.length for r in reqs], firsts, counts)
+        if not any(counts):
+            return
+        held, any_held = np.zeros(2 * len(reqs), dtype=np.uint64), False
+        for i, (r, (_, _, _, h_in, _)) in enumerate(zip(reqs, plan)):
+            if h_in:
+                held[2 * i], held[2 * i + 1], _ = self._held_pair(r)
+                any_held = True
+        with self._On(self, stream) as st:
+            self.lib.read_slots_kv(np.asarray([r.k_handle for r in reqs], dtype=np.uint64), np.asarray([r.v_handle for r in reqs], dtype=np.uint64),
+                                   np.asarray([p[0] for p in plan], dtype=np.uint64), np.asarray([p[1] for p in plan], dtype=np.uint64),
+                                   np.asarray([p[2] for p in plan], dtype=np.uint64), slot_mapping.data_ptr(), n_slots,
+                                   np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride, self.region_pages, st.cuda_stream,
+                                   elem=elem, held_in=held if any_held else None, held_stride=self.H * self.D * 2)
+
+    def store_paged(self, req_ids: Sequence[int], counts: Sequence[int], slot_mapping, caches, stream=None):
+        """Paged caches -> pool; the contract of SpeckvKVConnector.store_paged(fused=True) over the split pool.  Request req_ids[i]
+        gets counts[i] more positions, read from the slots slot_mapping[b_i : b_i + counts[i]] of `caches` (as load_paged): the K
+        plane's rows are encoded as FP8_E4M3 into its K allocation, the V plane's as MXFP4 into its V allocation -- from bf16 caches
+        the records of row.to(float16).  Exactly ONE speckv_ext_write_slots_kv call.  A request of odd length gives its tail as the
+        held row that completes its pair; a new odd last position comes back through held rows -- one [tails][layers][heads][dim]
+        fp16 tensor per kind for the call, row j becoming that request's tail_k / tail_v.  Lengths and the step bookkeeping move as
+        in write_prefill.  A slot < 0 or beyond the cache is stored as a row of zeros.  Returns the tensors the launch reads (the
+        held-in tails): hold them until the stream has passed the call; the caches and the mapping stay unchanged until then too.
+        A request named twice, length + count > max_tokens, a malformed slot_mapping or caches of another geometry raise ValueError
+        before any state changes."""
+        import numpy as np
+        import torch
+        reqs, counts, (n_slots, kind_stride, elem) = self._paged_call("store_paged", req_ids, counts, slot_mapping, caches)
+        if len(set(req_ids)) != len(reqs):
+            raise ValueError("store_paged: a request named twice")
+        for r, c in zip(reqs, counts):
+            if r.length + c > self.T:
+                raise ValueError(f"{r.length} + {c} positions in a request built for {self.T}")
+        plan = self.paged_plan([r.length for r in reqs], None, counts)
+        if not any(counts):
+            return []
+        n = len(reqs)
+        h_in, h_out, read = np.zeros(2 * n, dtype=np.uint64), np.zeros(2 * n, dtype=np.uint64), []
+        tails = [i for i, p in enumerate(plan) if p[4]]
+        for i, (r, p) in enumerate(zip(reqs, plan)):
+            if p[3]:
+                h_in[2 * i], h_in[2 * i + 1], keep = self._held_pair(r)
+                read += keep
+        with self._On(self, stream) as st:
+            tk = tv = None
+            if tails:
+                with torch.cuda.stream(st):
+                    tk = torch.empty((len(tails), self.L, self.H, self.D), dtype=torch.float16, device=slot_mapping.device)
+                    tv = torch.empty_like(tk)
+                row = tk[0].numel() * 2
+                for j, i in enumerate(tails):
+                    h_out[2 * i], h_out[2 * i + 1] = tk.data_ptr() + j * row, tv.data_ptr() + j * row
+            self.lib.write_slots_kv(np.asarray([r.k_handle for r in reqs], dtype=np.uint64), np.asarray([r.v_handle for r in reqs], dtype=np.uint64),
+                                    np.asarray([p[0] for p in plan], dtype=np.uint64), np.asarray([p[1] for p in plan], dtype=np.uint64),
+                                    np.asarray([p[2] for p in plan], dtype=np.uint64), slot_mapping.data_ptr(), n_slots,
+                                    np.asarray([c.data_ptr() for c in caches], dtype=np.uint64), 0, kind_stride, self.region_pages, st.cuda_stream,
+                                    elem=elem, held_in=h_in if read else None, held_stride=self.H * self.D * 2,
+                                    held_out=h_out if tails else None)
+        for r, c in zip(reqs, counts):
+            if c:
+                r.tail_k = r.tail_v = None
+                r.length += c
+        for j, i in enumerate(tails):
+            reqs[i].tail_k, reqs[i].tail_v = tk[j], tv[j]
+        self._epoch += 1
+        return read
 
     # ------------------------------------------------------------------ attention
     def _step_tails(self, req_ids, reqs):

@@ -88,6 +88,10 @@ _EXT_SIGNATURES = {
                                    c_uint64, c_void_p, c_void_p, c_uint64, c_void_p],
     "speckv_ext_write_slots_kmul": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint64,
                                     c_uint64, c_void_p, c_void_p, c_uint64, c_void_p],
+    "speckv_ext_read_slots_kv": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32,
+                                 c_uint64, c_uint64, c_void_p, c_void_p],
+    "speckv_ext_write_slots_kv": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32,
+                                  c_uint64, c_uint64, c_void_p, c_void_p],
     "speckv_ext_copy_runs": [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
     "speckv_ext_attend_chunk": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                 c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
@@ -381,14 +385,17 @@ class SpeckvLib:
                     page_step, stream)
 
     def _slots_ex(self, entry, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step,
-                  stream, elem, held_in, held_out, held_stride, reserved=0, k_mul=()):
+                  stream, elem, held_in, held_out, held_stride, reserved=0, k_mul=(), v_handles=None):
         n, nl = len(handles), len(caches)
         hs, fs, ns, bs = (as_arr(x, c_uint64, n) for x in (handles, first_tokens, n_tokens, slot_begins))
+        if v_handles is not None:                                                      # the _kv entries: two handle arrays in front
+            hs = (hs, as_arr(v_handles, c_uint64, n))
         hin = None if held_in is None else as_arr(held_in, c_uint64, 2 * n)            # (kept alive across the call)
         hout = None if held_out is None else as_arr(held_out, c_uint64, 2 * n)
         at = lambda a: None if a is None else (a.value if isinstance(a, c_void_p) else ctypes.addressof(a))
         rows = SlotRows(elem, reserved, at(hin), at(hout), held_stride)
-        self._ext(entry, hs, fs, ns, bs, n, c_void_p(d_slots), n_slots, as_arr(caches, c_uint64, nl), layer_begin, nl, kind_stride, page_step,
+        self._ext(entry, *(hs if v_handles is not None else (hs,)), fs, ns, bs, n, c_void_p(d_slots), n_slots, as_arr(caches, c_uint64, nl),
+                  layer_begin, nl, kind_stride, page_step,
                   ctypes.cast(ctypes.pointer(rows), c_void_p), *k_mul, c_void_p(stream))     # k_mul: the _kmul entries' two arguments
 
     def read_slots_ex(self, handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride, page_step,
@@ -425,6 +432,21 @@ class SpeckvLib:
         already and is not multiplied.  Arguments as read_slots_kmul."""
         self._slots_ex("speckv_ext_write_slots_kmul", handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin,
                        kind_stride, page_step, stream, elem, held_in, held_out, held_stride, reserved, (c_void_p(k_mul or None), k_mul_stride))
+
+    def read_slots_kv(self, k_handles, v_handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride,
+                      page_step, stream, elem=SLOT_ELEM_FP16, held_in=None, held_stride=0, held_out=None, reserved=0):
+        """read_slots_ex for the split pool (speckv_ext_read_slots_kv): span i = positions of the FP8_E4M3 allocation k_handles[i],
+        whose rows go to the K plane of the caches, and of the MXFP4 allocation v_handles[i], whose rows go to the V plane; the page
+        of (layer, position) is layer * page_step + position // 2 in either.  ONE launch.  Everything else as read_slots_ex."""
+        self._slots_ex("speckv_ext_read_slots_kv", k_handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin,
+                       kind_stride, page_step, stream, elem, held_in, held_out, held_stride, reserved, v_handles=v_handles)
+
+    def write_slots_kv(self, k_handles, v_handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin, kind_stride,
+                       page_step, stream, elem=SLOT_ELEM_FP16, held_in=None, held_stride=0, held_out=None, reserved=0):
+        """write_slots_ex for the split pool (speckv_ext_write_slots_kv): the K plane's rows are encoded as FP8_E4M3 into
+        k_handles[i], the V plane's as MXFP4 into v_handles[i], in ONE launch.  Arguments as read_slots_kv."""
+        self._slots_ex("speckv_ext_write_slots_kv", k_handles, first_tokens, n_tokens, slot_begins, d_slots, n_slots, caches, layer_begin,
+                       kind_stride, page_step, stream, elem, held_in, held_out, held_stride, reserved, v_handles=v_handles)
 
     def copy_runs(self, src, dst, n_pages, run_firsts, stream):
         """The stored records of pages [run_firsts[r], run_firsts[r] + n_pages[i]), every run r, copied from allocation src[i] to the same

@@ -273,6 +273,41 @@ speckv_status_t speckv_ext_write_slots_kmul(const speckv_handle_t* handles, cons
                                             uint64_t page_step, const speckv_ext_slot_rows_t* rows,
                                             const void* d_k_mul /* device, fp16 [heads][128] per layer, or NULL */,
                                             uint64_t k_mul_layer_stride_bytes, void* stream);
+/* The _ex entries for the split pool ("K8V4"): span i is positions of TWO allocations, k_handles[i] (SPECKV_COMP_FP8_E4M3) holding its
+ * K rows and v_handles[i] (SPECKV_COMP_MXFP4) holding its V rows, still ONE launch per call.  Additive: SPECKV_EXT_ABI_VERSION stays
+ * as it is.  The contract is that of speckv_ext_read_slots_ex / speckv_ext_write_slots_ex -- spans, d_slots, d_caches (K plane at 0, V
+ * plane at kind_stride_bytes), elem, held rows, ordering, placement, sealed destinations, statistics (2 * n_layers pages per position
+ * pair) -- except:
+ *   addressing  each allocation holds ONE kind, one region per layer: the page of (layer, position) is layer * page_step +
+ *               position / 2 in the K allocation and in the V allocation alike, for the layers [layer_begin, layer_begin + n_layers).
+ *   read        the K plane of a slot gets the bits speckv_ext_fetch_range writes as fp16 for that page of the K allocation, the V
+ *               plane those of the V allocation; bf16 caches get each value rounded once, as above.  A page never written gives zeros.
+ *   write       the records in each allocation are those speckv_ext_write_runs stores there for the same rows laid out contiguously
+ *               (from bf16 caches: for row.to(float16)).  Held rows are [heads][128] fp16 per kind as above; both allocations of a
+ *               span are unpacked if sealed and their cached pages invalidated.
+ *   rows        may be NULL: fp16 caches and no held rows.
+ *   SPECKV_ERR_INVAL    everything the _ex entries refuse with it (different schemes aside), and: k_handles[i] not FP8_E4M3 or
+ *                       v_handles[i] not MXFP4, k_handles[i] == v_handles[i], a NULL handle array; write: two spans that share a
+ *                       page in either allocation
+ *   SPECKV_ERR_GENERAL  an unknown handle, a span that leaves its region (first + n > 2 * page_step), pages that leave either allocation
+ * Every refusal launches nothing and leaves the held-out rows untouched.  Not built: a K factor (_kmul) for the split pool, capture
+ * into a HIP graph, rows of any other size than 2048 bytes. */
+speckv_status_t speckv_ext_read_slots_kv(const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                         const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                         const uint64_t* slot_begins, uint32_t n_spans,
+                                         const int64_t* d_slots /* device */, uint64_t n_slots,
+                                         void* const* d_caches /* host array of n_layers device pointers */,
+                                         uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                         uint64_t page_step, const speckv_ext_slot_rows_t* rows /* NULL = fp16, no held rows */,
+                                         void* stream);
+speckv_status_t speckv_ext_write_slots_kv(const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                          const uint64_t* first_tokens, const uint64_t* n_tokens,
+                                          const uint64_t* slot_begins, uint32_t n_spans,
+                                          const int64_t* d_slots /* device */, uint64_t n_slots,
+                                          const void* const* d_caches /* host array of n_layers device pointers */,
+                                          uint32_t layer_begin, uint32_t n_layers, uint64_t kind_stride_bytes,
+                                          uint64_t page_step, const speckv_ext_slot_rows_t* rows /* NULL = fp16, no held rows */,
+                                          void* stream);
 /* Fork: the STORED RECORDS of page runs copied from one allocation to another, nothing decoded.  Pair i copies pages
  * [run_firsts[r], run_firsts[r] + n_pages[i]) for every run r < n_runs from allocation src[i] to the same page numbers of
  * allocation dst[i] (in the shim layout the runs are the 2 * num_layers (layer, kind) regions and n_pages[i] = positions / 2: a
