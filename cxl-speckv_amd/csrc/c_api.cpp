@@ -298,6 +298,24 @@ speckv_status_t speckv_ext_copy_runs(const speckv_handle_t* src, const speckv_ha
     return guarded([&] { return g_engine->copy_runs(src, dst, n_pages, n_pairs, run_firsts, n_runs, static_cast<hipStream_t>(stream)); });
 }
 
+speckv_status_t speckv_ext_read_pairs_kv(const speckv_handle_t* k_handles, const speckv_handle_t* v_handles, const uint64_t* first_pages,
+                                         void* const* d_rows, uint32_t n_pairs, uint64_t page_step, uint32_t n_layers,
+                                         uint64_t layer_stride_bytes, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] { return g_engine->read_pairs_kv(k_handles, v_handles, first_pages, d_rows, n_pairs, page_step, n_layers, layer_stride_bytes,
+                                                        static_cast<hipStream_t>(stream)); });
+}
+
+speckv_status_t speckv_ext_copy_runs_kv(const speckv_handle_t* k_src, const speckv_handle_t* v_src, const speckv_handle_t* k_dst,
+                                        const speckv_handle_t* v_dst, const uint64_t* n_pages, uint32_t n_pairs, const uint64_t* run_firsts,
+                                        uint32_t n_runs, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] { return g_engine->copy_runs_kv(k_src, v_src, k_dst, v_dst, n_pages, n_pairs, run_firsts, n_runs,
+                                                       static_cast<hipStream_t>(stream)); });
+}
+
 speckv_status_t speckv_ext_write_runs(speckv_handle_t handle, const uint64_t* first_pages, const void* const* d_srcs, uint32_t n_runs,
                                       uint64_t n_pages_each, void* stream)
 {

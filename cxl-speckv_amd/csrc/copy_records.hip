@@ -14,50 +14,10 @@
 // the host computed the prefixes), then run = (i - prefix) / n_pages and page = run_firsts[run] + (i - prefix) % n_pages: consecutive
 // waves take consecutive pages of one run.  The index is the same for all lanes; what it selects is read once and kept in scalar
 // registers.  Everything written goes out through vector stores.
-#include "kernels.hpp"
-#include "attend_device.hpp"         // u32x4
+#include "copy_records_device.hpp"    // the accesses and the scalar bookkeeping, shared with copy_records_kv.hip
 
 namespace speckv {
 namespace {
-
-constexpr uint32_t kCopyWaves = 4;
-constexpr uint32_t kCopyWgsPerCu = 8;            // 32 waves per CU: the kernel needs few registers and no LDS
-
-typedef u32x4 __attribute__((address_space(1))) gc_u32x4;
-__device__ __forceinline__ u32x4 cp_ld16(const uint8_t* p)
-{
-    return __builtin_nontemporal_load((const gc_u32x4*)(reinterpret_cast<uintptr_t>(p)));
-}
-__device__ __forceinline__ void cp_st16(uint8_t* p, u32x4 v)
-{
-    __builtin_nontemporal_store(v, (gc_u32x4*)(reinterpret_cast<uintptr_t>(p)));
-}
-template <typename T> __device__ __forceinline__ void cp_store(void* p, T v)
-{
-    typedef T __attribute__((address_space(1))) G;
-    *(G*)(reinterpret_cast<uintptr_t>(p)) = v;
-}
-// a page-table entry read at an address all lanes share, kept in scalar registers
-struct EntryWords { uint64_t addr; uint32_t len, scale_bits; };
-__device__ __forceinline__ EntryWords cp_entry(const PageEntry* e)
-{
-    const u32x4 w = *(const gc_u32x4*)(reinterpret_cast<uintptr_t>(e));
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(w.x), hi = __builtin_amdgcn_readfirstlane(w.y);
-    return EntryWords{(static_cast<uint64_t>(hi) << 32) | lo, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(w.z)),
-                      static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(w.w))};
-}
-__device__ __forceinline__ uint64_t cp_uniform(uint64_t v)
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v)), hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-// the longest record of a scheme: what a copy is cut to, so that entry words that are not a record length can never carry a store
-// beyond the destination's slot (slots are at least this long: stride_for, engine_internal.hpp)
-template <int SCHEME> constexpr uint32_t max_rec_bytes()
-{
-    return SCHEME == kInt8 || SCHEME == kFp8E4m3 ? kBlockElems : SCHEME == kInt4G32 ? kInt4RecBytes : SCHEME == kMxFp4 ? kMx4RecBytes : 2u * kBlockElems;
-}
 
 template <int SCHEME>
 __global__ __launch_bounds__(64 * kCopyWaves) void k_copy_records(const CopyPair* __restrict__ pairs, const uint64_t* __restrict__ run_firsts,

@@ -178,6 +178,16 @@ public:
                    uint32_t n_layers, uint64_t layer_stride, hipStream_t s);
     int copy_runs(const uint64_t* src, const uint64_t* dst, const uint64_t* n_pages, uint32_t n_pairs, const uint64_t* run_firsts,
                   uint32_t n_runs, hipStream_t s);
+    // The split pool's forms (speckv_ext_read_pairs_kv / _copy_runs_kv): an FP8_E4M3 allocation with the K rows and an MXFP4 one with the V rows
+    // per pair, one descriptor slot and ONE launch over both.  pairs_read / runs_copy are the bodies, per side: one side = the entries above.
+    int read_pairs_kv(const uint64_t* k_handles, const uint64_t* v_handles, const uint64_t* firsts, void* const* d_rows, uint32_t n_pairs,
+                      uint64_t step, uint32_t n_layers, uint64_t layer_stride, hipStream_t s);
+    int copy_runs_kv(const uint64_t* k_src, const uint64_t* v_src, const uint64_t* k_dst, const uint64_t* v_dst, const uint64_t* n_pages,
+                     uint32_t n_pairs, const uint64_t* run_firsts, uint32_t n_runs, hipStream_t s);
+    int pairs_read(const uint64_t* handles, const uint64_t* v_handles, bool kv, const uint64_t* firsts, void* const* d_rows, uint32_t n_pairs,
+                   uint64_t step, uint32_t n_layers, uint64_t layer_stride, hipStream_t s);
+    int runs_copy(const uint64_t* const src[2], const uint64_t* const dst[2], bool kv, const uint64_t* n_pages, uint32_t n_pairs,
+                  const uint64_t* run_firsts, uint32_t n_runs, hipStream_t s);
     // Paged-cache transfers (engine_slots.cpp): spans of positions between the pool and the slots of a caller's paged cache
     struct SlotCall {
         const uint64_t *handles, *first_tokens, *n_tokens, *slot_begins; uint32_t n_spans;

@@ -338,48 +338,89 @@ int Engine::write_pairs(const uint64_t* handles, const uint64_t* firsts, const v
 int Engine::read_pairs(const uint64_t* handles, const uint64_t* firsts, void* const* d_rows, uint32_t n_pairs, uint64_t step,
                        uint32_t n_layers, uint64_t layer_stride, hipStream_t s)
 {
-    if (null_) return no_data_path("speckv_ext_read_pairs");
-    if (!handles || !firsts || !d_rows || step == 0 || !s || layer_stride % 16u) return SPECKV_ERR_INVAL;
+    return pairs_read(handles, nullptr, false, firsts, d_rows, n_pairs, step, n_layers, layer_stride, s);
+}
+
+// speckv_ext_read_pairs_kv: read_pairs for the split pool.  Pair i names TWO allocations, handles[i] (FP8_E4M3, the K rows) and
+// v_handles[i] (MXFP4, the V rows), each laid out as one region per layer: layer l of the pair is page firsts[i] + l * step of
+// either, for l < n_layers REAL layers.  One descriptor slot and ONE launch (k_read_pairs_kv) for both allocations of every pair.
+int Engine::read_pairs_kv(const uint64_t* k_handles, const uint64_t* v_handles, const uint64_t* firsts, void* const* d_rows, uint32_t n_pairs,
+                          uint64_t step, uint32_t n_layers, uint64_t layer_stride, hipStream_t s)
+{
+    return pairs_read(k_handles, v_handles, true, firsts, d_rows, n_pairs, step, n_layers, layer_stride, s);
+}
+
+// The body of both.  Everything it does per allocation -- find and the judgement repeated after descriptor_slot, the page-range
+// check, note_use -- it does for every side of a pair: one side (`handles`), or with kv two (`handles` = K, `v_handles` = V).  A
+// single-allocation call takes exactly the path it took before.
+int Engine::pairs_read(const uint64_t* handles, const uint64_t* v_handles, bool kv, const uint64_t* firsts, void* const* d_rows, uint32_t n_pairs,
+                       uint64_t step, uint32_t n_layers, uint64_t layer_stride, hipStream_t s)
+{
+    if (null_) return no_data_path(kv ? "speckv_ext_read_pairs_kv" : "speckv_ext_read_pairs");
+    if (!handles || (kv && !v_handles) || !firsts || !d_rows || step == 0 || !s || layer_stride % 16u) return SPECKV_ERR_INVAL;
     if (n_pairs == 0 || n_layers == 0) return SPECKV_OK;
-    const uint64_t n_each = 2ull * n_layers;
-    const auto check = [&](uint32_t i, Allocation** out) -> int {
-        Allocation* a = find(handles[i]);
-        if (!a) return SPECKV_ERR_GENERAL;
-        for (uint32_t k = 0; k < 4; ++k)
-            if (reinterpret_cast<uintptr_t>(d_rows[4u * i + k]) % 16u) return SPECKV_ERR_INVAL;
-        if (a->scheme != find(handles[0])->scheme) return SPECKV_ERR_INVAL;
-        if (firsts[i] >= a->n_pages || (n_each - 1) > (a->n_pages - 1 - firsts[i]) / step) return SPECKV_ERR_GENERAL;
-        *out = a;
+    const int n_sides = kv ? 2 : 1;
+    const uint64_t n_each = 2ull * n_layers;                  // pages per pair
+    const uint64_t n_side = kv ? n_layers : n_each;           // ... of which one allocation holds: firsts[i] + j * step, j < n_side
+    std::vector<Allocation*> as(n_pairs), vs(kv ? n_pairs : 0u);
+    const auto check = [&](uint32_t i) -> int {
+        for (int side = 0; side < n_sides; ++side) {
+            Allocation* a = find((side ? v_handles : handles)[i]);
+            if (!a) return SPECKV_ERR_GENERAL;
+            for (uint32_t k = 0; side == 0 && k < 4; ++k)
+                if (reinterpret_cast<uintptr_t>(d_rows[4u * i + k]) % 16u) return SPECKV_ERR_INVAL;
+            if (kv ? a->scheme != (side ? SPECKV_COMP_MXFP4 : SPECKV_COMP_FP8_E4M3) : a->scheme != find(handles[0])->scheme) return SPECKV_ERR_INVAL;
+            if (firsts[i] >= a->n_pages || (n_side - 1) > (a->n_pages - 1 - firsts[i]) / step) return SPECKV_ERR_GENERAL;
+            (side ? vs : as)[i] = a;
+        }
+        if (kv && as[i]->layout.num_tokens != vs[i]->layout.num_tokens) return SPECKV_ERR_INVAL;
         return SPECKV_OK;
     };
-    std::vector<Allocation*> as(n_pairs);
-    for (uint32_t i = 0; i < n_pairs; ++i) RC_TRY(check(i, &as[i]));
+    for (uint32_t i = 0; i < n_pairs; ++i) RC_TRY(check(i));
     DeviceScope device_scope(device_);
-    const size_t bytes = static_cast<size_t>(n_pairs) * sizeof(ReadPair);
+    const size_t bytes = static_cast<size_t>(n_pairs) * (kv ? sizeof(ReadPairKV) : sizeof(ReadPair));
     int slot = 0;
     void *staged = nullptr, *d_slot = nullptr;
     RC_TRY(descriptor_slot(bytes, &slot, &staged, &d_slot));  // may release the ABI lock: every pair is judged again
-    for (uint32_t i = 0; i < n_pairs; ++i) RC_TRY(check(i, &as[i]));
+    for (uint32_t i = 0; i < n_pairs; ++i) RC_TRY(check(i));
     for (uint32_t i = 0; i < n_pairs; ++i) {
         void* const* r = d_rows + 4u * i;
-        static_cast<ReadPair*>(staged)[i] = ReadPair{as[i]->row, 0u, firsts[i],
-            {static_cast<uint8_t*>(r[0]), static_cast<uint8_t*>(r[1]), static_cast<uint8_t*>(r[2]), static_cast<uint8_t*>(r[3])}};
+        if (kv)
+            static_cast<ReadPairKV*>(staged)[i] = ReadPairKV{{as[i]->row, vs[i]->row}, firsts[i],
+                {static_cast<uint8_t*>(r[0]), static_cast<uint8_t*>(r[1]), static_cast<uint8_t*>(r[2]), static_cast<uint8_t*>(r[3])}};
+        else
+            static_cast<ReadPair*>(staged)[i] = ReadPair{as[i]->row, 0u, firsts[i],
+                {static_cast<uint8_t*>(r[0]), static_cast<uint8_t*>(r[1]), static_cast<uint8_t*>(r[2]), static_cast<uint8_t*>(r[3])}};
     }
     if (!is_capturing(s))
         for (auto& w : write_evs_)
             if (w.s != s) HIP_TRY(hipStreamWaitEvent(s, w.ev, 0));      // (`dirty` is about the engine's stream, not this one)
     HIP_TRY(hipMemcpyAsync(d_slot, staged, bytes, hipMemcpyHostToDevice, s));
-    ReadPairArgs ra{};
-    ra.pairs = static_cast<const ReadPair*>(d_slot);
-    ra.tab = d_tab_;
-    ra.n_pairs = n_pairs;
-    ra.n_layers = n_layers;
-    ra.page_step = step;
-    ra.layer_stride = layer_stride;
-    ra.scheme = as[0]->scheme;
-    ra.quant_mode = quant_mode_;
-    HIP_TRY(launch_read_pairs(ra, s));
-    for (uint32_t i = 0; i < n_pairs; ++i) note_use(as[i], s);           // speckv_free waits for this stream
+    if (kv) {
+        ReadPairKVArgs ra{};
+        ra.pairs = static_cast<const ReadPairKV*>(d_slot);
+        ra.tab = d_tab_;
+        ra.n_pairs = n_pairs;
+        ra.n_layers = n_layers;
+        ra.page_step = step;
+        ra.layer_stride = layer_stride;
+        HIP_TRY(launch_read_pairs_kv(ra, s));
+    } else {
+        ReadPairArgs ra{};
+        ra.pairs = static_cast<const ReadPair*>(d_slot);
+        ra.tab = d_tab_;
+        ra.n_pairs = n_pairs;
+        ra.n_layers = n_layers;
+        ra.page_step = step;
+        ra.layer_stride = layer_stride;
+        ra.scheme = as[0]->scheme;
+        ra.quant_mode = quant_mode_;
+        HIP_TRY(launch_read_pairs(ra, s));
+    }
+    for (uint32_t i = 0; i < n_pairs; ++i) {                   // speckv_free waits for this stream
+        note_use(as[i], s);
+        if (kv) note_use(vs[i], s);
+    }
     const uint64_t n = static_cast<uint64_t>(n_pairs) * n_each;
     st_.total_decompressions += n;
     st_.dma_submitted += n;
@@ -399,8 +440,33 @@ int Engine::read_pairs(const uint64_t* handles, const uint64_t* firsts, void* co
 int Engine::copy_runs(const uint64_t* src, const uint64_t* dst, const uint64_t* n_pages, uint32_t n_pairs, const uint64_t* run_firsts,
                       uint32_t n_runs, hipStream_t s)
 {
-    if (null_) return no_data_path("speckv_ext_copy_runs");
-    if (!src || !dst || !n_pages || !run_firsts || !s) return SPECKV_ERR_INVAL;
+    const uint64_t* const from[2] = {src, nullptr};
+    const uint64_t* const to[2] = {dst, nullptr};
+    return runs_copy(from, to, false, n_pages, n_pairs, run_firsts, n_runs, s);
+}
+
+// speckv_ext_copy_runs_kv: copy_runs for the split pool.  Pair i copies the same pages in TWO allocation pairs, k_src[i] -> k_dst[i]
+// (FP8_E4M3, the K rows) and v_src[i] -> v_dst[i] (MXFP4, the V rows), with one descriptor slot and ONE launch (k_copy_records_kv).
+int Engine::copy_runs_kv(const uint64_t* k_src, const uint64_t* v_src, const uint64_t* k_dst, const uint64_t* v_dst, const uint64_t* n_pages,
+                         uint32_t n_pairs, const uint64_t* run_firsts, uint32_t n_runs, hipStream_t s)
+{
+    const uint64_t* const from[2] = {k_src, v_src};
+    const uint64_t* const to[2] = {k_dst, v_dst};
+    return runs_copy(from, to, true, n_pages, n_pairs, run_firsts, n_runs, s);
+}
+
+// The body of both.  Everything it does per allocation -- find and the judgement repeated after every wait, the page-range check,
+// unpacking a sealed destination, dropping cached destination pages, the host mirror, note_use -- it does for every side of a pair:
+// one (src[0] -> dst[0]), or with kv two (index 0 = K, 1 = V).  An allocation that is written is named once across both sides and
+// is not read.  A single-allocation call takes exactly the path it took before.
+int Engine::runs_copy(const uint64_t* const src[2], const uint64_t* const dst[2], bool kv, const uint64_t* n_pages, uint32_t n_pairs,
+                      const uint64_t* run_firsts, uint32_t n_runs, hipStream_t s)
+{
+    if (null_) return no_data_path(kv ? "speckv_ext_copy_runs_kv" : "speckv_ext_copy_runs");
+    const int n_sides = kv ? 2 : 1;
+    for (int side = 0; side < n_sides; ++side)
+        if (!src[side] || !dst[side]) return SPECKV_ERR_INVAL;
+    if (!n_pages || !run_firsts || !s) return SPECKV_ERR_INVAL;
     uint64_t most = 0;
     for (uint32_t i = 0; i < n_pairs; ++i) most = std::max(most, n_pages[i]);
     if (n_pairs == 0 || n_runs == 0 || most == 0) return SPECKV_OK;
@@ -413,41 +479,50 @@ int Engine::copy_runs(const uint64_t* src, const uint64_t* dst, const uint64_t* 
         if (order[r] - order[r - 1] < most) return SPECKV_ERR_INVAL;
     {
         std::vector<uint64_t> written, read;
-        for (uint32_t i = 0; i < n_pairs; ++i) {
-            if (src[i] == dst[i]) return SPECKV_ERR_INVAL;
-            if (n_pages[i]) { written.push_back(dst[i]); read.push_back(src[i]); }
-        }
+        for (int side = 0; side < n_sides; ++side)
+            for (uint32_t i = 0; i < n_pairs; ++i) {
+                if (src[side][i] == dst[side][i]) return SPECKV_ERR_INVAL;
+                if (n_pages[i]) { written.push_back(dst[side][i]); read.push_back(src[side][i]); }
+            }
         std::sort(written.begin(), written.end());
         std::sort(read.begin(), read.end());
         if (std::adjacent_find(written.begin(), written.end()) != written.end()) return SPECKV_ERR_INVAL;
         for (uint64_t h : written)
             if (std::binary_search(read.begin(), read.end(), h)) return SPECKV_ERR_INVAL;
     }
-    std::vector<Allocation*> from(n_pairs), to(n_pairs);
+    std::vector<Allocation*> from[2], to[2];
+    for (int side = 0; side < n_sides; ++side) { from[side].resize(n_pairs); to[side].resize(n_pairs); }
     const auto check = [&]() -> int {
         int scheme = -1;
         for (uint32_t i = 0; i < n_pairs; ++i) {
-            Allocation *a = find(src[i]), *b = find(dst[i]);
-            if (!a || !b) return SPECKV_ERR_GENERAL;
-            if (scheme < 0) scheme = a->scheme;
-            if (a->scheme != scheme || b->scheme != scheme) return SPECKV_ERR_INVAL;
-            if (n_pages[i] && (order.back() + n_pages[i] > a->n_pages || order.back() + n_pages[i] > b->n_pages)) return SPECKV_ERR_GENERAL;
-            from[i] = a;
-            to[i] = b;
+            for (int side = 0; side < n_sides; ++side) {
+                Allocation *a = find(src[side][i]), *b = find(dst[side][i]);
+                if (!a || !b) return SPECKV_ERR_GENERAL;
+                if (kv) scheme = side ? SPECKV_COMP_MXFP4 : SPECKV_COMP_FP8_E4M3;
+                else if (scheme < 0) scheme = a->scheme;
+                if (a->scheme != scheme || b->scheme != scheme) return SPECKV_ERR_INVAL;
+                if (n_pages[i] && (order.back() + n_pages[i] > a->n_pages || order.back() + n_pages[i] > b->n_pages)) return SPECKV_ERR_GENERAL;
+                from[side][i] = a;
+                to[side][i] = b;
+            }
+            if (kv && (from[0][i]->layout.num_tokens != from[1][i]->layout.num_tokens || to[0][i]->layout.num_tokens != to[1][i]->layout.num_tokens))
+                return SPECKV_ERR_INVAL;
         }
         return SPECKV_OK;
     };
     RC_TRY(check());
-    for (uint32_t i = 0; i < n_pairs; ++i)
-        if (n_pages[i] && to[i]->packed) {                      // sealed destinations go back into slots first
-            DeviceScope scope(device_);
-            RC_TRY(unpack(to[i]));
-            RC_TRY(check());
-        }
-    const auto each_dst_page = [&](auto&& f) {
+    for (int side = 0; side < n_sides; ++side)
         for (uint32_t i = 0; i < n_pairs; ++i)
-            for (uint32_t r = 0; r < n_runs; ++r)
-                for (uint64_t p = run_firsts[r]; p < run_firsts[r] + n_pages[i]; ++p) f(to[i], p);
+            if (n_pages[i] && to[side][i]->packed) {            // sealed destinations go back into slots first
+                DeviceScope scope(device_);
+                RC_TRY(unpack(to[side][i]));
+                RC_TRY(check());
+            }
+    const auto each_dst_page = [&](auto&& f) {
+        for (int side = 0; side < n_sides; ++side)
+            for (uint32_t i = 0; i < n_pairs; ++i)
+                for (uint32_t r = 0; r < n_runs; ++r)
+                    for (uint64_t p = run_firsts[r]; p < run_firsts[r] + n_pages[i]; ++p) f(to[side][i], p);
     };
     bool cached = false;
     each_dst_page([&](Allocation* a, uint64_t p) { cached = cached || (res_flags(a, p) & 3u) != 0; });
@@ -459,7 +534,7 @@ int Engine::copy_runs(const uint64_t* src, const uint64_t* dst, const uint64_t* 
         RC_TRY(flush_mirror());
         RC_TRY(wait_stream());
     }
-    const size_t pair_bytes = static_cast<size_t>(n_pairs) * sizeof(CopyPair);     // (a multiple of 8: the run firsts follow)
+    const size_t pair_bytes = static_cast<size_t>(n_pairs) * (kv ? sizeof(CopyPairKV) : sizeof(CopyPair));     // (a multiple of 8: the run firsts follow)
     const size_t bytes = pair_bytes + static_cast<size_t>(n_runs) * sizeof(uint64_t);
     int slot = 0;
     void *staged = nullptr, *d_slot = nullptr;
@@ -467,30 +542,49 @@ int Engine::copy_runs(const uint64_t* src, const uint64_t* dst, const uint64_t* 
     RC_TRY(check());
     uint64_t n_recs = 0;
     for (uint32_t i = 0; i < n_pairs; ++i) {
-        if (n_pages[i] && to[i]->packed) return SPECKV_ERR_GENERAL;          // sealed again by another caller meanwhile
-        static_cast<CopyPair*>(staged)[i] = CopyPair{to[i]->d_entries, to[i]->d_scale_tab, to[i]->region_pages, to[i]->scale_run,
-                                                     from[i]->row, 0u, n_pages[i], n_recs};
-        n_recs += n_pages[i] * n_runs;
+        for (int side = 0; side < n_sides; ++side)
+            if (n_pages[i] && to[side][i]->packed) return SPECKV_ERR_GENERAL;          // sealed again by another caller meanwhile
+        const Allocation* t = to[0][i];
+        if (kv)
+            static_cast<CopyPairKV*>(staged)[i] = CopyPairKV{{t->d_entries, to[1][i]->d_entries}, t->d_scale_tab, t->region_pages, t->scale_run,
+                                                             {from[0][i]->row, from[1][i]->row}, n_pages[i], n_recs};
+        else
+            static_cast<CopyPair*>(staged)[i] = CopyPair{t->d_entries, t->d_scale_tab, t->region_pages, t->scale_run, from[0][i]->row, 0u, n_pages[i], n_recs};
+        n_recs += n_pages[i] * n_runs * static_cast<uint64_t>(n_sides);
     }
     memcpy(static_cast<uint8_t*>(staged) + pair_bytes, run_firsts, static_cast<size_t>(n_runs) * sizeof(uint64_t));
     if (!is_capturing(s))
         for (auto& w : write_evs_)
             if (w.s != s) HIP_TRY(hipStreamWaitEvent(s, w.ev, 0));
     HIP_TRY(hipMemcpyAsync(d_slot, staged, bytes, hipMemcpyHostToDevice, s));
-    CopyArgs ca{};
-    ca.pairs = static_cast<const CopyPair*>(d_slot);
-    ca.run_firsts = reinterpret_cast<const uint64_t*>(static_cast<const uint8_t*>(d_slot) + pair_bytes);
-    ca.tab = d_tab_;
-    ca.n_pairs = n_pairs;
-    ca.n_runs = n_runs;
-    ca.n_recs = n_recs;
-    ca.n_cus = cus();
-    ca.scheme = from[0]->scheme;
-    HIP_TRY(launch_copy_records(ca, s));
-    for (uint32_t i = 0; i < n_pairs; ++i) {                  // the kernel is queued: host mirror first, then the orderings
-        note_use(from[i], s);                                 // speckv_free of either side waits for this stream
-        note_use(to[i], s);
+    const uint64_t* d_firsts = reinterpret_cast<const uint64_t*>(static_cast<const uint8_t*>(d_slot) + pair_bytes);
+    if (kv) {
+        CopyKVArgs ca{};
+        ca.pairs = static_cast<const CopyPairKV*>(d_slot);
+        ca.run_firsts = d_firsts;
+        ca.tab = d_tab_;
+        ca.n_pairs = n_pairs;
+        ca.n_runs = n_runs;
+        ca.n_recs = n_recs;
+        ca.n_cus = cus();
+        HIP_TRY(launch_copy_records_kv(ca, s));
+    } else {
+        CopyArgs ca{};
+        ca.pairs = static_cast<const CopyPair*>(d_slot);
+        ca.run_firsts = d_firsts;
+        ca.tab = d_tab_;
+        ca.n_pairs = n_pairs;
+        ca.n_runs = n_runs;
+        ca.n_recs = n_recs;
+        ca.n_cus = cus();
+        ca.scheme = from[0][0]->scheme;
+        HIP_TRY(launch_copy_records(ca, s));
     }
+    for (int side = 0; side < n_sides; ++side)
+        for (uint32_t i = 0; i < n_pairs; ++i) {              // the kernel is queued: host mirror first, then the orderings
+            note_use(from[side][i], s);                       // speckv_free of either side waits for this stream
+            note_use(to[side][i], s);
+        }
     each_dst_page([&](Allocation* a, uint64_t p) {
         if (a->scheme != SPECKV_COMP_FP16) a->flags[p] |= 4u; else a->flags[p] &= ~4u;
     });

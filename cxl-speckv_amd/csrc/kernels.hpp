@@ -107,6 +107,22 @@ struct ReadPair {
     uint64_t first;
     uint8_t* row[4];                  // K even, K odd, V even, V odd
 };
+// The pair read for the split pool (k_read_pairs_kv, row_transfer_kv.hip): a pair names an FP8_E4M3 allocation with its K rows and an
+// MXFP4 allocation with its V rows, each laid out as one region per layer.  Block j < 2 * n_layers (layer j >> 1, kind j & 1) is page
+// first + (j >> 1) * page_step of the allocation in table row table_row[kind]; rows as in ReadPair.
+struct ReadPairKV {
+    uint32_t table_row[2];            // DevAlloc rows: K, V
+    uint64_t first;
+    uint8_t* row[4];                  // K even, K odd, V even, V odd
+};
+struct ReadPairKVArgs {
+    const ReadPairKV* pairs;          // device array
+    const DevAlloc*   tab;
+    uint32_t          n_pairs;
+    uint32_t          n_layers;       // real layers: one region per layer in either allocation
+    uint64_t          page_step;
+    uint64_t          layer_stride;   // bytes, a multiple of 16
+};
 struct ReadPairArgs {
     const ReadPair* pairs;            // device array
     const DevAlloc* tab;              // the device allocation table
@@ -251,6 +267,31 @@ struct CopyArgs {
 };
 // ONE launch; a source page never written leaves the destination page never written (rec_bytes 0, its slot zero bytes)
 hipError_t launch_copy_records(const CopyArgs& a, hipStream_t s);
+// The record copy for the split pool (k_copy_records_kv, copy_records_kv.hip): a pair is TWO (source, destination) pairs of
+// allocations, index 0 = the FP8_E4M3 ones with the K rows, 1 = the MXFP4 ones with the V rows, and the same pages are copied in both.
+// scale_tab / region_pages / scale_run are the K destination's (an MXFP4 allocation has no scale table).  first_rec = the sum of
+// 2 * n_runs * n_pages over the pairs in front of this one; of a pair's records the first n_runs * n_pages are the K side's, run by
+// run as in CopyPair, the second n_runs * n_pages the V side's.
+struct CopyPairKV {
+    PageEntry* entries[2];            // destinations: K, V
+    float*     scale_tab;             // K destination
+    uint32_t   region_pages;
+    uint32_t   scale_run;
+    uint32_t   src_row[2];            // DevAlloc rows of the sources: K, V
+    uint64_t   n_pages;
+    uint64_t   first_rec;
+};
+struct CopyKVArgs {
+    const CopyPairKV* pairs;          // device array, and behind it in the same staged slot ...
+    const uint64_t*   run_firsts;     // ... the first page of every run (device array)
+    const DevAlloc*   tab;
+    uint32_t          n_pairs;
+    uint32_t          n_runs;
+    uint64_t          n_recs;         // 2 * n_runs * the sum of n_pages
+    uint32_t          n_cus;
+};
+// ONE launch over both allocations of every pair; per record what launch_copy_records does for its scheme
+hipError_t launch_copy_records_kv(const CopyKVArgs& a, hipStream_t s);
 
 // One sequence of a chunk-attention launch (ChunkArgs::seqs; attend_chunk.hip): pos_end (even) stored positions whose K pages are
 // k_first + p / 2 and whose V pages are v_first + p / 2 of the allocation in table row `table_row`, base in {0, 1} held odd last
@@ -480,6 +521,7 @@ hipError_t launch_compress_slots_kmul(const SlotKmulArgs& a, hipStream_t s);
 hipError_t launch_read_slots_kmul(const SlotKmulArgs& a, hipStream_t s);
 hipError_t launch_compress_slots_kv(const SlotKVArgs& a, hipStream_t s);     // (row_transfer_kv.hip)
 hipError_t launch_read_slots_kv(const SlotKVArgs& a, hipStream_t s);
+hipError_t launch_read_pairs_kv(const ReadPairKVArgs& a, hipStream_t s);
 
 // FPGACacheEngine::compress / ::decompress over a tensor of any length (tensor_compress.hip, tensor_decompress.hip): one scale, one delta chain and
 // one run-length stream across the whole tensor.  d_rle: 16-byte aligned, room for 2n bytes rounded up to 16; d_ws:

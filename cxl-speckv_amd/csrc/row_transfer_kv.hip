@@ -2,7 +2,8 @@
 // k_read_slots_ex and k_compress_slots_ex (row_transfer.hip) with both codecs in one launch.  A span names two allocations, an
 // FP8_E4M3 one with the K rows and an MXFP4 one with the V rows (SlotSpanKV, kernels.hpp); wave j = (layer, kind) of a page takes
 // allocation and codec j & 1.  The cache side, the held rows, the move waves and both wave orders are the _ex kernels': the work of
-// a wave is found by the same slot_work and move_work (slot_transfer_device.hpp).
+// a wave is found by the same slot_work and move_work (slot_transfer_device.hpp).  Beside them k_read_pairs_kv, k_read_pairs
+// (row_transfer.hip) with both codecs: the rollback and the fork of split requests (Engine::read_pairs_kv).
 //
 // A translation unit of its own: row_transfer.o holds the single-allocation families and nothing else (tests/test_commit_cpu.py
 // reads its symbols), and those kernels' register figures must not move with what is added here.
@@ -88,6 +89,37 @@ __global__ __launch_bounds__(kThreads) void k_compress_slots_kv(SlotKVArgs x)
     else compress_block<kFp8E4m3, kRefExact>(t, page, src, lds, lane, wave);
 }
 
+// k_read_pairs (row_transfer.hip) with both codecs: the rollback and the fork of split requests (Engine::read_pairs_kv).  Wave i is
+// block j = i % (2 * n_layers) of pair i / (2 * n_layers) -- layer j >> 1, kind j & 1 -- and decodes page first + (j >> 1) *
+// page_step of the pair's K allocation (kind 0, decode_fp8) or of its V allocation (kind 1, decode_mx4 with the tile-planar codes
+// PageEntry::scale points to) into the pair's two rows of that kind, layer_stride bytes further on per layer.  n_layers counts REAL
+// layers: a single-kind allocation has one region per layer, so there is no factor 2 and no kind term in the page.  The record is
+// found through the allocation table and the page's entry (any placement, a sealed source); a row that is nullptr is not stored
+// and, in the FP8 body, not read.  One block per wave, no LDS, no workgroup barrier.
+__global__ __launch_bounds__(kThreads) void k_read_pairs_kv(ReadPairKVArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
+    const uint32_t per = 2u * a.n_layers;
+    if (i >= static_cast<uint64_t>(a.n_pairs) * per) return;        // (whole waves leave: the body has no workgroup barrier)
+    const uint32_t pi = static_cast<uint32_t>(i / per), j = static_cast<uint32_t>(i - static_cast<uint64_t>(pi) * per);
+    const ReadPairKV* g = a.pairs + pi;
+    const uint32_t kind = j & 1u;                                    // wave-uniform: allocation and codec
+    const uint64_t off = static_cast<uint64_t>(j >> 1) * a.layer_stride;
+    uint8_t* const even = g->row[2u * kind];
+    uint8_t* const odd = g->row[2u * kind + 1u];
+    const RowSink dst{even ? even + off : nullptr, odd ? odd + off : nullptr};
+    if (!dst.even && !dst.odd) return;
+    const PageEntry* entries = a.tab[g->table_row[kind]].entries;
+    PageEntry e{0, 0, 1.0f};
+    if (entries) e = entries[g->first + static_cast<uint64_t>(j >> 1) * a.page_step];     // a row freed meanwhile decodes as a never-written page
+    const uint8_t* rec = reinterpret_cast<const uint8_t*>(e.pool_addr);
+    const uint32_t len = e.rec_bytes;
+    if (kind) decode_mx4<false, RowSink>(rec, rec + __float_as_uint(e.scale), len, dst, lane);
+    else decode_fp8<false, RowSink>(rec, len > kBlockElems ? kBlockElems : len, e.scale, dst, lane);
+}
+
 // what both launchers ask of a SlotKVArgs (slot_ex_args_ok, row_transfer.hip); *grid = one page or one moved row per wave, 0 =
 // nothing to do
 bool slot_kv_args_ok(const SlotKVArgs& x, uint32_t* grid)
@@ -119,6 +151,15 @@ hipError_t launch_read_slots_kv(const SlotKVArgs& x, hipStream_t s)
     if (grid == 0) return hipSuccess;
     if (x.bf16) hipLaunchKernelGGL((k_read_slots_kv<true>), dim3(grid), dim3(kThreads), 0, s, x);
     else hipLaunchKernelGGL((k_read_slots_kv<false>), dim3(grid), dim3(kThreads), 0, s, x);
+    return hipGetLastError();
+}
+
+hipError_t launch_read_pairs_kv(const ReadPairKVArgs& a, hipStream_t s)
+{
+    const uint64_t waves = static_cast<uint64_t>(a.n_pairs) * 2u * a.n_layers;       // one block per wave
+    if (waves == 0) return hipSuccess;
+    if (!a.pairs || !a.tab || a.page_step == 0 || a.layer_stride % 16u || waves > (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_read_pairs_kv, dim3(static_cast<uint32_t>((waves + kWaves - 1) / kWaves)), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }
 

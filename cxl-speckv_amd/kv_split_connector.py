@@ -25,7 +25,11 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
   attend_shared / attend_chunk_shared   attend / attend_chunk for members that SHARE A PREFIX without holding a copy of it: the own part as
                                         those methods issue it with the log-sum-exp kept, then ONE speckv_ext_attend_prefix_fold_kv launch
                                         that reads the prefix's FP8 keys and MXFP4 values once per 64 query rows and folds them in
-  commit                                the accepted prefix of a step into the pool: one speckv_ext_write_pairs per allocation
+  commit                                the accepted prefix of a step -- or, nodes=path, the accepted path of a tree step -- into the pool:
+                                        one speckv_ext_write_pairs per allocation
+  truncate                              roll requests back: ONE speckv_ext_read_pairs_kv brings the new odd last positions back as tails
+  fork                                  new requests from positions others hold: ONE speckv_ext_copy_runs_kv copies the stored records of
+                                        both allocations, at most ONE speckv_ext_read_pairs_kv reads the tails of odd shorter lengths
   kv_rows                               the stored rows of one layer and kind as fp16: one speckv_ext_fetch_range on the K or the V allocation
   load_paged / store_paged              positions between the pool and per-layer paged caches ([2, blocks, block_size, 8, 128], fp16 or
                                         bf16: vLLM's blocks), ONE speckv_ext_read_slots_kv / _write_slots_kv launch over both allocations
@@ -36,7 +40,7 @@ of attend_chunk (_chunk_judge, _chunk_rows) are SharedPrefixSteps' (kv_shared.py
 class's own there is the (K, V) handle arrays of a prefix, its decode and chunk step, the fold entry and the depth table.
 
 Not in this class: the planned and captured decode route (plan_step, HIP graphs: attend stages its descriptors
-per call), attend_spec over a shared prefix or for several layers at once, commit(nodes=path), fork, truncate, begin_step and
+per call), attend_spec over a shared prefix or for several layers at once, begin_step and
 the K pre-scale (load_paged / store_paged have none either); the vLLM adapter builds a SpeckvKVConnector; a shared prefix is one
 level deep and one layer per call."""
 from typing import Dict, Optional, Sequence
@@ -61,6 +65,7 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
     _On = SpeckvKVConnector._On          # the stream rule of the connector: torch's NULL stream goes through a side stream
     chunk_blocks = staticmethod(SpeckvKVConnector.chunk_blocks)
     _chunk_tree_parents = staticmethod(SpeckvKVConnector._chunk_tree_parents)
+    _tree_parents = staticmethod(SpeckvKVConnector._tree_parents)       # (what _checked_paths judges commit(nodes=..., parents=...) with)
 
     def __init__(self, lib: SpeckvLib, num_layers: int, num_kv_heads: int = 8, head_dim: int = 128, max_tokens: int = 4096):
         if num_kv_heads * head_dim * 2 != 2048:
@@ -592,17 +597,30 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                                   parents is not None, "attend_chunk_shared")
 
     # ------------------------------------------------------------------ commit
-    def commit(self, req_ids: Sequence[int], k_new, v_new, n_accept: Sequence[int], stream=None):
+    def commit(self, req_ids: Sequence[int], k_new, v_new, n_accept: Optional[Sequence[int]] = None, stream=None, *, nodes=None, parents=None):
         """Store the first n_accept[b] (0..S) of the S new positions k_new[b], v_new[b] ([batch][S][layers][heads][dim] fp16) of every
         request: the tail and the new rows are paired into pages, a leftover odd position becomes the tail (SpeckvKVConnector.commit_plan).
         TWO library calls for the whole batch, one speckv_ext_write_pairs per allocation, rows read where they lie.  That entry numbers
         the pages of a pair j = 0 .. 2 n_layers - 1 as (layer j / 2, kind j % 2) and reads row d_rows[2 kind (+ 1)] + (j / 2) *
         layer_stride; a single-kind allocation of L regions is addressed with n_layers = L / 2, layer_stride = two real layer strides,
         the even / odd rows of real layer 0 in the "K" slots and the same rows of real layer 1 in the "V" slots -- region j then reads
-        the row of real layer j.  Returns what the asynchronous launches read, to be held until the stream has passed them."""
+        the row of real layer j.  Returns what the asynchronous launches read, to be held until the stream has passed them.
+        nodes (keyword, in place of n_accept: exactly one of the two is given): nodes[b] = the accepted path of a TREE step, the step
+        positions to store in order -- the contract of SpeckvKVConnector.commit, judged by its rules (_checked_paths): with `parents`
+        (SpeckvKVConnector.tree_masks) the path must be a chain of the tree from a child of the committed context, without, the
+        caller vouches for ascending node indices (the path of a large tree verified by attend_chunk(parents=...)).  ValueError before
+        any state changes.  The launches are the same two calls; only the row addresses and the gather of the new tails follow
+        nodes[b][t] instead of t.  nodes[b] = range(n) stores what n_accept[b] = n stores."""
         import numpy as np
         import torch
         B, S = k_new.shape[0], k_new.shape[1]
+        if (n_accept is None) == (nodes is None):
+            raise ValueError("commit: exactly one of n_accept and nodes")
+        if nodes is not None:
+            nodes = SpeckvKVConnector._checked_paths(self, req_ids, k_new, v_new, nodes, parents)
+            n_accept = [len(path) for path in nodes]
+        elif parents is not None:
+            raise ValueError("commit: parents judges nodes; n_accept names a prefix of the step")
         n_accept = [int(n) for n in n_accept]
         reqs = [self.requests[rid] for rid in req_ids]
         if len(reqs) != B or len(n_accept) != B or tuple(v_new.shape) != tuple(k_new.shape) or tuple(k_new.shape[2:]) != (self.L, self.H, self.D):
@@ -624,7 +642,7 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                 k_new, v_new = k_new.contiguous(), v_new.contiguous()
                 keep += [k_new, v_new]
                 if tails:                                                                       # copies: the caller may reuse k_new
-                    it = _kc._device_index([b * S + t for b, t in tails])
+                    it = _kc._device_index([b * S + (t if nodes is None else nodes[b][t]) for b, t in tails])
                     tk = k_new.view(B * S, self.L, self.H, self.D).index_select(0, it)
                     tv = v_new.view(B * S, self.L, self.H, self.D).index_select(0, it)
             if pairs:
@@ -634,11 +652,17 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                 for b in used:
                     keep += [reqs[b].tail_k, reqs[b].tail_v]
                     tail_at[b] = reqs[b].tail_k.data_ptr(), reqs[b].tail_v.data_ptr()
+                node_of = None
+                if nodes is not None:                                                           # [b][source] -> the step position it names
+                    node_of = np.zeros((B, S + 1), dtype=np.int64)                              # (source -1 is the last column, unused)
+                    for b, path in enumerate(nodes):
+                        node_of[b, :len(path)] = path
                 for kind, (new, handle) in enumerate(((k_new, "k_handle"), (v_new, "v_handle"))):
                     rows = np.empty((len(plan), 4), dtype=np.uint64)
                     for half in (0, 1):
                         t = plan[:, 2 + half]
-                        new_row = ((b_of * S + np.maximum(t, 0)) * row_bytes).astype(np.uint64) + np.uint64(new.data_ptr())
+                        at = np.maximum(t, 0) if node_of is None else node_of[b_of, t]
+                        new_row = ((b_of * S + at) * row_bytes).astype(np.uint64) + np.uint64(new.data_ptr())
                         rows[:, half] = np.where(t < 0, tail_at[b_of, kind], new_row)          # real layer 0: the "K" slots
                         rows[:, 2 + half] = rows[:, half] + np.uint64(layer_bytes)             # real layer 1: the "V" slots
                     handles = np.asarray([getattr(reqs[b], handle) for b in b_of], dtype=np.uint64)
@@ -650,4 +674,142 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         for r, n in zip(reqs, n_accept):
             r.length += n
         self._epoch += 1
+        return keep
+
+    # ------------------------------------------------------------------ rollback and fork
+    def _moved(self):
+        """lengths, tails or the set of requests changed: nothing a step derived from them holds any longer"""
+        self._epoch += 1
+        self._tails = (None, None, None, None)
+        self._tree = (None, None, None)
+        self._fold = (None,)
+        self._spec = (None,)
+        self._shared_key, self._shared_plan = None, None
+
+    def _read_tails(self, reqs, positions, st):
+        """The rows of the EVEN stored positions positions[i] of reqs[i], every layer, K and V, as one [n][layers][heads][dim] fp16 tensor
+        pair: ONE speckv_ext_read_pairs_kv call on stream st.  Pair i is page positions[i] // 2 of layer 0's region in both
+        allocations, page_step = one region, n_layers = the real layers (no re-addressing as in commit: the entry knows the split
+        layout); the odd halves are not asked for."""
+        import numpy as np
+        import torch
+        n = len(reqs)
+        layer_bytes = self.H * self.D * 2
+        with torch.cuda.stream(st):
+            tk = torch.empty((n, self.L, self.H, self.D), dtype=torch.float16, device="cuda")
+            tv = torch.empty_like(tk)
+        rows = np.zeros((n, 4), dtype=np.uint64)                                                 # odd rows: 0 = not wanted
+        at = np.arange(n, dtype=np.uint64) * np.uint64(self.L * layer_bytes)
+        rows[:, 0], rows[:, 2] = at + np.uint64(tk.data_ptr()), at + np.uint64(tv.data_ptr())
+        self.lib.read_pairs_kv(np.asarray([r.k_handle for r in reqs], dtype=np.uint64), np.asarray([r.v_handle for r in reqs], dtype=np.uint64),
+                               np.asarray([self._page(0, pos) for pos in positions], dtype=np.uint64), rows, self.region_pages, self.L,
+                               layer_bytes, st.cuda_stream)
+        return tk, tv
+
+    def truncate(self, req_ids: Sequence[int], new_lengths: Sequence[int], stream=None):
+        """Roll the requests back to new_lengths[b] <= length positions; the contract of SpeckvKVConnector.truncate, planned by its
+        truncate_plan: afterwards lengths, tails, _epoch and every per-step cache are those of a connector that had stopped there.  A
+        request cut to an odd length inside stored pairs gets its new last position back as its tail: ONE speckv_ext_read_pairs_kv
+        call for the whole batch decodes that row -- the even half of page (new_len - 1) // 2 of every layer's region, in the K
+        allocation and in the V allocation -- into one [n][layers][heads][dim] tensor pair; the odd halves are null (not stored, and
+        in the FP8 allocation not read).  No other launch; when no request needs a row back, no launch at all.  ValueError
+        (truncate_plan) and KeyError before any state changes.  The allocations keep their size.
+
+        The row that comes back has been through its format once -- K through FP8_E4M3 with its page's block scale, V through MXFP4
+        with its group codes -- and it is encoded AGAIN with its new partner when the next commit completes its pair: the block scale
+        (K) and the 32-element group codes (V) are then chosen over the new pair, so the row's stored values may move once more by the
+        formats' rounding.  The tail itself is exactly the decoded stored row, bit for bit what kv_rows returned for it.
+
+        Records beyond the new length stay in both allocations as stale bytes, and nothing clears them, because their values are never
+        used.  Every K8V4 body takes its range from pos_end (length & ~1) and a page holds two positions, so a stale PAGE is either
+        wholly behind pos_end or rewritten whole by the commit that completes it: the decode kernel (k_attend_k8v4, all four
+        instances) sets the score of a position at or beyond pos_end inside the last 32-position tile to -inf before the softmax, which
+        gives it weight exactly 0, and drops the MXFP4 block code of such a page; the chunk and prefix kernels (k_attend_chunk /
+        k_attend_prefix, the K8V4 instances) score such positions -inf too and stage their V as zeros, against pos_end and against the
+        prefix length, which attend_shared bounds by the prefix's length rounded down to even.  tests/test_gpu_k8v4_lifecycle.py
+        commits rows of 200x and 1000x the kept magnitude behind the cut and holds attend, attend(window=W), attend_spec,
+        attend_chunk and attend_shared over a cut prefix to the float64 reference.  One difference
+        to a never-written page remains, as in SpeckvKVConnector.truncate: a stale V row that is not finite times a weight of 0 is
+        NaN; a caller that may have committed non-finite rows frees before it rolls back."""
+        reqs = [self.requests[rid] for rid in req_ids]
+        new_lengths = [int(n) for n in new_lengths]
+        if len(new_lengths) != len(reqs):
+            raise ValueError("new_lengths: one length per request")
+        drops, reads = SpeckvKVConnector.truncate_plan([r.length for r in reqs], new_lengths)
+        if all(n == r.length for n, r in zip(new_lengths, reqs)):
+            return
+        tk = tv = None
+        if reads:
+            with self._On(self, stream) as st:
+                tk, tv = self._read_tails([reqs[b] for b, _ in reads], [new_lengths[b] - 1 for b, _ in reads], st)
+        for b in drops:
+            reqs[b].tail_k = reqs[b].tail_v = None
+        for i, (b, _) in enumerate(reads):
+            reqs[b].tail_k, reqs[b].tail_v = tk[i], tv[i]
+        for r, n in zip(reqs, new_lengths):
+            r.length = n
+        self._moved()
+
+    def fork(self, src_ids: Sequence[int], new_ids: Sequence[int], lengths: Optional[Sequence[int]] = None, stream=None):
+        """Create the requests new_ids[b], each holding the first lengths[b] (default: all) positions of request src_ids[b]; the contract
+        of SpeckvKVConnector.fork, planned by its fork_plan.  A source may appear several times (parallel sampling, beams).  Afterwards
+        lengths, tails and _epoch are those of requests written independently with the same values, and source and fork go their
+        own ways.
+
+        ONE speckv_ext_copy_runs_kv call for the batch copies the stored records of the lengths[b] // 2 pairs of every layer's region
+        in BOTH allocations -- records, not values: the FP8 bytes with their block scales (scale table included) and the MXFP4 nibble
+        rows with their codes, nothing decoded or rounded again, so every reader gives the fork the source's bits (no call when no
+        pair is stored).  An odd length needs its last row as the new request's tail: equal to the source's length, the row is a CLONE
+        of the source's tail (never a view); shorter, it is the even half of stored page (length - 1) // 2, and at most ONE
+        speckv_ext_read_pairs_kv call reads those rows from the SOURCES, as truncate() installs tails.
+
+        KeyError for an existing (or repeated) new id and for an unknown source, ValueError from fork_plan: before any allocation or
+        change of state.  If a launch fails the allocations made here are freed again and the sources are untouched.  Returns the
+        tensors the launches write, for the caller to hold until the stream has passed them."""
+        import contextlib
+        import numpy as np
+        import torch
+        src_ids, new_ids = list(src_ids), list(new_ids)
+        if len(src_ids) != len(new_ids):
+            raise ValueError("new_ids: one new request per source")
+        for i, rid in enumerate(new_ids):
+            if rid in self.requests or rid in new_ids[:i]:
+                raise KeyError(f"request {rid} already exists")
+        srcs = [self.requests[rid] for rid in src_ids]
+        lengths = [r.length for r in srcs] if lengths is None else [int(n) for n in lengths]
+        if len(lengths) != len(srcs):
+            raise ValueError("lengths: one length per request")
+        n_pages, tails = SpeckvKVConnector.fork_plan([r.length for r in srcs], lengths)
+        if not new_ids:
+            return []
+        reads = [b for b, t in enumerate(tails) if t == "read"]
+        made, keep, tk, tv = [], [], None, None
+        try:
+            for rid in new_ids:
+                self.add_request(rid)
+                made.append(rid)
+            news = [self.requests[rid] for rid in new_ids]
+            if any(n_pages) or reads:
+                with self._On(self, stream) as st:
+                    if any(n_pages):
+                        firsts = np.arange(self.L, dtype=np.uint64) * np.uint64(self.region_pages)          # _page(layer, 0)
+                        handles = lambda rs, name: np.asarray([getattr(r, name) for r in rs], dtype=np.uint64)
+                        self.lib.copy_runs_kv(handles(srcs, "k_handle"), handles(srcs, "v_handle"), handles(news, "k_handle"), handles(news, "v_handle"),
+                                              np.asarray(n_pages, dtype=np.uint64), firsts, st.cuda_stream)
+                    if reads:
+                        tk, tv = self._read_tails([srcs[b] for b in reads], [lengths[b] - 1 for b in reads], st)
+                        keep += [tk, tv]
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():      # behind what produced the source's tail
+                for b, t in enumerate(tails):
+                    if t == "held":
+                        news[b].tail_k, news[b].tail_v = srcs[b].tail_k.clone(), srcs[b].tail_v.clone()
+        except BaseException:
+            for rid in made:
+                self.free_request(rid)
+            raise
+        for i, b in enumerate(reads):
+            news[b].tail_k, news[b].tail_v = tk[i], tv[i]
+        for r, n in zip(news, lengths):
+            r.length = n
+        self._moved()
         return keep

@@ -93,6 +93,8 @@ _EXT_SIGNATURES = {
     "speckv_ext_write_slots_kv": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32,
                                   c_uint64, c_uint64, c_void_p, c_void_p],
     "speckv_ext_copy_runs": [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
+    "speckv_ext_read_pairs_kv": [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_uint64, c_void_p],
+    "speckv_ext_copy_runs_kv": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
     "speckv_ext_attend_chunk": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                 c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_chunk_masked": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
@@ -456,6 +458,27 @@ class SpeckvLib:
         n, m = len(src), len(run_firsts)
         ss, ds, ns, fs = as_arr(src, c_uint64, n), as_arr(dst, c_uint64, n), as_arr(n_pages, c_uint64, n), as_arr(run_firsts, c_uint64, m)
         self._ext("speckv_ext_copy_runs", ss, ds, ns, n, fs, m, c_void_p(stream))
+
+    def read_pairs_kv(self, k_handles, v_handles, first_pages, rows, page_step, n_layers, layer_stride, stream):
+        """read_pairs for the split pool in ONE launch (speckv_ext_read_pairs_kv): pair i = page first_pages[i] + l*page_step of the
+        FP8_E4M3 allocation k_handles[i] and of the MXFP4 allocation v_handles[i] for every REAL layer l < n_layers, decoded into
+        rows[i] = (K even, K odd, V even, V odd) device addresses + l*layer_stride; an address of 0 = that row is not wanted.
+        Arguments as read_pairs behind the second handle array."""
+        n = len(k_handles)
+        if not hasattr(rows, "ctypes") and not isinstance(rows, ctypes.Array):
+            rows = [p for r in rows for p in r]
+        ks, vs, fs, rs = as_arr(k_handles, c_uint64, n), as_arr(v_handles, c_uint64, n), as_arr(first_pages, c_uint64, n), as_arr(rows, c_uint64, 4 * n)
+        self._ext("speckv_ext_read_pairs_kv", ks, vs, fs, rs, n, page_step, n_layers, layer_stride, c_void_p(stream))
+
+    def copy_runs_kv(self, k_src, v_src, k_dst, v_dst, n_pages, run_firsts, stream):
+        """copy_runs for the split pool in ONE launch (speckv_ext_copy_runs_kv): the stored records of pages [run_firsts[r], run_firsts[r]
+        + n_pages[i]), every run r, copied from k_src[i] to k_dst[i] (FP8_E4M3) and from v_src[i] to v_dst[i] (MXFP4).  A destination
+        appears once across k_dst and v_dst together and is no source of the same call.  Arguments as copy_runs behind the handle
+        arrays."""
+        n, m = len(k_src), len(run_firsts)
+        hs = [as_arr(x, c_uint64, n) for x in (k_src, v_src, k_dst, v_dst)]
+        ns, fs = as_arr(n_pages, c_uint64, n), as_arr(run_firsts, c_uint64, m)
+        self._ext("speckv_ext_copy_runs_kv", *hs, ns, n, fs, m, c_void_p(stream))
 
     def _chunk(self, entry, handles, layer, d_q, C, rows_per_pos, pos_end, n_q, d_k_new, d_v_new, seq_stride, pos_stride, tail_idx, d_k_tail,
                d_v_tail, tail_stride, form, sm_scale, d_out, d_lse, stream):

@@ -333,6 +333,41 @@ speckv_status_t speckv_ext_copy_runs(const speckv_handle_t* src, const speckv_ha
                                      const uint64_t* n_pages /* [n_pairs] pages per run of pair i */, uint32_t n_pairs,
                                      const uint64_t* run_firsts /* [n_runs] first page of each run, the same in src and dst */,
                                      uint32_t n_runs, void* stream);
+/* speckv_ext_read_pairs and speckv_ext_copy_runs for the split pool ("K8V4"): pair i names TWO allocations per role, an FP8_E4M3 one that
+ * holds a request's K rows and an MXFP4 one that holds its V rows, each laid out as ONE region per layer.  Both entries do for both
+ * allocations of every pair what their parents do for one, with ONE staged descriptor array and ONE launch per call (the parents refuse
+ * a call that mixes schemes, so a split request would cost two calls and two launches).  Additive: SPECKV_EXT_ABI_VERSION stays as it
+ * is.
+ * speckv_ext_read_pairs_kv: the page of layer l < n_layers of pair i is first_pages[i] + l * page_step in k_handles[i] and in
+ * v_handles[i] alike -- n_layers counts real layers, there is no factor 2 and no kind term.  d_rows[4 * i + 0 .. 3] are K even, K odd,
+ * V even, V odd: the first 2048 decoded bytes of the K page of layer l go to d_rows[4 * i] + l * layer_stride_bytes, the second 2048
+ * to d_rows[4 * i + 1] + l * layer_stride_bytes, those of the V page to d_rows[4 * i + 2] / d_rows[4 * i + 3] in the same way.  A NULL
+ * row is not written (and in the FP8 allocation not read).  The bits are the halves of what speckv_ext_fetch_range writes for the
+ * page of the K allocation and of the V allocation as fp16; a page never written gives zeros.  Ordering, placement (linear, striped,
+ * migrated, sealed; a sealed allocation stays sealed) and statistics (2 * n_layers pages per pair) as speckv_ext_read_pairs.
+ *   SPECKV_ERR_INVAL    what speckv_ext_read_pairs refuses with it (different schemes aside), a NULL handle array, k_handles[i] not
+ *                       FP8_E4M3 or v_handles[i] not MXFP4, the two allocations of a pair laid out for different num_tokens
+ *   SPECKV_ERR_GENERAL  an unknown handle, pages that leave either allocation
+ * speckv_ext_copy_runs_kv: pair i copies pages [run_firsts[r], run_firsts[r] + n_pages[i]), every run r, from k_src[i] to k_dst[i] and
+ * from v_src[i] to v_dst[i]; per allocation pair the contract of speckv_ext_copy_runs (records, not values; the FP8 block scales in
+ * the destination's scale table; the MXFP4 codes at the destination slot's own offset; a source page never written leaves the
+ * destination page never written; sealed destinations unpacked, cached destination pages invalidated).  Aliasing is judged ACROSS both
+ * sides: an allocation that is written is named once in k_dst and v_dst together and is not named in k_src or v_src.
+ *   SPECKV_ERR_INVAL    what speckv_ext_copy_runs refuses with it (different schemes aside), a NULL handle array, a K handle that is
+ *                       not FP8_E4M3 or a V handle that is not MXFP4, source == destination on either side, a destination named twice
+ *                       (on one side or on both) or also named as a source, allocations of a pair laid out for different num_tokens
+ *   SPECKV_ERR_GENERAL  an unknown handle, pages that leave any of the four allocations
+ * Counted in speckv_ext_stats_t.copied_pages: 2 * n_runs * n_pages[i] records per pair.  Every refusal launches nothing. */
+speckv_status_t speckv_ext_read_pairs_kv(const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                         const uint64_t* first_pages,
+                                         void* const* d_rows /* [n_pairs][4]: K even, K odd, V even, V odd; NULL = not wanted */,
+                                         uint32_t n_pairs, uint64_t page_step, uint32_t n_layers,
+                                         uint64_t layer_stride_bytes, void* stream);
+speckv_status_t speckv_ext_copy_runs_kv(const speckv_handle_t* k_src, const speckv_handle_t* v_src,
+                                        const speckv_handle_t* k_dst, const speckv_handle_t* v_dst,
+                                        const uint64_t* n_pages /* [n_pairs] pages per run of pair i */, uint32_t n_pairs,
+                                        const uint64_t* run_firsts /* [n_runs] first page of each run, the same in all four */,
+                                        uint32_t n_runs, void* stream);
 /* Several page runs of ONE allocation in one launch: run r = pages [first_pages[r], first_pages[r] + n_pages_each) from
  * d_srcs[r] (n_pages_each * 4096 contiguous bytes).  A prompt's K and V of every layer (2 * num_layers regions of the shim
  * layout) are stored with one call.  The runs must not overlap; the stream must not be NULL. */
