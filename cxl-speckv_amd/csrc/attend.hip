@@ -947,7 +947,8 @@ constexpr uint32_t kMaxSplits = 2048;
 __global__ __launch_bounds__(512) void k_attend_combine(const float* __restrict__ part_acc, const float* __restrict__ part_ml,
                                                         uint32_t g, uint32_t n_splits, float* __restrict__ out,
                                                         float* __restrict__ lse, const AttendSeq* __restrict__ seqs,
-                                                        uint32_t heads, uint32_t skip_single, AttendArgs::Stream sk, uint32_t n_tiles)
+                                                        uint32_t heads, uint32_t skip_single, AttendArgs::Stream sk, uint32_t n_tiles,
+                                                        uint32_t layer_seqs, uint32_t layer_parts)
 {
     __shared__ float w[kMaxSplits];
     __shared__ float red[8];
@@ -956,11 +957,14 @@ __global__ __launch_bounds__(512) void k_attend_combine(const float* __restrict_
     const uint32_t lane = t & 63u, wv = t >> 6;
     uint64_t part0 = static_cast<uint64_t>(rowq) * n_splits;           // first partial of this (layer | sequence, head)
     if (seqs) {
-        const AttendSeq sq = seqs[rowq / heads];
+        // layer_seqs != 0 (launch_attend_k8v4_layers): rows [layer][sequence] over one descriptor per sequence, layer i's partials i * layer_parts on
+        uint32_t member = rowq / heads, li = 0u;
+        if (layer_seqs) { li = member / layer_seqs; member -= li * layer_seqs; }
+        const AttendSeq sq = seqs[member];
         if (skip_single && sq.n_splits == 1u) return;        // written by the attention kernel itself (workgroup-uniform)
         if (skip_single == 2u && sq.n_splits == 0u) return;  // ... and so is a sequence with nothing stored (the held rows of a multi-position step)
         n_splits = sq.n_splits;
-        part0 = sq.part_base + static_cast<uint64_t>(rowq % heads) * n_splits;
+        part0 = sq.part_base + static_cast<uint64_t>(li) * layer_parts + static_cast<uint64_t>(rowq % heads) * n_splits;
     }
     if (sk.n_wgs) {                                                    // stream form: the row's own count, slots max_slots apart
         part0 = static_cast<uint64_t>(rowq) * sk.max_slots;
@@ -1023,7 +1027,8 @@ template <int WPR>
 __global__ __launch_bounds__(256) void k_attend_combine_small(const float* __restrict__ part_acc, const float* __restrict__ part_ml,
                                                               uint32_t g, uint32_t n_splits, float* __restrict__ out,
                                                               float* __restrict__ lse, const AttendSeq* __restrict__ seqs,
-                                                              uint32_t heads, uint32_t skip_single, uint32_t n_rows, AttendArgs::Stream sk, uint32_t n_tiles)
+                                                              uint32_t heads, uint32_t skip_single, uint32_t n_rows, AttendArgs::Stream sk, uint32_t n_tiles,
+                                                              uint32_t layer_seqs, uint32_t layer_parts)
 {
     typedef float v4f __attribute__((ext_vector_type(4)));
     const uint32_t lane = threadIdx.x & 63u, c = lane & 15u, kb = lane >> 4;
@@ -1033,11 +1038,13 @@ __global__ __launch_bounds__(256) void k_attend_combine_small(const float* __res
     if (rowq >= n_rows) return;
     uint64_t part0 = static_cast<uint64_t>(rowq) * n_splits;
     if (seqs) {
-        const AttendSeq sq = seqs[rowq / heads];
+        uint32_t member = rowq / heads, li = 0u;                       // (layer_seqs: see k_attend_combine)
+        if (layer_seqs) { li = member / layer_seqs; member -= li * layer_seqs; }
+        const AttendSeq sq = seqs[member];
         if (skip_single && sq.n_splits == 1u) return;
         if (skip_single == 2u && sq.n_splits == 0u) return;
         n_splits = sq.n_splits;
-        part0 = sq.part_base + static_cast<uint64_t>(rowq % heads) * n_splits;
+        part0 = sq.part_base + static_cast<uint64_t>(li) * layer_parts + static_cast<uint64_t>(rowq % heads) * n_splits;
     }
     if (sk.n_wgs) {                                                    // stream form (wave-uniform)
         part0 = static_cast<uint64_t>(rowq) * sk.max_slots;
@@ -1173,7 +1180,7 @@ hipError_t launch_qk_scores_fp8_linear(const AttendArgs& a, uint32_t n_layers, f
 }
 
 constexpr uint32_t kSmallCombineRowsShared = 8192;     // rows up to which the small merge spends a workgroup per row (k_attend_combine_small<4>)
-hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s)
+hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s, uint32_t layer_seqs, uint32_t layer_parts)
 {
     if (n_layers == 0) return hipSuccess;
     const uint32_t splits = a.stream.n_wgs ? a.stream.max_slots : a.n_splits;      // most partials a row can have
@@ -1185,14 +1192,14 @@ hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* 
         const uint32_t n_rows = n_layers * a.heads;
         if (n_rows <= kSmallCombineRowsShared)
             hipLaunchKernelGGL(k_attend_combine_small<4>, dim3(n_rows), dim3(256), 0, s, a.part_acc, a.part_ml, a.g,
-                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles);
+                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles, layer_seqs, layer_parts);
         else
             hipLaunchKernelGGL(k_attend_combine_small<1>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, a.part_acc, a.part_ml, a.g,
-                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles);
+                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles, layer_seqs, layer_parts);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_attend_combine, dim3(n_layers * a.heads * a.g), dim3(512), 0, s, a.part_acc, a.part_ml, a.g,
-                       a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, a.stream, n_tiles);
+                       a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, a.stream, n_tiles, layer_seqs, layer_parts);
     return hipGetLastError();
 }
 

@@ -671,6 +671,18 @@ speckv_status_t speckv_ext_attend_kv_spec_window(uint32_t n_seq, const speckv_ha
     });
 }
 
+speckv_status_t speckv_ext_attend_kv_layers(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles, uint32_t layer_begin,
+                                            uint32_t n_layers, const void* d_q_f16, uint32_t g, const uint32_t* pos_end, uint32_t n_tail,
+                                            const int32_t* d_tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,
+                                            float sm_scale, float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] {
+        return g_engine->attend_layers_kv(n_seq, k_handles, v_handles, layer_begin, n_layers, d_q_f16, g, pos_end, n_tail, d_tail_idx, d_k_tail, d_v_tail,
+                                          tail_stride_elems, sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream));
+    });
+}
+
 // the walk rule of that entry (spec_window.hpp); no engine needed
 speckv_status_t speckv_ext_spec_window_range(uint32_t length, uint32_t window, uint32_t* out_begin, int32_t* out_rel, uint32_t* out_n_pages)
 {

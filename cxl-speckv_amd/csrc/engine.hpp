@@ -261,6 +261,11 @@ public:
                        uint32_t rows_per_pos, const uint32_t* pos_end, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems,
                        uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s,
                        const uint32_t* length = nullptr, const uint32_t* d_depth = nullptr, uint32_t window = 0);
+    // the split pool's decode step for n_layers consecutive layers in one launch (speckv_ext_attend_kv_layers; engine_attend_kv.cpp): q / out / lse
+    // rows [layer][sequence], one descriptor per sequence, the tails of odd lengths folded inside the launch
+    int attend_layers_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer_begin, uint32_t n_layers, const void* d_q_f16,
+                         uint32_t g, const uint32_t* pos_end, uint32_t n_tail, const int32_t* d_tail_idx, const void* d_k_tail, const void* d_v_tail,
+                         uint64_t tail_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
     int attend_mx4(uint64_t handle, uint32_t layer, uint32_t n_layers, const void* d_q_f16, uint32_t g,
                    uint32_t pos_begin, uint32_t pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
     int migrate(uint64_t handle, uint64_t first_page, uint64_t n_pages, uint32_t target_pool);

@@ -771,7 +771,10 @@ __host__ __device__ inline uint32_t attend_tile_slot(uint32_t j) { return j < 8u
 // a.q8 = the fp16 query rows
 // [layers][heads][g][128]); writes the split partials, launch_attend_combine merges them
 hipError_t launch_attend_int4(const AttendArgs& a, uint32_t n_layers, hipStream_t s);
-hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s);
+// layer_seqs != 0 (launch_attend_k8v4_layers only; 0 for every other caller): the rows are [layer][sequence] over ONE descriptor per sequence --
+// row block y reads a.seqs[y % layer_seqs], its partials lie (y / layer_seqs) * layer_parts further on
+hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s, uint32_t layer_seqs = 0,
+                                 uint32_t layer_parts = 0);
 // MXFP4 records (attend_mx4.hip): a.lin_base | a.stripe_bases | a.table_form choose the address form, a.q16 = the fp16 query rows,
 // a.seqs the batch descriptors; n_rows = layers or sequences.  Launches the merge itself when the rows are not final.
 hipError_t launch_attend_mx4(const AttendArgs& a, uint32_t n_rows, float* d_out, float* d_lse, hipStream_t s);
@@ -811,6 +814,18 @@ struct AttendHeldArgs {
 // k_attend_k8v4<true, true> -- seq_skip[sequence] is then the sequence's signed rel of spec_window.hpp, not a position count.
 hipError_t launch_attend_k8v4_held(const AttendArgs& a, const AttendKvSide* d_vside, const AttendHeldArgs& h, uint32_t n_seq, bool merge, float* d_out,
                                    float* d_lse, hipStream_t s);
+// The decode step of SEVERAL layers over the split pool in one launch (k_attend_k8v4<false, false, AttendKvLayers>; speckv_ext_attend_kv_layers):
+// the grid carries layer x sequence x head quad, member y = [layer][sequence] is the row block of q / out / lse (a.batch_n_seq = n_seq,
+// a.batch_layer = the first layer).  a.seqs / d_vside hold ONE descriptor per sequence, for region 0 of its allocations: the kernel moves to
+// layer l by l * AttendSeq::layer_pages on k_first, on the scale-table index and on v_first.  A sequence's pieces are the same on every
+// layer; the partials of the call's layer i lie i * layer_parts further on (AttendSeq::part_base counts inside one layer).  a.order, if
+// set, lists the n_layers x n_seq MEMBERS.  a.tail_idx set (with a.tail_k / tail_v / tail_stride, the layout of AttendArgs::tail_k): split 0
+// of every member folds the sequence's tail position of its layer in front of att_store_rows8, scored with the fp16 query; a member with
+// nothing stored runs that epilogue alone, one without a tail either is written as zeros / lse -inf.
+struct AttendKvLayers { uint32_t layer_parts; };
+// merge: some sequence has several pieces -- ONE launch_attend_combine over all the layers follows on `s`
+hipError_t launch_attend_k8v4_layers(const AttendArgs& a, const AttendKvSide* d_vside, uint32_t n_seq, uint32_t n_layers, uint32_t layer_parts, bool merge,
+                                     float* d_out, float* d_lse, hipStream_t s);
 
 // every page's record (rec_bytes rounded up to 16) copied to d_new_addr[page], then entries[page].pool_addr = d_new_addr[page]
 hipError_t launch_repack(PageEntry* d_entries, const uint64_t* d_new_addr, uint64_t n, hipStream_t s);

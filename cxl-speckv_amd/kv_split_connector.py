@@ -15,6 +15,9 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
                                         ONE speckv_ext_attend_kv_batch -- the batch kernel over FP8 keys and MXFP4 values, no fp16 tile is
                                         materialised -- and one speckv_ext_attend_fold_tail for the requests with an odd length;
                                         window=W: a sliding-window layer, ONE speckv_ext_attend_kv_batch_window that walks the window only
+  attend_layers                         the DECODE step of several consecutive layers whose query rows exist at once: ONE
+                                        speckv_ext_attend_kv_layers -- one attention launch over layer x request x head quad, the tails of odd
+                                        lengths folded inside it, one merge for all layers where requests are cut into pieces
   attend_chunk                          one layer of a step of S >= 1 new positions per request -- a prefill chunk, a draft chain or tree --
                                         causal, under a window, a tree, a tree under a window, split over the chip (S = 1 works, but a
                                         64-row query block then carries rows_per_pos live rows: attend is the decode route)
@@ -40,7 +43,8 @@ of attend_chunk (_chunk_judge, _chunk_rows) are SharedPrefixSteps' (kv_shared.py
 class's own there is the (K, V) handle arrays of a prefix, its decode and chunk step, the fold entry and the depth table.
 
 Not in this class: the planned and captured decode route (plan_step, HIP graphs: attend stages its descriptors
-per call), attend_spec over a shared prefix or for several layers at once, begin_step and
+per call; attend_layers stages them once for all its layers), a window in attend_layers, attend_spec over a shared prefix or for
+several layers at once, begin_step and
 the K pre-scale (load_paged / store_paged have none either); the vLLM adapter builds a SpeckvKVConnector; a shared prefix is one
 level deep and one layer per call."""
 from typing import Dict, Optional, Sequence
@@ -87,6 +91,7 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         self._fold = (None,)                                  # attend: key, then what a step's calls share -- the count and device indices of the
                                                               # requests with an odd length, the handle arrays, the stored lengths,
                                                               # the query positions (attend under a window)
+        self._layers = (None,)                                # attend_layers: key, then the handle arrays, the stored lengths and the tail index on the device
         self._spec = (None,)                                  # attend_spec: key, then the step's mask words and gather index on the device, the
                                                               # handle arrays and the stored lengths
         self._shared_key, self._shared_plan = None, None      # attend_shared / attend_chunk_shared: the judged call of a step (_shared_args)
@@ -385,6 +390,42 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                 self.lib.attend_fold_tail(n_odd, rows.data_ptr(), self.H, G, q.data_ptr(), tk.data_ptr() + 2 * layer * row,
                                           tv.data_ptr() + 2 * layer * row, self.L * row, sm_scale, out.data_ptr(), lse.data_ptr(), st.cuda_stream)
         return out, lse, q
+
+    def attend_layers(self, layer_begin: int, n_layers: int, req_ids: Sequence[int], q, sm_scale: float, stream=None):
+        """attend for n_layers consecutive layers whose query rows exist at once: q [n_layers][batch][heads][g][dim] fp16, returns
+        [n_layers][batch][heads][g][dim] fp32 -- the contract of SpeckvKVConnector.attend_layers without `window`.  Changes no state.
+        ONE speckv_ext_attend_kv_layers call: one attention launch whose grid carries layer x request x head quad and, where requests are
+        cut into pieces, one merge for all the layers.  The handles, the stored lengths, the tail index and the stacked tails are derived
+        once per step (as attend does); the tails of odd lengths are folded inside the launch with the fp16 query, so there is no
+        speckv_ext_attend_fold_tail behind it.  Placement and refusals as attend: a SpeckvError passes through."""
+        import numpy as np
+        import torch
+        if len(q.shape) != 5:
+            raise ValueError("q must be [n_layers][batch][heads][g][dim]")
+        NL, B, H, G, D = (int(x) for x in q.shape)
+        if not _is_int(n_layers) or NL != n_layers or n_layers < 1:
+            raise ValueError("q must be [n_layers][batch][heads][g][dim] with one block per layer of the call")
+        if (H, D) != (self.H, self.D) or B != len(req_ids) or not 1 <= G <= 16:
+            raise ValueError("q must be [n_layers][batch][heads][g][dim] with g = 1..16 and one row block per request")
+        if not _is_int(layer_begin) or not 0 <= layer_begin <= self.L - n_layers:
+            raise ValueError(f"layers {layer_begin} .. {layer_begin + n_layers - 1} outside 0..{self.L - 1}")
+        reqs = [self.requests[r] for r in req_ids]
+        out = torch.empty((NL, B, H, G, D), dtype=torch.float32, device="cuda")
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):
+                q = q.contiguous()
+                tail_idx, tk, tv = self._step_tails(req_ids, reqs)
+                key = (tuple(req_ids), self._epoch)
+                if self._layers[0] != key:        # once per step: handles, stored lengths, the tail index on the device
+                    self._layers = (key, np.asarray([r.k_handle for r in reqs], dtype=np.uint64), np.asarray([r.v_handle for r in reqs], dtype=np.uint64),
+                                    np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
+                                    _kc._device_index([int(x) for x in tail_idx]) if tk is not None else None)
+                _, k_handles, v_handles, pos_end, d_idx = self._layers
+            n_tail = 0 if tk is None else int(tk.shape[0])
+            self.lib.attend_kv_layers(k_handles, v_handles, layer_begin, n_layers, q.data_ptr(), G, pos_end, n_tail, d_idx.data_ptr() if n_tail else 0,
+                                      tk.data_ptr() if n_tail else 0, tv.data_ptr() if n_tail else 0, self.L * self.H * self.D, sm_scale, out.data_ptr(),
+                                      None, st.cuda_stream)
+        return out
 
     def attend_chunk(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, splits=1,
                      window=None, parents=None):

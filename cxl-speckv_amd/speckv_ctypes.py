@@ -148,6 +148,8 @@ _EXT_SIGNATURES = {
     "speckv_ext_attend_kv_batch": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_kv_batch_window": [c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, ctypes.c_float, c_void_p,
                                           c_void_p, c_void_p],
+    "speckv_ext_attend_kv_layers": [c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+                                    c_uint64, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_int4_batch": [c_uint32, ctypes.POINTER(c_uint64), c_uint32, c_void_p, c_uint32, _u32p, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_batch_plan": [c_uint32, ctypes.POINTER(c_uint64), _u32p, c_uint32, c_void_p, c_size_t, c_void_p],
     "speckv_ext_attend_batch_plan_window": [c_uint32, ctypes.POINTER(c_uint64), _u32p, _u32p, c_uint32, c_uint32, c_void_p, c_size_t, c_void_p],
@@ -754,6 +756,18 @@ class SpeckvLib:
         u32 = lambda a: None if a is None else as_arr(a, c_uint32, n)
         self._ext("speckv_ext_attend_kv_batch_window", n, handles(k_handles), handles(v_handles), layer, c_void_p(d_q_f16), g, u32(pos_end),
                   u32(q_pos), window, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
+
+    def attend_kv_layers(self, k_handles, v_handles, layer_begin, n_layers, d_q_f16, g, pos_end, n_tail, d_tail_idx, d_k_tail, d_v_tail,
+                         tail_stride_elems, sm_scale, d_out, d_lse=None, stream=None):
+        """The decode step of a batch over a split pool for n_layers consecutive layers in one launch (speckv_ext_attend_kv_layers): d_q_f16
+        [n_layers][n][heads][g][128] fp16, d_out the same in fp32, d_lse optional [n_layers][n][heads][g]; the tails of odd lengths (n_tail of
+        them: d_tail_idx int32 [n] on the device, < 0 = none; fp16 rows [tail][layers][heads][128], tail_stride_elems apart) are folded
+        inside the launch.  Arrays as attend_kv_batch; 0 / None stands for a NULL pointer."""
+        n = len(pos_end if k_handles is None and v_handles is None else (v_handles if k_handles is None else k_handles))
+        handles = lambda h: None if h is None else as_arr(h, c_uint64, n)
+        self._ext("speckv_ext_attend_kv_layers", n, handles(k_handles), handles(v_handles), layer_begin, n_layers, c_void_p(d_q_f16), g,
+                  None if pos_end is None else as_arr(pos_end, c_uint32, n), n_tail, c_void_p(d_tail_idx or 0), c_void_p(d_k_tail or 0),
+                  c_void_p(d_v_tail or 0), tail_stride_elems, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
 
     def attend_kv_spec(self, k_handles, v_handles, layer, d_q_f16, g, rows_per_pos, pos_end, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems,
                        d_mask, mask_stride, sm_scale, d_out, d_lse=None, stream=None):

@@ -1356,6 +1356,50 @@ speckv_status_t speckv_ext_attend_kv_batch_window(uint32_t n_seq, const speckv_h
                                                   const uint32_t* q_pos, uint32_t window, float sm_scale, float* d_out, float* d_lse,
                                                   void* stream);
 
+/* speckv_ext_attend_kv_layers: the DECODE STEP of a batch over a SPLIT POOL for SEVERAL LAYERS whose query rows exist at once -- what
+ * n_layers calls of speckv_ext_attend_kv_batch (layer_begin, layer_begin + 1, ...) and the speckv_ext_attend_fold_tail behind each of them
+ * compute, in ONE attention launch and at most one merge launch: at most TWO launches whatever n_layers.  An additive entry:
+ * SPECKV_EXT_ABI_VERSION stays what it is.
+ *   k_handles, v_handles, pos_end : host arrays of n_seq (pos_end[i] even: the stored positions, the same on every layer)
+ *   d_q_f16 : [n_layers][n_seq][8][g][128] fp16 (device, 16-byte aligned), g = 1..16
+ *   d_out   : [n_layers][n_seq][8][g][128] fp32 (16-byte aligned)      d_lse : optional [n_layers][n_seq][8][g] fp32
+ *   n_tail, d_tail_idx, d_k_tail, d_v_tail, tail_stride_elems : the position a sequence keeps OUTSIDE the pool (a connector's odd last
+ *       position).  n_tail == 0: none, the other four are not read (d_tail_idx may be NULL).  Otherwise d_tail_idx is a DEVICE array of
+ *       n_seq int32 -- the index of sequence i's tail rows, < 0: it has none -- and the fp16 K / V rows of tail t, layer l (counted from
+ *       0, NOT from layer_begin), kv head h lie at d_k_tail / d_v_tail + t * tail_stride_elems + (l * 8 + h) * 128 elements: rows
+ *       [tail][layers][8][128] as a connector keeps them.  Both pointers 16-byte aligned, tail_stride_elems a multiple of 8 and at
+ *       least (layer_begin + n_layers) * 8 * 128.
+ * The grid carries layer x sequence x head quad.  The descriptors are staged once per SEQUENCE -- the kernel (k_attend_k8v4<false, false,
+ * AttendKvLayers>) moves to its layer by layer * num_tokens / 2 pages in both allocations -- so the staged bytes do not grow with n_layers
+ * (apart from the dispatch order, which lists the n_layers x n_seq members); the handles are looked up, the regions judged, the streams
+ * ordered and the descriptor slot taken once per call.  The launch decision is the one speckv_ext_attend_kv_batch makes, asked once for
+ * n_seq x n_layers members (every sequence's tiles repeated per layer): with n_layers == 1 exactly that entry's decision -- and, where no
+ * sequence has a tail, its bits.  A sequence's pieces are the same on every layer.
+ * The tail is folded INSIDE the launch by the workgroups of split 0 of every (layer, sequence), into their final rows or their partial:
+ * one more position in the same softmax, scored with the FP16 query (the stored positions with the E4M3 query, as in
+ * speckv_ext_attend_kv_batch) -- the value speckv_ext_attend_fold_tail gives, not its bits.  No tail row of another layer or another
+ * sequence is read.  A sequence with pos_end[i] == 0 and a tail gets that position alone; one without a tail either gets zeros and
+ * lse = -inf.  d_lse is optional whether or not there are tails.
+ * Values, addressing, placement (single runs only) and the stream rules are those of speckv_ext_attend_kv_batch.  NOT capturable into a
+ * HIP graph (the descriptors are staged per call).  No sliding window.
+ *   SPECKV_ERR_INVAL    each with its reason in the error text, nothing is launched, d_out is untouched: g == 0 or g > 16; n_layers == 0;
+ *                       d_q_f16 or d_out not 16-byte aligned; an odd pos_end[i]; n_tail != 0 with d_tail_idx, d_k_tail or d_v_tail NULL,
+ *                       with a tail pointer not 16-byte aligned, or with tail_stride_elems not a multiple of 8 or below (layer_begin +
+ *                       n_layers) * 8 * 128 -- these are judged first, on every engine --; a capturing stream; k_handles, v_handles,
+ *                       pos_end, d_q_f16 or d_out NULL (with n_seq != 0); an allocation of the wrong scheme or layout, pos_end[i] >
+ *                       num_tokens, (layer_begin + n_layers) * num_tokens / 2 beyond either allocation's pages (a layer range past its
+ *                       regions); an allocation whose records do not lie in one run; a member in more than 2048 pieces; a grid beyond
+ *                       the launch limits (n_seq * n_layers * 2 > 65535 workgroup rows in a grid that is not rows-first)
+ *   SPECKV_ERR_NOMEM    the scratch buffer of the partials could not grow -- nothing is launched
+ *   SPECKV_ERR_GENERAL  an unknown handle
+ *   SPECKV_ERR_DRIVER   an engine without a device ("/dev/null"): no data path
+ * speckv_free of either allocation waits for `stream`. */
+speckv_status_t speckv_ext_attend_kv_layers(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                            uint32_t layer_begin, uint32_t n_layers, const void* d_q_f16, uint32_t g,
+                                            const uint32_t* pos_end, uint32_t n_tail, const int32_t* d_tail_idx, const void* d_k_tail,
+                                            const void* d_v_tail, uint64_t tail_stride_elems, float sm_scale, float* d_out, float* d_lse,
+                                            void* stream);
+
 /* speckv_ext_attend_kv_spec: one MULTI-POSITION STEP of a batch over a SPLIT POOL -- verifying the draft positions of every sequence, a
  * chain or a tree, on the decode kernel: speckv_ext_attend_kv_batch with g = n_q x rows_per_pos query rows per kv head (row r belongs to
  * query position j = r / rows_per_pos, n_q <= SPECKV_HELD_MAX - 1), every row over all stored positions [0, pos_end[i]) in ONE pass over
