@@ -948,7 +948,7 @@ __global__ __launch_bounds__(512) void k_attend_combine(const float* __restrict_
                                                         uint32_t g, uint32_t n_splits, float* __restrict__ out,
                                                         float* __restrict__ lse, const AttendSeq* __restrict__ seqs,
                                                         uint32_t heads, uint32_t skip_single, AttendArgs::Stream sk, uint32_t n_tiles,
-                                                        uint32_t layer_seqs, uint32_t layer_parts)
+                                                        uint32_t layer_seqs, uint32_t layer_parts, uint32_t block_parts)
 {
     __shared__ float w[kMaxSplits];
     __shared__ float red[8];
@@ -970,6 +970,10 @@ __global__ __launch_bounds__(512) void k_attend_combine(const float* __restrict_
         part0 = static_cast<uint64_t>(rowq) * sk.max_slots;
         n_splits = attend_stream_count(rowq / heads, n_tiles, sk.len, sk.rem);
     }
+    // block_parts != 0 (launch_attend_k8v4_wide): g is 17..32, query row m lies in the 16-row partial (m >> 4) * block_parts further on, at its
+    // row m & 15; every other caller has m < 16 and block_parts = 0: + 0 and m itself
+    part0 += static_cast<uint64_t>(m >> 4) * block_parts;
+    const uint32_t mr = m & 15u;
     const float* ml = part_ml + part0 * 32u;
     auto block_reduce = [&](float v, bool is_max) {
 #pragma unroll
@@ -983,18 +987,18 @@ __global__ __launch_bounds__(512) void k_attend_combine(const float* __restrict_
         return r;
     };
     float mloc = -INFINITY;
-    for (uint32_t s = t; s < n_splits; s += 512u) mloc = fmaxf(mloc, ml[s * 32u + m]);
+    for (uint32_t s = t; s < n_splits; s += 512u) mloc = fmaxf(mloc, ml[s * 32u + mr]);
     const float M = block_reduce(mloc, true);
     const float Mu = (M == -INFINITY) ? 0.0f : M;
     float lloc = 0.0f;
     for (uint32_t s = t; s < n_splits; s += 512u) {
-        const float ws = __builtin_amdgcn_exp2f(ml[s * 32u + m] - Mu);
+        const float ws = __builtin_amdgcn_exp2f(ml[s * 32u + mr] - Mu);
         w[s] = ws;
-        lloc += ws * ml[s * 32u + 16u + m];
+        lloc += ws * ml[s * 32u + 16u + mr];
     }
     const float L = block_reduce(lloc, false);                     // (its barriers also publish w[])
     const uint32_t grp = t >> 7, d = t & 127u;
-    const float* acc = part_acc + (part0 * 16u + m) * 128u + d;
+    const float* acc = part_acc + (part0 * 16u + mr) * 128u + d;
     float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f;
     uint32_t s = grp;
     for (; s + 12u < n_splits; s += 16u) {                         // four independent loads in flight per thread
@@ -1028,7 +1032,7 @@ __global__ __launch_bounds__(256) void k_attend_combine_small(const float* __res
                                                               uint32_t g, uint32_t n_splits, float* __restrict__ out,
                                                               float* __restrict__ lse, const AttendSeq* __restrict__ seqs,
                                                               uint32_t heads, uint32_t skip_single, uint32_t n_rows, AttendArgs::Stream sk, uint32_t n_tiles,
-                                                              uint32_t layer_seqs, uint32_t layer_parts)
+                                                              uint32_t layer_seqs, uint32_t layer_parts, uint32_t block_parts)
 {
     typedef float v4f __attribute__((ext_vector_type(4)));
     const uint32_t lane = threadIdx.x & 63u, c = lane & 15u, kb = lane >> 4;
@@ -1050,6 +1054,10 @@ __global__ __launch_bounds__(256) void k_attend_combine_small(const float* __res
         part0 = static_cast<uint64_t>(rowq) * sk.max_slots;
         n_splits = attend_stream_count(rowq / heads, n_tiles, sk.len, sk.rem);
     }
+    // grid y (launch_attend_k8v4_wide only: two, with block_parts != 0; one for every other caller) = the 16-row block of the group: its
+    // partials lie block_parts further on, its rows are 16 cb .. of the g <= 32
+    const uint32_t cb = 16u * blockIdx.y;
+    part0 += static_cast<uint64_t>(blockIdx.y) * block_parts;
     const float* ml = part_ml + part0 * 32u + c;
     float m[kSmallCombineSplits], l[kSmallCombineSplits];
     float M = -INFINITY;
@@ -1070,17 +1078,17 @@ __global__ __launch_bounds__(256) void k_attend_combine_small(const float* __res
         if (s < n_splits) {                                          // wave-uniform
             const float w = __builtin_amdgcn_exp2f(m[s] - Mu);
             L += w * l[s];
-            if (c < g) {
+            if (cb + c < g) {
 #pragma unroll
                 for (int i = 0; i < kIn; ++i) o[i] += *reinterpret_cast<const v4f*>(src + static_cast<uint64_t>(s) * 2048u + 4 * i) * w;
             }
         }
     }
-    if (c < g) {
-        float* dst = out + (static_cast<uint64_t>(rowq) * g + c) * 128u + 32u * kb + 4 * i0;
+    if (cb + c < g) {
+        float* dst = out + (static_cast<uint64_t>(rowq) * g + cb + c) * 128u + 32u * kb + 4 * i0;
 #pragma unroll
         for (int i = 0; i < kIn; ++i) *reinterpret_cast<v4f*>(dst + 4 * i) = L > 0.0f ? o[i] / L : v4f{0.0f, 0.0f, 0.0f, 0.0f};
-        if (lse && kb == 0u && i0 == 0) lse[static_cast<uint64_t>(rowq) * g + c] = L > 0.0f ? (M + log2f(L)) * 0.6931471805599453f : -INFINITY;
+        if (lse && kb == 0u && i0 == 0) lse[static_cast<uint64_t>(rowq) * g + cb + c] = L > 0.0f ? (M + log2f(L)) * 0.6931471805599453f : -INFINITY;
     }
 }
 
@@ -1180,9 +1188,12 @@ hipError_t launch_qk_scores_fp8_linear(const AttendArgs& a, uint32_t n_layers, f
 }
 
 constexpr uint32_t kSmallCombineRowsShared = 8192;     // rows up to which the small merge spends a workgroup per row (k_attend_combine_small<4>)
-hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s, uint32_t layer_seqs, uint32_t layer_parts)
+hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s, uint32_t layer_seqs, uint32_t layer_parts,
+                                 uint32_t block_parts)
 {
     if (n_layers == 0) return hipSuccess;
+    if (block_parts && (a.g <= 16u || a.g > 32u)) return hipErrorInvalidValue;                 // two blocks: 17..32 rows
+    const uint32_t blocks = block_parts ? 2u : 1u;
     const uint32_t splits = a.stream.n_wgs ? a.stream.max_slots : a.n_splits;      // most partials a row can have
     const uint32_t n_tiles = a.stream.tiles ? a.stream.tiles : (a.n_pages + 15u) / 16u;
     if (splits > kMaxSplits) return hipErrorInvalidValue;
@@ -1191,15 +1202,15 @@ hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* 
     if (splits <= kSmallCombineSplits) {
         const uint32_t n_rows = n_layers * a.heads;
         if (n_rows <= kSmallCombineRowsShared)
-            hipLaunchKernelGGL(k_attend_combine_small<4>, dim3(n_rows), dim3(256), 0, s, a.part_acc, a.part_ml, a.g,
-                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles, layer_seqs, layer_parts);
+            hipLaunchKernelGGL(k_attend_combine_small<4>, dim3(n_rows, blocks), dim3(256), 0, s, a.part_acc, a.part_ml, a.g,
+                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles, layer_seqs, layer_parts, block_parts);
         else
-            hipLaunchKernelGGL(k_attend_combine_small<1>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, a.part_acc, a.part_ml, a.g,
-                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles, layer_seqs, layer_parts);
+            hipLaunchKernelGGL(k_attend_combine_small<1>, dim3((n_rows + 3u) / 4u, blocks), dim3(256), 0, s, a.part_acc, a.part_ml, a.g,
+                               a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, n_rows, a.stream, n_tiles, layer_seqs, layer_parts, block_parts);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_attend_combine, dim3(n_layers * a.heads * a.g), dim3(512), 0, s, a.part_acc, a.part_ml, a.g,
-                       a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, a.stream, n_tiles, layer_seqs, layer_parts);
+                       a.n_splits, d_out, d_lse, a.seqs, a.heads, skip_single, a.stream, n_tiles, layer_seqs, layer_parts, block_parts);
     return hipGetLastError();
 }
 

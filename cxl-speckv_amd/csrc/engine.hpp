@@ -254,13 +254,14 @@ public:
     // entry (speckv_ext_attend_kv_batch_window; decode_window.hpp), as attend_batch's -- window = 0: the launches of the entry without one
     int attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
                         const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos = nullptr, uint32_t window = 0,
-                        const AttendHeldArgs* held = nullptr);
+                        const AttendHeldArgs* held = nullptr, bool wide = false);
     // the step of several positions over the split pool (speckv_ext_attend_kv_spec): its own refusals, then attend_batch_kv with the held rows;
-    // length / d_depth / window: the step on a sliding-window layer (speckv_ext_attend_kv_spec_window; spec_window.hpp), window = 0: none
+    // length / d_depth / window: the step on a sliding-window layer (speckv_ext_attend_kv_spec_window; spec_window.hpp), window = 0: none;
+    // wide: 17..32 query rows per kv head in one pass (speckv_ext_attend_kv_spec_wide; k_attend_k8v4_wide)
     int attend_spec_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
                        uint32_t rows_per_pos, const uint32_t* pos_end, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems,
                        uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s,
-                       const uint32_t* length = nullptr, const uint32_t* d_depth = nullptr, uint32_t window = 0);
+                       const uint32_t* length = nullptr, const uint32_t* d_depth = nullptr, uint32_t window = 0, bool wide = false);
     // the split pool's decode step for n_layers consecutive layers in one launch (speckv_ext_attend_kv_layers; engine_attend_kv.cpp): q / out / lse
     // rows [layer][sequence], one descriptor per sequence, the tails of odd lengths folded inside the launch
     int attend_layers_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer_begin, uint32_t n_layers, const void* d_q_f16,

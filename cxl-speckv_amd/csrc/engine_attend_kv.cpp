@@ -1,5 +1,5 @@
 // cxl-speckv_amd/csrc/engine_attend_kv.cpp -- Engine::attend_batch_kv, the body behind speckv_ext_attend_kv_batch,
-// speckv_ext_attend_kv_batch_window, speckv_ext_attend_kv_spec and speckv_ext_attend_kv_spec_window: one decode step of a batch over the SPLIT POOL ("K8V4": a sequence's K rows in an FP8_E4M3
+// speckv_ext_attend_kv_batch_window, speckv_ext_attend_kv_spec, speckv_ext_attend_kv_spec_window and speckv_ext_attend_kv_spec_wide: one decode step of a batch over the SPLIT POOL ("K8V4": a sequence's K rows in an FP8_E4M3
 // allocation, its V rows in an MXFP4 allocation), one attention launch (k_attend_k8v4, attend_kv.hip) and, where members have several
 // pieces, the merge behind it
 #include "engine_internal.hpp"
@@ -30,12 +30,17 @@ namespace speckv {
 // slot of the descriptor ring carries the member's SIGNED rel (k_attend_k8v4<true, true> adds the row's depth).  A member no row of
 // which sees a pool position is one with nothing stored: its held positions alone.  A window that can cut no member (length + 16 <=
 // window for all): the descriptors, the instance and the launches of the entry without one.
+// wide (speckv_ext_attend_kv_spec_wide, with held): 17 <= g <= 32 rows in one pass -- k_attend_k8v4_wide (attend_kv_wide.hip), a wave per kv
+// head, sequence and piece as ever, so look-ups, the region rule, the window range, the launch decision (the FP8 batch rule with the same
+// members and tiles: no split rule of its own), the slot and the refusals are the ones above.  What differs: the bound on g, twice the
+// partials (a piece leaves one of 16 rows per block) and the launcher.
 int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
                             const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos, uint32_t window,
-                            const AttendHeldArgs* held)
+                            const AttendHeldArgs* held, bool wide)
 {
-    const char* entry = held ? (window ? "speckv_ext_attend_kv_spec_window" : "speckv_ext_attend_kv_spec")
-                             : window ? "speckv_ext_attend_kv_batch_window" : "speckv_ext_attend_kv_batch";
+    const char* entry = wide ? "speckv_ext_attend_kv_spec_wide"
+                        : held ? (window ? "speckv_ext_attend_kv_spec_window" : "speckv_ext_attend_kv_spec")
+                               : window ? "speckv_ext_attend_kv_batch_window" : "speckv_ext_attend_kv_batch";
     if (null_) return no_data_path(entry);
     if (window && !q_pos) return SPECKV_ERR_INVAL;
     if (!window) q_pos = nullptr;                                        // (no window: the launches of the entry without one)
@@ -44,7 +49,7 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
         SPECKV_ERR("%s cannot be captured into a HIP graph (its descriptors are staged per call)", entry);
         return SPECKV_ERR_INVAL;
     }
-    if (!k_handles || !v_handles || !pos_end || !d_q_f16 || !d_out || g == 0 || g > 16) return SPECKV_ERR_INVAL;
+    if (!k_handles || !v_handles || !pos_end || !d_q_f16 || !d_out || g == 0 || g > (wide ? 32u : 16u) || (wide && (!held || g <= 16))) return SPECKV_ERR_INVAL;
     if (reinterpret_cast<uintptr_t>(d_q_f16) % 16u || reinterpret_cast<uintptr_t>(d_out) % 16u) return SPECKV_ERR_INVAL;
     std::vector<AttendSeq> seqs(n_seq);
     std::vector<AttendKvSide> vside(n_seq);
@@ -109,7 +114,8 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
     bool merge = false;
     for (uint32_t i = 0; i < n_seq; ++i) merge = merge || seqs[i].n_splits > 1u;
     AttendArgs k{};
-    if (!attend_scratch(k, merge ? parts : 1u, 0, s)) return SPECKV_ERR_NOMEM;
+    if (wide && parts > 0xFFFFFFFFull) return SPECKV_ERR_INVAL;
+    if (!attend_scratch(k, merge ? parts * (wide ? 2u : 1u) : 1u, 0, s)) return SPECKV_ERR_NOMEM;
     // descriptors, then the V sides, then the dispatch order, then the skip array of a launch that a window cuts: one slot, read in place by
     // the kernels (Engine::attend_batch)
     const size_t desc_bytes = n_seq * sizeof(AttendSeq), side_bytes = n_seq * sizeof(AttendKvSide), idx_bytes = n_seq * sizeof(uint32_t);
@@ -142,7 +148,8 @@ int Engine::attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uin
     for (uint32_t i = 0; i < n_seq; ++i) { note_use(ks[i], s); note_use(vs[i], s); }      // speckv_free waits for this stream
     // The guard event is recorded on every way out from here on: the slot must not be written again under a kernel still reading it.
     SlotGuard slot_guard{seq_ring_.ev[slot], st};
-    if (held) HIP_TRY(launch_attend_k8v4_held(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), *held, n_seq, merge, d_out, d_lse, st));
+    if (wide) HIP_TRY(launch_attend_k8v4_wide(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), *held, n_seq, static_cast<uint32_t>(parts), merge, d_out, d_lse, st));
+    else if (held) HIP_TRY(launch_attend_k8v4_held(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), *held, n_seq, merge, d_out, d_lse, st));
     else HIP_TRY(launch_attend_k8v4(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), n_seq, merge, d_out, d_lse, st));
     if (!s) HIP_TRY(hipStreamSynchronize(stream_));
     return SPECKV_OK;
@@ -280,12 +287,15 @@ int Engine::attend_layers_kv(uint32_t n_seq, const uint64_t* k_handles, const ui
 
 // speckv_ext_attend_kv_spec.  What concerns the held rows and the mask is judged first, so a bad set is SPECKV_ERR_INVAL on every engine
 // (the folds' rule: Engine::fold_held_args_ok); the rest is attend_batch_kv's.  window != 0 (speckv_ext_attend_kv_spec_window): length and
-// d_depth are judged here as well; window == 0: neither is looked at.
+// d_depth are judged here as well; window == 0: neither is looked at.  wide (speckv_ext_attend_kv_spec_wide): the same judgement for
+// 17 <= g <= 32 with rows_per_pos >= 2.
 int Engine::attend_spec_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
                            uint32_t rows_per_pos, const uint32_t* pos_end, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems,
                            uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s,
-                           const uint32_t* length, const uint32_t* d_depth, uint32_t window)
+                           const uint32_t* length, const uint32_t* d_depth, uint32_t window, bool wide)
 {
+    // speckv_ext_attend_kv_spec_wide: 17..32 rows; fewer belong to the entries above, and one row per position would be 17+ positions
+    if (wide && (g <= 16 || g > 32 || rows_per_pos == 1)) return SPECKV_ERR_INVAL;
     if (rows_per_pos == 0 || g % rows_per_pos || g / rows_per_pos > SPECKV_HELD_MAX - 1u) return SPECKV_ERR_INVAL;
     if (!d_k_held || !d_v_held || !d_mask || mask_stride < g / rows_per_pos) return SPECKV_ERR_INVAL;
     if (seq_stride_elems % 8u || pos_stride_elems % 8u || pos_stride_elems < 8u * 128u) return SPECKV_ERR_INVAL;
@@ -297,7 +307,7 @@ int Engine::attend_spec_kv(uint32_t n_seq, const uint64_t* k_handles, const uint
     }
     const AttendHeldArgs held{static_cast<const uint16_t*>(d_k_held), static_cast<const uint16_t*>(d_v_held), seq_stride_elems, pos_stride_elems,
                               d_mask, mask_stride, rows_per_pos, window ? d_depth : nullptr};
-    return attend_batch_kv(n_seq, k_handles, v_handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse, s, window ? length : nullptr, window, &held);
+    return attend_batch_kv(n_seq, k_handles, v_handles, layer, d_q_f16, g, pos_end, sm_scale, d_out, d_lse, s, window ? length : nullptr, window, &held, wide);
 }
 
 } // namespace speckv

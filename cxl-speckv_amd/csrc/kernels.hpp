@@ -773,8 +773,10 @@ __host__ __device__ inline uint32_t attend_tile_slot(uint32_t j) { return j < 8u
 hipError_t launch_attend_int4(const AttendArgs& a, uint32_t n_layers, hipStream_t s);
 // layer_seqs != 0 (launch_attend_k8v4_layers only; 0 for every other caller): the rows are [layer][sequence] over ONE descriptor per sequence --
 // row block y reads a.seqs[y % layer_seqs], its partials lie (y / layer_seqs) * layer_parts further on
+// block_parts != 0 (launch_attend_k8v4_wide only; 0 for every other caller): a.g is 17..32 and a (head, piece) left TWO partials of 16 rows --
+// rows 16b .. 16b + 15 of the group in the partial block_parts behind block 0's -- which are merged into out / lse rows row * g + 16b + c
 hipError_t launch_attend_combine(const AttendArgs& a, uint32_t n_layers, float* d_out, float* d_lse, hipStream_t s, uint32_t layer_seqs = 0,
-                                 uint32_t layer_parts = 0);
+                                 uint32_t layer_parts = 0, uint32_t block_parts = 0);
 // MXFP4 records (attend_mx4.hip): a.lin_base | a.stripe_bases | a.table_form choose the address form, a.q16 = the fp16 query rows,
 // a.seqs the batch descriptors; n_rows = layers or sequences.  Launches the merge itself when the rows are not final.
 hipError_t launch_attend_mx4(const AttendArgs& a, uint32_t n_rows, float* d_out, float* d_lse, hipStream_t s);
@@ -814,6 +816,12 @@ struct AttendHeldArgs {
 // k_attend_k8v4<true, true> -- seq_skip[sequence] is then the sequence's signed rel of spec_window.hpp, not a position count.
 hipError_t launch_attend_k8v4_held(const AttendArgs& a, const AttendKvSide* d_vside, const AttendHeldArgs& h, uint32_t n_seq, bool merge, float* d_out,
                                    float* d_lse, hipStream_t s);
+// The same step with 17 <= a.g <= 32 query rows per kv head in ONE pass over the records (attend_kv_wide.hip: k_attend_k8v4_wide;
+// speckv_ext_attend_kv_spec_wide): a wave carries two blocks of 16 rows over each tile's K bytes and widened V operand.  The partials are
+// 16 rows each, so a (head, piece) leaves two: a.part_acc / part_ml hold 2 x block_parts of them, block 1's block_parts (= the partials of
+// one block, what assign_pieces counted) behind block 0's.  h.rows_per_pos >= 2: a step has at most SPECKV_HELD_MAX - 1 positions.
+hipError_t launch_attend_k8v4_wide(const AttendArgs& a, const AttendKvSide* d_vside, const AttendHeldArgs& h, uint32_t n_seq, uint32_t block_parts, bool merge,
+                                   float* d_out, float* d_lse, hipStream_t s);
 // The decode step of SEVERAL layers over the split pool in one launch (k_attend_k8v4<false, false, AttendKvLayers>; speckv_ext_attend_kv_layers):
 // the grid carries layer x sequence x head quad, member y = [layer][sequence] is the row block of q / out / lse (a.batch_n_seq = n_seq,
 // a.batch_layer = the first layer).  a.seqs / d_vside hold ONE descriptor per sequence, for region 0 of its allocations: the kernel moves to

@@ -787,15 +787,19 @@ class SpeckvKVConnector(SharedPrefixSteps):
 
     # ------------------------------------------------------------------ steps of several positions
     @staticmethod
-    def spec_groups(S: int, rows_per_pos: int):
+    def spec_groups(S: int, rows_per_pos: int, rows_per_pass: int = 16):
         """How a step of S new positions with rows_per_pos query rows per kv head and position goes through the attention kernels,
         which take at most 16 query rows per kv head in one pass over the records: [(first position, positions)] -- groups of
-        16 // rows_per_pos positions, the last one possibly shorter.  One group = one pass; every further group reads the records again."""
+        16 // rows_per_pos positions, the last one possibly shorter.  One group = one pass; every further group reads the records again.
+        rows_per_pass = 32 (SpeckvSplitKVConnector.attend_spec only; this connector's kernels take 16): groups of 32 // rows_per_pos
+        positions, for the split pool's kernel that carries two blocks of 16 rows through one pass."""
+        if rows_per_pass not in (16, 32):
+            raise ValueError("rows_per_pass must be 16 or 32 (query rows per kv head in one pass over the records)")
         if not 1 <= rows_per_pos <= 16:
             raise ValueError("rows_per_pos must be 1..16 (query rows per kv head of one position)")
         if not 1 <= S <= HELD_MAX - 1:
             raise ValueError(f"a step carries 1..{HELD_MAX - 1} new positions per request")
-        per = 16 // rows_per_pos
+        per = rows_per_pass // rows_per_pos
         return [(j0, min(per, S - j0)) for j0 in range(0, S, per)]
 
     @staticmethod

@@ -24,7 +24,9 @@ region l of the V allocation layer l's V.  Every write, copy and placement path 
   attend_spec                           one layer of a DRAFT step (S new positions per request, a chain or a tree) on the decode kernel: per
                                         group of 16 // rows_per_pos positions ONE speckv_ext_attend_kv_spec -- the stored positions walked
                                         once for up to 16 query rows per kv head, the tail and the new rows folded in inside that launch;
-                                        window=W: the step on a sliding-window layer, ONE speckv_ext_attend_kv_spec_window per group
+                                        window=W: the step on a sliding-window layer, ONE speckv_ext_attend_kv_spec_window per group;
+                                        rows_per_pass=32 (opt-in): groups of 32 // rows_per_pos positions, a group of 17..32 rows ONE
+                                        speckv_ext_attend_kv_spec_wide -- two blocks of 16 rows per wave in one pass over the records
   attend_shared / attend_chunk_shared   attend / attend_chunk for members that SHARE A PREFIX without holding a copy of it: the own part as
                                         those methods issue it with the log-sum-exp kept, then ONE speckv_ext_attend_prefix_fold_kv launch
                                         that reads the prefix's FP8 keys and MXFP4 values once per 64 query rows and folds them in
@@ -467,7 +469,7 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
 
     # ------------------------------------------------------------------ a draft step on the decode kernel
     def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None,
-                    window=None):
+                    window=None, rows_per_pass=16):
         """One layer of a step that carries S new positions per request -- draft tokens to verify -- on the DECODE kernel; signature and
         contract of SpeckvKVConnector.attend_spec.  q [batch][S][heads][rows_per_pos][dim] fp16; k_new / v_new
         [batch][S][layers][heads][dim] fp16, the positions that would follow each request's current length; n_new: optional per-request
@@ -495,6 +497,12 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         and at 256 x 8k stored positions, 0.93-0.94 at 8 x 32k with (S, rows_per_pos) = (4, 4) and (2, 8); at 8 x 32k with (16, 1) the
         two are equal within the spread (1.01, spread 0.021): with few requests and 16 positions per step attend_chunk(window=W) is as
         good.  0.28-0.83 of an unwindowed attend_spec, 1.30-1.50 single attend(window=W) steps.
+        rows_per_pass (16: exactly the calls above and their bits; 32: opt-in): the groups are spec_groups(S, rows_per_pos, 32), 32 //
+        rows_per_pos positions each; a group of more than 16 rows is ONE speckv_ext_attend_kv_spec_wide call (k_attend_k8v4_wide: two
+        blocks of 16 rows per wave over each tile's K bytes and widened V operand, window or not), a last or only group of 16 rows or
+        fewer goes through the entries above.  Chains, trees, ragged steps and window=W keep their contracts.  rows_per_pos = 1: a step
+        has at most 16 positions, so 32 is the 16-row route.  Whether it pays depends on the shape (profiles/k8v4_spec_wide.txt),
+        so 16 stays the default.  Any other value is a ValueError.
         Malformed arguments are a ValueError / KeyError before any library call; a placement the decode kernel does not serve
         (striped, migrated) is the library's SpeckvError, passed through as in attend."""
         import numbers
@@ -509,7 +517,7 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
             raise ValueError("k_new / v_new must be [batch][S][layers][heads][dim]")
         if not _is_int(layer) or not 0 <= layer < self.L:
             raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
-        groups = SpeckvKVConnector.spec_groups(S, R)
+        groups = SpeckvKVConnector.spec_groups(S, R, rows_per_pass)
         W = SpeckvKVConnector._decode_window(window)
         if n_new is not None:
             n_new = [int(n) for n in n_new]
@@ -560,6 +568,11 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                     parts.append((j0, n, g, q[:, j0:j0 + n].permute(0, 2, 1, 3, 4).reshape(B, H, g, D).contiguous(),
                                   torch.empty((B, H, g, D), dtype=torch.float32, device="cuda")))
             for j0, n, g, qg, og in parts:
+                if g > 16:                            # rows_per_pass = 32: both blocks of 16 rows in one pass over the records, window or not
+                    self.lib.attend_kv_spec_wide(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, lengths, depths.data_ptr() + 4 * j0 if W else 0, W,
+                                                 kh.data_ptr(), vh.data_ptr(), (1 + S) * row, row, masks.data_ptr() + 4 * j0, S, sm_scale,
+                                                 og.data_ptr(), 0, st.cuda_stream)
+                    continue
                 if W:                                 # a sliding-window layer: the same launch, the stored positions masked per row by its depth
                     self.lib.attend_kv_spec_window(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, lengths, depths.data_ptr() + 4 * j0, W,
                                                    kh.data_ptr(), vh.data_ptr(), (1 + S) * row, row, masks.data_ptr() + 4 * j0, S, sm_scale,

@@ -1466,6 +1466,27 @@ speckv_status_t speckv_ext_attend_kv_spec_window(uint32_t n_seq, const speckv_ha
                                                  const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask,
                                                  uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse /* optional */, void* stream);
 
+/* speckv_ext_attend_kv_spec_wide: the multi-position step over a split pool with 17 <= g <= 32 query rows per kv head in ONE pass over
+ * the records -- at 8 query heads per kv head, 3 or 4 draft positions (rows_per_pos = 8), up to 8 (rows_per_pos = 4) or up to 16
+ * (rows_per_pos = 2), which speckv_ext_attend_kv_spec[_window] take as two calls of 16 rows at most, each walking every stored K and V
+ * record again.  The argument list of speckv_ext_attend_kv_spec_window, every argument with its meaning there; window == 0: a global
+ * layer (neither length nor d_depth is read), window >= 1: a sliding-window layer.  An additive entry: SPECKV_EXT_ABI_VERSION stays what
+ * it is, and the two entries above keep refusing g > 16.
+ * The kernel (k_attend_k8v4_wide) carries two blocks of 16 query rows per wave, rows 0..15 and 16..31 of the group: each tile's K bytes,
+ * page scales, V bytes and widened V operand are fetched and built once and meet both blocks' query operands and weights.  Values per
+ * row are those of speckv_ext_attend_kv_spec[_window]: the row's own E4M3 query scale, its own softmax, its own mask word (query position
+ * r / rows_per_pos) and, under a window, its own depth; a held position is loaded once and scored against both blocks' fp16 rows.  The
+ * launch decision (pieces, dispatch order), addressing, placement (single runs only), stream rules, ordering behind pool writes and
+ * statuses are those of speckv_ext_attend_kv_spec.  NOT capturable into a HIP graph.
+ * SPECKV_ERR_INVAL besides what speckv_ext_attend_kv_spec_window refuses, judged before anything else and on every engine: g <= 16 (such a
+ * step belongs to the entries above), g > 32, rows_per_pos == 1 (17 or more positions: beyond SPECKV_HELD_MAX - 1 and the mask word) --
+ * nothing is launched, d_out is untouched.  Whether one wide call beats two 16-row calls depends on the shape: profiles/k8v4_spec_wide.txt. */
+speckv_status_t speckv_ext_attend_kv_spec_wide(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles,
+                                               uint32_t layer, const void* d_q_f16, uint32_t g, uint32_t rows_per_pos, const uint32_t* pos_end,
+                                               const uint32_t* length, const uint32_t* d_depth, uint32_t window, const void* d_k_held,
+                                               const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask,
+                                               uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse /* optional */, void* stream);
+
 /* The walk rule of speckv_ext_attend_kv_spec_window as a pure function (works without speckv_init, needs no device): for a member of
  * `length` committed positions under window W >= 1, *out_begin = the first position walked (a multiple of 32), *out_n_pages = the pages
  * walked from there (0: no row sees a stored position), *out_rel = length + 1 - W - begin, signed -- a row of depth d does not see the
