@@ -816,6 +816,11 @@ struct AttendHeldArgs {
 // k_attend_k8v4<true, true> -- seq_skip[sequence] is then the sequence's signed rel of spec_window.hpp, not a position count.
 hipError_t launch_attend_k8v4_held(const AttendArgs& a, const AttendKvSide* d_vside, const AttendHeldArgs& h, uint32_t n_seq, bool merge, float* d_out,
                                    float* d_lse, hipStream_t s);
+// The same step over ONE FP8_E4M3 allocation on a sliding-window layer (attend_fp8_spec.hip: k_attend_fp8_spec; speckv_ext_attend_spec_window):
+// a.seqs as for launch_attend_fp8_batch in the linear form (K and V regions by k_first / v_first), the descriptors starting at the tile of
+// depth 0's bound; a.seq_skip (always set: one instance) the members' signed rel of spec_window.hpp, h.depth the depth table.  a.direct_out
+// == d_out: members with one piece or none are written final by the kernel; merge: some member has several -- launch_attend_combine follows.
+hipError_t launch_attend_fp8_spec(const AttendArgs& a, const AttendHeldArgs& h, uint32_t n_seq, bool merge, float* d_out, float* d_lse, hipStream_t s);
 // The same step with 17 <= a.g <= 32 query rows per kv head in ONE pass over the records (attend_kv_wide.hip: k_attend_k8v4_wide;
 // speckv_ext_attend_kv_spec_wide): a wave carries two blocks of 16 rows over each tile's K bytes and widened V operand.  The partials are
 // 16 rows each, so a (head, piece) leaves two: a.part_acc / part_ml hold 2 x block_parts of them, block 1's block_parts (= the partials of

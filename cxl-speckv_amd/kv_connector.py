@@ -126,6 +126,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
         self._plan_stream = None
         self._kscale = self._kscale_inv = None               # set_k_channel_scale
         self._spec_key = self._spec_idx = self._spec_base = None     # attend_spec: where the held rows of a step come from
+        self._spec_window = (None,)                                  # attend_spec(window=W): (key, mask words, depths [batch][S], pos_end, lengths)
         self._tree_key = self._tree_masks = None                     # attend_spec(parents=...): the mask words of a step, [n_layers * batch][S]
         self._chunk_tree_key = self._chunk_tree_masks = None         # attend_chunk(parents=...): the mask rows of a step, [batch][S][W]
         self._chunk_tree_wtabs = {}                                  # attend_tree(window=W): W -> (key, mask rows, depths [batch][S])
@@ -932,7 +933,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
             held.append(flat.index_select(1, self._spec_idx))
         return held[0], held[1], self._spec_base
 
-    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None):
+    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None, window=None):
         """One layer of a step that carries S new positions per request -- draft tokens to verify, a chunk of a prompt: query position
         j of a request sees everything the request holds (pool and odd last position) and the new positions 0..j.
         q [batch][S][heads][rows_per_pos][dim] fp16; k_new / v_new [batch][S][layers][heads][dim] fp16, the positions that would follow
@@ -945,17 +946,32 @@ class SpeckvKVConnector(SharedPrefixSteps):
         parents (see tree_masks): the new positions form a tree instead of a chain -- node j sees what the request holds, its ancestors
         and itself, not its siblings.  The pass over the records is the same; the held rows are folded in by
         speckv_ext_attend_fold_masked, one launch per group, with the group's columns of the step's mask table (a node's ancestors in
-        earlier groups are held positions like any other).  Rows of dead nodes (>= n_new[b], or below one) are unspecified but finite."""
-        return self.attend_spec_layers(layer, 1, req_ids, q[None], k_new, v_new, sm_scale, n_new, stream, parents)[0]
+        earlier groups are held positions like any other).  Rows of dead nodes (>= n_new[b], or below one) are unspecified but finite.
+        window (None or 0: none, exactly the calls above and their bits; W >= 1: a sliding-window layer, FP8 pools only): the contract of
+        SpeckvSplitKVConnector.attend_spec(window=W).  Each group is ONE speckv_ext_attend_spec_window call per layer and nothing else --
+        no plan, no fold launch: node j of depth d (chunk_tree_depths; a chain: j) sits at length + d and sees the last W positions up to
+        itself, the stored ones from length + d + 1 - W on, masked per query row inside the kernel (k_attend_fp8_spec; the walk starts at
+        the tile of depth 0's bound, spec_window_range), the held ones through the words of tree_masks(window=W).  A dead node's rows are
+        the stored positions its depth's window shows, finite; zeros where it shows none.  Changes no state.  An INT4 or MXFP4 pool is a
+        ValueError: their local layers take attend_chunk(window=W) / attend_tree(window=W).
+        Against attend_chunk(window=W) with the same step, until now the only route on a local layer (profiles/fp8_spec_window.txt;
+        W = 1024, 16 query rows per kv head): 0.46-0.49 of its time at 256 requests x 2k and at 256 x 8k stored positions; at 8 x 32k it is
+        SLOWER, 1.05-1.10 of the chunk route's time -- the crossover lies at few requests, where attend_chunk(window=W) /
+        attend_tree(window=W) is the route to take.  0.28-0.82 of an unwindowed attend_spec, 1.75-1.94 single attend(window=W) steps."""
+        return self.attend_spec_layers(layer, 1, req_ids, q[None], k_new, v_new, sm_scale, n_new, stream, parents, window)[0]
 
     def attend_spec_layers(self, layer_begin: int, n_layers: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None,
-                           stream=None, parents=None):
+                           stream=None, parents=None, window=None):
         """attend_spec for n_layers consecutive layers whose query rows exist at once: q [n_layers][batch][S][heads][rows_per_pos][dim],
         returns the same shape in fp32.  Per group of positions one speckv_ext_attend_planned_layers call and one fold launch over all
-        the layers."""
+        the layers.  window=W >= 1 (the layers are sliding-window layers of one window; FP8 pools): per group and layer ONE
+        speckv_ext_attend_spec_window call, see attend_spec."""
         import torch
         if self.scheme not in FUSED:
             raise ValueError("attend_spec() needs an FP8, INT4 or MXFP4 pool")
+        W = self._decode_window(window)
+        if W and self.scheme != SCHEMES["fp8"]:
+            raise ValueError("attend_spec(window=W) serves FP8 pools; on an INT4 or MXFP4 pool a local layer takes attend_chunk(window=W) / attend_tree(window=W)")
         NL, B, S, H, R, D = q.shape
         if NL != n_layers or tuple(k_new.shape) != (B, S, self.L, H, D) or tuple(v_new.shape) != (B, S, self.L, H, D):
             raise ValueError("q must be [n_layers][batch][S][heads][rows_per_pos][dim], k_new / v_new [batch][S][layers][heads][dim]")
@@ -969,6 +985,8 @@ class SpeckvKVConnector(SharedPrefixSteps):
             q = q * self._kscale[layer_begin:layer_begin + n_layers][:, None, None, :, None, :]
             k_new = k_new * self._kscale_inv[None, None]
         out = torch.empty((NL, B, S, H, R, D), dtype=torch.float32, device="cuda")
+        if W:
+            return out if B == 0 else self._spec_window_layers(layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out)
         akey = (key, self._epoch)
         with self._On(self, stream) as st:
             if self._arg_key != (akey, st.cuda_stream):
@@ -999,6 +1017,40 @@ class SpeckvKVConnector(SharedPrefixSteps):
                     self.lib.attend_fold_held(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
                                               d_base.data_ptr(), 0 if d_live is None else d_live.data_ptr(), sm_scale, og.data_ptr(),
                                               lse.data_ptr(), st.cuda_stream)
+                    out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
+        return out
+
+    def _spec_window_layers(self, layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out):
+        """attend_spec_layers(window=W) on an FP8 pool: per group and layer one speckv_ext_attend_spec_window.  The mask words
+        (tree_masks(window=W); a chain is the tree parents[j] = j - 1), the depths, pos_end and the lengths are made once per
+        (batch, epoch, S, tree, live counts, W); the held rows are _held_rows'."""
+        import numpy as np
+        import torch
+        NL, B, S, H, R, D = q.shape
+        tree = list(range(-1, S - 1)) if parents is None else list(parents)
+        one = len(tree) > 0 and isinstance(tree[0], numbers.Integral)
+        wkey = (key, self._epoch, S, tuple(tree) if one else tuple(map(tuple, tree)), None if n_new is None else tuple(n_new), W)
+        if self._spec_window[0] != wkey:
+            trees = self._tree_parents(tree, B)
+            if len(trees[0]) != S:
+                raise ValueError("parents: one entry per new position")
+            words = self.tree_masks(trees, [r.length & 1 for r in reqs], n_new, window=W)
+            depths = self.chunk_tree_depths(trees, B)
+            self._spec_window = (wkey, _device_index([w for row in words for w in row]), _device_index([d for row in depths for d in row]),
+                                 np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32), np.asarray([r.length for r in reqs], dtype=np.uint32))
+        _, masks, depths, pos_end, lengths = self._spec_window
+        handles = self._batch(req_ids)[2]
+        with self._On(self, stream) as st:
+            with torch.cuda.stream(st):
+                kh, vh, _ = self._held_rows(req_ids, key, reqs, k_new, v_new, layer_begin, NL, st)      # [n_layers][batch][1 + S][heads][dim]
+                for j0, n in groups:
+                    g = n * R
+                    qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
+                    og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
+                    for l in range(NL):
+                        self.lib.attend_spec_window(handles, layer_begin + l, qg[l].data_ptr(), g, R, pos_end, lengths, depths.data_ptr() + 4 * j0, W,
+                                                    kh[l].data_ptr(), vh[l].data_ptr(), (1 + S) * H * D, H * D, masks.data_ptr() + 4 * j0, S, sm_scale,
+                                                    og[l].data_ptr(), 0, st.cuda_stream)
                     out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
         return out
 

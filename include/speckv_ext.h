@@ -1487,6 +1487,45 @@ speckv_status_t speckv_ext_attend_kv_spec_wide(uint32_t n_seq, const speckv_hand
                                                const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask,
                                                uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse /* optional */, void* stream);
 
+/* speckv_ext_attend_spec_window: the MULTI-POSITION STEP of a batch over an FP8_E4M3 pool on a SLIDING-WINDOW (local) layer -- verifying
+ * the draft positions of every sequence, a chain or a tree, on the decode kernel and in ONE launch: what speckv_ext_attend_kv_spec_window
+ * is to the split pool, for the pool format that keeps K and V in one allocation.  The arguments of speckv_ext_attend_kv_spec_window in
+ * the same order and with the same meaning, with ONE handle array in the place of two: sequence i is the FP8_E4M3 allocation handles[i],
+ * read as speckv_ext_attend_fp8_batch reads it (layout 8 heads x 128 fp16, num_tokens a multiple of 32, layer inside the layout).  An
+ * additive entry: SPECKV_EXT_ABI_VERSION stays what it is.
+ * The kernel (k_attend_fp8_spec): g = n_q x rows_per_pos <= 16 query rows per kv head in one pass over the records of the walk, a wave
+ * per kv head, sequence and piece; the walk, the per-row mask by node depth, the members without a visible stored position and the held
+ * rows folded by a sequence's first piece are those described at speckv_ext_attend_kv_spec_window (speckv_ext_spec_window_range is the
+ * rule).  Pieces and dispatch order are decided on the pages walked, by the rule of speckv_ext_attend_fp8_batch.
+ * Values.  The stored part as speckv_ext_attend_fp8_batch: the query as E4M3 x a row scale, K as its E4M3 values with the page scale on
+ * the score, V as its E4M3 values with the page scale on the fp16 weight (relative to the tile's largest).  A held position as in
+ * speckv_ext_attend_kv_spec: the FP16 query, fp32 sums, its fp16 V row weighted in fp32.  A row that sees nothing anywhere is zeros
+ * with lse = -inf; records in front of every row's window leave no trace whatever they hold.
+ * window >= 1 always: a global layer takes speckv_ext_attend_fp8_planned and a fold launch as before.  Single runs only; NOT capturable
+ * into a HIP graph; stream == NULL is the synchronous call; ordering behind pool writes as speckv_ext_attend_kv_batch.
+ * Refusals, in this order, nothing launched and d_out untouched.  SPECKV_ERR_INVAL, judged before anything else and on every engine:
+ *   g == 0, g > 16, rows_per_pos == 0, g not a multiple of rows_per_pos, g / rows_per_pos > SPECKV_HELD_MAX - 1, a stride that is not a
+ *       multiple of 8, pos_stride_elems < 8 * 128, seq_stride_elems below what g / rows_per_pos held positions take, a NULL d_q_f16,
+ *       d_k_held, d_v_held or d_out;
+ *   a NULL d_mask, mask_stride < g / rows_per_pos;
+ *   a query, output or held pointer that is not 16-byte aligned;
+ *   window == 0;
+ *   a NULL length or d_depth;
+ *   an odd pos_end[i], a length[i] outside {pos_end[i], pos_end[i] + 1}.
+ * Then SPECKV_ERR_DRIVER on an engine without a device ("/dev/null"); n_seq == 0 is SPECKV_OK; then SPECKV_ERR_INVAL for
+ *   a capturing stream;
+ *   a NULL handles or pos_end;
+ *   (SPECKV_ERR_GENERAL: an unknown handle)
+ *   an allocation of another scheme (INT4_G32, MXFP4: speckv_ext_attend_chunk_window serves them) or without a layout;
+ *   a layout that is not 8 x 128 fp16 with num_tokens % 32 == 0, a layer or a pos_end[i] outside it;
+ *   a placement that is not one run (striped, pages migrated): the message names speckv_ext_attend_chunk_window, which serves any.
+ * speckv_free of an allocation waits for `stream`.  Against the chunk route on the same step: profiles/fp8_spec_window.txt. */
+speckv_status_t speckv_ext_attend_spec_window(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g,
+                                              uint32_t rows_per_pos, const uint32_t* pos_end, const uint32_t* length, const uint32_t* d_depth,
+                                              uint32_t window, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems,
+                                              uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale,
+                                              float* d_out, float* d_lse /* optional */, void* stream);
+
 /* The walk rule of speckv_ext_attend_kv_spec_window as a pure function (works without speckv_init, needs no device): for a member of
  * `length` committed positions under window W >= 1, *out_begin = the first position walked (a multiple of 32), *out_n_pages = the pages
  * walked from there (0: no row sees a stored position), *out_rel = length + 1 - W - begin, signed -- a row of depth d does not see the

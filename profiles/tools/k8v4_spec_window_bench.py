@@ -30,13 +30,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from shared_prefix_bench import in_turn                                     # the method, unchanged
 
+# what profiles/tools/fp8_spec_window_bench.py replaces to run the same measurement over an FP8 pool
+POOL, OUT, TOOL = "the K8V4 split pool", "k8v4_spec_window.txt", "k8v4_spec_window_bench.py"
+
+
+def connector(lib, L, H, D, T):
+    from cxl_speckv_amd.kv_split_connector import SpeckvSplitKVConnector
+    return SpeckvSplitKVConnector(lib, L, H, D, T)
+
 
 def measure(a, library, routes, say):
     """-> {(n, ctx, S, R): [(median, spread) per route]} for the routes named, over `library`"""
     sys.path.insert(0, ROOT)
     import torch
     import cxl_speckv_amd as pkg
-    from cxl_speckv_amd.kv_split_connector import SpeckvSplitKVConnector
 
     L, H, D, W = 2, 8, 128, a.window                                         # (the split pool's allocations hold an even number of regions)
     sm = D ** -0.5
@@ -52,7 +59,7 @@ def measure(a, library, routes, say):
     for n, ctx in shapes:
         lib = pkg.SpeckvLib(library or pkg.library_path(), "hip:0")
         try:
-            conn = SpeckvSplitKVConnector(lib, L, H, D, ctx + 64)
+            conn = connector(lib, L, H, D, ctx + 64)
             rids = list(range(n))
             pk, pv = rnd(L, ctx, H, D), rnd(L, ctx, H, D)                   # (every request holds the same rows: the timing does not read values)
             keep = []
@@ -88,7 +95,7 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--alternations", type=int, default=2)
     ap.add_argument("--child", default=None, help="internal: measure routes c and d over this library and print one JSON line")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "k8v4_spec_window.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", OUT))
     a = ap.parse_args()
     if a.child is not None:
         got = measure(a, a.child or None, "cd", lambda *x: None)
@@ -101,8 +108,8 @@ def main():
     def say(line):
         print(line, flush=True)
         lines.append(line)
-    say(f"a draft step on a sliding-window layer over the K8V4 split pool: W = {a.window}, layer 0 of 2, {torch.cuda.get_device_properties(0).multi_processor_count} CUs, "
-        f"{datetime.date.today().isoformat()} (profiles/tools/k8v4_spec_window_bench.py, {a.rounds} rounds of {a.reps} calls, routes in turn; ms per call)")
+    say(f"a draft step on a sliding-window layer over {POOL}: W = {a.window}, layer 0 of 2, {torch.cuda.get_device_properties(0).multi_processor_count} CUs, "
+        f"{datetime.date.today().isoformat()} (profiles/tools/{TOOL}, {a.rounds} rounds of {a.reps} calls, routes in turn; ms per call)")
     say("columns: a = attend_spec(window=W) | b = attend_chunk(window=W, splits=0) | c = attend_spec, no window | d = attend(window=W), one position "
         "| a / b (b's spread) | a / c (c's spread) | a / d (d's spread)")
     rows = []
@@ -120,7 +127,7 @@ def main():
     if a.parent_lib:
         # the process that measured above has the GPU open and goes on; every child is a fresh process of its own, one at a time
         runs = {"parent": [], "this tree": []}
-        args = [sys.executable, os.path.abspath(__file__), "--shapes", a.shapes, "--steps", a.steps, "--window", str(a.window), "--reps", str(a.reps),
+        args = [sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), TOOL), "--shapes", a.shapes, "--steps", a.steps, "--window", str(a.window), "--reps", str(a.reps),
                 "--rounds", str(a.rounds)]
         for _ in range(a.alternations):
             for who, library in (("parent", os.path.abspath(a.parent_lib)), ("this tree", "")):
