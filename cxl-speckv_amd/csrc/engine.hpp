@@ -263,11 +263,12 @@ public:
                        uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s,
                        const uint32_t* length = nullptr, const uint32_t* d_depth = nullptr, uint32_t window = 0, bool wide = false);
     // the step of several positions over ONE FP8_E4M3 allocation per sequence on a sliding-window layer (speckv_ext_attend_spec_window;
-    // engine_attend_spec.cpp): one attention launch (k_attend_fp8_spec) with the held rows folded inside it, and its merge
+    // engine_attend_spec.cpp): one attention launch (k_attend_fp8_spec) with the held rows folded inside it, and its merge;
+    // wide: 17..32 query rows per kv head in one pass, window == 0 allowed (speckv_ext_attend_spec_wide; k_attend_fp8_wide)
     int attend_spec_window(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g, uint32_t rows_per_pos,
                            const uint32_t* pos_end, const uint32_t* length, const uint32_t* d_depth, uint32_t window, const void* d_k_held,
                            const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride,
-                           float sm_scale, float* d_out, float* d_lse, hipStream_t s);
+                           float sm_scale, float* d_out, float* d_lse, hipStream_t s, bool wide = false);
     // the split pool's decode step for n_layers consecutive layers in one launch (speckv_ext_attend_kv_layers; engine_attend_kv.cpp): q / out / lse
     // rows [layer][sequence], one descriptor per sequence, the tails of odd lengths folded inside the launch
     int attend_layers_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer_begin, uint32_t n_layers, const void* d_q_f16,

@@ -2,6 +2,8 @@
 // of a batch over an FP8_E4M3 pool on a SLIDING-WINDOW layer, one attention launch (k_attend_fp8_spec, attend_fp8_spec.hip) with the rows
 // held outside the pool folded inside it and, where members have several pieces, the merge behind it.  The FP8 counterpart of
 // Engine::attend_batch_kv's held-and-window path (engine_attend_kv.cpp), with one allocation per sequence in the place of two.
+// wide: the body behind speckv_ext_attend_spec_wide as well -- 17 <= g <= 32 rows in one pass (k_attend_fp8_wide, attend_fp8_wide.hip),
+// on a sliding-window layer or, window == 0, on a global one; the same descriptor staging, a.part_acc / part_ml for 2 x parts partials.
 #include "engine_internal.hpp"
 #include "spec_window.hpp"
 #include "tuning.hpp"
@@ -15,6 +17,8 @@ namespace speckv {
 // ONE form: every member in a single run with a scale table (Allocation::linear_base, d_scale_tab); a striped or migrated placement is
 // refused with SPECKV_ERR_INVAL -- speckv_ext_attend_chunk_window serves any placement.  An allocation of another scheme (INT4_G32, MXFP4)
 // is refused likewise: this entry serves the FP8 pool alone.
+// wide with window == 0: every member is walked over all pos_end / 2 pages from page 0, no rel array is staged (a.seq_skip stays NULL: the
+// kernel's plain instance), and neither length nor d_depth is looked at.
 // The walk is spec_window_range's: the descriptor starts at the tile of depth 0's bound in both regions (begin / 2 pages in: a multiple of
 // 16 records, a kernel tile stays one group of the scale table) whatever depths the call carries; a member no row of which sees a pool
 // position is one with nothing stored.  The launch decision is attend_geometry.hpp's for BatchShape{fp8 = true} over the pages actually
@@ -24,20 +28,26 @@ namespace speckv {
 int Engine::attend_spec_window(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g, uint32_t rows_per_pos,
                                const uint32_t* pos_end, const uint32_t* length, const uint32_t* d_depth, uint32_t window, const void* d_k_held,
                                const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride,
-                               float sm_scale, float* d_out, float* d_lse, hipStream_t s)
+                               float sm_scale, float* d_out, float* d_lse, hipStream_t s, bool wide)
 {
-    const char* entry = "speckv_ext_attend_spec_window";
+    const char* entry = wide ? "speckv_ext_attend_spec_wide" : "speckv_ext_attend_spec_window";
     const auto refuse = [&](const char* why) { SPECKV_ERR("%s: %s", entry, why); return SPECKV_ERR_INVAL; };
-    if (!fold_held_args_ok(8u, g, rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems, d_out, d_lse ? d_lse : d_out))
-        return refuse("g outside 1..16 or no multiple of rows_per_pos, more than SPECKV_HELD_MAX - 1 positions, overlapping held rows, or a NULL query, held row or output");
+    // speckv_ext_attend_spec_wide: 17..32 rows; fewer belong to the 16-row routes, and one row per position would be 17+ positions.  The
+    // rest of the held rows' rule is the folds', judged on the rows of one block
+    if (wide && (g <= 16 || g > 32 || rows_per_pos < 2u || g % rows_per_pos))
+        return refuse("g outside 17..32 or no multiple of rows_per_pos, or rows_per_pos below 2 (16 rows or fewer: speckv_ext_attend_spec_window, or the planned step and the fold launch)");
+    const uint32_t n_pos = rows_per_pos ? g / rows_per_pos : 0u;
+    if (!fold_held_args_ok(8u, wide ? n_pos : g, wide ? 1u : rows_per_pos, d_q_f16, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems, d_out, d_lse ? d_lse : d_out))
+        return refuse(wide ? "more than SPECKV_HELD_MAX - 1 positions, overlapping held rows, or a NULL query, held row or output" :
+                      "g outside 1..16 or no multiple of rows_per_pos, more than SPECKV_HELD_MAX - 1 positions, overlapping held rows, or a NULL query, held row or output");
     if (!d_mask || mask_stride < g / rows_per_pos) return refuse("no mask table, or mask_stride below g / rows_per_pos");
     if (reinterpret_cast<uintptr_t>(d_q_f16) % 16u || reinterpret_cast<uintptr_t>(d_out) % 16u || reinterpret_cast<uintptr_t>(d_k_held) % 16u ||
         reinterpret_cast<uintptr_t>(d_v_held) % 16u)
         return refuse("the query, the output or the held rows are not 16-byte aligned");
-    if (window == 0) return refuse("window is 0 (a global layer: the planned step and the fold launch)");
-    if (!length || !d_depth) return refuse("a NULL length or d_depth");
+    if (window == 0 && !wide) return refuse("window is 0 (a global layer: the planned step and the fold launch)");
+    if (window && (!length || !d_depth)) return refuse("a NULL length or d_depth");
     for (uint32_t i = 0; pos_end && i < n_seq; ++i)
-        if (pos_end[i] % 2u || (length[i] != pos_end[i] && length[i] != pos_end[i] + 1u)) return refuse("an odd pos_end, or a length outside {pos_end, pos_end + 1}");
+        if (pos_end[i] % 2u || (window && length[i] != pos_end[i] && length[i] != pos_end[i] + 1u)) return refuse("an odd pos_end, or a length outside {pos_end, pos_end + 1}");
     if (null_) return no_data_path(entry);
     if (n_seq == 0) return SPECKV_OK;
     if (is_capturing(s)) return refuse("cannot be captured into a HIP graph (its descriptors are staged per call)");
@@ -49,7 +59,7 @@ int Engine::attend_spec_window(uint32_t n_seq, const uint64_t* handles, uint32_t
     for (uint32_t i = 0; i < n_seq; ++i) {
         Allocation* a = find(handles[i]);
         if (!a) return SPECKV_ERR_GENERAL;
-        if (!a->has_layout || a->scheme != SPECKV_COMP_FP8_E4M3) return refuse("an allocation that is no FP8_E4M3 pool with a layout (INT4_G32 and MXFP4 pools: speckv_ext_attend_chunk_window)");
+        if (!a->has_layout || a->scheme != SPECKV_COMP_FP8_E4M3) return refuse("an allocation that is no FP8_E4M3 pool with a layout (INT4_G32 and MXFP4 pools: speckv_ext_attend_chunk_window; on a global layer the planned step and the fold launch)");
         const Layout& L = a->layout;
         // the region rule of the FP8 batch form: 8 x 128 fp16 per position, regions that start on a tile, the layer and pos_end inside the layout
         if (L.head_dim != 128 || L.bytes_per_element != 2 || L.num_heads != 8 || L.num_tokens % 32u || layer >= L.num_layers || pos_end[i] > L.num_tokens ||
@@ -61,7 +71,7 @@ int Engine::attend_spec_window(uint32_t n_seq, const uint64_t* handles, uint32_t
             return SPECKV_ERR_INVAL;
         }
         allocs[i] = a;
-        const SpecWindowRange r = spec_window_range(length[i], window);
+        const SpecWindowRange r = window ? spec_window_range(length[i], window) : SpecWindowRange{0u, 0, pos_end[i] / 2u};
         const uint32_t begin = r.n_pages ? r.begin : 0u;                // (no pool position in any row's window: nothing stored)
         rels[i] = r.n_pages ? static_cast<uint32_t>(r.rel) : 0u;
         AttendSeq& q = seqs[i];
@@ -92,7 +102,8 @@ int Engine::attend_spec_window(uint32_t n_seq, const uint64_t* handles, uint32_t
     bool merge = false;
     for (uint32_t i = 0; i < n_seq; ++i) merge = merge || seqs[i].n_splits > 1u;
     AttendArgs k{};
-    if (!attend_scratch(k, merge ? parts : 1u, 0, s)) return SPECKV_ERR_NOMEM;
+    if (wide && parts > 0xFFFFFFFFull) return refuse("more than 2^32 partials per row block");
+    if (!attend_scratch(k, merge ? parts * (wide ? 2u : 1u) : 1u, 0, s)) return SPECKV_ERR_NOMEM;
     // descriptors, then the dispatch order, then the rel array: one slot, read in place by the kernel (Engine::attend_batch)
     const size_t desc_bytes = n_seq * sizeof(AttendSeq), idx_bytes = n_seq * sizeof(uint32_t);
     int slot = 0;
@@ -112,20 +123,21 @@ int Engine::attend_spec_window(uint32_t n_seq, const uint64_t* handles, uint32_t
     k.lin_base = seqs[0].lin_base;                                       // (overridden per sequence)
     k.seqs = reinterpret_cast<const AttendSeq*>(d_slot);
     if (ordered) k.order = reinterpret_cast<const uint32_t*>(d_slot + desc_bytes);
-    k.seq_skip = reinterpret_cast<const uint32_t*>(d_slot + desc_bytes + idx_bytes);
+    if (window) k.seq_skip = reinterpret_cast<const uint32_t*>(d_slot + desc_bytes + idx_bytes);
     if (geo.rows_first) k.rows_first = 1u;
     k.direct_out = d_out;
     k.direct_lse = d_lse;
     k.direct_per_seq = 1u;                                               // members with one piece or none are final, the merge passes them over
     const AttendHeldArgs held{static_cast<const uint16_t*>(d_k_held), static_cast<const uint16_t*>(d_v_held), seq_stride_elems, pos_stride_elems,
-                              d_mask, mask_stride, rows_per_pos, d_depth};
+                              d_mask, mask_stride, rows_per_pos, window ? d_depth : nullptr};
     // behind the asynchronous pool writes on every other caller stream the engine knows (a commit on another stream)
     for (auto& w : write_evs_)
         if (w.s != st) HIP_TRY(hipStreamWaitEvent(st, w.ev, 0));
     for (uint32_t i = 0; i < n_seq; ++i) note_use(allocs[i], s);         // speckv_free waits for this stream
     // The guard event is recorded on every way out from here on: the slot must not be written again under a kernel still reading it.
     SlotGuard slot_guard{seq_ring_.ev[slot], st};
-    HIP_TRY(launch_attend_fp8_spec(k, held, n_seq, merge, d_out, d_lse, st));
+    if (wide) HIP_TRY(launch_attend_fp8_wide(k, held, n_seq, static_cast<uint32_t>(parts), merge, d_out, d_lse, st));
+    else HIP_TRY(launch_attend_fp8_spec(k, held, n_seq, merge, d_out, d_lse, st));
     if (!s) HIP_TRY(hipStreamSynchronize(stream_));
     return SPECKV_OK;
 }

@@ -827,6 +827,12 @@ hipError_t launch_attend_fp8_spec(const AttendArgs& a, const AttendHeldArgs& h, 
 // one block, what assign_pieces counted) behind block 0's.  h.rows_per_pos >= 2: a step has at most SPECKV_HELD_MAX - 1 positions.
 hipError_t launch_attend_k8v4_wide(const AttendArgs& a, const AttendKvSide* d_vside, const AttendHeldArgs& h, uint32_t n_seq, uint32_t block_parts, bool merge,
                                    float* d_out, float* d_lse, hipStream_t s);
+// launch_attend_fp8_spec with 17 <= a.g <= 32 query rows per kv head in ONE pass over the records (attend_fp8_wide.hip: k_attend_fp8_wide;
+// speckv_ext_attend_spec_wide), window or not: a.seq_skip and h.depth both set (a sliding-window layer, the descriptors from the tile of
+// depth 0's bound) or both NULL (a global layer, the descriptors from page 0).  Two partials per (head, piece) as for
+// launch_attend_k8v4_wide: a.part_acc / part_ml hold 2 x block_parts of them.  h.rows_per_pos >= 2.
+hipError_t launch_attend_fp8_wide(const AttendArgs& a, const AttendHeldArgs& h, uint32_t n_seq, uint32_t block_parts, bool merge, float* d_out, float* d_lse,
+                                  hipStream_t s);
 // The decode step of SEVERAL layers over the split pool in one launch (k_attend_k8v4<false, false, AttendKvLayers>; speckv_ext_attend_kv_layers):
 // the grid carries layer x sequence x head quad, member y = [layer][sequence] is the row block of q / out / lse (a.batch_n_seq = n_seq,
 // a.batch_layer = the first layer).  a.seqs / d_vside hold ONE descriptor per sequence, for region 0 of its allocations: the kernel moves to

@@ -792,8 +792,9 @@ class SpeckvKVConnector(SharedPrefixSteps):
         """How a step of S new positions with rows_per_pos query rows per kv head and position goes through the attention kernels,
         which take at most 16 query rows per kv head in one pass over the records: [(first position, positions)] -- groups of
         16 // rows_per_pos positions, the last one possibly shorter.  One group = one pass; every further group reads the records again.
-        rows_per_pass = 32 (SpeckvSplitKVConnector.attend_spec only; this connector's kernels take 16): groups of 32 // rows_per_pos
-        positions, for the split pool's kernel that carries two blocks of 16 rows through one pass."""
+        rows_per_pass = 32 (opt-in: SpeckvSplitKVConnector.attend_spec, and this connector's attend_spec on an FP8 pool): groups of
+        32 // rows_per_pos positions, for the kernels that carry two blocks of 16 rows through one pass (k_attend_k8v4_wide,
+        k_attend_fp8_wide); a trailing group of 16 rows or fewer takes the 16-row route."""
         if rows_per_pass not in (16, 32):
             raise ValueError("rows_per_pass must be 16 or 32 (query rows per kv head in one pass over the records)")
         if not 1 <= rows_per_pos <= 16:
@@ -933,7 +934,8 @@ class SpeckvKVConnector(SharedPrefixSteps):
             held.append(flat.index_select(1, self._spec_idx))
         return held[0], held[1], self._spec_base
 
-    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None, window=None):
+    def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None, window=None,
+                    rows_per_pass=16):
         """One layer of a step that carries S new positions per request -- draft tokens to verify, a chunk of a prompt: query position
         j of a request sees everything the request holds (pool and odd last position) and the new positions 0..j.
         q [batch][S][heads][rows_per_pos][dim] fp16; k_new / v_new [batch][S][layers][heads][dim] fp16, the positions that would follow
@@ -957,15 +959,27 @@ class SpeckvKVConnector(SharedPrefixSteps):
         Against attend_chunk(window=W) with the same step, until now the only route on a local layer (profiles/fp8_spec_window.txt;
         W = 1024, 16 query rows per kv head): 0.46-0.49 of its time at 256 requests x 2k and at 256 x 8k stored positions; at 8 x 32k it is
         SLOWER, 1.05-1.10 of the chunk route's time -- the crossover lies at few requests, where attend_chunk(window=W) /
-        attend_tree(window=W) is the route to take.  0.28-0.82 of an unwindowed attend_spec, 1.75-1.94 single attend(window=W) steps."""
-        return self.attend_spec_layers(layer, 1, req_ids, q[None], k_new, v_new, sm_scale, n_new, stream, parents, window)[0]
+        attend_tree(window=W) is the route to take.  0.28-0.82 of an unwindowed attend_spec, 1.75-1.94 single attend(window=W) steps.
+        rows_per_pass (16: exactly the calls above and their bits, the default; 32: opt-in, FP8 pools whose requests lie in a single run
+        each -- a striped or migrated placement is refused by the library, an INT4 or MXFP4 pool is a ValueError: rows_per_pass=16
+        serves both): the groups are spec_groups(S, rows_per_pos, 32).  A group of 17..32 query rows per kv head is ONE
+        speckv_ext_attend_spec_wide call per layer (k_attend_fp8_wide: two blocks of 16 rows share each tile's K bytes, V operand and
+        reference scale; the held rows folded inside it), with window=W or, on a global layer, without -- no plan and no fold launch;
+        a trailing group of 16 rows or fewer takes the 16-row route of its layer kind (under a window speckv_ext_attend_spec_window; on
+        a global layer the planned call and speckv_ext_attend_fold_masked, a chain being the tree parents[j] = j - 1).  Per row the
+        values are the 16-row kernel's.  Changes no state.  Measured against rows_per_pass=16 (profiles/fp8_spec_wide.txt; 32 rows per
+        kv head as (4, 8), (8, 4), (16, 2)): on a global layer 0.59-0.68 of its time at 256 requests x 2k stored positions, 0.54-0.55 at
+        256 x 8k, 0.72-0.74 at 8 x 32k; under W = 1024 0.68-0.69, 0.68-0.71 and 0.78-0.80 -- faster beyond both spreads at every shape
+        measured, level or slower at none; 1.17-2.24 plain attend steps.  16 stays the default."""
+        return self.attend_spec_layers(layer, 1, req_ids, q[None], k_new, v_new, sm_scale, n_new, stream, parents, window, rows_per_pass)[0]
 
     def attend_spec_layers(self, layer_begin: int, n_layers: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None,
-                           stream=None, parents=None, window=None):
+                           stream=None, parents=None, window=None, rows_per_pass=16):
         """attend_spec for n_layers consecutive layers whose query rows exist at once: q [n_layers][batch][S][heads][rows_per_pos][dim],
         returns the same shape in fp32.  Per group of positions one speckv_ext_attend_planned_layers call and one fold launch over all
         the layers.  window=W >= 1 (the layers are sliding-window layers of one window; FP8 pools): per group and layer ONE
-        speckv_ext_attend_spec_window call, see attend_spec."""
+        speckv_ext_attend_spec_window call, see attend_spec.  rows_per_pass=32 (FP8 pools): per group of 17..32 rows and layer ONE
+        speckv_ext_attend_spec_wide call, window or not, see attend_spec."""
         import torch
         if self.scheme not in FUSED:
             raise ValueError("attend_spec() needs an FP8, INT4 or MXFP4 pool")
@@ -975,7 +989,9 @@ class SpeckvKVConnector(SharedPrefixSteps):
         NL, B, S, H, R, D = q.shape
         if NL != n_layers or tuple(k_new.shape) != (B, S, self.L, H, D) or tuple(v_new.shape) != (B, S, self.L, H, D):
             raise ValueError("q must be [n_layers][batch][S][heads][rows_per_pos][dim], k_new / v_new [batch][S][layers][heads][dim]")
-        groups = self.spec_groups(S, R)
+        groups = self.spec_groups(S, R, rows_per_pass)
+        if rows_per_pass == 32 and self.scheme != SCHEMES["fp8"]:
+            raise ValueError("attend_spec(rows_per_pass=32) serves FP8 pools; an INT4 or MXFP4 pool takes rows_per_pass=16")
         if n_new is not None:
             n_new = [int(n) for n in n_new]
             if len(n_new) != B or not all(0 <= n <= S for n in n_new):
@@ -985,7 +1001,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
             q = q * self._kscale[layer_begin:layer_begin + n_layers][:, None, None, :, None, :]
             k_new = k_new * self._kscale_inv[None, None]
         out = torch.empty((NL, B, S, H, R, D), dtype=torch.float32, device="cuda")
-        if W:
+        if W or rows_per_pass == 32:
             return out if B == 0 else self._spec_window_layers(layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out)
         akey = (key, self._epoch)
         with self._On(self, stream) as st:
@@ -998,15 +1014,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
                 masks = None if parents is None else self._tree_table(key, reqs, parents, n_new, NL, S)
                 for j0, n in groups:
                     g = n * R
-                    qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
-                    og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
-                    lse = torch.empty((NL, B, H, g), dtype=torch.float32, device="cuda")
-                    if NL == 1:
-                        self.lib.attend_planned(self.scheme, self._plan.data_ptr(), B, layer_begin, qg.data_ptr(), g, self._plan_bound, sm_scale,
-                                                og.data_ptr(), lse.data_ptr(), st.cuda_stream)
-                    else:
-                        self.lib.attend_planned_layers(self.scheme, self._plan.data_ptr(), B, layer_begin, NL, qg.data_ptr(), g, self._plan_bound,
-                                                       sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
+                    qg, og, lse = self._spec_planned_group(layer_begin, q, j0, n, sm_scale, st)
                     if masks is not None:
                         self.lib.attend_fold_masked(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
                                                     masks.data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
@@ -1020,10 +1028,29 @@ class SpeckvKVConnector(SharedPrefixSteps):
                     out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
         return out
 
+    def _spec_planned_group(self, layer_begin, q, j0, n, sm_scale, st):
+        """The planned decode call of a global layer's group of n positions from j0 (<= 16 query rows per kv head) over the stored
+        positions, in front of its fold launch: (query rows [n_layers][batch][heads][g][dim], out, lse)."""
+        import torch
+        NL, B, S, H, R, D = q.shape
+        g = n * R
+        qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
+        og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
+        lse = torch.empty((NL, B, H, g), dtype=torch.float32, device="cuda")
+        if NL == 1:
+            self.lib.attend_planned(self.scheme, self._plan.data_ptr(), B, layer_begin, qg.data_ptr(), g, self._plan_bound, sm_scale,
+                                    og.data_ptr(), lse.data_ptr(), st.cuda_stream)
+        else:
+            self.lib.attend_planned_layers(self.scheme, self._plan.data_ptr(), B, layer_begin, NL, qg.data_ptr(), g, self._plan_bound,
+                                           sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
+        return qg, og, lse
+
     def _spec_window_layers(self, layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out):
-        """attend_spec_layers(window=W) on an FP8 pool: per group and layer one speckv_ext_attend_spec_window.  The mask words
-        (tree_masks(window=W); a chain is the tree parents[j] = j - 1), the depths, pos_end and the lengths are made once per
-        (batch, epoch, S, tree, live counts, W); the held rows are _held_rows'."""
+        """attend_spec_layers(window=W) and attend_spec_layers(rows_per_pass=32) on an FP8 pool, W = 0: a global layer.  Per layer, a
+        group of 17..32 rows is one speckv_ext_attend_spec_wide; one of 16 rows or fewer is one speckv_ext_attend_spec_window under a
+        window and, on a global layer (a trailing group of a wide step), the planned call and one speckv_ext_attend_fold_masked over
+        all the layers.  The mask words (tree_masks(window=W or None); a chain is the tree parents[j] = j - 1), the depths, pos_end and
+        the lengths are made once per (batch, epoch, S, tree, live counts, W); the held rows are _held_rows'."""
         import numpy as np
         import torch
         NL, B, S, H, R, D = q.shape
@@ -1034,7 +1061,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
             trees = self._tree_parents(tree, B)
             if len(trees[0]) != S:
                 raise ValueError("parents: one entry per new position")
-            words = self.tree_masks(trees, [r.length & 1 for r in reqs], n_new, window=W)
+            words = self.tree_masks(trees, [r.length & 1 for r in reqs], n_new, window=W or None)
             depths = self.chunk_tree_depths(trees, B)
             self._spec_window = (wkey, _device_index([w for row in words for w in row]), _device_index([d for row in depths for d in row]),
                                  np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32), np.asarray([r.length for r in reqs], dtype=np.uint32))
@@ -1045,12 +1072,22 @@ class SpeckvKVConnector(SharedPrefixSteps):
                 kh, vh, _ = self._held_rows(req_ids, key, reqs, k_new, v_new, layer_begin, NL, st)      # [n_layers][batch][1 + S][heads][dim]
                 for j0, n in groups:
                     g = n * R
-                    qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
-                    og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
-                    for l in range(NL):
-                        self.lib.attend_spec_window(handles, layer_begin + l, qg[l].data_ptr(), g, R, pos_end, lengths, depths.data_ptr() + 4 * j0, W,
-                                                    kh[l].data_ptr(), vh[l].data_ptr(), (1 + S) * H * D, H * D, masks.data_ptr() + 4 * j0, S, sm_scale,
-                                                    og[l].data_ptr(), 0, st.cuda_stream)
+                    if g <= 16 and not W:                                # the trailing group of a wide step on a global layer
+                        if self._arg_key != ((key, self._epoch), st.cuda_stream):
+                            self.plan_step(req_ids, st)
+                        self._plan_stream = st
+                        qg, og, lse = self._spec_planned_group(layer_begin, q, j0, n, sm_scale, st)
+                        self.lib.attend_fold_masked(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
+                                                    self._tree_table(key, reqs, tree, n_new, NL, S).data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(),
+                                                    lse.data_ptr(), st.cuda_stream)
+                    else:
+                        qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
+                        og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
+                        step = self.lib.attend_spec_wide if g > 16 else self.lib.attend_spec_window
+                        for l in range(NL):
+                            step(handles, layer_begin + l, qg[l].data_ptr(), g, R, pos_end, lengths, depths.data_ptr() + 4 * j0, W,
+                                 kh[l].data_ptr(), vh[l].data_ptr(), (1 + S) * H * D, H * D, masks.data_ptr() + 4 * j0, S, sm_scale,
+                                 og[l].data_ptr(), 0, st.cuda_stream)
                     out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
         return out
 

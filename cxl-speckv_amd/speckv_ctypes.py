@@ -167,6 +167,8 @@ _EXT_SIGNATURES = {
                                        c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_spec_window": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32,
                                       c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_spec_wide": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32,
+                                    c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_spec_window_range": [c_uint32, c_uint32, _u32p, ctypes.POINTER(ctypes.c_int32), _u32p],
     "speckv_ext_attend_fold_held": [c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
                                     ctypes.c_float, c_void_p, c_void_p, c_void_p],
@@ -808,6 +810,18 @@ class SpeckvLib:
         n = len(pos_end if handles is None else handles)
         u32 = lambda a: None if a is None else as_arr(a, c_uint32, n)
         self._ext("speckv_ext_attend_spec_window", n, None if handles is None else as_arr(handles, c_uint64, n), layer, c_void_p(d_q_f16), g, rows_per_pos,
+                  u32(pos_end), u32(length), c_void_p(d_depth or 0), window, c_void_p(d_k_held or 0), c_void_p(d_v_held or 0), seq_stride_elems,
+                  pos_stride_elems, c_void_p(d_mask or 0), mask_stride, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
+
+    def attend_spec_wide(self, handles, layer, d_q_f16, g, rows_per_pos, pos_end, length, d_depth, window, d_k_held, d_v_held, seq_stride_elems,
+                         pos_stride_elems, d_mask, mask_stride, sm_scale, d_out, d_lse=None, stream=None):
+        """The multi-position step of a batch over an FP8_E4M3 pool with 17 <= g <= 32 query rows per kv head in ONE pass over the records
+        (speckv_ext_attend_spec_wide: two blocks of 16 rows per wave share each tile's K bytes, V operand and reference scale).  The
+        arguments of attend_spec_window; window = 0: a global layer, length and d_depth are not read.  g <= 16 and rows_per_pos = 1 are
+        refused: those steps belong to the 16-row routes.  Arrays as attend_kv_batch; 0 / None stands for a NULL pointer."""
+        n = len(pos_end if handles is None else handles)
+        u32 = lambda a: None if a is None else as_arr(a, c_uint32, n)
+        self._ext("speckv_ext_attend_spec_wide", n, None if handles is None else as_arr(handles, c_uint64, n), layer, c_void_p(d_q_f16), g, rows_per_pos,
                   u32(pos_end), u32(length), c_void_p(d_depth or 0), window, c_void_p(d_k_held or 0), c_void_p(d_v_held or 0), seq_stride_elems,
                   pos_stride_elems, c_void_p(d_mask or 0), mask_stride, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
 

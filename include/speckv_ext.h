@@ -1526,6 +1526,32 @@ speckv_status_t speckv_ext_attend_spec_window(uint32_t n_seq, const speckv_handl
                                               uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale,
                                               float* d_out, float* d_lse /* optional */, void* stream);
 
+/* speckv_ext_attend_spec_wide: the multi-position step over an FP8_E4M3 pool with 17 <= g <= 32 query rows per kv head in ONE pass over
+ * the records -- at 8 query heads per kv head, 3 or 4 draft positions (rows_per_pos = 8), up to 8 (rows_per_pos = 4) or up to 16
+ * (rows_per_pos = 2), which the 16-row routes take as two groups, each walking every stored record again: on a sliding-window layer two
+ * speckv_ext_attend_spec_window calls, on a global layer two planned calls each followed by its fold launch.  The argument list of
+ * speckv_ext_attend_spec_window, every argument with its meaning there, except window: window == 0 is a GLOBAL layer, every member
+ * walked over all pos_end[i] / 2 pages from page 0 -- length and d_depth may then be NULL and are not looked at; window >= 1 is exactly
+ * that entry's walk (speckv_ext_spec_window_range).  An additive entry: SPECKV_EXT_ABI_VERSION stays what it is, and
+ * speckv_ext_attend_spec_window keeps refusing g > 16 and window == 0.
+ * The kernel (k_attend_fp8_wide) carries two blocks of 16 query rows per wave, rows 0..15 and 16..31 of the group: each tile's K bytes,
+ * page scales, V bytes, f16 V operand and V reference scale are fetched, built and elected once and meet both blocks' query operands and
+ * weights.  Values per row are those of speckv_ext_attend_spec_window, bit for bit over the same pieces: the row's own E4M3 query scale,
+ * its own softmax, its own mask word (query position r / rows_per_pos) and, under a window, its own depth; a held position is loaded once
+ * and scored against both blocks' fp16 rows.  The launch decision (pieces, dispatch order: speckv_ext_attend_fp8_batch's rule over the
+ * pages walked), addressing, placement (single runs only), stream rules, ordering behind pool writes and statuses are those of
+ * speckv_ext_attend_spec_window.  NOT capturable into a HIP graph.
+ * SPECKV_ERR_INVAL, judged before anything else and on every engine: g <= 16 (such a step belongs to the 16-row routes), g > 32,
+ * rows_per_pos < 2 (17 or more positions: beyond SPECKV_HELD_MAX - 1 and the mask word), g not a multiple of rows_per_pos; then what
+ * speckv_ext_attend_spec_window refuses, in its order, with "a NULL length or d_depth" and the rule on length[i] applying to window >= 1
+ * alone.  An INT4_G32 or MXFP4 pool, a striped or migrated placement: SPECKV_ERR_INVAL, the message names the route that serves them.
+ * Nothing is launched, d_out is untouched.  Whether one wide call beats the 16-row route depends on the shape: profiles/fp8_spec_wide.txt. */
+speckv_status_t speckv_ext_attend_spec_wide(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g,
+                                            uint32_t rows_per_pos, const uint32_t* pos_end, const uint32_t* length, const uint32_t* d_depth,
+                                            uint32_t window, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems,
+                                            uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale,
+                                            float* d_out, float* d_lse /* optional */, void* stream);
+
 /* The walk rule of speckv_ext_attend_kv_spec_window as a pure function (works without speckv_init, needs no device): for a member of
  * `length` committed positions under window W >= 1, *out_begin = the first position walked (a multiple of 32), *out_n_pages = the pages
  * walked from there (0: no row sees a stored position), *out_rel = length + 1 - W - begin, signed -- a row of depth d does not see the
