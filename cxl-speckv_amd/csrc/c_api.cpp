@@ -713,6 +713,18 @@ speckv_status_t speckv_ext_attend_spec_wide(uint32_t n_seq, const speckv_handle_
     });
 }
 
+speckv_status_t speckv_ext_attend_spec_mx4(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g,
+                                           uint32_t rows_per_pos, const uint32_t* pos_end, const void* d_k_held, const void* d_v_held,
+                                           uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride,
+                                           float sm_scale, float* d_out, float* d_lse, void* stream)
+{
+    LOCK; NEED_INIT;
+    return guarded([&] {
+        return g_engine->attend_spec_mx4(n_seq, handles, layer, d_q_f16, g, rows_per_pos, pos_end, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems,
+                                         d_mask, mask_stride, sm_scale, d_out, d_lse, static_cast<hipStream_t>(stream));
+    });
+}
+
 speckv_status_t speckv_ext_attend_kv_layers(uint32_t n_seq, const speckv_handle_t* k_handles, const speckv_handle_t* v_handles, uint32_t layer_begin,
                                             uint32_t n_layers, const void* d_q_f16, uint32_t g, const uint32_t* pos_end, uint32_t n_tail,
                                             const int32_t* d_tail_idx, const void* d_k_tail, const void* d_v_tail, uint64_t tail_stride_elems,

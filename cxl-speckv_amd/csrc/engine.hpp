@@ -269,6 +269,11 @@ public:
                            const uint32_t* pos_end, const uint32_t* length, const uint32_t* d_depth, uint32_t window, const void* d_k_held,
                            const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride,
                            float sm_scale, float* d_out, float* d_lse, hipStream_t s, bool wide = false);
+    // the step of several positions over ONE MXFP4 allocation per sequence on a global layer (speckv_ext_attend_spec_mx4; engine_attend_spec.cpp):
+    // one attention launch (k_attend_mx4_spec: 16 query rows per kv head in one pass) with the held rows folded inside it, and its merge
+    int attend_spec_mx4(uint32_t n_seq, const uint64_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g, uint32_t rows_per_pos,
+                        const uint32_t* pos_end, const void* d_k_held, const void* d_v_held, uint64_t seq_stride_elems, uint64_t pos_stride_elems,
+                        const uint32_t* d_mask, uint32_t mask_stride, float sm_scale, float* d_out, float* d_lse, hipStream_t s);
     // the split pool's decode step for n_layers consecutive layers in one launch (speckv_ext_attend_kv_layers; engine_attend_kv.cpp): q / out / lse
     // rows [layer][sequence], one descriptor per sequence, the tails of odd lengths folded inside the launch
     int attend_layers_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer_begin, uint32_t n_layers, const void* d_q_f16,
@@ -497,6 +502,8 @@ private:
     static bool fold_held_args_ok(uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16, const void* d_k_held, const void* d_v_held,
                                   uint64_t seq_stride_elems, uint64_t pos_stride_elems, const float* d_out, const float* d_lse);
     template <class Launch> int launch_on(hipStream_t s, Launch launch);
+    struct SpecStep;                                      // the members of a draft step over one allocation per sequence (engine_attend_spec.cpp)
+    int spec_step_launch(SpecStep& m, hipStream_t s);     // ... and what attend_spec_window and attend_spec_mx4 do once its descriptors stand
     int take_seq_slot(size_t bytes, int* slot, void** staged);
     int ensure_zero_page(hipStream_t s);
     uint8_t* attend_scratch(AttendArgs& k, uint64_t parts, size_t head_bytes, hipStream_t s);

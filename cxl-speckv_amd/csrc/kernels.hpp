@@ -833,6 +833,12 @@ hipError_t launch_attend_k8v4_wide(const AttendArgs& a, const AttendKvSide* d_vs
 // launch_attend_k8v4_wide: a.part_acc / part_ml hold 2 x block_parts of them.  h.rows_per_pos >= 2.
 hipError_t launch_attend_fp8_wide(const AttendArgs& a, const AttendHeldArgs& h, uint32_t n_seq, uint32_t block_parts, bool merge, float* d_out, float* d_lse,
                                   hipStream_t s);
+// The step of several positions over ONE MXFP4 allocation per sequence, records in one run (attend_mx4_spec.hip: k_attend_mx4_spec;
+// speckv_ext_attend_spec_mx4): a.seqs as for launch_attend_mx4 in the linear batch form with k_first / v_first multiples of 16 (layouts
+// with num_tokens % 32 == 0), a.g <= 16 query rows per kv head as the MFMA columns -- the records are fetched once --, the held rows folded
+// in by split 0.  a.direct_out == d_out: members with one piece or none are written final by the kernel; merge: some member has several --
+// launch_attend_combine follows.  No window (a.seq_skip and h.depth are not read).
+hipError_t launch_attend_mx4_spec(const AttendArgs& a, const AttendHeldArgs& h, uint32_t n_seq, bool merge, float* d_out, float* d_lse, hipStream_t s);
 // The decode step of SEVERAL layers over the split pool in one launch (k_attend_k8v4<false, false, AttendKvLayers>; speckv_ext_attend_kv_layers):
 // the grid carries layer x sequence x head quad, member y = [layer][sequence] is the row block of q / out / lse (a.batch_n_seq = n_seq,
 // a.batch_layer = the first layer).  a.seqs / d_vside hold ONE descriptor per sequence, for region 0 of its allocations: the kernel moves to

@@ -935,7 +935,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
         return held[0], held[1], self._spec_base
 
     def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None, window=None,
-                    rows_per_pass=16):
+                    rows_per_pass=16, row_block=None):
         """One layer of a step that carries S new positions per request -- draft tokens to verify, a chunk of a prompt: query position
         j of a request sees everything the request holds (pool and odd last position) and the new positions 0..j.
         q [batch][S][heads][rows_per_pos][dim] fp16; k_new / v_new [batch][S][layers][heads][dim] fp16, the positions that would follow
@@ -970,16 +970,29 @@ class SpeckvKVConnector(SharedPrefixSteps):
         values are the 16-row kernel's.  Changes no state.  Measured against rows_per_pass=16 (profiles/fp8_spec_wide.txt; 32 rows per
         kv head as (4, 8), (8, 4), (16, 2)): on a global layer 0.59-0.68 of its time at 256 requests x 2k stored positions, 0.54-0.55 at
         256 x 8k, 0.72-0.74 at 8 x 32k; under W = 1024 0.68-0.69, 0.68-0.71 and 0.78-0.80 -- faster beyond both spreads at every shape
-        measured, level or slower at none; 1.17-2.24 plain attend steps.  16 stays the default."""
-        return self.attend_spec_layers(layer, 1, req_ids, q[None], k_new, v_new, sm_scale, n_new, stream, parents, window, rows_per_pass)[0]
+        measured, level or slower at none; 1.17-2.24 plain attend steps.  16 stays the default.
+        row_block (None: exactly the calls above and their bits for every scheme, the default; 16: opt-in, MXFP4 pools whose requests
+        lie in a single run each -- a striped or migrated placement is refused by the library; an FP8 or INT4 pool, and any other value,
+        is a ValueError: the row block of 16 is the MXFP4 kernel family's): on an MXFP4 pool the planned route above takes query rows in
+        blocks of 8 per kv head, so a group of 9..16 rows walks every record twice and a fold launch follows.  With row_block=16 every
+        group of spec_groups(S, rows_per_pos, 16) and every layer is ONE speckv_ext_attend_spec_mx4 call (k_attend_mx4_spec: the 16
+        columns of the matrix instructions are the 16 query rows, the records are fetched once, the held rows folded inside the launch)
+        -- no plan and no fold launch; the mask words are tree_masks' (a chain is the tree parents[j] = j - 1), n_new and parents work as
+        above, the held rows are the same.  A dead node's rows are the stored positions alone, finite.  window=W and rows_per_pass=32
+        stay the ValueErrors they are on an MXFP4 pool.  Changes no state.  Measured against row_block=None (profiles/mx4_spec.txt; 16 rows
+        per kv head as (4, 4), (2, 8), (16, 1)): one layer 0.70-0.77 of its time at 256 requests x 2k stored positions, 0.59-0.61 at
+        256 x 8k, 0.81-0.89 at 8 x 32k; all 8 layers through attend_spec_layers 0.60-0.62, 0.54-0.55 and 0.66-0.82 -- faster beyond both
+        spreads at every shape measured, level or slower at none; 1.16-1.96 plain attend steps, 2.09 at (16, 1) x 256 x 2k x 8 layers."""
+        return self.attend_spec_layers(layer, 1, req_ids, q[None], k_new, v_new, sm_scale, n_new, stream, parents, window, rows_per_pass, row_block)[0]
 
     def attend_spec_layers(self, layer_begin: int, n_layers: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None,
-                           stream=None, parents=None, window=None, rows_per_pass=16):
+                           stream=None, parents=None, window=None, rows_per_pass=16, row_block=None):
         """attend_spec for n_layers consecutive layers whose query rows exist at once: q [n_layers][batch][S][heads][rows_per_pos][dim],
         returns the same shape in fp32.  Per group of positions one speckv_ext_attend_planned_layers call and one fold launch over all
         the layers.  window=W >= 1 (the layers are sliding-window layers of one window; FP8 pools): per group and layer ONE
         speckv_ext_attend_spec_window call, see attend_spec.  rows_per_pass=32 (FP8 pools): per group of 17..32 rows and layer ONE
-        speckv_ext_attend_spec_wide call, window or not, see attend_spec."""
+        speckv_ext_attend_spec_wide call, window or not, see attend_spec.  row_block=16 (MXFP4 pools): per group and layer ONE
+        speckv_ext_attend_spec_mx4 call, see attend_spec."""
         import torch
         if self.scheme not in FUSED:
             raise ValueError("attend_spec() needs an FP8, INT4 or MXFP4 pool")
@@ -992,6 +1005,8 @@ class SpeckvKVConnector(SharedPrefixSteps):
         groups = self.spec_groups(S, R, rows_per_pass)
         if rows_per_pass == 32 and self.scheme != SCHEMES["fp8"]:
             raise ValueError("attend_spec(rows_per_pass=32) serves FP8 pools; an INT4 or MXFP4 pool takes rows_per_pass=16")
+        if row_block is not None and (row_block != 16 or self.scheme != SCHEMES["mxfp4"]):
+            raise ValueError("attend_spec(row_block=...) must be None or 16, and 16 serves MXFP4 pools alone (an FP8 pool: rows_per_pass=32)")
         if n_new is not None:
             n_new = [int(n) for n in n_new]
             if len(n_new) != B or not all(0 <= n <= S for n in n_new):
@@ -1001,8 +1016,9 @@ class SpeckvKVConnector(SharedPrefixSteps):
             q = q * self._kscale[layer_begin:layer_begin + n_layers][:, None, None, :, None, :]
             k_new = k_new * self._kscale_inv[None, None]
         out = torch.empty((NL, B, S, H, R, D), dtype=torch.float32, device="cuda")
-        if W or rows_per_pass == 32:
-            return out if B == 0 else self._spec_window_layers(layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out)
+        if W or rows_per_pass == 32 or row_block:
+            return out if B == 0 else self._spec_window_layers(layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out,
+                                                               mx4=bool(row_block))
         akey = (key, self._epoch)
         with self._On(self, stream) as st:
             if self._arg_key != (akey, st.cuda_stream):
@@ -1045,12 +1061,14 @@ class SpeckvKVConnector(SharedPrefixSteps):
                                            sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
         return qg, og, lse
 
-    def _spec_window_layers(self, layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out):
+    def _spec_window_layers(self, layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out, mx4=False):
         """attend_spec_layers(window=W) and attend_spec_layers(rows_per_pass=32) on an FP8 pool, W = 0: a global layer.  Per layer, a
         group of 17..32 rows is one speckv_ext_attend_spec_wide; one of 16 rows or fewer is one speckv_ext_attend_spec_window under a
         window and, on a global layer (a trailing group of a wide step), the planned call and one speckv_ext_attend_fold_masked over
         all the layers.  The mask words (tree_masks(window=W or None); a chain is the tree parents[j] = j - 1), the depths, pos_end and
-        the lengths are made once per (batch, epoch, S, tree, live counts, W); the held rows are _held_rows'."""
+        the lengths are made once per (batch, epoch, S, tree, live counts, W); the held rows are _held_rows'.
+        mx4: attend_spec_layers(row_block=16) on an MXFP4 pool (W = 0) -- every group and layer is one speckv_ext_attend_spec_mx4 over
+        the same words, pos_end and held rows."""
         import numpy as np
         import torch
         NL, B, S, H, R, D = q.shape
@@ -1072,7 +1090,13 @@ class SpeckvKVConnector(SharedPrefixSteps):
                 kh, vh, _ = self._held_rows(req_ids, key, reqs, k_new, v_new, layer_begin, NL, st)      # [n_layers][batch][1 + S][heads][dim]
                 for j0, n in groups:
                     g = n * R
-                    if g <= 16 and not W:                                # the trailing group of a wide step on a global layer
+                    if mx4:
+                        qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
+                        og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
+                        for l in range(NL):
+                            self.lib.attend_spec_mx4(handles, layer_begin + l, qg[l].data_ptr(), g, R, pos_end, kh[l].data_ptr(), vh[l].data_ptr(),
+                                                     (1 + S) * H * D, H * D, masks.data_ptr() + 4 * j0, S, sm_scale, og[l].data_ptr(), 0, st.cuda_stream)
+                    elif g <= 16 and not W:                              # the trailing group of a wide step on a global layer
                         if self._arg_key != ((key, self._epoch), st.cuda_stream):
                             self.plan_step(req_ids, st)
                         self._plan_stream = st

@@ -169,6 +169,8 @@ _EXT_SIGNATURES = {
                                       c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_attend_spec_wide": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32,
                                     c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
+    "speckv_ext_attend_spec_mx4": [c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64,
+                                   c_void_p, c_uint32, ctypes.c_float, c_void_p, c_void_p, c_void_p],
     "speckv_ext_spec_window_range": [c_uint32, c_uint32, _u32p, ctypes.POINTER(ctypes.c_int32), _u32p],
     "speckv_ext_attend_fold_held": [c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
                                     ctypes.c_float, c_void_p, c_void_p, c_void_p],
@@ -823,6 +825,17 @@ class SpeckvLib:
         u32 = lambda a: None if a is None else as_arr(a, c_uint32, n)
         self._ext("speckv_ext_attend_spec_wide", n, None if handles is None else as_arr(handles, c_uint64, n), layer, c_void_p(d_q_f16), g, rows_per_pos,
                   u32(pos_end), u32(length), c_void_p(d_depth or 0), window, c_void_p(d_k_held or 0), c_void_p(d_v_held or 0), seq_stride_elems,
+                  pos_stride_elems, c_void_p(d_mask or 0), mask_stride, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
+
+    def attend_spec_mx4(self, handles, layer, d_q_f16, g, rows_per_pos, pos_end, d_k_held, d_v_held, seq_stride_elems, pos_stride_elems, d_mask,
+                        mask_stride, sm_scale, d_out, d_lse=None, stream=None):
+        """The multi-position step of a batch over an MXFP4 pool on a global layer (speckv_ext_attend_spec_mx4): the arguments of
+        attend_kv_spec with ONE handle array -- g = n_q x rows_per_pos <= 16 query rows per kv head in one pass over the records
+        (k_attend_mx4_spec: the 16 MFMA columns are the rows), the held rows folded in inside the same launch.  Requests in single runs
+        only.  Arrays as attend_kv_batch; 0 / None stands for a NULL pointer (for the library to refuse)."""
+        n = len(pos_end if handles is None else handles)
+        self._ext("speckv_ext_attend_spec_mx4", n, None if handles is None else as_arr(handles, c_uint64, n), layer, c_void_p(d_q_f16), g, rows_per_pos,
+                  None if pos_end is None else as_arr(pos_end, c_uint32, n), c_void_p(d_k_held or 0), c_void_p(d_v_held or 0), seq_stride_elems,
                   pos_stride_elems, c_void_p(d_mask or 0), mask_stride, ctypes.c_float(sm_scale), c_void_p(d_out), c_void_p(d_lse or 0), c_void_p(stream or 0))
 
     def attend_kv_spec_wide(self, k_handles, v_handles, layer, d_q_f16, g, rows_per_pos, pos_end, length, d_depth, window, d_k_held, d_v_held,

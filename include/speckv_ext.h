@@ -1552,6 +1552,35 @@ speckv_status_t speckv_ext_attend_spec_wide(uint32_t n_seq, const speckv_handle_
                                             uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride, float sm_scale,
                                             float* d_out, float* d_lse /* optional */, void* stream);
 
+/* speckv_ext_attend_spec_mx4: the MULTI-POSITION STEP of a batch over an MXFP4 pool on a global layer -- verifying draft positions, a short
+ * prompt chunk -- in ONE attention launch and one pass over the records for up to 16 query rows per kv head.  Until now such a step went
+ * through speckv_ext_attend_mx4_planned, whose kernel takes query rows in blocks of 8: 16 rows walked every record twice, and a fold launch
+ * (speckv_ext_attend_fold_held / _masked) followed.  Sequence i is the MXFP4 allocation handles[i] (8 kv heads x 128 fp16, num_tokens % 32
+ * == 0) with pos_end[i] stored positions (even) of layer `layer`; every row sees all of them.  d_q_f16 [n_seq][8][g][128] fp16, g = n_q x
+ * rows_per_pos <= 16, row r belongs to query position r / rows_per_pos; d_out [n_seq][8][g][128] fp32, d_lse [n_seq][8][g] (optional).
+ * The held rows are those of speckv_ext_attend_kv_spec, argument for argument: held position t of sequence i, kv head h, is fp16 at
+ * i * seq_stride_elems + t * pos_stride_elems + h * 128 elements of d_k_held / d_v_held (both strides multiples of 8, rows not overlapping);
+ * query position j of sequence i sees the held positions whose bit is set in d_mask[i * mask_stride + j] (bits >= SPECKV_HELD_MAX are
+ * dropped; mask_stride >= n_q), and no held position above the highest bit set in any word of a sequence is read.  The stored scores take
+ * the query quantised to MXFP8 per 16 channels exactly as speckv_ext_attend_mx4 quantises it; the held scores take the fp16 query.  A row
+ * that sees nothing, stored or held, is exactly 0 with lse -inf.
+ * The kernel (k_attend_mx4_spec) keeps speckv_ext_attend_mx4_batch's workgroup and LDS-DMA pipeline; the 16 columns of its matrix
+ * instructions are the 16 query rows.  The launch decision (pieces, dispatch order) is speckv_ext_attend_mx4_batch's rule, tuning keys
+ * attend_tiles_per_split and attend_order_as_given included; members in several pieces are merged by a second launch on the same stream.
+ * Stream rules, ordering behind pool writes and speckv_free are those of speckv_ext_attend_spec_window.  NOT capturable into a HIP graph:
+ * the descriptors are staged per call.  An additive entry: SPECKV_EXT_ABI_VERSION stays what it is, and speckv_ext_attend_spec_window and
+ * speckv_ext_attend_spec_wide keep refusing MXFP4 pools.
+ * SPECKV_ERR_INVAL, judged from the arguments alone and on every engine: g == 0 or g > 16 or no multiple of rows_per_pos, more than
+ * SPECKV_HELD_MAX - 1 positions, strides that are no multiples of 8 or let held rows overlap, a NULL query, held row, output or mask table,
+ * mask_stride < n_q, a query, output or held row that is not 16-byte aligned, an odd pos_end.  Then: a capturing stream; an allocation
+ * that is no MXFP4 pool with such a layout (FP8_E4M3, INT4_G32), a layer or pos_end outside it, records that do not lie in one run (a
+ * striped or migrated placement) -- the message names speckv_ext_attend_chunk, which serves every scheme and placement.  Nothing is
+ * launched, d_out is untouched.  No sliding window, no more than 16 rows.  Measured against the planned route: profiles/mx4_spec.txt. */
+speckv_status_t speckv_ext_attend_spec_mx4(uint32_t n_seq, const speckv_handle_t* handles, uint32_t layer, const void* d_q_f16, uint32_t g,
+                                           uint32_t rows_per_pos, const uint32_t* pos_end, const void* d_k_held, const void* d_v_held,
+                                           uint64_t seq_stride_elems, uint64_t pos_stride_elems, const uint32_t* d_mask, uint32_t mask_stride,
+                                           float sm_scale, float* d_out, float* d_lse /* optional */, void* stream);
+
 /* The walk rule of speckv_ext_attend_kv_spec_window as a pure function (works without speckv_init, needs no device): for a member of
  * `length` committed positions under window W >= 1, *out_begin = the first position walked (a multiple of 32), *out_n_pages = the pages
  * walked from there (0: no row sees a stored position), *out_rel = length + 1 - W - begin, signed -- a row of depth d does not see the
