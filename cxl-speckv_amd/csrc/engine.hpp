@@ -253,9 +253,8 @@ public:
     // region `layer` of the MXFP4 allocation v_handles[i], one attention launch (and its merge) for the batch.  q_pos / window: the window
     // entry (speckv_ext_attend_kv_batch_window; decode_window.hpp), as attend_batch's -- window = 0: the launches of the entry without one
     int attend_batch_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
-                        const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos = nullptr, uint32_t window = 0,
-                        const AttendHeldArgs* held = nullptr, bool wide = false);
-    // the step of several positions over the split pool (speckv_ext_attend_kv_spec): its own refusals, then attend_batch_kv with the held rows;
+                        const uint32_t* pos_end, float sm_scale, float* d_out, float* d_lse, hipStream_t s, const uint32_t* q_pos = nullptr, uint32_t window = 0);
+    // the step of several positions over the split pool (speckv_ext_attend_kv_spec; engine_attend_spec.cpp): the held rows folded inside the launch;
     // length / d_depth / window: the step on a sliding-window layer (speckv_ext_attend_kv_spec_window; spec_window.hpp), window = 0: none;
     // wide: 17..32 query rows per kv head in one pass (speckv_ext_attend_kv_spec_wide; k_attend_k8v4_wide)
     int attend_spec_kv(uint32_t n_seq, const uint64_t* k_handles, const uint64_t* v_handles, uint32_t layer, const void* d_q_f16, uint32_t g,
@@ -502,8 +501,14 @@ private:
     static bool fold_held_args_ok(uint32_t heads, uint32_t g, uint32_t rows_per_pos, const void* d_q_f16, const void* d_k_held, const void* d_v_held,
                                   uint64_t seq_stride_elems, uint64_t pos_stride_elems, const float* d_out, const float* d_lse);
     template <class Launch> int launch_on(hipStream_t s, Launch launch);
-    struct SpecStep;                                      // the members of a draft step over one allocation per sequence (engine_attend_spec.cpp)
-    int spec_step_launch(SpecStep& m, hipStream_t s);     // ... and what attend_spec_window and attend_spec_mx4 do once its descriptors stand
+    // a batch step staged per call (engine_internal.hpp): its members once their descriptors stand, and everything from the launch decision
+    // to the launch, which the entry issues itself.  split_member / spec_members fill the members of the split pool and of one allocation each
+    struct StagedStep;
+    template <class Launch> int staged_launch(StagedStep& m, hipStream_t s, Launch launch);
+    int split_member(StagedStep& m, uint32_t i, uint64_t k_handle, uint64_t v_handle, uint32_t layer, uint64_t layer_last, uint32_t pos_end, uint32_t begin,
+                     uint32_t n_pages);
+    int spec_members(StagedStep& m, int scheme, uint32_t n_seq, const uint64_t* handles, uint32_t layer, const uint32_t* pos_end, const uint32_t* length,
+                     uint32_t window);
     int take_seq_slot(size_t bytes, int* slot, void** staged);
     int ensure_zero_page(hipStream_t s);
     uint8_t* attend_scratch(AttendArgs& k, uint64_t parts, size_t head_bytes, hipStream_t s);

@@ -155,4 +155,88 @@ struct SlotGuard {
 };
 
 } // namespace
+
+// A step of a batch whose descriptors are staged per call (the decode and draft entries of engine_attend_kv.cpp and engine_attend_spec.cpp),
+// once its members stand: n_splits of a descriptor = the member's tiles until assign_pieces.  tiles / pages are the members of the launch
+// decision and may outnumber the sequences (attend_layers_kv: [layer][sequence]); everything else is per sequence.
+struct Engine::StagedStep {
+    const char* entry;                           // for messages
+    std::vector<AttendSeq> seqs;
+    std::vector<AttendKvSide> vside;             // the second allocation of a member of the split pool; empty: one allocation per sequence
+    std::vector<uint32_t> tiles, pages;
+    std::vector<uint32_t> skip;                  // AttendArgs::seq_skip, staged where not empty (a window's skip or rel array)
+    std::vector<Allocation*> allocs;             // what speckv_free must wait for
+    uint64_t total_tiles = 0;
+    bool fp8 = true, mx4 = false;                // the BatchShape whose launch decision the kernel follows
+    uint32_t copies = 1;                         // the partials are this many times those of the pieces (2: the wide kernels; the layers of a launch)
+    uint64_t grid_rows = 0;                      // the workgroup rows of a grid that is not rows-first, where they are more than the sequences' (0: not judged)
+    const void* d_q_f16; uint32_t g; float sm_scale; float* d_out; float* d_lse;
+    StagedStep(const char* entry, size_t n_seq, size_t members, bool split, const void* d_q_f16, uint32_t g, float sm_scale, float* d_out, float* d_lse)
+        : entry(entry), seqs(n_seq), vside(split ? n_seq : 0u), tiles(members), pages(members), d_q_f16(d_q_f16), g(g), sm_scale(sm_scale), d_out(d_out), d_lse(d_lse) { allocs.reserve(2u * n_seq); }
+};
+
+// What every such entry does behind its members: the launch decision of attend_geometry.hpp over the pages walked, the members' pieces, the scratch,
+// ONE slot of the pinned descriptor ring read in place by the kernels (descriptors, V sides, dispatch order, skip array: Engine::attend_batch),
+// the arguments every launch takes, the waits -- and the launch itself, which is the caller's: launch(args, the V sides on the device,
+// the partials of one copy, whether a merge follows, the stream) -> status, where the entry sets what only it knows and names its kernel.
+// NULL = the engine's stream and a synchronous call: the query may have been produced on any stream of the caller.
+template <class Launch>
+int Engine::staged_launch(StagedStep& m, hipStream_t s, Launch launch)
+{
+    const auto refuse = [&](const char* why) { SPECKV_ERR("%s: %s", m.entry, why); return SPECKV_ERR_INVAL; };
+    DeviceScope device_scope(device_);
+    if (!s) HIP_TRY(hipDeviceSynchronize());
+    hipStream_t st = s ? s : stream_;
+    const uint32_t n_seq = static_cast<uint32_t>(m.seqs.size()), members = static_cast<uint32_t>(m.tiles.size());
+    const BatchTuning tun = batch_tuning();
+    const BatchShape shape{m.fp8, m.mx4, members, 8u, cus(), false, false};
+    const BatchForm form = batch_form(shape, tun);
+    std::vector<uint32_t> order(members);
+    const bool ordered = batch_dispatch_order(form, tun, m.pages.data(), members, order.data());
+    const BatchGeometry geo = batch_geometry(kEntryBatch, shape, form, tun, m.tiles.data(), 0, ordered, nullptr);
+    if (!geo.fits) return refuse("a member in more than 2048 pieces");
+    const uint64_t parts = assign_pieces(geo, 8u, m.seqs.data(), n_seq);
+    bool merge = false;
+    for (uint32_t i = 0; i < n_seq; ++i) merge = merge || m.seqs[i].n_splits > 1u;
+    AttendArgs k{};
+    if ((m.copies > 1u && parts * m.copies > 0xFFFFFFFFull) || (!geo.rows_first && m.grid_rows > 65535u))
+        return refuse("a grid beyond the launch limits (the workgroup rows of all members, or more than 2^32 partials)");
+    if (!attend_scratch(k, merge ? parts * m.copies : 1u, 0, s)) return SPECKV_ERR_NOMEM;
+    const size_t desc_bytes = n_seq * sizeof(AttendSeq), side_bytes = m.vside.size() * sizeof(AttendKvSide), order_bytes = ordered ? members * sizeof(uint32_t) : 0u,
+                 skip_bytes = m.skip.size() * sizeof(uint32_t);
+    int slot = 0;
+    void* staged = nullptr;
+    RC_TRY(take_seq_slot(desc_bytes + side_bytes + order_bytes + skip_bytes, &slot, &staged));
+    uint8_t* h_slot = static_cast<uint8_t*>(staged);
+    memcpy(h_slot, m.seqs.data(), desc_bytes);
+    if (side_bytes) memcpy(h_slot + desc_bytes, m.vside.data(), side_bytes);
+    if (ordered) memcpy(h_slot + desc_bytes + side_bytes, order.data(), order_bytes);
+    if (skip_bytes) memcpy(h_slot + desc_bytes + side_bytes + order_bytes, m.skip.data(), skip_bytes);
+    uint8_t* d_slot = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_slot), staged, 0));
+    k.heads = 8u;
+    k.g = m.g;
+    k.n_splits = m.total_tiles ? geo.max_splits : 0u;
+    k.tiles_per_split = geo.tps;
+    k.q16 = static_cast<const uint16_t*>(m.d_q_f16);
+    k.scale_log2e = m.sm_scale * 1.4426950408889634f;
+    k.lin_base = m.seqs[0].lin_base;                                     // (overridden per sequence)
+    k.seqs = reinterpret_cast<const AttendSeq*>(d_slot);
+    if (ordered) k.order = reinterpret_cast<const uint32_t*>(d_slot + desc_bytes + side_bytes);
+    if (skip_bytes) k.seq_skip = reinterpret_cast<const uint32_t*>(d_slot + desc_bytes + side_bytes + order_bytes);
+    if (geo.rows_first) k.rows_first = 1u;
+    k.direct_out = m.d_out;
+    k.direct_lse = m.d_lse;
+    k.direct_per_seq = 1u;                                               // members with one piece or none are final, the merge passes them over
+    // behind the asynchronous pool writes on every other caller stream the engine knows (a commit on another stream)
+    for (auto& w : write_evs_)
+        if (w.s != st) HIP_TRY(hipStreamWaitEvent(st, w.ev, 0));
+    for (Allocation* a : m.allocs) note_use(a, s);                       // speckv_free waits for this stream
+    // The guard event is recorded on every way out from here on: the slot must not be written again under a kernel still reading it.
+    SlotGuard slot_guard{seq_ring_.ev[slot], st};
+    RC_TRY(launch(k, reinterpret_cast<const AttendKvSide*>(d_slot + desc_bytes), static_cast<uint32_t>(parts), merge, st));
+    if (!s) HIP_TRY(hipStreamSynchronize(stream_));
+    return SPECKV_OK;
+}
+
 } // namespace speckv

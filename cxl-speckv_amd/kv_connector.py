@@ -50,7 +50,7 @@ Only plain device pointers cross into the library; torch is used for device buff
 import numbers
 from typing import Dict, List, Optional, Sequence
 
-from .kv_shared import PARENTS_RULE, SPLITS_RULE, SharedPrefixSteps, _is_int, paged_cache_geometry, tail_index
+from .kv_shared import PARENTS_RULE, SPLITS_RULE, DraftSteps, SharedPrefixSteps, _is_int, paged_cache_geometry, tail_index, tree_key
 from .speckv_ctypes import HELD_MAX, SpeckvLib
 
 PAGE = 4096
@@ -92,7 +92,7 @@ def _device_index(values):
     return torch.tensor(values, dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
 
 
-class SpeckvKVConnector(SharedPrefixSteps):
+class SpeckvKVConnector(SharedPrefixSteps, DraftSteps):
     def __init__(self, lib: SpeckvLib, num_layers: int, num_kv_heads: int = 8, head_dim: int = 128, max_tokens: int = 4096,
                  scheme: str = "fp8"):
         if num_kv_heads * head_dim * 2 != 2048:
@@ -125,8 +125,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
         self._step_cols = {}
         self._plan_stream = None
         self._kscale = self._kscale_inv = None               # set_k_channel_scale
-        self._spec_key = self._spec_idx = self._spec_base = None     # attend_spec: where the held rows of a step come from
-        self._spec_window = (None,)                                  # attend_spec(window=W): (key, mask words, depths [batch][S], pos_end, lengths)
+        self._spec = (None,)                                         # attend_spec: key, then what the step derived once (DraftSteps._spec_step)
         self._tree_key = self._tree_masks = None                     # attend_spec(parents=...): the mask words of a step, [n_layers * batch][S]
         self._chunk_tree_key = self._chunk_tree_masks = None         # attend_chunk(parents=...): the mask rows of a step, [batch][S][W]
         self._chunk_tree_wtabs = {}                                  # attend_tree(window=W): W -> (key, mask rows, depths [batch][S])
@@ -863,11 +862,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
         if not trees:
             return []
         S = len(trees[0])
-        if n_new is None:
-            n_new = [S] * len(base)
-        n_new = [int(n) for n in n_new]
-        if len(n_new) != len(base) or not all(0 <= n <= S for n in n_new):
-            raise ValueError("n_new: one count 0..S per request")
+        n_new = DraftSteps._spec_live(n_new, len(base), S) or [S] * len(base)
         if not all(0 <= x and x + S <= HELD_MAX for x in base):
             raise ValueError(f"base: 0 .. {HELD_MAX} - S held positions in front of the new ones")
         words = []
@@ -908,31 +903,26 @@ class SpeckvKVConnector(SharedPrefixSteps):
         """max(0, rel + min(depth, 15)): the leading positions of a request's walk (spec_window_range) that a node of `depth` does not see"""
         return max(0, int(rel) + min(int(depth), 15))
 
-    def _held_rows(self, req_ids, key, reqs, k_new, v_new, layer_begin, n_layers, st):
+    _index = staticmethod(lambda values: _device_index(values))
+
+    def _spec_handles(self, req_ids, reqs):
+        return (self._batch(req_ids)[2],)
+
+    def _held_rows(self, req_ids, key, reqs, k_new, v_new, layer_begin, n_layers, st, step):
         """The rows a step holds outside the pool as speckv_ext_attend_fold_held takes them: fp16 [n_layers][batch][1 + S][heads][dim]
-        per kind -- the request's odd last position (if any) followed by its new positions -- and the count of positions in front of
-        the first new one, int32 [n_layers * batch].  Two torch kernels per kind; the gather indices are per (batch, lengths, S)."""
+        per kind -- the request's odd last position (if any) followed by its new positions.  Two torch kernels per kind; the gather
+        index is the step's (DraftSteps.held_row_index)."""
         import torch
         B, S = k_new.shape[0], k_new.shape[1]
         self._prepare_tails(req_ids, key, reqs, st)                     # the odd positions of the batch as one tensor per kind
-        skey = (key, self._epoch, S, n_layers)
-        if self._spec_key != skey:
-            idx, base, rank = [], [], 0
-            for b, r in enumerate(reqs):
-                if r.length & 1:
-                    idx += [B * S + rank] + [b * S + t for t in range(S)]
-                    rank += 1
-                else:
-                    idx += [b * S + t for t in range(S)] + [b * S + S - 1]      # (the last slot is never visible)
-                base.append(r.length & 1)
-            self._spec_key, self._spec_idx, self._spec_base = skey, _device_index(idx), _device_index(base * n_layers)
+        idx = self._spec_index(step, reqs, S)
         held = []
         for new, tails in ((k_new, self._fold_k), (v_new, self._fold_v)):
             flat = new[:, :, layer_begin:layer_begin + n_layers].permute(2, 0, 1, 3, 4).reshape(n_layers, B * S, self.H, self.D)
             if self._fold_n:
                 flat = torch.cat((flat, tails[:, layer_begin:layer_begin + n_layers].permute(1, 0, 2, 3)), dim=1)
-            held.append(flat.index_select(1, self._spec_idx))
-        return held[0], held[1], self._spec_base
+            held.append(flat.index_select(1, idx))
+        return held[0], held[1]
 
     def attend_spec(self, layer: int, req_ids: Sequence[int], q, k_new, v_new, sm_scale: float, n_new=None, stream=None, parents=None, window=None,
                     rows_per_pass=16, row_block=None):
@@ -1007,42 +997,43 @@ class SpeckvKVConnector(SharedPrefixSteps):
             raise ValueError("attend_spec(rows_per_pass=32) serves FP8 pools; an INT4 or MXFP4 pool takes rows_per_pass=16")
         if row_block is not None and (row_block != 16 or self.scheme != SCHEMES["mxfp4"]):
             raise ValueError("attend_spec(row_block=...) must be None or 16, and 16 serves MXFP4 pools alone (an FP8 pool: rows_per_pass=32)")
-        if n_new is not None:
-            n_new = [int(n) for n in n_new]
-            if len(n_new) != B or not all(0 <= n <= S for n in n_new):
-                raise ValueError("n_new: one count 0..S per request")
+        n_new = self._spec_live(n_new, B, S)
         key, reqs, _ = self._batch(req_ids)
         if self._kscale is not None:
             q = q * self._kscale[layer_begin:layer_begin + n_layers][:, None, None, :, None, :]
             k_new = k_new * self._kscale_inv[None, None]
         out = torch.empty((NL, B, S, H, R, D), dtype=torch.float32, device="cuda")
+        parents = None if parents is None else list(parents)
+        step = self._spec_step(key, S, parents, n_new)
         if W or rows_per_pass == 32 or row_block:
-            return out if B == 0 else self._spec_window_layers(layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out,
-                                                               mx4=bool(row_block))
-        akey = (key, self._epoch)
+            return out if B == 0 else self._spec_one_launch_layers(layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups,
+                                                                   out, step, self.lib.attend_spec_mx4 if row_block else None)
         with self._On(self, stream) as st:
-            if self._arg_key != (akey, st.cuda_stream):
-                self.plan_step(req_ids, st)
-            self._plan_stream = st
+            self._spec_plan(req_ids, key, st)
             with torch.cuda.stream(st):
-                kh, vh, base = self._held_rows(req_ids, key, reqs, k_new, v_new, layer_begin, n_layers, st)
+                kh, vh = self._held_rows(req_ids, key, reqs, k_new, v_new, layer_begin, n_layers, st, step)
+                if ("base", NL) not in step:
+                    step["base", NL] = _device_index([r.length & 1 for r in reqs] * NL)
                 live = None if n_new is None or parents is not None else _device_index(n_new * NL)
                 masks = None if parents is None else self._tree_table(key, reqs, parents, n_new, NL, S)
                 for j0, n in groups:
-                    g = n * R
                     qg, og, lse = self._spec_planned_group(layer_begin, q, j0, n, sm_scale, st)
                     if masks is not None:
-                        self.lib.attend_fold_masked(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
-                                                    masks.data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
-                        out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
-                        continue
-                    d_base = base + j0 if j0 else base
-                    d_live = None if live is None else (live - j0).clamp_(0, n)
-                    self.lib.attend_fold_held(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
-                                              d_base.data_ptr(), 0 if d_live is None else d_live.data_ptr(), sm_scale, og.data_ptr(),
-                                              lse.data_ptr(), st.cuda_stream)
-                    out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
+                        self._spec_fold_masked(masks, qg, kh, vh, S, R, j0, sm_scale, og, lse, st)
+                    else:
+                        d_base = step["base", NL] + j0 if j0 else step["base", NL]
+                        d_live = None if live is None else (live - j0).clamp_(0, n)
+                        self.lib.attend_fold_held(NL * B, 0, H, n * R, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
+                                                  d_base.data_ptr(), 0 if d_live is None else d_live.data_ptr(), sm_scale, og.data_ptr(),
+                                                  lse.data_ptr(), st.cuda_stream)
+                    self.scatter_rows(out, og, j0, n)
         return out
+
+    def _spec_plan(self, req_ids, key, st):
+        """the global plan of this step on this stream, made where it does not stand yet (attend's rule)"""
+        if self._arg_key != ((key, self._epoch), st.cuda_stream):
+            self.plan_step(req_ids, st)
+        self._plan_stream = st
 
     def _spec_planned_group(self, layer_begin, q, j0, n, sm_scale, st):
         """The planned decode call of a global layer's group of n positions from j0 (<= 16 query rows per kv head) over the stored
@@ -1050,7 +1041,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
         import torch
         NL, B, S, H, R, D = q.shape
         g = n * R
-        qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
+        qg = self.group_rows(q, j0, n)
         og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
         lse = torch.empty((NL, B, H, g), dtype=torch.float32, device="cuda")
         if NL == 1:
@@ -1061,58 +1052,42 @@ class SpeckvKVConnector(SharedPrefixSteps):
                                            sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
         return qg, og, lse
 
-    def _spec_window_layers(self, layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out, mx4=False):
-        """attend_spec_layers(window=W) and attend_spec_layers(rows_per_pass=32) on an FP8 pool, W = 0: a global layer.  Per layer, a
-        group of 17..32 rows is one speckv_ext_attend_spec_wide; one of 16 rows or fewer is one speckv_ext_attend_spec_window under a
-        window and, on a global layer (a trailing group of a wide step), the planned call and one speckv_ext_attend_fold_masked over
-        all the layers.  The mask words (tree_masks(window=W or None); a chain is the tree parents[j] = j - 1), the depths, pos_end and
-        the lengths are made once per (batch, epoch, S, tree, live counts, W); the held rows are _held_rows'.
-        mx4: attend_spec_layers(row_block=16) on an MXFP4 pool (W = 0) -- every group and layer is one speckv_ext_attend_spec_mx4 over
-        the same words, pos_end and held rows."""
-        import numpy as np
+    def _spec_fold_masked(self, masks, qg, kh, vh, S, R, j0, sm_scale, og, lse, st):
+        """... and the fold launch of a tree's group over all its layers, by the group's columns of the step's mask words (_tree_table)"""
+        NL, B, H, g, D = qg.shape
+        self.lib.attend_fold_masked(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
+                                    masks.data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(), lse.data_ptr(), st.cuda_stream)
+
+    def _spec_one_launch_layers(self, layer_begin, req_ids, key, reqs, q, k_new, v_new, sm_scale, n_new, stream, parents, W, groups, out, step, entry):
+        """The groups of attend_spec_layers that are ONE launch per layer with the held rows folded inside it, and the 16-row group that
+        trails a wide step on a global layer.  entry: the library entry every group goes to (row_block=16: speckv_ext_attend_spec_mx4);
+        None, an FP8 pool: a group of 17..32 rows is speckv_ext_attend_spec_wide, one of 16 rows or fewer is
+        speckv_ext_attend_spec_window under a window and, on a global layer (W = 0), the planned call and one
+        speckv_ext_attend_fold_masked over all the layers (a chain is the tree parents[j] = j - 1).  Mask words, depths, pos_end, lengths
+        and handles are the step's (DraftSteps._spec_tables); the held rows are _held_rows'."""
         import torch
         NL, B, S, H, R, D = q.shape
-        tree = list(range(-1, S - 1)) if parents is None else list(parents)
-        one = len(tree) > 0 and isinstance(tree[0], numbers.Integral)
-        wkey = (key, self._epoch, S, tuple(tree) if one else tuple(map(tuple, tree)), None if n_new is None else tuple(n_new), W)
-        if self._spec_window[0] != wkey:
-            trees = self._tree_parents(tree, B)
-            if len(trees[0]) != S:
-                raise ValueError("parents: one entry per new position")
-            words = self.tree_masks(trees, [r.length & 1 for r in reqs], n_new, window=W or None)
-            depths = self.chunk_tree_depths(trees, B)
-            self._spec_window = (wkey, _device_index([w for row in words for w in row]), _device_index([d for row in depths for d in row]),
-                                 np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32), np.asarray([r.length for r in reqs], dtype=np.uint32))
-        _, masks, depths, pos_end, lengths = self._spec_window
-        handles = self._batch(req_ids)[2]
         with self._On(self, stream) as st:
             with torch.cuda.stream(st):
-                kh, vh, _ = self._held_rows(req_ids, key, reqs, k_new, v_new, layer_begin, NL, st)      # [n_layers][batch][1 + S][heads][dim]
+                masks, depths, pos_end, lengths, (handles,), _ = self._spec_tables(step, req_ids, reqs, S, parents, n_new, W)
+                kh, vh = self._held_rows(req_ids, key, reqs, k_new, v_new, layer_begin, NL, st, step)      # [n_layers][batch][1 + S][heads][dim]
                 for j0, n in groups:
                     g = n * R
-                    if mx4:
-                        qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
-                        og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
-                        for l in range(NL):
-                            self.lib.attend_spec_mx4(handles, layer_begin + l, qg[l].data_ptr(), g, R, pos_end, kh[l].data_ptr(), vh[l].data_ptr(),
-                                                     (1 + S) * H * D, H * D, masks.data_ptr() + 4 * j0, S, sm_scale, og[l].data_ptr(), 0, st.cuda_stream)
-                    elif g <= 16 and not W:                              # the trailing group of a wide step on a global layer
-                        if self._arg_key != ((key, self._epoch), st.cuda_stream):
-                            self.plan_step(req_ids, st)
-                        self._plan_stream = st
+                    if entry is None and g <= 16 and not W:          # the trailing group of a wide step on a global layer
+                        self._spec_plan(req_ids, key, st)
                         qg, og, lse = self._spec_planned_group(layer_begin, q, j0, n, sm_scale, st)
-                        self.lib.attend_fold_masked(NL * B, 0, H, g, R, qg.data_ptr(), kh.data_ptr(), vh.data_ptr(), (1 + S) * H * D, H * D,
-                                                    self._tree_table(key, reqs, tree, n_new, NL, S).data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(),
-                                                    lse.data_ptr(), st.cuda_stream)
-                    else:
-                        qg = q[:, :, j0:j0 + n].permute(0, 1, 3, 2, 4, 5).reshape(NL, B, H, g, D).contiguous()
-                        og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
-                        step = self.lib.attend_spec_wide if g > 16 else self.lib.attend_spec_window
-                        for l in range(NL):
-                            step(handles, layer_begin + l, qg[l].data_ptr(), g, R, pos_end, lengths, depths.data_ptr() + 4 * j0, W,
-                                 kh[l].data_ptr(), vh[l].data_ptr(), (1 + S) * H * D, H * D, masks.data_ptr() + 4 * j0, S, sm_scale,
-                                 og[l].data_ptr(), 0, st.cuda_stream)
-                    out[:, :, j0:j0 + n] = og.view(NL, B, H, n, R, D).permute(0, 1, 3, 2, 4, 5)
+                        tree = list(range(-1, S - 1)) if parents is None else parents
+                        self._spec_fold_masked(self._tree_table(key, reqs, tree, n_new, NL, S), qg, kh, vh, S, R, j0, sm_scale, og, lse, st)
+                        self.scatter_rows(out, og, j0, n)
+                        continue
+                    qg = self.group_rows(q, j0, n)
+                    og = torch.empty((NL, B, H, g, D), dtype=torch.float32, device="cuda")
+                    window_args = () if entry is not None else (lengths, depths.data_ptr() + 4 * j0, W)
+                    launch = entry or (self.lib.attend_spec_wide if g > 16 else self.lib.attend_spec_window)
+                    for l in range(NL):
+                        launch(handles, layer_begin + l, qg[l].data_ptr(), g, R, pos_end, *window_args, kh[l].data_ptr(), vh[l].data_ptr(),
+                               (1 + S) * H * D, H * D, masks.data_ptr() + 4 * j0, S, sm_scale, og[l].data_ptr(), 0, st.cuda_stream)
+                    self.scatter_rows(out, og, j0, n)
         return out
 
     # ------------------------------------------------------------------ chunks of any length
@@ -1281,11 +1256,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
         if not trees:
             return []
         S = len(trees[0])
-        if n_new is None:
-            n_new = [S] * len(base)
-        n_new = [int(n) for n in n_new]
-        if len(n_new) != len(base) or not all(0 <= n <= S for n in n_new):
-            raise ValueError("n_new: one count 0..S per request")
+        n_new = DraftSteps._spec_live(n_new, len(base), S) or [S] * len(base)
         if not all(x in (0, 1) for x in base):
             raise ValueError("base: 0 or 1 held positions in front of the new ones")
         W = (S + 1 + 31) // 32
@@ -1315,8 +1286,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
         epoch, S, tree, live counts) the way _tree_table keeps its words: every layer's call of a step finds the same table."""
         import numpy as np
         import torch
-        one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)      # one tree for every request
-        tkey = (key, self._epoch, S, tuple(parents) if one else tuple(map(tuple, parents)), tuple(live))
+        tkey = (key, self._epoch, S, tree_key(parents), tuple(live))
         if self._chunk_tree_key != tkey:
             rows = self.chunk_tree_masks(parents, [r.length & 1 for r in reqs], live)
             if len(rows[0]) != S:
@@ -1331,8 +1301,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
         value beside the global layers' one, so a model's local and global layers each find theirs at every layer of a step."""
         import numpy as np
         import torch
-        one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)
-        tkey = (key, self._epoch, S, tuple(parents) if one else tuple(map(tuple, parents)), tuple(live), window)
+        tkey = (key, self._epoch, S, tree_key(parents), tuple(live), window)
         held = self._chunk_tree_wtabs.get(window)
         if held is None or held[0] != tkey:
             rows = self.chunk_tree_masks(parents, [r.length & 1 for r in reqs], live, window=window)
@@ -1573,8 +1542,7 @@ class SpeckvKVConnector(SharedPrefixSteps):
         """The mask words of a tree step on the device, int32 [n_layers * batch][S] (every layer the same words), kept per
         (batch, epoch, layers, S, tree, live counts) as the gather indices of _held_rows are: the per-layer calls of a step find them
         there -- the tree is judged (tree_masks) when the words are made, a call that finds them compares two tuples."""
-        one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)      # one tree for every request
-        tkey = (key, self._epoch, n_layers, S, tuple(parents) if one else tuple(map(tuple, parents)), None if n_new is None else tuple(n_new))
+        tkey = (key, self._epoch, n_layers, S, tree_key(parents), None if n_new is None else tuple(n_new))
         if self._tree_key != tkey:
             words = self.tree_masks(parents, [r.length & 1 for r in reqs], n_new)
             if len(words[0]) != S:

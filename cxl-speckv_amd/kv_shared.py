@@ -5,7 +5,8 @@ and supplies what differs between one allocation per request and two:
   _prefix_handles(prefix_ids)        the handle arrays of the prefix requests, as a tuple: one array, or (K, V) of the split pool
   _own_decode / _own_chunk(...)      its own decode / chunk step with the log-sum-exp kept -> (out, lse, q as launched)
   _prefix_fold(...)                  the fold launch (which entry, and whether own_seen is built, is the connector's)
-  _depth_table(...)                  the device depth table of a tree under a window, the one its own chunk step has just read"""
+  _depth_table(...)                  the device depth table of a tree under a window, the one its own chunk step has just read
+DraftSteps is the same for attend_spec: the held-row index, a step's tables behind one cache, a group's rows into a launch and back."""
 import numbers
 from typing import Optional, Sequence
 
@@ -16,6 +17,12 @@ PARENTS_RULE = "parents: one tree per request, or one tree for all"
 def _is_int(x):
     """an integer of any kind (python's, numpy's), but no bool"""
     return isinstance(x, numbers.Integral) and not isinstance(x, bool)
+
+
+def tree_key(parents):
+    """a step's `parents` argument -- one tree for every request, or one per request -- as a key for what is kept per tree"""
+    one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)
+    return tuple(parents) if one else tuple(map(tuple, parents))
 
 
 def tail_index(reqs):
@@ -61,6 +68,80 @@ def paged_cache_geometry(caches, n_layers, bf16=False):
     return geo, None
 
 
+class DraftSteps:
+    """attend_spec's host side, one body for both connectors: what a step of S new positions per request derives from (batch, epoch, S,
+    tree, live counts, W) -- once, behind ONE cache, `_spec` = (key, what was derived) -- and the way of a group's rows into a launch
+    and back.  A connector supplies _index(values) (an int32 device tensor of a list), _spec_handles(req_ids, reqs) (its handle arrays,
+    as a tuple), the pure rules _tree_parents, tree_masks and chunk_tree_depths, and the library entry a group goes to."""
+
+    @staticmethod
+    def held_row_index(reqs, S):
+        """Where the 1 + S held rows of every request come from, as indices into [batch * S new rows] + [the odd last positions by
+        rank]: the odd last position first where the length is odd, then the new positions; an even length repeats its last new row in
+        the slot behind them, which is never visible."""
+        B, idx, rank = len(reqs), [], 0
+        for b, r in enumerate(reqs):
+            new = [b * S + t for t in range(S)]
+            if r.length & 1:
+                idx += [B * S + rank] + new
+                rank += 1
+            else:
+                idx += new + [b * S + S - 1]
+        return idx
+
+    @staticmethod
+    def _spec_live(n_new, B, S):
+        """n_new as a list of ints, judged in front of any library call; None stays None"""
+        if n_new is None:
+            return None
+        n_new = [int(n) for n in n_new]
+        if len(n_new) != B or not all(0 <= n <= S for n in n_new):
+            raise ValueError("n_new: one count 0..S per request")
+        return n_new
+
+    def _spec_step(self, batch_key, S, parents, n_new):
+        """What is kept of this step (batch_key: tuple(req_ids); parents: None or a list), a dict that _spec_index and _spec_tables
+        fill: the same for every layer and group.  The window is no part of the key: the tables of a window value lie under that value
+        inside it, so the local and the global layers of a model share the index and keep one table each."""
+        key = (batch_key, self._epoch, S, None if parents is None else tree_key(parents), None if n_new is None else tuple(n_new))
+        if self._spec[0] != key:
+            self._spec = (key, {})
+        return self._spec[1]
+
+    def _spec_index(self, step, reqs, S):
+        """held_row_index on the device"""
+        if "idx" not in step:
+            step["idx"] = self._index(self.held_row_index(reqs, S))
+        return step["idx"]
+
+    def _spec_tables(self, step, req_ids, reqs, S, parents, n_new, W, with_depths=True):
+        """(mask words [batch][S] and depths [batch][S] on the device, pos_end, lengths, the handle arrays, the held-row index) of the
+        step under the window W (0: none): the tree -- a chain is parents[j] = j - 1 -- is judged here, when the words are made
+        (tree_masks(window=W or None)); a call that finds them looks one entry up.  with_depths=False: no depth table (None)."""
+        import numpy as np
+        if W not in step:
+            trees = self._tree_parents(list(range(-1, S - 1)) if parents is None else parents, len(reqs))
+            if len(trees[0]) != S:
+                raise ValueError("parents: one entry per new position")
+            words = self.tree_masks(trees, [r.length & 1 for r in reqs], n_new, window=W or None)
+            masks = self._index([w for row in words for w in row])
+            depths = self._index([d for row in self.chunk_tree_depths(trees, len(reqs)) for d in row]) if with_depths else None
+            step[W] = (masks, depths, np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32), np.asarray([r.length for r in reqs], dtype=np.uint32),
+                       self._spec_handles(req_ids, reqs), self._spec_index(step, reqs, S))
+        return step[W]
+
+    @staticmethod
+    def group_rows(q, j0, n):
+        """The query rows of positions j0 .. j0 + n - 1 as a launch reads them: q [..][batch][S][heads][rows_per_pos][dim] (an optional
+        leading layers axis) -> [..][batch][heads][n * rows_per_pos][dim], contiguous"""
+        return q.narrow(-4, j0, n).transpose(-4, -3).flatten(-3, -2).contiguous()
+
+    @staticmethod
+    def scatter_rows(out, og, j0, n):
+        """... and a launch's output og [..][batch][heads][n * rows_per_pos][dim] back into positions j0 .. j0 + n - 1 of out"""
+        out.narrow(-4, j0, n).copy_(og.unflatten(-2, (n, -1)).transpose(-4, -3))
+
+
 class SharedPrefixSteps:
     def _pool_check(self, what):
         pass
@@ -85,12 +166,7 @@ class SharedPrefixSteps:
             raise ValueError("q must be [batch][S][heads][rows_per_pos][dim], k_new / v_new [batch][S][layers][heads][dim], S >= 1")
         if not 0 <= layer < self.L:
             raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
-        if n_new is None:
-            live = [S] * B
-        else:
-            live = [int(n) for n in n_new]
-            if len(live) != B or not all(0 <= n <= S for n in live):
-                raise ValueError("n_new: one count 0..S per request")
+        live = DraftSteps._spec_live(n_new, B, S) or [S] * B
         counts, _ = self.chunk_blocks(live, R)
         reqs = self._reqs(req_ids)
         for r, n in zip(reqs, live):

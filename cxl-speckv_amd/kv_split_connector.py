@@ -53,7 +53,7 @@ from typing import Dict, Optional, Sequence
 
 from . import kv_connector as _kc
 from .kv_connector import SpeckvKVConnector
-from .kv_shared import SharedPrefixSteps, _is_int, paged_cache_geometry, tail_index
+from .kv_shared import DraftSteps, SharedPrefixSteps, _is_int, paged_cache_geometry, tail_index, tree_key
 from .speckv_ctypes import SpeckvLib
 
 K_SCHEME, V_SCHEME = 4, 5                # SPECKV_COMP_FP8_E4M3, SPECKV_COMP_MXFP4
@@ -67,11 +67,14 @@ class _SplitRequest:
         self.k_handle, self.v_handle, self.length, self.tail_k, self.tail_v = k_handle, v_handle, 0, None, None
 
 
-class SpeckvSplitKVConnector(SharedPrefixSteps):
+class SpeckvSplitKVConnector(SharedPrefixSteps, DraftSteps):
     _On = SpeckvKVConnector._On          # the stream rule of the connector: torch's NULL stream goes through a side stream
     chunk_blocks = staticmethod(SpeckvKVConnector.chunk_blocks)
     _chunk_tree_parents = staticmethod(SpeckvKVConnector._chunk_tree_parents)
     _tree_parents = staticmethod(SpeckvKVConnector._tree_parents)       # (what _checked_paths judges commit(nodes=..., parents=...) with)
+    tree_masks = staticmethod(SpeckvKVConnector.tree_masks)             # (... and, with these, what DraftSteps makes a step's tables from)
+    chunk_tree_depths = staticmethod(SpeckvKVConnector.chunk_tree_depths)
+    _index = staticmethod(lambda values: _kc._device_index(values))
 
     def __init__(self, lib: SpeckvLib, num_layers: int, num_kv_heads: int = 8, head_dim: int = 128, max_tokens: int = 4096):
         if num_kv_heads * head_dim * 2 != 2048:
@@ -94,7 +97,7 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                                                               # requests with an odd length, the handle arrays, the stored lengths,
                                                               # the query positions (attend under a window)
         self._layers = (None,)                                # attend_layers: key, then the handle arrays, the stored lengths and the tail index on the device
-        self._spec = (None,)                                  # attend_spec: key, then the step's mask words and gather index on the device, the
+        self._spec = (None,)                                  # attend_spec: key, then what the step derived once (DraftSteps): mask words and gather index on the device, the
                                                               # handle arrays and the stored lengths
         self._shared_key, self._shared_plan = None, None      # attend_shared / attend_chunk_shared: the judged call of a step (_shared_args)
 
@@ -322,11 +325,9 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
     def _step_tree(self, req_ids, reqs, parents, live, S, window):
         """(mask rows int32 [batch][S][W], depths int32 [batch][S] or None) of a tree step on the device, once per (batch, lengths, tree,
         live counts, window): the static helpers of SpeckvKVConnector build both, the window folded into the rows"""
-        import numbers
         import numpy as np
         import torch
-        one = len(parents) > 0 and isinstance(parents[0], numbers.Integral)
-        key = (tuple(req_ids), self._epoch, S, tuple(parents) if one else tuple(map(tuple, parents)), tuple(live), window)
+        key = (tuple(req_ids), self._epoch, S, tree_key(parents), tuple(live), window)
         if self._tree[0] != key:
             rows = SpeckvKVConnector.chunk_tree_masks(parents, [r.length & 1 for r in reqs], live, window=window or None)
             on_device = lambda a: torch.from_numpy(a).pin_memory().to("cuda", non_blocking=True)
@@ -505,8 +506,6 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         so 16 stays the default.  Any other value is a ValueError.
         Malformed arguments are a ValueError / KeyError before any library call; a placement the decode kernel does not serve
         (striped, migrated) is the library's SpeckvError, passed through as in attend."""
-        import numbers
-        import numpy as np
         import torch
         if len(q.shape) != 5:
             raise ValueError("q must be [batch][S][heads][rows_per_pos][dim]")
@@ -519,15 +518,10 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
             raise ValueError(f"layer {layer} outside 0..{self.L - 1}")
         groups = SpeckvKVConnector.spec_groups(S, R, rows_per_pass)
         W = SpeckvKVConnector._decode_window(window)
-        if n_new is not None:
-            n_new = [int(n) for n in n_new]
-            if len(n_new) != B or not all(0 <= n <= S for n in n_new):
-                raise ValueError("n_new: one count 0..S per request")
+        n_new = self._spec_live(n_new, B, S)
         reqs = [self.requests[r] for r in req_ids]
-        if parents is not None:                       # (judged once per step, below: a walk over batch x S entries is the host's share of a call)
-            parents = list(parents)
-            shared = len(parents) > 0 and isinstance(parents[0], numbers.Integral)
-            tree_key = tuple(parents) if shared else tuple(tuple(p) for p in parents)
+        parents = None if parents is None else list(parents)  # (judged once per step, below: a walk over batch x S entries is the host's share of a call)
+        step = self._spec_step(tuple(req_ids), S, parents, n_new)
         row = self.H * self.D
         out = torch.empty((B, S, H, R, D), dtype=torch.float32, device="cuda")
         if B == 0:
@@ -535,26 +529,7 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
         with self._On(self, stream) as st:
             with torch.cuda.stream(st):
                 _, tk, tv = self._step_tails(req_ids, reqs)
-                key = (tuple(req_ids), self._epoch, S, None if parents is None else tree_key, None if n_new is None else tuple(n_new), W)
-                if self._spec[0] != key:              # once per step: the same for every layer and group
-                    trees = SpeckvKVConnector._tree_parents(list(range(-1, S - 1)) if parents is None else parents, B)
-                    if len(trees[0]) != S:
-                        raise ValueError("parents: one entry per new position")
-                    words = SpeckvKVConnector.tree_masks(trees, [r.length & 1 for r in reqs], n_new, window=W or None)
-                    depths = SpeckvKVConnector.chunk_tree_depths(trees, B) if W else None
-                    idx, rank = [], 0
-                    for b, r in enumerate(reqs):      # the tail first where the length is odd, then the new positions (_held_rows)
-                        if r.length & 1:
-                            idx += [B * S + rank] + [b * S + t for t in range(S)]
-                            rank += 1
-                        else:
-                            idx += [b * S + t for t in range(S)] + [b * S + S - 1]       # (the last slot is never visible)
-                    self._spec = (key, _kc._device_index([w for per_request in words for w in per_request]),     # [batch][S] words (< 2^17)
-                                  _kc._device_index(idx), np.asarray([r.k_handle for r in reqs], dtype=np.uint64),
-                                  np.asarray([r.v_handle for r in reqs], dtype=np.uint64), np.asarray([r.length & ~1 for r in reqs], dtype=np.uint32),
-                                  _kc._device_index([d for per_request in depths for d in per_request]) if W else None,       # [batch][S] depths
-                                  np.asarray([r.length for r in reqs], dtype=np.uint32))
-                _, masks, idx, k_handles, v_handles, pos_end, depths, lengths = self._spec
+                masks, depths, pos_end, lengths, (k_handles, v_handles), idx = self._spec_tables(step, req_ids, reqs, S, parents, n_new, W, bool(W))
                 held = []
                 for new, tails in ((k_new, tk), (v_new, tv)):
                     flat = new[:, :, layer].reshape(B * S, H, D)
@@ -564,26 +539,25 @@ class SpeckvSplitKVConnector(SharedPrefixSteps):
                 kh, vh = held
                 parts = []
                 for j0, n in groups:
-                    g = n * R
-                    parts.append((j0, n, g, q[:, j0:j0 + n].permute(0, 2, 1, 3, 4).reshape(B, H, g, D).contiguous(),
-                                  torch.empty((B, H, g, D), dtype=torch.float32, device="cuda")))
-            for j0, n, g, qg, og in parts:
+                    parts.append((j0, n, self.group_rows(q, j0, n), torch.empty((B, H, n * R, D), dtype=torch.float32, device="cuda")))
+            for j0, n, qg, og in parts:
+                g = n * R
+                d_depth = depths.data_ptr() + 4 * j0 if W else 0
+                held_args = (kh.data_ptr(), vh.data_ptr(), (1 + S) * row, row, masks.data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(), 0, st.cuda_stream)
                 if g > 16:                            # rows_per_pass = 32: both blocks of 16 rows in one pass over the records, window or not
-                    self.lib.attend_kv_spec_wide(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, lengths, depths.data_ptr() + 4 * j0 if W else 0, W,
-                                                 kh.data_ptr(), vh.data_ptr(), (1 + S) * row, row, masks.data_ptr() + 4 * j0, S, sm_scale,
-                                                 og.data_ptr(), 0, st.cuda_stream)
-                    continue
-                if W:                                 # a sliding-window layer: the same launch, the stored positions masked per row by its depth
-                    self.lib.attend_kv_spec_window(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, lengths, depths.data_ptr() + 4 * j0, W,
-                                                   kh.data_ptr(), vh.data_ptr(), (1 + S) * row, row, masks.data_ptr() + 4 * j0, S, sm_scale,
-                                                   og.data_ptr(), 0, st.cuda_stream)
-                    continue
-                self.lib.attend_kv_spec(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, kh.data_ptr(), vh.data_ptr(), (1 + S) * row, row,
-                                        masks.data_ptr() + 4 * j0, S, sm_scale, og.data_ptr(), 0, st.cuda_stream)
+                    self.lib.attend_kv_spec_wide(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, lengths, d_depth, W, *held_args)
+                elif W:                               # a sliding-window layer: the same launch, the stored positions masked per row by its depth
+                    self.lib.attend_kv_spec_window(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, lengths, d_depth, W, *held_args)
+                else:
+                    self.lib.attend_kv_spec(k_handles, v_handles, layer, qg.data_ptr(), g, R, pos_end, *held_args)
             with torch.cuda.stream(st):
-                for j0, n, g, qg, og in parts:
-                    out[:, j0:j0 + n] = og.view(B, H, n, R, D).permute(0, 2, 1, 3, 4)
+                for j0, n, qg, og in parts:
+                    self.scatter_rows(out, og, j0, n)
         return out
+
+    def _spec_handles(self, req_ids, reqs):
+        import numpy as np
+        return np.asarray([r.k_handle for r in reqs], dtype=np.uint64), np.asarray([r.v_handle for r in reqs], dtype=np.uint64)
 
     # ------------------------------------------------------------------ a prefix shared by several requests
     # (the bodies are SharedPrefixSteps': this connector's side of them, then the two methods)

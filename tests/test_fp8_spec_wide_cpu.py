@@ -31,3 +31,16 @@ def test_the_rows_per_pass_argument(monkeypatch, window):
         assert trailing[:3] == today[:2] + [today[6]] and trailing[3][:5] + trailing[3][11:13] == ("attend_fold_masked", 4, 0, H, 8, PTR, 5)
     one, = _calls(torch, "fp8", st, *_step(torch, 4, 4, 8), 1, rows_per_pass=32, **how)          # S = 4: one wide group and nothing else
     assert one[:6] == ("attend_spec_wide", [0, 0, 0, 0], 1, PTR, 32, 8) and one[9] == window
+    # a tree with a ragged n_new: the calls of the chain (the tree and the live counts travel in the mask words alone)
+    step16 = lambda name, layer: (name, [0, 0, 0, 0], layer, PTR, 8, 8, POS_END, LENGTHS, PTR, 33, PTR, PTR, 6 * H * D, H * D, PTR, 5, 0.125, PTR, 0, 7)
+    plan = [("attend_plan_bytes", 4), ("attend_batch_plan", [0, 0, 0, 0], POS_END, T, 0, 0, 7)]
+    assert _calls(torch, "fp8", st, *step, 1, rows_per_pass=32, parents=[-1, 0, 1, 0, 3], n_new=[5, 0, 2, 4], **how) == [wide] + (
+        [step16("attend_spec_window", 1)] if window else
+        plan + [("attend_planned", 4, 0, 4, 1, PTR, 8, T, 0.125, PTR, PTR, 7),
+                ("attend_fold_masked", 4, 0, H, 8, 8, PTR, PTR, PTR, 6 * H * D, H * D, PTR, 5, 0.125, PTR, PTR, 7)])
+    # attend_spec_layers over layers 1 and 2: the wide group layer by layer, then the trailing group -- layer by layer under a window, ONE
+    # planned call and ONE fold over both layers on a global layer
+    assert _calls(torch, "fp8", st, *step, 1, n_layers=2, rows_per_pass=32, **how) == [wide, wide[:2] + (2,) + wide[3:]] + (
+        [step16("attend_spec_window", 1), step16("attend_spec_window", 2)] if window else
+        plan + [("attend_planned_layers", 4, 0, 4, 1, 2, PTR, 8, T, 0.125, PTR, PTR, 7),
+                ("attend_fold_masked", 8, 0, H, 8, 8, PTR, PTR, PTR, 6 * H * D, H * D, PTR, 5, 0.125, PTR, PTR, 7)])

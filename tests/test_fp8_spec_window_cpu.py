@@ -18,7 +18,7 @@ class _Recording:                  # every library call by name and arguments, t
         return lambda *a: (self.__dict__.setdefault("calls", []).append((name,) + tuple(plain(x) for x in a)), 0)[1]
 
 
-def _calls(torch, scheme, st, q, k_new, v_new, layer, lengths=(0, 1, 37, 36), **how):
+def _calls(torch, scheme, st, q, k_new, v_new, layer, lengths=(0, 1, 37, 36), n_layers=None, **how):
     conn = SpeckvKVConnector(_Recording(), L, H, D, T, scheme)
     for b, n in enumerate(lengths):
         conn.add_request(10 + b)
@@ -26,7 +26,10 @@ def _calls(torch, scheme, st, q, k_new, v_new, layer, lengths=(0, 1, 37, 36), **
         if n & 1:
             conn.requests[10 + b].set_tail(torch.randn((L, H, D)).to(torch.float16), torch.randn((L, H, D)).to(torch.float16))
     del conn.lib.calls[:]
-    conn.attend_spec(layer, [10 + b for b in range(len(lengths))], q, k_new, v_new, 0.125, stream=st, **how)
+    if n_layers is None:
+        conn.attend_spec(layer, [10 + b for b in range(len(lengths))], q, k_new, v_new, 0.125, stream=st, **how)
+    else:                                                        # attend_spec_layers from `layer` on, the same query rows on every layer
+        conn.attend_spec_layers(layer, n_layers, [10 + b for b in range(len(lengths))], torch.stack([q] * n_layers), k_new, v_new, 0.125, stream=st, **how)
     return conn.lib.calls
 
 
@@ -44,6 +47,10 @@ def test_the_window_argument(monkeypatch):
         assert _calls(torch, "fp8", st, *step, 1, **how) == today, how
     (name, handles, layer, _, g, R, pos_end, lengths, _, window, *rest), = _calls(torch, "fp8", st, *step, 1, window=33)
     assert (name, layer, g, R, pos_end, lengths, window) == ("attend_spec_window", 1, 16, 4, [0, 0, 36, 36], [0, 1, 37, 36], 33)
+    # attend_spec_layers over layers 1 and 2: one call per layer and nothing else
+    assert _calls(torch, "fp8", st, *step, 1, n_layers=2, window=33) == [
+        ("attend_spec_window", [0, 0, 0, 0], layer, PTR, 16, 4, [0, 0, 36, 36], [0, 1, 37, 36], PTR, 33, PTR, PTR, 5 * H * D, H * D, PTR, 4, 0.125, PTR, 0, 7)
+        for layer in (1, 2)]
 
 
 @pytest.mark.parametrize("length,window", [(97, 33), (61, 33), (200, 100)])

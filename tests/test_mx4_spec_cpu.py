@@ -26,3 +26,7 @@ def test_the_row_block_argument(monkeypatch):
         ("attend_spec_mx4", [0, 0, 0, 0], 1, PTR, 16, 8, [0, 0, 36, 36], PTR, PTR, 4 * H * D, H * D, PTR, 3, 0.125, PTR, 0, 7),
         ("attend_spec_mx4", [0, 0, 0, 0], 1, PTR, 8, 8, [0, 0, 36, 36], PTR, PTR, 4 * H * D, H * D, PTR, 3, 0.125, PTR, 0, 7)]
     assert [c[:3] for c in _calls(torch, "mxfp4", st, *step, 2, parents=[-1, 0, 0], n_new=[3, 0, 2, 1], row_block=16)] == [("attend_spec_mx4", [0, 0, 0, 0], 2)] * 2
+    # attend_spec_layers over layers 1 and 2: every group layer by layer
+    assert _calls(torch, "mxfp4", st, *step, 1, n_layers=2, row_block=16) == [
+        ("attend_spec_mx4", [0, 0, 0, 0], layer, PTR, g, 8, [0, 0, 36, 36], PTR, PTR, 4 * H * D, H * D, PTR, 3, 0.125, PTR, 0, 7)
+        for g in (16, 8) for layer in (1, 2)]
